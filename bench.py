@@ -11,12 +11,14 @@ linked (none can be built here), so gate evaluation / transcript / witness gener
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W               (a pre-set WORLD_SIZE is honoured: no second launcher)
   python bench.py --gpus N --single-process ...            (ONE process drives N devices: h2mi_init_devices(N))
+  python bench.py ... --full                               (also every auxiliary measurement and check, after the timed steps)
+  python bench.py ... --dump-outputs DIR                   (the last timed step's results as DIR/<name>.npy, see dump_outputs)
 
 N > 1: one process per GPU; the total work is fixed ("strong" scaling): every rank owns a contiguous
 1/N slice of both base sets, runs each MSM on its slice and the 96-byte partial points are combined at every
 transcript join (five per StandardPlonk proof) by an RCCL all-gather + device fold, all in HBM; every NTT runs on one GPU (by design): a transform whose output feeds a later
 commitment is replayed by every rank, the others are spread round-robin over the ranks.
-Rank 0 prints ONE JSON line (the contract's fields plus `roofline`, `issue_roofline`, `cpu_baseline`).
+Rank 0 prints ONE JSON line: the contract's fields, and with --full also `roofline`, `issue_roofline`, `cpu_baseline` and the rest.
 """
 import argparse
 import json
@@ -88,11 +90,21 @@ def main(argv=None):
                     help="N > 1: ONE process drives the N devices (h2mi_init_devices(N): what the reference's single create_proof call "
                          "is) instead of one process per GPU over RCCL — the other deployment of the same slice partition")
     ap.add_argument("--no-msm-only", action="store_true", help="N > 1: skip the MSM-only speed-up measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every auxiliary measurement and check: per-kernel device times, the k_msm_accum and NTT "
+                         "rooflines, the MSM-only timing, the data-true create_proof() legs, the CPU baseline and its in-run parity check "
+                         "(the --no-* options above select among them); a plain run times the replay steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64), see dump_outputs()")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and not args.single_process and "WORLD_SIZE" not in os.environ:
         # plain launch: become the launcher BEFORE torch / the library / any HIP call exists in this process
+        if args.dump_outputs:  # the ranks start in the repository root: hand them the directory this caller meant
+            argv = argv + ["--dump-outputs", os.path.abspath(args.dump_outputs)]
         raise SystemExit(spawn_ranks(args.gpus, argv))
 
     import torch  # first: the HIP runtime torch loads is the one libh2mi.so then shares
@@ -185,9 +197,10 @@ def main(argv=None):
         dist.all_reduce(t)
         adds = int(t.item())
 
-    lib.h2mi_profile_reset()
-    lib.h2mi_profile_filter(b"k_msm_accum")
-    lib.h2mi_profile_enable(1)
+    if args.full:  # HIP events around every k_msm_accum launch of the timed steps: the roofline's per-launch time
+        lib.h2mi_profile_reset()
+        lib.h2mi_profile_filter(b"k_msm_accum")
+        lib.h2mi_profile_enable(1)
     sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -200,39 +213,44 @@ def main(argv=None):
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    steps_run = args.warmup + args.steps  # replay steps so far: combines_per_step divides by it
 
-    tot_ms, cnt = C.c_double(), C.c_uint64()
-    lib.h2mi_profile_query(b"k_msm_accum", C.byref(tot_ms), C.byref(cnt))
-    accum_ms = tot_ms.value / max(cnt.value, 1)
+    if args.dump_outputs and rank == 0:  # before anything below reuses the replay's buffers
+        dump_outputs(args.dump_outputs, h2, R, commitments)
 
-    # per-phase device time (untimed extra pass, all kernels bracketed by events)
-    lib.h2mi_profile_reset()
-    lib.h2mi_profile_filter(b"")
-    lib.h2mi_profile_enable(1)
-    R.step()
-    R.finish()
-    lib.h2mi_profile_enable(0)
-    phases = {}
-    for name in ["k_msm_bin_count", "binscan_hipcub", "k_scan_seg", "k_msm_bin_scatter", "k_msm_bin_sort", "k_msm_accum", "k_msm_fold", "k_msm_finish", "k_msm_rowcol", "k_msm_weighted", "k_msm_final",
-                 "k_ntt_pass_col", "k_ntt_pass_row", "k_scale_powers"]:
-        lib.h2mi_profile_query(name.encode(), C.byref(tot_ms), C.byref(cnt))
-        phases[name] = {"ms": round(tot_ms.value, 4), "launches": cnt.value}
-    lib.h2mi_profile_reset()
-    msm_ms = sum(v["ms"] for k, v in phases.items() if k.startswith("k_msm") or k.startswith("binscan") or k == "k_scan_seg")
-    ntt_ms = sum(v["ms"] for k, v in phases.items() if k.startswith("k_ntt") or k.startswith("k_scale"))
+    create_proof_stats = msm_only = None
+    if args.full:
+        tot_ms, cnt = C.c_double(), C.c_uint64()
+        lib.h2mi_profile_query(b"k_msm_accum", C.byref(tot_ms), C.byref(cnt))
+        accum_ms = tot_ms.value / max(cnt.value, 1)
 
-    # ---- the first half of BASELINE's metric: create_proof() wall-clock, data-true (real witness, keygen'd pk,
-    # Blake2b-derived challenges, device permutation products / evaluate_h / openings / SHPLONK).  Host-inclusive:
-    # the transcript and the control flow run on the host between device phases, as they do in the reference.
-    create_proof_stats = None
-    if shape.name == "standard_plonk" and not args.no_create_proof:
-        create_proof_stats = time_create_proof(h2, R, args, dist, backend, torch.device("cuda", local_rank), coll_dev)
+        # per-phase device time (untimed extra pass, all kernels bracketed by events)
+        lib.h2mi_profile_reset()
+        lib.h2mi_profile_filter(b"")
+        lib.h2mi_profile_enable(1)
+        R.step()
+        R.finish()
+        steps_run += 1
+        lib.h2mi_profile_enable(0)
+        phases = {}
+        for name in ["k_msm_bin_count", "binscan_hipcub", "k_scan_seg", "k_msm_bin_scatter", "k_msm_bin_sort", "k_msm_accum", "k_msm_fold", "k_msm_finish", "k_msm_rowcol", "k_msm_weighted", "k_msm_final",
+                     "k_ntt_pass_col", "k_ntt_pass_row", "k_scale_powers"]:
+            lib.h2mi_profile_query(name.encode(), C.byref(tot_ms), C.byref(cnt))
+            phases[name] = {"ms": round(tot_ms.value, 4), "launches": cnt.value}
+        lib.h2mi_profile_reset()
+        msm_ms = sum(v["ms"] for k, v in phases.items() if k.startswith("k_msm") or k.startswith("binscan") or k == "k_scan_seg")
+        ntt_ms = sum(v["ms"] for k, v in phases.items() if k.startswith("k_ntt") or k.startswith("k_scale"))
 
-    # ---- north_star's ">= 6x MSM speed-up at 8 GPUs" is quoted on the MSM alone: the commitments of one proof queued back to
-    # back with ONE join (and one combine), no transforms between them
-    msm_only = None
-    if not args.no_msm_only:
-        msm_only = time_msm_only(h2, R, args, dist, coll_dev, n_devices, torch, sync_all)
+        # ---- the first half of BASELINE's metric: create_proof() wall-clock, data-true (real witness, keygen'd pk,
+        # Blake2b-derived challenges, device permutation products / evaluate_h / openings / SHPLONK).  Host-inclusive:
+        # the transcript and the control flow run on the host between device phases, as they do in the reference.
+        if shape.name == "standard_plonk" and not args.no_create_proof:
+            create_proof_stats = time_create_proof(h2, R, args, dist, backend, torch.device("cuda", local_rank), coll_dev)
+
+        # ---- north_star's ">= 6x MSM speed-up at 8 GPUs" is quoted on the MSM alone: the commitments of one proof queued back to
+        # back with ONE join (and one combine), no transforms between them
+        if not args.no_msm_only:
+            msm_only = time_msm_only(h2, R, args, dist, coll_dev, n_devices, torch, sync_all)
 
     if rank != 0:
         if dist is not None:
@@ -252,53 +270,54 @@ def main(argv=None):
     c, W, nb, nreg = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
     lib.h2mi_bases_info(R.params.g_handle, C.byref(c), C.byref(W), C.byref(nb), C.byref(nreg))
 
-    # 32 B scalar + 64 B affine base per pair, read once; one k_msm_accum launch sees one slice (a rank's, or
-    # in --single-process mode one device's)
-    algo_bytes = 96 * (R.n_local // n_devices)
-    achieved = algo_bytes / (accum_ms * 1e-3) / 1e9 if accum_ms > 0 else 0.0
-    # HBM traffic of the kernel comes from rocprofv3 PMC counters, which cannot be collected from inside this
-    # process: the field carries the figure of the latest committed counter run of this same workload and says so
-    traffic, traffic_source = None, None
-    for tname in ("r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):
-        tpath = os.path.join(ROOT, "profiles", tname)
-        if os.path.exists(tpath) and world == 1 and args.k == 20 and args.shape == "standard_plonk":
-            try:
-                traffic = json.load(open(tpath)).get("k_msm_accum_hbm_bytes_per_launch")
-                traffic_source = f"profiles/{tname} (separate rocprofv3 --pmc run of this command, not measured in this run)"
-                break
-            except Exception:
-                traffic = None
-    roofline = {
-        "kernel": "k_msm_accum",
-        "bound": "hbm",
-        "achieved": round(achieved, 3),
-        "peak": HBM_PEAK_GBS,
-        "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBS, 6),
-        "traffic": traffic,
-        "traffic_source": traffic_source,
-        "algorithmic_bytes_per_launch": algo_bytes,
-        "avg_launch_ms": round(accum_ms, 4),
-        "note": "MSM is 254-bit integer-multiply bound (v_mad_u64_u32), not HBM bound; see DESIGN.md",
-    }
+    if args.full:
+        # 32 B scalar + 64 B affine base per pair, read once; one k_msm_accum launch sees one slice (a rank's, or
+        # in --single-process mode one device's)
+        algo_bytes = 96 * (R.n_local // n_devices)
+        achieved = algo_bytes / (accum_ms * 1e-3) / 1e9 if accum_ms > 0 else 0.0
+        # HBM traffic of the kernel comes from rocprofv3 PMC counters, which cannot be collected from inside this
+        # process: the field carries the figure of the latest committed counter run of this same workload and says so
+        traffic, traffic_source = None, None
+        for tname in ("r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):
+            tpath = os.path.join(ROOT, "profiles", tname)
+            if os.path.exists(tpath) and world == 1 and args.k == 20 and args.shape == "standard_plonk":
+                try:
+                    traffic = json.load(open(tpath)).get("k_msm_accum_hbm_bytes_per_launch")
+                    traffic_source = f"profiles/{tname} (separate rocprofv3 --pmc run of this command, not measured in this run)"
+                    break
+                except Exception:
+                    traffic = None
+        roofline = {
+            "kernel": "k_msm_accum",
+            "bound": "hbm",
+            "achieved": round(achieved, 3),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 6),
+            "traffic": traffic,
+            "traffic_source": traffic_source,
+            "algorithmic_bytes_per_launch": algo_bytes,
+            "avg_launch_ms": round(accum_ms, 4),
+            "note": "MSM is 254-bit integer-multiply bound (v_mad_u64_u32), not HBM bound; see DESIGN.md",
+        }
 
-    # the binding resource, stated next to the (contractual) HBM roofline: 32-bit integer multiply issue.
-    # One mixed addition = 6 multiplications + 2 squarings + one two-product multiplication with a shared reduction (Y3) in
-    # 9 x 29-bit limbs = 6 * 162 + 2 * 126 + 243 = 1467 v_mad_u64_u32 (1548 before round 3's f29_mul2); the peak
-    # is the chip's measured v_mad_u64_u32 rate (tools/ubench.hip: 4.82 cycles per wavefront instruction per
-    # SIMD at 2.4 GHz = 32.6 T lane-multiplies/s).  Other instructions of the loop (masks, shifts, the m = t * p'
-    # products) share the same issue port, so ~0.7 is the practical ceiling of this fraction.
-    MADS_PER_MIXED_ADD, MAD_PEAK = 1467, 32.6e12
-    entries_per_launch = adds_local / max(shape.msm_per_proof, 1)  # bucket insertions (+ reduction adds) per MSM, this rank
-    issue = {
-        "kernel": "k_msm_accum",
-        "bound": "valu (v_mad_u64_u32 issue)",
-        "achieved": round(entries_per_launch * MADS_PER_MIXED_ADD / (accum_ms * 1e-3) / 1e12, 3) if accum_ms else None,
-        "peak": MAD_PEAK / 1e12,
-        "unit": "T mad/s",
-    }
-    if issue["achieved"]:
-        issue["frac"] = round(issue["achieved"] / issue["peak"], 4)
+        # the binding resource, stated next to the (contractual) HBM roofline: 32-bit integer multiply issue.
+        # One mixed addition = 6 multiplications + 2 squarings + one two-product multiplication with a shared reduction (Y3) in
+        # 9 x 29-bit limbs = 6 * 162 + 2 * 126 + 243 = 1467 v_mad_u64_u32 (1548 before round 3's f29_mul2); the peak
+        # is the chip's measured v_mad_u64_u32 rate (tools/ubench.hip: 4.82 cycles per wavefront instruction per
+        # SIMD at 2.4 GHz = 32.6 T lane-multiplies/s).  Other instructions of the loop (masks, shifts, the m = t * p'
+        # products) share the same issue port, so ~0.7 is the practical ceiling of this fraction.
+        MADS_PER_MIXED_ADD, MAD_PEAK = 1467, 32.6e12
+        entries_per_launch = adds_local / max(shape.msm_per_proof, 1)  # bucket insertions (+ reduction adds) per MSM, this rank
+        issue = {
+            "kernel": "k_msm_accum",
+            "bound": "valu (v_mad_u64_u32 issue)",
+            "achieved": round(entries_per_launch * MADS_PER_MIXED_ADD / (accum_ms * 1e-3) / 1e12, 3) if accum_ms else None,
+            "peak": MAD_PEAK / 1e12,
+            "unit": "T mad/s",
+        }
+        if issue["achieved"]:
+            issue["frac"] = round(issue["achieved"] / issue["peak"], 4)
 
     out = {
         "metric": "create_proof() wall-clock + MSM G1-adds/s at k=20 standard_plonk, 1/2/4/8 GPU",
@@ -324,7 +343,7 @@ def main(argv=None):
             "parallelism": (f"msm-slice{world}" if world > 1 else f"single-process msm-slice{n_devices}" if n_devices > 1 else "single-gpu"),
             "deployment": ("one process per GPU (torch.distributed)" if world > 1 else
                            f"one process, {n_devices} devices (h2mi_init_devices)" if n_devices > 1 else "one process, one GPU"),
-            "combines_per_step": (R.combiner.combines // max(args.warmup + args.steps + 1, 1)) if R.combiner is not None else 0,
+            "combines_per_step": (R.combiner.combines // max(steps_run, 1)) if R.combiner is not None else 0,
             "combine": ((("RCCL all-gather + device fold at every transcript join, device-resident" if R.combiner.mode == "rccl" else
                           "RCCL all-gather through host-synchronised copies (H2MI_COMBINE=host) + device fold at every transcript join")
                          if backend == "nccl" else "gloo all-gather (host) + device fold at every transcript join") if R.combiner is not None
@@ -341,15 +360,14 @@ def main(argv=None):
                           if R.spread else "every rank replays every transform"),
         "g1_adds_per_step": adds,
         "msm_pairs_per_s": round(shape.msm_per_proof * n / (ms_per_step * 1e-3), 1),
-        "device_ms_per_step": {"msm": round(msm_ms, 3), "ntt": round(ntt_ms, 3)},
-        "kernels": phases,
-        "roofline": roofline,
-        "issue_roofline": issue,
     }
+    if args.full:
+        out.update({"device_ms_per_step": {"msm": round(msm_ms, 3), "ntt": round(ntt_ms, 3)}, "kernels": phases, "roofline": roofline,
+                    "issue_roofline": issue})
 
     if msm_only is not None:
         out.update(msm_only)
-    if world == 1 and n_devices == 1 and args.k == 20 and shape.name == "standard_plonk":
+    if args.full and world == 1 and n_devices == 1 and args.k == 20 and shape.name == "standard_plonk":
         try:
             out["roofline_ntt"] = time_ntt_roofline(h2)
         except Exception as e:  # never lose the headline line to an auxiliary measurement
@@ -375,7 +393,7 @@ def main(argv=None):
             except Exception as e:  # never lose the headline line to an auxiliary measurement
                 out["halo2_lib_create_proof"] = {"error": repr(e)}
     parity_ok = True
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(R, args, n)
         par = out["cpu_baseline"].pop("parity")
         out["parity_in_run"] = bool(par["msm_commitment_equal"] and par["ntt_limbs_equal"])
@@ -387,6 +405,37 @@ def main(argv=None):
     if not parity_ok:  # a fast kernel whose results differ from the oracle's is not a measurement
         sys.stderr.write("bench.py: parity_in_run is FALSE — the GPU's results differ from the CPU restatement's on the same vectors\n")
         sys.exit(3)
+
+
+def dump_outputs(out_dir, h2, R, commitments, samples=4096):
+    """--dump-outputs: what the last timed step computed, so that two builds can be compared output for output.  Every array is
+    float64 holding 32-bit words (exact), little-endian word order within an element:
+      commitments.npy      the proof's commitments in affine form (G1::batch_normalize: x, y), (msm_per_proof, 2, 8)
+    and, when this rank ran every transform (one GPU, or --replicate-all-ntts), the same `samples` element positions (fixed seed) of
+      coeff_forms.npy      lagrange_to_coeff outputs, one row per column, (columns, samples, 8)
+      extended_forms.npy   coeff_to_extended outputs, (columns, samples, 8)
+      quotient_coeffs.npy  h(X) after extended_to_coeff, (1, samples, 8)
+    field elements as the library holds them (Montgomery limbs).  A few MB in all.  A directory this creates ignores itself in git."""
+    import numpy as np
+
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:
+            f.write("*\n")
+    aff = np.zeros((len(commitments), 8), dtype=np.uint64)
+    h2._lib.check(h2.lib.h2mi_g1_batch_normalize(np.ascontiguousarray(commitments).ctypes.data, len(commitments), aff.ctypes.data), "normalize")
+    arrays = {"commitments": aff.view(np.uint32).reshape(len(commitments), 2, 8)}
+    if not R.spread:
+        def sample(bufs, length):
+            idx = np.sort(np.random.default_rng(0x44554D50).choice(length, size=min(samples, length), replace=False))
+            return np.stack([b.to_numpy(shape=(length, 4))[idx] for b in bufs]).view(np.uint32)
+
+        ext = R.domain.extended_len()
+        arrays["coeff_forms"] = sample(R.work, R.n)
+        arrays["extended_forms"] = sample(R.ext, ext)
+        arrays["quotient_coeffs"] = sample([R.h], ext)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
 
 
 def time_msm_only(h2, R, args, dist, coll_dev, n_devices, torch, sync_all):

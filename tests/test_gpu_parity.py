@@ -998,7 +998,7 @@ def test_bench_world2_rehearsal_matches_single_gpu(gpu):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["bench.py", "--k", "13", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["bench.py", "--k", "13", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r1 = subprocess.run([sys.executable] + common, cwd=root, capture_output=True, text=True, timeout=600, env=env)
     assert r1.returncode == 0, r1.stderr[-2000:]
@@ -1058,6 +1058,48 @@ def test_bench_world2_rehearsal_matches_single_gpu(gpu):
     assert rccl["commitments_sha256"] == one["commitments_sha256"] and rccl["n_gpus"] == 1
     assert rccl["config"]["combines_per_step"] == 5 and "device-resident" in rccl["config"]["combine"]
     assert rccl["create_proof"]["last_proof_sha256"] == one["create_proof"]["last_proof_sha256"]
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """a plain bench.py run prints the headline only (the auxiliary legs run under --full); --dump-outputs writes the last timed
+    step's results as float64 arrays that are the same for any --steps and with or without --full, and whose commitments are the
+    points the line's digest hashes."""
+    import hashlib
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = [sys.executable, "bench.py", "--k", "13", "--warmup", "1"]
+
+    def run(steps, out, *extra):
+        r = subprocess.run(common + ["--steps", str(steps), "--dump-outputs", str(out)] + list(extra), cwd=root, capture_output=True,
+                           text=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="1"))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        dumped = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out)) if f.endswith(".npy")}
+        return json.loads(lines[0]), dumped
+
+    plain, d1 = run(2, tmp_path / "a")
+    _, d2 = run(3, tmp_path / "b")
+    full, d3 = run(2, tmp_path / "c", "--full", "--no-cpu-baseline")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain and key in full
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["higher_is_better"] is True
+    for key in ("roofline", "issue_roofline", "kernels", "msm_only_ms", "create_proof", "cpu_baseline", "parity_in_run"):
+        assert key not in plain
+    for key in ("roofline", "issue_roofline", "kernels", "msm_only_ms", "create_proof"):
+        assert key in full
+    assert plain["commitments_sha256"] == full["commitments_sha256"] and plain["g1_adds_per_step"] == full["g1_adds_per_step"]
+    assert sorted(d1) == ["coeff_forms", "commitments", "extended_forms", "quotient_coeffs"]
+    assert sum(a.nbytes for a in d1.values()) < 64 << 20
+    for name, a in d1.items():
+        assert a.dtype == np.float64 and np.array_equal(a, d2[name]) and np.array_equal(a, d3[name]), name
+        assert np.all((a >= 0) & (a < 2.0 ** 32) & (a == np.floor(a))), name  # exact 32-bit words
+    assert d1["commitments"].shape == (11, 2, 8) and d1["coeff_forms"].shape == (6, 4096, 8)
+    words = d1["commitments"].astype(np.uint32)
+    assert hashlib.sha256(words.tobytes()).hexdigest() == plain["commitments_sha256"]  # the affine points the line hashes
+    assert np.any(d1["extended_forms"] != 0) and np.any(d1["quotient_coeffs"] != 0)
 
 
 def test_eip196_vectors_hip_path(gpu, hooks):

@@ -330,6 +330,13 @@ def test_bench_honours_a_preset_world_size_and_rejects_mismatch():
     assert r.returncode != 0 and "WORLD_SIZE=4 but --gpus 2" in r.stderr and "starting" not in r.stderr
 
 
+def test_bench_refuses_zero_timed_steps_before_any_gpu_call():
+    """--steps is the number of timed steps the line's ms_per_step divides by: fewer than one is refused up front."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "0"], capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and r.stdout.strip() == ""
+
+
 def test_cpp_host_single_element_inversion_matches_pow():
     """include/h2mi.hpp detail::inv_mod_odd (division steps in batches of 62: what fr::invert / fq::invert of the C++ host use on the
     transcript's critical path) against Python's pow(x, -1, p), edge values and random ones, both fields, plain and Montgomery forms."""

@@ -8,7 +8,7 @@ export H2MI_LIBRARY="$PWD/halo2-scaffold_amd/libh2mi_ab.so"
 [ -f "$H2MI_LIBRARY" ] || { echo "build it first: make -C halo2-scaffold_amd/csrc ab" >&2; exit 2; }
 for r in $(seq "$REP"); do
   for v in $VALS; do
-    env "$VAR=$v" python3 bench.py --no-cpu-baseline --no-create-proof --no-msm-only "$@" 2>/dev/null | tail -1 | python3 -c "
+    env "$VAR=$v" python3 bench.py --full --no-cpu-baseline --no-create-proof --no-msm-only "$@" 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 s=sys.stdin.read(); d=json.loads(s[s.index('{'):])
 print('$VAR=$v', d['ms_per_step'], d['roofline']['avg_launch_ms'], d['issue_roofline']['frac'])"

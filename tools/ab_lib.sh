@@ -21,7 +21,7 @@ cp "$NEW" "$TMP/new/libh2mi.so"
 make -C examples -s
 py() { H2MI_LIBRARY="$TMP/$V/libh2mi.so" python3 "$@" 2>/dev/null; }
 cx() { LD_LIBRARY_PATH="$TMP/$V:${LD_LIBRARY_PATH:-}" "$@"; }
-step() { py bench.py --no-cpu-baseline --no-create-proof --no-msm-only | tail -1 | python3 -c "
+step() { py bench.py --full --no-cpu-baseline --no-create-proof --no-msm-only | tail -1 | python3 -c "
 import json,sys
 s=sys.stdin.read(); d=json.loads(s[s.index('{'):])
 print('step', d['ms_per_step'], d['roofline']['avg_launch_ms'], d['issue_roofline']['frac'])"; }

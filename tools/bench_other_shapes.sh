@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || true
 OUT=gpurun_out/other_shapes.jsonl
 : > $OUT
-B="python3 bench.py --no-cpu-baseline --no-create-proof --steps 5 --warmup 2"
+B="python3 bench.py --full --no-cpu-baseline --no-create-proof --steps 5 --warmup 2"
 $B --dist witness 2>/dev/null | tail -1 >> $OUT
 $B --shape halo2_lib_gate 2>/dev/null | tail -1 >> $OUT
 $B --shape range_lookup --k 22 2>/dev/null | tail -1 >> $OUT

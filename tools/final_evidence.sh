@@ -9,9 +9,9 @@ OUT=gpurun_out/ev_$TAG
 mkdir -p $OUT
 make -C examples -s
 if [ "$PART" = all ] || [ "$PART" = 1 ]; then
-echo "== bench"; python3 bench.py --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.err
+echo "== bench"; python3 bench.py --steps 10 --warmup 3 --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.err
 echo "== profiles"; bash tools/collect_profiles.sh $TAG > $OUT/collect.log 2>&1; tail -3 $OUT/collect.log
-echo "== with provers"; rocprofv3 --kernel-trace --stats -d $OUT/provers -o t --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_provers.json 2> $OUT/provers.err
+echo "== with provers"; rocprofv3 --kernel-trace --stats -d $OUT/provers -o t --output-format csv -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/bench_provers.json 2> $OUT/provers.err
 cp $(find $OUT/provers -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_with_provers.csv 2>/dev/null; rm -rf $OUT/provers
 echo "== op_bench"; python3 tools/op_bench.py > $OUT/op_bench.json 2> $OUT/op_bench.err
 fi

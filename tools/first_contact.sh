@@ -23,11 +23,11 @@ for N in 2 4 8; do
     echo "== one process per GPU, N = $N, H2MI_COMBINE=$MODE" | tee -a "$OUT/summary.txt"
     PORT=$((PORT + 1))
     H2MI_COMBINE=$MODE timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "$PORT" \
-      bench.py --gpus "$N" --steps 10 --warmup 3 > "$OUT/bench_ranks_${N}_${MODE}.json" 2> "$OUT/bench_ranks_${N}_${MODE}.err" \
+      bench.py --gpus "$N" --steps 10 --warmup 3 --full > "$OUT/bench_ranks_${N}_${MODE}.json" 2> "$OUT/bench_ranks_${N}_${MODE}.err" \
       || echo "   FAILED (rc $?): see $OUT/bench_ranks_${N}_${MODE}.err" | tee -a "$OUT/summary.txt"
   done
   echo "== one process, $N devices" | tee -a "$OUT/summary.txt"
-  timeout -k 10 900 python3 bench.py --gpus "$N" --single-process --steps 10 --warmup 3 > "$OUT/bench_single_${N}.json" 2> "$OUT/bench_single_${N}.err" \
+  timeout -k 10 900 python3 bench.py --gpus "$N" --single-process --steps 10 --warmup 3 --full > "$OUT/bench_single_${N}.json" 2> "$OUT/bench_single_${N}.err" \
     || echo "   FAILED (rc $?): see $OUT/bench_single_${N}.err" | tee -a "$OUT/summary.txt"
 done
 echo "== a many-column halo2-lib proof over the sliced SRS (24 range checks at DEGREE 7: 11 + 4 columns, up to 15 partial points per phase), N = 2 over RCCL" | tee -a "$OUT/summary.txt"

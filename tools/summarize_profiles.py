@@ -38,7 +38,7 @@ f_stream = known_stream / cal["calib_stream16"][0]
 fetch = per_kernel(f"{src}/fetch/f_counter_collection.csv", "FETCH_SIZE")
 write = per_kernel(f"{src}/write/w_counter_collection.csv", "WRITE_SIZE")
 out = {
-    "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `bench.py --steps 3 --warmup 1`, {tag}",
+    "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-create-proof --no-msm-only`, {tag}",
     "fetch_bytes_per_count": {"gather64_pattern": f_gather, "stream16_pattern": f_stream,
                               "note": "bytes per FETCH_SIZE count from tools/hbm_calib (known byte counts); "
                                       "stream16 is the guide's wide-coalesced case (expect 2048 = 2 x 1024)"},
@@ -87,7 +87,7 @@ if tr:
         alone = [d for d in replay if d <= 1.3 * med]
         bench_line = json.loads(open(f"{src}/bench_trace.json").read().strip().splitlines()[-1])
         acc = {
-            "source": f"rocprofv3 --kernel-trace over `bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-create-proof --no-msm-only`, {tag}: every k_msm_accum launch",
+            "source": f"rocprofv3 --kernel-trace over `bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-create-proof --no-msm-only`, {tag}: every k_msm_accum launch",
             "replay_dense_launches": {"count": len(replay), "avg_ns": round(sum(replay) / len(replay)), "min_ns": min(replay), "max_ns": max(replay)},
             "of_which_not_sharing_the_chip_with_transforms": {"count": len(alone), "avg_ns": round(sum(alone) / len(alone)),
                                                               "what": "launches within 30 % of the median: the accumulation alone on the SIMDs"},
