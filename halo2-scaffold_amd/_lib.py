@@ -6,8 +6,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def lib_path() -> str:
-    """the product library next to this file; H2MI_LIBRARY=<path> selects another build of the same sources (the -DH2MI_AB
-    build `make -C csrc ab` makes for the sweep tools: the product never needs it)"""
+    """the product library next to this file; H2MI_LIBRARY=<path> selects another product build (tools/ab_lib.sh and
+    tools/ab_host.sh compare two builds that way)"""
     return os.environ.get("H2MI_LIBRARY") or os.path.join(_HERE, "libh2mi.so")
 
 

@@ -89,7 +89,7 @@ H2_HD void xyzz29_madd(xyzz29& acc, const f29& x2, const f29& y2) {
   acc.zzz = f29_mul<F>(acc.zzz, ppp);
 }
 
-// ---- batched-affine pair addition (round 5 experiment: see "pair-affine accumulation" in h2mi_msm.hip) ------------------------------
+// ---- batched-affine pair addition (round 5 experiment; the accumulation built on it measured slower: HISTORY.md) --------------------
 // Two table points of one bucket are added in AFFINE coordinates, the inversion of x2 - x1 shared by every pair of the launch
 // (Montgomery's trick, hierarchically): 5 multiplications + 1 squaring per pair instead of a second mixed addition (8M + 2S).
 // d = x2 - x1 + 2p for canonical x's: normalized, 0 < value < 3p, nonzero modulo p whenever x1 != x2

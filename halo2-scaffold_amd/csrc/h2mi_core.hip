@@ -335,7 +335,7 @@ int h2mi_memcpy_d2h(void* dst, const void* d_src, size_t bytes) {
   // library's: a copy to pageable memory goes through the runtime's own staging and a second wait
   constexpr size_t PINNED_BYTES = 4096;
   static thread_local void* pinned = nullptr;  // per calling thread: two threads may read back at once
-  if (bytes <= PINNED_BYTES && !ab_env("H2MI_NO_PINNED_READBACK")) {
+  if (bytes <= PINNED_BYTES) {
     if (!pinned && hipHostMalloc(&pinned, PINNED_BYTES, hipHostMallocPortable) != hipSuccess) pinned = nullptr;
     if (pinned) {
       H2_HIP(hipMemcpyAsync(pinned, d_src, bytes, hipMemcpyDeviceToHost, primary_stream()));

@@ -102,9 +102,6 @@ struct Slot {
   uint32_t* scnt = nullptr;
   bool small_deferred = false;  // the deferred work of this slot is the small path's accumulate + final pair
   uint32_t small_n = 0;         // points of that MSM
-  // pair-affine accumulation (H2MI_MSM_PA, used by the -DH2MI_AB library only): products before each pair [PA_MAX_PAIRS][9][pa_T], chunk totals [9][pa_T]
-  uint32_t *pa_spill = nullptr, *pa_tot = nullptr;
-  uint32_t pa_T = 0;
 };
 // slots per handle = MSMs that can be in flight between two joins before a flush is forced
 // Eight for base sets up to 2^17 (round 3): with four, every fifth back-to-back MSM waited for the reduction batch of the four
@@ -340,7 +337,6 @@ __device__ __forceinline__ fe msm_scalar(const fe* scalars, size_t i, size_t n, 
 template <uint32_t CT>
 __device__ __forceinline__ void msm_bin_count_body(const fe* scalars, size_t n, const fe* shift, uint32_t c, uint32_t W, uint32_t lb, uint32_t nbins,
                                                    uint32_t ntiles, uint32_t* cnt_out, uint32_t* tile_live) {
-  H2_AB_PRIO();
   __shared__ uint32_t cnt[NBINS_MAX];
   __shared__ uint32_t any_live;
   const uint32_t tid = threadIdx.x;
@@ -374,7 +370,6 @@ template <uint32_t CT>
 __device__ __forceinline__ void msm_bin_scatter_body(const fe* scalars, size_t n, const fe* shift, size_t n_reg, uint32_t c, uint32_t W, uint32_t lb,
                                                      uint32_t nbins, uint32_t ntiles, const uint32_t* base, uint32_t* vals_out, void* keys_out_,
                                                      const uint32_t* tile_live) {
-  H2_AB_PRIO();
   constexpr bool WIDE = CT >= WIDE_MIN_C;  // in-bin keys of up to 10 bits: staged and written as 16-bit values
   if (!tile_live[blockIdx.x]) return;  // no non-zero scalar in this tile (k_msm_bin_count): block-uniform, before any barrier
   __shared__ uint32_t cnt[NBINS_MAX], lstart[NBINS_MAX + 1], wsum[NBINS_MAX / 64];
@@ -485,7 +480,6 @@ constexpr uint32_t NQ_MAX = 128;  // buckets per bin (c = 17: 2^16 buckets in 51
 __device__ __forceinline__ void msm_bin_sort_body(const uint8_t* keys_in, const uint32_t* vals_in, const uint32_t* base, uint32_t ntiles, uint32_t nbins,
                                                   uint32_t lb, uint32_t s0_fixed, uint32_t nb, uint32_t* vals_out, uint32_t* off, uint32_t* np0,
                                                   uint32_t* np1, uint32_t* s0_out) {
-  H2_AB_PRIO();
   __shared__ uint32_t wh[P2_THREADS / 64][NQ_MAX];
   __shared__ uint32_t run[NQ_MAX], ccnt[NQ_MAX], cstart[NQ_MAX], carry64;
   __shared__ uint32_t stage[P2_CH];
@@ -787,205 +781,13 @@ __global__ void __launch_bounds__(256) k_msm_accum(const uint32_t* entries, cons
   msm_accum_body(entries, off, toff, nb, s0_dev, table, part);
 }
 
-// ---- pair-affine accumulation (round 5 experiment; selected with H2MI_MSM_PA in the -DH2MI_AB library only) ------------------------
-// The accumulation spends 1467 multiply-adds per entry on a mixed XYZZ addition.  Two table points of the same bucket can instead be
-// added in AFFINE coordinates first — 5 multiplications and a squaring (936 multiply-adds) once the inverse of x2 - x1 is known — and
-// only their sum enters the accumulator: 2403 instead of 2934 multiply-adds per pair (-18 %).  The inverses are shared by EVERY pair of
-// the launch (Montgomery's trick in two levels), which takes three kernels:
-//   k_msm_pa_forward   per chunk (the accumulation's chunks): running product of the pairs' x2 - x1, the product BEFORE each pair
-//                      spilled (36 B per pair, lane-contiguous), the chunk's total written out.  Gathers every table point's x.
-//   k_msm_pa_invert    the inverses of the chunk totals: per workgroup 1024 totals, prefix / suffix products, ONE division-step inversion
-//   k_msm_pa_backward  the accumulation itself, walking its chunk BACKWARDS (the order in which Montgomery's trick releases the
-//                      inverses): pair sum in affine coordinates, then one mixed addition; same partial sums, same layout as
-//                      k_msm_accum (partials are numbered in array order, so walking down decrements the index)
-// Pairs are (start + 2j, start + 2j + 1) of a chunk; a pair that straddles a bucket boundary, holds an identity or two points with
-// the same x (P + P, P - P) is not combined: both kernels decide that from the same data and the backward pass adds such entries one
-// by one, exactly as k_msm_accum does.
-// Price: every table point is gathered twice and 72 B per pair are spilled and read back — 2.6 GB instead of 0.9 GB per 2^20 MSM.
-// MEASURED (profiles/r05_pair_affine_ab.txt, tools/pa_ab.py): a loss everywhere.  2^20: forward 0.46 ms + inversions 0.09 ms, and the
-// backward pass itself takes 1.31 ms against k_msm_accum's 1.11 ms although it issues 18 % fewer multiply-adds — two gathers and a
-// spill read per pair at 256 VGPRs leave the latency uncovered; back to back 1.76 against 1.27 ms per MSM, alone 2.34 against 1.62.
-// Kept in the A/B library (make ab) as the measured form of the estimate in HISTORY.md; the product does not contain it.
-#ifdef H2MI_AB
-constexpr uint32_t PA_MAX_PAIRS = S0_MAX / 2;
-__device__ __forceinline__ bool words_equal8(const uint32_t* a, const uint32_t* b) {
-  uint32_t d = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) d |= a[i] ^ b[i];
-  return d == 0;
-}
-__device__ __forceinline__ bool words_zero8(const uint32_t* a) {
-  uint32_t d = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) d |= a[i];
-  return d == 0;
-}
-// can the two table points be added by the affine formula?  (decided identically by the forward and the backward pass)
-__device__ __forceinline__ bool pa_pair_ok(const tab_entry& p0, const tab_entry& p1) {
-  return !words_zero8(p0.x.v) && !words_zero8(p1.x.v) && !words_equal8(p0.x.v, p1.x.v);
-}
-__device__ __forceinline__ void pa_store(uint32_t* base, uint32_t T, uint32_t t, const f29& a) {
-#pragma unroll
-  for (int i = 0; i < 9; i++) base[(size_t)i * T + t] = a.v[i];
-}
-__device__ __forceinline__ f29 pa_load(const uint32_t* base, uint32_t T, uint32_t t) {
-  f29 r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.v[i] = base[(size_t)i * T + t];
-  return r;
-}
-__global__ void __launch_bounds__(256) k_msm_pa_forward(const uint32_t* entries, const uint32_t* off, uint32_t nb, const uint32_t* s0_dev,
-                                                         const uint8_t* table, uint32_t T, uint32_t* spill, uint32_t* tot) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= T) return;
-  const uint32_t total = off[nb];
-  const uint32_t s0 = *s0_dev;
-  f29 prod = f29_const<Fq29>(Fq29::ONE);
-  if ((uint64_t)t * s0 < total && s0 <= 2 * PA_MAX_PAIRS) {
-    const uint32_t start = t * s0;
-    const uint32_t end = min(start + s0, total);
-    uint32_t b = find_bucket(off, nb, start);
-    uint32_t bend = off[b + 1];
-    tab_entry n0, n1;
-    if (start + 1 < end) {
-      n0 = tab_load(table, entries[start] & 0x7fffffffu);
-      n1 = tab_load(table, entries[start + 1] & 0x7fffffffu);
-    }
-    for (uint32_t k = start, j = 0; k + 1 < end; k += 2, j++) {
-      const tab_entry p0 = n0, p1 = n1;
-      if (k + 3 < end) {  // the next pair's points travel while this pair's product is formed
-        n0 = tab_load(table, entries[k + 2] & 0x7fffffffu);
-        n1 = tab_load(table, entries[k + 3] & 0x7fffffffu);
-      }
-      while (k >= bend) {
-        b++;
-        bend = off[b + 1];
-      }
-      if (k + 1 >= bend || !pa_pair_ok(p0, p1)) continue;
-      pa_store(spill + (size_t)j * 9 * T, T, t, prod);
-      prod = f29_mul<Fq29>(prod, affine29_pair_diff(tab_x(p0), tab_x(p1)));
-    }
-  }
-  pa_store(tot, T, t, prod);
-}
-// tot[t] <- 1 / tot[t] for t < T: 1024 values per workgroup of 256 threads
-__global__ void __launch_bounds__(256) k_msm_pa_invert(uint32_t* tot, uint32_t T) {
-  __shared__ f29 pre[256], suf[256];
-  __shared__ f29 winv;
-  const uint32_t tid = threadIdx.x, base = blockIdx.x * 1024;
-  f29 v[4], q[4];
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const uint32_t idx = base + i * 256 + tid;
-    v[i] = idx < T ? pa_load(tot, T, idx) : f29_const<Fq29>(Fq29::ONE);
-    q[i] = i ? f29_mul<Fq29>(q[i - 1], v[i]) : v[i];
-  }
-  pre[tid] = q[3];
-  suf[tid] = q[3];
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1) {  // inclusive prefix products in pre, inclusive suffix products in suf
-    f29 a, c;
-    if (tid >= d) a = pre[tid - d];
-    if (tid + d < 256) c = suf[tid + d];
-    __syncthreads();
-    if (tid >= d) pre[tid] = f29_mul<Fq29>(pre[tid], a);
-    if (tid + d < 256) suf[tid] = f29_mul<Fq29>(suf[tid], c);
-    __syncthreads();
-  }
-  if (tid < 64) {  // every lane of the first wavefront on the same value: uniform branches.  (W 2^261) read as Montgomery-2^256 is
-                   // (32 W) 2^256; its inverse times 2^10 is W^-1 2^261
-    fe w;
-    f29_pack(f29_reduce_canonical<Fq29>(pre[255]), w.v);
-    fe inv = fe_inv_ds<Fq>(w);
-    for (int i = 0; i < 10; i++) inv = fe_dbl<Fq>(inv);
-    if (tid == 0) winv = f29_unpack(inv.v);
-  }
-  __syncthreads();
-  f29 r = winv;  // -> 1 / q[3] of this thread: the workgroup's inverse times everyone else's totals
-  if (tid) r = f29_mul<Fq29>(r, pre[tid - 1]);
-  if (tid < 255) r = f29_mul<Fq29>(r, suf[tid + 1]);
-#pragma unroll
-  for (int i = 3; i >= 0; i--) {
-    const uint32_t idx = base + i * 256 + tid;
-    const f29 inv_i = i ? f29_mul<Fq29>(r, q[i - 1]) : r;
-    if (i) r = f29_mul<Fq29>(r, v[i]);
-    if (idx < T) pa_store(tot, T, idx, inv_i);
-  }
-}
-__global__ void __launch_bounds__(256) k_msm_pa_backward(const uint32_t* entries, const uint32_t* off, const uint32_t* toff, uint32_t nb,
-                                                          const uint32_t* s0_dev, const uint8_t* table, uint8_t* part, uint32_t T,
-                                                          const uint32_t* spill, const uint32_t* totinv) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t total = off[nb];
-  const uint32_t s0 = *s0_dev;
-  if (t >= T || (uint64_t)t * s0 >= total) return;
-  const uint32_t start = t * s0;
-  const uint32_t end = min(start + s0, total);
-  const bool pairs_on = s0 <= 2 * PA_MAX_PAIRS;  // longer chunks (a chunk override): the forward pass combined nothing
-  uint32_t b = find_bucket(off, nb, end - 1);  // the bucket that holds the chunk's LAST entry
-  uint32_t bstart = off[b];
-  uint32_t pidx = toff[b] + (t - off[b] / s0);
-  xyzz29 acc = xyzz29_identity();
-  f29 run = pa_load(totinv, T, t);
-  // make `idx` (below every entry handled so far) an entry of the current bucket: crossing a boundary closes a partial sum
-  auto cross = [&](uint32_t idx) {
-    if (idx >= bstart) return;
-    part_store(part + (size_t)pidx * PART_BYTES, acc);
-    pidx--;
-    acc = xyzz29_identity();
-    do {
-      b--;
-    } while (off[b] > idx);
-    bstart = off[b];
-  };
-  auto single = [&](const tab_entry& p, uint32_t neg) {
-    if (tab_is_identity(p)) return;
-    f29 y = tab_y(p);
-    if (neg) y = f29_sub(f29_zero(), y, Fq29::K2);
-    xyzz29_madd(acc, tab_x(p), y);
-  };
-  uint32_t hi = end;  // entries [hi, end) are done
-  if ((end - start) & 1u) {
-    const uint32_t e = entries[end - 1];
-    single(tab_load(table, e & 0x7fffffffu), e >> 31);
-    hi = end - 1;
-  }
-  uint32_t e0 = 0, e1 = 0;
-  tab_entry n0, n1;
-  if (hi > start) {
-    e0 = entries[hi - 2];
-    e1 = entries[hi - 1];
-    n0 = tab_load(table, e0 & 0x7fffffffu);
-    n1 = tab_load(table, e1 & 0x7fffffffu);
-  }
-  for (uint32_t k1 = hi; k1 > start; k1 -= 2) {  // the pair (k1 - 2, k1 - 1), j = (k1 - 2 - start) / 2
-    const uint32_t k0 = k1 - 2, j = (k0 - start) >> 1;
-    const tab_entry p0 = n0, p1 = n1;
-    const uint32_t neg0 = e0 >> 31, neg1 = e1 >> 31;
-    if (k0 > start) {
-      e0 = entries[k0 - 2];
-      e1 = entries[k0 - 1];
-      n0 = tab_load(table, e0 & 0x7fffffffu);
-      n1 = tab_load(table, e1 & 0x7fffffffu);
-    }
-    cross(k0 + 1);
-    if (pairs_on && k0 >= bstart && pa_pair_ok(p0, p1)) {
-      const f29 before = pa_load(spill + (size_t)j * 9 * T, T, t);
-      const f29 x0 = tab_x(p0), x1 = tab_x(p1);
-      const f29 dinv = f29_mul<Fq29>(run, before);
-      run = f29_mul<Fq29>(run, affine29_pair_diff(x0, x1));
-      f29 x3, y3;
-      affine29_pair_add(x0, tab_y(p0), neg0 != 0, x1, tab_y(p1), neg1 != 0, dinv, x3, y3);
-      xyzz29_madd(acc, x3, y3);
-    } else {
-      single(p1, neg1);
-      cross(k0);
-      single(p0, neg0);
-    }
-  }
-  part_store(part + (size_t)pidx * PART_BYTES, acc);
-}
-#endif  // H2MI_AB
+// Occupancy cap: the accumulation runs as fast with 2 wavefronts per SIMD as with 4 (it is bound by VALU
+// issue, not latency), but at 4 it owns every VGPR of the chip and the short kernels of the neighbouring
+// MSMs (bucket reduction, partition) cannot start until it drains.  An unused dynamic-LDS reservation of
+// 56000 B holds it at two workgroups per CU and leaves half the registers and 48 KB of LDS per CU free:
+// back-to-back MSMs 2^20: 1.90 -> 1.74 ms.
+constexpr size_t ACCUM_LDS = 56000;  // the dynamic LDS of every k_msm_accum launch
+// batched-affine accumulation was built and measured slower: HISTORY.md
 
 // ---- batched head: the partition and the accumulation of up to HEAD_BATCH MSMs of one length over ONE base set as ONE set of launches
 // (blockIdx.y = MSM; round 4).  At 2^16 rows and below a prover phase's three or four commitments were issued at the HOST's pace: eight
@@ -1557,26 +1359,19 @@ static uint32_t pick_window(size_t n) {
 // cells: 128 lanes, one cell each; beyond: 256 lanes and r = ceil(n W / (256 x 512)) cells each (<= 512 workgroups = two
 // wavefronts per SIMD: a lone wavefront issues a multiply-add every 8 cycles, two share the unit at ~4.8).  The window is the
 // widest whose table 2^(c-1) x W x n x 64 B stays within SMALL_TABLE_BUDGET.  Returns false when the set does not take the path.
-// First guesses by level count, then measured (tools/msm_small_sweep.sh -> profiles/r04_msm_small_sweep.txt).
+// First guesses by level count, then measured (profiles/r04_msm_small_sweep.txt).
 constexpr size_t SMALL_TABLE_BUDGET = (size_t)2 << 30;  // per base set: c = 7 up to 2^13 points (1.2 GB), c = 6 at 2^14 (1.4 GB)
 static bool small_geometry(size_t n, uint32_t* c, uint32_t* lanes, uint32_t* r) {
-  size_t max_n = SMALL_MAX_N;
-  if (const char* ev = ab_env("H2MI_MSM_SMALL_MAX_LOG"))
-    max_n = std::min<size_t>(SMALL_MAX_N, (size_t)1 << std::max(0, atoi(ev)));
-  if (n > max_n) return false;
+  if (n > SMALL_MAX_N) return false;
   if (getenv("H2MI_MSM_C")) return false;  // a forced window width means the general pipeline with that width (forced-path parity tests)
   uint32_t cc = SMALL_C_MAX;
   while (cc > 2 && ((size_t)1 << (cc - 1)) * ((255 + cc - 1) / cc) * n * 64 > SMALL_TABLE_BUDGET) cc--;
-  if (const char* ev = ab_env("H2MI_MSM_SMALL_C"))
-    if (atoi(ev) >= 2 && atoi(ev) <= (int)SMALL_C_MAX) cc = (uint32_t)atoi(ev);
   const size_t cells = n * ((255 + cc - 1) / cc);
   uint32_t ll = SMALL_CELLS, rr = 1;
   if (cells > (size_t)SMALL_CELLS * 256) {
     ll = SMALL_THREADS;
     rr = (uint32_t)((cells + (size_t)SMALL_THREADS * SMALL_PARTS_MAX - 1) / ((size_t)SMALL_THREADS * SMALL_PARTS_MAX));
   }
-  if (const char* ev = ab_env("H2MI_MSM_SMALL_R"))
-    if (atoi(ev) >= (int)rr && atoi(ev) <= 256) rr = (uint32_t)atoi(ev), ll = SMALL_THREADS;
   *c = cc;
   *lanes = ll;
   *r = rr;
@@ -1597,7 +1392,6 @@ static void free_bases(Bases* B) {
     H2_IGNORE(hipFree(S.vals[0])); H2_IGNORE(hipFree(S.vals[1]));
     H2_IGNORE(hipFree(S.bkeys)); H2_IGNORE(hipFree(S.bincnt)); H2_IGNORE(hipFree(S.binbase)); H2_IGNORE(hipFree(S.binseg)); H2_IGNORE(hipFree(S.tile_live));
     H2_IGNORE(hipFree(S.off)); H2_IGNORE(hipFree(S.s0_dev));
-    if (S.pa_spill) { H2_IGNORE(hipFree(S.pa_spill)); H2_IGNORE(hipFree(S.pa_tot)); }
     for (int i = 0; i < 2; i++) { H2_IGNORE(hipFree(S.np[i])); H2_IGNORE(hipFree(S.toff[i])); }
     H2_IGNORE(hipFree(S.dense)); H2_IGNORE(hipFree(S.dense2)); H2_IGNORE(hipFree(S.vsum)); H2_IGNORE(hipFree(S.tseg[0])); H2_IGNORE(hipFree(S.tseg[1]));
     H2_IGNORE(hipFree(S.part[0])); H2_IGNORE(hipFree(S.part[1])); H2_IGNORE(hipFree(S.rc)); H2_IGNORE(hipFree(S.g)); H2_IGNORE(hipFree(S.stats)); H2_IGNORE(hipFree(S.shift));
@@ -1649,8 +1443,6 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
   // 2^(c-1) >= 1024 entries for every window width pick_window() can return
   if ((B->nbins & 3u) || B->nb < 4 || (B->nb > SCAN_SEG_TASKS && !B->seg_log) || B->nbins > NBINS_MAX || (1u << B->lb) > NQW) { free_bases(B); return H2MI_ERANGE; }
   B->nslot = n > ((size_t)1 << 17) ? 4 : NSLOT;
-  if (const char* ev = ab_env("H2MI_MSM_SLOTS"))  // A/B knob
-    if (atoi(ev) >= 2 && atoi(ev) <= NSLOT) B->nslot = atoi(ev);
   for (int si_ = 0; si_ < B->nslot; si_++) {
     Slot& S = B->slot[si_];
     for (int i = 0; i < 2; i++) H2_ALLOC(S.vals[i], nW * 4);
@@ -1744,7 +1536,7 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
   // false), then its own table column.  Small base sets never use the shift (k_msm_pick_shift samples 64 scalars).
   const uint64_t h = g_next_handle++;
   g_bases[h] = B;  // msm_join_all walks the registered handles
-  if (n >= SHIFT_MIN_N && !B->small && !ab_env("H2MI_MSM_NO_SHIFT")) {
+  if (n >= SHIFT_MIN_N && !B->small) {
     fe* ones = nullptr;
     uint8_t* sum = nullptr;
     int rc = H2MI_OK;
@@ -1815,7 +1607,7 @@ static TailDesc tail_desc(const Bases* B, const Slot& S);
 // On a caller-provided stream everything runs in order on that stream.
 static int msm_small(Bases* B, const void* d_scalars, size_t n, void* d_out, hipStream_t s, bool inorder = false);
 static bool take_small(const Bases* B, bool general) {
-  return B->small && !general && !(B->n > SMALL_STREAM_N && B->since_join >= SMALL_STREAM_AFTER && !ab_env("H2MI_MSM_NO_AUTO_STREAM"));
+  return B->small && !general && !(B->n > SMALL_STREAM_N && B->since_join >= SMALL_STREAM_AFTER);
 }
 constexpr size_t HEAD_BATCH_MAX_N = (size_t)1 << 17;  // largest base set whose MSMs are partitioned and accumulated as a batch
 
@@ -1915,8 +1707,7 @@ static int msm_dev_batch(Bases* B, const void* const* d_scalars, size_t m, size_
     slots[j]->head_ever = true;
   }
   if (as != hs) H2_HIP(hipStreamWaitEvent(as, slots[m - 1]->head_done, 0));
-  static const size_t accum_lds = ab_env("H2MI_ACCUM_LDS") ? (size_t)atoi(ab_env("H2MI_ACCUM_LDS")) : 56000;
-  H2_LAUNCH("k_msm_accum", k_msm_accum_b, dim3(ceil_div_u32(chunks0, 256), mm), 256, accum_lds, as, hb, nb, (const uint8_t*)B->table);
+  H2_LAUNCH("k_msm_accum", k_msm_accum_b, dim3(ceil_div_u32(chunks0, 256), mm), 256, ACCUM_LDS, as, hb, nb, (const uint8_t*)B->table);
   for (size_t j = 0; j < m; j++) {
     Slot& S = *slots[j];
     S.d_out = (char*)d_out + 96 * j;
@@ -2142,44 +1933,7 @@ static int msm_dev(Bases* B, const void* d_scalars, size_t n, void* d_out, hipSt
     S.head_pending = true;
     S.head_ever = true;
   }
-  // Occupancy cap: the accumulation runs as fast with 2 wavefronts per SIMD as with 4 (it is bound by VALU
-  // issue, not latency), but at 4 it owns every VGPR of the chip and the short kernels of the neighbouring
-  // MSMs (bucket reduction, partition) cannot start until it drains.  An unused dynamic-LDS reservation of
-  // 56000 B holds it at two workgroups per CU and leaves half the registers and 48 KB of LDS per CU free:
-  // back-to-back MSMs 2^20: 1.90 -> 1.74 ms.  H2MI_ACCUM_LDS=0 removes the cap.
-  static const size_t accum_lds = ab_env("H2MI_ACCUM_LDS") ? (size_t)atoi(ab_env("H2MI_ACCUM_LDS")) : 56000;
-#ifdef H2MI_AB
-  static bool prio_set = false;
-  if (!prio_set && ab_env("H2MI_AB_PRIO")) {
-    const uint32_t one = 1;
-    H2_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_ab_prio), &one, 4));
-  }
-  prio_set = true;
-  // pair-affine accumulation (experiment, -DH2MI_AB library only): from H2MI_MSM_PA_MIN entries (default 2^22)
-  static const bool pa_on = ab_env("H2MI_MSM_PA") != nullptr;
-  static const uint32_t pa_min = ab_env("H2MI_MSM_PA_MIN") ? (uint32_t)atoll(ab_env("H2MI_MSM_PA_MIN")) : (1u << 22);
-  if (pa_on && !s0_fixed && total >= pa_min) {
-    if (S.pa_T < chunks0) {
-      if (S.pa_spill) { H2_HIP(hipFree(S.pa_spill)); H2_HIP(hipFree(S.pa_tot)); S.pa_spill = S.pa_tot = nullptr; S.pa_T = 0; }
-      const uint32_t cap = std::min(accum_rounds((uint32_t)(B->stride * W)) * ACCUM_RESIDENT_CHUNKS, (uint32_t)(B->stride * W));
-      H2_HIP(hipMalloc((void**)&S.pa_spill, (size_t)PA_MAX_PAIRS * 9 * 4 * cap));
-      H2_HIP(hipMalloc((void**)&S.pa_tot, (size_t)9 * 4 * cap));
-      S.pa_T = cap;
-    }
-    // the forward pass and the inversions belong to the head (they run beside the previous MSM's accumulation)
-    H2_LAUNCH("k_msm_pa_forward", k_msm_pa_forward, ceil_div_u32(chunks0, 256), 256, 0, hs, (const uint32_t*)S.vals[1], (const uint32_t*)S.off, nb,
-              (const uint32_t*)S.s0_dev, (const uint8_t*)B->table, chunks0, S.pa_spill, S.pa_tot);
-    H2_LAUNCH("k_msm_pa_invert", k_msm_pa_invert, ceil_div_u32(chunks0, 1024), 256, 0, hs, S.pa_tot, chunks0);
-    if (pipelined) {
-      H2_HIP(hipEventRecord(S.head_done, hs));
-      H2_HIP(hipStreamWaitEvent(as, S.head_done, 0));
-    }
-    H2_LAUNCH("k_msm_accum", k_msm_pa_backward, ceil_div_u32(chunks0, 256), 256, accum_lds, as, (const uint32_t*)S.vals[1], (const uint32_t*)S.off,
-              (const uint32_t*)S.toff[0], nb, (const uint32_t*)S.s0_dev, (const uint8_t*)B->table, S.part[0], chunks0, (const uint32_t*)S.pa_spill,
-              (const uint32_t*)S.pa_tot);
-  } else
-#endif
-  H2_LAUNCH("k_msm_accum", k_msm_accum, ceil_div_u32(chunks0, 256), 256, accum_lds, as, (const uint32_t*)S.vals[1], (const uint32_t*)S.off,
+  H2_LAUNCH("k_msm_accum", k_msm_accum, ceil_div_u32(chunks0, 256), 256, ACCUM_LDS, as, (const uint32_t*)S.vals[1], (const uint32_t*)S.off,
             (const uint32_t*)S.toff[0], nb, (const uint32_t*)S.s0_dev, (const uint8_t*)B->table, S.part[0]);
   S.d_out = d_out;
   S.tasks1 = tasks0 / S1 + nb;
@@ -2190,9 +1944,8 @@ static int msm_dev(Bases* B, const void* d_scalars, size_t n, void* d_out, hipSt
     S.accum_ever = true;
     S.tail_deferred = true;
     g_deferred.push_back({B, &S});
-    static const bool eager = ab_env("H2MI_MSM_EAGER_TAIL") != nullptr;  // A/B: one reduction per MSM, at once
     // half the slots: the reductions of one half run beside the accumulation of the other
-    if (eager || g_deferred.size() >= (size_t)std::max(1, B->nslot / 2)) return flush_tails();
+    if (g_deferred.size() >= (size_t)std::max(1, B->nslot / 2)) return flush_tails();
     return H2MI_OK;
   }
   TailBatch tb;
@@ -2255,8 +2008,7 @@ static int msm_small(Bases* B, const void* d_scalars, size_t n, void* d_out, hip
     S.tail_deferred = true;
     S.small_deferred = true;
     g_deferred.push_back({B, &S});
-    static const bool eager = ab_env("H2MI_MSM_EAGER_TAIL") != nullptr;
-    if (eager || g_deferred.size() >= (size_t)std::max(1, B->nslot / 2)) return flush_tails();
+    if (g_deferred.size() >= (size_t)std::max(1, B->nslot / 2)) return flush_tails();
     return H2MI_OK;
   }
   SmallBatch sb;
@@ -2276,12 +2028,11 @@ static int msm_small(Bases* B, const void* d_scalars, size_t n, void* d_out, hip
 static int launch_tails(const TailBatch& tb, uint32_t count, uint32_t max_tasks1, uint32_t max_nb, uint32_t max_logNh, uint32_t max_logNl,
                         uint32_t max_seg, hipStream_t t) {
   // fold / finish: quads (4 lanes per point operation) while the grid stays latency-bound, single lanes beyond
-  const bool force_lane = ab_env("H2MI_MSM_TAIL_LANES") != nullptr;  // A/B
   bool none_folds = true;
   for (uint32_t j = 0; j < count; j++) none_folds = none_folds && tb.d[j].no_fold != 0;
   if (none_folds) {
     // no fold level at all
-  } else if (!force_lane && (uint64_t)max_tasks1 * count <= 65536) {
+  } else if ((uint64_t)max_tasks1 * count <= 65536) {
     H2_LAUNCH("k_msm_fold", k_msm_fold<true>, dim3(ceil_div_u32((uint64_t)max_tasks1 * 4, 256), count), 256, 0, t, tb);
   } else {
     H2_LAUNCH("k_msm_fold", k_msm_fold<false>, dim3(ceil_div_u32(max_tasks1, 256), count), 256, 0, t, tb);
@@ -2290,7 +2041,7 @@ static int launch_tails(const TailBatch& tb, uint32_t count, uint32_t max_tasks1
   const size_t hot_lds = 64 * PART_BYTES;
   if (max_seg) {
     H2_LAUNCH("k_msm_finish", (k_msm_finish<false, FG_WIDE>), dim3(hot_blocks + ceil_div_u32((uint64_t)max_nb * FG_WIDE, 256), count), 256, hot_lds, t, tb, hot_blocks);
-  } else if (!force_lane && (uint64_t)max_nb * FG_NARROW * count <= 65536) {
+  } else if ((uint64_t)max_nb * FG_NARROW * count <= 65536) {
     H2_LAUNCH("k_msm_finish", (k_msm_finish<true, FG_NARROW>), dim3(hot_blocks + ceil_div_u32((uint64_t)max_nb * FG_NARROW * 4, 256), count), 256, hot_lds, t, tb,
               hot_blocks);
   } else {
@@ -2759,8 +2510,8 @@ static int msm_batch_entry(uint64_t handle, const void* const* d_scalars, size_t
 int h2mi_msm_bn254_g1_phase_dev(uint64_t handle, const void* const* d_scalars, size_t count, size_t n, void* d_out_jacobian, unsigned flags,
                                 h2mi_stream_t stream) {
   if (flags & ~(unsigned)(H2MI_MSM_SPARSE | H2MI_MSM_INORDER | H2MI_MSM_GENERAL)) return H2MI_EINVAL;
-  return msm_batch_entry(handle, d_scalars, count, n, d_out_jacobian, stream, (flags & H2MI_MSM_SPARSE) && !ab_env("H2MI_MSM_IGNORE_SPARSE_HINT"),
-                         (flags & H2MI_MSM_INORDER) && !ab_env("H2MI_MSM_IGNORE_INORDER"), (flags & H2MI_MSM_GENERAL) != 0);
+  return msm_batch_entry(handle, d_scalars, count, n, d_out_jacobian, stream, (flags & H2MI_MSM_SPARSE) != 0, (flags & H2MI_MSM_INORDER) != 0,
+                         (flags & H2MI_MSM_GENERAL) != 0);
 }
 static int msm_batch_entry(uint64_t handle, const void* const* d_scalars, size_t count, size_t n, void* d_out_jacobian, h2mi_stream_t stream, bool sparse,
                            bool inorder, bool general) {
@@ -2772,14 +2523,12 @@ static int msm_batch_entry(uint64_t handle, const void* const* d_scalars, size_t
   auto it = g_bases.find(handle);
   hipStream_t s = pick_stream(stream);
   const bool pipelined = (s == ctx().stream) && ctx().tail_stream && !getenv("H2MI_MSM_NO_PIPELINE");
-  static const bool eager = ab_env("H2MI_MSM_EAGER_TAIL") != nullptr;
   // batched launches: a plain (unsharded) handle on the library stream, narrow windows or the small path, small enough that launch
   // pace and not stage overlap is what the phase waits for; everything else is the loop the caller would have written
   // `sparse` (the caller's promise that the columns are mostly zeros or one repeated value): the kernels of such an MSM are short at
   // EVERY size — a 2^20-row witness column is 25 us of digit counting and a handful of 6-us kernels — so the batch is taken at any size
   if (count == 1 && inorder) return msm_dev_entry(handle, d_scalars[0], n, d_out_jacobian, stream, true, general);
-  if (n != 0 && count > 1 && !ab_env("H2MI_MSM_NO_HEAD_BATCH") && pipelined && !eager && it != g_bases.end() && n <= it->second->n &&
-      (it->second->n <= (ab_env("H2MI_HEAD_BATCH_MAX_LOG") ? (size_t)1 << atoi(ab_env("H2MI_HEAD_BATCH_MAX_LOG")) : HEAD_BATCH_MAX_N) || sparse)) {
+  if (n != 0 && count > 1 && pipelined && it != g_bases.end() && n <= it->second->n && (it->second->n <= HEAD_BATCH_MAX_N || sparse)) {
     Bases* B = it->second;
     if (B->small || B->seg_log == 0) {
       for (size_t j0 = 0; j0 < count;) {
@@ -2844,7 +2593,7 @@ int h2mi_msm_bn254_g1(uint64_t handle, const uint64_t* bases, const uint64_t* sc
   if (!rc && hipMemcpyAsync(d + 96, scalars, n * 32, hipMemcpyHostToDevice, s) != hipSuccess) rc = H2MI_EHIP;
   // best_multiexp returns its point: the call is a lone MSM read back at once, so it runs in order on the library stream (no stream hops,
   // nothing deferred: ~50 us less than the pipelined form) and the 96 bytes come back through pinned memory
-  if (!rc) rc = msm_dev(it->second, d + 96, n, d, s, /*inorder=*/!ab_env("H2MI_MSM_IGNORE_INORDER"));
+  if (!rc) rc = msm_dev(it->second, d + 96, n, d, s, /*inorder=*/true);
   if (!rc) rc = msm_join_all(s);
   static thread_local void* pinned = nullptr;  // 96 B of pinned host memory per calling thread, kept for the life of the thread
   if (!pinned && hipHostMalloc(&pinned, 96, hipHostMallocPortable) != hipSuccess) pinned = nullptr;

@@ -110,7 +110,7 @@ struct PassParams {
   f29 post;       // Montgomery-2^261 limbs (converted on the host: every thread of the last pass multiplies by it)
   uint32_t logN1, logN2;  // last pass: digit-reversal geometry
   uint32_t remap;         // XCD-aware block remap on/off
-  uint32_t nofuse;        // A/B (-DH2MI_AB, H2MI_NTT_NO_FUSE): the first / last round through LDS like the others
+  uint32_t nofuse;        // the first / last round through LDS like the others
   size_t in_len;          // elements of `in` that exist; indices beyond read as zero (first pass of a
                           // zero-extending transform: coeff_to_extended without materialising the padding)
 };
@@ -585,7 +585,6 @@ struct Plan {
   PowTab tw;
   fe* loc[3] = {nullptr, nullptr, nullptr};
   fe* wmat[3] = {nullptr, nullptr, nullptr};  // tile-ordered inter-pass twiddles of the non-final passes (k_ntt_wmat_build)
-  uint32_t wlogC[3] = {0, 0, 0};              // the tile geometry each was built for
   size_t wmat_bytes = 0;                      // what the matrices hold of the cache budget (g_wmat_bytes)
   Built built;
   uint64_t last_use = 0;
@@ -733,7 +732,7 @@ static int evict_tables() {
 }
 
 int get_powtab(const uint64_t base[4], uint32_t log_n, hipStream_t s, PowTab* out, bool full) {
-  full = full && log_n <= FULL_TABLE_MAX_LOG && !ab_env("H2MI_NTT_NO_FULL_TABLES");
+  full = full && log_n <= FULL_TABLE_MAX_LOG;
   Key k;
   memcpy(k.w, base, 32);
   k.log_n = log_n;
@@ -840,16 +839,7 @@ int get_powtabs(const uint64_t* bases /* m x 4 */, size_t m, uint32_t log_n, hip
 }
 
 static void choose_split(uint32_t log_n, Plan* pl) {
-  static const uint32_t MAXM = ab_env("H2MI_NTT_MAXM") ? (uint32_t)atoi(ab_env("H2MI_NTT_MAXM")) : 10;  // tuning knob (7 .. 10)
-  if (const char* ev = ab_env("H2MI_NTT_SPLIT")) {  // tuning knob: "8,8,4" — used for the size whose log_n the parts add up to
-    uint32_t a = 0, b = 0, c = 0;
-    const int got = sscanf(ev, "%u,%u,%u", &a, &b, &c);
-    if (got >= 2 && a + b + c == log_n && a >= 1 && b >= 1 && a <= 10 && b <= 10 && c <= 10) {
-      pl->P = c ? 3 : 2;
-      pl->m[0] = a; pl->m[1] = b; pl->m[2] = c;
-      return;
-    }
-  }
+  constexpr uint32_t MAXM = 10;  // the largest DFT a pass does
   if (log_n <= MAXM) {
     pl->P = 1;
     pl->m[0] = log_n;
@@ -905,10 +895,10 @@ static int get_plan(const uint64_t omega[4], uint32_t log_n, hipStream_t s, Plan
     // w_loc = omega^(n / 2^m): order 2^m
     H2_LAUNCH("k_pow_table", k_pow_table, ceil_div_u32(cnt, 256), 256, 0, s, pl.loc[p], cnt, w, log_n - m, m - 1);
   }
-  // tile-ordered twiddle matrices of the non-final passes (default tile: 2^10 elements): from the full table up to 2^22, from the
+  // tile-ordered twiddle matrices of the non-final passes (tiles of 2^10 elements): from the full table up to 2^22, from the
   // two-level table up to 2^24 (512 MB per 2^24 plan of 288 GB: the pass kernels then fetch the inter-pass twiddle instead of
   // multiplying two table entries per element — 11.75 -> 9.75 multiplications per element of a 2^24 transform)
-  if (pl.P > 1 && log_n <= WMAT_MAX_LOG && !ab_env("H2MI_NTT_NO_WMAT")) {
+  if (pl.P > 1 && log_n <= WMAT_MAX_LOG) {
     uint32_t log_seg = log_n;
     for (int p = 0; p + 1 < pl.P; p++) {
       const uint32_t m = pl.m[p], logS = log_seg - m;
@@ -934,7 +924,6 @@ static int get_plan(const uint64_t omega[4], uint32_t log_n, hipStream_t s, Plan
       }
       pl.wmat_bytes += wbytes;
       g_wmat_bytes += wbytes;
-      pl.wlogC[p] = logC;
       H2_LAUNCH("k_ntt_wmat_build", k_ntt_wmat_build, ceil_div_u32((size_t)1 << log_seg, 256), 256, 0, s, (const fe*)pl.tw.lo, (const fe*)pl.tw.hi, pl.tw.h,
                 pl.tw.full ? 1u : 0u, pl.wmat[p], log_seg, m, logC, log_n - log_seg);
       log_seg -= m;
@@ -1009,11 +998,6 @@ int release_tmp(hipStream_t s) {
   return H2MI_OK;
 }
 
-static uint32_t env_u32(const char* name, uint32_t dflt) {
-  const char* v = ab_env(name);  // tile geometry experiments: -DH2MI_AB builds only
-  return v ? (uint32_t)atoi(v) : dflt;
-}
-
 // d_src == d_a: in place.  Otherwise the first pass reads d_src (src_len elements, zero beyond) and the last
 // pass writes d_a; d_src is left untouched.
 static int ntt_dev(fe* d_a, uint32_t log_n, const uint64_t omega[4], const uint64_t* pre, const uint64_t* post, hipStream_t s,
@@ -1036,10 +1020,7 @@ static int ntt_dev(fe* d_a, uint32_t log_n, const uint64_t omega[4], const uint6
     rc = ensure_tmp(n, s);
     if (rc) return rc;
   }
-  const uint32_t tile_elems_log = env_u32("H2MI_NTT_TILE_LOG", NTT_TILE_LOG);  // elements staged per block
-  const uint32_t remap = env_u32("H2MI_NTT_XCD_REMAP", 1);
-  uint32_t nthreads = env_u32("H2MI_NTT_THREADS", 256);
-  if (nthreads != 64 && nthreads != 128 && nthreads != 256 && nthreads != 512) nthreads = 256;
+  constexpr uint32_t nthreads = 256;  // per workgroup of every pass
   static bool attr_set = false;
   if (!attr_set) {  // tiles above 64 KiB of LDS need the opt-in
 #define H2_NTT_ATTR(DS, M)                                                                                                                         \
@@ -1056,11 +1037,10 @@ static int ntt_dev(fe* d_a, uint32_t log_n, const uint64_t omega[4], const uint6
 #undef H2_NTT_ATTR
     attr_set = true;
   }
-  static const bool fixed_geometry = !ab_env("H2MI_NTT_RUNTIME_GEOMETRY");  // A/B knob (-DH2MI_AB): the run-time kernels everywhere
 // the compile-time form exists for 1024-element tiles and DFT sizes 2^7 .. 2^10 (every pass of every transform >= 2^14)
 #define H2_NTT_LAUNCH(NAME, KERNEL)                                                                                       \
   do {                                                                                                                    \
-    const bool fixed_ = fixed_geometry && pp.m + pp.logC == 10;                                                           \
+    const bool fixed_ = pp.m + pp.logC == 10;                                                                             \
     if (fixed_ && pp.m == 10) H2_LAUNCH(NAME, (KERNEL<1024, 10>), nblocks, nthreads, shmem, s, pp);                        \
     else if (fixed_ && pp.m == 9) H2_LAUNCH(NAME, (KERNEL<1024, 9>), nblocks, nthreads, shmem, s, pp);                     \
     else if (fixed_ && pp.m == 8) H2_LAUNCH(NAME, (KERNEL<1024, 8>), nblocks, nthreads, shmem, s, pp);                     \
@@ -1087,22 +1067,22 @@ static int ntt_dev(fe* d_a, uint32_t log_n, const uint64_t omega[4], const uint6
     pp.thi = pl.tw.hi;
     pp.h = pl.tw.h;
     pp.tfull = pl.tw.full;
-    pp.remap = remap;
+    pp.remap = 1;  // XCD-aware block order
     // below 2^18 a pass is a few dozen tiles and the regrouping barrier before the last round costs more than the LDS round trips
     // it saves (2^16: 36.0 -> 36.8 us fused; 2^20: 134.7 -> 129.5, 2^24: 2000 -> 1958: profiles/r04_ntt_fused_rounds.txt)
-    pp.nofuse = (log_n < 18 || ab_env("H2MI_NTT_NO_FUSE")) ? 1 : 0;
+    pp.nofuse = log_n < 18 ? 1 : 0;
     if (p == 0 && pre) {
       pp.plo = pt.lo;
       pp.phi = pt.hi;
       pp.ph = pt.h;
       pp.pfull = pt.full;
     }
-    uint32_t logC = pp.m >= tile_elems_log ? 0 : tile_elems_log - pp.m;
+    uint32_t logC = pp.m >= NTT_TILE_LOG ? 0 : NTT_TILE_LOG - pp.m;
     if (!last) {
       uint32_t logS = log_seg - pp.m;
       if (logC > logS) logC = logS;
       pp.logC = logC;
-      pp.wmat = (pl.wmat[p] && pl.wlogC[p] == logC) ? pl.wmat[p] : nullptr;  // (a tile-geometry experiment falls back to the gather)
+      pp.wmat = pl.wmat[p];  // null: the pass gathers its twiddles
       uint32_t nblocks = (uint32_t)(n >> (pp.m + logC));
       size_t shmem = ((size_t)1 << (pp.m + logC)) * 36 + std::min<size_t>((size_t)1 << (pp.m - 1), TW_STAGED) * 32;
       H2_NTT_LAUNCH("k_ntt_pass_col", k_ntt_pass_col);

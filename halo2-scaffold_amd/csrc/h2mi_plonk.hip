@@ -431,20 +431,14 @@ __device__ __forceinline__ void evaluate_h_range_body(const RangeCosets& c, uint
   acc = f29_add(acc, f29_mul3<F9>(s0.result(), load_unpack(&c.l0[idx]), sl, load_unpack(&c.l_last[idx]), sa.result(), load_unpack(&c.l_active[idx])));
   hstore(&out[idx], acc, h.tinv[idx & (rot - 1)]);
 }
-// two register budgets of the same body (round 3): unconstrained it takes 169 VGPRs (two wavefronts per
-// SIMD); held to 128 (four wavefronts) it spills 40 dwords to scratch.  Measured inside the range proof at DEGREE 22 on one
-// box, alternating: 74.8 / 75.1 ms unconstrained, 75.1 / 75.3 ms at 128 VGPRs — the kernel streams 2^24 rows at ~40 % of HBM and
-// the spills cost what the occupancy buys.  The unconstrained form is the product; the other exists in the -DH2MI_AB library (H2MI_EVALH_OCC=4).
+// register budget (round 3): unconstrained the body takes 169 VGPRs (two wavefronts per SIMD); held to 128
+// (four wavefronts) it spills 40 dwords to scratch.  Measured inside the range proof at DEGREE 22 on one box, alternating:
+// 74.8 / 75.1 ms unconstrained, 75.1 / 75.3 ms at 128 VGPRs — the kernel streams 2^24 rows at ~40 % of HBM and the spills cost
+// what the occupancy buys.  So the kernel is left unconstrained.
 __global__ void __launch_bounds__(256) k_evaluate_h_range(RangeCosets c, uint32_t ext_k, uint32_t k, uint32_t last_rot, HConsts h, const fe* xlo,
                                                            const fe* xhi, uint32_t xh, fe* out) {
   evaluate_h_range_body(c, ext_k, k, last_rot, h, xlo, xhi, xh, out);
 }
-#ifdef H2MI_AB  // the measured loser is compiled into the A/B library only (make ab), not into the product
-__global__ void __launch_bounds__(256, 4) k_evaluate_h_range_occ4(RangeCosets c, uint32_t ext_k, uint32_t k, uint32_t last_rot, HConsts h,
-                                                                  const fe* xlo, const fe* xhi, uint32_t xh, fe* out) {
-  evaluate_h_range_body(c, ext_k, k, last_rot, h, xlo, xhi, xh, out);
-}
-#endif
 
 // ---- quotient numerator, GENERAL form (round 4): what halo2-base configures when a circuit overflows one advice column --------
 // `builder.config(k, Some(minimum_rows))` (src/scaffold.rs:268) then takes num_advice > 1 gate columns — each with its own
@@ -812,9 +806,8 @@ int h2mi_plonk_lookup_product_dev(const void* d_input, const void* d_table, cons
   uint32_t* active = segsum + nseg + 8;
   const fe *in = (const fe*)d_input, *tab = (const fe*)d_table, *pin = (const fe*)d_permuted_input, *ptab = (const fe*)d_permuted_table;
   // the rows whose ratio can differ from one; the count decides between the sparse and the dense form (one 4-byte read)
-  static const bool force_dense = ab_env("H2MI_LOOKUP_DENSE") != nullptr;  // A/B (-DH2MI_AB)
   uint32_t n_act = usable_rows;
-  if (!force_dense && usable_rows >= 4096) {
+  if (usable_rows >= 4096) {
     H2_LAUNCH("k_lookup_flag", k_lookup_flag, ceil_div_u32(uu, 256), 256, 0, s, in, tab, pin, ptab, usable_rows, uu, flag);
     const uint32_t segs = ceil_div_u32(uu, SCAN_SEG_BINS);
     if (segs > 1) H2_LAUNCH("k_scan_segsum", k_scan_segsum<SCAN_SEG_BINS>, segs, 1024, 0, s, (const uint32_t*)flag, uu, segsum);
@@ -823,7 +816,7 @@ int h2mi_plonk_lookup_product_dev(const void* d_input, const void* d_table, cons
     H2_HIP(hipMemcpyAsync(&n_act, pos + uu, 4, hipMemcpyDeviceToHost, s));
     H2_HIP(hipStreamSynchronize(s));
   }
-  const bool sparse = (size_t)n_act * 4 <= u && !force_dense && usable_rows >= 4096;
+  const bool sparse = (size_t)n_act * 4 <= u && usable_rows >= 4096;
   const size_t total = sparse ? n_act : u;
   const uint32_t nblocks = ceil_div_u32(std::max<size_t>(total, 1), MS_TILE);
   fe* num = tmp_base();
@@ -925,14 +918,6 @@ int h2mi_plonk_evaluate_h_range_dev(const h2mi_range_cosets* c, uint32_t k, uint
     }
   }
   const uint32_t size = 1u << extended_k;
-#ifdef H2MI_AB
-  static const bool occ4 = ab_env("H2MI_EVALH_OCC") && atoi(ab_env("H2MI_EVALH_OCC")) == 4;
-  if (occ4) {
-    H2_LAUNCH("k_evaluate_h_range", k_evaluate_h_range_occ4, ceil_div_u32(size, 256), 256, 0, s, rc_, extended_k, k, blinding_factors + 1, hcst,
-              (const fe*)px.lo, (const fe*)px.hi, px.h, (fe*)d_h_out);
-    return H2MI_OK;
-  }
-#endif
   H2_LAUNCH("k_evaluate_h_range", k_evaluate_h_range, ceil_div_u32(size, 256), 256, 0, s, rc_, extended_k, k, blinding_factors + 1, hcst,
             (const fe*)px.lo, (const fe*)px.hi, px.h, (fe*)d_h_out);
   return H2MI_OK;

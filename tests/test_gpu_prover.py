@@ -360,8 +360,8 @@ def test_instance_coset_matches_transforms(gpu, k, degree, count):
 
 def test_lookup_product_sparse_equals_dense(gpu):
     """the lookup grand product over the flagged rows only (rows whose ratio differs from one) against the dense form of the
-    same call (H2MI_LOOKUP_DENSE in a child process would need a second library instance: instead both are compared with the
-    oracle's row-by-row product) at a size where the sparse form is taken: k = 13, a range-check-like input (a handful of limbs,
+    same call (the library has no switch that forces the dense form: instead both are compared with the oracle's row-by-row
+    product) at a size where the sparse form is taken: k = 13, a range-check-like input (a handful of limbs,
     zeros elsewhere) in a 2^8-row table."""
     from halo2_scaffold_amd import plonk as gp
     from oracle import lookup as L

@@ -17,7 +17,6 @@ echo "== op_bench"; python3 tools/op_bench.py > $OUT/op_bench.json 2> $OUT/op_be
 fi
 if [ "$PART" = all ] || [ "$PART" = 2 ]; then
 echo "== small msm"; python3 tools/msm_small_sweep.py 5 8 10 12 13 14 15 16 17 > $OUT/msm_small_final.txt 2>/dev/null
-H2MI_LIBRARY=$PWD/halo2-scaffold_amd/libh2mi_ab.so H2MI_MSM_NO_AUTO_STREAM=1 python3 tools/msm_small_sweep.py 12 13 14 15 2>/dev/null | grep "small path" >> $OUT/msm_small_final.txt
 echo "== group fft"; python3 tools/g1fft_sweep.py 12 16 18 20 22 2>/dev/null | grep -v amdgpu > $OUT/g1fft_sweep.txt
 echo "== fuzz"; python3 tools/fuzz_parity.py 150 2>&1 | grep -v amdgpu > $OUT/fuzz.txt; tail -1 $OUT/fuzz.txt
 echo "== msm sweep"; python3 tools/msm_sweep.py 18 19 20 21 22 > $OUT/msm_sweep.txt 2>/dev/null
