@@ -11,8 +11,12 @@
 // limb-wise add/sub.  Values are kept only loosely reduced ([0, ~8p)); p / 2^261 = 0.0059, so
 // mul(A, B) < (1 + 0.0059 * a * b) p for A < a p, B < b p — inputs up to ~8p give outputs < 1.4p.
 // Multiplication contract: limbs(a) < 1.9 * 2^30 and limbs(b) < 2^29 (b normalized), or both < 2^29.
-// This header is plain C++ (no intrinsics) so the same code is unit-tested on the host
-// (tests/test_f29_host.py) before it runs on the GPU.
+// This header also compiles as plain C++ with g++, and tests/test_f29_host.py unit-tests that build on the host at the limits
+// of the contracts above.  The host build is NOT the device's code: f29_mac_first is v_mad_u64_u32 inline asm under
+// __HIP_DEVICE_COMPILE__ (a plain 64-bit multiply-add on the host), and everything else comes out of another compiler.
+// tests/test_gpu_f29.py runs the same cases on the GPU through the h2mi_dbg_f29_* hooks (h2mi_hooks.hip), so the asm form is
+// checked against the big-integer oracle — and limb for limb against the host build — on chosen limbs, not only on the
+// uniform ones the kernels feed it.
 #pragma once
 #include <stdint.h>
 

@@ -1,5 +1,7 @@
 /* h2mi_hooks.h — test hooks of libh2mi_hooks.so (the product's objects + csrc/h2mi_hooks.hip); never part of libh2mi.so.
- * Elementwise device arithmetic on host arrays, used by the parity tests only. */
+ * Elementwise device arithmetic on host arrays, used by the parity tests only: the 32-bit-limb field operations and whole point
+ * operations (tests/test_gpu_parity.py), and the 29-bit-limb layer the hot kernels compute in, on chosen limbs
+ * (h2mi_dbg_f29_*, tests/test_gpu_f29.py). */
 #ifndef H2MI_HOOKS_H
 #define H2MI_HOOKS_H
 #include "../../include/h2mi.h"
@@ -13,6 +15,28 @@ int h2mi_dbg_g1_op(int op, const uint64_t* p_affine, const uint64_t* q_affine, u
 /* the lane-cooperative point operations of the bucket reduction (csrc/g1_29_quad.cuh), four lanes per
  * element: op 0 = P[i] + Q[i] (XYZZ + XYZZ), op 1 = 2 P[i]; affine Montgomery in, Jacobian out */
 int h2mi_dbg_g1_quad_op(int op, const uint64_t* p, const uint64_t* q_or_null, uint64_t* out_jac, size_t n);
+/* ---- the lazy 29-bit-limb layer (csrc/f29.cuh, g1_29.cuh) on the device.  Each hook mirrors an entry point of the g++ harness
+ * tests/host/f29_host.cpp (f29t_*): same arguments, same element layout, the same per-element body (csrc/f29_testops.cuh), one
+ * thread per element, operands read from global memory.  field: 0 = Fq29, 1 = Fr29.  The operands must respect the contracts
+ * stated in f29.cuh; the hooks do not check them. */
+/* a, b, out: 8 words per element (Mont256).  mode 0: a*b through Mont261; 1: NTT style, data a (Mont256, unpacked) x twiddle b
+ * (converted to Mont261), canonical; 2: the lazy chain (a - b + 2p, un-normalized) * (a + b); 4: f29_sqr(a); 5: f29_inv(a)
+ * (Fermat); 3: pack(unpack(a)) */
+int h2mi_dbg_f29_mul(int field, int mode, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n);
+/* raw 9-limb operands and results, 9 words per element */
+int h2mi_dbg_f29_reduce_loose(int field, const uint32_t* in9, uint32_t* out9, size_t n);   /* normalized, value < 64p -> canonical */
+int h2mi_dbg_f29_mul_raw(int field, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n); /* limbs(a) < 1.9 * 2^30, b normalized */
+int h2mi_dbg_f29_sqr_raw(int field, const uint32_t* a, uint32_t* out, size_t n);           /* a normalized */
+int h2mi_dbg_f29_mul2_raw(int field, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* out, size_t n);
+int h2mi_dbg_f29_mul3_raw(int field, const uint32_t* ops /* [6][n][9] */, uint32_t* out, size_t n);
+/* f29t_madd_chain, batched: chain c accumulates the affine points (Mont256, 16 words each; (0,0) skipped) offsets[c] ..
+ * offsets[c + 1] of pts with signs[i] != 0 meaning -P_i, one thread per chain, all chains in one launch; offsets has nchains + 1
+ * entries starting at 0.  tree = 0: mixed additions into one accumulator; 2 / 4 / 8 / 16: that many group accumulators folded
+ * pairwise with the full XYZZ addition (at 16 also the doubling and cancellation sequence).  out_xyzz: 4 x 8 words Mont256 per
+ * chain, all zeros for the identity.
+ * The pair-affine chain (f29t_pair_chain) has no device hook: no product kernel uses affine29_pair_add any more, so it stays a
+ * host-only test of the header. */
+int h2mi_dbg_g1_29_chains(const uint32_t* pts, const uint8_t* signs, const uint64_t* offsets, size_t nchains, uint32_t* out_xyzz, int tree);
 #ifdef __cplusplus
 }
 #endif

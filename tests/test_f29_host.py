@@ -1,8 +1,8 @@
 """CPU tests of the lazy 29-bit-limb field / curve layer (csrc/f29.cuh, g1_29.cuh) compiled with g++.
 
-The GPU kernels inline exactly this code; verifying it on the host against the big-integer oracle
-covers limb bounds, the Mont256 <-> Mont261 conversions and every special case of the mixed addition
-without needing a GPU."""
+The GPU kernels inline this code; verifying it on the host against the big-integer oracle covers limb bounds, the
+Mont256 <-> Mont261 conversions and every special case of the mixed addition without needing a GPU.  The cases and checks live
+in tests/f29_cases.py; tests/test_gpu_f29.py runs the same ones through the device build (whose f29_mac_first is inline asm)."""
 import ctypes as C
 import os
 import subprocess
@@ -12,20 +12,19 @@ import pytest
 
 from oracle import bn254 as o
 
+import f29_cases as K
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "f29_host.cpp")
-SO = os.path.join(ROOT, "tests", "host", "libf29host.so")
 
 
 @pytest.fixture(scope="module")
 def host():
-    deps = [SRC] + [os.path.join(ROOT, "halo2-scaffold_amd", "csrc", f) for f in ("f29.cuh", "g1_29.cuh", "f29_consts.inc")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SO, SRC])
-    L = C.CDLL(SO)
-    L.f29t_mul.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.f29t_madd_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
-    return L
+    return K.host_lib()
+
+
+@pytest.fixture(scope="module")
+def be(host):
+    return K.HostBackend(host)
 
 
 def test_generated_constants_are_current():
@@ -33,189 +32,48 @@ def test_generated_constants_are_current():
     assert gen == open(os.path.join(ROOT, "halo2-scaffold_amd", "csrc", "f29_consts.inc")).read()
 
 
-def _edge(mod):
-    return [0, 1, 2, mod - 1, mod - 2, (1 << 253) % mod, (1 << 232) - 1, 1 << 232, (1 << 29) - 1, 1 << 29, ((1 << 254) - 1) % mod]
+@pytest.mark.parametrize("field,mod", K.FIELDS)
+def test_f29_mul_modes(be, field, mod):
+    K.check_mul_modes(be, field, mod)
 
 
-@pytest.mark.parametrize("field,mod", [(0, o.Q), (1, o.R)])
-def test_f29_mul_modes(host, field, mod):
-    rng = np.random.default_rng(7 + field)
-    vals_a = _edge(mod) + [int.from_bytes(rng.bytes(32), "little") % mod for _ in range(3000)]
-    vals_b = list(reversed(_edge(mod))) + [int.from_bytes(rng.bytes(32), "little") % mod for _ in range(3000)]
-    n = len(vals_a)
-    A, B = o.pack(vals_a, mod), o.pack(vals_b, mod)
-    out = np.zeros((n, 4), dtype=np.uint64)
-    host.f29t_mul(field, 0, A.ctypes.data, B.ctypes.data, out.ctypes.data, n)
-    assert o.unpack(out, mod) == [x * y % mod for x, y in zip(vals_a, vals_b)]
-    host.f29t_mul(field, 1, A.ctypes.data, B.ctypes.data, out.ctypes.data, n)
-    assert o.unpack(out, mod) == [x * y % mod for x, y in zip(vals_a, vals_b)]
-    host.f29t_mul(field, 2, A.ctypes.data, B.ctypes.data, out.ctypes.data, n)
-    assert o.unpack(out, mod) == [(x + y) * (x - y) % mod for x, y in zip(vals_a, vals_b)]
-    host.f29t_mul(field, 4, A.ctypes.data, B.ctypes.data, out.ctypes.data, n)
-    assert o.unpack(out, mod) == [x * x % mod for x in vals_a]
-    host.f29t_mul(field, 5, A.ctypes.data, B.ctypes.data, out.ctypes.data, 64)
-    assert o.unpack(out[:64], mod) == [pow(x, -1, mod) if x else 0 for x in vals_a[:64]]
-    host.f29t_mul(field, 3, A.ctypes.data, B.ctypes.data, out.ctypes.data, n)
-    assert np.array_equal(out, A)
-    assert all(v < mod for v in o.unpack(out))
+@pytest.mark.parametrize("field,mod", K.FIELDS)
+def test_reduce_loose(be, field, mod):
+    K.check_reduce_loose(be, field, mod)
 
 
-@pytest.mark.parametrize("field,mod", [(0, o.Q), (1, o.R)])
-def test_reduce_loose(host, field, mod):
-    """the multiplication-free final reduction of the NTT: any normalized value below 64p -> canonical."""
-    rng = np.random.default_rng(11 + field)
-    vals = [0, 1, mod - 1, mod, mod + 1, 2 * mod - 1, 2 * mod, 3 * mod - 1, 3 * mod, 31 * mod + 5, 64 * mod - 1, 63 * mod, (1 << 232) - 1, 1 << 232]
-    vals += [k * mod + d for k in range(0, 64, 7) for d in (0, 1, mod - 1)]
-    vals += [int.from_bytes(rng.bytes(33), "little") % (64 * mod) for _ in range(20000)]
-    n = len(vals)
-    limbs = np.array([[(v >> (29 * i)) & ((1 << 29) - 1) if i < 8 else v >> 232 for i in range(9)] for v in vals], dtype=np.uint32)
-    out = np.zeros_like(limbs)
-    host.f29t_reduce_loose.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-    host.f29t_reduce_loose(field, limbs.ctypes.data, out.ctypes.data, n)
-    got = [sum(int(out[j, i]) << (29 * i) for i in range(9)) for j in range(n)]
-    assert got == [v % mod for v in vals]
-    assert (out[:, :8] < (1 << 29)).all()
+def test_madd_chain_random_and_special_cases(be):
+    K.check_madd_chain_random_and_special_cases(be)
 
 
-def _xyzz_to_affine(out):
-    X, Y, ZZ, ZZZ = (o.limbs_to_int(out[4 * i : 4 * i + 4]) * pow(o.MONT_R, -1, o.Q) % o.Q for i in range(4))
-    if ZZ == 0:
-        return None
-    assert pow(ZZ, 3, o.Q) == ZZZ * ZZZ % o.Q
-    return (X * pow(ZZ, -1, o.Q) % o.Q, Y * pow(ZZZ, -1, o.Q) % o.Q)
+def test_full_add_and_double_trees(be):
+    K.check_full_add_and_double_trees(be)
 
 
-def _chain(host, pts, signs, tree=0):
-    P = o.pack_points(pts)
-    S = np.array(signs, dtype=np.uint8)
-    out = np.zeros(16, dtype=np.uint64)
-    host.f29t_madd_chain(P.ctypes.data, S.ctypes.data, len(pts), out.ctypes.data, tree)
-    want = None
-    for p, s in zip(pts, signs):
-        want = o.g1_add(want, o.g1_neg(p) if s else p)
-    assert _xyzz_to_affine(out) == want
+def test_long_chain_keeps_invariants(be):
+    K.check_long_chain_keeps_invariants(be)
 
 
-def test_madd_chain_random_and_special_cases(host):
-    rng = np.random.default_rng(3)
-    pts = [o.g1_mul(int(rng.integers(1, 1 << 62)), o.G1_GEN) for _ in range(200)]
-    signs = [int(rng.integers(0, 2)) for _ in pts]
-    _chain(host, pts, signs)                      # long chain: the accumulator invariants must hold
-    _chain(host, pts[:1], [1])                    # single negated point
-    _chain(host, [pts[0], pts[0]], [0, 0])        # P + P  (doubling branch)
-    _chain(host, [pts[0], pts[0]], [1, 1])        # (-P) + (-P)
-    _chain(host, [pts[0], pts[0]], [0, 1])        # P - P = identity
-    _chain(host, [pts[0], pts[0], pts[1]], [0, 1, 0])      # identity then restart
-    _chain(host, [pts[0], pts[0], pts[0], pts[0]], [0, 0, 0, 0])  # 2P then +P then +P
-    _chain(host, [None, pts[2], None, pts[3]], [0, 0, 1, 1])      # identity table entries skipped
-    _chain(host, [o.G1_GEN] * 33, [0] * 33)       # n*G: first addition doubles, rest are generic
-    big = [o.g1_mul(o.R - 1 - i, o.G1_GEN) for i in range(5)]
-    _chain(host, big + pts[:5], [0] * 10)
+def test_extreme_limb_patterns(be):
+    K.check_extreme_limb_patterns(be)
 
 
-def test_full_add_and_double_trees(host):
-    """XYZZ + XYZZ additions (the fold / bucket-reduction kernels) incl. doubling and cancellation branches."""
-    rng = np.random.default_rng(11)
-    pts = [o.g1_mul(int(rng.integers(1, 1 << 62)), o.G1_GEN) for _ in range(300)]
-    signs = [int(rng.integers(0, 2)) for _ in pts]
-    for tree in (2, 4, 8, 16):
-        _chain(host, pts, signs, tree)
-        _chain(host, pts[:tree], signs[:tree], tree)          # one point per group
-        _chain(host, pts[:3], signs[:3], tree)                # mostly empty groups (identity operands)
-    _chain(host, [pts[0]] * 16, [0] * 16, 16)                 # all groups equal: every fold step doubles
-    _chain(host, [pts[0], pts[0]], [0, 1], 2)                 # groups cancel
+def test_mul2_shared_reduction_at_the_contract_limits(be):
+    K.check_mul2_at_the_contract_limits(be)
 
 
-def test_long_chain_keeps_invariants(host):
-    """5,000 mixed additions into one accumulator: the loose-reduction invariants of g1_29.cuh must hold
-    indefinitely (a drift in the value bounds would eventually corrupt the sum)."""
-    rng = np.random.default_rng(99)
-    base = [o.g1_mul(int(rng.integers(1, 1 << 62)), o.G1_GEN) for _ in range(50)]
-    pts, signs = [], []
-    for i in range(5000):
-        pts.append(base[int(rng.integers(0, 50))])
-        signs.append(int(rng.integers(0, 2)))
-    P = o.pack_points(pts)
-    S = np.array(signs, dtype=np.uint8)
-    out = np.zeros(16, dtype=np.uint64)
-    host.f29t_madd_chain(P.ctypes.data, S.ctypes.data, len(pts), out.ctypes.data, 0)
-    # expected: sum over the 50 base points of (count_plus - count_minus) * P
-    coef = {}
-    for p, s in zip(pts, signs):
-        coef[p] = coef.get(p, 0) + (-1 if s else 1)
-    want = None
-    for p, c in coef.items():
-        want = o.g1_add(want, o.g1_mul(c % o.R, p))
-    assert _xyzz_to_affine(out) == want
+def test_mul3_shared_reduction_at_the_contract_limits(be):
+    K.check_mul3_at_the_contract_limits(be)
 
 
-def test_extreme_limb_patterns(host):
-    """field elements whose 29-bit limbs are all-ones / alternating / near the modulus: worst cases for the
-    64-bit column accumulators of f29_mul and f29_sqr."""
-    for field, mod in [(0, o.Q), (1, o.R)]:
-        pats = [mod - 1, mod - 2, (1 << 254) - 1, ((1 << 254) - 1) - mod, int("1" * 253, 2), int("10" * 126, 2), int("01" * 127, 2),
-                ((1 << 29) - 1) * sum(1 << (29 * i) for i in range(8)), (1 << 232) - 1, (mod >> 1), (mod >> 1) + 1]
-        pats = [p % mod for p in pats]
-        A = o.pack([a for a in pats for _ in pats], mod)
-        B = o.pack([b for _ in pats for b in pats], mod)
-        n = len(A)
-        out = np.zeros((n, 4), dtype=np.uint64)
-        av, bv = o.unpack(A, mod), o.unpack(B, mod)
-        host.f29t_mul(field, 0, A.ctypes.data, B.ctypes.data, out.ctypes.data, n)
-        assert o.unpack(out, mod) == [x * y % mod for x, y in zip(av, bv)]
-        host.f29t_mul(field, 2, A.ctypes.data, B.ctypes.data, out.ctypes.data, n)
-        assert o.unpack(out, mod) == [(x + y) * (x - y) % mod for x, y in zip(av, bv)]
-        host.f29t_mul(field, 4, A.ctypes.data, B.ctypes.data, out.ctypes.data, n)
-        assert o.unpack(out, mod) == [x * x % mod for x in av]
+@pytest.mark.parametrize("field,mod", K.FIELDS)
+def test_mul_raw_at_the_contract_limit(be, field, mod):
+    K.check_mul_raw_at_the_contract_limit(be, field, mod)
 
 
-def test_mul2_shared_reduction_at_the_contract_limits(host):
-    """f29_mul2 = (a b + c d) / 2^261 with one reduction (the Y3 of the mixed addition): random operands and the
-    largest limbs its contract allows (a < 1.5 * 2^30, c < 2^30, b and d < 2^29 per limb) — the 64-bit column
-    accumulators must not wrap."""
-    host.f29t_mul2_raw.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_size_t]
-    rng = np.random.default_rng(29)
-    n = 4000
-    lim = {"a": 3 << 29, "b": 1 << 29, "c": 1 << 30, "d": 1 << 29}
-    ops = {k: rng.integers(0, v, size=(n, 9), dtype=np.uint32) for k, v in lim.items()}
-    for k, v in lim.items():
-        ops[k][:8] = v - 1        # every limb at its maximum, all four operands together
-        ops[k][8:16, ::2] = v - 1
-    ops["b"][:, 8] &= (1 << 25) - 1  # top limbs of normalized values below 8p
-    ops["d"][:, 8] &= (1 << 25) - 1
-    val = lambda row: sum(int(x) << (29 * i) for i, x in enumerate(row))
-    for field, mod in [(0, o.Q), (1, o.R)]:
-        out = np.zeros((n, 9), dtype=np.uint32)
-        host.f29t_mul2_raw(field, ops["a"].ctypes.data, ops["b"].ctypes.data, ops["c"].ctypes.data, ops["d"].ctypes.data, out.ctypes.data, n)
-        assert (out[:, :8] < (1 << 29)).all()
-        for i in range(n):
-            a, b, c, d = (val(ops[k][i]) for k in "abcd")
-            got = val(out[i])
-            assert got * (1 << 261) % mod == (a * b + c * d) % mod
-            assert got < (a * b + c * d) // (1 << 261) + mod + 1
-
-
-def test_mul3_shared_reduction_at_the_contract_limits(host):
-    """f29_mul3 = (a b + c d + e f) / 2^261 (three terms of a linear combination, one reduction): every limb of all six
-    operands at 2^29 - 1 and random normalized operands."""
-    host.f29t_mul3_raw.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-    rng = np.random.default_rng(31)
-    n = 3000
-    ops = rng.integers(0, 1 << 29, size=(6, n, 9), dtype=np.uint32)
-    ops[:, :8, :] = (1 << 29) - 1
-    ops[:, 8:16, ::2] = (1 << 29) - 1
-    ops[:, 16:, 8] &= (1 << 25) - 1
-    val = lambda row: sum(int(x) << (29 * i) for i, x in enumerate(row))
-    for field, mod in [(0, o.Q), (1, o.R)]:
-        out = np.zeros((n, 9), dtype=np.uint32)
-        host.f29t_mul3_raw(field, ops.ctypes.data, out.ctypes.data, n)
-        assert (out[:, :8] < (1 << 29)).all()
-        for i in range(n):
-            v = [val(ops[q, i]) for q in range(6)]
-            want = v[0] * v[1] + v[2] * v[3] + v[4] * v[5]
-            got = val(out[i])
-            assert got * (1 << 261) % mod == want % mod
-            assert got < want // (1 << 261) + mod + 1
+@pytest.mark.parametrize("field,mod", K.FIELDS)
+def test_sqr_raw_at_the_contract_limit(be, field, mod):
+    K.check_sqr_raw_at_the_contract_limit(be, field, mod)
 
 
 def test_pair_affine_chain_matches_oracle(host):
@@ -235,7 +93,7 @@ def test_pair_affine_chain_matches_oracle(host):
         want = None
         for p, s in zip(pts, signs):
             want = o.g1_add(want, o.g1_neg(p) if s else p)
-        assert _xyzz_to_affine(out) == want
+        assert K.xyzz_to_affine(out) == want
 
     for n in (1, 2, 3, 4, 7, 40):
         for trial in range(4):
