@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <map>
+#include <type_traits>
 #include <vector>
 
 #include "g1.cuh"
@@ -42,7 +43,7 @@ constexpr uint32_t HOT_MIN = 64; // a bucket with more folded partials than this
 constexpr uint32_t HOT_MIN_WIDE = 8;  // wide windows: two lanes per bucket, no fold level (the finish reads the accumulation's partials)
 
 // Entries per accumulation chunk (= additions per thread).  The accumulation is resident at two workgroups of
-// 256 threads per CU (the occupancy cap in msm_dev): ACCUM_RESIDENT_CHUNKS chunks run at once, all of the same
+// 256 threads per CU (the occupancy cap ACCUM_LDS): ACCUM_RESIDENT_CHUNKS chunks run at once, all of the same
 // length, so the kernel's time is (rounds of resident chunks) x (chunk length).  The length is chosen so that the
 // chunks fill a whole number of rounds — with a power-of-two length a 2^18 / 2^19 slice ran 1.06 rounds, a
 // second, nearly empty round of full-length chains (0.45 / 0.88 ms instead of 0.36 / 0.67 ms) — and from the
@@ -68,6 +69,24 @@ __host__ __device__ inline uint32_t accum_chunk_len(uint32_t entries) {
   return s0 < 8 ? 8 : s0;
 }
 
+// One stage of a slot's MSM (partition head, accumulation, bucket reduction) as the slot's later users see it: the event recorded
+// behind the stage's last kernel, `pending` while some later user may still have to wait for it (cleared once the slot's next MSM or
+// a join has waited) and `ever` once it has been recorded at all (a caller's stream, which no join orders, waits on that).
+struct Stage {
+  hipEvent_t ev = nullptr;
+  bool pending = false, ever = false;
+  hipError_t create() { return hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+  void destroy() { if (ev) H2_IGNORE(hipEventDestroy(ev)); }
+  hipError_t record(hipStream_t s) {
+    const hipError_t e = hipEventRecord(ev, s);
+    if (e == hipSuccess) pending = ever = true;
+    return e;
+  }
+  hipError_t wait(hipStream_t s) const { return hipStreamWaitEvent(s, ev, 0); }
+  hipError_t wait_if_pending(hipStream_t s) const { return pending ? wait(s) : hipSuccess; }
+  hipError_t wait_if_ever(hipStream_t s) const { return ever ? wait(s) : hipSuccess; }
+};
+
 // per-call workspace; several slots per handle so that consecutive MSMs overlap (partition of one beside
 // the accumulation of another) and their bucket reductions can be deferred and run as one batch.
 struct Slot {
@@ -89,9 +108,8 @@ struct Slot {
   uint8_t* g = nullptr;                             // weighted partials (<= 32)
   uint64_t* stats = nullptr;                        // [0] = insertions
   fe* shift = nullptr;                              // the dominant scalar value this MSM subtracts (k_msm_pick_shift), Montgomery
-  hipEvent_t input_ready = nullptr, head_done = nullptr, accum_done = nullptr, tail_done = nullptr;
-  bool tail_pending = false, accum_pending = false, head_pending = false;
-  bool tail_ever = false, accum_ever = false, head_ever = false;  // the events have been recorded at least once
+  Stage input_ready;            // the scalars have been consumed (only its event is used: recorded and waited for within one call)
+  Stage head, accum, tail;      // partition, accumulation (small path: digits), reduction (small path: accumulate + final pair)
   hipStream_t last_stream = nullptr;  // stream the slot's previous MSM was issued on
   bool tail_deferred = false;   // accumulation queued, bucket reduction not yet launched (see flush_tails)
   void* d_out = nullptr;        // where that reduction will write the result
@@ -102,6 +120,23 @@ struct Slot {
   uint32_t* scnt = nullptr;
   bool small_deferred = false;  // the deferred work of this slot is the small path's accumulate + final pair
   uint32_t small_n = 0;         // points of that MSM
+
+  hipError_t create_events() {
+    for (Stage* st : {&input_ready, &head, &accum, &tail})
+      if (hipError_t e = st->create()) return e;
+    return hipSuccess;
+  }
+  void destroy_events() {
+    for (Stage* st : {&input_ready, &head, &accum, &tail}) st->destroy();
+  }
+  // the slot's next MSM is ordered behind everything recorded so far
+  void clear_pending() { tail.pending = accum.pending = head.pending = false; }
+  // the slot's reduction has just been launched on t
+  hipError_t reduction_launched(hipStream_t t) {
+    const hipError_t e = tail.record(t);
+    if (e == hipSuccess) tail_deferred = small_deferred = false;
+    return e;
+  }
 };
 // slots per handle = MSMs that can be in flight between two joins before a flush is forced
 // Eight for base sets up to 2^17 (round 3): with four, every fifth back-to-back MSM waited for the reduction batch of the four
@@ -1396,12 +1431,463 @@ static void free_bases(Bases* B) {
     H2_IGNORE(hipFree(S.dense)); H2_IGNORE(hipFree(S.dense2)); H2_IGNORE(hipFree(S.vsum)); H2_IGNORE(hipFree(S.tseg[0])); H2_IGNORE(hipFree(S.tseg[1]));
     H2_IGNORE(hipFree(S.part[0])); H2_IGNORE(hipFree(S.part[1])); H2_IGNORE(hipFree(S.rc)); H2_IGNORE(hipFree(S.g)); H2_IGNORE(hipFree(S.stats)); H2_IGNORE(hipFree(S.shift));
     H2_IGNORE(hipFree(S.sdig)); H2_IGNORE(hipFree(S.spart)); H2_IGNORE(hipFree(S.scnt));
-    if (S.input_ready) H2_IGNORE(hipEventDestroy(S.input_ready));
-    if (S.head_done) H2_IGNORE(hipEventDestroy(S.head_done));
-    if (S.accum_done) H2_IGNORE(hipEventDestroy(S.accum_done));
-    if (S.tail_done) H2_IGNORE(hipEventDestroy(S.tail_done));
+    S.destroy_events();
   }
   delete B;
+}
+
+// ---- window-width dispatch ------------------------------------------------------------------------------------------
+// The widths whose count / scatter kernels are instantiated with a compile-time CT; every other width runs CT = 0.  One list per
+// kernel form serves both the launch (with_width) and the function attributes (each_width): a width cannot be launched without its attribute.
+// (LEFT folds below: clang instantiates the kernels in the order the fold names them, and that is their order in the code object —
+// with right folds the same kernels come out in reverse, and the device code no longer compares equal to an earlier build's.)
+template <uint32_t... CT>
+struct Widths {};
+using PlainWidths = Widths<13, 15, 16, 17, 18, 19, 20>;  // k_msm_bin_count<CT> / k_msm_bin_scatter<CT>
+using BatchWidths = Widths<13, 15, 16, 17>;              // their _b forms: narrow windows only
+template <uint32_t CT>
+using Width = std::integral_constant<uint32_t, CT>;
+// f(Width<CT>) for the one instantiation that serves window width c; hands f's status back
+template <class F, uint32_t... CT>
+static int with_width(Widths<CT...>, uint32_t c, F&& f) {
+  int rc = H2MI_OK;
+  const bool listed = (... || (c == CT && ((rc = f(Width<CT>{})), true)));
+  return listed ? rc : f(Width<0>{});
+}
+// f(Width<CT>) for every instantiation with_width can choose, until one fails
+template <class F, uint32_t... CT>
+static int each_width(Widths<CT...>, F&& f) {
+  int rc = f(Width<0>{});
+  (..., (rc = rc ? rc : f(Width<CT>{})));
+  return rc;
+}
+// the scatter kernel stages up to 144 KiB of pairs in LDS (W = 24; 90 KiB at W = 15)
+constexpr int SCATTER_LDS_MAX = 150 * 1024;
+template <class WidthList, class KernelOf>
+static int allow_scatter_lds(WidthList widths, bool (&done_dev)[16], KernelOf kernel_of) {
+  bool& done = done_dev[ctx().cur & 15];  // function attributes are per device (every shard of a sharded handle launches these)
+  if (done) return H2MI_OK;
+  int rc = each_width(widths, [&](auto ct) -> int {
+    H2_HIP(hipFuncSetAttribute(kernel_of(ct), hipFuncAttributeMaxDynamicSharedMemorySize, SCATTER_LDS_MAX));
+    return H2MI_OK;
+  });
+  done = rc == H2MI_OK;
+  return rc;
+}
+
+// ---- the head's launches: batch form (one HeadBatch of m MSMs, blockIdx.y = MSM), then plain form (one MSM, plain arguments) ----
+// first partition level on s: shift, bin count, offsets, scatter
+static int launch_level1_b(const Bases* B, const HeadBatch& hb, uint32_t m, size_t n, bool shifted, uint32_t ntiles, hipStream_t s) {
+  static bool attr_set_dev[16] = {};
+  int rc = allow_scatter_lds(BatchWidths{}, attr_set_dev, [](auto ct) { return reinterpret_cast<const void*>(k_msm_bin_scatter_b<decltype(ct)::value>); });
+  if (rc) return rc;
+  const uint32_t W = B->W;
+  if (shifted) H2_LAUNCH("k_msm_pick_shift", k_msm_pick_shift_b, dim3(1, m), 64, 0, s, hb, n);
+  rc = with_width(BatchWidths{}, B->c, [&](auto ct) -> int {
+    H2_LAUNCH("k_msm_bin_count", k_msm_bin_count_b<decltype(ct)::value>, dim3(ntiles, m), P1_TS, 0, s, hb, n, B->c, W, B->lb, B->nbins, ntiles);
+    return H2MI_OK;
+  });
+  if (rc) return rc;
+  const uint32_t cells = B->nbins * ntiles;
+  const uint32_t nseg = ceil_div_u32(cells, SCAN_SEG_BINS);
+  if (nseg > 1) H2_LAUNCH("k_scan_segsum", k_scan_segsum_bins_b, dim3(nseg, m), 1024, 0, s, hb, cells);
+  H2_LAUNCH("k_scan_seg_bins", k_scan_seg_bins_b, dim3(nseg, m), 1024, 0, s, hb, cells);
+  return with_width(BatchWidths{}, B->c, [&](auto ct) -> int {
+    H2_LAUNCH("k_msm_bin_scatter", k_msm_bin_scatter_b<decltype(ct)::value>, dim3(ntiles, m), P1_TS, (size_t)P1_TS * W * 6, s, hb, n, B->stride, B->c, W, B->lb,
+              B->nbins, ntiles);
+    return H2MI_OK;
+  });
+}
+// second partition level (per-bin sort, bucket tables) and task offsets on hs
+static int launch_level2_b(const Bases* B, const HeadBatch& hb, uint32_t m, uint32_t ntiles, uint32_t s0_fixed, hipStream_t hs) {
+  H2_LAUNCH("k_msm_bin_sort", k_msm_bin_sort_b, dim3(B->nbins, m), P2_THREADS, 0, hs, hb, ntiles, B->nbins, B->lb, s0_fixed, B->nb);
+  H2_LAUNCH("k_scan_seg_tasks", k_scan_seg_tasks_b, dim3(1, 2, m), 1024, 0, hs, hb, B->nb);
+  return H2MI_OK;
+}
+
+static int launch_level1(const Bases* B, const Slot& S, const fe* scalars, size_t n, bool shifted, uint32_t ntiles, hipStream_t s) {
+  static bool attr_set_dev[16] = {};
+  int rc = allow_scatter_lds(PlainWidths{}, attr_set_dev, [](auto ct) { return reinterpret_cast<const void*>(k_msm_bin_scatter<decltype(ct)::value>); });
+  if (rc) return rc;
+  const uint32_t W = B->W;
+  const fe* shift = shifted ? S.shift : nullptr;
+  // the partition's first level reads the scalars twice (count, scatter): both stay on s, so work queued
+  // on s after this call may overwrite them
+  if (shifted) H2_LAUNCH("k_msm_pick_shift", k_msm_pick_shift, 1, 64, 0, s, scalars, n, S.shift);
+  rc = with_width(PlainWidths{}, B->c, [&](auto ct) -> int {
+    H2_LAUNCH("k_msm_bin_count", k_msm_bin_count<decltype(ct)::value>, ntiles, P1_TS, 0, s, scalars, n, shift, B->c, W, B->lb, B->nbins, ntiles, S.bincnt, S.tile_live);
+    return H2MI_OK;
+  });
+  if (rc) return rc;
+  const uint32_t cells = B->nbins * ntiles;  // a multiple of 4 (checked at registration)
+  const uint32_t nseg = ceil_div_u32(cells, SCAN_SEG_BINS);
+  if (nseg > 1) H2_LAUNCH("k_scan_segsum", k_scan_segsum<SCAN_SEG_BINS>, nseg, 1024, 0, s, (const uint32_t*)S.bincnt, cells, S.binseg);
+  H2_LAUNCH("k_scan_seg_bins", k_scan_seg<SCAN_SEG_BINS>, dim3(nseg, 1), 1024, 0, s, (const uint32_t*)S.bincnt, S.binbase, (const uint32_t*)nullptr,
+            (uint32_t*)nullptr, cells, (const uint32_t*)S.binseg);
+  return with_width(PlainWidths{}, B->c, [&](auto ct) -> int {
+    H2_LAUNCH("k_msm_bin_scatter", k_msm_bin_scatter<decltype(ct)::value>, ntiles, P1_TS, (size_t)P1_TS * W * 6, s, scalars, n, shift, B->stride, B->c, W, B->lb,
+              B->nbins, ntiles, (const uint32_t*)S.binbase, S.vals[0], S.bkeys, (const uint32_t*)S.tile_live);
+    return H2MI_OK;
+  });
+}
+// (the wide-window sort and its segmented scans exist in this form only)
+static int launch_level2(const Bases* B, const Slot& S, uint32_t ntiles, uint32_t s0_fixed, hipStream_t hs) {
+  const uint32_t nb = B->nb;
+  if (B->seg_log) {
+    H2_LAUNCH("k_msm_bin_sort", k_msm_bin_sort_wide, B->nbins, P2_THREADS, 0, hs, (const uint16_t*)S.bkeys, (const uint32_t*)S.vals[0],
+              (const uint32_t*)S.binbase, ntiles, B->nbins, B->lb, s0_fixed, nb, S.vals[1], S.off, S.np[0], S.np[1], S.s0_dev);
+    const uint32_t tsegs = ceil_div_u32(nb, SCAN_SEG_BINS);  // nb > 65536 task counters: segmented, one array per launch
+    for (int i = 0; i < 2; i++) {
+      H2_LAUNCH("k_scan_segsum", k_scan_segsum<SCAN_SEG_BINS>, tsegs, 1024, 0, hs, (const uint32_t*)S.np[i], nb, S.tseg[i]);
+      H2_LAUNCH("k_scan_seg_tasks", k_scan_seg<SCAN_SEG_BINS>, dim3(tsegs, 1), 1024, 0, hs, (const uint32_t*)S.np[i], S.toff[i], (const uint32_t*)nullptr,
+                (uint32_t*)nullptr, nb, (const uint32_t*)S.tseg[i]);
+    }
+  } else {
+    H2_LAUNCH("k_msm_bin_sort", k_msm_bin_sort, B->nbins, P2_THREADS, 0, hs, (const uint8_t*)S.bkeys, (const uint32_t*)S.vals[0],
+              (const uint32_t*)S.binbase, ntiles, B->nbins, B->lb, s0_fixed, nb, S.vals[1], S.off, S.np[0], S.np[1], S.s0_dev);
+    H2_LAUNCH("k_scan_seg_tasks", k_scan_seg<SCAN_SEG_TASKS>, dim3(1, 2), 1024, 0, hs, (const uint32_t*)S.np[0], S.toff[0], (const uint32_t*)S.np[1], S.toff[1], nb,
+              (const uint32_t*)nullptr);
+  }
+  return H2MI_OK;
+}
+
+// ---- reductions: the bucket reduction of the general pipeline, the accumulate + final pair of the small path -------------
+// An MSM whose reduction is not launched with it is kept here until flush_tails launches it in a batch with the others.
+struct Deferred {
+  Bases* B;
+  Slot* S;
+};
+static std::vector<Deferred> g_deferred;
+
+// the batch kernels take their whole descriptor array by value: the entries past `count` repeat entry 0 and are never read (blockIdx.y < count)
+template <class T, size_t N>
+static void pad_descs(T (&d)[N], size_t count) {
+  for (size_t j = count; j < N; j++) d[j] = d[0];
+}
+
+static TailDesc tail_desc(const Bases* B, const Slot& S) {
+  TailDesc d;
+  d.part0 = S.part[0];
+  d.toff0 = S.toff[0]; d.np0 = S.np[0]; d.toff1 = S.toff[1]; d.np1 = S.np[1]; d.off = S.off;
+  d.part1 = S.part[1]; d.dense = S.dense; d.rc = S.rc; d.g = S.g; d.out = (uint8_t*)S.d_out;
+  d.stats = S.stats;
+  d.nb = B->nb; d.logNh = B->logNh; d.logNl = B->logNl; d.canonical = g_canonical ? 1u : 0u;
+  d.seg_log = B->seg_log; d.dense2 = S.dense2; d.vsum = S.vsum; d.mat = B->seg_log ? S.dense2 : S.dense;
+  d.hot_min = B->seg_log ? HOT_MIN_WIDE : HOT_MIN;
+  // wide windows: 2^17 .. 2^19 buckets hold a partial or two each, the fold level would copy them (0.08 - 0.18 ms per MSM, measured);
+  // the finish kernels read the accumulation's partials directly.  (Round 4 tried the same for up to 2^14 / 2^15 buckets, where the
+  // chain is what a join waits for: a lone 2^16 MSM gains ~10 us, a phase of four loses 4 - 7 %: profiles/r04_msm_mid_sweep.txt.)
+  d.no_fold = B->seg_log ? 1u : 0u;
+  if (d.no_fold) { d.part1 = S.part[0]; d.toff1 = S.toff[0]; d.np1 = S.np[0]; }
+  return d;
+}
+
+// The bucket reductions of `count` <= TAIL_BATCH MSMs as one set of launches on t.  `behind_accum`: t is not the stream their
+// accumulations were queued on (the deferred form), so it waits for each of them first.
+// The launches: one fold level (<= S1 partials per task: part[0] -> part[1]), then FG lanes per bucket finish into the
+// dense array.  A bucket holding m points leaves ceil(m / (s0 * S1)) partials for the finish kernel: 1 in
+// the uniform case at k = 20, <= ~50 for the hot 0/1 buckets of witness-like columns (7 serial additions
+// per lane), n / (s0 * S1) if every scalar is the same (slow but correct).  Then the weighted bucket sum.
+static int launch_tails(const Deferred* work, uint32_t count, hipStream_t t, bool behind_accum) {
+  TailBatch tb;
+  uint32_t max_tasks1 = 0, max_nb = 0, max_logNh = 0, max_logNl = 0, max_seg = 0;
+  bool none_folds = true;
+  for (uint32_t j = 0; j < count; j++) {
+    const Bases* B = work[j].B;
+    const Slot& S = *work[j].S;
+    if (behind_accum) H2_HIP(S.accum.wait(t));
+    tb.d[j] = tail_desc(B, S);
+    none_folds = none_folds && tb.d[j].no_fold != 0;
+    max_tasks1 = std::max(max_tasks1, S.tasks1);
+    max_nb = std::max(max_nb, B->nb);
+    max_logNh = std::max(max_logNh, B->logNh);
+    max_logNl = std::max(max_logNl, B->logNl);
+    max_seg = std::max(max_seg, B->seg_log);
+  }
+  pad_descs(tb.d, count);
+  // fold / finish: quads (4 lanes per point operation) while the grid stays latency-bound, single lanes beyond
+  if (none_folds) {
+    // no fold level at all
+  } else if ((uint64_t)max_tasks1 * count <= 65536) {
+    H2_LAUNCH("k_msm_fold", k_msm_fold<true>, dim3(ceil_div_u32((uint64_t)max_tasks1 * 4, 256), count), 256, 0, t, tb);
+  } else {
+    H2_LAUNCH("k_msm_fold", k_msm_fold<false>, dim3(ceil_div_u32(max_tasks1, 256), count), 256, 0, t, tb);
+  }
+  const uint32_t hot_blocks = ceil_div_u32(max_nb, 256);  // hot-bucket finishers: the first workgroups of the finish launch
+  const size_t hot_lds = 64 * PART_BYTES;
+  if (max_seg) {
+    H2_LAUNCH("k_msm_finish", (k_msm_finish<false, FG_WIDE>), dim3(hot_blocks + ceil_div_u32((uint64_t)max_nb * FG_WIDE, 256), count), 256, hot_lds, t, tb, hot_blocks);
+  } else if ((uint64_t)max_nb * FG_NARROW * count <= 65536) {
+    H2_LAUNCH("k_msm_finish", (k_msm_finish<true, FG_NARROW>), dim3(hot_blocks + ceil_div_u32((uint64_t)max_nb * FG_NARROW * 4, 256), count), 256, hot_lds, t, tb,
+              hot_blocks);
+  } else {
+    H2_LAUNCH("k_msm_finish", (k_msm_finish<false, FG_NARROW>), dim3(hot_blocks + ceil_div_u32((uint64_t)max_nb * FG_NARROW, 256), count), 256, hot_lds, t, tb,
+              hot_blocks);
+  }
+  if (max_seg) H2_LAUNCH("k_msm_seg", k_msm_seg, dim3((4u << MAT_LOG) / 256, count), 256, 0, t, tb);
+  H2_LAUNCH("k_msm_rowcol", k_msm_rowcol, dim3(((max_seg ? 2u : 1u) << max_logNh) + (1u << max_logNl), count), TAIL_THREADS, 256 * PART_BYTES, t, tb);
+  H2_LAUNCH("k_msm_weighted", k_msm_weighted, dim3(max_logNh + max_logNl + 1 + (max_seg ? 1 : 0), count), TAIL_THREADS, 256 * PART_BYTES, t, tb);
+  H2_LAUNCH("k_msm_final", k_msm_final, count, 128, 32 * PART_BYTES, t, tb);
+  return H2MI_OK;
+}
+
+static SmallDesc small_desc(const Bases* B, const Slot& S) {
+  SmallDesc d;
+  d.dig = S.sdig; d.table = B->stable; d.part = S.spart; d.cnt = S.scnt; d.ticket_at = B->sG; d.out = (uint8_t*)S.d_out; d.stats = S.stats;
+  d.n = S.small_n; d.n_reg = (uint32_t)B->n; d.W = B->sW; d.c = B->sc; d.r = B->sr; d.lanes = B->slanes; d.canonical = g_canonical ? 1u : 0u;
+  d.G = ceil_div_u32((uint64_t)d.n * d.W, (uint64_t)d.lanes * d.r);  // <= B->sG: an MSM over the first n <= n_reg bases
+  return d;
+}
+
+// the accumulate + final pairs of `count` <= SMALL_BATCH small-path MSMs as one launch on t (behind their digit kernels in stream order)
+static int launch_small(const Deferred* work, uint32_t count, hipStream_t t) {
+  SmallBatch sb;
+  uint32_t max_parts = 0;
+  for (uint32_t j = 0; j < count; j++) {
+    sb.d[j] = small_desc(work[j].B, *work[j].S);
+    max_parts = std::max(max_parts, sb.d[j].G);
+  }
+  pad_descs(sb.d, count);
+  constexpr size_t LDS = (size_t)SMALL_PARTS_MAX * PART_BYTES;  // 72 KB: above the 64 KB a kernel gets without asking
+  static bool attr_set_dev[16] = {};  // function attributes are per device (every shard of a sharded handle launches these)
+  bool& attr_set = attr_set_dev[ctx().cur & 15];
+  if (!attr_set) {
+    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_small_accum), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
+    attr_set = true;
+  }
+  H2_LAUNCH("k_msm_small_accum", k_msm_small_accum, dim3(max_parts, count), SMALL_THREADS, LDS, t, sb);
+  return H2MI_OK;
+}
+
+// Launches the reductions of work[0 .. n), all of one kind (`small`: the small path's pairs), on t in batches of what one launch
+// takes, and marks each launched: the one place a slot's tail event is recorded.
+static int run_reductions(const Deferred* work, size_t n, bool small, hipStream_t t, bool behind_accum) {
+  const size_t cap = small ? SMALL_BATCH : TAIL_BATCH;
+  for (size_t i = 0; i < n; i += cap) {
+    const uint32_t count = (uint32_t)std::min(cap, n - i);
+    int rc = small ? launch_small(work + i, count, t) : launch_tails(work + i, count, t, behind_accum);
+    if (rc) return rc;
+    for (uint32_t j = 0; j < count; j++) H2_HIP(work[i + j].S->reduction_launched(t));
+  }
+  return H2MI_OK;
+}
+
+// launch the deferred reductions (all handles) as batches on the tail stream
+static int flush_tails() {
+  if (g_deferred.empty()) return H2MI_OK;
+  const int prev = ctx().cur;
+  // the reductions of a device run on that device's tail stream, batched per device
+  for (int dev = 0; dev < (int)ctx().devs.size(); dev++) {
+    // three kinds of deferred work, each batched with its own kind: the small path's accumulate + final pairs, and the bucket
+    // reductions of narrow and of wide windows (a wide descriptor in a batch used to switch every member to the two-lane
+    // finish: correct, but a silent latency cliff for mixed-size commitment streams — round-3 ADVICE)
+    std::vector<Deferred> group[3];
+    for (const Deferred& d : g_deferred)
+      if (d.B->dev == dev) group[d.S->small_deferred ? 0 : d.B->seg_log ? 2 : 1].push_back(d);
+    if (group[0].empty() && group[1].empty() && group[2].empty()) continue;
+    int rc = use_device(dev);
+    if (rc) return rc;
+    // the small path's pair runs on the device's LIBRARY stream, behind the digit kernels that were queued there: a
+    // cross-stream hop costs ~10 us each way (event record -> wait -> launch, measured: 26 us of gaps around 81 us of
+    // kernels), more than these kernels could ever gain from running beside the stream's other work
+    rc = run_reductions(group[0].data(), group[0].size(), /*small=*/true, ctx().stream, /*behind_accum=*/false);
+    for (int gi = 1; gi < 3 && !rc; gi++) rc = run_reductions(group[gi].data(), group[gi].size(), /*small=*/false, ctx().tail_stream, /*behind_accum=*/true);
+    if (rc) return rc;
+  }
+  g_deferred.clear();
+  return use_device(prev);
+}
+
+// ---- slots: rotation and deferral -----------------------------------------------------------------------------------
+// The next slot of the handle's ring.  If its previous reduction is still deferred, every slot of the handle is waiting for its
+// reduction: they are launched first.
+static int acquire_slot(Bases* B, Slot*& S) {
+  S = &B->slot[B->next_slot];
+  B->last_slot = B->next_slot;
+  B->next_slot = (B->next_slot + 1) % B->nslot;
+  return S->tail_deferred ? flush_tails() : H2MI_OK;
+}
+
+// The reductions of the m MSMs just queued (one handle), in order on s itself, or — `deferred` — left to flush_tails(), which
+// runs them for every MSM queued since the last join.
+static int reduce_or_defer(const Deferred* work, size_t m, bool small, bool deferred, hipStream_t s) {
+  if (!deferred) return run_reductions(work, m, small, s, /*behind_accum=*/false);
+  for (size_t j = 0; j < m; j++) {
+    work[j].S->tail_deferred = true;
+    work[j].S->small_deferred = small;
+    g_deferred.push_back(work[j]);
+  }
+  // half the slots: the reductions of one half run beside the accumulation of the other
+  if (g_deferred.size() >= (size_t)std::max(1, work[0].B->nslot / 2)) return flush_tails();
+  return H2MI_OK;
+}
+
+// On the library's own stream an MSM is split over internal streams and only queues the partition and the accumulation; the
+// latency-bound bucket reduction is deferred to the next join (msm_join_all: h2mi_join / h2mi_sync / h2mi_memcpy_d2h), a full
+// batch, or the reuse of the slot.  On a caller-provided stream everything runs in order on that stream.
+// `inorder`: partition, accumulation and bucket reduction one after the other on `s`, nothing deferred and no stream hops — for a LONE
+// commitment whose point the caller reads next (h2mi_msm_bn254_g1_phase_dev with H2MI_MSM_INORDER): the three-stream split buys overlap between consecutive
+// MSMs and costs a lone one ~50 us of event hops (2^20: 1645 -> 1580 us, 2^16: 386 -> 336)
+static bool pipelined(hipStream_t s, bool inorder) { return !inorder && s == ctx().stream && ctx().tail_stream && !getenv("H2MI_MSM_NO_PIPELINE"); }
+
+// ---- small base sets: host side ---------------------------------------------------------------------------------
+// m MSMs over the first n bases of a small base set, results to d_out + 96 j.  The digit kernel runs on the caller's stream (it is
+// the only reader of the scalars: work queued on s afterwards may overwrite them); on the library stream the accumulate + final
+// pair is deferred to the next join / flush and batched with the other small MSMs of the phase, on a caller's stream or `inorder`
+// it follows at once (on the small path the pair runs on `s` anyway: nothing to defer for).
+// `batch` (the phase entry's groups, library stream only): one digit launch for the m MSMs; else m = 1 and the plain kernel.
+static int msm_small(Bases* B, const void* const* d_scalars, size_t m, size_t n, void* d_out, hipStream_t s, bool inorder, bool batch) {
+  const bool deferred = pipelined(s, inorder);
+  Deferred work[HEAD_BATCH];
+  SmallHeadBatch hb;
+  for (size_t j = 0; j < m; j++) {
+    Slot* slot;
+    int rc = acquire_slot(B, slot);
+    if (rc) return rc;
+    Slot& S = *slot;
+    // slot reuse: the digit bytes and partial sums are read by the slot's previous accumulate / final pair — and a slot last
+    // used by the general pipeline (H2MI_MSM_GENERAL, or the streaming rule of take_small) still owes its head / accumulation events
+    // (the single form off the pipeline always waits for a recorded tail; the batch form, which only runs on the library stream, does not)
+    if (S.tail.ever && (S.tail.pending || (!deferred && !batch) || S.last_stream != s)) H2_HIP(S.tail.wait(s));
+    H2_HIP(S.head.wait_if_pending(s));
+    H2_HIP(S.accum.wait_if_pending(s));
+    S.clear_pending();
+    S.last_stream = s;
+    S.d_out = (char*)d_out + 96 * j;
+    S.small_n = (uint32_t)n;
+    hb.scalars[j] = (const fe*)d_scalars[j];
+    hb.dig[j] = S.sdig;
+    work[j] = {B, &S};
+  }
+  if (batch) {
+    pad_descs(hb.scalars, m);
+    pad_descs(hb.dig, m);
+    H2_LAUNCH("k_msm_small_digits", k_msm_small_digits_b, dim3(ceil_div_u32(n, 64), (uint32_t)m), 64, 0, s, hb, (uint32_t)n, (uint32_t)B->n, B->sc, B->sW);
+  } else {
+    H2_LAUNCH("k_msm_small_digits", k_msm_small_digits, ceil_div_u32(n, 64), 64, 0, s, hb.scalars[0], (uint32_t)n, (uint32_t)B->n, B->sc, B->sW, hb.dig[0]);
+  }
+  if (deferred)
+    for (size_t j = 0; j < m; j++) H2_HIP(work[j].S->accum.record(s));  // "inputs consumed": what the deferred pair waits for
+  return reduce_or_defer(work, m, /*small=*/true, deferred, s);
+}
+
+// ---- general pipeline: host side ----------------------------------------------------------------------------------
+// m MSMs of n scalars each over B, results to d_out + 96 j.
+// Plain form (m = 1): streams: caller-provided stream, `inorder` or H2MI_MSM_NO_PIPELINE => everything in order on s.  Library stream => three stages:
+//   s : partition level 1: bin count, offsets, scatter (the only readers of the caller's scalars)
+//   hs: partition level 2 (per-bin sort, bucket tables), task offsets
+//   as: accumulation                   (never blocks s: NTTs queued on s meanwhile run beside it)
+//   tail stream: fold ... final, batched over the MSMs since the last join (flush_tails)
+// `batch` (m <= HEAD_BATCH, the phase entry's groups: narrow windows, library stream only): what m plain calls would compute, with
+// the partition and the accumulation of all m as ONE set of launches.  Slots, events and the deferred bucket reductions are those of m
+// single calls.  `inorder` there (the batch is all its phase commits and is read back next): everything, the bucket reductions included, on `s` itself.
+static int msm_general(Bases* B, const void* const* d_scalars, size_t m, size_t n, void* d_out, hipStream_t s, bool inorder, bool batch) {
+  const uint32_t nb = B->nb, W = B->W, mm = (uint32_t)m;
+  // dominant-value shift: only when the MSM covers every registered base (the extra base is their sum)
+  const bool shifted = B->has_sum && n == B->n;
+  const size_t n_eff = n + (shifted ? 1 : 0);
+  const uint32_t total = (uint32_t)(n_eff * W), ntiles = ceil_div_u32(n_eff, P1_TS);
+  // chunk length: chosen by k_msm_bin_sort from the entry count unless H2MI_MSM_S0 fixes it; the partial buffers
+  // were sized at registration, so an override must not produce more chunks than they hold
+  uint32_t s0_fixed = chunk_override();
+  while (s0_fixed && s0_fixed < S0_MAX && ((uint64_t)total + s0_fixed - 1) / s0_fixed + nb > B->max_tasks0) s0_fixed++;
+  if (s0_fixed && ((uint64_t)total + s0_fixed - 1) / s0_fixed + nb > B->max_tasks0) return H2MI_ERANGE;
+  if ((size_t)P1_TS * W * 6 > (size_t)SCATTER_LDS_MAX) return H2MI_ERANGE;
+  // upper bound of the chunks (zero digits leave no entry): whole rounds of the resident grid, or total / override
+  // (a chunk holds at least one entry: small base sets never come near a whole round)
+  const uint32_t chunks0 = s0_fixed ? (uint32_t)(((uint64_t)total + s0_fixed - 1) / s0_fixed) : std::min(accum_rounds(total) * ACCUM_RESIDENT_CHUNKS, total);
+  const uint32_t tasks0 = chunks0 + nb;  // upper bound of the partial sums
+  const bool deferred = pipelined(s, inorder);
+  // the slots follow the library-stream protocol (wait for what is pending, record every stage) when the reductions are deferred,
+  // and in the batch form even `inorder`: it only ever runs on the library stream, which every join orders behind the slots' events
+  const bool staged = deferred || batch;
+  // the batch form runs the second partition level and the accumulation on ONE stream: the separate accumulation stream exists so that the next
+  // MSM's partition overlaps this one's accumulation, which a batch does not need — and a stream hop is ~10 us on the phase's critical path
+  const hipStream_t hs = deferred ? ctx().head_stream : s, as = !deferred ? s : batch ? hs : ctx().accum_stream;
+  Deferred work[HEAD_BATCH];
+  HeadBatch hb;
+  for (size_t j = 0; j < m; j++) {
+    Slot* slot;
+    int rc = acquire_slot(B, slot);  // (a flush here never launches one of this group: m <= nslot)
+    if (rc) return rc;
+    Slot& S = *slot;
+    if (staged) {
+      // the first partition level (count, scan, scatter) is the only reader of the caller's scalars and stays
+      // on s.  It writes bincnt/binbase/bkeys/vals[0], last read by this slot's previous k_msm_bin_sort.
+      H2_HIP(S.head.wait_if_pending(s));
+      // the slot's previous MSM ran start to end on a caller's stream: its last kernel recorded the tail event there
+      if (S.tail.pending && S.last_stream != s) H2_HIP(S.tail.wait(s));
+    } else {
+      // a caller's stream is ordered against nothing the library did on its own streams (h2mi_join only makes the
+      // library stream wait), so it waits for every event this slot has ever recorded; a completed event is free
+      H2_HIP(S.head.wait_if_ever(s));
+      H2_HIP(S.accum.wait_if_ever(s));
+      H2_HIP(S.tail.wait_if_ever(s));
+    }
+    S.last_stream = s;
+    S.d_out = (char*)d_out + 96 * j;
+    S.tasks1 = tasks0 / S1 + nb;  // the reduction's fold grid bound
+    work[j] = {B, &S};
+    if (batch) {
+      HeadDesc& d = hb.d[j];
+      d.scalars = (const fe*)d_scalars[j];
+      d.shift = shifted ? S.shift : nullptr;
+      d.bincnt = S.bincnt; d.tile_live = S.tile_live; d.binseg = S.binseg; d.binbase = S.binbase;
+      d.vals0 = S.vals[0]; d.vals1 = S.vals[1]; d.bkeys = S.bkeys;
+      d.off = S.off; d.np0 = S.np[0]; d.np1 = S.np[1]; d.toff0 = S.toff[0]; d.toff1 = S.toff[1]; d.s0_dev = S.s0_dev;
+      d.part0 = S.part[0];
+    }
+  }
+  Slot& S0 = *work[0].S;
+  if (batch) pad_descs(hb.d, m);
+  int rc = batch ? launch_level1_b(B, hb, mm, n, shifted, ntiles, s) : launch_level1(B, S0, (const fe*)d_scalars[0], n, shifted, ntiles, s);
+  if (rc) return rc;
+  // one event for the group's inputs; the slots' own events for what later calls wait on per slot
+  if (hs != s) {
+    H2_HIP(S0.input_ready.record(s));
+    H2_HIP(S0.input_ready.wait(hs));
+  }
+  for (size_t j = 0; j < m; j++) {
+    Slot& S = *work[j].S;
+    if (staged) {
+      // slot reuse: the sorted buffers are read by this slot's previous accumulation, the partial buffers and
+      // bucket offsets by its previous tail
+      H2_HIP(S.accum.wait_if_pending(hs));
+      H2_HIP(S.tail.wait_if_pending(hs));
+    }
+    S.clear_pending();
+  }
+  rc = batch ? launch_level2_b(B, hb, mm, ntiles, s0_fixed, hs) : launch_level2(B, S0, ntiles, s0_fixed, hs);
+  if (rc) return rc;
+  if (staged) {
+    for (size_t j = 0; j < m; j++) H2_HIP(work[j].S->head.record(hs));
+    if (as != hs) H2_HIP(work[m - 1].S->head.wait(as));
+  }
+  if (batch) {
+    H2_LAUNCH("k_msm_accum", k_msm_accum_b, dim3(ceil_div_u32(chunks0, 256), mm), 256, ACCUM_LDS, as, hb, nb, (const uint8_t*)B->table);
+  } else {
+    H2_LAUNCH("k_msm_accum", k_msm_accum, ceil_div_u32(chunks0, 256), 256, ACCUM_LDS, as, (const uint32_t*)S0.vals[1], (const uint32_t*)S0.off,
+              (const uint32_t*)S0.toff[0], nb, (const uint32_t*)S0.s0_dev, (const uint8_t*)B->table, S0.part[0]);
+  }
+  if (staged)  // (the batch form records it `inorder` too, where the tail event that follows on the same stream covers it)
+    for (size_t j = 0; j < m; j++) H2_HIP(work[j].S->accum.record(as));
+  return reduce_or_defer(work, m, /*small=*/false, deferred, s);
+}
+
+// Which pipeline the next MSM of a base set with a digit-multiples table takes: see SMALL_STREAM_N
+static bool take_small(const Bases* B, bool general) {
+  return B->small && !general && !(B->n > SMALL_STREAM_N && B->since_join >= SMALL_STREAM_AFTER);
+}
+constexpr size_t HEAD_BATCH_MAX_N = (size_t)1 << 17;  // largest base set whose MSMs are partitioned and accumulated as a batch
+// m MSMs over one base set, issued together: one path for the group (a long phase crosses the streaming threshold of take_small
+// on its way, group by group).  `batch`: the forms that launch all m heads at once (msm_batch_entry); else m = 1.
+static int msm_group(Bases* B, const void* const* d_scalars, size_t m, size_t n, void* d_out, hipStream_t s, bool inorder, bool general, bool batch) {
+  B->last_small = take_small(B, general);
+  B->since_join += (uint32_t)m;
+  return B->last_small ? msm_small(B, d_scalars, m, n, d_out, s, inorder, batch) : msm_general(B, d_scalars, m, n, d_out, s, inorder, batch);
+}
+static int msm_dev(Bases* B, const void* d_scalars, size_t n, void* d_out, hipStream_t s, bool inorder = false, bool general = false) {
+  return msm_group(B, &d_scalars, 1, n, d_out, s, inorder, general, /*batch=*/false);
 }
 
 #define H2_ALLOC(ptr, bytes)                                   \
@@ -1413,8 +1899,6 @@ static void free_bases(Bases* B) {
       return e_ == hipErrorOutOfMemory ? H2MI_ENOMEM : H2MI_EHIP; \
     }                                                          \
   } while (0)
-
-static int msm_dev(Bases* B, const void* d_scalars, size_t n, void* d_out, hipStream_t s, bool inorder = false, bool general = false);
 
 static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hipStream_t s, bool allow_small = true) {
   if (n == 0 || n > ((size_t)1 << 26)) return H2MI_ERANGE;
@@ -1469,10 +1953,7 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
     H2_ALLOC(S.g, (size_t)64 * PART_BYTES);
     H2_ALLOC(S.stats, 64);
     H2_ALLOC(S.shift, 32);
-    if (hipEventCreateWithFlags(&S.input_ready, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&S.head_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&S.accum_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&S.tail_done, hipEventDisableTiming) != hipSuccess) {
+    if (S.create_events() != hipSuccess) {
       free_bases(B);
       return H2MI_EHIP;
     }
@@ -1564,10 +2045,6 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
   return H2MI_OK;
 }
 
-struct Deferred {
-  Bases* B;
-  Slot* S;
-};
 // ---- one prover process, several devices (h2mi_init_devices) ---------------------------------------------------
 // A sharded handle owns one ordinary registration per device, each over a contiguous slice of the bases — the
 // partition best_multiexp applies per CPU thread and the torchrun path applies per rank.  An MSM
@@ -1594,564 +2071,9 @@ struct PendingFold {
 };
 static std::map<uint64_t, Sharded*> g_sharded;
 static std::vector<PendingFold> g_pending_folds;
-static int fold_sharded(hipStream_t s0);
-static std::vector<Deferred> g_deferred;
-static int flush_tails();
-static int launch_tails(const TailBatch& tb, uint32_t count, uint32_t max_tasks1, uint32_t max_nb, uint32_t max_logNh, uint32_t max_logNl,
-                        uint32_t max_seg, hipStream_t t);
-static TailDesc tail_desc(const Bases* B, const Slot& S);
 
-// One MSM.  On the library's own stream the call is split over internal streams and only queues the
-// partition and the accumulation; the latency-bound bucket reduction is deferred to the next join
-// (msm_join_all: h2mi_join / h2mi_sync / h2mi_memcpy_d2h), a full batch, or the reuse of the slot.
-// On a caller-provided stream everything runs in order on that stream.
-static int msm_small(Bases* B, const void* d_scalars, size_t n, void* d_out, hipStream_t s, bool inorder = false);
-static bool take_small(const Bases* B, bool general) {
-  return B->small && !general && !(B->n > SMALL_STREAM_N && B->since_join >= SMALL_STREAM_AFTER);
-}
-constexpr size_t HEAD_BATCH_MAX_N = (size_t)1 << 17;  // largest base set whose MSMs are partitioned and accumulated as a batch
-
-// `m` <= HEAD_BATCH MSMs of n scalars each over B, results to d_out + 96 j: what m calls of msm_dev would compute, with the partition
-// and the accumulation of all m as ONE set of launches (narrow windows, library stream).  Slots, events and the deferred bucket
-// reductions are those of m single calls.
-static int msm_dev_batch(Bases* B, const void* const* d_scalars, size_t m, size_t n, void* d_out, hipStream_t s, bool inorder) {
-  const uint32_t nb = B->nb, W = B->W;
-  const bool shifted = B->has_sum && n == B->n;
-  const size_t n_eff = n + (shifted ? 1 : 0);
-  const uint32_t total = (uint32_t)(n_eff * W);
-  // the second partition level and the accumulation share ONE stream here: the separate accumulation stream exists so that the next
-  // MSM's partition overlaps this one's accumulation, which a batch does not need — and a stream hop is ~10 us on the phase's critical path
-  // `inorder` (the batch is all its phase commits and is read back next): everything, the bucket reductions included, on `s` itself
-  hipStream_t hs = inorder ? s : ctx().head_stream, as = hs;
-  uint32_t s0_fixed = chunk_override();
-  while (s0_fixed && s0_fixed < S0_MAX && ((uint64_t)total + s0_fixed - 1) / s0_fixed + nb > B->max_tasks0) s0_fixed++;
-  if (s0_fixed && ((uint64_t)total + s0_fixed - 1) / s0_fixed + nb > B->max_tasks0) return H2MI_ERANGE;
-  if ((size_t)P1_TS * W * 6 > 150 * 1024) return H2MI_ERANGE;
-  Slot* slots[HEAD_BATCH];
-  HeadBatch hb;
-  memset(&hb, 0, sizeof(hb));
-  for (size_t j = 0; j < m; j++) {
-    Slot& S = B->slot[B->next_slot];
-    B->last_slot = B->next_slot;
-    B->next_slot = (B->next_slot + 1) % B->nslot;
-    if (S.tail_deferred) {  // this slot still waits for its reduction (never one of this batch: m <= nslot)
-      int rc = flush_tails();
-      if (rc) return rc;
-    }
-    if (S.head_pending) H2_HIP(hipStreamWaitEvent(s, S.head_done, 0));
-    if (S.tail_pending && S.last_stream != s) H2_HIP(hipStreamWaitEvent(s, S.tail_done, 0));
-    S.last_stream = s;
-    slots[j] = &S;
-    HeadDesc& d = hb.d[j];
-    d.scalars = (const fe*)d_scalars[j];
-    d.shift = shifted ? S.shift : nullptr;
-    d.bincnt = S.bincnt; d.tile_live = S.tile_live; d.binseg = S.binseg; d.binbase = S.binbase;
-    d.vals0 = S.vals[0]; d.vals1 = S.vals[1]; d.bkeys = S.bkeys;
-    d.off = S.off; d.np0 = S.np[0]; d.np1 = S.np[1]; d.toff0 = S.toff[0]; d.toff1 = S.toff[1]; d.s0_dev = S.s0_dev;
-    d.part0 = S.part[0];
-  }
-  for (size_t j = m; j < HEAD_BATCH; j++) hb.d[j] = hb.d[0];  // never launched (gridDim.y = m)
-  const uint32_t ntiles = ceil_div_u32(n_eff, P1_TS), mm = (uint32_t)m;
-  static bool attr_set_dev[16] = {};  // function attributes are per device (every shard of a sharded handle launches these)
-  bool& attr_set = attr_set_dev[ctx().cur & 15];
-  if (!attr_set) {
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter_b<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter_b<13>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter_b<15>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter_b<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter_b<17>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    attr_set = true;
-  }
-#define H2_BIN_COUNT_B(CT) H2_LAUNCH("k_msm_bin_count", k_msm_bin_count_b<CT>, dim3(ntiles, mm), P1_TS, 0, s, hb, n, B->c, W, B->lb, B->nbins, ntiles)
-#define H2_BIN_SCATTER_B(CT) \
-  H2_LAUNCH("k_msm_bin_scatter", k_msm_bin_scatter_b<CT>, dim3(ntiles, mm), P1_TS, (size_t)P1_TS * W * 6, s, hb, n, B->stride, B->c, W, B->lb, B->nbins, ntiles)
-  if (shifted) H2_LAUNCH("k_msm_pick_shift", k_msm_pick_shift_b, dim3(1, mm), 64, 0, s, hb, n);
-  switch (B->c) {
-    case 13: H2_BIN_COUNT_B(13); break;
-    case 15: H2_BIN_COUNT_B(15); break;
-    case 16: H2_BIN_COUNT_B(16); break;
-    case 17: H2_BIN_COUNT_B(17); break;
-    default: H2_BIN_COUNT_B(0); break;
-  }
-  const uint32_t cells = B->nbins * ntiles;
-  const uint32_t nseg = ceil_div_u32(cells, SCAN_SEG_BINS);
-  if (nseg > 1) H2_LAUNCH("k_scan_segsum", k_scan_segsum_bins_b, dim3(nseg, mm), 1024, 0, s, hb, cells);
-  H2_LAUNCH("k_scan_seg_bins", k_scan_seg_bins_b, dim3(nseg, mm), 1024, 0, s, hb, cells);
-  switch (B->c) {
-    case 13: H2_BIN_SCATTER_B(13); break;
-    case 15: H2_BIN_SCATTER_B(15); break;
-    case 16: H2_BIN_SCATTER_B(16); break;
-    case 17: H2_BIN_SCATTER_B(17); break;
-    default: H2_BIN_SCATTER_B(0); break;
-  }
-#undef H2_BIN_COUNT_B
-#undef H2_BIN_SCATTER_B
-  // one event for the batch's inputs; the slots' own events for what later calls wait on per slot
-  if (hs != s) {
-    H2_HIP(hipEventRecord(slots[0]->input_ready, s));
-    H2_HIP(hipStreamWaitEvent(hs, slots[0]->input_ready, 0));
-  }
-  for (size_t j = 0; j < m; j++) {
-    Slot& S = *slots[j];
-    if (S.accum_pending) H2_HIP(hipStreamWaitEvent(hs, S.accum_done, 0));
-    if (S.tail_pending) H2_HIP(hipStreamWaitEvent(hs, S.tail_done, 0));
-    S.tail_pending = S.accum_pending = S.head_pending = false;
-  }
-  H2_LAUNCH("k_msm_bin_sort", k_msm_bin_sort_b, dim3(B->nbins, mm), P2_THREADS, 0, hs, hb, ntiles, B->nbins, B->lb, s0_fixed, nb);
-  H2_LAUNCH("k_scan_seg_tasks", k_scan_seg_tasks_b, dim3(1, 2, mm), 1024, 0, hs, hb, nb);
-  const uint32_t chunks0 = s0_fixed ? (uint32_t)(((uint64_t)total + s0_fixed - 1) / s0_fixed) : std::min(accum_rounds(total) * ACCUM_RESIDENT_CHUNKS, total);
-  const uint32_t tasks0 = chunks0 + nb;
-  for (size_t j = 0; j < m; j++) {
-    H2_HIP(hipEventRecord(slots[j]->head_done, hs));
-    slots[j]->head_pending = true;
-    slots[j]->head_ever = true;
-  }
-  if (as != hs) H2_HIP(hipStreamWaitEvent(as, slots[m - 1]->head_done, 0));
-  H2_LAUNCH("k_msm_accum", k_msm_accum_b, dim3(ceil_div_u32(chunks0, 256), mm), 256, ACCUM_LDS, as, hb, nb, (const uint8_t*)B->table);
-  for (size_t j = 0; j < m; j++) {
-    Slot& S = *slots[j];
-    S.d_out = (char*)d_out + 96 * j;
-    S.tasks1 = tasks0 / S1 + nb;
-    H2_HIP(hipEventRecord(S.accum_done, as));
-    S.accum_pending = true;
-    S.accum_ever = true;
-    if (!inorder) {
-      S.tail_deferred = true;
-      g_deferred.push_back({B, &S});
-    }
-  }
-  if (inorder) {  // the batch's own reductions at once, behind its accumulation on the same stream
-    TailBatch tb;
-    for (size_t j = 0; j < m; j++) tb.d[j] = tail_desc(B, *slots[j]);
-    for (size_t j = m; j < TAIL_BATCH; j++) tb.d[j] = tb.d[0];
-    int rc = launch_tails(tb, mm, slots[0]->tasks1, nb, B->logNh, B->logNl, B->seg_log, s);
-    if (rc) return rc;
-    for (size_t j = 0; j < m; j++) {
-      Slot& S = *slots[j];
-      H2_HIP(hipEventRecord(S.tail_done, s));
-      S.tail_pending = true;
-      S.tail_ever = true;
-    }
-    return H2MI_OK;
-  }
-  if (g_deferred.size() >= (size_t)std::max(1, B->nslot / 2)) return flush_tails();
-  return H2MI_OK;
-}
-
-// the small path's batch: one digit launch for the m MSMs; their accumulate / final pair is deferred and batched as ever
-static SmallDesc small_desc(const Bases* B, const Slot& S);
-static int launch_small(const SmallBatch& sb, uint32_t count, uint32_t max_parts, hipStream_t t);
-static int msm_small_batch(Bases* B, const void* const* d_scalars, size_t m, size_t n, void* d_out, hipStream_t s, bool inorder) {
-  SmallHeadBatch hb;
-  memset(&hb, 0, sizeof(hb));
-  Slot* slots[HEAD_BATCH];
-  for (size_t j = 0; j < m; j++) {
-    Slot& S = B->slot[B->next_slot];
-    B->last_slot = B->next_slot;
-    B->next_slot = (B->next_slot + 1) % B->nslot;
-    if (S.tail_deferred) {
-      int rc = flush_tails();
-      if (rc) return rc;
-    }
-    if (S.tail_ever && (S.tail_pending || S.last_stream != s)) H2_HIP(hipStreamWaitEvent(s, S.tail_done, 0));
-    if (S.head_pending) H2_HIP(hipStreamWaitEvent(s, S.head_done, 0));
-    if (S.accum_pending) H2_HIP(hipStreamWaitEvent(s, S.accum_done, 0));
-    S.tail_pending = S.accum_pending = S.head_pending = false;
-    S.last_stream = s;
-    S.d_out = (char*)d_out + 96 * j;
-    S.small_n = (uint32_t)n;
-    hb.scalars[j] = (const fe*)d_scalars[j];
-    hb.dig[j] = S.sdig;
-    slots[j] = &S;
-  }
-  for (size_t j = m; j < HEAD_BATCH; j++) { hb.scalars[j] = hb.scalars[0]; hb.dig[j] = hb.dig[0]; }
-  H2_LAUNCH("k_msm_small_digits", k_msm_small_digits_b, dim3(ceil_div_u32(n, 64), (uint32_t)m), 64, 0, s, hb, (uint32_t)n, (uint32_t)B->n, B->sc, B->sW);
-  if (inorder) {  // accumulate + final for the batch at once (on the small path they run on `s` anyway: nothing to defer for)
-    SmallBatch sb;
-    uint32_t max_parts = 0;
-    for (size_t j = 0; j < m; j++) {
-      sb.d[j] = small_desc(B, *slots[j]);
-      max_parts = std::max(max_parts, sb.d[j].G);
-    }
-    for (size_t j = m; j < SMALL_BATCH; j++) sb.d[j] = sb.d[0];
-    int rc = launch_small(sb, (uint32_t)m, max_parts, s);
-    if (rc) return rc;
-    for (size_t j = 0; j < m; j++) {
-      Slot& S = *slots[j];
-      H2_HIP(hipEventRecord(S.tail_done, s));
-      S.tail_pending = true;
-      S.tail_ever = true;
-    }
-    return H2MI_OK;
-  }
-  for (size_t j = 0; j < m; j++) {
-    Slot& S = *slots[j];
-    H2_HIP(hipEventRecord(S.accum_done, s));  // "inputs consumed": what the deferred pair waits for
-    S.accum_pending = true;
-    S.accum_ever = true;
-    S.tail_deferred = true;
-    S.small_deferred = true;
-    g_deferred.push_back({B, &S});
-  }
-  if (g_deferred.size() >= (size_t)std::max(1, B->nslot / 2)) return flush_tails();
-  return H2MI_OK;
-}
-
-// `inorder`: partition, accumulation and bucket reduction one after the other on `s`, nothing deferred and no stream hops — for a LONE
-// commitment whose point the caller reads next (h2mi_msm_bn254_g1_phase_dev with H2MI_MSM_INORDER): the three-stream split buys overlap between consecutive
-// MSMs and costs a lone one ~50 us of event hops (2^20: 1645 -> 1580 us, 2^16: 386 -> 336)
-static int msm_dev(Bases* B, const void* d_scalars, size_t n, void* d_out, hipStream_t s, bool inorder, bool general) {
-  B->last_small = take_small(B, general);
-  B->since_join++;
-  if (B->last_small) return msm_small(B, d_scalars, n, d_out, s, inorder);
-  const uint32_t nb = B->nb, W = B->W;
-  // dominant-value shift: only when the MSM covers every registered base (the extra base is their sum)
-  const bool shifted = B->has_sum && n == B->n;
-  const size_t n_eff = n + (shifted ? 1 : 0);
-  const uint32_t total = (uint32_t)(n_eff * W);
-  const bool pipelined = !inorder && (s == ctx().stream) && ctx().tail_stream && !getenv("H2MI_MSM_NO_PIPELINE");
-  Slot& S = B->slot[B->next_slot];
-  B->last_slot = B->next_slot;
-  B->next_slot = (B->next_slot + 1) % B->nslot;
-  if (S.tail_deferred) {  // every slot of this handle is waiting for its reduction
-    int rc = flush_tails();
-    if (rc) return rc;
-  }
-  // streams: caller-provided stream => everything in order on it.  Library stream => three stages:
-  //   s : partition level 1: bin count, offsets, scatter (the only readers of the caller's scalars)
-  //   hs: partition level 2 (per-bin sort, bucket tables), task offsets
-  //   as: accumulation                   (never blocks s: NTTs queued on s meanwhile run beside it)
-  //   tail stream: fold ... final, batched over the MSMs since the last join (flush_tails)
-  hipStream_t hs = s, as = s;
-  // chunk length: chosen by k_msm_bin_sort from the entry count unless H2MI_MSM_S0 fixes it; the partial buffers
-  // were sized at registration, so an override must not produce more chunks than they hold
-  uint32_t s0_fixed = chunk_override();
-  while (s0_fixed && s0_fixed < S0_MAX && ((uint64_t)total + s0_fixed - 1) / s0_fixed + nb > B->max_tasks0) s0_fixed++;
-  if (s0_fixed && ((uint64_t)total + s0_fixed - 1) / s0_fixed + nb > B->max_tasks0) return H2MI_ERANGE;
-  if (pipelined) {
-    hs = ctx().head_stream;
-    as = ctx().accum_stream;
-    // the first partition level (count, scan, scatter) is the only reader of the caller's scalars and stays
-    // on s.  It writes bincnt/binbase/bkeys/vals[0], last read by this slot's previous k_msm_bin_sort.
-    if (S.head_pending) H2_HIP(hipStreamWaitEvent(s, S.head_done, 0));
-    // the slot's previous MSM ran start to end on a caller's stream: its last kernel recorded tail_done there
-    if (S.tail_pending && S.last_stream != s) H2_HIP(hipStreamWaitEvent(s, S.tail_done, 0));
-  } else {
-    // a caller's stream is ordered against nothing the library did on its own streams (h2mi_join only makes the
-    // library stream wait), so it waits for every event this slot has ever recorded; a completed event is free
-    if (S.head_ever) H2_HIP(hipStreamWaitEvent(s, S.head_done, 0));
-    if (S.accum_ever) H2_HIP(hipStreamWaitEvent(s, S.accum_done, 0));
-    if (S.tail_ever) H2_HIP(hipStreamWaitEvent(s, S.tail_done, 0));
-  }
-  S.last_stream = s;
-  const uint32_t ntiles = ceil_div_u32(n_eff, P1_TS);
-  const fe* shift = shifted ? S.shift : nullptr;
-  static bool attr_set_dev[16] = {};  // function attributes are per device (every shard of a sharded handle launches these)
-  bool& attr_set = attr_set_dev[ctx().cur & 15];
-  if ((size_t)P1_TS * W * 6 > 150 * 1024) return H2MI_ERANGE;
-  if (!attr_set) {  // the scatter kernel stages up to 144 KiB of pairs in LDS (W = 24; 90 KiB at W = 15)
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter<13>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter<15>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter<17>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter<18>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter<19>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_bin_scatter<20>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    attr_set = true;
-  }
-  {
-    // the partition's first level reads the scalars twice (count, scatter): both stay on s, so work queued
-    // on s after this call may overwrite them
-#define H2_BIN_COUNT(CT) \
-  H2_LAUNCH("k_msm_bin_count", k_msm_bin_count<CT>, ntiles, P1_TS, 0, s, (const fe*)d_scalars, n, shift, B->c, W, B->lb, B->nbins, ntiles, S.bincnt, S.tile_live)
-#define H2_BIN_SCATTER(CT)                                                                                                                        \
-  H2_LAUNCH("k_msm_bin_scatter", k_msm_bin_scatter<CT>, ntiles, P1_TS, (size_t)P1_TS * W * 6, s, (const fe*)d_scalars, n, shift, B->stride, B->c, W, \
-            B->lb, B->nbins, ntiles, (const uint32_t*)S.binbase, S.vals[0], S.bkeys, (const uint32_t*)S.tile_live)
-    if (shifted) H2_LAUNCH("k_msm_pick_shift", k_msm_pick_shift, 1, 64, 0, s, (const fe*)d_scalars, n, S.shift);
-    switch (B->c) {
-      case 13: H2_BIN_COUNT(13); break;
-      case 15: H2_BIN_COUNT(15); break;
-      case 16: H2_BIN_COUNT(16); break;
-      case 17: H2_BIN_COUNT(17); break;
-      case 18: H2_BIN_COUNT(18); break;
-      case 19: H2_BIN_COUNT(19); break;
-      case 20: H2_BIN_COUNT(20); break;
-      default: H2_BIN_COUNT(0); break;
-    }
-    const uint32_t cells = B->nbins * ntiles;  // a multiple of 4 (checked at registration)
-    const uint32_t nseg = ceil_div_u32(cells, SCAN_SEG_BINS);
-    if (nseg > 1) H2_LAUNCH("k_scan_segsum", k_scan_segsum<SCAN_SEG_BINS>, nseg, 1024, 0, s, (const uint32_t*)S.bincnt, cells, S.binseg);
-    H2_LAUNCH("k_scan_seg_bins", k_scan_seg<SCAN_SEG_BINS>, dim3(nseg, 1), 1024, 0, s, (const uint32_t*)S.bincnt, S.binbase, (const uint32_t*)nullptr,
-              (uint32_t*)nullptr, cells, (const uint32_t*)S.binseg);
-    switch (B->c) {
-      case 13: H2_BIN_SCATTER(13); break;
-      case 15: H2_BIN_SCATTER(15); break;
-      case 16: H2_BIN_SCATTER(16); break;
-      case 17: H2_BIN_SCATTER(17); break;
-      case 18: H2_BIN_SCATTER(18); break;
-      case 19: H2_BIN_SCATTER(19); break;
-      case 20: H2_BIN_SCATTER(20); break;
-      default: H2_BIN_SCATTER(0); break;
-    }
-#undef H2_BIN_COUNT
-#undef H2_BIN_SCATTER
-  }
-  if (pipelined) {
-    H2_HIP(hipEventRecord(S.input_ready, s));
-    H2_HIP(hipStreamWaitEvent(hs, S.input_ready, 0));
-    // slot reuse: the sorted buffers are read by this slot's previous accumulation, the partial buffers and
-    // bucket offsets by its previous tail
-    if (S.accum_pending) H2_HIP(hipStreamWaitEvent(hs, S.accum_done, 0));
-    if (S.tail_pending) H2_HIP(hipStreamWaitEvent(hs, S.tail_done, 0));
-  }
-  S.tail_pending = false;
-  S.accum_pending = false;
-  S.head_pending = false;
-  if (B->seg_log) {
-    H2_LAUNCH("k_msm_bin_sort", k_msm_bin_sort_wide, B->nbins, P2_THREADS, 0, hs, (const uint16_t*)S.bkeys, (const uint32_t*)S.vals[0],
-              (const uint32_t*)S.binbase, ntiles, B->nbins, B->lb, s0_fixed, nb, S.vals[1], S.off, S.np[0], S.np[1], S.s0_dev);
-    const uint32_t tsegs = ceil_div_u32(nb, SCAN_SEG_BINS);  // nb > 65536 task counters: segmented, one array per launch
-    for (int i = 0; i < 2; i++) {
-      H2_LAUNCH("k_scan_segsum", k_scan_segsum<SCAN_SEG_BINS>, tsegs, 1024, 0, hs, (const uint32_t*)S.np[i], nb, S.tseg[i]);
-      H2_LAUNCH("k_scan_seg_tasks", k_scan_seg<SCAN_SEG_BINS>, dim3(tsegs, 1), 1024, 0, hs, (const uint32_t*)S.np[i], S.toff[i], (const uint32_t*)nullptr,
-                (uint32_t*)nullptr, nb, (const uint32_t*)S.tseg[i]);
-    }
-  } else {
-    H2_LAUNCH("k_msm_bin_sort", k_msm_bin_sort, B->nbins, P2_THREADS, 0, hs, (const uint8_t*)S.bkeys, (const uint32_t*)S.vals[0],
-              (const uint32_t*)S.binbase, ntiles, B->nbins, B->lb, s0_fixed, nb, S.vals[1], S.off, S.np[0], S.np[1], S.s0_dev);
-    H2_LAUNCH("k_scan_seg_tasks", k_scan_seg<SCAN_SEG_TASKS>, dim3(1, 2), 1024, 0, hs, (const uint32_t*)S.np[0], S.toff[0], (const uint32_t*)S.np[1], S.toff[1], nb,
-              (const uint32_t*)nullptr);
-  }
-  // upper bound of the chunks (zero digits leave no entry): whole rounds of the resident grid, or total / override
-  // (a chunk holds at least one entry: small base sets never come near a whole round)
-  const uint32_t chunks0 = s0_fixed ? (uint32_t)(((uint64_t)total + s0_fixed - 1) / s0_fixed) : std::min(accum_rounds(total) * ACCUM_RESIDENT_CHUNKS, total);
-  const uint32_t tasks0 = chunks0 + nb;                                             // upper bound of the partial sums
-  if (pipelined) {
-    H2_HIP(hipEventRecord(S.head_done, hs));
-    H2_HIP(hipStreamWaitEvent(as, S.head_done, 0));
-    S.head_pending = true;
-    S.head_ever = true;
-  }
-  H2_LAUNCH("k_msm_accum", k_msm_accum, ceil_div_u32(chunks0, 256), 256, ACCUM_LDS, as, (const uint32_t*)S.vals[1], (const uint32_t*)S.off,
-            (const uint32_t*)S.toff[0], nb, (const uint32_t*)S.s0_dev, (const uint8_t*)B->table, S.part[0]);
-  S.d_out = d_out;
-  S.tasks1 = tasks0 / S1 + nb;
-  if (pipelined) {
-    // the bucket reduction is deferred: flush_tails() runs it for every MSM queued since the last join
-    H2_HIP(hipEventRecord(S.accum_done, as));
-    S.accum_pending = true;
-    S.accum_ever = true;
-    S.tail_deferred = true;
-    g_deferred.push_back({B, &S});
-    // half the slots: the reductions of one half run beside the accumulation of the other
-    if (g_deferred.size() >= (size_t)std::max(1, B->nslot / 2)) return flush_tails();
-    return H2MI_OK;
-  }
-  TailBatch tb;
-  for (uint32_t j = 0; j < TAIL_BATCH; j++) tb.d[j] = tail_desc(B, S);
-  int rc = launch_tails(tb, 1, S.tasks1, nb, B->logNh, B->logNl, B->seg_log, s);
-  if (rc) return rc;
-  H2_HIP(hipEventRecord(S.tail_done, s));
-  S.tail_pending = true;
-  S.tail_ever = true;
-  return H2MI_OK;
-}
-
-// ---- small base sets: host side ---------------------------------------------------------------------------------
-static SmallDesc small_desc(const Bases* B, const Slot& S) {
-  SmallDesc d;
-  d.dig = S.sdig; d.table = B->stable; d.part = S.spart; d.cnt = S.scnt; d.ticket_at = B->sG; d.out = (uint8_t*)S.d_out; d.stats = S.stats;
-  d.n = S.small_n; d.n_reg = (uint32_t)B->n; d.W = B->sW; d.c = B->sc; d.r = B->sr; d.lanes = B->slanes; d.canonical = g_canonical ? 1u : 0u;
-  d.G = ceil_div_u32((uint64_t)d.n * d.W, (uint64_t)d.lanes * d.r);  // <= B->sG: an MSM over the first n <= n_reg bases
-  return d;
-}
-
-static int launch_small(const SmallBatch& sb, uint32_t count, uint32_t max_parts, hipStream_t t) {
-  constexpr size_t LDS = (size_t)SMALL_PARTS_MAX * PART_BYTES;  // 72 KB: above the 64 KB a kernel gets without asking
-  static bool attr_set_dev[16] = {};  // function attributes are per device (every shard of a sharded handle launches these)
-  bool& attr_set = attr_set_dev[ctx().cur & 15];
-  if (!attr_set) {
-    H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_small_accum), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    attr_set = true;
-  }
-  H2_LAUNCH("k_msm_small_accum", k_msm_small_accum, dim3(max_parts, count), SMALL_THREADS, LDS, t, sb);
-  return H2MI_OK;
-}
-
-// One MSM over the first n bases of a small base set.  The digit kernel runs on the caller's stream (it is the only reader of
-// the scalars: work queued on s afterwards may overwrite them); on the library stream the accumulate + final pair is deferred
-// to the next join / flush and batched with the other small MSMs of the phase, on a caller's stream it follows in order.
-static int msm_small(Bases* B, const void* d_scalars, size_t n, void* d_out, hipStream_t s, bool inorder) {
-  const bool pipelined = !inorder && (s == ctx().stream) && ctx().tail_stream && !getenv("H2MI_MSM_NO_PIPELINE");
-  Slot& S = B->slot[B->next_slot];
-  B->last_slot = B->next_slot;
-  B->next_slot = (B->next_slot + 1) % B->nslot;
-  if (S.tail_deferred) {  // every slot of this handle is waiting for its reduction
-    int rc = flush_tails();
-    if (rc) return rc;
-  }
-  // slot reuse: the digit bytes and partial sums are read by the slot's previous accumulate / final pair — and a slot last
-  // used by the general pipeline (H2MI_MSM_GENERAL, or the streaming rule of take_small) still owes its head / accumulation events
-  if (S.tail_ever && (S.tail_pending || !pipelined || S.last_stream != s)) H2_HIP(hipStreamWaitEvent(s, S.tail_done, 0));
-  if (S.head_pending) H2_HIP(hipStreamWaitEvent(s, S.head_done, 0));
-  if (S.accum_pending) H2_HIP(hipStreamWaitEvent(s, S.accum_done, 0));
-  S.tail_pending = S.accum_pending = S.head_pending = false;
-  S.last_stream = s;
-  S.d_out = d_out;
-  S.small_n = (uint32_t)n;
-  H2_LAUNCH("k_msm_small_digits", k_msm_small_digits, ceil_div_u32(n, 64), 64, 0, s, (const fe*)d_scalars, (uint32_t)n, (uint32_t)B->n, B->sc, B->sW, S.sdig);
-  if (pipelined) {
-    H2_HIP(hipEventRecord(S.accum_done, s));  // "inputs consumed": what the deferred pair waits for
-    S.accum_pending = true;
-    S.accum_ever = true;
-    S.tail_deferred = true;
-    S.small_deferred = true;
-    g_deferred.push_back({B, &S});
-    if (g_deferred.size() >= (size_t)std::max(1, B->nslot / 2)) return flush_tails();
-    return H2MI_OK;
-  }
-  SmallBatch sb;
-  for (uint32_t j = 0; j < SMALL_BATCH; j++) sb.d[j] = small_desc(B, S);
-  int rc = launch_small(sb, 1, sb.d[0].G, s);
-  if (rc) return rc;
-  H2_HIP(hipEventRecord(S.tail_done, s));
-  S.tail_pending = true;
-  S.tail_ever = true;
-  return H2MI_OK;
-}
-
-// one fold level (<= S1 partials per task: part[0] -> part[1]), then FG lanes per bucket finish into the
-// dense array.  A bucket holding m points leaves ceil(m / (s0 * S1)) partials for the finish kernel: 1 in
-// the uniform case at k = 20, <= ~50 for the hot 0/1 buckets of witness-like columns (7 serial additions
-// per lane), n / (s0 * S1) if every scalar is the same (slow but correct).  Then the weighted bucket sum.
-static int launch_tails(const TailBatch& tb, uint32_t count, uint32_t max_tasks1, uint32_t max_nb, uint32_t max_logNh, uint32_t max_logNl,
-                        uint32_t max_seg, hipStream_t t) {
-  // fold / finish: quads (4 lanes per point operation) while the grid stays latency-bound, single lanes beyond
-  bool none_folds = true;
-  for (uint32_t j = 0; j < count; j++) none_folds = none_folds && tb.d[j].no_fold != 0;
-  if (none_folds) {
-    // no fold level at all
-  } else if ((uint64_t)max_tasks1 * count <= 65536) {
-    H2_LAUNCH("k_msm_fold", k_msm_fold<true>, dim3(ceil_div_u32((uint64_t)max_tasks1 * 4, 256), count), 256, 0, t, tb);
-  } else {
-    H2_LAUNCH("k_msm_fold", k_msm_fold<false>, dim3(ceil_div_u32(max_tasks1, 256), count), 256, 0, t, tb);
-  }
-  const uint32_t hot_blocks = ceil_div_u32(max_nb, 256);  // hot-bucket finishers: the first workgroups of the finish launch
-  const size_t hot_lds = 64 * PART_BYTES;
-  if (max_seg) {
-    H2_LAUNCH("k_msm_finish", (k_msm_finish<false, FG_WIDE>), dim3(hot_blocks + ceil_div_u32((uint64_t)max_nb * FG_WIDE, 256), count), 256, hot_lds, t, tb, hot_blocks);
-  } else if ((uint64_t)max_nb * FG_NARROW * count <= 65536) {
-    H2_LAUNCH("k_msm_finish", (k_msm_finish<true, FG_NARROW>), dim3(hot_blocks + ceil_div_u32((uint64_t)max_nb * FG_NARROW * 4, 256), count), 256, hot_lds, t, tb,
-              hot_blocks);
-  } else {
-    H2_LAUNCH("k_msm_finish", (k_msm_finish<false, FG_NARROW>), dim3(hot_blocks + ceil_div_u32((uint64_t)max_nb * FG_NARROW, 256), count), 256, hot_lds, t, tb,
-              hot_blocks);
-  }
-  if (max_seg) H2_LAUNCH("k_msm_seg", k_msm_seg, dim3((4u << MAT_LOG) / 256, count), 256, 0, t, tb);
-  H2_LAUNCH("k_msm_rowcol", k_msm_rowcol, dim3(((max_seg ? 2u : 1u) << max_logNh) + (1u << max_logNl), count), TAIL_THREADS, 256 * PART_BYTES, t, tb);
-  H2_LAUNCH("k_msm_weighted", k_msm_weighted, dim3(max_logNh + max_logNl + 1 + (max_seg ? 1 : 0), count), TAIL_THREADS, 256 * PART_BYTES, t, tb);
-  H2_LAUNCH("k_msm_final", k_msm_final, count, 128, 32 * PART_BYTES, t, tb);
-  return H2MI_OK;
-}
-
-static TailDesc tail_desc(const Bases* B, const Slot& S) {
-  TailDesc d;
-  d.part0 = S.part[0];
-  d.toff0 = S.toff[0]; d.np0 = S.np[0]; d.toff1 = S.toff[1]; d.np1 = S.np[1]; d.off = S.off;
-  d.part1 = S.part[1]; d.dense = S.dense; d.rc = S.rc; d.g = S.g; d.out = (uint8_t*)S.d_out;
-  d.stats = S.stats;
-  d.nb = B->nb; d.logNh = B->logNh; d.logNl = B->logNl; d.canonical = g_canonical ? 1u : 0u;
-  d.seg_log = B->seg_log; d.dense2 = S.dense2; d.vsum = S.vsum; d.mat = B->seg_log ? S.dense2 : S.dense;
-  d.hot_min = B->seg_log ? HOT_MIN_WIDE : HOT_MIN;
-  // wide windows: 2^17 .. 2^19 buckets hold a partial or two each, the fold level would copy them (0.08 - 0.18 ms per MSM, measured);
-  // the finish kernels read the accumulation's partials directly.  (Round 4 tried the same for up to 2^14 / 2^15 buckets, where the
-  // chain is what a join waits for: a lone 2^16 MSM gains ~10 us, a phase of four loses 4 - 7 %: profiles/r04_msm_mid_sweep.txt.)
-  d.no_fold = B->seg_log ? 1u : 0u;
-  if (d.no_fold) { d.part1 = S.part[0]; d.toff1 = S.toff[0]; d.np1 = S.np[0]; }
-  return d;
-}
-
-// launch the deferred bucket reductions (all handles) as batches on the tail stream
-static int flush_tails() {
-  if (g_deferred.empty()) return H2MI_OK;
-  const int prev = ctx().cur;
-  // the reductions of a device run on that device's tail stream, batched per device
-  for (int dev = 0; dev < (int)ctx().devs.size(); dev++) {
-    std::vector<Deferred> mine;
-    for (const Deferred& d : g_deferred)
-      if (d.B->dev == dev) mine.push_back(d);
-    if (mine.empty()) continue;
-    int rc0 = use_device(dev);
-    if (rc0) return rc0;
-    hipStream_t t = ctx().tail_stream;
-    // three kinds of deferred work, each batched with its own kind: the small path's accumulate + final pairs, and the bucket
-    // reductions of narrow and of wide windows (a wide descriptor in a batch used to switch every member to the two-lane
-    // finish: correct, but a silent latency cliff for mixed-size commitment streams — round-3 ADVICE)
-    std::vector<Deferred> group[3];
-    for (const Deferred& d : mine) group[d.S->small_deferred ? 0 : d.B->seg_log ? 2 : 1].push_back(d);
-    for (size_t i = 0; i < group[0].size();) {
-      SmallBatch sb;
-      uint32_t count = 0, max_parts = 0;
-      const size_t first = i;
-      // the small path's pair runs on the device's LIBRARY stream, behind the digit kernels that were queued there: a
-      // cross-stream hop costs ~10 us each way (event record -> wait -> launch, measured: 26 us of gaps around 81 us of
-      // kernels), more than these kernels could ever gain from running beside the stream's other work
-      hipStream_t ls = ctx().stream;
-      for (; i < group[0].size() && count < SMALL_BATCH; i++, count++) {
-        Bases* B = group[0][i].B;
-        Slot& S = *group[0][i].S;
-        sb.d[count] = small_desc(B, S);
-        max_parts = std::max(max_parts, sb.d[count].G);
-      }
-      for (uint32_t j = count; j < SMALL_BATCH; j++) sb.d[j] = sb.d[0];  // never read: blockIdx.y < count
-      int rc = launch_small(sb, count, max_parts, ls);
-      if (rc) return rc;
-      for (size_t j = first; j < i; j++) {
-        Slot& S = *group[0][j].S;
-        H2_HIP(hipEventRecord(S.tail_done, ls));
-        S.tail_pending = true;
-        S.tail_ever = true;
-        S.tail_deferred = false;
-        S.small_deferred = false;
-      }
-    }
-    for (int gi = 1; gi < 3; gi++) {
-      const std::vector<Deferred>& grp = group[gi];
-      size_t i = 0;
-      while (i < grp.size()) {
-        TailBatch tb;
-        uint32_t count = 0, max_tasks1 = 0, max_nb = 0, max_logNh = 0, max_logNl = 0, max_seg = 0;
-        const size_t first = i;
-        for (; i < grp.size() && count < TAIL_BATCH; i++, count++) {
-          Bases* B = grp[i].B;
-          Slot& S = *grp[i].S;
-          H2_HIP(hipStreamWaitEvent(t, S.accum_done, 0));
-          tb.d[count] = tail_desc(B, S);
-          max_tasks1 = std::max(max_tasks1, S.tasks1);
-          max_nb = std::max(max_nb, B->nb);
-          max_logNh = std::max(max_logNh, B->logNh);
-          max_logNl = std::max(max_logNl, B->logNl);
-          max_seg = std::max(max_seg, B->seg_log);
-        }
-        for (uint32_t j = count; j < TAIL_BATCH; j++) tb.d[j] = tb.d[0];  // never read: blockIdx.y < count
-        int rc = launch_tails(tb, count, max_tasks1, max_nb, max_logNh, max_logNl, max_seg, t);
-        if (rc) return rc;
-        for (size_t j = first; j < i; j++) {
-          Slot& S = *grp[j].S;
-          H2_HIP(hipEventRecord(S.tail_done, t));
-          S.tail_pending = true;
-          S.tail_ever = true;
-          S.tail_deferred = false;
-        }
-      }
-    }
-  }
-  g_deferred.clear();
-  return use_device(prev);
-}
-
-static const uint64_t G1_IDENTITY_J[12] = {0, 0, 0, 0, 0xd35d438dc58f0d9dULL, 0x0a78eb28f5c70b3dULL, 0x666ea36f7879462cULL, 0x0e0a77c19a07df2fULL, 0, 0, 0, 0};
+// G1::identity() = (0, 1, 0) in Montgomery form: what best_multiexp returns for empty slices
+static const uint64_t G1_IDENTITY[12] = {0, 0, 0, 0, 0xd35d438dc58f0d9dULL, 0x0a78eb28f5c70b3dULL, 0x666ea36f7879462cULL, 0x0e0a77c19a07df2fULL, 0, 0, 0, 0};
 
 static hipError_t copy_between(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, hipStream_t s) {
   const int pd = ctx().devs[(size_t)dst_dev].device, ps = ctx().devs[(size_t)src_dev].device;
@@ -2269,7 +2191,7 @@ static int msm_sharded(Sharded* sh, const void* scalars, bool on_host, size_t n,
     if (cnt == 0) {
       // nothing of this MSM falls into the shard: its partial result is the identity.  msm_join_all only waits for the
       // reductions of slots that ran an MSM, so the primary stream is ordered behind this write explicitly
-      H2_HIP(hipMemcpyAsync(out, G1_IDENTITY_J, 96, hipMemcpyHostToDevice, si));
+      H2_HIP(hipMemcpyAsync(out, G1_IDENTITY, 96, hipMemcpyHostToDevice, si));
       H2_HIP(hipEventRecord(sd.ready, si));
       H2_HIP(hipStreamWaitEvent(s0, sd.ready, 0));
       continue;
@@ -2326,10 +2248,10 @@ int msm_join_all(hipStream_t s) {
   for (auto& kv : g_bases) kv.second->since_join = 0;  // the caller has caught up with its queue
   for (auto& kv : g_bases)
     for (Slot& S : kv.second->slot)
-      if (S.tail_pending) {
-        H2_HIP(hipStreamWaitEvent(s, S.tail_done, 0));
+      if (S.tail.pending) {
+        H2_HIP(S.tail.wait(s));
         // only the owning device's library stream is thereby ordered behind this slot's previous use
-        if (s == ctx().devs[(size_t)kv.second->dev].stream) S.tail_pending = false;
+        if (s == ctx().devs[(size_t)kv.second->dev].stream) S.tail.pending = false;
       }
   if (s == ctx().devs[0].stream) return fold_sharded(s);  // partial results of sharded MSMs: gather + fold on the primary device
   return H2MI_OK;
@@ -2479,14 +2401,7 @@ static int adhoc_handle(const uint64_t* bases, size_t n, uint64_t* handle_out) {
   return H2MI_OK;
 }
 
-// G1::identity() = (0, 1, 0) in Montgomery form: what best_multiexp returns for empty slices
-static const uint64_t G1_IDENTITY[12] = {0, 0, 0, 0, 0xd35d438dc58f0d9dULL, 0x0a78eb28f5c70b3dULL, 0x666ea36f7879462cULL, 0x0e0a77c19a07df2fULL, 0, 0, 0, 0};
-
-static int msm_dev_entry(uint64_t handle, const void* d_scalars, size_t n, void* d_out_jacobian, h2mi_stream_t stream, bool inorder, bool general = false);
-int h2mi_msm_bn254_g1_dev(uint64_t handle, const void* d_scalars, size_t n, void* d_out_jacobian, h2mi_stream_t stream) {
-  return msm_dev_entry(handle, d_scalars, n, d_out_jacobian, stream, false);
-}
-static int msm_dev_entry(uint64_t handle, const void* d_scalars, size_t n, void* d_out_jacobian, h2mi_stream_t stream, bool inorder, bool general) {
+static int msm_dev_entry(uint64_t handle, const void* d_scalars, size_t n, void* d_out_jacobian, h2mi_stream_t stream, bool inorder, bool general = false) {
   H2_REQUIRE_INIT();
   if (!d_out_jacobian || (!d_scalars && n != 0)) return H2MI_EINVAL;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
@@ -2504,15 +2419,10 @@ static int msm_dev_entry(uint64_t handle, const void* d_scalars, size_t n, void*
   if (n > it->second->n) return H2MI_ERANGE;
   return msm_dev(it->second, d_scalars, n, d_out_jacobian, pick_stream(stream), inorder, general);
 }
-
-static int msm_batch_entry(uint64_t handle, const void* const* d_scalars, size_t count, size_t n, void* d_out_jacobian, h2mi_stream_t stream, bool sparse,
-                           bool inorder, bool general);
-int h2mi_msm_bn254_g1_phase_dev(uint64_t handle, const void* const* d_scalars, size_t count, size_t n, void* d_out_jacobian, unsigned flags,
-                                h2mi_stream_t stream) {
-  if (flags & ~(unsigned)(H2MI_MSM_SPARSE | H2MI_MSM_INORDER | H2MI_MSM_GENERAL)) return H2MI_EINVAL;
-  return msm_batch_entry(handle, d_scalars, count, n, d_out_jacobian, stream, (flags & H2MI_MSM_SPARSE) != 0, (flags & H2MI_MSM_INORDER) != 0,
-                         (flags & H2MI_MSM_GENERAL) != 0);
+int h2mi_msm_bn254_g1_dev(uint64_t handle, const void* d_scalars, size_t n, void* d_out_jacobian, h2mi_stream_t stream) {
+  return msm_dev_entry(handle, d_scalars, n, d_out_jacobian, stream, false);
 }
+
 static int msm_batch_entry(uint64_t handle, const void* const* d_scalars, size_t count, size_t n, void* d_out_jacobian, h2mi_stream_t stream, bool sparse,
                            bool inorder, bool general) {
   H2_REQUIRE_INIT();
@@ -2522,22 +2432,17 @@ static int msm_batch_entry(uint64_t handle, const void* const* d_scalars, size_t
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   auto it = g_bases.find(handle);
   hipStream_t s = pick_stream(stream);
-  const bool pipelined = (s == ctx().stream) && ctx().tail_stream && !getenv("H2MI_MSM_NO_PIPELINE");
   // batched launches: a plain (unsharded) handle on the library stream, narrow windows or the small path, small enough that launch
   // pace and not stage overlap is what the phase waits for; everything else is the loop the caller would have written
   // `sparse` (the caller's promise that the columns are mostly zeros or one repeated value): the kernels of such an MSM are short at
   // EVERY size — a 2^20-row witness column is 25 us of digit counting and a handful of 6-us kernels — so the batch is taken at any size
   if (count == 1 && inorder) return msm_dev_entry(handle, d_scalars[0], n, d_out_jacobian, stream, true, general);
-  if (n != 0 && count > 1 && pipelined && it != g_bases.end() && n <= it->second->n && (it->second->n <= HEAD_BATCH_MAX_N || sparse)) {
+  if (n != 0 && count > 1 && pipelined(s, /*inorder=*/false) && it != g_bases.end() && n <= it->second->n && (it->second->n <= HEAD_BATCH_MAX_N || sparse)) {
     Bases* B = it->second;
     if (B->small || B->seg_log == 0) {
       for (size_t j0 = 0; j0 < count;) {
         const size_t m = std::min({count - j0, (size_t)HEAD_BATCH, (size_t)B->nslot});
-        const bool small = take_small(B, general);  // per group of launches: a long group crosses the streaming threshold on its way
-        B->last_small = small;
-        B->since_join += (uint32_t)m;
-        int rc = small ? msm_small_batch(B, d_scalars + j0, m, n, (char*)d_out_jacobian + 96 * j0, s, inorder)
-                       : msm_dev_batch(B, d_scalars + j0, m, n, (char*)d_out_jacobian + 96 * j0, s, inorder);
+        int rc = msm_group(B, d_scalars + j0, m, n, (char*)d_out_jacobian + 96 * j0, s, inorder, general, /*batch=*/true);
         if (rc) return rc;
         j0 += m;
       }
@@ -2549,6 +2454,12 @@ static int msm_batch_entry(uint64_t handle, const void* const* d_scalars, size_t
     if (rc) return rc;
   }
   return H2MI_OK;
+}
+int h2mi_msm_bn254_g1_phase_dev(uint64_t handle, const void* const* d_scalars, size_t count, size_t n, void* d_out_jacobian, unsigned flags,
+                                h2mi_stream_t stream) {
+  if (flags & ~(unsigned)(H2MI_MSM_SPARSE | H2MI_MSM_INORDER | H2MI_MSM_GENERAL)) return H2MI_EINVAL;
+  return msm_batch_entry(handle, d_scalars, count, n, d_out_jacobian, stream, (flags & H2MI_MSM_SPARSE) != 0, (flags & H2MI_MSM_INORDER) != 0,
+                         (flags & H2MI_MSM_GENERAL) != 0);
 }
 
 int h2mi_msm_bn254_g1(uint64_t handle, const uint64_t* bases, const uint64_t* scalars, size_t n, uint64_t out[12]) {
