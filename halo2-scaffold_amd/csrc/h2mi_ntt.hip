@@ -30,13 +30,11 @@ namespace h2 {
 // by at most 2p per stage (< 25p after 10 stages, capacity 2^261 = 169p), so stages need no modular
 // correction at all — one carry normalisation per output.
 
-// out[i] = (base^(2^log_stride))^i for i < count = 2^bits, written as canonical Montgomery-2^261 words.  Per-challenge
-// tables (evaluation points, their inverses) are built on a prover's critical path, so the chain is kept short: the
-// lazy 29-bit-limb layer, log_stride squarings, then square-and-multiply over the `bits` exponent bits that can be set
-// (the 32-bit-limb version walked all 32 bits: 36 us per launch, 28 launches per proof).
-__global__ void __launch_bounds__(256) k_pow_table(fe* out, uint32_t count, fe base, uint32_t log_stride, uint32_t bits) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
+// (base^(2^log_stride))^i over the low `bits` bits of i, as canonical Montgomery-2^261 words.  Per-challenge tables (evaluation
+// points, their inverses) are built on a prover's critical path, so the chain is kept short: the lazy 29-bit-limb layer, log_stride
+// squarings, then square-and-multiply over the `bits` exponent bits that can be set (the 32-bit-limb version walked all 32 bits:
+// 36 us per launch, 28 launches per proof).
+__device__ __forceinline__ fe pow_chain(const fe& base, uint32_t log_stride, uint32_t bits, uint32_t i) {
   f29 b = f29_from_mont256<F9>(base.v);  // Mont261; products of Mont261 values stay Mont261
   for (uint32_t s = 0; s < log_stride; s++) b = f29_sqr<F9>(b);
   f29 r = f29_const<F9>(F9::ONE);
@@ -46,29 +44,18 @@ __global__ void __launch_bounds__(256) k_pow_table(fe* out, uint32_t count, fe b
   }
   fe o;
   f29_pack(f29_reduce_canonical<F9>(f29_mul<F9>(r, f29_const<F9>(F9::ONE))), o.v);  // below 2p, then canonical
-  fe_store(&out[i], o);
+  return o;
 }
-// lo (i < 2^h) and hi ((base^(2^h))^i, i < 2^(log_n - h)) halves of a two-level table in one launch
-__global__ void __launch_bounds__(256) k_pow_table2(fe* lo, fe* hi, uint32_t h, uint32_t hi_bits, fe base) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool is_hi = blockIdx.y != 0;
-  const uint32_t count = 1u << (is_hi ? hi_bits : h);
+// out[i] = (base^(2^log_stride))^i for i < count = 2^bits: a pass's local twiddles
+__global__ void __launch_bounds__(256) k_pow_table(fe* out, uint32_t count, fe base, uint32_t log_stride, uint32_t bits) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  f29 b = f29_from_mont256<F9>(base.v);
-  if (is_hi)
-    for (uint32_t s = 0; s < h; s++) b = f29_sqr<F9>(b);
-  f29 r = f29_const<F9>(F9::ONE);
-  for (int bit = (int)(is_hi ? hi_bits : h) - 1; bit >= 0; bit--) {
-    r = f29_sqr<F9>(r);
-    if ((i >> bit) & 1u) r = f29_mul<F9>(r, b);
-  }
-  fe o;
-  f29_pack(f29_reduce_canonical<F9>(f29_mul<F9>(r, f29_const<F9>(F9::ONE))), o.v);
-  fe_store(&(is_hi ? hi : lo)[i], o);
+  fe_store(&out[i], pow_chain(base, log_stride, bits, i));
 }
 
-// up to POW_BATCH two-level tables of one geometry in one launch (blockIdx.z = table): a proof's evaluation points and the division
-// roots' powers are known together, and one launch per table was a dozen 10-us launches per proof
+// lo (base^i, i < 2^h) and hi ((base^(2^h))^i, i < 2^hi_bits) halves (blockIdx.y) of up to POW_BATCH two-level tables of one geometry
+// in one launch (blockIdx.z = table): a proof's evaluation points and the division roots' powers are known together, and one launch
+// per table was a dozen 10-us launches per proof
 constexpr uint32_t POW_BATCH = 8;
 struct PowBatch {
   fe* lo[POW_BATCH];
@@ -78,19 +65,9 @@ struct PowBatch {
 __global__ void __launch_bounds__(256) k_pow_table2_b(const PowBatch pb, uint32_t h, uint32_t hi_bits) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.z;
   const bool is_hi = blockIdx.y != 0;
-  const uint32_t count = 1u << (is_hi ? hi_bits : h);
-  if (i >= count) return;
-  f29 b = f29_from_mont256<F9>(pb.base[t].v);
-  if (is_hi)
-    for (uint32_t s = 0; s < h; s++) b = f29_sqr<F9>(b);
-  f29 r = f29_const<F9>(F9::ONE);
-  for (int bit = (int)(is_hi ? hi_bits : h) - 1; bit >= 0; bit--) {
-    r = f29_sqr<F9>(r);
-    if ((i >> bit) & 1u) r = f29_mul<F9>(r, b);
-  }
-  fe o;
-  f29_pack(f29_reduce_canonical<F9>(f29_mul<F9>(r, f29_const<F9>(F9::ONE))), o.v);
-  fe_store(&(is_hi ? pb.hi[t] : pb.lo[t])[i], o);
+  const uint32_t bits = is_hi ? hi_bits : h;
+  if (i >= (1u << bits)) return;
+  fe_store(&(is_hi ? pb.hi[t] : pb.lo[t])[i], pow_chain(pb.base[t], is_hi ? h : 0, bits, i));
 }
 
 struct PassParams {
@@ -109,7 +86,6 @@ struct PassParams {
   int has_post;
   f29 post;       // Montgomery-2^261 limbs (converted on the host: every thread of the last pass multiplies by it)
   uint32_t logN1, logN2;  // last pass: digit-reversal geometry
-  uint32_t remap;         // XCD-aware block remap on/off
   uint32_t nofuse;        // the first / last round through LDS like the others
   size_t in_len;          // elements of `in` that exist; indices beyond read as zero (first pass of a
                           // zero-extending transform: coeff_to_extended without materialising the padding)
@@ -119,8 +95,8 @@ __device__ __forceinline__ uint32_t bitrev(uint32_t x, uint32_t m) { return m ? 
 
 // blocks b and b+8 share an XCD (and its L2): give each XCD a contiguous run of tiles so that tiles
 // sharing 128-B lines (adjacent columns) hit the same L2.  Bijective when nblocks % 8 == 0.
-__device__ __forceinline__ uint32_t tile_of_block(uint32_t b, uint32_t nb, uint32_t remap) {
-  if (!remap || (nb & 7u)) return b;
+__device__ __forceinline__ uint32_t tile_of_block(uint32_t b, uint32_t nb) {
+  if (nb & 7u) return b;
   return (b & 7u) * (nb >> 3) + (b >> 3);
 }
 
@@ -180,55 +156,72 @@ __device__ __forceinline__ f29 tw_fetch(const uint32_t* tw, uint32_t cnt, const 
   if ((2u << s) <= cnt) return tw_get(tw, cnt, j);
   return load_unpack(&loc[bitrev(j, m - 1)]);
 }
+// one radix-4 butterfly (stages s, s + 1) on registers: inputs x0..x3 from positions i + j h (h = 2^s), result j handed to out(j, y_j)
+// as soon as it exists (the stores of y0, y2 then overlap the arithmetic of y1, y3: 1 - 1.5 us of a 2^14 .. 2^17 transform, whose
+// few tiles leave a wavefront alone on its SIMD).  twid(0): the stage-s twiddle of both pairs; twid(1) / twid(2): the stage-(s+1)
+// twiddles of (a0, a2) / (a1, a3); each is fetched where it is used.
+// `first`: stages 0, 1, where twid(0) = twid(1) = omega^0 — not fetched, no multiplication; a2 = x2 + x3 < 4p, limbs < 2^30.
+// (named values, not an array: an f29[4] passed by reference stayed in scratch memory — 304 B per thread, passes 8 - 20 % slower)
+template <class TW, class OUT>
+__device__ __forceinline__ void ntt_r4(bool first, const f29& x0, const f29& x1, const f29& x2, const f29& x3, TW&& twid, OUT&& out) {
+  f29 t1 = x1, t3 = x3;
+  if (!first) {
+    const f29 wa = twid(0);
+    t1 = f29_mul<F9>(x1, wa);
+    t3 = f29_mul<F9>(x3, wa);
+  }
+  const f29 a0 = f29_add(x0, t1), a1 = f29_sub(x0, t1, F9::K2);
+  const f29 a2 = f29_add(x2, t3), a3 = f29_sub(x2, t3, F9::K2);
+  const f29 u3 = f29_mul<F9>(a3, twid(2));
+  if (first) {
+    out(0, f29_normalize(f29_add(a0, a2)));
+    out(2, f29_normalize(f29_sub(a0, a2, F9::KW4)));
+  } else {
+    const f29 u2 = f29_mul<F9>(a2, twid(1));
+    out(0, f29_normalize(f29_add(a0, u2)));
+    out(2, f29_normalize(f29_sub(a0, u2, F9::K2)));
+  }
+  out(1, f29_normalize(f29_add(a1, u3)));
+  out(3, f29_normalize(f29_sub(a1, u3, F9::K2)));
+}
+// the quad at LDS positions i + j 2^s of the round that starts at stage s, through the butterfly; pos = its butterfly position (i mod 2^s)
+template <class OUT>
+__device__ __forceinline__ void ntt_r4_lds(const uint32_t* lds, uint32_t dstride, const uint32_t* tw, const fe* loc, uint32_t m, uint32_t s, uint32_t i,
+                                           uint32_t pos, OUT&& out) {
+  const uint32_t h = 1u << s, tcnt = tw_staged_count(m);
+  const f29 x0 = lds_get(lds, dstride, i), x1 = lds_get(lds, dstride, i + h), x2 = lds_get(lds, dstride, i + 2 * h), x3 = lds_get(lds, dstride, i + 3 * h);
+  const uint32_t pb = bitrev(pos, s);  // the twiddle table is staged in bit-reversed order (see stage_twiddles)
+  ntt_r4(s == 0, x0, x1, x2, x3, [&](uint32_t t) { return tw_fetch(tw, tcnt, loc, m, s, t ? 2 * pb + t - 1 : pb); }, out);
+}
+// round s of quad q of the tile (DFT c = q >> (m-2)) through LDS: get four, butterfly, put four
+__device__ __forceinline__ void ntt_round(uint32_t* lds, uint32_t dstride, const uint32_t* tw, const fe* loc, uint32_t m, uint32_t s, uint32_t q) {
+  const uint32_t h = 1u << s, c = q >> (m - 2), r = q & ((1u << (m - 2)) - 1);
+  const uint32_t pos = r & (h - 1), grp = r >> s;
+  const uint32_t i = (c << m) | (grp << (s + 2)) | pos;
+  ntt_r4_lds(lds, dstride, tw, loc, m, s, i, pos, [&](uint32_t j, const f29& y) { lds_put(lds, dstride, i + j * h, y); });
+}
+// after round s.  One quad per thread and 64 quads per wavefront: a wavefront's quads of round s stay inside its own aligned block
+// of 256 elements while 2^(s+2) <= 256, so consecutive rounds up to s = 6 exchange data only between lanes of one wavefront.  LDS
+// instructions of a wavefront execute in order, so those rounds need no workgroup barrier: three barriers per 2^10 tile instead of
+// six.  `same_quads`: that thread mapping holds and the next round keeps it.
+__device__ __forceinline__ void ntt_round_barrier(bool same_quads, uint32_t s) {
+  if (same_quads && s + 4 <= 8) __builtin_amdgcn_wave_barrier();
+  else __syncthreads();
+}
 __device__ __forceinline__ void local_ntt(uint32_t* lds, uint32_t dstride, const uint32_t* tw, const fe* loc, uint32_t m, uint32_t logC) {
   const uint32_t T = blockDim.x, tid = threadIdx.x;
   if (m == 0) return;
-  const uint32_t tcnt = tw_staged_count(m);
   uint32_t s = 0;
   if (m >= 2) {
     const uint32_t nq = 1u << (m - 2 + logC);
-    // One quad per thread and 64 quads per wavefront: a wavefront's quads of round s stay inside its own aligned block
-    // of 256 elements while 2^(s+2) <= 256, so consecutive rounds up to s = 6 exchange data only between lanes of one
-    // wavefront.  LDS instructions of a wavefront execute in order, so those rounds need no workgroup barrier: three
-    // barriers per 2^10 tile instead of six.
-    const bool wave_local = nq == T && (T & 63u) == 0;
+    const bool quad_per_thread = nq == T && (T & 63u) == 0;
     for (; s + 1 < m; s += 2) {
-      const uint32_t h = 1u << s;
-      for (uint32_t q = tid; q < nq; q += T) {
-        uint32_t c = q >> (m - 2);
-        uint32_t r = q & ((1u << (m - 2)) - 1);
-        uint32_t pos = r & (h - 1);
-        uint32_t grp = r >> s;
-        uint32_t i = (c << m) | (grp << (s + 2)) | pos;
-        f29 x0 = lds_get(lds, dstride, i), x1 = lds_get(lds, dstride, i + h);
-        f29 x2 = lds_get(lds, dstride, i + 2 * h), x3 = lds_get(lds, dstride, i + 3 * h);
-        f29 t1 = x1, t3 = x3;
-        const uint32_t pb = bitrev(pos, s);  // the twiddle table is staged in bit-reversed order (see stage_twiddles)
-        if (s != 0) {
-          f29 wa = tw_fetch(tw, tcnt, loc, m, s, pb);
-          t1 = f29_mul<F9>(x1, wa);
-          t3 = f29_mul<F9>(x3, wa);
-        }
-        f29 a0 = f29_add(x0, t1), a1 = f29_sub(x0, t1, F9::K2);
-        f29 a2 = f29_add(x2, t3), a3 = f29_sub(x2, t3, F9::K2);
-        f29 u3 = f29_mul<F9>(a3, tw_fetch(tw, tcnt, loc, m, s, 2 * pb + 1));
-        if (s == 0) {  // pos = 0: the twiddle of (a0, a2) is omega^0 — no multiplication; a2 = x2 + x3 < 4p, limbs < 2^30
-          lds_put(lds, dstride, i, f29_normalize(f29_add(a0, a2)));
-          lds_put(lds, dstride, i + 2 * h, f29_normalize(f29_sub(a0, a2, F9::KW4)));
-        } else {
-          f29 u2 = f29_mul<F9>(a2, tw_fetch(tw, tcnt, loc, m, s, 2 * pb));
-          lds_put(lds, dstride, i, f29_normalize(f29_add(a0, u2)));
-          lds_put(lds, dstride, i + 2 * h, f29_normalize(f29_sub(a0, u2, F9::K2)));
-        }
-        lds_put(lds, dstride, i + h, f29_normalize(f29_add(a1, u3)));
-        lds_put(lds, dstride, i + 3 * h, f29_normalize(f29_sub(a1, u3, F9::K2)));
-      }
-      if (wave_local && s + 3 < m && s + 4 <= 8) __builtin_amdgcn_wave_barrier();  // next round is a wave-local radix-4 round
-      else __syncthreads();
+      for (uint32_t q = tid; q < nq; q += T) ntt_round(lds, dstride, tw, loc, m, s, q);
+      ntt_round_barrier(quad_per_thread && s + 3 < m, s);  // the next round is a radix-4 round too
     }
   }
   if (s < m) {  // odd m: one closing radix-2 stage (s = m - 1; for m = 1 it is the multiplication-free stage 0)
-    const uint32_t nbf = 1u << (m - 1 + logC), half = 1u << s;
+    const uint32_t nbf = 1u << (m - 1 + logC), half = 1u << s, tcnt = tw_staged_count(m);
     for (uint32_t b = tid; b < nbf; b += T) {
       uint32_t c = b >> (m - 1);
       uint32_t i_ = b & ((1u << (m - 1)) - 1);
@@ -252,100 +245,81 @@ __device__ __forceinline__ void local_ntt(uint32_t* lds, uint32_t dstride, const
 // registers and the last round's results go straight to the store: two of a 2^10 tile's six LDS round trips (initial put, five
 // get / put rounds, final get) and one barrier disappear; the arithmetic, and with it every result bit, is that of local_ntt.
 // m >= 4 with compile-time geometry only (every pass of the default splits); an odd m ends with the closing radix-2 stage instead.
-// one radix-4 round on registers: inputs x0..x3 from positions i, i+h, i+2h, i+3h; outputs for the same positions
-template <bool FIRST>
-__device__ __forceinline__ void ntt_r4(const f29& x0, const f29& x1, const f29& x2, const f29& x3, const f29& wa, const f29& w2, const f29& w3,
-                                       f29& r0, f29& r1, f29& r2, f29& r3) {
-  f29 t1 = x1, t3 = x3;
-  if (!FIRST) {
-    t1 = f29_mul<F9>(x1, wa);
-    t3 = f29_mul<F9>(x3, wa);
-  }
-  const f29 a0 = f29_add(x0, t1), a1 = f29_sub(x0, t1, F9::K2);
-  const f29 a2 = f29_add(x2, t3), a3 = f29_sub(x2, t3, F9::K2);
-  const f29 u3 = f29_mul<F9>(a3, w3);
-  if (FIRST) {  // the twiddle of (a0, a2) is omega^0
-    r0 = f29_normalize(f29_add(a0, a2));
-    r2 = f29_normalize(f29_sub(a0, a2, F9::KW4));
-  } else {
-    const f29 u2 = f29_mul<F9>(a2, w2);
-    r0 = f29_normalize(f29_add(a0, u2));
-    r2 = f29_normalize(f29_sub(a0, u2, F9::K2));
-  }
-  r1 = f29_normalize(f29_add(a1, u3));
-  r3 = f29_normalize(f29_sub(a1, u3, F9::K2));
-}
 // first round (stages 0, 1) on the loaded elements e_k = element e0 + k 2^(m-2) of DFT c, results to their LDS positions
-// (named values, not an array: an f29[4] passed by reference stayed in scratch memory — 304 B per thread, passes 8 - 20 % slower)
 __device__ __forceinline__ void ntt_first_round_put(uint32_t* lds, uint32_t dstride, const fe* loc, uint32_t m, uint32_t c, uint32_t e0, const f29& e_0,
                                                     const f29& e_1, const f29& e_2, const f29& e_3) {
   const uint32_t i = (c << m) | (bitrev(e0, m - 2) << 2);
   // bit reversal: element k sits at position i + bitrev2(k): (x0, x1, x2, x3) of the round = elements 0, 2, 1, 3
-  const f29 w3 = load_unpack(&loc[1u << (m - 2)]);  // staged entry 1 = loc[bitrev(1, m - 1)]
-  f29 r0, r1, r2, r3;
-  ntt_r4<true>(e_0, e_2, e_1, e_3, w3, w3, w3, r0, r1, r2, r3);
-  lds_put(lds, dstride, i, r0);
-  lds_put(lds, dstride, i + 1, r1);
-  lds_put(lds, dstride, i + 2, r2);
-  lds_put(lds, dstride, i + 3, r3);
+  const f29 w3 = load_unpack(&loc[1u << (m - 2)]);  // staged entry 1 = loc[bitrev(1, m - 1)] (the twiddles are not staged yet)
+  ntt_r4(true, e_0, e_2, e_1, e_3, [&](uint32_t) { return w3; }, [&](uint32_t j, const f29& y) { lds_put(lds, dstride, i + j, y); });
 }
 // rounds s = 2 .. m - 4 through LDS, as local_ntt runs them; ends with a workgroup barrier (the last round regroups the threads)
-__device__ __forceinline__ void ntt_middle_rounds(uint32_t* lds, uint32_t dstride, const uint32_t* tw, const fe* loc, uint32_t m, uint32_t logC) {
-  const uint32_t tid = threadIdx.x, tcnt = tw_staged_count(m);
+__device__ __forceinline__ void ntt_middle_rounds(uint32_t* lds, uint32_t dstride, const uint32_t* tw, const fe* loc, uint32_t m) {
   for (uint32_t s = 2; s + 2 < m; s += 2) {
-    const uint32_t h = 1u << s;
-    const uint32_t c = tid >> (m - 2), r = tid & ((1u << (m - 2)) - 1);
-    const uint32_t pos = r & (h - 1), grp = r >> s;
-    const uint32_t i = (c << m) | (grp << (s + 2)) | pos;
-    const f29 x0 = lds_get(lds, dstride, i), x1 = lds_get(lds, dstride, i + h), x2 = lds_get(lds, dstride, i + 2 * h), x3 = lds_get(lds, dstride, i + 3 * h);
-    const uint32_t pb = bitrev(pos, s);
-    f29 r0, r1, r2, r3;
-    ntt_r4<false>(x0, x1, x2, x3, tw_fetch(tw, tcnt, loc, m, s, pb), tw_fetch(tw, tcnt, loc, m, s, 2 * pb), tw_fetch(tw, tcnt, loc, m, s, 2 * pb + 1), r0, r1,
-                  r2, r3);
-    lds_put(lds, dstride, i, r0);
-    lds_put(lds, dstride, i + h, r1);
-    lds_put(lds, dstride, i + 2 * h, r2);
-    lds_put(lds, dstride, i + 3 * h, r3);
-    // wave-local while the next round's quads stay inside a wavefront's own 256 elements — and the next round is not the last
-    if (s + 4 < m && s + 4 <= 8) __builtin_amdgcn_wave_barrier();
-    else __syncthreads();
+    ntt_round(lds, dstride, tw, loc, m, s, threadIdx.x);
+    ntt_round_barrier(s + 4 < m, s);  // the next round is not the last
   }
 }
-// last round (stages m-2, m-1) for the quad (c, pos): y[j] = the DFT's output k = pos + j 2^(m-2)
-__device__ __forceinline__ void ntt_last_round_get(const uint32_t* lds, uint32_t dstride, const uint32_t* tw, const fe* loc, uint32_t m, uint32_t c,
-                                                   uint32_t pos, f29& y0, f29& y1, f29& y2, f29& y3) {
-  const uint32_t s = m - 2, h = 1u << s, tcnt = tw_staged_count(m);
-  const uint32_t i = (c << m) | pos;
-  const f29 x0 = lds_get(lds, dstride, i), x1 = lds_get(lds, dstride, i + h), x2 = lds_get(lds, dstride, i + 2 * h), x3 = lds_get(lds, dstride, i + 3 * h);
-  const uint32_t pb = bitrev(pos, s);
-  ntt_r4<false>(x0, x1, x2, x3, tw_fetch(tw, tcnt, loc, m, s, pb), tw_fetch(tw, tcnt, loc, m, s, 2 * pb), tw_fetch(tw, tcnt, loc, m, s, 2 * pb + 1), y0, y1, y2,
-                y3);
-}
-// odd m: the closing radix-2 stage s = m - 1 for the thread's two butterflies (pos, pos + 2Q) and (pos + Q, pos + 3Q), Q = 2^(m-2):
-// the same four outputs k = pos + j Q
-__device__ __forceinline__ void ntt_last_stage_get_odd(const uint32_t* lds, uint32_t dstride, const uint32_t* tw, const fe* loc, uint32_t m, uint32_t c,
-                                                       uint32_t pos, f29& y0, f29& y1, f29& y2, f29& y3) {
-  const uint32_t s = m - 1, half = 1u << s, Q = 1u << (m - 2), tcnt = tw_staged_count(m);
-  const uint32_t i = (c << m) | pos;
-  const f29 u0 = lds_get(lds, dstride, i), v0 = lds_get(lds, dstride, i + half);
-  const f29 u1 = lds_get(lds, dstride, i + Q), v1 = lds_get(lds, dstride, i + Q + half);
-  const f29 t0 = f29_mul<F9>(v0, tw_fetch(tw, tcnt, loc, m, s - 1, bitrev(pos, s)));
-  const f29 t1 = f29_mul<F9>(v1, tw_fetch(tw, tcnt, loc, m, s - 1, bitrev(pos + Q, s)));
-  y0 = f29_normalize(f29_add(u0, t0));
-  y2 = f29_normalize(f29_sub(u0, t0, F9::K2));
-  y1 = f29_normalize(f29_add(u1, t1));
-  y3 = f29_normalize(f29_sub(u1, t1, F9::K2));
-}
-template <uint32_t M>
-__device__ __forceinline__ void ntt_last_get(const uint32_t* lds, uint32_t dstride, const uint32_t* tw, const fe* loc, uint32_t c, uint32_t pos, f29& y0,
-                                             f29& y1, f29& y2, f29& y3) {
-  if (M & 1u) ntt_last_stage_get_odd(lds, dstride, tw, loc, M, c, pos, y0, y1, y2, y3);
-  else ntt_last_round_get(lds, dstride, tw, loc, M, c, pos, y0, y1, y2, y3);
+// the last round or stage for the quad (c, pos): out(j, y) with y = the DFT's output k = pos + j Q, Q = 2^(m-2).  Even m: the radix-4 round of
+// stages m-2, m-1.  Odd m: the closing radix-2 stage s = m - 1 for the thread's two butterflies (pos, pos + 2Q) and (pos + Q, pos + 3Q).
+template <uint32_t M, class OUT>
+__device__ __forceinline__ void ntt_last_get(const uint32_t* lds, uint32_t dstride, const uint32_t* tw, const fe* loc, uint32_t c, uint32_t pos, OUT&& out) {
+  const uint32_t i = (c << M) | pos;
+  if constexpr (M & 1u) {
+    const uint32_t s = M - 1, half = 1u << s, Q = 1u << (M - 2), tcnt = tw_staged_count(M);
+    const f29 u0 = lds_get(lds, dstride, i), v0 = lds_get(lds, dstride, i + half);
+    const f29 u1 = lds_get(lds, dstride, i + Q), v1 = lds_get(lds, dstride, i + Q + half);
+    const f29 t0 = f29_mul<F9>(v0, tw_fetch(tw, tcnt, loc, M, s - 1, bitrev(pos, s)));
+    const f29 t1 = f29_mul<F9>(v1, tw_fetch(tw, tcnt, loc, M, s - 1, bitrev(pos + Q, s)));
+    out(0, f29_normalize(f29_add(u0, t0)));
+    out(2, f29_normalize(f29_sub(u0, t0, F9::K2)));
+    out(1, f29_normalize(f29_add(u1, t1)));
+    out(3, f29_normalize(f29_sub(u1, t1, F9::K2)));
+  } else {
+    ntt_r4_lds(lds, dstride, tw, loc, M, M - 2, i, pos, out);
+  }
 }
 constexpr bool ntt_fused_geometry(uint32_t DS, uint32_t M) { return DS != 0 && M >= 4; }
 
-
 extern __shared__ uint32_t h2_smem[];
+
+// element idx of a pass's input, times its coset power on a pre-scaled first pass.  Zero-extended input (coeff_to_extended: three
+// quarters of a 4n coset transform's input are padding): a padded element needs neither its load nor its coset power (two table
+// loads and two multiplications above 2^22) — round 4: coset 2^24 from 2^22
+__device__ __forceinline__ f29 pass_load(const PassParams& p, size_t idx) {
+  f29 x = f29_zero();
+  if (idx < p.in_len) {
+    x = load_unpack(&p.in[idx]);
+    if (p.plo) x = f29_mul<F9>(x, powtab(p.plo, p.phi, p.ph, p.pfull, (uint32_t)idx));
+  }
+  return x;
+}
+// column pass: output k of column jl0 + c of the segment at `base`, times its inter-pass twiddle, stored in place
+__device__ __forceinline__ void col_store(const PassParams& p, uint32_t m, uint32_t logC, size_t base, uint32_t jl0, uint32_t c, uint32_t k, const f29& y) {
+  f29 v;
+  if (p.wmat) {  // tile-ordered copy of the twiddles: entry (k << logC) | c of this tile, whichever segment the tile sits in
+    v = f29_mul<F9>(y, load_unpack(&p.wmat[((size_t)(jl0 >> logC) << (m + logC)) + ((k << logC) | c)]));
+  } else {
+    v = f29_mul<F9>(y, powtab(p.tlo, p.thi, p.h, p.tfull, ((jl0 + c) * k) << (p.log_n - p.log_seg)));  // exponent < n
+  }
+  // the product is normalized and below 1.2 p (< 2^255): stored as it is, without the canonical reduction — the next pass
+  // reads it as a loosely reduced input (its lazy rounds then stay below 34 p of the 169 p capacity; the LAST pass alone
+  // returns canonical values)
+  fe o_;
+  f29_pack(v, o_.v);
+  fe_store(&p.out[base + ((size_t)k << (p.log_seg - m)) + jl0 + c], o_);
+}
+// row pass: output k of row (k1_0 + c, k2), to its digit-reversed slot
+__device__ __forceinline__ void row_store(const PassParams& p, uint32_t k1_0, uint32_t k2, uint32_t c, uint32_t k, const f29& y) {
+  const size_t oidx = (size_t)(k1_0 + c) + ((size_t)k2 << p.logN1) + ((size_t)k << (p.logN1 + p.logN2));
+  if (p.has_post) {  // the caller's post-scale also brings the lazily accumulated value back below 2p
+    pack_store(&p.out[oidx], f29_mul<F9>(y, p.post));
+  } else {  // m/2 lazy rounds leave a value below (2 + 6 * ceil(m/2)) p <= 32p: reduce it directly
+    fe o_;
+    f29_pack(f29_reduce_loose<F9>(y), o_.v);
+    fe_store(&p.out[oidx], o_);
+  }
+}
 
 // Compile-time geometry (round 3; tools/ntt_isa_budget.py): DS = elements per tile (limb-plane stride of the LDS image), M =
 // log2 of the DFT size.  With both known the nine plane offsets l * DS * 4 of every LDS get / put and the eight of every staged-
@@ -361,82 +335,38 @@ __global__ void __launch_bounds__(512) k_ntt_pass_col(PassParams p) {
   uint32_t* tw = lds + 9 * dstride;  // 8 word planes of packed twiddles, at most TW_STAGED entries: a 2^10 tile is 40 KiB = 4 blocks/CU
   const uint32_t T = blockDim.x, tid = threadIdx.x;
   const uint32_t logS = p.log_seg - m;
-  const uint32_t tile = tile_of_block(blockIdx.x, gridDim.x, p.remap);
+  const uint32_t tile = tile_of_block(blockIdx.x, gridDim.x);
   const uint32_t tiles_per_seg_log = logS - logC;
   const uint32_t seg = tile >> tiles_per_seg_log;
   const uint32_t jl0 = (tile & ((1u << tiles_per_seg_log) - 1)) << logC;
   const size_t base = (size_t)seg << p.log_seg;
-  const uint32_t sh = p.log_n - p.log_seg;
+  auto in_idx = [&](uint32_t c, uint32_t e) { return base + ((size_t)e << logS) + jl0 + c; };
 
   if constexpr (ntt_fused_geometry(DS, M)) if (T * 4 == DS && !p.nofuse) {  // one quad per thread: first round on the loaded registers, last round into the store
     const uint32_t c = tid & (C - 1), e0 = tid >> logC, Q = 1u << (m - 2);
-    auto ld = [&](uint32_t k) {
-      const size_t idx = base + ((size_t)(e0 + k * Q) << logS) + jl0 + c;
-      f29 x = f29_zero();
-      if (idx < p.in_len) {
-        x = load_unpack(&p.in[idx]);
-        if (p.plo) x = f29_mul<F9>(x, powtab(p.plo, p.phi, p.ph, p.pfull, (uint32_t)idx));
-      }
-      return x;
-    };
     {
-      const f29 x0 = ld(0), x1 = ld(1), x2 = ld(2), x3 = ld(3);
+      const f29 x0 = pass_load(p, in_idx(c, e0)), x1 = pass_load(p, in_idx(c, e0 + Q)), x2 = pass_load(p, in_idx(c, e0 + 2 * Q)),
+                x3 = pass_load(p, in_idx(c, e0 + 3 * Q));
       ntt_first_round_put(lds, dstride, p.loc, m, c, e0, x0, x1, x2, x3);
     }
     stage_twiddles(tw, p.loc, m);
     __syncthreads();
-    ntt_middle_rounds(lds, dstride, tw, p.loc, m, logC);
-    f29 y0, y1, y2, y3;
-    ntt_last_get<M>(lds, dstride, tw, p.loc, c, e0, y0, y1, y2, y3);  // pos = e0: this thread's outputs k = e0 + j Q of DFT c
-    auto st = [&](uint32_t j, const f29& y) {
-      const uint32_t k = e0 + j * Q, o = (k << logC) | c;
-      f29 v;
-      if (p.wmat) {
-        v = f29_mul<F9>(y, load_unpack(&p.wmat[((size_t)(jl0 >> logC) << (m + logC)) + o]));
-      } else {
-        v = f29_mul<F9>(y, powtab(p.tlo, p.thi, p.h, p.tfull, ((jl0 + c) * k) << sh));
-      }
-      fe o_;
-      f29_pack(v, o_.v);
-      fe_store(&p.out[base + ((size_t)k << logS) + jl0 + c], o_);
-    };
-    st(0, y0);
-    st(1, y1);
-    st(2, y2);
-    st(3, y3);
+    ntt_middle_rounds(lds, dstride, tw, p.loc, m);
+    // pos = e0: this thread's outputs k = e0 + j Q of DFT c
+    ntt_last_get<M>(lds, dstride, tw, p.loc, c, e0, [&](uint32_t j, const f29& y) { col_store(p, m, logC, base, jl0, c, e0 + j * Q, y); });
     return;
   }
 
   for (uint32_t o = tid; o < (C << m); o += T) {
-    uint32_t c = o & (C - 1), e = o >> logC;
-    size_t idx = base + ((size_t)e << logS) + jl0 + c;
-    // zero-extended input (coeff_to_extended: three quarters of a 4n coset transform's input are padding): a padded element needs
-    // neither its load nor its coset power (two table loads and two multiplications above 2^22) — round 4: coset 2^24 from 2^22
-    f29 x = f29_zero();
-    if (idx < p.in_len) {
-      x = load_unpack(&p.in[idx]);
-      if (p.plo) x = f29_mul<F9>(x, powtab(p.plo, p.phi, p.ph, p.pfull, (uint32_t)idx));
-    }
-    lds_put(lds, dstride, (c << m) | bitrev(e, m), x);
+    const uint32_t c = o & (C - 1), e = o >> logC;
+    lds_put(lds, dstride, (c << m) | bitrev(e, m), pass_load(p, in_idx(c, e)));
   }
   stage_twiddles(tw, p.loc, m);
   __syncthreads();
   local_ntt(lds, dstride, tw, p.loc, m, logC);
   for (uint32_t o = tid; o < (C << m); o += T) {
-    uint32_t c = o & (C - 1), k = o >> logC;
-    f29 x = lds_get(lds, dstride, (c << m) | k);
-    if (p.wmat) {  // tile-ordered copy of the twiddles: entry o of this tile, whichever segment the tile sits in
-      x = f29_mul<F9>(x, load_unpack(&p.wmat[((size_t)(jl0 >> logC) << (m + logC)) + o]));
-    } else {
-      uint32_t ex = ((jl0 + c) * k) << sh;  // < n
-      x = f29_mul<F9>(x, powtab(p.tlo, p.thi, p.h, p.tfull, ex));
-    }
-    // the product is normalized and below 1.2 p (< 2^255): stored as it is, without the canonical reduction — the next pass
-    // reads it as a loosely reduced input (its lazy rounds then stay below 34 p of the 169 p capacity; the LAST pass alone
-    // returns canonical values)
-    fe o_;
-    f29_pack(x, o_.v);
-    fe_store(&p.out[base + ((size_t)k << logS) + jl0 + c], o_);
+    const uint32_t c = o & (C - 1), k = o >> logC;
+    col_store(p, m, logC, base, jl0, c, k, lds_get(lds, dstride, (c << m) | k));
   }
 }
 
@@ -448,81 +378,37 @@ __global__ void __launch_bounds__(512) k_ntt_pass_row(PassParams p) {
   uint32_t* lds = h2_smem;
   uint32_t* tw = lds + 9 * dstride;
   const uint32_t T = blockDim.x, tid = threadIdx.x;
-  const uint32_t tile = tile_of_block(blockIdx.x, gridDim.x, p.remap);
+  const uint32_t tile = tile_of_block(blockIdx.x, gridDim.x);
   const uint32_t k2 = tile & ((1u << p.logN2) - 1);
   const uint32_t k1_0 = (tile >> p.logN2) << logC;
+  auto in_idx = [&](uint32_t c, uint32_t e) { return (((((size_t)(k1_0 + c) << p.logN2) + k2)) << m) + e; };
 
   if constexpr (ntt_fused_geometry(DS, M)) if (T * 4 == DS && !p.nofuse) {  // see k_ntt_pass_col
     const uint32_t Q = 1u << (m - 2);
     {
       const uint32_t c = tid >> (m - 2), e0 = tid & (Q - 1);  // loads: a wavefront reads 64 consecutive elements of one row
-      const size_t rho = ((size_t)(k1_0 + c) << p.logN2) + k2;
-      auto ld = [&](uint32_t k) {
-        const size_t idx = (rho << m) + e0 + k * Q;
-        f29 x = f29_zero();
-        if (idx < p.in_len) {
-          x = load_unpack(&p.in[idx]);
-          if (p.plo) x = f29_mul<F9>(x, powtab(p.plo, p.phi, p.ph, p.pfull, (uint32_t)idx));
-        }
-        return x;
-      };
-      const f29 x0 = ld(0), x1 = ld(1), x2 = ld(2), x3 = ld(3);
+      const f29 x0 = pass_load(p, in_idx(c, e0)), x1 = pass_load(p, in_idx(c, e0 + Q)), x2 = pass_load(p, in_idx(c, e0 + 2 * Q)),
+                x3 = pass_load(p, in_idx(c, e0 + 3 * Q));
       ntt_first_round_put(lds, dstride, p.loc, m, c, e0, x0, x1, x2, x3);
     }
     stage_twiddles(tw, p.loc, m);
     __syncthreads();
-    ntt_middle_rounds(lds, dstride, tw, p.loc, m, logC);
+    ntt_middle_rounds(lds, dstride, tw, p.loc, m);
     const uint32_t c = tid & (C - 1), pos = tid >> logC;  // stores: the C rows' outputs k are adjacent in memory
-    f29 y0, y1, y2, y3;
-    ntt_last_get<M>(lds, dstride, tw, p.loc, c, pos, y0, y1, y2, y3);
-    const f29 fin = p.post;
-    auto st = [&](uint32_t j, const f29& y) {
-      const uint32_t k = pos + j * Q;
-      const size_t oidx = (size_t)(k1_0 + c) + ((size_t)k2 << p.logN1) + ((size_t)k << (p.logN1 + p.logN2));
-      if (p.has_post) {
-        pack_store(&p.out[oidx], f29_mul<F9>(y, fin));
-      } else {
-        fe o_;
-        f29_pack(f29_reduce_loose<F9>(y), o_.v);
-        fe_store(&p.out[oidx], o_);
-      }
-    };
-    st(0, y0);
-    st(1, y1);
-    st(2, y2);
-    st(3, y3);
+    ntt_last_get<M>(lds, dstride, tw, p.loc, c, pos, [&](uint32_t j, const f29& y) { row_store(p, k1_0, k2, c, pos + j * Q, y); });
     return;
   }
 
   for (uint32_t o = tid; o < (C << m); o += T) {
-    uint32_t c = o >> m, e = o & ((1u << m) - 1);
-    size_t rho = ((size_t)(k1_0 + c) << p.logN2) + k2;
-    size_t idx = (rho << m) + e;
-    // zero-extended input (coeff_to_extended: three quarters of a 4n coset transform's input are padding): a padded element needs
-    // neither its load nor its coset power (two table loads and two multiplications above 2^22) — round 4: coset 2^24 from 2^22
-    f29 x = f29_zero();
-    if (idx < p.in_len) {
-      x = load_unpack(&p.in[idx]);
-      if (p.plo) x = f29_mul<F9>(x, powtab(p.plo, p.phi, p.ph, p.pfull, (uint32_t)idx));
-    }
-    lds_put(lds, dstride, (c << m) | bitrev(e, m), x);
+    const uint32_t c = o >> m, e = o & ((1u << m) - 1);
+    lds_put(lds, dstride, (c << m) | bitrev(e, m), pass_load(p, in_idx(c, e)));
   }
   stage_twiddles(tw, p.loc, m);
   __syncthreads();
   local_ntt(lds, dstride, tw, p.loc, m, logC);
-  // the caller's post-scale also brings the lazily accumulated value back below 2p
-  const f29 fin = p.post;
   for (uint32_t o = tid; o < (C << m); o += T) {
-    uint32_t c = o & (C - 1), k = o >> logC;
-    f29 x = lds_get(lds, dstride, (c << m) | k);
-    size_t oidx = (size_t)(k1_0 + c) + ((size_t)k2 << p.logN1) + ((size_t)k << (p.logN1 + p.logN2));
-    if (p.has_post) {
-      pack_store(&p.out[oidx], f29_mul<F9>(x, fin));
-    } else {  // m/2 lazy rounds leave a value below (2 + 6 * ceil(m/2)) p <= 32p: reduce it directly
-      fe o_;
-      f29_pack(f29_reduce_loose<F9>(x), o_.v);
-      fe_store(&p.out[oidx], o_);
-    }
+    const uint32_t c = o & (C - 1), k = o >> logC;
+    row_store(p, k1_0, k2, c, k, lds_get(lds, dstride, (c << m) | k));
   }
 }
 
@@ -579,6 +465,13 @@ struct Key {
     return memcmp(w, o.w, 32) < 0;
   }
 };
+static Key make_key(const uint64_t w[4], uint32_t log_n, bool full = false) {
+  Key k;
+  memcpy(k.w, w, 32);
+  k.log_n = log_n;
+  k.full = full;
+  return k;
+}
 struct Plan {
   int P = 0;
   uint32_t m[3] = {0, 0, 0};
@@ -610,6 +503,11 @@ static Scratch g_scratch[N_SCRATCH];
 static Scratch* g_cur = nullptr;
 static uint64_t g_scratch_clock = 0;
 static fe* g_tmp = nullptr;
+// device staging of the host-pointer transform (h2mi_ntt_ext_bn254_fr), kept between calls (grow-only, like the ping-pong
+// scratch): EvaluationDomain calls it dozens of times per proof with two sizes
+static fe* g_stage = nullptr;
+static size_t g_stage_bytes = 0;
+static bool g_pass_attr_set = false;  // the pass kernels' LDS opt-in is in place (ntt_dev)
 
 // `full`: one table entry per power (32 B x 2^log_n) so that a kernel fetches base^e instead of multiplying
 // two table entries: for the bases that live as long as a domain (omega, the coset generator), up to 2^22.
@@ -687,6 +585,14 @@ static void free_plan(Plan& pl) {
   pl.built.destroy();
 }
 
+// over the limits an eviction brings the cache back under: the tables' alone, or the tables' and the plans'
+static bool tables_over_keep() { return g_powtabs.size() > POWTAB_KEEP_ENTRIES || g_powtab_bytes > POWTAB_KEEP_BYTES; }
+static bool cache_over_keep() { return tables_over_keep() || g_plans.size() > PLAN_KEEP || g_wmat_bytes > WMAT_KEEP_BYTES; }
+using Aged = std::vector<std::pair<uint64_t, Key>>;  // (last_use, key)
+static void sort_oldest_first(Aged& v) {
+  std::sort(v.begin(), v.end(), [](const Aged::value_type& a, const Aged::value_type& b) { return a.first < b.first; });
+}
+
 static int evict_tables() {
   H2_HIP(hipDeviceSynchronize());  // every stream: a table may be read by kernels the caller queued elsewhere
   // What fills the cache in a prover loop are the per-challenge tables (evaluation points, their inverses: a dozen per proof, used
@@ -695,16 +601,16 @@ static int evict_tables() {
   // call was freed on every eviction — harmless while a plan was two small twiddle tables, but a plan now owns its tile-ordered
   // twiddle matrices, 32 - 512 MB: a proof loop rebuilt them every five or six proofs, k_ntt_wmat_build inside the steady state.)
   auto drop_unreferenced = [&]() {
-    std::vector<std::pair<uint64_t, Key>> order;
+    Aged order;
     for (auto& kv : g_powtabs) {
       if (kv.second.last_use >= g_epoch) continue;  // handed out during this call
       bool referenced = false;
       for (auto& pk : g_plans) referenced = referenced || pk.second.tw.lo == kv.second.lo;
       if (!referenced) order.push_back({kv.second.last_use, kv.first});
     }
-    std::sort(order.begin(), order.end(), [](const std::pair<uint64_t, Key>& a, const std::pair<uint64_t, Key>& b) { return a.first < b.first; });
+    sort_oldest_first(order);
     for (auto& e : order) {
-      if (g_powtabs.size() <= POWTAB_KEEP_ENTRIES && g_powtab_bytes <= POWTAB_KEEP_BYTES) break;
+      if (!tables_over_keep()) break;
       auto it = g_powtabs.find(e.second);
       table_release(it->second.lo, it->second.bytes);  // hi lives in the same allocation
       it->second.built.destroy();
@@ -713,97 +619,62 @@ static int evict_tables() {
     }
   };
   drop_unreferenced();
-  if (g_powtabs.size() > POWTAB_KEEP_ENTRIES || g_powtab_bytes > POWTAB_KEEP_BYTES || g_plans.size() > PLAN_KEEP || g_wmat_bytes > WMAT_KEEP_BYTES) {
+  if (cache_over_keep()) {
     // still over: the plans of domains no longer in use (oldest first), then the tables they held
-    std::vector<std::pair<uint64_t, Key>> plans;
+    Aged plans;
     for (auto& kv : g_plans)
       if (kv.second.last_use < g_epoch) plans.push_back({kv.second.last_use, kv.first});
-    std::sort(plans.begin(), plans.end(), [](const std::pair<uint64_t, Key>& a, const std::pair<uint64_t, Key>& b) { return a.first < b.first; });
+    sort_oldest_first(plans);
     for (auto& e : plans) {
       auto it = g_plans.find(e.second);
       free_plan(it->second);
       g_plans.erase(it);
       drop_unreferenced();
-      if (g_powtabs.size() <= POWTAB_KEEP_ENTRIES && g_powtab_bytes <= POWTAB_KEEP_BYTES && g_plans.size() <= PLAN_KEEP && g_wmat_bytes <= WMAT_KEEP_BYTES) break;
+      if (!cache_over_keep()) break;
     }
   }
   g_evictions++;
   return H2MI_OK;
 }
 
-int get_powtab(const uint64_t base[4], uint32_t log_n, hipStream_t s, PowTab* out, bool full) {
-  full = full && log_n <= FULL_TABLE_MAX_LOG;
-  Key k;
-  memcpy(k.w, base, 32);
-  k.log_n = log_n;
-  k.full = full;
-  auto it = g_powtabs.find(k);
-  if (it != g_powtabs.end()) {
-    it->second.last_use = g_epoch;
-    H2_HIP(it->second.built.use(s));
-    *out = it->second;
-    return H2MI_OK;
-  }
-  static const size_t max_entries = getenv("H2MI_POWTAB_MAX") ? (size_t)atoi(getenv("H2MI_POWTAB_MAX")) : POWTAB_MAX_ENTRIES;
-  if (g_powtabs.size() >= max_entries || g_powtab_bytes > POWTAB_MAX_BYTES) {
-    int rc = evict_tables();
-    if (rc) return rc;
-  }
-  PowTab t;
-  t.full = full;
-  t.h = full ? log_n : (log_n + 1) / 2;
-  uint32_t nlo = 1u << t.h, nhi = 1u << (log_n - t.h);
-  t.bytes = ((size_t)nlo + nhi) * 32;
-  t.lo = table_alloc(t.bytes);
-  if (!t.lo) return H2MI_ENOMEM;
-  t.hi = t.lo + nlo;
-  fe b = host_fe(base);
-  H2_LAUNCH("k_pow_table", k_pow_table2, dim3(ceil_div_u32(std::max(nlo, nhi), 256), 2), 256, 0, s, t.lo, t.hi, t.h, log_n - t.h, b);
-  H2_HIP(t.built.mark(s));
-  t.last_use = g_epoch;
-  g_powtab_bytes += t.bytes;
-  g_powtabs[k] = t;
-  *out = t;
-  return H2MI_OK;
-}
-
-// the tables of `m` bases at one size: cache hits as get_powtab, the missing ones allocated and built by ONE launch per POW_BATCH
-int get_powtabs(const uint64_t* bases /* m x 4 */, size_t m, uint32_t log_n, hipStream_t s, PowTab* out) {
-  std::vector<size_t> missing;
+// The tables of `m` bases at one size.  A cached table is pinned for this call and ordered before stream s; the missing ones are
+// allocated, built by ONE launch per POW_BATCH and registered.  full: one entry per power (h = log_n, hi = {1}).
+static int powtabs_for(const uint64_t* bases /* m x 4 */, size_t m, uint32_t log_n, bool full, hipStream_t s, PowTab* out) {
+  std::vector<size_t> missing;         // request indices of the distinct bases to build
+  std::vector<int> fresh_of(m, -1);    // request index -> index into `missing` (the same base twice in one request is built once)
   for (size_t i = 0; i < m; i++) {
-    Key k;
-    memcpy(k.w, bases + 4 * i, 32);
-    k.log_n = log_n;
-    k.full = false;
-    auto it = g_powtabs.find(k);
+    auto it = g_powtabs.find(make_key(bases + 4 * i, log_n, full));
     if (it != g_powtabs.end()) {
       it->second.last_use = g_epoch;
       H2_HIP(it->second.built.use(s));
       out[i] = it->second;
       continue;
     }
-    bool dup = false;  // the same base twice in one request: built once, copied below
-    for (size_t j : missing) dup = dup || memcmp(bases + 4 * j, bases + 4 * i, 32) == 0;
-    if (!dup) missing.push_back(i);
+    for (size_t j = 0; j < missing.size() && fresh_of[i] < 0; j++)
+      if (memcmp(bases + 4 * missing[j], bases + 4 * i, 32) == 0) fresh_of[i] = (int)j;
+    if (fresh_of[i] < 0) {
+      fresh_of[i] = (int)missing.size();
+      missing.push_back(i);
+    }
   }
   static const size_t max_entries = getenv("H2MI_POWTAB_MAX") ? (size_t)atoi(getenv("H2MI_POWTAB_MAX")) : POWTAB_MAX_ENTRIES;
   if (!missing.empty() && (g_powtabs.size() + missing.size() > max_entries || g_powtab_bytes > POWTAB_MAX_BYTES)) {
     int rc = evict_tables();  // entries handed out above carry this call's epoch: never evicted
     if (rc) return rc;
   }
-  const uint32_t h = (log_n + 1) / 2, nlo = 1u << h, nhi = 1u << (log_n - h);
+  const uint32_t h = full ? log_n : (log_n + 1) / 2, nlo = 1u << h, nhi = 1u << (log_n - h);
+  std::vector<PowTab> fresh(missing.size());
   for (size_t b0 = 0; b0 < missing.size(); b0 += POW_BATCH) {
     const uint32_t cnt = (uint32_t)std::min<size_t>(POW_BATCH, missing.size() - b0);
-    PowBatch pb;
-    PowTab tabs[POW_BATCH];
+    PowBatch pb = {};
     for (uint32_t j = 0; j < cnt; j++) {
-      PowTab& t = tabs[j];
-      t.full = false;
+      PowTab& t = fresh[b0 + j];
+      t.full = full;
       t.h = h;
       t.bytes = ((size_t)nlo + nhi) * 32;
       t.lo = table_alloc(t.bytes);
       if (!t.lo) {
-        for (uint32_t q = 0; q < j; q++) table_release(tabs[q].lo, tabs[q].bytes);
+        for (uint32_t q = 0; q < j; q++) table_release(fresh[b0 + q].lo, fresh[b0 + q].bytes);
         return H2MI_ENOMEM;
       }
       t.hi = t.lo + nlo;
@@ -811,31 +682,25 @@ int get_powtabs(const uint64_t* bases /* m x 4 */, size_t m, uint32_t log_n, hip
       pb.hi[j] = t.hi;
       pb.base[j] = host_fe(bases + 4 * missing[b0 + j]);
     }
-    for (uint32_t j = cnt; j < POW_BATCH; j++) { pb.lo[j] = pb.lo[0]; pb.hi[j] = pb.hi[0]; pb.base[j] = pb.base[0]; }
     H2_LAUNCH("k_pow_table", k_pow_table2_b, dim3(ceil_div_u32(std::max(nlo, nhi), 256), 2, cnt), 256, 0, s, pb, h, log_n - h);
     for (uint32_t j = 0; j < cnt; j++) {
-      PowTab& t = tabs[j];
+      PowTab& t = fresh[b0 + j];
       H2_HIP(t.built.mark(s));
       t.last_use = g_epoch;
       g_powtab_bytes += t.bytes;
-      Key k;
-      memcpy(k.w, bases + 4 * missing[b0 + j], 32);
-      k.log_n = log_n;
-      k.full = false;
+      const Key k = make_key(bases + 4 * missing[b0 + j], log_n, full);
       g_powtabs[k] = t;
     }
   }
-  for (size_t i = 0; i < m; i++) {  // the freshly built ones (and duplicates of them)
-    Key k;
-    memcpy(k.w, bases + 4 * i, 32);
-    k.log_n = log_n;
-    k.full = false;
-    auto it = g_powtabs.find(k);
-    if (it == g_powtabs.end()) return H2MI_EHIP;
-    H2_HIP(it->second.built.use(s));
-    out[i] = it->second;
-  }
+  for (size_t i = 0; i < m; i++)
+    if (fresh_of[i] >= 0) out[i] = fresh[fresh_of[i]];
   return H2MI_OK;
+}
+int get_powtab(const uint64_t base[4], uint32_t log_n, hipStream_t s, PowTab* out, bool full) {
+  return powtabs_for(base, 1, log_n, full && log_n <= FULL_TABLE_MAX_LOG, s, out);
+}
+int get_powtabs(const uint64_t* bases /* m x 4 */, size_t m, uint32_t log_n, hipStream_t s, PowTab* out) {
+  return powtabs_for(bases, m, log_n, false, s, out);
 }
 
 static void choose_split(uint32_t log_n, Plan* pl) {
@@ -859,10 +724,12 @@ static void choose_split(uint32_t log_n, Plan* pl) {
   }
 }
 
+// log2 of the DFTs a pass's tile holds: 2^NTT_TILE_LOG elements, but no more DFTs than `avail_log` allows (a column pass: the
+// segment's stride, log_seg - m; the row pass: logN1)
+static uint32_t pass_logC(uint32_t m, uint32_t avail_log) { return std::min(m >= NTT_TILE_LOG ? 0u : NTT_TILE_LOG - m, avail_log); }
+
 static int get_plan(const uint64_t omega[4], uint32_t log_n, hipStream_t s, Plan* out) {
-  Key k;
-  memcpy(k.w, omega, 32);
-  k.log_n = log_n;
+  const Key k = make_key(omega, log_n);
   auto it = g_plans.find(k);
   if (it != g_plans.end()) {
     Plan& pl = it->second;
@@ -901,8 +768,7 @@ static int get_plan(const uint64_t omega[4], uint32_t log_n, hipStream_t s, Plan
   if (pl.P > 1 && log_n <= WMAT_MAX_LOG) {
     uint32_t log_seg = log_n;
     for (int p = 0; p + 1 < pl.P; p++) {
-      const uint32_t m = pl.m[p], logS = log_seg - m;
-      const uint32_t logC = std::min(m >= NTT_TILE_LOG ? 0u : NTT_TILE_LOG - m, logS);
+      const uint32_t m = pl.m[p], logC = pass_logC(m, log_seg - m);
       // the matrices are an accelerator, not a requirement: over budget or out of memory, older plans go first, and if that does
       // not help the pass keeps the two-level gather (ntt_dev reads wmat = nullptr as exactly that)
       const size_t wbytes = ((size_t)1 << log_seg) * 32;
@@ -955,6 +821,10 @@ void ntt_teardown() {
   }
   g_cur = nullptr;
   g_tmp = nullptr;
+  if (g_stage) H2_IGNORE(hipFree(g_stage));
+  g_stage = nullptr;
+  g_stage_bytes = 0;
+  g_pass_attr_set = false;
 }
 
 int ensure_tmp(size_t elems, hipStream_t s) {
@@ -998,6 +868,28 @@ int release_tmp(hipStream_t s) {
   return H2MI_OK;
 }
 
+// The instantiations of the pass kernels.  The compile-time form exists for 1024-element tiles and DFT sizes 2^4 .. 2^10 (every pass
+// of every transform >= 2^14); <0, 0> is the run-time form that serves every other geometry.  One list feeds both the launch and the
+// function attributes: a form cannot be launched without its attribute.
+using PassKernel = void (*)(PassParams);
+struct PassForm {
+  uint32_t ds, m;
+  PassKernel col, row;
+};
+#define H2_NTT_FORM(DS, M) {DS, M, k_ntt_pass_col<DS, M>, k_ntt_pass_row<DS, M>}
+static const PassForm g_pass_forms[] = {H2_NTT_FORM(0, 0),    H2_NTT_FORM(1024, 4), H2_NTT_FORM(1024, 5), H2_NTT_FORM(1024, 6),
+                                        H2_NTT_FORM(1024, 7), H2_NTT_FORM(1024, 8), H2_NTT_FORM(1024, 9), H2_NTT_FORM(1024, 10)};
+#undef H2_NTT_FORM
+static const PassForm& pass_form(uint32_t m, uint32_t logC) {
+  for (const PassForm& f : g_pass_forms)
+    if (f.ds == (1u << (m + logC)) && f.m == m) return f;
+  return g_pass_forms[0];
+}
+// the tile (nine limb planes of 2^(m + logC) elements) and the staged local twiddles
+static size_t pass_lds_bytes(uint32_t m, uint32_t logC) {
+  return ((size_t)1 << (m + logC)) * 36 + (m ? std::min<size_t>((size_t)1 << (m - 1), TW_STAGED) : 1) * 32;
+}
+
 // d_src == d_a: in place.  Otherwise the first pass reads d_src (src_len elements, zero beyond) and the last
 // pass writes d_a; d_src is left untouched.
 static int ntt_dev(fe* d_a, uint32_t log_n, const uint64_t omega[4], const uint64_t* pre, const uint64_t* post, hipStream_t s,
@@ -1020,36 +912,12 @@ static int ntt_dev(fe* d_a, uint32_t log_n, const uint64_t omega[4], const uint6
     rc = ensure_tmp(n, s);
     if (rc) return rc;
   }
-  constexpr uint32_t nthreads = 256;  // per workgroup of every pass
-  static bool attr_set = false;
-  if (!attr_set) {  // tiles above 64 KiB of LDS need the opt-in
-#define H2_NTT_ATTR(DS, M)                                                                                                                         \
-  H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass_col<DS, M>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));       \
-  H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass_row<DS, M>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-    H2_NTT_ATTR(0, 0);
-    H2_NTT_ATTR(1024, 4);
-    H2_NTT_ATTR(1024, 5);
-    H2_NTT_ATTR(1024, 6);
-    H2_NTT_ATTR(1024, 7);
-    H2_NTT_ATTR(1024, 8);
-    H2_NTT_ATTR(1024, 9);
-    H2_NTT_ATTR(1024, 10);
-#undef H2_NTT_ATTR
-    attr_set = true;
+  if (!g_pass_attr_set) {  // tiles above 64 KiB of LDS need the opt-in
+    for (const PassForm& f : g_pass_forms)
+      for (PassKernel kern : {f.col, f.row})
+        H2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    g_pass_attr_set = true;
   }
-// the compile-time form exists for 1024-element tiles and DFT sizes 2^7 .. 2^10 (every pass of every transform >= 2^14)
-#define H2_NTT_LAUNCH(NAME, KERNEL)                                                                                       \
-  do {                                                                                                                    \
-    const bool fixed_ = pp.m + pp.logC == 10;                                                                             \
-    if (fixed_ && pp.m == 10) H2_LAUNCH(NAME, (KERNEL<1024, 10>), nblocks, nthreads, shmem, s, pp);                        \
-    else if (fixed_ && pp.m == 9) H2_LAUNCH(NAME, (KERNEL<1024, 9>), nblocks, nthreads, shmem, s, pp);                     \
-    else if (fixed_ && pp.m == 8) H2_LAUNCH(NAME, (KERNEL<1024, 8>), nblocks, nthreads, shmem, s, pp);                     \
-    else if (fixed_ && pp.m == 7) H2_LAUNCH(NAME, (KERNEL<1024, 7>), nblocks, nthreads, shmem, s, pp);                     \
-    else if (fixed_ && pp.m == 6) H2_LAUNCH(NAME, (KERNEL<1024, 6>), nblocks, nthreads, shmem, s, pp);                     \
-    else if (fixed_ && pp.m == 5) H2_LAUNCH(NAME, (KERNEL<1024, 5>), nblocks, nthreads, shmem, s, pp);                     \
-    else if (fixed_ && pp.m == 4) H2_LAUNCH(NAME, (KERNEL<1024, 4>), nblocks, nthreads, shmem, s, pp);                     \
-    else H2_LAUNCH(NAME, (KERNEL<0, 0>), nblocks, nthreads, shmem, s, pp);                                                 \
-  } while (0)
   // buffer schedule: P=1: a->a ; P=2: a->tmp, tmp->a ; P=3: a->tmp, tmp->tmp, tmp->a
   uint32_t log_seg = log_n;
   for (int p = 0; p < pl.P; p++) {
@@ -1067,7 +935,6 @@ static int ntt_dev(fe* d_a, uint32_t log_n, const uint64_t omega[4], const uint6
     pp.thi = pl.tw.hi;
     pp.h = pl.tw.h;
     pp.tfull = pl.tw.full;
-    pp.remap = 1;  // XCD-aware block order
     // below 2^18 a pass is a few dozen tiles and the regrouping barrier before the last round costs more than the LDS round trips
     // it saves (2^16: 36.0 -> 36.8 us fused; 2^20: 134.7 -> 129.5, 2^24: 2000 -> 1958: profiles/r04_ntt_fused_rounds.txt)
     pp.nofuse = log_n < 18 ? 1 : 0;
@@ -1077,38 +944,40 @@ static int ntt_dev(fe* d_a, uint32_t log_n, const uint64_t omega[4], const uint6
       pp.ph = pt.h;
       pp.pfull = pt.full;
     }
-    uint32_t logC = pp.m >= NTT_TILE_LOG ? 0 : NTT_TILE_LOG - pp.m;
     if (!last) {
-      uint32_t logS = log_seg - pp.m;
-      if (logC > logS) logC = logS;
-      pp.logC = logC;
+      pp.logC = pass_logC(pp.m, log_seg - pp.m);
       pp.wmat = pl.wmat[p];  // null: the pass gathers its twiddles
-      uint32_t nblocks = (uint32_t)(n >> (pp.m + logC));
-      size_t shmem = ((size_t)1 << (pp.m + logC)) * 36 + std::min<size_t>((size_t)1 << (pp.m - 1), TW_STAGED) * 32;
-      H2_NTT_LAUNCH("k_ntt_pass_col", k_ntt_pass_col);
     } else {
       pp.has_post = post ? 1 : 0;
       pp.post = post ? f29_from_mont256<F9>(host_fe(post).v) : f29_zero();
-      if (pl.P == 1) {
-        pp.logN1 = 0;
-        pp.logN2 = 0;
-      } else if (pl.P == 2) {
-        pp.logN1 = pl.m[0];
-        pp.logN2 = 0;
-      } else {
-        pp.logN1 = pl.m[0];
-        pp.logN2 = pl.m[1];
-      }
-      if (logC > pp.logN1) logC = pp.logN1;
-      pp.logC = logC;
-      uint32_t nblocks = (uint32_t)(n >> (pp.m + logC));
-      size_t shmem = ((size_t)1 << (pp.m + logC)) * 36 + (pp.m ? std::min<size_t>((size_t)1 << (pp.m - 1), TW_STAGED) : 1) * 32;
-      H2_NTT_LAUNCH("k_ntt_pass_row", k_ntt_pass_row);
+      pp.logN1 = pl.P > 1 ? pl.m[0] : 0;
+      pp.logN2 = pl.P > 2 ? pl.m[1] : 0;
+      pp.logC = pass_logC(pp.m, pp.logN1);
     }
+    const PassForm& f = pass_form(pp.m, pp.logC);
+    const PassKernel kern = last ? f.row : f.col;
+    H2_LAUNCH(last ? "k_ntt_pass_row" : "k_ntt_pass_col", kern, (uint32_t)(n >> (pp.m + pp.logC)), 256, pass_lds_bytes(pp.m, pp.logC), s, pp);
     log_seg -= pp.m;
   }
   if (pl.P > 1) return release_tmp(s);
   return H2MI_OK;
+}
+
+// the prologue of the entry points over base^i, i < n: checks, lock, stream, the table of the next power of two; then f(table, stream)
+template <class F>
+static int with_powers(const void* d, size_t n, const uint64_t base[4], h2mi_stream_t stream, F&& f) {
+  H2_REQUIRE_INIT();
+  if (!d || !base || n == 0) return H2MI_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  CallScope scope_;
+  hipStream_t s = pick_stream(stream);
+  uint32_t log_n = 0;
+  while (((size_t)1 << log_n) < n) log_n++;
+  if (log_n > 31) return H2MI_ERANGE;
+  PowTab pt;
+  int rc = get_powtab(base, log_n, s, &pt);
+  if (rc) return rc;
+  return f(pt, s);
 }
 
 }  // namespace h2
@@ -1144,23 +1013,19 @@ int h2mi_ntt_ext_bn254_fr(uint64_t* a, uint32_t log_n, const uint64_t omega[4], 
   CallScope scope_;
   hipStream_t s = ctx().stream;
   const size_t bytes = ((size_t)1 << log_n) * 32;
-  // device staging kept between calls (grow-only, like the ping-pong scratch): EvaluationDomain calls this
-  // dozens of times per proof with two sizes
-  static fe* stage = nullptr;
-  static size_t stage_bytes = 0;
-  if (stage_bytes < bytes) {
-    if (stage) {
+  if (g_stage_bytes < bytes) {
+    if (g_stage) {
       H2_HIP(hipStreamSynchronize(s));
-      H2_IGNORE(hipFree(stage));
-      stage = nullptr;
-      stage_bytes = 0;
+      H2_IGNORE(hipFree(g_stage));
+      g_stage = nullptr;
+      g_stage_bytes = 0;
     }
-    hipError_t e = hipMalloc(&stage, bytes);
+    hipError_t e = hipMalloc(&g_stage, bytes);
     if (e == hipErrorOutOfMemory) return H2MI_ENOMEM;
     H2_HIP(e);
-    stage_bytes = bytes;
+    g_stage_bytes = bytes;
   }
-  fe* d = stage;
+  fe* d = g_stage;
   int rc = H2MI_OK;
   if (hipMemcpyAsync(d, a, bytes, hipMemcpyHostToDevice, s) != hipSuccess) rc = H2MI_EHIP;
   if (!rc) rc = ntt_dev(d, log_n, omega, pre, post, s);
@@ -1174,38 +1039,18 @@ int h2mi_ntt_bn254_fr(uint64_t* a, const uint64_t omega[4], uint32_t log_n) {
 }
 
 int h2mi_fr_scale_powers_dev(void* d_a, size_t n, const uint64_t base[4], const uint64_t* post, h2mi_stream_t stream) {
-  H2_REQUIRE_INIT();
-  if (!d_a || !base || n == 0) return H2MI_EINVAL;
-  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
-  CallScope scope_;
-  hipStream_t s = pick_stream(stream);
-  uint32_t log_n = 0;
-  while (((size_t)1 << log_n) < n) log_n++;
-  if (log_n > 31) return H2MI_ERANGE;
-  PowTab pt;
-  int rc = get_powtab(base, log_n, s, &pt);
-  if (rc) return rc;
-  f29 p = post ? f29_from_mont256<F9>(host_fe(post).v) : f29_zero();
-  H2_LAUNCH("k_scale_powers", k_scale_powers, ceil_div_u32(n, 256), 256, 0, s, (fe*)d_a, n, (const fe*)pt.lo, (const fe*)pt.hi, pt.h,
-            post ? 1 : 0, p);
-  return H2MI_OK;
+  const f29 p = post ? f29_from_mont256<F9>(host_fe(post).v) : f29_zero();
+  return with_powers(d_a, n, base, stream, [&](const PowTab& pt, hipStream_t s) -> int {
+    H2_LAUNCH("k_scale_powers", k_scale_powers, ceil_div_u32(n, 256), 256, 0, s, (fe*)d_a, n, (const fe*)pt.lo, (const fe*)pt.hi, pt.h, post ? 1 : 0, p);
+    return H2MI_OK;
+  });
 }
 
 int h2mi_fr_powers_dev(void* d_out, size_t n, const uint64_t base[4], h2mi_stream_t stream) {
-  H2_REQUIRE_INIT();
-  if (!d_out || !base || n == 0) return H2MI_EINVAL;
-  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
-  CallScope scope_;
-  hipStream_t s = pick_stream(stream);
-  uint32_t log_n = 0;
-  while (((size_t)1 << log_n) < n) log_n++;
-  if (log_n > 31) return H2MI_ERANGE;
-  PowTab pt;
-  int rc = get_powtab(base, log_n, s, &pt);
-  if (rc) return rc;
-  H2_LAUNCH("k_powers", k_powers, ceil_div_u32(n, 256), 256, 0, s, (fe*)d_out, n, (const fe*)pt.lo, (const fe*)pt.hi, pt.h);
-  return H2MI_OK;
+  return with_powers(d_out, n, base, stream, [&](const PowTab& pt, hipStream_t s) -> int {
+    H2_LAUNCH("k_powers", k_powers, ceil_div_u32(n, 256), 256, 0, s, (fe*)d_out, n, (const fe*)pt.lo, (const fe*)pt.hi, pt.h);
+    return H2MI_OK;
+  });
 }
-
 
 }  // extern "C"

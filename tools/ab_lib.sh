@@ -4,7 +4,8 @@
 # pointing at a private directory that holds the build under the name libh2mi.so.
 #   usage: gpurun -- bash tools/ab_lib.sh <mode> [old.so] [new.so] [repeats]
 #   modes: msm (MSM 2^20 + replay step) | proof (2^20 proofs, both hosts) | small (C++ proofs at 2^5 / 2^8 / 2^16 / 2^20) |
-#          range (C++ range DEGREE 22 + poseidon) | poly (opening-argument kernels) | evalh (evaluate_h)
+#          range (C++ range DEGREE 22 + poseidon) | poly (opening-argument kernels) | evalh (evaluate_h) |
+#          ntt (transforms 2^14 .. 2^24: unfused / fused forms, three passes, two-level tables)
 #   defaults: old = halo2-scaffold_amd/libh2mi.so.prev (git-ignored, travels with gpurun), new = halo2-scaffold_amd/libh2mi.so
 set -euo pipefail
 cd "${GRAFT_REPO_ROOT:?run on the GPU box through gpurun}"
@@ -35,6 +36,7 @@ for r in $(seq "$REP"); do
       range) H2MI_PROOFS=5 cx ./examples/halo2_lib range 22 16 77 0x5ec2e7 1 | grep steady; H2MI_PROOFS=8 cx ./examples/halo2_lib poseidon 20 0 5 0x5ec2e7 1 | grep steady ;;
       poly) py tools/poly_sweep.py 20 22 | grep log_n | cut -c1-200 ;;
       evalh) py tools/poly_sweep.py 20 | grep evaluate_h | cut -c1-140 ;;
+      ntt) py tools/ntt_sweep.py 14 16 17 18 20 21 22 24 | cut -c1-120 ;;
       *) echo "unknown mode $MODE" >&2; exit 2 ;;
     esac
   done
