@@ -8,6 +8,7 @@ reaches through ``create_proof`` (reference examples/standard_plonk.rs:41-49, sr
   params.ParamsKZG                         halo2_proofs::poly::kzg::commitment::ParamsKZG
   replay.StandardPlonkReplay               the MSM/NTT sequence one StandardPlonk proof issues
   transcript.Blake2bWrite / Blake2bRead    halo2_proofs::transcript (Challenge255), serde: to_repr / to_bytes
+  custom.ConstraintSystem / Keys / create_proof       halo2's create_gate API: circuits with hand-written gates (src/circuits/is_zero.rs, or.rs)
   scaffold.mock / gen_key / prove_private / prove   the reference's src/scaffold.rs, name for name, over flex.* (the halo2-lib builders)
 
 All arithmetic runs in hand-written HIP kernels; there is no CPU fallback — importing this package
@@ -22,3 +23,4 @@ from .arithmetic import best_fft, best_multiexp, eval_polynomial, kate_division,
 from .domain import EvaluationDomain  # noqa: F401
 from .params import ParamsKZG, gen_srs, gen_srs_secret  # noqa: F401
 from . import serde, transcript  # noqa: F401
+from . import custom  # noqa: F401

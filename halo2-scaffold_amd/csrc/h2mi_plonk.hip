@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "h2mi_expr.hpp"
 #include "h2mi_fr_tables.h"
 #include "scan.cuh"
 
@@ -471,34 +472,32 @@ struct FlexConsts {
   fe beta, gamma, y, delta, zeta;  // Montgomery-2^256 words
   fe tinv[16];
 };
-__global__ void __launch_bounds__(256) k_evaluate_h_flex(FlexCosets c, uint32_t ext_k, uint32_t k, uint32_t last_rot, FlexConsts h, const fe* xlo,
-                                                          const fe* xhi, uint32_t xh, fe* out) {
+// one domain (Montgomery-2^261), every value normalized and below ~8 p between operations
+namespace gen {
+__device__ __forceinline__ f29 ld(const fe* p) { return f29_from_mont256<F9>(fe_load(p).v); }
+__device__ __forceinline__ f29 cst(const fe& v) { return f29_from_mont256<F9>(v.v); }
+__device__ __forceinline__ f29 mul(const f29& a, const f29& b) { return f29_mul<F9>(a, b); }                              // b normalized (every value here is)
+__device__ __forceinline__ f29 add(const f29& a, const f29& b) { return f29_normalize(f29_add(a, b)); }
+__device__ __forceinline__ f29 sub(const f29& a, const f29& b) { return f29_normalize(f29_sub(a, b, F9::K4)); }           // b < 4p - 2^232
+__device__ __forceinline__ f29 red(const f29& a) { return f29_mul<F9>(a, f29_const<F9>(F9::ONE)); }                       // back below 1.1 p (ONE = 2^261 mod p)
+__device__ __forceinline__ void horner(f29& acc, const f29& y, const f29& term) { acc = add(mul(acc, y), term); }
+}  // namespace gen
+// What follows the gate terms in evaluate_h's order — the permutation argument (chunks of any length), then the lookups — folded into
+// `acc` by Horner's rule in y, times t_inv, stored: the tail k_evaluate_h_flex and k_evaluate_h_expr share.
+__device__ __forceinline__ void evaluate_h_tail(const FlexCosets& c, uint32_t ext_k, uint32_t k, uint32_t last_rot, const FlexConsts& h, const fe* xlo,
+                                                const fe* xhi, uint32_t xh, uint32_t idx, f29 acc, const f29& y, fe* out) {
+  using namespace gen;
   const uint32_t size = 1u << ext_k, rot = 1u << (ext_k - k);
-  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= size) return;
   auto at = [&](int r) { return (idx + size + (uint32_t)(r * (int)rot)) & (size - 1); };
   const uint32_t r_next = at(1), r_prev = at(-1), r_last = at(-(int)last_rot);
-  // one domain (Montgomery-2^261), every value normalized and below ~8 p between operations
-  auto ld = [](const fe* p) { return f29_from_mont256<F9>(fe_load(p).v); };
-  auto cst = [](const fe& v) { return f29_from_mont256<F9>(v.v); };
-  auto mul = [](const f29& a, const f29& b) { return f29_mul<F9>(a, b); };                            // b normalized (every value here is)
-  auto add = [](const f29& a, const f29& b) { return f29_normalize(f29_add(a, b)); };
-  auto sub = [](const f29& a, const f29& b) { return f29_normalize(f29_sub(a, b, F9::K4)); };           // b < 4p - 2^232
-  auto red = [](const f29& a) { return f29_mul<F9>(a, f29_const<F9>(F9::ONE)); };                       // back below 1.1 p (ONE = 2^261 mod p)
-  const f29 one = f29_const<F9>(F9::ONE), beta = cst(h.beta), gamma = cst(h.gamma), y = cst(h.y), delta = cst(h.delta);
-  f29 acc = f29_zero();
-  auto horner = [&](const f29& term) { acc = add(mul(acc, y), term); };
-  for (uint32_t g = 0; g < c.n_gates; g++) {
-    const fe* a = c.gate_a[g];
-    horner(mul(sub(add(ld(&a[idx]), mul(ld(&a[at(1)]), ld(&a[at(2)]))), ld(&a[at(3)])), ld(&c.gate_q[g][idx])));
-  }
+  const f29 one = f29_const<F9>(F9::ONE), beta = cst(h.beta), gamma = cst(h.gamma), delta = cst(h.delta);
   const f29 l0 = ld(&c.l0[idx]), ll = ld(&c.l_last[idx]), lact = ld(&c.l_active[idx]);
   if (c.n_perm) {
     const uint32_t sets = (c.n_perm + c.chunk - 1) / c.chunk;
     const f29 z_first = ld(&c.perm_z[0][idx]), z_lastset = ld(&c.perm_z[sets - 1][idx]);
-    horner(mul(sub(one, z_first), l0));
-    horner(mul(red(sub(mul(z_lastset, z_lastset), z_lastset)), ll));
-    for (uint32_t s = 1; s < sets; s++) horner(mul(sub(ld(&c.perm_z[s][idx]), ld(&c.perm_z[s - 1][r_last])), l0));
+    horner(acc, y, mul(sub(one, z_first), l0));
+    horner(acc, y, mul(red(sub(mul(z_lastset, z_lastset), z_lastset)), ll));
+    for (uint32_t s = 1; s < sets; s++) horner(acc, y, mul(sub(ld(&c.perm_z[s][idx]), ld(&c.perm_z[s - 1][r_last])), l0));
     f29 cur = mul(mul(pow2tab(xlo, xhi, xh, idx), cst(h.zeta)), beta);  // beta * X, X = zeta * extended_omega^idx
     for (uint32_t s = 0; s < sets; s++) {
       f29 left = ld(&c.perm_z[s][r_next]), right = ld(&c.perm_z[s][idx]);
@@ -509,7 +508,7 @@ __global__ void __launch_bounds__(256) k_evaluate_h_flex(FlexCosets c, uint32_t 
         right = mul(right, add(add(val, cur), gamma));
         cur = mul(cur, delta);
       }
-      horner(mul(sub(left, right), lact));
+      horner(acc, y, mul(sub(left, right), lact));
     }
   }
   for (uint32_t l = 0; l < c.n_lookups; l++) {
@@ -517,17 +516,94 @@ __global__ void __launch_bounds__(256) k_evaluate_h_flex(FlexCosets c, uint32_t 
     if (c.lk_in_b[l]) a_in = mul(a_in, ld(&c.lk_in_b[l][idx]));
     const f29 t_in = ld(&c.lk_table[l][idx]), ap = ld(&c.lk_pin[l][idx]), ap_prev = ld(&c.lk_pin[l][r_prev]), sp = ld(&c.lk_ptab[l][idx]);
     const f29 lz = ld(&c.lk_z[l][idx]), lz_next = ld(&c.lk_z[l][r_next]);
-    horner(mul(sub(one, lz), l0));
-    horner(mul(red(sub(mul(lz, lz), lz)), ll));
+    horner(acc, y, mul(sub(one, lz), l0));
+    horner(acc, y, mul(red(sub(mul(lz, lz), lz)), ll));
     const f29 lhs = mul(mul(lz_next, add(ap, beta)), add(sp, gamma)), rhs = mul(mul(lz, add(a_in, beta)), add(t_in, gamma));
-    horner(mul(sub(lhs, rhs), lact));
+    horner(acc, y, mul(sub(lhs, rhs), lact));
     const f29 d = sub(ap, sp);
-    horner(mul(d, l0));
-    horner(mul(red(mul(d, sub(ap, ap_prev))), lact));
+    horner(acc, y, mul(d, l0));
+    horner(acc, y, mul(red(mul(d, sub(ap, ap_prev))), lact));
   }
   fe o;
   f29_to_mont256<F9>(mul(acc, cst(h.tinv[idx & (rot - 1)])), o.v);
   fe_store(&out[idx], o);
+}
+__global__ void __launch_bounds__(256) k_evaluate_h_flex(FlexCosets c, uint32_t ext_k, uint32_t k, uint32_t last_rot, FlexConsts h, const fe* xlo,
+                                                          const fe* xhi, uint32_t xh, fe* out) {
+  using namespace gen;
+  const uint32_t size = 1u << ext_k, rot = 1u << (ext_k - k);
+  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= size) return;
+  auto at = [&](int r) { return (idx + size + (uint32_t)(r * (int)rot)) & (size - 1); };
+  const f29 y = cst(h.y);
+  f29 acc = f29_zero();
+  for (uint32_t g = 0; g < c.n_gates; g++) {
+    const fe* a = c.gate_a[g];
+    horner(acc, y, mul(sub(add(ld(&a[idx]), mul(ld(&a[at(1)]), ld(&a[at(2)]))), ld(&a[at(3)])), ld(&c.gate_q[g][idx])));
+  }
+  evaluate_h_tail(c, ext_k, k, last_rot, h, xlo, xhi, xh, idx, acc, y, out);
+}
+
+// ---- quotient numerator with the gates as DATA: a postfix program over column queries (h2mi_gate_program, include/h2mi.h) -------------
+// The arithmetic is k_evaluate_h_flex's (one domain, operands converted on load, every value normalized between operations, Horner in y
+// over the polynomials in program order, then the shared tail).  New is the interpreter:
+//   * the program is wave-uniform: the loop counter does not depend on the lane and the ops / column pointers are read through
+//     __restrict__ const pointers at uniform addresses (scalar loads), so dispatch is a uniform branch and a query's base pointer and
+//     row offset are scalars;
+//   * the operand stack keeps its top in registers and the rest in LDS as [level][limb][thread] (a wavefront's 64 lanes read 64
+//     consecutive words: no bank conflict), max_stack - 1 levels of 9 KB, sized per launch — never a runtime-indexed private array;
+//   * the column-pointer table, the constants (already Montgomery-2^261 words) and the ops live in ONE device buffer: the launch carries
+//     three addresses into it, not 129 pointers.
+// Ops as uploaded: word x = code | index << 8, word y = the row offset of the rotation, (r mod n) 2^(ext_k - k).  The uploader inserts
+// EX_RED where its static bound on a value would otherwise pass what the next operation takes (see expr_encode).
+enum : uint32_t { EX_COL = 0, EX_CONST, EX_ADD, EX_SUB, EX_MUL, EX_NEG, EX_RED, EX_END };
+constexpr uint32_t EX_COLS = H2MI_EXPR_MAX_ADVICE + H2MI_EXPR_MAX_FIXED + 1;  // advice, fixed, the instance column
+__global__ void __launch_bounds__(256) k_evaluate_h_expr(FlexCosets c, const fe* const* __restrict__ cols, const fe* __restrict__ consts,
+                                                          const uint2* __restrict__ ops, uint32_t n_ops, uint32_t ext_k, uint32_t k, uint32_t last_rot,
+                                                          FlexConsts h, const fe* xlo, const fe* xhi, uint32_t xh, fe* out) {
+  using namespace gen;
+  extern __shared__ uint32_t ex_stack[];  // [level][limb][thread]
+  const uint32_t size = 1u << ext_k;
+  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= size) return;  // no barrier below: a thread touches its own stack slots only
+  uint32_t* const slot = ex_stack + threadIdx.x;
+  auto spill = [&](const f29& v, uint32_t level) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) slot[(level * 9 + i) * 256] = v.v[i];
+  };
+  auto fill = [&](uint32_t level) {
+    f29 v;
+#pragma unroll
+    for (int i = 0; i < 9; i++) v.v[i] = slot[(level * 9 + i) * 256];
+    return v;
+  };
+  const f29 y = cst(h.y);
+  f29 acc = f29_zero(), tos = f29_zero();
+  uint32_t sp = 0;  // values on the stack: tos and LDS levels 0 .. sp - 2
+  for (uint32_t pc = 0; pc < n_ops; pc++) {
+    const uint2 op = ops[pc];
+    const uint32_t code = op.x & 0xffu, index = op.x >> 8;
+    if (code <= EX_CONST) {
+      if (sp) spill(tos, sp - 1);
+      sp++;
+      if (code == EX_COL) tos = ld(&cols[index][(idx + op.y) & (size - 1)]);
+      else tos = load_unpack(&consts[index]);
+    } else if (code <= EX_MUL) {
+      const f29 a = fill(sp - 2);
+      sp--;
+      if (code == EX_MUL) tos = mul(a, tos);
+      else if (code == EX_ADD) tos = add(a, tos);
+      else tos = sub(a, tos);
+    } else if (code == EX_NEG) {
+      tos = sub(f29_zero(), tos);
+    } else if (code == EX_RED) {
+      tos = red(tos);
+    } else {  // EX_END: the one value left is this polynomial
+      horner(acc, y, tos);
+      sp = 0;
+    }
+  }
+  evaluate_h_tail(c, ext_k, k, last_rot, h, xlo, xhi, xh, idx, acc, y, out);
 }
 
 // the one inversion on the critical path, by division steps on the 32-bit-limb layer (fe_inv_ds; round 4: the shift / subtract
@@ -633,6 +709,61 @@ static void fill_common(HConsts& h, const fe& beta, const fe& gamma, const fe& d
     cur = h_mul256(cur, delta);
   }
   for (uint32_t i = 0; i < rot; i++) h.tinv[i] = h_level(host_fe(t_inv + 4 * i), -1);
+}
+
+// the permutation / lookup / Lagrange pointers of h2mi_flex_cosets or h2mi_expr_cosets (the same fields) -> the kernels' argument
+template <class Cosets>
+static bool fill_tail(FlexCosets& fc, const Cosets& c) {
+  fc.n_perm = c.n_perm; fc.chunk = c.chunk_len ? c.chunk_len : 1; fc.n_lookups = c.n_lookups;
+  for (uint32_t j = 0; j < c.n_perm; j++) {
+    fc.perm_value[j] = (const fe*)c.perm_value[j]; fc.perm_sigma[j] = (const fe*)c.perm_sigma[j];
+    if (!fc.perm_value[j] || !fc.perm_sigma[j]) return false;
+  }
+  for (uint32_t q = 0; c.n_perm && q < (c.n_perm + fc.chunk - 1) / fc.chunk; q++) {
+    fc.perm_z[q] = (const fe*)c.perm_z[q];
+    if (!fc.perm_z[q]) return false;
+  }
+  for (uint32_t l = 0; l < c.n_lookups; l++) {
+    fc.lk_in[l] = (const fe*)c.lookup_input[l]; fc.lk_in_b[l] = (const fe*)c.lookup_input_b[l]; fc.lk_table[l] = (const fe*)c.lookup_table[l];
+    fc.lk_pin[l] = (const fe*)c.lookup_permuted_input[l]; fc.lk_ptab[l] = (const fe*)c.lookup_permuted_table[l]; fc.lk_z[l] = (const fe*)c.lookup_z[l];
+    if (!fc.lk_in[l] || !fc.lk_table[l] || !fc.lk_pin[l] || !fc.lk_ptab[l] || !fc.lk_z[l]) return false;
+  }
+  fc.l0 = (const fe*)c.l0; fc.l_last = (const fe*)c.l_last; fc.l_active = (const fe*)c.l_active;
+  return fc.l0 && fc.l_last && fc.l_active;
+}
+
+// The program as the kernel reads it.  Every stack value carries a static bound in units of p (a converted load 1.04, a constant 1,
+// a product 1 + 0.006 a b since p / 2^261 < 0.006, a sum a + b, a difference a + 4, a negation 4, EX_RED 1 + 0.006 a); EX_RED goes
+// in front of a SUB / NEG whose subtrahend may reach 4p - 2^232 (f29_sub's contract with K4) and behind an operation whose result
+// may pass 8p, the range k_evaluate_h_flex keeps its values in.  The reference's gates and the vertical gate need none.
+static void expr_encode(const h2mi_gate_program* g, uint32_t k, uint32_t extended_k, std::vector<uint2>& out) {
+  const uint32_t n = 1u << k, rot = 1u << (extended_k - k);
+  double b[H2MI_MAX_EXPR_STACK];
+  uint32_t sp = 0;
+  auto emit = [&](uint32_t code, uint32_t index = 0, uint32_t off = 0) { out.push_back(make_uint2(code | index << 8, off)); };
+  auto cap = [&] {
+    if (b[sp - 1] > 8.0) { emit(EX_RED); b[sp - 1] = 1.0 + 0.006 * b[sp - 1]; }
+  };
+  auto small_top = [&] {
+    if (b[sp - 1] > 3.9) { emit(EX_RED); b[sp - 1] = 1.0 + 0.006 * b[sp - 1]; }
+  };
+  for (uint32_t i = 0; i < g->n_ops; i++) {
+    const h2mi_expr_op& o = g->ops[i];
+    switch (o.op) {
+      case H2MI_EXPR_ADVICE: case H2MI_EXPR_FIXED: case H2MI_EXPR_INSTANCE: {
+        const uint32_t slot = o.op == H2MI_EXPR_ADVICE ? o.index : o.op == H2MI_EXPR_FIXED ? H2MI_EXPR_MAX_ADVICE + o.index : EX_COLS - 1;
+        emit(EX_COL, slot, (uint32_t)(((int64_t)o.rotation + n) % n) * rot);
+        b[sp++] = 1.04;
+        break;
+      }
+      case H2MI_EXPR_CONSTANT: emit(EX_CONST, o.index); b[sp++] = 1.0; break;
+      case H2MI_EXPR_ADD: emit(EX_ADD); b[sp - 2] += b[sp - 1]; sp--; cap(); break;
+      case H2MI_EXPR_SUB: small_top(); emit(EX_SUB); b[sp - 2] += 4.0; sp--; cap(); break;
+      case H2MI_EXPR_MUL: emit(EX_MUL); b[sp - 2] = 1.0 + 0.006 * b[sp - 2] * b[sp - 1]; sp--; break;
+      case H2MI_EXPR_NEG: small_top(); emit(EX_NEG); b[sp - 1] = 4.0; break;
+      default: emit(EX_END); sp = 0; break;  // H2MI_EXPR_END (expr_walk has refused anything else)
+    }
+  }
 }
 
 }  // namespace h2
@@ -934,26 +1065,12 @@ int h2mi_plonk_evaluate_h_flex_dev(const h2mi_flex_cosets* c, uint32_t k, uint32
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 64 <= 4096, "the quotient kernel's arguments travel by value");
   FlexCosets fc;
   memset(&fc, 0, sizeof(fc));
-  fc.n_gates = c->n_gates; fc.n_perm = c->n_perm; fc.chunk = c->chunk_len ? c->chunk_len : 1; fc.n_lookups = c->n_lookups;
+  fc.n_gates = c->n_gates;
   for (uint32_t g = 0; g < c->n_gates; g++) {
     fc.gate_a[g] = (const fe*)c->gate_a[g]; fc.gate_q[g] = (const fe*)c->gate_q[g];
     if (!fc.gate_a[g] || !fc.gate_q[g]) return H2MI_EINVAL;
   }
-  for (uint32_t j = 0; j < c->n_perm; j++) {
-    fc.perm_value[j] = (const fe*)c->perm_value[j]; fc.perm_sigma[j] = (const fe*)c->perm_sigma[j];
-    if (!fc.perm_value[j] || !fc.perm_sigma[j]) return H2MI_EINVAL;
-  }
-  for (uint32_t q = 0; c->n_perm && q < (c->n_perm + fc.chunk - 1) / fc.chunk; q++) {
-    fc.perm_z[q] = (const fe*)c->perm_z[q];
-    if (!fc.perm_z[q]) return H2MI_EINVAL;
-  }
-  for (uint32_t l = 0; l < c->n_lookups; l++) {
-    fc.lk_in[l] = (const fe*)c->lookup_input[l]; fc.lk_in_b[l] = (const fe*)c->lookup_input_b[l]; fc.lk_table[l] = (const fe*)c->lookup_table[l];
-    fc.lk_pin[l] = (const fe*)c->lookup_permuted_input[l]; fc.lk_ptab[l] = (const fe*)c->lookup_permuted_table[l]; fc.lk_z[l] = (const fe*)c->lookup_z[l];
-    if (!fc.lk_in[l] || !fc.lk_table[l] || !fc.lk_pin[l] || !fc.lk_ptab[l] || !fc.lk_z[l]) return H2MI_EINVAL;
-  }
-  fc.l0 = (const fe*)c->l0; fc.l_last = (const fe*)c->l_last; fc.l_active = (const fe*)c->l_active;
-  if (!fc.l0 || !fc.l_last || !fc.l_active) return H2MI_EINVAL;
+  if (!fill_tail(fc, *c)) return H2MI_EINVAL;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
@@ -969,6 +1086,62 @@ int h2mi_plonk_evaluate_h_flex_dev(const h2mi_flex_cosets* c, uint32_t k, uint32
   H2_LAUNCH("k_evaluate_h_flex", k_evaluate_h_flex, ceil_div_u32(size, 256), 256, 0, s, fc, extended_k, k, blinding_factors + 1, hc_, (const fe*)px.lo,
             (const fe*)px.hi, px.h, (fe*)d_h_out);
   return H2MI_OK;
+}
+
+int h2mi_plonk_evaluate_h_expr_dev(const h2mi_expr_cosets* c, const h2mi_gate_program* gates, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
+                                   const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
+                                   const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!c || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
+  if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  if (c->n_perm > H2MI_FLEX_MAX_PERM || c->n_lookups > H2MI_FLEX_MAX_LOOKUPS || (c->n_perm && c->chunk_len == 0)) return H2MI_EINVAL;
+  ExprShape shape;
+  int rc = expr_walk(gates, k, [&](uint32_t kind, uint32_t index, int32_t) {
+    return kind == H2MI_EXPR_ADVICE ? index < H2MI_EXPR_MAX_ADVICE && c->advice[index]
+         : kind == H2MI_EXPR_FIXED  ? index < H2MI_EXPR_MAX_FIXED && c->fixed[index]
+                                    : index == 0 && c->instance;
+  }, &shape);
+  if (rc) return rc;
+  static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
+  FlexCosets fc;
+  memset(&fc, 0, sizeof(fc));
+  if (!fill_tail(fc, *c)) return H2MI_EINVAL;
+  std::vector<uint2> ops;
+  expr_encode(gates, k, extended_k, ops);
+  // one buffer: the column-pointer table, the constants as Montgomery-2^261 words, the ops (each part a whole number of 32-byte words)
+  const size_t cols_fe = (EX_COLS * sizeof(void*) + 31) / 32, const_fe = std::max<size_t>(gates->n_constants, 1), ops_fe = (ops.size() * 8 + 31) / 32;
+  std::vector<fe> image(cols_fe + const_fe + ops_fe);
+  memset(image.data(), 0, image.size() * sizeof(fe));
+  {
+    const void** tab = (const void**)image.data();
+    for (uint32_t i = 0; i < H2MI_EXPR_MAX_ADVICE; i++) tab[i] = c->advice[i];
+    for (uint32_t i = 0; i < H2MI_EXPR_MAX_FIXED; i++) tab[H2MI_EXPR_MAX_ADVICE + i] = c->fixed[i];
+    tab[EX_COLS - 1] = c->instance;
+    for (uint32_t i = 0; i < gates->n_constants; i++) image[cols_fe + i] = h_canon(f29_from_mont256<F9>(host_fe(gates->constants + 4 * i).v));
+    memcpy(&image[cols_fe + const_fe], ops.data(), ops.size() * 8);
+  }
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  CallScope scope_;
+  hipStream_t s = pick_stream(stream);
+  PowTab px;
+  rc = get_powtab(extended_omega, extended_k, s, &px);
+  if (rc) return rc;
+  rc = ensure_tmp(image.size(), s);
+  if (rc) return rc;
+  fe* d_image = tmp_base();
+  // pageable source: the copy has left `image` when the call returns
+  H2_HIP(hipMemcpyAsync(d_image, image.data(), image.size() * sizeof(fe), hipMemcpyHostToDevice, s));
+  const uint32_t rot = 1u << (extended_k - k);
+  FlexConsts hc_;
+  memset(&hc_, 0, sizeof(hc_));
+  hc_.beta = host_fe(beta); hc_.gamma = host_fe(gamma); hc_.y = host_fe(y); hc_.delta = host_fe(delta); hc_.zeta = host_fe(zeta);
+  for (uint32_t i = 0; i < rot; i++) hc_.tinv[i] = host_fe(t_inv + 4 * i);
+  const uint32_t size = 1u << extended_k;
+  const size_t lds = (size_t)(shape.max_stack - 1) * 9 * 256 * sizeof(uint32_t);  // at most 7 levels: 63 KB
+  H2_LAUNCH("k_evaluate_h_expr", k_evaluate_h_expr, ceil_div_u32(size, 256), 256, lds, s, fc, (const fe* const*)d_image, (const fe*)(d_image + cols_fe),
+            (const uint2*)(d_image + cols_fe + const_fe), (uint32_t)ops.size(), extended_k, k, blinding_factors + 1, hc_, (const fe*)px.lo,
+            (const fe*)px.hi, px.h, (fe*)d_h_out);
+  return release_tmp(s);
 }
 
 int h2mi_plonk_evaluate_h_standard_dev(const h2mi_standard_plonk_cosets* c, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/h2mi_prover.h"
+#include "h2mi_expr.hpp"
 #include "h2mi_hostmath.hpp"
 
 namespace {
@@ -116,7 +117,32 @@ std::vector<G1Affine> commit_points(uint64_t handle, const std::vector<Dev>& col
 }
 
 // ---- the constraint system ---------------------------------------------------------------------------------------------------
-void validate(const h2mi_constraint_system& cs) {
+static_assert(H2MI_EXPR_MAX_ADVICE == H2MI_MAX_ADVICE && H2MI_EXPR_MAX_FIXED == H2MI_MAX_FIXED, "h2mi_expr_cosets holds every column of a constraint system");
+static_assert(H2MI_EXPR_ADVICE == H2MI_COL_ADVICE && H2MI_EXPR_FIXED == H2MI_COL_FIXED && H2MI_EXPR_INSTANCE == H2MI_COL_INSTANCE, "query ops are the column kinds");
+
+// the rules of h2mi_gate_program_check (include/h2mi_prover.h)
+int check_program(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, h2::ExprShape* shape) {
+  if (cs.k == 0 || cs.k > H2MI_MAX_LOG_N || cs.n_advice > H2MI_MAX_ADVICE || cs.n_fixed > H2MI_MAX_FIXED || cs.n_instance > 1 ||
+      cs.n_advice_queries > H2MI_MAX_QUERIES || cs.n_fixed_queries > H2MI_MAX_QUERIES)
+    return H2MI_EINVAL;
+  auto listed = [](const h2mi_query* q, uint32_t count, uint32_t column, int32_t rotation) {
+    for (uint32_t i = 0; i < count; i++)
+      if (q[i].column == column && q[i].rotation == rotation) return true;
+    return false;
+  };
+  h2::ExprShape sh;
+  const int rc = h2::expr_walk(gates, cs.k, [&](uint32_t kind, uint32_t index, int32_t rotation) {
+    if (kind == H2MI_EXPR_ADVICE) return index < cs.n_advice && listed(cs.advice_queries, cs.n_advice_queries, index, rotation);
+    if (kind == H2MI_EXPR_FIXED) return index < cs.n_fixed && listed(cs.fixed_queries, cs.n_fixed_queries, index, rotation);
+    return index < cs.n_instance;  // instance columns are not opened (KZG): no query list
+  }, &sh);
+  if (rc) return rc;
+  if (sh.degree > cs.degree) return H2MI_EINVAL;
+  if (shape) *shape = sh;
+  return H2MI_OK;
+}
+
+void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates) {
   auto bad = [](const char* what) { throw Error(H2MI_EINVAL, std::string("constraint system: ") + what); };
   if (cs.k == 0 || cs.k > H2MI_MAX_LOG_N) throw Error(H2MI_ERANGE, "constraint system: k");
   if (cs.degree < 3 || cs.degree > 9) bad("degree");
@@ -138,11 +164,17 @@ void validate(const h2mi_constraint_system& cs) {
     if (cs.n_advice != 3 || cs.n_fixed != 5 || cs.n_instance != 0 || cs.n_lookups != 0 || cs.degree != 3 || cs.n_perm != 3) bad("not the StandardPlonk shape");
     for (uint32_t j = 0; j < 3; j++)
       if (cs.perm_columns[j].kind != H2MI_COL_ADVICE || cs.perm_columns[j].index != j) bad("StandardPlonk's permutation runs over a, b, c");
-  } else if (cs.gates == H2MI_GATES_FLEX_VERTICAL) {
-    if (cs.n_gates == 0 || cs.n_gates > H2MI_MAX_GATES) bad("gate count");
-    for (uint32_t g = 0; g < cs.n_gates; g++)
-      if (cs.gate_advice[g] >= cs.n_advice || cs.gate_selector[g] >= cs.n_fixed) bad("gate columns");
-    if (cs.n_perm && cs.degree - 2 > 3) bad("permutation chunks longer than three columns");
+  } else if (cs.gates == H2MI_GATES_FLEX_VERTICAL || cs.gates == H2MI_GATES_EXPRESSIONS) {
+    if (cs.gates == H2MI_GATES_EXPRESSIONS) {
+      // the permutation products take any chunk length, and so does the quotient kernel that interprets the program
+      if (!gates) bad("gates given as expressions go through h2mi_prover_keygen_gates");
+      if (check_program(cs, gates, nullptr)) bad("gate program");
+    } else {
+      if (cs.n_gates == 0 || cs.n_gates > H2MI_MAX_GATES) bad("gate count");
+      for (uint32_t g = 0; g < cs.n_gates; g++)
+        if (cs.gate_advice[g] >= cs.n_advice || cs.gate_selector[g] >= cs.n_fixed) bad("gate columns");
+      if (cs.n_perm && cs.degree - 2 > 3) bad("permutation chunks longer than three columns");
+    }
     for (uint32_t l = 0; l < cs.n_lookups; l++) {
       const h2mi_lookup& lk = cs.lookups[l];
       if (lk.input.kind != H2MI_COL_ADVICE || lk.input.index >= cs.n_advice || lk.table_fixed >= cs.n_fixed) bad("lookup columns");
@@ -154,6 +186,7 @@ void validate(const h2mi_constraint_system& cs) {
   uint32_t ext_k = cs.k;
   while (((uint64_t)1 << ext_k) < ((uint64_t)1 << cs.k) * (cs.degree - 1)) ext_k++;
   if (ext_k - cs.k > 4 || ext_k > H2MI_MAX_LOG_N) throw Error(H2MI_ERANGE, "constraint system: extended domain");
+  if (gates && cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_gates takes H2MI_GATES_EXPRESSIONS");
 }
 
 struct Table {  // a lookup table's distinct usable values in ascending canonical order, for the device's counting sort
@@ -176,6 +209,10 @@ struct h2mi_pk_s {
   uint32_t n_active = 0;
   Table tables[H2MI_MAX_LOOKUPS];
   std::vector<G1Affine> fixed_commitments, permutation_commitments;
+  // H2MI_GATES_EXPRESSIONS: the key's own copy of the gate program
+  std::vector<h2mi_expr_op> gate_ops;
+  std::vector<uint64_t> gate_constants;
+  h2mi_gate_program gate_program = {nullptr, 0, nullptr, 0};
   explicit h2mi_pk_s(const h2mi_constraint_system& c)
       : cs(c), domain(c.degree, c.k), n((size_t)1 << c.k), ext(domain.extended_len()), u((uint32_t)n - (c.blinding_factors + 1)),
         chunk(c.degree - 2), n_sets(c.n_perm ? (c.n_perm + c.degree - 3) / (c.degree - 2) : 0), delta(fr_delta()) {}
@@ -234,11 +271,16 @@ void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells) {
   check(h2mi_memcpy_h2d(t.mult->p, mult.data(), mult.size() * 4), "table");
 }
 
-std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, uint64_t g_lagrange, const h2mi_column_cells* fixed, const uint32_t* copies,
-                                  size_t n_copies, unsigned flags) {
-  validate(cs);
+std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, uint64_t g_lagrange, const h2mi_column_cells* fixed,
+                                  const uint32_t* copies, size_t n_copies, unsigned flags) {
+  validate(cs, gates);
   std::unique_ptr<h2mi_pk_s> pkp(new h2mi_pk_s(cs));
   h2mi_pk_s& pk = *pkp;
+  if (gates) {
+    pk.gate_ops.assign(gates->ops, gates->ops + gates->n_ops);
+    if (gates->n_constants) pk.gate_constants.assign(gates->constants, gates->constants + 4 * (size_t)gates->n_constants);
+    pk.gate_program = {pk.gate_ops.data(), gates->n_ops, pk.gate_constants.data(), gates->n_constants};
+  }
   pk.vk_only = (flags & H2MI_KEYGEN_VK_ONLY) != 0;
   const poly::EvaluationDomain& dom = pk.domain;
   const size_t n = pk.n;
@@ -804,6 +846,36 @@ void phase_quotient(h2mi_prover_s& p, const Fr& y, uint64_t* points_out) {
     check(h2mi_plonk_evaluate_h_standard_dev(&sc, d.k(), d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l,
                                              (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
+  } else if (cs.gates == H2MI_GATES_EXPRESSIONS) {
+    // gates given as a program: the interpreting kernel reads any column of the proof through one pointer table
+    h2mi_expr_cosets ec;
+    std::memset(&ec, 0, sizeof(ec));
+    for (uint32_t j = 0; j < cs.n_advice; j++) ec.advice[j] = p.advice[j].coset->p;
+    for (uint32_t j = 0; j < cs.n_fixed; j++) ec.fixed[j] = pk.fixed_cosets[j]->p;
+    if (cs.n_instance) ec.instance = p.instance_coset->p;
+    ec.n_perm = m;
+    ec.chunk_len = pk.chunk;
+    for (uint32_t j = 0; j < m; j++) {
+      ec.perm_value[j] = coset_col(cs.perm_columns[j]);
+      ec.perm_sigma[j] = pk.sigma_cosets[j]->p;
+    }
+    for (uint32_t s = 0; s < n_sets; s++) ec.perm_z[s] = p.z[s].coset->p;
+    ec.n_lookups = L;
+    for (uint32_t l = 0; l < L; l++) {
+      const h2mi_lookup& lk = cs.lookups[l];
+      ec.lookup_input[l] = p.advice[lk.input.index].coset->p;
+      ec.lookup_input_b[l] = lk.selector_fixed >= 0 ? pk.fixed_cosets[lk.selector_fixed]->p : nullptr;
+      ec.lookup_table[l] = pk.fixed_cosets[lk.table_fixed]->p;
+      ec.lookup_permuted_input[l] = p.lk[l].a.coset->p;
+      ec.lookup_permuted_table[l] = p.lk[l].s.coset->p;
+      ec.lookup_z[l] = p.lk[l].z.coset->p;
+    }
+    ec.l0 = pk.l0->p;
+    ec.l_last = pk.l_last->p;
+    ec.l_active = pk.l_active->p;
+    check(h2mi_plonk_evaluate_h_expr_dev(&ec, &pk.gate_program, d.k(), d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l,
+                                         d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
+          "evaluate_h");
   } else if (cs.n_gates == 1 && m >= 1 && m <= 4 && L <= 1) {
     // one gate column: the specialised kernel (its level bookkeeping is written for this shape; faster per point than the general one)
     h2mi_range_cosets rc;
@@ -1172,7 +1244,30 @@ int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_han
   *pk_out = nullptr;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;  // no CPU fallback: the prover exists on a GPU or not at all
   return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, g_lagrange_handle, fixed, copies, n_copies, flags);
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    g_live_pks.insert(pk.get());
+    *pk_out = pk.release();
+  });
+}
+
+int h2mi_gate_program_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint32_t* degree_out, uint32_t* max_stack_out) {
+  if (!cs || !gates) return H2MI_EINVAL;
+  h2::ExprShape sh;
+  const int rc = check_program(*cs, gates, &sh);
+  if (rc) return rc;
+  if (degree_out) *degree_out = sh.degree;
+  if (max_stack_out) *max_stack_out = sh.max_stack;
+  return H2MI_OK;
+}
+
+int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed,
+                             const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
+  if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)H2MI_KEYGEN_VK_ONLY)) return H2MI_EINVAL;
+  *pk_out = nullptr;
+  if (h2mi_device_count() == 0) return H2MI_ENODEV;
+  return guarded([&] {
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, g_lagrange_handle, fixed, copies, n_copies, flags);
     std::lock_guard<std::mutex> lk(g_reg_mu);
     g_live_pks.insert(pk.get());
     *pk_out = pk.release();

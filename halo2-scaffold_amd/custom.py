@@ -1,0 +1,386 @@
+"""Circuits with hand-written gates: halo2's `ConstraintSystem` API, name for name, in front of the library's prover.
+
+The reference's src/circuits/is_zero.rs and or.rs configure their circuits with `meta.create_gate("...", |meta| vec![...])` over
+`meta.query_advice(column, Rotation)` expressions.  This module is that API — `ConstraintSystem.advice_column / fixed_column /
+instance_column / selector / enable_equality / create_gate`, `Expression` with + - * and `Expression.constant` — so that such a
+configure() can be transcribed line by line, and the region API of synthesize() (`Assignment.assign_advice / assign_fixed /
+enable_selector / constrain_equal / constrain_instance`).  `ConstraintSystem.program()` compiles the gate polynomials to the postfix
+program of include/h2mi.h (h2mi_gate_program), `abi(k)` gives the constraint system as data with gates = H2MI_GATES_EXPRESSIONS;
+`Keys` and `create_proof` are thin calls into libh2mi.so exactly as flex.FlexKeys / flex.create_proof are: one kernel interprets the
+program on the extended coset (csrc/h2mi_plonk.hip k_evaluate_h_expr), everything else is the prover every other shape uses.
+
+halo2's bookkeeping, restated from memory [RECALL halo2_proofs plonk/circuit.rs]:
+  * enable_equality queries its column at Rotation::cur when it is called; query lists are in first-use order;
+  * blinding_factors = max(3, most queries on one advice column) + 2;  degree = max(3, gate degrees) (no lookups here);
+  * every selector becomes ONE fixed column, appended after the user's fixed columns in selector order and queried last.  The crate's
+    compress_selectors, which merges disjoint simple selectors into one column, is NOT modelled: a circuit whose selectors the crate
+    would merge gets one column more here than there (and other proof bytes).  The C ABI sees expressions after the substitution
+    and does not care.
+Lookups (`meta.lookup`) are not part of this module; the single-expression lookups of the ABI are reached through flex.py.
+"""
+from . import engine, flex
+from . import field as F
+from .domain import EvaluationDomain
+from .keygen import transcript_repr
+from .params import ParamsKZG
+
+R = F.FR_MODULUS
+ADVICE, FIXED, INSTANCE = flex.ADVICE, flex.FIXED, flex.INSTANCE
+_KIND = {ADVICE: engine.ADVICE, FIXED: engine.FIXED, INSTANCE: engine.INSTANCE}
+_OP = {"add": engine.EXPR_ADD, "sub": engine.EXPR_SUB, "mul": engine.EXPR_MUL}
+
+
+class Rotation(int):
+    """poly::Rotation: a row offset"""
+
+    @classmethod
+    def cur(cls):
+        return cls(0)
+
+    @classmethod
+    def next(cls):
+        return cls(1)
+
+    @classmethod
+    def prev(cls):
+        return cls(-1)
+
+
+class Column:
+    def __init__(self, kind: str, index: int):
+        self.kind, self.index = kind, index
+
+    def __repr__(self):
+        return f"Column({self.kind}, {self.index})"
+
+
+class Selector:
+    def __init__(self, index: int):
+        self.index = index
+
+
+class Cell:
+    def __init__(self, kind: str, column: int, row: int, value: int):
+        self.kind, self.column, self.row, self.value = kind, column, row, value
+
+
+class Expression:
+    """plonk::Expression<F>: a polynomial over column queries.  node: ("constant", v) | ("query", kind, column, rotation) |
+    ("selector", index) | ("neg", e) | ("add" | "sub" | "mul", a, b).  A selector stays symbolic until the constraint system knows how
+    many fixed columns the user took (`resolve`)."""
+
+    def __init__(self, *node):
+        self.node = node
+
+    @staticmethod
+    def constant(v: int) -> "Expression":
+        return Expression("constant", v % R)
+
+    @staticmethod
+    def _wrap(v) -> "Expression":
+        return v if isinstance(v, Expression) else Expression.constant(v)
+
+    def __add__(self, o):
+        return Expression("add", self, Expression._wrap(o))
+
+    def __radd__(self, o):
+        return Expression("add", Expression._wrap(o), self)
+
+    def __sub__(self, o):
+        return Expression("sub", self, Expression._wrap(o))
+
+    def __rsub__(self, o):
+        return Expression("sub", Expression._wrap(o), self)
+
+    def __mul__(self, o):
+        return Expression("mul", self, Expression._wrap(o))
+
+    def __rmul__(self, o):
+        return Expression("mul", Expression._wrap(o), self)
+
+    def __neg__(self):
+        return Expression("neg", self)
+
+    def clone(self):
+        return self
+
+    def resolve(self, first_selector_column: int) -> "Expression":
+        """the expression keygen sees: every selector replaced by the query of its fixed column"""
+        t = self.node[0]
+        if t == "selector":
+            return Expression("query", FIXED, first_selector_column + self.node[1], 0)
+        if t in ("constant", "query"):
+            return self
+        return Expression(t, *[e.resolve(first_selector_column) for e in self.node[1:]])
+
+    def degree(self) -> int:
+        t = self.node[0]
+        if t == "constant":
+            return 0
+        if t in ("query", "selector"):
+            return 1
+        if t == "neg":
+            return self.node[1].degree()
+        a, b = self.node[1].degree(), self.node[2].degree()
+        return a + b if t == "mul" else max(a, b)
+
+    def stack_depth(self) -> int:
+        """operand-stack depth of the postfix `program()` emits"""
+        t = self.node[0]
+        if t in ("constant", "query", "selector"):
+            return 1
+        if t == "neg":
+            return self.node[1].stack_depth()
+        first, second = self._order()
+        return max(first.stack_depth(), 1 + second.stack_depth())
+
+    def _order(self):
+        """operands in emission order: ADD and MUL commute, so the deeper operand goes first (it runs on an empty stack, the
+        shallower one on top of its result); SUB keeps its order"""
+        a, b = self.node[1], self.node[2]
+        if self.node[0] != "sub" and b.stack_depth() > a.stack_depth():
+            return b, a
+        return a, b
+
+    def evaluate(self, q) -> int:
+        """the value with q(kind, column, rotation) for the queries (selectors resolved)"""
+        t = self.node[0]
+        if t == "constant":
+            return self.node[1]
+        if t == "query":
+            return q(*self.node[1:]) % R
+        if t == "neg":
+            return -self.node[1].evaluate(q) % R
+        a, b = self.node[1].evaluate(q), self.node[2].evaluate(q)
+        return (a + b if t == "add" else a - b if t == "sub" else a * b) % R
+
+    def _emit(self, ops, constants):
+        t = self.node[0]
+        if t == "constant":
+            if self.node[1] not in constants:
+                constants[self.node[1]] = len(constants)
+            ops.append((engine.EXPR_CONSTANT, constants[self.node[1]], 0))
+        elif t == "query":
+            ops.append((_KIND[self.node[1]], self.node[2], int(self.node[3])))
+        elif t == "neg":
+            self.node[1]._emit(ops, constants)
+            ops.append((engine.EXPR_NEG, 0, 0))
+        elif t == "selector":
+            raise ValueError("resolve() the selectors before compiling")
+        else:
+            first, second = self._order()
+            first._emit(ops, constants)
+            second._emit(ops, constants)
+            ops.append((_OP[t], 0, 0))
+
+    def program(self, constants: dict = None):
+        """the postfix compiler: -> (ops [(op, index, rotation)] closed by END, constants [int]).  `constants`: a {value: index} table
+        shared by the polynomials of one constraint system."""
+        constants = {} if constants is None else constants
+        ops = []
+        self._emit(ops, constants)
+        ops.append((engine.EXPR_END, 0, 0))
+        return ops, sorted(constants, key=constants.get)
+
+
+class ConstraintSystem:
+    """plonk::ConstraintSystem<F> as configure() fills it"""
+
+    def __init__(self):
+        self.n_advice = self.n_user_fixed = self.n_instance = self.n_selectors = 0
+        self.perm_columns = []                      # [(kind, column)] in enable_equality order
+        self.advice_queries, self._fixed_queries, self.instance_queries = [], [], []
+        self.gate_names, self._polys = [], []       # one entry per polynomial, selectors unresolved
+
+    # ---- columns -----------------------------------------------------------------------------------------------------
+    def advice_column(self) -> Column:
+        self.n_advice += 1
+        return Column(ADVICE, self.n_advice - 1)
+
+    def fixed_column(self) -> Column:
+        self.n_user_fixed += 1
+        return Column(FIXED, self.n_user_fixed - 1)
+
+    def instance_column(self) -> Column:
+        self.n_instance += 1
+        return Column(INSTANCE, self.n_instance - 1)
+
+    def selector(self) -> Selector:
+        self.n_selectors += 1
+        return Selector(self.n_selectors - 1)
+
+    def enable_equality(self, column: Column) -> None:
+        self._query(column, 0)
+        if (column.kind, column.index) not in self.perm_columns:
+            self.perm_columns.append((column.kind, column.index))
+
+    # ---- gates (the closure receives this object as `meta`: VirtualCells) ---------------------------------------------
+    def _query(self, column: Column, rotation: int) -> Expression:
+        lst = {ADVICE: self.advice_queries, FIXED: self._fixed_queries, INSTANCE: self.instance_queries}[column.kind]
+        if (column.index, int(rotation)) not in lst:
+            lst.append((column.index, int(rotation)))
+        return Expression("query", column.kind, column.index, int(rotation))
+
+    def query_advice(self, column: Column, rotation: int) -> Expression:
+        assert column.kind == ADVICE
+        return self._query(column, rotation)
+
+    def query_fixed(self, column: Column, rotation: int = 0) -> Expression:
+        assert column.kind == FIXED
+        return self._query(column, rotation)
+
+    def query_instance(self, column: Column, rotation: int) -> Expression:
+        assert column.kind == INSTANCE
+        return self._query(column, rotation)
+
+    def query_selector(self, selector: Selector) -> Expression:
+        return Expression("selector", selector.index)
+
+    def create_gate(self, name: str, constraints) -> None:
+        polys = list(constraints(self))
+        assert polys, "a gate needs at least one polynomial"
+        for p in polys:
+            self.gate_names.append(name)
+            self._polys.append(Expression._wrap(p))
+
+    # ---- what keygen and create_proof read off it ------------------------------------------------------------------------
+    @property
+    def n_fixed(self) -> int:
+        return self.n_user_fixed + self.n_selectors
+
+    @property
+    def fixed_queries(self):
+        return self._fixed_queries + [(self.n_user_fixed + s, 0) for s in range(self.n_selectors)]
+
+    def selector_column(self, selector: Selector) -> int:
+        return self.n_user_fixed + selector.index
+
+    @property
+    def polynomials(self):
+        return [p.resolve(self.n_user_fixed) for p in self._polys]
+
+    @property
+    def gates(self):
+        """the polynomials as callables g(q), q(kind, column, rotation) -> value: the form oracle.flex.ConstraintSystem takes"""
+        return [(lambda q, p=p: p.evaluate(q)) for p in self.polynomials]
+
+    def degree(self) -> int:
+        return max([3] + [p.degree() for p in self._polys])
+
+    def blinding_factors(self) -> int:
+        per_column = [sum(1 for c, _ in self.advice_queries if c == j) for j in range(self.n_advice)]
+        return max([3] + per_column) + 2
+
+    def program(self):
+        """every gate polynomial in create_gate order -> (ops, constants) of one h2mi_gate_program"""
+        constants, ops = {}, []
+        for p in self.polynomials:
+            ops += p.program(constants)[0]
+        return ops, sorted(constants, key=constants.get)
+
+    def gate_program(self) -> engine.GateProgram:
+        return engine.GateProgram.build(*self.program())
+
+    def abi(self, k: int) -> engine.ConstraintSystem:
+        assert self.n_instance <= 1, "the prover ABI takes one instance column"
+        return engine.ConstraintSystem.build(k, self.n_advice, self.n_fixed, self.n_instance, self.degree(), self.blinding_factors(),
+                                             engine.GATES_EXPRESSIONS, [], [(_KIND[kind], c) for kind, c in self.perm_columns], [],
+                                             self.advice_queries, self.fixed_queries)
+
+
+class Assignment:
+    """what synthesize() leaves, through the calls of halo2's Region: sparse cells per column, the copy constraints in call order, the
+    public inputs (one instance column)"""
+
+    def __init__(self, cs: ConstraintSystem, instance=()):
+        self.cs = cs
+        self.advice = [dict() for _ in range(cs.n_advice)]
+        self.fixed = [dict() for _ in range(cs.n_fixed)]
+        self.instance = [v % R for v in instance]
+        self.copies = []  # ((kind, column, row), (kind, column, row))
+
+    def assign_advice(self, column: Column, row: int, value: int) -> Cell:
+        assert column.kind == ADVICE
+        self.advice[column.index][row] = value % R
+        return Cell(ADVICE, column.index, row, value % R)
+
+    def assign_fixed(self, column: Column, row: int, value: int) -> Cell:
+        assert column.kind == FIXED
+        self.fixed[column.index][row] = value % R
+        return Cell(FIXED, column.index, row, value % R)
+
+    def enable_selector(self, selector: Selector, row: int) -> None:
+        self.fixed[self.cs.selector_column(selector)][row] = 1
+
+    def constrain_equal(self, left: Cell, right: Cell) -> None:
+        self.copies.append(((left.kind, left.column, left.row), (right.kind, right.column, right.row)))
+
+    def constrain_instance(self, cell: Cell, column: Column, row: int) -> None:
+        assert column.kind == INSTANCE
+        self.copies.append(((cell.kind, cell.column, cell.row), (INSTANCE, column.index, row)))
+
+    def copy_advice(self, cell: Cell, column: Column, row: int) -> Cell:
+        """AssignedCell::copy_advice: assign the value again and constrain the two cells equal"""
+        new = self.assign_advice(column, row, cell.value)
+        self.constrain_equal(cell, new)
+        return new
+
+
+def mock(asg: Assignment, k: int) -> None:
+    """MockProver::run(k, ..).assert_satisfied() on the host: no cell or copy constraint beyond the usable rows, every gate polynomial
+    zero on every usable row (unassigned cells are zero; rotations wrap around 2^k), every copy constraint between equal cells.
+    Raises ValueError naming the first violation."""
+    cs = asg.cs
+    n = 1 << k
+    u = n - (cs.blinding_factors() + 1)
+    rows = [(f"fixed column {c}", max(cells)) for c, cells in enumerate(asg.fixed) if cells]
+    rows += [(f"advice column {c}", max(cells)) for c, cells in enumerate(asg.advice) if cells]
+    rows += [("a copy constraint", max(left[2], right[2])) for left, right in asg.copies]
+    rows.append(("the instance column", len(asg.instance) - 1))
+    for what, row in rows:
+        if row >= u:
+            raise ValueError(f"NotEnoughRowsAvailable: {what} reaches row {row}, the usable rows end at {u}")
+    value = {ADVICE: lambda c, r: asg.advice[c].get(r, 0), FIXED: lambda c, r: asg.fixed[c].get(r, 0),
+             INSTANCE: lambda c, r: asg.instance[r] if r < len(asg.instance) else 0}
+    for name, poly in zip(cs.gate_names, cs.polynomials):
+        for row in range(u):
+            if poly.evaluate(lambda kind, c, rot: value[kind](c, (row + rot) % n)):
+                raise ValueError(f"gate {name!r} not satisfied at row {row}")
+    for left, right in asg.copies:
+        if value[left[0]](left[1], left[2]) % R != value[right[0]](right[1], right[2]) % R:
+            raise ValueError(f"copy constraint {left} == {right} not satisfied")
+
+
+class Keys:
+    """keygen_vk + keygen_pk through h2mi_prover_keygen_gates: the fixed cells of a run of synthesize() (selector columns included), the
+    copy constraints with their columns renumbered into the permutation argument's order, the gates as a program the key copies.
+    Same attributes as flex.FlexKeys."""
+
+    def __init__(self, params: ParamsKZG, cs: ConstraintSystem, asg: Assignment):
+        self.cs = cs
+        k = params.k
+        self.domain = d = EvaluationDomain(cs.degree(), k)
+        self.u = d.n - (cs.blinding_factors() + 1)
+        index = {col: j for j, col in enumerate(cs.perm_columns)}
+        copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
+        self.keys = engine.Keys(cs.abi(k), params, list(asg.fixed), copies, gates=cs.gate_program())
+        self.fixed_commitments, self.permutation_commitments = self.keys.fixed_commitments, self.keys.permutation_commitments
+        nf, m = cs.n_fixed, len(cs.perm_columns)
+        self.fixed_values, self.fixed_polys, self.fixed_cosets = (self.keys.views(kd, nf) for kd in (engine.PKBUF_FIXED, engine.PKBUF_FIXED_POLY, engine.PKBUF_FIXED_COSET))
+        self.sigma_values, self.sigma_polys, self.sigma_cosets = (self.keys.views(kd, m) for kd in (engine.PKBUF_SIGMA, engine.PKBUF_SIGMA_POLY, engine.PKBUF_SIGMA_COSET))
+        self._vk_bytes, self.transcript_repr = transcript_repr(k, cs.degree(), self.fixed_commitments, self.permutation_commitments)
+
+    def vk_bytes(self) -> bytes:
+        return self._vk_bytes
+
+    def release(self):
+        self.keys.release()
+
+
+Workspace = flex.FlexWorkspace  # one library prover kept from proof to proof: nothing in it depends on the gate shape
+
+
+def create_proof(params: ParamsKZG, keys: Keys, asg: Assignment, seed: int, transcript=None, trace: dict = None, ws: Workspace = None) -> bytes:
+    """create_proof for one circuit: the transcript on this side, seven phase calls into the library (flex.create_proof's body: the
+    phases do not depend on how the gates were given)"""
+    return flex.create_proof(params, keys, asg, seed, transcript=transcript, trace=trace, ws=ws)

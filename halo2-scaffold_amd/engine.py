@@ -18,7 +18,7 @@ from ._lib import H2miError, check, lib
 from .transcript import Blake2bWrite
 
 ADVICE, FIXED, INSTANCE = 0, 1, 2  # H2MI_COL_*
-GATES_STANDARD_PLONK, GATES_FLEX_VERTICAL = 1, 2
+GATES_STANDARD_PLONK, GATES_FLEX_VERTICAL, GATES_EXPRESSIONS = 1, 2, 3
 CELLS_CANONICAL = 1
 KEYGEN_VK_ONLY = 1
 EUNSAT = -7
@@ -75,6 +75,36 @@ class ConstraintSystem(C.Structure):
         for i, (c, r) in enumerate(fixed_queries):
             cs.fixed_queries[i] = Query(c, r)
         return cs
+
+
+# h2mi_expr_op.op (include/h2mi.h): the first three are the column kinds above
+EXPR_ADVICE, EXPR_FIXED, EXPR_INSTANCE, EXPR_CONSTANT, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG, EXPR_END = range(9)
+MAX_EXPR_OPS, MAX_EXPR_CONSTANTS, MAX_EXPR_STACK = 4096, 256, 8
+
+
+class ExprOp(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("index", C.c_uint32), ("rotation", C.c_int32)]
+
+
+class GateProgram(C.Structure):
+    """h2mi_gate_program: the gate polynomials in postfix, each closed by END, with the constants they push (Montgomery limbs)"""
+    _fields_ = [("ops", C.POINTER(ExprOp)), ("n_ops", C.c_uint32), ("constants", C.c_void_p), ("n_constants", C.c_uint32)]
+
+    @classmethod
+    def build(cls, ops, constants) -> "GateProgram":
+        """ops: [(op, index, rotation)]; constants: integers below r.  The arrays stay alive with the object."""
+        g = cls()
+        g._ops = (ExprOp * max(len(ops), 1))(*[ExprOp(*o) for o in ops])
+        g._constants = np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in constants])) if len(constants) else np.zeros((1, 4), dtype=np.uint64)
+        g.ops, g.n_ops = g._ops, len(ops)
+        g.constants, g.n_constants = g._constants.ctypes.data, len(constants)
+        return g
+
+    def check(self, cs: "ConstraintSystem"):
+        """h2mi_gate_program_check -> (largest polynomial degree, deepest stack); H2miError(-1) for a program keygen would refuse"""
+        degree, depth = C.c_uint32(), C.c_uint32()
+        check(lib.h2mi_gate_program_check(C.byref(cs), C.byref(self), C.byref(degree), C.byref(depth)), "gate_program_check")
+        return degree.value, depth.value
 
 
 class ColumnCells(C.Structure):
@@ -152,17 +182,21 @@ class _Views:
 
 
 class Keys:
-    """h2mi_prover_keygen: keygen_vk + keygen_pk for a constraint system given as data.  fixed: one {row: value} dict (or dense
+    """h2mi_prover_keygen (h2mi_prover_keygen_gates when `gates` is given): keygen_vk + keygen_pk for a constraint system given as data.  fixed: one {row: value} dict (or dense
     list) per fixed column as synthesize() assigns them; copies: [(left column, left row, right column, right row)] per
     constrain_equal in call order, columns as indices into the permutation argument.  `params` is the WHOLE SRS."""
 
-    def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False):
+    def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False, gates: GateProgram = None):
         self.cs = cs
         cells, keep = pack_cells(fixed)
         cp = np.ascontiguousarray(np.array(copies, dtype=np.uint32).reshape(-1, 4))
         h = C.c_void_p()
-        check(lib.h2mi_prover_keygen(C.byref(cs), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), KEYGEN_VK_ONLY if vk_only else 0, C.byref(h)),
-              "keygen")
+        flags = KEYGEN_VK_ONLY if vk_only else 0
+        if gates is None:
+            check(lib.h2mi_prover_keygen(C.byref(cs), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
+        else:  # GATES_EXPRESSIONS: the gates travel beside the struct; the key copies them
+            check(lib.h2mi_prover_keygen_gates(C.byref(cs), C.byref(gates), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)),
+                  "keygen")
         del keep
         self.handle = h.value
         self._provers = weakref.WeakSet()  # the library refuses to release a key while a prover created against it is alive

@@ -234,3 +234,46 @@ def evaluate_h_flex(domain: EvaluationDomain, gates, perm_values, perm_sigmas, p
     args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
     _check(lib.h2mi_plonk_evaluate_h_flex_dev(C.byref(cs), domain.k, domain.extended_k, blinding_factors, *[x.ctypes.data for x in args],
                                               t_inv.ctypes.data, out.ptr, None), "evaluate_h_flex")
+
+
+class _ExprCosets(C.Structure):
+    """include/h2mi.h h2mi_expr_cosets"""
+    A, Fx, P, L = 64, 64, 64, 8  # H2MI_EXPR_MAX_ADVICE / _FIXED, H2MI_FLEX_MAX_PERM / _LOOKUPS
+    _fields_ = [("advice", C.c_void_p * A), ("fixed", C.c_void_p * Fx), ("instance", C.c_void_p), ("n_perm", C.c_uint32), ("chunk_len", C.c_uint32),
+                ("perm_value", C.c_void_p * P), ("perm_sigma", C.c_void_p * P), ("perm_z", C.c_void_p * P), ("n_lookups", C.c_uint32),
+                ("lookup_input", C.c_void_p * L), ("lookup_input_b", C.c_void_p * L), ("lookup_table", C.c_void_p * L),
+                ("lookup_permuted_input", C.c_void_p * L), ("lookup_permuted_table", C.c_void_p * L), ("lookup_z", C.c_void_p * L),
+                ("l0", C.c_void_p), ("l_last", C.c_void_p), ("l_active", C.c_void_p)]
+
+
+def evaluate_h_expr(domain: EvaluationDomain, program, advice, fixed, instance, perm_values, perm_sigmas, perm_zs, chunk_len: int, lookups,
+                    l0: DevBuf, l_last: DevBuf, l_active: DevBuf, beta: int, gamma: int, y: int, out: DevBuf,
+                    blinding_factors: int = BLINDING_FACTORS) -> None:
+    """h(X) on the extended coset with the gates given as a postfix program (h2mi_plonk_evaluate_h_expr_dev): `program` an
+    engine.GateProgram over the coset forms `advice` / `fixed` (lists, None for a column the program does not read) and `instance`
+    (or None); permutation argument and lookups as evaluate_h_flex takes them, both optional."""
+    m = len(perm_values)
+    assert len(advice) <= _ExprCosets.A and len(fixed) <= _ExprCosets.Fx and m <= _ExprCosets.P and len(perm_sigmas) == m
+    assert len(perm_zs) == (-(-m // chunk_len) if m else 0) and len(lookups) <= _ExprCosets.L
+    cs = _ExprCosets()
+    for j, a in enumerate(advice):
+        cs.advice[j] = a.ptr if a is not None else None
+    for j, f in enumerate(fixed):
+        cs.fixed[j] = f.ptr if f is not None else None
+    cs.instance = instance.ptr if instance is not None else None
+    cs.n_perm, cs.chunk_len = m, chunk_len
+    for j in range(m):
+        cs.perm_value[j], cs.perm_sigma[j] = perm_values[j].ptr, perm_sigmas[j].ptr
+    for s, z in enumerate(perm_zs):
+        cs.perm_z[s] = z.ptr
+    cs.n_lookups = len(lookups)
+    for l, (a_in, b_in, table, pin, ptab, z) in enumerate(lookups):
+        cs.lookup_input[l], cs.lookup_table[l] = a_in.ptr, table.ptr
+        cs.lookup_input_b[l] = b_in.ptr if b_in is not None else None
+        cs.lookup_permuted_input[l], cs.lookup_permuted_table[l], cs.lookup_z[l] = pin.ptr, ptab.ptr, z.ptr
+    cs.l0, cs.l_last, cs.l_active = l0.ptr, l_last.ptr, l_active.ptr
+    mm = F.fr_to_mont_limbs
+    t_inv = np.ascontiguousarray(vanishing_inverses(domain))
+    args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
+    _check(lib.h2mi_plonk_evaluate_h_expr_dev(C.byref(cs), C.byref(program), domain.k, domain.extended_k, blinding_factors,
+                                              *[x.ctypes.data for x in args], t_inv.ctypes.data, out.ptr, None), "evaluate_h_expr")

@@ -407,6 +407,54 @@ int h2mi_plonk_evaluate_h_flex_dev(const h2mi_flex_cosets* cosets, uint32_t k, u
                                    const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv /* 2^(extended_k-k) x 4 */,
                                    void* d_h_out, h2mi_stream_t stream);
 
+/* Gates given as DATA: the polynomials of `meta.create_gate(...)` (reference src/circuits/is_zero.rs, or.rs) as a postfix program that
+ * one kernel interprets on the extended coset, in front of the permutation and lookup terms of the general form above.
+ * One gate polynomial after another, each in postfix, in the order evaluate_h folds them with y (gates in create_gate order, a
+ * gate's polynomials in the order of its Vec).  Expression<F> maps op for op; Scaled(e, c) is `e, CONSTANT c, MUL`, a selector is the
+ * fixed query keygen substitutes for it. */
+enum { H2MI_EXPR_ADVICE = 0, H2MI_EXPR_FIXED = 1, H2MI_EXPR_INSTANCE = 2,   /* = H2MI_COL_*: push column `index` at `rotation` */
+       H2MI_EXPR_CONSTANT = 3,                                             /* push constants[index] */
+       H2MI_EXPR_ADD, H2MI_EXPR_SUB, H2MI_EXPR_MUL, H2MI_EXPR_NEG,          /* on the top of the stack */
+       H2MI_EXPR_END };                                                    /* the one value left is this polynomial */
+#define H2MI_MAX_EXPR_OPS 4096
+#define H2MI_MAX_EXPR_CONSTANTS 256
+#define H2MI_MAX_EXPR_STACK 8
+#define H2MI_EXPR_MAX_ADVICE 64 /* = H2MI_MAX_ADVICE / H2MI_MAX_FIXED of h2mi_prover.h */
+#define H2MI_EXPR_MAX_FIXED 64
+typedef struct { uint32_t op; uint32_t index; int32_t rotation; } h2mi_expr_op;
+typedef struct {
+  const h2mi_expr_op* ops;   uint32_t n_ops;        /* <= H2MI_MAX_EXPR_OPS */
+  const uint64_t* constants; uint32_t n_constants;  /* n x 4 limbs, Montgomery; <= H2MI_MAX_EXPR_CONSTANTS */
+} h2mi_gate_program;
+/* h2mi_flex_cosets with the columns a program may query where gate_a / gate_q were.  A column the program does not read may be NULL;
+ * n_perm == 0 and n_lookups == 0 are accepted (the gate terms alone). */
+typedef struct {
+  const void* advice[H2MI_EXPR_MAX_ADVICE];
+  const void* fixed[H2MI_EXPR_MAX_FIXED];
+  const void* instance;
+  uint32_t n_perm, chunk_len; /* chunk_len = cs.degree() - 2: any length */
+  const void* perm_value[H2MI_FLEX_MAX_PERM];
+  const void* perm_sigma[H2MI_FLEX_MAX_PERM];
+  const void* perm_z[H2MI_FLEX_MAX_PERM];
+  uint32_t n_lookups;
+  const void* lookup_input[H2MI_FLEX_MAX_LOOKUPS];
+  const void* lookup_input_b[H2MI_FLEX_MAX_LOOKUPS];
+  const void* lookup_table[H2MI_FLEX_MAX_LOOKUPS];
+  const void* lookup_permuted_input[H2MI_FLEX_MAX_LOOKUPS];
+  const void* lookup_permuted_table[H2MI_FLEX_MAX_LOOKUPS];
+  const void* lookup_z[H2MI_FLEX_MAX_LOOKUPS];
+  const void* l0;
+  const void* l_last;
+  const void* l_active;
+} h2mi_expr_cosets;
+/* H2MI_EINVAL for a program that is malformed (unknown op, stack underflow or deeper than H2MI_MAX_EXPR_STACK, not exactly one value
+ * at an END, no final END, empty), reads a NULL column or a constant beyond n_constants, or rotates by 2^k or more.  The column
+ * pointers, the program and its constants (converted to the kernel's domain) travel in one device buffer written on `stream`. */
+int h2mi_plonk_evaluate_h_expr_dev(const h2mi_expr_cosets* cosets, const h2mi_gate_program* gates, uint32_t k, uint32_t extended_k,
+                                   uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
+                                   const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
+                                   const uint64_t* t_inv /* 2^(extended_k-k) x 4 */, void* d_h_out, h2mi_stream_t stream);
+
 /* ---- SRS generation helper: ParamsKZG::setup's g[i] = s_i * G   ------------------
  * d_scalars: n Fr (Montgomery).  d_out_affine: n G1Affine.  Fixed-base windowed multiplication of the
  * generator (1, 2) with on-device normalisation. */

@@ -32,6 +32,11 @@
  *                              H2MI_MAX_LOOKUPS (8) single-expression lookups (a lookup-advice column, or q_lookup * a), one instance
  *                              column, up to H2MI_MAX_PERM (64) equality-enabled columns: every column count
  *                              `builder.config(k, Some(minimum_rows))` takes for a circuit that fills a few dozen columns
+ *   H2MI_GATES_EXPRESSIONS     any `meta.create_gate(...)` (src/circuits/is_zero.rs, or.rs; the StandardPlonk and vertical gates too):
+ *                              the gate polynomials as a postfix program beside the struct (h2mi_gate_program, h2mi.h; keygen through
+ *                              h2mi_prover_keygen_gates) which ONE kernel interprets on the extended coset — any query of an advice,
+ *                              fixed or instance column at any rotation, constants, + - *, degree up to 9 (permutation chunks up to
+ *                              7); lookups, permutation and column limits as for FLEX_VERTICAL
  * Every function returns H2MI_OK or a negative H2MI_E* code (h2mi.h); no exception crosses the boundary.  Field elements
  * and points use the layouts of h2mi.h (4 / 8 uint64 limbs, Montgomery form).  A prover object is used by one thread at a time.
  */
@@ -58,6 +63,7 @@ typedef struct {
 
 #define H2MI_GATES_STANDARD_PLONK 1u
 #define H2MI_GATES_FLEX_VERTICAL 2u
+#define H2MI_GATES_EXPRESSIONS 3u /* cs->gates; n_gates / gate_advice / gate_selector are ignored: the gates are an h2mi_gate_program */
 
 #define H2MI_MAX_GATES H2MI_FLEX_MAX_GATES     /* 32 */
 #define H2MI_MAX_PERM H2MI_FLEX_MAX_PERM       /* 64 */
@@ -118,6 +124,17 @@ typedef struct h2mi_prover_s* h2mi_prover_t; /* the buffers, streams and phase s
 #define H2MI_KEYGEN_VK_ONLY 1u
 int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
                        size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
+/* The same with the gates as a program (cs->gates == H2MI_GATES_EXPRESSIONS; any other value: H2MI_EINVAL, as is that value given to
+ * h2mi_prover_keygen).  The key keeps its own copy of the ops and constants: the caller's memory is free after the call.
+ * h2mi_gate_program_check is the validation keygen applies, on the host alone (it works without a GPU): H2MI_EINVAL unless every op is
+ * known, every column index is within n_advice / n_fixed / n_instance and every constant index within n_constants, |rotation| < 2^k,
+ * the stack never underflows nor exceeds H2MI_MAX_EXPR_STACK and holds exactly one value at each END, the program ends with END and
+ * holds at least one polynomial, every advice / fixed (column, rotation) it reads is in cs->advice_queries / cs->fixed_queries (no
+ * verifier could check the proof otherwise), and every polynomial's degree (a query 1, a constant 0; ADD / SUB the larger, MUL the
+ * sum) is at most cs->degree.  It reports the largest polynomial degree and the deepest stack (either pointer may be NULL). */
+int h2mi_gate_program_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint32_t* degree_out, uint32_t* max_stack_out);
+int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint64_t g_lagrange_handle,
+                             const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
 int h2mi_prover_pk_release(h2mi_pk_t pk); /* H2MI_EINVAL while a prover created against it is alive */
 /* VerifyingKey::{fixed_commitments, permutation.commitments}: affine points (8 limbs each); either pointer may be NULL */
 int h2mi_prover_vk_commitments(h2mi_pk_t pk, uint64_t* fixed_out /* n_fixed x 8 */, uint64_t* permutation_out /* n_perm x 8 */);

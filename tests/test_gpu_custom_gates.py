@@ -1,0 +1,329 @@
+"""Gates given as data, on the device: k_evaluate_h_expr (csrc/h2mi_plonk.hip) against Python integers on random programs; the committed
+golden proofs of StandardPlonk, halo2_lib and the multi-column range circuit reproduced with their gates handed over as programs; the
+reference's is_zero and or circuits and a degree-6 circuit through custom.py against the oracle's generic prover and verifier
+(oracle/flex.py takes gates as callables), byte for byte; the ABI's refusals."""
+import ctypes as C
+import json
+import os
+import random
+import types
+
+import numpy as np
+import pytest
+
+import custom_gate_cases as cases
+from custom_gate_cases import OP_ADD, OP_ADVICE, OP_CONSTANT, OP_END, OP_FIXED, OP_INSTANCE, OP_MUL, OP_NEG, OP_SUB
+from oracle import bn254 as o
+from oracle import flex as FX
+
+pytestmark = pytest.mark.gpu
+
+R = o.R
+SRS_SECRET = 0x5EC2E7 + 0x48324D49
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _vals(buf, count):
+    return o.unpack(buf.to_numpy(shape=(count, 4), nbytes=count * 32), o.R)
+
+
+def _check_keys(keys, okeys, n):
+    assert o.unpack_points(keys.fixed_commitments) == okeys.fixed_commitments
+    assert o.unpack_points(keys.permutation_commitments) == okeys.permutation_commitments
+    assert keys.vk_bytes() == okeys.vk_bytes() and keys.transcript_repr == okeys.transcript_repr
+    for dev, want in zip(keys.sigma_values, okeys.sigma):
+        assert _vals(dev, n) == want
+    for dev, want in zip(keys.fixed_polys, okeys.fixed_polys):
+        assert _vals(dev, n) == want
+
+
+# ---- 1. the kernel alone -----------------------------------------------------------------------------------------------------------
+N_ADV, N_FIX = 3, 2
+KINDS = {OP_ADVICE: "advice", OP_FIXED: "fixed", OP_INSTANCE: "instance"}
+
+
+# (k, degree) of the random cases: every degree 3 .. 9, k = 4 .. 6; with k <= 6 only k = 6 with a degree from 6 (extended domain 8 n) reaches
+# an extended size of 512, so most cases sit there
+RANDOM_SHAPES = [(6, 6), (6, 7), (6, 8), (6, 9), (4, 3), (6, 6), (6, 7), (5, 4), (6, 8), (6, 9), (6, 5), (5, 9), (4, 5), (6, 7), (5, 3), (6, 8)]
+
+
+def _sub_chain(custom, rng, columns, leaves):
+    """x0 - (x1 - (x2 - ...)): SUB keeps its operand order, so `leaves` queries need a stack of `leaves`"""
+    qs = [custom.Expression("query", *_pick(rng, columns)) for _ in range(leaves)]
+    e = qs[-1]
+    for x in reversed(qs[:-1]):
+        e = x - e
+    return e
+
+
+def _pick(rng, columns):
+    kind, index, rots = rng.choice(columns)
+    return kind, index, rng.choice(rots)
+
+
+def _kernel_case(custom, case):
+    """-> (k, cs degree, [trees]).  Cases 0 .. 3 are built on purpose (stack depths 8 and 1, a sum and a subtrahend large enough for
+    the uploader's extra reductions, the degree limit 9); the rest are random trees of every degree 3 .. 9.  The degree also sizes the extended domain: 2^k (degree - 1) rounded up."""
+    rng = random.Random(4242 + case)
+    rots = list(range(-3, 4))
+    columns = [("advice", j, rots) for j in range(N_ADV)] + [("fixed", j, rots) for j in range(N_FIX)] + [("instance", 0, rots)]
+    Q = lambda: custom.Expression("query", *_pick(rng, columns))
+    if case == 0:  # the deepest stack the ABI allows (63 KB of LDS, four blocks), and a one-slot polynomial beside it
+        return 6, 9, [_sub_chain(custom, rng, columns, 8), -Q()]
+    if case == 1:  # stack depth 1 only; idx = 0 with a negative rotation is in every case, here it is all there is
+        return 4, 3, [custom.Expression("query", "advice", 0, -3), -custom.Expression("query", "instance", 0, -1), custom.Expression.constant(R - 1)]
+    if case == 2:  # a twelve-term sum (bound above 8p) and differences whose subtrahend is a sum of five: reductions get inserted
+        s12 = Q()
+        for _ in range(11):
+            s12 = s12 + Q()
+        s5 = Q() + Q() + Q() + Q() + Q()
+        return 6, 4, [s12 * Q(), Q() - s5, (-s5 + (s5 + s5)) * Q() * Q()]
+    if case == 3:  # degree 9: a product of nine queries
+        p = Q()
+        for _ in range(8):
+            p = p * Q()
+        return 6, 9, [p + custom.Expression.constant(5), Q() * Q() - Q()]
+    k, degree = RANDOM_SHAPES[case - 4]
+    while True:
+        trees = [cases.random_tree(custom, rng, rng.randrange(2, 6), columns, leaf_bias=0.2) for _ in range(rng.randrange(1, 4))]
+        if max(t.degree() for t in trees) == degree and max(t.stack_depth() for t in trees) <= 8:
+            return k, degree, trees
+
+
+@pytest.mark.parametrize("case", range(20))
+def test_expression_kernel_against_python_integers(gpu, case):
+    """h2mi_plonk_evaluate_h_expr_dev without permutation and lookups: h[i] = (Horner in y over the polynomials) * t_inv[i mod 2^(ek-k)]
+    at every point of the extended coset, with rotations wrapping around its ends"""
+    from halo2_scaffold_amd import custom, engine, plonk
+    from halo2_scaffold_amd.device import DevBuf
+
+    k, degree, trees = _kernel_case(custom, case)
+    dom = gpu.EvaluationDomain(degree, k)
+    size, rot = 1 << dom.extended_k, 1 << (dom.extended_k - k)
+    rng = random.Random(99 + case)
+    special = [0, 1, R - 1]
+    column = lambda: [rng.choice(special) if rng.random() < 0.3 else rng.randrange(R) for _ in range(size)]
+    data = {("advice", j): column() for j in range(N_ADV)}
+    data.update({("fixed", j): column() for j in range(N_FIX)})
+    data[("instance", 0)] = column()
+    bufs = {key: DevBuf.from_numpy(o.pack(col, R)) for key, col in data.items()}
+    constants, ops = {}, []
+    for t in trees:
+        ops += t.program(constants)[0]
+    consts = sorted(constants, key=constants.get)
+    prog = engine.GateProgram.build(ops, consts)
+    if case == 0:
+        assert max(t.stack_depth() for t in trees) == 8
+    if case == 1:
+        assert max(t.stack_depth() for t in trees) == 1
+    y = rng.randrange(R)
+    out = DevBuf(size * 32)
+    unused = DevBuf.from_numpy(o.pack([rng.randrange(R) for _ in range(size)], R))  # l_0 / l_last / l_active: loaded, multiplied into no term
+    plonk.evaluate_h_expr(dom, prog, [bufs[("advice", j)] for j in range(N_ADV)], [bufs[("fixed", j)] for j in range(N_FIX)], bufs[("instance", 0)],
+                          [], [], [], 1, [], unused, unused, unused, rng.randrange(R), rng.randrange(R), y, out, blinding_factors=5)
+    got = _vals(out, size)
+    tinv = [pow((pow(dom.g_coset * pow(dom.extended_omega, i, R) % R, 1 << k, R) - 1) % R, -1, R) for i in range(rot)]
+    want = []
+    for idx in range(size):
+        q = lambda op, c, r: data[(KINDS[op], c)][(idx + r * rot) % size]
+        polys, _ = cases.run_postfix(ops, consts, q)
+        v = 0
+        for p in polys:
+            v = (v * y + p) % R
+        want.append(v * tinv[idx % rot] % R)
+    assert got == want
+
+
+def test_kernel_cases_cover_what_they_should(h2):
+    from halo2_scaffold_amd import custom
+
+    used, degrees, depths, several_blocks = set(), set(), set(), 0
+    for case in range(20):
+        k, degree, trees = _kernel_case(custom, case)
+        several_blocks += 1 << (k + (degree - 2).bit_length()) >= 512  # the extended size 2^k (degree - 1) rounded up; a block takes 256 points
+        for t in trees:
+            used |= {op for op, _, _ in t.program()[0]}
+        degrees.add(max(t.degree() for t in trees))
+        depths.add(max(t.stack_depth() for t in trees))
+        assert 4 <= k <= 6
+    assert used == {OP_ADVICE, OP_FIXED, OP_INSTANCE, OP_CONSTANT, OP_ADD, OP_SUB, OP_MUL, OP_NEG, OP_END}
+    assert degrees >= set(range(3, 10)) and {1, 8} <= depths and several_blocks >= 11
+
+
+# ---- 2. one circuit, two descriptions ----------------------------------------------------------------------------------------------
+def _prove(params, keys, transcript_repr, advice, instance, seed):
+    from halo2_scaffold_amd import flex
+
+    pk = types.SimpleNamespace(keys=keys, transcript_repr=transcript_repr)
+    return flex.create_proof(params, pk, types.SimpleNamespace(advice=advice, instance=instance), seed)
+
+
+def test_standard_plonk_golden_through_a_program(gpu):
+    from halo2_scaffold_amd import circuits, custom, engine, keygen
+
+    g = json.load(open(os.path.join(GOLD, "standard_plonk_proofs.json")))
+    case = next(c for c in g["cases"] if c["k"] == 5)
+    params = gpu.ParamsKZG.setup(5, int(g["srs_secret"], 16))
+    cs = keygen.constraint_system(circuits.StandardPlonk, 5)
+    cs.gates = engine.GATES_EXPRESSIONS
+    syn = circuits.StandardPlonk(None).synthesize()
+    copies = [(lc, lr, rc, rr) for (lc, lr), (rc, rr) in syn.copies]
+    keys = engine.Keys(cs, params, syn.fixed, copies, gates=cases.standard_plonk_cs(custom).gate_program())
+    vk_bytes, repr_ = keygen.transcript_repr(5, 3, keys.fixed_commitments, keys.permutation_commitments)
+    assert vk_bytes.hex() == case["vk_bytes"]
+    proof = _prove(params, keys, repr_, circuits.StandardPlonk(int(case["witness_x"], 16)).synthesize().advice, [], case["seed"])
+    assert proof.hex() == case["proof"]
+    keys.release()
+    params.release()
+
+
+@pytest.mark.parametrize("name,shape,k", [("flex_proofs.json", "halo2_lib", 6), ("flex_multi_proofs.json", "range", 5)])
+def test_halo2_lib_goldens_through_a_program(gpu, name, shape, k):
+    """the vertical gates as ops instead of gate_advice / gate_selector: the same proof bytes as the proofs committed before the feature —
+    through the shared permutation / lookup tail, Horner's order over 1 and 3 gate polynomials, and (range: three gate columns, one
+    lookup-advice column, degree 4) the lookup path"""
+    from halo2_scaffold_amd import engine, flex, keygen
+
+    g = json.load(open(os.path.join(GOLD, name)))
+    case = next(c for c in g["cases"] if c["shape"] == shape and c["k"] == k)
+    bits, x, seed = case["lookup_bits"], int(case["x"], 16), case["seed"]
+    closure = (lambda cs: flex.range_closure(cs, x, bits)) if shape == "range" else (lambda cs: flex.halo2_lib_closure(cs, x))
+    cs = flex.configure(shape == "range", k, closure) if "num_advice" in case else flex.FlexGateCS(lookup=shape == "range")
+    if "num_advice" in case:
+        assert (cs.num_advice, cs.num_lookup_advice) == (case["num_advice"], case["num_lookup_advice"]) == (3, 1)
+    asg = closure(cs)
+    params = gpu.ParamsKZG.setup(k, int(g["srs_secret"], 16))
+    abi = cs.abi(k)
+    abi.gates = engine.GATES_EXPRESSIONS
+    prog = engine.GateProgram.build(cases.vertical_gate_ops(list(enumerate(cs.col_qs))), [])
+    assert prog.check(abi) == (3, 2)
+    fixed_cells = list(asg.fixed)
+    if cs.lookup:
+        fixed_cells[cs.col_table] = [v % R for v in asg.table_values]
+    index = {col: j for j, col in enumerate(cs.perm_columns)}
+    copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
+    keys = engine.Keys(abi, params, fixed_cells, copies, gates=prog)
+    del prog  # the key holds its own copy
+    vk_bytes, repr_ = keygen.transcript_repr(k, cs.degree, keys.fixed_commitments, keys.permutation_commitments)
+    assert vk_bytes.hex() == case["vk_bytes"]
+    proof = _prove(params, keys, repr_, asg.advice, asg.instance, seed)
+    assert proof.hex() == case["proof"]
+    keys.release()
+    params.release()
+
+
+# ---- 3. the reference's own circuits, 4. beyond degree 3 ---------------------------------------------------------------------------
+def _against_oracle(gpu, cs, asg, k, seed, name):
+    from halo2_scaffold_amd import custom
+
+    params = gpu.ParamsKZG.setup(k, SRS_SECRET)
+    keys = custom.Keys(params, cs, asg)
+    ocs = cases.oracle_cs(cs, name)
+    oasg = cases.oracle_assignment(ocs, asg)
+    okeys = FX.Keys(ocs, k, SRS_SECRET, oasg.fixed, oasg.copies)
+    _check_keys(keys, okeys, 1 << k)
+    ws = custom.Workspace(params, keys)
+    trace = {}
+    proof = custom.create_proof(params, keys, asg, seed, trace=trace, ws=ws)
+    want = FX.prove(okeys, oasg, seed)
+    for ch in ("theta", "beta", "gamma", "y", "x"):
+        assert trace[ch] == want[ch], ch
+    assert proof == want["proof"]
+    assert FX.verify(okeys, proof, oasg.instance)
+    return params, keys, ws, okeys, oasg, proof
+
+
+def _release(params, keys, ws):
+    ws.release()
+    keys.release()
+    params.release()
+
+
+@pytest.mark.parametrize("x", [0, 0x1234567])
+def test_is_zero_matches_the_oracle(gpu, x):
+    """src/circuits/is_zero.rs at k = 5 (its MockProver tests' size): keys, challenges, proof bytes; a witness with `out` flipped is
+    refused by mock, still proved by the device (create_proof does not check constraints), and refused by the verifier"""
+    from halo2_scaffold_amd import custom
+
+    cs, asg = cases.is_zero_circuit(custom, x)
+    custom.mock(asg, 5)
+    params, keys, ws, okeys, oasg, proof = _against_oracle(gpu, cs, asg, 5, 31 + x % 7, "is_zero")
+    _, broken = cases.is_zero_circuit(custom, x, flip_out=True)
+    with pytest.raises(ValueError, match="ISZERO gate"):
+        custom.mock(broken, 5)
+    bad_proof = custom.create_proof(params, keys, broken, 31, ws=ws)
+    assert len(bad_proof) == len(proof) and not FX.verify(okeys, bad_proof, oasg.instance)
+    _release(params, keys, ws)
+
+
+@pytest.mark.parametrize("a,b", [(1, 1), (0, 1)])
+def test_or_matches_the_oracle(gpu, a, b):
+    """src/circuits/or.rs at k = 5: one column queried at rotations 0, 1, 2"""
+    from halo2_scaffold_amd import custom
+
+    cs, asg = cases.or_circuit(custom, a, b)
+    custom.mock(asg, 5)
+    params, keys, ws, okeys, oasg, proof = _against_oracle(gpu, cs, asg, 5, 8, "or")
+    _, broken = cases.or_circuit(custom, a, b, flip_out=True)
+    with pytest.raises(ValueError, match="OR gate"):
+        custom.mock(broken, 5)
+    assert not FX.verify(okeys, custom.create_proof(params, keys, broken, 8, ws=ws), oasg.instance)
+    _release(params, keys, ws)
+
+
+@pytest.mark.parametrize("k", [4, 5])
+def test_degree_six_circuit_matches_the_oracle(gpu, k):
+    """gates of degree 6 with a negative rotation and an instance query: extended domain 8 n, five h pieces, one permutation set of
+    three columns (chunks of four)"""
+    from halo2_scaffold_amd import custom
+
+    cs, asg = cases.degree6_circuit(custom, 3, 11)
+    custom.mock(asg, k)
+    params, keys, ws, okeys, oasg, proof = _against_oracle(gpu, cs, asg, k, 2024, "degree6")
+    c = ws.prover.counts
+    assert (c.quotient, c.products) == (5, 2) and keys.domain.extended_k == k + 3
+    other = list(asg.instance)
+    other[-1] = (other[-1] + 1) % R
+    assert not FX.verify(okeys, proof, [other])
+    _release(params, keys, ws)
+
+
+# ---- 5. refusals -------------------------------------------------------------------------------------------------------------------
+def test_keygen_refuses_the_wrong_entry_point_and_bad_programs(gpu):
+    from halo2_scaffold_amd import custom, engine, flex
+
+    lib = gpu.lib
+    params = gpu.ParamsKZG.setup(5, SRS_SECRET)
+    cs, asg = cases.is_zero_circuit(custom, 3)
+    abi, good = cs.abi(5), cs.gate_program()
+    cells, keep = engine.pack_cells(asg.fixed)
+    copies = np.array([[1, 0, 0, 1]], dtype=np.uint32)
+
+    def keygen_gates(abi_, prog):
+        pk = C.c_void_p(0xDEAD)
+        rc = lib.h2mi_prover_keygen_gates(C.byref(abi_), C.byref(prog) if prog is not None else None, params.g_lagrange_handle, cells, copies.ctypes.data, 1,
+                                          0, C.byref(pk))
+        return rc, pk.value
+
+    pk = C.c_void_p(0xDEAD)
+    assert lib.h2mi_prover_keygen(C.byref(abi), params.g_lagrange_handle, cells, copies.ctypes.data, 1, 0, C.byref(pk)) == -1 and pk.value is None
+    rc, handle = keygen_gates(abi, good)
+    assert rc == 0 and handle
+    assert lib.h2mi_prover_pk_release(handle) == 0
+    underflow = engine.GateProgram.build([(OP_ADVICE, 0, 0), (OP_MUL, 0, 0), (OP_END, 0, 0)], [])
+    unqueried = engine.GateProgram.build([(OP_ADVICE, 1, 1), (OP_END, 0, 0)], [])
+    for prog in (underflow, unqueried):
+        assert keygen_gates(abi, prog) == (-1, None)
+    fabi = flex.FlexGateCS(lookup=False).abi(5)  # gates == 2
+    fcells, fkeep = engine.pack_cells([{}, {}])
+    pk = C.c_void_p(0xDEAD)
+    prog = engine.GateProgram.build(cases.vertical_gate_ops([(0, 1)]), [])
+    assert lib.h2mi_prover_keygen_gates(C.byref(fabi), C.byref(prog), params.g_lagrange_handle, fcells, None, 0, 0, C.byref(pk)) == -1 and pk.value is None
+    # a degree-3 constraint system cannot take a degree-4 polynomial; permutation chunks above three are fine for this shape
+    deg4 = engine.GateProgram.build([(OP_ADVICE, 0, 0)] * 4 + [(OP_MUL, 0, 0)] * 3 + [(OP_END, 0, 0)], [])
+    assert keygen_gates(abi, deg4) == (-1, None)
+    abi.degree = 9
+    rc, handle = keygen_gates(abi, deg4)
+    assert rc == 0 and lib.h2mi_prover_pk_release(handle) == 0
+    del keep, fkeep
+    params.release()
