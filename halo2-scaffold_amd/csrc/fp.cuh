@@ -266,24 +266,9 @@ __device__ __forceinline__ fe fe_to_mont(const fe& a) {  // canonical -> Montgom
   return fe_mul<F>(a, fe_const<F>(F::R2));
 }
 
-// a^(MOD-2) by square-and-multiply over the fixed exponent (Fermat inversion); inv(0) = 0.
-template <class F>
-__device__ __noinline__ fe fe_inv(const fe& a) {
-  fe r = fe_one<F>();
-  // exponent = MOD - 2 (MOD is odd and its low word is > 2, so only limb 0 changes)
-  for (int i = 7; i >= 0; i--) {
-    uint32_t e = F::MOD[i] - (i == 0 ? 2u : 0u);
-    for (int b = 31; b >= 0; b--) {
-      r = fe_sqr<F>(r);
-      if ((e >> b) & 1u) r = fe_mul<F>(r, a);
-    }
-  }
-  return r;
-}
-
 // a^-1 by the binary extended Euclidean algorithm: ~2 * 254 shift / subtract rounds of 256-bit integer work
 // instead of ~380 dependent multiplications — for the places where ONE inversion sits on a latency-critical
-// path (a lone lane: ~50 us against ~500 us for fe_inv).  Montgomery in and out; inv(0) = 0.  Not constant time.
+// path (a lone lane: ~50 us against ~500 us for a Fermat inversion on these limbs).  Montgomery in and out; inv(0) = 0.  Not constant time.
 template <class F>
 __device__ __noinline__ fe fe_inv_gcd(const fe& a_mont) {
   if (fe_is_zero(a_mont)) return a_mont;
@@ -326,7 +311,7 @@ __device__ __noinline__ fe fe_inv_gcd(const fe& a_mont) {
 
 // The same inverse by division steps (inv_divsteps.cuh): a third of the instructions, no data-dependent branches inside a batch.
 // For the single inversions a prover's critical path waits for (the grand products' denominators); fe_inv_gcd stays as its
-// fallback and cross-check (h2mi_dbg_field_op: op 4 = Fermat, op 9 = this, op 10 = fe_inv_gcd).
+// fallback and cross-check (h2mi_dbg_field_op: op 9 = this, op 10 = fe_inv_gcd).
 template <class F>
 __device__ __noinline__ fe fe_inv_ds(const fe& a_mont) {
   if (fe_is_zero(a_mont)) return a_mont;

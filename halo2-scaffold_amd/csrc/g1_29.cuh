@@ -1,5 +1,9 @@
-// XYZZ mixed addition on the lazy 29-bit-limb representation (f29.cuh) — the inner loop of the MSM
-// bucket accumulation.  Same group law as g1.cuh (madd-2008-s, complete), different field layer.
+// The BN254 G1 group law (y^2 = x^3 + 3 over Fq) on the lazy 29-bit-limb representation (f29.cuh) — the only one on the device:
+// the MSM kernels, the table builders, the group FFT and the small point kernels of h2mi_core.hip all run these functions
+// (g1_29_quad.cuh: the same formulas spread over four lanes).  Extended Jacobian "XYZZ" coordinates (x = X/ZZ, y = Y/ZZZ,
+// ZZ^3 = ZZZ^2; identity ZZ = 0): madd-2008-s (8M + 2S, no inversion), add-2008-s, dbl-2008-s-1, every special case handled
+// (identity operands, P + P, P + (-P)).  Host and device, free of the 32-bit-limb `fe`: tests/host/f29_host.cpp compiles this header
+// with g++.  The ABI's Montgomery-2^256 point layouts and their conversion to and from xyzz29 are in g1.cuh.
 //
 // Coordinates are Montgomery-2^261 values, loosely reduced.  Invariants of an accumulator between
 // additions (value bounds in units of p; all limbs normalized):
@@ -168,6 +172,28 @@ H2_HD void xyzz29_add(xyzz29& a, const xyzz29& b) {
   a.y = f29_mul2<F>(t, r, f29_sub(f29_zero(), s1, F::K2), ppp);  // Y3 = (T*R + (2p - S1)*PPP) / 2^261 < 1.2: one reduction
   a.zz = zz;
   a.zzz = zzz;
+}
+
+// Jacobian (X, Y, Z) (x = X / Z^2, y = Y / Z^3; Z limbs all zero = identity) -> XYZZ: ZZ = Z^2, ZZZ = Z^3.  In: X < 6, Y < 4,
+// Z < 8 (units of p), normalized.  Out: X, Y unchanged, ZZ < 1 + eps * 64 = 1.38, ZZZ = ZZ * Z < 1 + eps * 11.1 = 1.07 — the
+// xyzz29_dbl / xyzz29_add invariant.  (From canonical coordinates, what g1.cuh feeds it: X, Y < 1, ZZ, ZZZ < 1.006.)
+H2_HD xyzz29 xyzz29_from_jacobian(const f29& x, const f29& y, const f29& z) {
+  using F = Fq29;
+  if (f29_limbs_zero(z)) return xyzz29_identity();
+  xyzz29 r;
+  r.x = x;
+  r.y = y;
+  r.zz = f29_sqr<F>(z);
+  r.zzz = f29_mul<F>(r.zz, z);
+  return r;
+}
+// XYZZ -> Jacobian without inversion: (X * ZZ, Y * ZZZ, ZZ), since ZZ^3 = ZZZ^2.  In: the xyzz29_dbl invariant, not the
+// identity (the caller encodes that one in its own format).  Out: X < 1 + eps * 9 = 1.06, Y < 1 + eps * 6 = 1.04, Z = ZZ < 1.5.
+H2_HD void xyzz29_to_jacobian(const xyzz29& p, f29& x, f29& y, f29& z) {
+  using F = Fq29;
+  x = f29_mul<F>(p.x, p.zz);
+  y = f29_mul<F>(p.y, p.zzz);
+  z = p.zz;
 }
 
 // XYZZ -> affine (canonical Montgomery-2^261 limbs): x = X / ZZ, y = Y / ZZZ with one inversion

@@ -61,57 +61,48 @@ void prof_begin(const char* name, hipStream_t s) {
 void prof_end(hipStream_t s) { H2_IGNORE(hipEventRecord(ctx().prof.back().b, s)); }
 
 // sum of k Jacobian points by one thread (k is tiny: the number of GPUs)
-__global__ void k_g1_sum_jac(const uint8_t* pts, size_t k, uint8_t* out) {
+__global__ void __launch_bounds__(64) k_g1_sum_jac(const uint8_t* pts, size_t k, uint8_t* out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  xyzz acc = xyzz_identity();
-  for (size_t i = 0; i < k; i++) {
-    xyzz p = jac_to_xyzz(jac_load(pts + i * 96));
-    xyzz_add(acc, p);
-  }
-  jac_store(out, xyzz_to_jac(acc));
+  xyzz29 acc = xyzz29_identity();
+  for (size_t i = 0; i < k; i++) xyzz29_add(acc, xyzz29_from_jac(jac_load(pts + i * 96)));
+  jac_store(out, jac_from_xyzz29(acc));
 }
 
 // out[j] = sum over r < world of pts[r*k + j]  (rank-major partial results of k MSMs)
 __global__ void __launch_bounds__(64) k_g1_fold_groups(const uint8_t* pts, size_t world, size_t k, uint8_t* out) {
   size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= k) return;
-  xyzz acc = xyzz_identity();
-  for (size_t r = 0; r < world; r++) {
-    xyzz p = jac_to_xyzz(jac_load(pts + (r * k + j) * 96));
-    xyzz_add(acc, p);
-  }
-  jac_store(out + j * 96, xyzz_to_jac(acc));
+  xyzz29 acc = xyzz29_identity();
+  for (size_t r = 0; r < world; r++) xyzz29_add(acc, xyzz29_from_jac(jac_load(pts + (r * k + j) * 96)));
+  jac_store(out + j * 96, jac_from_xyzz29(acc));
 }
 
 __global__ void k_g1_normalize(const uint8_t* pts, size_t k, uint8_t* out) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= k) return;
-  xyzz p = jac_to_xyzz(jac_load(pts + i * 96));
-  affine_store(out + i * 64, xyzz_to_affine(p));
+  affine_store(out + i * 64, affine_from_xyzz29(xyzz29_from_jac(jac_load(pts + i * 96))));
 }
 
 // ---- fixed-base table of the generator: T[w][d] = d * 2^(8w) * G, d in 1..255 (d = 0 unused) -------
+// Only k_fixed_base_mul reads it: like the MSM's tables, an entry is the packed canonical Montgomery-2^261 limbs of (x, y).
 __global__ void __launch_bounds__(256) k_fixed_base_table(uint8_t* table) {
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;  // t = w*256 + d
   if (t >= 32 * 256) return;
   uint32_t w = t >> 8, d = t & 255;
-  affine g;
-  g.x = fe_one<Fq>();
-  g.y = fe_dbl<Fq>(fe_one<Fq>());  // (1, 2) in Montgomery form
-  affine outp;
-  if (d == 0) {
-    outp.x = fe_zero();
-    outp.y = fe_zero();
-  } else {
-    // scalar = d << (8w): left-to-right double-and-add over the 8 bits of d, then 8w doublings
-    xyzz acc = xyzz_identity();
-    for (int b = 7; b >= 0; b--) {
-      acc = xyzz_dbl(acc);
-      if ((d >> b) & 1u) xyzz_madd(acc, g);
-    }
-    for (uint32_t i = 0; i < 8 * w; i++) acc = xyzz_dbl(acc);
-    outp = xyzz_to_affine(acc);
+  const f29 gx = f29_const<Fq29>(Fq29::ONE);                                           // G = (1, 2)
+  const f29 gy = f29_reduce_canonical<Fq29>(f29_normalize(f29_dbl(gx)));               // 2 * ONE < 2p -> canonical
+  // scalar = d << (8w): left-to-right double-and-add over the 8 bits of d, then 8w doublings (d = 0: the identity throughout)
+  xyzz29 acc = xyzz29_identity();
+  for (int b = 7; b >= 0; b--) {
+    acc = xyzz29_dbl(acc);
+    if ((d >> b) & 1u) xyzz29_madd(acc, gx, gy);
   }
+  for (uint32_t i = 0; i < 8 * w; i++) acc = xyzz29_dbl(acc);
+  f29 x, y;
+  xyzz29_to_affine(acc, x, y);  // identity -> (0, 0)
+  affine outp;
+  f29_pack(x, outp.x.v);
+  f29_pack(y, outp.y.v);
   affine_store(table + (size_t)t * 64, outp);
 }
 
@@ -119,15 +110,20 @@ __global__ void __launch_bounds__(256) k_fixed_base_mul(const fe* scalars, size_
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   fe s = fe_from_mont<FrP>(fe_load(&scalars[i]));
-  xyzz acc = xyzz_identity();
+  xyzz29 acc = xyzz29_identity();
   for (int w = 0; w < 32; w++) {
-    uint32_t d = (s.v[w >> 2] >> ((w & 3) * 8)) & 255u;
-    if (d) {
-      affine p = affine_load(table + ((size_t)(w * 256 + d)) * 64);
-      xyzz_madd(acc, p);
+    // digit w is the low byte, then the scalar moves down a byte (static indices only: a digit index into the word array would
+    // put it in scratch memory; see g1fft_scale)
+    const uint32_t d = s.v[0] & 255u;
+#pragma unroll
+    for (int j = 0; j < 7; j++) s.v[j] = (s.v[j] >> 8) | (s.v[j + 1] << 24);
+    s.v[7] >>= 8;
+    if (d) {  // a table point is never the identity (d 2^(8w) < r)
+      const affine p = affine_load(table + ((size_t)(w * 256 + d)) * 64);
+      xyzz29_madd(acc, f29_unpack(p.x.v), f29_unpack(p.y.v));
     }
   }
-  affine_store(out + i * 64, xyzz_to_affine(acc));
+  affine_store(out + i * 64, affine_from_xyzz29(acc));
 }
 
 int launch_fold_groups(const uint8_t* pts, size_t world, size_t k, uint8_t* out, hipStream_t s) {

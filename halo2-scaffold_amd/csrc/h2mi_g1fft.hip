@@ -14,7 +14,6 @@
 // Integer-multiply bound like the MSM accumulation (no MFMA: these are not dense contractions); 2 x 144 B of HBM traffic per
 // butterfly against ~380 point operations.
 #include "g1.cuh"
-#include "g1_29.cuh"
 #include "h2mi_fr_tables.h"
 
 namespace h2 {
@@ -72,14 +71,7 @@ __device__ xyzz29 g1fft_scale(const xyzz29& b, const Scalar256& k) {
 __global__ void __launch_bounds__(256) k_g1fft_load(const uint8_t* in, uint32_t* scratch, uint32_t log_n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (1u << log_n)) return;
-  const affine a = affine_load(in + (size_t)i * 64);
-  xyzz29 p = xyzz29_identity();
-  if (!affine_is_identity(a)) {
-    p.x = f29_reduce_canonical<Fq29>(f29_from_mont256<Fq29>(a.x.v));
-    p.y = f29_reduce_canonical<Fq29>(f29_from_mont256<Fq29>(a.y.v));
-    p.zz = f29_const<Fq29>(Fq29::ONE);
-    p.zzz = f29_const<Fq29>(Fq29::ONE);
-  }
+  const xyzz29 p = xyzz29_from_affine(affine_load(in + (size_t)i * 64));
   const uint32_t r = log_n ? (__brev(i) >> (32 - log_n)) : 0;
   g1fft_store(scratch + (size_t)r * G1FFT_POINT_WORDS, p);
 }
@@ -118,17 +110,7 @@ __global__ void __launch_bounds__(256) k_g1fft_store(const uint32_t* a, uint32_t
   if (i >= n) return;
   xyzz29 p = g1fft_load(a + (size_t)i * G1FFT_POINT_WORDS);
   if (has_scale) p = g1fft_scale(p, scale);
-  affine o;
-  if (xyzz29_is_identity(p)) {
-    o.x = fe_zero();
-    o.y = fe_zero();
-  } else {
-    f29 x, y;
-    xyzz29_to_affine(p, x, y);
-    f29_to_mont256<Fq29>(x, o.x.v);
-    f29_to_mont256<Fq29>(y, o.y.v);
-  }
-  affine_store(out + (size_t)i * 64, o);
+  affine_store(out + (size_t)i * 64, affine_from_xyzz29(p));
 }
 
 }  // namespace h2

@@ -1,6 +1,6 @@
 /* h2mi_hooks.h — test hooks of libh2mi_hooks.so (the product's objects + csrc/h2mi_hooks.hip); never part of libh2mi.so.
  * Elementwise device arithmetic on host arrays, used by the parity tests only: the 32-bit-limb field operations and whole point
- * operations (tests/test_gpu_parity.py), and the 29-bit-limb layer the hot kernels compute in, on chosen limbs
+ * operations of the one group law (tests/test_gpu_parity.py), and the 29-bit-limb layer the hot kernels compute in, on chosen limbs
  * (h2mi_dbg_f29_*, tests/test_gpu_f29.py). */
 #ifndef H2MI_HOOKS_H
 #define H2MI_HOOKS_H
@@ -8,9 +8,10 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-int h2mi_dbg_field_op(int field /*0=Fq,1=Fr*/, int op /*0=mul,1=add,2=sub,3=sqr,4=inv (Fermat),5=from_mont,6=to_mont,7=neg,8=dbl,9=inv by division steps,10=inv by binary Euclid*/,
+int h2mi_dbg_field_op(int field /*0=Fq,1=Fr*/, int op /*0=mul,1=add,2=sub,3=sqr,5=from_mont,6=to_mont,7=neg,8=dbl,9=inv by division steps,10=inv by binary Euclid*/,
                       const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
-/* op 0: out = P + Q (affine inputs, via XYZZ mixed add); 1: 2P; 2: P + Q via XYZZ full add; output Jacobian (12 limbs each) */
+/* the group law the MSM runs (csrc/g1_29.cuh) through the format bridge of csrc/g1.cuh.  op 0: out = P + Q (affine inputs, via
+ * xyzz29_madd); 1: 2P (xyzz29_dbl); 2: P + Q via xyzz29_add, Q as a representative with ZZ != 1; output Jacobian (12 limbs each) */
 int h2mi_dbg_g1_op(int op, const uint64_t* p_affine, const uint64_t* q_affine, uint64_t* out_jac, size_t n);
 /* the lane-cooperative point operations of the bucket reduction (csrc/g1_29_quad.cuh), four lanes per
  * element: op 0 = P[i] + Q[i] (XYZZ + XYZZ), op 1 = 2 P[i]; affine Montgomery in, Jacobian out */

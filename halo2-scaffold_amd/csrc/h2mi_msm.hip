@@ -200,10 +200,10 @@ __global__ void __launch_bounds__(256) k_msm_table_first(const uint8_t* bases, u
   if (i >= n) return;
   affine p = affine_load(bases + i * 64);
   if (!affine_is_identity(p)) {
-    affine q;
-    f29_pack(f29_reduce_canonical<Fq29>(f29_from_mont256<Fq29>(p.x.v)), q.x.v);
-    f29_pack(f29_reduce_canonical<Fq29>(f29_from_mont256<Fq29>(p.y.v)), q.y.v);
-    p = q;
+    f29 x, y;
+    affine_to_f29(p, x, y);
+    f29_pack(x, p.x.v);
+    f29_pack(y, p.y.v);
   }
   affine_store(table0 + i * 64, p);
 }
@@ -231,13 +231,13 @@ __global__ void __launch_bounds__(256) k_msm_table_next(const uint8_t* prev, uin
 __global__ void __launch_bounds__(64) k_msm_table_sum_point(const uint8_t* sum_jac, uint8_t* table, size_t stride, size_t n, uint32_t W, uint32_t c) {
   const uint32_t w = threadIdx.x;
   if (w >= W) return;
-  const jac j = jac_load(sum_jac);
+  const xyzz29 b = xyzz29_from_jac(jac_load(sum_jac));
   affine out;
   out.x = fe_zero();
   out.y = fe_zero();
-  if (!fe_is_zero(j.z)) {
-    const affine a = xyzz_to_affine(jac_to_xyzz(j));  // Montgomery-2^256
-    f29 x = f29_reduce_canonical<Fq29>(f29_from_mont256<Fq29>(a.x.v)), y = f29_reduce_canonical<Fq29>(f29_from_mont256<Fq29>(a.y.v));
+  if (!xyzz29_is_identity(b)) {
+    f29 x, y;
+    xyzz29_to_affine(b, x, y);
     if (w) {
       xyzz29 acc = xyzz29_dbl_affine(x, y);
       for (uint32_t k = 1; k < c * w; k++) acc = xyzz29_dbl(acc);
@@ -1132,22 +1132,8 @@ __global__ void __launch_bounds__(128) k_msm_final(const TailBatch tb) {
     __syncthreads();
   }
   if (tid == 0) {
-    xyzz29 r = lds[0];
-    jac j;
-    if (xyzz29_is_identity(r)) {
-      j.x = fe_zero(); j.y = fe_one<Fq>(); j.z = fe_zero();
-    } else if (d.canonical) {  // h2mi_msm_set_canonical(1): the representative with Z = 1
-      f29 ax, ay;
-      xyzz29_to_affine(r, ax, ay);
-      f29_to_mont256<Fq29>(ax, j.x.v);
-      f29_to_mont256<Fq29>(ay, j.y.v);
-      j.z = fe_one<Fq>();
-    } else {
-      f29_to_mont256<Fq29>(f29_mul<Fq29>(r.x, r.zz), j.x.v);
-      f29_to_mont256<Fq29>(f29_mul<Fq29>(r.y, r.zzz), j.y.v);
-      f29_to_mont256<Fq29>(r.zz, j.z.v);
-    }
-    jac_store(d.out, j);
+    const xyzz29 r = lds[0];
+    jac_store(d.out, jac_from_xyzz29(r, d.canonical));  // h2mi_msm_set_canonical(1): the representative with Z = 1
     if (d.stats) d.stats[0] = d.off[d.nb];
   }
 }
@@ -1283,22 +1269,8 @@ __device__ __forceinline__ void small_finish(const SmallDesc& d, xyzz29* X) {
   __syncthreads();
   seg_tree_sum(X, 1, T);
   if (tid == 0) {
-    xyzz29 r = X[0];
-    jac j;
-    if (xyzz29_is_identity(r)) {
-      j.x = fe_zero(); j.y = fe_one<Fq>(); j.z = fe_zero();
-    } else if (d.canonical) {
-      f29 ax, ay;
-      xyzz29_to_affine(r, ax, ay);
-      f29_to_mont256<Fq29>(ax, j.x.v);
-      f29_to_mont256<Fq29>(ay, j.y.v);
-      j.z = fe_one<Fq>();
-    } else {
-      f29_to_mont256<Fq29>(f29_mul<Fq29>(r.x, r.zz), j.x.v);
-      f29_to_mont256<Fq29>(f29_mul<Fq29>(r.y, r.zzz), j.y.v);
-      f29_to_mont256<Fq29>(r.zz, j.z.v);
-    }
-    jac_store(d.out, j);
+    const xyzz29 r = X[0];
+    jac_store(d.out, jac_from_xyzz29(r, d.canonical));
     if (d.stats) d.stats[0] = ins_sh;
   }
 }

@@ -41,7 +41,6 @@ def test_field_ops_bit_exact(gpu, hooks, field, mod):
     assert o.unpack(run(3, False), mod) == [x * x % mod for x in a]
     assert o.unpack(run(7, False), mod) == [(-x) % mod for x in a]
     assert o.unpack(run(8, False), mod) == [2 * x % mod for x in a]
-    assert o.unpack(run(4, False), mod) == [pow(x, -1, mod) if x else 0 for x in a]
     # the two Euclid-style inversions: division steps (what the grand products' one inversion runs) and the shift / subtract form
     assert o.unpack(run(9, False), mod) == [pow(x, -1, mod) if x else 0 for x in a]
     assert o.unpack(run(10, False), mod) == [pow(x, -1, mod) if x else 0 for x in a]
@@ -103,6 +102,94 @@ def test_g1_quad_lane_ops(gpu, hooks):
         assert [o.unpack_jacobian(out[i]) for i in range(n)] == [o.g1_add(p, q) for p, q in zip(P, Qs)]
         assert hooks.h2mi_dbg_g1_quad_op(1, A.ctypes.data, None, out.ctypes.data, n) == 0
         assert [o.unpack_jacobian(out[i]) for i in range(n)] == [o.g1_double(p) for p in P]
+
+
+def _jacobians(points, rng):
+    """(n, 12) Jacobian limbs (x l^2, y l^3, l) of the affine points with a fresh random l != 1 each; None -> (0, 1, 0)"""
+    return np.stack([o.pack_jacobian(p, z=int.from_bytes(rng.bytes(32), "little") % (o.Q - 2) + 2) for p in points])
+
+
+def test_g1_point_kernels_edge_cases(gpu):
+    """h2mi_g1_sum_jacobian, h2mi_g1_fold_groups and h2mi_g1_batch_normalize on Jacobian inputs with Z != 1 (other representatives
+    of the points than the Z = 1 the conversions could get away with), at the branches of the complete addition: the identity
+    (Z = 0) first, in the middle and last; the doubling branch (the same point twice in a row as two representatives, and a
+    running sum A + B met by A + B); a point, its negative, then a further point; a total that is the identity;
+    k = 1; fold shapes world 1 / 3 x k 1 / 65 (one past a 64-lane block); 257 points to normalise (one past a 256-lane
+    block).  Group elements against the oracle."""
+    lib = gpu.lib
+    rng = np.random.default_rng(61)
+    A, B, Cc, D, E = [o.g1_mul(int(rng.integers(2, 1 << 20)), o.G1_GEN) for _ in range(5)]
+    AB = o.g1_add(A, B)
+    patterns = [
+        [None, A, B], [A, None, B], [A, B, None],  # the identity first, in the middle, last
+        [B, B, Cc],                                # accumulator == addend: the doubling branch
+        [A, B, AB],                                # the same with an accumulator that is itself a sum (ZZ != Z^2 of any input)
+        [D, o.g1_neg(D), E],                       # cancels to the identity, then goes on
+        [A, B, o.g1_neg(AB)],                      # the total is the identity
+        [None, None, None],
+        [Cc, D, E],
+    ]
+
+    def total(points):
+        acc = None
+        for q in points:
+            acc = o.g1_add(acc, q)
+        return acc
+
+    assert total(patterns[6]) is None and total(patterns[5]) == E
+    out = np.zeros(12, dtype=np.uint64)
+    for pts in patterns + [[A], [None], [None, A, B, None, B, Cc, None, D, o.g1_neg(D), E, None]]:  # k = 1 among them
+        jac = _jacobians(pts, rng)
+        assert lib.h2mi_g1_sum_jacobian(jac.ctypes.data, len(pts), out.ctypes.data) == 0
+        assert o.unpack_jacobian(out) == total(pts), pts
+    for world, k in [(1, 1), (1, 65), (3, 1), (3, 65)]:
+        if world == 3:  # column j = the points of MSM j, one per rank; k = 1: the doubling pattern
+            cols = [patterns[(j + 3) % len(patterns)] for j in range(k)]
+        else:  # A, B, the identity, ... singly
+            cols = [[patterns[j % 7][j % 3]] for j in range(k)]
+        jac = np.zeros((world, k, 12), dtype=np.uint64)
+        for j, col in enumerate(cols):
+            jac[:, j] = _jacobians(col, rng)
+        got = np.zeros((k, 12), dtype=np.uint64)
+        assert lib.h2mi_g1_fold_groups(jac.ctypes.data, world, k, got.ctypes.data) == 0
+        assert [o.unpack_jacobian(g) for g in got] == [total(col) for col in cols], (world, k)
+    pool = [None, A, B, AB, Cc, D, o.g1_neg(D), E]
+    pts = [pool[int(i)] for i in rng.integers(1, len(pool), 257)]
+    pts[0] = pts[128] = pts[256] = None
+    jac = _jacobians(pts, rng)
+    aff = np.zeros((257, 8), dtype=np.uint64)
+    assert lib.h2mi_g1_batch_normalize(jac.ctypes.data, 257, aff.ctypes.data) == 0
+    assert o.unpack_points(aff) == pts
+
+
+def test_fixed_base_mul_edge_scalars(gpu):
+    """h2mi_g1_fixed_base_mul_dev (one table point per non-zero scalar byte) against o.g1_mul(k, G): 0 -> (0, 0); the small and
+    the extreme scalars; every byte non-zero (32 additions); exactly one non-zero byte, in each of the 32 positions (one addition
+    into the identity accumulator, from each window's table); random ones up to 257 = one past a 256-lane block; and n = 1."""
+    from halo2_scaffold_amd.device import DevBuf
+
+    rng = np.random.default_rng(62)
+    ks = [0, 1, 2, 255, 256, (1 << 8) - 1 + (1 << 8), 1 << 248, o.R - 1]
+    ks.append(int.from_bytes(bytes([0x2F] + [int(b) for b in rng.integers(1, 256, 30)] + [0x01]), "little"))  # every byte non-zero, < r
+    ks += [int(rng.integers(1, 0x30 if w == 31 else 256)) << (8 * w) for w in range(32)]  # one non-zero byte (top byte of r is 0x30)
+    ks += [int.from_bytes(rng.bytes(32), "little") % o.R for _ in range(257 - len(ks))]
+    assert len(ks) == 257 and all(k < o.R for k in ks) and all(b for b in ks[8].to_bytes(32, "little"))
+    want = [o.g1_mul(k, o.G1_GEN) if k else None for k in ks]
+    d_sc = DevBuf.from_numpy(o.pack(ks, o.R))
+    d_out = DevBuf(257 * 64)
+    for n in (257, 1):
+        assert gpu.lib.h2mi_memset_zero(d_out.ptr, 257 * 64) == 0
+        assert gpu.lib.h2mi_g1_fixed_base_mul_dev(d_sc.ptr, n, d_out.ptr, None) == 0
+        got = d_out.to_numpy(shape=(257, 8))
+        assert o.unpack_points(got[:n]) == want[:n], n
+        assert not got[n:].any()  # nothing written past n
+    for k1 in (o.R - 1, ks[8]):  # n = 1 on a scalar that takes every window
+        one = DevBuf.from_numpy(o.pack([k1], o.R))
+        assert gpu.lib.h2mi_g1_fixed_base_mul_dev(one.ptr, 1, d_out.ptr, None) == 0
+        assert o.unpack_points(d_out.to_numpy(shape=(257, 8))[:1]) == [o.g1_mul(k1, o.G1_GEN)]
+        one.free()
+    d_sc.free()
+    d_out.free()
 
 
 @pytest.mark.parametrize("log_n", [0, 1, 2, 3, 5, 8, 10, 11, 12, 13])
@@ -276,6 +363,26 @@ def test_msm_edge_cases(gpu):
     # digit carry chain: scalars with all-ones windows
     carry = o.pack([(1 << 253) - 1, (1 << 200) - 1, 0x7FFF8000_7FFF8000, 0x8000, 0x8001, 0xFFFF], o.R)
     _msm_case(gpu, carry, pts[:6])
+
+
+def test_msm_sum_point_that_is_the_identity(gpu):
+    """a base set whose points sum to the identity (P, -P, Q, -Q, ...): the registration's sum point — slot n of every window,
+    the extra base of the dominant-value shift — is then the identity (k_msm_table_sum_point's Z = 0 branch).  n = 4096 ad-hoc
+    bases: the smallest set that gets a sum point (SHIFT_MIN_N, and an ad-hoc set never takes the small path).  All scalars
+    equal, so the shift is taken: the result is the identity; and with one scalar different, (s' - s) P_0."""
+    from oracle import cref
+
+    n = 4096
+    half = o.unpack_points(cref.g1_mul_gen(o.random_field_limbs(n // 2, 4242), 4))
+    pts = [q for p in half for q in (p, o.g1_neg(p))]
+    bases = o.pack_points(pts)
+    s, s1 = 0x1234567 * 0x89ABCDEF123 % o.R, o.R - 5
+    sc = np.tile(o.pack([s], o.R)[0], (n, 1))
+    assert o.unpack_jacobian(gpu.best_multiexp(sc, bases)) is None
+    sc[0] = o.pack([s1], o.R)[0]
+    want = o.g1_mul((s1 - s) % o.R, pts[0])
+    assert o.unpack_jacobian(cref.msm(sc, bases, 2)) == want
+    assert o.unpack_jacobian(gpu.best_multiexp(sc, bases)) == want
 
 
 MSM_SPARSE, MSM_INORDER, MSM_GENERAL = 1, 2, 4  # include/h2mi.h H2MI_MSM_*
@@ -1104,8 +1211,10 @@ def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):
 
 def test_eip196_vectors_hip_path(gpu, hooks):
     """third-party anchors (tests/golden/eip196_vectors.json: EIP-196 ECADD / ECMUL vectors, not derived from the oracle)
-    through the HIP path: the XYZZ mixed / full additions and the lane-cooperative addition of the bucket reduction for
-    ECADD, the MSM pipeline (ad-hoc bases, n = 1 and n = 2) for ECMUL and ECADD."""
+    through the HIP path.  The device has one group law (csrc/g1_29.cuh, on the 29-bit-limb field), so ECADD goes through the
+    very formulas the MSM runs: its mixed and full XYZZ additions (h2mi_dbg_g1_op: xyzz29_madd, xyzz29_add behind the format
+    bridge of csrc/g1.cuh) and the lane-cooperative addition of the bucket reduction; the MSM pipeline (ad-hoc bases, n = 1 and
+    n = 2) for ECMUL and ECADD."""
     import json
 
     v196 = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "eip196_vectors.json")))
