@@ -17,6 +17,7 @@
 // Integer / byte work over HBM-resident vectors: no field multiplication except the Montgomery -> canonical conversion
 // of the inputs.
 #include <algorithm>
+#include <vector>
 
 #include "fp.cuh"
 #include "h2mi_internal.h"
@@ -136,6 +137,141 @@ __global__ void __launch_bounds__(256) k_lk_fill_table(const uint32_t* repeated,
   fe_store(&s_perm[j], fe_load(&sorted_mont[run_of(lstart, n_unique, after)]));
 }
 
+// ---- per-proof tables: the distinct values of a vector, sorted (h2mi_fr_sort_unique_dev) -----------------------------------------
+// A table that is compressed with theta, or holds advice, is known only inside the proof, so the keygen-time host sort above does
+// not apply.  LSD radix sort, 8-bit digits, over an INDEX permutation (the 32-byte keys are converted to canonical form once and
+// never move): per digit a tile histogram laid out [digit][tile], ONE exclusive scan of it (scan.cuh) = every tile's output
+// offset for every digit, and a stable scatter.  k_su_canon also ORs key ^ key[0] over all keys: the host reads those 32 bytes back
+// once and launches passes only for the byte positions on which the keys differ at all — 2 of 32 for a 16-bit counting table, none
+// when all keys are equal, and no round trip per pass.  The chosen bytes are packed into one 64-bit word per key that moves with
+// its index, so a pass reads and writes 12 coalesced bytes per key.  With more than eight differing bytes (theta-compressed tables:
+// uniform keys) the sort runs on the top 2 log2(count) + 16 bits of them, rounded up to bytes — enough to order uniform keys but
+// for a chance of about 2^-15 (the top byte of a 254-bit value carries six bits) — and k_su_heads counts neighbours the prefix left unresolved; that count comes back with n_unique, and only if it
+// is not zero the keys are sorted again on every differing byte, by gathering passes.  Then run heads -> scan -> distinct values
+// and multiplicities.
+constexpr uint32_t RS_ITEMS = 4, RS_TILE = 256 * RS_ITEMS;
+__device__ __forceinline__ uint32_t rs_digit(const uint32_t* canon, uint32_t i, uint32_t byte) {
+  return (canon[8 * (size_t)i + (byte >> 2)] >> ((byte & 3u) * 8u)) & 0xffu;
+}
+__global__ void __launch_bounds__(256) k_su_canon(const fe* in, uint32_t count, fe* canon, uint32_t* idx, uint32_t* diff /* 8 */) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (i < count) {
+    const fe v = fe_from_mont<Fr>(fe_load(&in[i])), first = fe_from_mont<Fr>(fe_load(&in[0]));
+    fe_store(&canon[i], v);
+    idx[i] = i;
+#pragma unroll
+    for (int w = 0; w < 8; w++) d[w] = v.v[w] ^ first.v[w];
+  }
+#pragma unroll
+  for (int w = 0; w < 8; w++) {
+#pragma unroll
+    for (int o = 32; o; o >>= 1) d[w] |= (uint32_t)__shfl_xor((int)d[w], o);
+  }
+  // same-address atomics retire at ~90 M/s (see k_lk_rank): a wavefront adds only bits the mask does not show yet — it saturates
+  // after a few wavefronts, and a stale read costs one redundant atomic, never a missing bit
+  if ((threadIdx.x & 63u) == 0) {
+#pragma unroll
+    for (int w = 0; w < 8; w++)
+      if (d[w] & ~((volatile uint32_t*)diff)[w]) atomicOr(&diff[w], d[w]);
+  }
+}
+// A pass reads its digit from the 32-byte key through the index (PACKED = false: exact for any input), or from a 64-bit word that
+// holds up to eight chosen key bytes and travels with the index (PACKED = true: coalesced 12 bytes per key instead of a gather).
+struct RsBytes {
+  uint8_t pos[8];
+};
+__global__ void __launch_bounds__(256) k_rs_pack(const uint32_t* canon, uint32_t count, RsBytes bytes, uint32_t nb, uint64_t* packed) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  uint64_t v = 0;
+  for (uint32_t j = 0; j < nb; j++) v |= (uint64_t)rs_digit(canon, i, bytes.pos[j]) << (8 * j);
+  packed[i] = v;
+}
+template <bool PACKED>
+__global__ void __launch_bounds__(256) k_rs_hist(const uint32_t* canon, const uint64_t* packed, const uint32_t* idx, uint32_t count, uint32_t byte,
+                                                 uint32_t ntiles, uint32_t* hist) {
+  __shared__ uint32_t h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t base = blockIdx.x * RS_TILE;
+  for (uint32_t r = 0; r < RS_ITEMS; r++) {
+    const uint32_t j = base + r * 256 + threadIdx.x;
+    if (j < count) atomicAdd(&h[PACKED ? (uint32_t)(packed[j] >> (8 * byte)) & 0xffu : rs_digit(canon, idx[j], byte)], 1u);
+  }
+  __syncthreads();
+  hist[threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
+}
+// stable: a tile is taken in RS_ITEMS rounds of 256 consecutive positions; within a round a key's place among the equal digits is
+// (equal digits in earlier wavefronts) + (equal digits in lower lanes of its own: eight ballots match the digit)
+template <bool PACKED>
+__global__ void __launch_bounds__(256) k_rs_scatter(const uint32_t* canon, const uint64_t* packed, uint64_t* packed_out, const uint32_t* src, uint32_t* dst,
+                                                    uint32_t count, uint32_t byte, uint32_t ntiles, const uint32_t* offs) {
+  __shared__ uint32_t base[256], wcnt[4][256];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  base[tid] = offs[tid * ntiles + blockIdx.x];
+#pragma unroll
+  for (int w = 0; w < 4; w++) wcnt[w][tid] = 0;
+  __syncthreads();
+  for (uint32_t r = 0; r < RS_ITEMS; r++) {
+    const uint32_t j = blockIdx.x * RS_TILE + r * 256 + tid;
+    const bool active = j < count;
+    const uint32_t id = active ? src[j] : 0u;
+    const uint64_t pk = PACKED && active ? packed[j] : 0ull;
+    const uint32_t d = !active ? 0u : PACKED ? (uint32_t)(pk >> (8 * byte)) & 0xffu : rs_digit(canon, id, byte);
+    unsigned long long peers = __ballot(active);
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+      const bool bit = (d >> b) & 1u;
+      const unsigned long long bal = __ballot(bit);
+      peers &= bit ? bal : ~bal;
+    }
+    const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+    if (active && rank == 0) wcnt[wave][d] = (uint32_t)__popcll(peers);
+    __syncthreads();
+    if (active) {
+      uint32_t pos = base[d] + rank;
+      for (uint32_t w = 0; w < wave; w++) pos += wcnt[w][d];
+      if (pos < count) {  // always true (the offsets are a scan of this pass's histogram)
+        dst[pos] = id;
+        if (PACKED) packed_out[pos] = pk;
+      }
+    }
+    __syncthreads();
+    base[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
+#pragma unroll
+    for (int w = 0; w < 4; w++) wcnt[w][tid] = 0;
+    __syncthreads();
+  }
+}
+__global__ void __launch_bounds__(256) k_su_iota(uint32_t* idx, uint32_t count) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) idx[i] = i;
+}
+// packed != NULL: the keys were sorted on a prefix of their differing bytes; two neighbours with equal prefixes and different keys
+// are a tie the prefix did not resolve (counted: the caller then sorts again on every byte)
+__global__ void __launch_bounds__(256) k_su_heads(const fe* canon, const uint32_t* idx, const uint64_t* packed, uint32_t count, uint32_t* head, uint32_t* ties) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  const bool differ = j == 0 || cmp256(fe_load(&canon[idx[j]]), fe_load(&canon[idx[j - 1]])) != 0;
+  head[j] = differ ? 1u : 0u;
+  if (packed && j && differ && packed[j] == packed[j - 1]) atomicAdd(ties, 1u);
+}
+__global__ void __launch_bounds__(256) k_su_emit(const fe* canon, const fe* in, const uint32_t* idx, const uint32_t* head, const uint32_t* rank, uint32_t count,
+                                                 fe* out_canon, fe* out_mont, uint32_t* start) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count || !head[j]) return;
+  const uint32_t r = rank[j], i = idx[j];  // r < count: at most one head per position
+  fe_store(&out_canon[r], fe_load(&canon[i]));
+  fe_store(&out_mont[r], fe_load(&in[i]));
+  start[r] = j;
+}
+__global__ void __launch_bounds__(256) k_su_mult(const uint32_t* start, const uint32_t* total, uint32_t count, uint32_t* mult) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x, n_unique = *total;
+  if (r >= n_unique || r >= count) return;
+  mult[r] = (r + 1 < n_unique ? start[r + 1] : count) - start[r];
+}
+
 static uint32_t* g_lk_scratch = nullptr;
 static size_t g_lk_words = 0;
 static hipEvent_t g_lk_event = nullptr;     // last use of the scratch: a caller on another stream queues behind it
@@ -145,6 +281,22 @@ static int scan_u32(const uint32_t* in, uint32_t* out, uint32_t m /* multiple of
   const uint32_t nseg = ceil_div_u32(m, SCAN_SEG_BINS);
   if (nseg > 1) H2_LAUNCH("k_scan_segsum", k_scan_segsum<SCAN_SEG_BINS>, nseg, 1024, 0, s, in, m, segsum);
   H2_LAUNCH("k_scan_seg_lookup", k_scan_seg<SCAN_SEG_BINS>, dim3(nseg, 1), 1024, 0, s, in, out, (const uint32_t*)nullptr, (uint32_t*)nullptr, m, (const uint32_t*)segsum);
+  return H2MI_OK;
+}
+
+// the scratch grows behind a device synchronisation (a launch of an earlier call may still read it)
+static int lk_scratch_reserve(size_t words) {
+  if (g_lk_words >= words) return H2MI_OK;
+  if (g_lk_scratch) {
+    H2_HIP(hipDeviceSynchronize());
+    H2_HIP(hipFree(g_lk_scratch));
+    g_lk_scratch = nullptr;
+    g_lk_words = 0;
+  }
+  hipError_t e = hipMalloc((void**)&g_lk_scratch, words * 4);
+  if (e == hipErrorOutOfMemory) return H2MI_ENOMEM;
+  H2_HIP(e);
+  g_lk_words = words;
   return H2MI_OK;
 }
 
@@ -185,17 +337,9 @@ int h2mi_plonk_lookup_permute_dev(const void* d_input, const void* d_table_sorte
   const uint32_t nseg = ceil_div_u32(std::max(mu, uu), SCAN_SEG_BINS) + 1;
   // scratch (words): cnt[mu+4] start[mu+4] left[mu+4] lstart[mu+4] rep[uu+4] rep_before[uu+4] segsum[nseg] missing[4]
   const size_t words = 4 * ((size_t)mu + 4) + 2 * ((size_t)uu + 4) + nseg + 4;
-  if (g_lk_words < words) {
-    if (g_lk_scratch) {
-      H2_HIP(hipDeviceSynchronize());
-      H2_HIP(hipFree(g_lk_scratch));
-      g_lk_scratch = nullptr;
-      g_lk_words = 0;
-    }
-    hipError_t e = hipMalloc((void**)&g_lk_scratch, words * 4);
-    if (e == hipErrorOutOfMemory) return H2MI_ENOMEM;
-    H2_HIP(e);
-    g_lk_words = words;
+  {
+    int rcs = lk_scratch_reserve(words);
+    if (rcs) return rcs;
   }
   uint32_t* cnt = g_lk_scratch;
   uint32_t* start = cnt + mu + 4;
@@ -230,6 +374,108 @@ int h2mi_plonk_lookup_permute_dev(const void* d_input, const void* d_table_sorte
   H2_HIP(hipMemcpyAsync(&m, missing, 4, hipMemcpyDeviceToHost, s));
   H2_HIP(hipStreamSynchronize(s));
   *not_in_table_out = m;
+  return H2MI_OK;
+}
+
+int h2mi_fr_sort_unique_dev(const void* d_in, uint32_t count, void* d_sorted_canonical, void* d_sorted_mont, void* d_mult, uint32_t* n_unique_out,
+                            h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_in || !d_sorted_canonical || !d_sorted_mont || !d_mult || !n_unique_out) return H2MI_EINVAL;
+  if (count == 0 || count > (1u << H2MI_MAX_LOG_N)) return H2MI_ERANGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  {
+    int rc0 = use_device(0);
+    if (rc0) return rc0;
+  }
+  hipStream_t s = pick_stream(stream);
+  const uint32_t c4 = (count + 3u) & ~3u, ntiles = ceil_div_u32(count, RS_TILE), hm = 256 * ntiles;  // hm: a multiple of 4
+  const uint32_t nseg = ceil_div_u32(std::max(hm, c4), SCAN_SEG_BINS) + 1, nseg4 = (nseg + 3u) & ~3u;
+  // scratch (words; every part starts on a multiple of 4): canon[8 count] packed0[2 c4] packed1[2 c4] idx0[c4] idx1[c4] hist[hm+4]
+  // offs[hm+4] head[c4+4] rank[c4+4] start[c4+4] segsum[nseg4] diff[8]
+  const size_t words = 8 * (size_t)count + 6 * (size_t)c4 + 2 * ((size_t)hm + 4) + 3 * ((size_t)c4 + 4) + nseg4 + 8;
+  {
+    int rcs = lk_scratch_reserve(words);
+    if (rcs) return rcs;
+  }
+  uint32_t* canon_w = g_lk_scratch;
+  uint64_t* packed[2] = {(uint64_t*)(canon_w + 8 * (size_t)count), (uint64_t*)(canon_w + 8 * (size_t)count + 2 * (size_t)c4)};
+  uint32_t* idx[2] = {canon_w + 8 * (size_t)count + 4 * (size_t)c4, canon_w + 8 * (size_t)count + 5 * (size_t)c4};
+  uint32_t* hist = idx[1] + c4;
+  uint32_t* offs = hist + hm + 4;
+  uint32_t* head = offs + hm + 4;
+  uint32_t* rank = head + c4 + 4;  // rank[c4]: n_unique (the scan's total); rank[c4 + 1]: ties the prefix sort left
+  uint32_t* start = rank + c4 + 4;
+  uint32_t* segsum = start + c4 + 4;
+  uint32_t* diff = segsum + nseg4;
+  fe* canon = (fe*)canon_w;
+  const fe* in = (const fe*)d_in;
+  const size_t tail_words = 3 * ((size_t)c4 + 4) + nseg4 + 8;
+  if (g_lk_event && g_lk_stream != s) H2_HIP(hipStreamWaitEvent(s, g_lk_event, 0));
+  H2_HIP(hipMemsetAsync(head, 0, tail_words * 4, s));  // the scans' pads, the tie count, the difference mask
+  const uint32_t grid = ceil_div_u32(count, 256);
+  H2_LAUNCH("k_su_canon", k_su_canon, grid, 256, 0, s, in, count, canon, idx[0], diff);
+  uint32_t mask[8];
+  H2_HIP(hipMemcpyAsync(mask, diff, 32, hipMemcpyDeviceToHost, s));
+  H2_HIP(hipStreamSynchronize(s));
+  std::vector<uint32_t> differing;  // byte positions on which the keys differ at all, ascending: elsewhere a pass is the identity
+  for (uint32_t byte = 0; byte < 32; byte++)
+    if ((mask[byte >> 2] >> ((byte & 3u) * 8u)) & 0xffu) differing.push_back(byte);
+  uint32_t log_count = 0;
+  while (((uint64_t)1 << log_count) < count) log_count++;
+  const uint32_t prefix = std::min<uint32_t>(8, (2 * log_count + 16 + 7) / 8);  // bytes of a prefix sort
+  const bool exact = differing.size() <= 8;                                      // every differing byte fits the packed word
+  const uint32_t nb = exact ? (uint32_t)differing.size() : prefix;
+  int cur = 0;
+  if (nb) {
+    RsBytes bytes;
+    memset(&bytes, 0, sizeof(bytes));
+    for (uint32_t j = 0; j < nb; j++) bytes.pos[j] = (uint8_t)differing[differing.size() - nb + j];  // the top nb of them, ascending
+    H2_LAUNCH("k_rs_pack", k_rs_pack, grid, 256, 0, s, (const uint32_t*)canon_w, count, bytes, nb, packed[0]);
+    for (uint32_t j = 0; j < nb; j++) {
+      H2_LAUNCH("k_rs_hist", k_rs_hist<true>, ntiles, 256, 0, s, (const uint32_t*)canon_w, (const uint64_t*)packed[cur], (const uint32_t*)idx[cur], count, j,
+                ntiles, hist);
+      int rc = scan_u32(hist, offs, hm, segsum, s);
+      if (rc) return rc;
+      H2_LAUNCH("k_rs_scatter", k_rs_scatter<true>, ntiles, 256, 0, s, (const uint32_t*)canon_w, (const uint64_t*)packed[cur], packed[cur ^ 1],
+                (const uint32_t*)idx[cur], idx[cur ^ 1], count, j, ntiles, (const uint32_t*)offs);
+      cur ^= 1;
+    }
+  }
+  uint32_t result[2] = {0, 0};  // n_unique, unresolved ties
+  auto finish = [&](const uint64_t* pk) -> int {
+    H2_LAUNCH("k_su_heads", k_su_heads, grid, 256, 0, s, (const fe*)canon, (const uint32_t*)idx[cur], pk, count, head, rank + c4 + 1);
+    int rc = scan_u32(head, rank, c4, segsum, s);
+    if (rc) return rc;
+    H2_LAUNCH("k_su_emit", k_su_emit, grid, 256, 0, s, (const fe*)canon, in, (const uint32_t*)idx[cur], (const uint32_t*)head, (const uint32_t*)rank, count,
+              (fe*)d_sorted_canonical, (fe*)d_sorted_mont, start);
+    H2_LAUNCH("k_su_mult", k_su_mult, grid, 256, 0, s, (const uint32_t*)start, (const uint32_t*)(rank + c4), count, (uint32_t*)d_mult);
+    H2_HIP(hipMemcpyAsync(result, rank + c4, 8, hipMemcpyDeviceToHost, s));
+    H2_HIP(hipStreamSynchronize(s));
+    return H2MI_OK;
+  };
+  int rc = finish(exact || !nb ? nullptr : (const uint64_t*)packed[cur]);
+  if (rc) return rc;
+  if (result[1]) {  // keys that agree on the whole prefix: sort again on every differing byte
+    H2_HIP(hipMemsetAsync(head, 0, (tail_words - 8) * 4, s));
+    cur = 0;
+    H2_LAUNCH("k_su_iota", k_su_iota, grid, 256, 0, s, idx[0], count);
+    for (uint32_t byte : differing) {
+      H2_LAUNCH("k_rs_hist", k_rs_hist<false>, ntiles, 256, 0, s, (const uint32_t*)canon_w, (const uint64_t*)nullptr, (const uint32_t*)idx[cur], count, byte,
+                ntiles, hist);
+      rc = scan_u32(hist, offs, hm, segsum, s);
+      if (rc) return rc;
+      H2_LAUNCH("k_rs_scatter", k_rs_scatter<false>, ntiles, 256, 0, s, (const uint32_t*)canon_w, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                (const uint32_t*)idx[cur], idx[cur ^ 1], count, byte, ntiles, (const uint32_t*)offs);
+      cur ^= 1;
+    }
+    rc = finish(nullptr);
+    if (rc) return rc;
+  }
+  if (!g_lk_event) H2_HIP(hipEventCreateWithFlags(&g_lk_event, hipEventDisableTiming));
+  H2_HIP(hipEventRecord(g_lk_event, s));
+  g_lk_stream = s;
+  const uint32_t total = result[0];
+  *n_unique_out = total;
   return H2MI_OK;
 }
 

@@ -558,14 +558,11 @@ __global__ void __launch_bounds__(256) k_evaluate_h_flex(FlexCosets c, uint32_t 
 // EX_RED where its static bound on a value would otherwise pass what the next operation takes (see expr_encode).
 enum : uint32_t { EX_COL = 0, EX_CONST, EX_ADD, EX_SUB, EX_MUL, EX_NEG, EX_RED, EX_END };
 constexpr uint32_t EX_COLS = H2MI_EXPR_MAX_ADVICE + H2MI_EXPR_MAX_FIXED + 1;  // advice, fixed, the instance column
-__global__ void __launch_bounds__(256) k_evaluate_h_expr(FlexCosets c, const fe* const* __restrict__ cols, const fe* __restrict__ consts,
-                                                          const uint2* __restrict__ ops, uint32_t n_ops, uint32_t ext_k, uint32_t k, uint32_t last_rot,
-                                                          FlexConsts h, const fe* xlo, const fe* xhi, uint32_t xh, fe* out) {
+// The interpreter loop, shared by the quotient kernel and the lookup compression: `sink(value)` receives each polynomial at its END.
+template <class Sink>
+__device__ __forceinline__ void expr_interpret(const fe* const* __restrict__ cols, const fe* __restrict__ consts, const uint2* __restrict__ ops,
+                                               uint32_t n_ops, uint32_t idx, uint32_t size, uint32_t* ex_stack, Sink&& sink) {
   using namespace gen;
-  extern __shared__ uint32_t ex_stack[];  // [level][limb][thread]
-  const uint32_t size = 1u << ext_k;
-  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= size) return;  // no barrier below: a thread touches its own stack slots only
   uint32_t* const slot = ex_stack + threadIdx.x;
   auto spill = [&](const f29& v, uint32_t level) {
 #pragma unroll
@@ -577,8 +574,7 @@ __global__ void __launch_bounds__(256) k_evaluate_h_expr(FlexCosets c, const fe*
     for (int i = 0; i < 9; i++) v.v[i] = slot[(level * 9 + i) * 256];
     return v;
   };
-  const f29 y = cst(h.y);
-  f29 acc = f29_zero(), tos = f29_zero();
+  f29 tos = f29_zero();
   uint32_t sp = 0;  // values on the stack: tos and LDS levels 0 .. sp - 2
   for (uint32_t pc = 0; pc < n_ops; pc++) {
     const uint2 op = ops[pc];
@@ -599,11 +595,41 @@ __global__ void __launch_bounds__(256) k_evaluate_h_expr(FlexCosets c, const fe*
     } else if (code == EX_RED) {
       tos = red(tos);
     } else {  // EX_END: the one value left is this polynomial
-      horner(acc, y, tos);
+      sink(tos);
       sp = 0;
     }
   }
+}
+__global__ void __launch_bounds__(256) k_evaluate_h_expr(FlexCosets c, const fe* const* __restrict__ cols, const fe* __restrict__ consts,
+                                                          const uint2* __restrict__ ops, uint32_t n_ops, uint32_t ext_k, uint32_t k, uint32_t last_rot,
+                                                          FlexConsts h, const fe* xlo, const fe* xhi, uint32_t xh, fe* out) {
+  using namespace gen;
+  extern __shared__ uint32_t ex_stack[];  // [level][limb][thread]
+  const uint32_t size = 1u << ext_k;
+  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= size) return;  // no barrier below: a thread touches its own stack slots only
+  const f29 y = cst(h.y);
+  f29 acc = f29_zero();
+  expr_interpret(cols, consts, ops, n_ops, idx, size, ex_stack, [&](const f29& poly) { horner(acc, y, poly); });
   evaluate_h_tail(c, ext_k, k, last_rot, h, xlo, xhi, xh, idx, acc, y, out);
+}
+// The lookup argument's theta compression (plonk/lookup/prover.rs commit_permuted `compress_expressions`, plonk/evaluation.rs for
+// the extended coset [RECALL]): out[i] = sum_j e_j(i) theta^(m-1-j), the fold acc theta + e_j over the program's m polynomials, on
+// the 2^dom_k points of the Lagrange rows (dom_k = k) or of the extended coset.  The same interpreter; the sink at END is Horner's
+// rule in theta instead of y, and the value is stored in the memory format (fully reduced Montgomery-2^256).
+__global__ void __launch_bounds__(256) k_expr_compress(const fe* const* __restrict__ cols, const fe* __restrict__ consts, const uint2* __restrict__ ops,
+                                                        uint32_t n_ops, uint32_t dom_k, fe theta, fe* out) {
+  using namespace gen;
+  extern __shared__ uint32_t ex_stack[];
+  const uint32_t size = 1u << dom_k;
+  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= size) return;
+  const f29 th = cst(theta);
+  f29 acc = f29_zero();
+  expr_interpret(cols, consts, ops, n_ops, idx, size, ex_stack, [&](const f29& poly) { horner(acc, th, poly); });
+  fe o;
+  f29_to_mont256<F9>(acc, o.v);
+  fe_store(&out[idx], o);
 }
 
 // the one inversion on the critical path, by division steps on the 32-bit-limb layer (fe_inv_ds; round 4: the shift / subtract
@@ -765,6 +791,40 @@ static void expr_encode(const h2mi_gate_program* g, uint32_t k, uint32_t extende
     }
   }
 }
+
+// What an interpreting launch reads, validated (expr_walk: a malformed program, a NULL column, a constant beyond n_constants or a
+// rotation of 2^k or more is H2MI_EINVAL) and laid out as ONE buffer: the column-pointer table, the constants as Montgomery-2^261
+// words, the ops (each part a whole number of 32-byte words).  dom_k: the domain the columns are given on (k or extended_k).
+struct ExprImage {
+  std::vector<fe> image;
+  size_t cols_fe = 0, const_fe = 0, lds = 0;
+  uint32_t n_ops = 0;
+  int build(const h2mi_gate_program* g, const void* const* advice, const void* const* fixed, const void* instance, uint32_t k, uint32_t dom_k) {
+    ExprShape shape;
+    const int rc = expr_walk(g, k, [&](uint32_t kind, uint32_t index, int32_t) {
+      return kind == H2MI_EXPR_ADVICE ? index < H2MI_EXPR_MAX_ADVICE && advice[index]
+           : kind == H2MI_EXPR_FIXED  ? index < H2MI_EXPR_MAX_FIXED && fixed[index]
+                                      : index == 0 && instance;
+    }, &shape);
+    if (rc) return rc;
+    std::vector<uint2> ops;
+    expr_encode(g, k, dom_k, ops);
+    cols_fe = (EX_COLS * sizeof(void*) + 31) / 32;
+    const_fe = std::max<size_t>(g->n_constants, 1);
+    const size_t ops_fe = (ops.size() * 8 + 31) / 32;
+    image.resize(cols_fe + const_fe + ops_fe);
+    memset(image.data(), 0, image.size() * sizeof(fe));
+    const void** tab = (const void**)image.data();
+    for (uint32_t i = 0; i < H2MI_EXPR_MAX_ADVICE; i++) tab[i] = advice[i];
+    for (uint32_t i = 0; i < H2MI_EXPR_MAX_FIXED; i++) tab[H2MI_EXPR_MAX_ADVICE + i] = fixed[i];
+    tab[EX_COLS - 1] = instance;
+    for (uint32_t i = 0; i < g->n_constants; i++) image[cols_fe + i] = h_canon(f29_from_mont256<F9>(host_fe(g->constants + 4 * i).v));
+    memcpy(&image[cols_fe + const_fe], ops.data(), ops.size() * 8);
+    n_ops = (uint32_t)ops.size();
+    lds = (size_t)(shape.max_stack - 1) * 9 * 256 * sizeof(uint32_t);  // at most 7 levels: 63 KB
+    return H2MI_OK;
+  }
+};
 
 }  // namespace h2
 
@@ -1095,52 +1155,60 @@ int h2mi_plonk_evaluate_h_expr_dev(const h2mi_expr_cosets* c, const h2mi_gate_pr
   if (!c || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
   if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
   if (c->n_perm > H2MI_FLEX_MAX_PERM || c->n_lookups > H2MI_FLEX_MAX_LOOKUPS || (c->n_perm && c->chunk_len == 0)) return H2MI_EINVAL;
-  ExprShape shape;
-  int rc = expr_walk(gates, k, [&](uint32_t kind, uint32_t index, int32_t) {
-    return kind == H2MI_EXPR_ADVICE ? index < H2MI_EXPR_MAX_ADVICE && c->advice[index]
-         : kind == H2MI_EXPR_FIXED  ? index < H2MI_EXPR_MAX_FIXED && c->fixed[index]
-                                    : index == 0 && c->instance;
-  }, &shape);
+  ExprImage im;
+  int rc = im.build(gates, c->advice, c->fixed, c->instance, k, extended_k);
   if (rc) return rc;
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
   FlexCosets fc;
   memset(&fc, 0, sizeof(fc));
   if (!fill_tail(fc, *c)) return H2MI_EINVAL;
-  std::vector<uint2> ops;
-  expr_encode(gates, k, extended_k, ops);
-  // one buffer: the column-pointer table, the constants as Montgomery-2^261 words, the ops (each part a whole number of 32-byte words)
-  const size_t cols_fe = (EX_COLS * sizeof(void*) + 31) / 32, const_fe = std::max<size_t>(gates->n_constants, 1), ops_fe = (ops.size() * 8 + 31) / 32;
-  std::vector<fe> image(cols_fe + const_fe + ops_fe);
-  memset(image.data(), 0, image.size() * sizeof(fe));
-  {
-    const void** tab = (const void**)image.data();
-    for (uint32_t i = 0; i < H2MI_EXPR_MAX_ADVICE; i++) tab[i] = c->advice[i];
-    for (uint32_t i = 0; i < H2MI_EXPR_MAX_FIXED; i++) tab[H2MI_EXPR_MAX_ADVICE + i] = c->fixed[i];
-    tab[EX_COLS - 1] = c->instance;
-    for (uint32_t i = 0; i < gates->n_constants; i++) image[cols_fe + i] = h_canon(f29_from_mont256<F9>(host_fe(gates->constants + 4 * i).v));
-    memcpy(&image[cols_fe + const_fe], ops.data(), ops.size() * 8);
-  }
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
   PowTab px;
   rc = get_powtab(extended_omega, extended_k, s, &px);
   if (rc) return rc;
-  rc = ensure_tmp(image.size(), s);
+  rc = ensure_tmp(im.image.size(), s);
   if (rc) return rc;
   fe* d_image = tmp_base();
   // pageable source: the copy has left `image` when the call returns
-  H2_HIP(hipMemcpyAsync(d_image, image.data(), image.size() * sizeof(fe), hipMemcpyHostToDevice, s));
+  H2_HIP(hipMemcpyAsync(d_image, im.image.data(), im.image.size() * sizeof(fe), hipMemcpyHostToDevice, s));
   const uint32_t rot = 1u << (extended_k - k);
   FlexConsts hc_;
   memset(&hc_, 0, sizeof(hc_));
   hc_.beta = host_fe(beta); hc_.gamma = host_fe(gamma); hc_.y = host_fe(y); hc_.delta = host_fe(delta); hc_.zeta = host_fe(zeta);
   for (uint32_t i = 0; i < rot; i++) hc_.tinv[i] = host_fe(t_inv + 4 * i);
   const uint32_t size = 1u << extended_k;
-  const size_t lds = (size_t)(shape.max_stack - 1) * 9 * 256 * sizeof(uint32_t);  // at most 7 levels: 63 KB
-  H2_LAUNCH("k_evaluate_h_expr", k_evaluate_h_expr, ceil_div_u32(size, 256), 256, lds, s, fc, (const fe* const*)d_image, (const fe*)(d_image + cols_fe),
-            (const uint2*)(d_image + cols_fe + const_fe), (uint32_t)ops.size(), extended_k, k, blinding_factors + 1, hc_, (const fe*)px.lo,
+  H2_LAUNCH("k_evaluate_h_expr", k_evaluate_h_expr, ceil_div_u32(size, 256), 256, im.lds, s, fc, (const fe* const*)d_image, (const fe*)(d_image + im.cols_fe),
+            (const uint2*)(d_image + im.cols_fe + im.const_fe), im.n_ops, extended_k, k, blinding_factors + 1, hc_, (const fe*)px.lo,
             (const fe*)px.hi, px.h, (fe*)d_h_out);
+  return release_tmp(s);
+}
+
+int h2mi_plonk_expr_compress_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
+                                 const h2mi_gate_program* exprs, uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out,
+                                 h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!exprs || !theta || !d_out || (n_advice && !d_advice) || (n_fixed && !d_fixed) || n_advice > H2MI_EXPR_MAX_ADVICE || n_fixed > H2MI_EXPR_MAX_FIXED)
+    return H2MI_EINVAL;
+  if (k == 0 || domain_k < k || domain_k - k > 4 || domain_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  const void* adv[H2MI_EXPR_MAX_ADVICE] = {nullptr};
+  const void* fix[H2MI_EXPR_MAX_FIXED] = {nullptr};
+  for (uint32_t i = 0; i < n_advice; i++) adv[i] = d_advice[i];
+  for (uint32_t i = 0; i < n_fixed; i++) fix[i] = d_fixed[i];
+  ExprImage im;
+  int rc = im.build(exprs, adv, fix, d_instance, k, domain_k);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  CallScope scope_;
+  hipStream_t s = pick_stream(stream);
+  rc = ensure_tmp(im.image.size(), s);
+  if (rc) return rc;
+  fe* d_image = tmp_base();
+  H2_HIP(hipMemcpyAsync(d_image, im.image.data(), im.image.size() * sizeof(fe), hipMemcpyHostToDevice, s));
+  const uint32_t size = 1u << domain_k;
+  H2_LAUNCH("k_expr_compress", k_expr_compress, ceil_div_u32(size, 256), 256, im.lds, s, (const fe* const*)d_image, (const fe*)(d_image + im.cols_fe),
+            (const uint2*)(d_image + im.cols_fe + im.const_fe), im.n_ops, domain_k, host_fe(theta), (fe*)d_out);
   return release_tmp(s);
 }
 

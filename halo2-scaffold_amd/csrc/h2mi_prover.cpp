@@ -142,7 +142,47 @@ int check_program(const h2mi_constraint_system& cs, const h2mi_gate_program* gat
   return H2MI_OK;
 }
 
-void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates) {
+// the rules of h2mi_lookup_program_check (include/h2mi_prover.h).  slices: per lookup the sub-programs of its input and its table
+// polynomials (they point into lp->exprs.ops and share its constants).
+struct LookupSlices {
+  h2mi_gate_program input[H2MI_MAX_LOOKUPS], table[H2MI_MAX_LOOKUPS];
+};
+int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_program* lp, uint32_t* degree_out, LookupSlices* slices) {
+  if (!lp || lp->n_lookups == 0 || lp->n_lookups > H2MI_MAX_LOOKUPS || lp->n_lookups != cs.n_lookups) return H2MI_EINVAL;
+  h2::ExprShape all;
+  {
+    h2mi_constraint_system any = cs;  // the structural rules and the query lists; the degree rule is per lookup, below
+    any.degree = 0xffffffffu;
+    const int rc = check_program(any, &lp->exprs, &all);
+    if (rc) return rc;
+  }
+  uint32_t want = 0;
+  for (uint32_t l = 0; l < lp->n_lookups; l++) {
+    if (lp->n_pairs[l] == 0 || lp->n_pairs[l] > H2MI_MAX_EXPR_OPS) return H2MI_EINVAL;
+    want += 2 * lp->n_pairs[l];
+  }
+  if (all.n_polys != want) return H2MI_EINVAL;
+  uint32_t pos = 0, degree = 0;
+  auto take = [&](uint32_t polys, h2mi_gate_program* out) {  // the next `polys` polynomials -> their largest degree
+    const uint32_t first = pos;
+    for (uint32_t seen = 0; seen < polys; pos++) seen += lp->exprs.ops[pos].op == H2MI_EXPR_END;
+    const h2mi_gate_program sub = {lp->exprs.ops + first, pos - first, lp->exprs.constants, lp->exprs.n_constants};
+    h2::ExprShape sh;
+    h2::expr_walk(&sub, cs.k, [](uint32_t, uint32_t, int32_t) { return true; }, &sh);  // validated above
+    if (out) *out = sub;
+    return std::max(sh.degree, 1u);
+  };
+  for (uint32_t l = 0; l < lp->n_lookups; l++) {
+    const uint32_t in = take(lp->n_pairs[l], slices ? &slices->input[l] : nullptr), tab = take(lp->n_pairs[l], slices ? &slices->table[l] : nullptr);
+    const uint32_t d = std::max(4u, 2 + in + tab);  // [RECALL plonk/lookup.rs Argument::required_degree]
+    if (d > cs.degree) return H2MI_EINVAL;
+    degree = std::max(degree, d);
+  }
+  if (degree_out) *degree_out = degree;
+  return H2MI_OK;
+}
+
+void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups) {
   auto bad = [](const char* what) { throw Error(H2MI_EINVAL, std::string("constraint system: ") + what); };
   if (cs.k == 0 || cs.k > H2MI_MAX_LOG_N) throw Error(H2MI_ERANGE, "constraint system: k");
   if (cs.degree < 3 || cs.degree > 9) bad("degree");
@@ -175,7 +215,11 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates) 
         if (cs.gate_advice[g] >= cs.n_advice || cs.gate_selector[g] >= cs.n_fixed) bad("gate columns");
       if (cs.n_perm && cs.degree - 2 > 3) bad("permutation chunks longer than three columns");
     }
-    for (uint32_t l = 0; l < cs.n_lookups; l++) {
+    if (lookups) {  // the lookups as a program: cs.lookups[] is not read
+      if (cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_exprs takes H2MI_GATES_EXPRESSIONS");
+      if (check_lookup_program(cs, lookups, nullptr, nullptr)) bad("lookup program");
+    }
+    for (uint32_t l = 0; !lookups && l < cs.n_lookups; l++) {
       const h2mi_lookup& lk = cs.lookups[l];
       if (lk.input.kind != H2MI_COL_ADVICE || lk.input.index >= cs.n_advice || lk.table_fixed >= cs.n_fixed) bad("lookup columns");
       if (lk.selector_fixed >= (int32_t)cs.n_fixed || lk.selector_fixed < -1) bad("lookup selector");
@@ -186,7 +230,7 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates) 
   uint32_t ext_k = cs.k;
   while (((uint64_t)1 << ext_k) < ((uint64_t)1 << cs.k) * (cs.degree - 1)) ext_k++;
   if (ext_k - cs.k > 4 || ext_k > H2MI_MAX_LOG_N) throw Error(H2MI_ERANGE, "constraint system: extended domain");
-  if (gates && cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_gates takes H2MI_GATES_EXPRESSIONS");
+  if ((gates || lookups) && cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_gates / _exprs take H2MI_GATES_EXPRESSIONS");
 }
 
 struct Table {  // a lookup table's distinct usable values in ascending canonical order, for the device's counting sort
@@ -213,6 +257,11 @@ struct h2mi_pk_s {
   std::vector<h2mi_expr_op> gate_ops;
   std::vector<uint64_t> gate_constants;
   h2mi_gate_program gate_program = {nullptr, 0, nullptr, 0};
+  // lookups given as a program (h2mi_prover_keygen_exprs): the key's own copy, cut into each lookup's input and table polynomials
+  bool lookup_exprs = false;
+  std::vector<h2mi_expr_op> lookup_ops;
+  std::vector<uint64_t> lookup_constants;
+  LookupSlices lookup_slices;
   explicit h2mi_pk_s(const h2mi_constraint_system& c)
       : cs(c), domain(c.degree, c.k), n((size_t)1 << c.k), ext(domain.extended_len()), u((uint32_t)n - (c.blinding_factors + 1)),
         chunk(c.degree - 2), n_sets(c.n_perm ? (c.n_perm + c.degree - 3) / (c.degree - 2) : 0), delta(fr_delta()) {}
@@ -271,15 +320,23 @@ void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells) {
   check(h2mi_memcpy_h2d(t.mult->p, mult.data(), mult.size() * 4), "table");
 }
 
-std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, uint64_t g_lagrange, const h2mi_column_cells* fixed,
-                                  const uint32_t* copies, size_t n_copies, unsigned flags) {
-  validate(cs, gates);
+std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, uint64_t g_lagrange,
+                                  const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags) {
+  validate(cs, gates, lookups);
   std::unique_ptr<h2mi_pk_s> pkp(new h2mi_pk_s(cs));
   h2mi_pk_s& pk = *pkp;
   if (gates) {
     pk.gate_ops.assign(gates->ops, gates->ops + gates->n_ops);
     if (gates->n_constants) pk.gate_constants.assign(gates->constants, gates->constants + 4 * (size_t)gates->n_constants);
     pk.gate_program = {pk.gate_ops.data(), gates->n_ops, pk.gate_constants.data(), gates->n_constants};
+  }
+  if (lookups) {
+    pk.lookup_exprs = true;
+    pk.lookup_ops.assign(lookups->exprs.ops, lookups->exprs.ops + lookups->exprs.n_ops);
+    if (lookups->exprs.n_constants) pk.lookup_constants.assign(lookups->exprs.constants, lookups->exprs.constants + 4 * (size_t)lookups->exprs.n_constants);
+    h2mi_lookup_program own = *lookups;
+    own.exprs = {pk.lookup_ops.data(), lookups->exprs.n_ops, pk.lookup_constants.data(), lookups->exprs.n_constants};
+    if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices)) throw Error(H2MI_EINVAL, "lookup program");
   }
   pk.vk_only = (flags & H2MI_KEYGEN_VK_ONLY) != 0;
   const poly::EvaluationDomain& dom = pk.domain;
@@ -363,7 +420,8 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     to_poly_and_coset(dom, *la, *tmp, *pk.l_active);
     check(h2mi_sync(), "sync");
   }
-  for (uint32_t l = 0; l < cs.n_lookups; l++) build_table(pk, pk.tables[l], fixed[cs.lookups[l].table_fixed]);
+  // a lookup given as expressions has no keygen-time table: theta, or an advice column in it, is known only inside a proof
+  for (uint32_t l = 0; !pk.lookup_exprs && l < cs.n_lookups; l++) build_table(pk, pk.tables[l], fixed[cs.lookups[l].table_fixed]);
   return pkp;
 }
 
@@ -500,7 +558,12 @@ struct h2mi_prover_s {
   struct Lk {
     Dev input;  // selector * column rows (single-column form); otherwise the advice column itself is the input
     Forms a, s, z;
+    // lookups given as expressions: `input` and `table` are the compressed expressions on the rows, in_coset / tab_coset the same
+    // on the extended coset, and the table's distinct values are sorted inside the proof
+    Dev table, in_coset, tab_coset;
+    Table sorted;
   } lk[H2MI_MAX_LOOKUPS];
+  Fr theta;
   Dev random_poly, h, h_poly, points, evals;
   // SHPLONK: three lanes (the library stream and two side streams), each with its own scratch
   Dev nx[3], tmp[3], h_x, l_x, h2_x;
@@ -528,8 +591,20 @@ struct h2mi_prover_s {
       if (st) h2mi_stream_destroy(st);
   }
   const DeviceVec& lookup_input(uint32_t l) const {
+    if (pk->lookup_exprs) return *lk[l].input;
     const h2mi_lookup& d = pk->cs.lookups[l];
     return d.selector_fixed >= 0 ? *lk[l].input : *advice[d.input.index].value;
+  }
+  const DeviceVec& lookup_table(uint32_t l) const { return pk->lookup_exprs ? *lk[l].table : *pk->fixed_values[pk->cs.lookups[l].table_fixed]; }
+  // one side of lookup l compressed with theta, on the rows (coset = false) or on the extended coset
+  void compress(const h2mi_gate_program& prog, bool coset, DeviceVec& out) const {
+    const h2mi_constraint_system& cs = pk->cs;
+    const void *adv[H2MI_MAX_ADVICE], *fix[H2MI_MAX_FIXED];
+    for (uint32_t j = 0; j < cs.n_advice; j++) adv[j] = coset ? advice[j].coset->p : advice[j].value->p;
+    for (uint32_t j = 0; j < cs.n_fixed; j++) fix[j] = coset ? pk->fixed_cosets[j]->p : pk->fixed_values[j]->p;
+    const void* inst = cs.n_instance ? (coset ? instance_coset->p : instance->p) : nullptr;
+    check(h2mi_plonk_expr_compress_dev(adv, cs.n_advice, fix, cs.n_fixed, inst, &prog, cs.k, coset ? pk->domain.extended_k() : cs.k, theta.l, out.p, nullptr),
+          "expr_compress");
   }
   void* out_slot(size_t slot) const { return (char*)(d_partial ? d_partial : points->p) + 96 * slot; }
   const void* col(const DeviceVec& d, size_t offset_elems = 0) const { return (const char*)d.p + (offset_elems + lo) * 32; }
@@ -605,7 +680,18 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
     p.instance_coset = vec(ext);
   }
   for (uint32_t l = 0; l < cs.n_lookups; l++) {
-    if (cs.lookups[l].selector_fixed >= 0) p.lk[l].input = vec(n);
+    if (pk->lookup_exprs) {
+      Dev* rows[2] = {&p.lk[l].input, &p.lk[l].table};
+      for (Dev* d : rows) *d = vec(n);
+      p.lk[l].in_coset = vec(ext);
+      p.lk[l].tab_coset = vec(ext);
+      Table& t = p.lk[l].sorted;
+      t.sorted = vec(pk->u);
+      t.sorted_mont = vec(pk->u);
+      t.mult = vec(pk->u / 8 + 1);
+    } else if (cs.lookups[l].selector_fixed >= 0) {
+      p.lk[l].input = vec(n);
+    }
     p.lk[l].a.alloc(n, ext);
     p.lk[l].s.alloc(n, ext);
     p.lk[l].z.alloc(n, ext);
@@ -689,7 +775,7 @@ void phase_advice(h2mi_prover_s& p, const h2mi_column_cells* advice, const uint6
 }
 
 // ---- phase 2: lookups' permuted columns (plonk/lookup/prover.rs commit_permuted) -----------------------------------------------
-void phase_lookups(h2mi_prover_s& p, uint64_t* points_out) {
+void phase_lookups(h2mi_prover_s& p, const uint64_t* theta, uint64_t* points_out) {
   const h2mi_pk_s& pk = *p.pk;
   const h2mi_constraint_system& cs = pk.cs;
   const size_t n = pk.n;
@@ -700,13 +786,24 @@ void phase_lookups(h2mi_prover_s& p, uint64_t* points_out) {
     const std::vector<Fr> lb = p.blinding(4, (size_t)2 * (bf + 1) * L);
     PatchList pl;
     std::vector<const void*> cols;
+    if (pk.lookup_exprs) {
+      if (!theta) throw Error(H2MI_EINVAL, "theta");
+      std::memcpy(p.theta.l, theta, 32);
+    }
     for (uint32_t l = 0; l < L; l++) {
       const h2mi_lookup& d = cs.lookups[l];
-      if (d.selector_fixed >= 0)  // the input expression's rows: q_lookup * a, zero wherever the selector is off
+      if (pk.lookup_exprs) {
+        // both sides compressed on all 2^k rows; the table's usable rows sorted here, inside the proof
+        p.compress(pk.lookup_slices.input[l], false, *p.lk[l].input);
+        p.compress(pk.lookup_slices.table[l], false, *p.lk[l].table);
+        Table& ts = p.lk[l].sorted;
+        check(h2mi_fr_sort_unique_dev(p.lk[l].table->p, u, ts.sorted->p, ts.sorted_mont->p, ts.mult->p, &ts.n_unique, nullptr), "sort_unique");
+      } else if (d.selector_fixed >= 0) {  // the input expression's rows: q_lookup * a, zero wherever the selector is off
         check(h2mi_fr_mul_dev(pk.fixed_values[d.selector_fixed]->p, p.advice[d.input.index].value->p, n, p.lk[l].input->p, nullptr), "lookup input");
+      }
       DeviceVec &a_perm = *p.lk[l].a.value, &s_perm = *p.lk[l].s.value;
       uint64_t missing = 0;
-      const Table& t = pk.tables[l];
+      const Table& t = pk.lookup_exprs ? p.lk[l].sorted : pk.tables[l];
       check(h2mi_plonk_lookup_permute_dev(p.lookup_input(l).p, t.sorted->p, t.sorted_mont->p, t.mult->p, t.n_unique, cs.k, u, a_perm.p, s_perm.p,
                                           &missing, nullptr),
             "lookup_permute");
@@ -796,7 +893,7 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
       const std::vector<Fr> lzb = p.blinding(5, (size_t)bf * L);
       for (uint32_t l = 0; l < L; l++) {
         DeviceVec& lz = *p.lk[l].z.value;
-        check(h2mi_plonk_lookup_product_dev(p.lookup_input(l).p, pk.fixed_values[cs.lookups[l].table_fixed]->p, p.lk[l].a.value->p, p.lk[l].s.value->p, cs.k,
+        check(h2mi_plonk_lookup_product_dev(p.lookup_input(l).p, p.lookup_table(l).p, p.lk[l].a.value->p, p.lk[l].s.value->p, cs.k,
                                             u, beta.l, gamma.l, lz.p, nullptr),
               "lookup_product");
         PatchList pl;
@@ -863,9 +960,18 @@ void phase_quotient(h2mi_prover_s& p, const Fr& y, uint64_t* points_out) {
     ec.n_lookups = L;
     for (uint32_t l = 0; l < L; l++) {
       const h2mi_lookup& lk = cs.lookups[l];
-      ec.lookup_input[l] = p.advice[lk.input.index].coset->p;
-      ec.lookup_input_b[l] = lk.selector_fixed >= 0 ? pk.fixed_cosets[lk.selector_fixed]->p : nullptr;
-      ec.lookup_table[l] = pk.fixed_cosets[lk.table_fixed]->p;
+      if (pk.lookup_exprs) {
+        // compressed on the extended coset itself: a product of columns is no polynomial of degree < n, so transforming the
+        // compressed rows would give another function
+        p.compress(pk.lookup_slices.input[l], true, *p.lk[l].in_coset);
+        p.compress(pk.lookup_slices.table[l], true, *p.lk[l].tab_coset);
+        ec.lookup_input[l] = p.lk[l].in_coset->p;
+        ec.lookup_table[l] = p.lk[l].tab_coset->p;
+      } else {
+        ec.lookup_input[l] = p.advice[lk.input.index].coset->p;
+        ec.lookup_input_b[l] = lk.selector_fixed >= 0 ? pk.fixed_cosets[lk.selector_fixed]->p : nullptr;
+        ec.lookup_table[l] = pk.fixed_cosets[lk.table_fixed]->p;
+      }
       ec.lookup_permuted_input[l] = p.lk[l].a.coset->p;
       ec.lookup_permuted_table[l] = p.lk[l].s.coset->p;
       ec.lookup_z[l] = p.lk[l].z.coset->p;
@@ -1244,7 +1350,7 @@ int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_han
   *pk_out = nullptr;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;  // no CPU fallback: the prover exists on a GPU or not at all
   return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
     std::lock_guard<std::mutex> lk(g_reg_mu);
     g_live_pks.insert(pk.get());
     *pk_out = pk.release();
@@ -1267,7 +1373,26 @@ int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_p
   *pk_out = nullptr;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;
   return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, g_lagrange_handle, fixed, copies, n_copies, flags);
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    g_live_pks.insert(pk.get());
+    *pk_out = pk.release();
+  });
+}
+
+int h2mi_lookup_program_check(const h2mi_constraint_system* cs, const h2mi_lookup_program* lookups, uint32_t* degree_out) {
+  if (!cs || !lookups) return H2MI_EINVAL;
+  return check_lookup_program(*cs, lookups, degree_out, nullptr);
+}
+
+int h2mi_prover_keygen_exprs(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, uint64_t g_lagrange_handle,
+                             const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
+  if (!lookups) return h2mi_prover_keygen_gates(cs, gates, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
+  if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)H2MI_KEYGEN_VK_ONLY)) return H2MI_EINVAL;
+  *pk_out = nullptr;
+  if (h2mi_device_count() == 0) return H2MI_ENODEV;
+  return guarded([&] {
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, g_lagrange_handle, fixed, copies, n_copies, flags);
     std::lock_guard<std::mutex> lk(g_reg_mu);
     g_live_pks.insert(pk.get());
     *pk_out = pk.release();
@@ -1363,8 +1488,7 @@ int h2mi_prover_advice(h2mi_prover_t prover, const h2mi_column_cells* advice, co
 }
 int h2mi_prover_lookups(h2mi_prover_t prover, const uint64_t theta[4], uint64_t* points_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
-  (void)theta;  // single-expression lookups have nothing to compress
-  return guarded([&] { phase_lookups(*prover, points_out); });
+  return guarded([&] { phase_lookups(*prover, theta, points_out); });  // theta compresses lookups given as expressions only
 }
 int h2mi_prover_products(h2mi_prover_t prover, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* points_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;

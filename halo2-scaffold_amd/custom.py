@@ -2,7 +2,7 @@
 
 The reference's src/circuits/is_zero.rs and or.rs configure their circuits with `meta.create_gate("...", |meta| vec![...])` over
 `meta.query_advice(column, Rotation)` expressions.  This module is that API — `ConstraintSystem.advice_column / fixed_column /
-instance_column / selector / enable_equality / create_gate`, `Expression` with + - * and `Expression.constant` — so that such a
+instance_column / selector / enable_equality / create_gate / lookup / lookup_any`, `Expression` with + - * and `Expression.constant` — so that such a
 configure() can be transcribed line by line, and the region API of synthesize() (`Assignment.assign_advice / assign_fixed /
 enable_selector / constrain_equal / constrain_instance`).  `ConstraintSystem.program()` compiles the gate polynomials to the postfix
 program of include/h2mi.h (h2mi_gate_program), `abi(k)` gives the constraint system as data with gates = H2MI_GATES_EXPRESSIONS;
@@ -11,12 +11,17 @@ program on the extended coset (csrc/h2mi_plonk.hip k_evaluate_h_expr), everythin
 
 halo2's bookkeeping, restated from memory [RECALL halo2_proofs plonk/circuit.rs]:
   * enable_equality queries its column at Rotation::cur when it is called; query lists are in first-use order;
-  * blinding_factors = max(3, most queries on one advice column) + 2;  degree = max(3, gate degrees) (no lookups here);
+  * blinding_factors = max(3, most queries on one advice column) + 2;  degree = max(3, gate degrees, per lookup
+    max(4, 2 + max(1, input degrees) + max(1, table degrees)));
   * every selector becomes ONE fixed column, appended after the user's fixed columns in selector order and queried last.  The crate's
     compress_selectors, which merges disjoint simple selectors into one column, is NOT modelled: a circuit whose selectors the crate
     would merge gets one column more here than there (and other proof bytes).  The C ABI sees expressions after the substitution
     and does not care.
-Lookups (`meta.lookup`) are not part of this module; the single-expression lookups of the ABI are reached through flex.py.
+Lookups: `meta.lookup(name, |meta| vec![(input, table), ..])` and `lookup_any` take any expressions on both sides (the crate's `lookup`
+wants its table side to be TableColumn queries; here both spell the same argument).  `lookup_program()` compiles them to an
+h2mi_lookup_program and `Keys` hands it to h2mi_prover_keygen_exprs: each side is compressed with theta and the table sorted inside
+every proof (csrc/h2mi_lookup.hip h2mi_fr_sort_unique_dev).  The single-expression lookups against a fixed table, sorted once at
+keygen, stay the fast path of range checks and are reached through flex.py.
 """
 from . import engine, flex
 from . import field as F
@@ -191,6 +196,7 @@ class ConstraintSystem:
         self.perm_columns = []                      # [(kind, column)] in enable_equality order
         self.advice_queries, self._fixed_queries, self.instance_queries = [], [], []
         self.gate_names, self._polys = [], []       # one entry per polynomial, selectors unresolved
+        self.lookup_names, self._lookups = [], []   # per lookup [(input, table)] expressions, selectors unresolved
 
     # ---- columns -----------------------------------------------------------------------------------------------------
     def advice_column(self) -> Column:
@@ -243,6 +249,17 @@ class ConstraintSystem:
             self.gate_names.append(name)
             self._polys.append(Expression._wrap(p))
 
+    def lookup(self, name: str, table_map) -> int:
+        """meta.lookup: table_map(meta) -> [(input Expression, table Expression)]; the queries it makes enter the query lists in
+        first-use order.  -> the lookup's index"""
+        pairs = [(Expression._wrap(a), Expression._wrap(t)) for a, t in table_map(self)]
+        assert pairs, "a lookup needs at least one (input, table) pair"
+        self.lookup_names.append(name)
+        self._lookups.append(pairs)
+        return len(self._lookups) - 1
+
+    lookup_any = lookup  # any expression on the table side: advice columns, rotations
+
     # ---- what keygen and create_proof read off it ------------------------------------------------------------------------
     @property
     def n_fixed(self) -> int:
@@ -264,8 +281,13 @@ class ConstraintSystem:
         """the polynomials as callables g(q), q(kind, column, rotation) -> value: the form oracle.flex.ConstraintSystem takes"""
         return [(lambda q, p=p: p.evaluate(q)) for p in self.polynomials]
 
+    @property
+    def lookups(self):
+        return [[(a.resolve(self.n_user_fixed), t.resolve(self.n_user_fixed)) for a, t in pairs] for pairs in self._lookups]
+
     def degree(self) -> int:
-        return max([3] + [p.degree() for p in self._polys])
+        lookups = [max(4, 2 + max([1] + [a.degree() for a, _ in pairs]) + max([1] + [t.degree() for _, t in pairs])) for pairs in self._lookups]
+        return max([3] + [p.degree() for p in self._polys] + lookups)
 
     def blinding_factors(self) -> int:
         per_column = [sum(1 for c, _ in self.advice_queries if c == j) for j in range(self.n_advice)]
@@ -281,7 +303,22 @@ class ConstraintSystem:
     def gate_program(self) -> engine.GateProgram:
         return engine.GateProgram.build(*self.program())
 
+    def lookup_program(self):
+        """the lookups -> engine.LookupProgram (per lookup its input polynomials, then its table polynomials), None without lookups"""
+        if not self._lookups:
+            return None
+        constants, ops = {}, []
+        for pairs in self.lookups:
+            for e in [a for a, _ in pairs] + [t for _, t in pairs]:
+                ops += e.program(constants)[0]
+        return engine.LookupProgram.build([len(pairs) for pairs in self._lookups], ops, sorted(constants, key=constants.get))
+
     def abi(self, k: int) -> engine.ConstraintSystem:
+        abi = self._abi(k)
+        abi.n_lookups = len(self._lookups)  # described by lookup_program(), not by the struct's single-expression entries
+        return abi
+
+    def _abi(self, k: int) -> engine.ConstraintSystem:
         assert self.n_instance <= 1, "the prover ABI takes one instance column"
         return engine.ConstraintSystem.build(k, self.n_advice, self.n_fixed, self.n_instance, self.degree(), self.blinding_factors(),
                                              engine.GATES_EXPRESSIONS, [], [(_KIND[kind], c) for kind, c in self.perm_columns], [],
@@ -328,7 +365,8 @@ class Assignment:
 
 def mock(asg: Assignment, k: int) -> None:
     """MockProver::run(k, ..).assert_satisfied() on the host: no cell or copy constraint beyond the usable rows, every gate polynomial
-    zero on every usable row (unassigned cells are zero; rotations wrap around 2^k), every copy constraint between equal cells.
+    zero on every usable row (unassigned cells are zero; rotations wrap around 2^k), every copy constraint between equal cells, every
+    lookup's input tuple on a usable row equal to its table tuple on some usable row.
     Raises ValueError naming the first violation."""
     cs = asg.cs
     n = 1 << k
@@ -349,10 +387,16 @@ def mock(asg: Assignment, k: int) -> None:
     for left, right in asg.copies:
         if value[left[0]](left[1], left[2]) % R != value[right[0]](right[1], right[2]) % R:
             raise ValueError(f"copy constraint {left} == {right} not satisfied")
+    for name, pairs in zip(cs.lookup_names, cs.lookups):
+        at = lambda e, row: e.evaluate(lambda kind, c, rot: value[kind](c, (row + rot) % n))
+        table = {tuple(at(t, row) for _, t in pairs) for row in range(u)}
+        for row in range(u):
+            if tuple(at(a, row) for a, _ in pairs) not in table:
+                raise ValueError(f"lookup {name!r} not satisfied at row {row}")
 
 
 class Keys:
-    """keygen_vk + keygen_pk through h2mi_prover_keygen_gates: the fixed cells of a run of synthesize() (selector columns included), the
+    """keygen_vk + keygen_pk through h2mi_prover_keygen_gates (h2mi_prover_keygen_exprs when the circuit has lookups): the fixed cells of a run of synthesize() (selector columns included), the
     copy constraints with their columns renumbered into the permutation argument's order, the gates as a program the key copies.
     Same attributes as flex.FlexKeys."""
 
@@ -363,7 +407,7 @@ class Keys:
         self.u = d.n - (cs.blinding_factors() + 1)
         index = {col: j for j, col in enumerate(cs.perm_columns)}
         copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
-        self.keys = engine.Keys(cs.abi(k), params, list(asg.fixed), copies, gates=cs.gate_program())
+        self.keys = engine.Keys(cs.abi(k), params, list(asg.fixed), copies, gates=cs.gate_program(), lookups=cs.lookup_program())
         self.fixed_commitments, self.permutation_commitments = self.keys.fixed_commitments, self.keys.permutation_commitments
         nf, m = cs.n_fixed, len(cs.perm_columns)
         self.fixed_values, self.fixed_polys, self.fixed_cosets = (self.keys.views(kd, nf) for kd in (engine.PKBUF_FIXED, engine.PKBUF_FIXED_POLY, engine.PKBUF_FIXED_COSET))
@@ -382,5 +426,5 @@ Workspace = flex.FlexWorkspace  # one library prover kept from proof to proof: n
 
 def create_proof(params: ParamsKZG, keys: Keys, asg: Assignment, seed: int, transcript=None, trace: dict = None, ws: Workspace = None) -> bytes:
     """create_proof for one circuit: the transcript on this side, seven phase calls into the library (flex.create_proof's body: the
-    phases do not depend on how the gates were given)"""
+    phases do not depend on how the gates were given; theta reaches the lookups phase through engine.Prover.drive)"""
     return flex.create_proof(params, keys, asg, seed, transcript=transcript, trace=trace, ws=ws)

@@ -107,6 +107,30 @@ class GateProgram(C.Structure):
         return degree.value, depth.value
 
 
+class LookupProgram(C.Structure):
+    """h2mi_lookup_program: the lookups of a constraint system as expressions — per lookup its n_pairs input polynomials, then its
+    n_pairs table polynomials, in one postfix program"""
+    _fields_ = [("n_lookups", C.c_uint32), ("n_pairs", C.c_uint32 * MAX_LOOKUPS), ("exprs", GateProgram)]
+
+    @classmethod
+    def build(cls, n_pairs, ops, constants) -> "LookupProgram":
+        """n_pairs: pairs per lookup; ops / constants as GateProgram.build takes them"""
+        assert len(n_pairs) <= MAX_LOOKUPS
+        lp = cls()
+        lp.n_lookups = len(n_pairs)
+        for l, m in enumerate(n_pairs):
+            lp.n_pairs[l] = m
+        lp._exprs = GateProgram.build(ops, constants)  # keeps the arrays alive
+        lp.exprs = lp._exprs
+        return lp
+
+    def check(self, cs: "ConstraintSystem") -> int:
+        """h2mi_lookup_program_check -> the largest required degree; H2miError(-1) for a program keygen would refuse"""
+        degree = C.c_uint32()
+        check(lib.h2mi_lookup_program_check(C.byref(cs), C.byref(self), C.byref(degree)), "lookup_program_check")
+        return degree.value
+
+
 class ColumnCells(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("values", C.c_void_p), ("count", C.c_size_t), ("flags", C.c_uint32)]
 
@@ -182,11 +206,12 @@ class _Views:
 
 
 class Keys:
-    """h2mi_prover_keygen (h2mi_prover_keygen_gates when `gates` is given): keygen_vk + keygen_pk for a constraint system given as data.  fixed: one {row: value} dict (or dense
+    """h2mi_prover_keygen (h2mi_prover_keygen_gates when `gates` is given, h2mi_prover_keygen_exprs when `lookups` is too): keygen_vk + keygen_pk for a constraint system given as data.  fixed: one {row: value} dict (or dense
     list) per fixed column as synthesize() assigns them; copies: [(left column, left row, right column, right row)] per
     constrain_equal in call order, columns as indices into the permutation argument.  `params` is the WHOLE SRS."""
 
-    def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False, gates: GateProgram = None):
+    def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False, gates: GateProgram = None,
+                 lookups: LookupProgram = None):
         self.cs = cs
         cells, keep = pack_cells(fixed)
         cp = np.ascontiguousarray(np.array(copies, dtype=np.uint32).reshape(-1, 4))
@@ -194,6 +219,9 @@ class Keys:
         flags = KEYGEN_VK_ONLY if vk_only else 0
         if gates is None:
             check(lib.h2mi_prover_keygen(C.byref(cs), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
+        elif lookups is not None:  # the lookups as expressions too
+            check(lib.h2mi_prover_keygen_exprs(C.byref(cs), C.byref(gates), C.byref(lookups), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp),
+                                               flags, C.byref(h)), "keygen")
         else:  # GATES_EXPRESSIONS: the gates travel beside the struct; the key copies them
             check(lib.h2mi_prover_keygen_gates(C.byref(cs), C.byref(gates), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)),
                   "keygen")

@@ -277,3 +277,20 @@ def evaluate_h_expr(domain: EvaluationDomain, program, advice, fixed, instance, 
     args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
     _check(lib.h2mi_plonk_evaluate_h_expr_dev(C.byref(cs), C.byref(program), domain.k, domain.extended_k, blinding_factors,
                                               *[x.ctypes.data for x in args], t_inv.ctypes.data, out.ptr, None), "evaluate_h_expr")
+
+
+def expr_compress(program, advice, fixed, instance, k: int, domain_k: int, theta: int, out: DevBuf) -> None:
+    """h2mi_plonk_expr_compress_dev: out[i] = sum_j e_j(i) theta^(m-1-j) over the m polynomials of `program` (an engine.GateProgram) on
+    the 2^domain_k points the columns are given on (lists of DevBuf, None for a column the program does not read)"""
+    ptrs = lambda cols: (C.c_void_p * max(len(cols), 1))(*[c.ptr if c is not None else None for c in cols])
+    _check(lib.h2mi_plonk_expr_compress_dev(ptrs(advice), len(advice), ptrs(fixed), len(fixed), instance.ptr if instance is not None else None,
+                                            C.byref(program), k, domain_k, F.fr_to_mont_limbs(theta).ctypes.data, out.ptr, None), "expr_compress")
+
+
+def sort_unique(values: DevBuf, count: int):
+    """h2mi_fr_sort_unique_dev over the first `count` elements -> (canonical values, Montgomery values, u32 multiplicities, n_unique):
+    the table arguments of h2mi_plonk_lookup_permute_dev"""
+    canon, mont, mult = DevBuf(count * 32), DevBuf(count * 32), DevBuf(count * 4)
+    n_unique = C.c_uint32()
+    _check(lib.h2mi_fr_sort_unique_dev(values.ptr, count, canon.ptr, mont.ptr, mult.ptr, C.byref(n_unique), None), "sort_unique")
+    return canon, mont, mult, n_unique.value

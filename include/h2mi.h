@@ -327,6 +327,15 @@ int h2mi_plonk_permutation_products_sparse_dev(const void* const* d_values, cons
 int h2mi_plonk_lookup_permute_dev(const void* d_input, const void* d_table_sorted_canonical, const void* d_table_sorted_mont,
                                   const void* d_table_mult /* u32 x n_unique */, uint32_t n_unique, uint32_t k, uint32_t usable_rows,
                                   void* d_permuted_input, void* d_permuted_table, uint64_t* not_in_table_out, h2mi_stream_t stream);
+/* The table side of that call for a table that is NOT fixed — compressed with the proof's theta, or holding advice (lookup_any): the
+ * distinct values of d_in[0 .. count) (Montgomery) in ascending canonical-integer order, as the three arrays
+ * h2mi_plonk_lookup_permute_dev takes (canonical values, the same values in Montgomery form, u32 multiplicities; each with room for
+ * `count` entries) and their number.  A radix sort over an index permutation, on the device, for any input (all keys equal, keys
+ * that differ in one word, a 16-bit counting table, uniform keys): digit positions on which every key agrees cost nothing.  The
+ * call synchronises `stream` twice (32 bytes that say where the keys differ, then n_unique), and once more in the rare case that keys
+ * which differ in more than eight bytes were not told apart by the prefix they are sorted on first.  count in [1, 2^H2MI_MAX_LOG_N]. */
+int h2mi_fr_sort_unique_dev(const void* d_in, uint32_t count, void* d_sorted_canonical, void* d_sorted_mont, void* d_mult /* u32 x count */,
+                            uint32_t* n_unique_out, h2mi_stream_t stream);
 /* extended-coset form of an instance column from the proving key's l_0 coset, without transforms: the column holds `count`
  * <= 16 public inputs on rows 0 .. count - 1 (what the scaffold's builders constrain: src/scaffold.rs:411, 480) and zeros
  * elsewhere, so its coset values are sum_r values[r] * l0_coset[(j - r 2^(extended_k - k)) mod 2^extended_k] — the same field
@@ -454,6 +463,16 @@ int h2mi_plonk_evaluate_h_expr_dev(const h2mi_expr_cosets* cosets, const h2mi_ga
                                    uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
                                    const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
                                    const uint64_t* t_inv /* 2^(extended_k-k) x 4 */, void* d_h_out, h2mi_stream_t stream);
+
+/* A lookup's expressions compressed with theta (plonk/lookup/prover.rs compress_expressions): `exprs` holds m polynomials e_0 ..
+ * e_(m-1) and d_out[i] = sum_j e_j(i) theta^(m-1-j) — the fold acc theta + e_j — for the 2^domain_k points the columns are given on:
+ * the Lagrange rows (domain_k = k) or the extended coset (domain_k = extended_k).  A query at rotation r reads point
+ * (i + (r mod 2^k) 2^(domain_k-k)) mod 2^domain_k.  d_advice / d_fixed: n_advice / n_fixed column pointers (a column the program does
+ * not read may be NULL); d_instance: the instance column or NULL.  The same interpreter and the same refusals as
+ * h2mi_plonk_evaluate_h_expr_dev.  d_out must not be one of the columns.  Values are stored fully reduced, Montgomery. */
+int h2mi_plonk_expr_compress_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
+                                 const h2mi_gate_program* exprs, uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out,
+                                 h2mi_stream_t stream);
 
 /* ---- SRS generation helper: ParamsKZG::setup's g[i] = s_i * G   ------------------
  * d_scalars: n Fr (Montgomery).  d_out_affine: n G1Affine.  Fixed-base windowed multiplication of the

@@ -36,7 +36,11 @@
  *                              the gate polynomials as a postfix program beside the struct (h2mi_gate_program, h2mi.h; keygen through
  *                              h2mi_prover_keygen_gates) which ONE kernel interprets on the extended coset — any query of an advice,
  *                              fixed or instance column at any rotation, constants, + - *, degree up to 9 (permutation chunks up to
- *                              7); lookups, permutation and column limits as for FLEX_VERTICAL
+ *                              7); permutation and column limits as for FLEX_VERTICAL.  Its lookups are either the
+ *                              single-expression ones of FLEX_VERTICAL (cs->lookups[], a fixed table sorted once at keygen: the fast
+ *                              path of range checks) or DATA as well — any `meta.lookup` / `meta.lookup_any`: per lookup a list of
+ *                              (input expression, table expression) pairs in the same postfix form (h2mi_lookup_program; keygen
+ *                              through h2mi_prover_keygen_exprs), compressed with theta and sorted inside each proof
  * Every function returns H2MI_OK or a negative H2MI_E* code (h2mi.h); no exception crosses the boundary.  Field elements
  * and points use the layouts of h2mi.h (4 / 8 uint64 limbs, Montgomery form).  A prover object is used by one thread at a time.
  */
@@ -135,6 +139,25 @@ int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_han
 int h2mi_gate_program_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint32_t* degree_out, uint32_t* max_stack_out);
 int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint64_t g_lagrange_handle,
                              const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
+/* Lookups as a program beside the constraint system: `meta.lookup(|meta| vec![(input, table), ..])` with any expressions on both sides,
+ * advice in the table (lookup_any) and rotations included.  The argument compresses each side with the challenge theta, A = theta^(m-1)
+ * a_0 + .. + a_(m-1) and S likewise (on all 2^k rows, rotations modulo 2^k), permutes and multiplies over the usable rows; transcript
+ * order, quotient terms, openings and blinding streams are those of the single-expression lookups.
+ * h2mi_lookup_program_check (host only, works without a GPU): H2MI_EINVAL unless n_lookups == cs->n_lookups (1 .. H2MI_MAX_LOOKUPS), every
+ * n_pairs >= 1, exprs passes the rules of h2mi_gate_program_check except the degree rule (every advice / fixed query in the query
+ * lists), holds exactly 2 * sum n_pairs polynomials, and every lookup's required degree max(4, 2 + max(1, input degrees) + max(1, table
+ * degrees)) is at most cs->degree.  degree_out (may be NULL): the largest required degree.
+ * h2mi_prover_keygen_exprs: h2mi_prover_keygen_gates with the lookups given this way (lookups == NULL: exactly that call).  Requires
+ * cs->gates == H2MI_GATES_EXPRESSIONS; the key copies the program. */
+typedef struct {
+  uint32_t n_lookups;                 /* == cs->n_lookups; cs->lookups[] is then ignored */
+  uint32_t n_pairs[H2MI_MAX_LOOKUPS]; /* >= 1 */
+  h2mi_gate_program exprs;            /* per lookup: its n_pairs input polynomials, then its n_pairs table polynomials */
+} h2mi_lookup_program;
+int h2mi_lookup_program_check(const h2mi_constraint_system* cs, const h2mi_lookup_program* lookups, uint32_t* degree_out);
+int h2mi_prover_keygen_exprs(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
+                             uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags,
+                             h2mi_pk_t* pk_out);
 int h2mi_prover_pk_release(h2mi_pk_t pk); /* H2MI_EINVAL while a prover created against it is alive */
 /* VerifyingKey::{fixed_commitments, permutation.commitments}: affine points (8 limbs each); either pointer may be NULL */
 int h2mi_prover_vk_commitments(h2mi_pk_t pk, uint64_t* fixed_out /* n_fixed x 8 */, uint64_t* permutation_out /* n_perm x 8 */);
@@ -180,9 +203,10 @@ int h2mi_prover_set_rng_key(h2mi_prover_t prover, const uint8_t key[32]);
  * points_out: n_advice commitments. */
 int h2mi_prover_advice(h2mi_prover_t prover, const h2mi_column_cells* advice, const uint64_t* instance, size_t n_instance_values, uint64_t seed,
                        uint64_t* points_out);
-/* theta is accepted for the crate's multi-expression lookups and unused by the single-expression ones.
+/* theta compresses the lookups of a key made by h2mi_prover_keygen_exprs (each side's expressions folded with it on the rows, the
+ * table's usable rows sorted on the device); the single-expression lookups do not use it.
  * points_out: per lookup the permuted input, then the permuted table commitment (2 x n_lookups; nothing without lookups — the call
- * may then be skipped).  H2MI_EUNSAT: a lookup input is not a table value. */
+ * may then be skipped).  H2MI_EUNSAT: a lookup input (a compressed input tuple) is not a table value (a table row). */
 int h2mi_prover_lookups(h2mi_prover_t prover, const uint64_t theta[4], uint64_t* points_out);
 /* points_out: the permutation argument's ceil(n_perm / (degree - 2)) grand products, one product per lookup, then the vanishing
  * argument's random polynomial: the order create_proof commits (and writes) them in. */

@@ -1,0 +1,371 @@
+"""Lookups given as data, on the device: h2mi_fr_sort_unique_dev against sorted() + Counter, h2mi_plonk_expr_compress_dev against
+Python integers on random programs, proofs of circuits with tuple lookups through custom.py (accepted by the helper verifier of
+tests/lookup_expr_cases.py, their device buffers equal to the restatement), the committed range goldens reproduced byte for byte
+with their lookups re-described as one-pair programs, and the refusals."""
+import collections
+import ctypes as C
+import json
+import os
+import random
+import types
+
+import numpy as np
+import pytest
+
+import custom_gate_cases as gate_cases
+import lookup_expr_cases as cases
+from custom_gate_cases import OP_ADVICE, OP_END, OP_FIXED
+from oracle import bn254 as o
+from oracle import flex as FX
+from oracle import lookup as L
+
+pytestmark = pytest.mark.gpu
+
+R = o.R
+SRS_SECRET = 0x5EC2E7 + 0x48324D49
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+KINDS = {0: "advice", 1: "fixed", 2: "instance"}
+
+
+def _vals(buf, count):
+    return o.unpack(buf.to_numpy(shape=(count, 4), nbytes=count * 32), R)
+
+
+def _ints(arr):
+    """(count, 4) uint64 limbs -> Python integers"""
+    raw = np.ascontiguousarray(arr).tobytes()
+    return [int.from_bytes(raw[i : i + 32], "little") for i in range(0, len(raw), 32)]
+
+
+def _limbs(values):
+    return np.frombuffer(b"".join(v.to_bytes(32, "little") for v in values), dtype=np.uint64).reshape(-1, 4)
+
+
+# ---- 1. the sort -------------------------------------------------------------------------------------------------------------------
+COUNTS = [1, 2, 3, 26, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4097, (1 << 16) - 6, (1 << 18) + 5]
+KEY_CLASSES = ["all equal", "counting", "top word", "words 3 and 4", "ends of the field", "uniform", "half zeros"]
+
+
+def _keys(cls, c, rng):
+    if cls == "all equal":
+        return [rng.randrange(R)] * c
+    if cls == "counting":  # 0 .. c - 1 shuffled: the upper words are all zero
+        keys = list(range(c))
+        rng.shuffle(keys)
+        return keys
+    if cls == "top word":  # only the top 32-bit word differs (it stays below the modulus' 0x30644e72)
+        base = rng.randrange(1 << 224)
+        return [base + (rng.randrange(min(c, 0x30000000)) << 224) for _ in range(c)]
+    if cls == "words 3 and 4":  # the two 32-bit words on either side of the boundary between the 64-bit limbs 1 and 2
+        base = rng.randrange(R >> 8) & ~(((1 << 64) - 1) << 96)
+        return [base + (rng.randrange(1 + c // 3) << (96 if rng.random() < 0.5 else 128)) for _ in range(c)]
+    if cls == "ends of the field":
+        return [rng.choice([0, 1, R - 2, R - 1]) for _ in range(c)]
+    if cls == "uniform":
+        return [rng.randrange(R) for _ in range(c)]
+    return [0 if rng.random() < 0.5 else rng.randrange(R) for _ in range(c)]
+
+
+@pytest.mark.parametrize("cls", KEY_CLASSES)
+@pytest.mark.parametrize("count", COUNTS)
+def test_sort_unique_against_sorted_and_counter(gpu, count, cls):
+    from halo2_scaffold_amd import plonk
+    from halo2_scaffold_amd.device import DevBuf
+
+    rng = random.Random(count * 131 + KEY_CLASSES.index(cls))
+    keys = _keys(cls, count, rng)
+    mont = lambda v: (v << 256) % R
+    buf = DevBuf.from_numpy(_limbs([mont(v) for v in keys]))
+    canon, smont, mult, n_unique = plonk.sort_unique(buf, count)
+    tally = collections.Counter(keys)
+    want = sorted(tally)
+    assert n_unique == len(want)
+    assert _ints(canon.to_numpy(shape=(n_unique, 4), nbytes=n_unique * 32)) == want
+    assert _ints(smont.to_numpy(shape=(n_unique, 4), nbytes=n_unique * 32)) == [mont(v) for v in want]
+    assert mult.to_numpy(dtype=np.uint32, nbytes=n_unique * 4).tolist() == [tally[v] for v in want]
+
+
+def test_sort_unique_refusals(gpu):
+    from halo2_scaffold_amd.device import DevBuf
+
+    buf, n = DevBuf(64), C.c_uint32()
+    assert gpu.lib.h2mi_fr_sort_unique_dev(buf.ptr, 0, buf.ptr, buf.ptr, buf.ptr, C.byref(n), None) == -6   # H2MI_ERANGE
+    assert gpu.lib.h2mi_fr_sort_unique_dev(None, 1, buf.ptr, buf.ptr, buf.ptr, C.byref(n), None) == -1      # H2MI_EINVAL
+    assert gpu.lib.h2mi_fr_sort_unique_dev(buf.ptr, 1, buf.ptr, buf.ptr, buf.ptr, None, None) == -1
+
+
+# ---- 2. the compression ------------------------------------------------------------------------------------------------------------
+N_ADV, N_FIX = 3, 2
+DOMAINS = [(5, 5), (5, 7), (7, 9)]  # the Lagrange rows, an extended coset, and more than one workgroup
+N_COMPRESS_CASES = 24
+
+
+def _compress_case(custom, case):
+    """-> (k, domain_k, [trees]): m in {1, 2, 3, 5} polynomials of degree 1 .. 4, rotations -3 .. 3; cases 0 and 1 have the deepest
+    and the shallowest stack"""
+    rng = random.Random(777 + case)
+    rots = list(range(-3, 4))
+    columns = [("advice", j, rots) for j in range(N_ADV)] + [("fixed", j, rots) for j in range(N_FIX)] + [("instance", 0, rots)]
+    k, domain_k = DOMAINS[case % 3]
+    m = [1, 2, 3, 5][(case // 3) % 4]
+    if case == 0:  # m = 1, (5, 5)
+        qs = [custom.Expression("query", *((lambda c: (c[0], c[1], rng.choice(c[2])))(rng.choice(columns)))) for _ in range(8)]
+        e = qs[-1]
+        for x in reversed(qs[:-1]):
+            e = x - e
+        return k, domain_k, [e]
+    if case == 1:  # m = 1, (5, 7): queries, a negation and a constant, one stack slot each
+        return k, domain_k, [-custom.Expression("query", "instance", 0, -3)]
+    if case == 4:  # m = 2: a constant as a whole expression, and idx = 0 with a negative rotation
+        return k, domain_k, [custom.Expression.constant(R - 1), custom.Expression("query", "advice", 0, -3)]
+    want_degree = 1 + case % 4
+    while True:
+        trees = [gate_cases.random_tree(custom, rng, rng.randrange(1, 5), columns, leaf_bias=0.25) for _ in range(m)]
+        if max(t.degree() for t in trees) == want_degree and max(t.stack_depth() for t in trees) <= 8:
+            return k, domain_k, trees
+
+
+@pytest.mark.parametrize("case", range(N_COMPRESS_CASES))
+def test_expr_compress_against_python_integers(gpu, case):
+    from halo2_scaffold_amd import custom, engine, plonk
+    from halo2_scaffold_amd.device import DevBuf
+
+    k, domain_k, trees = _compress_case(custom, case)
+    size, rot = 1 << domain_k, 1 << (domain_k - k)
+    rng = random.Random(5 + case)
+    column = lambda: [rng.choice([0, 1, R - 1]) if rng.random() < 0.3 else rng.randrange(R) for _ in range(size)]
+    data = {("advice", j): column() for j in range(N_ADV)}
+    data.update({("fixed", j): column() for j in range(N_FIX)})
+    data[("instance", 0)] = column()
+    bufs = {key: DevBuf.from_numpy(o.pack(col, R)) for key, col in data.items()}
+    constants, ops = {}, []
+    for t in trees:
+        ops += t.program(constants)[0]
+    consts = sorted(constants, key=constants.get)
+    prog = engine.GateProgram.build(ops, consts)
+    out = DevBuf(size * 32)
+    results = []
+    for theta in (rng.randrange(R), rng.randrange(R)):
+        plonk.expr_compress(prog, [bufs[("advice", j)] for j in range(N_ADV)], [bufs[("fixed", j)] for j in range(N_FIX)], bufs[("instance", 0)], k,
+                            domain_k, theta, out)
+        got = _vals(out, size)
+        want = []
+        for idx in range(size):
+            polys, _ = gate_cases.run_postfix(ops, consts, lambda op, c, r: data[(KINDS[op], c)][(idx + (r % (1 << k)) * rot) % size])
+            want.append(cases.compress(polys, theta))
+        assert got == want
+        results.append(got)
+    assert (results[0] == results[1]) == (len(trees) == 1)  # one expression: nothing to compress, theta does not enter
+
+
+def test_compress_cases_cover_what_they_should(h2):
+    from halo2_scaffold_amd import custom
+
+    ms, degrees, depths, domains, used, rotations = set(), set(), set(), set(), set(), set()
+    for case in range(N_COMPRESS_CASES):
+        k, domain_k, trees = _compress_case(custom, case)
+        ms.add(len(trees))
+        domains.add((k, domain_k))
+        degrees.add(max(t.degree() for t in trees))
+        depths.add(max(t.stack_depth() for t in trees))
+        for t in trees:
+            for op, _, r in t.program()[0]:
+                used.add(op)
+                if op <= 2:
+                    rotations.add(r)
+    assert ms == {1, 2, 3, 5} and domains == set(DOMAINS) and degrees >= {1, 2, 3, 4} and {1, 8} <= depths
+    assert used == set(range(9)) and rotations == set(range(-3, 4)) and N_COMPRESS_CASES >= 20
+
+
+def test_expr_compress_refusals(gpu):
+    from halo2_scaffold_amd import engine
+    from halo2_scaffold_amd.device import DevBuf
+
+    col, out = DevBuf(32 * 32), DevBuf(32 * 32)
+    theta = np.zeros(4, dtype=np.uint64)
+    cols = (C.c_void_p * 1)(col.ptr)
+
+    def call(ops, k=5, domain_k=5, n_adv=1):
+        prog = engine.GateProgram.build(ops, [])
+        return gpu.lib.h2mi_plonk_expr_compress_dev(cols, n_adv, None, 0, None, C.byref(prog), k, domain_k, theta.ctypes.data, out.ptr, None)
+
+    assert call([(OP_ADVICE, 0, 0), (OP_END, 0, 0)]) == 0
+    assert call([(OP_ADVICE, 1, 0), (OP_END, 0, 0)]) == -1     # a column that is not there
+    assert call([(OP_FIXED, 0, 0), (OP_END, 0, 0)]) == -1
+    assert call([(OP_ADVICE, 0, 32), (OP_END, 0, 0)]) == -1    # a rotation of 2^k
+    assert call([(OP_ADVICE, 0, 0)]) == -1                     # no END
+    assert call([(OP_ADVICE, 0, 0), (OP_END, 0, 0)], domain_k=4) == -6 and call([(OP_ADVICE, 0, 0), (OP_END, 0, 0)], domain_k=10) == -6
+
+
+# ---- 3. proofs -----------------------------------------------------------------------------------------------------------------------
+def _prove_and_check(gpu, name, seed):
+    """prove through custom.py; the helper verifier accepts; the compressed columns (through the level-A call on the prover's own
+    buffers), the permuted columns and the product equal the restatement"""
+    from halo2_scaffold_amd import custom, engine, plonk
+    from halo2_scaffold_amd.device import DevBuf
+
+    build, k = cases.CIRCUITS[name]
+    cs, asg = build(custom)
+    custom.mock(asg, k)
+    n, bf = 1 << k, cs.blinding_factors()
+    u = n - (bf + 1)
+    params = gpu.ParamsKZG.setup(k, SRS_SECRET)
+    keys = custom.Keys(params, cs, asg)
+    ws = custom.Workspace(params, keys)
+    trace = {}
+    proof = custom.create_proof(params, keys, asg, seed, trace=trace, ws=ws)
+    ocs = gate_cases.oracle_cs(cs, name)
+    oasg = gate_cases.oracle_assignment(ocs, asg)
+    vk = FX.VerifierKeys(ocs, k, SRS_SECRET, oasg.fixed, oasg.copies)
+    assert o.unpack_points(keys.fixed_commitments) == vk.fixed_commitments and keys.transcript_repr == vk.transcript_repr
+    lookups = cases.expr_lookups(cs)
+    assert cases.verify(vk, proof, oasg.instance, lookups)
+    flipped = bytearray(proof)
+    flipped[cases.first_lookup_evaluation_offset(ocs, len(lookups), cs.degree() - 1) + 64] ^= 1
+    assert not cases.verify(vk, bytes(flipped), oasg.instance, lookups)
+    # the device's intermediates
+    pr = ws.prover
+    adv_views = list(pr.views(engine.BUF_ADVICE, cs.n_advice))
+    fix_views = list(keys.fixed_values)
+    inst_view = pr.view(engine.BUF_INSTANCE) if cs.n_instance else None
+    columns = {"advice": [_vals(v, n) for v in adv_views], "fixed": [_vals(v, n) for v in fix_views],
+               "instance": [list(asg.instance) + [0] * (n - len(asg.instance))]}
+    for c, cells in enumerate(asg.advice):  # the witness where it was assigned, blinding scalars beyond the usable rows
+        assert all(columns["advice"][c][r] == v for r, v in cells.items())
+    value = lambda kind, c, row: columns[kind][c][row]
+    theta, beta, gamma = trace["theta"], trace["beta"], trace["gamma"]
+    nl = len(cs.lookups)
+    lb, lzb = FX._rand(2 * (bf + 1) * nl, seed + 4), FX._rand(bf * nl, seed + 5)
+    out = DevBuf(n * 32)
+    for l, pairs in enumerate(cs.lookups):
+        sides = []
+        for exprs in ([a for a, _ in pairs], [t for _, t in pairs]):
+            want = cases.compress_rows(exprs, value, n, theta)
+            constants, ops = {}, []
+            for e in exprs:
+                ops += e.program(constants)[0]
+            prog = engine.GateProgram.build(ops, sorted(constants, key=constants.get))
+            plonk.expr_compress(prog, adv_views, fix_views, inst_view, k, k, theta, out)
+            assert _vals(out, n) == want
+            sides.append(want)
+        a_col, s_col = sides
+        o0 = 2 * (bf + 1) * l
+        ap, sp = L.permute_expression_pair(a_col, s_col, u, lb[o0 : o0 + bf + 1], lb[o0 + bf + 1 : o0 + 2 * bf + 2])
+        assert _vals(pr.views(engine.BUF_LOOKUP_PERMUTED_INPUT, nl)[l], n) == ap
+        assert _vals(pr.views(engine.BUF_LOOKUP_PERMUTED_TABLE, nl)[l], n) == sp
+        z = L.lookup_product(a_col, s_col, ap, sp, beta, gamma, u, lzb[bf * l : bf * (l + 1)])
+        assert _vals(pr.views(engine.BUF_LOOKUP_Z, nl)[l], n) == z
+    return params, keys, ws, vk, oasg, lookups, cs
+
+
+def _release(params, keys, ws):
+    ws.release()
+    keys.release()
+    params.release()
+
+
+def test_xor_table_proof(gpu):
+    """(a) the 2-bit XOR table: three pairs, inputs of degree 2; then the two unsatisfied witnesses: H2MI_EUNSAT"""
+    from halo2_scaffold_amd import custom
+
+    params, keys, ws, vk, oasg, lookups, cs = _prove_and_check(gpu, "xor", 21)
+    assert cs.degree() == 5 and ws.prover.counts.lookups == 2 and ws.prover.counts.quotient == 4
+    for bad in sorted(cases.XOR_BAD):
+        _, broken = cases.xor_circuit(custom, bad=bad)
+        with pytest.raises(ValueError, match="ConstraintSystemFailure"):
+            custom.create_proof(params, keys, broken, 21, ws=ws)
+    _, good = cases.xor_circuit(custom)
+    assert cases.verify(vk, custom.create_proof(params, keys, good, 22, ws=ws), oasg.instance, lookups)  # the prover recovers
+    _release(params, keys, ws)
+
+
+def test_lookup_any_with_advice_table_and_rotations(gpu):
+    """(b) advice in the table, b(w^-1 X) and y(w X): rotations on the rows wrap around 2^k, on the coset by 2^(extended_k - k)"""
+    params, keys, ws, vk, oasg, lookups, cs = _prove_and_check(gpu, "any", 5)
+    assert cs.degree() == 6 and keys.domain.extended_k == 5 + 3
+    _release(params, keys, ws)
+
+
+def test_two_lookups_gate_and_instance(gpu):
+    """(c) a one-pair and a two-pair lookup, degree 6 from the lookup argument alone, a gate on an instance query, k = 6"""
+    params, keys, ws, vk, oasg, lookups, cs = _prove_and_check(gpu, "two", 77)
+    c = ws.prover.counts
+    assert cs.degree() == 6 and max(p.degree() for p in cs.polynomials) == 2 and (c.lookups, c.quotient) == (4, 5)
+    other = [[(oasg.instance[0][0] + 1) % R] + oasg.instance[0][1:]]
+    from halo2_scaffold_amd import custom
+
+    _, asg = cases.two_lookups_circuit(custom)
+    proof = custom.create_proof(params, keys, asg, 78, ws=ws)
+    assert cases.verify(vk, proof, oasg.instance, lookups) and not cases.verify(vk, proof, other, lookups)
+    _release(params, keys, ws)
+
+
+# ---- 4. the range goldens through one-pair programs ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,k", [("flex_proofs.json", 7), ("flex_multi_proofs.json", 5), ("flex_multi_proofs.json", 6)])
+def test_range_goldens_through_one_pair_programs(gpu, name, k):
+    """q_lookup * a in the table (k = 7) and a lookup-advice column in the table (k = 5, 6): compressed (m = 1), sorted on the device
+    and permuted, the proofs come out byte for byte as through the keygen-time table"""
+    from halo2_scaffold_amd import engine, flex, keygen
+
+    g = json.load(open(os.path.join(GOLD, name)))
+    case = next(c for c in g["cases"] if c["shape"] == "range" and c["k"] == k)
+    cs, asg, abi = cases.golden_product_case(flex, engine, case)
+    params = gpu.ParamsKZG.setup(k, int(g["srs_secret"], 16))
+    gates = engine.GateProgram.build(gate_cases.vertical_gate_ops(list(enumerate(cs.col_qs))), [])
+    lp = engine.LookupProgram.build(*cases.one_pair_ops(abi), [])
+    assert lp.check(abi) == cs.degree
+    fixed_cells = list(asg.fixed)
+    fixed_cells[cs.col_table] = [v % R for v in asg.table_values]
+    index = {col: j for j, col in enumerate(cs.perm_columns)}
+    copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
+    keys = engine.Keys(abi, params, fixed_cells, copies, gates=gates, lookups=lp)
+    del gates, lp  # the key holds its own copies
+    vk_bytes, repr_ = keygen.transcript_repr(k, cs.degree, keys.fixed_commitments, keys.permutation_commitments)
+    assert vk_bytes.hex() == case["vk_bytes"]
+    pk = types.SimpleNamespace(keys=keys, transcript_repr=repr_)
+    proof = flex.create_proof(params, pk, types.SimpleNamespace(advice=asg.advice, instance=asg.instance), case["seed"])
+    assert proof.hex() == case["proof"]
+    keys.release()
+    params.release()
+
+
+# ---- 5. refusals -----------------------------------------------------------------------------------------------------------------------
+def test_keygen_exprs_refusals(gpu):
+    from halo2_scaffold_amd import custom, engine, flex
+
+    lib = gpu.lib
+    params = gpu.ParamsKZG.setup(5, SRS_SECRET)
+    cs, asg = cases.xor_circuit(custom)
+    abi, gates, lp = cs.abi(5), cs.gate_program(), cs.lookup_program()
+    cells, keep = engine.pack_cells(asg.fixed)
+    copies = np.array([[0, 0, 0, 5]], dtype=np.uint32)
+
+    def keygen_exprs(abi_, gates_, lp_):
+        pk = C.c_void_p(0xDEAD)
+        rc = lib.h2mi_prover_keygen_exprs(C.byref(abi_), C.byref(gates_), C.byref(lp_) if lp_ is not None else None, params.g_lagrange_handle, cells,
+                                          copies.ctypes.data, 1, 0, C.byref(pk))
+        return rc, pk.value
+
+    rc, handle = keygen_exprs(abi, gates, lp)
+    assert rc == 0 and handle and lib.h2mi_prover_pk_release(handle) == 0
+    short = engine.LookupProgram.build([2], [(OP_ADVICE, 0, 0), (OP_END, 0, 0), (OP_FIXED, 0, 0), (OP_END, 0, 0)], [])  # 2 pairs, 2 polynomials
+    assert keygen_exprs(abi, gates, short) == (-1, None)
+    low = cs.abi(5)
+    low.degree = 4
+    assert keygen_exprs(low, gates, lp) == (-1, None)
+    vertical = flex.FlexGateCS(lookup=True).abi(5)  # gates == H2MI_GATES_FLEX_VERTICAL
+    one = engine.LookupProgram.build(*cases.one_pair_ops(vertical), [])
+    assert keygen_exprs(vertical, gates, one) == (-1, None)
+    # lookups == NULL is h2mi_prover_keygen_gates, which reads cs->lookups[]: a constraint system without lookups goes through,
+    # and the older entry points behave as before
+    plain, pasg = gate_cases.is_zero_circuit(custom, 3)
+    pcells, pkeep = engine.pack_cells(pasg.fixed)
+    pcopies = np.array([[1, 0, 0, 1]], dtype=np.uint32)
+    for fn, args in ((lib.h2mi_prover_keygen_exprs, (C.byref(plain.gate_program()), None)), (lib.h2mi_prover_keygen_gates, (C.byref(plain.gate_program()),))):
+        pk = C.c_void_p()
+        assert fn(C.byref(plain.abi(5)), *args, params.g_lagrange_handle, pcells, pcopies.ctypes.data, 1, 0, C.byref(pk)) == 0
+        assert lib.h2mi_prover_pk_release(pk.value) == 0
+    pk = C.c_void_p(0xDEAD)
+    assert lib.h2mi_prover_keygen(C.byref(plain.abi(5)), params.g_lagrange_handle, pcells, pcopies.ctypes.data, 1, 0, C.byref(pk)) == -1 and pk.value is None
+    del keep, pkeep
+    params.release()
