@@ -101,6 +101,8 @@ def _load():
         "h2mi_plonk_evaluate_h_flex_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_expr_dev": ([vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_expr_compress_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
+        "h2mi_plonk_evaluate_h_expr_ch_dev": ([vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "h2mi_plonk_expr_compress_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_fr_sort_unique_dev": ([vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), vp], C.c_int),
         "h2mi_g1_fixed_base_mul_dev": ([vp, sz, vp, vp], C.c_int),
         "h2mi_fr_powers_dev": ([vp, sz, vp, vp], C.c_int),
@@ -116,6 +118,8 @@ def _load():
         "h2mi_prover_keygen_gates": ([vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_lookup_program_check": ([vp, vp, C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_prover_keygen_exprs": ([vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
+        "h2mi_advice_phases_check": ([vp, vp, vp, vp], C.c_int),
+        "h2mi_prover_keygen_phases": ([vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_prover_pk_release": ([vp], C.c_int),
         "h2mi_prover_vk_commitments": ([vp, vp, vp], C.c_int),
         "h2mi_prover_create": ([vp, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(vp)], C.c_int),
@@ -124,6 +128,9 @@ def _load():
         "h2mi_prover_set_rng_key": ([vp, vp], C.c_int),
         "h2mi_prover_get_counts": ([vp, vp], C.c_int),
         "h2mi_prover_advice": ([vp, vp, vp, sz, C.c_uint64, vp], C.c_int),
+        "h2mi_prover_advice_phase": ([vp, C.c_uint32, vp, vp, sz, C.c_uint64, vp], C.c_int),
+        "h2mi_prover_set_challenges": ([vp, vp], C.c_int),
+        "h2mi_prover_get_phase_counts": ([vp, vp], C.c_int),
         "h2mi_prover_lookups": ([vp, vp, vp], C.c_int),
         "h2mi_prover_products": ([vp, vp, vp, vp], C.c_int),
         "h2mi_prover_quotient": ([vp, vp, vp], C.c_int),

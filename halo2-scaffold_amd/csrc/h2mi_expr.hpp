@@ -15,10 +15,13 @@ struct ExprShape {
 };
 
 // Structural rules of a program: known ops, constant indices, |rotation| < 2^k, stack discipline, END placement.  `column(kind, index,
-// rotation)` decides whether a query is allowed (column counts, query lists, non-NULL pointers: the caller's business).
+// rotation)` decides whether a query is allowed (column counts, query lists, non-NULL pointers: the caller's business).  n_challenges:
+// how many challenges the caller knows of — a CHALLENGE op with an index at or beyond it is refused (0: every CHALLENGE op); the
+// operand has degree 0 [RECALL halo2_proofs v2023_02_02 plonk/circuit.rs Expression::degree].
 template <class ColumnOk>
-inline int expr_walk(const h2mi_gate_program* g, uint32_t k, ColumnOk&& column, ExprShape* out) {
-  if (!g || !g->ops || g->n_ops == 0 || g->n_ops > H2MI_MAX_EXPR_OPS || g->n_constants > H2MI_MAX_EXPR_CONSTANTS) return H2MI_EINVAL;
+inline int expr_walk(const h2mi_gate_program* g, uint32_t k, uint32_t n_challenges, ColumnOk&& column, ExprShape* out) {
+  if (!g || !g->ops || g->n_ops == 0 || g->n_ops > H2MI_MAX_EXPR_OPS || g->n_constants > H2MI_MAX_EXPR_CONSTANTS || n_challenges > H2MI_MAX_CHALLENGES)
+    return H2MI_EINVAL;
   if (g->n_constants && !g->constants) return H2MI_EINVAL;
   const int64_t n = (int64_t)1 << k;
   uint32_t deg[H2MI_MAX_EXPR_STACK];
@@ -36,6 +39,10 @@ inline int expr_walk(const h2mi_gate_program* g, uint32_t k, ColumnOk&& column, 
         break;
       case H2MI_EXPR_CONSTANT:
         if (o.index >= g->n_constants || sp == H2MI_MAX_EXPR_STACK) return H2MI_EINVAL;
+        deg[sp++] = 0;
+        break;
+      case H2MI_EXPR_CHALLENGE:
+        if (o.index >= n_challenges || sp == H2MI_MAX_EXPR_STACK) return H2MI_EINVAL;
         deg[sp++] = 0;
         break;
       case H2MI_EXPR_ADD:

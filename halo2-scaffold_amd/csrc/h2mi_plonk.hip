@@ -553,7 +553,11 @@ __global__ void __launch_bounds__(256) k_evaluate_h_flex(FlexCosets c, uint32_t 
 //   * the operand stack keeps its top in registers and the rest in LDS as [level][limb][thread] (a wavefront's 64 lanes read 64
 //     consecutive words: no bank conflict), max_stack - 1 levels of 9 KB, sized per launch — never a runtime-indexed private array;
 //   * the column-pointer table, the constants (already Montgomery-2^261 words) and the ops live in ONE device buffer: the launch carries
-//     three addresses into it, not 129 pointers.
+//     three addresses into it, not 129 pointers;
+//   * a challenge (H2MI_EXPR_CHALLENGE: a value the transcript yields between two advice phases) is a constant of the LAUNCH rather than
+//     of the program: the uploader lays the challenge values out behind the program's constants, in the same words, and encodes the
+//     operand as EX_CONST with index n_constants + challenge — the same wave-uniform load, no dispatch case of its own, and the device
+//     code of a program without challenges is what it was.
 // Ops as uploaded: word x = code | index << 8, word y = the row offset of the rotation, (r mod n) 2^(ext_k - k).  The uploader inserts
 // EX_RED where its static bound on a value would otherwise pass what the next operation takes (see expr_encode).
 enum : uint32_t { EX_COL = 0, EX_CONST, EX_ADD, EX_SUB, EX_MUL, EX_NEG, EX_RED, EX_END };
@@ -783,6 +787,7 @@ static void expr_encode(const h2mi_gate_program* g, uint32_t k, uint32_t extende
         break;
       }
       case H2MI_EXPR_CONSTANT: emit(EX_CONST, o.index); b[sp++] = 1.0; break;
+      case H2MI_EXPR_CHALLENGE: emit(EX_CONST, g->n_constants + o.index); b[sp++] = 1.0; break;  // canonical like a constant: the same bound
       case H2MI_EXPR_ADD: emit(EX_ADD); b[sp - 2] += b[sp - 1]; sp--; cap(); break;
       case H2MI_EXPR_SUB: small_top(); emit(EX_SUB); b[sp - 2] += 4.0; sp--; cap(); break;
       case H2MI_EXPR_MUL: emit(EX_MUL); b[sp - 2] = 1.0 + 0.006 * b[sp - 2] * b[sp - 1]; sp--; break;
@@ -793,15 +798,18 @@ static void expr_encode(const h2mi_gate_program* g, uint32_t k, uint32_t extende
 }
 
 // What an interpreting launch reads, validated (expr_walk: a malformed program, a NULL column, a constant beyond n_constants or a
-// rotation of 2^k or more is H2MI_EINVAL) and laid out as ONE buffer: the column-pointer table, the constants as Montgomery-2^261
-// words, the ops (each part a whole number of 32-byte words).  dom_k: the domain the columns are given on (k or extended_k).
+// rotation of 2^k or more is H2MI_EINVAL) and laid out as ONE buffer: the column-pointer table, the constants and behind them the
+// challenges as Montgomery-2^261 words, the ops (each part a whole number of 32-byte words).  dom_k: the domain the columns are given
+// on (k or extended_k).
 struct ExprImage {
   std::vector<fe> image;
   size_t cols_fe = 0, const_fe = 0, lds = 0;
   uint32_t n_ops = 0;
-  int build(const h2mi_gate_program* g, const void* const* advice, const void* const* fixed, const void* instance, uint32_t k, uint32_t dom_k) {
+  int build(const h2mi_gate_program* g, const uint64_t* challenges, uint32_t n_challenges, const void* const* advice, const void* const* fixed,
+            const void* instance, uint32_t k, uint32_t dom_k) {
+    if (n_challenges > H2MI_MAX_CHALLENGES || (n_challenges && !challenges)) return H2MI_EINVAL;
     ExprShape shape;
-    const int rc = expr_walk(g, k, [&](uint32_t kind, uint32_t index, int32_t) {
+    const int rc = expr_walk(g, k, n_challenges, [&](uint32_t kind, uint32_t index, int32_t) {
       return kind == H2MI_EXPR_ADVICE ? index < H2MI_EXPR_MAX_ADVICE && advice[index]
            : kind == H2MI_EXPR_FIXED  ? index < H2MI_EXPR_MAX_FIXED && fixed[index]
                                       : index == 0 && instance;
@@ -810,7 +818,7 @@ struct ExprImage {
     std::vector<uint2> ops;
     expr_encode(g, k, dom_k, ops);
     cols_fe = (EX_COLS * sizeof(void*) + 31) / 32;
-    const_fe = std::max<size_t>(g->n_constants, 1);
+    const_fe = std::max<size_t>((size_t)g->n_constants + n_challenges, 1);
     const size_t ops_fe = (ops.size() * 8 + 31) / 32;
     image.resize(cols_fe + const_fe + ops_fe);
     memset(image.data(), 0, image.size() * sizeof(fe));
@@ -819,6 +827,7 @@ struct ExprImage {
     for (uint32_t i = 0; i < H2MI_EXPR_MAX_FIXED; i++) tab[H2MI_EXPR_MAX_ADVICE + i] = fixed[i];
     tab[EX_COLS - 1] = instance;
     for (uint32_t i = 0; i < g->n_constants; i++) image[cols_fe + i] = h_canon(f29_from_mont256<F9>(host_fe(g->constants + 4 * i).v));
+    for (uint32_t i = 0; i < n_challenges; i++) image[cols_fe + g->n_constants + i] = h_canon(f29_from_mont256<F9>(host_fe(challenges + 4 * i).v));
     memcpy(&image[cols_fe + const_fe], ops.data(), ops.size() * 8);
     n_ops = (uint32_t)ops.size();
     lds = (size_t)(shape.max_stack - 1) * 9 * 256 * sizeof(uint32_t);  // at most 7 levels: 63 KB
@@ -1151,12 +1160,20 @@ int h2mi_plonk_evaluate_h_flex_dev(const h2mi_flex_cosets* c, uint32_t k, uint32
 int h2mi_plonk_evaluate_h_expr_dev(const h2mi_expr_cosets* c, const h2mi_gate_program* gates, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
                                    const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
                                    const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
+  return h2mi_plonk_evaluate_h_expr_ch_dev(c, gates, nullptr, 0, k, extended_k, blinding_factors, beta, gamma, y, delta, zeta, extended_omega, t_inv, d_h_out,
+                                           stream);
+}
+
+int h2mi_plonk_evaluate_h_expr_ch_dev(const h2mi_expr_cosets* c, const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k,
+                                      uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
+                                      const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out,
+                                      h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!c || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
   if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
   if (c->n_perm > H2MI_FLEX_MAX_PERM || c->n_lookups > H2MI_FLEX_MAX_LOOKUPS || (c->n_perm && c->chunk_len == 0)) return H2MI_EINVAL;
   ExprImage im;
-  int rc = im.build(gates, c->advice, c->fixed, c->instance, k, extended_k);
+  int rc = im.build(gates, challenges, n_challenges, c->advice, c->fixed, c->instance, k, extended_k);
   if (rc) return rc;
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
   FlexCosets fc;
@@ -1188,6 +1205,12 @@ int h2mi_plonk_evaluate_h_expr_dev(const h2mi_expr_cosets* c, const h2mi_gate_pr
 int h2mi_plonk_expr_compress_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
                                  const h2mi_gate_program* exprs, uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out,
                                  h2mi_stream_t stream) {
+  return h2mi_plonk_expr_compress_ch_dev(d_advice, n_advice, d_fixed, n_fixed, d_instance, exprs, nullptr, 0, k, domain_k, theta, d_out, stream);
+}
+
+int h2mi_plonk_expr_compress_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
+                                    const h2mi_gate_program* exprs, const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t domain_k,
+                                    const uint64_t theta[4], void* d_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!exprs || !theta || !d_out || (n_advice && !d_advice) || (n_fixed && !d_fixed) || n_advice > H2MI_EXPR_MAX_ADVICE || n_fixed > H2MI_EXPR_MAX_FIXED)
     return H2MI_EINVAL;
@@ -1197,7 +1220,7 @@ int h2mi_plonk_expr_compress_dev(const void* const* d_advice, uint32_t n_advice,
   for (uint32_t i = 0; i < n_advice; i++) adv[i] = d_advice[i];
   for (uint32_t i = 0; i < n_fixed; i++) fix[i] = d_fixed[i];
   ExprImage im;
-  int rc = im.build(exprs, adv, fix, d_instance, k, domain_k);
+  int rc = im.build(exprs, challenges, n_challenges, adv, fix, d_instance, k, domain_k);
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;

@@ -121,7 +121,7 @@ static_assert(H2MI_EXPR_MAX_ADVICE == H2MI_MAX_ADVICE && H2MI_EXPR_MAX_FIXED == 
 static_assert(H2MI_EXPR_ADVICE == H2MI_COL_ADVICE && H2MI_EXPR_FIXED == H2MI_COL_FIXED && H2MI_EXPR_INSTANCE == H2MI_COL_INSTANCE, "query ops are the column kinds");
 
 // the rules of h2mi_gate_program_check (include/h2mi_prover.h)
-int check_program(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, h2::ExprShape* shape) {
+int check_program(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, h2::ExprShape* shape, uint32_t n_challenges = 0) {
   if (cs.k == 0 || cs.k > H2MI_MAX_LOG_N || cs.n_advice > H2MI_MAX_ADVICE || cs.n_fixed > H2MI_MAX_FIXED || cs.n_instance > 1 ||
       cs.n_advice_queries > H2MI_MAX_QUERIES || cs.n_fixed_queries > H2MI_MAX_QUERIES)
     return H2MI_EINVAL;
@@ -131,7 +131,7 @@ int check_program(const h2mi_constraint_system& cs, const h2mi_gate_program* gat
     return false;
   };
   h2::ExprShape sh;
-  const int rc = h2::expr_walk(gates, cs.k, [&](uint32_t kind, uint32_t index, int32_t rotation) {
+  const int rc = h2::expr_walk(gates, cs.k, n_challenges, [&](uint32_t kind, uint32_t index, int32_t rotation) {
     if (kind == H2MI_EXPR_ADVICE) return index < cs.n_advice && listed(cs.advice_queries, cs.n_advice_queries, index, rotation);
     if (kind == H2MI_EXPR_FIXED) return index < cs.n_fixed && listed(cs.fixed_queries, cs.n_fixed_queries, index, rotation);
     return index < cs.n_instance;  // instance columns are not opened (KZG): no query list
@@ -147,13 +147,14 @@ int check_program(const h2mi_constraint_system& cs, const h2mi_gate_program* gat
 struct LookupSlices {
   h2mi_gate_program input[H2MI_MAX_LOOKUPS], table[H2MI_MAX_LOOKUPS];
 };
-int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_program* lp, uint32_t* degree_out, LookupSlices* slices) {
+int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_program* lp, uint32_t* degree_out, LookupSlices* slices,
+                         uint32_t n_challenges = 0) {
   if (!lp || lp->n_lookups == 0 || lp->n_lookups > H2MI_MAX_LOOKUPS || lp->n_lookups != cs.n_lookups) return H2MI_EINVAL;
   h2::ExprShape all;
   {
     h2mi_constraint_system any = cs;  // the structural rules and the query lists; the degree rule is per lookup, below
     any.degree = 0xffffffffu;
-    const int rc = check_program(any, &lp->exprs, &all);
+    const int rc = check_program(any, &lp->exprs, &all, n_challenges);
     if (rc) return rc;
   }
   uint32_t want = 0;
@@ -168,7 +169,7 @@ int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_pro
     for (uint32_t seen = 0; seen < polys; pos++) seen += lp->exprs.ops[pos].op == H2MI_EXPR_END;
     const h2mi_gate_program sub = {lp->exprs.ops + first, pos - first, lp->exprs.constants, lp->exprs.n_constants};
     h2::ExprShape sh;
-    h2::expr_walk(&sub, cs.k, [](uint32_t, uint32_t, int32_t) { return true; }, &sh);  // validated above
+    h2::expr_walk(&sub, cs.k, n_challenges, [](uint32_t, uint32_t, int32_t) { return true; }, &sh);  // validated above
     if (out) *out = sub;
     return std::max(sh.degree, 1u);
   };
@@ -182,8 +183,30 @@ int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_pro
   return H2MI_OK;
 }
 
-void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups) {
+// the rules of h2mi_advice_phases_check (include/h2mi_prover.h) [RECALL halo2_proofs v2023_02_02 plonk/circuit.rs advice_column_in,
+// challenge_usable_after]: a column in phase p > 0 needs one in phase p - 1 and a challenge usable after p needs a column in p — with
+// n_phases stated, that is: every phase below n_phases holds a column, every column and every challenge names a phase below it
+int check_phases(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, const h2mi_advice_phases& ph) {
+  if (cs.gates != H2MI_GATES_EXPRESSIONS || !gates) return H2MI_EINVAL;
+  if (ph.n_phases == 0 || ph.n_phases > H2MI_MAX_ADVICE_PHASES || ph.n_challenges > H2MI_MAX_CHALLENGES || cs.n_advice > H2MI_MAX_ADVICE) return H2MI_EINVAL;
+  uint32_t columns[H2MI_MAX_ADVICE_PHASES] = {0, 0, 0};
+  for (uint32_t j = 0; j < cs.n_advice; j++) {
+    if (ph.advice_phase[j] >= ph.n_phases) return H2MI_EINVAL;
+    columns[ph.advice_phase[j]]++;
+  }
+  for (uint32_t p = 0; p < ph.n_phases; p++)
+    if (!columns[p]) return H2MI_EINVAL;
+  for (uint32_t i = 0; i < ph.n_challenges; i++)
+    if (ph.challenge_phase[i] >= ph.n_phases) return H2MI_EINVAL;
+  int rc = check_program(cs, gates, nullptr, ph.n_challenges);
+  if (!rc && lookups) rc = check_lookup_program(cs, lookups, nullptr, nullptr, ph.n_challenges);
+  return rc;
+}
+
+void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, const h2mi_advice_phases* phases) {
   auto bad = [](const char* what) { throw Error(H2MI_EINVAL, std::string("constraint system: ") + what); };
+  const uint32_t n_ch = phases ? phases->n_challenges : 0;
+  if (phases && check_phases(cs, gates, lookups, *phases)) bad("advice phases / challenges");
   if (cs.k == 0 || cs.k > H2MI_MAX_LOG_N) throw Error(H2MI_ERANGE, "constraint system: k");
   if (cs.degree < 3 || cs.degree > 9) bad("degree");
   if (((uint64_t)1 << cs.k) <= (uint64_t)cs.blinding_factors + 2) throw Error(H2MI_ERANGE, "constraint system: no usable rows");
@@ -208,7 +231,7 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, 
     if (cs.gates == H2MI_GATES_EXPRESSIONS) {
       // the permutation products take any chunk length, and so does the quotient kernel that interprets the program
       if (!gates) bad("gates given as expressions go through h2mi_prover_keygen_gates");
-      if (check_program(cs, gates, nullptr)) bad("gate program");
+      if (check_program(cs, gates, nullptr, n_ch)) bad("gate program");
     } else {
       if (cs.n_gates == 0 || cs.n_gates > H2MI_MAX_GATES) bad("gate count");
       for (uint32_t g = 0; g < cs.n_gates; g++)
@@ -217,7 +240,7 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, 
     }
     if (lookups) {  // the lookups as a program: cs.lookups[] is not read
       if (cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_exprs takes H2MI_GATES_EXPRESSIONS");
-      if (check_lookup_program(cs, lookups, nullptr, nullptr)) bad("lookup program");
+      if (check_lookup_program(cs, lookups, nullptr, nullptr, n_ch)) bad("lookup program");
     }
     for (uint32_t l = 0; !lookups && l < cs.n_lookups; l++) {
       const h2mi_lookup& lk = cs.lookups[l];
@@ -262,6 +285,9 @@ struct h2mi_pk_s {
   std::vector<h2mi_expr_op> lookup_ops;
   std::vector<uint64_t> lookup_constants;
   LookupSlices lookup_slices;
+  // advice phases and challenges (h2mi_prover_keygen_phases); every other keygen: one phase, no challenges
+  h2mi_advice_phases phases;
+  uint32_t phase_columns[H2MI_MAX_ADVICE_PHASES] = {0, 0, 0};
   explicit h2mi_pk_s(const h2mi_constraint_system& c)
       : cs(c), domain(c.degree, c.k), n((size_t)1 << c.k), ext(domain.extended_len()), u((uint32_t)n - (c.blinding_factors + 1)),
         chunk(c.degree - 2), n_sets(c.n_perm ? (c.n_perm + c.degree - 3) / (c.degree - 2) : 0), delta(fr_delta()) {}
@@ -320,11 +346,16 @@ void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells) {
   check(h2mi_memcpy_h2d(t.mult->p, mult.data(), mult.size() * 4), "table");
 }
 
-std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, uint64_t g_lagrange,
-                                  const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags) {
-  validate(cs, gates, lookups);
+std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
+                                  const h2mi_advice_phases* phases, uint64_t g_lagrange, const h2mi_column_cells* fixed, const uint32_t* copies,
+                                  size_t n_copies, unsigned flags) {
+  validate(cs, gates, lookups, phases);
   std::unique_ptr<h2mi_pk_s> pkp(new h2mi_pk_s(cs));
   h2mi_pk_s& pk = *pkp;
+  std::memset(&pk.phases, 0, sizeof(pk.phases));
+  pk.phases.n_phases = 1;
+  if (phases) pk.phases = *phases;
+  for (uint32_t j = 0; j < cs.n_advice; j++) pk.phase_columns[pk.phases.advice_phase[j]]++;
   if (gates) {
     pk.gate_ops.assign(gates->ops, gates->ops + gates->n_ops);
     if (gates->n_constants) pk.gate_constants.assign(gates->constants, gates->constants + 4 * (size_t)gates->n_constants);
@@ -336,7 +367,7 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     if (lookups->exprs.n_constants) pk.lookup_constants.assign(lookups->exprs.constants, lookups->exprs.constants + 4 * (size_t)lookups->exprs.n_constants);
     h2mi_lookup_program own = *lookups;
     own.exprs = {pk.lookup_ops.data(), lookups->exprs.n_ops, pk.lookup_constants.data(), lookups->exprs.n_constants};
-    if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices)) throw Error(H2MI_EINVAL, "lookup program");
+    if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices, pk.phases.n_challenges)) throw Error(H2MI_EINVAL, "lookup program");
   }
   pk.vk_only = (flags & H2MI_KEYGEN_VK_ONLY) != 0;
   const poly::EvaluationDomain& dom = pk.domain;
@@ -540,7 +571,8 @@ struct Forms {  // a column of the proof in Lagrange, coefficient and extended-c
   }
 };
 
-enum Phase { IDLE = 0, ADVICE, LOOKUPS, PRODUCTS, QUOTIENT, EVALUATIONS, SHPLONK_Q };
+// ADVICE: every advice phase is committed; ADVICE_PHASES: some are (h2mi_prover_s::advice_done of them)
+enum Phase { IDLE = 0, ADVICE, LOOKUPS, PRODUCTS, QUOTIENT, EVALUATIONS, SHPLONK_Q, ADVICE_PHASES };
 
 }  // namespace
 
@@ -564,6 +596,10 @@ struct h2mi_prover_s {
     Table sorted;
   } lk[H2MI_MAX_LOOKUPS];
   Fr theta;
+  // the circuit's challenges (h2mi_prover_set_challenges): read by the lookups' compression and by the quotient
+  std::vector<Fr> challenges;
+  bool have_challenges = false;
+  uint32_t advice_done = 0;
   Dev random_poly, h, h_poly, points, evals;
   // SHPLONK: three lanes (the library stream and two side streams), each with its own scratch
   Dev nx[3], tmp[3], h_x, l_x, h2_x;
@@ -603,8 +639,17 @@ struct h2mi_prover_s {
     for (uint32_t j = 0; j < cs.n_advice; j++) adv[j] = coset ? advice[j].coset->p : advice[j].value->p;
     for (uint32_t j = 0; j < cs.n_fixed; j++) fix[j] = coset ? pk->fixed_cosets[j]->p : pk->fixed_values[j]->p;
     const void* inst = cs.n_instance ? (coset ? instance_coset->p : instance->p) : nullptr;
-    check(h2mi_plonk_expr_compress_dev(adv, cs.n_advice, fix, cs.n_fixed, inst, &prog, cs.k, coset ? pk->domain.extended_k() : cs.k, theta.l, out.p, nullptr),
+    check(h2mi_plonk_expr_compress_ch_dev(adv, cs.n_advice, fix, cs.n_fixed, inst, &prog, challenge_limbs(), pk->phases.n_challenges, cs.k,
+                                          coset ? pk->domain.extended_k() : cs.k, theta.l, out.p, nullptr),
           "expr_compress");
+  }
+  const uint64_t* challenge_limbs() const { return pk->phases.n_challenges ? (const uint64_t*)challenges.data() : nullptr; }
+  // a key with challenges: the phases behind the advice need their values
+  void require_challenges() {
+    if (pk->phases.n_challenges && !have_challenges) {
+      phase = IDLE;
+      throw Error(H2MI_EINVAL, "h2mi_prover_set_challenges has not been called");
+    }
   }
   void* out_slot(size_t slot) const { return (char*)(d_partial ? d_partial : points->p) + 96 * slot; }
   const void* col(const DeviceVec& d, size_t offset_elems = 0) const { return (const char*)d.p + (offset_elems + lo) * 32; }
@@ -719,29 +764,44 @@ void require_phase(h2mi_prover_s& p, Phase want) {
   }
 }
 
-// ---- phase 1: advice columns ------------------------------------------------------------------------------------------------
-void phase_advice(h2mi_prover_s& p, const h2mi_column_cells* advice, const uint64_t* instance, size_t n_inst, uint64_t seed, uint64_t* points_out) {
+// ---- phase 1: advice columns, one call per advice phase [RECALL halo2_proofs v2023_02_02 plonk/prover.rs create_proof: per phase
+// synthesize, keep that phase's columns, blind and commit them in column order, write the points, squeeze that phase's challenges] ----
+void phase_advice(h2mi_prover_s& p, uint32_t ph, const h2mi_column_cells* advice, const uint64_t* instance, size_t n_inst, uint64_t seed,
+                  uint64_t* points_out) {
   const h2mi_pk_s& pk = *p.pk;
   const h2mi_constraint_system& cs = pk.cs;
+  const h2mi_advice_phases& phases = pk.phases;
   const size_t n = pk.n;
   const uint32_t bf = cs.blinding_factors, u = pk.u, na = cs.n_advice;
-  p.phase = IDLE;
-  if (seed >> (p.keyed ? 61 : 32)) throw Error(H2MI_EINVAL, p.keyed ? "nonce must be below 2^61" : "seed must be below 2^32");
-  if (n_inst && (!cs.n_instance || !instance)) throw Error(H2MI_EINVAL, "public inputs without an instance column");
-  if (n_inst > u) throw Error(H2MI_ERANGE, "more public inputs than usable rows");
-  p.seed = seed;
-  p.instance_vals.resize(n_inst);
-  if (n_inst) std::memcpy(p.instance_vals.data(), instance, n_inst * 32);
+  const Phase was = p.phase;
+  p.phase = IDLE;  // whatever is refused below abandons the proof
+  if (ph >= phases.n_phases) throw Error(H2MI_EINVAL, "advice phase beyond the key's");
+  if (ph > 0 && (was != ADVICE_PHASES || p.advice_done != ph)) throw Error(H2MI_EINVAL, "advice phases out of order");
+  for (uint32_t j = 0; j < na; j++)
+    if (phases.advice_phase[j] != ph && advice[j].count) throw Error(H2MI_EINVAL, "cells for an advice column of another phase");
   PatchList pl;
-  if (cs.n_instance) {
-    h2mi_column_cells ic = {nullptr, instance, n_inst, 0};
-    fill_column(*p.instance, n, ic, u, pl);
+  if (ph == 0) {  // a new proof: the seed and the public inputs
+    if (seed >> (p.keyed ? 61 : 32)) throw Error(H2MI_EINVAL, p.keyed ? "nonce must be below 2^61" : "seed must be below 2^32");
+    if (n_inst && (!cs.n_instance || !instance)) throw Error(H2MI_EINVAL, "public inputs without an instance column");
+    if (n_inst > u) throw Error(H2MI_ERANGE, "more public inputs than usable rows");
+    p.seed = seed;
+    p.have_challenges = false;
+    p.instance_vals.resize(n_inst);
+    if (n_inst) std::memcpy(p.instance_vals.data(), instance, n_inst * 32);
+    if (cs.n_instance) {
+      h2mi_column_cells ic = {nullptr, instance, n_inst, 0};
+      fill_column(*p.instance, n, ic, u, pl);
+    }
   }
   // witness cells + blinding rows.  Assigned cells and blinding rows of every column travel in ONE launch's arguments when the
-  // columns are short (h2mi_fr_patch_cells_dev) instead of a dozen 32-byte copies in front of the phase's commitments
+  // columns are short (h2mi_fr_patch_cells_dev) instead of a dozen 32-byte copies in front of the phase's commitments.  Column j's
+  // blinding row r is scalar j (bf + 1) + r of the stream whatever the column's phase
   const std::vector<Fr> blind = p.blinding(1, (size_t)na * (bf + 1));
   size_t assigned = 0;
+  std::vector<uint32_t> mine;  // this phase's columns, in column order
   for (uint32_t j = 0; j < na; j++) {
+    if (phases.advice_phase[j] != ph) continue;
+    mine.push_back(j);
     DeviceVec& colv = *p.advice[j].value;
     fill_column(colv, n, advice[j], u, pl);
     assigned = std::max(assigned, advice[j].count);
@@ -749,20 +809,21 @@ void phase_advice(h2mi_prover_s& p, const h2mi_column_cells* advice, const uint6
   }
   pl.flush();
   // the sparse promise (batched launches at every size) holds for the padded witness columns of the reference's circuits; a
-  // column assigned on more than a quarter of its rows takes the pipelined loop
+  // column assigned on more than a quarter of its rows takes the pipelined loop.  Decided per phase from that phase's columns: a
+  // later phase's running sums are typically dense where the first phase's columns are not
   p.advice_sparse = assigned * 4 <= n;
   {
     std::vector<const void*> cols;
-    for (uint32_t j = 0; j < na; j++) cols.push_back(p.col(*p.advice[j].value));
+    for (uint32_t j : mine) cols.push_back(p.col(*p.advice[j].value));
     p.commit_phase(true, cols, 0, p.advice_sparse, /*inorder=*/true);
   }
   check(h2mi_msm_flush(), "flush");  // the bucket reductions start now, not when the host reaches the join
   // The coefficient / extended forms of the advice and instance columns depend on no challenge (create_proof computes them after
-  // y): on the side stream they run beside the transcript round trips, the lookups' counting sorts and the grand products' chains
-  // of small scans instead of queueing behind the next phases' commitments
+  // y): on the side stream they run beside the transcript round trips, the caller's witness generation for the next advice phase,
+  // the lookups' counting sorts and the grand products' chains of small scans instead of queueing behind the next phases' commitments
   check(h2mi_stream_wait(p.side, nullptr), "stream_wait");
-  for (uint32_t j = 0; j < na; j++) p.forms(p.advice[j], p.side);
-  if (cs.n_instance) {
+  for (uint32_t j : mine) p.forms(p.advice[j], p.side);
+  if (ph == 0 && cs.n_instance) {
     if (n_inst <= 16) {  // a handful of public inputs: sum_r v_r * (l_0's coset rotated by r rows), no transform
       check(h2mi_plonk_instance_coset_dev(pk.l0->p, cs.k, pk.domain.extended_k(), instance, n_inst, p.instance_coset->p, p.side), "instance coset");
     } else {
@@ -770,8 +831,9 @@ void phase_advice(h2mi_prover_s& p, const h2mi_column_cells* advice, const uint6
       to_poly_and_coset(pk.domain, *p.instance, *p.instance_poly, *p.instance_coset, p.side);
     }
   }
-  p.read_points(na, points_out);
-  p.phase = ADVICE;
+  p.read_points(mine.size(), points_out);
+  p.advice_done = ph + 1;
+  p.phase = p.advice_done == phases.n_phases ? ADVICE : ADVICE_PHASES;
 }
 
 // ---- phase 2: lookups' permuted columns (plonk/lookup/prover.rs commit_permuted) -----------------------------------------------
@@ -781,6 +843,7 @@ void phase_lookups(h2mi_prover_s& p, const uint64_t* theta, uint64_t* points_out
   const size_t n = pk.n;
   const uint32_t bf = cs.blinding_factors, u = pk.u, L = cs.n_lookups;
   require_phase(p, ADVICE);
+  p.require_challenges();
   p.phase = IDLE;
   if (L) {
     const std::vector<Fr> lb = p.blinding(4, (size_t)2 * (bf + 1) * L);
@@ -835,6 +898,7 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
   const uint32_t bf = cs.blinding_factors, u = pk.u, L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
   if (p.phase == ADVICE && L == 0) p.phase = LOOKUPS;  // nothing to permute: the lookup phase may be skipped
   require_phase(p, LOOKUPS);
+  p.require_challenges();
   p.phase = IDLE;
   p.beta = beta;
   p.gamma = gamma;
@@ -979,8 +1043,8 @@ void phase_quotient(h2mi_prover_s& p, const Fr& y, uint64_t* points_out) {
     ec.l0 = pk.l0->p;
     ec.l_last = pk.l_last->p;
     ec.l_active = pk.l_active->p;
-    check(h2mi_plonk_evaluate_h_expr_dev(&ec, &pk.gate_program, d.k(), d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l,
-                                         d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
+    check(h2mi_plonk_evaluate_h_expr_ch_dev(&ec, &pk.gate_program, p.challenge_limbs(), pk.phases.n_challenges, d.k(), d.extended_k(), bf, p.beta.l,
+                                            p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
   } else if (cs.n_gates == 1 && m >= 1 && m <= 4 && L <= 1) {
     // one gate column: the specialised kernel (its level bookkeeping is written for this shape; faster per point than the general one)
@@ -1350,7 +1414,7 @@ int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_han
   *pk_out = nullptr;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;  // no CPU fallback: the prover exists on a GPU or not at all
   return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
     std::lock_guard<std::mutex> lk(g_reg_mu);
     g_live_pks.insert(pk.get());
     *pk_out = pk.release();
@@ -1373,7 +1437,7 @@ int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_p
   *pk_out = nullptr;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;
   return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
     std::lock_guard<std::mutex> lk(g_reg_mu);
     g_live_pks.insert(pk.get());
     *pk_out = pk.release();
@@ -1392,7 +1456,27 @@ int h2mi_prover_keygen_exprs(const h2mi_constraint_system* cs, const h2mi_gate_p
   *pk_out = nullptr;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;
   return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, g_lagrange_handle, fixed, copies, n_copies, flags);
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    g_live_pks.insert(pk.get());
+    *pk_out = pk.release();
+  });
+}
+
+int h2mi_advice_phases_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
+                             const h2mi_advice_phases* phases) {
+  if (!cs || !gates || !phases) return H2MI_EINVAL;
+  return check_phases(*cs, gates, lookups, *phases);
+}
+
+int h2mi_prover_keygen_phases(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
+                              const h2mi_advice_phases* phases, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
+                              size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
+  if (!cs || !gates || !phases || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)H2MI_KEYGEN_VK_ONLY)) return H2MI_EINVAL;
+  *pk_out = nullptr;
+  if (h2mi_device_count() == 0) return H2MI_ENODEV;
+  return guarded([&] {
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, phases, g_lagrange_handle, fixed, copies, n_copies, flags);
     std::lock_guard<std::mutex> lk(g_reg_mu);
     g_live_pks.insert(pk.get());
     *pk_out = pk.release();
@@ -1484,7 +1568,40 @@ int h2mi_prover_advice(h2mi_prover_t prover, const h2mi_column_cells* advice, co
                        uint64_t* points_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
   if (!advice) return H2MI_EINVAL;
-  return guarded([&] { phase_advice(*prover, advice, instance, n_instance_values, seed, points_out); });
+  if (prover->pk->phases.n_phases > 1) {  // the advice of such a key is committed phase by phase
+    prover->phase = IDLE;
+    return H2MI_EINVAL;
+  }
+  return guarded([&] { phase_advice(*prover, 0, advice, instance, n_instance_values, seed, points_out); });
+}
+int h2mi_prover_advice_phase(h2mi_prover_t prover, uint32_t phase, const h2mi_column_cells* advice, const uint64_t* instance, size_t n_instance_values,
+                             uint64_t seed, uint64_t* points_out) {
+  if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
+  if (!advice) return H2MI_EINVAL;
+  return guarded([&] { phase_advice(*prover, phase, advice, instance, n_instance_values, seed, points_out); });
+}
+int h2mi_prover_set_challenges(h2mi_prover_t prover, const uint64_t* values) {
+  if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
+  const uint32_t nc = prover->pk->phases.n_challenges;
+  if (prover->phase != ADVICE || (nc && !values)) {
+    prover->phase = IDLE;
+    return H2MI_EINVAL;
+  }
+  prover->challenges.resize(nc);
+  if (nc) std::memcpy(prover->challenges.data(), values, (size_t)nc * 32);
+  prover->have_challenges = true;
+  return H2MI_OK;
+}
+int h2mi_prover_get_phase_counts(h2mi_prover_t prover, h2mi_prover_phase_counts* out) {
+  if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
+  if (!out) return H2MI_EINVAL;
+  const h2mi_pk_s& pk = *prover->pk;
+  std::memset(out, 0, sizeof(*out));
+  out->n_phases = pk.phases.n_phases;
+  out->n_challenges = pk.phases.n_challenges;
+  for (uint32_t p = 0; p < pk.phases.n_phases; p++) out->advice[p] = pk.phase_columns[p];
+  for (uint32_t i = 0; i < pk.phases.n_challenges; i++) out->challenges[pk.phases.challenge_phase[i]]++;
+  return H2MI_OK;
 }
 int h2mi_prover_lookups(h2mi_prover_t prover, const uint64_t theta[4], uint64_t* points_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;

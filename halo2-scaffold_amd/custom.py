@@ -22,6 +22,11 @@ wants its table side to be TableColumn queries; here both spell the same argumen
 h2mi_lookup_program and `Keys` hands it to h2mi_prover_keygen_exprs: each side is compressed with theta and the table sorted inside
 every proof (csrc/h2mi_lookup.hip h2mi_fr_sort_unique_dev).  The single-expression lookups against a fixed table, sorted once at
 keygen, stay the fast path of range checks and are reached through flex.py.
+Phases and challenges [RECALL halo2_proofs v2023_02_02 plonk/circuit.rs, plonk/prover.rs]: `advice_column_in(phase)` (phases 0 .. 2; a
+later phase needs a column in the one before), `challenge_usable_after(phase)` (needs a column in that phase; numbered in creation
+order), `query_challenge` -> an Expression of degree 0 that any gate and either side of any lookup may hold.  `Keys` then goes through
+h2mi_prover_keygen_phases, and `create_proof` takes synthesize(challenges) -> Assignment in place of an Assignment: it is called once
+per advice phase with the challenges squeezed so far, and only that phase's columns are taken from what it returns.
 """
 from . import engine, flex
 from . import field as F
@@ -64,6 +69,13 @@ class Selector:
         self.index = index
 
 
+class Challenge:
+    """plonk::Challenge: its index (creation order) and the phase after which the transcript yields it"""
+
+    def __init__(self, index: int, phase: int):
+        self.index, self.phase = index, phase
+
+
 class Cell:
     def __init__(self, kind: str, column: int, row: int, value: int):
         self.kind, self.column, self.row, self.value = kind, column, row, value
@@ -71,11 +83,12 @@ class Cell:
 
 class Expression:
     """plonk::Expression<F>: a polynomial over column queries.  node: ("constant", v) | ("query", kind, column, rotation) |
-    ("selector", index) | ("neg", e) | ("add" | "sub" | "mul", a, b).  A selector stays symbolic until the constraint system knows how
+    ("selector", index) | ("challenge", index) | ("neg", e) | ("add" | "sub" | "mul", a, b).  A selector stays symbolic until the constraint system knows how
     many fixed columns the user took (`resolve`)."""
 
     def __init__(self, *node):
         self.node = node
+        self._depth = None  # stack_depth(), computed once: a node never changes, and a long sum would otherwise cost 2^terms
 
     @staticmethod
     def constant(v: int) -> "Expression":
@@ -114,13 +127,13 @@ class Expression:
         t = self.node[0]
         if t == "selector":
             return Expression("query", FIXED, first_selector_column + self.node[1], 0)
-        if t in ("constant", "query"):
+        if t in ("constant", "query", "challenge"):
             return self
         return Expression(t, *[e.resolve(first_selector_column) for e in self.node[1:]])
 
     def degree(self) -> int:
         t = self.node[0]
-        if t == "constant":
+        if t in ("constant", "challenge"):
             return 0
         if t in ("query", "selector"):
             return 1
@@ -131,13 +144,16 @@ class Expression:
 
     def stack_depth(self) -> int:
         """operand-stack depth of the postfix `program()` emits"""
-        t = self.node[0]
-        if t in ("constant", "query", "selector"):
-            return 1
-        if t == "neg":
-            return self.node[1].stack_depth()
-        first, second = self._order()
-        return max(first.stack_depth(), 1 + second.stack_depth())
+        if self._depth is None:
+            t = self.node[0]
+            if t in ("constant", "query", "selector", "challenge"):
+                self._depth = 1
+            elif t == "neg":
+                self._depth = self.node[1].stack_depth()
+            else:
+                first, second = self._order()
+                self._depth = max(first.stack_depth(), 1 + second.stack_depth())
+        return self._depth
 
     def _order(self):
         """operands in emission order: ADD and MUL commute, so the deeper operand goes first (it runs on an empty stack, the
@@ -147,16 +163,18 @@ class Expression:
             return b, a
         return a, b
 
-    def evaluate(self, q) -> int:
-        """the value with q(kind, column, rotation) for the queries (selectors resolved)"""
+    def evaluate(self, q, challenges=()) -> int:
+        """the value with q(kind, column, rotation) for the queries (selectors resolved) and challenges[i] for challenge i"""
         t = self.node[0]
         if t == "constant":
             return self.node[1]
         if t == "query":
             return q(*self.node[1:]) % R
+        if t == "challenge":
+            return challenges[self.node[1]] % R
         if t == "neg":
-            return -self.node[1].evaluate(q) % R
-        a, b = self.node[1].evaluate(q), self.node[2].evaluate(q)
+            return -self.node[1].evaluate(q, challenges) % R
+        a, b = self.node[1].evaluate(q, challenges), self.node[2].evaluate(q, challenges)
         return (a + b if t == "add" else a - b if t == "sub" else a * b) % R
 
     def _emit(self, ops, constants):
@@ -167,6 +185,8 @@ class Expression:
             ops.append((engine.EXPR_CONSTANT, constants[self.node[1]], 0))
         elif t == "query":
             ops.append((_KIND[self.node[1]], self.node[2], int(self.node[3])))
+        elif t == "challenge":
+            ops.append((engine.EXPR_CHALLENGE, self.node[1], 0))
         elif t == "neg":
             self.node[1]._emit(ops, constants)
             ops.append((engine.EXPR_NEG, 0, 0))
@@ -197,11 +217,26 @@ class ConstraintSystem:
         self.advice_queries, self._fixed_queries, self.instance_queries = [], [], []
         self.gate_names, self._polys = [], []       # one entry per polynomial, selectors unresolved
         self.lookup_names, self._lookups = [], []   # per lookup [(input, table)] expressions, selectors unresolved
+        self.advice_phase, self.challenge_phase = [], []  # per advice column its phase; per challenge the phase it is usable after
 
     # ---- columns -----------------------------------------------------------------------------------------------------
     def advice_column(self) -> Column:
+        return self.advice_column_in(0)
+
+    def advice_column_in(self, phase: int) -> Column:
+        """meta.advice_column_in(FirstPhase | SecondPhase | ThirdPhase) with the crate's assertion [RECALL plonk/circuit.rs]: a later
+        phase needs an advice column in the phase before it"""
+        assert 0 <= phase < engine.MAX_ADVICE_PHASES, "phases are 0, 1, 2"
+        assert phase == 0 or phase - 1 in self.advice_phase, f"no advice column in phase {phase - 1} yet"
         self.n_advice += 1
+        self.advice_phase.append(phase)
         return Column(ADVICE, self.n_advice - 1)
+
+    def challenge_usable_after(self, phase: int) -> Challenge:
+        """meta.challenge_usable_after(phase), with the crate's assertion: the phase holds an advice column"""
+        assert phase in self.advice_phase, f"no advice column in phase {phase}: nothing the challenge could depend on"
+        self.challenge_phase.append(phase)
+        return Challenge(len(self.challenge_phase) - 1, phase)
 
     def fixed_column(self) -> Column:
         self.n_user_fixed += 1
@@ -242,6 +277,9 @@ class ConstraintSystem:
     def query_selector(self, selector: Selector) -> Expression:
         return Expression("selector", selector.index)
 
+    def query_challenge(self, challenge: Challenge) -> Expression:
+        return Expression("challenge", challenge.index)
+
     def create_gate(self, name: str, constraints) -> None:
         polys = list(constraints(self))
         assert polys, "a gate needs at least one polynomial"
@@ -278,8 +316,9 @@ class ConstraintSystem:
 
     @property
     def gates(self):
-        """the polynomials as callables g(q), q(kind, column, rotation) -> value: the form oracle.flex.ConstraintSystem takes"""
-        return [(lambda q, p=p: p.evaluate(q)) for p in self.polynomials]
+        """the polynomials as callables g(q, challenges=()), q(kind, column, rotation) -> value: the form oracle.flex.ConstraintSystem
+        takes"""
+        return [(lambda q, challenges=(), p=p: p.evaluate(q, challenges)) for p in self.polynomials]
 
     @property
     def lookups(self):
@@ -313,6 +352,16 @@ class ConstraintSystem:
                 ops += e.program(constants)[0]
         return engine.LookupProgram.build([len(pairs) for pairs in self._lookups], ops, sorted(constants, key=constants.get))
 
+    @property
+    def n_phases(self) -> int:
+        return 1 + max(self.advice_phase, default=0)
+
+    def phases(self):
+        """-> engine.AdvicePhases, or None for a circuit with one advice phase and no challenge (the keygen calls without phases)"""
+        if self.n_phases == 1 and not self.challenge_phase:
+            return None
+        return engine.AdvicePhases.build(self.advice_phase, self.challenge_phase)
+
     def abi(self, k: int) -> engine.ConstraintSystem:
         abi = self._abi(k)
         abi.n_lookups = len(self._lookups)  # described by lookup_program(), not by the struct's single-expression entries
@@ -329,8 +378,9 @@ class Assignment:
     """what synthesize() leaves, through the calls of halo2's Region: sparse cells per column, the copy constraints in call order, the
     public inputs (one instance column)"""
 
-    def __init__(self, cs: ConstraintSystem, instance=()):
+    def __init__(self, cs: ConstraintSystem, instance=(), challenges=()):
         self.cs = cs
+        self.challenges = list(challenges)  # the values known to this run of synthesize(): integers, None for those not yet squeezed
         self.advice = [dict() for _ in range(cs.n_advice)]
         self.fixed = [dict() for _ in range(cs.n_fixed)]
         self.instance = [v % R for v in instance]
@@ -349,6 +399,10 @@ class Assignment:
     def enable_selector(self, selector: Selector, row: int) -> None:
         self.fixed[self.cs.selector_column(selector)][row] = 1
 
+    def get_challenge(self, challenge: Challenge):
+        """Assignment::get_challenge: the value, or None while the transcript has not yielded it (Value::unknown)"""
+        return self.challenges[challenge.index] if challenge.index < len(self.challenges) else None
+
     def constrain_equal(self, left: Cell, right: Cell) -> None:
         self.copies.append(((left.kind, left.column, left.row), (right.kind, right.column, right.row)))
 
@@ -363,10 +417,11 @@ class Assignment:
         return new
 
 
-def mock(asg: Assignment, k: int) -> None:
+def mock(asg: Assignment, k: int, challenges=()) -> None:
     """MockProver::run(k, ..).assert_satisfied() on the host: no cell or copy constraint beyond the usable rows, every gate polynomial
     zero on every usable row (unassigned cells are zero; rotations wrap around 2^k), every copy constraint between equal cells, every
-    lookup's input tuple on a usable row equal to its table tuple on some usable row.
+    lookup's input tuple on a usable row equal to its table tuple on some usable row.  challenges: the values the gates and lookups
+    read (MockProver derives its own; here the caller states the ones the witness was made with).
     Raises ValueError naming the first violation."""
     cs = asg.cs
     n = 1 << k
@@ -382,13 +437,13 @@ def mock(asg: Assignment, k: int) -> None:
              INSTANCE: lambda c, r: asg.instance[r] if r < len(asg.instance) else 0}
     for name, poly in zip(cs.gate_names, cs.polynomials):
         for row in range(u):
-            if poly.evaluate(lambda kind, c, rot: value[kind](c, (row + rot) % n)):
+            if poly.evaluate(lambda kind, c, rot: value[kind](c, (row + rot) % n), challenges):
                 raise ValueError(f"gate {name!r} not satisfied at row {row}")
     for left, right in asg.copies:
         if value[left[0]](left[1], left[2]) % R != value[right[0]](right[1], right[2]) % R:
             raise ValueError(f"copy constraint {left} == {right} not satisfied")
     for name, pairs in zip(cs.lookup_names, cs.lookups):
-        at = lambda e, row: e.evaluate(lambda kind, c, rot: value[kind](c, (row + rot) % n))
+        at = lambda e, row: e.evaluate(lambda kind, c, rot: value[kind](c, (row + rot) % n), challenges)
         table = {tuple(at(t, row) for _, t in pairs) for row in range(u)}
         for row in range(u):
             if tuple(at(a, row) for a, _ in pairs) not in table:
@@ -396,7 +451,8 @@ def mock(asg: Assignment, k: int) -> None:
 
 
 class Keys:
-    """keygen_vk + keygen_pk through h2mi_prover_keygen_gates (h2mi_prover_keygen_exprs when the circuit has lookups): the fixed cells of a run of synthesize() (selector columns included), the
+    """keygen_vk + keygen_pk through h2mi_prover_keygen_gates (h2mi_prover_keygen_exprs when the circuit has lookups,
+    h2mi_prover_keygen_phases when it has an advice column in a later phase or a challenge): the fixed cells of a run of synthesize() (selector columns included), the
     copy constraints with their columns renumbered into the permutation argument's order, the gates as a program the key copies.
     Same attributes as flex.FlexKeys."""
 
@@ -407,7 +463,8 @@ class Keys:
         self.u = d.n - (cs.blinding_factors() + 1)
         index = {col: j for j, col in enumerate(cs.perm_columns)}
         copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
-        self.keys = engine.Keys(cs.abi(k), params, list(asg.fixed), copies, gates=cs.gate_program(), lookups=cs.lookup_program())
+        self.keys = engine.Keys(cs.abi(k), params, list(asg.fixed), copies, gates=cs.gate_program(), lookups=cs.lookup_program(),
+                                phases=cs.phases())
         self.fixed_commitments, self.permutation_commitments = self.keys.fixed_commitments, self.keys.permutation_commitments
         nf, m = cs.n_fixed, len(cs.perm_columns)
         self.fixed_values, self.fixed_polys, self.fixed_cosets = (self.keys.views(kd, nf) for kd in (engine.PKBUF_FIXED, engine.PKBUF_FIXED_POLY, engine.PKBUF_FIXED_COSET))
@@ -424,7 +481,22 @@ class Keys:
 Workspace = flex.FlexWorkspace  # one library prover kept from proof to proof: nothing in it depends on the gate shape
 
 
-def create_proof(params: ParamsKZG, keys: Keys, asg: Assignment, seed: int, transcript=None, trace: dict = None, ws: Workspace = None) -> bytes:
-    """create_proof for one circuit: the transcript on this side, seven phase calls into the library (flex.create_proof's body: the
-    phases do not depend on how the gates were given; theta reaches the lookups phase through engine.Prover.drive)"""
+class _PhasedWitness:
+    """what flex.create_proof reads off an assignment, for a witness made phase by phase: the public inputs of the first run of
+    synthesize() and, as `advice`, the callable engine.Prover.drive calls once per advice phase"""
+
+    def __init__(self, synthesize, n_challenges: int):
+        first = [synthesize([None] * n_challenges)]  # the first phase's run, made here for its public inputs and used for phase 0
+        self.instance = first[0].instance
+        self.advice = lambda challenges: (first.pop() if first else synthesize(challenges)).advice
+
+
+def create_proof(params: ParamsKZG, keys: Keys, asg, seed: int, transcript=None, trace: dict = None, ws: Workspace = None) -> bytes:
+    """create_proof for one circuit: the transcript on this side, the phase calls into the library (flex.create_proof's body: the
+    phases do not depend on how the gates were given; theta reaches the lookups phase through engine.Prover.drive).
+    asg: an Assignment, or — a circuit whose witness reads challenges — a callable synthesize(challenges) -> Assignment, called once
+    per advice phase with the challenges squeezed so far (None for the others); only that phase's advice columns are taken from
+    what it returns, as the crate does."""
+    if callable(asg):
+        asg = _PhasedWitness(asg, len(keys.cs.challenge_phase))
     return flex.create_proof(params, keys, asg, seed, transcript=transcript, trace=trace, ws=ws)

@@ -23,6 +23,7 @@ CELLS_CANONICAL = 1
 KEYGEN_VK_ONLY = 1
 EUNSAT = -7
 MAX_GATES, MAX_PERM, MAX_LOOKUPS, MAX_QUERIES = 32, 64, 8, 192  # H2MI_MAX_* (include/h2mi_prover.h)
+MAX_ADVICE, MAX_CHALLENGES, MAX_ADVICE_PHASES = 64, 16, 3
 
 # h2mi_prover_buffer kinds
 (BUF_ADVICE, BUF_ADVICE_POLY, BUF_ADVICE_COSET, BUF_INSTANCE, BUF_PERM_Z, BUF_PERM_Z_POLY, BUF_PERM_Z_COSET, BUF_LOOKUP_PERMUTED_INPUT,
@@ -78,7 +79,7 @@ class ConstraintSystem(C.Structure):
 
 
 # h2mi_expr_op.op (include/h2mi.h): the first three are the column kinds above
-EXPR_ADVICE, EXPR_FIXED, EXPR_INSTANCE, EXPR_CONSTANT, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG, EXPR_END = range(9)
+EXPR_ADVICE, EXPR_FIXED, EXPR_INSTANCE, EXPR_CONSTANT, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG, EXPR_END, EXPR_CHALLENGE = range(10)
 MAX_EXPR_OPS, MAX_EXPR_CONSTANTS, MAX_EXPR_STACK = 4096, 256, 8
 
 
@@ -129,6 +130,31 @@ class LookupProgram(C.Structure):
         degree = C.c_uint32()
         check(lib.h2mi_lookup_program_check(C.byref(cs), C.byref(self), C.byref(degree)), "lookup_program_check")
         return degree.value
+
+
+class AdvicePhases(C.Structure):
+    """h2mi_advice_phases: the phase of every advice column and of every challenge (meta.advice_column_in, meta.challenge_usable_after)"""
+    _fields_ = [("n_phases", C.c_uint32), ("advice_phase", C.c_uint32 * MAX_ADVICE), ("n_challenges", C.c_uint32),
+                ("challenge_phase", C.c_uint32 * MAX_CHALLENGES)]
+
+    @classmethod
+    def build(cls, advice_phase, challenge_phase=(), n_phases: int = None) -> "AdvicePhases":
+        """advice_phase: the phase per advice column; challenge_phase: per challenge the phase it is usable after.  More challenges
+        than H2MI_MAX_CHALLENGES are counted, not stored: the check refuses them."""
+        assert len(advice_phase) <= MAX_ADVICE
+        ph = cls()
+        ph.n_phases = 1 + max(advice_phase, default=0) if n_phases is None else n_phases
+        for j, p in enumerate(advice_phase):
+            ph.advice_phase[j] = p
+        ph.n_challenges = len(challenge_phase)
+        for i, p in enumerate(challenge_phase[:MAX_CHALLENGES]):
+            ph.challenge_phase[i] = p
+        return ph
+
+    def check(self, cs: "ConstraintSystem", gates: GateProgram, lookups: LookupProgram = None) -> None:
+        """h2mi_advice_phases_check; H2miError(-1) for what keygen would refuse"""
+        check(lib.h2mi_advice_phases_check(C.byref(cs), C.byref(gates), C.byref(lookups) if lookups is not None else None, C.byref(self)),
+              "advice_phases_check")
 
 
 class ColumnCells(C.Structure):
@@ -211,13 +237,16 @@ class Keys:
     constrain_equal in call order, columns as indices into the permutation argument.  `params` is the WHOLE SRS."""
 
     def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False, gates: GateProgram = None,
-                 lookups: LookupProgram = None):
+                 lookups: LookupProgram = None, phases: AdvicePhases = None):
         self.cs = cs
         cells, keep = pack_cells(fixed)
         cp = np.ascontiguousarray(np.array(copies, dtype=np.uint32).reshape(-1, 4))
         h = C.c_void_p()
         flags = KEYGEN_VK_ONLY if vk_only else 0
-        if gates is None:
+        if phases is not None:  # advice columns of a later phase, challenges: h2mi_prover_keygen_exprs with the phases beside it
+            check(lib.h2mi_prover_keygen_phases(C.byref(cs), C.byref(gates), C.byref(lookups) if lookups is not None else None, C.byref(phases),
+                                                params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
+        elif gates is None:
             check(lib.h2mi_prover_keygen(C.byref(cs), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
         elif lookups is not None:  # the lookups as expressions too
             check(lib.h2mi_prover_keygen_exprs(C.byref(cs), C.byref(gates), C.byref(lookups), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp),
@@ -227,6 +256,7 @@ class Keys:
                   "keygen")
         del keep
         self.handle = h.value
+        self.phases = phases
         self._provers = weakref.WeakSet()  # the library refuses to release a key while a prover created against it is alive
         self.fixed_commitments = np.zeros((cs.n_fixed, 8), dtype=np.uint64)
         self.permutation_commitments = np.zeros((cs.n_perm, 8), dtype=np.uint64)
@@ -250,6 +280,11 @@ class _Counts(C.Structure):
     _fields_ = [("advice", C.c_uint32), ("lookups", C.c_uint32), ("products", C.c_uint32), ("quotient", C.c_uint32), ("evaluations", C.c_uint32)]
 
 
+class _PhaseCounts(C.Structure):
+    _fields_ = [("n_phases", C.c_uint32), ("n_challenges", C.c_uint32), ("advice", C.c_uint32 * MAX_ADVICE_PHASES),
+                ("challenges", C.c_uint32 * MAX_ADVICE_PHASES)]
+
+
 _COMBINE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t)
 
 
@@ -268,6 +303,8 @@ class Prover:
         keys._provers.add(self)
         self.counts = _Counts()
         check(lib.h2mi_prover_get_counts(self.handle, C.byref(self.counts)), "prover counts")
+        self.phase_counts = _PhaseCounts()
+        check(lib.h2mi_prover_get_phase_counts(self.handle, C.byref(self.phase_counts)), "prover phase counts")
         self._points = np.zeros((max(self.counts.advice, self.counts.lookups, self.counts.products, self.counts.quotient, 8), 8), dtype=np.uint64)
         self._evals = np.zeros((self.counts.evaluations, 4), dtype=np.uint64)
         self._cb = None
@@ -310,7 +347,10 @@ class Prover:
 
     def drive(self, advice, instance, seed: int, transcript: Blake2bWrite, trace: dict = None) -> None:
         """create_proof between the transcript's challenges.  advice: one {row: value} dict or dense list per advice column;
-        instance: the public inputs (integers).  The caller has hashed vk.transcript_repr and the public inputs already."""
+        instance: the public inputs (integers).  The caller has hashed vk.transcript_repr and the public inputs already.
+        A key with several advice phases or with challenges: `advice` may be a callable, synthesize(challenges) -> such a list,
+        called once per advice phase with the challenges known so far (integers; None for those not yet squeezed), of whose result
+        only that phase's columns are taken [RECALL halo2_proofs v2023_02_02 plonk/prover.rs]; a plain list serves every phase."""
         c, h, pts = self.counts, self.handle, self._points
         pp = pts.ctypes.data
         sq = transcript.squeeze_challenge  # 4 Montgomery limbs
@@ -323,11 +363,33 @@ class Prover:
 
         marks = [("start", time.perf_counter())]
         mark = (lambda name: marks.append((name, time.perf_counter()))) if trace is not None else (lambda name: None)
-        cells, keep = pack_cells(advice)
         inst = np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in instance])) if len(instance) else np.zeros((1, 4), dtype=np.uint64)
-        self._phase(lib.h2mi_prover_advice(h, cells, inst.ctypes.data, len(instance), seed, pp), "advice")
-        del keep
-        write_points(c.advice)
+        pc = self.phase_counts
+        if pc.n_phases == 1 and pc.n_challenges == 0 and not callable(advice):
+            cells, keep = pack_cells(advice)
+            self._phase(lib.h2mi_prover_advice(h, cells, inst.ctypes.data, len(instance), seed, pp), "advice")
+            del keep
+            write_points(c.advice)
+        else:
+            column_phase = self.keys.phases.advice_phase if self.keys.phases is not None else [0] * c.advice
+            challenge_phase = self.keys.phases.challenge_phase if pc.n_challenges else []
+            limbs, known = [None] * pc.n_challenges, [None] * pc.n_challenges
+            for phase in range(pc.n_phases):
+                columns = advice(list(known)) if callable(advice) else advice
+                cells, keep = pack_cells([cells_ if column_phase[j] == phase else {} for j, cells_ in enumerate(columns)])
+                self._phase(lib.h2mi_prover_advice_phase(h, phase, cells, inst.ctypes.data, len(instance), seed, pp), f"advice phase {phase}")
+                del keep
+                write_points(pc.advice[phase])
+                for i in range(pc.n_challenges):  # in index order, the challenges usable after this phase
+                    if challenge_phase[i] == phase:
+                        limbs[i] = sq()
+                        known[i] = F.fr_from_mont_limbs(limbs[i])
+                mark(f"advice phase {phase} committed")
+            if pc.n_challenges:
+                ch = np.ascontiguousarray(np.stack(limbs))
+                self._phase(lib.h2mi_prover_set_challenges(h, ch.ctypes.data), "set_challenges")
+            if trace is not None:
+                trace["challenges"] = list(known)
         mark("advice committed")
         theta = sq()  # drawn even without lookups
         if c.lookups:

@@ -248,10 +248,11 @@ class _ExprCosets(C.Structure):
 
 def evaluate_h_expr(domain: EvaluationDomain, program, advice, fixed, instance, perm_values, perm_sigmas, perm_zs, chunk_len: int, lookups,
                     l0: DevBuf, l_last: DevBuf, l_active: DevBuf, beta: int, gamma: int, y: int, out: DevBuf,
-                    blinding_factors: int = BLINDING_FACTORS) -> None:
+                    blinding_factors: int = BLINDING_FACTORS, challenges=None) -> None:
     """h(X) on the extended coset with the gates given as a postfix program (h2mi_plonk_evaluate_h_expr_dev): `program` an
     engine.GateProgram over the coset forms `advice` / `fixed` (lists, None for a column the program does not read) and `instance`
-    (or None); permutation argument and lookups as evaluate_h_flex takes them, both optional."""
+    (or None); permutation argument and lookups as evaluate_h_flex takes them, both optional.  challenges: a list of integers, the
+    values CHALLENGE ops push (h2mi_plonk_evaluate_h_expr_ch_dev); None: the entry point that knows of none."""
     m = len(perm_values)
     assert len(advice) <= _ExprCosets.A and len(fixed) <= _ExprCosets.Fx and m <= _ExprCosets.P and len(perm_sigmas) == m
     assert len(perm_zs) == (-(-m // chunk_len) if m else 0) and len(lookups) <= _ExprCosets.L
@@ -275,14 +276,30 @@ def evaluate_h_expr(domain: EvaluationDomain, program, advice, fixed, instance, 
     mm = F.fr_to_mont_limbs
     t_inv = np.ascontiguousarray(vanishing_inverses(domain))
     args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
-    _check(lib.h2mi_plonk_evaluate_h_expr_dev(C.byref(cs), C.byref(program), domain.k, domain.extended_k, blinding_factors,
-                                              *[x.ctypes.data for x in args], t_inv.ctypes.data, out.ptr, None), "evaluate_h_expr")
+    if challenges is None:
+        _check(lib.h2mi_plonk_evaluate_h_expr_dev(C.byref(cs), C.byref(program), domain.k, domain.extended_k, blinding_factors,
+                                                  *[x.ctypes.data for x in args], t_inv.ctypes.data, out.ptr, None), "evaluate_h_expr")
+    else:
+        ch = _challenge_limbs(challenges)
+        _check(lib.h2mi_plonk_evaluate_h_expr_ch_dev(C.byref(cs), C.byref(program), ch.ctypes.data, len(challenges), domain.k, domain.extended_k,
+                                                     blinding_factors, *[x.ctypes.data for x in args], t_inv.ctypes.data, out.ptr, None), "evaluate_h_expr")
 
 
-def expr_compress(program, advice, fixed, instance, k: int, domain_k: int, theta: int, out: DevBuf) -> None:
+def _challenge_limbs(challenges) -> np.ndarray:
+    return np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in challenges])) if len(challenges) else np.zeros((1, 4), dtype=np.uint64)
+
+
+def expr_compress(program, advice, fixed, instance, k: int, domain_k: int, theta: int, out: DevBuf, challenges=None) -> None:
     """h2mi_plonk_expr_compress_dev: out[i] = sum_j e_j(i) theta^(m-1-j) over the m polynomials of `program` (an engine.GateProgram) on
-    the 2^domain_k points the columns are given on (lists of DevBuf, None for a column the program does not read)"""
+    the 2^domain_k points the columns are given on (lists of DevBuf, None for a column the program does not read).  challenges: as
+    evaluate_h_expr takes them (h2mi_plonk_expr_compress_ch_dev)."""
     ptrs = lambda cols: (C.c_void_p * max(len(cols), 1))(*[c.ptr if c is not None else None for c in cols])
+    if challenges is not None:
+        ch = _challenge_limbs(challenges)
+        _check(lib.h2mi_plonk_expr_compress_ch_dev(ptrs(advice), len(advice), ptrs(fixed), len(fixed), instance.ptr if instance is not None else None,
+                                                   C.byref(program), ch.ctypes.data, len(challenges), k, domain_k, F.fr_to_mont_limbs(theta).ctypes.data,
+                                                   out.ptr, None), "expr_compress")
+        return
     _check(lib.h2mi_plonk_expr_compress_dev(ptrs(advice), len(advice), ptrs(fixed), len(fixed), instance.ptr if instance is not None else None,
                                             C.byref(program), k, domain_k, F.fr_to_mont_limbs(theta).ctypes.data, out.ptr, None), "expr_compress")
 

@@ -424,10 +424,14 @@ int h2mi_plonk_evaluate_h_flex_dev(const h2mi_flex_cosets* cosets, uint32_t k, u
 enum { H2MI_EXPR_ADVICE = 0, H2MI_EXPR_FIXED = 1, H2MI_EXPR_INSTANCE = 2,   /* = H2MI_COL_*: push column `index` at `rotation` */
        H2MI_EXPR_CONSTANT = 3,                                             /* push constants[index] */
        H2MI_EXPR_ADD, H2MI_EXPR_SUB, H2MI_EXPR_MUL, H2MI_EXPR_NEG,          /* on the top of the stack */
-       H2MI_EXPR_END };                                                    /* the one value left is this polynomial */
+       H2MI_EXPR_END,                                                      /* the one value left is this polynomial */
+       H2MI_EXPR_CHALLENGE };                                              /* push challenge `index` (rotation ignored): Expression::Challenge,
+                                                                              degree 0.  Known only to the entry points that take challenges */
 #define H2MI_MAX_EXPR_OPS 4096
 #define H2MI_MAX_EXPR_CONSTANTS 256
 #define H2MI_MAX_EXPR_STACK 8
+#define H2MI_MAX_CHALLENGES 16    /* meta.challenge_usable_after(phase): values squeezed from the transcript between the advice phases */
+#define H2MI_MAX_ADVICE_PHASES 3  /* FirstPhase .. ThirdPhase */
 #define H2MI_EXPR_MAX_ADVICE 64 /* = H2MI_MAX_ADVICE / H2MI_MAX_FIXED of h2mi_prover.h */
 #define H2MI_EXPR_MAX_FIXED 64
 typedef struct { uint32_t op; uint32_t index; int32_t rotation; } h2mi_expr_op;
@@ -463,6 +467,15 @@ int h2mi_plonk_evaluate_h_expr_dev(const h2mi_expr_cosets* cosets, const h2mi_ga
                                    uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
                                    const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
                                    const uint64_t* t_inv /* 2^(extended_k-k) x 4 */, void* d_h_out, h2mi_stream_t stream);
+/* The same with the values of the circuit's challenges: n_challenges x 4 limbs, Montgomery, n_challenges <= H2MI_MAX_CHALLENGES (NULL
+ * with 0).  An H2MI_EXPR_CHALLENGE op pushes challenges[index]; index >= n_challenges is H2MI_EINVAL.  The values travel behind the
+ * program's constants in the launch's one device buffer.  The call above is this one with no challenges: a CHALLENGE op is H2MI_EINVAL
+ * there. */
+int h2mi_plonk_evaluate_h_expr_ch_dev(const h2mi_expr_cosets* cosets, const h2mi_gate_program* gates, const uint64_t* challenges,
+                                      uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
+                                      const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
+                                      const uint64_t extended_omega[4], const uint64_t* t_inv /* 2^(extended_k-k) x 4 */, void* d_h_out,
+                                      h2mi_stream_t stream);
 
 /* A lookup's expressions compressed with theta (plonk/lookup/prover.rs compress_expressions): `exprs` holds m polynomials e_0 ..
  * e_(m-1) and d_out[i] = sum_j e_j(i) theta^(m-1-j) — the fold acc theta + e_j — for the 2^domain_k points the columns are given on:
@@ -473,6 +486,10 @@ int h2mi_plonk_evaluate_h_expr_dev(const h2mi_expr_cosets* cosets, const h2mi_ga
 int h2mi_plonk_expr_compress_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
                                  const h2mi_gate_program* exprs, uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out,
                                  h2mi_stream_t stream);
+/* The same with challenges, as h2mi_plonk_evaluate_h_expr_ch_dev takes them; the call above is this one with none. */
+int h2mi_plonk_expr_compress_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
+                                    const void* d_instance, const h2mi_gate_program* exprs, const uint64_t* challenges, uint32_t n_challenges,
+                                    uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out, h2mi_stream_t stream);
 
 /* ---- SRS generation helper: ParamsKZG::setup's g[i] = s_i * G   ------------------
  * d_scalars: n Fr (Montgomery).  d_out_affine: n G1Affine.  Fixed-base windowed multiplication of the

@@ -40,7 +40,10 @@
  *                              single-expression ones of FLEX_VERTICAL (cs->lookups[], a fixed table sorted once at keygen: the fast
  *                              path of range checks) or DATA as well — any `meta.lookup` / `meta.lookup_any`: per lookup a list of
  *                              (input expression, table expression) pairs in the same postfix form (h2mi_lookup_program; keygen
- *                              through h2mi_prover_keygen_exprs), compressed with theta and sorted inside each proof
+ *                              through h2mi_prover_keygen_exprs), compressed with theta and sorted inside each proof.  Advice columns
+ *                              of a later phase and challenges (h2mi_advice_phases; keygen through h2mi_prover_keygen_phases): the
+ *                              advice is then committed phase by phase (h2mi_prover_advice_phase) with the caller squeezing the
+ *                              challenges in between, and gates and lookups may read them
  * Every function returns H2MI_OK or a negative H2MI_E* code (h2mi.h); no exception crosses the boundary.  Field elements
  * and points use the layouts of h2mi.h (4 / 8 uint64 limbs, Montgomery form).  A prover object is used by one thread at a time.
  */
@@ -158,6 +161,29 @@ int h2mi_lookup_program_check(const h2mi_constraint_system* cs, const h2mi_looku
 int h2mi_prover_keygen_exprs(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                              uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags,
                              h2mi_pk_t* pk_out);
+/* Advice phases and challenges beside the constraint system: `meta.advice_column_in(SecondPhase)`, `meta.challenge_usable_after(phase)`
+ * and Expression::Challenge [RECALL halo2_proofs v2023_02_02 plonk/circuit.rs, plonk/prover.rs — restated from memory like the rest].
+ * create_proof commits the advice columns phase by phase and squeezes, after each phase, the challenges usable after it; the next
+ * phase's witness, any gate and either side of any lookup may read them (H2MI_EXPR_CHALLENGE, h2mi.h: degree 0).  Query lists,
+ * blinding_factors, degree and the order of the evaluations do not depend on phases.
+ * h2mi_advice_phases_check (host only, works without a GPU): H2MI_EINVAL unless cs->gates == H2MI_GATES_EXPRESSIONS, n_phases is 1 ..
+ * H2MI_MAX_ADVICE_PHASES, every advice column's and every challenge's phase is below n_phases, every phase below n_phases holds a column
+ * (the crate: a column in phase p > 0 needs one in phase p - 1, a challenge after p needs a column in p), n_challenges <=
+ * H2MI_MAX_CHALLENGES, and `gates` / `lookups` (may be NULL) pass h2mi_gate_program_check / h2mi_lookup_program_check with CHALLENGE
+ * ops of an index below n_challenges allowed — those two functions by themselves know of no challenges and refuse the op.
+ * h2mi_prover_keygen_phases: h2mi_prover_keygen_exprs with the phases; the key copies the struct.  With n_phases == 1 and no challenges
+ * the key is the one h2mi_prover_keygen_exprs makes. */
+typedef struct {
+  uint32_t n_phases;                                 /* 1 .. H2MI_MAX_ADVICE_PHASES */
+  uint32_t advice_phase[H2MI_MAX_ADVICE];            /* phase of advice column j (cs->n_advice entries) */
+  uint32_t n_challenges;                             /* <= H2MI_MAX_CHALLENGES, numbered in creation order */
+  uint32_t challenge_phase[H2MI_MAX_CHALLENGES];     /* challenge i is squeezed after the commitments of this phase */
+} h2mi_advice_phases;
+int h2mi_advice_phases_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
+                             const h2mi_advice_phases* phases);
+int h2mi_prover_keygen_phases(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
+                              const h2mi_advice_phases* phases, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
+                              size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
 int h2mi_prover_pk_release(h2mi_pk_t pk); /* H2MI_EINVAL while a prover created against it is alive */
 /* VerifyingKey::{fixed_commitments, permutation.commitments}: affine points (8 limbs each); either pointer may be NULL */
 int h2mi_prover_vk_commitments(h2mi_pk_t pk, uint64_t* fixed_out /* n_fixed x 8 */, uint64_t* permutation_out /* n_perm x 8 */);
@@ -203,6 +229,21 @@ int h2mi_prover_set_rng_key(h2mi_prover_t prover, const uint8_t key[32]);
  * points_out: n_advice commitments. */
 int h2mi_prover_advice(h2mi_prover_t prover, const h2mi_column_cells* advice, const uint64_t* instance, size_t n_instance_values, uint64_t seed,
                        uint64_t* points_out);
+/* The same, one advice phase at a time (a key of h2mi_prover_keygen_phases; on a one-phase key phase 0 IS h2mi_prover_advice, and
+ * h2mi_prover_advice on a key with more phases is H2MI_EINVAL).  Per phase p = 0 .. n_phases - 1 the caller synthesizes with the
+ * challenges known so far, calls this, writes points_out to its transcript and squeezes, in index order, the challenges whose phase
+ * is p.  advice: cs->n_advice entries; only the columns of phase p are read, and an entry of another phase's column must have count ==
+ * 0 (H2MI_EINVAL).  instance and seed are read at phase 0, which starts a new proof at any time.  points_out: this phase's commitments
+ * in column order (h2mi_prover_get_phase_counts).  Phases come in order, each once: anything else is H2MI_EINVAL and abandons the
+ * proof.  A column's blinding scalars do not depend on its phase.  The coefficient and extended forms of the phase's columns run on
+ * the device while the caller generates the next phase's witness. */
+int h2mi_prover_advice_phase(h2mi_prover_t prover, uint32_t phase, const h2mi_column_cells* advice, const uint64_t* instance,
+                             size_t n_instance_values, uint64_t seed, uint64_t* points_out);
+/* The values of all the circuit's challenges (n_challenges x 4 limbs, Montgomery), once per proof: after the last advice phase and
+ * before h2mi_prover_lookups / h2mi_prover_products (any other time: H2MI_EINVAL, the proof is abandoned).  Required when the key has
+ * challenges — the next phase is H2MI_EINVAL without it.  The library reads them in the lookups' compression and in the quotient;
+ * witness generation, which reads them first, is the caller's. */
+int h2mi_prover_set_challenges(h2mi_prover_t prover, const uint64_t* values);
 /* theta compresses the lookups of a key made by h2mi_prover_keygen_exprs (each side's expressions folded with it on the rows, the
  * table's usable rows sorted on the device); the single-expression lookups do not use it.
  * points_out: per lookup the permuted input, then the permuted table commitment (2 x n_lookups; nothing without lookups — the call
@@ -227,6 +268,14 @@ typedef struct {
   uint32_t advice, lookups, products, quotient, evaluations;
 } h2mi_prover_counts;
 int h2mi_prover_get_counts(h2mi_prover_t prover, h2mi_prover_counts* out);
+/* per advice phase: the commitments h2mi_prover_advice_phase returns (they sum to h2mi_prover_counts.advice) and the challenges to
+ * squeeze behind them */
+typedef struct {
+  uint32_t n_phases, n_challenges;
+  uint32_t advice[H2MI_MAX_ADVICE_PHASES];
+  uint32_t challenges[H2MI_MAX_ADVICE_PHASES];
+} h2mi_prover_phase_counts;
+int h2mi_prover_get_phase_counts(h2mi_prover_t prover, h2mi_prover_phase_counts* out);
 
 /* ---- device-resident intermediates, for callers that check or reuse them (the test-suite evaluates the quotient identity on them):
  * d_ptr_out / count_out receive the vector's address and its length in field elements.  Valid until the prover / pk is destroyed;

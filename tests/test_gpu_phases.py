@@ -1,0 +1,384 @@
+"""Advice phases and challenges on the device: the interpreter's challenge operand against Python integers through both level-A entry
+points that take challenges; a key of h2mi_prover_keygen_phases with one phase and no challenges giving the bytes of the existing
+route; a two-phase running linear combination and a three-phase circuit with a challenge inside a lookup, proved through custom.py
+and accepted by the phase-aware verifier of tests/phase_cases.py; the order and argument errors of the new calls."""
+import ctypes as C
+import random
+
+import numpy as np
+import pytest
+
+import custom_gate_cases as gate_cases
+import lookup_expr_cases as lookup_cases
+import phase_cases as cases
+from phase_cases import OP_ADVICE, OP_CHALLENGE, OP_END, OP_MUL
+from oracle import bn254 as o
+from oracle import flex as FX
+from oracle import lookup as L
+
+pytestmark = pytest.mark.gpu
+
+R = o.R
+SRS_SECRET = 0x5EC2E7 + 0x48324D49
+KINDS = {0: "advice", 1: "fixed", 2: "instance"}
+
+
+def _vals(buf, count):
+    return o.unpack(buf.to_numpy(shape=(count, 4), nbytes=count * 32), R)
+
+
+# ---- 1. the interpreter against Python integers ---------------------------------------------------------------------------------------
+N_ADV, N_FIX, N_CH = 3, 2, 16
+N_KERNEL_CASES = 14
+RANDOM_SHAPES = [(4, 3), (5, 4), (6, 5), (4, 6), (5, 7), (6, 8), (4, 9), (5, 3), (6, 6), (4, 8)]  # (k, cs degree): extended_k = k + 1 .. k + 3
+
+
+def _tree(custom, rng, degree, columns):
+    """a random Expression of exactly `degree` with challenges among its leaves: a product of `degree` random factors of degree one,
+    grouped at random, plus or minus a random term of lower degree"""
+    Q = lambda: custom.Expression("query", *((lambda c: (c[0], c[1], rng.choice(c[2])))(rng.choice(columns))))
+    CH = lambda: custom.Expression("challenge", rng.choice([0, 15, rng.randrange(N_CH)]))
+    K = lambda: custom.Expression.constant(rng.choice([0, 1, R - 1, rng.randrange(R)]))
+
+    def factor():
+        return rng.choice([Q, lambda: Q() + CH(), lambda: CH() * Q() - K(), lambda: -(Q() - CH() * CH()), lambda: K() - Q(), lambda: Q() - Q() * CH(),
+                           lambda: -Q()])()
+
+    def product(d):
+        if d == 1:
+            return factor()
+        left = rng.randrange(1, d)
+        return product(left) * product(d - left)
+
+    e = product(degree)
+    low = rng.choice([CH, K, lambda: product(rng.randrange(1, degree)) * CH()])()
+    return rng.choice([lambda: e + low, lambda: low - e, lambda: e - low, lambda: e])()
+
+
+def _kernel_case(custom, case):
+    """-> (k, cs degree, [trees], challenge values).  Cases 0 .. 3 are built on purpose, the rest are random trees of every degree 3 .. 9
+    with challenge leaves.  The cs degree sizes the extended domain: 2^k (degree - 1) rounded up."""
+    rng = random.Random(1717 + case)
+    rots = list(range(-3, 4))
+    columns = [("advice", j, rots) for j in range(N_ADV)] + [("fixed", j, rots) for j in range(N_FIX)] + [("instance", 0, rots)]
+    Q = lambda: custom.Expression("query", *((lambda c: (c[0], c[1], rng.choice(c[2])))(rng.choice(columns))))
+    CH = lambda i: custom.Expression("challenge", i)
+    values = [0, 1, R - 1] + [rng.randrange(R) for _ in range(N_CH - 3)]
+    rng.shuffle(values)
+    if case == 0:  # stack depth 8 (seven LDS levels) with challenges spilled and filled; degree 9 with a challenge as both operands of a MUL
+        leaves = [Q(), CH(0), Q(), CH(15), Q(), Q(), CH(7), Q()]
+        chain = leaves[-1]
+        for x in reversed(leaves[:-1]):
+            chain = x - chain
+        p = CH(15) * CH(15)
+        for _ in range(9):
+            p = p * Q()
+        return 6, 9, [chain, p], values
+    if case == 1:  # stack depth 1, no LDS, no constants: a challenge as a whole polynomial, one under NEG, a query
+        return 4, 3, [CH(0), -CH(15), custom.Expression("query", "advice", 0, -3)], values
+    if case == 2:  # 256 constants beside 16 challenges, every challenge index read; challenges on either side of a SUB
+        s = CH(0) * Q()
+        consts = rng.sample(range(2, 1 << 62), 255) + [R - 2]
+        for i, c in enumerate(consts):
+            s = s + custom.Expression.constant(c) * (Q() if i % 3 else CH(i % N_CH))
+        every = CH(0)
+        for i in range(1, N_CH):
+            every = every + CH(i) * Q()
+        return 5, 4, [s, Q() - CH(3), CH(15) - Q() * Q(), every], values
+    if case == 3:  # n_constants == 0 beside challenges: products and differences of challenges alone, and a zero / one / r - 1 value met
+        values = [0, 1, R - 1, R - 1] + values[4:]
+        return 6, 5, [CH(0) * CH(15), CH(1) * Q() - CH(2), -(CH(3) * CH(2)) * Q() * Q(), CH(1) - CH(0)], values
+    k, degree = RANDOM_SHAPES[case - 4]
+    trees = [_tree(custom, rng, d, columns) for d in [degree] + [rng.randrange(1, degree + 1) for _ in range(rng.randrange(0, 3))]]
+    rng.shuffle(trees)
+    assert max(t.degree() for t in trees) == degree and max(t.stack_depth() for t in trees) <= 8
+    return k, degree, trees, values
+
+
+def _program(engine, trees):
+    constants, ops = {}, []
+    for t in trees:
+        ops += t.program(constants)[0]
+    consts = sorted(constants, key=constants.get)
+    return ops, consts, engine.GateProgram.build(ops, consts)
+
+
+@pytest.mark.parametrize("case", range(N_KERNEL_CASES))
+def test_challenge_operand_against_python_integers(gpu, case):
+    """h2mi_plonk_evaluate_h_expr_ch_dev (no permutation, no lookups: h[i] = Horner in y over the polynomials times t_inv) on the extended
+    coset, and h2mi_plonk_expr_compress_ch_dev (the fold with theta) on the rows and on the extended coset: every element, exactly"""
+    from halo2_scaffold_amd import custom, engine, plonk
+    from halo2_scaffold_amd.device import DevBuf
+
+    k, degree, trees, ch = _kernel_case(custom, case)
+    dom = gpu.EvaluationDomain(degree, k)
+    assert 1 <= dom.extended_k - k <= 3
+    ops, consts, prog = _program(engine, trees)
+    rng = random.Random(31 + case)
+    y, theta = rng.randrange(R), rng.randrange(R)
+    for domain_k in (dom.extended_k, k):
+        size, rot = 1 << domain_k, 1 << (domain_k - k)
+        column = lambda: [rng.choice([0, 1, R - 1]) if rng.random() < 0.3 else rng.randrange(R) for _ in range(size)]
+        data = {("advice", j): column() for j in range(N_ADV)}
+        data.update({("fixed", j): column() for j in range(N_FIX)})
+        data[("instance", 0)] = column()
+        bufs = {key: DevBuf.from_numpy(o.pack(col, R)) for key, col in data.items()}
+        adv, fix, inst = [bufs[("advice", j)] for j in range(N_ADV)], [bufs[("fixed", j)] for j in range(N_FIX)], bufs[("instance", 0)]
+        polys = [cases.run_postfix(ops, consts, lambda op, c, r: data[(KINDS[op], c)][(idx + (r % (1 << k)) * rot) % size], ch) for idx in range(size)]
+        out = DevBuf(size * 32)
+        plonk.expr_compress(prog, adv, fix, inst, k, domain_k, theta, out, challenges=ch)
+        assert _vals(out, size) == [lookup_cases.compress(p, theta) for p in polys]
+        if domain_k == k:
+            continue
+        unused = DevBuf.from_numpy(o.pack([rng.randrange(R) for _ in range(size)], R))  # l_0 / l_last / l_active: multiplied into no term
+        plonk.evaluate_h_expr(dom, prog, adv, fix, inst, [], [], [], 1, [], unused, unused, unused, rng.randrange(R), rng.randrange(R), y, out,
+                              blinding_factors=5, challenges=ch)
+        tinv = [pow((pow(dom.g_coset * pow(dom.extended_omega, i, R) % R, 1 << k, R) - 1) % R, -1, R) for i in range(rot)]
+        assert _vals(out, size) == [lookup_cases.compress(p, y) * tinv[idx % rot] % R for idx, p in enumerate(polys)]
+
+
+def test_kernel_cases_cover_what_they_should(h2):
+    from halo2_scaffold_amd import custom, engine
+
+    shapes, degrees, depths, indices, values = set(), set(), set(), set(), set()
+    no_constants = many_constants = mul_both = under_sub = under_neg = 0
+    for case in range(N_KERNEL_CASES):
+        k, degree, trees, ch = _kernel_case(custom, case)
+        ops, consts, _ = _program(engine, trees)
+        shapes.add((k, (degree - 2).bit_length()))
+        degrees.add(max(t.degree() for t in trees))
+        depths.add(max(t.stack_depth() for t in trees))
+        used = {i for op, i, _ in ops if op == OP_CHALLENGE}
+        assert used
+        indices |= used
+        values |= {ch[i] for i in used}
+        no_constants += not consts
+        many_constants += len(consts) == 256 and used == set(range(N_CH))
+        for a, b, c in zip(ops, ops[1:], ops[2:]):
+            mul_both += a[0] == b[0] == OP_CHALLENGE and c[0] == OP_MUL
+            under_sub += b[0] == OP_CHALLENGE and c[0] == cases.OP_SUB
+            under_neg += b[0] == OP_CHALLENGE and c[0] == cases.OP_NEG
+        assert all(r in range(-3, 4) for op, _, r in ops if op <= 2)
+    assert {k for k, _ in shapes} == {4, 5, 6} and {e for _, e in shapes} == {1, 2, 3}
+    assert degrees >= set(range(3, 10)) and {1, 8} <= depths and {0, 15} <= indices and {0, 1, R - 1} <= values and len(values) > 8
+    assert no_constants and many_constants and mul_both and under_sub and under_neg
+
+
+def test_level_a_challenge_refusals(gpu):
+    """the existing two entry points refuse a CHALLENGE op; the new ones refuse an index at or beyond n_challenges and 17 challenges"""
+    from halo2_scaffold_amd import engine, plonk
+    from halo2_scaffold_amd._lib import H2miError
+    from halo2_scaffold_amd.device import DevBuf
+
+    col, out = DevBuf(32 * 32), DevBuf(64 * 32)
+    prog = engine.GateProgram.build([(OP_ADVICE, 0, 0), (OP_CHALLENGE, 1, 0), (OP_MUL, 0, 0), (OP_END, 0, 0)], [])
+
+    def compress(challenges):
+        plonk.expr_compress(prog, [col], [], None, 5, 5, 3, out, challenges=challenges)
+
+    compress([4, 5])
+    for bad in (None, [], [4], [1] * 17):
+        with pytest.raises(H2miError) as e:
+            compress(bad)
+        assert e.value.code == -1
+    dom = gpu.EvaluationDomain(3, 5)
+    coset = DevBuf(64 * 32)
+    args = (dom, prog, [coset], [], None, [], [], [], 1, [], coset, coset, coset, 1, 2, 3, out)
+    plonk.evaluate_h_expr(*args, challenges=[4, 5])
+    for bad in (None, [4], [1] * 17):
+        with pytest.raises(H2miError) as e:
+            plonk.evaluate_h_expr(*args, challenges=bad)
+        assert e.value.code == -1
+
+
+# ---- 2. one phase, no challenges: the bytes of the existing route -----------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["is_zero", "or", "xor"])
+def test_one_phase_key_gives_the_existing_bytes(gpu, name):
+    from halo2_scaffold_amd import custom, engine
+
+    k = 5
+    build = {"is_zero": lambda: gate_cases.is_zero_circuit(custom, 3), "or": lambda: gate_cases.or_circuit(custom, 1, 0),
+             "xor": lambda: lookup_cases.xor_circuit(custom)}[name]
+    cs, asg = build()
+    params = gpu.ParamsKZG.setup(k, SRS_SECRET)
+    keys = custom.Keys(params, cs, asg)
+    assert keys.keys.phases is None
+    want = custom.create_proof(params, keys, asg, 77)
+    keys.release()
+    cs.phases = lambda: engine.AdvicePhases.build([0] * cs.n_advice)  # h2mi_prover_keygen_phases with one phase and no challenges
+    phased = custom.Keys(params, cs, asg)
+    assert phased.keys.phases is not None and phased.transcript_repr == keys.transcript_repr
+    ws = custom.Workspace(params, phased)
+    pc = ws.prover.phase_counts
+    assert (pc.n_phases, pc.n_challenges, list(pc.advice), list(pc.challenges)) == (1, 0, [cs.n_advice, 0, 0], [0, 0, 0])
+    calls = []
+    through_phase = custom.create_proof(params, phased, lambda challenges: calls.append(challenges) or asg, 77, ws=ws)  # h2mi_prover_advice_phase(.., 0, ..)
+    assert through_phase == want and calls == [[]]
+    assert custom.create_proof(params, phased, asg, 77, ws=ws) == want                                                  # h2mi_prover_advice on that key
+    ws.release()
+    phased.release()
+    params.release()
+
+
+# ---- 3. / 4. proofs ---------------------------------------------------------------------------------------------------------------------
+def _setup(gpu, name, *args):
+    from halo2_scaffold_amd import custom
+
+    build, k = cases.CIRCUITS[name]
+    cs, synthesize = build(custom, *args)
+    first = synthesize([None] * len(cs.challenge_phase))  # the fixed cells and the copy constraints do not depend on challenges
+    params = gpu.ParamsKZG.setup(k, SRS_SECRET)
+    keys = custom.Keys(params, cs, first)
+    ws = custom.Workspace(params, keys)
+    ocs = gate_cases.oracle_cs(cs, name)
+    oasg = gate_cases.oracle_assignment(ocs, first)
+    vk = FX.VerifierKeys(ocs, k, SRS_SECRET, oasg.fixed, oasg.copies)
+    assert o.unpack_points(keys.fixed_commitments) == vk.fixed_commitments and keys.transcript_repr == vk.transcript_repr
+    return custom, cs, synthesize, k, params, keys, ws, vk, oasg
+
+
+def _release(params, keys, ws):
+    ws.release()
+    keys.release()
+    params.release()
+
+
+def _flips_rejected(vk, cs, proof, instance, offsets):
+    for at in offsets:
+        flipped = bytearray(proof)
+        flipped[at] ^= 1
+        assert not cases.verify_circuit(vk, cs, bytes(flipped), instance), at
+
+
+def test_two_phase_running_linear_combination(gpu):
+    """phase 0 commits a; gamma; phase 1 commits acc.  Accepted; rejected with a byte flipped; rejected when prover and library were
+    handed another gamma than the transcript's; the phase-0 commitment does not depend on the phase-1 witness"""
+    from halo2_scaffold_amd import engine
+    from halo2_scaffold_amd import field as F
+    from halo2_scaffold_amd.transcript import Blake2bWrite
+
+    custom, cs, synthesize, k, params, keys, ws, vk, oasg = _setup(gpu, "rlc")
+    n = 1 << k
+    pc = ws.prover.phase_counts
+    assert (pc.n_phases, pc.n_challenges, list(pc.advice), list(pc.challenges)) == (2, 1, [1, 1, 0], [1, 0, 0]) and ws.prover.counts.advice == 2
+    seen, trace = [], {}
+    proof = custom.create_proof(params, keys, lambda ch: seen.append(ch) or synthesize(ch), 31, trace=trace, ws=ws)
+    got = []
+    assert cases.verify_circuit(vk, cs, proof, oasg.instance, got)
+    (gamma,) = got
+    assert seen == [[None], [gamma]] and trace["challenges"] == [gamma]  # one call per phase, with what is known by then
+    custom.mock(synthesize([gamma]), k, [gamma])
+    acc = _vals(ws.prover.views(engine.BUF_ADVICE, 2)[1], n)
+    run, want = 0, []
+    for v in cases.RLC_VALUES:
+        run = (run * gamma + v) % R if want else v % R
+        want.append(run)
+    assert acc[: len(want)] == want and acc[len(want) + 1] == want[-1]
+    evals = 32 * (2 + 1 + 1 + (cs.degree() - 1))  # behind the commitments: advice a, acc; one permutation product; random; h pieces
+    _flips_rejected(vk, cs, proof, oasg.instance, [3, 32 + 3, evals + 5, len(proof) - 1])
+
+    class OtherGamma(Blake2bWrite):  # the first squeeze is gamma: hand prover and library gamma + 1, keep the transcript's own state
+        squeezes = 0
+
+        def squeeze_challenge(self):
+            limbs = super().squeeze_challenge()
+            self.squeezes += 1
+            return F.fr_to_mont_limbs((F.fr_from_mont_limbs(limbs) + 1) % R) if self.squeezes == 1 else limbs
+
+    t2 = {}
+    other = custom.create_proof(params, keys, synthesize, 31, transcript=OtherGamma.init(), trace=t2, ws=ws)
+    assert t2["challenges"] == [(gamma + 1) % R]
+    assert other[:32] == proof[:32] and other[32:64] != proof[32:64]
+    assert not cases.verify_circuit(vk, cs, other, oasg.instance)
+    # a phase-1 witness made with another gamma than the one the library is handed: the same phase-0 point, an unsatisfied gate
+    _, wrong = cases.rlc_circuit(custom, 1)
+    bad = custom.create_proof(params, keys, wrong, 31, ws=ws)
+    assert bad[:32] == proof[:32] and bad[32:64] != proof[32:64]
+    assert not cases.verify_circuit(vk, cs, bad, oasg.instance)
+    assert custom.create_proof(params, keys, synthesize, 31, ws=ws) == proof  # reproducible, and the prover has recovered
+    _release(params, keys, ws)
+
+
+def test_three_phases_and_a_challenge_inside_a_lookup(gpu):
+    from halo2_scaffold_amd import engine
+
+    custom, cs, synthesize, k, params, keys, ws, vk, oasg = _setup(gpu, "three")
+    n, bf = 1 << k, cs.blinding_factors()
+    u = n - (bf + 1)
+    pc, c = ws.prover.phase_counts, ws.prover.counts
+    assert (pc.n_phases, pc.n_challenges, list(pc.advice), list(pc.challenges)) == (3, 2, [2, 1, 1], [1, 1, 0])
+    assert cs.degree() == 5 and (c.advice, c.lookups, c.quotient) == (4, 2, 4)
+    seed, seen, trace = 9, [], {}
+    proof = custom.create_proof(params, keys, lambda ch: seen.append(ch) or synthesize(ch), seed, trace=trace, ws=ws)
+    ch = []
+    assert cases.verify_circuit(vk, cs, proof, oasg.instance, ch)
+    assert seen == [[None, None], [ch[0], None], ch] and trace["challenges"] == ch
+    witness = synthesize(ch)
+    custom.mock(witness, k, ch)
+    other = [[(oasg.instance[0][0] + 1) % R]]
+    assert not cases.verify_circuit(vk, cs, proof, other)
+    _flips_rejected(vk, cs, proof, oasg.instance, [3, 64 + 3, 96 + 3, len(proof) - 1])
+    # the device's intermediates: the compressed columns restated over the device's advice, oracle.lookup on them
+    pr = ws.prover
+    columns = {"advice": [_vals(v, n) for v in pr.views(engine.BUF_ADVICE, cs.n_advice)], "fixed": [_vals(v, n) for v in keys.fixed_values],
+               "instance": [list(witness.instance) + [0] * (n - len(witness.instance))]}
+    for col, cells in enumerate(witness.advice):
+        assert all(columns["advice"][col][r] == v for r, v in cells.items())
+    value = lambda kind, col, row: columns[kind][col][row]
+    theta, beta, gamma = trace["theta"], trace["beta"], trace["gamma"]
+    (pairs,) = cs.lookups
+    a_col = cases.compress_rows([a for a, _ in pairs], value, n, theta, ch)
+    s_col = cases.compress_rows([t for _, t in pairs], value, n, theta, ch)
+    assert s_col[:8] == [(x + ch[0] * y) % R for x, y in cases.THREE_TABLE] and not any(s_col[8:u])
+    lb, lzb = FX._rand(2 * (bf + 1), seed + 4), FX._rand(bf, seed + 5)
+    ap, sp = L.permute_expression_pair(a_col, s_col, u, lb[: bf + 1], lb[bf + 1 : 2 * bf + 2])
+    assert _vals(pr.views(engine.BUF_LOOKUP_PERMUTED_INPUT, 1)[0], n) == ap
+    assert _vals(pr.views(engine.BUF_LOOKUP_PERMUTED_TABLE, 1)[0], n) == sp
+    assert _vals(pr.views(engine.BUF_LOOKUP_Z, 1)[0], n) == L.lookup_product(a_col, s_col, ap, sp, beta, gamma, u, lzb)
+    # a phase-1 witness made with a wrong c0: the compressed input is no table value
+    _, wrong = cases.three_phase_circuit(custom, 1)
+    with pytest.raises(ValueError, match="ConstraintSystemFailure"):
+        custom.create_proof(params, keys, wrong, seed, ws=ws)
+    assert custom.create_proof(params, keys, synthesize, seed, ws=ws) == proof  # the prover recovers
+    _release(params, keys, ws)
+
+
+# ---- 5. order and argument errors ----------------------------------------------------------------------------------------------------
+def test_phase_order_and_argument_errors(gpu):
+    """each H2MI_EINVAL, each leaving the prover usable"""
+    from halo2_scaffold_amd import engine
+    from halo2_scaffold_amd import field as F
+
+    custom, cs, synthesize, k, params, keys, ws, vk, oasg = _setup(gpu, "rlc")
+    lib, h = gpu.lib, ws.prover.handle
+    gamma = 0xABCDEF
+    asg = synthesize([gamma])
+    both, keep = engine.pack_cells(asg.advice)
+    only_a, keep_a = engine.pack_cells([asg.advice[0], {}])
+    only_acc, keep_acc = engine.pack_cells([{}, asg.advice[1]])
+    pts = np.zeros((8, 8), dtype=np.uint64)
+    g = np.ascontiguousarray(F.fr_to_mont_limbs(gamma))
+    theta = np.ascontiguousarray(F.fr_to_mont_limbs(5))
+    adv = lambda phase, cells: lib.h2mi_prover_advice_phase(h, phase, cells, None, 0, 31, pts.ctypes.data)
+    ok_advice = lambda: adv(0, only_a) == 0 and adv(1, only_acc) == 0
+    EINVAL = -1
+    assert adv(1, only_acc) == EINVAL                                    # phase 1 before phase 0
+    assert adv(0, only_a) == 0 and adv(0, only_a) == 0                   # phase 0 starts a new proof at any time
+    first = pts[0].copy()
+    assert adv(1, only_acc) == 0 and adv(1, only_acc) == EINVAL          # a phase called twice
+    assert adv(0, both) == EINVAL                                        # cells for a column of another phase
+    assert adv(0, only_a) == 0 and adv(1, only_a) == EINVAL
+    assert adv(0, only_a) == 0 and adv(2, only_acc) == EINVAL            # a phase the key does not have
+    assert lib.h2mi_prover_advice(h, both, None, 0, 31, pts.ctypes.data) == EINVAL  # on a key with two phases
+    assert adv(0, only_a) == 0 and lib.h2mi_prover_set_challenges(h, g.ctypes.data) == EINVAL  # before the last advice phase
+    assert ok_advice() and lib.h2mi_prover_lookups(h, theta.ctypes.data, pts.ctypes.data) == EINVAL  # without h2mi_prover_set_challenges
+    assert ok_advice() and lib.h2mi_prover_products(h, theta.ctypes.data, theta.ctypes.data, pts.ctypes.data) == EINVAL
+    assert ok_advice() and lib.h2mi_prover_set_challenges(h, None) == EINVAL
+    assert ok_advice() and lib.h2mi_prover_set_challenges(h, g.ctypes.data) == 0
+    assert lib.h2mi_prover_lookups(h, theta.ctypes.data, pts.ctypes.data) == 0
+    assert lib.h2mi_prover_products(h, theta.ctypes.data, theta.ctypes.data, pts.ctypes.data) == 0
+    assert adv(0, only_a) == 0 and (pts[0] == first).all()               # the same seed: the same phase-0 commitment
+    del keep, keep_a, keep_acc
+    proof = custom.create_proof(params, keys, synthesize, 31, ws=ws)     # and a whole proof on the same prover
+    assert cases.verify_circuit(vk, cs, proof, oasg.instance)
+    _release(params, keys, ws)
