@@ -256,6 +256,73 @@ def xor_circuit(custom, triples=((1, 2, 3), (3, 3, 0), (0, 2, 2), (2, 1, 3)), ba
     return meta, region
 
 
+XOR4_MARGIN = 8  # usable rows left free at the end (the copied cell sits among them)
+XOR4_OFTEN = (9, 12, 5)
+XOR4_ABSENT = (3, 5, 7)  # 3 ^ 5 = 6: in no table row
+
+
+def xor4_rows(k: int, blinding_factors: int = 5) -> int:
+    return (1 << k) - (blinding_factors + 1) - XOR4_MARGIN
+
+
+def xor4_triples(k: int, seed: int = 4):
+    """row -> (a, b, a ^ b), or None where the selector stays off (the zero tuple): about 60 % one triple, the rest uniform over the
+    table's 256 rows, a selector off on every 97th row"""
+    import random
+
+    rng = random.Random(seed * 1000 + k)
+    triples = []
+    for row in range(xor4_rows(k)):
+        if row % 97 == 41:
+            triples.append(None)
+        elif rng.random() < 0.6:
+            triples.append(XOR4_OFTEN)
+        else:
+            x, y = rng.randrange(16), rng.randrange(16)
+            triples.append((x, y, x ^ y))
+    return triples
+
+
+def xor4_circuit(custom, k: int, bad_row: int = None):
+    """xor_circuit at any size: the 4-bit XOR table (256 rows) in three fixed columns, the inputs (q a, q b, q c) on every usable row
+    but a margin at the end, the same packing gate and one copy constraint.  bad_row: that row's triple becomes XOR4_ABSENT.
+    -> (cs, assignment)"""
+    meta = custom.ConstraintSystem()
+    a, b, c, p = (meta.advice_column() for _ in range(4))
+    t_a, t_b, t_c = (meta.fixed_column() for _ in range(3))
+    q = meta.selector()
+    meta.enable_equality(p)
+    cur = custom.Rotation.cur()
+
+    def pack(meta):
+        a_, b_, c_, p_ = (meta.query_advice(col, cur) for col in (a, b, c, p))
+        return [meta.query_selector(q) * (a_ + b_ * 16 + c_ * 256 - p_)]
+
+    meta.create_gate("pack", pack)
+    meta.lookup("xor4", lambda meta: [(meta.query_selector(q) * meta.query_advice(col, cur), meta.query_fixed(tab, cur))
+                                      for col, tab in ((a, t_a), (b, t_b), (c, t_c))])
+    region = custom.Assignment(meta)
+    for i in range(256):
+        for tab, v in ((t_a, i >> 4), (t_b, i & 15), (t_c, (i >> 4) ^ (i & 15))):
+            region.assign_fixed(tab, i, v)
+    triples = xor4_triples(k)
+    assert meta.blinding_factors() == 5 and triples[0] is not None
+    if bad_row is not None:
+        assert triples[bad_row] is not None
+        triples[bad_row] = XOR4_ABSENT
+    first = None
+    for row, t in enumerate(triples):
+        x, y, z = t if t is not None else (0, 0, 0)
+        for col, v in ((a, x), (b, y), (c, z)):
+            region.assign_advice(col, row, v)
+        cell = region.assign_advice(p, row, x + 16 * y + 256 * z)
+        first = first or cell
+        if t is not None:
+            region.enable_selector(q, row)
+    region.copy_advice(first, p, len(triples) + 1)  # selector off there: a free cell tied to the first packed value
+    return meta, region
+
+
 def any_circuit(custom):
     """(b) lookup_any, advice in the table, rotations on both sides: (q a, q b(w^-1 X)) in (q_t x, q_t y(w X)), where a gate makes
     y(w X) = x^2 + 1 on the table's rows.  The selectors are off on the rows whose rotated query reaches a blinding row.

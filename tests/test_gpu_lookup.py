@@ -1,10 +1,14 @@
 """GPU tests of the lookup argument on the device (BASELINE config 3: range.rs with LOOKUP_BITS): the
 permuted input / table columns (a counting sort against the fixed table instead of the crate's sort + BTreeMap walk), the
 lookup grand product and `evaluate_h` of the range-check constraint system (degree 4, extended domain 4n) against
-oracle/lookup.py — element for element at k <= 8, through the quotient identity at k = 16."""
+oracle/lookup.py — element for element at k <= 8, through the quotient identity at k = 16; then the permuted columns and the grand
+product alone, row by row, at the sizes where their kernels take more than one workgroup, tile or scan segment (k = 11 .. 14)."""
+import types
+
 import numpy as np
 import pytest
 
+import lookup_scale_cases as scale
 from oracle import bn254 as o
 from oracle import lookup as L
 from oracle.plonk import BLINDING_FACTORS
@@ -213,3 +217,118 @@ def test_range_quotient_identity_at_2pow16(gpu):
     missing, h_bad, exact_bad, zl_end, zp_end = run(la_bad)
     assert missing == 0 and zl_end == 1 and zp_end != 1
     assert not exact_bad or not check(la_bad, h_bad)
+
+
+# ---- beyond one workgroup: tests/lookup_scale_cases.py (checked on the CPU by tests/test_lookup_scale_host.py) ------------------------
+def _upload(gpu, values):
+    return gpu.DevBuf.from_numpy(scale.mont_limbs(values))
+
+
+def _assert_column(buf, want, what):
+    """the buffer's bytes == the Montgomery form of `want`; a mismatch names the first row"""
+    got = buf.to_numpy(shape=(len(want), 4), nbytes=len(want) * 32)
+    if np.array_equal(got, scale.mont_limbs(want)):
+        return
+    values = scale.from_mont_limbs(got)
+    rows = [r for r in range(len(want)) if values[r] != want[r]]
+    assert not rows, f"{what}: {len(rows)} rows differ, the first at row {rows[0]}: {values[rows[0]]:#x} != {want[rows[0]]:#x}"
+    raise AssertionError(f"{what}: equal as field elements, but not in the canonical Montgomery form")
+
+
+def _check_permute(gpu, case):
+    """both routes into h2mi_plonk_lookup_permute_dev — the table sorted on the host (gp.LookupTable) and on the device
+    (plonk.sort_unique of the Montgomery column) — against the oracle on all n rows; the rows beyond u are the caller's"""
+    from halo2_scaffold_amd import plonk as gp
+
+    k, n, u = case.k, case.n, case.u
+    want_a, want_s = L.permute_expression_pair(case.inputs, case.table, u, case.keep_a, case.keep_s)
+    d_in, d_tab = _upload(gpu, case.inputs), _upload(gpu, case.table)
+    host = gp.LookupTable(case.table, u)
+    canon, mont, mult, n_unique = gp.sort_unique(d_tab, u)
+    assert n_unique == host.n_unique == len(set(case.table[:u]))
+    device = types.SimpleNamespace(sorted_canonical=canon, sorted_mont=mont, mult=mult, n_unique=n_unique, usable_rows=u)
+    routes = (("host table", host), ("device table", device))
+    for route, table in routes:
+        d_a, d_s = _upload(gpu, [0] * u + case.keep_a), _upload(gpu, [0] * u + case.keep_s)
+        assert gp.lookup_permute(k, d_in, table, d_a, d_s) == 0, route
+        _assert_column(d_a, want_a, f"A' ({route})")
+        _assert_column(d_s, want_s, f"S' ({route})")
+        d_a.free()
+        d_s.free()
+    return d_in, routes, (canon, mont, mult, d_tab, host)
+
+
+def _free(d_in, keep):
+    canon, mont, mult, d_tab, host = keep
+    for b in (d_in, canon, mont, mult, d_tab):
+        b.free()
+    host.free()
+
+
+@pytest.mark.parametrize("k,table_kind,input_kind", scale.PERMUTE_CASES, ids=[f"k{k}-{t}-{i}".replace(" ", "_") for k, t, i in scale.PERMUTE_CASES])
+def test_lookup_permute_beyond_one_workgroup(gpu, k, table_kind, input_kind):
+    """k_lk_rank with two and more workgroups — the binary search on arbitrary tables, the guess `rank = low word` landing on a real
+    entry that differs above word 0, every rank of a workgroup in one slot of its 64-slot table (the global-atomic fallback), the two
+    ends of the search — and, at k = 14, the counter scans in two segments.  Then three inputs that are in no table row (below the
+    smallest, above the largest, between two neighbours; rows 0, 1024 and u - 1): exactly three are counted."""
+    from halo2_scaffold_amd import plonk as gp
+
+    case = scale.permute_case(k, table_kind, input_kind)
+    d_in, routes, keep = _check_permute(gpu, case)
+    d_bad = _upload(gpu, case.bad_inputs)
+    d_a, d_s = gpu.DevBuf(case.n * 32), gpu.DevBuf(case.n * 32)
+    for route, table in routes:
+        assert gp.lookup_permute(k, d_bad, table, d_a, d_s) == 3, route
+    for b in (d_bad, d_a, d_s):
+        b.free()
+    _free(d_in, keep)
+
+
+@pytest.mark.parametrize("index", range(len(scale.USABLE_ROWS)), ids=[f"k{k}-u{u}-distinct{scale.usable_case_distinct(i)}" for i, (k, u) in enumerate(scale.USABLE_ROWS)])
+def test_lookup_permute_usable_rows_and_scan_pads(gpu, index):
+    """usable_rows as a free argument: every residue modulo 4 of it and of the table's distinct count (the scans run over lengths
+    rounded up to 4 and k_lk_fill_table reads the total at index u: the pads must be zero), one row either side of a k_lk_rank
+    workgroup (1024) and of a scan segment (8192)"""
+    d_in, _, keep = _check_permute(gpu, scale.usable_case(index))
+    _free(d_in, keep)
+
+
+def _compact_launches(gpu, call):
+    """launches of k_lookup_compact (the sparse form's position list) during call(), from the library's launch profile"""
+    import ctypes as C
+
+    lib = gpu.lib
+    assert lib.h2mi_profile_reset() == 0 and lib.h2mi_profile_filter(b"") == 0 and lib.h2mi_profile_enable(1) == 0
+    try:
+        call()
+    finally:
+        assert lib.h2mi_profile_enable(0) == 0
+    ms, count, every = C.c_double(), C.c_uint64(), C.c_uint64()
+    assert lib.h2mi_profile_query(b"k_lookup_compact", C.byref(ms), C.byref(count)) == 0
+    assert lib.h2mi_profile_query(b"", C.byref(ms), C.byref(every)) == 0
+    assert lib.h2mi_profile_reset() == 0
+    assert every.value > 0  # the profile did record this call's launches
+    return count.value
+
+
+@pytest.mark.parametrize("name", list(scale.PRODUCT_CASES), ids=[name.replace(" ", "_") for name in scale.PRODUCT_CASES])
+def test_lookup_product_every_regime(gpu, name):
+    """h2mi_plonk_lookup_product_dev on four columns of which exactly m rows have a ratio other than one, rows 0 .. u against the
+    oracle's row-by-row product: the dense form over several tiles of 1024 (tile offsets, the reverse scan over a partial last tile),
+    both sides of `usable_rows >= 4096 && 4 m <= u`, the empty position list, position counts around a tile, positions in the second
+    scan segment of the compaction.  Which form ran is read from the library's launch profile (one k_lookup_compact launch in the
+    sparse form with m > 0, none otherwise), so that a case cannot pass through the other branch."""
+    from halo2_scaffold_amd import plonk as gp
+
+    case = scale.product_case(name)
+    n, u = case.n, case.u
+    want = L.lookup_product(case.inputs, case.table, case.pin, case.ptab, case.beta, case.gamma, u, [])
+    assert len(want) == u + 1
+    assert sum(want[i + 1] != want[i] for i in range(u)) == case.m
+    bufs = [_upload(gpu, col) for col in (case.inputs, case.table, case.pin, case.ptab)]
+    d_z = _upload(gpu, [scale.SENTINEL] * n)
+    launches = _compact_launches(gpu, lambda: gp.lookup_product(case.k, *bufs, case.beta, case.gamma, u, d_z))
+    _assert_column(d_z, want + [scale.SENTINEL] * (n - u - 1), "z")  # z_0 .. z_u; the rows beyond are the caller's
+    assert launches == (1 if case.form == "sparse" and case.m else 0)
+    for b in bufs + [d_z]:
+        b.free()

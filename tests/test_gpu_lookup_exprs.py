@@ -198,14 +198,14 @@ def test_expr_compress_refusals(gpu):
 
 
 # ---- 3. proofs -----------------------------------------------------------------------------------------------------------------------
-def _prove_and_check(gpu, name, seed):
-    """prove through custom.py; the helper verifier accepts; the compressed columns (through the level-A call on the prover's own
-    buffers), the permuted columns and the product equal the restatement"""
+def _prove_and_check(gpu, name, k, seed, build=None):
+    """prove through custom.py at 2^k rows; the helper verifier accepts; the compressed columns (through the level-A call on the
+    prover's own buffers), the permuted columns and the product equal the restatement.  build: custom -> (cs, assignment), the
+    circuit `name` of cases.CIRCUITS by default"""
     from halo2_scaffold_amd import custom, engine, plonk
     from halo2_scaffold_amd.device import DevBuf
 
-    build, k = cases.CIRCUITS[name]
-    cs, asg = build(custom)
+    cs, asg = (build or cases.CIRCUITS[name][0])(custom)
     custom.mock(asg, k)
     n, bf = 1 << k, cs.blinding_factors()
     u = n - (bf + 1)
@@ -268,7 +268,7 @@ def test_xor_table_proof(gpu):
     """(a) the 2-bit XOR table: three pairs, inputs of degree 2; then the two unsatisfied witnesses: H2MI_EUNSAT"""
     from halo2_scaffold_amd import custom
 
-    params, keys, ws, vk, oasg, lookups, cs = _prove_and_check(gpu, "xor", 21)
+    params, keys, ws, vk, oasg, lookups, cs = _prove_and_check(gpu, "xor", 5, 21)
     assert cs.degree() == 5 and ws.prover.counts.lookups == 2 and ws.prover.counts.quotient == 4
     for bad in sorted(cases.XOR_BAD):
         _, broken = cases.xor_circuit(custom, bad=bad)
@@ -281,14 +281,14 @@ def test_xor_table_proof(gpu):
 
 def test_lookup_any_with_advice_table_and_rotations(gpu):
     """(b) advice in the table, b(w^-1 X) and y(w X): rotations on the rows wrap around 2^k, on the coset by 2^(extended_k - k)"""
-    params, keys, ws, vk, oasg, lookups, cs = _prove_and_check(gpu, "any", 5)
+    params, keys, ws, vk, oasg, lookups, cs = _prove_and_check(gpu, "any", 5, 5)
     assert cs.degree() == 6 and keys.domain.extended_k == 5 + 3
     _release(params, keys, ws)
 
 
 def test_two_lookups_gate_and_instance(gpu):
     """(c) a one-pair and a two-pair lookup, degree 6 from the lookup argument alone, a gate on an instance query, k = 6"""
-    params, keys, ws, vk, oasg, lookups, cs = _prove_and_check(gpu, "two", 77)
+    params, keys, ws, vk, oasg, lookups, cs = _prove_and_check(gpu, "two", 6, 77)
     c = ws.prover.counts
     assert cs.degree() == 6 and max(p.degree() for p in cs.polynomials) == 2 and (c.lookups, c.quotient) == (4, 5)
     other = [[(oasg.instance[0][0] + 1) % R] + oasg.instance[0][1:]]
@@ -297,6 +297,39 @@ def test_two_lookups_gate_and_instance(gpu):
     _, asg = cases.two_lookups_circuit(custom)
     proof = custom.create_proof(params, keys, asg, 78, ws=ws)
     assert cases.verify(vk, proof, oasg.instance, lookups) and not cases.verify(vk, proof, other, lookups)
+    _release(params, keys, ws)
+
+
+@pytest.mark.parametrize("k", [11, 14])
+def test_xor4_table_proof_at_real_sizes(gpu, k):
+    """a theta-compressed lookup on (nearly) every usable row: the prover's sort_unique -> lookup_permute -> lookup_product with two
+    k_lk_rank workgroups (k = 11) and with two scan segments and 16 tiles (k = 14), 256 distinct compressed values of which one
+    takes 60 % of the rows, the zero tuple from the rows whose selector is off and from the table's padding"""
+    params, keys, ws, vk, oasg, lookups, cs = _prove_and_check(gpu, "xor4", k, 31 + k, build=lambda custom: cases.xor4_circuit(custom, k))
+    assert cs.degree() == 5 and (1 << k) - 6 - cases.XOR4_MARGIN == cases.xor4_rows(k) > 2000
+    _release(params, keys, ws)
+
+
+def test_xor4_absent_triple_in_the_second_workgroup(gpu):
+    """one triple that is in no table row, on a row k_lk_rank's second workgroup takes: ConstraintSystemFailure, and the workspace
+    proves the good witness afterwards"""
+    from halo2_scaffold_amd import custom
+
+    k, bad_row = 11, 1500
+    assert bad_row >= 1024 and cases.xor4_triples(k)[bad_row] is not None
+    params = gpu.ParamsKZG.setup(k, SRS_SECRET)
+    cs, good = cases.xor4_circuit(custom, k)
+    keys = custom.Keys(params, cs, good)
+    ws = custom.Workspace(params, keys)
+    _, broken = cases.xor4_circuit(custom, k, bad_row=bad_row)
+    with pytest.raises(ValueError, match="lookup 'xor4' not satisfied at row 1500"):
+        custom.mock(broken, k)
+    with pytest.raises(ValueError, match="ConstraintSystemFailure"):
+        custom.create_proof(params, keys, broken, 41, ws=ws)
+    ocs = gate_cases.oracle_cs(cs, "xor4")
+    oasg = gate_cases.oracle_assignment(ocs, good)
+    vk = FX.VerifierKeys(ocs, k, SRS_SECRET, oasg.fixed, oasg.copies)
+    assert cases.verify(vk, custom.create_proof(params, keys, good, 42, ws=ws), oasg.instance, cases.expr_lookups(cs))  # the prover recovers
     _release(params, keys, ws)
 
 
