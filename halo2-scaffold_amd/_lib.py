@@ -103,6 +103,10 @@ def _load():
         "h2mi_plonk_expr_compress_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_expr_ch_dev": ([vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_expr_compress_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
+        "h2mi_plonk_expr_check_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32), vp],
+                                         C.c_int),
+        "h2mi_plonk_copy_check_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp], C.c_int),
+        "h2mi_plonk_lookup_member_dev": ([vp, vp, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
         "h2mi_fr_sort_unique_dev": ([vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), vp], C.c_int),
         "h2mi_g1_fixed_base_mul_dev": ([vp, sz, vp, vp], C.c_int),
         "h2mi_fr_powers_dev": ([vp, sz, vp, vp], C.c_int),
@@ -115,6 +119,7 @@ def _load():
         # include/h2mi_prover.h: the resident prover behind its phase-level ABI
         "h2mi_prover_keygen": ([vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_gate_program_check": ([vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], C.c_int),
+        "h2mi_shape_gate_program": ([vp, vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_prover_keygen_gates": ([vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_lookup_program_check": ([vp, vp, C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_prover_keygen_exprs": ([vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
@@ -131,6 +136,7 @@ def _load():
         "h2mi_prover_advice_phase": ([vp, C.c_uint32, vp, vp, sz, C.c_uint64, vp], C.c_int),
         "h2mi_prover_set_challenges": ([vp, vp], C.c_int),
         "h2mi_prover_get_phase_counts": ([vp, vp], C.c_int),
+        "h2mi_prover_check": ([vp, vp, vp, sz, C.POINTER(sz)], C.c_int),
         "h2mi_prover_lookups": ([vp, vp, vp], C.c_int),
         "h2mi_prover_products": ([vp, vp, vp, vp], C.c_int),
         "h2mi_prover_quotient": ([vp, vp, vp], C.c_int),

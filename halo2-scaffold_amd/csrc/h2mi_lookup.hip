@@ -93,6 +93,33 @@ __global__ void __launch_bounds__(1024) k_lk_rank(const fe* input, uint32_t u, c
   if (threadIdx.x < LK_SLOTS && hkey[threadIdx.x] != LK_EMPTY) atomicAdd(&cnt[hkey[threadIdx.x]], hcnt[threadIdx.x]);
 }
 
+// Membership alone, for the witness check (h2mi_prover_check): is the input of usable row i one of the table's distinct values?  The
+// binary search of k_lk_rank without its histogram.  report = {absent rows, the smallest of them}, from {0, 0xffffffff}; votes are
+// merged within the wavefront first (lane order is row order), so a witness whose inputs are all in the table issues no atomic.
+__global__ void __launch_bounds__(256) k_lk_member(const fe* input, uint32_t u, const fe* sorted, uint32_t n_unique, uint32_t* report) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool absent = false;
+  if (i < u) {
+    const fe v = fe_from_mont<Fr>(fe_load(&input[i]));
+    uint32_t lo = min(v.v[0], n_unique - 1);  // a range-check table: the value is its rank
+    if (cmp256(fe_load(&sorted[lo]), v) != 0) {
+      uint32_t hi = n_unique;
+      lo = 0;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (cmp256(fe_load(&sorted[mid]), v) < 0) lo = mid + 1;
+        else hi = mid;
+      }
+      absent = lo >= n_unique || cmp256(fe_load(&sorted[lo]), v) != 0;
+    }
+  }
+  const unsigned long long m = __ballot(absent);
+  if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll(m) - 1)) {
+    atomicAdd(&report[0], (uint32_t)__popcll(m));
+    atomicMin(&report[1], i);
+  }
+}
+
 __global__ void __launch_bounds__(256) k_lk_leftover(const uint32_t* cnt, const uint32_t* mult, uint32_t n_unique, uint32_t* left, uint32_t* missing) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_unique) return;
@@ -374,6 +401,32 @@ int h2mi_plonk_lookup_permute_dev(const void* d_input, const void* d_table_sorte
   H2_HIP(hipMemcpyAsync(&m, missing, 4, hipMemcpyDeviceToHost, s));
   H2_HIP(hipStreamSynchronize(s));
   *not_in_table_out = m;
+  return H2MI_OK;
+}
+
+int h2mi_plonk_lookup_member_dev(const void* d_input, const void* d_table_sorted, uint32_t n_unique, uint32_t usable_rows, uint32_t report_out[2],
+                                 h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_input || !d_table_sorted || !report_out || n_unique == 0) return H2MI_EINVAL;
+  if (usable_rows == 0 || usable_rows > (1u << H2MI_MAX_LOG_N) || n_unique > usable_rows) return H2MI_ERANGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  {
+    int rc0 = use_device(0);
+    if (rc0) return rc0;
+  }
+  hipStream_t s = pick_stream(stream);
+  {
+    int rcs = lk_scratch_reserve(4);
+    if (rcs) return rcs;
+  }
+  // the first two words of the scratch; a permutation of an earlier call on another stream may still read them
+  if (g_lk_event && g_lk_stream != s) H2_HIP(hipStreamWaitEvent(s, g_lk_event, 0));
+  const uint32_t init[2] = {0, 0xffffffffu};
+  H2_HIP(hipMemcpyAsync(g_lk_scratch, init, 8, hipMemcpyHostToDevice, s));
+  H2_LAUNCH("k_lk_member", k_lk_member, ceil_div_u32(usable_rows, 256), 256, 0, s, (const fe*)d_input, usable_rows, (const fe*)d_table_sorted, n_unique,
+            g_lk_scratch);
+  H2_HIP(hipMemcpyAsync(report_out, g_lk_scratch, 8, hipMemcpyDeviceToHost, s));
+  H2_HIP(hipStreamSynchronize(s));
   return H2MI_OK;
 }
 

@@ -635,6 +635,60 @@ __global__ void __launch_bounds__(256) k_expr_compress(const fe* const* __restri
   f29_to_mont256<F9>(acc, o.v);
   fe_store(&out[idx], o);
 }
+// The witness check: the same program on the Lagrange rows, each polynomial tested for zero on each row instead of folded.  The sink
+// counts the ENDs it has seen (j), brings the value below p (EX_RED's multiplication by the Montgomery one, then the conditional
+// subtraction: a value that is an unreduced multiple of r becomes the zero word — no word of an unreduced value is compared) and
+// votes: `report[j] = {rows where polynomial j is not zero, the smallest of them}`, the caller having set {0, 0xffffffff}.  The
+// program is wave-uniform, so every lane of a wavefront reaches every END together; a lane past n_rows (or past 2^k, in a launch
+// smaller than a wavefront: its loads wrap into the columns like any rotation) runs along and votes false.  One atomicAdd and one
+// atomicMin per wavefront and polynomial with a failing row, issued by the lowest failing lane (lane order is row order, so its row
+// is the wavefront's smallest); none for a satisfied witness.
+__global__ void __launch_bounds__(256) k_expr_check(const fe* const* __restrict__ cols, const fe* __restrict__ consts, const uint2* __restrict__ ops,
+                                                     uint32_t n_ops, uint32_t k, uint32_t n_rows, uint32_t* __restrict__ report) {
+  using namespace gen;
+  extern __shared__ uint32_t ex_stack[];
+  const uint32_t size = 1u << k;
+  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = idx < n_rows;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t j = 0;
+  expr_interpret(cols, consts, ops, n_ops, idx, size, ex_stack, [&](const f29& poly) {
+    const f29 c = f29_reduce_canonical<F9>(red(poly));
+    uint32_t z = 0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) z |= c.v[i];
+    const unsigned long long m = __ballot(live && z != 0);
+    if (m && lane == (uint32_t)(__ffsll(m) - 1)) {
+      atomicAdd(&report[2 * j], (uint32_t)__popcll(m));
+      atomicMin(&report[2 * j + 1], idx);
+    }
+    j++;
+  });
+}
+// Copy constraints on the rows: one thread per moved cell of the permutation (a cell whose sigma is not the identity), as keygen
+// lists them: {column, row} of the cell and of its image, columns numbered in the permutation argument's order.  Equal cycles have
+// every cell equal to its image (compared as canonical integers).  report = {unequal cells, the smallest index of one in `cells`},
+// from {0, 0xffffffff}: keygen sorts the list by (column, row), so the smallest index is the smallest cell in permutation order and
+// the lowest failing lane holds its wavefront's.  The same wavefront-first reduction.  The column pointers are read from device
+// memory (a table indexed by a loaded value: in the launch's arguments it would be a runtime-indexed private array).
+__global__ void __launch_bounds__(256) k_copy_check(const fe* const* __restrict__ cols, const uint4* __restrict__ cells, uint32_t n_cells,
+                                                     uint32_t* __restrict__ report) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  if (i < n_cells) {
+    const uint4 m = cells[i];
+    const fe a = fe_from_mont<Fr>(fe_load(&cols[m.x][m.y])), b = fe_from_mont<Fr>(fe_load(&cols[m.z][m.w]));
+    uint32_t d = 0;
+#pragma unroll
+    for (int w = 0; w < 8; w++) d |= a.v[w] ^ b.v[w];
+    bad = d != 0;
+  }
+  const unsigned long long m = __ballot(bad);
+  if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll(m) - 1)) {
+    atomicAdd(&report[0], (uint32_t)__popcll(m));
+    atomicMin(&report[1], i);
+  }
+}
 
 // the one inversion on the critical path, by division steps on the 32-bit-limb layer (fe_inv_ds; round 4: the shift / subtract
 // Euclid it replaces took 110 us for a lone wavefront).  in = x 2^261 read
@@ -1232,6 +1286,70 @@ int h2mi_plonk_expr_compress_ch_dev(const void* const* d_advice, uint32_t n_advi
   const uint32_t size = 1u << domain_k;
   H2_LAUNCH("k_expr_compress", k_expr_compress, ceil_div_u32(size, 256), 256, im.lds, s, (const fe* const*)d_image, (const fe*)(d_image + im.cols_fe),
             (const uint2*)(d_image + im.cols_fe + im.const_fe), im.n_ops, domain_k, host_fe(theta), (fe*)d_out);
+  return release_tmp(s);
+}
+
+int h2mi_plonk_expr_check_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
+                                 const h2mi_gate_program* polys, const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t n_rows,
+                                 uint32_t* report_out, uint32_t* n_polys_out, h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!polys || !report_out || (n_advice && !d_advice) || (n_fixed && !d_fixed) || n_advice > H2MI_EXPR_MAX_ADVICE || n_fixed > H2MI_EXPR_MAX_FIXED)
+    return H2MI_EINVAL;
+  if (k == 0 || k > H2MI_MAX_LOG_N || n_rows == 0 || n_rows > ((uint64_t)1 << k)) return H2MI_ERANGE;
+  const void* adv[H2MI_EXPR_MAX_ADVICE] = {nullptr};
+  const void* fix[H2MI_EXPR_MAX_FIXED] = {nullptr};
+  for (uint32_t i = 0; i < n_advice; i++) adv[i] = d_advice[i];
+  for (uint32_t i = 0; i < n_fixed; i++) fix[i] = d_fixed[i];
+  ExprImage im;
+  int rc = im.build(polys, challenges, n_challenges, adv, fix, d_instance, k, k);
+  if (rc) return rc;
+  uint32_t n_polys = 0;
+  for (uint32_t i = 0; i < polys->n_ops; i++) n_polys += polys->ops[i].op == H2MI_EXPR_END;
+  // the report travels behind the image, already {0, 0xffffffff} per polynomial: one copy on the stream sets both up
+  const size_t image_fe = im.image.size(), report_fe = ((size_t)n_polys * 8 + 31) / 32;
+  im.image.resize(image_fe + report_fe);
+  uint32_t* init = (uint32_t*)(im.image.data() + image_fe);
+  for (uint32_t j = 0; j < n_polys; j++) { init[2 * j] = 0; init[2 * j + 1] = 0xffffffffu; }
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  CallScope scope_;
+  hipStream_t s = pick_stream(stream);
+  rc = ensure_tmp(im.image.size(), s);
+  if (rc) return rc;
+  fe* d_image = tmp_base();
+  H2_HIP(hipMemcpyAsync(d_image, im.image.data(), im.image.size() * sizeof(fe), hipMemcpyHostToDevice, s));
+  H2_LAUNCH("k_expr_check", k_expr_check, ceil_div_u32(n_rows, 256), 256, im.lds, s, (const fe* const*)d_image, (const fe*)(d_image + im.cols_fe),
+            (const uint2*)(d_image + im.cols_fe + im.const_fe), im.n_ops, k, n_rows, (uint32_t*)(d_image + image_fe));
+  H2_HIP(hipMemcpyAsync(report_out, d_image + image_fe, (size_t)n_polys * 8, hipMemcpyDeviceToHost, s));
+  H2_HIP(hipStreamSynchronize(s));
+  if (n_polys_out) *n_polys_out = n_polys;
+  return release_tmp(s);
+}
+
+int h2mi_plonk_copy_check_dev(const void* const* d_values, uint32_t m, const void* d_cells, uint32_t n_cells, uint32_t report_out[2], h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_values || !report_out || m == 0 || m > H2MI_FLEX_MAX_PERM || (n_cells && !d_cells)) return H2MI_EINVAL;
+  for (uint32_t j = 0; j < m; j++)
+    if (!d_values[j]) return H2MI_EINVAL;
+  report_out[0] = 0;
+  report_out[1] = 0xffffffffu;
+  if (!n_cells) return H2MI_OK;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  CallScope scope_;
+  hipStream_t s = pick_stream(stream);
+  // the column pointers and, behind them, the report: one copy
+  constexpr size_t cols_fe = H2MI_FLEX_MAX_PERM * sizeof(void*) / 32;
+  fe image[cols_fe + 1];
+  memset(image, 0, sizeof(image));
+  memcpy(image, d_values, m * sizeof(void*));
+  ((uint32_t*)(image + cols_fe))[1] = 0xffffffffu;
+  int rc = ensure_tmp(cols_fe + 1, s);
+  if (rc) return rc;
+  fe* d_image = tmp_base();
+  H2_HIP(hipMemcpyAsync(d_image, image, sizeof(image), hipMemcpyHostToDevice, s));
+  H2_LAUNCH("k_copy_check", k_copy_check, ceil_div_u32(n_cells, 256), 256, 0, s, (const fe* const*)d_image, (const uint4*)d_cells, n_cells,
+            (uint32_t*)(d_image + cols_fe));
+  H2_HIP(hipMemcpyAsync(report_out, d_image + cols_fe, 8, hipMemcpyDeviceToHost, s));
+  H2_HIP(hipStreamSynchronize(s));
   return release_tmp(s);
 }
 

@@ -9,6 +9,7 @@
 // launches — the part rounds 2-4 tuned on the two former hosts (include/h2mi_plonk.hpp, halo2-scaffold_amd/prover.py + flex.py),
 // which are now thin callers of these phases.
 #include <algorithm>
+#include <array>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -288,6 +289,12 @@ struct h2mi_pk_s {
   // advice phases and challenges (h2mi_prover_keygen_phases); every other keygen: one phase, no challenges
   h2mi_advice_phases phases;
   uint32_t phase_columns[H2MI_MAX_ADVICE_PHASES] = {0, 0, 0};
+  // h2mi_prover_check: the cells the permutation moves, {column, row, image column, image row} sorted by (column, row), on the host
+  // and on the device; the gate polynomials as a program whatever the shape (the key's own, or the hard-wired shape's equivalent)
+  std::vector<uint32_t> moved_cells;
+  Dev moved_cells_dev;
+  std::vector<h2mi_expr_op> shape_ops;
+  h2mi_gate_program check_gates = {nullptr, 0, nullptr, 0};
   explicit h2mi_pk_s(const h2mi_constraint_system& c)
       : cs(c), domain(c.degree, c.k), n((size_t)1 << c.k), ext(domain.extended_len()), u((uint32_t)n - (c.blinding_factors + 1)),
         chunk(c.degree - 2), n_sets(c.n_perm ? (c.n_perm + c.degree - 3) / (c.degree - 2) : 0), delta(fr_delta()) {}
@@ -370,6 +377,15 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices, pk.phases.n_challenges)) throw Error(H2MI_EINVAL, "lookup program");
   }
   pk.vk_only = (flags & H2MI_KEYGEN_VK_ONLY) != 0;
+  if (gates) {
+    pk.check_gates = pk.gate_program;
+  } else {  // a hard-wired shape: its gates as the program the witness check interprets
+    uint32_t n_ops = 0, n_constants = 0;
+    pk.shape_ops.resize(H2MI_SHAPE_PROGRAM_MAX_OPS);
+    if (h2mi_shape_gate_program(&cs, pk.shape_ops.data(), H2MI_SHAPE_PROGRAM_MAX_OPS, &n_ops, nullptr, 0, &n_constants)) throw Error(H2MI_EINVAL, "shape program");
+    pk.shape_ops.resize(n_ops);
+    pk.check_gates = {pk.shape_ops.data(), n_ops, nullptr, 0};
+  }
   const poly::EvaluationDomain& dom = pk.domain;
   const size_t n = pk.n;
   const uint32_t u = pk.u, m = cs.n_perm;
@@ -408,12 +424,21 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
       pk.sigma_values.push_back(std::move(d));
     }
     std::vector<uint32_t> pos;
+    std::vector<std::array<uint32_t, 4>> moved;
     asm_.for_each([&](const Cell& from, const Cell& to) {
       if (from == to) return;
       pl.add(*pk.sigma_values[from.first], from.second, fr::mul(dpow[to.first], fr::pow_u64(dom.get_omega(), to.second)));
       if (from.second < u) pos.push_back((from.first / pk.chunk) * u + from.second);
+      if (!pk.vk_only) moved.push_back({from.first, from.second, to.first, to.second});
     });
     pl.flush();
+    if (!moved.empty()) {  // what h2mi_prover_check compares: 16 bytes per moved cell, uploaded once
+      std::sort(moved.begin(), moved.end());
+      pk.moved_cells.resize(4 * moved.size());
+      std::memcpy(pk.moved_cells.data(), moved.data(), 16 * moved.size());
+      pk.moved_cells_dev = vec(moved.size() / 2 + 1);
+      check(h2mi_memcpy_h2d(pk.moved_cells_dev->p, pk.moved_cells.data(), 16 * moved.size()), "moved cells");
+    }
     check(h2mi_sync(), "sync");  // omega_pows is released below
     std::sort(pos.begin(), pos.end());
     pos.erase(std::unique(pos.begin(), pos.end()), pos.end());
@@ -595,6 +620,9 @@ struct h2mi_prover_s {
     Dev table, in_coset, tab_coset;
     Table sorted;
   } lk[H2MI_MAX_LOOKUPS];
+  // h2mi_prover_check's own scratch, allocated by its first call: a lookup's input and table rows, the table's sorted distinct values
+  Dev check_in, check_tab;
+  Table check_sorted;
   Fr theta;
   // the circuit's challenges (h2mi_prover_set_challenges): read by the lookups' compression and by the quotient
   std::vector<Fr> challenges;
@@ -633,14 +661,14 @@ struct h2mi_prover_s {
   }
   const DeviceVec& lookup_table(uint32_t l) const { return pk->lookup_exprs ? *lk[l].table : *pk->fixed_values[pk->cs.lookups[l].table_fixed]; }
   // one side of lookup l compressed with theta, on the rows (coset = false) or on the extended coset
-  void compress(const h2mi_gate_program& prog, bool coset, DeviceVec& out) const {
+  void compress(const h2mi_gate_program& prog, bool coset, DeviceVec& out, const Fr* th = nullptr) const {
     const h2mi_constraint_system& cs = pk->cs;
     const void *adv[H2MI_MAX_ADVICE], *fix[H2MI_MAX_FIXED];
     for (uint32_t j = 0; j < cs.n_advice; j++) adv[j] = coset ? advice[j].coset->p : advice[j].value->p;
     for (uint32_t j = 0; j < cs.n_fixed; j++) fix[j] = coset ? pk->fixed_cosets[j]->p : pk->fixed_values[j]->p;
     const void* inst = cs.n_instance ? (coset ? instance_coset->p : instance->p) : nullptr;
     check(h2mi_plonk_expr_compress_ch_dev(adv, cs.n_advice, fix, cs.n_fixed, inst, &prog, challenge_limbs(), pk->phases.n_challenges, cs.k,
-                                          coset ? pk->domain.extended_k() : cs.k, theta.l, out.p, nullptr),
+                                          coset ? pk->domain.extended_k() : cs.k, (th ? *th : theta).l, out.p, nullptr),
           "expr_compress");
   }
   const uint64_t* challenge_limbs() const { return pk->phases.n_challenges ? (const uint64_t*)challenges.data() : nullptr; }
@@ -888,6 +916,78 @@ void phase_lookups(h2mi_prover_s& p, const uint64_t* theta, uint64_t* points_out
     p.read_points(2 * L, points_out);
   }
   p.phase = LOOKUPS;
+}
+
+// ---- the witness check between the advice and the lookups (h2mi_prover_check): gates, copies, lookups on the rows -----------------
+// Reads the advice / instance / fixed columns behind the advice fill on the library stream, writes only scratch of its own, and
+// leaves the phase state alone: the proof in flight goes on whatever it finds or refuses.
+std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* theta) {
+  const h2mi_pk_s& pk = *p.pk;
+  const h2mi_constraint_system& cs = pk.cs;
+  const size_t n = pk.n;
+  const uint32_t u = pk.u, L = cs.n_lookups, m = cs.n_perm;
+  if (p.phase != ADVICE && p.phase != LOOKUPS) throw Error(H2MI_EINVAL, "check: between the last advice phase and the products");
+  if (pk.phases.n_challenges && !p.have_challenges) throw Error(H2MI_EINVAL, "check: h2mi_prover_set_challenges has not been called");
+  if (L && pk.lookup_exprs && !theta) throw Error(H2MI_EINVAL, "check: theta");
+  std::vector<h2mi_check_failure> out;
+  const void *adv[H2MI_MAX_ADVICE], *fix[H2MI_MAX_FIXED];
+  for (uint32_t j = 0; j < cs.n_advice; j++) adv[j] = p.advice[j].value->p;
+  for (uint32_t j = 0; j < cs.n_fixed; j++) fix[j] = pk.fixed_values[j]->p;
+  {  // every gate polynomial on all 2^k rows of the blinded columns: the condition under which the quotient is a polynomial
+    uint32_t n_polys = 0;
+    for (uint32_t i = 0; i < pk.check_gates.n_ops; i++) n_polys += pk.check_gates.ops[i].op == H2MI_EXPR_END;
+    std::vector<uint32_t> report(2 * (size_t)n_polys);
+    check(h2mi_plonk_expr_check_ch_dev(adv, cs.n_advice, fix, cs.n_fixed, cs.n_instance ? p.instance->p : nullptr, &pk.check_gates, p.challenge_limbs(),
+                                       pk.phases.n_challenges, cs.k, (uint32_t)n, report.data(), nullptr, nullptr),
+          "expr_check");
+    for (uint32_t j = 0; j < n_polys; j++)
+      if (report[2 * j]) out.push_back({H2MI_CHECK_GATE, j, report[2 * j + 1], report[2 * j]});
+  }
+  if (m && !pk.moved_cells.empty()) {
+    const void* vals[H2MI_MAX_PERM];
+    for (uint32_t j = 0; j < m; j++) {
+      const h2mi_column& c = cs.perm_columns[j];
+      vals[j] = c.kind == H2MI_COL_ADVICE ? p.advice[c.index].value->p : c.kind == H2MI_COL_INSTANCE ? p.instance->p : pk.fixed_values[c.index]->p;
+    }
+    uint32_t report[2];
+    check(h2mi_plonk_copy_check_dev(vals, m, pk.moved_cells_dev->p, (uint32_t)(pk.moved_cells.size() / 4), report, nullptr), "copy_check");
+    if (report[0]) out.push_back({H2MI_CHECK_COPY, pk.moved_cells[4 * (size_t)report[1]], pk.moved_cells[4 * (size_t)report[1] + 1], report[0]});
+  }
+  for (uint32_t l = 0; l < L; l++) {
+    const void* input;
+    const Table* t;
+    if (pk.lookup_exprs) {  // what the lookups phase does with the transcript's theta, on scratch of this call's own
+      if (!p.check_in) {
+        p.check_in = vec(n);
+        p.check_tab = vec(n);
+        p.check_sorted.sorted = vec(u);
+        p.check_sorted.sorted_mont = vec(u);
+        p.check_sorted.mult = vec(u / 8 + 1);
+      }
+      Fr th;
+      std::memcpy(th.l, theta, 32);
+      p.compress(pk.lookup_slices.input[l], false, *p.check_in, &th);
+      p.compress(pk.lookup_slices.table[l], false, *p.check_tab, &th);
+      Table& ts = p.check_sorted;
+      check(h2mi_fr_sort_unique_dev(p.check_tab->p, u, ts.sorted->p, ts.sorted_mont->p, ts.mult->p, &ts.n_unique, nullptr), "sort_unique");
+      input = p.check_in->p;
+      t = &ts;
+    } else {
+      const h2mi_lookup& d = cs.lookups[l];
+      if (d.selector_fixed >= 0) {
+        if (!p.check_in) p.check_in = vec(n);
+        check(h2mi_fr_mul_dev(pk.fixed_values[d.selector_fixed]->p, p.advice[d.input.index].value->p, n, p.check_in->p, nullptr), "lookup input");
+        input = p.check_in->p;
+      } else {
+        input = p.advice[d.input.index].value->p;
+      }
+      t = &pk.tables[l];
+    }
+    uint32_t report[2];
+    check(h2mi_plonk_lookup_member_dev(input, t->sorted->p, t->n_unique, u, report, nullptr), "lookup_member");
+    if (report[0]) out.push_back({H2MI_CHECK_LOOKUP, l, report[1], report[0]});
+  }
+  return out;
 }
 
 // ---- phase 3: grand products + the vanishing argument's random polynomial ----------------------------------------------------
@@ -1431,6 +1531,55 @@ int h2mi_gate_program_check(const h2mi_constraint_system* cs, const h2mi_gate_pr
   return H2MI_OK;
 }
 
+int h2mi_shape_gate_program(const h2mi_constraint_system* cs, h2mi_expr_op* ops, uint32_t ops_cap, uint32_t* n_ops_out, uint64_t* constants,
+                            uint32_t constants_cap, uint32_t* n_constants_out) {
+  (void)constants;
+  (void)constants_cap;
+  if (!cs || !n_ops_out || !n_constants_out || (ops_cap && !ops)) return H2MI_EINVAL;
+  std::vector<h2mi_expr_op> prog;
+  auto q = [&](uint32_t kind, uint32_t column, int32_t rotation = 0) { prog.push_back({kind, column, rotation}); };
+  auto op = [&](uint32_t code) { prog.push_back({code, 0, 0}); };
+  if (cs->gates == H2MI_GATES_STANDARD_PLONK) {  // q_a a + q_b b + q_c c + q_ab a b + constant: advice 0..2, fixed 0..4
+    for (uint32_t i = 0; i < 3; i++) {
+      q(H2MI_EXPR_FIXED, i);
+      q(H2MI_EXPR_ADVICE, i);
+      op(H2MI_EXPR_MUL);
+      if (i) op(H2MI_EXPR_ADD);
+    }
+    q(H2MI_EXPR_FIXED, 3);
+    q(H2MI_EXPR_ADVICE, 0);
+    op(H2MI_EXPR_MUL);
+    q(H2MI_EXPR_ADVICE, 1);
+    op(H2MI_EXPR_MUL);
+    op(H2MI_EXPR_ADD);
+    q(H2MI_EXPR_FIXED, 4);
+    op(H2MI_EXPR_ADD);
+    op(H2MI_EXPR_END);
+  } else if (cs->gates == H2MI_GATES_FLEX_VERTICAL) {  // per gate column q (a + a(wX) a(w^2 X) - a(w^3 X)), in evaluate_h's order
+    if (cs->n_gates == 0 || cs->n_gates > H2MI_MAX_GATES) return H2MI_EINVAL;
+    for (uint32_t g = 0; g < cs->n_gates; g++) {
+      const uint32_t a = cs->gate_advice[g];
+      q(H2MI_EXPR_ADVICE, a, 1);
+      q(H2MI_EXPR_ADVICE, a, 2);
+      op(H2MI_EXPR_MUL);
+      q(H2MI_EXPR_ADVICE, a, 0);
+      op(H2MI_EXPR_ADD);
+      q(H2MI_EXPR_ADVICE, a, 3);
+      op(H2MI_EXPR_SUB);
+      q(H2MI_EXPR_FIXED, cs->gate_selector[g]);
+      op(H2MI_EXPR_MUL);
+      op(H2MI_EXPR_END);
+    }
+  } else {
+    return H2MI_EINVAL;  // H2MI_GATES_EXPRESSIONS: the caller holds the program
+  }
+  *n_ops_out = (uint32_t)prog.size();
+  *n_constants_out = 0;  // neither shape pushes a constant
+  if (prog.size() > ops_cap) return H2MI_ERANGE;
+  std::memcpy(ops, prog.data(), prog.size() * sizeof(h2mi_expr_op));
+  return H2MI_OK;
+}
+
 int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed,
                              const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
   if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)H2MI_KEYGEN_VK_ONLY)) return H2MI_EINVAL;
@@ -1606,6 +1755,17 @@ int h2mi_prover_get_phase_counts(h2mi_prover_t prover, h2mi_prover_phase_counts*
 int h2mi_prover_lookups(h2mi_prover_t prover, const uint64_t theta[4], uint64_t* points_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
   return guarded([&] { phase_lookups(*prover, theta, points_out); });  // theta compresses lookups given as expressions only
+}
+int h2mi_prover_check(h2mi_prover_t prover, const uint64_t theta[4], h2mi_check_failure* out, size_t cap, size_t* n_out) {
+  if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
+  if (!n_out || (cap && !out)) return H2MI_EINVAL;
+  *n_out = 0;
+  std::vector<h2mi_check_failure> found;
+  const int rc = guarded([&] { found = run_check(*prover, theta); });
+  if (rc) return rc;
+  *n_out = found.size();
+  for (size_t i = 0; i < found.size() && i < cap; i++) out[i] = found[i];
+  return found.empty() ? H2MI_OK : H2MI_EUNSAT;
 }
 int h2mi_prover_products(h2mi_prover_t prover, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* points_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;

@@ -27,6 +27,8 @@ later phase needs a column in the one before), `challenge_usable_after(phase)` (
 order), `query_challenge` -> an Expression of degree 0 that any gate and either side of any lookup may hold.  `Keys` then goes through
 h2mi_prover_keygen_phases, and `create_proof` takes synthesize(challenges) -> Assignment in place of an Assignment: it is called once
 per advice phase with the challenges squeezed so far, and only that phase's columns are taken from what it returns.
+`mock` is MockProver::run(..).assert_satisfied() on the host, row by row in Python integers; `check` asks the same question of the
+device, at the sizes the prover runs at (h2mi_prover_check: gates, copy constraints and lookups on the columns of a proof in flight).
 """
 from . import engine, flex
 from . import field as F
@@ -500,3 +502,27 @@ def create_proof(params: ParamsKZG, keys: Keys, asg, seed: int, transcript=None,
     if callable(asg):
         asg = _PhasedWitness(asg, len(keys.cs.challenge_phase))
     return flex.create_proof(params, keys, asg, seed, transcript=transcript, trace=trace, ws=ws)
+
+
+def check(params: ParamsKZG, keys: Keys, asg, seed: int = 1, ws: Workspace = None, trace: dict = None) -> None:
+    """`mock` on the device, at the sizes the prover runs at (h2mi_prover_check, include/h2mi_prover.h): the advice phase(s) with the
+    transcript exactly as create_proof starts — asg an Assignment or synthesize(challenges) — then the check, and the proof is dropped.
+    Raises ValueError in mock's words for the first violation (gates in create_gate order, then copy constraints, then lookups) with
+    the number of rows or cells that fail; the whole report is the exception's `failures`.  Unlike mock it tests the gates on the
+    blinding rows too: a gate that no selector switches off there fails at a row at or beyond the usable rows — the verifier looks
+    there as well."""
+    if callable(asg):
+        asg = _PhasedWitness(asg, len(keys.cs.challenge_phase))
+    failures = flex.device_check(params, keys, asg, seed, ws, trace)
+    cs = keys.cs
+    for f in failures:
+        if f.kind == engine.CHECK_GATE:
+            msg = f"gate {cs.gate_names[f.index]!r} not satisfied at row {f.row} ({f.count} rows)"
+        elif f.kind == engine.CHECK_COPY:
+            kind, column = cs.perm_columns[f.index]
+            msg = f"copy constraint at cell {(kind, column, f.row)} not satisfied ({f.count} cells differ from their copy)"
+        else:
+            msg = f"lookup {cs.lookup_names[f.index]!r} not satisfied at row {f.row} ({f.count} rows)"
+        e = ValueError(msg)
+        e.failures = failures
+        raise e

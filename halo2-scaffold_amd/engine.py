@@ -157,6 +157,31 @@ class AdvicePhases(C.Structure):
               "advice_phases_check")
 
 
+def shape_gate_program(cs: "ConstraintSystem", ops_cap: int = None, constants_cap: int = 0):
+    """h2mi_shape_gate_program (host only): the gate program equivalent to a hard-wired shape -> (ops [(op, index, rotation)], constants
+    [int]).  ops_cap / constants_cap: the buffers to offer (default: enough); H2miError(-6) when they are too small"""
+    cap = MAX_GATES * 10 if ops_cap is None else ops_cap
+    ops = (ExprOp * max(cap, 1))()
+    consts = np.zeros((max(constants_cap, 1), 4), dtype=np.uint64)
+    n_ops, n_constants = C.c_uint32(), C.c_uint32()
+    check(lib.h2mi_shape_gate_program(C.byref(cs), ops, cap, C.byref(n_ops), consts.ctypes.data, constants_cap, C.byref(n_constants)), "shape_gate_program")
+    return ([(o.op, o.index, o.rotation) for o in ops[:n_ops.value]], [F.fr_from_mont_limbs(consts[i]) for i in range(n_constants.value)])
+
+
+CHECK_GATE, CHECK_COPY, CHECK_LOOKUP = 0, 1, 2  # h2mi_check_failure.kind
+
+
+class CheckFailure(C.Structure):
+    """h2mi_check_failure: one entry of h2mi_prover_check's report"""
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("row", C.c_uint32), ("count", C.c_uint32)]
+
+    def __repr__(self):
+        return f"CheckFailure({('GATE', 'COPY', 'LOOKUP')[self.kind]}, index={self.index}, row={self.row}, count={self.count})"
+
+    def astuple(self):
+        return self.kind, self.index, self.row, self.count
+
+
 class ColumnCells(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("values", C.c_void_p), ("count", C.c_size_t), ("flags", C.c_uint32)]
 
@@ -345,12 +370,30 @@ class Prover:
             raise ValueError("lookup input not in the table (ConstraintSystemFailure)")
         check(rc, what)
 
-    def drive(self, advice, instance, seed: int, transcript: Blake2bWrite, trace: dict = None) -> None:
+    def check(self, theta=None, cap: int = 64) -> list:
+        """h2mi_prover_check on the proof in flight (after the last advice phase and set_challenges, before the products): -> the
+        failures [CheckFailure], empty for a witness that satisfies the circuit.  theta: 4 Montgomery limbs (an array) or an integer;
+        needed by a key whose lookups are a program.  Read-only: the proof goes on as if it had not been called."""
+        if theta is not None and not isinstance(theta, np.ndarray):
+            theta = F.fr_to_mont_limbs(theta)
+        theta = None if theta is None else np.ascontiguousarray(theta, dtype=np.uint64)
+        out, n = (CheckFailure * max(cap, 1))(), C.c_size_t()
+        rc = lib.h2mi_prover_check(self.handle, None if theta is None else theta.ctypes.data, out, cap, C.byref(n))
+        if rc != EUNSAT:
+            check(rc, "check")
+        if n.value > cap:
+            return self.check(theta, n.value)
+        return list(out[:n.value])
+
+    def drive(self, advice, instance, seed: int, transcript: Blake2bWrite, trace: dict = None, witness_check: str = None):
         """create_proof between the transcript's challenges.  advice: one {row: value} dict or dense list per advice column;
         instance: the public inputs (integers).  The caller has hashed vk.transcript_repr and the public inputs already.
         A key with several advice phases or with challenges: `advice` may be a callable, synthesize(challenges) -> such a list,
         called once per advice phase with the challenges known so far (integers; None for those not yet squeezed), of whose result
-        only that phase's columns are taken [RECALL halo2_proofs v2023_02_02 plonk/prover.rs]; a plain list serves every phase."""
+        only that phase's columns are taken [RECALL halo2_proofs v2023_02_02 plonk/prover.rs]; a plain list serves every phase.
+        witness_check: "only" — run the witness check (self.check with the transcript's theta) once the advice is committed and return its
+        failures without going on (the next proof starts at the advice as usual); "also" — run it and prove on: the bytes are those
+        of a proof without it.  Either way trace["check"] holds the failures."""
         c, h, pts = self.counts, self.handle, self._points
         pp = pts.ctypes.data
         sq = transcript.squeeze_challenge  # 4 Montgomery limbs
@@ -392,6 +435,13 @@ class Prover:
                 trace["challenges"] = list(known)
         mark("advice committed")
         theta = sq()  # drawn even without lookups
+        if witness_check is not None:
+            failures = self.check(theta)
+            mark("witness check")
+            if trace is not None:
+                trace["check"], trace["theta"] = failures, F.fr_from_mont_limbs(theta)
+            if witness_check == "only":
+                return failures
         if c.lookups:
             self._phase(lib.h2mi_prover_lookups(h, theta.ctypes.data, pp), "lookups")
             write_points(c.lookups)

@@ -422,3 +422,38 @@ def create_proof(params: ParamsKZG, pk: FlexKeys, asg: Assignment, seed: int, tr
     finally:
         if own:
             ws.release()
+
+
+def device_check(params: ParamsKZG, pk, asg, seed: int = 1, ws: FlexWorkspace = None, trace: dict = None) -> list:
+    """the witness check of include/h2mi_prover.h (h2mi_prover_check) on a proof that is started exactly as create_proof starts it
+    — the transcript, the advice phase(s), theta — and dropped behind the check: -> [engine.CheckFailure], empty for a witness that
+    satisfies the circuit.  What `mock` answers on the host, at the sizes the prover runs at; the advice commitments are paid."""
+    own = ws is None
+    ws = ws or FlexWorkspace(params, pk)
+    try:
+        transcript = Blake2bWrite.init()
+        transcript.common_scalar(_m(pk.transcript_repr))
+        for v in asg.instance:
+            transcript.common_scalar(_m(v))
+        return ws.prover.drive(asg.advice, asg.instance, seed, transcript, trace, witness_check="only")
+    finally:
+        if own:
+            ws.release()
+
+
+def check(params: ParamsKZG, pk: FlexKeys, asg: Assignment, seed: int = 1, ws: FlexWorkspace = None, trace: dict = None) -> None:
+    """`mock` on the device: raises ValueError in mock's words for the first violation (gates by gate column, then copy constraints,
+    then lookups), with the number of rows or cells that fail; the whole report is the exception's `failures`"""
+    failures = device_check(params, pk, asg, seed, ws, trace)
+    cs = pk.cs
+    for f in failures:
+        if f.kind == engine.CHECK_GATE:
+            msg = f"gate not satisfied at row {f.row}" + (f" of column {f.index}" if len(cs.col_qs) > 1 else "") + f" ({f.count} rows)"
+        elif f.kind == engine.CHECK_COPY:
+            kind, column = cs.perm_columns[f.index]
+            msg = f"copy constraint at cell {(kind, column, f.row)} not satisfied ({f.count} cells differ from their copy)"
+        else:
+            msg = f"lookup not satisfied at row {f.row}" + (f" of lookup column {f.index}" if cs.num_lookup_advice > 1 else "") + f" ({f.count} rows)"
+        e = ValueError(msg)
+        e.failures = failures
+        raise e

@@ -304,6 +304,35 @@ def expr_compress(program, advice, fixed, instance, k: int, domain_k: int, theta
                                             C.byref(program), k, domain_k, F.fr_to_mont_limbs(theta).ctypes.data, out.ptr, None), "expr_compress")
 
 
+def expr_check(program, advice, fixed, instance, k: int, n_rows: int = None, challenges=None):
+    """h2mi_plonk_expr_check_ch_dev: per polynomial of `program` (an engine.GateProgram) -> (the number of rows below n_rows on which it
+    is not zero, the smallest such row or 0xffffffff); columns on the 2^k rows as expr_compress takes them, n_rows = 2^k by default"""
+    ptrs = lambda cols: (C.c_void_p * max(len(cols), 1))(*[c.ptr if c is not None else None for c in cols])
+    ch = _challenge_limbs(challenges) if challenges else None
+    report = np.zeros((max(sum(1 for i in range(program.n_ops) if program.ops[i].op == 8), 1), 2), dtype=np.uint32)
+    n_polys = C.c_uint32()
+    _check(lib.h2mi_plonk_expr_check_ch_dev(ptrs(advice), len(advice), ptrs(fixed), len(fixed), instance.ptr if instance is not None else None,
+                                            C.byref(program), ch.ctypes.data if ch is not None else None, len(challenges) if challenges else 0, k,
+                                            (1 << k) if n_rows is None else n_rows, report.ctypes.data, C.byref(n_polys), None), "expr_check")
+    return [(int(c), int(f)) for c, f in report[: n_polys.value]]
+
+
+def copy_check(values, cells: DevBuf, n_cells: int):
+    """h2mi_plonk_copy_check_dev: values — the permutation argument's columns on the rows (DevBuf); cells — n_cells x 4 uint32 on the
+    device, (column, row, image column, image row) -> (unequal cells, the smallest index of one or 0xffffffff)"""
+    report = np.zeros(2, dtype=np.uint32)
+    ptrs = (C.c_void_p * max(len(values), 1))(*[v.ptr for v in values])
+    _check(lib.h2mi_plonk_copy_check_dev(ptrs, len(values), cells.ptr, n_cells, report.ctypes.data, None), "copy_check")
+    return int(report[0]), int(report[1])
+
+
+def lookup_member(inputs: DevBuf, sorted_canonical: DevBuf, n_unique: int, usable_rows: int):
+    """h2mi_plonk_lookup_member_dev -> (rows below usable_rows whose input is none of the n_unique sorted table values, the smallest)"""
+    report = np.zeros(2, dtype=np.uint32)
+    _check(lib.h2mi_plonk_lookup_member_dev(inputs.ptr, sorted_canonical.ptr, n_unique, usable_rows, report.ctypes.data, None), "lookup_member")
+    return int(report[0]), int(report[1])
+
+
 def sort_unique(values: DevBuf, count: int):
     """h2mi_fr_sort_unique_dev over the first `count` elements -> (canonical values, Montgomery values, u32 multiplicities, n_unique):
     the table arguments of h2mi_plonk_lookup_permute_dev"""

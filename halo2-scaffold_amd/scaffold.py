@@ -10,6 +10,8 @@ taken whenever LOOKUP_BITS is set, as in the reference.  Differences, by necessi
 public inputs; blinding comes from a fresh 256-bit key per prover (`h2mi_prover_set_rng_key`), standing where the reference passes
 `OsRng`.  Errors: an unsatisfied circuit raises ValueError from `mock` (MockProver's assert_satisfied), a lookup input outside the
 table raises ValueError from the prover (ConstraintSystemFailure), "LOOKUP_BITS needs to be less than DEGREE" is asserted as there.
+Added: `mock_device(f, private_inputs, pk)` — `mock` against a key `gen_key` made, on the device (flex.check): at DEGREE 20 - 22 the
+prover says nothing about an unsatisfied gate or copy constraint, and its proof would be accepted by no verifier.
 """
 import os
 
@@ -93,6 +95,17 @@ def prove_private(f, private_inputs, pk: ProvingKey, break_points):
         raise ValueError("the circuit's break points differ from the ones stored at keygen: the closure's shape depends on its inputs")
     pk.proofs += 1
     pk.last_proof = flex.create_proof(pk.params, pk.keys, asg, pk.proofs, ws=pk.workspace)  # the seed is the keyed stream's per-proof nonce
+    return list(asg.instance)
+
+
+def mock_device(f, private_inputs, pk: ProvingKey):
+    """`mock` at proving sizes: the witness of the private inputs checked on the device against the key `gen_key` made (flex.check:
+    gates, copy constraints, lookups; ValueError naming the first violation) -> the public inputs.  No proof is made and none is
+    verified; the advice commitments of the proof the check rides on are paid, and the nonce it takes is not used again."""
+    _, lookup_bits, _ = _env()
+    asg = _synthesize(f, private_inputs, pk.cs, lookup_bits)
+    pk.proofs += 1
+    flex.check(pk.params, pk.keys, asg, pk.proofs, ws=pk.workspace)
     return list(asg.instance)
 
 

@@ -491,6 +491,30 @@ int h2mi_plonk_expr_compress_ch_dev(const void* const* d_advice, uint32_t n_advi
                                     const void* d_instance, const h2mi_gate_program* exprs, const uint64_t* challenges, uint32_t n_challenges,
                                     uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out, h2mi_stream_t stream);
 
+/* ---- the witness check on the rows (what MockProver::run(..).assert_satisfied() answers on the host): does a witness satisfy the
+ * circuit, and where not?  Three calls over Lagrange-row columns; each returns when its report is on the host.  h2mi_prover_check
+ * (h2mi_prover.h) runs them on the columns of a proof in flight.
+ * Polynomials: `polys` holds n polynomials (any program the calls above take: the same interpreter, the same uploader, the same
+ * refusals; columns on the 2^k rows, rotations modulo 2^k).  report_out receives, per polynomial in program order, {the number of
+ * rows i < n_rows on which it is not zero modulo r, the smallest such row or 0xffffffff}: 2 uint32 per polynomial, HOST memory, room
+ * for every END of the program; n_polys_out (may be NULL) their number.  n_rows in [1, 2^k]: rows at or beyond it are not tested but
+ * are read by rotations.  A satisfied witness costs no atomic operation. */
+int h2mi_plonk_expr_check_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
+                                 const void* d_instance, const h2mi_gate_program* polys, const uint64_t* challenges, uint32_t n_challenges,
+                                 uint32_t k, uint32_t n_rows, uint32_t* report_out /* host, n_polys x 2 */, uint32_t* n_polys_out,
+                                 h2mi_stream_t stream);
+/* Copy constraints: d_cells holds n_cells x 4 uint32 in DEVICE memory, {column, row, image column, image row} per cell that the
+ * permutation moves, columns as indices into d_values (m <= H2MI_FLEX_MAX_PERM Lagrange-row columns, the permutation argument's order)
+ * — trusted like the active rows of h2mi_plonk_permutation_products_sparse_dev: every column below m, every row inside its column.
+ * report_out (host) = {cells whose value differs from their image's, the smallest index of such a cell in d_cells or 0xffffffff}. */
+int h2mi_plonk_copy_check_dev(const void* const* d_values, uint32_t m, const void* d_cells, uint32_t n_cells, uint32_t report_out[2],
+                              h2mi_stream_t stream);
+/* Lookup membership: report_out (host) = {rows i < usable_rows whose d_input[i] (Montgomery) is none of the n_unique ascending
+ * canonical values of d_table_sorted (h2mi_fr_sort_unique_dev's first output, or a key's table), the smallest such row or 0xffffffff}.
+ * h2mi_plonk_lookup_permute_dev counts the same rows but cannot say which. */
+int h2mi_plonk_lookup_member_dev(const void* d_input, const void* d_table_sorted, uint32_t n_unique, uint32_t usable_rows, uint32_t report_out[2],
+                                 h2mi_stream_t stream);
+
 /* ---- SRS generation helper: ParamsKZG::setup's g[i] = s_i * G   ------------------
  * d_scalars: n Fr (Montgomery).  d_out_affine: n G1Affine.  Fixed-base windowed multiplication of the
  * generator (1, 2) with on-device normalisation. */

@@ -602,5 +602,26 @@ inline void create_proof(const poly::kzg::ParamsKZG& params, const FlexKeys& pk,
   plonk::drive_proof(*workspace, advice, asg.instance, seed, tr);
 }
 
+// `mock` on the device, at the sizes the prover runs at: the advice phase with the transcript exactly as create_proof starts, then
+// h2mi_prover_check (plonk::check_witness), and the proof is dropped.  Throws Error(H2MI_EUNSAT) naming the first violation — a gate column's
+// polynomial and row, a copied cell, a lookup and row.  No proof is made and nothing is verified.
+inline void check(const poly::kzg::ParamsKZG& params, const FlexKeys& pk, const Assignment& asg, uint64_t seed = 1, FlexWorkspace* workspace = nullptr) {
+  std::unique_ptr<FlexWorkspace> own;
+  if (!workspace) {
+    own.reset(new FlexWorkspace(params, pk));
+    workspace = own.get();
+  }
+  transcript::Blake2bWrite tr;
+  tr.common_scalar(pk.vk.transcript_repr);
+  for (const Fr& v : asg.instance) tr.common_scalar(v);
+  std::vector<h2mi_column_cells> advice;
+  for (const std::vector<Fr>& col : asg.advice) advice.push_back({nullptr, (const uint64_t*)col.data(), col.size(), 0});
+  std::vector<G1Affine> pts(std::max(workspace->counts.advice, 1u));
+  h2mi::check(h2mi_prover_advice(workspace->prover, advice.data(), (const uint64_t*)asg.instance.data(), asg.instance.size(), seed, (uint64_t*)pts.data()), "advice");
+  for (uint32_t i = 0; i < workspace->counts.advice; i++) tr.write_point(pts[i]);
+  const Fr theta = tr.squeeze_challenge();
+  plonk::check_witness(*workspace, &theta);
+}
+
 }  // namespace flex
 }  // namespace h2mi

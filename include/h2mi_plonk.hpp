@@ -261,6 +261,31 @@ inline void drive_proof(ProverWorkspace& ws, const std::vector<h2mi_column_cells
   mark(6);
 }
 
+// The witness check beside the phase calls (h2mi_prover_check: after the advice, before the products; `check` is the error helper
+// of h2mi.hpp, hence the longer names): -> the failures, empty for a
+// witness that satisfies the circuit.  theta: the transcript's, or any random value; read only by a key whose lookups are a program.
+// The proof in flight goes on as if the call had not been made.
+inline std::vector<h2mi_check_failure> check_report(ProverWorkspace& ws, const Fr* theta = nullptr) {
+  std::vector<h2mi_check_failure> out(16);
+  size_t n = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    const int rc = h2mi_prover_check(ws.prover, theta ? theta->l : nullptr, out.data(), out.size(), &n);
+    if (rc != H2MI_EUNSAT) check(rc, "check");
+    if (n <= out.size()) break;
+    out.resize(n);
+  }
+  out.resize(n);
+  return out;
+}
+// ... throwing Error(H2MI_EUNSAT) that names the first failure: the gate polynomial and row, the copied cell, the lookup and row
+inline void check_witness(ProverWorkspace& ws, const Fr* theta = nullptr) {
+  const std::vector<h2mi_check_failure> f = check_report(ws, theta);
+  if (f.empty()) return;
+  const char* what = f[0].kind == H2MI_CHECK_GATE ? "check: gate polynomial " : f[0].kind == H2MI_CHECK_COPY ? "check: copy constraint at permutation column " : "check: lookup ";
+  throw Error(H2MI_EUNSAT, what + std::to_string(f[0].index) + " not satisfied at row " + std::to_string(f[0].row) + " (" + std::to_string(f[0].count) +
+                               (f[0].kind == H2MI_CHECK_COPY ? " cells, " : " rows, ") + std::to_string(f.size()) + " failures in all)");
+}
+
 // ---- create_proof ---------------------------------------------------------------------------------------------------
 inline void create_proof(const poly::kzg::ParamsKZG& params, const ProvingKey& pk, const StandardPlonk& circuit, uint64_t seed,
                          transcript::Blake2bWrite& tr, ProverWorkspace* workspace = nullptr) {

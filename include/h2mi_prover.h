@@ -140,6 +140,17 @@ int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_han
  * verifier could check the proof otherwise), and every polynomial's degree (a query 1, a constant 0; ADD / SUB the larger, MUL the
  * sum) is at most cs->degree.  It reports the largest polynomial degree and the deepest stack (either pointer may be NULL). */
 int h2mi_gate_program_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint32_t* degree_out, uint32_t* max_stack_out);
+/* The gate program equivalent to a hard-wired shape (host only, works without a GPU): for cs->gates == H2MI_GATES_STANDARD_PLONK the one
+ * polynomial q_a a + q_b b + q_c c + q_ab a b + constant over advice 0..2 and fixed 0..4; for H2MI_GATES_FLEX_VERTICAL one polynomial
+ * q_g (a + a(wX) a(w^2 X) - a(w^3 X)) per gate column g < cs->n_gates over (cs->gate_advice[g], cs->gate_selector[g]), in
+ * evaluate_h's order.  Only cs->gates, n_gates, gate_advice and gate_selector are read.  The ops are written to `ops` (room for
+ * ops_cap; H2MI_SHAPE_PROGRAM_MAX_OPS always suffices) and the constants to `constants` (constants_cap x 4 limbs; neither shape has
+ * any today, so NULL / 0 is accepted); the counts go to n_ops_out / n_constants_out in every case, and H2MI_ERANGE says that a buffer
+ * was too small and nothing was written.  H2MI_EINVAL for H2MI_GATES_EXPRESSIONS (the caller holds that program) or an unknown shape.
+ * This is the program h2mi_prover_check runs for a key of those shapes, built once at keygen. */
+#define H2MI_SHAPE_PROGRAM_MAX_OPS (10 * H2MI_MAX_GATES)
+int h2mi_shape_gate_program(const h2mi_constraint_system* cs, h2mi_expr_op* ops, uint32_t ops_cap, uint32_t* n_ops_out, uint64_t* constants,
+                            uint32_t constants_cap, uint32_t* n_constants_out);
 int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint64_t g_lagrange_handle,
                              const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
 /* Lookups as a program beside the constraint system: `meta.lookup(|meta| vec![(input, table), ..])` with any expressions on both sides,
@@ -244,6 +255,32 @@ int h2mi_prover_advice_phase(h2mi_prover_t prover, uint32_t phase, const h2mi_co
  * challenges — the next phase is H2MI_EINVAL without it.  The library reads them in the lookups' compression and in the quotient;
  * witness generation, which reads them first, is the caller's. */
 int h2mi_prover_set_challenges(h2mi_prover_t prover, const uint64_t* values);
+/* The witness check, on the device at proving sizes: does the witness of the proof in flight satisfy the circuit, and where not?  What
+ * MockProver::run(..).assert_satisfied() answers on the host; NOT a verification of anything (there is no verifier in this library).
+ * When: after the last advice phase — on a key with challenges also after h2mi_prover_set_challenges — and before
+ * h2mi_prover_products; at any other time H2MI_EINVAL.  The call is optional and read-only: phase state, buffers and blinding streams,
+ * and therefore every byte of the proof, are the same with or without it, and no return value abandons the proof.  It runs behind the
+ * advice fill on the library stream, on scratch of its own (allocated by the first call), and returns when the report is on the host.
+ * H2MI_OK: nothing to report.  H2MI_EUNSAT: *n_out failures, the first `cap` of them written to `out`, in this order:
+ *   H2MI_CHECK_GATE    per gate polynomial that is not zero somewhere: index = the polynomial in program order (a key of a hard-wired
+ *                      shape: the program of h2mi_shape_gate_program), row = the smallest failing row, count = the failing rows.  All 2^k
+ *                      rows of the BLINDED columns are tested — the condition under which the quotient is a polynomial.  A first row at
+ *                      or beyond 2^k - blinding_factors - 1 says that the gate is not switched off on the blinding rows: MockProver does
+ *                      not look there, the verifier does.
+ *   H2MI_CHECK_COPY    at most one: count = the cells whose value differs from the cell the permutation maps them to, (index, row) = the
+ *                      smallest such cell, index its column in the permutation argument's order.
+ *   H2MI_CHECK_LOOKUP  per failing lookup: index = the lookup, row = the smallest usable row whose input is not a table value on a
+ *                      usable row, count = such rows.  Lookups given as a program: both sides are compressed with `theta` on the rows and
+ *                      the table side sorted, as the lookups phase does; theta must not be NULL and may be the transcript's or any
+ *                      random value — two different tuples among u rows of m expressions collide, and hide a failure, with probability
+ *                      about u^2 m / r (below 2^-190 at 2^28 rows).  The single-expression lookups compare q * a (or the column) with
+ *                      the key's keygen-sorted table and ignore theta.
+ * Multi-device modes: the vectors are on the primary device, as for the lookups. */
+#define H2MI_CHECK_GATE 0u
+#define H2MI_CHECK_COPY 1u
+#define H2MI_CHECK_LOOKUP 2u
+typedef struct { uint32_t kind /* H2MI_CHECK_* */, index, row, count; } h2mi_check_failure;
+int h2mi_prover_check(h2mi_prover_t prover, const uint64_t theta[4], h2mi_check_failure* out, size_t cap, size_t* n_out);
 /* theta compresses the lookups of a key made by h2mi_prover_keygen_exprs (each side's expressions folded with it on the rows, the
  * table's usable rows sorted on the device); the single-expression lookups do not use it.
  * points_out: per lookup the permuted input, then the permuted table commitment (2 x n_lookups; nothing without lookups — the call
