@@ -6,6 +6,7 @@ quotient identity evaluated at a fresh random point with the device's eval_polyn
 import numpy as np
 import pytest
 
+import perm_scale_cases
 from oracle import bn254 as o
 from oracle import plonk as P
 from oracle import prover as OP
@@ -230,19 +231,8 @@ def test_permutation_products_all_sets_match_formula(gpu, k, m, chunk):
         vals[j2][i2] = vals[j1][i1]  # equal cells, so the product still telescopes where it should
     beta, gamma = 0xBEEF + k, 0xCAFE
     sets = -(-m // chunk)
-    want = []
-    start = 1
-    for s in range(sets):
-        z = [0xDEAD] * n
-        z[0] = start
-        for i in range(u):
-            num = den = 1
-            for j in range(s * chunk, min(m, (s + 1) * chunk)):
-                num = num * ((vals[j][i] + beta * ident(j, i) + gamma) % o.R) % o.R
-                den = den * ((vals[j][i] + beta * sig[j][i] + gamma) % o.R) % o.R
-            z[i + 1] = z[i] * num % o.R * pow(den, -1, o.R) % o.R
-        start = z[u]
-        want.append(z)
+    want = perm_scale_cases.formula_products(k, u, chunk, vals, sig, beta, gamma, sentinel=0xDEAD)  # row by row, 0xDEAD beyond row u
+    assert len(want) == sets
     dv = [gpu.DevBuf.from_numpy(o.pack(v, o.R)) for v in vals]
     ds = [gpu.DevBuf.from_numpy(o.pack(v, o.R)) for v in sig]
     dz = [gpu.DevBuf.from_numpy(o.pack([0xDEAD] * n, o.R)) for _ in range(sets)]
