@@ -102,6 +102,8 @@ def _load():
         "h2mi_plonk_evaluate_h_expr_dev": ([vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_expr_compress_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_expr_ch_dev": ([vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "h2mi_plonk_evaluate_h_expr_batch_dev": ([vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+                                                 C.c_int),
         "h2mi_plonk_expr_compress_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_expr_check_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32), vp],
                                          C.c_int),
@@ -144,6 +146,13 @@ def _load():
         "h2mi_prover_evaluations": ([vp, vp, vp], C.c_int),
         "h2mi_prover_shplonk_quotient": ([vp, vp, vp, vp], C.c_int),
         "h2mi_prover_shplonk_open": ([vp, vp, vp], C.c_int),
+        "h2mi_batch_create": ([vp, C.c_uint32, C.POINTER(vp)], C.c_int),
+        "h2mi_batch_destroy": ([vp], C.c_int),
+        "h2mi_batch_quotient": ([vp, vp, vp], C.c_int),
+        "h2mi_batch_num_evaluations": ([vp, C.POINTER(sz)], C.c_int),
+        "h2mi_batch_evaluations": ([vp, vp, vp], C.c_int),
+        "h2mi_batch_shplonk_quotient": ([vp, vp, vp, vp], C.c_int),
+        "h2mi_batch_shplonk_open": ([vp, vp, vp], C.c_int),
         "h2mi_prover_buffer": ([vp, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(sz)], C.c_int),
         "h2mi_prover_pk_buffer": ([vp, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(sz)], C.c_int),
     }

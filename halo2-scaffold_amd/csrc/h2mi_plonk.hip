@@ -482,18 +482,22 @@ __device__ __forceinline__ f29 sub(const f29& a, const f29& b) { return f29_norm
 __device__ __forceinline__ f29 red(const f29& a) { return f29_mul<F9>(a, f29_const<F9>(F9::ONE)); }                       // back below 1.1 p (ONE = 2^261 mod p)
 __device__ __forceinline__ void horner(f29& acc, const f29& y, const f29& term) { acc = add(mul(acc, y), term); }
 }  // namespace gen
-// What follows the gate terms in evaluate_h's order — the permutation argument (chunks of any length), then the lookups — folded into
-// `acc` by Horner's rule in y, times t_inv, stored: the tail k_evaluate_h_flex and k_evaluate_h_expr share.
-__device__ __forceinline__ void evaluate_h_tail(const FlexCosets& c, uint32_t ext_k, uint32_t k, uint32_t last_rot, const FlexConsts& h, const fe* xlo,
-                                                const fe* xhi, uint32_t xh, uint32_t idx, f29 acc, const f29& y, fe* out) {
+// What follows ONE circuit's gate terms in evaluate_h's order — the permutation argument (chunks of any length), then the lookups —
+// folded into `acc` by Horner's rule in y: the body k_evaluate_h_flex, k_evaluate_h_expr and k_evaluate_h_expr_batch share.  `sh` holds
+// what every circuit of a proof shares (the counts, the sigma cosets, l_0 / l_last / l_active), `c` what belongs to the circuit (the
+// permuted columns' values, the grand products, the six vectors of each lookup): a single-circuit kernel passes its FlexCosets as both,
+// the batch kernel its arguments and one CircuitCosets record in device memory.
+template <class Circuit>
+__device__ __forceinline__ void evaluate_h_fold(const Circuit& c, const FlexCosets& sh, uint32_t ext_k, uint32_t k, uint32_t last_rot, const FlexConsts& h,
+                                                const fe* xlo, const fe* xhi, uint32_t xh, uint32_t idx, f29& acc, const f29& y) {
   using namespace gen;
   const uint32_t size = 1u << ext_k, rot = 1u << (ext_k - k);
   auto at = [&](int r) { return (idx + size + (uint32_t)(r * (int)rot)) & (size - 1); };
   const uint32_t r_next = at(1), r_prev = at(-1), r_last = at(-(int)last_rot);
   const f29 one = f29_const<F9>(F9::ONE), beta = cst(h.beta), gamma = cst(h.gamma), delta = cst(h.delta);
-  const f29 l0 = ld(&c.l0[idx]), ll = ld(&c.l_last[idx]), lact = ld(&c.l_active[idx]);
-  if (c.n_perm) {
-    const uint32_t sets = (c.n_perm + c.chunk - 1) / c.chunk;
+  const f29 l0 = ld(&sh.l0[idx]), ll = ld(&sh.l_last[idx]), lact = ld(&sh.l_active[idx]);
+  if (sh.n_perm) {
+    const uint32_t sets = (sh.n_perm + sh.chunk - 1) / sh.chunk;
     const f29 z_first = ld(&c.perm_z[0][idx]), z_lastset = ld(&c.perm_z[sets - 1][idx]);
     horner(acc, y, mul(sub(one, z_first), l0));
     horner(acc, y, mul(red(sub(mul(z_lastset, z_lastset), z_lastset)), ll));
@@ -501,17 +505,17 @@ __device__ __forceinline__ void evaluate_h_tail(const FlexCosets& c, uint32_t ex
     f29 cur = mul(mul(pow2tab(xlo, xhi, xh, idx), cst(h.zeta)), beta);  // beta * X, X = zeta * extended_omega^idx
     for (uint32_t s = 0; s < sets; s++) {
       f29 left = ld(&c.perm_z[s][r_next]), right = ld(&c.perm_z[s][idx]);
-      const uint32_t j0 = c.chunk * s, j1 = min(c.n_perm, c.chunk * (s + 1));
+      const uint32_t j0 = sh.chunk * s, j1 = min(sh.n_perm, sh.chunk * (s + 1));
       for (uint32_t j = j0; j < j1; j++) {
         const f29 val = ld(&c.perm_value[j][idx]);
-        left = mul(left, add(add(val, mul(beta, ld(&c.perm_sigma[j][idx]))), gamma));
+        left = mul(left, add(add(val, mul(beta, ld(&sh.perm_sigma[j][idx]))), gamma));
         right = mul(right, add(add(val, cur), gamma));
         cur = mul(cur, delta);
       }
       horner(acc, y, mul(sub(left, right), lact));
     }
   }
-  for (uint32_t l = 0; l < c.n_lookups; l++) {
+  for (uint32_t l = 0; l < sh.n_lookups; l++) {
     f29 a_in = ld(&c.lk_in[l][idx]);
     if (c.lk_in_b[l]) a_in = mul(a_in, ld(&c.lk_in_b[l][idx]));
     const f29 t_in = ld(&c.lk_table[l][idx]), ap = ld(&c.lk_pin[l][idx]), ap_prev = ld(&c.lk_pin[l][r_prev]), sp = ld(&c.lk_ptab[l][idx]);
@@ -524,9 +528,20 @@ __device__ __forceinline__ void evaluate_h_tail(const FlexCosets& c, uint32_t ex
     horner(acc, y, mul(d, l0));
     horner(acc, y, mul(red(mul(d, sub(ap, ap_prev))), lact));
   }
+}
+// the division by X^n - 1 behind the LAST circuit's terms, and the one store
+__device__ __forceinline__ void evaluate_h_finish(const f29& acc, uint32_t ext_k, uint32_t k, const FlexConsts& h, uint32_t idx, fe* out) {
+  using namespace gen;
+  const uint32_t rot = 1u << (ext_k - k);
   fe o;
   f29_to_mont256<F9>(mul(acc, cst(h.tinv[idx & (rot - 1)])), o.v);
   fe_store(&out[idx], o);
+}
+// one circuit: its terms, then the finish
+__device__ __forceinline__ void evaluate_h_tail(const FlexCosets& c, uint32_t ext_k, uint32_t k, uint32_t last_rot, const FlexConsts& h, const fe* xlo,
+                                                const fe* xhi, uint32_t xh, uint32_t idx, f29 acc, const f29& y, fe* out) {
+  evaluate_h_fold(c, c, ext_k, k, last_rot, h, xlo, xhi, xh, idx, acc, y);
+  evaluate_h_finish(acc, ext_k, k, h, idx, out);
 }
 __global__ void __launch_bounds__(256) k_evaluate_h_flex(FlexCosets c, uint32_t ext_k, uint32_t k, uint32_t last_rot, FlexConsts h, const fe* xlo,
                                                           const fe* xhi, uint32_t xh, fe* out) {
@@ -616,6 +631,42 @@ __global__ void __launch_bounds__(256) k_evaluate_h_expr(FlexCosets c, const fe*
   f29 acc = f29_zero();
   expr_interpret(cols, consts, ops, n_ops, idx, size, ex_stack, [&](const f29& poly) { horner(acc, y, poly); });
   evaluate_h_tail(c, ext_k, k, last_rot, h, xlo, xhi, xh, idx, acc, y, out);
+}
+// Several circuits in one proof [RECALL halo2_proofs v2023_02_02 plonk/evaluation.rs evaluate_h: ONE `values` vector walks the circuits
+// in order, per circuit values = values y + term over its gates, its permutation terms, its lookup terms; the division by X^n - 1
+// comes behind the last circuit].  The accumulator stays in registers across the circuits: one t_inv multiplication and one store per
+// point, where a chain of single launches with a carry-in would read and write h once per circuit.  Program, constants and challenges
+// are the proof's; what differs per circuit is pointers, and those sit in device memory as consecutive records behind the program (a
+// table indexed by a loaded value does not belong in the launch's arguments, see k_copy_check).  The circuit counter does not depend
+// on the lane: a record's pointers arrive by scalar loads at uniform addresses, as the ops do.
+struct CircuitCosets {
+  const fe* cols[EX_COLS];  // the interpreter's table: advice, fixed, the instance column
+  const fe* perm_value[H2MI_FLEX_MAX_PERM];
+  const fe* perm_z[H2MI_FLEX_MAX_PERM];
+  const fe* lk_in[H2MI_FLEX_MAX_LOOKUPS];
+  const fe* lk_in_b[H2MI_FLEX_MAX_LOOKUPS];
+  const fe* lk_table[H2MI_FLEX_MAX_LOOKUPS];
+  const fe* lk_pin[H2MI_FLEX_MAX_LOOKUPS];
+  const fe* lk_ptab[H2MI_FLEX_MAX_LOOKUPS];
+  const fe* lk_z[H2MI_FLEX_MAX_LOOKUPS];
+};
+__global__ void __launch_bounds__(256) k_evaluate_h_expr_batch(FlexCosets sh, const CircuitCosets* __restrict__ circuits, uint32_t n_circuits,
+                                                                const fe* __restrict__ consts, const uint2* __restrict__ ops, uint32_t n_ops,
+                                                                uint32_t ext_k, uint32_t k, uint32_t last_rot, FlexConsts h, const fe* xlo,
+                                                                const fe* xhi, uint32_t xh, fe* out) {
+  using namespace gen;
+  extern __shared__ uint32_t ex_stack[];  // [level][limb][thread]
+  const uint32_t size = 1u << ext_k;
+  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= size) return;  // no barrier below
+  const f29 y = cst(h.y);
+  f29 acc = f29_zero();
+  for (uint32_t i = 0; i < n_circuits; i++) {
+    const CircuitCosets& c = circuits[i];
+    expr_interpret(c.cols, consts, ops, n_ops, idx, size, ex_stack, [&](const f29& poly) { horner(acc, y, poly); });
+    evaluate_h_fold(c, sh, ext_k, k, last_rot, h, xlo, xhi, xh, idx, acc, y);
+  }
+  evaluate_h_finish(acc, ext_k, k, h, idx, out);
 }
 // The lookup argument's theta compression (plonk/lookup/prover.rs commit_permuted `compress_expressions`, plonk/evaluation.rs for
 // the extended coset [RECALL]): out[i] = sum_j e_j(i) theta^(m-1-j), the fold acc theta + e_j over the program's m polynomials, on
@@ -1253,6 +1304,81 @@ int h2mi_plonk_evaluate_h_expr_ch_dev(const h2mi_expr_cosets* c, const h2mi_gate
   H2_LAUNCH("k_evaluate_h_expr", k_evaluate_h_expr, ceil_div_u32(size, 256), 256, im.lds, s, fc, (const fe* const*)d_image, (const fe*)(d_image + im.cols_fe),
             (const uint2*)(d_image + im.cols_fe + im.const_fe), im.n_ops, extended_k, k, blinding_factors + 1, hc_, (const fe*)px.lo,
             (const fe*)px.hi, px.h, (fe*)d_h_out);
+  return release_tmp(s);
+}
+
+int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_expr_cosets* circuits, uint32_t n_circuits, const h2mi_gate_program* gates, const uint64_t* challenges,
+                                         uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
+                                         const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
+                                         const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!circuits || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
+  if (n_circuits == 0 || n_circuits > H2MI_MAX_CIRCUITS) return H2MI_EINVAL;
+  if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  const h2mi_expr_cosets& c0 = circuits[0];
+  if (c0.n_perm > H2MI_FLEX_MAX_PERM || c0.n_lookups > H2MI_FLEX_MAX_LOOKUPS || (c0.n_perm && c0.chunk_len == 0)) return H2MI_EINVAL;
+  // the program, its constants and the challenges once, as the single-circuit call lays them out (the image's own column table is
+  // circuit 0's and is not read here); the circuits' records behind it
+  ExprImage im;
+  int rc = im.build(gates, challenges, n_challenges, c0.advice, c0.fixed, c0.instance, k, extended_k);
+  if (rc) return rc;
+  static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
+  static_assert(sizeof(CircuitCosets) % 8 == 0, "records are arrays of pointers");
+  FlexCosets sh;
+  memset(&sh, 0, sizeof(sh));
+  if (!fill_tail(sh, c0)) return H2MI_EINVAL;
+  const size_t rec_fe = (sizeof(CircuitCosets) + sizeof(fe) - 1) / sizeof(fe), prog_fe = im.image.size();
+  im.image.resize(prog_fe + rec_fe * n_circuits);
+  for (uint32_t i = 0; i < n_circuits; i++) {
+    const h2mi_expr_cosets& c = circuits[i];
+    if (c.n_perm != c0.n_perm || c.chunk_len != c0.chunk_len || c.n_lookups != c0.n_lookups) return H2MI_EINVAL;
+    FlexCosets fc;
+    memset(&fc, 0, sizeof(fc));
+    if (!fill_tail(fc, c)) return H2MI_EINVAL;
+    // what the proof shares is read from entry 0: an entry that names other sigma or Lagrange cosets is a caller's mistake
+    if (memcmp(fc.perm_sigma, sh.perm_sigma, sizeof(fc.perm_sigma)) || fc.l0 != sh.l0 || fc.l_last != sh.l_last || fc.l_active != sh.l_active) return H2MI_EINVAL;
+    if (i) {  // every column the program reads is there (entry 0: im.build above)
+      rc = expr_walk(gates, k, n_challenges, [&](uint32_t kind, uint32_t index, int32_t) {
+        return kind == H2MI_EXPR_ADVICE ? index < H2MI_EXPR_MAX_ADVICE && c.advice[index]
+             : kind == H2MI_EXPR_FIXED  ? index < H2MI_EXPR_MAX_FIXED && c.fixed[index]
+                                        : index == 0 && c.instance;
+      }, nullptr);
+      if (rc) return rc;
+    }
+    CircuitCosets rec;
+    memset(&rec, 0, sizeof(rec));
+    for (uint32_t j = 0; j < H2MI_EXPR_MAX_ADVICE; j++) rec.cols[j] = (const fe*)c.advice[j];
+    for (uint32_t j = 0; j < H2MI_EXPR_MAX_FIXED; j++) rec.cols[H2MI_EXPR_MAX_ADVICE + j] = (const fe*)c.fixed[j];
+    rec.cols[EX_COLS - 1] = (const fe*)c.instance;
+    memcpy(rec.perm_value, fc.perm_value, sizeof(rec.perm_value));
+    memcpy(rec.perm_z, fc.perm_z, sizeof(rec.perm_z));
+    memcpy(rec.lk_in, fc.lk_in, sizeof(rec.lk_in));
+    memcpy(rec.lk_in_b, fc.lk_in_b, sizeof(rec.lk_in_b));
+    memcpy(rec.lk_table, fc.lk_table, sizeof(rec.lk_table));
+    memcpy(rec.lk_pin, fc.lk_pin, sizeof(rec.lk_pin));
+    memcpy(rec.lk_ptab, fc.lk_ptab, sizeof(rec.lk_ptab));
+    memcpy(rec.lk_z, fc.lk_z, sizeof(rec.lk_z));
+    memcpy((char*)&im.image[prog_fe] + sizeof(CircuitCosets) * i, &rec, sizeof(rec));
+  }
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  CallScope scope_;
+  hipStream_t s = pick_stream(stream);
+  PowTab px;
+  rc = get_powtab(extended_omega, extended_k, s, &px);
+  if (rc) return rc;
+  rc = ensure_tmp(im.image.size(), s);
+  if (rc) return rc;
+  fe* d_image = tmp_base();
+  H2_HIP(hipMemcpyAsync(d_image, im.image.data(), im.image.size() * sizeof(fe), hipMemcpyHostToDevice, s));
+  const uint32_t rot = 1u << (extended_k - k);
+  FlexConsts hc_;
+  memset(&hc_, 0, sizeof(hc_));
+  hc_.beta = host_fe(beta); hc_.gamma = host_fe(gamma); hc_.y = host_fe(y); hc_.delta = host_fe(delta); hc_.zeta = host_fe(zeta);
+  for (uint32_t i = 0; i < rot; i++) hc_.tinv[i] = host_fe(t_inv + 4 * i);
+  const uint32_t size = 1u << extended_k;
+  H2_LAUNCH("k_evaluate_h_expr_batch", k_evaluate_h_expr_batch, ceil_div_u32(size, 256), 256, im.lds, s, sh, (const CircuitCosets*)(d_image + prog_fe),
+            n_circuits, (const fe*)(d_image + im.cols_fe), (const uint2*)(d_image + im.cols_fe + im.const_fe), im.n_ops, extended_k, k,
+            blinding_factors + 1, hc_, (const fe*)px.lo, (const fe*)px.hi, px.h, (fe*)d_h_out);
   return release_tmp(s);
 }
 

@@ -303,7 +303,7 @@ struct h2mi_pk_s {
 namespace {
 
 std::mutex g_reg_mu;
-std::set<const void*> g_live_pks, g_live_provers;
+std::set<const void*> g_live_pks, g_live_provers, g_live_batches;
 template <class T>
 bool alive(const std::set<const void*>& s, T p) {
   std::lock_guard<std::mutex> lk(g_reg_mu);
@@ -601,10 +601,16 @@ enum Phase { IDLE = 0, ADVICE, LOOKUPS, PRODUCTS, QUOTIENT, EVALUATIONS, SHPLONK
 
 }  // namespace
 
+struct h2mi_batch_s;
+
 struct h2mi_prover_s {
   h2mi_pk_s* pk;
   uint64_t g, gl;
   size_t lo, cnt;
+  // several circuits per proof: the batch this prover is bound into and its place there.  Member 0 leads: the proof's one random
+  // polynomial, h, the evaluations and SHPLONK's vectors, the result slots and the combiner of the joint phases are its own
+  h2mi_batch_s* batch = nullptr;
+  uint32_t batch_index = 0;
   // sliced SRS
   void *d_partial = nullptr, *d_combined = nullptr;
   h2mi_combine_fn combine = nullptr;
@@ -713,13 +719,25 @@ struct h2mi_prover_s {
   std::vector<Fr> blinding(uint32_t purpose, size_t count) const {
     return keyed ? chacha_fr(key, (seed << 3) | purpose, count) : uniform_fr(seed + purpose, count);
   }
+  // one random polynomial per proof: a bound member behind the first neither draws nor commits one
+  bool draws_random() const { return !batch || batch_index == 0; }
   void random_vector(uint32_t purpose, DeviceVec& out, size_t count) const {
     if (keyed) check(h2mi_fr_random_chacha_dev(out.p, count, key, (seed << 3) | purpose, 0, nullptr), "random_poly");
     else check(h2mi_fr_random_dev(out.p, count, seed + purpose, 0, nullptr), "random_poly");
   }
 };
 
+// N provers over one key whose circuits go into ONE proof (h2mi_batch_create).  The per-circuit phases stay on the members; the joint
+// phases run over `members` in order with members[0] leading, and their phase state is the leader's (PRODUCTS -> QUOTIENT ->
+// EVALUATIONS -> SHPLONK_Q -> IDLE) while the others wait in PRODUCTS
+struct h2mi_batch_s {
+  std::vector<h2mi_prover_s*> members;
+};
+
 namespace {
+
+// the circuits of one proof, in order; [0] leads.  A prover outside a batch is the list of length one
+typedef std::vector<h2mi_prover_s*> Circuits;
 
 // commitments of the largest phase: the result slots a prover (and a combiner's two buffers) must hold
 uint32_t max_phase_points(const h2mi_pk_s& pk) {
@@ -1004,8 +1022,11 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
   p.gamma = gamma;
   // the random polynomial's commitment is written after the grand products' but depends on nothing: queued first, the one dense
   // MSM of this phase accumulates beside their latency-bound scans.  Result slot: where the transcript expects it.
-  p.random_vector(3, *p.random_poly, n);
-  p.commit(false, p.col(*p.random_poly), n_sets + L);
+  const bool random = p.draws_random();
+  if (random) {
+    p.random_vector(3, *p.random_poly, n);
+    p.commit(false, p.col(*p.random_poly), n_sets + L);
+  }
   // permutation argument: every set in one device pass, over the copy constraints' support when that is sparse
   const bool perm_sparse = (uint64_t)pk.n_active * 8 <= (uint64_t)n_sets * u;
   if (m) {
@@ -1045,7 +1066,7 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
     check(h2mi_msm_flush(), "flush");
     for (uint32_t s = 0; s < n_sets; s++) p.forms(p.z[s], nullptr);
     check(h2mi_stream_wait(nullptr, p.side), "stream_wait");  // evaluate_h and the openings read the advice forms
-    p.read_points(n_sets + 1, points_out);
+    p.read_points(n_sets + (random ? 1 : 0), points_out);
   } else {
     // the halo2-lib shapes' schedule (measured at DEGREE 20 / 22): forms on the side stream, ordered behind the columns and AHEAD
     // of their commitments' partition kernels, which a dense accumulation in flight starves for milliseconds at DEGREE 22
@@ -1068,7 +1089,7 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
         p.commit(true, p.col(lz), slot++);
       }
     }
-    slot++;  // the random polynomial's commitment, queued before the grand products
+    if (random) slot++;  // the random polynomial's commitment, queued before the grand products
     check(h2mi_msm_flush(), "flush");
     p.read_points(slot, points_out);
     // joined AFTER the read-back: the copy runs on the library stream, and a join in front of it made the transcript wait for every
@@ -1079,14 +1100,103 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
 }
 
 // ---- phase 4: the quotient (plonk/evaluation.rs evaluate_h + vanishing division), its pieces committed ---------------------------
-void phase_quotient(h2mi_prover_s& p, const Fr& y, uint64_t* points_out) {
+// every extended-coset vector of one circuit as the interpreting quotient kernels take them: the columns a program may query through
+// one pointer table, the permutation argument, the lookups (given as expressions: compressed on the extended coset here)
+void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec) {
+  const h2mi_pk_s& pk = *p.pk;
+  const h2mi_constraint_system& cs = pk.cs;
+  const uint32_t L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
+  std::memset(&ec, 0, sizeof(ec));
+  for (uint32_t j = 0; j < cs.n_advice; j++) ec.advice[j] = p.advice[j].coset->p;
+  for (uint32_t j = 0; j < cs.n_fixed; j++) ec.fixed[j] = pk.fixed_cosets[j]->p;
+  if (cs.n_instance) ec.instance = p.instance_coset->p;
+  ec.n_perm = m;
+  ec.chunk_len = pk.chunk;
+  for (uint32_t j = 0; j < m; j++) {
+    const h2mi_column& c = cs.perm_columns[j];
+    ec.perm_value[j] = c.kind == H2MI_COL_ADVICE ? p.advice[c.index].coset->p : c.kind == H2MI_COL_INSTANCE ? p.instance_coset->p : pk.fixed_cosets[c.index]->p;
+    ec.perm_sigma[j] = pk.sigma_cosets[j]->p;
+  }
+  for (uint32_t s = 0; s < n_sets; s++) ec.perm_z[s] = p.z[s].coset->p;
+  ec.n_lookups = L;
+  for (uint32_t l = 0; l < L; l++) {
+    const h2mi_lookup& lk = cs.lookups[l];
+    if (pk.lookup_exprs) {
+      // compressed on the extended coset itself: a product of columns is no polynomial of degree < n, so transforming the
+      // compressed rows would give another function
+      p.compress(pk.lookup_slices.input[l], true, *p.lk[l].in_coset);
+      p.compress(pk.lookup_slices.table[l], true, *p.lk[l].tab_coset);
+      ec.lookup_input[l] = p.lk[l].in_coset->p;
+      ec.lookup_table[l] = p.lk[l].tab_coset->p;
+    } else {
+      ec.lookup_input[l] = p.advice[lk.input.index].coset->p;
+      ec.lookup_input_b[l] = lk.selector_fixed >= 0 ? pk.fixed_cosets[lk.selector_fixed]->p : nullptr;
+      ec.lookup_table[l] = pk.fixed_cosets[lk.table_fixed]->p;
+    }
+    ec.lookup_permuted_input[l] = p.lk[l].a.coset->p;
+    ec.lookup_permuted_table[l] = p.lk[l].s.coset->p;
+    ec.lookup_z[l] = p.lk[l].z.coset->p;
+  }
+  ec.l0 = pk.l0->p;
+  ec.l_last = pk.l_last->p;
+  ec.l_active = pk.l_active->p;
+}
+
+// a joint phase of a batch: the members behind the leader must still be where their products left them (one that has started another
+// proof since has overwritten its columns)
+void require_members(const Circuits& all) {
+  for (size_t i = 1; i < all.size(); i++)
+    if (all[i]->phase != PRODUCTS) {
+      all[0]->phase = IDLE;
+      throw Error(H2MI_EINVAL, "a member of the batch has left the proof");
+    }
+}
+// the proof is complete, or abandoned: every circuit's next proof starts with its advice
+void finish_members(const Circuits& all) {
+  for (h2mi_prover_s* c : all) c->phase = IDLE;
+}
+
+// the numerator of one circuit by the kernel of its shape (the single prover's route, unchanged)
+void evaluate_h_single(h2mi_prover_s& p, const Fr& y);
+
+void phase_quotient(const Circuits& all, const Fr& y, uint64_t* points_out) {
+  h2mi_prover_s& p = *all[0];
   const h2mi_pk_s& pk = *p.pk;
   const h2mi_constraint_system& cs = pk.cs;
   const poly::EvaluationDomain& d = pk.domain;
   const size_t n = pk.n;
-  const uint32_t bf = cs.blinding_factors, L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
   require_phase(p, PRODUCTS);
+  require_members(all);
   p.phase = IDLE;
+  DeviceVec& h = *p.h;
+  if (!p.batch) {
+    evaluate_h_single(p, y);
+  } else {
+    // several circuits (or a batch of one): ONE launch folds every circuit's terms into h, whatever the key's shape — a hard-wired
+    // shape through the equivalent program keygen built for the witness check, which computes the same field elements
+    std::vector<h2mi_expr_cosets> ec(all.size());
+    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i]);
+    const std::vector<Fr>& t_inv = d.t_inv();
+    check(h2mi_plonk_evaluate_h_expr_batch_dev(ec.data(), (uint32_t)ec.size(), &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
+                                               d.extended_k(), cs.blinding_factors, p.beta.l, p.gamma.l, y.l, pk.delta.l, d.get_g_coset().l,
+                                               d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
+          "evaluate_h");
+  }
+  check(h2mi_ntt_bn254_fr_dev(h.p, d.extended_k(), d.get_extended_omega_inv().l, nullptr, nullptr, nullptr), "extended_to_coeff");
+  check(h2mi_fr_scale_powers_dev(h.p, pk.ext, d.get_g_coset_inv().l, d.get_extended_ifft_divisor().l, nullptr), "distribute_powers_zeta");
+  const uint32_t pieces = cs.degree - 1;
+  std::vector<const void*> cols;
+  for (uint32_t i = 0; i < pieces; i++) cols.push_back(p.col(h, (size_t)i * n));
+  p.commit_phase(false, cols, 0, /*sparse=*/false, /*inorder=*/true);
+  p.read_points(pieces, points_out);
+  p.phase = QUOTIENT;
+}
+
+void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
+  const h2mi_pk_s& pk = *p.pk;
+  const h2mi_constraint_system& cs = pk.cs;
+  const poly::EvaluationDomain& d = pk.domain;
+  const uint32_t bf = cs.blinding_factors, L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
   DeviceVec& h = *p.h;
   const Fr& zeta = d.get_g_coset();
   const std::vector<Fr>& t_inv = d.t_inv();  // (X^n - 1)^-1 on the coset: cached in the domain
@@ -1110,39 +1220,7 @@ void phase_quotient(h2mi_prover_s& p, const Fr& y, uint64_t* points_out) {
   } else if (cs.gates == H2MI_GATES_EXPRESSIONS) {
     // gates given as a program: the interpreting kernel reads any column of the proof through one pointer table
     h2mi_expr_cosets ec;
-    std::memset(&ec, 0, sizeof(ec));
-    for (uint32_t j = 0; j < cs.n_advice; j++) ec.advice[j] = p.advice[j].coset->p;
-    for (uint32_t j = 0; j < cs.n_fixed; j++) ec.fixed[j] = pk.fixed_cosets[j]->p;
-    if (cs.n_instance) ec.instance = p.instance_coset->p;
-    ec.n_perm = m;
-    ec.chunk_len = pk.chunk;
-    for (uint32_t j = 0; j < m; j++) {
-      ec.perm_value[j] = coset_col(cs.perm_columns[j]);
-      ec.perm_sigma[j] = pk.sigma_cosets[j]->p;
-    }
-    for (uint32_t s = 0; s < n_sets; s++) ec.perm_z[s] = p.z[s].coset->p;
-    ec.n_lookups = L;
-    for (uint32_t l = 0; l < L; l++) {
-      const h2mi_lookup& lk = cs.lookups[l];
-      if (pk.lookup_exprs) {
-        // compressed on the extended coset itself: a product of columns is no polynomial of degree < n, so transforming the
-        // compressed rows would give another function
-        p.compress(pk.lookup_slices.input[l], true, *p.lk[l].in_coset);
-        p.compress(pk.lookup_slices.table[l], true, *p.lk[l].tab_coset);
-        ec.lookup_input[l] = p.lk[l].in_coset->p;
-        ec.lookup_table[l] = p.lk[l].tab_coset->p;
-      } else {
-        ec.lookup_input[l] = p.advice[lk.input.index].coset->p;
-        ec.lookup_input_b[l] = lk.selector_fixed >= 0 ? pk.fixed_cosets[lk.selector_fixed]->p : nullptr;
-        ec.lookup_table[l] = pk.fixed_cosets[lk.table_fixed]->p;
-      }
-      ec.lookup_permuted_input[l] = p.lk[l].a.coset->p;
-      ec.lookup_permuted_table[l] = p.lk[l].s.coset->p;
-      ec.lookup_z[l] = p.lk[l].z.coset->p;
-    }
-    ec.l0 = pk.l0->p;
-    ec.l_last = pk.l_last->p;
-    ec.l_active = pk.l_active->p;
+    fill_expr_cosets(p, ec);
     check(h2mi_plonk_evaluate_h_expr_ch_dev(&ec, &pk.gate_program, p.challenge_limbs(), pk.phases.n_challenges, d.k(), d.extended_k(), bf, p.beta.l,
                                             p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
@@ -1212,29 +1290,27 @@ void phase_quotient(h2mi_prover_s& p, const Fr& y, uint64_t* points_out) {
                                          (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
   }
-  check(h2mi_ntt_bn254_fr_dev(h.p, d.extended_k(), d.get_extended_omega_inv().l, nullptr, nullptr, nullptr), "extended_to_coeff");
-  check(h2mi_fr_scale_powers_dev(h.p, pk.ext, d.get_g_coset_inv().l, d.get_extended_ifft_divisor().l, nullptr), "distribute_powers_zeta");
-  const uint32_t pieces = cs.degree - 1;
-  std::vector<const void*> cols;
-  for (uint32_t i = 0; i < pieces; i++) cols.push_back(p.col(h, (size_t)i * n));
-  p.commit_phase(false, cols, 0, /*sparse=*/false, /*inorder=*/true);
-  p.read_points(pieces, points_out);
-  p.phase = QUOTIENT;
 }
 
-size_t num_evaluations(const h2mi_pk_s& pk) {
+// per circuit: its advice queries, its permutation sets, its lookups; once per proof: the fixed queries, the random polynomial, sigma
+size_t num_evaluations(const h2mi_pk_s& pk, size_t n_circuits = 1) {
   const h2mi_constraint_system& cs = pk.cs;
-  return cs.n_advice_queries + cs.n_fixed_queries + 1 + cs.n_perm + (pk.n_sets ? 3 * (size_t)pk.n_sets - 1 : 0) + 5 * (size_t)cs.n_lookups;
+  return n_circuits * cs.n_advice_queries + cs.n_fixed_queries + 1 + cs.n_perm +
+         n_circuits * ((pk.n_sets ? 3 * (size_t)pk.n_sets - 1 : 0) + 5 * (size_t)cs.n_lookups);
 }
 
 // ---- phase 5: every evaluation create_proof writes -------------------------------------------------------------------------------
-void phase_evaluations(h2mi_prover_s& p, const Fr& x, uint64_t* evals_out) {
+// [RECALL halo2_proofs v2023_02_02 plonk/prover.rs] with several circuits: the advice evaluations of every circuit in order, the
+// fixed ones, the random polynomial, sigma, every circuit's permutation sets, every circuit's lookups
+void phase_evaluations(const Circuits& all, const Fr& x, uint64_t* evals_out) {
+  h2mi_prover_s& p = *all[0];
   const h2mi_pk_s& pk = *p.pk;
   const h2mi_constraint_system& cs = pk.cs;
   const poly::EvaluationDomain& d = pk.domain;
   const size_t n = pk.n;
   const uint32_t bf = cs.blinding_factors, L = cs.n_lookups, n_sets = pk.n_sets, pieces = cs.degree - 1;
   require_phase(p, QUOTIENT);
+  require_members(all);
   p.phase = IDLE;
   if (!evals_out) throw Error(H2MI_EINVAL, "evals_out");
   const Fr omega = d.get_omega(), omega_inv = d.get_omega_inv();
@@ -1258,22 +1334,25 @@ void phase_evaluations(h2mi_prover_s& p, const Fr& x, uint64_t* evals_out) {
     Fr point;
   };
   std::vector<Q> written;
-  for (uint32_t i = 0; i < cs.n_advice_queries; i++) written.push_back({p.advice[cs.advice_queries[i].column].poly.get(), rot(cs.advice_queries[i].rotation)});
+  for (const h2mi_prover_s* c : all)
+    for (uint32_t i = 0; i < cs.n_advice_queries; i++) written.push_back({c->advice[cs.advice_queries[i].column].poly.get(), rot(cs.advice_queries[i].rotation)});
   for (uint32_t i = 0; i < cs.n_fixed_queries; i++) written.push_back({pk.fixed_polys[cs.fixed_queries[i].column].get(), rot(cs.fixed_queries[i].rotation)});
   written.push_back({&random_poly, x});
   for (auto& sp : pk.sigma_polys) written.push_back({sp.get(), x});
-  for (uint32_t i = 0; i < n_sets; i++) {
-    written.push_back({p.z[i].poly.get(), x});
-    written.push_back({p.z[i].poly.get(), x_next});
-    if (i + 1 < n_sets) written.push_back({p.z[i].poly.get(), x_last});
-  }
-  for (uint32_t l = 0; l < L; l++) {
-    written.push_back({p.lk[l].z.poly.get(), x});
-    written.push_back({p.lk[l].z.poly.get(), x_next});
-    written.push_back({p.lk[l].a.poly.get(), x});
-    written.push_back({p.lk[l].a.poly.get(), x_inv});
-    written.push_back({p.lk[l].s.poly.get(), x});
-  }
+  for (const h2mi_prover_s* c : all)
+    for (uint32_t i = 0; i < n_sets; i++) {
+      written.push_back({c->z[i].poly.get(), x});
+      written.push_back({c->z[i].poly.get(), x_next});
+      if (i + 1 < n_sets) written.push_back({c->z[i].poly.get(), x_last});
+    }
+  for (const h2mi_prover_s* c : all)
+    for (uint32_t l = 0; l < L; l++) {
+      written.push_back({c->lk[l].z.poly.get(), x});
+      written.push_back({c->lk[l].z.poly.get(), x_next});
+      written.push_back({c->lk[l].a.poly.get(), x});
+      written.push_back({c->lk[l].a.poly.get(), x_inv});
+      written.push_back({c->lk[l].s.poly.get(), x});
+    }
   std::vector<Q> todo = written;
   todo.push_back({&h_poly, x});  // opened but not written (the verifier recomputes it)
   // every evaluation in ONE call: groups of up to 24 distinct polynomials per distinct point (h2mi_fr_eval_polys_multi_dev)
@@ -1316,22 +1395,24 @@ void phase_evaluations(h2mi_prover_s& p, const Fr& x, uint64_t* evals_out) {
     std::memcpy(evals_out + 4 * i, v.l, 32);
   }
   p.n_written = written.size();
-  // the queries in create_proof's order (advice; permutation.open: every set at x and omega x, then all but the last at
-  // omega^last x in reverse; lookups; fixed; sigma; vanishing.open: h, the random polynomial)
+  // the queries in create_proof's order (per circuit: advice; permutation.open: every set at x and omega x, then all but the last
+  // at omega^last x in reverse; lookups — then fixed; sigma; vanishing.open: h, the random polynomial)
   p.queries.clear();
   auto q = [&](const DeviceVec* poly, const Fr& pt) { p.queries.push_back({poly, pt, value_of(poly, pt)}); };
-  for (uint32_t i = 0; i < cs.n_advice_queries; i++) q(p.advice[cs.advice_queries[i].column].poly.get(), rot(cs.advice_queries[i].rotation));
-  for (uint32_t i = 0; i < n_sets; i++) {
-    q(p.z[i].poly.get(), x);
-    q(p.z[i].poly.get(), x_next);
-  }
-  for (uint32_t i = n_sets > 0 ? n_sets - 1 : 0; i-- > 0;) q(p.z[i].poly.get(), x_last);
-  for (uint32_t l = 0; l < L; l++) {
-    q(p.lk[l].z.poly.get(), x);
-    q(p.lk[l].a.poly.get(), x);
-    q(p.lk[l].s.poly.get(), x);
-    q(p.lk[l].a.poly.get(), x_inv);
-    q(p.lk[l].z.poly.get(), x_next);
+  for (const h2mi_prover_s* c : all) {
+    for (uint32_t i = 0; i < cs.n_advice_queries; i++) q(c->advice[cs.advice_queries[i].column].poly.get(), rot(cs.advice_queries[i].rotation));
+    for (uint32_t i = 0; i < n_sets; i++) {
+      q(c->z[i].poly.get(), x);
+      q(c->z[i].poly.get(), x_next);
+    }
+    for (uint32_t i = n_sets > 0 ? n_sets - 1 : 0; i-- > 0;) q(c->z[i].poly.get(), x_last);
+    for (uint32_t l = 0; l < L; l++) {
+      q(c->lk[l].z.poly.get(), x);
+      q(c->lk[l].a.poly.get(), x);
+      q(c->lk[l].s.poly.get(), x);
+      q(c->lk[l].a.poly.get(), x_inv);
+      q(c->lk[l].z.poly.get(), x_next);
+    }
   }
   for (uint32_t i = 0; i < cs.n_fixed_queries; i++) q(pk.fixed_polys[cs.fixed_queries[i].column].get(), rot(cs.fixed_queries[i].rotation));
   for (auto& sp : pk.sigma_polys) q(sp.get(), x);
@@ -1348,9 +1429,11 @@ void shplonk_commit(h2mi_prover_s& p, const DeviceVec& poly, uint64_t* point_out
 }
 
 // ---- phase 6: ProverSHPLONK up to the commitment of h(X) = sum_i v^i Q_i(X) ------------------------------------------------------
-void phase_shplonk_quotient(h2mi_prover_s& p, const Fr& y, const Fr& v, uint64_t* point_out) {
+void phase_shplonk_quotient(const Circuits& all, const Fr& y, const Fr& v, uint64_t* point_out) {
+  h2mi_prover_s& p = *all[0];  // the queries name every circuit's polynomials; the scratch, the lanes and the commitment are the leader's
   const size_t n = p.pk->n;
   require_phase(p, EVALUATIONS);
+  require_members(all);
   p.phase = IDLE;
   // construct_intermediate_sets
   std::vector<std::pair<const DeviceVec*, std::vector<std::pair<Fr, Fr>>>> by_poly;  // first-appearance order
@@ -1429,9 +1512,11 @@ void phase_shplonk_quotient(h2mi_prover_s& p, const Fr& y, const Fr& v, uint64_t
 }
 
 // ---- phase 7: the linearisation L(X) at u, divided by (X - u) -------------------------------------------------------------------
-void phase_shplonk_open(h2mi_prover_s& p, const Fr& u, uint64_t* point_out) {
+void phase_shplonk_open(const Circuits& all, const Fr& u, uint64_t* point_out) {
+  h2mi_prover_s& p = *all[0];
   const size_t n = p.pk->n;
   require_phase(p, SHPLONK_Q);
+  require_members(all);
   p.phase = IDLE;
   const std::vector<RotationSet>& sets = p.sets;
   const std::vector<Fr>& super_points = p.super_points;
@@ -1467,7 +1552,7 @@ void phase_shplonk_open(h2mi_prover_s& p, const Fr& u, uint64_t* point_out) {
   check(h2mi_memset_zero(p.h2_x->p, n * 32), "zero");
   kate_chain(*p.l_x, n, {u}, *p.tmp[0], *p.h2_x, nullptr, nullptr);
   shplonk_commit(p, *p.h2_x, point_out);
-  p.phase = IDLE;  // the proof is complete; the next one starts with h2mi_prover_advice
+  finish_members(all);  // the proof is complete; the next one starts with h2mi_prover_advice
 }
 
 Fr load_fr(const uint64_t* l) {
@@ -1669,7 +1754,9 @@ int h2mi_prover_create(h2mi_pk_t pk, uint64_t g_handle, uint64_t g_lagrange_hand
 int h2mi_prover_destroy(h2mi_prover_t prover) {
   {
     std::lock_guard<std::mutex> lk(g_reg_mu);
-    if (!prover || !g_live_provers.erase(prover)) return H2MI_EHANDLE;
+    if (!prover || !g_live_provers.count(prover)) return H2MI_EHANDLE;
+    if (prover->batch) return H2MI_EINVAL;  // destroy the batch it is bound into first
+    g_live_provers.erase(prover);
     prover->pk->users--;
   }
   h2mi_sync();
@@ -1707,7 +1794,7 @@ int h2mi_prover_get_counts(h2mi_prover_t prover, h2mi_prover_counts* out) {
   const h2mi_pk_s& pk = *prover->pk;
   out->advice = pk.cs.n_advice;
   out->lookups = 2 * pk.cs.n_lookups;
-  out->products = pk.n_sets + pk.cs.n_lookups + 1;
+  out->products = pk.n_sets + pk.cs.n_lookups + (prover->draws_random() ? 1 : 0);
   out->quotient = pk.cs.degree - 1;
   out->evaluations = (uint32_t)num_evaluations(pk);
   return H2MI_OK;
@@ -1774,8 +1861,8 @@ int h2mi_prover_products(h2mi_prover_t prover, const uint64_t beta[4], const uin
 }
 int h2mi_prover_quotient(h2mi_prover_t prover, const uint64_t y[4], uint64_t* points_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
-  if (!y) return H2MI_EINVAL;
-  return guarded([&] { phase_quotient(*prover, load_fr(y), points_out); });
+  if (!y || prover->batch) return H2MI_EINVAL;  // a bound member's joint phases are its batch's: nothing is abandoned
+  return guarded([&] { phase_quotient({prover}, load_fr(y), points_out); });
 }
 int h2mi_prover_num_evaluations(h2mi_prover_t prover, size_t* count_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
@@ -1785,18 +1872,102 @@ int h2mi_prover_num_evaluations(h2mi_prover_t prover, size_t* count_out) {
 }
 int h2mi_prover_evaluations(h2mi_prover_t prover, const uint64_t x[4], uint64_t* evals_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
-  if (!x) return H2MI_EINVAL;
-  return guarded([&] { phase_evaluations(*prover, load_fr(x), evals_out); });
+  if (!x || prover->batch) return H2MI_EINVAL;
+  return guarded([&] { phase_evaluations({prover}, load_fr(x), evals_out); });
 }
 int h2mi_prover_shplonk_quotient(h2mi_prover_t prover, const uint64_t y[4], const uint64_t v[4], uint64_t point_out[8]) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
-  if (!y || !v) return H2MI_EINVAL;
-  return guarded([&] { phase_shplonk_quotient(*prover, load_fr(y), load_fr(v), point_out); });
+  if (!y || !v || prover->batch) return H2MI_EINVAL;
+  return guarded([&] { phase_shplonk_quotient({prover}, load_fr(y), load_fr(v), point_out); });
 }
 int h2mi_prover_shplonk_open(h2mi_prover_t prover, const uint64_t u[4], uint64_t point_out[8]) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
+  if (!u || prover->batch) return H2MI_EINVAL;
+  return guarded([&] { phase_shplonk_open({prover}, load_fr(u), point_out); });
+}
+
+// ---- several circuits per proof ----------------------------------------------------------------------------------------------------
+int h2mi_batch_create(const h2mi_prover_t* members, uint32_t n, h2mi_batch_t* batch_out) {
+  if (!batch_out) return H2MI_EINVAL;
+  *batch_out = nullptr;
+  if (!members || n == 0 || n > H2MI_MAX_CIRCUITS) return H2MI_EINVAL;
+  std::lock_guard<std::mutex> lk(g_reg_mu);
+  for (uint32_t i = 0; i < n; i++) {
+    const h2mi_prover_s* m = members[i];
+    if (!m || !g_live_provers.count(m)) return H2MI_EHANDLE;
+    const h2mi_prover_s* m0 = members[0];
+    if (m->batch || m->phase != IDLE) return H2MI_EINVAL;  // bound already, or a proof in flight
+    if (m->pk != m0->pk || m->g != m0->g || m->gl != m0->gl || m->lo != m0->lo || m->cnt != m0->cnt) return H2MI_EINVAL;
+    for (uint32_t j = 0; j < i; j++)
+      if (members[j] == m) return H2MI_EINVAL;
+  }
+  h2mi_batch_s* b = new (std::nothrow) h2mi_batch_s;
+  if (!b) return H2MI_ENOMEM;
+  b->members.assign(members, members + n);
+  for (uint32_t i = 0; i < n; i++) {
+    members[i]->batch = b;
+    members[i]->batch_index = i;
+  }
+  g_live_batches.insert(b);
+  *batch_out = b;
+  return H2MI_OK;
+}
+
+int h2mi_batch_destroy(h2mi_batch_t batch) {
+  {
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    if (!batch || !g_live_batches.erase(batch)) return H2MI_EHANDLE;
+    for (h2mi_prover_s* m : batch->members) {  // ordinary provers again; a proof in flight is abandoned
+      m->batch = nullptr;
+      m->batch_index = 0;
+      m->phase = IDLE;
+    }
+  }
+  delete batch;
+  return H2MI_OK;
+}
+
+int h2mi_batch_quotient(h2mi_batch_t batch, const uint64_t y[4], uint64_t* points_out) {
+  if (!alive(g_live_batches, batch)) return H2MI_EHANDLE;
+  if (!y) return H2MI_EINVAL;
+  const Circuits& all = batch->members;
+  // what makes N circuits one proof, checked before anything is touched: a refusal here abandons nothing
+  for (const h2mi_prover_s* m : all) {
+    const h2mi_prover_s& m0 = *all[0];
+    if (m->phase != PRODUCTS) return H2MI_EINVAL;
+    if (!(m->beta == m0.beta) || !(m->gamma == m0.gamma)) return H2MI_EINVAL;
+    if (m->pk->phases.n_challenges && !std::equal(m->challenges.begin(), m->challenges.end(), m0.challenges.begin(), m0.challenges.end())) return H2MI_EINVAL;
+  }
+  // blinding streams that could overlap would open two columns with the same blinding: seeded streams are seed + purpose (1 .. 5),
+  // keyed ones nonce << 3 | purpose under the key
+  for (size_t i = 0; i < all.size(); i++)
+    for (size_t j = 0; j < i; j++) {
+      const h2mi_prover_s &a = *all[i], &b = *all[j];
+      if (a.keyed != b.keyed) continue;
+      if (a.keyed ? (!std::memcmp(a.key, b.key, 32) && a.seed == b.seed) : (a.seed > b.seed ? a.seed - b.seed : b.seed - a.seed) < 8) return H2MI_EINVAL;
+    }
+  return guarded([&] { phase_quotient(all, load_fr(y), points_out); });
+}
+int h2mi_batch_num_evaluations(h2mi_batch_t batch, size_t* count_out) {
+  if (!alive(g_live_batches, batch)) return H2MI_EHANDLE;
+  if (!count_out) return H2MI_EINVAL;
+  *count_out = num_evaluations(*batch->members[0]->pk, batch->members.size());
+  return H2MI_OK;
+}
+int h2mi_batch_evaluations(h2mi_batch_t batch, const uint64_t x[4], uint64_t* evals_out) {
+  if (!alive(g_live_batches, batch)) return H2MI_EHANDLE;
+  if (!x) return H2MI_EINVAL;
+  return guarded([&] { phase_evaluations(batch->members, load_fr(x), evals_out); });
+}
+int h2mi_batch_shplonk_quotient(h2mi_batch_t batch, const uint64_t y[4], const uint64_t v[4], uint64_t point_out[8]) {
+  if (!alive(g_live_batches, batch)) return H2MI_EHANDLE;
+  if (!y || !v) return H2MI_EINVAL;
+  return guarded([&] { phase_shplonk_quotient(batch->members, load_fr(y), load_fr(v), point_out); });
+}
+int h2mi_batch_shplonk_open(h2mi_batch_t batch, const uint64_t u[4], uint64_t point_out[8]) {
+  if (!alive(g_live_batches, batch)) return H2MI_EHANDLE;
   if (!u) return H2MI_EINVAL;
-  return guarded([&] { phase_shplonk_open(*prover, load_fr(u), point_out); });
+  return guarded([&] { phase_shplonk_open(batch->members, load_fr(u), point_out); });
 }
 
 int h2mi_prover_buffer(h2mi_prover_t prover, uint32_t kind, uint32_t index, void** d_ptr_out, size_t* count_out) {

@@ -460,6 +460,7 @@ class Keys:
 
     def __init__(self, params: ParamsKZG, cs: ConstraintSystem, asg: Assignment):
         self.cs = cs
+        self.params = params  # prove_many's default SRS
         k = params.k
         self.domain = d = EvaluationDomain(cs.degree(), k)
         self.u = d.n - (cs.blinding_factors() + 1)
@@ -502,6 +503,53 @@ def create_proof(params: ParamsKZG, keys: Keys, asg, seed: int, transcript=None,
     if callable(asg):
         asg = _PhasedWitness(asg, len(keys.cs.challenge_phase))
     return flex.create_proof(params, keys, asg, seed, transcript=transcript, trace=trace, ws=ws)
+
+
+class BatchWorkspace:
+    """n library provers against one key bound into one engine.Batch, kept from proof to proof"""
+
+    def __init__(self, params: ParamsKZG, keys, n: int):
+        self.provers = [engine.Prover(keys.keys, params) for _ in range(n)]
+        try:
+            self.batch = engine.Batch(self.provers)
+        except Exception:
+            for p in self.provers:
+                p.release()
+            raise
+
+    def release(self):
+        self.batch.release()
+        for p in self.provers:
+            p.release()
+
+
+def prove_many(pk, assignments, instances=None, seeds=None, params: ParamsKZG = None, transcript=None, trace: dict = None, ws: BatchWorkspace = None,
+               hooks: dict = None) -> bytes:
+    """create_proof(&params, &pk, &[circuit_0, .., circuit_(N-1)], &[instances_0, ..], rng, &mut transcript): ONE proof of N <= 8 circuits
+    against one key — the fixed and sigma columns, the random polynomial and h(X) opened once, one quotient, one SHPLONK round.
+    assignments: per circuit an Assignment or a callable synthesize(challenges) -> Assignment as create_proof takes them (a phase's
+    commitments of every circuit precede that phase's challenges).  instances: per circuit its public inputs (default: each
+    assignment's own).  seeds: per circuit the seed of its blinding streams, at least 8 apart (the library refuses closer ones: two
+    columns of one proof would share their blinding); default 1, 9, 17, ...  params: the SRS (default: the one the key was made with).
+    `prove` / `create_proof` stay the single-circuit route; a batch of one gives the same bytes."""
+    params = params if params is not None else pk.params
+    n_challenges = len(getattr(getattr(pk, "cs", None), "challenge_phase", ()))
+    wits = [_PhasedWitness(a, n_challenges) if callable(a) else a for a in assignments]
+    instances = [list(w.instance) for w in wits] if instances is None else [list(v) for v in instances]
+    seeds = [1 + 8 * i for i in range(len(wits))] if seeds is None else list(seeds)
+    own = ws is None
+    ws = ws or BatchWorkspace(params, pk, len(wits))
+    try:
+        transcript = transcript or flex.Blake2bWrite.init()
+        transcript.common_scalar(flex._m(pk.transcript_repr))
+        for inst in instances:  # KZG: every circuit's public inputs are hashed as scalars, in circuit order
+            for v in inst:
+                transcript.common_scalar(flex._m(v))
+        ws.batch.drive([w.advice for w in wits], instances, seeds, transcript, trace, hooks)
+        return transcript.finalize()
+    finally:
+        if own:
+            ws.release()
 
 
 def check(params: ParamsKZG, keys: Keys, asg, seed: int = 1, ws: Workspace = None, trace: dict = None) -> None:

@@ -477,4 +477,113 @@ class Prover:
             self.handle = None
 
 
-__all__ = ["ConstraintSystem", "Keys", "Prover", "DevView", "H2miError"]
+class Batch:
+    """one h2mi_batch_t: N provers over one key whose circuits go into ONE proof — create_proof(&params, &pk, &[c_0, .., c_(N-1)], ..).
+    The per-circuit phases run on the members, `drive()` orders their points in the transcript as the crate does [RECALL halo2_proofs
+    v2023_02_02 plonk/prover.rs] and calls the joint phases on the batch.  While the batch lives its members cannot be released;
+    release() makes them ordinary provers again."""
+
+    def __init__(self, provers):
+        self.members = list(provers)
+        arr = (C.c_void_p * max(len(self.members), 1))(*[p.handle for p in self.members])
+        h = C.c_void_p()
+        check(lib.h2mi_batch_create(arr, len(self.members), C.byref(h)), "batch_create")
+        self.handle = h.value
+        for p in self.members:  # a member behind the first commits no random polynomial: its products count has changed
+            check(lib.h2mi_prover_get_counts(p.handle, C.byref(p.counts)), "prover counts")
+        n = C.c_size_t()
+        check(lib.h2mi_batch_num_evaluations(self.handle, C.byref(n)), "batch num_evaluations")
+        self.n_evaluations = n.value
+        self._evals = np.zeros((max(n.value, 1), 4), dtype=np.uint64)
+
+    def drive(self, advices, instances, seeds, transcript: Blake2bWrite, trace: dict = None, hooks: dict = None):
+        """create_proof for the batch between the transcript's challenges.  advices[i] / instances[i] / seeds[i]: what Prover.drive
+        takes, for circuit i (a callable synthesize(challenges) per circuit when the witness reads challenges: every circuit's
+        commitments of a phase precede that phase's challenges, which all circuits then read).  The caller has hashed
+        vk.transcript_repr and every circuit's public inputs, in circuit order.  hooks (tests): "products_done"(batch) is called when
+        every member has run its products, "y"(limbs) -> the y handed to the library instead of the transcript's."""
+        ms, hooks = self.members, hooks or {}
+        lead = ms[0]
+        c, pc = lead.counts, lead.phase_counts
+        assert len(advices) == len(instances) == len(seeds) == len(ms)
+        sq = transcript.squeeze_challenge
+        m = F.fr_from_mont_limbs
+
+        def points(p, k):
+            return [p._points[i].copy() for i in range(k)]
+
+        def write(pts):
+            for pt in pts:
+                transcript.write_point(pt)
+
+        insts = [np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in inst])) if len(inst) else np.zeros((1, 4), dtype=np.uint64) for inst in instances]
+        column_phase = lead.keys.phases.advice_phase if lead.keys.phases is not None else [0] * c.advice
+        challenge_phase = lead.keys.phases.challenge_phase if pc.n_challenges else []
+        limbs, known = [None] * pc.n_challenges, [None] * pc.n_challenges
+        single = pc.n_phases == 1 and pc.n_challenges == 0
+        for phase in range(pc.n_phases):
+            for i, p in enumerate(ms):  # this phase's commitments of every circuit, in circuit order
+                columns = advices[i](list(known)) if callable(advices[i]) else advices[i]
+                pp = p._points.ctypes.data
+                if single:
+                    cells, keep = pack_cells(columns)
+                    p._phase(lib.h2mi_prover_advice(p.handle, cells, insts[i].ctypes.data, len(instances[i]), seeds[i], pp), "advice")
+                else:
+                    cells, keep = pack_cells([cells_ if column_phase[j] == phase else {} for j, cells_ in enumerate(columns)])
+                    p._phase(lib.h2mi_prover_advice_phase(p.handle, phase, cells, insts[i].ctypes.data, len(instances[i]), seeds[i], pp), f"advice phase {phase}")
+                del keep
+                write(points(p, pc.advice[phase]))
+            for i in range(pc.n_challenges):  # then its challenges, once for the proof
+                if challenge_phase[i] == phase:
+                    limbs[i] = sq()
+                    known[i] = m(limbs[i])
+        if pc.n_challenges:
+            ch = np.ascontiguousarray(np.stack(limbs))
+            for p in ms:
+                p._phase(lib.h2mi_prover_set_challenges(p.handle, ch.ctypes.data), "set_challenges")
+        theta = sq()
+        if c.lookups:
+            for p in ms:
+                p._phase(lib.h2mi_prover_lookups(p.handle, theta.ctypes.data, p._points.ctypes.data), "lookups")
+                write(points(p, c.lookups))
+        beta, gamma = sq(), sq()
+        n_sets = c.products - 1 - c.lookups // 2
+        products = []
+        for p in ms:
+            p._phase(lib.h2mi_prover_products(p.handle, beta.ctypes.data, gamma.ctypes.data, p._points.ctypes.data), "products")
+            products.append(points(p, p.counts.products))
+        for pts in products:  # every circuit's permutation products, then every circuit's lookup products, then the random polynomial
+            write(pts[:n_sets])
+        for pts in products:
+            write(pts[n_sets:n_sets + c.lookups // 2])
+        write(products[0][n_sets + c.lookups // 2:])
+        if "products_done" in hooks:
+            hooks["products_done"](self)
+        y = sq()
+        y_lib = hooks["y"](y) if "y" in hooks else y
+        pp = lead._points.ctypes.data
+        lead._phase(lib.h2mi_batch_quotient(self.handle, y_lib.ctypes.data, pp), "batch quotient")
+        write(points(lead, c.quotient))
+        x = sq()
+        lead._phase(lib.h2mi_batch_evaluations(self.handle, x.ctypes.data, self._evals.ctypes.data), "batch evaluations")
+        for e in self._evals[:self.n_evaluations]:
+            transcript.write_scalar(e)
+        sy, sv = sq(), sq()
+        lead._phase(lib.h2mi_batch_shplonk_quotient(self.handle, sy.ctypes.data, sv.ctypes.data, pp), "batch shplonk quotient")
+        write(points(lead, 1))
+        su = sq()
+        lead._phase(lib.h2mi_batch_shplonk_open(self.handle, su.ctypes.data, pp), "batch shplonk open")
+        write(points(lead, 1))
+        if trace is not None:
+            trace.update(theta=m(theta), beta=m(beta), gamma=m(gamma), y=m(y), x=m(x), challenges=list(known))
+
+    def release(self):
+        if self.handle:
+            check(lib.h2mi_batch_destroy(self.handle), "batch_destroy")
+            self.handle = None
+            for p in self.members:
+                if p.handle:
+                    check(lib.h2mi_prover_get_counts(p.handle, C.byref(p.counts)), "prover counts")
+
+
+__all__ = ["ConstraintSystem", "Keys", "Prover", "Batch", "DevView", "H2miError"]

@@ -285,6 +285,47 @@ def evaluate_h_expr(domain: EvaluationDomain, program, advice, fixed, instance, 
                                                      blinding_factors, *[x.ctypes.data for x in args], t_inv.ctypes.data, out.ptr, None), "evaluate_h_expr")
 
 
+def expr_cosets_array(circuits, perm_sigmas, chunk_len: int, l0: DevBuf, l_last: DevBuf, l_active: DevBuf):
+    """-> an array of h2mi_expr_cosets, one entry per circuit of a proof.  circuits: per circuit a dict with `advice`, `fixed` (lists of
+    DevBuf, None for a column the program does not read), `instance` (or None), `perm_values`, `perm_zs`, `lookups` as evaluate_h_expr
+    takes them; what the proof shares — perm_sigmas, chunk_len, the Lagrange cosets — is given once and stated in every entry."""
+    arr = (_ExprCosets * max(len(circuits), 1))()
+    for cs, c in zip(arr, circuits):
+        m = len(c["perm_values"])
+        assert len(perm_sigmas) == m and len(c["perm_zs"]) == (-(-m // chunk_len) if m else 0)
+        for j, a in enumerate(c["advice"]):
+            cs.advice[j] = a.ptr if a is not None else None
+        for j, f in enumerate(c["fixed"]):
+            cs.fixed[j] = f.ptr if f is not None else None
+        cs.instance = c["instance"].ptr if c.get("instance") is not None else None
+        cs.n_perm, cs.chunk_len = m, chunk_len
+        for j in range(m):
+            cs.perm_value[j], cs.perm_sigma[j] = c["perm_values"][j].ptr, perm_sigmas[j].ptr
+        for s, z in enumerate(c["perm_zs"]):
+            cs.perm_z[s] = z.ptr
+        cs.n_lookups = len(c["lookups"])
+        for l, (a_in, b_in, table, pin, ptab, z) in enumerate(c["lookups"]):
+            cs.lookup_input[l], cs.lookup_table[l] = a_in.ptr, table.ptr
+            cs.lookup_input_b[l] = b_in.ptr if b_in is not None else None
+            cs.lookup_permuted_input[l], cs.lookup_permuted_table[l], cs.lookup_z[l] = pin.ptr, ptab.ptr, z.ptr
+        cs.l0, cs.l_last, cs.l_active = l0.ptr, l_last.ptr, l_active.ptr
+    return arr
+
+
+def evaluate_h_expr_batch(domain: EvaluationDomain, program, cosets, n_circuits: int, beta: int, gamma: int, y: int, out: DevBuf,
+                          blinding_factors: int = BLINDING_FACTORS, challenges=()) -> None:
+    """h(X) of SEVERAL circuits in one proof (h2mi_plonk_evaluate_h_expr_batch_dev): one accumulator folded with y over every circuit's
+    gate, permutation and lookup terms in circuit order, one division by X^n - 1.  cosets: expr_cosets_array's result (the first
+    n_circuits entries are read); program and challenges are the proof's."""
+    mm = F.fr_to_mont_limbs
+    t_inv = np.ascontiguousarray(vanishing_inverses(domain))
+    args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
+    ch = _challenge_limbs(challenges)
+    _check(lib.h2mi_plonk_evaluate_h_expr_batch_dev(cosets, n_circuits, C.byref(program), ch.ctypes.data if len(challenges) else None, len(challenges),
+                                                    domain.k, domain.extended_k, blinding_factors, *[x.ctypes.data for x in args], t_inv.ctypes.data,
+                                                    out.ptr, None), "evaluate_h_expr_batch")
+
+
 def _challenge_limbs(challenges) -> np.ndarray:
     return np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in challenges])) if len(challenges) else np.zeros((1, 4), dtype=np.uint64)
 

@@ -476,6 +476,21 @@ int h2mi_plonk_evaluate_h_expr_ch_dev(const h2mi_expr_cosets* cosets, const h2mi
                                       const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
                                       const uint64_t extended_omega[4], const uint64_t* t_inv /* 2^(extended_k-k) x 4 */, void* d_h_out,
                                       h2mi_stream_t stream);
+/* Several circuits of one proof [RECALL halo2_proofs v2023_02_02 plonk/evaluation.rs evaluate_h]: ONE accumulator walks circuits[0 ..
+ * n_circuits - 1] in order, per circuit acc = acc y + term over its gate polynomials, its permutation terms and its lookup terms, and
+ * the division by X^n - 1 comes behind the last circuit — one launch and one pass over d_h_out whatever n_circuits is.  The program,
+ * its constants and the challenges are the proof's; an entry holds what belongs to one circuit (advice, instance, perm_value, perm_z,
+ * the six vectors of each lookup).  What the circuits share — fixed, perm_sigma, l0, l_last, l_active — is stated in every entry:
+ * perm_sigma and the three Lagrange cosets are read from entry 0 and must be the same pointers in the others; two entries may share
+ * any other pointer too (the same advice twice is folded twice).  The entries travel as consecutive records behind the program in the
+ * launch's one device buffer.  H2MI_EINVAL: n_circuits == 0 or > H2MI_MAX_CIRCUITS; entries that disagree in n_perm, chunk_len or
+ * n_lookups; whatever the call above refuses, in any entry.  With n_circuits == 1 the words of d_h_out are that call's. */
+#define H2MI_MAX_CIRCUITS 8
+int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_expr_cosets* circuits, uint32_t n_circuits, const h2mi_gate_program* gates,
+                                         const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
+                                         uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
+                                         const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
+                                         const uint64_t* t_inv /* 2^(extended_k-k) x 4 */, void* d_h_out, h2mi_stream_t stream);
 
 /* A lookup's expressions compressed with theta (plonk/lookup/prover.rs compress_expressions): `exprs` holds m polynomials e_0 ..
  * e_(m-1) and d_out[i] = sum_j e_j(i) theta^(m-1-j) — the fold acc theta + e_j — for the 2^domain_k points the columns are given on:

@@ -25,6 +25,11 @@
  * streams, MSM batching, flush / join order, the coefficient and extended-coset forms, SHPLONK's rotation sets.  Only
  * 64-byte points and 32-byte scalars cross the boundary after the witness.
  *
+ * `circuits` is a slice there.  One prover object (h2mi_prover_t) holds ONE circuit of a proof; several circuits against one key go
+ * into one proof through a batch (h2mi_batch_t, below): the per-circuit phases — advice, lookups, products — stay on each member,
+ * with the caller's transcript putting their points in the crate's order, and the joint ones — quotient, evaluations, SHPLONK — are
+ * called once on the batch.  The fixed columns, the sigma columns, the random polynomial and h(X) are then opened once, not N times.
+ *
  * The constraint system is DATA (h2mi_constraint_system).  Shapes accepted are the ones the reference proves:
  *   H2MI_GATES_STANDARD_PLONK  src/circuits/standard_plonk.rs:29-48 — q_a a + q_b b + q_c c + q_ab a b + constant
  *   H2MI_GATES_FLEX_VERTICAL   halo2-base's FlexGate through scaffold::prove (src/scaffold.rs:246-366, 379-485):
@@ -300,7 +305,55 @@ int h2mi_prover_evaluations(h2mi_prover_t prover, const uint64_t x[4], uint64_t*
 int h2mi_prover_shplonk_quotient(h2mi_prover_t prover, const uint64_t y[4], const uint64_t v[4], uint64_t point_out[8]);
 int h2mi_prover_shplonk_open(h2mi_prover_t prover, const uint64_t u[4], uint64_t point_out[8]);
 
-/* number of points the phases return, so that a caller can size buffers from the constraint system alone */
+/* ---- several circuits per proof: create_proof(&params, &pk, &[c_0, .., c_(N-1)], &[instances_0, ..], rng, &mut transcript) ----------
+ * A batch binds N <= H2MI_MAX_CIRCUITS (h2mi.h: 8) ordinary provers of h2mi_prover_create, member i holding circuit i.  All members are
+ * against the same pk with the same SRS handles and slice, none with a proof in flight (its last phase call, if any, was
+ * h2mi_prover_shplonk_open or a refusal) and none bound already: H2MI_EINVAL otherwise (H2MI_EHANDLE for a dead handle).  While bound, a
+ * member cannot be destroyed (H2MI_EINVAL, as h2mi_prover_pk_release is while a prover is alive); h2mi_batch_destroy makes the members
+ * ordinary provers again and abandons a proof in flight.
+ *
+ * Per circuit, on its member, unchanged: h2mi_prover_advice / _advice_phase, _set_challenges, _check, _lookups, _products — one circuit
+ * each, in any interleaving between members that respects each member's own order.  The caller's transcript orders the points as
+ * create_proof does [RECALL halo2_proofs v2023_02_02 plonk/prover.rs]: per advice phase every circuit's commitments of that phase in
+ * circuit order, then that phase's challenges; theta; every circuit's permuted lookup pairs; beta, gamma; every circuit's permutation
+ * products; every circuit's lookup products; the random polynomial; y; the h pieces; x; the evaluations; SHPLONK.
+ * There is ONE random polynomial per proof: member 0's products phase draws and commits it as ever (last in its points_out); a bound
+ * member with index > 0 neither draws nor commits one, so its points_out is one point shorter (h2mi_prover_get_counts says so) and
+ * its H2MI_BUF_RANDOM_POLY is stale.  A caller that writes member 0's points first keeps the random polynomial's back until every
+ * member's products are written.
+ * A bound member's own h2mi_prover_quotient, _evaluations, _shplonk_quotient and _shplonk_open return H2MI_EINVAL and abandon nothing.
+ *
+ * Joint, on the batch, each once per proof and in this order (H2MI_EINVAL otherwise, and the proof is abandoned — except for the
+ * refusals of h2mi_batch_quotient listed next, which leave every member where it was):
+ *   h2mi_batch_quotient         requires every member behind its h2mi_prover_products, all with the same beta and gamma and, on a key with
+ *                               challenges, the same challenge values; and refuses members whose blinding streams could overlap — two
+ *                               columns of one proof would be opened with the same blinding: seeded streams are seed + purpose (1 .. 5), so
+ *                               two members' seeds must be at least 8 apart; under the same rng key two members need different nonces.
+ *                               One kernel folds every circuit's gate, permutation and lookup terms into h in circuit order
+ *                               (h2mi_plonk_evaluate_h_expr_batch_dev); a key of a hard-wired shape goes through the equivalent program of
+ *                               h2mi_shape_gate_program, which computes the same field elements as the shape's own kernel.
+ *                               points_out: the degree - 1 pieces of h(X).
+ *   h2mi_batch_evaluations      evals_out: every circuit's advice queries in circuit order; the fixed queries; the random polynomial; the
+ *                               sigma polynomials; every circuit's permutation sets (per set as h2mi_prover_evaluations); every circuit's
+ *                               lookups (per lookup likewise).  h2mi_batch_num_evaluations = N advice queries + fixed queries + 1 + n_perm
+ *                               + N (3 n_sets - 1 if n_sets > 0) + N 5 n_lookups.
+ *   h2mi_batch_shplonk_quotient, h2mi_batch_shplonk_open
+ *                               over the queries in create_proof's order: per circuit advice, permutation.open, lookups.open; then fixed,
+ *                               sigma, h, the random polynomial.
+ * The joint vectors are member 0's: h2mi_prover_buffer(member 0, H2MI_BUF_H / _H_POLY / _RANDOM_POLY / _SHPLONK_H / _SHPLONK_H2) reads
+ * the batch's; every member's per-circuit buffers stay readable through the member.  The joint commitments go through member 0's result
+ * slots and combiner (multi-device modes: the vectors are on the primary device). */
+typedef struct h2mi_batch_s* h2mi_batch_t;
+int h2mi_batch_create(const h2mi_prover_t* members, uint32_t n, h2mi_batch_t* batch_out);
+int h2mi_batch_destroy(h2mi_batch_t batch);
+int h2mi_batch_quotient(h2mi_batch_t batch, const uint64_t y[4], uint64_t* points_out);
+int h2mi_batch_num_evaluations(h2mi_batch_t batch, size_t* count_out);
+int h2mi_batch_evaluations(h2mi_batch_t batch, const uint64_t x[4], uint64_t* evals_out);
+int h2mi_batch_shplonk_quotient(h2mi_batch_t batch, const uint64_t y[4], const uint64_t v[4], uint64_t point_out[8]);
+int h2mi_batch_shplonk_open(h2mi_batch_t batch, const uint64_t u[4], uint64_t point_out[8]);
+
+/* number of points the phases return, so that a caller can size buffers from the constraint system alone (products: without the random
+ * polynomial for a bound member behind the first) */
 typedef struct {
   uint32_t advice, lookups, products, quotient, evaluations;
 } h2mi_prover_counts;
