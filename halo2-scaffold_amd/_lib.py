@@ -97,6 +97,7 @@ def _load():
         "h2mi_plonk_lookup_permute_dev": ([vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64p, vp], C.c_int),
         "h2mi_plonk_instance_coset_dev": ([vp, C.c_uint32, C.c_uint32, vp, sz, vp, vp], C.c_int),
         "h2mi_plonk_lookup_product_dev": ([vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp], C.c_int),
+        "h2mi_plonk_shuffle_product_dev": ([vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_range_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_flex_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_expr_dev": ([vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
@@ -104,11 +105,15 @@ def _load():
         "h2mi_plonk_evaluate_h_expr_ch_dev": ([vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_expr_batch_dev": ([vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
                                                  C.c_int),
+        "h2mi_plonk_evaluate_h_expr_sh_dev": ([vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "h2mi_plonk_evaluate_h_expr_batch_sh_dev": ([vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                     vp], C.c_int),
         "h2mi_plonk_expr_compress_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_expr_check_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32), vp],
                                          C.c_int),
         "h2mi_plonk_copy_check_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp], C.c_int),
         "h2mi_plonk_lookup_member_dev": ([vp, vp, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
+        "h2mi_plonk_shuffle_member_dev": ([vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
         "h2mi_fr_sort_unique_dev": ([vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), vp], C.c_int),
         "h2mi_g1_fixed_base_mul_dev": ([vp, sz, vp, vp], C.c_int),
         "h2mi_fr_powers_dev": ([vp, sz, vp, vp], C.c_int),
@@ -127,6 +132,9 @@ def _load():
         "h2mi_prover_keygen_exprs": ([vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_advice_phases_check": ([vp, vp, vp, vp], C.c_int),
         "h2mi_prover_keygen_phases": ([vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
+        "h2mi_shuffle_program_check": ([vp, vp, C.POINTER(C.c_uint32)], C.c_int),
+        "h2mi_shuffle_phases_check": ([vp, vp, vp, C.POINTER(C.c_uint32)], C.c_int),
+        "h2mi_prover_keygen_shuffles": ([vp, vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_prover_pk_release": ([vp], C.c_int),
         "h2mi_prover_vk_commitments": ([vp, vp, vp], C.c_int),
         "h2mi_prover_create": ([vp, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(vp)], C.c_int),

@@ -120,6 +120,33 @@ __global__ void __launch_bounds__(256) k_lk_member(const fe* input, uint32_t u, 
   }
 }
 
+// The shuffle argument's witness check: both sides hold u values, sorted into distinct values with multiplicities.  Row i fails when
+// its input value occurs more often among the inputs than on the shuffle side (absent there: zero times).  k_lk_member's binary search,
+// once per side; the same vote.
+__device__ __forceinline__ uint32_t sf_mult_of(const fe& v, const fe* sorted, const uint32_t* mult, uint32_t n_unique) {
+  uint32_t lo = 0, hi = n_unique;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (cmp256(fe_load(&sorted[mid]), v) < 0) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n_unique && cmp256(fe_load(&sorted[lo]), v) == 0 ? mult[lo] : 0u;
+}
+__global__ void __launch_bounds__(256) k_sf_member(const fe* input, uint32_t u, const fe* in_sorted, const uint32_t* in_mult, uint32_t n_in,
+                                                    const fe* sh_sorted, const uint32_t* sh_mult, uint32_t n_sh, uint32_t* report) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool excess = false;
+  if (i < u) {
+    const fe v = fe_from_mont<Fr>(fe_load(&input[i]));
+    excess = sf_mult_of(v, in_sorted, in_mult, n_in) > sf_mult_of(v, sh_sorted, sh_mult, n_sh);
+  }
+  const unsigned long long m = __ballot(excess);
+  if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll(m) - 1)) {
+    atomicAdd(&report[0], (uint32_t)__popcll(m));
+    atomicMin(&report[1], i);
+  }
+}
+
 __global__ void __launch_bounds__(256) k_lk_leftover(const uint32_t* cnt, const uint32_t* mult, uint32_t n_unique, uint32_t* left, uint32_t* missing) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_unique) return;
@@ -425,6 +452,33 @@ int h2mi_plonk_lookup_member_dev(const void* d_input, const void* d_table_sorted
   H2_HIP(hipMemcpyAsync(g_lk_scratch, init, 8, hipMemcpyHostToDevice, s));
   H2_LAUNCH("k_lk_member", k_lk_member, ceil_div_u32(usable_rows, 256), 256, 0, s, (const fe*)d_input, usable_rows, (const fe*)d_table_sorted, n_unique,
             g_lk_scratch);
+  H2_HIP(hipMemcpyAsync(report_out, g_lk_scratch, 8, hipMemcpyDeviceToHost, s));
+  H2_HIP(hipStreamSynchronize(s));
+  return H2MI_OK;
+}
+
+int h2mi_plonk_shuffle_member_dev(const void* d_input, const void* d_input_sorted, const void* d_input_mult, uint32_t n_input_unique,
+                                  const void* d_shuffle_sorted, const void* d_shuffle_mult, uint32_t n_shuffle_unique, uint32_t usable_rows,
+                                  uint32_t report_out[2], h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_input || !d_input_sorted || !d_input_mult || !d_shuffle_sorted || !d_shuffle_mult || !report_out || n_input_unique == 0 || n_shuffle_unique == 0)
+    return H2MI_EINVAL;
+  if (usable_rows == 0 || usable_rows > (1u << H2MI_MAX_LOG_N) || n_input_unique > usable_rows || n_shuffle_unique > usable_rows) return H2MI_ERANGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  {
+    int rc0 = use_device(0);
+    if (rc0) return rc0;
+  }
+  hipStream_t s = pick_stream(stream);
+  {
+    int rcs = lk_scratch_reserve(4);
+    if (rcs) return rcs;
+  }
+  if (g_lk_event && g_lk_stream != s) H2_HIP(hipStreamWaitEvent(s, g_lk_event, 0));
+  const uint32_t init[2] = {0, 0xffffffffu};
+  H2_HIP(hipMemcpyAsync(g_lk_scratch, init, 8, hipMemcpyHostToDevice, s));
+  H2_LAUNCH("k_sf_member", k_sf_member, ceil_div_u32(usable_rows, 256), 256, 0, s, (const fe*)d_input, usable_rows, (const fe*)d_input_sorted,
+            (const uint32_t*)d_input_mult, n_input_unique, (const fe*)d_shuffle_sorted, (const uint32_t*)d_shuffle_mult, n_shuffle_unique, g_lk_scratch);
   H2_HIP(hipMemcpyAsync(report_out, g_lk_scratch, 8, hipMemcpyDeviceToHost, s));
   H2_HIP(hipStreamSynchronize(s));
   return H2MI_OK;

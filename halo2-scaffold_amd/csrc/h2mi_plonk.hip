@@ -291,6 +291,17 @@ __global__ void __launch_bounds__(256) k_lookup_numden(const fe* input, const fe
   fe_store(&num[i], pack261(f29_mul<F9>(f29_add(lift(&input[i]), b), f29_normalize(f29_add(lift(&table[i]), g)))));
   fe_store(&den[i], pack261(f29_mul<F9>(f29_add(lift(&pin[i]), b), f29_normalize(f29_add(lift(&ptab[i]), g)))));
 }
+// shuffle argument's grand product [RECALL halo2_proofs (PSE line) plonk/shuffle/prover.rs commit_product, restated in DESIGN.md 4.5]:
+// num_i = A_i + gamma, den_i = S_i + gamma over the compressed input and shuffle-side rows, i < u, as the canonical Montgomery-2^261
+// words the scans take.  No beta; the dense chain (mulscan, k_fr_inv_one, k_perm_ratio, k_perm_write_sets) follows unchanged.
+__global__ void __launch_bounds__(256) k_shuffle_numden(const fe* input, const fe* shuffle, fe gamma, uint32_t u, fe* num, fe* den) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= u) return;
+  const f29 g = f29_from_mont256<F9>(gamma.v), one = f29_const<F9>(F9::ONE);
+  // a sum of two converted values may pass the 2p pack261 takes: one multiplication by the Montgomery one brings it back below 1.1 p
+  fe_store(&num[i], pack261(f29_mul<F9>(f29_add(f29_from_mont256<F9>(fe_load(&input[i]).v), g), one)));
+  fe_store(&den[i], pack261(f29_mul<F9>(f29_add(f29_from_mont256<F9>(fe_load(&shuffle[i]).v), g), one)));
+}
 
 // Sparse form of the lookup grand product (round 3).  ratio_i = (a_i + beta)(t_i + gamma) / ((a'_i + beta)(s'_i + gamma)) is
 // exactly one wherever (a_i, t_i) = (a'_i, s'_i) — for a range check at DEGREE 22 on all but ~2^17 of 2^22 rows (input and
@@ -452,7 +463,7 @@ __global__ void __launch_bounds__(256) k_evaluate_h_range(RangeCosets c, uint32_
 // circuit is a small one by construction — and, being independent of the level bookkeeping, a cross-check of it: with one gate and
 // the selector form of the lookup input both kernels must produce the same h (tests/test_gpu_flex.py).
 struct FlexCosets {
-  uint32_t n_gates, n_perm, chunk, n_lookups;
+  uint32_t n_gates, n_perm, chunk, n_lookups, n_shuffles;
   const fe* gate_a[H2MI_FLEX_MAX_GATES];
   const fe* gate_q[H2MI_FLEX_MAX_GATES];
   const fe* perm_value[H2MI_FLEX_MAX_PERM];
@@ -464,6 +475,9 @@ struct FlexCosets {
   const fe* lk_pin[H2MI_FLEX_MAX_LOOKUPS];
   const fe* lk_ptab[H2MI_FLEX_MAX_LOOKUPS];
   const fe* lk_z[H2MI_FLEX_MAX_LOOKUPS];
+  const fe* sf_in[H2MI_MAX_SHUFFLES];   // shuffle arguments: the compressed input, the compressed shuffle side, the product
+  const fe* sf_tab[H2MI_MAX_SHUFFLES];
+  const fe* sf_z[H2MI_MAX_SHUFFLES];
   const fe* l0;
   const fe* l_last;
   const fe* l_active;
@@ -527,6 +541,15 @@ __device__ __forceinline__ void evaluate_h_fold(const Circuit& c, const FlexCose
     const f29 d = sub(ap, sp);
     horner(acc, y, mul(d, l0));
     horner(acc, y, mul(red(mul(d, sub(ap, ap_prev))), lact));
+  }
+  // the shuffle arguments [RECALL halo2_proofs (PSE line) plonk/evaluation.rs, restated in DESIGN.md 4.5]: behind the lookups, three
+  // terms each; the count is the launch's and the pointers come from the argument struct or the circuit's record (wave-uniform)
+  for (uint32_t s = 0; s < sh.n_shuffles; s++) {
+    const f29 a_in = ld(&c.sf_in[s][idx]), s_in = ld(&c.sf_tab[s][idx]);
+    const f29 sz = ld(&c.sf_z[s][idx]), sz_next = ld(&c.sf_z[s][r_next]);
+    horner(acc, y, mul(sub(one, sz), l0));
+    horner(acc, y, mul(red(sub(mul(sz, sz), sz)), ll));
+    horner(acc, y, mul(sub(mul(sz_next, add(s_in, gamma)), mul(sz, add(a_in, gamma))), lact));
   }
 }
 // the division by X^n - 1 behind the LAST circuit's terms, and the one store
@@ -649,6 +672,9 @@ struct CircuitCosets {
   const fe* lk_pin[H2MI_FLEX_MAX_LOOKUPS];
   const fe* lk_ptab[H2MI_FLEX_MAX_LOOKUPS];
   const fe* lk_z[H2MI_FLEX_MAX_LOOKUPS];
+  const fe* sf_in[H2MI_MAX_SHUFFLES];
+  const fe* sf_tab[H2MI_MAX_SHUFFLES];
+  const fe* sf_z[H2MI_MAX_SHUFFLES];
 };
 __global__ void __launch_bounds__(256) k_evaluate_h_expr_batch(FlexCosets sh, const CircuitCosets* __restrict__ circuits, uint32_t n_circuits,
                                                                 const fe* __restrict__ consts, const uint2* __restrict__ ops, uint32_t n_ops,
@@ -865,6 +891,17 @@ static bool fill_tail(FlexCosets& fc, const Cosets& c) {
   }
   fc.l0 = (const fe*)c.l0; fc.l_last = (const fe*)c.l_last; fc.l_active = (const fe*)c.l_active;
   return fc.l0 && fc.l_last && fc.l_active;
+}
+
+// the shuffle pointers of an h2mi_shuffle_cosets (NULL: none) -> the kernels' argument
+static bool fill_shuffles(FlexCosets& fc, const h2mi_shuffle_cosets* sc) {
+  fc.n_shuffles = sc ? sc->n_shuffles : 0;
+  if (fc.n_shuffles > H2MI_MAX_SHUFFLES) return false;
+  for (uint32_t s = 0; s < fc.n_shuffles; s++) {
+    fc.sf_in[s] = (const fe*)sc->input[s]; fc.sf_tab[s] = (const fe*)sc->shuffle[s]; fc.sf_z[s] = (const fe*)sc->z[s];
+    if (!fc.sf_in[s] || !fc.sf_tab[s] || !fc.sf_z[s]) return false;
+  }
+  return true;
 }
 
 // The program as the kernel reads it.  Every stack value carries a static bound in units of p (a converted load 1.04, a constant 1,
@@ -1165,6 +1202,48 @@ int h2mi_plonk_lookup_product_dev(const void* d_input, const void* d_table, cons
   return release_tmp(s);
 }
 
+int h2mi_plonk_shuffle_product_dev(const void* d_input, const void* d_shuffle, uint32_t k, uint32_t usable_rows, const uint64_t gamma[4], void* d_z,
+                                   h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_input || !d_shuffle || !gamma || !d_z) return H2MI_EINVAL;
+  if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k)) return H2MI_ERANGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  CallScope scope_;
+  hipStream_t s = pick_stream(stream);
+  const size_t u = usable_rows;
+  const uint32_t nblocks = ceil_div_u32(u, MS_TILE);
+  int rc = ensure_tmp(3 * u + 2 * (size_t)nblocks + 2, s);
+  if (rc) return rc;
+  fe* num = tmp_base();
+  fe* P = num + u;
+  fe* S = P + u;
+  fe* totals = S + u;
+  fe* offsets = totals + nblocks;
+  fe* inv_total = offsets + nblocks;
+  ZOut zo;
+  memset(&zo, 0, sizeof(zo));
+  zo.z[0] = (fe*)d_z;
+  H2_LAUNCH("k_shuffle_numden", k_shuffle_numden, ceil_div_u32(u, 256), 256, 0, s, (const fe*)d_input, (const fe*)d_shuffle, host_fe(gamma), usable_rows, num, P);
+  H2_HIP(hipMemcpyAsync(S, P, u * 32, hipMemcpyDeviceToDevice, s));
+  rc = mulscan(P, u, 0, totals, offsets, s);
+  if (!rc) rc = mulscan(S, u, 1, totals, offsets, s);
+  if (rc) return rc;
+  H2_LAUNCH("k_fr_inv_one", k_fr_inv_one, 1, 64, 0, s, (const fe*)(P + (u - 1)), inv_total);
+  H2_LAUNCH("k_perm_ratio", k_perm_ratio, ceil_div_u32(u, 256), 256, 0, s, (const fe*)num, (const fe*)P, (const fe*)S, (const fe*)inv_total, u, num);
+  rc = mulscan(num, u, 0, totals, offsets, s);
+  if (rc) return rc;
+  H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, dim3(ceil_div_u32((uint64_t)usable_rows + 1, 256), 1), 256, 0, s, (const fe*)num, usable_rows, zo,
+            (const uint32_t*)nullptr, 0u);
+  // the ONE comparison: a satisfied shuffle ends at one (the Montgomery-2^256 one, fully reduced as every stored value is)
+  fe last;
+  H2_HIP(hipMemcpyAsync(&last, (const fe*)d_z + u, sizeof(fe), hipMemcpyDeviceToHost, s));
+  H2_HIP(hipStreamSynchronize(s));
+  rc = release_tmp(s);
+  if (rc) return rc;
+  const fe one = h_canon(f29_const<F9>(F9::TO256));
+  return memcmp(last.v, one.v, sizeof(one.v)) ? H2MI_EUNSAT : H2MI_OK;
+}
+
 int h2mi_plonk_evaluate_h_range_dev(const h2mi_range_cosets* c, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
                                     const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
                                     const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
@@ -1273,6 +1352,15 @@ int h2mi_plonk_evaluate_h_expr_ch_dev(const h2mi_expr_cosets* c, const h2mi_gate
                                       uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
                                       const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out,
                                       h2mi_stream_t stream) {
+  return h2mi_plonk_evaluate_h_expr_sh_dev(c, nullptr, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma, y, delta, zeta,
+                                           extended_omega, t_inv, d_h_out, stream);
+}
+
+int h2mi_plonk_evaluate_h_expr_sh_dev(const h2mi_expr_cosets* c, const h2mi_shuffle_cosets* shuffles, const h2mi_gate_program* gates,
+                                      const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
+                                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
+                                      const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out,
+                                      h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!c || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
   if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
@@ -1283,7 +1371,7 @@ int h2mi_plonk_evaluate_h_expr_ch_dev(const h2mi_expr_cosets* c, const h2mi_gate
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
   FlexCosets fc;
   memset(&fc, 0, sizeof(fc));
-  if (!fill_tail(fc, *c)) return H2MI_EINVAL;
+  if (!fill_tail(fc, *c) || !fill_shuffles(fc, shuffles)) return H2MI_EINVAL;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
@@ -1311,6 +1399,15 @@ int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_expr_cosets* circuits, uint3
                                          uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
                                          const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
                                          const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
+  return h2mi_plonk_evaluate_h_expr_batch_sh_dev(circuits, nullptr, n_circuits, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma,
+                                                 y, delta, zeta, extended_omega, t_inv, d_h_out, stream);
+}
+
+int h2mi_plonk_evaluate_h_expr_batch_sh_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, uint32_t n_circuits,
+                                            const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k,
+                                            uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
+                                            const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
+                                            const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!circuits || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
   if (n_circuits == 0 || n_circuits > H2MI_MAX_CIRCUITS) return H2MI_EINVAL;
@@ -1326,7 +1423,7 @@ int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_expr_cosets* circuits, uint3
   static_assert(sizeof(CircuitCosets) % 8 == 0, "records are arrays of pointers");
   FlexCosets sh;
   memset(&sh, 0, sizeof(sh));
-  if (!fill_tail(sh, c0)) return H2MI_EINVAL;
+  if (!fill_tail(sh, c0) || !fill_shuffles(sh, shuffles)) return H2MI_EINVAL;
   const size_t rec_fe = (sizeof(CircuitCosets) + sizeof(fe) - 1) / sizeof(fe), prog_fe = im.image.size();
   im.image.resize(prog_fe + rec_fe * n_circuits);
   for (uint32_t i = 0; i < n_circuits; i++) {
@@ -1334,7 +1431,7 @@ int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_expr_cosets* circuits, uint3
     if (c.n_perm != c0.n_perm || c.chunk_len != c0.chunk_len || c.n_lookups != c0.n_lookups) return H2MI_EINVAL;
     FlexCosets fc;
     memset(&fc, 0, sizeof(fc));
-    if (!fill_tail(fc, c)) return H2MI_EINVAL;
+    if (!fill_tail(fc, c) || !fill_shuffles(fc, shuffles ? shuffles + i : nullptr) || fc.n_shuffles != sh.n_shuffles) return H2MI_EINVAL;
     // what the proof shares is read from entry 0: an entry that names other sigma or Lagrange cosets is a caller's mistake
     if (memcmp(fc.perm_sigma, sh.perm_sigma, sizeof(fc.perm_sigma)) || fc.l0 != sh.l0 || fc.l_last != sh.l_last || fc.l_active != sh.l_active) return H2MI_EINVAL;
     if (i) {  // every column the program reads is there (entry 0: im.build above)
@@ -1358,6 +1455,9 @@ int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_expr_cosets* circuits, uint3
     memcpy(rec.lk_pin, fc.lk_pin, sizeof(rec.lk_pin));
     memcpy(rec.lk_ptab, fc.lk_ptab, sizeof(rec.lk_ptab));
     memcpy(rec.lk_z, fc.lk_z, sizeof(rec.lk_z));
+    memcpy(rec.sf_in, fc.sf_in, sizeof(rec.sf_in));
+    memcpy(rec.sf_tab, fc.sf_tab, sizeof(rec.sf_tab));
+    memcpy(rec.sf_z, fc.sf_z, sizeof(rec.sf_z));
     memcpy((char*)&im.image[prog_fe] + sizeof(CircuitCosets) * i, &rec, sizeof(rec));
   }
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);

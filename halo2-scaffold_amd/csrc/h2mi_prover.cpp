@@ -184,6 +184,47 @@ int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_pro
   return H2MI_OK;
 }
 
+// the rules of h2mi_shuffle_program_check (include/h2mi_prover.h) [RECALL halo2_proofs (PSE line) plonk/shuffle.rs Argument::required_degree,
+// restated from memory and pinned to DESIGN.md 4.5].  slices: per shuffle the sub-programs of its input and its shuffle-side polynomials
+struct ShuffleSlices {
+  h2mi_gate_program input[H2MI_MAX_SHUFFLES], table[H2MI_MAX_SHUFFLES];
+};
+int check_shuffle_program(const h2mi_constraint_system& cs, const h2mi_shuffle_program* sp, uint32_t* degree_out, ShuffleSlices* slices,
+                          uint32_t n_challenges = 0) {
+  if (!sp || sp->n_shuffles == 0 || sp->n_shuffles > H2MI_MAX_SHUFFLES) return H2MI_EINVAL;
+  h2::ExprShape all;
+  {
+    h2mi_constraint_system any = cs;  // the structural rules and the query lists; the degree rule is per shuffle, below
+    any.degree = 0xffffffffu;
+    const int rc = check_program(any, &sp->exprs, &all, n_challenges);
+    if (rc) return rc;
+  }
+  uint32_t want = 0;
+  for (uint32_t i = 0; i < sp->n_shuffles; i++) {
+    if (sp->n_pairs[i] == 0 || sp->n_pairs[i] > H2MI_MAX_EXPR_OPS) return H2MI_EINVAL;
+    want += 2 * sp->n_pairs[i];
+  }
+  if (all.n_polys != want) return H2MI_EINVAL;
+  uint32_t pos = 0, degree = 0;
+  auto take = [&](uint32_t polys, h2mi_gate_program* out) {  // the next `polys` polynomials -> their largest degree
+    const uint32_t first = pos;
+    for (uint32_t seen = 0; seen < polys; pos++) seen += sp->exprs.ops[pos].op == H2MI_EXPR_END;
+    const h2mi_gate_program sub = {sp->exprs.ops + first, pos - first, sp->exprs.constants, sp->exprs.n_constants};
+    h2::ExprShape sh;
+    h2::expr_walk(&sub, cs.k, n_challenges, [](uint32_t, uint32_t, int32_t) { return true; }, &sh);  // validated above
+    if (out) *out = sub;
+    return sh.degree;
+  };
+  for (uint32_t i = 0; i < sp->n_shuffles; i++) {
+    const uint32_t in = take(sp->n_pairs[i], slices ? &slices->input[i] : nullptr), tab = take(sp->n_pairs[i], slices ? &slices->table[i] : nullptr);
+    const uint32_t d = 2 + std::max({1u, in, tab});
+    if (d > cs.degree) return H2MI_EINVAL;
+    degree = std::max(degree, d);
+  }
+  if (degree_out) *degree_out = degree;
+  return H2MI_OK;
+}
+
 // the rules of h2mi_advice_phases_check (include/h2mi_prover.h) [RECALL halo2_proofs v2023_02_02 plonk/circuit.rs advice_column_in,
 // challenge_usable_after]: a column in phase p > 0 needs one in phase p - 1 and a challenge usable after p needs a column in p — with
 // n_phases stated, that is: every phase below n_phases holds a column, every column and every challenge names a phase below it
@@ -204,7 +245,8 @@ int check_phases(const h2mi_constraint_system& cs, const h2mi_gate_program* gate
   return rc;
 }
 
-void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, const h2mi_advice_phases* phases) {
+void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, const h2mi_advice_phases* phases,
+              const h2mi_shuffle_program* shuffles) {
   auto bad = [](const char* what) { throw Error(H2MI_EINVAL, std::string("constraint system: ") + what); };
   const uint32_t n_ch = phases ? phases->n_challenges : 0;
   if (phases && check_phases(cs, gates, lookups, *phases)) bad("advice phases / challenges");
@@ -255,6 +297,10 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, 
   while (((uint64_t)1 << ext_k) < ((uint64_t)1 << cs.k) * (cs.degree - 1)) ext_k++;
   if (ext_k - cs.k > 4 || ext_k > H2MI_MAX_LOG_N) throw Error(H2MI_ERANGE, "constraint system: extended domain");
   if ((gates || lookups) && cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_gates / _exprs take H2MI_GATES_EXPRESSIONS");
+  if (shuffles) {
+    if (cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_shuffles takes H2MI_GATES_EXPRESSIONS");
+    if (check_shuffle_program(cs, shuffles, nullptr, nullptr, n_ch)) bad("shuffle program");
+  }
 }
 
 struct Table {  // a lookup table's distinct usable values in ascending canonical order, for the device's counting sort
@@ -286,6 +332,11 @@ struct h2mi_pk_s {
   std::vector<h2mi_expr_op> lookup_ops;
   std::vector<uint64_t> lookup_constants;
   LookupSlices lookup_slices;
+  // shuffle arguments (h2mi_prover_keygen_shuffles): the key's own copy, cut into each shuffle's input and shuffle-side polynomials
+  uint32_t n_shuffles = 0;
+  std::vector<h2mi_expr_op> shuffle_ops;
+  std::vector<uint64_t> shuffle_constants;
+  ShuffleSlices shuffle_slices;
   // advice phases and challenges (h2mi_prover_keygen_phases); every other keygen: one phase, no challenges
   h2mi_advice_phases phases;
   uint32_t phase_columns[H2MI_MAX_ADVICE_PHASES] = {0, 0, 0};
@@ -355,8 +406,8 @@ void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells) {
 
 std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                                   const h2mi_advice_phases* phases, uint64_t g_lagrange, const h2mi_column_cells* fixed, const uint32_t* copies,
-                                  size_t n_copies, unsigned flags) {
-  validate(cs, gates, lookups, phases);
+                                  size_t n_copies, unsigned flags, const h2mi_shuffle_program* shuffles = nullptr) {
+  validate(cs, gates, lookups, phases, shuffles);
   std::unique_ptr<h2mi_pk_s> pkp(new h2mi_pk_s(cs));
   h2mi_pk_s& pk = *pkp;
   std::memset(&pk.phases, 0, sizeof(pk.phases));
@@ -375,6 +426,14 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     h2mi_lookup_program own = *lookups;
     own.exprs = {pk.lookup_ops.data(), lookups->exprs.n_ops, pk.lookup_constants.data(), lookups->exprs.n_constants};
     if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices, pk.phases.n_challenges)) throw Error(H2MI_EINVAL, "lookup program");
+  }
+  if (shuffles) {
+    pk.n_shuffles = shuffles->n_shuffles;
+    pk.shuffle_ops.assign(shuffles->exprs.ops, shuffles->exprs.ops + shuffles->exprs.n_ops);
+    if (shuffles->exprs.n_constants) pk.shuffle_constants.assign(shuffles->exprs.constants, shuffles->exprs.constants + 4 * (size_t)shuffles->exprs.n_constants);
+    h2mi_shuffle_program own = *shuffles;
+    own.exprs = {pk.shuffle_ops.data(), shuffles->exprs.n_ops, pk.shuffle_constants.data(), shuffles->exprs.n_constants};
+    if (check_shuffle_program(cs, &own, nullptr, &pk.shuffle_slices, pk.phases.n_challenges)) throw Error(H2MI_EINVAL, "shuffle program");
   }
   pk.vk_only = (flags & H2MI_KEYGEN_VK_ONLY) != 0;
   if (gates) {
@@ -626,10 +685,17 @@ struct h2mi_prover_s {
     Dev table, in_coset, tab_coset;
     Table sorted;
   } lk[H2MI_MAX_LOOKUPS];
+  // shuffle arguments: both sides compressed with theta on the rows and on the extended coset, the product in its three forms
+  struct Sf {
+    Dev input, table, in_coset, tab_coset;
+    Forms z;
+  } sf[H2MI_MAX_SHUFFLES];
   // h2mi_prover_check's own scratch, allocated by its first call: a lookup's input and table rows, the table's sorted distinct values
+  // (a shuffle: both sides' rows, and the distinct values of both)
   Dev check_in, check_tab;
-  Table check_sorted;
+  Table check_sorted, check_sorted_in;
   Fr theta;
+  bool have_theta = false;  // a key with shuffles: h2mi_prover_lookups has delivered theta for this proof
   // the circuit's challenges (h2mi_prover_set_challenges): read by the lookups' compression and by the quotient
   std::vector<Fr> challenges;
   bool have_challenges = false;
@@ -714,8 +780,8 @@ struct h2mi_prover_s {
     std::memcpy(out, aff.data(), k * 64);
   }
   void forms(Forms& f, h2mi_stream_t stream) { to_poly_and_coset(pk->domain, *f.value, *f.poly, *f.coset, stream); }
-  // `count` blinding scalars for purpose 1 .. 5 (advice rows, permutation products, the random polynomial, permuted lookup columns,
-  // lookup products): the streams seed + purpose of the seeded generator, or ChaCha20 stream id (nonce << 3 | purpose) under the key
+  // `count` blinding scalars for purpose 1 .. 6 (advice rows, permutation products, the random polynomial, permuted lookup columns,
+  // lookup products, shuffle products): the streams seed + purpose of the seeded generator, or ChaCha20 stream id (nonce << 3 | purpose) under the key
   std::vector<Fr> blinding(uint32_t purpose, size_t count) const {
     return keyed ? chacha_fr(key, (seed << 3) | purpose, count) : uniform_fr(seed + purpose, count);
   }
@@ -742,7 +808,7 @@ typedef std::vector<h2mi_prover_s*> Circuits;
 // commitments of the largest phase: the result slots a prover (and a combiner's two buffers) must hold
 uint32_t max_phase_points(const h2mi_pk_s& pk) {
   const h2mi_constraint_system& cs = pk.cs;
-  return std::max({cs.n_advice, 2 * cs.n_lookups, pk.n_sets + cs.n_lookups + 1, cs.degree - 1, 8u});
+  return std::max({cs.n_advice, 2 * cs.n_lookups, pk.n_sets + cs.n_lookups + pk.n_shuffles + 1, cs.degree - 1, 8u});
 }
 
 std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t gl, size_t lo, size_t cnt) {
@@ -786,6 +852,14 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
     p.lk[l].a.alloc(n, ext);
     p.lk[l].s.alloc(n, ext);
     p.lk[l].z.alloc(n, ext);
+  }
+  for (uint32_t i = 0; i < pk->n_shuffles; i++) {
+    h2mi_prover_s::Sf& sf = p.sf[i];
+    sf.input = vec(n);
+    sf.table = vec(n);
+    sf.in_coset = vec(ext);
+    sf.tab_coset = vec(ext);
+    sf.z.alloc(n, ext);
   }
   p.random_poly = vec(n);
   p.h = vec(ext);
@@ -832,6 +906,7 @@ void phase_advice(h2mi_prover_s& p, uint32_t ph, const h2mi_column_cells* advice
     if (n_inst > u) throw Error(H2MI_ERANGE, "more public inputs than usable rows");
     p.seed = seed;
     p.have_challenges = false;
+    p.have_theta = false;
     p.instance_vals.resize(n_inst);
     if (n_inst) std::memcpy(p.instance_vals.data(), instance, n_inst * 32);
     if (cs.n_instance) {
@@ -891,6 +966,11 @@ void phase_lookups(h2mi_prover_s& p, const uint64_t* theta, uint64_t* points_out
   require_phase(p, ADVICE);
   p.require_challenges();
   p.phase = IDLE;
+  if (pk.n_shuffles) {  // the shuffles are compressed with theta in the products phase: this call carries it, lookups or none
+    if (!theta) throw Error(H2MI_EINVAL, "theta");
+    std::memcpy(p.theta.l, theta, 32);
+    p.have_theta = true;
+  }
   if (L) {
     const std::vector<Fr> lb = p.blinding(4, (size_t)2 * (bf + 1) * L);
     PatchList pl;
@@ -946,7 +1026,7 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
   const uint32_t u = pk.u, L = cs.n_lookups, m = cs.n_perm;
   if (p.phase != ADVICE && p.phase != LOOKUPS) throw Error(H2MI_EINVAL, "check: between the last advice phase and the products");
   if (pk.phases.n_challenges && !p.have_challenges) throw Error(H2MI_EINVAL, "check: h2mi_prover_set_challenges has not been called");
-  if (L && pk.lookup_exprs && !theta) throw Error(H2MI_EINVAL, "check: theta");
+  if (((L && pk.lookup_exprs) || pk.n_shuffles) && !theta) throw Error(H2MI_EINVAL, "check: theta");
   std::vector<h2mi_check_failure> out;
   const void *adv[H2MI_MAX_ADVICE], *fix[H2MI_MAX_FIXED];
   for (uint32_t j = 0; j < cs.n_advice; j++) adv[j] = p.advice[j].value->p;
@@ -1005,6 +1085,27 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
     check(h2mi_plonk_lookup_member_dev(input, t->sorted->p, t->n_unique, u, report, nullptr), "lookup_member");
     if (report[0]) out.push_back({H2MI_CHECK_LOOKUP, l, report[1], report[0]});
   }
+  for (uint32_t i = 0; i < pk.n_shuffles; i++) {  // both sides compressed and sorted; a row fails when its value is rarer on the other side
+    if (!p.check_in) p.check_in = vec(n);
+    if (!p.check_tab) p.check_tab = vec(n);
+    for (Table* t : {&p.check_sorted, &p.check_sorted_in})
+      if (!t->sorted) {
+        t->sorted = vec(u);
+        t->sorted_mont = vec(u);
+        t->mult = vec(u / 8 + 1);
+      }
+    Fr th;
+    std::memcpy(th.l, theta, 32);
+    p.compress(pk.shuffle_slices.input[i], false, *p.check_in, &th);
+    p.compress(pk.shuffle_slices.table[i], false, *p.check_tab, &th);
+    Table &ti = p.check_sorted_in, &ts = p.check_sorted;
+    check(h2mi_fr_sort_unique_dev(p.check_in->p, u, ti.sorted->p, ti.sorted_mont->p, ti.mult->p, &ti.n_unique, nullptr), "sort_unique");
+    check(h2mi_fr_sort_unique_dev(p.check_tab->p, u, ts.sorted->p, ts.sorted_mont->p, ts.mult->p, &ts.n_unique, nullptr), "sort_unique");
+    uint32_t report[2];
+    check(h2mi_plonk_shuffle_member_dev(p.check_in->p, ti.sorted->p, ti.mult->p, ti.n_unique, ts.sorted->p, ts.mult->p, ts.n_unique, u, report, nullptr),
+          "shuffle_member");
+    if (report[0]) out.push_back({H2MI_CHECK_SHUFFLE, i, report[1], report[0]});
+  }
   return out;
 }
 
@@ -1014,18 +1115,37 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
   const h2mi_constraint_system& cs = pk.cs;
   const size_t n = pk.n;
   const uint32_t bf = cs.blinding_factors, u = pk.u, L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
-  if (p.phase == ADVICE && L == 0) p.phase = LOOKUPS;  // nothing to permute: the lookup phase may be skipped
+  const uint32_t S = pk.n_shuffles;
+  if (p.phase == ADVICE && L == 0 && S == 0) p.phase = LOOKUPS;  // nothing to permute and no theta to deliver: the lookup phase may be skipped
   require_phase(p, LOOKUPS);
   p.require_challenges();
   p.phase = IDLE;
   p.beta = beta;
   p.gamma = gamma;
+  // shuffle arguments [RECALL halo2_proofs (PSE line) plonk/shuffle/prover.rs, restated in DESIGN.md 4.5]: both sides compressed on
+  // the rows, the product, its blinding rows.  In front of everything this phase queues: an unsatisfied shuffle (z[u] != 1) abandons
+  // the proof with no commitment in flight.  Their commitments follow the lookups' below, in transcript order.
+  if (S) {
+    if (!p.have_theta) throw Error(H2MI_EINVAL, "a key with shuffles takes theta through h2mi_prover_lookups");
+    const std::vector<Fr> szb = p.blinding(6, (size_t)bf * S);
+    PatchList pl;
+    for (uint32_t i = 0; i < S; i++) {
+      h2mi_prover_s::Sf& sf = p.sf[i];
+      p.compress(pk.shuffle_slices.input[i], false, *sf.input);
+      p.compress(pk.shuffle_slices.table[i], false, *sf.table);
+      const int rc = h2mi_plonk_shuffle_product_dev(sf.input->p, sf.table->p, cs.k, u, gamma.l, sf.z.value->p, nullptr);
+      if (rc == H2MI_EUNSAT) throw Error(H2MI_EUNSAT, "shuffle: the two sides are not the same multiset (ConstraintSystemFailure)");
+      check(rc, "shuffle_product");
+      for (uint32_t r = 0; r < bf; r++) pl.add(*sf.z.value, u + 1 + r, szb[(size_t)bf * i + r]);
+    }
+    pl.flush();
+  }
   // the random polynomial's commitment is written after the grand products' but depends on nothing: queued first, the one dense
   // MSM of this phase accumulates beside their latency-bound scans.  Result slot: where the transcript expects it.
   const bool random = p.draws_random();
   if (random) {
     p.random_vector(3, *p.random_poly, n);
-    p.commit(false, p.col(*p.random_poly), n_sets + L);
+    p.commit(false, p.col(*p.random_poly), n_sets + L + S);
   }
   // permutation argument: every set in one device pass, over the copy constraints' support when that is sparse
   const bool perm_sparse = (uint64_t)pk.n_active * 8 <= (uint64_t)n_sets * u;
@@ -1089,6 +1209,11 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
         p.commit(true, p.col(lz), slot++);
       }
     }
+    for (uint32_t i = 0; i < S; i++) {
+      check(h2mi_stream_wait(p.side, nullptr), "stream_wait");
+      p.forms(p.sf[i].z, p.side);
+      p.commit(true, p.col(*p.sf[i].z.value), slot++);
+    }
     if (random) slot++;  // the random polynomial's commitment, queued before the grand products
     check(h2mi_msm_flush(), "flush");
     p.read_points(slot, points_out);
@@ -1102,7 +1227,7 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
 // ---- phase 4: the quotient (plonk/evaluation.rs evaluate_h + vanishing division), its pieces committed ---------------------------
 // every extended-coset vector of one circuit as the interpreting quotient kernels take them: the columns a program may query through
 // one pointer table, the permutation argument, the lookups (given as expressions: compressed on the extended coset here)
-void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec) {
+void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_cosets& sc) {
   const h2mi_pk_s& pk = *p.pk;
   const h2mi_constraint_system& cs = pk.cs;
   const uint32_t L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
@@ -1140,6 +1265,15 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec) {
   ec.l0 = pk.l0->p;
   ec.l_last = pk.l_last->p;
   ec.l_active = pk.l_active->p;
+  std::memset(&sc, 0, sizeof(sc));
+  sc.n_shuffles = pk.n_shuffles;
+  for (uint32_t i = 0; i < pk.n_shuffles; i++) {  // compressed on the extended coset itself, as the lookups given as expressions are
+    p.compress(pk.shuffle_slices.input[i], true, *p.sf[i].in_coset);
+    p.compress(pk.shuffle_slices.table[i], true, *p.sf[i].tab_coset);
+    sc.input[i] = p.sf[i].in_coset->p;
+    sc.shuffle[i] = p.sf[i].tab_coset->p;
+    sc.z[i] = p.sf[i].z.coset->p;
+  }
 }
 
 // a joint phase of a batch: the members behind the leader must still be where their products left them (one that has started another
@@ -1175,11 +1309,12 @@ void phase_quotient(const Circuits& all, const Fr& y, uint64_t* points_out) {
     // several circuits (or a batch of one): ONE launch folds every circuit's terms into h, whatever the key's shape — a hard-wired
     // shape through the equivalent program keygen built for the witness check, which computes the same field elements
     std::vector<h2mi_expr_cosets> ec(all.size());
-    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i]);
+    std::vector<h2mi_shuffle_cosets> sc(all.size());
+    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i], sc[i]);
     const std::vector<Fr>& t_inv = d.t_inv();
-    check(h2mi_plonk_evaluate_h_expr_batch_dev(ec.data(), (uint32_t)ec.size(), &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
-                                               d.extended_k(), cs.blinding_factors, p.beta.l, p.gamma.l, y.l, pk.delta.l, d.get_g_coset().l,
-                                               d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
+    check(h2mi_plonk_evaluate_h_expr_batch_sh_dev(ec.data(), pk.n_shuffles ? sc.data() : nullptr, (uint32_t)ec.size(), &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
+                                                  d.extended_k(), cs.blinding_factors, p.beta.l, p.gamma.l, y.l, pk.delta.l, d.get_g_coset().l,
+                                                  d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
   }
   check(h2mi_ntt_bn254_fr_dev(h.p, d.extended_k(), d.get_extended_omega_inv().l, nullptr, nullptr, nullptr), "extended_to_coeff");
@@ -1220,9 +1355,11 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
   } else if (cs.gates == H2MI_GATES_EXPRESSIONS) {
     // gates given as a program: the interpreting kernel reads any column of the proof through one pointer table
     h2mi_expr_cosets ec;
-    fill_expr_cosets(p, ec);
-    check(h2mi_plonk_evaluate_h_expr_ch_dev(&ec, &pk.gate_program, p.challenge_limbs(), pk.phases.n_challenges, d.k(), d.extended_k(), bf, p.beta.l,
-                                            p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
+    h2mi_shuffle_cosets sc;
+    fill_expr_cosets(p, ec, sc);
+    check(h2mi_plonk_evaluate_h_expr_sh_dev(&ec, pk.n_shuffles ? &sc : nullptr, &pk.gate_program, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
+                                            d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l,
+                                            (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
   } else if (cs.n_gates == 1 && m >= 1 && m <= 4 && L <= 1) {
     // one gate column: the specialised kernel (its level bookkeeping is written for this shape; faster per point than the general one)
@@ -1292,11 +1429,11 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
   }
 }
 
-// per circuit: its advice queries, its permutation sets, its lookups; once per proof: the fixed queries, the random polynomial, sigma
+// per circuit: its advice queries, its permutation sets, its lookups, its shuffles; once per proof: the fixed queries, the random polynomial, sigma
 size_t num_evaluations(const h2mi_pk_s& pk, size_t n_circuits = 1) {
   const h2mi_constraint_system& cs = pk.cs;
   return n_circuits * cs.n_advice_queries + cs.n_fixed_queries + 1 + cs.n_perm +
-         n_circuits * ((pk.n_sets ? 3 * (size_t)pk.n_sets - 1 : 0) + 5 * (size_t)cs.n_lookups);
+         n_circuits * ((pk.n_sets ? 3 * (size_t)pk.n_sets - 1 : 0) + 5 * (size_t)cs.n_lookups + 2 * (size_t)pk.n_shuffles);
 }
 
 // ---- phase 5: every evaluation create_proof writes -------------------------------------------------------------------------------
@@ -1352,6 +1489,11 @@ void phase_evaluations(const Circuits& all, const Fr& x, uint64_t* evals_out) {
       written.push_back({c->lk[l].a.poly.get(), x});
       written.push_back({c->lk[l].a.poly.get(), x_inv});
       written.push_back({c->lk[l].s.poly.get(), x});
+    }
+  for (const h2mi_prover_s* c : all)  // every circuit's shuffles behind every circuit's lookups
+    for (uint32_t i = 0; i < pk.n_shuffles; i++) {
+      written.push_back({c->sf[i].z.poly.get(), x});
+      written.push_back({c->sf[i].z.poly.get(), x_next});
     }
   std::vector<Q> todo = written;
   todo.push_back({&h_poly, x});  // opened but not written (the verifier recomputes it)
@@ -1412,6 +1554,10 @@ void phase_evaluations(const Circuits& all, const Fr& x, uint64_t* evals_out) {
       q(c->lk[l].s.poly.get(), x);
       q(c->lk[l].a.poly.get(), x_inv);
       q(c->lk[l].z.poly.get(), x_next);
+    }
+    for (uint32_t i = 0; i < pk.n_shuffles; i++) {  // shuffles.open
+      q(c->sf[i].z.poly.get(), x);
+      q(c->sf[i].z.poly.get(), x_next);
     }
   }
   for (uint32_t i = 0; i < cs.n_fixed_queries; i++) q(pk.fixed_polys[cs.fixed_queries[i].column].get(), rot(cs.fixed_queries[i].rotation));
@@ -1717,6 +1863,32 @@ int h2mi_prover_keygen_phases(const h2mi_constraint_system* cs, const h2mi_gate_
   });
 }
 
+int h2mi_shuffle_program_check(const h2mi_constraint_system* cs, const h2mi_shuffle_program* shuffles, uint32_t* degree_out) {
+  if (!cs || !shuffles) return H2MI_EINVAL;
+  return check_shuffle_program(*cs, shuffles, degree_out, nullptr);
+}
+
+int h2mi_shuffle_phases_check(const h2mi_constraint_system* cs, const h2mi_shuffle_program* shuffles, const h2mi_advice_phases* phases,
+                              uint32_t* degree_out) {
+  if (!cs || !shuffles) return H2MI_EINVAL;
+  if (phases && phases->n_challenges > H2MI_MAX_CHALLENGES) return H2MI_EINVAL;
+  return check_shuffle_program(*cs, shuffles, degree_out, nullptr, phases ? phases->n_challenges : 0);
+}
+
+int h2mi_prover_keygen_shuffles(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
+                                const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles, uint64_t g_lagrange_handle,
+                                const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
+  if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)H2MI_KEYGEN_VK_ONLY)) return H2MI_EINVAL;
+  *pk_out = nullptr;
+  if (h2mi_device_count() == 0) return H2MI_ENODEV;
+  return guarded([&] {
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, phases, g_lagrange_handle, fixed, copies, n_copies, flags, shuffles);
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    g_live_pks.insert(pk.get());
+    *pk_out = pk.release();
+  });
+}
+
 int h2mi_prover_pk_release(h2mi_pk_t pk) {
   {
     std::lock_guard<std::mutex> lk(g_reg_mu);
@@ -1794,7 +1966,7 @@ int h2mi_prover_get_counts(h2mi_prover_t prover, h2mi_prover_counts* out) {
   const h2mi_pk_s& pk = *prover->pk;
   out->advice = pk.cs.n_advice;
   out->lookups = 2 * pk.cs.n_lookups;
-  out->products = pk.n_sets + pk.cs.n_lookups + (prover->draws_random() ? 1 : 0);
+  out->products = pk.n_sets + pk.cs.n_lookups + pk.n_shuffles + (prover->draws_random() ? 1 : 0);
   out->quotient = pk.cs.degree - 1;
   out->evaluations = (uint32_t)num_evaluations(pk);
   return H2MI_OK;
@@ -1938,7 +2110,7 @@ int h2mi_batch_quotient(h2mi_batch_t batch, const uint64_t y[4], uint64_t* point
     if (!(m->beta == m0.beta) || !(m->gamma == m0.gamma)) return H2MI_EINVAL;
     if (m->pk->phases.n_challenges && !std::equal(m->challenges.begin(), m->challenges.end(), m0.challenges.begin(), m0.challenges.end())) return H2MI_EINVAL;
   }
-  // blinding streams that could overlap would open two columns with the same blinding: seeded streams are seed + purpose (1 .. 5),
+  // blinding streams that could overlap would open two columns with the same blinding: seeded streams are seed + purpose (1 .. 6),
   // keyed ones nonce << 3 | purpose under the key
   for (size_t i = 0; i < all.size(); i++)
     for (size_t j = 0; j < i; j++) {
@@ -1995,6 +2167,10 @@ int h2mi_prover_buffer(h2mi_prover_t prover, uint32_t kind, uint32_t index, void
     case H2MI_BUF_H_POLY: return pick(p.h_poly, index, d_ptr_out, count_out);
     case H2MI_BUF_SHPLONK_H: return pick(p.h_x, index, d_ptr_out, count_out);
     case H2MI_BUF_SHPLONK_H2: return pick(p.h2_x, index, d_ptr_out, count_out);
+    case H2MI_BUF_SHUFFLE_Z: return index < p.pk->n_shuffles ? pick(p.sf[index].z.value, 0, d_ptr_out, count_out) : H2MI_ERANGE;
+    case H2MI_BUF_SHUFFLE_Z_POLY: return index < p.pk->n_shuffles ? pick(p.sf[index].z.poly, 0, d_ptr_out, count_out) : H2MI_ERANGE;
+    case H2MI_BUF_SHUFFLE_INPUT: return index < p.pk->n_shuffles ? pick(p.sf[index].input, 0, d_ptr_out, count_out) : H2MI_ERANGE;
+    case H2MI_BUF_SHUFFLE_TABLE: return index < p.pk->n_shuffles ? pick(p.sf[index].table, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     default: return h2mi_prover_pk_buffer(p.pk, kind, index, d_ptr_out, count_out);
   }
 }

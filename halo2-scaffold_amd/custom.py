@@ -27,6 +27,10 @@ later phase needs a column in the one before), `challenge_usable_after(phase)` (
 order), `query_challenge` -> an Expression of degree 0 that any gate and either side of any lookup may hold.  `Keys` then goes through
 h2mi_prover_keygen_phases, and `create_proof` takes synthesize(challenges) -> Assignment in place of an Assignment: it is called once
 per advice phase with the challenges squeezed so far, and only that phase's columns are taken from what it returns.
+Shuffles [RECALL halo2_proofs, PSE line, plonk/shuffle.rs — restated from memory and pinned to DESIGN.md 4.5, not to the crate]:
+`meta.shuffle(name, |meta| vec![(input, shuffle), ..])` states that the two tuples take the same multiset of values over the usable
+rows; required degree 2 + max(1, input degrees, shuffle degrees).  `shuffle_program()` compiles them to an h2mi_shuffle_program and
+`Keys` goes through h2mi_prover_keygen_shuffles — only for a circuit that has shuffles: every other circuit takes the calls it took.
 `mock` is MockProver::run(..).assert_satisfied() on the host, row by row in Python integers; `check` asks the same question of the
 device, at the sizes the prover runs at (h2mi_prover_check: gates, copy constraints and lookups on the columns of a proof in flight).
 """
@@ -219,6 +223,7 @@ class ConstraintSystem:
         self.advice_queries, self._fixed_queries, self.instance_queries = [], [], []
         self.gate_names, self._polys = [], []       # one entry per polynomial, selectors unresolved
         self.lookup_names, self._lookups = [], []   # per lookup [(input, table)] expressions, selectors unresolved
+        self.shuffle_names, self._shuffles = [], []  # per shuffle [(input, shuffle)] expressions, selectors unresolved
         self.advice_phase, self.challenge_phase = [], []  # per advice column its phase; per challenge the phase it is usable after
 
     # ---- columns -----------------------------------------------------------------------------------------------------
@@ -300,6 +305,15 @@ class ConstraintSystem:
 
     lookup_any = lookup  # any expression on the table side: advice columns, rotations
 
+    def shuffle(self, name: str, shuffle_map) -> int:
+        """meta.shuffle: shuffle_map(meta) -> [(input Expression, shuffle Expression)]; the queries it makes enter the query lists in
+        first-use order.  -> the shuffle's index"""
+        pairs = [(Expression._wrap(a), Expression._wrap(s)) for a, s in shuffle_map(self)]
+        assert pairs, "a shuffle needs at least one (input, shuffle) pair"
+        self.shuffle_names.append(name)
+        self._shuffles.append(pairs)
+        return len(self._shuffles) - 1
+
     # ---- what keygen and create_proof read off it ------------------------------------------------------------------------
     @property
     def n_fixed(self) -> int:
@@ -326,9 +340,14 @@ class ConstraintSystem:
     def lookups(self):
         return [[(a.resolve(self.n_user_fixed), t.resolve(self.n_user_fixed)) for a, t in pairs] for pairs in self._lookups]
 
+    @property
+    def shuffles(self):
+        return [[(a.resolve(self.n_user_fixed), s.resolve(self.n_user_fixed)) for a, s in pairs] for pairs in self._shuffles]
+
     def degree(self) -> int:
         lookups = [max(4, 2 + max([1] + [a.degree() for a, _ in pairs]) + max([1] + [t.degree() for _, t in pairs])) for pairs in self._lookups]
-        return max([3] + [p.degree() for p in self._polys] + lookups)
+        shuffles = [2 + max([1] + [a.degree() for a, _ in pairs] + [s.degree() for _, s in pairs]) for pairs in self._shuffles]
+        return max([3] + [p.degree() for p in self._polys] + lookups + shuffles)
 
     def blinding_factors(self) -> int:
         per_column = [sum(1 for c, _ in self.advice_queries if c == j) for j in range(self.n_advice)]
@@ -353,6 +372,16 @@ class ConstraintSystem:
             for e in [a for a, _ in pairs] + [t for _, t in pairs]:
                 ops += e.program(constants)[0]
         return engine.LookupProgram.build([len(pairs) for pairs in self._lookups], ops, sorted(constants, key=constants.get))
+
+    def shuffle_program(self):
+        """the shuffles -> engine.ShuffleProgram (per shuffle its input polynomials, then its shuffle-side polynomials), None without"""
+        if not self._shuffles:
+            return None
+        constants, ops = {}, []
+        for pairs in self.shuffles:
+            for e in [a for a, _ in pairs] + [s for _, s in pairs]:
+                ops += e.program(constants)[0]
+        return engine.ShuffleProgram.build([len(pairs) for pairs in self._shuffles], ops, sorted(constants, key=constants.get))
 
     @property
     def n_phases(self) -> int:
@@ -422,7 +451,8 @@ class Assignment:
 def mock(asg: Assignment, k: int, challenges=()) -> None:
     """MockProver::run(k, ..).assert_satisfied() on the host: no cell or copy constraint beyond the usable rows, every gate polynomial
     zero on every usable row (unassigned cells are zero; rotations wrap around 2^k), every copy constraint between equal cells, every
-    lookup's input tuple on a usable row equal to its table tuple on some usable row.  challenges: the values the gates and lookups
+    lookup's input tuple on a usable row equal to its table tuple on some usable row, every shuffle's input tuples over the usable rows
+    the same multiset as its shuffle-side tuples.  challenges: the values the gates and lookups
     read (MockProver derives its own; here the caller states the ones the witness was made with).
     Raises ValueError naming the first violation."""
     cs = asg.cs
@@ -450,6 +480,10 @@ def mock(asg: Assignment, k: int, challenges=()) -> None:
         for row in range(u):
             if tuple(at(a, row) for a, _ in pairs) not in table:
                 raise ValueError(f"lookup {name!r} not satisfied at row {row}")
+    for name, pairs in zip(cs.shuffle_names, cs.shuffles):
+        at = lambda e, row: e.evaluate(lambda kind, c, rot: value[kind](c, (row + rot) % n), challenges)
+        if sorted(tuple(at(a, row) for a, _ in pairs) for row in range(u)) != sorted(tuple(at(s, row) for _, s in pairs) for row in range(u)):
+            raise ValueError(f"shuffle {name!r} not satisfied: the two sides are not the same multiset over the usable rows")
 
 
 class Keys:
@@ -467,7 +501,7 @@ class Keys:
         index = {col: j for j, col in enumerate(cs.perm_columns)}
         copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
         self.keys = engine.Keys(cs.abi(k), params, list(asg.fixed), copies, gates=cs.gate_program(), lookups=cs.lookup_program(),
-                                phases=cs.phases())
+                                phases=cs.phases(), shuffles=cs.shuffle_program())
         self.fixed_commitments, self.permutation_commitments = self.keys.fixed_commitments, self.keys.permutation_commitments
         nf, m = cs.n_fixed, len(cs.perm_columns)
         self.fixed_values, self.fixed_polys, self.fixed_cosets = (self.keys.views(kd, nf) for kd in (engine.PKBUF_FIXED, engine.PKBUF_FIXED_POLY, engine.PKBUF_FIXED_COSET))
@@ -555,7 +589,7 @@ def prove_many(pk, assignments, instances=None, seeds=None, params: ParamsKZG = 
 def check(params: ParamsKZG, keys: Keys, asg, seed: int = 1, ws: Workspace = None, trace: dict = None) -> None:
     """`mock` on the device, at the sizes the prover runs at (h2mi_prover_check, include/h2mi_prover.h): the advice phase(s) with the
     transcript exactly as create_proof starts — asg an Assignment or synthesize(challenges) — then the check, and the proof is dropped.
-    Raises ValueError in mock's words for the first violation (gates in create_gate order, then copy constraints, then lookups) with
+    Raises ValueError in mock's words for the first violation (gates in create_gate order, then copy constraints, then lookups, then shuffles) with
     the number of rows or cells that fail; the whole report is the exception's `failures`.  Unlike mock it tests the gates on the
     blinding rows too: a gate that no selector switches off there fails at a row at or beyond the usable rows — the verifier looks
     there as well."""
@@ -569,6 +603,8 @@ def check(params: ParamsKZG, keys: Keys, asg, seed: int = 1, ws: Workspace = Non
         elif f.kind == engine.CHECK_COPY:
             kind, column = cs.perm_columns[f.index]
             msg = f"copy constraint at cell {(kind, column, f.row)} not satisfied ({f.count} cells differ from their copy)"
+        elif f.kind == engine.CHECK_SHUFFLE:
+            msg = f"shuffle {cs.shuffle_names[f.index]!r} not satisfied at row {f.row} ({f.count} rows whose input is rarer on the shuffle side)"
         else:
             msg = f"lookup {cs.lookup_names[f.index]!r} not satisfied at row {f.row} ({f.count} rows)"
         e = ValueError(msg)

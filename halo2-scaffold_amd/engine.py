@@ -23,11 +23,13 @@ CELLS_CANONICAL = 1
 KEYGEN_VK_ONLY = 1
 EUNSAT = -7
 MAX_GATES, MAX_PERM, MAX_LOOKUPS, MAX_QUERIES = 32, 64, 8, 192  # H2MI_MAX_* (include/h2mi_prover.h)
+MAX_SHUFFLES = 8  # H2MI_MAX_SHUFFLES (include/h2mi.h)
 MAX_ADVICE, MAX_CHALLENGES, MAX_ADVICE_PHASES = 64, 16, 3
 
 # h2mi_prover_buffer kinds
 (BUF_ADVICE, BUF_ADVICE_POLY, BUF_ADVICE_COSET, BUF_INSTANCE, BUF_PERM_Z, BUF_PERM_Z_POLY, BUF_PERM_Z_COSET, BUF_LOOKUP_PERMUTED_INPUT,
- BUF_LOOKUP_PERMUTED_TABLE, BUF_LOOKUP_Z, BUF_RANDOM_POLY, BUF_H, BUF_H_POLY, BUF_SHPLONK_H, BUF_SHPLONK_H2) = range(15)
+ BUF_LOOKUP_PERMUTED_TABLE, BUF_LOOKUP_Z, BUF_RANDOM_POLY, BUF_H, BUF_H_POLY, BUF_SHPLONK_H, BUF_SHPLONK_H2, BUF_SHUFFLE_Z, BUF_SHUFFLE_Z_POLY,
+ BUF_SHUFFLE_INPUT, BUF_SHUFFLE_TABLE) = range(19)
 (PKBUF_FIXED, PKBUF_FIXED_POLY, PKBUF_FIXED_COSET, PKBUF_SIGMA, PKBUF_SIGMA_POLY, PKBUF_SIGMA_COSET, PKBUF_L0_COSET, PKBUF_L_LAST_COSET,
  PKBUF_L_ACTIVE_COSET) = range(64, 73)
 
@@ -132,6 +134,34 @@ class LookupProgram(C.Structure):
         return degree.value
 
 
+class ShuffleProgram(C.Structure):
+    """h2mi_shuffle_program: the shuffle arguments of a constraint system — per shuffle its n_pairs input polynomials, then its n_pairs
+    shuffle-side polynomials, in one postfix program"""
+    _fields_ = [("n_shuffles", C.c_uint32), ("n_pairs", C.c_uint32 * MAX_SHUFFLES), ("exprs", GateProgram)]
+
+    @classmethod
+    def build(cls, n_pairs, ops, constants) -> "ShuffleProgram":
+        """n_pairs: pairs per shuffle (more than H2MI_MAX_SHUFFLES entries are counted, not stored: the check refuses them); ops /
+        constants as GateProgram.build takes them"""
+        sp = cls()
+        sp.n_shuffles = len(n_pairs)
+        for i, m in enumerate(n_pairs[:MAX_SHUFFLES]):
+            sp.n_pairs[i] = m
+        sp._exprs = GateProgram.build(ops, constants)  # keeps the arrays alive
+        sp.exprs = sp._exprs
+        return sp
+
+    def check(self, cs: "ConstraintSystem", phases: "AdvicePhases" = None) -> int:
+        """h2mi_shuffle_program_check (h2mi_shuffle_phases_check when `phases` is given: CHALLENGE ops allowed) -> the largest required
+        degree; H2miError(-1) for a program keygen would refuse"""
+        degree = C.c_uint32()
+        if phases is None:
+            check(lib.h2mi_shuffle_program_check(C.byref(cs), C.byref(self), C.byref(degree)), "shuffle_program_check")
+        else:
+            check(lib.h2mi_shuffle_phases_check(C.byref(cs), C.byref(self), C.byref(phases), C.byref(degree)), "shuffle_phases_check")
+        return degree.value
+
+
 class AdvicePhases(C.Structure):
     """h2mi_advice_phases: the phase of every advice column and of every challenge (meta.advice_column_in, meta.challenge_usable_after)"""
     _fields_ = [("n_phases", C.c_uint32), ("advice_phase", C.c_uint32 * MAX_ADVICE), ("n_challenges", C.c_uint32),
@@ -168,7 +198,7 @@ def shape_gate_program(cs: "ConstraintSystem", ops_cap: int = None, constants_ca
     return ([(o.op, o.index, o.rotation) for o in ops[:n_ops.value]], [F.fr_from_mont_limbs(consts[i]) for i in range(n_constants.value)])
 
 
-CHECK_GATE, CHECK_COPY, CHECK_LOOKUP = 0, 1, 2  # h2mi_check_failure.kind
+CHECK_GATE, CHECK_COPY, CHECK_LOOKUP, CHECK_SHUFFLE = 0, 1, 2, 3  # h2mi_check_failure.kind
 
 
 class CheckFailure(C.Structure):
@@ -176,7 +206,7 @@ class CheckFailure(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("row", C.c_uint32), ("count", C.c_uint32)]
 
     def __repr__(self):
-        return f"CheckFailure({('GATE', 'COPY', 'LOOKUP')[self.kind]}, index={self.index}, row={self.row}, count={self.count})"
+        return f"CheckFailure({('GATE', 'COPY', 'LOOKUP', 'SHUFFLE')[self.kind]}, index={self.index}, row={self.row}, count={self.count})"
 
     def astuple(self):
         return self.kind, self.index, self.row, self.count
@@ -262,13 +292,18 @@ class Keys:
     constrain_equal in call order, columns as indices into the permutation argument.  `params` is the WHOLE SRS."""
 
     def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False, gates: GateProgram = None,
-                 lookups: LookupProgram = None, phases: AdvicePhases = None):
+                 lookups: LookupProgram = None, phases: AdvicePhases = None, shuffles: ShuffleProgram = None):
         self.cs = cs
+        self.n_shuffles = shuffles.n_shuffles if shuffles is not None else 0
         cells, keep = pack_cells(fixed)
         cp = np.ascontiguousarray(np.array(copies, dtype=np.uint32).reshape(-1, 4))
         h = C.c_void_p()
         flags = KEYGEN_VK_ONLY if vk_only else 0
-        if phases is not None:  # advice columns of a later phase, challenges: h2mi_prover_keygen_exprs with the phases beside it
+        if shuffles is not None:  # shuffle arguments: h2mi_prover_keygen_phases with the shuffles beside it; every other circuit takes the calls below
+            check(lib.h2mi_prover_keygen_shuffles(C.byref(cs), C.byref(gates), C.byref(lookups) if lookups is not None else None,
+                                                  C.byref(phases) if phases is not None else None, C.byref(shuffles), params.g_lagrange_handle, cells,
+                                                  cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
+        elif phases is not None:  # advice columns of a later phase, challenges: h2mi_prover_keygen_exprs with the phases beside it
             check(lib.h2mi_prover_keygen_phases(C.byref(cs), C.byref(gates), C.byref(lookups) if lookups is not None else None, C.byref(phases),
                                                 params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
         elif gates is None:
@@ -367,7 +402,8 @@ class Prover:
             e, self._cb_error = self._cb_error, None
             raise e
         if rc == EUNSAT:
-            raise ValueError("lookup input not in the table (ConstraintSystemFailure)")
+            raise ValueError("shuffle sides are not the same multiset (ConstraintSystemFailure)" if what == "products" else
+                             "lookup input not in the table (ConstraintSystemFailure)")
         check(rc, what)
 
     def check(self, theta=None, cap: int = 64) -> list:
@@ -442,7 +478,7 @@ class Prover:
                 trace["check"], trace["theta"] = failures, F.fr_from_mont_limbs(theta)
             if witness_check == "only":
                 return failures
-        if c.lookups:
+        if c.lookups or self.keys.n_shuffles:  # a key with shuffles takes theta through this call even without lookups (no points then)
             self._phase(lib.h2mi_prover_lookups(h, theta.ctypes.data, pp), "lookups")
             write_points(c.lookups)
             mark("permuted lookup columns committed")
@@ -542,12 +578,13 @@ class Batch:
             for p in ms:
                 p._phase(lib.h2mi_prover_set_challenges(p.handle, ch.ctypes.data), "set_challenges")
         theta = sq()
-        if c.lookups:
+        n_sh = lead.keys.n_shuffles
+        if c.lookups or n_sh:
             for p in ms:
                 p._phase(lib.h2mi_prover_lookups(p.handle, theta.ctypes.data, p._points.ctypes.data), "lookups")
                 write(points(p, c.lookups))
         beta, gamma = sq(), sq()
-        n_sets = c.products - 1 - c.lookups // 2
+        n_sets = c.products - 1 - c.lookups // 2 - n_sh
         products = []
         for p in ms:
             p._phase(lib.h2mi_prover_products(p.handle, beta.ctypes.data, gamma.ctypes.data, p._points.ctypes.data), "products")
@@ -556,7 +593,9 @@ class Batch:
             write(pts[:n_sets])
         for pts in products:
             write(pts[n_sets:n_sets + c.lookups // 2])
-        write(products[0][n_sets + c.lookups // 2:])
+        for pts in products:  # every circuit's shuffle products behind every circuit's lookup products
+            write(pts[n_sets + c.lookups // 2:n_sets + c.lookups // 2 + n_sh])
+        write(products[0][n_sets + c.lookups // 2 + n_sh:])
         if "products_done" in hooks:
             hooks["products_done"](self)
         y = sq()
@@ -586,4 +625,4 @@ class Batch:
                     check(lib.h2mi_prover_get_counts(p.handle, C.byref(p.counts)), "prover counts")
 
 
-__all__ = ["ConstraintSystem", "Keys", "Prover", "Batch", "DevView", "H2miError"]
+__all__ = ["ConstraintSystem", "Keys", "Prover", "Batch", "DevView", "H2miError", "ShuffleProgram"]

@@ -157,6 +157,17 @@ def lookup_product(k: int, d_input: DevBuf, d_table: DevBuf, d_permuted_input: D
                                              g_.ctypes.data, d_z.ptr, None), "lookup_product")
 
 
+def shuffle_product(k: int, d_input: DevBuf, d_shuffle: DevBuf, gamma: int, usable_rows: int, d_z: DevBuf) -> bool:
+    """h2mi_plonk_shuffle_product_dev: z[0] = 1, z[i+1] = z[i] (A_i + gamma) / (S_i + gamma) on rows 0 .. usable_rows of d_z over the
+    compressed rows of the two sides -> True when z[usable_rows] is one (the sides are the same multiset), False for H2MI_EUNSAT; z is
+    written either way"""
+    rc = lib.h2mi_plonk_shuffle_product_dev(d_input.ptr, d_shuffle.ptr, k, usable_rows, F.fr_to_mont_limbs(gamma).ctypes.data, d_z.ptr, None)
+    if rc == -7:  # H2MI_EUNSAT
+        return False
+    _check(rc, "shuffle_product")
+    return True
+
+
 class _RangeCosets(C.Structure):
     _fields_ = [("a", C.c_void_p), ("lookup_advice", C.c_void_p), ("lookup_selector", C.c_void_p), ("q", C.c_void_p), ("table", C.c_void_p),
                 ("perm_value", C.c_void_p * 4), ("perm_sigma", C.c_void_p * 4), ("perm_z", C.c_void_p * 4), ("lookup_permuted_input", C.c_void_p),

@@ -349,6 +349,15 @@ int h2mi_plonk_instance_coset_dev(const void* d_l0_coset, uint32_t k, uint32_t e
  * other streams keep running) */
 int h2mi_plonk_lookup_product_dev(const void* d_input, const void* d_table, const void* d_permuted_input, const void* d_permuted_table, uint32_t k,
                                   uint32_t usable_rows, const uint64_t beta[4], const uint64_t gamma[4], void* d_z, h2mi_stream_t stream);
+/* The shuffle argument's product [RECALL halo2_proofs (PSE line) plonk/shuffle/prover.rs commit_product — restated from memory like
+ * the rest, pinned to DESIGN.md 4.5 and not to the crate]: z[0] = 1, z[i+1] = z[i] (A_i + gamma) / (S_i + gamma), i < usable_rows, over
+ * the compressed input rows d_input and the compressed shuffle-side rows d_shuffle; rows 0 .. usable_rows of d_z are written, the
+ * blinding rows untouched; one field inversion per call.  Dense form only: a shuffle that leaves most rows in place has no use.
+ * H2MI_EUNSAT: z[usable_rows] is not one — the two sides are not the same multiset (z is written all the same); the call reads that one
+ * element back, i.e. it waits for the work queued on `stream`.  A row with S_i + gamma = 0 (probability usable_rows / r over gamma)
+ * gets no special handling: the one inversion is then of zero and z is meaningless. */
+int h2mi_plonk_shuffle_product_dev(const void* d_input, const void* d_shuffle, uint32_t k, uint32_t usable_rows, const uint64_t gamma[4], void* d_z,
+                                   h2mi_stream_t stream);
 /* evaluate_h + vanishing division for the halo2-lib constraint systems [halo2-base shapes restated from memory]: gate
  * q (a + a(wX) a(w^2 X) - a(w^3 X)), permutation argument over n_perm <= 4 columns in chunks of chunk_len (= cs.degree()
  * - 2 = 1 .. 3), and — has_lookup (the Range builder, extended domain 4n) — one lookup in `table` of either
@@ -491,6 +500,29 @@ int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_expr_cosets* circuits, uint3
                                          uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
                                          const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
                                          const uint64_t* t_inv /* 2^(extended_k-k) x 4 */, void* d_h_out, h2mi_stream_t stream);
+/* The two calls above with shuffle arguments [RECALL halo2_proofs (PSE line) plonk/shuffle.rs, plonk/evaluation.rs — restated from
+ * memory, pinned to DESIGN.md 4.5]: behind a circuit's lookup terms, per shuffle, l_0 (1 - z), l_last (z^2 - z), l_active (z(wX) (S +
+ * gamma) - z(X) (A + gamma)), Horner in y; beta is not read.  input / shuffle: both sides compressed with theta on the extended coset
+ * (h2mi_plonk_expr_compress_dev at domain_k = extended_k); z: the product's extended-coset form.  `shuffles` is one entry (the batch
+ * call: n_circuits entries, all with the same n_shuffles) or NULL, which is the call above word for word.  H2MI_EINVAL: n_shuffles >
+ * H2MI_MAX_SHUFFLES, a NULL vector. */
+#define H2MI_MAX_SHUFFLES 8
+typedef struct {
+  uint32_t n_shuffles;
+  const void* input[H2MI_MAX_SHUFFLES];
+  const void* shuffle[H2MI_MAX_SHUFFLES];
+  const void* z[H2MI_MAX_SHUFFLES];
+} h2mi_shuffle_cosets;
+int h2mi_plonk_evaluate_h_expr_sh_dev(const h2mi_expr_cosets* cosets, const h2mi_shuffle_cosets* shuffles, const h2mi_gate_program* gates,
+                                      const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
+                                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
+                                      const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out,
+                                      h2mi_stream_t stream);
+int h2mi_plonk_evaluate_h_expr_batch_sh_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, uint32_t n_circuits,
+                                            const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k,
+                                            uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
+                                            const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
+                                            const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream);
 
 /* A lookup's expressions compressed with theta (plonk/lookup/prover.rs compress_expressions): `exprs` holds m polynomials e_0 ..
  * e_(m-1) and d_out[i] = sum_j e_j(i) theta^(m-1-j) — the fold acc theta + e_j — for the 2^domain_k points the columns are given on:
@@ -529,6 +561,13 @@ int h2mi_plonk_copy_check_dev(const void* const* d_values, uint32_t m, const voi
  * h2mi_plonk_lookup_permute_dev counts the same rows but cannot say which. */
 int h2mi_plonk_lookup_member_dev(const void* d_input, const void* d_table_sorted, uint32_t n_unique, uint32_t usable_rows, uint32_t report_out[2],
                                  h2mi_stream_t stream);
+/* Shuffle multiplicities: both sides sorted by h2mi_fr_sort_unique_dev (ascending canonical distinct values and their u32
+ * multiplicities).  report_out (host) = {rows i < usable_rows whose d_input[i] (Montgomery) occurs more often among the inputs than on
+ * the shuffle side — not at all included —, the smallest such row or 0xffffffff}.  Both sides hold usable_rows values, so unequal
+ * multisets always report at least one row. */
+int h2mi_plonk_shuffle_member_dev(const void* d_input, const void* d_input_sorted, const void* d_input_mult, uint32_t n_input_unique,
+                                  const void* d_shuffle_sorted, const void* d_shuffle_mult, uint32_t n_shuffle_unique, uint32_t usable_rows,
+                                  uint32_t report_out[2], h2mi_stream_t stream);
 
 /* ---- SRS generation helper: ParamsKZG::setup's g[i] = s_i * G   ------------------
  * d_scalars: n Fr (Montgomery).  d_out_affine: n G1Affine.  Fixed-base windowed multiplication of the

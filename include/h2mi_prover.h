@@ -48,7 +48,10 @@
  *                              through h2mi_prover_keygen_exprs), compressed with theta and sorted inside each proof.  Advice columns
  *                              of a later phase and challenges (h2mi_advice_phases; keygen through h2mi_prover_keygen_phases): the
  *                              advice is then committed phase by phase (h2mi_prover_advice_phase) with the caller squeezing the
- *                              challenges in between, and gates and lookups may read them
+ *                              challenges in between, and gates and lookups may read them.  Shuffle arguments (`meta.shuffle` of
+ *                              the PSE line of halo2_proofs, h2mi_shuffle_program; keygen through h2mi_prover_keygen_shuffles): per
+ *                              shuffle a list of (input expression, shuffle expression) pairs whose tuples must be the same multiset
+ *                              over the usable rows; one grand product each, committed behind the lookups' products
  * Every function returns H2MI_OK or a negative H2MI_E* code (h2mi.h); no exception crosses the boundary.  Field elements
  * and points use the layouts of h2mi.h (4 / 8 uint64 limbs, Montgomery form).  A prover object is used by one thread at a time.
  */
@@ -200,6 +203,34 @@ int h2mi_advice_phases_check(const h2mi_constraint_system* cs, const h2mi_gate_p
 int h2mi_prover_keygen_phases(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                               const h2mi_advice_phases* phases, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
                               size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
+/* Shuffle arguments beside the constraint system: `meta.shuffle(name, |meta| vec![(input, shuffle), ..])` [RECALL halo2_proofs, PSE
+ * line, plonk/shuffle.rs, plonk/shuffle/prover.rs, plonk/shuffle/verifier.rs — restated from memory like everything else here, and
+ * pinned only to the restatement in DESIGN.md 4.5 and tests/shuffle_cases.py, not to the crate].  Two tuples of expressions take the
+ * same multiset of values over the usable rows.  Per shuffle of m >= 1 pairs A = theta^(m-1) a_0 + .. + a_(m-1) and S likewise from
+ * the shuffle side (all 2^k rows, rotations modulo 2^k: the lookups' folding); z[0] = 1, z[i+1] = z[i] (A_i + gamma) / (S_i + gamma)
+ * for i < u = 2^k - blinding_factors - 1, rows u + 1 .. 2^k - 1 blinding scalars, z[u] = 1 for a satisfied witness.  beta is not used.
+ * Required degree 2 + max(1, input degrees, shuffle degrees), part of cs->degree.  create_proof commits the shuffle products behind
+ * the lookup products and in front of the random polynomial; evaluate_h adds per shuffle, behind the circuit's lookup terms, l_0 (1 -
+ * z), l_last (z^2 - z), l_active (z(wX) (S + gamma) - z(X) (A + gamma)); per shuffle z(x), z(omega x) are written behind the lookups'
+ * evaluations and opened behind lookups.open.
+ * h2mi_shuffle_program_check (host only, works without a GPU): H2MI_EINVAL unless n_shuffles is 1 .. H2MI_MAX_SHUFFLES (h2mi.h: 8), every
+ * n_pairs >= 1, exprs passes the rules of h2mi_gate_program_check except the degree rule, holds exactly 2 * sum n_pairs polynomials,
+ * and every shuffle's required degree is at most cs->degree.  degree_out (may be NULL): the largest required degree.  It knows of no
+ * challenges and refuses H2MI_EXPR_CHALLENGE; h2mi_shuffle_phases_check is the same with CHALLENGE ops of an index below
+ * phases->n_challenges allowed (phases == NULL: exactly the call above), as h2mi_advice_phases_check is for gates and lookups.
+ * h2mi_prover_keygen_shuffles: h2mi_prover_keygen_phases plus the shuffles.  phases == NULL: one phase, no challenges; shuffles == NULL:
+ * exactly the key the existing calls make.  Requires cs->gates == H2MI_GATES_EXPRESSIONS; the key copies the program. */
+typedef struct {
+  uint32_t n_shuffles;                  /* 1 .. H2MI_MAX_SHUFFLES */
+  uint32_t n_pairs[H2MI_MAX_SHUFFLES];  /* >= 1 */
+  h2mi_gate_program exprs;              /* per shuffle: its n_pairs input polynomials, then its n_pairs shuffle-side polynomials */
+} h2mi_shuffle_program;
+int h2mi_shuffle_program_check(const h2mi_constraint_system* cs, const h2mi_shuffle_program* shuffles, uint32_t* degree_out);
+int h2mi_shuffle_phases_check(const h2mi_constraint_system* cs, const h2mi_shuffle_program* shuffles, const h2mi_advice_phases* phases,
+                              uint32_t* degree_out);
+int h2mi_prover_keygen_shuffles(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
+                                const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles, uint64_t g_lagrange_handle,
+                                const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
 int h2mi_prover_pk_release(h2mi_pk_t pk); /* H2MI_EINVAL while a prover created against it is alive */
 /* VerifyingKey::{fixed_commitments, permutation.commitments}: affine points (8 limbs each); either pointer may be NULL */
 int h2mi_prover_vk_commitments(h2mi_pk_t pk, uint64_t* fixed_out /* n_fixed x 8 */, uint64_t* permutation_out /* n_perm x 8 */);
@@ -225,7 +256,8 @@ int h2mi_prover_set_combiner(h2mi_prover_t prover, void* d_partial, void* d_comb
  * 32 bits.  With a key: every blinding scalar of the following proofs is Fr::from_u512 of one ChaCha20 block (RFC 7539 block function with
  * a 64-bit block counter and a 64-bit stream id, the layout of rand_chacha's ChaCha20Rng; one block per scalar, as `Fr::random(rng)`
  * consumes it) under this 256-bit key: block counter = the scalar's index, stream id = nonce << 3 | purpose (1 advice blinding rows,
- * 2 permutation products, 3 the vanishing argument's random polynomial, 4 permuted lookup columns, 5 lookup products), nonce = the `seed`
+ * 2 permutation products, 3 the vanishing argument's random polynomial, 4 permuted lookup columns, 5 lookup products, 6 shuffle
+ * products), nonce = the `seed`
  * argument of h2mi_prover_advice (then below 2^61: a per-proof counter).  A fork fills the key from its rng once per prover.
  * key = NULL returns to the seeded streams.  Abandons a proof in flight. */
 int h2mi_prover_set_rng_key(h2mi_prover_t prover, const uint8_t key[32]);
@@ -240,7 +272,7 @@ int h2mi_prover_set_rng_key(h2mi_prover_t prover, const uint8_t key[32]);
  * inputs of the instance column (count values, Montgomery; the caller hashes them into its transcript itself).  seed: stands where the
  * crate takes `rng` — every blinding scalar is drawn from counter-based SplitMix64 streams of this seed (h2mi_fr_random_dev's
  * generator: seed + 1 advice blinding rows, + 2 permutation products, + 3 the vanishing argument's random polynomial, + 4 permuted
- * lookup columns, + 5 lookup products; seed < 2^32), or — after h2mi_prover_set_rng_key — the per-proof nonce of the keyed ChaCha20
+ * lookup columns, + 5 lookup products, + 6 shuffle products; seed < 2^32), or — after h2mi_prover_set_rng_key — the per-proof nonce of the keyed ChaCha20
  * streams (< 2^61).
  * points_out: n_advice commitments. */
 int h2mi_prover_advice(h2mi_prover_t prover, const h2mi_column_cells* advice, const uint64_t* instance, size_t n_instance_values, uint64_t seed,
@@ -280,25 +312,34 @@ int h2mi_prover_set_challenges(h2mi_prover_t prover, const uint64_t* values);
  *                      random value — two different tuples among u rows of m expressions collide, and hide a failure, with probability
  *                      about u^2 m / r (below 2^-190 at 2^28 rows).  The single-expression lookups compare q * a (or the column) with
  *                      the key's keygen-sorted table and ignore theta.
+ *   H2MI_CHECK_SHUFFLE per failing shuffle, behind the lookups: index = the shuffle, count = the usable rows whose compressed input value
+ *                      occurs more often among the inputs than on the shuffle side (not at all included), row = the smallest such row.
+ *                      Both sides hold u rows, so unequal multisets always yield at least one such row.  Both sides are compressed
+ *                      with `theta` on the rows and sorted (the lookups' sort and rank kernels); theta has the role and the collision
+ *                      bound it has for program lookups.
  * Multi-device modes: the vectors are on the primary device, as for the lookups. */
 #define H2MI_CHECK_GATE 0u
 #define H2MI_CHECK_COPY 1u
 #define H2MI_CHECK_LOOKUP 2u
+#define H2MI_CHECK_SHUFFLE 3u
 typedef struct { uint32_t kind /* H2MI_CHECK_* */, index, row, count; } h2mi_check_failure;
 int h2mi_prover_check(h2mi_prover_t prover, const uint64_t theta[4], h2mi_check_failure* out, size_t cap, size_t* n_out);
 /* theta compresses the lookups of a key made by h2mi_prover_keygen_exprs (each side's expressions folded with it on the rows, the
  * table's usable rows sorted on the device); the single-expression lookups do not use it.
  * points_out: per lookup the permuted input, then the permuted table commitment (2 x n_lookups; nothing without lookups — the call
- * may then be skipped).  H2MI_EUNSAT: a lookup input (a compressed input tuple) is not a table value (a table row). */
+ * may then be skipped — except on a key with shuffles, whose two sides the products phase compresses with this theta: there the call is
+ * required, with theta, and returns no points when there are no lookups; h2mi_prover_products is H2MI_EINVAL without it).
+ * H2MI_EUNSAT: a lookup input (a compressed input tuple) is not a table value (a table row). */
 int h2mi_prover_lookups(h2mi_prover_t prover, const uint64_t theta[4], uint64_t* points_out);
-/* points_out: the permutation argument's ceil(n_perm / (degree - 2)) grand products, one product per lookup, then the vanishing
- * argument's random polynomial: the order create_proof commits (and writes) them in. */
+/* points_out: the permutation argument's ceil(n_perm / (degree - 2)) grand products, one product per lookup, one product per shuffle,
+ * then the vanishing argument's random polynomial: the order create_proof commits (and writes) them in.  H2MI_EUNSAT: a shuffle's
+ * product over the usable rows is not one (one comparison of z[u]); the proof is abandoned. */
 int h2mi_prover_products(h2mi_prover_t prover, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* points_out);
 /* points_out: the degree - 1 pieces of h(X) */
 int h2mi_prover_quotient(h2mi_prover_t prover, const uint64_t y[4], uint64_t* points_out);
 /* evals_out: every evaluation create_proof writes, in its order: advice queries, fixed queries, the random polynomial, the sigma
  * polynomials, per permutation product z(x), z(omega x) and — all but the last — z(omega^-(blinding_factors + 1) x), per lookup
- * z(x), z(omega x), A'(x), A'(omega^-1 x), S'(x).  h2mi_prover_num_evaluations gives the count (4 limbs each). */
+ * z(x), z(omega x), A'(x), A'(omega^-1 x), S'(x), per shuffle z(x), z(omega x).  h2mi_prover_num_evaluations gives the count (4 limbs each). */
 int h2mi_prover_num_evaluations(h2mi_prover_t prover, size_t* count_out);
 int h2mi_prover_evaluations(h2mi_prover_t prover, const uint64_t x[4], uint64_t* evals_out);
 /* ProverSHPLONK::create_proof (poly/kzg/multiopen/shplonk/prover.rs) over the queries create_proof collects, cut at its two commitments */
@@ -316,7 +357,7 @@ int h2mi_prover_shplonk_open(h2mi_prover_t prover, const uint64_t u[4], uint64_t
  * each, in any interleaving between members that respects each member's own order.  The caller's transcript orders the points as
  * create_proof does [RECALL halo2_proofs v2023_02_02 plonk/prover.rs]: per advice phase every circuit's commitments of that phase in
  * circuit order, then that phase's challenges; theta; every circuit's permuted lookup pairs; beta, gamma; every circuit's permutation
- * products; every circuit's lookup products; the random polynomial; y; the h pieces; x; the evaluations; SHPLONK.
+ * products; every circuit's lookup products; every circuit's shuffle products; the random polynomial; y; the h pieces; x; the evaluations; SHPLONK.
  * There is ONE random polynomial per proof: member 0's products phase draws and commits it as ever (last in its points_out); a bound
  * member with index > 0 neither draws nor commits one, so its points_out is one point shorter (h2mi_prover_get_counts says so) and
  * its H2MI_BUF_RANDOM_POLY is stale.  A caller that writes member 0's points first keeps the random polynomial's back until every
@@ -327,18 +368,20 @@ int h2mi_prover_shplonk_open(h2mi_prover_t prover, const uint64_t u[4], uint64_t
  * refusals of h2mi_batch_quotient listed next, which leave every member where it was):
  *   h2mi_batch_quotient         requires every member behind its h2mi_prover_products, all with the same beta and gamma and, on a key with
  *                               challenges, the same challenge values; and refuses members whose blinding streams could overlap — two
- *                               columns of one proof would be opened with the same blinding: seeded streams are seed + purpose (1 .. 5), so
+ *                               columns of one proof would be opened with the same blinding: seeded streams are seed + purpose (1 .. 6), so
  *                               two members' seeds must be at least 8 apart; under the same rng key two members need different nonces.
- *                               One kernel folds every circuit's gate, permutation and lookup terms into h in circuit order
+ *                               One kernel folds every circuit's gate, permutation, lookup and shuffle terms into h in circuit order
  *                               (h2mi_plonk_evaluate_h_expr_batch_dev); a key of a hard-wired shape goes through the equivalent program of
  *                               h2mi_shape_gate_program, which computes the same field elements as the shape's own kernel.
  *                               points_out: the degree - 1 pieces of h(X).
  *   h2mi_batch_evaluations      evals_out: every circuit's advice queries in circuit order; the fixed queries; the random polynomial; the
  *                               sigma polynomials; every circuit's permutation sets (per set as h2mi_prover_evaluations); every circuit's
- *                               lookups (per lookup likewise).  h2mi_batch_num_evaluations = N advice queries + fixed queries + 1 + n_perm
- *                               + N (3 n_sets - 1 if n_sets > 0) + N 5 n_lookups.
+ *                               lookups (per lookup likewise); every circuit's shuffles (per shuffle z(x), z(omega x)).
+ *                               h2mi_batch_num_evaluations = N advice queries + fixed queries + 1 + n_perm
+ *                               + N (3 n_sets - 1 if n_sets > 0) + N 5 n_lookups + N 2 n_shuffles.
  *   h2mi_batch_shplonk_quotient, h2mi_batch_shplonk_open
- *                               over the queries in create_proof's order: per circuit advice, permutation.open, lookups.open; then fixed,
+ *                               over the queries in create_proof's order: per circuit advice, permutation.open, lookups.open,
+ *                               shuffles.open (z at x, then at omega x); then fixed,
  *                               sigma, h, the random polynomial.
  * The joint vectors are member 0's: h2mi_prover_buffer(member 0, H2MI_BUF_H / _H_POLY / _RANDOM_POLY / _SHPLONK_H / _SHPLONK_H2) reads
  * the batch's; every member's per-circuit buffers stay readable through the member.  The joint commitments go through member 0's result
@@ -376,6 +419,7 @@ enum {
   H2MI_BUF_LOOKUP_PERMUTED_INPUT, H2MI_BUF_LOOKUP_PERMUTED_TABLE, H2MI_BUF_LOOKUP_Z,
   H2MI_BUF_RANDOM_POLY, H2MI_BUF_H /* (degree - 1) n coefficients: piece i at i n */, H2MI_BUF_H_POLY,
   H2MI_BUF_SHPLONK_H, H2MI_BUF_SHPLONK_H2,
+  H2MI_BUF_SHUFFLE_Z, H2MI_BUF_SHUFFLE_Z_POLY, H2MI_BUF_SHUFFLE_INPUT /* compressed rows */, H2MI_BUF_SHUFFLE_TABLE /* compressed rows */,
   H2MI_PKBUF_FIXED = 64, H2MI_PKBUF_FIXED_POLY, H2MI_PKBUF_FIXED_COSET, H2MI_PKBUF_SIGMA, H2MI_PKBUF_SIGMA_POLY, H2MI_PKBUF_SIGMA_COSET,
   H2MI_PKBUF_L0_COSET, H2MI_PKBUF_L_LAST_COSET, H2MI_PKBUF_L_ACTIVE_COSET
 };
