@@ -98,6 +98,8 @@ def _load():
         "h2mi_plonk_instance_coset_dev": ([vp, C.c_uint32, C.c_uint32, vp, sz, vp, vp], C.c_int),
         "h2mi_plonk_lookup_product_dev": ([vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_shuffle_product_dev": ([vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
+        "h2mi_plonk_logup_multiplicity_dev": ([vp, vp, C.c_uint32, C.c_uint32, vp, u64p, vp], C.c_int),
+        "h2mi_plonk_logup_sum_dev": ([vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_range_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_flex_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_expr_dev": ([vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
@@ -115,6 +117,7 @@ def _load():
         "h2mi_plonk_lookup_member_dev": ([vp, vp, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
         "h2mi_plonk_shuffle_member_dev": ([vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
         "h2mi_fr_sort_unique_dev": ([vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), vp], C.c_int),
+        "h2mi_fr_sort_unique_first_dev": ([vp, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint32), vp], C.c_int),
         "h2mi_g1_fixed_base_mul_dev": ([vp, sz, vp, vp], C.c_int),
         "h2mi_fr_powers_dev": ([vp, sz, vp, vp], C.c_int),
         "h2mi_fft_bn254_g1_dev": ([vp, vp, C.c_uint32, vp, vp, vp], C.c_int),

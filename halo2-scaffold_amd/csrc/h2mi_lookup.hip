@@ -312,18 +312,38 @@ __global__ void __launch_bounds__(256) k_su_heads(const fe* canon, const uint32_
   if (packed && j && differ && packed[j] == packed[j - 1]) atomicAdd(ties, 1u);
 }
 __global__ void __launch_bounds__(256) k_su_emit(const fe* canon, const fe* in, const uint32_t* idx, const uint32_t* head, const uint32_t* rank, uint32_t count,
-                                                 fe* out_canon, fe* out_mont, uint32_t* start) {
+                                                 fe* out_canon, fe* out_mont, uint32_t* start, uint32_t* first) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= count || !head[j]) return;
   const uint32_t r = rank[j], i = idx[j];  // r < count: at most one head per position
   fe_store(&out_canon[r], fe_load(&canon[i]));
   fe_store(&out_mont[r], fe_load(&in[i]));
   start[r] = j;
+  // the sort is stable over an index permutation that starts as the identity: a run's head is its value's lowest position in `in`
+  if (first) first[r] = i;
+}
+// logUp multiplicities [restated in DESIGN.md 4.5]: the count of every distinct table value goes to the table's first row that holds
+// it, as a field element in the memory format (Montgomery); d_m is zero everywhere else (cleared by the caller)
+__global__ void __launch_bounds__(256) k_logup_scatter(const uint32_t* cnt, const uint32_t* first, uint32_t n_unique, uint32_t u, fe* m) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_unique || !cnt[r]) return;
+  const uint32_t row = first[r];
+  if (row >= u) return;  // always false: first rows are positions of the u sorted values
+  fe c = fe_zero();
+  c.v[0] = cnt[r];
+  fe_store(&m[row], fe_to_mont<Fr>(c));
 }
 __global__ void __launch_bounds__(256) k_su_mult(const uint32_t* start, const uint32_t* total, uint32_t count, uint32_t* mult) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x, n_unique = *total;
   if (r >= n_unique || r >= count) return;
   mult[r] = (r + 1 < n_unique ? start[r + 1] : count) - start[r];
+}
+
+// words of scratch h2mi_fr_sort_unique_dev lays out for `count` keys (every part starts on a multiple of 4)
+static size_t su_scratch_words(uint32_t count) {
+  const uint32_t c4 = (count + 3u) & ~3u, hm = 256 * ceil_div_u32(count, RS_TILE);
+  const uint32_t nseg = ceil_div_u32(std::max(hm, c4), SCAN_SEG_BINS) + 1, nseg4 = (nseg + 3u) & ~3u;
+  return 8 * (size_t)count + 6 * (size_t)c4 + 2 * ((size_t)hm + 4) + 3 * ((size_t)c4 + 4) + nseg4 + 8;
 }
 
 static uint32_t* g_lk_scratch = nullptr;
@@ -484,8 +504,9 @@ int h2mi_plonk_shuffle_member_dev(const void* d_input, const void* d_input_sorte
   return H2MI_OK;
 }
 
-int h2mi_fr_sort_unique_dev(const void* d_in, uint32_t count, void* d_sorted_canonical, void* d_sorted_mont, void* d_mult, uint32_t* n_unique_out,
-                            h2mi_stream_t stream) {
+// h2mi_fr_sort_unique_dev's body; d_first (optional, u32 x count): per distinct value the lowest position of d_in that holds it
+static int sort_unique(const void* d_in, uint32_t count, void* d_sorted_canonical, void* d_sorted_mont, void* d_mult, void* d_first,
+                       uint32_t* n_unique_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!d_in || !d_sorted_canonical || !d_sorted_mont || !d_mult || !n_unique_out) return H2MI_EINVAL;
   if (count == 0 || count > (1u << H2MI_MAX_LOG_N)) return H2MI_ERANGE;
@@ -499,7 +520,7 @@ int h2mi_fr_sort_unique_dev(const void* d_in, uint32_t count, void* d_sorted_can
   const uint32_t nseg = ceil_div_u32(std::max(hm, c4), SCAN_SEG_BINS) + 1, nseg4 = (nseg + 3u) & ~3u;
   // scratch (words; every part starts on a multiple of 4): canon[8 count] packed0[2 c4] packed1[2 c4] idx0[c4] idx1[c4] hist[hm+4]
   // offs[hm+4] head[c4+4] rank[c4+4] start[c4+4] segsum[nseg4] diff[8]
-  const size_t words = 8 * (size_t)count + 6 * (size_t)c4 + 2 * ((size_t)hm + 4) + 3 * ((size_t)c4 + 4) + nseg4 + 8;
+  const size_t words = su_scratch_words(count);
   {
     int rcs = lk_scratch_reserve(words);
     if (rcs) return rcs;
@@ -554,7 +575,7 @@ int h2mi_fr_sort_unique_dev(const void* d_in, uint32_t count, void* d_sorted_can
     int rc = scan_u32(head, rank, c4, segsum, s);
     if (rc) return rc;
     H2_LAUNCH("k_su_emit", k_su_emit, grid, 256, 0, s, (const fe*)canon, in, (const uint32_t*)idx[cur], (const uint32_t*)head, (const uint32_t*)rank, count,
-              (fe*)d_sorted_canonical, (fe*)d_sorted_mont, start);
+              (fe*)d_sorted_canonical, (fe*)d_sorted_mont, start, (uint32_t*)d_first);
     H2_LAUNCH("k_su_mult", k_su_mult, grid, 256, 0, s, (const uint32_t*)start, (const uint32_t*)(rank + c4), count, (uint32_t*)d_mult);
     H2_HIP(hipMemcpyAsync(result, rank + c4, 8, hipMemcpyDeviceToHost, s));
     H2_HIP(hipStreamSynchronize(s));
@@ -583,6 +604,60 @@ int h2mi_fr_sort_unique_dev(const void* d_in, uint32_t count, void* d_sorted_can
   g_lk_stream = s;
   const uint32_t total = result[0];
   *n_unique_out = total;
+  return H2MI_OK;
+}
+
+int h2mi_fr_sort_unique_dev(const void* d_in, uint32_t count, void* d_sorted_canonical, void* d_sorted_mont, void* d_mult, uint32_t* n_unique_out,
+                            h2mi_stream_t stream) {
+  return sort_unique(d_in, count, d_sorted_canonical, d_sorted_mont, d_mult, nullptr, n_unique_out, stream);
+}
+
+int h2mi_fr_sort_unique_first_dev(const void* d_in, uint32_t count, void* d_sorted_canonical, void* d_sorted_mont, void* d_mult, void* d_first,
+                                  uint32_t* n_unique_out, h2mi_stream_t stream) {
+  if (!d_first) return H2MI_EINVAL;
+  return sort_unique(d_in, count, d_sorted_canonical, d_sorted_mont, d_mult, d_first, n_unique_out, stream);
+}
+
+int h2mi_plonk_logup_multiplicity_dev(const void* d_input, const void* d_table, uint32_t k, uint32_t usable_rows, void* d_m, uint64_t* not_in_table_out,
+                                      h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_input || !d_table || !d_m || !not_in_table_out) return H2MI_EINVAL;  // the count is mandatory, as for the permuted columns
+  if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k)) return H2MI_ERANGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  {
+    int rc0 = use_device(0);
+    if (rc0) return rc0;
+  }
+  hipStream_t s = pick_stream(stream);
+  const uint32_t u = usable_rows, u4 = (u + 3u) & ~3u;
+  // behind the sort's own scratch (words): sorted[8 u4] sorted_mont[8 u4] mult[u4] first[u4] cnt[u4] missing[4]; reserved in one piece
+  // BEFORE the sort, whose own reservation then finds room and moves nothing
+  const size_t base = (su_scratch_words(u) + 3u) & ~(size_t)3u, words = base + 19 * (size_t)u4 + 4;
+  {
+    int rcs = lk_scratch_reserve(words);
+    if (rcs) return rcs;
+  }
+  uint32_t* sorted = g_lk_scratch + base;
+  uint32_t* sorted_mont = sorted + 8 * (size_t)u4;
+  uint32_t* mult = sorted_mont + 8 * (size_t)u4;
+  uint32_t* first = mult + u4;
+  uint32_t* cnt = first + u4;
+  uint32_t* missing = cnt + u4;
+  uint32_t n_unique = 0;
+  int rc = sort_unique(d_table, u, sorted, sorted_mont, mult, first, &n_unique, stream);  // waits for an earlier call on another stream
+  if (rc) return rc;
+  if (n_unique == 0 || n_unique > u) return H2MI_EHIP;
+  H2_HIP(hipMemsetAsync(cnt, 0, ((size_t)u4 + 4) * 4, s));
+  H2_HIP(hipMemsetAsync(d_m, 0, (size_t)u * 32, s));  // rows 0 .. u - 1; the blinding rows behind them are the caller's
+  H2_LAUNCH("k_lk_rank", k_lk_rank, ceil_div_u32(u, 1024), 1024, 0, s, (const fe*)d_input, u, (const fe*)sorted, n_unique, cnt, missing);
+  H2_LAUNCH("k_logup_scatter", k_logup_scatter, ceil_div_u32(n_unique, 256), 256, 0, s, (const uint32_t*)cnt, (const uint32_t*)first, n_unique, u, (fe*)d_m);
+  if (!g_lk_event) H2_HIP(hipEventCreateWithFlags(&g_lk_event, hipEventDisableTiming));
+  H2_HIP(hipEventRecord(g_lk_event, s));
+  g_lk_stream = s;
+  uint32_t m = 0;
+  H2_HIP(hipMemcpyAsync(&m, missing, 4, hipMemcpyDeviceToHost, s));
+  H2_HIP(hipStreamSynchronize(s));
+  *not_in_table_out = m;
   return H2MI_OK;
 }
 

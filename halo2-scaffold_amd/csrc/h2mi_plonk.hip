@@ -464,6 +464,7 @@ __global__ void __launch_bounds__(256) k_evaluate_h_range(RangeCosets c, uint32_
 // the selector form of the lookup input both kernels must produce the same h (tests/test_gpu_flex.py).
 struct FlexCosets {
   uint32_t n_gates, n_perm, chunk, n_lookups, n_shuffles;
+  uint32_t logup;  // the lookups are logUp arguments: lk_pin holds M, lk_z the running sum, lk_ptab is not read
   const fe* gate_a[H2MI_FLEX_MAX_GATES];
   const fe* gate_q[H2MI_FLEX_MAX_GATES];
   const fe* perm_value[H2MI_FLEX_MAX_PERM];
@@ -532,6 +533,17 @@ __device__ __forceinline__ void evaluate_h_fold(const Circuit& c, const FlexCose
   for (uint32_t l = 0; l < sh.n_lookups; l++) {
     f29 a_in = ld(&c.lk_in[l][idx]);
     if (c.lk_in_b[l]) a_in = mul(a_in, ld(&c.lk_in_b[l][idx]));
+    if (sh.logup) {
+      // logUp [Haboeck; the mv-lookup feature of halo2_proofs forks, restated from memory in DESIGN.md 4.5]: three terms, no gamma.  The
+      // mode is the launch's (wave-uniform); M and phi arrive through the slots of the permuted input and of the product
+      const f29 ab = add(a_in, beta), sb = add(ld(&c.lk_table[l][idx]), beta);
+      const f29 phi = ld(&c.lk_z[l][idx]);
+      horner(acc, y, mul(phi, l0));
+      horner(acc, y, mul(phi, ll));
+      const f29 lhs = mul(mul(sub(ld(&c.lk_z[l][r_next]), phi), ab), sb), rhs = red(sub(sb, mul(ld(&c.lk_pin[l][idx]), ab)));
+      horner(acc, y, mul(sub(lhs, rhs), lact));
+      continue;
+    }
     const f29 t_in = ld(&c.lk_table[l][idx]), ap = ld(&c.lk_pin[l][idx]), ap_prev = ld(&c.lk_pin[l][r_prev]), sp = ld(&c.lk_ptab[l][idx]);
     const f29 lz = ld(&c.lk_z[l][idx]), lz_next = ld(&c.lk_z[l][r_next]);
     horner(acc, y, mul(sub(one, lz), l0));
@@ -849,6 +861,83 @@ __global__ void __launch_bounds__(256) k_perm_write(const fe* R, const fe* start
   if (i == u && last_or_null) fe_store(last_or_null, v);
 }
 
+// ---- logUp: the running sum phi [Haboeck; restated from memory in DESIGN.md 4.5] ------------------------------------------------------
+// Per usable row ONE fraction, 1 / (A + beta) - M / (S + beta) = ((S + beta) - M (A + beta)) / ((A + beta)(S + beta)): numerator and
+// denominator as the canonical Montgomery-2^261 words the scans take, so that the dense chain (k_mulscan_* over the denominators, the
+// one inversion, k_perm_ratio) turns them into the fractions' values; then an ADDITIVE prefix scan.
+__global__ void __launch_bounds__(256) k_logup_numden(const fe* input, const fe* table, const fe* mult, fe beta, uint32_t u, fe* num, fe* den) {
+  using namespace gen;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= u) return;
+  const f29 b = cst(beta), ab = add(ld(&input[i]), b), sb = add(ld(&table[i]), b);
+  fe_store(&num[i], pack261(red(sub(sb, mul(ld(&mult[i]), ab)))));
+  fe_store(&den[i], pack261(mul(ab, sb)));
+}
+// The additive scan over Fr, shaped like the multiplicative one (local / offsets / apply, tiles of AS_TILE) without a multiplication:
+// the words are canonical (below r), so a sum is one 256-bit addition and one conditional subtraction on the 32-bit-limb layer, and
+// the Montgomery factor 2^261 rides along unchanged.
+constexpr uint32_t AS_TILE = 1024;
+__global__ void __launch_bounds__(256) k_addscan_local(const fe* in, uint32_t n, fe* local, fe* totals) {
+  __shared__ fe tsum[256];
+  const uint32_t tid = threadIdx.x, base = blockIdx.x * AS_TILE + 4 * tid;
+  fe v[4];
+#pragma unroll
+  for (int r = 0; r < 4; r++) v[r] = base + r < n ? fe_load(&in[base + r]) : fe_zero();
+#pragma unroll
+  for (int r = 1; r < 4; r++) v[r] = fe_add<Fr>(v[r - 1], v[r]);
+  tsum[tid] = v[3];
+  __syncthreads();
+  for (uint32_t d = 1; d < 256; d <<= 1) {  // inclusive scan of the 256 thread sums (Hillis-Steele)
+    fe w = fe_zero();
+    if (tid >= d) w = tsum[tid - d];
+    __syncthreads();
+    if (tid >= d) tsum[tid] = fe_add<Fr>(tsum[tid], w);
+    __syncthreads();
+  }
+  const fe left = tid ? tsum[tid - 1] : fe_zero();
+#pragma unroll
+  for (int r = 0; r < 4; r++)
+    if (base + r < n) fe_store(&local[base + r], fe_add<Fr>(left, v[r]));
+  if (tid == 255) fe_store(&totals[blockIdx.x], tsum[255]);
+}
+// exclusive scan of the tile totals in ONE workgroup: every thread owns a run of consecutive totals (k_mulscan_offsets' layout)
+__global__ void __launch_bounds__(1024) k_addscan_offsets(const fe* totals, uint32_t nblocks, fe* offsets) {
+  __shared__ fe tsum[1024];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t per = (nblocks + 1023) / 1024;
+  const uint32_t lo = min(tid * per, nblocks), hi = min(lo + per, nblocks);
+  fe run = fe_zero();
+  for (uint32_t b = lo; b < hi; b++) run = fe_add<Fr>(run, fe_load(&totals[b]));
+  tsum[tid] = run;
+  __syncthreads();
+  const uint32_t used = (nblocks + per - 1) / per;
+  for (uint32_t d = 1; d < used; d <<= 1) {
+    fe w = fe_zero();
+    if (tid >= d) w = tsum[tid - d];
+    __syncthreads();
+    if (tid >= d) tsum[tid] = fe_add<Fr>(tsum[tid], w);
+    __syncthreads();
+  }
+  fe acc = tid ? tsum[tid - 1] : fe_zero();
+  for (uint32_t b = lo; b < hi; b++) {
+    fe_store(&offsets[b], acc);
+    acc = fe_add<Fr>(acc, fe_load(&totals[b]));
+  }
+}
+// apply, as the plain exclusive scan the column is: phi[0] = 0, phi[i] = local[i - 1] + offsets[tile of i - 1] for 1 <= i <= u, brought
+// to the columns' Montgomery-2^256 form; rows beyond u untouched.  offsets == NULL: one tile
+__global__ void __launch_bounds__(256) k_addscan_apply(const fe* local, const fe* offsets, uint32_t u, fe* phi) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > u) return;
+  fe o = fe_zero();
+  if (i) {
+    fe v = fe_load(&local[i - 1]);
+    if (offsets && i - 1 >= AS_TILE) v = fe_add<Fr>(v, fe_load(&offsets[(i - 1) / AS_TILE]));
+    f29_to_mont256<F9>(f29_unpack(v.v), o.v);
+  }
+  fe_store(&phi[i], o);
+}
+
 struct HostY {  // y^0 .. y^(count-1), Montgomery-2^256
   fe p[24];
   HostY(const fe& y, uint32_t count) {
@@ -875,7 +964,9 @@ static void fill_common(HConsts& h, const fe& beta, const fe& gamma, const fe& d
 // the permutation / lookup / Lagrange pointers of h2mi_flex_cosets or h2mi_expr_cosets (the same fields) -> the kernels' argument
 template <class Cosets>
 static bool fill_tail(FlexCosets& fc, const Cosets& c) {
-  fc.n_perm = c.n_perm; fc.chunk = c.chunk_len ? c.chunk_len : 1; fc.n_lookups = c.n_lookups;
+  fc.n_perm = c.n_perm; fc.chunk = c.chunk_len ? c.chunk_len : 1;
+  fc.n_lookups = c.n_lookups & ~(uint32_t)H2MI_LOOKUPS_LOGUP; fc.logup = (c.n_lookups & H2MI_LOOKUPS_LOGUP) ? 1u : 0u;
+  if (fc.n_lookups > H2MI_FLEX_MAX_LOOKUPS) return false;
   for (uint32_t j = 0; j < c.n_perm; j++) {
     fc.perm_value[j] = (const fe*)c.perm_value[j]; fc.perm_sigma[j] = (const fe*)c.perm_sigma[j];
     if (!fc.perm_value[j] || !fc.perm_sigma[j]) return false;
@@ -884,10 +975,10 @@ static bool fill_tail(FlexCosets& fc, const Cosets& c) {
     fc.perm_z[q] = (const fe*)c.perm_z[q];
     if (!fc.perm_z[q]) return false;
   }
-  for (uint32_t l = 0; l < c.n_lookups; l++) {
+  for (uint32_t l = 0; l < fc.n_lookups; l++) {
     fc.lk_in[l] = (const fe*)c.lookup_input[l]; fc.lk_in_b[l] = (const fe*)c.lookup_input_b[l]; fc.lk_table[l] = (const fe*)c.lookup_table[l];
     fc.lk_pin[l] = (const fe*)c.lookup_permuted_input[l]; fc.lk_ptab[l] = (const fe*)c.lookup_permuted_table[l]; fc.lk_z[l] = (const fe*)c.lookup_z[l];
-    if (!fc.lk_in[l] || !fc.lk_table[l] || !fc.lk_pin[l] || !fc.lk_ptab[l] || !fc.lk_z[l]) return false;
+    if (!fc.lk_in[l] || !fc.lk_table[l] || !fc.lk_pin[l] || (!fc.lk_ptab[l] && !fc.logup) || !fc.lk_z[l]) return false;
   }
   fc.l0 = (const fe*)c.l0; fc.l_last = (const fe*)c.l_last; fc.l_active = (const fe*)c.l_active;
   return fc.l0 && fc.l_last && fc.l_active;
@@ -1244,6 +1335,40 @@ int h2mi_plonk_shuffle_product_dev(const void* d_input, const void* d_shuffle, u
   return memcmp(last.v, one.v, sizeof(one.v)) ? H2MI_EUNSAT : H2MI_OK;
 }
 
+int h2mi_plonk_logup_sum_dev(const void* d_input, const void* d_table, const void* d_m, uint32_t k, uint32_t usable_rows, const uint64_t beta[4],
+                             void* d_phi, h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_input || !d_table || !d_m || !beta || !d_phi) return H2MI_EINVAL;
+  if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k)) return H2MI_ERANGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  CallScope scope_;
+  hipStream_t s = pick_stream(stream);
+  const size_t u = usable_rows;
+  const uint32_t nblocks = ceil_div_u32(u, MS_TILE);
+  static_assert(AS_TILE == MS_TILE, "one pair of totals / offsets vectors serves both scans");
+  int rc = ensure_tmp(3 * u + 2 * (size_t)nblocks + 2, s);
+  if (rc) return rc;
+  fe* num = tmp_base();
+  fe* P = num + u;
+  fe* S = P + u;
+  fe* totals = S + u;
+  fe* offsets = totals + nblocks;
+  fe* inv_total = offsets + nblocks;
+  H2_LAUNCH("k_logup_numden", k_logup_numden, ceil_div_u32(u, 256), 256, 0, s, (const fe*)d_input, (const fe*)d_table, (const fe*)d_m, host_fe(beta),
+            usable_rows, num, P);
+  H2_HIP(hipMemcpyAsync(S, P, u * 32, hipMemcpyDeviceToDevice, s));
+  rc = mulscan(P, u, 0, totals, offsets, s);
+  if (!rc) rc = mulscan(S, u, 1, totals, offsets, s);
+  if (rc) return rc;
+  H2_LAUNCH("k_fr_inv_one", k_fr_inv_one, 1, 64, 0, s, (const fe*)(P + (u - 1)), inv_total);
+  H2_LAUNCH("k_perm_ratio", k_perm_ratio, ceil_div_u32(u, 256), 256, 0, s, (const fe*)num, (const fe*)P, (const fe*)S, (const fe*)inv_total, u, num);
+  H2_LAUNCH("k_addscan_local", k_addscan_local, nblocks, 256, 0, s, (const fe*)num, usable_rows, num, totals);
+  if (nblocks > 1) H2_LAUNCH("k_addscan_offsets", k_addscan_offsets, 1, 1024, 0, s, (const fe*)totals, nblocks, offsets);
+  H2_LAUNCH("k_addscan_apply", k_addscan_apply, ceil_div_u32((uint64_t)usable_rows + 1, 256), 256, 0, s, (const fe*)num,
+            (const fe*)(nblocks > 1 ? offsets : nullptr), usable_rows, (fe*)d_phi);
+  return release_tmp(s);
+}
+
 int h2mi_plonk_evaluate_h_range_dev(const h2mi_range_cosets* c, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
                                     const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
                                     const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
@@ -1364,7 +1489,7 @@ int h2mi_plonk_evaluate_h_expr_sh_dev(const h2mi_expr_cosets* c, const h2mi_shuf
   H2_REQUIRE_INIT();
   if (!c || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
   if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
-  if (c->n_perm > H2MI_FLEX_MAX_PERM || c->n_lookups > H2MI_FLEX_MAX_LOOKUPS || (c->n_perm && c->chunk_len == 0)) return H2MI_EINVAL;
+  if (c->n_perm > H2MI_FLEX_MAX_PERM || (c->n_lookups & ~(uint32_t)H2MI_LOOKUPS_LOGUP) > H2MI_FLEX_MAX_LOOKUPS || (c->n_perm && c->chunk_len == 0)) return H2MI_EINVAL;
   ExprImage im;
   int rc = im.build(gates, challenges, n_challenges, c->advice, c->fixed, c->instance, k, extended_k);
   if (rc) return rc;
@@ -1413,7 +1538,7 @@ int h2mi_plonk_evaluate_h_expr_batch_sh_dev(const h2mi_expr_cosets* circuits, co
   if (n_circuits == 0 || n_circuits > H2MI_MAX_CIRCUITS) return H2MI_EINVAL;
   if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
   const h2mi_expr_cosets& c0 = circuits[0];
-  if (c0.n_perm > H2MI_FLEX_MAX_PERM || c0.n_lookups > H2MI_FLEX_MAX_LOOKUPS || (c0.n_perm && c0.chunk_len == 0)) return H2MI_EINVAL;
+  if (c0.n_perm > H2MI_FLEX_MAX_PERM || (c0.n_lookups & ~(uint32_t)H2MI_LOOKUPS_LOGUP) > H2MI_FLEX_MAX_LOOKUPS || (c0.n_perm && c0.chunk_len == 0)) return H2MI_EINVAL;
   // the program, its constants and the challenges once, as the single-circuit call lays them out (the image's own column table is
   // circuit 0's and is not read here); the circuits' records behind it
   ExprImage im;

@@ -329,6 +329,8 @@ struct h2mi_pk_s {
   h2mi_gate_program gate_program = {nullptr, 0, nullptr, 0};
   // lookups given as a program (h2mi_prover_keygen_exprs): the key's own copy, cut into each lookup's input and table polynomials
   bool lookup_exprs = false;
+  // H2MI_KEYGEN_LOGUP: every program lookup of the key is a logUp argument (multiplicities M and a running sum phi)
+  bool logup = false;
   std::vector<h2mi_expr_op> lookup_ops;
   std::vector<uint64_t> lookup_constants;
   LookupSlices lookup_slices;
@@ -436,6 +438,7 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     if (check_shuffle_program(cs, &own, nullptr, &pk.shuffle_slices, pk.phases.n_challenges)) throw Error(H2MI_EINVAL, "shuffle program");
   }
   pk.vk_only = (flags & H2MI_KEYGEN_VK_ONLY) != 0;
+  pk.logup = lookups && (flags & H2MI_KEYGEN_LOGUP) != 0;
   if (gates) {
     pk.check_gates = pk.gate_program;
   } else {  // a hard-wired shape: its gates as the program the witness check interprets
@@ -808,7 +811,7 @@ typedef std::vector<h2mi_prover_s*> Circuits;
 // commitments of the largest phase: the result slots a prover (and a combiner's two buffers) must hold
 uint32_t max_phase_points(const h2mi_pk_s& pk) {
   const h2mi_constraint_system& cs = pk.cs;
-  return std::max({cs.n_advice, 2 * cs.n_lookups, pk.n_sets + cs.n_lookups + pk.n_shuffles + 1, cs.degree - 1, 8u});
+  return std::max({cs.n_advice, (pk.logup ? 1 : 2) * cs.n_lookups, pk.n_sets + cs.n_lookups + pk.n_shuffles + 1, cs.degree - 1, 8u});
 }
 
 std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t gl, size_t lo, size_t cnt) {
@@ -850,7 +853,7 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
       p.lk[l].input = vec(n);
     }
     p.lk[l].a.alloc(n, ext);
-    p.lk[l].s.alloc(n, ext);
+    if (!pk->logup) p.lk[l].s.alloc(n, ext);  // a logUp key: `a` holds M, `z` the running sum, there is no permuted table
     p.lk[l].z.alloc(n, ext);
   }
   for (uint32_t i = 0; i < pk->n_shuffles; i++) {
@@ -971,7 +974,31 @@ void phase_lookups(h2mi_prover_s& p, const uint64_t* theta, uint64_t* points_out
     std::memcpy(p.theta.l, theta, 32);
     p.have_theta = true;
   }
-  if (L) {
+  if (L && pk.logup) {
+    // logUp [restated in DESIGN.md 4.5]: compress -> multiplicities -> blinding rows -> one in-order commitment group of L columns.
+    // M's blinding rows u .. 2^k - 1 come from the permuted columns' stream (purpose 4): bf + 1 scalars per lookup, in lookup order
+    if (!theta) throw Error(H2MI_EINVAL, "theta");
+    std::memcpy(p.theta.l, theta, 32);
+    const std::vector<Fr> mb = p.blinding(4, (size_t)(bf + 1) * L);
+    PatchList pl;
+    std::vector<const void*> cols;
+    for (uint32_t l = 0; l < L; l++) {
+      p.compress(pk.lookup_slices.input[l], false, *p.lk[l].input);
+      p.compress(pk.lookup_slices.table[l], false, *p.lk[l].table);
+      DeviceVec& mult = *p.lk[l].a.value;
+      uint64_t missing = 0;
+      check(h2mi_plonk_logup_multiplicity_dev(p.lk[l].input->p, p.lk[l].table->p, cs.k, u, mult.p, &missing, nullptr), "logup_multiplicity");
+      if (missing) throw Error(H2MI_EUNSAT, "lookup input not in the table (ConstraintSystemFailure)");
+      for (uint32_t r = 0; r <= bf; r++) pl.add(mult, u + r, mb[(size_t)(bf + 1) * l + r]);
+      cols.push_back(p.col(mult));
+    }
+    pl.flush();
+    p.commit_phase(true, cols, 0, /*sparse=*/false, /*inorder=*/true);
+    check(h2mi_msm_flush(), "flush");
+    check(h2mi_stream_wait(p.side, nullptr), "stream_wait");
+    for (uint32_t l = 0; l < L; l++) p.forms(p.lk[l].a, p.side);
+    p.read_points(L, points_out);
+  } else if (L) {
     const std::vector<Fr> lb = p.blinding(4, (size_t)2 * (bf + 1) * L);
     PatchList pl;
     std::vector<const void*> cols;
@@ -1140,6 +1167,18 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
     }
     pl.flush();
   }
+  // logUp running sums [restated in DESIGN.md 4.5], like the shuffles' products in front of everything this phase queues; their
+  // blinding rows u + 1 .. 2^k - 1 come from the lookup products' stream (purpose 5): bf scalars per lookup, in lookup order
+  if (L && pk.logup) {
+    const std::vector<Fr> pb = p.blinding(5, (size_t)bf * L);
+    PatchList pl;
+    for (uint32_t l = 0; l < L; l++) {
+      DeviceVec& phi = *p.lk[l].z.value;
+      check(h2mi_plonk_logup_sum_dev(p.lk[l].input->p, p.lk[l].table->p, p.lk[l].a.value->p, cs.k, u, beta.l, phi.p, nullptr), "logup_sum");
+      for (uint32_t r = 0; r < bf; r++) pl.add(phi, u + 1 + r, pb[(size_t)bf * l + r]);
+    }
+    pl.flush();
+  }
   // the random polynomial's commitment is written after the grand products' but depends on nothing: queued first, the one dense
   // MSM of this phase accumulates beside their latency-bound scans.  Result slot: where the transcript expects it.
   const bool random = p.draws_random();
@@ -1194,7 +1233,13 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
     for (uint32_t s = 0; s < n_sets; s++) p.forms(p.z[s], p.side);
     if (n_sets) p.commit_phase(true, zcols, 0, perm_sparse, false);
     size_t slot = n_sets;
-    if (L) {
+    if (L && pk.logup) {
+      for (uint32_t l = 0; l < L; l++) {  // built above; the commitment in the lookup product's slot, the forms on the side stream
+        check(h2mi_stream_wait(p.side, nullptr), "stream_wait");
+        p.forms(p.lk[l].z, p.side);
+        p.commit(true, p.col(*p.lk[l].z.value), slot++);
+      }
+    } else if (L) {
       const std::vector<Fr> lzb = p.blinding(5, (size_t)bf * L);
       for (uint32_t l = 0; l < L; l++) {
         DeviceVec& lz = *p.lk[l].z.value;
@@ -1243,7 +1288,7 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_coset
     ec.perm_sigma[j] = pk.sigma_cosets[j]->p;
   }
   for (uint32_t s = 0; s < n_sets; s++) ec.perm_z[s] = p.z[s].coset->p;
-  ec.n_lookups = L;
+  ec.n_lookups = L | (pk.logup ? H2MI_LOOKUPS_LOGUP : 0u);
   for (uint32_t l = 0; l < L; l++) {
     const h2mi_lookup& lk = cs.lookups[l];
     if (pk.lookup_exprs) {
@@ -1259,7 +1304,7 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_coset
       ec.lookup_table[l] = pk.fixed_cosets[lk.table_fixed]->p;
     }
     ec.lookup_permuted_input[l] = p.lk[l].a.coset->p;
-    ec.lookup_permuted_table[l] = p.lk[l].s.coset->p;
+    ec.lookup_permuted_table[l] = pk.logup ? nullptr : p.lk[l].s.coset->p;
     ec.lookup_z[l] = p.lk[l].z.coset->p;
   }
   ec.l0 = pk.l0->p;
@@ -1433,7 +1478,7 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
 size_t num_evaluations(const h2mi_pk_s& pk, size_t n_circuits = 1) {
   const h2mi_constraint_system& cs = pk.cs;
   return n_circuits * cs.n_advice_queries + cs.n_fixed_queries + 1 + cs.n_perm +
-         n_circuits * ((pk.n_sets ? 3 * (size_t)pk.n_sets - 1 : 0) + 5 * (size_t)cs.n_lookups + 2 * (size_t)pk.n_shuffles);
+         n_circuits * ((pk.n_sets ? 3 * (size_t)pk.n_sets - 1 : 0) + (pk.logup ? 3 : 5) * (size_t)cs.n_lookups + 2 * (size_t)pk.n_shuffles);
 }
 
 // ---- phase 5: every evaluation create_proof writes -------------------------------------------------------------------------------
@@ -1487,6 +1532,7 @@ void phase_evaluations(const Circuits& all, const Fr& x, uint64_t* evals_out) {
       written.push_back({c->lk[l].z.poly.get(), x});
       written.push_back({c->lk[l].z.poly.get(), x_next});
       written.push_back({c->lk[l].a.poly.get(), x});
+      if (pk.logup) continue;  // phi(x), phi(omega x), M(x)
       written.push_back({c->lk[l].a.poly.get(), x_inv});
       written.push_back({c->lk[l].s.poly.get(), x});
     }
@@ -1548,7 +1594,12 @@ void phase_evaluations(const Circuits& all, const Fr& x, uint64_t* evals_out) {
       q(c->z[i].poly.get(), x_next);
     }
     for (uint32_t i = n_sets > 0 ? n_sets - 1 : 0; i-- > 0;) q(c->z[i].poly.get(), x_last);
-    for (uint32_t l = 0; l < L; l++) {
+    for (uint32_t l = 0; l < L && pk.logup; l++) {  // lookups.open of a logUp key: phi at x, phi at omega x, M at x
+      q(c->lk[l].z.poly.get(), x);
+      q(c->lk[l].z.poly.get(), x_next);
+      q(c->lk[l].a.poly.get(), x);
+    }
+    for (uint32_t l = 0; l < L && !pk.logup; l++) {
       q(c->lk[l].z.poly.get(), x);
       q(c->lk[l].a.poly.get(), x);
       q(c->lk[l].s.poly.get(), x);
@@ -1832,7 +1883,9 @@ int h2mi_lookup_program_check(const h2mi_constraint_system* cs, const h2mi_looku
 int h2mi_prover_keygen_exprs(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, uint64_t g_lagrange_handle,
                              const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
   if (!lookups) return h2mi_prover_keygen_gates(cs, gates, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
-  if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)H2MI_KEYGEN_VK_ONLY)) return H2MI_EINVAL;
+  if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)(H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP)) ||
+      ((flags & H2MI_KEYGEN_LOGUP) && !lookups))
+    return H2MI_EINVAL;
   *pk_out = nullptr;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;
   return guarded([&] {
@@ -1852,7 +1905,9 @@ int h2mi_advice_phases_check(const h2mi_constraint_system* cs, const h2mi_gate_p
 int h2mi_prover_keygen_phases(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                               const h2mi_advice_phases* phases, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
                               size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  if (!cs || !gates || !phases || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)H2MI_KEYGEN_VK_ONLY)) return H2MI_EINVAL;
+  if (!cs || !gates || !phases || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)(H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP)) ||
+      ((flags & H2MI_KEYGEN_LOGUP) && !lookups))
+    return H2MI_EINVAL;
   *pk_out = nullptr;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;
   return guarded([&] {
@@ -1878,7 +1933,9 @@ int h2mi_shuffle_phases_check(const h2mi_constraint_system* cs, const h2mi_shuff
 int h2mi_prover_keygen_shuffles(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                                 const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles, uint64_t g_lagrange_handle,
                                 const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)H2MI_KEYGEN_VK_ONLY)) return H2MI_EINVAL;
+  if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)(H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP)) ||
+      ((flags & H2MI_KEYGEN_LOGUP) && !lookups))
+    return H2MI_EINVAL;
   *pk_out = nullptr;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;
   return guarded([&] {
@@ -1965,7 +2022,7 @@ int h2mi_prover_get_counts(h2mi_prover_t prover, h2mi_prover_counts* out) {
   if (!out) return H2MI_EINVAL;
   const h2mi_pk_s& pk = *prover->pk;
   out->advice = pk.cs.n_advice;
-  out->lookups = 2 * pk.cs.n_lookups;
+  out->lookups = (pk.logup ? 1 : 2) * pk.cs.n_lookups;
   out->products = pk.n_sets + pk.cs.n_lookups + pk.n_shuffles + (prover->draws_random() ? 1 : 0);
   out->quotient = pk.cs.degree - 1;
   out->evaluations = (uint32_t)num_evaluations(pk);
@@ -2170,6 +2227,8 @@ int h2mi_prover_buffer(h2mi_prover_t prover, uint32_t kind, uint32_t index, void
     case H2MI_BUF_SHUFFLE_Z: return index < p.pk->n_shuffles ? pick(p.sf[index].z.value, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     case H2MI_BUF_SHUFFLE_Z_POLY: return index < p.pk->n_shuffles ? pick(p.sf[index].z.poly, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     case H2MI_BUF_SHUFFLE_INPUT: return index < p.pk->n_shuffles ? pick(p.sf[index].input, 0, d_ptr_out, count_out) : H2MI_ERANGE;
+    case H2MI_BUF_LOGUP_M: return p.pk->logup && index < p.pk->cs.n_lookups ? pick(p.lk[index].a.value, 0, d_ptr_out, count_out) : H2MI_ERANGE;
+    case H2MI_BUF_LOGUP_PHI: return p.pk->logup && index < p.pk->cs.n_lookups ? pick(p.lk[index].z.value, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     case H2MI_BUF_SHUFFLE_TABLE: return index < p.pk->n_shuffles ? pick(p.sf[index].table, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     default: return h2mi_prover_pk_buffer(p.pk, kind, index, d_ptr_out, count_out);
   }

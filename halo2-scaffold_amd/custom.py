@@ -490,10 +490,15 @@ class Keys:
     """keygen_vk + keygen_pk through h2mi_prover_keygen_gates (h2mi_prover_keygen_exprs when the circuit has lookups,
     h2mi_prover_keygen_phases when it has an advice column in a later phase or a challenge): the fixed cells of a run of synthesize() (selector columns included), the
     copy constraints with their columns renumbered into the permutation argument's order, the gates as a program the key copies.
-    Same attributes as flex.FlexKeys."""
+    Same attributes as flex.FlexKeys.
+    logup=True [the `mv-lookup` feature of the Scroll and ezkl lines of halo2_proofs, after Haboeck — restated from memory and pinned to
+    DESIGN.md 4.5 and tests/logup_cases.py, not to a crate]: every lookup of the key is proven with a multiplicity column and a running
+    sum (H2MI_KEYGEN_LOGUP) in place of the permuted columns and the grand product; needs a circuit with lookups.  `create_proof` and
+    `prove_many` follow the key; `mock` and `check` test membership and do not depend on it."""
 
-    def __init__(self, params: ParamsKZG, cs: ConstraintSystem, asg: Assignment):
+    def __init__(self, params: ParamsKZG, cs: ConstraintSystem, asg: Assignment, logup: bool = False):
         self.cs = cs
+        self.logup = bool(logup)
         self.params = params  # prove_many's default SRS
         k = params.k
         self.domain = d = EvaluationDomain(cs.degree(), k)
@@ -501,7 +506,7 @@ class Keys:
         index = {col: j for j, col in enumerate(cs.perm_columns)}
         copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
         self.keys = engine.Keys(cs.abi(k), params, list(asg.fixed), copies, gates=cs.gate_program(), lookups=cs.lookup_program(),
-                                phases=cs.phases(), shuffles=cs.shuffle_program())
+                                phases=cs.phases(), shuffles=cs.shuffle_program(), logup=logup)
         self.fixed_commitments, self.permutation_commitments = self.keys.fixed_commitments, self.keys.permutation_commitments
         nf, m = cs.n_fixed, len(cs.perm_columns)
         self.fixed_values, self.fixed_polys, self.fixed_cosets = (self.keys.views(kd, nf) for kd in (engine.PKBUF_FIXED, engine.PKBUF_FIXED_POLY, engine.PKBUF_FIXED_COSET))

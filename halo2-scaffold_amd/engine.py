@@ -21,6 +21,7 @@ ADVICE, FIXED, INSTANCE = 0, 1, 2  # H2MI_COL_*
 GATES_STANDARD_PLONK, GATES_FLEX_VERTICAL, GATES_EXPRESSIONS = 1, 2, 3
 CELLS_CANONICAL = 1
 KEYGEN_VK_ONLY = 1
+KEYGEN_LOGUP = 2  # H2MI_KEYGEN_LOGUP: the key's program lookups are logUp arguments (include/h2mi_prover.h)
 EUNSAT = -7
 MAX_GATES, MAX_PERM, MAX_LOOKUPS, MAX_QUERIES = 32, 64, 8, 192  # H2MI_MAX_* (include/h2mi_prover.h)
 MAX_SHUFFLES = 8  # H2MI_MAX_SHUFFLES (include/h2mi.h)
@@ -29,7 +30,7 @@ MAX_ADVICE, MAX_CHALLENGES, MAX_ADVICE_PHASES = 64, 16, 3
 # h2mi_prover_buffer kinds
 (BUF_ADVICE, BUF_ADVICE_POLY, BUF_ADVICE_COSET, BUF_INSTANCE, BUF_PERM_Z, BUF_PERM_Z_POLY, BUF_PERM_Z_COSET, BUF_LOOKUP_PERMUTED_INPUT,
  BUF_LOOKUP_PERMUTED_TABLE, BUF_LOOKUP_Z, BUF_RANDOM_POLY, BUF_H, BUF_H_POLY, BUF_SHPLONK_H, BUF_SHPLONK_H2, BUF_SHUFFLE_Z, BUF_SHUFFLE_Z_POLY,
- BUF_SHUFFLE_INPUT, BUF_SHUFFLE_TABLE) = range(19)
+ BUF_SHUFFLE_INPUT, BUF_SHUFFLE_TABLE, BUF_LOGUP_M, BUF_LOGUP_PHI) = range(21)
 (PKBUF_FIXED, PKBUF_FIXED_POLY, PKBUF_FIXED_COSET, PKBUF_SIGMA, PKBUF_SIGMA_POLY, PKBUF_SIGMA_COSET, PKBUF_L0_COSET, PKBUF_L_LAST_COSET,
  PKBUF_L_ACTIVE_COSET) = range(64, 73)
 
@@ -292,13 +293,14 @@ class Keys:
     constrain_equal in call order, columns as indices into the permutation argument.  `params` is the WHOLE SRS."""
 
     def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False, gates: GateProgram = None,
-                 lookups: LookupProgram = None, phases: AdvicePhases = None, shuffles: ShuffleProgram = None):
+                 lookups: LookupProgram = None, phases: AdvicePhases = None, shuffles: ShuffleProgram = None, logup: bool = False):
         self.cs = cs
+        self.logup = bool(logup)  # H2MI_KEYGEN_LOGUP; the library refuses it without a lookup program
         self.n_shuffles = shuffles.n_shuffles if shuffles is not None else 0
         cells, keep = pack_cells(fixed)
         cp = np.ascontiguousarray(np.array(copies, dtype=np.uint32).reshape(-1, 4))
         h = C.c_void_p()
-        flags = KEYGEN_VK_ONLY if vk_only else 0
+        flags = (KEYGEN_VK_ONLY if vk_only else 0) | (KEYGEN_LOGUP if logup else 0)
         if shuffles is not None:  # shuffle arguments: h2mi_prover_keygen_phases with the shuffles beside it; every other circuit takes the calls below
             check(lib.h2mi_prover_keygen_shuffles(C.byref(cs), C.byref(gates), C.byref(lookups) if lookups is not None else None,
                                                   C.byref(phases) if phases is not None else None, C.byref(shuffles), params.g_lagrange_handle, cells,
@@ -584,7 +586,8 @@ class Batch:
                 p._phase(lib.h2mi_prover_lookups(p.handle, theta.ctypes.data, p._points.ctypes.data), "lookups")
                 write(points(p, c.lookups))
         beta, gamma = sq(), sq()
-        n_sets = c.products - 1 - c.lookups // 2 - n_sh
+        n_lk = c.lookups if lead.keys.logup else c.lookups // 2  # lookup products; a logUp key: one running sum per multiplicity column
+        n_sets = c.products - 1 - n_lk - n_sh
         products = []
         for p in ms:
             p._phase(lib.h2mi_prover_products(p.handle, beta.ctypes.data, gamma.ctypes.data, p._points.ctypes.data), "products")
@@ -592,10 +595,10 @@ class Batch:
         for pts in products:  # every circuit's permutation products, then every circuit's lookup products, then the random polynomial
             write(pts[:n_sets])
         for pts in products:
-            write(pts[n_sets:n_sets + c.lookups // 2])
+            write(pts[n_sets:n_sets + n_lk])
         for pts in products:  # every circuit's shuffle products behind every circuit's lookup products
-            write(pts[n_sets + c.lookups // 2:n_sets + c.lookups // 2 + n_sh])
-        write(products[0][n_sets + c.lookups // 2 + n_sh:])
+            write(pts[n_sets + n_lk:n_sets + n_lk + n_sh])
+        write(products[0][n_sets + n_lk + n_sh:])
         if "products_done" in hooks:
             hooks["products_done"](self)
         y = sq()

@@ -168,6 +168,24 @@ def shuffle_product(k: int, d_input: DevBuf, d_shuffle: DevBuf, gamma: int, usab
     return True
 
 
+# ---- logUp, the logarithmic-derivative lookup argument [Haboeck; the `mv-lookup` feature of halo2_proofs forks — restated from memory,
+# pinned to DESIGN.md 4.5 and tests/logup_cases.py].  Transcript: [M] per lookup behind theta, [phi] per lookup in the lookup product's
+# slot behind beta and gamma; evaluations per lookup phi(x), phi(omega x), M(x); lookups.open the same three. -----------------------------
+def logup_multiplicity(k: int, d_input: DevBuf, d_table: DevBuf, usable_rows: int, d_m: DevBuf) -> int:
+    """h2mi_plonk_logup_multiplicity_dev: d_m[r] = #{i < usable_rows: input[i] = table[r]} on the first usable row r that holds its
+    table value, zero on the other usable rows (Montgomery); the blinding rows are left to the caller.  Returns the number of inputs
+    that are not table values (the lookup is unsatisfied when non-zero)."""
+    missing = C.c_uint64()
+    _check(lib.h2mi_plonk_logup_multiplicity_dev(d_input.ptr, d_table.ptr, k, usable_rows, d_m.ptr, C.byref(missing), None), "logup_multiplicity")
+    return missing.value
+
+
+def logup_sum(k: int, d_input: DevBuf, d_table: DevBuf, d_m: DevBuf, beta: int, usable_rows: int, d_phi: DevBuf) -> None:
+    """h2mi_plonk_logup_sum_dev: phi[0] = 0, phi[i+1] = phi[i] + 1 / (A_i + beta) - M_i / (S_i + beta) on rows 0 .. usable_rows of d_phi"""
+    _check(lib.h2mi_plonk_logup_sum_dev(d_input.ptr, d_table.ptr, d_m.ptr, k, usable_rows, F.fr_to_mont_limbs(beta).ctypes.data, d_phi.ptr, None),
+           "logup_sum")
+
+
 class _RangeCosets(C.Structure):
     _fields_ = [("a", C.c_void_p), ("lookup_advice", C.c_void_p), ("lookup_selector", C.c_void_p), ("q", C.c_void_p), ("table", C.c_void_p),
                 ("perm_value", C.c_void_p * 4), ("perm_sigma", C.c_void_p * 4), ("perm_z", C.c_void_p * 4), ("lookup_permuted_input", C.c_void_p),

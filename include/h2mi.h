@@ -358,6 +358,29 @@ int h2mi_plonk_lookup_product_dev(const void* d_input, const void* d_table, cons
  * gets no special handling: the one inversion is then of zero and z is meaningless. */
 int h2mi_plonk_shuffle_product_dev(const void* d_input, const void* d_shuffle, uint32_t k, uint32_t usable_rows, const uint64_t gamma[4], void* d_z,
                                    h2mi_stream_t stream);
+/* ---- logUp: the logarithmic-derivative lookup argument [Haboeck, "Multivariate lookups based on logarithmic derivatives"; the
+ * `mv-lookup` feature of the Scroll and ezkl lines of halo2_proofs — restated from memory like the shuffle, pinned to DESIGN.md 4.5 and
+ * tests/logup_cases.py and not to a crate].  One input tuple per lookup; d_input / d_table are the two sides compressed with theta on the
+ * 2^k rows (h2mi_plonk_expr_compress_dev at domain_k = k), Montgomery.
+ * h2mi_fr_sort_unique_first_dev is h2mi_fr_sort_unique_dev with one more output: d_first[r] (u32 x count) = the lowest position of
+ * d_in that holds distinct value r (the sort is stable over an index permutation).
+ * Multiplicities: d_m[r] = the number of rows i < usable_rows with d_input[i] = d_table[r] for every row r < usable_rows that is the
+ * FIRST usable row holding its table value, zero on every other row below usable_rows — as field elements in Montgomery form; rows at
+ * and beyond usable_rows (the blinding rows) are left untouched.  The table's usable rows are sorted into distinct values on the
+ * device, the inputs ranked against them with equal ranks merged per wavefront and workgroup (k_lk_rank), the counts scattered to
+ * the first rows.  not_in_table_out (mandatory; the call synchronises on it): the inputs that are no table value — the lookup is
+ * unsatisfied then and d_m does not sum to usable_rows. */
+int h2mi_fr_sort_unique_first_dev(const void* d_in, uint32_t count, void* d_sorted_canonical, void* d_sorted_mont, void* d_mult /* u32 x count */,
+                                  void* d_first /* u32 x count */, uint32_t* n_unique_out, h2mi_stream_t stream);
+int h2mi_plonk_logup_multiplicity_dev(const void* d_input, const void* d_table, uint32_t k, uint32_t usable_rows, void* d_m,
+                                      uint64_t* not_in_table_out, h2mi_stream_t stream);
+/* The running sum: phi[0] = 0, phi[i+1] = phi[i] + 1 / (A_i + beta) - M_i / (S_i + beta), i < usable_rows; rows 0 .. usable_rows of
+ * d_phi are written (phi[usable_rows] = 0 when d_m holds the multiplicities of a satisfied lookup), the blinding rows untouched.  One
+ * fraction per row, ONE field inversion per call (prefix and suffix products of the denominators), then an additive prefix scan.
+ * Dense form only.  A zero denominator (probability about 2 usable_rows / r over beta) gets no special handling: phi is then
+ * meaningless. */
+int h2mi_plonk_logup_sum_dev(const void* d_input, const void* d_table, const void* d_m, uint32_t k, uint32_t usable_rows, const uint64_t beta[4],
+                             void* d_phi, h2mi_stream_t stream);
 /* evaluate_h + vanishing division for the halo2-lib constraint systems [halo2-base shapes restated from memory]: gate
  * q (a + a(wX) a(w^2 X) - a(w^3 X)), permutation argument over n_perm <= 4 columns in chunks of chunk_len (= cs.degree()
  * - 2 = 1 .. 3), and — has_lookup (the Range builder, extended domain 4n) — one lookup in `table` of either
@@ -469,6 +492,11 @@ typedef struct {
   const void* l_last;
   const void* l_active;
 } h2mi_expr_cosets;
+/* n_lookups | H2MI_LOOKUPS_LOGUP in an h2mi_expr_cosets: every lookup of the entry is a logUp argument.  lookup_permuted_input then holds
+ * the multiplicity column M and lookup_z the running sum phi (extended-coset forms), lookup_permuted_table is not read (may be NULL),
+ * and a lookup contributes three terms in the place of its five, Horner in y: l_0 phi, l_last phi, l_active ((phi(wX) - phi(X)) (A +
+ * beta)(S + beta) - ((S + beta) - M (A + beta))); gamma is not read.  In a batch every entry states the same mode. */
+#define H2MI_LOOKUPS_LOGUP 0x80000000u
 /* H2MI_EINVAL for a program that is malformed (unknown op, stack underflow or deeper than H2MI_MAX_EXPR_STACK, not exactly one value
  * at an END, no final END, empty), reads a NULL column or a constant beyond n_constants, or rotates by 2^k or more.  The column
  * pointers, the program and its constants (converted to the kernel's domain) travel in one device buffer written on `stream`. */

@@ -137,6 +137,23 @@ typedef struct h2mi_prover_s* h2mi_prover_t; /* the buffers, streams and phase s
  * The pk holds: fixed / sigma columns in Lagrange, coefficient and extended-coset form, l_0 / l_last / l_active cosets, the support
  * of the copy constraints, each lookup table's sorted distinct values. */
 #define H2MI_KEYGEN_VK_ONLY 1u
+/* H2MI_KEYGEN_LOGUP: every program lookup of the key is proven with the logarithmic-derivative argument ("logUp": Haboeck; the
+ * `mv-lookup` feature of the Scroll and ezkl lines of halo2_proofs) in place of the permuted columns and the grand product.  Like the
+ * shuffle it is RESTATED FROM MEMORY: DESIGN.md 4.5 and tests/logup_cases.py are the pin, not a crate.  Selection is per key — all of
+ * its lookups or none; one input tuple per lookup (the crate's merging of several input sets over one table is not modelled).
+ * Accepted by h2mi_prover_keygen_exprs / _phases / _shuffles with lookups != NULL only (H2MI_EINVAL otherwise, and from
+ * h2mi_prover_keygen / _keygen_gates always); h2mi_lookup_program, its check, the required degree, blinding_factors and the query lists
+ * are what they are without it.  Per lookup, with A and S the two sides compressed with theta and u the usable rows:
+ *   M[r] = #{i < u : A[i] = S[r]} on the FIRST usable row r that holds its table value, 0 on every other usable row, blinding scalars
+ *          on rows u .. 2^k - 1 (the permuted columns' stream: (blinding_factors + 1) scalars per lookup, in lookup order);
+ *   phi[0] = 0, phi[i+1] = phi[i] + 1 / (A_i + beta) - M_i / (S_i + beta) for i < u, blinding scalars on rows u + 1 .. 2^k - 1 (the
+ *          lookup products' stream: blinding_factors scalars per lookup); phi[u] = 0; gamma is not used.
+ * h2mi_prover_lookups returns n_lookups points ([M], in lookup order) instead of 2 n_lookups and refuses an input that is no table
+ * value with H2MI_EUNSAT, as without the flag; h2mi_prover_products returns [phi] in the lookup product's slot.  Quotient, per lookup
+ * in the place of its five terms: l_0 phi, l_last phi, l_active ((phi(wX) - phi(X)) (A + beta)(S + beta) - ((S + beta) - M (A + beta))).
+ * Evaluations per lookup in the place of its five: phi(x), phi(omega x), M(x); lookups.open: phi at x, phi at omega x, M at x.
+ * h2mi_prover_check tests membership and does not depend on the argument.  Batches: M and phi per member, one joint quotient. */
+#define H2MI_KEYGEN_LOGUP 2u
 int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
                        size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
 /* The same with the gates as a program (cs->gates == H2MI_GATES_EXPRESSIONS; any other value: H2MI_EINVAL, as is that value given to
@@ -420,6 +437,7 @@ enum {
   H2MI_BUF_RANDOM_POLY, H2MI_BUF_H /* (degree - 1) n coefficients: piece i at i n */, H2MI_BUF_H_POLY,
   H2MI_BUF_SHPLONK_H, H2MI_BUF_SHPLONK_H2,
   H2MI_BUF_SHUFFLE_Z, H2MI_BUF_SHUFFLE_Z_POLY, H2MI_BUF_SHUFFLE_INPUT /* compressed rows */, H2MI_BUF_SHUFFLE_TABLE /* compressed rows */,
+  H2MI_BUF_LOGUP_M /* a logUp key's multiplicity column of lookup `index`, rows */, H2MI_BUF_LOGUP_PHI /* its running sum, rows */,
   H2MI_PKBUF_FIXED = 64, H2MI_PKBUF_FIXED_POLY, H2MI_PKBUF_FIXED_COSET, H2MI_PKBUF_SIGMA, H2MI_PKBUF_SIGMA_POLY, H2MI_PKBUF_SIGMA_COSET,
   H2MI_PKBUF_L0_COSET, H2MI_PKBUF_L_LAST_COSET, H2MI_PKBUF_L_ACTIVE_COSET
 };
