@@ -100,6 +100,11 @@ def _load():
         "h2mi_plonk_shuffle_product_dev": ([vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_logup_multiplicity_dev": ([vp, vp, C.c_uint32, C.c_uint32, vp, u64p, vp], C.c_int),
         "h2mi_plonk_logup_sum_dev": ([vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
+        "h2mi_plonk_logup_multiplicity_sets_dev": ([vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, u64p, vp], C.c_int),
+        "h2mi_plonk_logup_sum_sets_dev": ([vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
+        "h2mi_plonk_evaluate_h_expr_lg_dev": ([vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "h2mi_plonk_evaluate_h_expr_batch_lg_dev": ([vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
+                                                     vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_range_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_flex_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_expr_dev": ([vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
@@ -138,6 +143,8 @@ def _load():
         "h2mi_shuffle_program_check": ([vp, vp, C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_shuffle_phases_check": ([vp, vp, vp, C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_prover_keygen_shuffles": ([vp, vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
+        "h2mi_logup_inputs_check": ([vp, vp, vp, vp, C.POINTER(C.c_uint32)], C.c_int),
+        "h2mi_prover_keygen_logup": ([vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_prover_pk_release": ([vp], C.c_int),
         "h2mi_prover_vk_commitments": ([vp, vp, vp], C.c_int),
         "h2mi_prover_create": ([vp, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(vp)], C.c_int),

@@ -41,18 +41,18 @@ __device__ __forceinline__ int cmp256(const fe& a, const fe& b) {  // canonical 
 // uniform), then within the workgroup through a 64-slot LDS table keyed by rank (a slot taken by another rank falls
 // back to the global atomic), and only the table is flushed to HBM: 2^22 zero rows -> 4096 global atomics.
 constexpr uint32_t LK_SLOTS = 64, LK_EMPTY = 0xFFFFFFFFu;
-__global__ void __launch_bounds__(1024) k_lk_rank(const fe* input, uint32_t u, const fe* sorted, uint32_t n_unique, uint32_t* cnt, uint32_t* missing) {
+// `src`: this thread's input element, NULL for a thread beyond the rows
+__device__ __forceinline__ void lk_rank_body(const fe* src, const fe* sorted, uint32_t n_unique, uint32_t* cnt, uint32_t* missing) {
   __shared__ uint32_t hkey[LK_SLOTS], hcnt[LK_SLOTS];
   if (threadIdx.x < LK_SLOTS) {
     hkey[threadIdx.x] = LK_EMPTY;
     hcnt[threadIdx.x] = 0;
   }
   __syncthreads();
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t lo = LK_EMPTY;
   bool active = false;
-  if (i < u) {
-    const fe v = fe_from_mont<Fr>(fe_load(&input[i]));
+  if (src) {
+    const fe v = fe_from_mont<Fr>(fe_load(src));
     // first index with sorted[idx] >= v.  A range-check table holds 0 .. 2^bits - 1, where a value IS its rank: the guess "rank = low
     // word of v" is tried first (one load instead of seventeen dependent ones); any other table falls through to the binary search
     const uint32_t guess = min(v.v[0], n_unique - 1);
@@ -91,6 +91,18 @@ __global__ void __launch_bounds__(1024) k_lk_rank(const fe* input, uint32_t u, c
   }
   __syncthreads();
   if (threadIdx.x < LK_SLOTS && hkey[threadIdx.x] != LK_EMPTY) atomicAdd(&cnt[hkey[threadIdx.x]], hcnt[threadIdx.x]);
+}
+__global__ void __launch_bounds__(1024) k_lk_rank(const fe* input, uint32_t u, const fe* sorted, uint32_t n_unique, uint32_t* cnt, uint32_t* missing) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  lk_rank_body(i < u ? &input[i] : nullptr, sorted, n_unique, cnt, missing);
+}
+// logUp over several input sets [restated in DESIGN.md 4.5]: the usable rows of gridDim.y consecutive vectors (`stride` elements apart)
+// ranked in ONE launch into the same histogram and the same counter of absent inputs.  blockIdx.y is the set, so a workgroup (and its
+// LDS table) stays inside one set, no index passes 32 bits and the all-equal input still costs one global atomic per workgroup
+__global__ void __launch_bounds__(1024) k_lk_rank_sets(const fe* inputs, size_t stride, uint32_t u, const fe* sorted, uint32_t n_unique, uint32_t* cnt,
+                                                       uint32_t* missing) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  lk_rank_body(i < u ? &inputs[(size_t)blockIdx.y * stride + i] : nullptr, sorted, n_unique, cnt, missing);
 }
 
 // Membership alone, for the witness check (h2mi_prover_check): is the input of usable row i one of the table's distinct values?  The
@@ -620,8 +632,14 @@ int h2mi_fr_sort_unique_first_dev(const void* d_in, uint32_t count, void* d_sort
 
 int h2mi_plonk_logup_multiplicity_dev(const void* d_input, const void* d_table, uint32_t k, uint32_t usable_rows, void* d_m, uint64_t* not_in_table_out,
                                       h2mi_stream_t stream) {
+  return h2mi_plonk_logup_multiplicity_sets_dev(d_input, 1, d_table, k, usable_rows, d_m, not_in_table_out, stream);
+}
+
+int h2mi_plonk_logup_multiplicity_sets_dev(const void* d_inputs, uint32_t n_inputs, const void* d_table, uint32_t k, uint32_t usable_rows, void* d_m,
+                                           uint64_t* not_in_table_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
-  if (!d_input || !d_table || !d_m || !not_in_table_out) return H2MI_EINVAL;  // the count is mandatory, as for the permuted columns
+  if (!d_inputs || !d_table || !d_m || !not_in_table_out) return H2MI_EINVAL;  // the count is mandatory, as for the permuted columns
+  if (n_inputs == 0 || n_inputs > H2MI_MAX_LOGUP_INPUTS) return H2MI_EINVAL;
   if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k)) return H2MI_ERANGE;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   {
@@ -631,7 +649,7 @@ int h2mi_plonk_logup_multiplicity_dev(const void* d_input, const void* d_table, 
   hipStream_t s = pick_stream(stream);
   const uint32_t u = usable_rows, u4 = (u + 3u) & ~3u;
   // behind the sort's own scratch (words): sorted[8 u4] sorted_mont[8 u4] mult[u4] first[u4] cnt[u4] missing[4]; reserved in one piece
-  // BEFORE the sort, whose own reservation then finds room and moves nothing
+  // BEFORE the sort, whose own reservation then finds room and moves nothing.  The input sets need none: they share cnt and missing
   const size_t base = (su_scratch_words(u) + 3u) & ~(size_t)3u, words = base + 19 * (size_t)u4 + 4;
   {
     int rcs = lk_scratch_reserve(words);
@@ -644,12 +662,17 @@ int h2mi_plonk_logup_multiplicity_dev(const void* d_input, const void* d_table, 
   uint32_t* cnt = first + u4;
   uint32_t* missing = cnt + u4;
   uint32_t n_unique = 0;
-  int rc = sort_unique(d_table, u, sorted, sorted_mont, mult, first, &n_unique, stream);  // waits for an earlier call on another stream
+  int rc = sort_unique(d_table, u, sorted, sorted_mont, mult, first, &n_unique, stream);  // ONE sort, whatever n_inputs; waits for an earlier call on another stream
   if (rc) return rc;
   if (n_unique == 0 || n_unique > u) return H2MI_EHIP;
   H2_HIP(hipMemsetAsync(cnt, 0, ((size_t)u4 + 4) * 4, s));
   H2_HIP(hipMemsetAsync(d_m, 0, (size_t)u * 32, s));  // rows 0 .. u - 1; the blinding rows behind them are the caller's
-  H2_LAUNCH("k_lk_rank", k_lk_rank, ceil_div_u32(u, 1024), 1024, 0, s, (const fe*)d_input, u, (const fe*)sorted, n_unique, cnt, missing);
+  if (n_inputs == 1) {
+    H2_LAUNCH("k_lk_rank", k_lk_rank, ceil_div_u32(u, 1024), 1024, 0, s, (const fe*)d_inputs, u, (const fe*)sorted, n_unique, cnt, missing);
+  } else {
+    H2_LAUNCH("k_lk_rank_sets", k_lk_rank_sets, dim3(ceil_div_u32(u, 1024), n_inputs), 1024, 0, s, (const fe*)d_inputs, (size_t)1 << k, u,
+              (const fe*)sorted, n_unique, cnt, missing);
+  }
   H2_LAUNCH("k_logup_scatter", k_logup_scatter, ceil_div_u32(n_unique, 256), 256, 0, s, (const uint32_t*)cnt, (const uint32_t*)first, n_unique, u, (fe*)d_m);
   if (!g_lk_event) H2_HIP(hipEventCreateWithFlags(&g_lk_event, hipEventDisableTiming));
   H2_HIP(hipEventRecord(g_lk_event, s));

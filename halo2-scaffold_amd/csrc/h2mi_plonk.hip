@@ -465,6 +465,8 @@ __global__ void __launch_bounds__(256) k_evaluate_h_range(RangeCosets c, uint32_
 struct FlexCosets {
   uint32_t n_gates, n_perm, chunk, n_lookups, n_shuffles;
   uint32_t logup;  // the lookups are logUp arguments: lk_pin holds M, lk_z the running sum, lk_ptab is not read
+  // logUp: the input sets of lookup l, four bits each (1 .. H2MI_MAX_LOGUP_INPUTS): lk_in[l] points at that many CONSECUTIVE vectors
+  uint32_t lk_sets;
   const fe* gate_a[H2MI_FLEX_MAX_GATES];
   const fe* gate_q[H2MI_FLEX_MAX_GATES];
   const fe* perm_value[H2MI_FLEX_MAX_PERM];
@@ -536,12 +538,23 @@ __device__ __forceinline__ void evaluate_h_fold(const Circuit& c, const FlexCose
     if (sh.logup) {
       // logUp [Haboeck; the mv-lookup feature of halo2_proofs forks, restated from memory in DESIGN.md 4.5]: three terms, no gamma.  The
       // mode is the launch's (wave-uniform); M and phi arrive through the slots of the permuted input and of the product
-      const f29 ab = add(a_in, beta), sb = add(ld(&c.lk_table[l][idx]), beta);
+      // With K input sets over the one table the fraction of a row is N / D, built by the recurrence (N, D) = (-M, s), then per input
+      // N <- N a_j + D, D <- D a_j (a_j = A_j + beta, s = S + beta): two products per input, no array.  K is launch data (wave-uniform)
+      // and set j of the lookup is the vector j * 2^ext_k behind lk_in[l].  Bounds in units of p (a load 1.04, a product 1 + 0.006 a b):
+      // a_j, s <= 2.08; N starts at 4 (a negation) and is a product plus D afterwards, <= 1.05 + 2.08; D <= 2.08, then a product
       const f29 phi = ld(&c.lk_z[l][idx]);
       horner(acc, y, mul(phi, l0));
       horner(acc, y, mul(phi, ll));
-      const f29 lhs = mul(mul(sub(ld(&c.lk_z[l][r_next]), phi), ab), sb), rhs = red(sub(sb, mul(ld(&c.lk_pin[l][idx]), ab)));
-      horner(acc, y, mul(sub(lhs, rhs), lact));
+      f29 den = add(ld(&c.lk_table[l][idx]), beta), num = sub(f29_zero(), ld(&c.lk_pin[l][idx]));
+      const uint32_t sets = (sh.lk_sets >> (4 * l)) & 15u;
+      for (uint32_t j = 0;;) {
+        const f29 ab = add(a_in, beta);
+        num = add(mul(num, ab), den);
+        den = mul(den, ab);
+        if (++j >= sets) break;
+        a_in = ld(&c.lk_in[l][(size_t)j * size + idx]);
+      }
+      horner(acc, y, mul(sub(mul(sub(ld(&c.lk_z[l][r_next]), phi), den), num), lact));
       continue;
     }
     const f29 t_in = ld(&c.lk_table[l][idx]), ap = ld(&c.lk_pin[l][idx]), ap_prev = ld(&c.lk_pin[l][r_prev]), sp = ld(&c.lk_ptab[l][idx]);
@@ -873,6 +886,28 @@ __global__ void __launch_bounds__(256) k_logup_numden(const fe* input, const fe*
   fe_store(&num[i], pack261(red(sub(sb, mul(ld(&mult[i]), ab)))));
   fe_store(&den[i], pack261(mul(ab, sb)));
 }
+// With n_sets >= 2 input vectors (`stride` elements apart) over the one table the row's fraction is sum_j 1 / a_j - M / s = N / D, a_j =
+// A_j + beta, s = S + beta, by the recurrence (N, D) = (-M, s), then per input N <- N a_j + D, D <- D a_j: D = s prod a_j and N = s sum_j
+// prod_{m != j} a_m - M prod a_j, two products per input, no per-thread array; one input would give the kernel above's pair.  A kernel of
+// its own: the loop-carried pair and beta cost 15 VGPRs, and the one-set kernel keeps its 8 waves per SIMD.  gen::'s bounds in units of
+// p, whatever n_sets (6 at most): a load <= 1.04, so a_j, s <= 2.08; N starts as a negation (4, which a product takes), then is a product
+// plus D: <= (1 + 0.006 * 4 * 2.08) + 2.08 < 3.2 in the first round and <= (1 + 0.006 * 3.2 * 2.08) + 1.03 < 2.1 afterwards; D <= 2.08,
+// then a product <= 1 + 0.006 * 2.08^2 < 1.03.  N is reduced once before it is packed; D leaves the loop as a product
+__global__ void __launch_bounds__(256) k_logup_numden_sets(const fe* inputs, uint32_t n_sets, size_t stride, const fe* table, const fe* mult, fe beta,
+                                                           uint32_t u, fe* num, fe* den) {
+  using namespace gen;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= u) return;
+  const f29 b = cst(beta);
+  f29 d = add(ld(&table[i]), b), n = sub(f29_zero(), ld(&mult[i]));
+  for (uint32_t j = 0; j < n_sets; j++) {
+    const f29 ab = add(ld(&inputs[(size_t)j * stride + i]), b);
+    n = add(mul(n, ab), d);
+    d = mul(d, ab);
+  }
+  fe_store(&num[i], pack261(red(n)));
+  fe_store(&den[i], pack261(d));
+}
 // The additive scan over Fr, shaped like the multiplicative one (local / offsets / apply, tiles of AS_TILE) without a multiplication:
 // the words are canonical (below r), so a sum is one 256-bit addition and one conditional subtraction on the 32-bit-limb layer, and
 // the Montgomery factor 2^261 rides along unchanged.
@@ -967,6 +1002,7 @@ static bool fill_tail(FlexCosets& fc, const Cosets& c) {
   fc.n_perm = c.n_perm; fc.chunk = c.chunk_len ? c.chunk_len : 1;
   fc.n_lookups = c.n_lookups & ~(uint32_t)H2MI_LOOKUPS_LOGUP; fc.logup = (c.n_lookups & H2MI_LOOKUPS_LOGUP) ? 1u : 0u;
   if (fc.n_lookups > H2MI_FLEX_MAX_LOOKUPS) return false;
+  fc.lk_sets = 0x11111111u;  // one input set per lookup; fill_sets states another count
   for (uint32_t j = 0; j < c.n_perm; j++) {
     fc.perm_value[j] = (const fe*)c.perm_value[j]; fc.perm_sigma[j] = (const fe*)c.perm_sigma[j];
     if (!fc.perm_value[j] || !fc.perm_sigma[j]) return false;
@@ -982,6 +1018,20 @@ static bool fill_tail(FlexCosets& fc, const Cosets& c) {
   }
   fc.l0 = (const fe*)c.l0; fc.l_last = (const fe*)c.l_last; fc.l_active = (const fe*)c.l_active;
   return fc.l0 && fc.l_last && fc.l_active;
+}
+
+// the input sets of an h2mi_logup_cosets (NULL: one per lookup) -> the kernels' argument.  A count of 0 or above the maximum, or
+// another count than 1 where the lookups are no logUp arguments, is the caller's mistake
+static bool fill_sets(FlexCosets& fc, const h2mi_logup_cosets* lg) {
+  static_assert(H2MI_FLEX_MAX_LOOKUPS * 4 <= 32 && H2MI_MAX_LOGUP_INPUTS < 16, "four bits per lookup");
+  if (!lg) return true;
+  fc.lk_sets = 0;
+  for (uint32_t l = 0; l < H2MI_FLEX_MAX_LOOKUPS; l++) {
+    const uint32_t sets = l < fc.n_lookups ? lg->n_inputs[l] : 1u;  // counts beyond n_lookups are not read
+    if (sets == 0 || sets > H2MI_MAX_LOGUP_INPUTS || (sets != 1 && !fc.logup)) return false;
+    fc.lk_sets |= sets << (4 * l);
+  }
+  return true;
 }
 
 // the shuffle pointers of an h2mi_shuffle_cosets (NULL: none) -> the kernels' argument
@@ -1337,8 +1387,14 @@ int h2mi_plonk_shuffle_product_dev(const void* d_input, const void* d_shuffle, u
 
 int h2mi_plonk_logup_sum_dev(const void* d_input, const void* d_table, const void* d_m, uint32_t k, uint32_t usable_rows, const uint64_t beta[4],
                              void* d_phi, h2mi_stream_t stream) {
+  return h2mi_plonk_logup_sum_sets_dev(d_input, 1, d_table, d_m, k, usable_rows, beta, d_phi, stream);
+}
+
+int h2mi_plonk_logup_sum_sets_dev(const void* d_inputs, uint32_t n_inputs, const void* d_table, const void* d_m, uint32_t k, uint32_t usable_rows,
+                                  const uint64_t beta[4], void* d_phi, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
-  if (!d_input || !d_table || !d_m || !beta || !d_phi) return H2MI_EINVAL;
+  const void* d_input = d_inputs;
+  if (!d_input || !d_table || !d_m || !beta || !d_phi || n_inputs == 0 || n_inputs > H2MI_MAX_LOGUP_INPUTS) return H2MI_EINVAL;
   if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k)) return H2MI_ERANGE;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
@@ -1354,8 +1410,12 @@ int h2mi_plonk_logup_sum_dev(const void* d_input, const void* d_table, const voi
   fe* totals = S + u;
   fe* offsets = totals + nblocks;
   fe* inv_total = offsets + nblocks;
-  H2_LAUNCH("k_logup_numden", k_logup_numden, ceil_div_u32(u, 256), 256, 0, s, (const fe*)d_input, (const fe*)d_table, (const fe*)d_m, host_fe(beta),
-            usable_rows, num, P);
+  if (n_inputs == 1)
+    H2_LAUNCH("k_logup_numden", k_logup_numden, ceil_div_u32(u, 256), 256, 0, s, (const fe*)d_input, (const fe*)d_table, (const fe*)d_m, host_fe(beta),
+              usable_rows, num, P);
+  else
+    H2_LAUNCH("k_logup_numden_sets", k_logup_numden_sets, ceil_div_u32(u, 256), 256, 0, s, (const fe*)d_input, n_inputs, (size_t)1 << k, (const fe*)d_table,
+              (const fe*)d_m, host_fe(beta), usable_rows, num, P);
   H2_HIP(hipMemcpyAsync(S, P, u * 32, hipMemcpyDeviceToDevice, s));
   rc = mulscan(P, u, 0, totals, offsets, s);
   if (!rc) rc = mulscan(S, u, 1, totals, offsets, s);
@@ -1486,6 +1546,15 @@ int h2mi_plonk_evaluate_h_expr_sh_dev(const h2mi_expr_cosets* c, const h2mi_shuf
                                       const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
                                       const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out,
                                       h2mi_stream_t stream) {
+  return h2mi_plonk_evaluate_h_expr_lg_dev(c, shuffles, nullptr, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma, y, delta, zeta,
+                                           extended_omega, t_inv, d_h_out, stream);
+}
+
+int h2mi_plonk_evaluate_h_expr_lg_dev(const h2mi_expr_cosets* c, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                      const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
+                                      uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
+                                      const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
+                                      void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!c || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
   if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
@@ -1496,7 +1565,7 @@ int h2mi_plonk_evaluate_h_expr_sh_dev(const h2mi_expr_cosets* c, const h2mi_shuf
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
   FlexCosets fc;
   memset(&fc, 0, sizeof(fc));
-  if (!fill_tail(fc, *c) || !fill_shuffles(fc, shuffles)) return H2MI_EINVAL;
+  if (!fill_tail(fc, *c) || !fill_shuffles(fc, shuffles) || !fill_sets(fc, logup)) return H2MI_EINVAL;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
@@ -1533,6 +1602,15 @@ int h2mi_plonk_evaluate_h_expr_batch_sh_dev(const h2mi_expr_cosets* circuits, co
                                             uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
                                             const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
                                             const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
+  return h2mi_plonk_evaluate_h_expr_batch_lg_dev(circuits, shuffles, nullptr, n_circuits, gates, challenges, n_challenges, k, extended_k, blinding_factors,
+                                                 beta, gamma, y, delta, zeta, extended_omega, t_inv, d_h_out, stream);
+}
+
+int h2mi_plonk_evaluate_h_expr_batch_lg_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                            uint32_t n_circuits, const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges,
+                                            uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
+                                            const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
+                                            const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!circuits || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
   if (n_circuits == 0 || n_circuits > H2MI_MAX_CIRCUITS) return H2MI_EINVAL;
@@ -1548,7 +1626,7 @@ int h2mi_plonk_evaluate_h_expr_batch_sh_dev(const h2mi_expr_cosets* circuits, co
   static_assert(sizeof(CircuitCosets) % 8 == 0, "records are arrays of pointers");
   FlexCosets sh;
   memset(&sh, 0, sizeof(sh));
-  if (!fill_tail(sh, c0) || !fill_shuffles(sh, shuffles)) return H2MI_EINVAL;
+  if (!fill_tail(sh, c0) || !fill_shuffles(sh, shuffles) || !fill_sets(sh, logup)) return H2MI_EINVAL;  // the counts are the key's: one struct for the batch
   const size_t rec_fe = (sizeof(CircuitCosets) + sizeof(fe) - 1) / sizeof(fe), prog_fe = im.image.size();
   im.image.resize(prog_fe + rec_fe * n_circuits);
   for (uint32_t i = 0; i < n_circuits; i++) {

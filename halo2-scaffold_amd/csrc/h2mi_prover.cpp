@@ -145,12 +145,18 @@ int check_program(const h2mi_constraint_system& cs, const h2mi_gate_program* gat
 
 // the rules of h2mi_lookup_program_check (include/h2mi_prover.h).  slices: per lookup the sub-programs of its input and its table
 // polynomials (they point into lp->exprs.ops and share its constants).
+// With an h2mi_logup_inputs (the rules of h2mi_logup_inputs_check): lookup l holds sets[l] input tuples, input[l][j] is tuple j, and the
+// required degree is the logUp rule 2 + sum_j max(1, deg A_j) + max(1, deg S) — with one set the number the lookup rule gives.
 struct LookupSlices {
-  h2mi_gate_program input[H2MI_MAX_LOOKUPS], table[H2MI_MAX_LOOKUPS];
+  uint32_t sets[H2MI_MAX_LOOKUPS];
+  h2mi_gate_program input[H2MI_MAX_LOOKUPS][H2MI_MAX_LOGUP_INPUTS], table[H2MI_MAX_LOOKUPS];
 };
 int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_program* lp, uint32_t* degree_out, LookupSlices* slices,
-                         uint32_t n_challenges = 0) {
+                         uint32_t n_challenges = 0, const h2mi_logup_inputs* li = nullptr) {
   if (!lp || lp->n_lookups == 0 || lp->n_lookups > H2MI_MAX_LOOKUPS || lp->n_lookups != cs.n_lookups) return H2MI_EINVAL;
+  auto sets = [&](uint32_t l) { return li ? li->n_inputs[l] : 1u; };
+  for (uint32_t l = 0; l < lp->n_lookups; l++)
+    if (sets(l) == 0 || sets(l) > H2MI_MAX_LOGUP_INPUTS) return H2MI_EINVAL;
   h2::ExprShape all;
   {
     h2mi_constraint_system any = cs;  // the structural rules and the query lists; the degree rule is per lookup, below
@@ -161,7 +167,7 @@ int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_pro
   uint32_t want = 0;
   for (uint32_t l = 0; l < lp->n_lookups; l++) {
     if (lp->n_pairs[l] == 0 || lp->n_pairs[l] > H2MI_MAX_EXPR_OPS) return H2MI_EINVAL;
-    want += 2 * lp->n_pairs[l];
+    want += (sets(l) + 1) * lp->n_pairs[l];
   }
   if (all.n_polys != want) return H2MI_EINVAL;
   uint32_t pos = 0, degree = 0;
@@ -175,8 +181,11 @@ int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_pro
     return std::max(sh.degree, 1u);
   };
   for (uint32_t l = 0; l < lp->n_lookups; l++) {
-    const uint32_t in = take(lp->n_pairs[l], slices ? &slices->input[l] : nullptr), tab = take(lp->n_pairs[l], slices ? &slices->table[l] : nullptr);
-    const uint32_t d = std::max(4u, 2 + in + tab);  // [RECALL plonk/lookup.rs Argument::required_degree]
+    uint32_t in = 0;
+    for (uint32_t j = 0; j < sets(l); j++) in += take(lp->n_pairs[l], slices ? &slices->input[l][j] : nullptr);
+    const uint32_t tab = take(lp->n_pairs[l], slices ? &slices->table[l] : nullptr);
+    if (slices) slices->sets[l] = sets(l);
+    const uint32_t d = std::max(4u, 2 + in + tab);  // [RECALL plonk/lookup.rs Argument::required_degree]; several sets: DESIGN.md 4.5
     if (d > cs.degree) return H2MI_EINVAL;
     degree = std::max(degree, d);
   }
@@ -228,7 +237,8 @@ int check_shuffle_program(const h2mi_constraint_system& cs, const h2mi_shuffle_p
 // the rules of h2mi_advice_phases_check (include/h2mi_prover.h) [RECALL halo2_proofs v2023_02_02 plonk/circuit.rs advice_column_in,
 // challenge_usable_after]: a column in phase p > 0 needs one in phase p - 1 and a challenge usable after p needs a column in p — with
 // n_phases stated, that is: every phase below n_phases holds a column, every column and every challenge names a phase below it
-int check_phases(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, const h2mi_advice_phases& ph) {
+int check_phases(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, const h2mi_advice_phases& ph,
+                 const h2mi_logup_inputs* inputs = nullptr) {
   if (cs.gates != H2MI_GATES_EXPRESSIONS || !gates) return H2MI_EINVAL;
   if (ph.n_phases == 0 || ph.n_phases > H2MI_MAX_ADVICE_PHASES || ph.n_challenges > H2MI_MAX_CHALLENGES || cs.n_advice > H2MI_MAX_ADVICE) return H2MI_EINVAL;
   uint32_t columns[H2MI_MAX_ADVICE_PHASES] = {0, 0, 0};
@@ -241,15 +251,15 @@ int check_phases(const h2mi_constraint_system& cs, const h2mi_gate_program* gate
   for (uint32_t i = 0; i < ph.n_challenges; i++)
     if (ph.challenge_phase[i] >= ph.n_phases) return H2MI_EINVAL;
   int rc = check_program(cs, gates, nullptr, ph.n_challenges);
-  if (!rc && lookups) rc = check_lookup_program(cs, lookups, nullptr, nullptr, ph.n_challenges);
+  if (!rc && lookups) rc = check_lookup_program(cs, lookups, nullptr, nullptr, ph.n_challenges, inputs);
   return rc;
 }
 
 void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, const h2mi_advice_phases* phases,
-              const h2mi_shuffle_program* shuffles) {
+              const h2mi_shuffle_program* shuffles, const h2mi_logup_inputs* inputs = nullptr) {
   auto bad = [](const char* what) { throw Error(H2MI_EINVAL, std::string("constraint system: ") + what); };
   const uint32_t n_ch = phases ? phases->n_challenges : 0;
-  if (phases && check_phases(cs, gates, lookups, *phases)) bad("advice phases / challenges");
+  if (phases && check_phases(cs, gates, lookups, *phases, inputs)) bad("advice phases / challenges");
   if (cs.k == 0 || cs.k > H2MI_MAX_LOG_N) throw Error(H2MI_ERANGE, "constraint system: k");
   if (cs.degree < 3 || cs.degree > 9) bad("degree");
   if (((uint64_t)1 << cs.k) <= (uint64_t)cs.blinding_factors + 2) throw Error(H2MI_ERANGE, "constraint system: no usable rows");
@@ -283,7 +293,7 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, 
     }
     if (lookups) {  // the lookups as a program: cs.lookups[] is not read
       if (cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_exprs takes H2MI_GATES_EXPRESSIONS");
-      if (check_lookup_program(cs, lookups, nullptr, nullptr, n_ch)) bad("lookup program");
+      if (check_lookup_program(cs, lookups, nullptr, nullptr, n_ch, inputs)) bad("lookup program");
     }
     for (uint32_t l = 0; !lookups && l < cs.n_lookups; l++) {
       const h2mi_lookup& lk = cs.lookups[l];
@@ -408,8 +418,8 @@ void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells) {
 
 std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                                   const h2mi_advice_phases* phases, uint64_t g_lagrange, const h2mi_column_cells* fixed, const uint32_t* copies,
-                                  size_t n_copies, unsigned flags, const h2mi_shuffle_program* shuffles = nullptr) {
-  validate(cs, gates, lookups, phases, shuffles);
+                                  size_t n_copies, unsigned flags, const h2mi_shuffle_program* shuffles = nullptr, const h2mi_logup_inputs* inputs = nullptr) {
+  validate(cs, gates, lookups, phases, shuffles, inputs);
   std::unique_ptr<h2mi_pk_s> pkp(new h2mi_pk_s(cs));
   h2mi_pk_s& pk = *pkp;
   std::memset(&pk.phases, 0, sizeof(pk.phases));
@@ -427,7 +437,8 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     if (lookups->exprs.n_constants) pk.lookup_constants.assign(lookups->exprs.constants, lookups->exprs.constants + 4 * (size_t)lookups->exprs.n_constants);
     h2mi_lookup_program own = *lookups;
     own.exprs = {pk.lookup_ops.data(), lookups->exprs.n_ops, pk.lookup_constants.data(), lookups->exprs.n_constants};
-    if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices, pk.phases.n_challenges)) throw Error(H2MI_EINVAL, "lookup program");
+    // an h2mi_logup_inputs is copied into the slices (their `sets`): the key reads the caller's struct here and never again
+    if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices, pk.phases.n_challenges, inputs)) throw Error(H2MI_EINVAL, "lookup program");
   }
   if (shuffles) {
     pk.n_shuffles = shuffles->n_shuffles;
@@ -736,14 +747,15 @@ struct h2mi_prover_s {
   }
   const DeviceVec& lookup_table(uint32_t l) const { return pk->lookup_exprs ? *lk[l].table : *pk->fixed_values[pk->cs.lookups[l].table_fixed]; }
   // one side of lookup l compressed with theta, on the rows (coset = false) or on the extended coset
-  void compress(const h2mi_gate_program& prog, bool coset, DeviceVec& out, const Fr* th = nullptr) const {
+  // (`at`: the element of `out` the vector starts at — the input sets of a logUp lookup lie behind one another)
+  void compress(const h2mi_gate_program& prog, bool coset, DeviceVec& out, const Fr* th = nullptr, size_t at = 0) const {
     const h2mi_constraint_system& cs = pk->cs;
     const void *adv[H2MI_MAX_ADVICE], *fix[H2MI_MAX_FIXED];
     for (uint32_t j = 0; j < cs.n_advice; j++) adv[j] = coset ? advice[j].coset->p : advice[j].value->p;
     for (uint32_t j = 0; j < cs.n_fixed; j++) fix[j] = coset ? pk->fixed_cosets[j]->p : pk->fixed_values[j]->p;
     const void* inst = cs.n_instance ? (coset ? instance_coset->p : instance->p) : nullptr;
     check(h2mi_plonk_expr_compress_ch_dev(adv, cs.n_advice, fix, cs.n_fixed, inst, &prog, challenge_limbs(), pk->phases.n_challenges, cs.k,
-                                          coset ? pk->domain.extended_k() : cs.k, (th ? *th : theta).l, out.p, nullptr),
+                                          coset ? pk->domain.extended_k() : cs.k, (th ? *th : theta).l, (char*)out.p + at * 32, nullptr),
           "expr_compress");
   }
   const uint64_t* challenge_limbs() const { return pk->phases.n_challenges ? (const uint64_t*)challenges.data() : nullptr; }
@@ -841,9 +853,10 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
   }
   for (uint32_t l = 0; l < cs.n_lookups; l++) {
     if (pk->lookup_exprs) {
-      Dev* rows[2] = {&p.lk[l].input, &p.lk[l].table};
-      for (Dev* d : rows) *d = vec(n);
-      p.lk[l].in_coset = vec(ext);
+      const size_t sets = pk->lookup_slices.sets[l];  // a logUp lookup's input sets, contiguous: one but for a key of h2mi_prover_keygen_logup
+      p.lk[l].input = vec(sets * n);
+      p.lk[l].table = vec(n);
+      p.lk[l].in_coset = vec(sets * ext);
       p.lk[l].tab_coset = vec(ext);
       Table& t = p.lk[l].sorted;
       t.sorted = vec(pk->u);
@@ -983,11 +996,12 @@ void phase_lookups(h2mi_prover_s& p, const uint64_t* theta, uint64_t* points_out
     PatchList pl;
     std::vector<const void*> cols;
     for (uint32_t l = 0; l < L; l++) {
-      p.compress(pk.lookup_slices.input[l], false, *p.lk[l].input);
+      const uint32_t sets = pk.lookup_slices.sets[l];
+      for (uint32_t j = 0; j < sets; j++) p.compress(pk.lookup_slices.input[l][j], false, *p.lk[l].input, nullptr, (size_t)j * pk.n);
       p.compress(pk.lookup_slices.table[l], false, *p.lk[l].table);
       DeviceVec& mult = *p.lk[l].a.value;
       uint64_t missing = 0;
-      check(h2mi_plonk_logup_multiplicity_dev(p.lk[l].input->p, p.lk[l].table->p, cs.k, u, mult.p, &missing, nullptr), "logup_multiplicity");
+      check(h2mi_plonk_logup_multiplicity_sets_dev(p.lk[l].input->p, sets, p.lk[l].table->p, cs.k, u, mult.p, &missing, nullptr), "logup_multiplicity");
       if (missing) throw Error(H2MI_EUNSAT, "lookup input not in the table (ConstraintSystemFailure)");
       for (uint32_t r = 0; r <= bf; r++) pl.add(mult, u + r, mb[(size_t)(bf + 1) * l + r]);
       cols.push_back(p.col(mult));
@@ -1010,7 +1024,7 @@ void phase_lookups(h2mi_prover_s& p, const uint64_t* theta, uint64_t* points_out
       const h2mi_lookup& d = cs.lookups[l];
       if (pk.lookup_exprs) {
         // both sides compressed on all 2^k rows; the table's usable rows sorted here, inside the proof
-        p.compress(pk.lookup_slices.input[l], false, *p.lk[l].input);
+        p.compress(pk.lookup_slices.input[l][0], false, *p.lk[l].input);
         p.compress(pk.lookup_slices.table[l], false, *p.lk[l].table);
         Table& ts = p.lk[l].sorted;
         check(h2mi_fr_sort_unique_dev(p.lk[l].table->p, u, ts.sorted->p, ts.sorted_mont->p, ts.mult->p, &ts.n_unique, nullptr), "sort_unique");
@@ -1078,9 +1092,15 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
     check(h2mi_plonk_copy_check_dev(vals, m, pk.moved_cells_dev->p, (uint32_t)(pk.moved_cells.size() / 4), report, nullptr), "copy_check");
     if (report[0]) out.push_back({H2MI_CHECK_COPY, pk.moved_cells[4 * (size_t)report[1]], pk.moved_cells[4 * (size_t)report[1] + 1], report[0]});
   }
+  // one input column against a table's sorted distinct values -> the lookup's entry grows by the absent rows and keeps the smallest
+  auto member = [&](const void* input, const Table& t, uint32_t& absent, uint32_t& first_row) {
+    uint32_t report[2];
+    check(h2mi_plonk_lookup_member_dev(input, t.sorted->p, t.n_unique, u, report, nullptr), "lookup_member");
+    absent += report[0];
+    first_row = std::min(first_row, report[1]);
+  };
   for (uint32_t l = 0; l < L; l++) {
-    const void* input;
-    const Table* t;
+    uint32_t absent = 0, first_row = 0xffffffffu;
     if (pk.lookup_exprs) {  // what the lookups phase does with the transcript's theta, on scratch of this call's own
       if (!p.check_in) {
         p.check_in = vec(n);
@@ -1091,26 +1111,25 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
       }
       Fr th;
       std::memcpy(th.l, theta, 32);
-      p.compress(pk.lookup_slices.input[l], false, *p.check_in, &th);
       p.compress(pk.lookup_slices.table[l], false, *p.check_tab, &th);
       Table& ts = p.check_sorted;
       check(h2mi_fr_sort_unique_dev(p.check_tab->p, u, ts.sorted->p, ts.sorted_mont->p, ts.mult->p, &ts.n_unique, nullptr), "sort_unique");
-      input = p.check_in->p;
-      t = &ts;
+      // every input set of a merged logUp lookup against the one sorted table: the entry counts the absent (row, set) pairs
+      for (uint32_t j = 0; j < pk.lookup_slices.sets[l]; j++) {
+        p.compress(pk.lookup_slices.input[l][j], false, *p.check_in, &th);
+        member(p.check_in->p, ts, absent, first_row);
+      }
     } else {
       const h2mi_lookup& d = cs.lookups[l];
+      const void* input = p.advice[d.input.index].value->p;
       if (d.selector_fixed >= 0) {
         if (!p.check_in) p.check_in = vec(n);
-        check(h2mi_fr_mul_dev(pk.fixed_values[d.selector_fixed]->p, p.advice[d.input.index].value->p, n, p.check_in->p, nullptr), "lookup input");
+        check(h2mi_fr_mul_dev(pk.fixed_values[d.selector_fixed]->p, input, n, p.check_in->p, nullptr), "lookup input");
         input = p.check_in->p;
-      } else {
-        input = p.advice[d.input.index].value->p;
       }
-      t = &pk.tables[l];
+      member(input, pk.tables[l], absent, first_row);
     }
-    uint32_t report[2];
-    check(h2mi_plonk_lookup_member_dev(input, t->sorted->p, t->n_unique, u, report, nullptr), "lookup_member");
-    if (report[0]) out.push_back({H2MI_CHECK_LOOKUP, l, report[1], report[0]});
+    if (absent) out.push_back({H2MI_CHECK_LOOKUP, l, first_row, absent});
   }
   for (uint32_t i = 0; i < pk.n_shuffles; i++) {  // both sides compressed and sorted; a row fails when its value is rarer on the other side
     if (!p.check_in) p.check_in = vec(n);
@@ -1174,7 +1193,8 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
     PatchList pl;
     for (uint32_t l = 0; l < L; l++) {
       DeviceVec& phi = *p.lk[l].z.value;
-      check(h2mi_plonk_logup_sum_dev(p.lk[l].input->p, p.lk[l].table->p, p.lk[l].a.value->p, cs.k, u, beta.l, phi.p, nullptr), "logup_sum");
+      check(h2mi_plonk_logup_sum_sets_dev(p.lk[l].input->p, pk.lookup_slices.sets[l], p.lk[l].table->p, p.lk[l].a.value->p, cs.k, u, beta.l, phi.p, nullptr),
+            "logup_sum");
       for (uint32_t r = 0; r < bf; r++) pl.add(phi, u + 1 + r, pb[(size_t)bf * l + r]);
     }
     pl.flush();
@@ -1272,7 +1292,7 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
 // ---- phase 4: the quotient (plonk/evaluation.rs evaluate_h + vanishing division), its pieces committed ---------------------------
 // every extended-coset vector of one circuit as the interpreting quotient kernels take them: the columns a program may query through
 // one pointer table, the permutation argument, the lookups (given as expressions: compressed on the extended coset here)
-void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_cosets& sc) {
+void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_cosets& sc, h2mi_logup_cosets& lg) {
   const h2mi_pk_s& pk = *p.pk;
   const h2mi_constraint_system& cs = pk.cs;
   const uint32_t L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
@@ -1289,12 +1309,13 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_coset
   }
   for (uint32_t s = 0; s < n_sets; s++) ec.perm_z[s] = p.z[s].coset->p;
   ec.n_lookups = L | (pk.logup ? H2MI_LOOKUPS_LOGUP : 0u);
+  for (uint32_t l = 0; l < H2MI_FLEX_MAX_LOOKUPS; l++) lg.n_inputs[l] = l < L && pk.lookup_exprs ? pk.lookup_slices.sets[l] : 1u;
   for (uint32_t l = 0; l < L; l++) {
     const h2mi_lookup& lk = cs.lookups[l];
     if (pk.lookup_exprs) {
       // compressed on the extended coset itself: a product of columns is no polynomial of degree < n, so transforming the
       // compressed rows would give another function
-      p.compress(pk.lookup_slices.input[l], true, *p.lk[l].in_coset);
+      for (uint32_t j = 0; j < pk.lookup_slices.sets[l]; j++) p.compress(pk.lookup_slices.input[l][j], true, *p.lk[l].in_coset, nullptr, (size_t)j * pk.ext);
       p.compress(pk.lookup_slices.table[l], true, *p.lk[l].tab_coset);
       ec.lookup_input[l] = p.lk[l].in_coset->p;
       ec.lookup_table[l] = p.lk[l].tab_coset->p;
@@ -1355,9 +1376,10 @@ void phase_quotient(const Circuits& all, const Fr& y, uint64_t* points_out) {
     // shape through the equivalent program keygen built for the witness check, which computes the same field elements
     std::vector<h2mi_expr_cosets> ec(all.size());
     std::vector<h2mi_shuffle_cosets> sc(all.size());
-    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i], sc[i]);
+    h2mi_logup_cosets lg;  // the key's: the same for every member
+    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i], sc[i], lg);
     const std::vector<Fr>& t_inv = d.t_inv();
-    check(h2mi_plonk_evaluate_h_expr_batch_sh_dev(ec.data(), pk.n_shuffles ? sc.data() : nullptr, (uint32_t)ec.size(), &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
+    check(h2mi_plonk_evaluate_h_expr_batch_lg_dev(ec.data(), pk.n_shuffles ? sc.data() : nullptr, &lg, (uint32_t)ec.size(), &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
                                                   d.extended_k(), cs.blinding_factors, p.beta.l, p.gamma.l, y.l, pk.delta.l, d.get_g_coset().l,
                                                   d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
@@ -1401,8 +1423,9 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
     // gates given as a program: the interpreting kernel reads any column of the proof through one pointer table
     h2mi_expr_cosets ec;
     h2mi_shuffle_cosets sc;
-    fill_expr_cosets(p, ec, sc);
-    check(h2mi_plonk_evaluate_h_expr_sh_dev(&ec, pk.n_shuffles ? &sc : nullptr, &pk.gate_program, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
+    h2mi_logup_cosets lg;
+    fill_expr_cosets(p, ec, sc, lg);
+    check(h2mi_plonk_evaluate_h_expr_lg_dev(&ec, pk.n_shuffles ? &sc : nullptr, &lg, &pk.gate_program, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
                                             d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l,
                                             (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
@@ -1933,13 +1956,30 @@ int h2mi_shuffle_phases_check(const h2mi_constraint_system* cs, const h2mi_shuff
 int h2mi_prover_keygen_shuffles(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                                 const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles, uint64_t g_lagrange_handle,
                                 const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
+  return h2mi_prover_keygen_logup(cs, gates, lookups, nullptr, phases, shuffles, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
+}
+
+int h2mi_logup_inputs_check(const h2mi_constraint_system* cs, const h2mi_lookup_program* lookups, const h2mi_logup_inputs* inputs,
+                            const h2mi_advice_phases* phases, uint32_t* degree_out) {
+  if (!cs || !lookups) return H2MI_EINVAL;
+  if (phases && phases->n_challenges > H2MI_MAX_CHALLENGES) return H2MI_EINVAL;
+  return check_lookup_program(*cs, lookups, degree_out, nullptr, phases ? phases->n_challenges : 0, inputs);
+}
+
+int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
+                             const h2mi_logup_inputs* inputs, const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles,
+                             uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags,
+                             h2mi_pk_t* pk_out) {
   if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)(H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP)) ||
       ((flags & H2MI_KEYGEN_LOGUP) && !lookups))
     return H2MI_EINVAL;
   *pk_out = nullptr;
+  if (inputs && !lookups) return H2MI_EINVAL;
+  for (uint32_t l = 0; inputs && l < lookups->n_lookups && l < H2MI_MAX_LOOKUPS; l++)  // several sets are a logUp key's
+    if (inputs->n_inputs[l] != 1 && !(flags & H2MI_KEYGEN_LOGUP)) return H2MI_EINVAL;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;
   return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, phases, g_lagrange_handle, fixed, copies, n_copies, flags, shuffles);
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, phases, g_lagrange_handle, fixed, copies, n_copies, flags, shuffles, inputs);
     std::lock_guard<std::mutex> lk(g_reg_mu);
     g_live_pks.insert(pk.get());
     *pk_out = pk.release();

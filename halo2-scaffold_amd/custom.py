@@ -31,6 +31,9 @@ Shuffles [RECALL halo2_proofs, PSE line, plonk/shuffle.rs — restated from memo
 `meta.shuffle(name, |meta| vec![(input, shuffle), ..])` states that the two tuples take the same multiset of values over the usable
 rows; required degree 2 + max(1, input degrees, shuffle degrees).  `shuffle_program()` compiles them to an h2mi_shuffle_program and
 `Keys` goes through h2mi_prover_keygen_shuffles — only for a circuit that has shuffles: every other circuit takes the calls it took.
+Merged lookups [RECALL the `mv-lookup` line's merging of lookups over one table — restated from memory and pinned to DESIGN.md 4.5 and
+tests/logup_sets_cases.py]: `merge_lookups(max_degree=None)` is an explicit opt-in that turns the lookups sharing a table into ONE logUp
+argument of several input sets (h2mi_logup_inputs); `Keys(..., logup=True)` then goes through h2mi_prover_keygen_logup.
 `mock` is MockProver::run(..).assert_satisfied() on the host, row by row in Python integers; `check` asks the same question of the
 device, at the sizes the prover runs at (h2mi_prover_check: gates, copy constraints and lookups on the columns of a proof in flight).
 """
@@ -127,6 +130,10 @@ class Expression:
 
     def clone(self):
         return self
+
+    def key(self):
+        """the expression's structure as nested tuples: two expressions are structurally equal when their keys are"""
+        return tuple(e.key() if isinstance(e, Expression) else e for e in self.node)
 
     def resolve(self, first_selector_column: int) -> "Expression":
         """the expression keygen sees: every selector replaced by the query of its fixed column"""
@@ -225,6 +232,7 @@ class ConstraintSystem:
         self.lookup_names, self._lookups = [], []   # per lookup [(input, table)] expressions, selectors unresolved
         self.shuffle_names, self._shuffles = [], []  # per shuffle [(input, shuffle)] expressions, selectors unresolved
         self.advice_phase, self.challenge_phase = [], []  # per advice column its phase; per challenge the phase it is usable after
+        self._merged = None  # merge_lookups(): per lookup ARGUMENT the indices of the declared lookups it proves; None: one each
 
     # ---- columns -----------------------------------------------------------------------------------------------------
     def advice_column(self) -> Column:
@@ -301,9 +309,49 @@ class ConstraintSystem:
         assert pairs, "a lookup needs at least one (input, table) pair"
         self.lookup_names.append(name)
         self._lookups.append(pairs)
+        self._merged = None  # a merge made before this lookup does not know of it: merge_lookups() is called again
         return len(self._lookups) - 1
 
     lookup_any = lookup  # any expression on the table side: advice columns, rotations
+
+    def merge_lookups(self, max_degree: int = None):
+        """Opt in to ONE logUp argument per group of lookups over the same table (several input sets, h2mi_logup_inputs; a key of it
+        needs Keys(..., logup=True)).  Lookups whose TABLE expression lists are structurally equal are grouped in declaration order; a
+        group's inputs are then chunked greedily, in that order, so that every argument's required degree 2 + sum_j max(1, deg A_j) +
+        max(1, deg S) stays within the budget [RECALL the chunking of lookups by degree in the mv-lookup line of halo2_proofs; restated
+        from memory like the argument].  max_degree None: the largest degree that keeps the unmerged system's extended domain, 2^ceil(
+        log2(degree() - 1)) + 1, at most 9 — the extended domain is what a degree costs, so a degree-4 system merges pairs for
+        free.  Declaring another lookup afterwards undoes the merge (call it again); degree(), lookup_program(), logup_inputs() and abi() follow the merged
+        system, mock and the declared lookups do not change.  -> the arguments as lists of lookup indices"""
+        self._merged = None
+        if max_degree is None:
+            max_degree = min(9, (1 << (self.degree() - 2).bit_length()) + 1)
+        assert max_degree <= 9, "the prover takes degrees up to 9"
+        groups = {}  # table key -> the lookups over it; dicts keep declaration order
+        for l, pairs in enumerate(self._lookups):
+            groups.setdefault(tuple(t.key() for _, t in pairs), []).append(l)
+        deg_in = lambda l: max([1] + [a.degree() for a, _ in self._lookups[l]])
+        chunks = []
+        for members in groups.values():
+            tab = max([1] + [t.degree() for _, t in self._lookups[members[0]]])
+            cur = []
+            for l in members:
+                if cur and (len(cur) == engine.MAX_LOGUP_INPUTS or 2 + tab + sum(deg_in(m) for m in cur) + deg_in(l) > max_degree):
+                    chunks.append(cur)
+                    cur = []
+                cur.append(l)
+            chunks.append(cur)
+        self._merged = sorted(chunks)  # arguments in the order of their first lookup
+        return self._merged
+
+    @property
+    def lookup_arguments(self):
+        """per lookup argument the indices of the declared lookups it proves"""
+        return self._merged if self._merged is not None else [[l] for l in range(len(self._lookups))]
+
+    @property
+    def argument_names(self):
+        return [" + ".join(self.lookup_names[l] for l in arg) for arg in self.lookup_arguments]
 
     def shuffle(self, name: str, shuffle_map) -> int:
         """meta.shuffle: shuffle_map(meta) -> [(input Expression, shuffle Expression)]; the queries it makes enter the query lists in
@@ -345,7 +393,9 @@ class ConstraintSystem:
         return [[(a.resolve(self.n_user_fixed), s.resolve(self.n_user_fixed)) for a, s in pairs] for pairs in self._shuffles]
 
     def degree(self) -> int:
-        lookups = [max(4, 2 + max([1] + [a.degree() for a, _ in pairs]) + max([1] + [t.degree() for _, t in pairs])) for pairs in self._lookups]
+        # per argument; merged: 2 + sum over its input sets + the table, which with one set is the lookup's own rule
+        lookups = [max(4, 2 + sum(max([1] + [a.degree() for a, _ in self._lookups[l]]) for l in arg) +
+                       max([1] + [t.degree() for _, t in self._lookups[arg[0]]])) for arg in self.lookup_arguments]
         shuffles = [2 + max([1] + [a.degree() for a, _ in pairs] + [s.degree() for _, s in pairs]) for pairs in self._shuffles]
         return max([3] + [p.degree() for p in self._polys] + lookups + shuffles)
 
@@ -364,14 +414,22 @@ class ConstraintSystem:
         return engine.GateProgram.build(*self.program())
 
     def lookup_program(self):
-        """the lookups -> engine.LookupProgram (per lookup its input polynomials, then its table polynomials), None without lookups"""
+        """the lookups -> engine.LookupProgram (per lookup argument its input polynomials, set by set, then its table polynomials), None
+        without lookups"""
         if not self._lookups:
             return None
         constants, ops = {}, []
-        for pairs in self.lookups:
-            for e in [a for a, _ in pairs] + [t for _, t in pairs]:
+        resolved = self.lookups
+        for arg in self.lookup_arguments:
+            for e in [a for l in arg for a, _ in resolved[l]] + [t for _, t in resolved[arg[0]]]:
                 ops += e.program(constants)[0]
-        return engine.LookupProgram.build([len(pairs) for pairs in self._lookups], ops, sorted(constants, key=constants.get))
+        return engine.LookupProgram.build([len(self._lookups[arg[0]]) for arg in self.lookup_arguments], ops, sorted(constants, key=constants.get))
+
+    def logup_inputs(self):
+        """-> engine.LogupInputs after merge_lookups(), None before (the keygen calls without it)"""
+        if self._merged is None:
+            return None
+        return engine.LogupInputs.build([len(arg) for arg in self._merged])
 
     def shuffle_program(self):
         """the shuffles -> engine.ShuffleProgram (per shuffle its input polynomials, then its shuffle-side polynomials), None without"""
@@ -395,7 +453,7 @@ class ConstraintSystem:
 
     def abi(self, k: int) -> engine.ConstraintSystem:
         abi = self._abi(k)
-        abi.n_lookups = len(self._lookups)  # described by lookup_program(), not by the struct's single-expression entries
+        abi.n_lookups = len(self.lookup_arguments)  # described by lookup_program(), not by the struct's single-expression entries
         return abi
 
     def _abi(self, k: int) -> engine.ConstraintSystem:
@@ -494,11 +552,14 @@ class Keys:
     logup=True [the `mv-lookup` feature of the Scroll and ezkl lines of halo2_proofs, after Haboeck — restated from memory and pinned to
     DESIGN.md 4.5 and tests/logup_cases.py, not to a crate]: every lookup of the key is proven with a multiplicity column and a running
     sum (H2MI_KEYGEN_LOGUP) in place of the permuted columns and the grand product; needs a circuit with lookups.  `create_proof` and
-    `prove_many` follow the key; `mock` and `check` test membership and do not depend on it."""
+    `prove_many` follow the key; `mock` and `check` test membership and do not depend on it.  A constraint system after
+    merge_lookups() goes through h2mi_prover_keygen_logup and needs logup=True."""
 
     def __init__(self, params: ParamsKZG, cs: ConstraintSystem, asg: Assignment, logup: bool = False):
         self.cs = cs
         self.logup = bool(logup)
+        if not logup and any(len(arg) > 1 for arg in cs.lookup_arguments):
+            raise ValueError("merge_lookups() merged lookups over one table: only a logUp key proves them, Keys(..., logup=True)")
         self.params = params  # prove_many's default SRS
         k = params.k
         self.domain = d = EvaluationDomain(cs.degree(), k)
@@ -506,7 +567,7 @@ class Keys:
         index = {col: j for j, col in enumerate(cs.perm_columns)}
         copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
         self.keys = engine.Keys(cs.abi(k), params, list(asg.fixed), copies, gates=cs.gate_program(), lookups=cs.lookup_program(),
-                                phases=cs.phases(), shuffles=cs.shuffle_program(), logup=logup)
+                                phases=cs.phases(), shuffles=cs.shuffle_program(), logup=logup, logup_inputs=cs.logup_inputs() if logup else None)
         self.fixed_commitments, self.permutation_commitments = self.keys.fixed_commitments, self.keys.permutation_commitments
         nf, m = cs.n_fixed, len(cs.perm_columns)
         self.fixed_values, self.fixed_polys, self.fixed_cosets = (self.keys.views(kd, nf) for kd in (engine.PKBUF_FIXED, engine.PKBUF_FIXED_POLY, engine.PKBUF_FIXED_COSET))
@@ -611,7 +672,7 @@ def check(params: ParamsKZG, keys: Keys, asg, seed: int = 1, ws: Workspace = Non
         elif f.kind == engine.CHECK_SHUFFLE:
             msg = f"shuffle {cs.shuffle_names[f.index]!r} not satisfied at row {f.row} ({f.count} rows whose input is rarer on the shuffle side)"
         else:
-            msg = f"lookup {cs.lookup_names[f.index]!r} not satisfied at row {f.row} ({f.count} rows)"
+            msg = f"lookup {cs.argument_names[f.index]!r} not satisfied at row {f.row} ({f.count} rows)"
         e = ValueError(msg)
         e.failures = failures
         raise e

@@ -25,6 +25,7 @@ KEYGEN_LOGUP = 2  # H2MI_KEYGEN_LOGUP: the key's program lookups are logUp argum
 EUNSAT = -7
 MAX_GATES, MAX_PERM, MAX_LOOKUPS, MAX_QUERIES = 32, 64, 8, 192  # H2MI_MAX_* (include/h2mi_prover.h)
 MAX_SHUFFLES = 8  # H2MI_MAX_SHUFFLES (include/h2mi.h)
+MAX_LOGUP_INPUTS = 6  # H2MI_MAX_LOGUP_INPUTS (include/h2mi.h)
 MAX_ADVICE, MAX_CHALLENGES, MAX_ADVICE_PHASES = 64, 16, 3
 
 # h2mi_prover_buffer kinds
@@ -132,6 +133,27 @@ class LookupProgram(C.Structure):
         """h2mi_lookup_program_check -> the largest required degree; H2miError(-1) for a program keygen would refuse"""
         degree = C.c_uint32()
         check(lib.h2mi_lookup_program_check(C.byref(cs), C.byref(self), C.byref(degree)), "lookup_program_check")
+        return degree.value
+
+
+class LogupInputs(C.Structure):
+    """h2mi_logup_inputs: per lookup of a logUp key the number of input tuples over its one table; the LookupProgram then holds per
+    lookup its n_inputs x n_pairs input polynomials (set by set), then its n_pairs table polynomials"""
+    _fields_ = [("n_inputs", C.c_uint32 * MAX_LOOKUPS)]
+
+    @classmethod
+    def build(cls, n_inputs) -> "LogupInputs":
+        assert len(n_inputs) <= MAX_LOOKUPS
+        li = cls()
+        for l in range(MAX_LOOKUPS):
+            li.n_inputs[l] = n_inputs[l] if l < len(n_inputs) else 1
+        return li
+
+    def check(self, cs: "ConstraintSystem", lookups: LookupProgram, phases: "AdvicePhases" = None) -> int:
+        """h2mi_logup_inputs_check -> the largest required degree; H2miError(-1) for what keygen would refuse"""
+        degree = C.c_uint32()
+        check(lib.h2mi_logup_inputs_check(C.byref(cs), C.byref(lookups), C.byref(self), C.byref(phases) if phases is not None else None,
+                                          C.byref(degree)), "logup_inputs_check")
         return degree.value
 
 
@@ -293,7 +315,8 @@ class Keys:
     constrain_equal in call order, columns as indices into the permutation argument.  `params` is the WHOLE SRS."""
 
     def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False, gates: GateProgram = None,
-                 lookups: LookupProgram = None, phases: AdvicePhases = None, shuffles: ShuffleProgram = None, logup: bool = False):
+                 lookups: LookupProgram = None, phases: AdvicePhases = None, shuffles: ShuffleProgram = None, logup: bool = False,
+                 logup_inputs: "LogupInputs" = None):
         self.cs = cs
         self.logup = bool(logup)  # H2MI_KEYGEN_LOGUP; the library refuses it without a lookup program
         self.n_shuffles = shuffles.n_shuffles if shuffles is not None else 0
@@ -301,7 +324,11 @@ class Keys:
         cp = np.ascontiguousarray(np.array(copies, dtype=np.uint32).reshape(-1, 4))
         h = C.c_void_p()
         flags = (KEYGEN_VK_ONLY if vk_only else 0) | (KEYGEN_LOGUP if logup else 0)
-        if shuffles is not None:  # shuffle arguments: h2mi_prover_keygen_phases with the shuffles beside it; every other circuit takes the calls below
+        opt = lambda s: C.byref(s) if s is not None else None
+        if logup_inputs is not None:  # several input sets per logUp lookup: h2mi_prover_keygen_shuffles with the counts beside it
+            check(lib.h2mi_prover_keygen_logup(C.byref(cs), C.byref(gates), opt(lookups), C.byref(logup_inputs), opt(phases), opt(shuffles),
+                                               params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
+        elif shuffles is not None:  # shuffle arguments: h2mi_prover_keygen_phases with the shuffles beside it; every other circuit takes the calls below
             check(lib.h2mi_prover_keygen_shuffles(C.byref(cs), C.byref(gates), C.byref(lookups) if lookups is not None else None,
                                                   C.byref(phases) if phases is not None else None, C.byref(shuffles), params.g_lagrange_handle, cells,
                                                   cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")

@@ -186,6 +186,23 @@ def logup_sum(k: int, d_input: DevBuf, d_table: DevBuf, d_m: DevBuf, beta: int, 
            "logup_sum")
 
 
+def logup_multiplicity_sets(k: int, d_inputs: DevBuf, n_inputs: int, d_table: DevBuf, usable_rows: int, d_m: DevBuf) -> int:
+    """h2mi_plonk_logup_multiplicity_sets_dev: d_inputs holds n_inputs consecutive vectors of 2^k elements; d_m[r] = sum over the sets of
+    #{i < usable_rows: A_j[i] = table[r]} on the first usable row r that holds its table value.  Returns the inputs of any set that are
+    not table values."""
+    missing = C.c_uint64()
+    _check(lib.h2mi_plonk_logup_multiplicity_sets_dev(d_inputs.ptr, n_inputs, d_table.ptr, k, usable_rows, d_m.ptr, C.byref(missing), None),
+           "logup_multiplicity_sets")
+    return missing.value
+
+
+def logup_sum_sets(k: int, d_inputs: DevBuf, n_inputs: int, d_table: DevBuf, d_m: DevBuf, beta: int, usable_rows: int, d_phi: DevBuf) -> None:
+    """h2mi_plonk_logup_sum_sets_dev: phi[0] = 0, phi[i+1] = phi[i] + sum_j 1 / (A_j,i + beta) - M_i / (S_i + beta) on rows 0 ..
+    usable_rows of d_phi"""
+    _check(lib.h2mi_plonk_logup_sum_sets_dev(d_inputs.ptr, n_inputs, d_table.ptr, d_m.ptr, k, usable_rows, F.fr_to_mont_limbs(beta).ctypes.data,
+                                             d_phi.ptr, None), "logup_sum_sets")
+
+
 class _RangeCosets(C.Structure):
     _fields_ = [("a", C.c_void_p), ("lookup_advice", C.c_void_p), ("lookup_selector", C.c_void_p), ("q", C.c_void_p), ("table", C.c_void_p),
                 ("perm_value", C.c_void_p * 4), ("perm_sigma", C.c_void_p * 4), ("perm_z", C.c_void_p * 4), ("lookup_permuted_input", C.c_void_p),

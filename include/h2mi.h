@@ -360,7 +360,7 @@ int h2mi_plonk_shuffle_product_dev(const void* d_input, const void* d_shuffle, u
                                    h2mi_stream_t stream);
 /* ---- logUp: the logarithmic-derivative lookup argument [Haboeck, "Multivariate lookups based on logarithmic derivatives"; the
  * `mv-lookup` feature of the Scroll and ezkl lines of halo2_proofs — restated from memory like the shuffle, pinned to DESIGN.md 4.5 and
- * tests/logup_cases.py and not to a crate].  One input tuple per lookup; d_input / d_table are the two sides compressed with theta on the
+ * tests/logup_cases.py and not to a crate].  One input tuple per lookup here (several: the _sets calls below); d_input / d_table are the two sides compressed with theta on the
  * 2^k rows (h2mi_plonk_expr_compress_dev at domain_k = k), Montgomery.
  * h2mi_fr_sort_unique_first_dev is h2mi_fr_sort_unique_dev with one more output: d_first[r] (u32 x count) = the lowest position of
  * d_in that holds distinct value r (the sort is stable over an index permutation).
@@ -381,6 +381,19 @@ int h2mi_plonk_logup_multiplicity_dev(const void* d_input, const void* d_table, 
  * meaningless. */
 int h2mi_plonk_logup_sum_dev(const void* d_input, const void* d_table, const void* d_m, uint32_t k, uint32_t usable_rows, const uint64_t beta[4],
                              void* d_phi, h2mi_stream_t stream);
+/* Several input sets over ONE table (the merged form): d_inputs points at n_inputs (1 .. H2MI_MAX_LOGUP_INPUTS)
+ * consecutive vectors of 2^k elements, set j at element j 2^k, each compressed with theta.
+ *   M[r] = sum_j #{i < usable_rows : A_j[i] = S[r]} on the lowest usable row r that holds its table value, 0 on the other usable rows:
+ *          ONE sort of the table, every set ranked into the same histogram in one launch; not_in_table_out counts the inputs of ANY
+ *          set that are no table value.
+ *   phi[i+1] = phi[i] + sum_j 1 / (A_j,i + beta) - M_i / (S_i + beta): the row's fraction N / D by the recurrence (N, D) = (-M, S + beta),
+ *          then per input N <- N (A_j + beta) + D, D <- D (A_j + beta); the inversion chain and the additive scan are the one-set call's.
+ * The two calls above are these with n_inputs == 1.  H2MI_EINVAL: n_inputs == 0 or above the maximum. */
+#define H2MI_MAX_LOGUP_INPUTS 6
+int h2mi_plonk_logup_multiplicity_sets_dev(const void* d_inputs, uint32_t n_inputs, const void* d_table, uint32_t k, uint32_t usable_rows, void* d_m,
+                                           uint64_t* not_in_table_out, h2mi_stream_t stream);
+int h2mi_plonk_logup_sum_sets_dev(const void* d_inputs, uint32_t n_inputs, const void* d_table, const void* d_m, uint32_t k, uint32_t usable_rows,
+                                  const uint64_t beta[4], void* d_phi, h2mi_stream_t stream);
 /* evaluate_h + vanishing division for the halo2-lib constraint systems [halo2-base shapes restated from memory]: gate
  * q (a + a(wX) a(w^2 X) - a(w^3 X)), permutation argument over n_perm <= 4 columns in chunks of chunk_len (= cs.degree()
  * - 2 = 1 .. 3), and — has_lookup (the Range builder, extended domain 4n) — one lookup in `table` of either
@@ -549,6 +562,26 @@ int h2mi_plonk_evaluate_h_expr_sh_dev(const h2mi_expr_cosets* cosets, const h2mi
 int h2mi_plonk_evaluate_h_expr_batch_sh_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, uint32_t n_circuits,
                                             const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k,
                                             uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
+                                            const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
+                                            const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream);
+/* The two calls above for logUp lookups with SEVERAL INPUT SETS over one table [restated from memory, pinned to DESIGN.md 4.5 and
+ * tests/logup_sets_cases.py].  `logup` states per lookup the number K of input tuples, 1 .. H2MI_MAX_LOGUP_INPUTS; lookup_input[l] then
+ * points at K CONSECUTIVE extended-coset vectors (set j at element j 2^extended_k), each compressed with theta, and the lookup's third
+ * term is l_active ((phi(wX) - phi(X)) D - N) with (N, D) from the recurrence (N, D) = (-M, S + beta), then per input N <- N (A_j + beta)
+ * + D, D <- D (A_j + beta).  h2mi_expr_cosets keeps its layout and the meaning of every field.  `logup` is one struct for the call (the
+ * batch call: for every circuit) or NULL; NULL or all ones is the call above word for word.  Counts beyond n_lookups are not read.
+ * H2MI_EINVAL: a count of 0 or above the maximum; a count other than 1 without H2MI_LOOKUPS_LOGUP. */
+typedef struct {
+  uint32_t n_inputs[H2MI_FLEX_MAX_LOOKUPS];
+} h2mi_logup_cosets;
+int h2mi_plonk_evaluate_h_expr_lg_dev(const h2mi_expr_cosets* cosets, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                      const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
+                                      uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
+                                      const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
+                                      void* d_h_out, h2mi_stream_t stream);
+int h2mi_plonk_evaluate_h_expr_batch_lg_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                            uint32_t n_circuits, const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges,
+                                            uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
                                             const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
                                             const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream);
 

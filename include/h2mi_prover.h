@@ -140,7 +140,7 @@ typedef struct h2mi_prover_s* h2mi_prover_t; /* the buffers, streams and phase s
 /* H2MI_KEYGEN_LOGUP: every program lookup of the key is proven with the logarithmic-derivative argument ("logUp": Haboeck; the
  * `mv-lookup` feature of the Scroll and ezkl lines of halo2_proofs) in place of the permuted columns and the grand product.  Like the
  * shuffle it is RESTATED FROM MEMORY: DESIGN.md 4.5 and tests/logup_cases.py are the pin, not a crate.  Selection is per key — all of
- * its lookups or none; one input tuple per lookup (the crate's merging of several input sets over one table is not modelled).
+ * its lookups or none.  A lookup of the key may hold several input tuples over its one table (h2mi_logup_inputs, below).
  * Accepted by h2mi_prover_keygen_exprs / _phases / _shuffles with lookups != NULL only (H2MI_EINVAL otherwise, and from
  * h2mi_prover_keygen / _keygen_gates always); h2mi_lookup_program, its check, the required degree, blinding_factors and the query lists
  * are what they are without it.  Per lookup, with A and S the two sides compressed with theta and u the usable rows:
@@ -248,6 +248,35 @@ int h2mi_shuffle_phases_check(const h2mi_constraint_system* cs, const h2mi_shuff
 int h2mi_prover_keygen_shuffles(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                                 const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles, uint64_t g_lagrange_handle,
                                 const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
+/* Several input sets over one table in a logUp lookup [the merging of lookups that share a table, restated from memory like the
+ * argument itself: DESIGN.md 4.5 and tests/logup_sets_cases.py are the pin, not a crate].  Lookup l has K = n_inputs[l] input tuples A_1
+ * .. A_K and one table tuple S, all of n_pairs[l] components; with an h2mi_logup_inputs, lookups->exprs holds per lookup its n_inputs x
+ * n_pairs input polynomials (set by set), then its n_pairs table polynomials.  Every tuple is compressed with theta on all 2^k rows.
+ *   M[r] = sum_j #{i < u : A_j[i] = S[r]} on the lowest usable row r that holds its table value, 0 on every other usable row; blinding
+ *          rows, stream and offsets as with one set.  An input of ANY set that is no table value: H2MI_EUNSAT from h2mi_prover_lookups.
+ *   phi[0] = 0, phi[i+1] = phi[i] + sum_j 1 / (A_j,i + beta) - M_i / (S_i + beta); phi[u] = 0.
+ *   Quotient, per lookup: l_0 phi, l_last phi, l_active ((phi(wX) - phi(X)) D - N), with a_j = A_j + beta, s = S + beta, D = s prod_j a_j,
+ *          N = s sum_j prod_{m != j} a_m - M prod_j a_j — by the recurrence (N, D) = (-M, s), then per input N <- N a_j + D, D <- D a_j.
+ *   Required degree 2 + sum_j max(1, deg A_j) + max(1, deg S), deg A_j the largest degree among tuple j's components; with cs->degree
+ *          <= 9 that allows H2MI_MAX_LOGUP_INPUTS (6) sets of degree-1 inputs.
+ * A merged lookup is ONE argument: one [M], one [phi], three evaluations and three openings whatever K; counts, evaluation numbers and
+ * buffer kinds are per argument.  Against K unmerged logUp lookups the proof loses (K - 1) x (2 points + 3 scalars); where the merge
+ * raises cs->degree it gains one quotient piece per step.  The prover holds K + 1 compressed row vectors and K + 1 extended-coset vectors per lookup.
+ * h2mi_logup_inputs_check (host only, works without a GPU): the rules of h2mi_lookup_program_check with sum (n_inputs + 1) n_pairs
+ * polynomials and the degree rule above; every count in 1 .. H2MI_MAX_LOGUP_INPUTS; CHALLENGE ops of an index below phases->n_challenges
+ * allowed (phases == NULL: none).  inputs == NULL: one set per lookup.  degree_out (may be NULL): the largest required degree.
+ * h2mi_prover_keygen_logup: h2mi_prover_keygen_shuffles plus `inputs`.  A count above 1 without H2MI_KEYGEN_LOGUP (or without
+ * lookups): H2MI_EINVAL.  inputs == NULL or all ones: the key h2mi_prover_keygen_shuffles makes.  The key copies the struct.
+ * h2mi_prover_check tests the membership of every set: a lookup's entry counts the absent (row, set) pairs and names the smallest row. */
+typedef struct {
+  uint32_t n_inputs[H2MI_MAX_LOOKUPS]; /* 1 .. H2MI_MAX_LOGUP_INPUTS for the lookups->n_lookups lookups; the rest is not read */
+} h2mi_logup_inputs;
+int h2mi_logup_inputs_check(const h2mi_constraint_system* cs, const h2mi_lookup_program* lookups, const h2mi_logup_inputs* inputs,
+                            const h2mi_advice_phases* phases, uint32_t* degree_out);
+int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
+                             const h2mi_logup_inputs* inputs, const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles,
+                             uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags,
+                             h2mi_pk_t* pk_out);
 int h2mi_prover_pk_release(h2mi_pk_t pk); /* H2MI_EINVAL while a prover created against it is alive */
 /* VerifyingKey::{fixed_commitments, permutation.commitments}: affine points (8 limbs each); either pointer may be NULL */
 int h2mi_prover_vk_commitments(h2mi_pk_t pk, uint64_t* fixed_out /* n_fixed x 8 */, uint64_t* permutation_out /* n_perm x 8 */);
