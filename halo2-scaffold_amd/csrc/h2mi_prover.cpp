@@ -627,7 +627,9 @@ void lincomb(const std::vector<const DeviceVec*>& polys, const std::vector<Fr>& 
   }
 }
 void add_head(DeviceVec& poly, const std::vector<Fr>& head, h2mi_stream_t stream = nullptr) {
-  check(h2mi_fr_add_head_dev(poly.p, (const uint64_t*)head.data(), head.size(), stream), "add_head");
+  // the entry takes at most 16 coefficients per call (they travel as kernel arguments): a rotation set of more points goes in slices
+  for (size_t at = 0; at < head.size(); at += 16)
+    check(h2mi_fr_add_head_dev((char*)poly.p + 32 * at, (const uint64_t*)(head.data() + at), std::min<size_t>(16, head.size() - at), stream), "add_head");
 }
 // out = src / prod (X - root); `out` must have been zeroed (the quotient has n - #roots coefficients, the rest stay zero).
 // Two to four roots: ONE round of independent divisions weighted by the partial-fraction coefficients; otherwise a chain through

@@ -43,7 +43,7 @@ def _limbs(values):
 
 # ---- 1. the sort -------------------------------------------------------------------------------------------------------------------
 COUNTS = [1, 2, 3, 26, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4097, (1 << 16) - 6, (1 << 18) + 5]
-KEY_CLASSES = ["all equal", "counting", "top word", "words 3 and 4", "ends of the field", "uniform", "half zeros"]
+KEY_CLASSES = ["all equal", "counting", "top word", "words 3 and 4", "ends of the field", "uniform", "half zeros", "signed range", "shared prefix"]
 
 
 def _keys(cls, c, rng):
@@ -63,6 +63,12 @@ def _keys(cls, c, rng):
         return [rng.choice([0, 1, R - 2, R - 1]) for _ in range(c)]
     if cls == "uniform":
         return [rng.randrange(R) for _ in range(c)]
+    if cls == "signed range":  # {0 .. c/4} and {r - c/4 .. r - 1} with repeats: every byte differs, and the small half ties on any prefix
+        return [rng.randrange(c // 4 + 1) if rng.random() < 0.5 else R - 1 - rng.randrange(max(1, c // 4)) for _ in range(c)]
+    if cls == "shared prefix":  # three top parts over uniform low 20 bytes: more than eight bytes differ, every 8-byte prefix ties
+        tops = [0, 0x1D2C3B4A59687786 << 192, (R >> 160) - 1 << 160]
+        return [rng.choice(tops) + rng.randrange(1 << 160) for _ in range(c)]
+    assert cls == "half zeros"
     return [0 if rng.random() < 0.5 else rng.randrange(R) for _ in range(c)]
 
 
@@ -83,6 +89,47 @@ def test_sort_unique_against_sorted_and_counter(gpu, count, cls):
     assert _ints(canon.to_numpy(shape=(n_unique, 4), nbytes=n_unique * 32)) == want
     assert _ints(smont.to_numpy(shape=(n_unique, 4), nbytes=n_unique * 32)) == [mont(v) for v in want]
     assert mult.to_numpy(dtype=np.uint32, nbytes=n_unique * 4).tolist() == [tally[v] for v in want]
+
+
+RESORT_COUNT = 4097  # two tiles of the radix passes, the second ragged
+
+
+@pytest.mark.parametrize("cls", ["signed range", "shared prefix", "uniform"])
+def test_full_resort_is_reached_and_keeps_the_first_positions(gpu, cls):
+    """keys that tie on the whole prefix are sorted again on every differing byte, from the identity permutation (k_su_iota): the two
+    classes made for that path launch it — hundreds of digits per pass, across tiles — and uniform keys do not.  The re-sort starting
+    from the identity is what keeps h2mi_fr_sort_unique_first_dev's `first` right: per distinct value the LOWEST input position"""
+    from halo2_scaffold_amd.device import DevBuf
+
+    lib, count = gpu.lib, RESORT_COUNT
+    rng = random.Random(count * 131 + KEY_CLASSES.index(cls))
+    keys = _keys(cls, count, rng)
+    mont = lambda v: (v << 256) % R
+    d_in = DevBuf.from_numpy(_limbs([mont(v) for v in keys]))
+    bufs = [DevBuf(count * 32), DevBuf(count * 32), DevBuf(count * 4), DevBuf(count * 4)]
+    n_unique = C.c_uint32()
+    assert lib.h2mi_profile_reset() == 0 and lib.h2mi_profile_filter(b"") == 0 and lib.h2mi_profile_enable(1) == 0
+    try:
+        assert lib.h2mi_fr_sort_unique_first_dev(d_in.ptr, count, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, C.byref(n_unique), None) == 0
+    finally:
+        assert lib.h2mi_profile_enable(0) == 0
+    ms, launched = C.c_double(), C.c_uint64()
+    assert lib.h2mi_profile_query(b"k_su_iota", C.byref(ms), C.byref(launched)) == 0 and lib.h2mi_profile_reset() == 0
+    print(cls, "k_su_iota launches:", launched.value)
+    assert (launched.value == 1) == (cls != "uniform") and launched.value <= 1
+    tally = collections.Counter(keys)
+    lowest = {}
+    for at, v in enumerate(keys):
+        lowest.setdefault(v, at)
+    want = sorted(lowest)
+    if cls != "uniform":
+        assert len(want) > 1000  # hundreds of digits in a pass, spread over both tiles
+    assert n_unique.value == len(want)
+    assert _ints(bufs[0].to_numpy(shape=(len(want), 4), nbytes=len(want) * 32)) == want
+    assert bufs[3].to_numpy(dtype=np.uint32, nbytes=len(want) * 4).tolist() == [lowest[v] for v in want]
+    assert bufs[2].to_numpy(dtype=np.uint32, nbytes=len(want) * 4).tolist() == [tally[v] for v in want]
+    for b in bufs + [d_in]:
+        b.free()
 
 
 def test_sort_unique_refusals(gpu):

@@ -107,6 +107,66 @@ def test_single_process_two_physical_devices(gpu, tmp_path):
     assert r.returncode == 0 and "MULTIDEV_OK 2" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
 
 
+# ---- the arguments given as data under the multi-device mode ------------------------------------------------------------------------
+# The data-given arguments keep their vectors on device 0 (use_device(0)) while every commitment is a sharded MSM: a merged logUp
+# key with shuffles (tests/limit_cases.py args_logup) and three advice phases with sixteen challenges (phases) must give, under
+# h2mi_init_devices, the bytes one device gives.
+_LIMITS_WORKER = r"""
+import json, os, sys
+sys.path.insert(0, {root!r})
+sys.path.insert(0, os.path.join({root!r}, "tests"))
+import torch  # first: one HIP runtime
+import _load_pkg
+h2 = _load_pkg.load()
+NDEV = {ndev}
+assert h2.lib.h2mi_device_count() == 0
+assert h2.lib.h2mi_init_devices(NDEV) == 0 and h2.lib.h2mi_device_count() == NDEV
+from halo2_scaffold_amd import custom
+import limit_cases as cases
+out = {{}}
+for name in ("args_logup", "phases"):
+    cs, witness, k, logup = cases.build(custom, name)
+    params = h2.ParamsKZG.setup(k, 0x5EC2E7 + 0x48324D49)
+    keys = custom.Keys(params, cs, cases.first_assignment(cs, witness), logup=logup)
+    custom.check(params, keys, witness)
+    out[name] = custom.create_proof(params, keys, witness, 33).hex()
+    keys.release()
+    params.release()
+print("LIMITS_PROOFS " + json.dumps(out))
+"""
+
+
+def _limit_proofs(tmp_path, ndev: int) -> dict:
+    import json
+
+    script = tmp_path / ("limits%d.py" % ndev)
+    script.write_text(_LIMITS_WORKER.format(root=ROOT, ndev=ndev))
+    env = dict(os.environ, H2MI_VIRTUAL_DEVICES="1", OMP_NUM_THREADS="1")
+    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=600, env=env)
+    lines = [line for line in r.stdout.splitlines() if line.startswith("LIMITS_PROOFS ")]
+    assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-3000:]
+    return json.loads(lines[0][len("LIMITS_PROOFS "):])
+
+
+def test_data_given_arguments_under_three_virtual_devices(gpu, tmp_path):
+    """args_logup and phases (tests/limit_cases.py): the proofs this process makes on one device, with a fixed seed, against those of a
+    child process under h2mi_init_devices(3) — the same bytes"""
+    from halo2_scaffold_amd import custom
+
+    import limit_cases as cases
+
+    one = {}
+    for name in ("args_logup", "phases"):
+        cs, witness, k, logup = cases.build(custom, name)
+        params = gpu.ParamsKZG.setup(k, 0x5EC2E7 + 0x48324D49)
+        keys = custom.Keys(params, cs, cases.first_assignment(cs, witness), logup=logup)
+        one[name] = custom.create_proof(params, keys, witness, 33).hex()
+        assert len(one[name]) == 2 * cases.proof_length(cs, 1, logup)
+        keys.release()
+        params.release()
+    assert _limit_proofs(tmp_path, 3) == one
+
+
 # ---- the ABI from two host threads (SURVEY.md 8b: "calls may arrive concurrently from rayon worker threads") ---------------------
 # HIP's current device belongs to the HOST THREAD.  Round 3 cached "the device hipSetDevice last selected" process-wide, so a second
 # thread calling after h2mi_init(d != 0) allocated and launched on device 0.  The worker drives the library from two threads at
