@@ -1135,12 +1135,57 @@ static int mulscan(fe* data, size_t n, int reverse, fe* totals, fe* offsets, hip
   return H2MI_OK;
 }
 
+// The grand products' part of the transforms' shared, stream-ordered scratch: num, P (prefix of den), S (suffix of den) of `cap`
+// elements each, the tile totals / offsets of `tiles` each, the inverse of the total.
+struct RatioTmp {
+  fe *num, *P, *S, *totals, *offsets, *inv_total;
+};
+static size_t ratio_tmp_size(size_t cap, uint32_t tiles) { return 3 * cap + 2 * (size_t)tiles + 2; }
+static RatioTmp carve_ratio_tmp(size_t cap, uint32_t tiles) {
+  RatioTmp t;
+  t.num = tmp_base();
+  t.P = t.num + cap;
+  t.S = t.P + cap;
+  t.totals = t.S + cap;
+  t.offsets = t.totals + tiles;
+  t.inv_total = t.offsets + tiles;
+  return t;
+}
+
+// num[i] / P[i] over `total` elements with one inversion: the ratios overwrite num (P and S end as the prefix and suffix products)
+static int ratios(const RatioTmp& t, size_t total, hipStream_t s) {
+  H2_HIP(hipMemcpyAsync(t.S, t.P, total * 32, hipMemcpyDeviceToDevice, s));
+  int rc = mulscan(t.P, total, 0, t.totals, t.offsets, s);
+  if (!rc) rc = mulscan(t.S, total, 1, t.totals, t.offsets, s);
+  if (rc) return rc;
+  H2_LAUNCH("k_fr_inv_one", k_fr_inv_one, 1, 64, 0, s, (const fe*)(t.P + (total - 1)), t.inv_total);
+  H2_LAUNCH("k_perm_ratio", k_perm_ratio, ceil_div_u32(total, 256), 256, 0, s, (const fe*)t.num, (const fe*)t.P, (const fe*)t.S, (const fe*)t.inv_total,
+            total, t.num);
+  return H2MI_OK;
+}
+// ... and their prefix products, which give z
+static int running_product(const RatioTmp& t, size_t total, hipStream_t s) {
+  const int rc = ratios(t, total, s);
+  return rc ? rc : mulscan(t.num, total, 0, t.totals, t.offsets, s);
+}
+
+static bool rows_out_of_range(uint32_t k, uint32_t usable_rows) {
+  return k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k);
+}
+
+static ZOut single_out(void* d_z) {
+  ZOut zo;
+  memset(&zo, 0, sizeof(zo));
+  zo.z[0] = (fe*)d_z;
+  return zo;
+}
+
 int h2mi_plonk_permutation_product_dev(const void* const* d_values, const void* const* d_sigmas, uint32_t m, uint32_t k, uint32_t usable_rows,
                                        const uint64_t beta[4], const uint64_t gamma[4], const uint64_t* beta_delta_pows, const uint64_t omega[4],
                                        const void* d_start_or_null, void* d_z, void* d_last_or_null, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!d_values || !d_sigmas || !beta || !gamma || !beta_delta_pows || !omega || !d_z || m == 0 || m > H2MI_FLEX_MAX_PERM) return H2MI_EINVAL;
-  if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k)) return H2MI_ERANGE;
+  if (rows_out_of_range(k, usable_rows)) return H2MI_ERANGE;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
@@ -1159,28 +1204,14 @@ int h2mi_plonk_permutation_product_dev(const void* const* d_values, const void* 
   PowTab pw;
   int rc = get_powtab(omega, k, s, &pw);
   if (rc) return rc;
-  // scratch (the transforms' shared, stream-ordered buffer): num, P (prefix of den), S (suffix of den), tile
-  // totals / offsets, the inverse of the total
   const uint32_t nblocks = ceil_div_u32(n, MS_TILE);
-  rc = ensure_tmp(3 * n + 2 * (size_t)nblocks + 2, s);
+  rc = ensure_tmp(ratio_tmp_size(n, nblocks), s);
   if (rc) return rc;
-  fe* num = tmp_base();
-  fe* P = num + n;
-  fe* S = P + n;
-  fe* totals = S + n;
-  fe* offsets = totals + nblocks;
-  fe* inv_total = offsets + nblocks;
-  H2_LAUNCH("k_perm_numden", k_perm_numden, ceil_div_u32(n, 256), 256, 0, s, a, n, usable_rows, (const fe*)pw.lo, (const fe*)pw.hi, pw.h, num, P);
-  H2_HIP(hipMemcpyAsync(S, P, n * 32, hipMemcpyDeviceToDevice, s));
-  rc = mulscan(P, n, 0, totals, offsets, s);
-  if (!rc) rc = mulscan(S, n, 1, totals, offsets, s);
+  const RatioTmp t = carve_ratio_tmp(n, nblocks);
+  H2_LAUNCH("k_perm_numden", k_perm_numden, ceil_div_u32(n, 256), 256, 0, s, a, n, usable_rows, (const fe*)pw.lo, (const fe*)pw.hi, pw.h, t.num, t.P);
+  rc = running_product(t, n, s);
   if (rc) return rc;
-  H2_LAUNCH("k_fr_inv_one", k_fr_inv_one, 1, 64, 0, s, (const fe*)(P + (n - 1)), inv_total);
-  // the ratios overwrite num; their prefix products then give z
-  H2_LAUNCH("k_perm_ratio", k_perm_ratio, ceil_div_u32(n, 256), 256, 0, s, (const fe*)num, (const fe*)P, (const fe*)S, (const fe*)inv_total, n, num);
-  rc = mulscan(num, n, 0, totals, offsets, s);
-  if (rc) return rc;
-  H2_LAUNCH("k_perm_write", k_perm_write, ceil_div_u32((uint64_t)usable_rows + 1, 256), 256, 0, s, (const fe*)num, (const fe*)d_start_or_null, usable_rows,
+  H2_LAUNCH("k_perm_write", k_perm_write, ceil_div_u32((uint64_t)usable_rows + 1, 256), 256, 0, s, (const fe*)t.num, (const fe*)d_start_or_null, usable_rows,
             (fe*)d_z, (fe*)d_last_or_null);
   return release_tmp(s);
 }
@@ -1190,7 +1221,7 @@ static int perm_products(const void* const* d_values, const void* const* d_sigma
                          const uint32_t* d_active, uint32_t n_active, void* const* d_z, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!d_values || !d_sigmas || !beta || !gamma || !beta_delta_pows || !omega || !d_z || m == 0 || m > H2MI_FLEX_MAX_PERM || chunk_len == 0) return H2MI_EINVAL;
-  if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k)) return H2MI_ERANGE;
+  if (rows_out_of_range(k, usable_rows)) return H2MI_ERANGE;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
@@ -1231,26 +1262,15 @@ static int perm_products(const void* const* d_values, const void* const* d_sigma
   }
   const size_t total = d_active ? (size_t)n_active : (size_t)sets * usable_rows;  // elements the scans run over
   const uint32_t nblocks = ceil_div_u32(total, MS_TILE);
-  rc = ensure_tmp(3 * total + 2 * (size_t)nblocks + 2, s);
+  rc = ensure_tmp(ratio_tmp_size(total, nblocks), s);
   if (rc) return rc;
-  fe* num = tmp_base();
-  fe* P = num + total;
-  fe* S = P + total;
-  fe* totals = S + total;
-  fe* offsets = totals + nblocks;
-  fe* inv_total = offsets + nblocks;
+  const RatioTmp t = carve_ratio_tmp(total, nblocks);
   H2_LAUNCH("k_perm_numden_sets", k_perm_numden_sets, ceil_div_u32(total, 256), 256, 0, s, a, chunk_len, total, usable_rows, (const fe*)pw.lo, (const fe*)pw.hi,
-            pw.h, d_active, num, P);
-  H2_HIP(hipMemcpyAsync(S, P, total * 32, hipMemcpyDeviceToDevice, s));
-  rc = mulscan(P, total, 0, totals, offsets, s);
-  if (!rc) rc = mulscan(S, total, 1, totals, offsets, s);
+            pw.h, d_active, t.num, t.P);
+  rc = running_product(t, total, s);
   if (rc) return rc;
-  H2_LAUNCH("k_fr_inv_one", k_fr_inv_one, 1, 64, 0, s, (const fe*)(P + (total - 1)), inv_total);
-  H2_LAUNCH("k_perm_ratio", k_perm_ratio, ceil_div_u32(total, 256), 256, 0, s, (const fe*)num, (const fe*)P, (const fe*)S, (const fe*)inv_total, total, num);
-  rc = mulscan(num, total, 0, totals, offsets, s);
-  if (rc) return rc;
-  if (d_active) H2_LAUNCH("k_perm_to_mont256", k_perm_to_mont256, ceil_div_u32(n_active, 256), 256, 0, s, num, n_active);
-  H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, wgrid, 256, 0, s, (const fe*)num, usable_rows, zo, d_active, n_active);
+  if (d_active) H2_LAUNCH("k_perm_to_mont256", k_perm_to_mont256, ceil_div_u32(n_active, 256), 256, 0, s, t.num, n_active);
+  H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, wgrid, 256, 0, s, (const fe*)t.num, usable_rows, zo, d_active, n_active);
   return release_tmp(s);
 }
 
@@ -1272,7 +1292,7 @@ int h2mi_plonk_lookup_product_dev(const void* d_input, const void* d_table, cons
                                   uint32_t usable_rows, const uint64_t beta[4], const uint64_t gamma[4], void* d_z, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!d_input || !d_table || !d_permuted_input || !d_permuted_table || !beta || !gamma || !d_z) return H2MI_EINVAL;
-  if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k)) return H2MI_ERANGE;
+  if (rows_out_of_range(k, usable_rows)) return H2MI_ERANGE;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
@@ -1281,9 +1301,9 @@ int h2mi_plonk_lookup_product_dev(const void* d_input, const void* d_table, cons
   const uint32_t nseg = ceil_div_u32(uu, SCAN_SEG_BINS) + 1;
   const size_t words = 2 * ((size_t)uu + 8) + nseg + 8 + u / 4 + 8;  // flag, pos (+ total), segment sums, active positions
   const uint32_t nblocks_dense = ceil_div_u32(u, MS_TILE);
-  int rc = ensure_tmp(3 * u + 2 * (size_t)nblocks_dense + 2 + (words * 4 + 31) / 32, s);
+  int rc = ensure_tmp(ratio_tmp_size(u, nblocks_dense) + (words * 4 + 31) / 32, s);
   if (rc) return rc;
-  uint32_t* flag = reinterpret_cast<uint32_t*>(tmp_base() + 3 * u + 2 * (size_t)nblocks_dense + 2);
+  uint32_t* flag = reinterpret_cast<uint32_t*>(tmp_base() + ratio_tmp_size(u, nblocks_dense));
   uint32_t* pos = flag + uu + 8;
   uint32_t* segsum = pos + uu + 8;
   uint32_t* active = segsum + nseg + 8;
@@ -1301,43 +1321,28 @@ int h2mi_plonk_lookup_product_dev(const void* d_input, const void* d_table, cons
   }
   const bool sparse = (size_t)n_act * 4 <= u && usable_rows >= 4096;
   const size_t total = sparse ? n_act : u;
-  const uint32_t nblocks = ceil_div_u32(std::max<size_t>(total, 1), MS_TILE);
-  fe* num = tmp_base();
-  fe* P = num + u;
-  fe* S = P + u;
-  fe* totals = S + u;
-  fe* offsets = totals + nblocks_dense;
-  fe* inv_total = offsets + nblocks_dense;
-  ZOut zo;
-  memset(&zo, 0, sizeof(zo));
-  zo.z[0] = (fe*)d_z;
+  const RatioTmp t = carve_ratio_tmp(u, nblocks_dense);  // carved for the dense form; the scans run over total <= u
+  const ZOut zo = single_out(d_z);
   if (sparse && n_act == 0) {  // every ratio is one: z = 1 on rows 0 .. u (an empty position list)
-    H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, dim3(ceil_div_u32((uint64_t)usable_rows + 1, 256), 1), 256, 0, s, (const fe*)num, usable_rows, zo,
+    H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, dim3(ceil_div_u32((uint64_t)usable_rows + 1, 256), 1), 256, 0, s, (const fe*)t.num, usable_rows, zo,
               (const uint32_t*)active, 0u);
     return release_tmp(s);
   }
   if (sparse) {
     H2_LAUNCH("k_lookup_compact", k_lookup_compact, ceil_div_u32(usable_rows, 256), 256, 0, s, (const uint32_t*)flag, (const uint32_t*)pos, usable_rows, active);
     H2_LAUNCH("k_lookup_numden", k_lookup_numden_sparse, ceil_div_u32(n_act, 256), 256, 0, s, in, tab, pin, ptab, host_fe(beta), host_fe(gamma),
-              (const uint32_t*)active, n_act, num, P);
+              (const uint32_t*)active, n_act, t.num, t.P);
   } else {
-    H2_LAUNCH("k_lookup_numden", k_lookup_numden, ceil_div_u32(total, 256), 256, 0, s, in, tab, pin, ptab, host_fe(beta), host_fe(gamma), usable_rows, num, P);
+    H2_LAUNCH("k_lookup_numden", k_lookup_numden, ceil_div_u32(total, 256), 256, 0, s, in, tab, pin, ptab, host_fe(beta), host_fe(gamma), usable_rows, t.num, t.P);
   }
-  (void)nblocks;
-  H2_HIP(hipMemcpyAsync(S, P, total * 32, hipMemcpyDeviceToDevice, s));
-  rc = mulscan(P, total, 0, totals, offsets, s);
-  if (!rc) rc = mulscan(S, total, 1, totals, offsets, s);
-  if (rc) return rc;
-  H2_LAUNCH("k_fr_inv_one", k_fr_inv_one, 1, 64, 0, s, (const fe*)(P + (total - 1)), inv_total);
-  H2_LAUNCH("k_perm_ratio", k_perm_ratio, ceil_div_u32(total, 256), 256, 0, s, (const fe*)num, (const fe*)P, (const fe*)S, (const fe*)inv_total, total, num);
-  rc = mulscan(num, total, 0, totals, offsets, s);
+  rc = running_product(t, total, s);
   if (rc) return rc;
   if (sparse) {
-    H2_LAUNCH("k_perm_to_mont256", k_perm_to_mont256, ceil_div_u32(n_act, 256), 256, 0, s, num, n_act);
-    H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, dim3(ceil_div_u32((uint64_t)usable_rows + 1, 256), 1), 256, 0, s, (const fe*)num, usable_rows, zo,
+    H2_LAUNCH("k_perm_to_mont256", k_perm_to_mont256, ceil_div_u32(n_act, 256), 256, 0, s, t.num, n_act);
+    H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, dim3(ceil_div_u32((uint64_t)usable_rows + 1, 256), 1), 256, 0, s, (const fe*)t.num, usable_rows, zo,
               (const uint32_t*)active, n_act);
   } else {
-    H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, dim3(ceil_div_u32((uint64_t)usable_rows + 1, 256), 1), 256, 0, s, (const fe*)num, usable_rows, zo,
+    H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, dim3(ceil_div_u32((uint64_t)usable_rows + 1, 256), 1), 256, 0, s, (const fe*)t.num, usable_rows, zo,
               (const uint32_t*)nullptr, 0u);
   }
   return release_tmp(s);
@@ -1347,33 +1352,20 @@ int h2mi_plonk_shuffle_product_dev(const void* d_input, const void* d_shuffle, u
                                    h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!d_input || !d_shuffle || !gamma || !d_z) return H2MI_EINVAL;
-  if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k)) return H2MI_ERANGE;
+  if (rows_out_of_range(k, usable_rows)) return H2MI_ERANGE;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
   const size_t u = usable_rows;
   const uint32_t nblocks = ceil_div_u32(u, MS_TILE);
-  int rc = ensure_tmp(3 * u + 2 * (size_t)nblocks + 2, s);
+  int rc = ensure_tmp(ratio_tmp_size(u, nblocks), s);
   if (rc) return rc;
-  fe* num = tmp_base();
-  fe* P = num + u;
-  fe* S = P + u;
-  fe* totals = S + u;
-  fe* offsets = totals + nblocks;
-  fe* inv_total = offsets + nblocks;
-  ZOut zo;
-  memset(&zo, 0, sizeof(zo));
-  zo.z[0] = (fe*)d_z;
-  H2_LAUNCH("k_shuffle_numden", k_shuffle_numden, ceil_div_u32(u, 256), 256, 0, s, (const fe*)d_input, (const fe*)d_shuffle, host_fe(gamma), usable_rows, num, P);
-  H2_HIP(hipMemcpyAsync(S, P, u * 32, hipMemcpyDeviceToDevice, s));
-  rc = mulscan(P, u, 0, totals, offsets, s);
-  if (!rc) rc = mulscan(S, u, 1, totals, offsets, s);
+  const RatioTmp t = carve_ratio_tmp(u, nblocks);
+  const ZOut zo = single_out(d_z);
+  H2_LAUNCH("k_shuffle_numden", k_shuffle_numden, ceil_div_u32(u, 256), 256, 0, s, (const fe*)d_input, (const fe*)d_shuffle, host_fe(gamma), usable_rows, t.num, t.P);
+  rc = running_product(t, u, s);
   if (rc) return rc;
-  H2_LAUNCH("k_fr_inv_one", k_fr_inv_one, 1, 64, 0, s, (const fe*)(P + (u - 1)), inv_total);
-  H2_LAUNCH("k_perm_ratio", k_perm_ratio, ceil_div_u32(u, 256), 256, 0, s, (const fe*)num, (const fe*)P, (const fe*)S, (const fe*)inv_total, u, num);
-  rc = mulscan(num, u, 0, totals, offsets, s);
-  if (rc) return rc;
-  H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, dim3(ceil_div_u32((uint64_t)usable_rows + 1, 256), 1), 256, 0, s, (const fe*)num, usable_rows, zo,
+  H2_LAUNCH("k_perm_write_sets", k_perm_write_sets, dim3(ceil_div_u32((uint64_t)usable_rows + 1, 256), 1), 256, 0, s, (const fe*)t.num, usable_rows, zo,
             (const uint32_t*)nullptr, 0u);
   // the ONE comparison: a satisfied shuffle ends at one (the Montgomery-2^256 one, fully reduced as every stored value is)
   fe last;
@@ -1395,37 +1387,28 @@ int h2mi_plonk_logup_sum_sets_dev(const void* d_inputs, uint32_t n_inputs, const
   H2_REQUIRE_INIT();
   const void* d_input = d_inputs;
   if (!d_input || !d_table || !d_m || !beta || !d_phi || n_inputs == 0 || n_inputs > H2MI_MAX_LOGUP_INPUTS) return H2MI_EINVAL;
-  if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k)) return H2MI_ERANGE;
+  if (rows_out_of_range(k, usable_rows)) return H2MI_ERANGE;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
   const size_t u = usable_rows;
   const uint32_t nblocks = ceil_div_u32(u, MS_TILE);
   static_assert(AS_TILE == MS_TILE, "one pair of totals / offsets vectors serves both scans");
-  int rc = ensure_tmp(3 * u + 2 * (size_t)nblocks + 2, s);
+  int rc = ensure_tmp(ratio_tmp_size(u, nblocks), s);
   if (rc) return rc;
-  fe* num = tmp_base();
-  fe* P = num + u;
-  fe* S = P + u;
-  fe* totals = S + u;
-  fe* offsets = totals + nblocks;
-  fe* inv_total = offsets + nblocks;
+  const RatioTmp t = carve_ratio_tmp(u, nblocks);
   if (n_inputs == 1)
     H2_LAUNCH("k_logup_numden", k_logup_numden, ceil_div_u32(u, 256), 256, 0, s, (const fe*)d_input, (const fe*)d_table, (const fe*)d_m, host_fe(beta),
-              usable_rows, num, P);
+              usable_rows, t.num, t.P);
   else
     H2_LAUNCH("k_logup_numden_sets", k_logup_numden_sets, ceil_div_u32(u, 256), 256, 0, s, (const fe*)d_input, n_inputs, (size_t)1 << k, (const fe*)d_table,
-              (const fe*)d_m, host_fe(beta), usable_rows, num, P);
-  H2_HIP(hipMemcpyAsync(S, P, u * 32, hipMemcpyDeviceToDevice, s));
-  rc = mulscan(P, u, 0, totals, offsets, s);
-  if (!rc) rc = mulscan(S, u, 1, totals, offsets, s);
+              (const fe*)d_m, host_fe(beta), usable_rows, t.num, t.P);
+  rc = ratios(t, u, s);
   if (rc) return rc;
-  H2_LAUNCH("k_fr_inv_one", k_fr_inv_one, 1, 64, 0, s, (const fe*)(P + (u - 1)), inv_total);
-  H2_LAUNCH("k_perm_ratio", k_perm_ratio, ceil_div_u32(u, 256), 256, 0, s, (const fe*)num, (const fe*)P, (const fe*)S, (const fe*)inv_total, u, num);
-  H2_LAUNCH("k_addscan_local", k_addscan_local, nblocks, 256, 0, s, (const fe*)num, usable_rows, num, totals);
-  if (nblocks > 1) H2_LAUNCH("k_addscan_offsets", k_addscan_offsets, 1, 1024, 0, s, (const fe*)totals, nblocks, offsets);
-  H2_LAUNCH("k_addscan_apply", k_addscan_apply, ceil_div_u32((uint64_t)usable_rows + 1, 256), 256, 0, s, (const fe*)num,
-            (const fe*)(nblocks > 1 ? offsets : nullptr), usable_rows, (fe*)d_phi);
+  H2_LAUNCH("k_addscan_local", k_addscan_local, nblocks, 256, 0, s, (const fe*)t.num, usable_rows, t.num, t.totals);
+  if (nblocks > 1) H2_LAUNCH("k_addscan_offsets", k_addscan_offsets, 1, 1024, 0, s, (const fe*)t.totals, nblocks, t.offsets);
+  H2_LAUNCH("k_addscan_apply", k_addscan_apply, ceil_div_u32((uint64_t)usable_rows + 1, 256), 256, 0, s, (const fe*)t.num,
+            (const fe*)(nblocks > 1 ? t.offsets : nullptr), usable_rows, (fe*)d_phi);
   return release_tmp(s);
 }
 

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <array>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -43,6 +44,10 @@ struct PatchList {
   void add(const DeviceVec& d, size_t row, const Fr& v) {
     cells.push_back(at(d, row));
     vals.push_back(v);
+  }
+  // the blinding rows u + 1 .. 2^k - 1 behind product (or running sum) i of its phase: scalars bf i .. bf i + bf - 1 of its stream
+  void add_tail(const DeviceVec& z, size_t u, uint32_t bf, const std::vector<Fr>& blind, size_t i) {
+    for (uint32_t r = 0; r < bf; r++) add(z, u + 1 + r, blind[bf * i + r]);
   }
   void flush() {
     if (!cells.empty()) check(h2mi_fr_patch_cells_dev(cells.data(), (const uint64_t*)vals.data(), cells.size(), nullptr), "patch_cells");
@@ -143,49 +148,64 @@ int check_program(const h2mi_constraint_system& cs, const h2mi_gate_program* gat
   return H2MI_OK;
 }
 
-// the rules of h2mi_lookup_program_check (include/h2mi_prover.h).  slices: per lookup the sub-programs of its input and its table
-// polynomials (they point into lp->exprs.ops and share its constants).
-// With an h2mi_logup_inputs (the rules of h2mi_logup_inputs_check): lookup l holds sets[l] input tuples, input[l][j] is tuple j, and the
-// required degree is the logUp rule 2 + sum_j max(1, deg A_j) + max(1, deg S) — with one set the number the lookup rule gives.
-struct LookupSlices {
-  uint32_t sets[H2MI_MAX_LOOKUPS];
-  h2mi_gate_program input[H2MI_MAX_LOOKUPS][H2MI_MAX_LOGUP_INPUTS], table[H2MI_MAX_LOOKUPS];
+// An expression block cut into arguments (lookups or shuffles): per argument the sub-programs of its input sets and of its table
+// (shuffle) side, which point into exprs.ops and share its constants, and the largest degree among each part's polynomials.
+constexpr uint32_t MAX_ARGUMENTS = std::max(H2MI_MAX_LOOKUPS, H2MI_MAX_SHUFFLES);
+struct ArgumentSlices {
+  uint32_t sets[MAX_ARGUMENTS];  // one but for a logUp lookup with several input sets
+  h2mi_gate_program input[MAX_ARGUMENTS][H2MI_MAX_LOGUP_INPUTS], table[MAX_ARGUMENTS];
+  uint32_t in_degree[MAX_ARGUMENTS][H2MI_MAX_LOGUP_INPUTS], tab_degree[MAX_ARGUMENTS];
 };
-int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_program* lp, uint32_t* degree_out, LookupSlices* slices,
-                         uint32_t n_challenges = 0, const h2mi_logup_inputs* li = nullptr) {
-  if (!lp || lp->n_lookups == 0 || lp->n_lookups > H2MI_MAX_LOOKUPS || lp->n_lookups != cs.n_lookups) return H2MI_EINVAL;
-  auto sets = [&](uint32_t l) { return li ? li->n_inputs[l] : 1u; };
-  for (uint32_t l = 0; l < lp->n_lookups; l++)
-    if (sets(l) == 0 || sets(l) > H2MI_MAX_LOGUP_INPUTS) return H2MI_EINVAL;
+// exprs holds per argument its sets[i] (NULL: one) x n_pairs[i] input polynomials, set by set, then its n_pairs[i] table polynomials
+int slice_program(const h2mi_constraint_system& cs, const h2mi_gate_program& exprs, uint32_t n_args, const uint32_t* n_pairs, const uint32_t* sets,
+                  uint32_t n_challenges, ArgumentSlices& out) {
   h2::ExprShape all;
   {
-    h2mi_constraint_system any = cs;  // the structural rules and the query lists; the degree rule is per lookup, below
+    h2mi_constraint_system any = cs;  // the structural rules and the query lists; the degree rule is per argument, the caller's
     any.degree = 0xffffffffu;
-    const int rc = check_program(any, &lp->exprs, &all, n_challenges);
+    const int rc = check_program(any, &exprs, &all, n_challenges);
     if (rc) return rc;
   }
   uint32_t want = 0;
-  for (uint32_t l = 0; l < lp->n_lookups; l++) {
-    if (lp->n_pairs[l] == 0 || lp->n_pairs[l] > H2MI_MAX_EXPR_OPS) return H2MI_EINVAL;
-    want += (sets(l) + 1) * lp->n_pairs[l];
+  for (uint32_t i = 0; i < n_args; i++) {
+    out.sets[i] = sets ? sets[i] : 1u;
+    if (n_pairs[i] == 0 || n_pairs[i] > H2MI_MAX_EXPR_OPS) return H2MI_EINVAL;
+    want += (out.sets[i] + 1) * n_pairs[i];
   }
   if (all.n_polys != want) return H2MI_EINVAL;
-  uint32_t pos = 0, degree = 0;
-  auto take = [&](uint32_t polys, h2mi_gate_program* out) {  // the next `polys` polynomials -> their largest degree
+  uint32_t pos = 0;
+  auto take = [&](uint32_t polys, h2mi_gate_program& sub) {  // the next `polys` polynomials -> their largest degree
     const uint32_t first = pos;
-    for (uint32_t seen = 0; seen < polys; pos++) seen += lp->exprs.ops[pos].op == H2MI_EXPR_END;
-    const h2mi_gate_program sub = {lp->exprs.ops + first, pos - first, lp->exprs.constants, lp->exprs.n_constants};
+    for (uint32_t seen = 0; seen < polys; pos++) seen += exprs.ops[pos].op == H2MI_EXPR_END;
+    sub = {exprs.ops + first, pos - first, exprs.constants, exprs.n_constants};
     h2::ExprShape sh;
     h2::expr_walk(&sub, cs.k, n_challenges, [](uint32_t, uint32_t, int32_t) { return true; }, &sh);  // validated above
-    if (out) *out = sub;
-    return std::max(sh.degree, 1u);
+    return sh.degree;
   };
+  for (uint32_t i = 0; i < n_args; i++) {
+    for (uint32_t j = 0; j < out.sets[i]; j++) out.in_degree[i][j] = take(n_pairs[i], out.input[i][j]);
+    out.tab_degree[i] = take(n_pairs[i], out.table[i]);
+  }
+  return H2MI_OK;
+}
+
+// the rules of h2mi_lookup_program_check (include/h2mi_prover.h).
+// With an h2mi_logup_inputs (the rules of h2mi_logup_inputs_check): lookup l holds sets[l] input tuples, input[l][j] is tuple j, and the
+// required degree is the logUp rule 2 + sum_j max(1, deg A_j) + max(1, deg S) — with one set the number the lookup rule gives.
+int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_program* lp, uint32_t* degree_out, ArgumentSlices* slices,
+                         uint32_t n_challenges = 0, const h2mi_logup_inputs* li = nullptr) {
+  if (!lp || lp->n_lookups == 0 || lp->n_lookups > H2MI_MAX_LOOKUPS || lp->n_lookups != cs.n_lookups) return H2MI_EINVAL;
+  for (uint32_t l = 0; li && l < lp->n_lookups; l++)
+    if (li->n_inputs[l] == 0 || li->n_inputs[l] > H2MI_MAX_LOGUP_INPUTS) return H2MI_EINVAL;
+  ArgumentSlices own, &sl = slices ? *slices : own;
+  const int rc = slice_program(cs, lp->exprs, lp->n_lookups, lp->n_pairs, li ? li->n_inputs : nullptr, n_challenges, sl);
+  if (rc) return rc;
+  uint32_t degree = 0;
   for (uint32_t l = 0; l < lp->n_lookups; l++) {
     uint32_t in = 0;
-    for (uint32_t j = 0; j < sets(l); j++) in += take(lp->n_pairs[l], slices ? &slices->input[l][j] : nullptr);
-    const uint32_t tab = take(lp->n_pairs[l], slices ? &slices->table[l] : nullptr);
-    if (slices) slices->sets[l] = sets(l);
-    const uint32_t d = std::max(4u, 2 + in + tab);  // [RECALL plonk/lookup.rs Argument::required_degree]; several sets: DESIGN.md 4.5
+    for (uint32_t j = 0; j < sl.sets[l]; j++) in += std::max(sl.in_degree[l][j], 1u);
+    // [RECALL plonk/lookup.rs Argument::required_degree]; several sets: DESIGN.md 4.5
+    const uint32_t d = std::max(4u, 2 + in + std::max(sl.tab_degree[l], 1u));
     if (d > cs.degree) return H2MI_EINVAL;
     degree = std::max(degree, d);
   }
@@ -194,39 +214,16 @@ int check_lookup_program(const h2mi_constraint_system& cs, const h2mi_lookup_pro
 }
 
 // the rules of h2mi_shuffle_program_check (include/h2mi_prover.h) [RECALL halo2_proofs (PSE line) plonk/shuffle.rs Argument::required_degree,
-// restated from memory and pinned to DESIGN.md 4.5].  slices: per shuffle the sub-programs of its input and its shuffle-side polynomials
-struct ShuffleSlices {
-  h2mi_gate_program input[H2MI_MAX_SHUFFLES], table[H2MI_MAX_SHUFFLES];
-};
-int check_shuffle_program(const h2mi_constraint_system& cs, const h2mi_shuffle_program* sp, uint32_t* degree_out, ShuffleSlices* slices,
+// restated from memory and pinned to DESIGN.md 4.5]
+int check_shuffle_program(const h2mi_constraint_system& cs, const h2mi_shuffle_program* sp, uint32_t* degree_out, ArgumentSlices* slices,
                           uint32_t n_challenges = 0) {
   if (!sp || sp->n_shuffles == 0 || sp->n_shuffles > H2MI_MAX_SHUFFLES) return H2MI_EINVAL;
-  h2::ExprShape all;
-  {
-    h2mi_constraint_system any = cs;  // the structural rules and the query lists; the degree rule is per shuffle, below
-    any.degree = 0xffffffffu;
-    const int rc = check_program(any, &sp->exprs, &all, n_challenges);
-    if (rc) return rc;
-  }
-  uint32_t want = 0;
+  ArgumentSlices own, &sl = slices ? *slices : own;
+  const int rc = slice_program(cs, sp->exprs, sp->n_shuffles, sp->n_pairs, nullptr, n_challenges, sl);
+  if (rc) return rc;
+  uint32_t degree = 0;
   for (uint32_t i = 0; i < sp->n_shuffles; i++) {
-    if (sp->n_pairs[i] == 0 || sp->n_pairs[i] > H2MI_MAX_EXPR_OPS) return H2MI_EINVAL;
-    want += 2 * sp->n_pairs[i];
-  }
-  if (all.n_polys != want) return H2MI_EINVAL;
-  uint32_t pos = 0, degree = 0;
-  auto take = [&](uint32_t polys, h2mi_gate_program* out) {  // the next `polys` polynomials -> their largest degree
-    const uint32_t first = pos;
-    for (uint32_t seen = 0; seen < polys; pos++) seen += sp->exprs.ops[pos].op == H2MI_EXPR_END;
-    const h2mi_gate_program sub = {sp->exprs.ops + first, pos - first, sp->exprs.constants, sp->exprs.n_constants};
-    h2::ExprShape sh;
-    h2::expr_walk(&sub, cs.k, n_challenges, [](uint32_t, uint32_t, int32_t) { return true; }, &sh);  // validated above
-    if (out) *out = sub;
-    return sh.degree;
-  };
-  for (uint32_t i = 0; i < sp->n_shuffles; i++) {
-    const uint32_t in = take(sp->n_pairs[i], slices ? &slices->input[i] : nullptr), tab = take(sp->n_pairs[i], slices ? &slices->table[i] : nullptr);
-    const uint32_t d = 2 + std::max({1u, in, tab});
+    const uint32_t d = 2 + std::max({1u, sl.in_degree[i][0], sl.tab_degree[i]});
     if (d > cs.degree) return H2MI_EINVAL;
     degree = std::max(degree, d);
   }
@@ -316,6 +313,11 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, 
 struct Table {  // a lookup table's distinct usable values in ascending canonical order, for the device's counting sort
   Dev sorted, sorted_mont, mult;
   uint32_t n_unique = 0;
+  void alloc(size_t rows) {  // room for `rows` distinct values (h2mi_fr_sort_unique_dev inside a proof fills it)
+    sorted = vec(rows);
+    sorted_mont = vec(rows);
+    mult = vec(rows / 8 + 1);
+  }
 };
 
 }  // namespace
@@ -343,12 +345,12 @@ struct h2mi_pk_s {
   bool logup = false;
   std::vector<h2mi_expr_op> lookup_ops;
   std::vector<uint64_t> lookup_constants;
-  LookupSlices lookup_slices;
+  ArgumentSlices lookup_slices;
   // shuffle arguments (h2mi_prover_keygen_shuffles): the key's own copy, cut into each shuffle's input and shuffle-side polynomials
   uint32_t n_shuffles = 0;
   std::vector<h2mi_expr_op> shuffle_ops;
   std::vector<uint64_t> shuffle_constants;
-  ShuffleSlices shuffle_slices;
+  ArgumentSlices shuffle_slices;
   // advice phases and challenges (h2mi_prover_keygen_phases); every other keygen: one phase, no challenges
   h2mi_advice_phases phases;
   uint32_t phase_columns[H2MI_MAX_ADVICE_PHASES] = {0, 0, 0};
@@ -408,12 +410,17 @@ void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells) {
   }
   if (zeros_extra) mult[0] += (uint32_t)zeros_extra;  // zero sorts first
   t.n_unique = (uint32_t)mult.size();
-  t.sorted = vec(mult.size());
-  t.sorted_mont = vec(mult.size());
-  t.mult = vec(mult.size() / 8 + 1);
+  t.alloc(mult.size());
   check(h2mi_memcpy_h2d(t.sorted->p, canon.data(), canon.size() * 32), "table");
   check(h2mi_memcpy_h2d(t.sorted_mont->p, mont.data(), mont.size() * 32), "table");
   check(h2mi_memcpy_h2d(t.mult->p, mult.data(), mult.size() * 4), "table");
+}
+
+// a caller's program copied into vectors the key owns -> the view over the copy
+h2mi_gate_program own_program(const h2mi_gate_program& g, std::vector<h2mi_expr_op>& ops, std::vector<uint64_t>& constants) {
+  ops.assign(g.ops, g.ops + g.n_ops);
+  if (g.n_constants) constants.assign(g.constants, g.constants + 4 * (size_t)g.n_constants);
+  return {ops.data(), g.n_ops, constants.data(), g.n_constants};
 }
 
 std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
@@ -426,26 +433,18 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
   pk.phases.n_phases = 1;
   if (phases) pk.phases = *phases;
   for (uint32_t j = 0; j < cs.n_advice; j++) pk.phase_columns[pk.phases.advice_phase[j]]++;
-  if (gates) {
-    pk.gate_ops.assign(gates->ops, gates->ops + gates->n_ops);
-    if (gates->n_constants) pk.gate_constants.assign(gates->constants, gates->constants + 4 * (size_t)gates->n_constants);
-    pk.gate_program = {pk.gate_ops.data(), gates->n_ops, pk.gate_constants.data(), gates->n_constants};
-  }
+  if (gates) pk.gate_program = own_program(*gates, pk.gate_ops, pk.gate_constants);
   if (lookups) {
     pk.lookup_exprs = true;
-    pk.lookup_ops.assign(lookups->exprs.ops, lookups->exprs.ops + lookups->exprs.n_ops);
-    if (lookups->exprs.n_constants) pk.lookup_constants.assign(lookups->exprs.constants, lookups->exprs.constants + 4 * (size_t)lookups->exprs.n_constants);
     h2mi_lookup_program own = *lookups;
-    own.exprs = {pk.lookup_ops.data(), lookups->exprs.n_ops, pk.lookup_constants.data(), lookups->exprs.n_constants};
+    own.exprs = own_program(lookups->exprs, pk.lookup_ops, pk.lookup_constants);
     // an h2mi_logup_inputs is copied into the slices (their `sets`): the key reads the caller's struct here and never again
     if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices, pk.phases.n_challenges, inputs)) throw Error(H2MI_EINVAL, "lookup program");
   }
   if (shuffles) {
     pk.n_shuffles = shuffles->n_shuffles;
-    pk.shuffle_ops.assign(shuffles->exprs.ops, shuffles->exprs.ops + shuffles->exprs.n_ops);
-    if (shuffles->exprs.n_constants) pk.shuffle_constants.assign(shuffles->exprs.constants, shuffles->exprs.constants + 4 * (size_t)shuffles->exprs.n_constants);
     h2mi_shuffle_program own = *shuffles;
-    own.exprs = {pk.shuffle_ops.data(), shuffles->exprs.n_ops, pk.shuffle_constants.data(), shuffles->exprs.n_constants};
+    own.exprs = own_program(shuffles->exprs, pk.shuffle_ops, pk.shuffle_constants);
     if (check_shuffle_program(cs, &own, nullptr, &pk.shuffle_slices, pk.phases.n_challenges)) throw Error(H2MI_EINVAL, "shuffle program");
   }
   pk.vk_only = (flags & H2MI_KEYGEN_VK_ONLY) != 0;
@@ -693,17 +692,21 @@ struct h2mi_prover_s {
   // buffers
   std::vector<Forms> advice, z;
   Dev instance, instance_poly, instance_coset;
+  // both sides of an argument given as expressions, compressed with theta: on the rows, and the same on the extended coset
+  struct Sides {
+    Dev input, table, in_coset, tab_coset;
+  };
   struct Lk {
-    Dev input;  // selector * column rows (single-column form); otherwise the advice column itself is the input
+    // lookups given as expressions: both sides compressed (a logUp lookup's input sets behind one another), and the table's distinct
+    // values are sorted inside the proof.  The single-column form holds selector * column rows in c.input and nothing else; without
+    // a selector the advice column itself is the input
+    Sides c;
     Forms a, s, z;
-    // lookups given as expressions: `input` and `table` are the compressed expressions on the rows, in_coset / tab_coset the same
-    // on the extended coset, and the table's distinct values are sorted inside the proof
-    Dev table, in_coset, tab_coset;
     Table sorted;
   } lk[H2MI_MAX_LOOKUPS];
-  // shuffle arguments: both sides compressed with theta on the rows and on the extended coset, the product in its three forms
+  // shuffle arguments: both sides compressed, the product in its three forms
   struct Sf {
-    Dev input, table, in_coset, tab_coset;
+    Sides c;
     Forms z;
   } sf[H2MI_MAX_SHUFFLES];
   // h2mi_prover_check's own scratch, allocated by its first call: a lookup's input and table rows, the table's sorted distinct values
@@ -743,11 +746,11 @@ struct h2mi_prover_s {
       if (st) h2mi_stream_destroy(st);
   }
   const DeviceVec& lookup_input(uint32_t l) const {
-    if (pk->lookup_exprs) return *lk[l].input;
+    if (pk->lookup_exprs) return *lk[l].c.input;
     const h2mi_lookup& d = pk->cs.lookups[l];
-    return d.selector_fixed >= 0 ? *lk[l].input : *advice[d.input.index].value;
+    return d.selector_fixed >= 0 ? *lk[l].c.input : *advice[d.input.index].value;
   }
-  const DeviceVec& lookup_table(uint32_t l) const { return pk->lookup_exprs ? *lk[l].table : *pk->fixed_values[pk->cs.lookups[l].table_fixed]; }
+  const DeviceVec& lookup_table(uint32_t l) const { return pk->lookup_exprs ? *lk[l].c.table : *pk->fixed_values[pk->cs.lookups[l].table_fixed]; }
   // one side of lookup l compressed with theta, on the rows (coset = false) or on the extended coset
   // (`at`: the element of `out` the vector starts at — the input sets of a logUp lookup lie behind one another)
   void compress(const h2mi_gate_program& prog, bool coset, DeviceVec& out, const Fr* th = nullptr, size_t at = 0) const {
@@ -759,6 +762,18 @@ struct h2mi_prover_s {
     check(h2mi_plonk_expr_compress_ch_dev(adv, cs.n_advice, fix, cs.n_fixed, inst, &prog, challenge_limbs(), pk->phases.n_challenges, cs.k,
                                           coset ? pk->domain.extended_k() : cs.k, (th ? *th : theta).l, (char*)out.p + at * 32, nullptr),
           "expr_compress");
+  }
+  // both sides of argument i of `sl` (a lookup given as expressions, a shuffle) on the rows or on the extended coset: input set j
+  // lands one domain's length behind set j - 1 in `in`, the table (shuffle) side in `tab`
+  void compress_sides(const ArgumentSlices& sl, uint32_t i, bool coset, DeviceVec& in, DeviceVec& tab, const Fr* th = nullptr) const {
+    for (uint32_t j = 0; j < sl.sets[i]; j++) compress(sl.input[i][j], coset, in, th, j * (coset ? pk->ext : pk->n));
+    compress(sl.table[i], coset, tab, th);
+  }
+  // a permutation column on the rows (coset = false) or on the extended coset
+  const void* perm_column(const h2mi_column& c, bool coset) const {
+    if (c.kind == H2MI_COL_ADVICE) return coset ? advice[c.index].coset->p : advice[c.index].value->p;
+    if (c.kind == H2MI_COL_INSTANCE) return coset ? instance_coset->p : instance->p;
+    return coset ? pk->fixed_cosets[c.index]->p : pk->fixed_values[c.index]->p;
   }
   const uint64_t* challenge_limbs() const { return pk->phases.n_challenges ? (const uint64_t*)challenges.data() : nullptr; }
   // a key with challenges: the phases behind the advice need their values
@@ -856,28 +871,18 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
   for (uint32_t l = 0; l < cs.n_lookups; l++) {
     if (pk->lookup_exprs) {
       const size_t sets = pk->lookup_slices.sets[l];  // a logUp lookup's input sets, contiguous: one but for a key of h2mi_prover_keygen_logup
-      p.lk[l].input = vec(sets * n);
-      p.lk[l].table = vec(n);
-      p.lk[l].in_coset = vec(sets * ext);
-      p.lk[l].tab_coset = vec(ext);
-      Table& t = p.lk[l].sorted;
-      t.sorted = vec(pk->u);
-      t.sorted_mont = vec(pk->u);
-      t.mult = vec(pk->u / 8 + 1);
+      p.lk[l].c = {vec(sets * n), vec(n), vec(sets * ext), vec(ext)};
+      p.lk[l].sorted.alloc(pk->u);
     } else if (cs.lookups[l].selector_fixed >= 0) {
-      p.lk[l].input = vec(n);
+      p.lk[l].c.input = vec(n);
     }
     p.lk[l].a.alloc(n, ext);
     if (!pk->logup) p.lk[l].s.alloc(n, ext);  // a logUp key: `a` holds M, `z` the running sum, there is no permuted table
     p.lk[l].z.alloc(n, ext);
   }
   for (uint32_t i = 0; i < pk->n_shuffles; i++) {
-    h2mi_prover_s::Sf& sf = p.sf[i];
-    sf.input = vec(n);
-    sf.table = vec(n);
-    sf.in_coset = vec(ext);
-    sf.tab_coset = vec(ext);
-    sf.z.alloc(n, ext);
+    p.sf[i].c = {vec(n), vec(n), vec(ext), vec(ext)};
+    p.sf[i].z.alloc(n, ext);
   }
   p.random_poly = vec(n);
   p.h = vec(ext);
@@ -893,6 +898,14 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
   for (int i = 0; i < 2; i++) check(h2mi_stream_create(&p.lane[i]), "stream_create");
   check(h2mi_stream_create(&p.side), "stream_create");
   return pp;
+}
+
+// theta as the caller delivers it
+Fr take_theta(const uint64_t* theta, const char* refusal = "theta") {
+  if (!theta) throw Error(H2MI_EINVAL, refusal);
+  Fr th;
+  std::memcpy(th.l, theta, 32);
+  return th;
 }
 
 void require_phase(h2mi_prover_s& p, Phase want) {
@@ -985,25 +998,22 @@ void phase_lookups(h2mi_prover_s& p, const uint64_t* theta, uint64_t* points_out
   p.require_challenges();
   p.phase = IDLE;
   if (pk.n_shuffles) {  // the shuffles are compressed with theta in the products phase: this call carries it, lookups or none
-    if (!theta) throw Error(H2MI_EINVAL, "theta");
-    std::memcpy(p.theta.l, theta, 32);
+    p.theta = take_theta(theta);
     p.have_theta = true;
   }
   if (L && pk.logup) {
     // logUp [restated in DESIGN.md 4.5]: compress -> multiplicities -> blinding rows -> one in-order commitment group of L columns.
     // M's blinding rows u .. 2^k - 1 come from the permuted columns' stream (purpose 4): bf + 1 scalars per lookup, in lookup order
-    if (!theta) throw Error(H2MI_EINVAL, "theta");
-    std::memcpy(p.theta.l, theta, 32);
+    p.theta = take_theta(theta);
     const std::vector<Fr> mb = p.blinding(4, (size_t)(bf + 1) * L);
     PatchList pl;
     std::vector<const void*> cols;
     for (uint32_t l = 0; l < L; l++) {
-      const uint32_t sets = pk.lookup_slices.sets[l];
-      for (uint32_t j = 0; j < sets; j++) p.compress(pk.lookup_slices.input[l][j], false, *p.lk[l].input, nullptr, (size_t)j * pk.n);
-      p.compress(pk.lookup_slices.table[l], false, *p.lk[l].table);
+      const h2mi_prover_s::Sides& c = p.lk[l].c;
+      p.compress_sides(pk.lookup_slices, l, false, *c.input, *c.table);
       DeviceVec& mult = *p.lk[l].a.value;
       uint64_t missing = 0;
-      check(h2mi_plonk_logup_multiplicity_sets_dev(p.lk[l].input->p, sets, p.lk[l].table->p, cs.k, u, mult.p, &missing, nullptr), "logup_multiplicity");
+      check(h2mi_plonk_logup_multiplicity_sets_dev(c.input->p, pk.lookup_slices.sets[l], c.table->p, cs.k, u, mult.p, &missing, nullptr), "logup_multiplicity");
       if (missing) throw Error(H2MI_EUNSAT, "lookup input not in the table (ConstraintSystemFailure)");
       for (uint32_t r = 0; r <= bf; r++) pl.add(mult, u + r, mb[(size_t)(bf + 1) * l + r]);
       cols.push_back(p.col(mult));
@@ -1018,20 +1028,16 @@ void phase_lookups(h2mi_prover_s& p, const uint64_t* theta, uint64_t* points_out
     const std::vector<Fr> lb = p.blinding(4, (size_t)2 * (bf + 1) * L);
     PatchList pl;
     std::vector<const void*> cols;
-    if (pk.lookup_exprs) {
-      if (!theta) throw Error(H2MI_EINVAL, "theta");
-      std::memcpy(p.theta.l, theta, 32);
-    }
+    if (pk.lookup_exprs) p.theta = take_theta(theta);
     for (uint32_t l = 0; l < L; l++) {
       const h2mi_lookup& d = cs.lookups[l];
       if (pk.lookup_exprs) {
         // both sides compressed on all 2^k rows; the table's usable rows sorted here, inside the proof
-        p.compress(pk.lookup_slices.input[l][0], false, *p.lk[l].input);
-        p.compress(pk.lookup_slices.table[l], false, *p.lk[l].table);
+        p.compress_sides(pk.lookup_slices, l, false, *p.lk[l].c.input, *p.lk[l].c.table);
         Table& ts = p.lk[l].sorted;
-        check(h2mi_fr_sort_unique_dev(p.lk[l].table->p, u, ts.sorted->p, ts.sorted_mont->p, ts.mult->p, &ts.n_unique, nullptr), "sort_unique");
+        check(h2mi_fr_sort_unique_dev(p.lk[l].c.table->p, u, ts.sorted->p, ts.sorted_mont->p, ts.mult->p, &ts.n_unique, nullptr), "sort_unique");
       } else if (d.selector_fixed >= 0) {  // the input expression's rows: q_lookup * a, zero wherever the selector is off
-        check(h2mi_fr_mul_dev(pk.fixed_values[d.selector_fixed]->p, p.advice[d.input.index].value->p, n, p.lk[l].input->p, nullptr), "lookup input");
+        check(h2mi_fr_mul_dev(pk.fixed_values[d.selector_fixed]->p, p.advice[d.input.index].value->p, n, p.lk[l].c.input->p, nullptr), "lookup input");
       }
       DeviceVec &a_perm = *p.lk[l].a.value, &s_perm = *p.lk[l].s.value;
       uint64_t missing = 0;
@@ -1069,7 +1075,7 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
   const uint32_t u = pk.u, L = cs.n_lookups, m = cs.n_perm;
   if (p.phase != ADVICE && p.phase != LOOKUPS) throw Error(H2MI_EINVAL, "check: between the last advice phase and the products");
   if (pk.phases.n_challenges && !p.have_challenges) throw Error(H2MI_EINVAL, "check: h2mi_prover_set_challenges has not been called");
-  if (((L && pk.lookup_exprs) || pk.n_shuffles) && !theta) throw Error(H2MI_EINVAL, "check: theta");
+  const Fr th = (L && pk.lookup_exprs) || pk.n_shuffles ? take_theta(theta, "check: theta") : fr_zero();
   std::vector<h2mi_check_failure> out;
   const void *adv[H2MI_MAX_ADVICE], *fix[H2MI_MAX_FIXED];
   for (uint32_t j = 0; j < cs.n_advice; j++) adv[j] = p.advice[j].value->p;
@@ -1088,7 +1094,7 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
     const void* vals[H2MI_MAX_PERM];
     for (uint32_t j = 0; j < m; j++) {
       const h2mi_column& c = cs.perm_columns[j];
-      vals[j] = c.kind == H2MI_COL_ADVICE ? p.advice[c.index].value->p : c.kind == H2MI_COL_INSTANCE ? p.instance->p : pk.fixed_values[c.index]->p;
+      vals[j] = p.perm_column(c, false);
     }
     uint32_t report[2];
     check(h2mi_plonk_copy_check_dev(vals, m, pk.moved_cells_dev->p, (uint32_t)(pk.moved_cells.size() / 4), report, nullptr), "copy_check");
@@ -1107,12 +1113,8 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
       if (!p.check_in) {
         p.check_in = vec(n);
         p.check_tab = vec(n);
-        p.check_sorted.sorted = vec(u);
-        p.check_sorted.sorted_mont = vec(u);
-        p.check_sorted.mult = vec(u / 8 + 1);
+        p.check_sorted.alloc(u);
       }
-      Fr th;
-      std::memcpy(th.l, theta, 32);
       p.compress(pk.lookup_slices.table[l], false, *p.check_tab, &th);
       Table& ts = p.check_sorted;
       check(h2mi_fr_sort_unique_dev(p.check_tab->p, u, ts.sorted->p, ts.sorted_mont->p, ts.mult->p, &ts.n_unique, nullptr), "sort_unique");
@@ -1137,15 +1139,8 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
     if (!p.check_in) p.check_in = vec(n);
     if (!p.check_tab) p.check_tab = vec(n);
     for (Table* t : {&p.check_sorted, &p.check_sorted_in})
-      if (!t->sorted) {
-        t->sorted = vec(u);
-        t->sorted_mont = vec(u);
-        t->mult = vec(u / 8 + 1);
-      }
-    Fr th;
-    std::memcpy(th.l, theta, 32);
-    p.compress(pk.shuffle_slices.input[i], false, *p.check_in, &th);
-    p.compress(pk.shuffle_slices.table[i], false, *p.check_tab, &th);
+      if (!t->sorted) t->alloc(u);
+    p.compress_sides(pk.shuffle_slices, i, false, *p.check_in, *p.check_tab, &th);
     Table &ti = p.check_sorted_in, &ts = p.check_sorted;
     check(h2mi_fr_sort_unique_dev(p.check_in->p, u, ti.sorted->p, ti.sorted_mont->p, ti.mult->p, &ti.n_unique, nullptr), "sort_unique");
     check(h2mi_fr_sort_unique_dev(p.check_tab->p, u, ts.sorted->p, ts.sorted_mont->p, ts.mult->p, &ts.n_unique, nullptr), "sort_unique");
@@ -1179,12 +1174,11 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
     PatchList pl;
     for (uint32_t i = 0; i < S; i++) {
       h2mi_prover_s::Sf& sf = p.sf[i];
-      p.compress(pk.shuffle_slices.input[i], false, *sf.input);
-      p.compress(pk.shuffle_slices.table[i], false, *sf.table);
-      const int rc = h2mi_plonk_shuffle_product_dev(sf.input->p, sf.table->p, cs.k, u, gamma.l, sf.z.value->p, nullptr);
+      p.compress_sides(pk.shuffle_slices, i, false, *sf.c.input, *sf.c.table);
+      const int rc = h2mi_plonk_shuffle_product_dev(sf.c.input->p, sf.c.table->p, cs.k, u, gamma.l, sf.z.value->p, nullptr);
       if (rc == H2MI_EUNSAT) throw Error(H2MI_EUNSAT, "shuffle: the two sides are not the same multiset (ConstraintSystemFailure)");
       check(rc, "shuffle_product");
-      for (uint32_t r = 0; r < bf; r++) pl.add(*sf.z.value, u + 1 + r, szb[(size_t)bf * i + r]);
+      pl.add_tail(*sf.z.value, u, bf, szb, i);
     }
     pl.flush();
   }
@@ -1195,9 +1189,9 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
     PatchList pl;
     for (uint32_t l = 0; l < L; l++) {
       DeviceVec& phi = *p.lk[l].z.value;
-      check(h2mi_plonk_logup_sum_sets_dev(p.lk[l].input->p, pk.lookup_slices.sets[l], p.lk[l].table->p, p.lk[l].a.value->p, cs.k, u, beta.l, phi.p, nullptr),
+      check(h2mi_plonk_logup_sum_sets_dev(p.lk[l].c.input->p, pk.lookup_slices.sets[l], p.lk[l].c.table->p, p.lk[l].a.value->p, cs.k, u, beta.l, phi.p, nullptr),
             "logup_sum");
-      for (uint32_t r = 0; r < bf; r++) pl.add(phi, u + 1 + r, pb[(size_t)bf * l + r]);
+      pl.add_tail(phi, u, bf, pb, l);
     }
     pl.flush();
   }
@@ -1216,8 +1210,7 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
     std::vector<Fr> bd;
     Fr dp = fr::ONE;
     for (uint32_t j = 0; j < m; j++) {
-      const h2mi_column& c = cs.perm_columns[j];
-      vals.push_back(c.kind == H2MI_COL_ADVICE ? p.advice[c.index].value->p : c.kind == H2MI_COL_INSTANCE ? p.instance->p : pk.fixed_values[c.index]->p);
+      vals.push_back(p.perm_column(cs.perm_columns[j], false));
       sigs.push_back(pk.sigma_values[j]->p);
       bd.push_back(fr::mul(beta, dp));
       dp = fr::mul(dp, pk.delta);
@@ -1233,8 +1226,7 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
             "permutation_products");
     const std::vector<Fr> zblind = p.blinding(2, (size_t)n_sets * bf);
     PatchList pl;
-    for (uint32_t s = 0; s < n_sets; s++)
-      for (uint32_t r = 0; r < bf; r++) pl.add(*p.z[s].value, u + 1 + r, zblind[(size_t)s * bf + r]);
+    for (uint32_t s = 0; s < n_sets; s++) pl.add_tail(*p.z[s].value, u, bf, zblind, s);
     pl.flush();
   }
   std::vector<const void*> zcols;
@@ -1269,7 +1261,7 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
                                             u, beta.l, gamma.l, lz.p, nullptr),
               "lookup_product");
         PatchList pl;
-        for (uint32_t r = 0; r < bf; r++) pl.add(lz, u + 1 + r, lzb[(size_t)bf * l + r]);
+        pl.add_tail(lz, u, bf, lzb, l);
         pl.flush();
         check(h2mi_stream_wait(p.side, nullptr), "stream_wait");
         p.forms(p.lk[l].z, p.side);
@@ -1305,8 +1297,7 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_coset
   ec.n_perm = m;
   ec.chunk_len = pk.chunk;
   for (uint32_t j = 0; j < m; j++) {
-    const h2mi_column& c = cs.perm_columns[j];
-    ec.perm_value[j] = c.kind == H2MI_COL_ADVICE ? p.advice[c.index].coset->p : c.kind == H2MI_COL_INSTANCE ? p.instance_coset->p : pk.fixed_cosets[c.index]->p;
+    ec.perm_value[j] = p.perm_column(cs.perm_columns[j], true);
     ec.perm_sigma[j] = pk.sigma_cosets[j]->p;
   }
   for (uint32_t s = 0; s < n_sets; s++) ec.perm_z[s] = p.z[s].coset->p;
@@ -1317,10 +1308,9 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_coset
     if (pk.lookup_exprs) {
       // compressed on the extended coset itself: a product of columns is no polynomial of degree < n, so transforming the
       // compressed rows would give another function
-      for (uint32_t j = 0; j < pk.lookup_slices.sets[l]; j++) p.compress(pk.lookup_slices.input[l][j], true, *p.lk[l].in_coset, nullptr, (size_t)j * pk.ext);
-      p.compress(pk.lookup_slices.table[l], true, *p.lk[l].tab_coset);
-      ec.lookup_input[l] = p.lk[l].in_coset->p;
-      ec.lookup_table[l] = p.lk[l].tab_coset->p;
+      p.compress_sides(pk.lookup_slices, l, true, *p.lk[l].c.in_coset, *p.lk[l].c.tab_coset);
+      ec.lookup_input[l] = p.lk[l].c.in_coset->p;
+      ec.lookup_table[l] = p.lk[l].c.tab_coset->p;
     } else {
       ec.lookup_input[l] = p.advice[lk.input.index].coset->p;
       ec.lookup_input_b[l] = lk.selector_fixed >= 0 ? pk.fixed_cosets[lk.selector_fixed]->p : nullptr;
@@ -1336,10 +1326,9 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_coset
   std::memset(&sc, 0, sizeof(sc));
   sc.n_shuffles = pk.n_shuffles;
   for (uint32_t i = 0; i < pk.n_shuffles; i++) {  // compressed on the extended coset itself, as the lookups given as expressions are
-    p.compress(pk.shuffle_slices.input[i], true, *p.sf[i].in_coset);
-    p.compress(pk.shuffle_slices.table[i], true, *p.sf[i].tab_coset);
-    sc.input[i] = p.sf[i].in_coset->p;
-    sc.shuffle[i] = p.sf[i].tab_coset->p;
+    p.compress_sides(pk.shuffle_slices, i, true, *p.sf[i].c.in_coset, *p.sf[i].c.tab_coset);
+    sc.input[i] = p.sf[i].c.in_coset->p;
+    sc.shuffle[i] = p.sf[i].c.tab_coset->p;
     sc.z[i] = p.sf[i].z.coset->p;
   }
 }
@@ -1404,9 +1393,6 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
   DeviceVec& h = *p.h;
   const Fr& zeta = d.get_g_coset();
   const std::vector<Fr>& t_inv = d.t_inv();  // (X^n - 1)^-1 on the coset: cached in the domain
-  auto coset_col = [&](const h2mi_column& c) -> const void* {
-    return c.kind == H2MI_COL_ADVICE ? p.advice[c.index].coset->p : c.kind == H2MI_COL_INSTANCE ? p.instance_coset->p : pk.fixed_cosets[c.index]->p;
-  };
   if (cs.gates == H2MI_GATES_STANDARD_PLONK) {
     h2mi_standard_plonk_cosets sc;
     for (int i = 0; i < 3; i++) {
@@ -1438,7 +1424,7 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
     rc.a = p.advice[cs.gate_advice[0]].coset->p;
     rc.q = pk.fixed_cosets[cs.gate_selector[0]]->p;
     for (uint32_t j = 0; j < m; j++) {
-      rc.perm_value[j] = coset_col(cs.perm_columns[j]);
+      rc.perm_value[j] = p.perm_column(cs.perm_columns[j], true);
       rc.perm_sigma[j] = pk.sigma_cosets[j]->p;
     }
     for (uint32_t s = 0; s < n_sets; s++) rc.perm_z[s] = p.z[s].coset->p;
@@ -1476,7 +1462,7 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
     fc.n_perm = m;
     fc.chunk_len = pk.chunk;
     for (uint32_t j = 0; j < m; j++) {
-      fc.perm_value[j] = coset_col(cs.perm_columns[j]);
+      fc.perm_value[j] = p.perm_column(cs.perm_columns[j], true);
       fc.perm_sigma[j] = pk.sigma_cosets[j]->p;
     }
     for (uint32_t s = 0; s < n_sets; s++) fc.perm_z[s] = p.z[s].coset->p;
@@ -1811,21 +1797,34 @@ int pick(const Dev& d, uint32_t index, void** d_ptr, size_t* count) {
   return H2MI_OK;
 }
 
+// What the five keygen entries share.  `required`: the pointers the entry refuses to do without (besides cs and pk_out); `allowed`:
+// its flags.  An h2mi_logup_inputs comes through h2mi_prover_keygen_logup alone.
+int keygen_entry(const h2mi_constraint_system* cs, std::initializer_list<const void*> required, unsigned allowed, const h2mi_gate_program* gates,
+                 const h2mi_lookup_program* lookups, const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles, const h2mi_logup_inputs* inputs,
+                 uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
+  if (!cs || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~allowed) || ((flags & H2MI_KEYGEN_LOGUP) && !lookups)) return H2MI_EINVAL;
+  for (const void* ptr : required)
+    if (!ptr) return H2MI_EINVAL;
+  *pk_out = nullptr;
+  if (inputs && !lookups) return H2MI_EINVAL;
+  for (uint32_t l = 0; inputs && l < lookups->n_lookups && l < H2MI_MAX_LOOKUPS; l++)  // several sets are a logUp key's
+    if (inputs->n_inputs[l] != 1 && !(flags & H2MI_KEYGEN_LOGUP)) return H2MI_EINVAL;
+  if (h2mi_device_count() == 0) return H2MI_ENODEV;  // no CPU fallback: the prover exists on a GPU or not at all
+  return guarded([&] {
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, phases, g_lagrange_handle, fixed, copies, n_copies, flags, shuffles, inputs);
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    g_live_pks.insert(pk.get());
+    *pk_out = pk.release();
+  });
+}
+
 }  // namespace
 
 extern "C" {
 
 int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies,
                        unsigned flags, h2mi_pk_t* pk_out) {
-  if (!cs || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)H2MI_KEYGEN_VK_ONLY)) return H2MI_EINVAL;
-  *pk_out = nullptr;
-  if (h2mi_device_count() == 0) return H2MI_ENODEV;  // no CPU fallback: the prover exists on a GPU or not at all
-  return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_live_pks.insert(pk.get());
-    *pk_out = pk.release();
-  });
+  return keygen_entry(cs, {}, H2MI_KEYGEN_VK_ONLY, nullptr, nullptr, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
 }
 
 int h2mi_gate_program_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint32_t* degree_out, uint32_t* max_stack_out) {
@@ -1889,15 +1888,7 @@ int h2mi_shape_gate_program(const h2mi_constraint_system* cs, h2mi_expr_op* ops,
 
 int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed,
                              const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)H2MI_KEYGEN_VK_ONLY)) return H2MI_EINVAL;
-  *pk_out = nullptr;
-  if (h2mi_device_count() == 0) return H2MI_ENODEV;
-  return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_live_pks.insert(pk.get());
-    *pk_out = pk.release();
-  });
+  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY, gates, nullptr, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
 }
 
 int h2mi_lookup_program_check(const h2mi_constraint_system* cs, const h2mi_lookup_program* lookups, uint32_t* degree_out) {
@@ -1908,17 +1899,8 @@ int h2mi_lookup_program_check(const h2mi_constraint_system* cs, const h2mi_looku
 int h2mi_prover_keygen_exprs(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, uint64_t g_lagrange_handle,
                              const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
   if (!lookups) return h2mi_prover_keygen_gates(cs, gates, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
-  if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)(H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP)) ||
-      ((flags & H2MI_KEYGEN_LOGUP) && !lookups))
-    return H2MI_EINVAL;
-  *pk_out = nullptr;
-  if (h2mi_device_count() == 0) return H2MI_ENODEV;
-  return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_live_pks.insert(pk.get());
-    *pk_out = pk.release();
-  });
+  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP, gates, lookups, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies,
+                      flags, pk_out);
 }
 
 int h2mi_advice_phases_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
@@ -1930,17 +1912,8 @@ int h2mi_advice_phases_check(const h2mi_constraint_system* cs, const h2mi_gate_p
 int h2mi_prover_keygen_phases(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                               const h2mi_advice_phases* phases, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
                               size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  if (!cs || !gates || !phases || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)(H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP)) ||
-      ((flags & H2MI_KEYGEN_LOGUP) && !lookups))
-    return H2MI_EINVAL;
-  *pk_out = nullptr;
-  if (h2mi_device_count() == 0) return H2MI_ENODEV;
-  return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, phases, g_lagrange_handle, fixed, copies, n_copies, flags);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_live_pks.insert(pk.get());
-    *pk_out = pk.release();
-  });
+  return keygen_entry(cs, {gates, phases}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP, gates, lookups, phases, nullptr, nullptr, g_lagrange_handle, fixed, copies,
+                      n_copies, flags, pk_out);
 }
 
 int h2mi_shuffle_program_check(const h2mi_constraint_system* cs, const h2mi_shuffle_program* shuffles, uint32_t* degree_out) {
@@ -1972,20 +1945,8 @@ int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_p
                              const h2mi_logup_inputs* inputs, const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles,
                              uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags,
                              h2mi_pk_t* pk_out) {
-  if (!cs || !gates || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(unsigned)(H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP)) ||
-      ((flags & H2MI_KEYGEN_LOGUP) && !lookups))
-    return H2MI_EINVAL;
-  *pk_out = nullptr;
-  if (inputs && !lookups) return H2MI_EINVAL;
-  for (uint32_t l = 0; inputs && l < lookups->n_lookups && l < H2MI_MAX_LOOKUPS; l++)  // several sets are a logUp key's
-    if (inputs->n_inputs[l] != 1 && !(flags & H2MI_KEYGEN_LOGUP)) return H2MI_EINVAL;
-  if (h2mi_device_count() == 0) return H2MI_ENODEV;
-  return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, phases, g_lagrange_handle, fixed, copies, n_copies, flags, shuffles, inputs);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_live_pks.insert(pk.get());
-    *pk_out = pk.release();
-  });
+  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP, gates, lookups, phases, shuffles, inputs, g_lagrange_handle, fixed, copies,
+                      n_copies, flags, pk_out);
 }
 
 int h2mi_prover_pk_release(h2mi_pk_t pk) {
@@ -2268,10 +2229,10 @@ int h2mi_prover_buffer(h2mi_prover_t prover, uint32_t kind, uint32_t index, void
     case H2MI_BUF_SHPLONK_H2: return pick(p.h2_x, index, d_ptr_out, count_out);
     case H2MI_BUF_SHUFFLE_Z: return index < p.pk->n_shuffles ? pick(p.sf[index].z.value, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     case H2MI_BUF_SHUFFLE_Z_POLY: return index < p.pk->n_shuffles ? pick(p.sf[index].z.poly, 0, d_ptr_out, count_out) : H2MI_ERANGE;
-    case H2MI_BUF_SHUFFLE_INPUT: return index < p.pk->n_shuffles ? pick(p.sf[index].input, 0, d_ptr_out, count_out) : H2MI_ERANGE;
+    case H2MI_BUF_SHUFFLE_INPUT: return index < p.pk->n_shuffles ? pick(p.sf[index].c.input, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     case H2MI_BUF_LOGUP_M: return p.pk->logup && index < p.pk->cs.n_lookups ? pick(p.lk[index].a.value, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     case H2MI_BUF_LOGUP_PHI: return p.pk->logup && index < p.pk->cs.n_lookups ? pick(p.lk[index].z.value, 0, d_ptr_out, count_out) : H2MI_ERANGE;
-    case H2MI_BUF_SHUFFLE_TABLE: return index < p.pk->n_shuffles ? pick(p.sf[index].table, 0, d_ptr_out, count_out) : H2MI_ERANGE;
+    case H2MI_BUF_SHUFFLE_TABLE: return index < p.pk->n_shuffles ? pick(p.sf[index].c.table, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     default: return h2mi_prover_pk_buffer(p.pk, kind, index, d_ptr_out, count_out);
   }
 }

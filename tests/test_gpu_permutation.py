@@ -172,3 +172,39 @@ def test_copies_proofs_take_every_permutation_form(gpu, k, cycles):
     ws.release()
     keys.release()
     params.release()
+
+
+CENSUS = ("k_shuffle_numden", "k_lookup_numden", "k_lookup_flag", "k_logup_numden", "k_logup_numden_sets", "k_mulscan_local", "k_mulscan_offsets",
+          "k_mulscan_apply", "k_fr_inv_one", "k_perm_ratio", "k_perm_write_sets", "k_addscan_local", "k_addscan_offsets", "k_addscan_apply")
+
+
+@pytest.mark.parametrize("k,u", [(5, 22), (11, 1025)], ids=["one_tile", "two_tiles"])
+def test_single_output_entries_launch_census(gpu, k, u):
+    """The launches of the four entries with one output (shuffle product, dense lookup product, logUp sum of one set and of three) over
+    one scan tile of 1024 rows and over two: the fractions-to-ratios block they share (two multiplicative scans, one inversion, the
+    ratios), then a third multiplicative scan and the write, or for logUp the additive scan.  The values are arbitrary and nonzero
+    (tests/test_gpu_shuffle.py, test_gpu_lookup.py, test_gpu_logup.py and test_gpu_logup_sets.py check values); a lookup product
+    below 4096 rows flags nothing.  Names are matched as prefixes: k_logup_numden counts k_logup_numden_sets too, hence the difference."""
+    from halo2_scaffold_amd import plonk as gp
+
+    n, more = 1 << k, int(u > 1024)  # beyond one tile every scan adds its offsets pass, the multiplicative ones an apply pass as well
+    cols = [_upload(gpu, [c * n + i + 1 for i in range(n)]) for c in range(4)]
+    three = _upload(gpu, [7 * n + i for i in range(3 * n)])
+    out = _upload(gpu, [scale.SENTINEL] * n)
+    shared = {"k_fr_inv_one": 1, "k_perm_ratio": 1, "k_lookup_flag": 0}
+    product = dict(shared, k_mulscan_local=3, k_mulscan_offsets=3 * more, k_mulscan_apply=3 * more, k_perm_write_sets=1, k_addscan_local=0,
+                   k_addscan_offsets=0, k_addscan_apply=0, k_logup_numden=0, k_logup_numden_sets=0)
+    running_sum = dict(shared, k_mulscan_local=2, k_mulscan_offsets=2 * more, k_mulscan_apply=2 * more, k_perm_write_sets=0, k_addscan_local=1,
+                       k_addscan_offsets=more, k_addscan_apply=1, k_shuffle_numden=0, k_lookup_numden=0)
+    entries = {
+        "shuffle product": (lambda: gp.shuffle_product(k, cols[0], cols[1], 5, u, out), dict(product, k_shuffle_numden=1, k_lookup_numden=0)),
+        "lookup product": (lambda: gp.lookup_product(k, cols[0], cols[1], cols[2], cols[3], 5, 9, u, out), dict(product, k_shuffle_numden=0, k_lookup_numden=1)),
+        "logUp sum, one set": (lambda: gp.logup_sum(k, cols[0], cols[1], cols[2], 5, u, out), dict(running_sum, k_logup_numden=1, k_logup_numden_sets=0)),
+        "logUp sum, three sets": (lambda: gp.logup_sum_sets(k, three, 3, cols[1], cols[2], 5, u, out), dict(running_sum, k_logup_numden=0, k_logup_numden_sets=1)),
+    }
+    for what, (call, want) in entries.items():
+        launches = _launches(gpu, call, CENSUS)
+        launches["k_logup_numden"] -= launches["k_logup_numden_sets"]
+        _assert_form(launches, want, f"{what}, (k, u) = ({k}, {u})")
+    for b in cols + [three, out]:
+        b.free()
