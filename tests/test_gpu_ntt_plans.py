@@ -18,6 +18,7 @@ All comparisons are exact (np.array_equal on the words)."""
 import numpy as np
 import pytest
 
+from extreme_cases import EXTREME_WORDS  # raw Mont256 words (not values): all below r
 from oracle import bn254 as o, cref
 
 pytestmark = pytest.mark.gpu
@@ -26,10 +27,6 @@ THREADS = 16  # of the C oracle's transform
 FULL_SIZES = list(range(14, 26))
 OPTION_SIZES = [14, 17, 18, 19, 20, 21, 23]
 EXTREME_SIZES = [4, 7, 9, 10, 13, 16, 19, 20, 21]
-
-M232 = (1 << 232) - 1
-# raw Mont256 words (not values): all below r
-EXTREME_WORDS = [o.R - 1, (((o.R >> 232) - 1) << 232) | M232, M232, 0, 1, o.R >> 1]
 
 
 def _mont(v):
