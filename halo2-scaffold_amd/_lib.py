@@ -92,6 +92,7 @@ def _load():
         "h2mi_fr_kate_division_dev": ([vp, sz, vp, vp, vp, vp], C.c_int),
         "h2mi_fr_kate_division_multi_dev": ([vp, sz, vp, vp, vp, sz, vp, vp], C.c_int),
         "h2mi_fr_lincomb_dev": ([vp, vp, sz, sz, vp, vp], C.c_int),
+        "h2mi_fr_gwc_witness_dev": ([vp, vp, vp, vp, vp, sz, sz, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_standard_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_permutation_product_dev": ([vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_lookup_permute_dev": ([vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64p, vp], C.c_int),
@@ -164,6 +165,8 @@ def _load():
         "h2mi_prover_evaluations": ([vp, vp, vp], C.c_int),
         "h2mi_prover_shplonk_quotient": ([vp, vp, vp, vp], C.c_int),
         "h2mi_prover_shplonk_open": ([vp, vp, vp], C.c_int),
+        "h2mi_prover_gwc_num_points": ([vp, vp], C.c_int),
+        "h2mi_prover_gwc_open": ([vp, vp, vp], C.c_int),
         "h2mi_batch_create": ([vp, C.c_uint32, C.POINTER(vp)], C.c_int),
         "h2mi_batch_destroy": ([vp], C.c_int),
         "h2mi_batch_quotient": ([vp, vp, vp], C.c_int),
@@ -171,6 +174,8 @@ def _load():
         "h2mi_batch_evaluations": ([vp, vp, vp], C.c_int),
         "h2mi_batch_shplonk_quotient": ([vp, vp, vp, vp], C.c_int),
         "h2mi_batch_shplonk_open": ([vp, vp, vp], C.c_int),
+        "h2mi_batch_gwc_num_points": ([vp, vp], C.c_int),
+        "h2mi_batch_gwc_open": ([vp, vp, vp], C.c_int),
         "h2mi_prover_buffer": ([vp, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(sz)], C.c_int),
         "h2mi_prover_pk_buffer": ([vp, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(sz)], C.c_int),
     }

@@ -152,22 +152,9 @@ __device__ __forceinline__ fe wave_suffix_fe(fe v) {
   }
   return v;
 }
-__global__ void __launch_bounds__(256) k_kate_local_multi(const fe* a, size_t n, KateRoots R, uint32_t nblocks, fe* local, fe* totals) {
-  __shared__ fe tile[KATE_TILE + 8];
-  __shared__ fe wtot[4];
-  const uint32_t tid = threadIdx.x, r = blockIdx.y, lane = tid & 63u, wave = tid >> 6;
-  const size_t base = (size_t)blockIdx.x * KATE_TILE;
-  local += (size_t)r * n;
-  totals += (size_t)r * nblocks;
-  for (uint32_t q = 0; q < 4; q++) {  // coalesced: element base + tid + 256 q
-    const uint32_t loc = tid + 256 * q;
-    fe o = fe_zero();
-    if (base + loc < n) {
-      f29 x = f29_mul<F9>(load_unpack(&a[base + loc]), kate_small_power(R.lo[r], R.hi[r], R.h[r], loc));
-      f29_pack(f29_reduce_canonical<F9>(x), o.v);
-    }
-    tile[loc] = o;
-  }
+// pass 1 behind the tile fill (tile[loc] = a_(base + loc) b^loc, canonical; zero beyond n): the suffix scan in LDS, local' and the tile's total
+__device__ __forceinline__ void kate_tile_suffix(fe* tile, fe* wtot, size_t base, size_t n, fe* local, fe* totals) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   __syncthreads();
   // a thread owns 4 consecutive elements: local suffix, a suffix scan of the thread totals inside the wavefront (shuffles), the four
   // wavefront totals through LDS
@@ -188,6 +175,22 @@ __global__ void __launch_bounds__(256) k_kate_local_multi(const fe* a, size_t n,
     if (base + loc < n) fe_store(&local[base + loc], tile[loc]);
   }
   if (tid == 0) fe_store(&totals[blockIdx.x], tile[0]);
+}
+__global__ void __launch_bounds__(256) k_kate_local_multi(const fe* a, size_t n, KateRoots R, uint32_t nblocks, fe* local, fe* totals) {
+  __shared__ fe tile[KATE_TILE + 8];
+  __shared__ fe wtot[4];
+  const uint32_t tid = threadIdx.x, r = blockIdx.y;
+  const size_t base = (size_t)blockIdx.x * KATE_TILE;
+  for (uint32_t q = 0; q < 4; q++) {  // coalesced: element base + tid + 256 q
+    const uint32_t loc = tid + 256 * q;
+    fe o = fe_zero();
+    if (base + loc < n) {
+      f29 x = f29_mul<F9>(load_unpack(&a[base + loc]), kate_small_power(R.lo[r], R.hi[r], R.h[r], loc));
+      f29_pack(f29_reduce_canonical<F9>(x), o.v);
+    }
+    tile[loc] = o;
+  }
+  kate_tile_suffix(tile, wtot, base, n, local + (size_t)r * n, totals + (size_t)r * nblocks);
 }
 // pass 2, one workgroup of 1024 threads per root: the tile offsets O'_t, and the root's weighted inverse powers ct[loc] = c b^-loc
 // (Montgomery-2^261) that pass 3 multiplies by.  A thread owns `per` consecutive tiles.
@@ -264,6 +267,71 @@ __global__ void __launch_bounds__(256) k_lincomb(LincombArgs args, size_t n, fe*
   fe o;
   f29_pack(f29_reduce_loose<F9>(acc), o.v);  // < 10p -> canonical without a multiplication
   fe_store(&out[i], o);
+}
+
+// ---- ProverGWC's witness polynomials: W_r = (sum_j c_rj p_rj) / (X - z_r) for up to KATE_MULTI_MAX points per launch,
+// on the tile scheme above with blockIdx.y = point.  Pass 1 forms the sum in registers (k_lincomb's groups of three) and goes
+// straight into the suffix scan: the summed polynomial is never stored.  Pass 2 is k_kate_offsets_multi with weight one; pass 3
+// writes one quotient per point.
+// The launch's terms, all points behind one another: point r owns terms first[r] .. first[r + 1) - 1.  GWC_TERMS = 72 is the cap of a
+// launch AND of one point: 72 x (8 B pointer + 36 B scalar) + 20 B = 3188 B, beside KateRoots (296 B) and 40 B of plain arguments
+// inside the 4 KB kernel-argument block.  A point with more terms enters with its sum made by k_lincomb first (gwc_witness).
+constexpr uint32_t GWC_TERMS = 72;
+struct GwcTerms {
+  const fe* poly[GWC_TERMS];
+  f29 scalar[GWC_TERMS];  // Montgomery-2^261 limbs, converted on the host (as LincombArgs)
+  uint32_t first[KATE_MULTI_MAX + 1];
+};
+struct GwcOuts {
+  fe* out[KATE_MULTI_MAX];
+};
+static_assert(sizeof(GwcTerms) + sizeof(KateRoots) + 64 <= 4096, "the kernel-argument block is 4 KB");
+__global__ void __launch_bounds__(256) k_gwc_local(GwcTerms T, size_t n, KateRoots R, uint32_t nblocks, fe* local, fe* totals) {
+  __shared__ fe tile[KATE_TILE + 8];
+  __shared__ fe wtot[4];
+  const uint32_t tid = threadIdx.x, r = blockIdx.y;
+  const size_t base = (size_t)blockIdx.x * KATE_TILE;
+  const uint32_t k0 = T.first[r], k1 = T.first[r + 1];
+  for (uint32_t q = 0; q < 4; q++) {  // coalesced: element base + tid + 256 q of every term
+    const uint32_t loc = tid + 256 * q;
+    fe o = fe_zero();
+    if (base + loc < n) {
+      const size_t i = base + loc;
+      f29 acc = f29_zero();
+      uint32_t k = k0;
+      for (; k + 3 <= k1; k += 3) {
+        f29 t = f29_mul3<F9>(load_unpack(&T.poly[k][i]), T.scalar[k], load_unpack(&T.poly[k + 1][i]), T.scalar[k + 1], load_unpack(&T.poly[k + 2][i]),
+                             T.scalar[k + 2]);
+        acc = f29_normalize(f29_add(acc, t));  // each group < 1.02p (k_lincomb's bound): at the cap 24 groups, < 24.5p < 2^259
+      }
+      if (k1 - k == 2)
+        acc = f29_normalize(f29_add(acc, f29_mul2<F9>(load_unpack(&T.poly[k][i]), T.scalar[k], load_unpack(&T.poly[k + 1][i]), T.scalar[k + 1])));
+      else if (k1 - k == 1)
+        acc = f29_normalize(f29_add(acc, f29_mul<F9>(load_unpack(&T.poly[k][i]), T.scalar[k])));
+      // normalized, limb 8 < 2^27: inside the multiplication's contract; times a canonical power < (1 + 0.0059 * 24.5) p < 1.15p
+      f29 x = f29_mul<F9>(acc, kate_small_power(R.lo[r], R.hi[r], R.h[r], loc));
+      f29_pack(f29_reduce_canonical<F9>(x), o.v);
+    }
+    tile[loc] = o;
+  }
+  kate_tile_suffix(tile, wtot, base, n, local + (size_t)r * n, totals + (size_t)r * nblocks);
+}
+// pass 3, one quotient per point: out_r[i] = (local'_r[j] + O'_r[tile(j)]) * ct_r[loc(j)], j = i + 1 < n; out_r[n - 1] = 0
+__global__ void __launch_bounds__(256) k_gwc_finish(const fe* local, const fe* offsets, const fe* ct, size_t n, uint32_t nblocks, GwcOuts O) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t r = blockIdx.y;
+  if (i >= n) return;
+  fe* q = O.out[r];
+  if (i + 1 == n) {
+    fe_store(&q[i], fe_zero());
+    return;
+  }
+  const size_t j = i + 1;
+  const uint32_t t = (uint32_t)(j / KATE_TILE), loc = (uint32_t)(j % KATE_TILE);
+  const f29 x = f29_unpack(fe_add<Fr>(fe_load(&local[(size_t)r * n + j]), fe_load(&offsets[(size_t)r * nblocks + t])).v);
+  fe o;
+  f29_pack(f29_reduce_loose<F9>(f29_mul<F9>(x, load_unpack(&ct[(size_t)r * KATE_TILE + loc]))), o.v);
+  fe_store(&q[i], o);
 }
 
 // out[i] = value
@@ -572,6 +640,117 @@ int h2mi_fr_lincomb_dev(const void* const* d_polys, const uint64_t* scalars, siz
   return H2MI_OK;
 }
 
+
+// out_g = (sum_j scalars_gj poly_gj) / (X - root_g), n coefficients each (the last one zero): slices of up to KATE_MULTI_MAX points and
+// GWC_TERMS terms, three launches per slice; a group of more than GWC_TERMS terms is summed by k_lincomb into scratch first and enters
+// as one operand of weight one (every partial sum is canonical: the split changes no bit)
+static int gwc_witness(const void* const* d_polys, const uint64_t* scalars, const size_t* group_counts, const uint64_t* roots, const uint64_t* roots_inv,
+                       size_t ngroups, size_t n, void* const* d_outs, hipStream_t s) {
+  uint32_t log_n = 0;
+  while (((size_t)1 << log_n) < n) log_n++;
+  if (log_n > 30) return H2MI_ERANGE;
+  std::vector<uint64_t> bases(8 * ngroups);  // roots, then inverses: the missing tables of all points at once
+  memcpy(bases.data(), roots, 32 * ngroups);
+  memcpy(bases.data() + 4 * ngroups, roots_inv, 32 * ngroups);
+  std::vector<PowTab> tabs(2 * ngroups);
+  int rc = get_powtabs(bases.data(), 2 * ngroups, log_n, s, tabs.data());
+  if (rc) return rc;
+  const uint32_t nblocks = (uint32_t)((n + KATE_TILE - 1) / KATE_TILE), M = KATE_MULTI_MAX;
+  size_t presums = 0;
+  for (size_t g = 0; g < ngroups; g++) presums += group_counts[g] > GWC_TERMS;
+  const size_t slice_elems = M * (n + 2 * (size_t)nblocks + KATE_TILE);
+  rc = ensure_tmp(slice_elems + presums * n + 16, s);
+  if (rc) return rc;
+  fe* local = tmp_base();
+  fe* totals = local + M * n;
+  fe* offsets = totals + M * nblocks;
+  fe* ct = offsets + M * nblocks;
+  fe* presum = ct + M * KATE_TILE;
+  const f29 one = f29_const<F9>(F9::ONE);
+  const fe one_c = h_canon(one);
+  // the terms of group g as the fused pass takes them: its own, or its k_lincomb sum
+  struct Term {
+    const fe* poly;
+    f29 scalar;
+  };
+  std::vector<std::vector<Term>> terms(ngroups);
+  size_t off = 0;
+  for (size_t g = 0; g < ngroups; off += group_counts[g], g++) {
+    const size_t cnt = group_counts[g];
+    if (cnt <= GWC_TERMS) {
+      for (size_t j = 0; j < cnt; j++) terms[g].push_back({(const fe*)d_polys[off + j], f29_from_mont256<F9>(host_fe(scalars + 4 * (off + j)).v)});
+      continue;
+    }
+    for (size_t j = 0; j < cnt;) {  // LINCOMB_MAX operands per launch, the running sum re-entering with weight one
+      LincombArgs args;
+      memset(&args, 0, sizeof(args));
+      if (j) {
+        args.poly[0] = presum;
+        args.scalar[0] = one;
+        args.count = 1;
+      }
+      for (; j < cnt && args.count < LINCOMB_MAX; j++, args.count++) {
+        args.poly[args.count] = (const fe*)d_polys[off + j];
+        args.scalar[args.count] = f29_from_mont256<F9>(host_fe(scalars + 4 * (off + j)).v);
+      }
+      H2_LAUNCH("k_lincomb", k_lincomb, ceil_div_u32(n, 256), 256, 0, s, args, n, presum);
+    }
+    terms[g].push_back({presum, one});
+    presum += n;
+  }
+  for (size_t g0 = 0; g0 < ngroups;) {
+    GwcTerms T;
+    GwcOuts O;
+    KateRoots R;
+    memset(&T, 0, sizeof(T));
+    memset(&O, 0, sizeof(O));
+    memset(&R, 0, sizeof(R));
+    uint32_t m = 0, nt = 0;
+    for (; g0 + m < ngroups && m < M && nt + terms[g0 + m].size() <= GWC_TERMS; m++) {
+      const size_t g = g0 + m;
+      const PowTab &pb = tabs[g], &pi = tabs[ngroups + g];
+      R.lo[m] = pb.lo; R.hi[m] = pb.hi; R.h[m] = pb.h;
+      R.ilo[m] = pi.lo; R.ihi[m] = pi.hi; R.ih[m] = pi.h;
+      R.c[m] = one_c;  // weight one, Montgomery-2^261
+      O.out[m] = (fe*)d_outs[g];
+      T.first[m] = nt;
+      for (const Term& t : terms[g]) {
+        T.poly[nt] = t.poly;
+        T.scalar[nt++] = t.scalar;
+      }
+    }
+    for (uint32_t r = m; r <= M; r++) T.first[r] = nt;
+    R.m = m;
+    H2_LAUNCH("k_gwc_local", k_gwc_local, dim3(nblocks, m), 256, 0, s, T, n, R, nblocks, local, totals);
+    H2_LAUNCH("k_kate_offsets", k_kate_offsets_multi, m, 1024, 0, s, (const fe*)totals, nblocks, n, R, offsets, ct);
+    H2_LAUNCH("k_gwc_finish", k_gwc_finish, dim3(ceil_div_u32(n, 256), m), 256, 0, s, (const fe*)local, (const fe*)offsets, (const fe*)ct, n, nblocks, O);
+    g0 += m;
+  }
+  return release_tmp(s);
+}
+
+int h2mi_fr_gwc_witness_dev(const void* const* d_polys, const uint64_t* scalars, const size_t* group_counts, const uint64_t* roots,
+                            const uint64_t* roots_inv, size_t ngroups, size_t n, void* const* d_outs, h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_polys || !scalars || !group_counts || !roots || !roots_inv || !d_outs || n < 2 || ngroups == 0) return H2MI_EINVAL;
+  size_t total = 0;
+  for (size_t g = 0; g < ngroups; g++) {
+    const uint64_t *z = roots + 4 * g, *zi = roots_inv + 4 * g;
+    if (group_counts[g] == 0 || !d_outs[g] || !(z[0] | z[1] | z[2] | z[3]) || !(zi[0] | zi[1] | zi[2] | zi[3])) return H2MI_EINVAL;
+    total += group_counts[g];
+  }
+  for (size_t i = 0; i < total; i++)
+    if (!d_polys[i]) return H2MI_EINVAL;
+  try {  // the term lists are host vectors: no exception crosses the ABI
+    std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+    CallScope scope_;
+    return gwc_witness(d_polys, scalars, group_counts, roots, roots_inv, ngroups, n, d_outs, pick_stream(stream));
+  } catch (const std::bad_alloc&) {
+    return H2MI_ENOMEM;
+  } catch (...) {
+    return H2MI_EINVAL;
+  }
+}
 
 int h2mi_fr_mul_dev(const void* d_a, const void* d_b, size_t n, void* d_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();

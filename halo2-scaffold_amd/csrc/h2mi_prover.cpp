@@ -843,6 +843,8 @@ uint32_t max_phase_points(const h2mi_pk_s& pk) {
   return std::max({cs.n_advice, (pk.logup ? 1 : 2) * cs.n_lookups, pk.n_sets + cs.n_lookups + pk.n_shuffles + 1, cs.degree - 1, 8u});
 }
 
+size_t gwc_num_points(const h2mi_pk_s& pk);  // the commitments of a GWC tail (below, with the phase)
+
 std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t gl, size_t lo, size_t cnt) {
   if (pk->vk_only) throw Error(H2MI_EINVAL, "prover_create: the key was built with H2MI_KEYGEN_VK_ONLY");
   if (cnt == 0 || lo + cnt > pk->n) throw Error(H2MI_ERANGE, "prover_create: base slice");
@@ -887,7 +889,7 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
   p.random_poly = vec(n);
   p.h = vec(ext);
   p.h_poly = vec(n);
-  p.points = vec(3 * (size_t)max_phase_points(*pk));  // 96 B per commitment of the largest phase
+  p.points = vec(3 * std::max<size_t>(max_phase_points(*pk), gwc_num_points(*pk)));  // 96 B per commitment of the largest phase (GWC's tail included)
   for (int i = 0; i < 3; i++) {
     p.nx[i] = vec(n);
     p.tmp[i] = vec(n);
@@ -1763,6 +1765,81 @@ void phase_shplonk_open(const Circuits& all, const Fr& u, uint64_t* point_out) {
   finish_members(all);  // the proof is complete; the next one starts with h2mi_prover_advice
 }
 
+// ---- ProverGWC (poly/kzg/multiopen/gwc, restated from memory: DESIGN.md 4.5) — the other ending of a proof ----------------------------
+// the opening points of a key's query list: its distinct rotations modulo 2^k (the queries of phase_evaluations, by the key alone)
+size_t gwc_num_points(const h2mi_pk_s& pk) {
+  const h2mi_constraint_system& cs = pk.cs;
+  const int64_t n = (int64_t)pk.n;
+  std::vector<int64_t> rots = {0};  // h and the random polynomial, at least
+  auto add = [&](int64_t r) {
+    r = ((r % n) + n) % n;
+    if (std::find(rots.begin(), rots.end(), r) == rots.end()) rots.push_back(r);
+  };
+  for (uint32_t i = 0; i < cs.n_advice_queries; i++) add(cs.advice_queries[i].rotation);
+  for (uint32_t i = 0; i < cs.n_fixed_queries; i++) add(cs.fixed_queries[i].rotation);
+  if (pk.n_sets || cs.n_lookups || pk.n_shuffles) add(1);
+  if (pk.n_sets > 1) add(-(int64_t)(cs.blinding_factors + 1));
+  if (cs.n_lookups && !pk.logup) add(-1);
+  return rots.size();
+}
+// W_i lives in the SHPLONK scratch (a proof uses one ending): q[0], s[0], q[1], s[1], ..
+Dev& gwc_w(h2mi_prover_s& p, size_t i) {
+  std::vector<Dev>& v = i % 2 ? p.s : p.q;
+  while (v.size() <= i / 2) v.push_back(vec(p.pk->n));
+  return v[i / 2];
+}
+
+// v in, [W_0] .. [W_(P-1)] out: group the queries by point in order of first appearance, W_i = (sum_j v^j p_ij) / (X - z_i) — the
+// division drops the remainder sum_j v^j e_ij, so the evaluations stay on the host — and commit the W_i as one phase
+void phase_gwc_open(const Circuits& all, const Fr& v, uint64_t* points_out) {
+  h2mi_prover_s& p = *all[0];  // the queries name every circuit's polynomials; the scratch and the commitments are the leader's
+  const size_t n = p.pk->n;
+  require_phase(p, EVALUATIONS);
+  require_members(all);
+  p.phase = IDLE;
+  if (!points_out) throw Error(H2MI_EINVAL, "points_out");
+  std::vector<Fr> pts;
+  std::vector<std::vector<const DeviceVec*>> groups;
+  for (const ProverQuery& q : p.queries) {
+    size_t g = std::find(pts.begin(), pts.end(), q.point) - pts.begin();
+    if (g == pts.size()) {
+      pts.push_back(q.point);
+      groups.emplace_back();
+    }
+    groups[g].push_back(q.poly);
+  }
+  const size_t P = pts.size();
+  if (P != gwc_num_points(*p.pk) || contains(pts, fr_zero())) throw Error(H2MI_EINVAL, "gwc: the opening points coincide or vanish");
+  const std::vector<Fr> inv = fr::batch_invert(pts);
+  std::vector<const void*> polys;
+  std::vector<Fr> scalars;
+  std::vector<size_t> counts;
+  std::vector<void*> outs;
+  for (size_t i = 0; i < P; i++) {
+    Fr vp = fr::ONE;
+    for (const DeviceVec* poly : groups[i]) {
+      polys.push_back(poly->p);
+      scalars.push_back(vp);
+      vp = fr::mul(vp, v);
+    }
+    counts.push_back(groups[i].size());
+    outs.push_back(gwc_w(p, i)->p);
+  }
+  check(h2mi_fr_gwc_witness_dev(polys.data(), (const uint64_t*)scalars.data(), counts.data(), (const uint64_t*)pts.data(), (const uint64_t*)inv.data(), P, n,
+                                outs.data(), nullptr),
+        "gwc_witness");
+  // one phase of P commitments; a combiner's buffers hold the largest of the other phases, so there the phase goes in that many at a time
+  const size_t slots = p.d_partial ? max_phase_points(*p.pk) : P;
+  for (size_t c0 = 0; c0 < P; c0 += slots) {
+    const size_t cnt = std::min(slots, P - c0);
+    std::vector<const void*> cols;
+    for (size_t i = 0; i < cnt; i++) cols.push_back(p.col(*gwc_w(p, c0 + i)));
+    p.commit_phase(false, cols, 0, /*sparse=*/false, /*inorder=*/true);
+    p.read_points(cnt, points_out + 8 * c0);
+  }
+  finish_members(all);  // the proof is complete; the next one starts with h2mi_prover_advice
+}
+
 Fr load_fr(const uint64_t* l) {
   Fr a;
   std::memcpy(a.l, l, 32);
@@ -2117,6 +2194,17 @@ int h2mi_prover_shplonk_open(h2mi_prover_t prover, const uint64_t u[4], uint64_t
   if (!u || prover->batch) return H2MI_EINVAL;
   return guarded([&] { phase_shplonk_open({prover}, load_fr(u), point_out); });
 }
+int h2mi_prover_gwc_num_points(h2mi_prover_t prover, size_t* count_out) {
+  if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
+  if (!count_out) return H2MI_EINVAL;
+  *count_out = gwc_num_points(*prover->pk);
+  return H2MI_OK;
+}
+int h2mi_prover_gwc_open(h2mi_prover_t prover, const uint64_t v[4], uint64_t* points_out) {
+  if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
+  if (!v || prover->batch) return H2MI_EINVAL;
+  return guarded([&] { phase_gwc_open({prover}, load_fr(v), points_out); });
+}
 
 // ---- several circuits per proof ----------------------------------------------------------------------------------------------------
 int h2mi_batch_create(const h2mi_prover_t* members, uint32_t n, h2mi_batch_t* batch_out) {
@@ -2201,6 +2289,17 @@ int h2mi_batch_shplonk_open(h2mi_batch_t batch, const uint64_t u[4], uint64_t po
   if (!u) return H2MI_EINVAL;
   return guarded([&] { phase_shplonk_open(batch->members, load_fr(u), point_out); });
 }
+int h2mi_batch_gwc_num_points(h2mi_batch_t batch, size_t* count_out) {
+  if (!alive(g_live_batches, batch)) return H2MI_EHANDLE;
+  if (!count_out) return H2MI_EINVAL;
+  *count_out = gwc_num_points(*batch->members[0]->pk);
+  return H2MI_OK;
+}
+int h2mi_batch_gwc_open(h2mi_batch_t batch, const uint64_t v[4], uint64_t* points_out) {
+  if (!alive(g_live_batches, batch)) return H2MI_EHANDLE;
+  if (!v) return H2MI_EINVAL;
+  return guarded([&] { phase_gwc_open(batch->members, load_fr(v), points_out); });
+}
 
 int h2mi_prover_buffer(h2mi_prover_t prover, uint32_t kind, uint32_t index, void** d_ptr_out, size_t* count_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
@@ -2233,6 +2332,7 @@ int h2mi_prover_buffer(h2mi_prover_t prover, uint32_t kind, uint32_t index, void
     case H2MI_BUF_LOGUP_M: return p.pk->logup && index < p.pk->cs.n_lookups ? pick(p.lk[index].a.value, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     case H2MI_BUF_LOGUP_PHI: return p.pk->logup && index < p.pk->cs.n_lookups ? pick(p.lk[index].z.value, 0, d_ptr_out, count_out) : H2MI_ERANGE;
     case H2MI_BUF_SHUFFLE_TABLE: return index < p.pk->n_shuffles ? pick(p.sf[index].c.table, 0, d_ptr_out, count_out) : H2MI_ERANGE;
+    case H2MI_BUF_GWC_W: return index < gwc_num_points(*p.pk) ? pick(index % 2 ? p.s : p.q, index / 2, d_ptr_out, count_out) : H2MI_ERANGE;
     default: return h2mi_prover_pk_buffer(p.pk, kind, index, d_ptr_out, count_out);
   }
 }

@@ -594,15 +594,17 @@ class _PhasedWitness:
         self.advice = lambda challenges: (first.pop() if first else synthesize(challenges)).advice
 
 
-def create_proof(params: ParamsKZG, keys: Keys, asg, seed: int, transcript=None, trace: dict = None, ws: Workspace = None) -> bytes:
+def create_proof(params: ParamsKZG, keys: Keys, asg, seed: int, transcript=None, trace: dict = None, ws: Workspace = None,
+                 multiopen: str = "shplonk") -> bytes:
     """create_proof for one circuit: the transcript on this side, the phase calls into the library (flex.create_proof's body: the
     phases do not depend on how the gates were given; theta reaches the lookups phase through engine.Prover.drive).
     asg: an Assignment, or — a circuit whose witness reads challenges — a callable synthesize(challenges) -> Assignment, called once
     per advice phase with the challenges squeezed so far (None for the others); only that phase's advice columns are taken from
-    what it returns, as the crate does."""
+    what it returns, as the crate does.  multiopen: "shplonk" (ProverSHPLONK) or "gwc" (ProverGWC) — the crate's type parameter."""
+    engine.check_multiopen(multiopen)
     if callable(asg):
         asg = _PhasedWitness(asg, len(keys.cs.challenge_phase))
-    return flex.create_proof(params, keys, asg, seed, transcript=transcript, trace=trace, ws=ws)
+    return flex.create_proof(params, keys, asg, seed, transcript=transcript, trace=trace, ws=ws, multiopen=multiopen)
 
 
 class BatchWorkspace:
@@ -624,14 +626,15 @@ class BatchWorkspace:
 
 
 def prove_many(pk, assignments, instances=None, seeds=None, params: ParamsKZG = None, transcript=None, trace: dict = None, ws: BatchWorkspace = None,
-               hooks: dict = None) -> bytes:
+               hooks: dict = None, multiopen: str = "shplonk") -> bytes:
     """create_proof(&params, &pk, &[circuit_0, .., circuit_(N-1)], &[instances_0, ..], rng, &mut transcript): ONE proof of N <= 8 circuits
     against one key — the fixed and sigma columns, the random polynomial and h(X) opened once, one quotient, one SHPLONK round.
     assignments: per circuit an Assignment or a callable synthesize(challenges) -> Assignment as create_proof takes them (a phase's
     commitments of every circuit precede that phase's challenges).  instances: per circuit its public inputs (default: each
     assignment's own).  seeds: per circuit the seed of its blinding streams, at least 8 apart (the library refuses closer ones: two
     columns of one proof would share their blinding); default 1, 9, 17, ...  params: the SRS (default: the one the key was made with).
-    `prove` / `create_proof` stay the single-circuit route; a batch of one gives the same bytes."""
+    `prove` / `create_proof` stay the single-circuit route; a batch of one gives the same bytes.  multiopen: as create_proof takes it."""
+    engine.check_multiopen(multiopen)
     params = params if params is not None else pk.params
     n_challenges = len(getattr(getattr(pk, "cs", None), "challenge_phase", ()))
     wits = [_PhasedWitness(a, n_challenges) if callable(a) else a for a in assignments]
@@ -645,7 +648,7 @@ def prove_many(pk, assignments, instances=None, seeds=None, params: ParamsKZG = 
         for inst in instances:  # KZG: every circuit's public inputs are hashed as scalars, in circuit order
             for v in inst:
                 transcript.common_scalar(flex._m(v))
-        ws.batch.drive([w.advice for w in wits], instances, seeds, transcript, trace, hooks)
+        ws.batch.drive([w.advice for w in wits], instances, seeds, transcript, trace, hooks, multiopen=multiopen)
         return transcript.finalize()
     finally:
         if own:

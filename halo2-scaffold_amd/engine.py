@@ -31,7 +31,7 @@ MAX_ADVICE, MAX_CHALLENGES, MAX_ADVICE_PHASES = 64, 16, 3
 # h2mi_prover_buffer kinds
 (BUF_ADVICE, BUF_ADVICE_POLY, BUF_ADVICE_COSET, BUF_INSTANCE, BUF_PERM_Z, BUF_PERM_Z_POLY, BUF_PERM_Z_COSET, BUF_LOOKUP_PERMUTED_INPUT,
  BUF_LOOKUP_PERMUTED_TABLE, BUF_LOOKUP_Z, BUF_RANDOM_POLY, BUF_H, BUF_H_POLY, BUF_SHPLONK_H, BUF_SHPLONK_H2, BUF_SHUFFLE_Z, BUF_SHUFFLE_Z_POLY,
- BUF_SHUFFLE_INPUT, BUF_SHUFFLE_TABLE, BUF_LOGUP_M, BUF_LOGUP_PHI) = range(21)
+ BUF_SHUFFLE_INPUT, BUF_SHUFFLE_TABLE, BUF_LOGUP_M, BUF_LOGUP_PHI, BUF_GWC_W) = range(22)
 (PKBUF_FIXED, PKBUF_FIXED_POLY, PKBUF_FIXED_COSET, PKBUF_SIGMA, PKBUF_SIGMA_POLY, PKBUF_SIGMA_COSET, PKBUF_L0_COSET, PKBUF_L_LAST_COSET,
  PKBUF_L_ACTIVE_COSET) = range(64, 73)
 
@@ -377,6 +377,14 @@ class _PhaseCounts(C.Structure):
 _COMBINE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t)
 
 
+MULTIOPEN = ("shplonk", "gwc")  # the multi-opening schemes create_proof ends with (the crate's type parameter P: ProverSHPLONK / ProverGWC)
+
+
+def check_multiopen(multiopen: str) -> None:
+    if multiopen not in MULTIOPEN:
+        raise ValueError(f"multiopen must be one of {MULTIOPEN}, not {multiopen!r}")
+
+
 class Prover:
     """one h2mi_prover_t: the device buffers, streams and phase state of one create_proof at a time, reused from proof to proof
     (the reference's drivers prove repeatedly against one pk / SRS, e.g. examples/linear_regression.rs:126-195).
@@ -450,7 +458,14 @@ class Prover:
             return self.check(theta, n.value)
         return list(out[:n.value])
 
-    def drive(self, advice, instance, seed: int, transcript: Blake2bWrite, trace: dict = None, witness_check: str = None):
+    def gwc_num_points(self) -> int:
+        """h2mi_prover_gwc_num_points: the commitments of a GWC tail — the distinct rotations of the key's queries"""
+        n = C.c_size_t()
+        check(lib.h2mi_prover_gwc_num_points(self.handle, C.byref(n)), "gwc_num_points")
+        return n.value
+
+    def drive(self, advice, instance, seed: int, transcript: Blake2bWrite, trace: dict = None, witness_check: str = None,
+              multiopen: str = "shplonk"):
         """create_proof between the transcript's challenges.  advice: one {row: value} dict or dense list per advice column;
         instance: the public inputs (integers).  The caller has hashed vk.transcript_repr and the public inputs already.
         A key with several advice phases or with challenges: `advice` may be a callable, synthesize(challenges) -> such a list,
@@ -458,7 +473,10 @@ class Prover:
         only that phase's columns are taken [RECALL halo2_proofs v2023_02_02 plonk/prover.rs]; a plain list serves every phase.
         witness_check: "only" — run the witness check (self.check with the transcript's theta) once the advice is committed and return its
         failures without going on (the next proof starts at the advice as usual); "also" — run it and prove on: the bytes are those
-        of a proof without it.  Either way trace["check"] holds the failures."""
+        of a proof without it.  Either way trace["check"] holds the failures.
+        multiopen: "shplonk" (ProverSHPLONK: two points) or "gwc" (ProverGWC: one point per distinct opening point); the bytes before
+        the opening argument do not depend on it."""
+        check_multiopen(multiopen)
         c, h, pts = self.counts, self.handle, self._points
         pp = pts.ctypes.data
         sq = transcript.squeeze_challenge  # 4 Montgomery limbs
@@ -524,13 +542,20 @@ class Prover:
         for e in self._evals:
             transcript.write_scalar(e)
         mark("evaluations written")
-        sy, sv = sq(), sq()  # ProverSHPLONK: y, v
-        self._phase(lib.h2mi_prover_shplonk_quotient(h, sy.ctypes.data, sv.ctypes.data, pp), "shplonk quotient")
-        write_points(1)
-        su = sq()
-        self._phase(lib.h2mi_prover_shplonk_open(h, su.ctypes.data, pp), "shplonk open")
-        write_points(1)
-        mark("shplonk done")
+        if multiopen == "gwc":  # ProverGWC: v, then every [W_i]
+            gv, w = sq(), np.zeros((self.gwc_num_points(), 8), dtype=np.uint64)
+            self._phase(lib.h2mi_prover_gwc_open(h, gv.ctypes.data, w.ctypes.data), "gwc open")
+            for pt in w:
+                transcript.write_point(pt)
+            mark("gwc done")
+        else:
+            sy, sv = sq(), sq()  # ProverSHPLONK: y, v
+            self._phase(lib.h2mi_prover_shplonk_quotient(h, sy.ctypes.data, sv.ctypes.data, pp), "shplonk quotient")
+            write_points(1)
+            su = sq()
+            self._phase(lib.h2mi_prover_shplonk_open(h, su.ctypes.data, pp), "shplonk open")
+            write_points(1)
+            mark("shplonk done")
         if trace is not None:
             m = F.fr_from_mont_limbs
             trace.update(theta=m(theta), beta=m(beta), gamma=m(gamma), y=m(y), x=m(x),
@@ -561,12 +586,19 @@ class Batch:
         self.n_evaluations = n.value
         self._evals = np.zeros((max(n.value, 1), 4), dtype=np.uint64)
 
-    def drive(self, advices, instances, seeds, transcript: Blake2bWrite, trace: dict = None, hooks: dict = None):
+    def gwc_num_points(self) -> int:
+        n = C.c_size_t()
+        check(lib.h2mi_batch_gwc_num_points(self.handle, C.byref(n)), "batch gwc_num_points")
+        return n.value
+
+    def drive(self, advices, instances, seeds, transcript: Blake2bWrite, trace: dict = None, hooks: dict = None, multiopen: str = "shplonk"):
         """create_proof for the batch between the transcript's challenges.  advices[i] / instances[i] / seeds[i]: what Prover.drive
         takes, for circuit i (a callable synthesize(challenges) per circuit when the witness reads challenges: every circuit's
         commitments of a phase precede that phase's challenges, which all circuits then read).  The caller has hashed
         vk.transcript_repr and every circuit's public inputs, in circuit order.  hooks (tests): "products_done"(batch) is called when
-        every member has run its products, "y"(limbs) -> the y handed to the library instead of the transcript's."""
+        every member has run its products, "y"(limbs) -> the y handed to the library instead of the transcript's.
+        multiopen: as Prover.drive takes it."""
+        check_multiopen(multiopen)
         ms, hooks = self.members, hooks or {}
         lead = ms[0]
         c, pc = lead.counts, lead.phase_counts
@@ -637,12 +669,17 @@ class Batch:
         lead._phase(lib.h2mi_batch_evaluations(self.handle, x.ctypes.data, self._evals.ctypes.data), "batch evaluations")
         for e in self._evals[:self.n_evaluations]:
             transcript.write_scalar(e)
-        sy, sv = sq(), sq()
-        lead._phase(lib.h2mi_batch_shplonk_quotient(self.handle, sy.ctypes.data, sv.ctypes.data, pp), "batch shplonk quotient")
-        write(points(lead, 1))
-        su = sq()
-        lead._phase(lib.h2mi_batch_shplonk_open(self.handle, su.ctypes.data, pp), "batch shplonk open")
-        write(points(lead, 1))
+        if multiopen == "gwc":
+            gv, w = sq(), np.zeros((self.gwc_num_points(), 8), dtype=np.uint64)
+            lead._phase(lib.h2mi_batch_gwc_open(self.handle, gv.ctypes.data, w.ctypes.data), "batch gwc open")
+            write(w)
+        else:
+            sy, sv = sq(), sq()
+            lead._phase(lib.h2mi_batch_shplonk_quotient(self.handle, sy.ctypes.data, sv.ctypes.data, pp), "batch shplonk quotient")
+            write(points(lead, 1))
+            su = sq()
+            lead._phase(lib.h2mi_batch_shplonk_open(self.handle, su.ctypes.data, pp), "batch shplonk open")
+            write(points(lead, 1))
         if trace is not None:
             trace.update(theta=m(theta), beta=m(beta), gamma=m(gamma), y=m(y), x=m(x), challenges=list(known))
 

@@ -406,10 +406,11 @@ class FlexWorkspace:
 
 
 def create_proof(params: ParamsKZG, pk: FlexKeys, asg: Assignment, seed: int, transcript: Blake2bWrite = None, trace: dict = None,
-                 ws: FlexWorkspace = None) -> bytes:
+                 ws: FlexWorkspace = None, multiopen: str = "shplonk") -> bytes:
     """create_proof for one circuit with one instance column: scaffold::prove's call (src/scaffold.rs:322-331,
     `&[&[&public_io]]`).  `params` is the whole SRS, or one rank's slice of it together with ws.combiner.  Without `ws` the
-    device buffers live for this call only (released on every exit path)."""
+    device buffers live for this call only (released on every exit path).  multiopen: "shplonk" or "gwc" (engine.Prover.drive)."""
+    engine.check_multiopen(multiopen)
     own = ws is None
     ws = ws or FlexWorkspace(params, pk)
     try:
@@ -417,7 +418,7 @@ def create_proof(params: ParamsKZG, pk: FlexKeys, asg: Assignment, seed: int, tr
         transcript.common_scalar(_m(pk.transcript_repr))
         for v in asg.instance:  # KZG: the public inputs are hashed as scalars, not committed
             transcript.common_scalar(_m(v))
-        ws.prover.drive(asg.advice, asg.instance, seed, transcript, trace)
+        ws.prover.drive(asg.advice, asg.instance, seed, transcript, trace, multiopen=multiopen)
         return transcript.finalize()
     finally:
         if own:

@@ -50,16 +50,17 @@ class ProverWorkspace:
 
 
 def create_proof(params: ParamsKZG, pk: ProvingKey, circuit, seed: int, transcript: Blake2bWrite = None, ws: ProverWorkspace = None,
-                 trace: dict = None) -> bytes:
+                 trace: dict = None, multiopen: str = "shplonk") -> bytes:
     """-> proof bytes (transcript.finalize()).  `trace`, if given, receives the challenges and the workspace (whose views
-    reach the intermediate polynomials left in HBM)."""
+    reach the intermediate polynomials left in HBM).  multiopen: "shplonk" or "gwc" (engine.Prover.drive)."""
+    engine.check_multiopen(multiopen)
     own_ws = ws is None
     ws = ws or ProverWorkspace(params, pk)
     transcript = transcript or Blake2bWrite.init()
     transcript.common_scalar(_m(pk.vk.transcript_repr))  # vk.hash_into
     syn = circuit.synthesize()  # witness cells: the control plane
     try:
-        ws.prover.drive(syn.advice, [], seed, transcript, trace)
+        ws.prover.drive(syn.advice, [], seed, transcript, trace, multiopen=multiopen)
     except BaseException:
         if own_ws:
             ws.release()

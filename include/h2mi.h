@@ -242,6 +242,17 @@ int h2mi_fr_kate_division_multi_dev(const void* d_poly, size_t n, const uint64_t
 /* out[i] = sum_k scalars[k] * polys[k][i], count <= 24 (the challenge-weighted sums of SHPLONK) */
 int h2mi_fr_lincomb_dev(const void* const* d_polys, const uint64_t* scalars /* count*4 */, size_t count, size_t n, void* d_out,
                         h2mi_stream_t stream);
+/* ProverGWC's witness polynomials (poly/kzg/multiopen/gwc [RECALL]), all points in one call:
+ * d_outs[g] = (sum_j scalars_gj * poly_gj) / (X - roots[g]) for `ngroups` groups laid out as in h2mi_fr_eval_polys_multi_dev (d_polys
+ * and scalars hold the groups behind one another, group g has group_counts[g] members; roots, roots_inv: ngroups x 4 limbs, Montgomery,
+ * the inverses from the caller).  Each d_outs[g] holds n coefficients: the n - 1 of the quotient and a zero at n - 1.  The remainder —
+ * the sum's value at the root — is dropped as kate_division drops it: the quotient does not read the numerator's constant term, so
+ * the evaluations need not be subtracted first.  A polynomial may appear in several groups; outputs must not alias inputs or each
+ * other.  Three launches per slice of up to 4 points and 72 terms, the summed polynomials never stored; a group of more than 72 terms
+ * is summed by the linear-combination kernel into scratch first (same bits).  H2MI_EINVAL: n < 2, no group, an empty group, a null
+ * pointer, a zero root or inverse.  Scratch: 4 x (n + n / 512 + 1024) field elements per stream, plus n per group over 72 terms. */
+int h2mi_fr_gwc_witness_dev(const void* const* d_polys, const uint64_t* scalars, const size_t* group_counts, const uint64_t* roots,
+                            const uint64_t* roots_inv, size_t ngroups, size_t n, void* const* d_outs, h2mi_stream_t stream);
 
 /* poly[i] += head[i] for i < count <= 16: the low-degree remainder terms R(X) / r = R(u) that SHPLONK subtracts
  * from a (linear combination of) opened polynomial(s) — poly/kzg/multiopen/shplonk/prover.rs

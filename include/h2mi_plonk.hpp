@@ -210,10 +210,14 @@ struct ProverWorkspace {
   }
 };
 
+// the multi-opening scheme a proof ends with: the crate's type parameter P of create_proof (ProverSHPLONK / ProverGWC)
+enum class MultiOpen { SHPLONK, GWC };
+
 // create_proof between the transcript's challenges: what the body of a fork's create_proof looks like.  The
-// caller has already hashed vk.transcript_repr and the public inputs into `tr`.
+// caller has already hashed vk.transcript_repr and the public inputs into `tr`.  multiopen: the bytes before the opening argument
+// do not depend on it; GWC's time goes to phase_us[5].
 inline void drive_proof(ProverWorkspace& ws, const std::vector<h2mi_column_cells>& advice, const std::vector<Fr>& instance, uint64_t seed,
-                        transcript::Blake2bWrite& tr) {
+                        transcript::Blake2bWrite& tr, MultiOpen multiopen = MultiOpen::SHPLONK) {
   h2mi_prover_t p = ws.prover;
   const h2mi_prover_counts& c = ws.counts;
   std::vector<G1Affine> pts(std::max({c.advice, c.lookups, c.products, c.quotient, 1u}));
@@ -251,6 +255,16 @@ inline void drive_proof(ProverWorkspace& ws, const std::vector<h2mi_column_cells
   check(h2mi_prover_evaluations(p, x.l, (uint64_t*)evals.data()), "evaluations");
   for (const Fr& e : evals) tr.write_scalar(e);
   mark(4);
+  if (multiopen == MultiOpen::GWC) {  // ProverGWC: v, then one [W] per distinct opening point
+    size_t count = 0;
+    check(h2mi_prover_gwc_num_points(p, &count), "gwc num_points");
+    std::vector<G1Affine> w(count);
+    const Fr gv = tr.squeeze_challenge();
+    check(h2mi_prover_gwc_open(p, gv.l, (uint64_t*)w.data()), "gwc open");
+    for (const G1Affine& pt : w) tr.write_point(pt);
+    mark(5);
+    return;
+  }
   const Fr sy = tr.squeeze_challenge(), sv = tr.squeeze_challenge();  // ProverSHPLONK: y, v
   check(h2mi_prover_shplonk_quotient(p, sy.l, sv.l, (uint64_t*)pts.data()), "shplonk quotient");
   write_points(1);
@@ -288,7 +302,7 @@ inline void check_witness(ProverWorkspace& ws, const Fr* theta = nullptr) {
 
 // ---- create_proof ---------------------------------------------------------------------------------------------------
 inline void create_proof(const poly::kzg::ParamsKZG& params, const ProvingKey& pk, const StandardPlonk& circuit, uint64_t seed,
-                         transcript::Blake2bWrite& tr, ProverWorkspace* workspace = nullptr) {
+                         transcript::Blake2bWrite& tr, ProverWorkspace* workspace = nullptr, MultiOpen multiopen = MultiOpen::SHPLONK) {
   if (!circuit.x) throw Error(H2MI_EINVAL, "create_proof: the circuit has no witness (Value::unknown())");
   std::unique_ptr<ProverWorkspace> own;
   if (!workspace) {
@@ -301,7 +315,7 @@ inline void create_proof(const poly::kzg::ParamsKZG& params, const ProvingKey& p
   for (const auto& col : syn.advice) cells.push_back(ColumnCells(col));
   std::vector<h2mi_column_cells> advice;
   for (const ColumnCells& c : cells) advice.push_back(c.view());
-  drive_proof(*workspace, advice, {}, seed, tr);
+  drive_proof(*workspace, advice, {}, seed, tr, multiopen);
 }
 
 }  // namespace plonk

@@ -391,6 +391,17 @@ int h2mi_prover_evaluations(h2mi_prover_t prover, const uint64_t x[4], uint64_t*
 /* ProverSHPLONK::create_proof (poly/kzg/multiopen/shplonk/prover.rs) over the queries create_proof collects, cut at its two commitments */
 int h2mi_prover_shplonk_quotient(h2mi_prover_t prover, const uint64_t y[4], const uint64_t v[4], uint64_t point_out[8]);
 int h2mi_prover_shplonk_open(h2mi_prover_t prover, const uint64_t u[4], uint64_t point_out[8]);
+/* ProverGWC::create_proof (poly/kzg/multiopen/gwc [RECALL], as DESIGN.md 4.5 states it): the OTHER ending of a proof, in place of the
+ * two SHPLONK calls — for callers whose verifier is a Gwc19 one.  The queries are grouped by point in order of first appearance (no
+ * deduplication); per group W_i(X) = (sum_j v^j p_ij(X) - sum_j v^j e_ij) / (X - z_i), committed without blinding; points_out receives
+ * [W_0] .. [W_(P-1)], written to the transcript in this order with nothing squeezed between them.  P = h2mi_prover_gwc_num_points: the
+ * distinct rotations (modulo 2^k) of the key's queries — from the key alone, valid from h2mi_prover_create on.  The proof's tail is
+ * 32 P bytes where SHPLONK's is 64.  Requires the evaluations to be the last phase, as h2mi_prover_shplonk_quotient does, and completes
+ * the proof: a h2mi_prover_shplonk_* call behind it is H2MI_EINVAL as after any completed proof, and h2mi_prover_gwc_open behind
+ * h2mi_prover_shplonk_quotient is H2MI_EINVAL and abandons the proof.  The W_i commitments are one phase of P MSMs (a combiner's buffers
+ * hold the largest of the other phases: with one set the P go in that many at a time). */
+int h2mi_prover_gwc_num_points(h2mi_prover_t prover, size_t* count_out);
+int h2mi_prover_gwc_open(h2mi_prover_t prover, const uint64_t v[4], uint64_t* points_out /* count x 8 */);
 
 /* ---- several circuits per proof: create_proof(&params, &pk, &[c_0, .., c_(N-1)], &[instances_0, ..], rng, &mut transcript) ----------
  * A batch binds N <= H2MI_MAX_CIRCUITS (h2mi.h: 8) ordinary provers of h2mi_prover_create, member i holding circuit i.  All members are
@@ -408,7 +419,7 @@ int h2mi_prover_shplonk_open(h2mi_prover_t prover, const uint64_t u[4], uint64_t
  * member with index > 0 neither draws nor commits one, so its points_out is one point shorter (h2mi_prover_get_counts says so) and
  * its H2MI_BUF_RANDOM_POLY is stale.  A caller that writes member 0's points first keeps the random polynomial's back until every
  * member's products are written.
- * A bound member's own h2mi_prover_quotient, _evaluations, _shplonk_quotient and _shplonk_open return H2MI_EINVAL and abandon nothing.
+ * A bound member's own h2mi_prover_quotient, _evaluations, _shplonk_quotient, _shplonk_open and _gwc_open return H2MI_EINVAL and abandon nothing.
  *
  * Joint, on the batch, each once per proof and in this order (H2MI_EINVAL otherwise, and the proof is abandoned — except for the
  * refusals of h2mi_batch_quotient listed next, which leave every member where it was):
@@ -440,6 +451,9 @@ int h2mi_batch_num_evaluations(h2mi_batch_t batch, size_t* count_out);
 int h2mi_batch_evaluations(h2mi_batch_t batch, const uint64_t x[4], uint64_t* evals_out);
 int h2mi_batch_shplonk_quotient(h2mi_batch_t batch, const uint64_t y[4], const uint64_t v[4], uint64_t point_out[8]);
 int h2mi_batch_shplonk_open(h2mi_batch_t batch, const uint64_t u[4], uint64_t point_out[8]);
+/* the GWC ending of a batch's proof, in place of the two calls above: h2mi_prover_gwc_open over every circuit's queries */
+int h2mi_batch_gwc_num_points(h2mi_batch_t batch, size_t* count_out);
+int h2mi_batch_gwc_open(h2mi_batch_t batch, const uint64_t v[4], uint64_t* points_out);
 
 /* number of points the phases return, so that a caller can size buffers from the constraint system alone (products: without the random
  * polynomial for a bound member behind the first) */
@@ -467,6 +481,7 @@ enum {
   H2MI_BUF_SHPLONK_H, H2MI_BUF_SHPLONK_H2,
   H2MI_BUF_SHUFFLE_Z, H2MI_BUF_SHUFFLE_Z_POLY, H2MI_BUF_SHUFFLE_INPUT /* compressed rows */, H2MI_BUF_SHUFFLE_TABLE /* compressed rows */,
   H2MI_BUF_LOGUP_M /* a logUp key's multiplicity column of lookup `index`, rows */, H2MI_BUF_LOGUP_PHI /* its running sum, rows */,
+  H2MI_BUF_GWC_W /* W_index of the last h2mi_prover_gwc_open, n coefficients (a batch: member 0's); shares SHPLONK's scratch */,
   H2MI_PKBUF_FIXED = 64, H2MI_PKBUF_FIXED_POLY, H2MI_PKBUF_FIXED_COSET, H2MI_PKBUF_SIGMA, H2MI_PKBUF_SIGMA_POLY, H2MI_PKBUF_SIGMA_COSET,
   H2MI_PKBUF_L0_COSET, H2MI_PKBUF_L_LAST_COSET, H2MI_PKBUF_L_ACTIVE_COSET
 };
