@@ -64,6 +64,54 @@ H2_HD void f29t_mul3_one(const uint32_t* ops, size_t n, size_t i, uint32_t* out)
   f29t_store9(f29_mul3<F>(x[0], x[1], x[2], x[3], x[4], x[5]), out);
 }
 
+H2_HD xyzz29 f29t_load_xyzz(const uint32_t* p) {
+  xyzz29 r;
+  r.x = f29t_load9(p); r.y = f29t_load9(p + 9); r.zz = f29t_load9(p + 18); r.zzz = f29t_load9(p + 27);
+  return r;
+}
+H2_HD void f29t_store_xyzz(const xyzz29& r, uint32_t* p) {
+  f29t_store9(r.x, p); f29t_store9(r.y, p + 9); f29t_store9(r.zz, p + 18); f29t_store9(r.zzz, p + 27);
+}
+
+// one point operation of g1_29.cuh on RAW operands: 9 limbs per coordinate, loaded exactly as given (no reduction, no
+// canonicalisation), so a test can put every coordinate at the bounds the header states.  a, b: 36 words per element each (an XYZZ
+// point fills them; an affine (x, y) the first 18, a Jacobian (X, Y, Z) the first 27), out: 36 words.
+//   0: xyzz29_madd(acc = a, x2 = b[0..9), y2 = b[9..18))        1: xyzz29_dbl(a)        2: xyzz29_add(a, b)
+//   3: xyzz29_dbl_affine(x = b[0..9), y_any = b[9..18))
+//   4: xyzz29_from_jacobian(a) then xyzz29_to_jacobian of it: out = ZZ, ZZZ of the first, then X, Y of the second (X, Y and Z of
+//      the pair are copies of inputs / of ZZ); the identity gives all zeros
+//   5: xyzz29_to_affine(a): x, y in the first 18 words, the rest zero
+H2_HD void f29t_point_raw_one(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  for (int k = 0; k < 36; k++) out[k] = 0;
+  if (op == 0) {
+    xyzz29 acc = f29t_load_xyzz(a);
+    xyzz29_madd(acc, f29t_load9(b), f29t_load9(b + 9));
+    f29t_store_xyzz(acc, out);
+  } else if (op == 1) {
+    f29t_store_xyzz(xyzz29_dbl(f29t_load_xyzz(a)), out);
+  } else if (op == 2) {
+    xyzz29 acc = f29t_load_xyzz(a);
+    xyzz29_add(acc, f29t_load_xyzz(b));
+    f29t_store_xyzz(acc, out);
+  } else if (op == 3) {
+    f29t_store_xyzz(xyzz29_dbl_affine(f29t_load9(b), f29t_load9(b + 9)), out);
+  } else if (op == 4) {
+    const xyzz29 p = xyzz29_from_jacobian(f29t_load9(a), f29t_load9(a + 9), f29t_load9(a + 18));
+    if (xyzz29_is_identity(p)) return;
+    f29 x, y, z;
+    xyzz29_to_jacobian(p, x, y, z);
+    f29t_store9(p.zz, out);
+    f29t_store9(p.zzz, out + 9);
+    f29t_store9(x, out + 18);
+    f29t_store9(y, out + 27);
+  } else {
+    f29 x, y;
+    xyzz29_to_affine(f29t_load_xyzz(a), x, y);
+    f29t_store9(x, out);
+    f29t_store9(y, out + 9);
+  }
+}
+
 // table format of an affine point (Mont256, 16 words): canonical Mont261 packed words, read back as the kernels read them;
 // false for the identity (0, 0), which the caller skips
 H2_HD bool f29t_table_point(const uint32_t* p, bool neg, f29& x2, f29& y2) {

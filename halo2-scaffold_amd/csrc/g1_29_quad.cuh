@@ -9,14 +9,16 @@
 //   add:  1) U1 = X1*ZZ2   U2 = X2*ZZ1   S1 = Y1*ZZZ2   S2 = Y2*ZZZ1        P = U2 - U1, R = S2 - S1
 //         2) PP = P^2      RR = R^2      ZZ12 = ZZ1*ZZ2 ZZZ12 = ZZZ1*ZZZ2
 //         3) PPP = P*PP    Q = U1*PP     ZZ3 = ZZ12*PP  -                   X3 = RR - PPP - 2Q
-//         4) T1 = (Q-X3)*R T2 = S1*PPP   ZZZ3 = ZZZ12*PPP -                 Y3 = T1 - T2
+//         4) Y3 = (Q-X3)*R - S1*PPP (one reduction, f29_mul2)   ZZZ3 = ZZZ12*PPP
 //   dbl:  1) V = U^2 (U = 2Y)  XX = X^2  -  -                               M = 3 XX
 //         2) W = U*V       S = X*V       MM = M^2       ZZ3 = V*ZZ          X3 = MM - 2S
-//         3) T1 = (S-X3)*M T2 = W*Y      ZZZ3 = W*ZZZ   -                   Y3 = T1 - T2
+//         3) Y3 = (S-X3)*M - W*Y (one reduction, f29_mul2)      ZZZ3 = W*ZZZ
 // Operands and results are REPLICATED in the four lanes (every lane holds both inputs and gets the result),
 // so callers keep their one-value-per-lane structure with a lane stride of 4.  Same lazy-reduction choices,
 // value bounds and special cases (identity operands, P + P, P + (-P)) as xyzz29_add / xyzz29_dbl in
-// g1_29.cuh.  All four lanes of a quad must be active together (callers branch on quad-uniform conditions).
+// g1_29.cuh, and the same WORDS: every product has the operands it has there, Y3 included (the last round is
+// f29_mul2 in every lane, the lanes that owe one product adding 0 * 0) — tests/test_gpu_g1_29_edges.py holds
+// the two forms equal limb for limb on operands at the bounds of the invariant.  All four lanes of a quad must be active together (callers branch on quad-uniform conditions).
 #pragma once
 #include "g1_29.cuh"
 
@@ -58,11 +60,12 @@ __device__ __forceinline__ xyzz29 xyzz29_dbl_quad(const xyzz29& p) {
   r.zz = quad_bcast<3>(m2);
   r.x = f29_normalize(f29_sub(mm, f29_dbl(s), F::KW4));
   f29 t = f29_sub(s, r.x, F::K6);
-  // round 3: T1 = T*M | T2 = W*Y | ZZZ3 = W*ZZZ
-  f29 m3 = f29_mul<F>(quad_pick(role, t, w, w, w), quad_pick(role, m, p.y, p.zzz, p.zzz));
-  f29 t1 = quad_bcast<0>(m3), t2 = quad_bcast<1>(m3);
-  r.zzz = quad_bcast<2>(m3);
-  r.y = f29_normalize(f29_sub(t1, t2, F::K2));
+  // round 3: Y3 = (T*M + (4p - Y)*W) / 2^261 | ZZZ3 = W*ZZZ (+ 0*0) — one reduction for both products of Y3, as xyzz29_dbl
+  const f29 zero = f29_zero();
+  f29 m3 = f29_mul2<F>(quad_pick(role, t, w, w, w), quad_pick(role, m, p.zzz, p.zzz, p.zzz),
+                       quad_pick(role, f29_sub(zero, p.y, F::K4), zero, zero, zero), quad_pick(role, w, zero, zero, zero));
+  r.y = quad_bcast<0>(m3);
+  r.zzz = quad_bcast<1>(m3);
   if (xyzz29_is_identity(p)) return p;
   return r;
 }
@@ -90,11 +93,12 @@ __device__ __forceinline__ xyzz29 xyzz29_add_quad(const xyzz29& a, const xyzz29&
   out.zz = quad_bcast<2>(m3);
   out.x = f29_normalize(f29_sub(rr, f29_add(ppp, f29_dbl(q)), F::KW4));
   f29 t = f29_sub(q, out.x, F::K6);
-  // round 4: T1 = T*R | T2 = S1*PPP | ZZZ3 = ZZZ12*PPP
-  f29 m4 = f29_mul<F>(quad_pick(role, t, s1, zzz12, s1), quad_pick(role, r, ppp, ppp, ppp));
-  f29 t1 = quad_bcast<0>(m4), t2 = quad_bcast<1>(m4);
-  out.zzz = quad_bcast<2>(m4);
-  out.y = f29_normalize(f29_sub(t1, t2, F::K2));
+  // round 4: Y3 = (T*R + (2p - S1)*PPP) / 2^261 | ZZZ3 = ZZZ12*PPP (+ 0*0) — one reduction for both products of Y3, as xyzz29_add
+  const f29 zero = f29_zero();
+  f29 m4 = f29_mul2<F>(quad_pick(role, t, zzz12, zzz12, zzz12), quad_pick(role, r, ppp, ppp, ppp),
+                       quad_pick(role, f29_sub(zero, s1, F::K2), zero, zero, zero), quad_pick(role, ppp, zero, zero, zero));
+  out.y = quad_bcast<0>(m4);
+  out.zzz = quad_bcast<1>(m4);
   // special cases: every flag is computed from replicated values, hence uniform inside the quad
   if (b_id) return a;
   if (a_id) return b;

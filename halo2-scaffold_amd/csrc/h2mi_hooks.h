@@ -30,6 +30,14 @@ int h2mi_dbg_f29_mul_raw(int field, const uint32_t* a, const uint32_t* b, uint32
 int h2mi_dbg_f29_sqr_raw(int field, const uint32_t* a, uint32_t* out, size_t n);           /* a normalized */
 int h2mi_dbg_f29_mul2_raw(int field, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* out, size_t n);
 int h2mi_dbg_f29_mul3_raw(int field, const uint32_t* ops /* [6][n][9] */, uint32_t* out, size_t n);
+/* one point operation of csrc/g1_29.cuh per element on RAW coordinates (9 limbs each, loaded as given: no reduction, no
+ * canonicalisation), so that operands can sit at the bounds the header states; a, b and out hold 36 words per element (an XYZZ
+ * point fills them, an affine (x, y) the first 18, a Jacobian (X, Y, Z) the first 27; an operand an op does not take is ignored
+ * but must be there).  Ops 0..5 are f29t_point_raw_one, one thread per element, as f29t_point_raw of the g++ harness: 0 =
+ * xyzz29_madd(a, b.x, b.y); 1 = xyzz29_dbl(a); 2 = xyzz29_add(a, b); 3 = xyzz29_dbl_affine(b.x, b.y); 4 = xyzz29_from_jacobian(a)
+ * then xyzz29_to_jacobian (out = ZZ, ZZZ, X', Y'); 5 = xyzz29_to_affine(a).  Ops 6 / 7 are the lane-cooperative
+ * xyzz29_add_quad(a, b) / xyzz29_dbl_quad(a) of csrc/g1_29_quad.cuh, four lanes per element, the writing lane rotating. */
+int h2mi_dbg_g1_29_raw_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n);
 /* f29t_madd_chain, batched: chain c accumulates the affine points (Mont256, 16 words each; (0,0) skipped) offsets[c] ..
  * offsets[c + 1] of pts with signs[i] != 0 meaning -P_i, one thread per chain, all chains in one launch; offsets has nchains + 1
  * entries starting at 0.  tree = 0: mixed additions into one accumulator; 2 / 4 / 8 / 16: that many group accumulators folded

@@ -1,8 +1,8 @@
 """Cases of the lazy 29-bit-limb field / curve layer (csrc/f29.cuh, g1_29.cuh): the operand builders and the big-integer checks
 behind tests/test_f29_host.py (the g++ build of the headers) and tests/test_gpu_f29.py (the same code as the device compiles it,
-through the h2mi_dbg_f29_* hooks).  Every check takes a backend with the same seven calls (HostBackend / DeviceBackend below):
+through the h2mi_dbg_f29_* hooks).  Every check takes a backend with the same eight calls (HostBackend / DeviceBackend below):
     mul(field, mode, A, B, n)  reduce_loose(field, limbs)  mul_raw(field, a, b)  sqr_raw(field, a)
-    mul2_raw(field, a, b, c, d)  mul3_raw(field, ops)  chains([(pts, signs), ...], tree)
+    mul2_raw(field, a, b, c, d)  mul3_raw(field, ops)  chains([(pts, signs), ...], tree)  point_raw(op, a, b)
 Every comparison is exact: against Python integers modulo p, `got * 2^261 == want (mod p)`, `got < want // 2^261 + p + 1`, limbs
 0..7 below 2^29, canonical outputs below p.  All operands stay inside the contracts f29.cuh states."""
 import ctypes as C
@@ -26,6 +26,7 @@ _SIGNATURES = {
     "sqr_raw": [C.c_int, _VP, _VP, _SZ],
     "mul2_raw": [C.c_int] + [_VP] * 5 + [_SZ],
     "mul3_raw": [C.c_int, _VP, _VP, _SZ],
+    "point_raw": [C.c_int, _VP, _VP, _VP, _SZ],
 }
 
 
@@ -43,7 +44,7 @@ def host_lib():
 
 
 class _Backend:
-    """the six elementwise calls over a library; `symbols`: its entry point for each; `checked`: they return a status that must be 0"""
+    """the seven elementwise calls over a library; `symbols`: its entry point for each; `checked`: they return a status that must be 0"""
 
     def __init__(self, lib, symbols, checked):
         self.lib, self.checked = lib, checked
@@ -91,13 +92,23 @@ class _Backend:
         self._call("mul3_raw", field, ops.ctypes.data, out.ctypes.data, n)
         return out
 
+    def point_raw(self, op, a, b):
+        """one g1_29.cuh point operation per element on raw coordinates (f29t_point_raw_one; the cases: tests/g1_29_edge_cases.py):
+        a, b and the result hold 36 words per element"""
+        a, b = (np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b))
+        n = len(a)
+        assert a.shape == (n, 36) and b.shape == (n, 36)
+        out = np.zeros((n, 36), dtype=np.uint32)
+        self._call("point_raw", op, a.ctypes.data, b.ctypes.data, out.ctypes.data, n)
+        return out
+
 
 class HostBackend(_Backend):
     """tests/host/f29_host.cpp compiled with g++ (f29t_*)"""
 
     def __init__(self, lib):
         symbols = {"mul": "f29t_mul", "reduce_loose": "f29t_reduce_loose", "mul_raw": "f29t_mul_raw", "sqr_raw": "f29t_sqr_raw",
-                   "mul2_raw": "f29t_mul2_raw", "mul3_raw": "f29t_mul3_raw"}
+                   "mul2_raw": "f29t_mul2_raw", "mul3_raw": "f29t_mul3_raw", "point_raw": "f29t_point_raw"}
         super().__init__(lib, symbols, checked=False)
         lib.f29t_madd_chain.argtypes, lib.f29t_madd_chain.restype = [_VP, _VP, _SZ, _VP, C.c_int], None
 
@@ -115,7 +126,8 @@ class DeviceBackend(_Backend):
 
     def __init__(self, lib):
         symbols = {"mul": "h2mi_dbg_f29_mul", "reduce_loose": "h2mi_dbg_f29_reduce_loose", "mul_raw": "h2mi_dbg_f29_mul_raw",
-                   "sqr_raw": "h2mi_dbg_f29_sqr_raw", "mul2_raw": "h2mi_dbg_f29_mul2_raw", "mul3_raw": "h2mi_dbg_f29_mul3_raw"}
+                   "sqr_raw": "h2mi_dbg_f29_sqr_raw", "mul2_raw": "h2mi_dbg_f29_mul2_raw", "mul3_raw": "h2mi_dbg_f29_mul3_raw",
+                   "point_raw": "h2mi_dbg_g1_29_raw_op"}
         super().__init__(lib, symbols, checked=True)
         lib.h2mi_dbg_g1_29_chains.argtypes, lib.h2mi_dbg_g1_29_chains.restype = [_VP, _VP, _VP, _SZ, _VP, C.c_int], C.c_int
 

@@ -50,6 +50,12 @@ void f29t_mul3_raw(int field, const uint32_t* ops /* [6][n][9] */, uint32_t* out
   }
 }
 
+// one point operation of g1_29.cuh per element on raw 9-limb coordinates (f29t_point_raw_one: ops 0..5); a, b, out hold 36 words
+// per element (b may be null for the ops that take no second operand)
+void f29t_point_raw(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+  for (size_t i = 0; i < n; i++) f29t_point_raw_one(op, a + 36 * i, b ? b + 36 * i : nullptr, out + 36 * i);
+}
+
 // accumulate n affine points (Mont256, 16 words each; (0,0) skipped) with signs[i] != 0 meaning -P_i;
 // writes the XYZZ result as 4 x 8 words Mont256 (canonical); `tree`: see f29t_chain_one
 void f29t_madd_chain(const uint32_t* pts, const uint8_t* signs, size_t n, uint32_t* out_xyzz, int tree) {
