@@ -119,6 +119,15 @@ def _load():
         "h2mi_plonk_expr_compress_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_expr_check_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32), vp],
                                          C.c_int),
+        # several instance columns (h2mi_instance_cosets)
+        "h2mi_plonk_instance_coset_multi_dev": ([vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, vp], C.c_int),
+        "h2mi_plonk_evaluate_h_expr_in_dev": ([vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+                                              C.c_int),
+        "h2mi_plonk_evaluate_h_expr_batch_in_dev": ([vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
+                                                     vp, vp, vp, vp], C.c_int),
+        "h2mi_plonk_expr_compress_in_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
+        "h2mi_plonk_expr_check_in_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32), vp],
+                                         C.c_int),
         "h2mi_plonk_copy_check_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp], C.c_int),
         "h2mi_plonk_lookup_member_dev": ([vp, vp, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
         "h2mi_plonk_shuffle_member_dev": ([vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
@@ -153,6 +162,7 @@ def _load():
         "h2mi_prover_set_combiner": ([vp, vp, vp, vp, vp], C.c_int),
         "h2mi_prover_set_rng_key": ([vp, vp], C.c_int),
         "h2mi_prover_get_counts": ([vp, vp], C.c_int),
+        "h2mi_prover_instances": ([vp, vp], C.c_int),
         "h2mi_prover_advice": ([vp, vp, vp, sz, C.c_uint64, vp], C.c_int),
         "h2mi_prover_advice_phase": ([vp, C.c_uint32, vp, vp, sz, C.c_uint64, vp], C.c_int),
         "h2mi_prover_set_challenges": ([vp, vp], C.c_int),

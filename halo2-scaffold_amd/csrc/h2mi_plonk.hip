@@ -616,7 +616,7 @@ __global__ void __launch_bounds__(256) k_evaluate_h_flex(FlexCosets c, uint32_t 
 //   * the operand stack keeps its top in registers and the rest in LDS as [level][limb][thread] (a wavefront's 64 lanes read 64
 //     consecutive words: no bank conflict), max_stack - 1 levels of 9 KB, sized per launch — never a runtime-indexed private array;
 //   * the column-pointer table, the constants (already Montgomery-2^261 words) and the ops live in ONE device buffer: the launch carries
-//     three addresses into it, not 129 pointers;
+//     three addresses into it, not 136 pointers (64 advice, 64 fixed, H2MI_MAX_INSTANCE instance columns);
 //   * a challenge (H2MI_EXPR_CHALLENGE: a value the transcript yields between two advice phases) is a constant of the LAUNCH rather than
 //     of the program: the uploader lays the challenge values out behind the program's constants, in the same words, and encodes the
 //     operand as EX_CONST with index n_constants + challenge — the same wave-uniform load, no dispatch case of its own, and the device
@@ -624,7 +624,8 @@ __global__ void __launch_bounds__(256) k_evaluate_h_flex(FlexCosets c, uint32_t 
 // Ops as uploaded: word x = code | index << 8, word y = the row offset of the rotation, (r mod n) 2^(ext_k - k).  The uploader inserts
 // EX_RED where its static bound on a value would otherwise pass what the next operation takes (see expr_encode).
 enum : uint32_t { EX_COL = 0, EX_CONST, EX_ADD, EX_SUB, EX_MUL, EX_NEG, EX_RED, EX_END };
-constexpr uint32_t EX_COLS = H2MI_EXPR_MAX_ADVICE + H2MI_EXPR_MAX_FIXED + 1;  // advice, fixed, the instance column
+constexpr uint32_t EX_INSTANCE = H2MI_EXPR_MAX_ADVICE + H2MI_EXPR_MAX_FIXED;   // instance column i sits in slot EX_INSTANCE + i
+constexpr uint32_t EX_COLS = EX_INSTANCE + H2MI_MAX_INSTANCE;                 // advice, fixed, the instance columns
 // The interpreter loop, shared by the quotient kernel and the lookup compression: `sink(value)` receives each polynomial at its END.
 template <class Sink>
 __device__ __forceinline__ void expr_interpret(const fe* const* __restrict__ cols, const fe* __restrict__ consts, const uint2* __restrict__ ops,
@@ -688,7 +689,7 @@ __global__ void __launch_bounds__(256) k_evaluate_h_expr(FlexCosets c, const fe*
 // table indexed by a loaded value does not belong in the launch's arguments, see k_copy_check).  The circuit counter does not depend
 // on the lane: a record's pointers arrive by scalar loads at uniform addresses, as the ops do.
 struct CircuitCosets {
-  const fe* cols[EX_COLS];  // the interpreter's table: advice, fixed, the instance column
+  const fe* cols[EX_COLS];  // the interpreter's table: advice, fixed, the instance columns
   const fe* perm_value[H2MI_FLEX_MAX_PERM];
   const fe* perm_z[H2MI_FLEX_MAX_PERM];
   const fe* lk_in[H2MI_FLEX_MAX_LOOKUPS];
@@ -1064,7 +1065,7 @@ static void expr_encode(const h2mi_gate_program* g, uint32_t k, uint32_t extende
     const h2mi_expr_op& o = g->ops[i];
     switch (o.op) {
       case H2MI_EXPR_ADVICE: case H2MI_EXPR_FIXED: case H2MI_EXPR_INSTANCE: {
-        const uint32_t slot = o.op == H2MI_EXPR_ADVICE ? o.index : o.op == H2MI_EXPR_FIXED ? H2MI_EXPR_MAX_ADVICE + o.index : EX_COLS - 1;
+        const uint32_t slot = o.op == H2MI_EXPR_ADVICE ? o.index : o.op == H2MI_EXPR_FIXED ? H2MI_EXPR_MAX_ADVICE + o.index : EX_INSTANCE + o.index;
         emit(EX_COL, slot, (uint32_t)(((int64_t)o.rotation + n) % n) * rot);
         b[sp++] = 1.04;
         break;
@@ -1084,18 +1085,30 @@ static void expr_encode(const h2mi_gate_program* g, uint32_t k, uint32_t extende
 // rotation of 2^k or more is H2MI_EINVAL) and laid out as ONE buffer: the column-pointer table, the constants and behind them the
 // challenges as Montgomery-2^261 words, the ops (each part a whole number of 32-byte words).  dom_k: the domain the columns are given
 // on (k or extended_k).
+// the instance columns of one circuit as the entry points take them: an h2mi_instance_cosets, or the one pointer of the older calls
+// (column 0).  ok = false: more columns than the table holds
+struct InstanceCols {
+  const void* col[H2MI_MAX_INSTANCE] = {nullptr};
+  bool ok = true;
+  InstanceCols(const h2mi_instance_cosets* in, const void* single) {
+    if (!in) { col[0] = single; return; }
+    ok = in->n_instance <= H2MI_MAX_INSTANCE;
+    for (uint32_t i = 0; ok && i < in->n_instance; i++) col[i] = in->column[i];
+  }
+  bool has(uint32_t index) const { return index < H2MI_MAX_INSTANCE && col[index]; }
+};
 struct ExprImage {
   std::vector<fe> image;
   size_t cols_fe = 0, const_fe = 0, lds = 0;
   uint32_t n_ops = 0;
   int build(const h2mi_gate_program* g, const uint64_t* challenges, uint32_t n_challenges, const void* const* advice, const void* const* fixed,
-            const void* instance, uint32_t k, uint32_t dom_k) {
+            const InstanceCols& instance, uint32_t k, uint32_t dom_k) {
     if (n_challenges > H2MI_MAX_CHALLENGES || (n_challenges && !challenges)) return H2MI_EINVAL;
     ExprShape shape;
     const int rc = expr_walk(g, k, n_challenges, [&](uint32_t kind, uint32_t index, int32_t) {
       return kind == H2MI_EXPR_ADVICE ? index < H2MI_EXPR_MAX_ADVICE && advice[index]
            : kind == H2MI_EXPR_FIXED  ? index < H2MI_EXPR_MAX_FIXED && fixed[index]
-                                      : index == 0 && instance;
+                                      : instance.has(index);
     }, &shape);
     if (rc) return rc;
     std::vector<uint2> ops;
@@ -1108,7 +1121,7 @@ struct ExprImage {
     const void** tab = (const void**)image.data();
     for (uint32_t i = 0; i < H2MI_EXPR_MAX_ADVICE; i++) tab[i] = advice[i];
     for (uint32_t i = 0; i < H2MI_EXPR_MAX_FIXED; i++) tab[H2MI_EXPR_MAX_ADVICE + i] = fixed[i];
-    tab[EX_COLS - 1] = instance;
+    for (uint32_t i = 0; i < H2MI_MAX_INSTANCE; i++) tab[EX_INSTANCE + i] = instance.col[i];
     for (uint32_t i = 0; i < g->n_constants; i++) image[cols_fe + i] = h_canon(f29_from_mont256<F9>(host_fe(g->constants + 4 * i).v));
     for (uint32_t i = 0; i < n_challenges; i++) image[cols_fe + g->n_constants + i] = h_canon(f29_from_mont256<F9>(host_fe(challenges + 4 * i).v));
     memcpy(&image[cols_fe + const_fe], ops.data(), ops.size() * 8);
@@ -1538,12 +1551,23 @@ int h2mi_plonk_evaluate_h_expr_lg_dev(const h2mi_expr_cosets* c, const h2mi_shuf
                                       uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
                                       const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
                                       void* d_h_out, h2mi_stream_t stream) {
+  return h2mi_plonk_evaluate_h_expr_in_dev(c, shuffles, logup, nullptr, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma, y, delta,
+                                           zeta, extended_omega, t_inv, d_h_out, stream);
+}
+
+int h2mi_plonk_evaluate_h_expr_in_dev(const h2mi_expr_cosets* c, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                      const h2mi_instance_cosets* instances, const h2mi_gate_program* gates, const uint64_t* challenges,
+                                      uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
+                                      const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
+                                      const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!c || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
   if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
   if (c->n_perm > H2MI_FLEX_MAX_PERM || (c->n_lookups & ~(uint32_t)H2MI_LOOKUPS_LOGUP) > H2MI_FLEX_MAX_LOOKUPS || (c->n_perm && c->chunk_len == 0)) return H2MI_EINVAL;
+  const InstanceCols inst(instances, c->instance);
+  if (!inst.ok) return H2MI_EINVAL;
   ExprImage im;
-  int rc = im.build(gates, challenges, n_challenges, c->advice, c->fixed, c->instance, k, extended_k);
+  int rc = im.build(gates, challenges, n_challenges, c->advice, c->fixed, inst, k, extended_k);
   if (rc) return rc;
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
   FlexCosets fc;
@@ -1594,6 +1618,16 @@ int h2mi_plonk_evaluate_h_expr_batch_lg_dev(const h2mi_expr_cosets* circuits, co
                                             uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
                                             const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
                                             const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
+  return h2mi_plonk_evaluate_h_expr_batch_in_dev(circuits, shuffles, logup, nullptr, n_circuits, gates, challenges, n_challenges, k, extended_k,
+                                                 blinding_factors, beta, gamma, y, delta, zeta, extended_omega, t_inv, d_h_out, stream);
+}
+
+int h2mi_plonk_evaluate_h_expr_batch_in_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                            const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
+                                            const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
+                                            uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
+                                            const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
+                                            void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!circuits || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
   if (n_circuits == 0 || n_circuits > H2MI_MAX_CIRCUITS) return H2MI_EINVAL;
@@ -1602,8 +1636,10 @@ int h2mi_plonk_evaluate_h_expr_batch_lg_dev(const h2mi_expr_cosets* circuits, co
   if (c0.n_perm > H2MI_FLEX_MAX_PERM || (c0.n_lookups & ~(uint32_t)H2MI_LOOKUPS_LOGUP) > H2MI_FLEX_MAX_LOOKUPS || (c0.n_perm && c0.chunk_len == 0)) return H2MI_EINVAL;
   // the program, its constants and the challenges once, as the single-circuit call lays them out (the image's own column table is
   // circuit 0's and is not read here); the circuits' records behind it
+  const InstanceCols inst0(instances, c0.instance);
+  if (!inst0.ok) return H2MI_EINVAL;
   ExprImage im;
-  int rc = im.build(gates, challenges, n_challenges, c0.advice, c0.fixed, c0.instance, k, extended_k);
+  int rc = im.build(gates, challenges, n_challenges, c0.advice, c0.fixed, inst0, k, extended_k);
   if (rc) return rc;
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
   static_assert(sizeof(CircuitCosets) % 8 == 0, "records are arrays of pointers");
@@ -1620,11 +1656,13 @@ int h2mi_plonk_evaluate_h_expr_batch_lg_dev(const h2mi_expr_cosets* circuits, co
     if (!fill_tail(fc, c) || !fill_shuffles(fc, shuffles ? shuffles + i : nullptr) || fc.n_shuffles != sh.n_shuffles) return H2MI_EINVAL;
     // what the proof shares is read from entry 0: an entry that names other sigma or Lagrange cosets is a caller's mistake
     if (memcmp(fc.perm_sigma, sh.perm_sigma, sizeof(fc.perm_sigma)) || fc.l0 != sh.l0 || fc.l_last != sh.l_last || fc.l_active != sh.l_active) return H2MI_EINVAL;
+    const InstanceCols inst(instances ? instances + i : nullptr, c.instance);
+    if (!inst.ok) return H2MI_EINVAL;
     if (i) {  // every column the program reads is there (entry 0: im.build above)
       rc = expr_walk(gates, k, n_challenges, [&](uint32_t kind, uint32_t index, int32_t) {
         return kind == H2MI_EXPR_ADVICE ? index < H2MI_EXPR_MAX_ADVICE && c.advice[index]
              : kind == H2MI_EXPR_FIXED  ? index < H2MI_EXPR_MAX_FIXED && c.fixed[index]
-                                        : index == 0 && c.instance;
+                                        : inst.has(index);
       }, nullptr);
       if (rc) return rc;
     }
@@ -1632,7 +1670,7 @@ int h2mi_plonk_evaluate_h_expr_batch_lg_dev(const h2mi_expr_cosets* circuits, co
     memset(&rec, 0, sizeof(rec));
     for (uint32_t j = 0; j < H2MI_EXPR_MAX_ADVICE; j++) rec.cols[j] = (const fe*)c.advice[j];
     for (uint32_t j = 0; j < H2MI_EXPR_MAX_FIXED; j++) rec.cols[H2MI_EXPR_MAX_ADVICE + j] = (const fe*)c.fixed[j];
-    rec.cols[EX_COLS - 1] = (const fe*)c.instance;
+    for (uint32_t j = 0; j < H2MI_MAX_INSTANCE; j++) rec.cols[EX_INSTANCE + j] = (const fe*)inst.col[j];
     memcpy(rec.perm_value, fc.perm_value, sizeof(rec.perm_value));
     memcpy(rec.perm_z, fc.perm_z, sizeof(rec.perm_z));
     memcpy(rec.lk_in, fc.lk_in, sizeof(rec.lk_in));
@@ -1677,7 +1715,16 @@ int h2mi_plonk_expr_compress_dev(const void* const* d_advice, uint32_t n_advice,
 int h2mi_plonk_expr_compress_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
                                     const h2mi_gate_program* exprs, const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t domain_k,
                                     const uint64_t theta[4], void* d_out, h2mi_stream_t stream) {
+  const h2mi_instance_cosets one = {1, {d_instance}};
+  return h2mi_plonk_expr_compress_in_dev(d_advice, n_advice, d_fixed, n_fixed, &one, exprs, challenges, n_challenges, k, domain_k, theta, d_out, stream);
+}
+
+int h2mi_plonk_expr_compress_in_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
+                                    const h2mi_instance_cosets* instances, const h2mi_gate_program* exprs, const uint64_t* challenges,
+                                    uint32_t n_challenges, uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
+  const InstanceCols inst(instances, nullptr);
+  if (!inst.ok) return H2MI_EINVAL;
   if (!exprs || !theta || !d_out || (n_advice && !d_advice) || (n_fixed && !d_fixed) || n_advice > H2MI_EXPR_MAX_ADVICE || n_fixed > H2MI_EXPR_MAX_FIXED)
     return H2MI_EINVAL;
   if (k == 0 || domain_k < k || domain_k - k > 4 || domain_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
@@ -1686,7 +1733,7 @@ int h2mi_plonk_expr_compress_ch_dev(const void* const* d_advice, uint32_t n_advi
   for (uint32_t i = 0; i < n_advice; i++) adv[i] = d_advice[i];
   for (uint32_t i = 0; i < n_fixed; i++) fix[i] = d_fixed[i];
   ExprImage im;
-  int rc = im.build(exprs, challenges, n_challenges, adv, fix, d_instance, k, domain_k);
+  int rc = im.build(exprs, challenges, n_challenges, adv, fix, inst, k, domain_k);
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
@@ -1704,7 +1751,17 @@ int h2mi_plonk_expr_compress_ch_dev(const void* const* d_advice, uint32_t n_advi
 int h2mi_plonk_expr_check_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
                                  const h2mi_gate_program* polys, const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t n_rows,
                                  uint32_t* report_out, uint32_t* n_polys_out, h2mi_stream_t stream) {
+  const h2mi_instance_cosets one = {1, {d_instance}};
+  return h2mi_plonk_expr_check_in_dev(d_advice, n_advice, d_fixed, n_fixed, &one, polys, challenges, n_challenges, k, n_rows, report_out, n_polys_out, stream);
+}
+
+int h2mi_plonk_expr_check_in_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
+                                 const h2mi_instance_cosets* instances, const h2mi_gate_program* polys, const uint64_t* challenges,
+                                 uint32_t n_challenges, uint32_t k, uint32_t n_rows, uint32_t* report_out, uint32_t* n_polys_out,
+                                 h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
+  const InstanceCols inst(instances, nullptr);
+  if (!inst.ok) return H2MI_EINVAL;
   if (!polys || !report_out || (n_advice && !d_advice) || (n_fixed && !d_fixed) || n_advice > H2MI_EXPR_MAX_ADVICE || n_fixed > H2MI_EXPR_MAX_FIXED)
     return H2MI_EINVAL;
   if (k == 0 || k > H2MI_MAX_LOG_N || n_rows == 0 || n_rows > ((uint64_t)1 << k)) return H2MI_ERANGE;
@@ -1713,7 +1770,7 @@ int h2mi_plonk_expr_check_ch_dev(const void* const* d_advice, uint32_t n_advice,
   for (uint32_t i = 0; i < n_advice; i++) adv[i] = d_advice[i];
   for (uint32_t i = 0; i < n_fixed; i++) fix[i] = d_fixed[i];
   ExprImage im;
-  int rc = im.build(polys, challenges, n_challenges, adv, fix, d_instance, k, k);
+  int rc = im.build(polys, challenges, n_challenges, adv, fix, inst, k, k);
   if (rc) return rc;
   uint32_t n_polys = 0;
   for (uint32_t i = 0; i < polys->n_ops; i++) n_polys += polys->ops[i].op == H2MI_EXPR_END;

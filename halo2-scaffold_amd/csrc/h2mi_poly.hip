@@ -5,6 +5,7 @@
 // (reference examples/standard_plonk.rs:41-49, src/scaffold.rs:322-331) through csrc/h2mi_prover.cpp.  Power tables and scratch
 // vectors come from h2mi_ntt.hip (h2mi_fr_tables.h).  Split out of h2mi_ntt.hip in round 5; the kernels are unchanged.
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "h2mi_fr_tables.h"
@@ -414,6 +415,63 @@ __global__ void __launch_bounds__(256) k_fr_random_chacha(fe* out, size_t n, Cha
 }
 #undef H2_QR
 
+// k_instance_coset (above) for all the short instance columns of one circuit in ONE launch.  The rotated l_0 value of step r does not depend on the
+// column, so a thread loads it once and feeds one accumulator per column; per column the products, the carries after every fourth
+// addend (limbs stay below 2^32) and the final reduction are k_instance_coset's, so column c's words are those of that kernel on
+// column c's values.  The scaled values do not travel by value: `vals` is a device buffer of IC_TILE x 16 elements (column c's value
+// r at 16 c + r, zero beyond its count) written on the launch's stream — the address depends on no lane, so a value arrives by
+// scalar loads, and no run-time index reaches a by-value argument (see k_instance_coset).  count[c] and out[c] are indexed by a
+// compile-time column counter only.  A column beyond the circuit's has out[c] == NULL and is skipped; an empty column is written as zeros.
+// Column tile: ALL EIGHT columns per launch.  The gfx950 build reports 105 VGPRs, 52 SGPRs, no scratch and no spill for this kernel
+// (nine accumulator limbs per column = 72, the loaded l_0 value, the product in flight): four wavefronts per SIMD.  The 4 + 4 split
+// would fit eight wavefronts per SIMD but load and unpack every l_0 value twice and launch twice; the pass is bound by its up to 128
+// field multiplications per thread, not by memory, so the occupancy would buy little.  The values reach the kernel by scalar loads
+// (15 s_load in the build, 2 vector loads: the l_0 element).  Measured on an MI355X at 2^20 rows, eight columns of 16 values, kernel
+// time from the launch profile, median of ten: 1.90 ms on the 2^21-point coset (3.67 ms on 2^22) against 2.04 ms (3.97 ms) for eight
+// k_instance_coset launches.
+constexpr uint32_t IC_TILE = H2MI_MAX_INSTANCE;
+struct InstanceMultiArgs {
+  fe* out[IC_TILE];
+  uint32_t count[IC_TILE];
+};
+// the column counter is a template parameter (a fold over 0 .. IC_TILE - 1), not a loop variable: the accumulators are then plain
+// registers whatever the unroller decides about a loop whose body holds eight multiplications
+template <uint32_t C>
+__device__ __forceinline__ void ic_accumulate(f29 (&acc)[IC_TILE], const f29& l, const fe* __restrict__ vals, const InstanceMultiArgs& a, uint32_t r) {
+  if (r < a.count[C]) {
+    acc[C] = f29_add(acc[C], f29_mul<F9>(l, f29_unpack(vals[16 * C + r].v)));
+    if ((r & 3u) == 3u) acc[C] = f29_normalize(acc[C]);  // four normalized addends at most between carries (limbs stay below 2^32)
+  }
+}
+template <uint32_t C>
+__device__ __forceinline__ void ic_store(const f29 (&acc)[IC_TILE], const InstanceMultiArgs& a, uint32_t j) {
+  if (a.out[C]) {
+    fe o;
+    f29_pack(f29_reduce_loose<F9>(f29_normalize(acc[C])), o.v);
+    fe_store(&a.out[C][j], o);
+  }
+}
+template <uint32_t... C>
+__device__ __forceinline__ void ic_body(std::integer_sequence<uint32_t, C...>, const fe* __restrict__ l0, uint32_t size, uint32_t rot,
+                                        const fe* __restrict__ vals, const InstanceMultiArgs& a, uint32_t max_count, uint32_t j) {
+  f29 acc[IC_TILE];
+  ((acc[C] = f29_zero()), ...);
+  for (uint32_t r = 0; r < max_count; r++) {  // max_count <= 16; a run-time r is fine here: it indexes device memory only
+    const f29 l = load_unpack(&l0[(j + size - r * rot) & (size - 1)]);
+    (ic_accumulate<C>(acc, l, vals, a, r), ...);
+  }
+  (ic_store<C>(acc, a, j), ...);
+}
+__global__ void __launch_bounds__(256) k_instance_coset_multi(const fe* __restrict__ l0, uint32_t ext_k, uint32_t rot, const fe* __restrict__ vals,
+                                                               InstanceMultiArgs a, uint32_t max_count) {
+  const uint32_t size = 1u << ext_k;
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= size) return;
+  ic_body(std::make_integer_sequence<uint32_t, IC_TILE>(), l0, size, rot, vals, a, max_count, j);
+}
+// (Defined behind every other kernel of this file, next to nothing it resembles, on purpose: the device code of the kernels above keeps
+// the place in the code object it had before this kernel existed.)
+
 }  // namespace h2
 
 using namespace h2;
@@ -589,6 +647,40 @@ int h2mi_plonk_instance_coset_dev(const void* d_l0_coset, uint32_t k, uint32_t e
   H2_LAUNCH("k_instance_coset", k_instance_coset, ceil_div_u32(size, 256), 256, 0, s, (const fe*)d_l0_coset, extended_k, 1u << (extended_k - k), a,
             (uint32_t)count, (fe*)d_out);
   return H2MI_OK;
+}
+
+int h2mi_plonk_instance_coset_multi_dev(const void* d_l0_coset, uint32_t k, uint32_t extended_k, const uint64_t* const* values, const size_t* counts,
+                                        uint32_t n_columns, void* const* d_out, h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_l0_coset || !d_out || !counts || !values || n_columns == 0 || n_columns > IC_TILE) return H2MI_EINVAL;
+  for (uint32_t c = 0; c < n_columns; c++)
+    if (!d_out[c] || (counts[c] && !values[c]) || counts[c] > 16) return H2MI_EINVAL;
+  if (k == 0 || extended_k < k || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  for (uint32_t c = 0; c < n_columns; c++)
+    if (counts[c] > ((size_t)1 << k)) return H2MI_ERANGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  hipStream_t s = pick_stream(stream);
+  // the values scaled exactly as the single-column call scales them, zero beyond a column's count
+  fe image[IC_TILE * 16];
+  memset(image, 0, sizeof(image));
+  InstanceMultiArgs a;
+  memset(&a, 0, sizeof(a));
+  uint32_t max_count = 0;
+  for (uint32_t c = 0; c < n_columns; c++) {
+    a.out[c] = (fe*)d_out[c];
+    a.count[c] = (uint32_t)counts[c];
+    max_count = std::max(max_count, a.count[c]);
+    for (size_t r = 0; r < counts[c]; r++) image[16 * c + r] = h_level(host_fe(values[c] + 4 * r), -1);
+  }
+  int rc = ensure_tmp(IC_TILE * 16, s);
+  if (rc) return rc;
+  fe* d_vals = tmp_base();
+  // pageable source: the copy has left `image` when the call returns
+  H2_HIP(hipMemcpyAsync(d_vals, image, sizeof(image), hipMemcpyHostToDevice, s));
+  const uint32_t size = 1u << extended_k;
+  H2_LAUNCH("k_instance_coset_multi", k_instance_coset_multi, ceil_div_u32(size, 256), 256, 0, s, (const fe*)d_l0_coset, extended_k,
+            1u << (extended_k - k), (const fe*)d_vals, a, max_count);
+  return release_tmp(s);
 }
 
 int h2mi_fr_kate_division_multi_dev(const void* d_poly, size_t n, const uint64_t* roots, const uint64_t* roots_inv, const uint64_t* weights,

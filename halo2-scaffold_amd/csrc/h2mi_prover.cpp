@@ -128,7 +128,7 @@ static_assert(H2MI_EXPR_ADVICE == H2MI_COL_ADVICE && H2MI_EXPR_FIXED == H2MI_COL
 
 // the rules of h2mi_gate_program_check (include/h2mi_prover.h)
 int check_program(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, h2::ExprShape* shape, uint32_t n_challenges = 0) {
-  if (cs.k == 0 || cs.k > H2MI_MAX_LOG_N || cs.n_advice > H2MI_MAX_ADVICE || cs.n_fixed > H2MI_MAX_FIXED || cs.n_instance > 1 ||
+  if (cs.k == 0 || cs.k > H2MI_MAX_LOG_N || cs.n_advice > H2MI_MAX_ADVICE || cs.n_fixed > H2MI_MAX_FIXED || cs.n_instance > H2MI_MAX_INSTANCE ||
       cs.n_advice_queries > H2MI_MAX_QUERIES || cs.n_fixed_queries > H2MI_MAX_QUERIES)
     return H2MI_EINVAL;
   auto listed = [](const h2mi_query* q, uint32_t count, uint32_t column, int32_t rotation) {
@@ -260,7 +260,7 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, 
   if (cs.k == 0 || cs.k > H2MI_MAX_LOG_N) throw Error(H2MI_ERANGE, "constraint system: k");
   if (cs.degree < 3 || cs.degree > 9) bad("degree");
   if (((uint64_t)1 << cs.k) <= (uint64_t)cs.blinding_factors + 2) throw Error(H2MI_ERANGE, "constraint system: no usable rows");
-  if (cs.n_advice == 0 || cs.n_advice > H2MI_MAX_ADVICE || cs.n_fixed > H2MI_MAX_FIXED || cs.n_instance > 1) bad("column counts");
+  if (cs.n_advice == 0 || cs.n_advice > H2MI_MAX_ADVICE || cs.n_fixed > H2MI_MAX_FIXED || cs.n_instance > H2MI_MAX_INSTANCE) bad("column counts");
   if (cs.n_perm > H2MI_MAX_PERM || cs.n_lookups > H2MI_MAX_LOOKUPS) bad("permutation / lookup counts");
   if (cs.n_advice_queries > H2MI_MAX_QUERIES || cs.n_fixed_queries > H2MI_MAX_QUERIES) bad("query counts");
   for (uint32_t j = 0; j < cs.n_perm; j++) {
@@ -691,7 +691,12 @@ struct h2mi_prover_s {
   void* combine_ctx = nullptr;
   // buffers
   std::vector<Forms> advice, z;
-  Dev instance, instance_poly, instance_coset;
+  // the instance columns (cs.n_instance of each): rows, extended coset, and — allocated when a column first holds more than 16 values
+  // and takes the transform route — coefficients
+  std::vector<Dev> instance, instance_poly, instance_coset;
+  // h2mi_prover_instances: the public inputs of the NEXT proof, per column, Montgomery; consumed (or dropped) by its phase-0 call
+  std::vector<std::vector<Fr>> pending_instances;
+  bool have_pending_instances = false;
   // both sides of an argument given as expressions, compressed with theta: on the rows, and the same on the extended coset
   struct Sides {
     Dev input, table, in_coset, tab_coset;
@@ -731,7 +736,6 @@ struct h2mi_prover_s {
   bool keyed = false;
   uint8_t key[32] = {0};
   uint64_t seed = 0;
-  std::vector<Fr> instance_vals;
   bool advice_sparse = true;
   Fr beta, gamma;
   std::vector<ProverQuery> queries;
@@ -758,10 +762,18 @@ struct h2mi_prover_s {
     const void *adv[H2MI_MAX_ADVICE], *fix[H2MI_MAX_FIXED];
     for (uint32_t j = 0; j < cs.n_advice; j++) adv[j] = coset ? advice[j].coset->p : advice[j].value->p;
     for (uint32_t j = 0; j < cs.n_fixed; j++) fix[j] = coset ? pk->fixed_cosets[j]->p : pk->fixed_values[j]->p;
-    const void* inst = cs.n_instance ? (coset ? instance_coset->p : instance->p) : nullptr;
-    check(h2mi_plonk_expr_compress_ch_dev(adv, cs.n_advice, fix, cs.n_fixed, inst, &prog, challenge_limbs(), pk->phases.n_challenges, cs.k,
+    const h2mi_instance_cosets inst = instance_columns(coset);
+    check(h2mi_plonk_expr_compress_in_dev(adv, cs.n_advice, fix, cs.n_fixed, &inst, &prog, challenge_limbs(), pk->phases.n_challenges, cs.k,
                                           coset ? pk->domain.extended_k() : cs.k, (th ? *th : theta).l, (char*)out.p + at * 32, nullptr),
           "expr_compress");
+  }
+  // every instance column on the rows (coset = false) or on the extended coset, as the interpreting kernels take them
+  h2mi_instance_cosets instance_columns(bool coset) const {
+    h2mi_instance_cosets ic;
+    std::memset(&ic, 0, sizeof(ic));
+    ic.n_instance = pk->cs.n_instance;
+    for (uint32_t i = 0; i < ic.n_instance; i++) ic.column[i] = coset ? instance_coset[i]->p : instance[i]->p;
+    return ic;
   }
   // both sides of argument i of `sl` (a lookup given as expressions, a shuffle) on the rows or on the extended coset: input set j
   // lands one domain's length behind set j - 1 in `in`, the table (shuffle) side in `tab`
@@ -772,7 +784,7 @@ struct h2mi_prover_s {
   // a permutation column on the rows (coset = false) or on the extended coset
   const void* perm_column(const h2mi_column& c, bool coset) const {
     if (c.kind == H2MI_COL_ADVICE) return coset ? advice[c.index].coset->p : advice[c.index].value->p;
-    if (c.kind == H2MI_COL_INSTANCE) return coset ? instance_coset->p : instance->p;
+    if (c.kind == H2MI_COL_INSTANCE) return coset ? instance_coset[c.index]->p : instance[c.index]->p;
     return coset ? pk->fixed_cosets[c.index]->p : pk->fixed_values[c.index]->p;
   }
   const uint64_t* challenge_limbs() const { return pk->phases.n_challenges ? (const uint64_t*)challenges.data() : nullptr; }
@@ -866,9 +878,10 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
   for (Forms& f : p.advice) f.alloc(n, ext);
   p.z.resize(pk->n_sets);
   for (Forms& f : p.z) f.alloc(n, ext);
-  if (cs.n_instance) {
-    p.instance = vec(n);
-    p.instance_coset = vec(ext);
+  p.instance_poly.resize(cs.n_instance);
+  for (uint32_t i = 0; i < cs.n_instance; i++) {
+    p.instance.push_back(vec(n));
+    p.instance_coset.push_back(vec(ext));
   }
   for (uint32_t l = 0; l < cs.n_lookups; l++) {
     if (pk->lookup_exprs) {
@@ -928,6 +941,14 @@ void phase_advice(h2mi_prover_s& p, uint32_t ph, const h2mi_column_cells* advice
   const uint32_t bf = cs.blinding_factors, u = pk.u, na = cs.n_advice;
   const Phase was = p.phase;
   p.phase = IDLE;  // whatever is refused below abandons the proof
+  // the public inputs of this proof, per instance column: what h2mi_prover_instances left (it holds for this proof only, taken or
+  // refused), or column 0 through the older arguments
+  std::vector<std::vector<Fr>> inst;
+  const bool by_columns = ph == 0 && p.have_pending_instances;
+  if (ph == 0) {
+    inst.swap(p.pending_instances);
+    p.have_pending_instances = false;
+  }
   if (ph >= phases.n_phases) throw Error(H2MI_EINVAL, "advice phase beyond the key's");
   if (ph > 0 && (was != ADVICE_PHASES || p.advice_done != ph)) throw Error(H2MI_EINVAL, "advice phases out of order");
   for (uint32_t j = 0; j < na; j++)
@@ -936,15 +957,20 @@ void phase_advice(h2mi_prover_s& p, uint32_t ph, const h2mi_column_cells* advice
   if (ph == 0) {  // a new proof: the seed and the public inputs
     if (seed >> (p.keyed ? 61 : 32)) throw Error(H2MI_EINVAL, p.keyed ? "nonce must be below 2^61" : "seed must be below 2^32");
     if (n_inst && (!cs.n_instance || !instance)) throw Error(H2MI_EINVAL, "public inputs without an instance column");
+    if (n_inst && cs.n_instance > 1) throw Error(H2MI_EINVAL, "several instance columns: the public inputs go through h2mi_prover_instances");
+    if (n_inst && by_columns) throw Error(H2MI_EINVAL, "public inputs both through h2mi_prover_instances and through the advice call");
     if (n_inst > u) throw Error(H2MI_ERANGE, "more public inputs than usable rows");
     p.seed = seed;
     p.have_challenges = false;
     p.have_theta = false;
-    p.instance_vals.resize(n_inst);
-    if (n_inst) std::memcpy(p.instance_vals.data(), instance, n_inst * 32);
-    if (cs.n_instance) {
-      h2mi_column_cells ic = {nullptr, instance, n_inst, 0};
-      fill_column(*p.instance, n, ic, u, pl);
+    inst.resize(cs.n_instance);
+    if (n_inst) {
+      inst[0].resize(n_inst);
+      std::memcpy(inst[0].data(), instance, n_inst * 32);
+    }
+    for (uint32_t i = 0; i < cs.n_instance; i++) {
+      h2mi_column_cells ic = {nullptr, (const uint64_t*)inst[i].data(), inst[i].size(), 0};
+      fill_column(*p.instance[i], n, ic, u, pl);
     }
   }
   // witness cells + blinding rows.  Assigned cells and blinding rows of every column travel in ONE launch's arguments when the
@@ -978,12 +1004,29 @@ void phase_advice(h2mi_prover_s& p, uint32_t ph, const h2mi_column_cells* advice
   check(h2mi_stream_wait(p.side, nullptr), "stream_wait");
   for (uint32_t j : mine) p.forms(p.advice[j], p.side);
   if (ph == 0 && cs.n_instance) {
-    if (n_inst <= 16) {  // a handful of public inputs: sum_r v_r * (l_0's coset rotated by r rows), no transform
-      check(h2mi_plonk_instance_coset_dev(pk.l0->p, cs.k, pk.domain.extended_k(), instance, n_inst, p.instance_coset->p, p.side), "instance coset");
-    } else {
-      if (!p.instance_poly) p.instance_poly = vec(n);
-      to_poly_and_coset(pk.domain, *p.instance, *p.instance_poly, *p.instance_coset, p.side);
+    // a column of a handful of public inputs: sum_r v_r * (l_0's coset rotated by r rows), no transform — one column by the launch
+    // it has always had, the short columns of a key with several in ONE launch; a longer column goes through the transforms
+    const void* short_vals[H2MI_MAX_INSTANCE];
+    size_t short_counts[H2MI_MAX_INSTANCE];
+    void* short_out[H2MI_MAX_INSTANCE];
+    uint32_t n_short = 0;
+    for (uint32_t i = 0; i < cs.n_instance; i++) {
+      if (inst[i].size() <= 16) {
+        short_vals[n_short] = inst[i].data();
+        short_counts[n_short] = inst[i].size();
+        short_out[n_short++] = p.instance_coset[i]->p;
+      } else {
+        if (!p.instance_poly[i]) p.instance_poly[i] = vec(n);
+        to_poly_and_coset(pk.domain, *p.instance[i], *p.instance_poly[i], *p.instance_coset[i], p.side);
+      }
     }
+    if (cs.n_instance == 1 && n_short)
+      check(h2mi_plonk_instance_coset_dev(pk.l0->p, cs.k, pk.domain.extended_k(), (const uint64_t*)short_vals[0], short_counts[0], short_out[0], p.side),
+            "instance coset");
+    else if (n_short)
+      check(h2mi_plonk_instance_coset_multi_dev(pk.l0->p, cs.k, pk.domain.extended_k(), (const uint64_t* const*)short_vals, short_counts, n_short, short_out,
+                                                p.side),
+            "instance coset");
   }
   p.read_points(mine.size(), points_out);
   p.advice_done = ph + 1;
@@ -1086,8 +1129,9 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
     uint32_t n_polys = 0;
     for (uint32_t i = 0; i < pk.check_gates.n_ops; i++) n_polys += pk.check_gates.ops[i].op == H2MI_EXPR_END;
     std::vector<uint32_t> report(2 * (size_t)n_polys);
-    check(h2mi_plonk_expr_check_ch_dev(adv, cs.n_advice, fix, cs.n_fixed, cs.n_instance ? p.instance->p : nullptr, &pk.check_gates, p.challenge_limbs(),
-                                       pk.phases.n_challenges, cs.k, (uint32_t)n, report.data(), nullptr, nullptr),
+    const h2mi_instance_cosets inst = p.instance_columns(false);
+    check(h2mi_plonk_expr_check_in_dev(adv, cs.n_advice, fix, cs.n_fixed, &inst, &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, cs.k,
+                                       (uint32_t)n, report.data(), nullptr, nullptr),
           "expr_check");
     for (uint32_t j = 0; j < n_polys; j++)
       if (report[2 * j]) out.push_back({H2MI_CHECK_GATE, j, report[2 * j + 1], report[2 * j]});
@@ -1288,14 +1332,15 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
 // ---- phase 4: the quotient (plonk/evaluation.rs evaluate_h + vanishing division), its pieces committed ---------------------------
 // every extended-coset vector of one circuit as the interpreting quotient kernels take them: the columns a program may query through
 // one pointer table, the permutation argument, the lookups (given as expressions: compressed on the extended coset here)
-void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_cosets& sc, h2mi_logup_cosets& lg) {
+void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_cosets& sc, h2mi_logup_cosets& lg, h2mi_instance_cosets& ic) {
   const h2mi_pk_s& pk = *p.pk;
   const h2mi_constraint_system& cs = pk.cs;
   const uint32_t L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
   std::memset(&ec, 0, sizeof(ec));
   for (uint32_t j = 0; j < cs.n_advice; j++) ec.advice[j] = p.advice[j].coset->p;
   for (uint32_t j = 0; j < cs.n_fixed; j++) ec.fixed[j] = pk.fixed_cosets[j]->p;
-  if (cs.n_instance) ec.instance = p.instance_coset->p;
+  ic = p.instance_columns(true);
+  ec.instance = ic.column[0];  // what the calls without an h2mi_instance_cosets read
   ec.n_perm = m;
   ec.chunk_len = pk.chunk;
   for (uint32_t j = 0; j < m; j++) {
@@ -1369,10 +1414,11 @@ void phase_quotient(const Circuits& all, const Fr& y, uint64_t* points_out) {
     // shape through the equivalent program keygen built for the witness check, which computes the same field elements
     std::vector<h2mi_expr_cosets> ec(all.size());
     std::vector<h2mi_shuffle_cosets> sc(all.size());
+    std::vector<h2mi_instance_cosets> ic(all.size());
     h2mi_logup_cosets lg;  // the key's: the same for every member
-    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i], sc[i], lg);
+    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i], sc[i], lg, ic[i]);
     const std::vector<Fr>& t_inv = d.t_inv();
-    check(h2mi_plonk_evaluate_h_expr_batch_lg_dev(ec.data(), pk.n_shuffles ? sc.data() : nullptr, &lg, (uint32_t)ec.size(), &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
+    check(h2mi_plonk_evaluate_h_expr_batch_in_dev(ec.data(), pk.n_shuffles ? sc.data() : nullptr, &lg, ic.data(), (uint32_t)ec.size(), &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
                                                   d.extended_k(), cs.blinding_factors, p.beta.l, p.gamma.l, y.l, pk.delta.l, d.get_g_coset().l,
                                                   d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
@@ -1414,8 +1460,9 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
     h2mi_expr_cosets ec;
     h2mi_shuffle_cosets sc;
     h2mi_logup_cosets lg;
-    fill_expr_cosets(p, ec, sc, lg);
-    check(h2mi_plonk_evaluate_h_expr_lg_dev(&ec, pk.n_shuffles ? &sc : nullptr, &lg, &pk.gate_program, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
+    h2mi_instance_cosets ic;
+    fill_expr_cosets(p, ec, sc, lg, ic);
+    check(h2mi_plonk_evaluate_h_expr_in_dev(&ec, pk.n_shuffles ? &sc : nullptr, &lg, &ic, &pk.gate_program, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
                                             d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l,
                                             (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
@@ -2109,12 +2156,35 @@ int h2mi_prover_get_counts(h2mi_prover_t prover, h2mi_prover_counts* out) {
   return H2MI_OK;
 }
 
+int h2mi_prover_instances(h2mi_prover_t prover, const h2mi_column_cells* instance) {
+  if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
+  h2mi_prover_s& p = *prover;
+  p.pending_instances.clear();  // a refusal leaves nothing behind: the next proof's columns are then empty
+  p.have_pending_instances = false;
+  const h2mi_constraint_system& cs = p.pk->cs;
+  if (cs.n_instance && !instance) return H2MI_EINVAL;
+  return guarded([&] {
+    std::vector<std::vector<Fr>> cols(cs.n_instance);
+    for (uint32_t i = 0; i < cs.n_instance; i++) {
+      const h2mi_column_cells& c = instance[i];
+      if (c.rows) throw Error(H2MI_EINVAL, "an instance column's values lie on rows 0 .. count - 1");
+      if (c.count && !c.values) throw Error(H2MI_EINVAL, "column cells without values");
+      if (c.count > p.pk->u) throw Error(H2MI_ERANGE, "more public inputs than usable rows (InstanceTooLarge)");
+      cols[i].resize(c.count);
+      for (size_t r = 0; r < c.count; r++) cols[i][r] = cell_value(c, r);
+    }
+    p.pending_instances.swap(cols);
+    p.have_pending_instances = true;
+  });
+}
 int h2mi_prover_advice(h2mi_prover_t prover, const h2mi_column_cells* advice, const uint64_t* instance, size_t n_instance_values, uint64_t seed,
                        uint64_t* points_out) {
   if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
   if (!advice) return H2MI_EINVAL;
   if (prover->pk->phases.n_phases > 1) {  // the advice of such a key is committed phase by phase
     prover->phase = IDLE;
+    prover->pending_instances.clear();
+    prover->have_pending_instances = false;
     return H2MI_EINVAL;
   }
   return guarded([&] { phase_advice(*prover, 0, advice, instance, n_instance_values, seed, points_out); });

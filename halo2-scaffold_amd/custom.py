@@ -457,7 +457,7 @@ class ConstraintSystem:
         return abi
 
     def _abi(self, k: int) -> engine.ConstraintSystem:
-        assert self.n_instance <= 1, "the prover ABI takes one instance column"
+        assert self.n_instance <= engine.MAX_INSTANCE, "the prover ABI takes up to eight instance columns"
         return engine.ConstraintSystem.build(k, self.n_advice, self.n_fixed, self.n_instance, self.degree(), self.blinding_factors(),
                                              engine.GATES_EXPRESSIONS, [], [(_KIND[kind], c) for kind, c in self.perm_columns], [],
                                              self.advice_queries, self.fixed_queries)
@@ -465,14 +465,20 @@ class ConstraintSystem:
 
 class Assignment:
     """what synthesize() leaves, through the calls of halo2's Region: sparse cells per column, the copy constraints in call order, the
-    public inputs (one instance column)"""
+    public inputs — `instance` is the list of values of the one instance column, or, for a constraint system with several instance
+    columns, one list per column (missing columns are empty)"""
 
     def __init__(self, cs: ConstraintSystem, instance=(), challenges=()):
         self.cs = cs
         self.challenges = list(challenges)  # the values known to this run of synthesize(): integers, None for those not yet squeezed
         self.advice = [dict() for _ in range(cs.n_advice)]
         self.fixed = [dict() for _ in range(cs.n_fixed)]
-        self.instance = [v % R for v in instance]
+        if cs.n_instance > 1:
+            assert engine.instance_columns(instance) is not None or not len(instance), "several instance columns: one list of values per column"
+            assert len(instance) <= cs.n_instance, "more lists of public inputs than instance columns"
+            self.instance = [[v % R for v in col] for col in instance] + [[] for _ in range(cs.n_instance - len(instance))]
+        else:
+            self.instance = [v % R for v in instance]
         self.copies = []  # ((kind, column, row), (kind, column, row))
 
     def assign_advice(self, column: Column, row: int, value: int) -> Cell:
@@ -506,6 +512,13 @@ class Assignment:
         return new
 
 
+def instance_columns(asg: Assignment) -> list:
+    """the public inputs of an assignment as one list per instance column, whichever form asg.instance has"""
+    if asg.cs.n_instance > 1:
+        return asg.instance
+    return [asg.instance] if asg.cs.n_instance else []
+
+
 def mock(asg: Assignment, k: int, challenges=()) -> None:
     """MockProver::run(k, ..).assert_satisfied() on the host: no cell or copy constraint beyond the usable rows, every gate polynomial
     zero on every usable row (unassigned cells are zero; rotations wrap around 2^k), every copy constraint between equal cells, every
@@ -519,12 +532,13 @@ def mock(asg: Assignment, k: int, challenges=()) -> None:
     rows = [(f"fixed column {c}", max(cells)) for c, cells in enumerate(asg.fixed) if cells]
     rows += [(f"advice column {c}", max(cells)) for c, cells in enumerate(asg.advice) if cells]
     rows += [("a copy constraint", max(left[2], right[2])) for left, right in asg.copies]
-    rows.append(("the instance column", len(asg.instance) - 1))
+    inst = instance_columns(asg)
+    rows += [("the instance column" if len(inst) == 1 else f"instance column {c}", len(col) - 1) for c, col in enumerate(inst)]
     for what, row in rows:
         if row >= u:
             raise ValueError(f"NotEnoughRowsAvailable: {what} reaches row {row}, the usable rows end at {u}")
     value = {ADVICE: lambda c, r: asg.advice[c].get(r, 0), FIXED: lambda c, r: asg.fixed[c].get(r, 0),
-             INSTANCE: lambda c, r: asg.instance[r] if r < len(asg.instance) else 0}
+             INSTANCE: lambda c, r: inst[c][r] if r < len(inst[c]) else 0}
     for name, poly in zip(cs.gate_names, cs.polynomials):
         for row in range(u):
             if poly.evaluate(lambda kind, c, rot: value[kind](c, (row + rot) % n), challenges):
@@ -638,7 +652,7 @@ def prove_many(pk, assignments, instances=None, seeds=None, params: ParamsKZG = 
     params = params if params is not None else pk.params
     n_challenges = len(getattr(getattr(pk, "cs", None), "challenge_phase", ()))
     wits = [_PhasedWitness(a, n_challenges) if callable(a) else a for a in assignments]
-    instances = [list(w.instance) for w in wits] if instances is None else [list(v) for v in instances]
+    instances = [list(w.instance) for w in wits] if instances is None else [list(v) for v in instances]  # per circuit: flat, or a list of columns
     seeds = [1 + 8 * i for i in range(len(wits))] if seeds is None else list(seeds)
     own = ws is None
     ws = ws or BatchWorkspace(params, pk, len(wits))
@@ -646,7 +660,7 @@ def prove_many(pk, assignments, instances=None, seeds=None, params: ParamsKZG = 
         transcript = transcript or flex.Blake2bWrite.init()
         transcript.common_scalar(flex._m(pk.transcript_repr))
         for inst in instances:  # KZG: every circuit's public inputs are hashed as scalars, in circuit order
-            for v in inst:
+            for v in engine.instance_values(inst):  # a circuit with several instance columns: column by column
                 transcript.common_scalar(flex._m(v))
         ws.batch.drive([w.advice for w in wits], instances, seeds, transcript, trace, hooks, multiopen=multiopen)
         return transcript.finalize()

@@ -27,6 +27,7 @@ MAX_GATES, MAX_PERM, MAX_LOOKUPS, MAX_QUERIES = 32, 64, 8, 192  # H2MI_MAX_* (in
 MAX_SHUFFLES = 8  # H2MI_MAX_SHUFFLES (include/h2mi.h)
 MAX_LOGUP_INPUTS = 6  # H2MI_MAX_LOGUP_INPUTS (include/h2mi.h)
 MAX_ADVICE, MAX_CHALLENGES, MAX_ADVICE_PHASES = 64, 16, 3
+MAX_INSTANCE = 8  # H2MI_MAX_INSTANCE (include/h2mi.h)
 
 # h2mi_prover_buffer kinds
 (BUF_ADVICE, BUF_ADVICE_POLY, BUF_ADVICE_COSET, BUF_INSTANCE, BUF_PERM_Z, BUF_PERM_Z_POLY, BUF_PERM_Z_COSET, BUF_LOOKUP_PERMUTED_INPUT,
@@ -269,6 +270,24 @@ def pack_cells(columns):
     return arr, keep
 
 
+def instance_columns(instance):
+    """the public inputs of one circuit as callers give them -> None for a flat list of integers (one instance column: the form
+    every caller has used so far), or the list of columns for a list of lists (`&[&[col_0], &[col_1], ..]`)"""
+    instance = list(instance)
+    if all(isinstance(v, (int, np.integer)) for v in instance):
+        return None
+    if any(isinstance(v, (int, np.integer)) for v in instance):
+        raise ValueError("public inputs are a flat list of integers (one instance column) or a list of columns, not a mixture")
+    return [list(col) for col in instance]
+
+
+def instance_values(instance):
+    """the public inputs of one circuit in the order the transcript hashes them (KZG: as scalars, before the advice): column by
+    column, each column's values in row order"""
+    columns = instance_columns(instance)
+    return list(instance) if columns is None else [v for col in columns for v in col]
+
+
 class DevView:
     """a device vector owned by the library (h2mi_prover_buffer / h2mi_prover_pk_buffer): the DevBuf read interface, no ownership"""
 
@@ -464,10 +483,29 @@ class Prover:
         check(lib.h2mi_prover_gwc_num_points(self.handle, C.byref(n)), "gwc_num_points")
         return n.value
 
+    def set_instances(self, columns) -> None:
+        """h2mi_prover_instances: the public inputs of the NEXT proof, one list of integers per instance column (it holds for that
+        proof only)"""
+        cells, keep = pack_cells(columns)
+        check(lib.h2mi_prover_instances(self.handle, cells), "instances")
+        del keep
+
+    def _public_inputs(self, instance):
+        """what the advice call takes for `instance` -> (limbs, count): a flat list travels in its arguments as ever; a list of
+        columns goes through h2mi_prover_instances first and leaves the arguments empty"""
+        columns = instance_columns(instance)
+        if columns is not None:
+            self.set_instances(columns)
+            instance = []
+        inst = np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in instance])) if len(instance) else np.zeros((1, 4), dtype=np.uint64)
+        return inst, len(instance)
+
     def drive(self, advice, instance, seed: int, transcript: Blake2bWrite, trace: dict = None, witness_check: str = None,
               multiopen: str = "shplonk"):
         """create_proof between the transcript's challenges.  advice: one {row: value} dict or dense list per advice column;
-        instance: the public inputs (integers).  The caller has hashed vk.transcript_repr and the public inputs already.
+        instance: the public inputs — a flat list of integers (one instance column), or a list of columns, each a list of integers (any
+        number of instance columns; engine.instance_values gives the order in which the caller hashes them).  The caller has hashed
+        vk.transcript_repr and the public inputs already.
         A key with several advice phases or with challenges: `advice` may be a callable, synthesize(challenges) -> such a list,
         called once per advice phase with the challenges known so far (integers; None for those not yet squeezed), of whose result
         only that phase's columns are taken [RECALL halo2_proofs v2023_02_02 plonk/prover.rs]; a plain list serves every phase.
@@ -489,11 +527,11 @@ class Prover:
 
         marks = [("start", time.perf_counter())]
         mark = (lambda name: marks.append((name, time.perf_counter()))) if trace is not None else (lambda name: None)
-        inst = np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in instance])) if len(instance) else np.zeros((1, 4), dtype=np.uint64)
+        inst, n_inst = self._public_inputs(instance)
         pc = self.phase_counts
         if pc.n_phases == 1 and pc.n_challenges == 0 and not callable(advice):
             cells, keep = pack_cells(advice)
-            self._phase(lib.h2mi_prover_advice(h, cells, inst.ctypes.data, len(instance), seed, pp), "advice")
+            self._phase(lib.h2mi_prover_advice(h, cells, inst.ctypes.data, n_inst, seed, pp), "advice")
             del keep
             write_points(c.advice)
         else:
@@ -503,7 +541,7 @@ class Prover:
             for phase in range(pc.n_phases):
                 columns = advice(list(known)) if callable(advice) else advice
                 cells, keep = pack_cells([cells_ if column_phase[j] == phase else {} for j, cells_ in enumerate(columns)])
-                self._phase(lib.h2mi_prover_advice_phase(h, phase, cells, inst.ctypes.data, len(instance), seed, pp), f"advice phase {phase}")
+                self._phase(lib.h2mi_prover_advice_phase(h, phase, cells, inst.ctypes.data, n_inst, seed, pp), f"advice phase {phase}")
                 del keep
                 write_points(pc.advice[phase])
                 for i in range(pc.n_challenges):  # in index order, the challenges usable after this phase
@@ -593,7 +631,7 @@ class Batch:
 
     def drive(self, advices, instances, seeds, transcript: Blake2bWrite, trace: dict = None, hooks: dict = None, multiopen: str = "shplonk"):
         """create_proof for the batch between the transcript's challenges.  advices[i] / instances[i] / seeds[i]: what Prover.drive
-        takes, for circuit i (a callable synthesize(challenges) per circuit when the witness reads challenges: every circuit's
+        takes, for circuit i — instances[i] flat or a list of columns, every member with its own — (a callable synthesize(challenges) per circuit when the witness reads challenges: every circuit's
         commitments of a phase precede that phase's challenges, which all circuits then read).  The caller has hashed
         vk.transcript_repr and every circuit's public inputs, in circuit order.  hooks (tests): "products_done"(batch) is called when
         every member has run its products, "y"(limbs) -> the y handed to the library instead of the transcript's.
@@ -613,7 +651,7 @@ class Batch:
             for pt in pts:
                 transcript.write_point(pt)
 
-        insts = [np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in inst])) if len(inst) else np.zeros((1, 4), dtype=np.uint64) for inst in instances]
+        pubs = [p._public_inputs(inst) for p, inst in zip(ms, instances)]  # every member's own columns, read by its phase-0 call
         column_phase = lead.keys.phases.advice_phase if lead.keys.phases is not None else [0] * c.advice
         challenge_phase = lead.keys.phases.challenge_phase if pc.n_challenges else []
         limbs, known = [None] * pc.n_challenges, [None] * pc.n_challenges
@@ -622,12 +660,13 @@ class Batch:
             for i, p in enumerate(ms):  # this phase's commitments of every circuit, in circuit order
                 columns = advices[i](list(known)) if callable(advices[i]) else advices[i]
                 pp = p._points.ctypes.data
+                inst, n_inst = pubs[i]
                 if single:
                     cells, keep = pack_cells(columns)
-                    p._phase(lib.h2mi_prover_advice(p.handle, cells, insts[i].ctypes.data, len(instances[i]), seeds[i], pp), "advice")
+                    p._phase(lib.h2mi_prover_advice(p.handle, cells, inst.ctypes.data, n_inst, seeds[i], pp), "advice")
                 else:
                     cells, keep = pack_cells([cells_ if column_phase[j] == phase else {} for j, cells_ in enumerate(columns)])
-                    p._phase(lib.h2mi_prover_advice_phase(p.handle, phase, cells, insts[i].ctypes.data, len(instances[i]), seeds[i], pp), f"advice phase {phase}")
+                    p._phase(lib.h2mi_prover_advice_phase(p.handle, phase, cells, inst.ctypes.data, n_inst, seeds[i], pp), f"advice phase {phase}")
                 del keep
                 write(points(p, pc.advice[phase]))
             for i in range(pc.n_challenges):  # then its challenges, once for the proof

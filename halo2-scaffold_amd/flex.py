@@ -416,7 +416,7 @@ def create_proof(params: ParamsKZG, pk: FlexKeys, asg: Assignment, seed: int, tr
     try:
         transcript = transcript or Blake2bWrite.init()
         transcript.common_scalar(_m(pk.transcript_repr))
-        for v in asg.instance:  # KZG: the public inputs are hashed as scalars, not committed
+        for v in engine.instance_values(asg.instance):  # KZG: the public inputs are hashed as scalars, not committed; column by column
             transcript.common_scalar(_m(v))
         ws.prover.drive(asg.advice, asg.instance, seed, transcript, trace, multiopen=multiopen)
         return transcript.finalize()
@@ -434,7 +434,7 @@ def device_check(params: ParamsKZG, pk, asg, seed: int = 1, ws: FlexWorkspace = 
     try:
         transcript = Blake2bWrite.init()
         transcript.common_scalar(_m(pk.transcript_repr))
-        for v in asg.instance:
+        for v in engine.instance_values(asg.instance):
             transcript.common_scalar(_m(v))
         return ws.prover.drive(asg.advice, asg.instance, seed, transcript, trace, witness_check="only")
     finally:

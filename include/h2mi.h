@@ -353,6 +353,13 @@ int h2mi_fr_sort_unique_dev(const void* d_in, uint32_t count, void* d_sorted_can
  * elements coeff_to_extended(lagrange_to_coeff(column)) yields.  values: count x 4 limbs, Montgomery. */
 int h2mi_plonk_instance_coset_dev(const void* d_l0_coset, uint32_t k, uint32_t extended_k, const uint64_t* values, size_t count, void* d_out,
                                   h2mi_stream_t stream);
+/* The same for the n_columns <= H2MI_MAX_INSTANCE instance columns of one circuit in ONE launch: column c holds counts[c] <= 16 public
+ * inputs values[c] (counts[c] x 4 limbs, Montgomery; may be NULL with a count of 0: the column is zero) and its coset form goes to
+ * d_out[c], 2^extended_k elements.  Every thread loads each rotated l_0 value once for all the columns.  The scaled values travel in a
+ * device buffer written on `stream`.  Column c's words are those of the call above on values[c].  d_out entries must not overlap. */
+#define H2MI_MAX_INSTANCE 8
+int h2mi_plonk_instance_coset_multi_dev(const void* d_l0_coset, uint32_t k, uint32_t extended_k, const uint64_t* const* values, const size_t* counts,
+                                        uint32_t n_columns, void* const* d_out, h2mi_stream_t stream);
 /* commit_product: z[0] = 1, z[i+1] = z[i] (a_i + beta)(t_i + gamma) / ((a'_i + beta)(s'_i + gamma)), i < usable_rows;
  * blinding rows untouched; one field inversion per call.  From 4096 usable rows the product runs over the rows whose ratio can
  * differ from one ((a_i, t_i) != (a'_i, s'_i): all but ~2^17 of 2^22 rows of a range check are skipped) when they are at most
@@ -500,7 +507,7 @@ typedef struct {
 typedef struct {
   const void* advice[H2MI_EXPR_MAX_ADVICE];
   const void* fixed[H2MI_EXPR_MAX_FIXED];
-  const void* instance;
+  const void* instance;       /* instance column 0, or NULL; a circuit with several: h2mi_instance_cosets beside this struct (below) */
   uint32_t n_perm, chunk_len; /* chunk_len = cs.degree() - 2: any length */
   const void* perm_value[H2MI_FLEX_MAX_PERM];
   const void* perm_sigma[H2MI_FLEX_MAX_PERM];
@@ -595,6 +602,28 @@ int h2mi_plonk_evaluate_h_expr_batch_lg_dev(const h2mi_expr_cosets* circuits, co
                                             uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
                                             const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
                                             const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream);
+/* The two calls above for a circuit with SEVERAL INSTANCE COLUMNS (up to H2MI_MAX_INSTANCE: `meta.instance_column()` called more than
+ * once).  An H2MI_EXPR_INSTANCE op carries the column's index as the advice and fixed queries do; the interpreter's pointer table holds
+ * instance column i behind the advice and fixed columns, in slot H2MI_EXPR_MAX_ADVICE + H2MI_EXPR_MAX_FIXED + i.  h2mi_expr_cosets keeps its
+ * layout: its one `instance` pointer is column 0 of every call that takes no `instances`.  `instances` is one entry (the batch call:
+ * n_circuits entries, one per circuit) or NULL; with it, cosets->instance is not read and column i of the circuit is column[i] (a column the
+ * program does not read may be NULL).  NULL is the call above word for word, and so is an entry {1, {cosets->instance}}.
+ * H2MI_EINVAL: n_instance > H2MI_MAX_INSTANCE; a query of a column at or beyond n_instance, or of a NULL column. */
+typedef struct {
+  uint32_t n_instance;
+  const void* column[H2MI_MAX_INSTANCE];
+} h2mi_instance_cosets;
+int h2mi_plonk_evaluate_h_expr_in_dev(const h2mi_expr_cosets* cosets, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                      const h2mi_instance_cosets* instances, const h2mi_gate_program* gates, const uint64_t* challenges,
+                                      uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
+                                      const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
+                                      const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream);
+int h2mi_plonk_evaluate_h_expr_batch_in_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                            const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
+                                            const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
+                                            uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
+                                            const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
+                                            void* d_h_out, h2mi_stream_t stream);
 
 /* A lookup's expressions compressed with theta (plonk/lookup/prover.rs compress_expressions): `exprs` holds m polynomials e_0 ..
  * e_(m-1) and d_out[i] = sum_j e_j(i) theta^(m-1-j) — the fold acc theta + e_j — for the 2^domain_k points the columns are given on:
@@ -609,6 +638,11 @@ int h2mi_plonk_expr_compress_dev(const void* const* d_advice, uint32_t n_advice,
 int h2mi_plonk_expr_compress_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
                                     const void* d_instance, const h2mi_gate_program* exprs, const uint64_t* challenges, uint32_t n_challenges,
                                     uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out, h2mi_stream_t stream);
+/* The same with several instance columns (h2mi_instance_cosets, above: here the columns are given on the 2^domain_k points, whatever
+ * the struct's name says); `instances` NULL: no instance column.  The call above is this one with {1, {d_instance}}. */
+int h2mi_plonk_expr_compress_in_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
+                                    const h2mi_instance_cosets* instances, const h2mi_gate_program* exprs, const uint64_t* challenges,
+                                    uint32_t n_challenges, uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out, h2mi_stream_t stream);
 
 /* ---- the witness check on the rows (what MockProver::run(..).assert_satisfied() answers on the host): does a witness satisfy the
  * circuit, and where not?  Three calls over Lagrange-row columns; each returns when its report is on the host.  h2mi_prover_check
@@ -622,6 +656,11 @@ int h2mi_plonk_expr_check_ch_dev(const void* const* d_advice, uint32_t n_advice,
                                  const void* d_instance, const h2mi_gate_program* polys, const uint64_t* challenges, uint32_t n_challenges,
                                  uint32_t k, uint32_t n_rows, uint32_t* report_out /* host, n_polys x 2 */, uint32_t* n_polys_out,
                                  h2mi_stream_t stream);
+/* The same with several instance columns on the rows (h2mi_instance_cosets); NULL: none.  The call above is this one with {1, {d_instance}}. */
+int h2mi_plonk_expr_check_in_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
+                                 const h2mi_instance_cosets* instances, const h2mi_gate_program* polys, const uint64_t* challenges,
+                                 uint32_t n_challenges, uint32_t k, uint32_t n_rows, uint32_t* report_out /* host, n_polys x 2 */,
+                                 uint32_t* n_polys_out, h2mi_stream_t stream);
 /* Copy constraints: d_cells holds n_cells x 4 uint32 in DEVICE memory, {column, row, image column, image row} per cell that the
  * permutation moves, columns as indices into d_values (m <= H2MI_FLEX_MAX_PERM Lagrange-row columns, the permutation argument's order)
  * — trusted like the active rows of h2mi_plonk_permutation_products_sparse_dev: every column below m, every row inside its column.

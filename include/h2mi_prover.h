@@ -41,7 +41,9 @@
  *                              the gate polynomials as a postfix program beside the struct (h2mi_gate_program, h2mi.h; keygen through
  *                              h2mi_prover_keygen_gates) which ONE kernel interprets on the extended coset — any query of an advice,
  *                              fixed or instance column at any rotation, constants, + - *, degree up to 9 (permutation chunks up to
- *                              7); permutation and column limits as for FLEX_VERTICAL.  Its lookups are either the
+ *                              7); permutation and column limits as for FLEX_VERTICAL, but up to H2MI_MAX_INSTANCE (h2mi.h: 8)
+ *                              instance columns, any of them in the permutation argument, in gates and on either side of a lookup
+ *                              or shuffle (public inputs per column: h2mi_prover_instances).  Its lookups are either the
  *                              single-expression ones of FLEX_VERTICAL (cs->lookups[], a fixed table sorted once at keygen: the fast
  *                              path of range checks) or DATA as well — any `meta.lookup` / `meta.lookup_any`: per lookup a list of
  *                              (input expression, table expression) pairs in the same postfix form (h2mi_lookup_program; keygen
@@ -97,7 +99,7 @@ typedef struct {
 typedef struct {
   uint32_t k;                 /* rows = 2^k */
   uint32_t n_advice, n_fixed; /* at most H2MI_MAX_ADVICE / H2MI_MAX_FIXED */
-  uint32_t n_instance;        /* 0 or 1 instance columns */
+  uint32_t n_instance;        /* instance columns: 0 .. H2MI_MAX_INSTANCE (8) */
   uint32_t degree;            /* cs.degree(): extended domain 2^ceil(log2((degree - 1) n)), degree - 1 h pieces, permutation chunks of degree - 2 */
   uint32_t blinding_factors;  /* cs.blinding_factors() */
   uint32_t gates;             /* H2MI_GATES_* */
@@ -315,7 +317,8 @@ int h2mi_prover_set_rng_key(h2mi_prover_t prover, const uint8_t key[32]);
  * running on the device behind it. */
 
 /* advice[c]: the witness cells of advice column c (cs->n_advice of them), rows below 2^k - blinding_factors - 1.  instance: the public
- * inputs of the instance column (count values, Montgomery; the caller hashes them into its transcript itself).  seed: stands where the
+ * inputs of the instance column of a key with at most one (count values, Montgomery; the caller hashes them into its transcript itself;
+ * a key with several instance columns: h2mi_prover_instances, below, and 0 values here).  seed: stands where the
  * crate takes `rng` — every blinding scalar is drawn from counter-based SplitMix64 streams of this seed (h2mi_fr_random_dev's
  * generator: seed + 1 advice blinding rows, + 2 permutation products, + 3 the vanishing argument's random polynomial, + 4 permuted
  * lookup columns, + 5 lookup products, + 6 shuffle products; seed < 2^32), or — after h2mi_prover_set_rng_key — the per-proof nonce of the keyed ChaCha20
@@ -323,6 +326,20 @@ int h2mi_prover_set_rng_key(h2mi_prover_t prover, const uint8_t key[32]);
  * points_out: n_advice commitments. */
 int h2mi_prover_advice(h2mi_prover_t prover, const h2mi_column_cells* advice, const uint64_t* instance, size_t n_instance_values, uint64_t seed,
                        uint64_t* points_out);
+/* The public inputs of a circuit with several instance columns (`&[&[col_0], &[col_1], ..]` of create_proof), one entry per instance
+ * column (cs->n_instance of them; NULL is accepted when there are none): `count` values on rows 0 .. count - 1 — rows must be NULL
+ * (H2MI_EINVAL) — Montgomery, or canonical integers with H2MI_CELLS_CANONICAL; the other rows of the column are zero.  H2MI_ERANGE: a
+ * column with more values than usable rows, 2^k - blinding_factors - 1 (the crate's InstanceTooLarge).  The library copies the values:
+ * the caller's memory is free after the call.  The caller hashes them into its transcript itself: column by column, each column's
+ * values in row order.
+ * Called before h2mi_prover_advice (h2mi_prover_advice_phase with phase 0) and holds for THAT proof only, whether the call takes it or
+ * refuses: a proof started without it has empty columns, except for what the `instance` argument of the advice call puts into column
+ * 0.  That argument stays the route of a key with one instance column, where both routes are valid and give the same proof; values
+ * through it on a key with several instance columns, or through both routes for one proof, are H2MI_EINVAL from the advice call.  A
+ * refusal here leaves nothing behind and does not touch a proof in flight.  Columns of at most 16 values take no transform (one
+ * launch for all of them, h2mi_plonk_instance_coset_multi_dev), longer ones are transformed one by one.
+ * Batches: every member has its own instance columns; the call goes to the member, like its advice. */
+int h2mi_prover_instances(h2mi_prover_t prover, const h2mi_column_cells* instance /* cs->n_instance entries */);
 /* The same, one advice phase at a time (a key of h2mi_prover_keygen_phases; on a one-phase key phase 0 IS h2mi_prover_advice, and
  * h2mi_prover_advice on a key with more phases is H2MI_EINVAL).  Per phase p = 0 .. n_phases - 1 the caller synthesizes with the
  * challenges known so far, calls this, writes points_out to its transcript and squeezes, in index order, the challenges whose phase
@@ -474,7 +491,7 @@ int h2mi_prover_get_phase_counts(h2mi_prover_t prover, h2mi_prover_phase_counts*
  * d_ptr_out / count_out receive the vector's address and its length in field elements.  Valid until the prover / pk is destroyed;
  * contents are those of the last proof. */
 enum {
-  H2MI_BUF_ADVICE = 0, H2MI_BUF_ADVICE_POLY, H2MI_BUF_ADVICE_COSET, H2MI_BUF_INSTANCE,
+  H2MI_BUF_ADVICE = 0, H2MI_BUF_ADVICE_POLY, H2MI_BUF_ADVICE_COSET, H2MI_BUF_INSTANCE /* index < n_instance: that column's rows */,
   H2MI_BUF_PERM_Z, H2MI_BUF_PERM_Z_POLY, H2MI_BUF_PERM_Z_COSET,
   H2MI_BUF_LOOKUP_PERMUTED_INPUT, H2MI_BUF_LOOKUP_PERMUTED_TABLE, H2MI_BUF_LOOKUP_Z,
   H2MI_BUF_RANDOM_POLY, H2MI_BUF_H /* (degree - 1) n coefficients: piece i at i n */, H2MI_BUF_H_POLY,
