@@ -7,7 +7,10 @@ Every case is derived from one printed seed; a failure names it.
         phase entry under every flag combination
   NTT   log_n 1 .. 19: forward, inverse with n^-1 fused, coset pre-scale, zero-extended out-of-place
   PROOF StandardPlonk at 2^5 .. 2^14 through the prover ABI (the oracle verifier against the closed-form verifying key), range through
-        the single- and multi-column configurations (oracle/flex.py verifier)"""
+        the single- and multi-column configurations (oracle/flex.py verifier)
+  CUSTOM  (fuzz_custom; not in run()'s mix: run_custom, tools/fuzz_parity.py --custom) one constraint system of
+        tests/random_circuit_cases.py per case — gates, lookups plain / logUp / merged, shuffles, phases, challenges, instance columns,
+        batches, SHPLONK or GWC together — through mock, the device check, create_proof / prove_many and instance_cases.verify_circuits"""
 import ctypes as C
 import random
 import time
@@ -52,7 +55,7 @@ class Fuzzer:
         """h2: the loaded product package (initialised on a GPU)"""
         self.h2, self.seed0 = h2, seed
         self.rng = random.Random(seed)
-        self.counts = {"msm": 0, "msm_batches": 0, "msm_phase_batches": 0, "ntt": 0, "proof": 0, "flex": 0, "flex_wide": 0, "flex_refused": 0}
+        self.counts = {"msm": 0, "msm_batches": 0, "msm_phase_batches": 0, "ntt": 0, "proof": 0, "flex": 0, "flex_wide": 0, "flex_refused": 0, "custom": 0}
         self._big_bases = {}
 
     def run(self, budget_s: float, progress=None) -> dict:
@@ -64,6 +67,73 @@ class Fuzzer:
                 last = time.time()
                 progress(last - t0, self.counts)
         return self.counts
+
+    def run_custom(self, budget_s: float, progress=None) -> dict:
+        """the long sweep's second mix: generated constraint systems only"""
+        t0 = last = time.time()
+        while time.time() - t0 < budget_s:
+            self.fuzz_custom()
+            if progress is not None and time.time() - last > 45:
+                last = time.time()
+                progress(last - t0, self.counts)
+        return self.counts
+
+    def fuzz_custom(self):
+        """one generated constraint system: mock accepts its witness, the device check has nothing to report, the proof is accepted
+        and is rejected with a public input changed, a byte flipped, or read with the other multi-opening"""
+        rng, counts, seed0 = self.rng, self.counts, self.seed0
+        from halo2_scaffold_amd import custom
+
+        import random_circuit_cases
+
+        case = random_circuit_cases.generate(custom, rng.randrange(1 << 30))
+        try:
+            self._custom_case(case)
+        except Exception as e:  # whatever stops the case: the message carries the run's seed and the case
+            raise AssertionError(("custom", seed0, case.describe(), f"{type(e).__name__}: {e}")) from e
+        counts["custom"] += 1
+
+    def _custom_case(self, case):
+        h2, rng, seed0 = self.h2, self.rng, self.seed0
+        from halo2_scaffold_amd import custom
+
+        import instance_cases
+        import random_circuit_cases
+
+        cs, k = case.cs, case.k
+        what = ("custom", seed0, case.describe())
+        challenges = random_circuit_cases.challenges_for(case)
+        for s in case.synthesizers:
+            custom.mock(s(challenges), k, challenges)
+        none = [None] * len(cs.challenge_phase)
+        first = case.synthesizers[0](none)
+        params = h2.ParamsKZG.setup(k, S)
+        keys = custom.Keys(params, cs, first, logup=case.logup)
+        ocs = instance_cases.oracle_cs(cs, "random")
+        oasg = instance_cases.oracle_assignment(ocs, cs, first)
+        vk = FX.VerifierKeys(ocs, k, S, oasg.fixed, oasg.copies)
+        wits = random_circuit_cases.witnesses(case)
+        for w in wits:
+            custom.check(params, keys, w)
+        seed = rng.randrange(1 << 30)
+        if len(wits) > 1:
+            proof = custom.prove_many(keys, wits, seeds=[seed + 8 * i for i in range(len(wits))], multiopen=case.multiopen)
+        else:
+            proof = custom.create_proof(params, keys, wits[0], seed, multiopen=case.multiopen)
+        instances = [instance_cases.columns_of(cs, s(none)) for s in case.synthesizers]
+        verify = lambda pf, inst, ending=case.multiopen: instance_cases.verify_circuits(vk, cs, pf, inst, logup=case.logup, multiopen=ending)
+        assert verify(proof, instances), what
+        bad = bytearray(proof)
+        bad[rng.randrange(len(bad))] ^= 1
+        assert not verify(bytes(bad), instances), ("tampered proof accepted",) + what
+        assert not verify(proof, instances, "gwc" if case.multiopen == "shplonk" else "shplonk"), ("the other ending accepted",) + what
+        filled = [(i, c) for i, cols in enumerate(instances) for c, col in enumerate(cols) if col]
+        if filled:
+            i, c = rng.choice(filled)
+            changed = [instance_cases.tampered(cols, c) if j == i else cols for j, cols in enumerate(instances)]
+            assert not verify(proof, changed), ("changed public input accepted", i, c) + what
+        keys.release()
+        params.release()
 
     def fuzz_msm(self):
         h2, rng, counts, seed0 = self.h2, self.rng, self.counts, self.seed0

@@ -14,7 +14,12 @@ Circuits:
 The verifier: `verify` is tests/gwc_cases.py's `verify` from its signature down to and including the query list, copied line for line
 — that text already reads `instances[i][c]` and `cs.instance_queries`, i.e. any number of instance columns — with BOTH tails behind
 it: ProverSHPLONK's (tests/logup_sets_cases.py's last lines) and ProverGWC's (gwc_cases.gwc_check).  What is new here is only
-`verify_circuits`, which hands every circuit's LIST OF COLUMNS through where the other files wrap one column."""
+`verify_circuits`, which hands every circuit's LIST OF COLUMNS through where the other files wrap one column.
+
+`coset_circuit` / `check_quotient` (GPU tests): a proof's vectors recomputed in Python integers from the prover's row buffers and
+H2MI_BUF_H against `batched_quotient` on every extended-coset point — gates, the permutation argument, lookups (permuted or logUp,
+merged sets), shuffles, challenges, any number of instance columns and circuits; shared by tests/test_gpu_instances.py and
+tests/test_gpu_random_circuits.py."""
 import random
 
 import shuffle_cases
@@ -224,8 +229,11 @@ def extreme_columns(counts, seed: int):
     return cols
 
 
-def batched_quotient(k, extended_k, zeta, extended_omega, delta, blinding_factors, ops, constants, challenges, circuits, shared, beta, gamma, y):
-    """shuffle_cases.batched_quotient with a circuit's "instance" a LIST of columns on the extended coset (an INSTANCE op's index picks one)"""
+def batched_quotient(k, extended_k, zeta, extended_omega, delta, blinding_factors, ops, constants, challenges, circuits, shared, beta, gamma, y,
+                     logup: bool = False):
+    """shuffle_cases.batched_quotient with a circuit's "instance" a LIST of columns on the extended coset (an INSTANCE op's index picks one).
+    logup: a circuit's "lookups" entries are logup_sets_cases.batched_quotient's (LIST of compressed inputs, None, compressed table, M,
+    None, phi) and their terms logup_terms"""
     size, rot = 1 << extended_k, 1 << (extended_k - k)
     t_inv = [pow((pow(zeta * pow(extended_omega, i, R) % R, 1 << k, R) - 1) % R, -1, R) for i in range(rot)]
     sig, chunk = shared["perm_sigmas"], shared["chunk"]
@@ -244,6 +252,9 @@ def batched_quotient(k, extended_k, zeta, extended_omega, delta, blinding_factor
             v = permutation_terms(v, y, beta, gamma, delta, chunk, [p[idx] for p in c["perm_values"]], [s[idx] for s in sig], [z[idx] for z in zs],
                                   [z[nxt] for z in zs], [z[lst] for z in zs], l0, ll, la, x)
             for a_in, b_in, table, pin, ptab, lz in c.get("lookups", ()):
+                if logup:
+                    v = logup_terms(v, y, beta, [a[idx] for a in a_in], table[idx], pin[idx], lz[idx], lz[nxt], l0, ll, la)
+                    continue
                 a_val = a_in[idx] * b_in[idx] % R if b_in is not None else a_in[idx]
                 v = lookup_terms(v, y, beta, gamma, a_val, table[idx], pin[idx], pin[prv], ptab[idx], lz[idx], lz[nxt], l0, ll, la)
             for a_in, s_in, sz in c.get("shuffles", ()):
@@ -251,6 +262,94 @@ def batched_quotient(k, extended_k, zeta, extended_omega, delta, blinding_factor
         out.append(v * t_inv[idx % rot] % R)
         x = x * extended_omega % R
     return out
+
+
+# ---- a proof's vectors in Python integers (GPU tests: the buffers are the device's) -----------------------------------------------------
+def device_values(buf, count):
+    return o.unpack(buf.to_numpy(shape=(count, 4), nbytes=count * 32), R)
+
+
+def _compress_coset(exprs, cols, size, rot, theta, challenges):
+    """custom.Expression list -> the theta-compressed column on the extended coset, point by point: a rotation r reads idx + r rot"""
+    out = []
+    for idx in range(size):
+        q = lambda kind, c, r: cols[kind][c][(idx + r * rot) % size]
+        out.append(compress([e.evaluate(q, challenges) for e in exprs], theta))
+    return out
+
+
+def coset_circuit(cs, keys, prover, k, theta=0, challenges=(), logup: bool = False):
+    """every vector the quotient reads for one circuit, recomputed in Python integers on the extended coset from the ROW buffers of the
+    prover (advice, instance columns, products; per lookup argument the permuted columns and the product, or M and phi of a logUp key;
+    shuffle products) and of the key; nothing is read from a device coset buffer.  -> (circuit, shared, oracle domain, the instance
+    columns' rows) as batched_quotient takes them"""
+    from halo2_scaffold_amd import engine
+
+    n = 1 << k
+    dom = o.Domain(k, cs.degree())
+    size, rot = 1 << dom.extended_k, 1 << (dom.extended_k - k)
+    ext = lambda rows: dom.coeff_to_extended(dom.lagrange_to_coeff(rows))
+    rows_of = lambda views: [device_values(v, n) for v in views]
+    advice = [ext(r) for r in rows_of(prover.views(engine.BUF_ADVICE, cs.n_advice))]
+    fixed = [ext(r) for r in rows_of(keys.fixed_values)]
+    sigma = [ext(r) for r in rows_of(keys.sigma_values)]
+    instance_rows = rows_of(prover.views(engine.BUF_INSTANCE, cs.n_instance))
+    instance = [ext(r) for r in instance_rows]
+    m, chunk = len(cs.perm_columns), cs.degree() - 2
+    n_sets = -(-m // chunk)
+    perm_zs = [ext(r) for r in rows_of(prover.views(engine.BUF_PERM_Z, n_sets))]
+    by_kind = {"advice": advice, "fixed": fixed, "instance": instance}
+    perm_values = [by_kind[kind][c] for kind, c in cs.perm_columns]
+    circuit = {"advice": advice, "fixed": fixed, "instance": instance, "perm_values": perm_values, "perm_zs": perm_zs}
+    L, S = len(cs.lookup_arguments), len(cs.shuffles)
+    declared = cs.lookups
+    view = lambda kind, count, i: ext(device_values(prover.views(kind, count)[i], n))
+    lookups = []
+    for l, arg in enumerate(cs.lookup_arguments):
+        a_ins = [_compress_coset([a for a, _ in declared[j]], by_kind, size, rot, theta, challenges) for j in arg]
+        t_in = _compress_coset([t for _, t in declared[arg[0]]], by_kind, size, rot, theta, challenges)
+        if logup:
+            lookups.append((a_ins, None, t_in, view(engine.BUF_LOGUP_M, L, l), None, view(engine.BUF_LOGUP_PHI, L, l)))
+        else:
+            assert len(a_ins) == 1
+            lookups.append((a_ins[0], None, t_in, view(engine.BUF_LOOKUP_PERMUTED_INPUT, L, l), view(engine.BUF_LOOKUP_PERMUTED_TABLE, L, l),
+                            view(engine.BUF_LOOKUP_Z, L, l)))
+    shuffles = []
+    for i, pairs in enumerate(cs.shuffles):
+        a_in = _compress_coset([a for a, _ in pairs], by_kind, size, rot, theta, challenges)
+        s_in = _compress_coset([s for _, s in pairs], by_kind, size, rot, theta, challenges)
+        shuffles.append((a_in, s_in, view(engine.BUF_SHUFFLE_Z, S, i)))
+    if lookups:
+        circuit["lookups"] = lookups
+    if shuffles:
+        circuit["shuffles"] = shuffles
+    u = n - (cs.blinding_factors() + 1)
+    unit = lambda row: [1 if i == row else 0 for i in range(n)]
+    shared = {"perm_sigmas": sigma, "chunk": chunk, "l0": ext(unit(0)), "l_last": ext(unit(u)), "l_active": ext([1] * u + [0] * (n - u))}
+    return circuit, shared, dom, instance_rows
+
+
+def check_quotient(cs, keys, provers, asgs, k, trace, logup: bool = False):
+    """H2MI_BUF_H of a proof just made (the quotient kernel's values through the inverse transform, a bijection) against
+    batched_quotient on every extended-coset point; the instance buffers against the assignments' public inputs.  provers / asgs: one
+    per circuit of the proof; trace: create_proof's or prove_many's.  -> (the circuits' vectors, the arguments of batched_quotient
+    before `circuits`, the expected vector), for further questions about the same proof"""
+    from halo2_scaffold_amd import engine
+
+    ops, consts = cs.program()
+    challenges = list(trace.get("challenges") or [])
+    built = [coset_circuit(cs, keys, p, k, trace["theta"], challenges, logup) for p in provers]
+    n = 1 << k
+    for (_, _, _, rows), asg in zip(built, asgs):  # H2MI_BUF_INSTANCE, index < n_instance: that column's values, zero below them
+        assert rows == [list(col) + [0] * (n - len(col)) for col in columns_of(cs, asg)]
+    shared, dom = built[0][1], built[0][2]
+    args = (k, dom.extended_k, dom.g_coset, dom.extended_omega, keys_delta(), cs.blinding_factors(), ops, consts, challenges)
+    tail = (shared, trace["beta"], trace["gamma"], trace["y"], logup)
+    want = batched_quotient(*args, [b[0] for b in built], *tail)
+    size = 1 << dom.extended_k
+    got = dom.coeff_to_extended(device_values(provers[0].view(engine.BUF_H), size))
+    assert len(want) == size and got == want
+    return built, args, tail, want
 
 
 # ---- the verifier ---------------------------------------------------------------------------------------------------------------------

@@ -144,54 +144,20 @@ def _case(gpu, name, logup=False):
     return custom_, cs, asg, first, k, params, keys, vk
 
 
-def _coset_circuit(cs, keys, prover, k):
-    """every vector the quotient reads for one circuit of eight_cols (gates and the permutation argument), recomputed in Python integers
-    on the extended coset from the ROW buffers of the prover and of the key; nothing is read from a device coset buffer"""
-    from halo2_scaffold_amd import engine
-
-    n = 1 << k
-    dom = o.Domain(k, cs.degree())
-    ext = lambda rows: dom.coeff_to_extended(dom.lagrange_to_coeff(rows))
-    rows_of = lambda views: [_vals(v, n) for v in views]
-    advice = [ext(r) for r in rows_of(prover.views(engine.BUF_ADVICE, cs.n_advice))]
-    fixed = [ext(r) for r in rows_of(keys.fixed_values)]
-    sigma = [ext(r) for r in rows_of(keys.sigma_values)]
-    instance_rows = rows_of(prover.views(engine.BUF_INSTANCE, cs.n_instance))
-    instance = [ext(r) for r in instance_rows]
-    m, chunk = len(cs.perm_columns), cs.degree() - 2
-    n_sets = -(-m // chunk)
-    perm_zs = [ext(r) for r in rows_of(prover.views(engine.BUF_PERM_Z, n_sets))]
-    by_kind = {"advice": advice, "fixed": fixed, "instance": instance}
-    perm_values = [by_kind[kind][c] for kind, c in cs.perm_columns]
-    u = n - (cs.blinding_factors() + 1)
-    unit = lambda row: [1 if i == row else 0 for i in range(n)]
-    shared = {"perm_sigmas": sigma, "chunk": chunk, "l0": ext(unit(0)), "l_last": ext(unit(u)), "l_active": ext([1] * u + [0] * (n - u))}
-    circuit = {"advice": advice, "fixed": fixed, "instance": instance, "perm_values": perm_values, "perm_zs": perm_zs}
-    return circuit, shared, dom, instance_rows
-
-
 def _check_quotient(cs, keys, provers, asgs, k, trace):
+    """instance_cases.check_quotient (every extended-coset point of H2MI_BUF_H, the instance buffers), then what is particular to these
+    circuits: every instance column is in h"""
     from halo2_scaffold_amd import engine
 
     assert not cs.lookups and not cs.shuffles
-    ops, consts = cs.program()
-    built = [_coset_circuit(cs, keys, p, k) for p in provers]
-    n = 1 << k
-    for (_, _, _, rows), asg in zip(built, asgs):  # H2MI_BUF_INSTANCE, index < n_instance: that column's values, zero below them
-        assert rows == [list(col) + [0] * (n - len(col)) for col in cases.columns_of(cs, asg)]
-    shared, dom = built[0][1], built[0][2]
-    want = cases.batched_quotient(k, dom.extended_k, dom.g_coset, dom.extended_omega, cases.keys_delta(), cs.blinding_factors(), ops, consts, [],
-                                  [b[0] for b in built], shared, trace["beta"], trace["gamma"], trace["y"])
-    size = 1 << dom.extended_k
-    got = dom.coeff_to_extended(_vals(provers[0].view(engine.BUF_H), size))
-    assert len(want) == size and got == want
+    built, args, tail, want = cases.check_quotient(cs, keys, provers, asgs, k, trace)
+    size = len(want)
     # every column is in h: with any one of them zeroed the reference is another vector
     for c in range(cs.n_instance):
         if not any(built[0][0]["instance"][c]):
             continue
         zeroed = [dict(b[0], instance=[col if j != c else [0] * size for j, col in enumerate(b[0]["instance"])]) for b in built]
-        assert cases.batched_quotient(k, dom.extended_k, dom.g_coset, dom.extended_omega, cases.keys_delta(), cs.blinding_factors(), ops, consts, [],
-                                      zeroed, shared, trace["beta"], trace["gamma"], trace["y"]) != want, c
+        assert cases.batched_quotient(*args, zeroed, *tail) != want, c
     with pytest.raises(Exception):
         provers[0].views(engine.BUF_INSTANCE, cs.n_instance + 1)[cs.n_instance]
 
