@@ -75,6 +75,10 @@ def _load():
         "h2mi_fr_add_head_dev": ([vp, vp, sz, vp], C.c_int),
         "h2mi_fr_fill_dev": ([vp, sz, vp, vp], C.c_int),
         "h2mi_fr_mul_dev": ([vp, vp, sz, vp, vp], C.c_int),
+        # assigned cells: ff's BatchInvert, Assigned::evaluate over a vector, and the rational cells of several columns in one chain
+        "h2mi_fr_batch_invert_dev": ([vp, sz, vp, vp], C.c_int),
+        "h2mi_fr_assigned_evaluate_dev": ([vp, sz, vp, vp], C.c_int),
+        "h2mi_fr_assigned_columns_dev": ([vp, C.c_uint32, C.c_int, u64p, vp], C.c_int),
         "h2mi_fr_random_dev": ([vp, sz, C.c_uint64, C.c_uint64, vp], C.c_int),
         "h2mi_fr_random_chacha_dev": ([vp, sz, vp, C.c_uint64, C.c_uint64, vp], C.c_int),
         "h2mi_ntt_bn254_fr": ([vp, vp, C.c_uint32], C.c_int),

@@ -192,6 +192,183 @@ __global__ void __launch_bounds__(256) k_mulscan_apply(fe* local, const fe* offs
   fe_store(p, pack261(f29_mul<F9>(ld261(p), ld261(&offsets[j / MS_TILE]))));
 }
 
+// ---- assigned cells: num / den with ONE field inversion per call, den = 0 -> 0 ---------------------------------------------------------
+// [RECALL halo2_proofs v2023_02_02 plonk/assigned.rs Assigned::evaluate, poly.rs batch_invert_assigned, ff's BatchInvert — restated from
+// memory: a Rational(n, d) evaluates to n d^-1, a zero denominator is skipped by the batched inversion and the cell evaluates to 0.]
+// Montgomery's trick in tiles of ASG_TILE elements, three launches whatever the size (the ratios() chain above has no rule for zeros and
+// takes every element through HBM about ten times):
+//   (a) k_assigned_tile_products: every workgroup multiplies its tile's denominators, a zero replaced by one, and writes ONE word;
+//   (b) k_assigned_tile_inverses: one workgroup — exclusive prefix and suffix products of the tile products (runs per thread as in
+//       k_mulscan_offsets), the ONE inversion (of the grand total, wavefront-uniform), tileinv_t = pre_t suf_t / total;
+//   (c) k_assigned_finish: every workgroup reloads its tile, scans the 256 thread products both ways in LDS, forms
+//       den_i^-1 = (left)(right) tileinv_t (the other denominators of the thread), multiplies by the numerator, SELECTS zero where the
+//       denominator was zero (no branch around a multiplication) and stores the canonical Montgomery-2^256 word — contiguous or through a row list.
+// A thread owns four consecutive elements: 128 B (denominators alone) or 256 B (pairs) of whole cache lines, no staging through LDS.
+// The products live in the lazy 29-bit-limb layer as Montgomery-2^261 values; num 2^256 times (den^-1 2^261) / 2^261 is the result in the
+// columns' own form, so the way out costs no conversion.
+constexpr uint32_t ASG_TILE = 1024;
+constexpr uint32_t ASG_MAX_SEGS = 64;  // = H2MI_MAX_ADVICE / H2MI_MAX_FIXED: every column of a call in one chain
+// where element e of the staging vector lands: segment s covers e in [start[s], start[s + 1]); dst[s] + (e - start[s]), or
+// dst[s] + rows[s][e - start[s]] with a row list.  2 KB by value.
+struct AssignedSegs {
+  fe* dst[ASG_MAX_SEGS];
+  const uint32_t* rows[ASG_MAX_SEGS];
+  uint64_t start[ASG_MAX_SEGS + 1];
+  uint32_t n_segs;
+};
+// one operand as a normalized Montgomery-2^261 value: from the Montgomery-2^256 word, or from a canonical integer (counted when not below r)
+__device__ __forceinline__ f29 asg_load261(const fe* p, int canonical, uint32_t& bad) {
+  const fe w = fe_load(p);
+  uint32_t borrow;
+  raw_sub_mod<Fr>(w, borrow);
+  bad += (canonical && !borrow) ? 1u : 0u;
+  return f29_mul<F9>(f29_unpack(w.v), canonical ? f29_const<F9>(F9::R2) : f29_const<F9>(F9::TO261));
+}
+__device__ __forceinline__ f29 asg_select(bool c, const f29& a, const f29& b) {  // c ? a : b, limb by limb
+  f29 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.v[i] = c ? a.v[i] : b.v[i];
+  return r;
+}
+// the thread's four denominators (one beyond n; a zero replaced by one and remembered in `zero`), Montgomery-2^261
+__device__ __forceinline__ void asg_load_dens(const fe* in, uint32_t stride, size_t n, size_t e0, int canonical, f29 d[4], bool zero[4], uint32_t& bad) {
+  const f29 one = f29_const<F9>(F9::ONE);
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    d[r] = one;
+    zero[r] = false;
+    if (e0 + r < n) {
+      const f29 v = asg_load261(&in[(e0 + r) * stride + (stride - 1)], canonical, bad);
+      zero[r] = f29_is_zero_mod<F9>(v);
+      d[r] = asg_select(zero[r], one, v);
+    }
+  }
+}
+__global__ void __launch_bounds__(256) k_assigned_tile_products(const fe* in, uint32_t stride, size_t n, int canonical, fe* totals, unsigned long long* invalid) {
+  __shared__ fe tprod[256];
+  const uint32_t tid = threadIdx.x;
+  f29 d[4];
+  bool zero[4];
+  uint32_t bad = 0;
+  asg_load_dens(in, stride, n, (size_t)blockIdx.x * ASG_TILE + 4 * tid, canonical, d, zero, bad);
+  if (bad) atomicAdd(invalid, (unsigned long long)bad);
+  tprod[tid] = pack261(f29_mul<F9>(f29_mul<F9>(d[0], d[1]), f29_mul<F9>(d[2], d[3])));
+  __syncthreads();
+  for (uint32_t w = 128; w; w >>= 1) {
+    if (tid < w) tprod[tid] = pack261(f29_mul<F9>(f29_unpack(tprod[tid].v), f29_unpack(tprod[tid + w].v)));
+    __syncthreads();
+  }
+  if (tid == 0) fe_store(&totals[blockIdx.x], tprod[0]);
+}
+// inclusive Hillis-Steele scan over sh[0 .. used) — forward (prefix) or backward (suffix); every thread of the workgroup calls it
+__device__ __forceinline__ void asg_scan(fe* sh, uint32_t tid, uint32_t used, bool backward) {
+  for (uint32_t dd = 1; dd < used; dd <<= 1) {
+    const bool on = backward ? tid + dd < used : (tid >= dd && tid < used);
+    fe v = one261();
+    if (on) v = sh[backward ? tid + dd : tid - dd];
+    __syncthreads();
+    if (on) sh[tid] = pack261(f29_mul<F9>(f29_unpack(sh[tid].v), f29_unpack(v.v)));
+    __syncthreads();
+  }
+}
+__global__ void __launch_bounds__(1024) k_assigned_tile_inverses(const fe* totals, uint32_t ntiles, fe* tileinv) {
+  __shared__ fe sh[1024];
+  __shared__ fe sh_inv;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t per = (ntiles + 1023) / 1024;
+  const uint32_t lo = min(tid * per, ntiles), hi = min(lo + per, ntiles);
+  const uint32_t used = (ntiles + per - 1) / per;  // threads that own a run
+  f29 run = f29_const<F9>(F9::ONE);
+  for (uint32_t b = lo; b < hi; b++) run = f29_mul<F9>(run, ld261(&totals[b]));
+  const fe mine = pack261(run);
+  sh[tid] = mine;
+  __syncthreads();
+  asg_scan(sh, tid, used, false);
+  f29 left = f29_const<F9>(F9::ONE);
+  if (tid && tid < used) left = f29_unpack(sh[tid - 1].v);
+  if (tid < 64) {  // (total 2^261) read as Montgomery-2^256 is (32 total) 2^256; its inverse times 2^10 is total^-1 2^261 (k_fr_inv_one).
+    fe inv = fe_inv_ds<Fr>(sh[used - 1]);  // Every lane inverts the same value: the division steps' branches are wavefront-uniform
+    for (int q = 0; q < 10; q++) inv = fe_dbl<Fr>(inv);
+    if (tid == 0) sh_inv = inv;
+  }
+  __syncthreads();
+  sh[tid] = mine;
+  __syncthreads();
+  asg_scan(sh, tid, used, true);
+  f29 right = f29_const<F9>(F9::ONE);
+  if (tid + 1 < used) right = f29_unpack(sh[tid + 1].v);
+  // the run again: forward with the prefix (times 1 / total), backward with the suffix
+  f29 acc = f29_mul<F9>(left, f29_unpack(sh_inv.v));
+  for (uint32_t b = lo; b < hi; b++) {
+    fe_store(&tileinv[b], pack261(acc));
+    acc = f29_mul<F9>(acc, ld261(&totals[b]));
+  }
+  acc = right;
+  for (uint32_t b = hi; b-- > lo;) {
+    fe_store(&tileinv[b], pack261(f29_mul<F9>(ld261(&tileinv[b]), acc)));
+    acc = f29_mul<F9>(acc, ld261(&totals[b]));
+  }
+}
+__global__ void __launch_bounds__(256) k_assigned_finish(const fe* in, uint32_t stride, size_t n, int canonical, const fe* tileinv, AssignedSegs segs,
+                                                         unsigned long long* invalid) {
+  __shared__ fe pre[256], suf[256];
+  const uint32_t tid = threadIdx.x;
+  const size_t e0 = (size_t)blockIdx.x * ASG_TILE + 4 * tid;
+  f29 d[4];
+  bool zero[4];
+  uint32_t bad = 0;
+  asg_load_dens(in, stride, n, e0, canonical, d, zero, bad);  // the denominators were counted in pass (a)
+  bad = 0;
+  const f29 p1 = f29_mul<F9>(d[0], d[1]), p2 = f29_mul<F9>(p1, d[2]);  // products from the left ...
+  const f29 s2 = f29_mul<F9>(d[2], d[3]), s1 = f29_mul<F9>(d[1], s2);  // ... and from the right
+  const fe q = pack261(f29_mul<F9>(p1, s2));
+  pre[tid] = q;
+  suf[tid] = q;
+  __syncthreads();
+  for (uint32_t dd = 1; dd < 256; dd <<= 1) {  // pre: inclusive prefix products of the thread products; suf: inclusive suffix products
+    fe vp = one261(), vs = one261();
+    if (tid >= dd) vp = pre[tid - dd];
+    if (tid + dd < 256) vs = suf[tid + dd];
+    __syncthreads();
+    pre[tid] = pack261(f29_mul<F9>(f29_unpack(pre[tid].v), f29_unpack(vp.v)));
+    suf[tid] = pack261(f29_mul<F9>(f29_unpack(suf[tid].v), f29_unpack(vs.v)));
+    __syncthreads();
+  }
+  // c = tileinv * (thread products to the left) * (thread products to the right); threads 0 and 255 have one side only and discard a product
+  const f29 ti = ld261(&tileinv[blockIdx.x]);
+  f29 c = asg_select(tid != 0, f29_mul<F9>(ti, f29_unpack(pre[tid ? tid - 1 : 0].v)), ti);
+  c = asg_select(tid < 255, f29_mul<F9>(c, f29_unpack(suf[tid < 255 ? tid + 1 : 255].v)), c);
+  // the numerator as the plain Montgomery-2^256 word: times (1 / d) 2^261, divided by 2^261, is the cell.  A canonical integer gets its
+  // 2^256 first (times 2^517 / 2^261); batch_invert's numerator is the Montgomery one
+  const f29 c517 = f29_mul<F9>(f29_const<F9>(F9::R2), f29_const<F9>(F9::TO256));
+  uint32_t seg = 0;
+  auto finish = [&](uint32_t r, const f29& inv, bool was_zero) {
+    const size_t e = e0 + r;
+    if (e >= n) return;
+    f29 num = f29_const<F9>(F9::TO256);
+    if (stride == 2) {
+      const fe w = fe_load(&in[2 * e]);
+      uint32_t borrow;
+      raw_sub_mod<Fr>(w, borrow);
+      bad += (canonical && !borrow) ? 1u : 0u;
+      num = f29_unpack(w.v);
+      if (canonical) num = f29_mul<F9>(num, c517);  // uniform over the launch
+    }
+    const f29 v = f29_reduce_canonical<F9>(f29_mul<F9>(num, inv));
+    fe o;
+    f29_pack(asg_select(was_zero, f29_zero(), v), o.v);
+    while (seg + 1 < segs.n_segs && e >= segs.start[seg + 1]) seg++;
+    const size_t off = e - segs.start[seg];
+    fe_store(&segs.dst[seg][segs.rows[seg] ? (size_t)segs.rows[seg][off] : off], o);
+  };
+  // 1 / d_r = c * (the thread's other three denominators)
+  finish(0, f29_mul<F9>(c, s1), zero[0]);
+  finish(1, f29_mul<F9>(f29_mul<F9>(c, d[0]), s2), zero[1]);
+  finish(2, f29_mul<F9>(f29_mul<F9>(c, p1), d[3]), zero[2]);
+  finish(3, f29_mul<F9>(c, p2), zero[3]);
+  if (bad) atomicAdd(invalid, (unsigned long long)bad);
+}
+
 // up to H2MI_FLEX_MAX_PERM columns by value: 3.1 KB of the 4 KB a launch's arguments may take
 struct PermArgs {
   const fe* value[H2MI_FLEX_MAX_PERM];
@@ -1180,6 +1357,91 @@ static int ratios(const RatioTmp& t, size_t total, hipStream_t s) {
 static int running_product(const RatioTmp& t, size_t total, hipStream_t s) {
   const int rc = ratios(t, total, s);
   return rc ? rc : mulscan(t.num, total, 0, t.totals, t.offsets, s);
+}
+
+// ---- assigned cells (kernels: k_assigned_*) -------------------------------------------------------------------------------------------
+// the three launches over n staged elements (stride 1: denominators alone, 2: (numerator, denominator) pairs)
+static int assigned_chain(const fe* in, uint32_t stride, size_t n, int canonical, const AssignedSegs& segs, fe* totals, fe* tileinv,
+                          unsigned long long* invalid, hipStream_t s) {
+  const uint32_t ntiles = ceil_div_u32(n, ASG_TILE);
+  H2_LAUNCH("k_assigned_tile_products", k_assigned_tile_products, ntiles, 256, 0, s, in, stride, n, canonical, totals, invalid);
+  H2_LAUNCH("k_assigned_tile_inverses", k_assigned_tile_inverses, 1, 1024, 0, s, (const fe*)totals, ntiles, tileinv);
+  H2_LAUNCH("k_assigned_finish", k_assigned_finish, ntiles, 256, 0, s, in, stride, n, canonical, (const fe*)tileinv, segs, invalid);
+  return H2MI_OK;
+}
+static int assigned_vector(const void* d_in, uint32_t stride, size_t n, void* d_out, h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (n == 0) return H2MI_OK;
+  if (!d_in || !d_out || ((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u) || n > ((size_t)1 << 32)) return H2MI_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  hipStream_t s = pick_stream(stream);
+  const uint32_t ntiles = ceil_div_u32(n, ASG_TILE);
+  int rc = ensure_tmp(2 * (size_t)ntiles + 1, s);
+  if (rc) return rc;
+  AssignedSegs segs;
+  memset(&segs, 0, sizeof(segs));
+  segs.n_segs = 1;
+  segs.dst[0] = (fe*)d_out;
+  segs.start[1] = n;
+  rc = assigned_chain((const fe*)d_in, stride, n, 0, segs, tmp_base(), tmp_base() + ntiles, reinterpret_cast<unsigned long long*>(tmp_base() + 2 * (size_t)ntiles), s);
+  return rc ? rc : release_tmp(s);
+}
+int h2mi_fr_batch_invert_dev(const void* d_in, size_t n, void* d_out, h2mi_stream_t stream) { return assigned_vector(d_in, 1, n, d_out, stream); }
+int h2mi_fr_assigned_evaluate_dev(const void* d_pairs, size_t n, void* d_out, h2mi_stream_t stream) {
+  if (n && d_pairs == d_out) return H2MI_EINVAL;  // a thread's four results would overwrite pairs of its neighbours
+  return assigned_vector(d_pairs, 2, n, d_out, stream);
+}
+int h2mi_fr_assigned_columns_dev(const h2mi_assigned_cells* cols, uint32_t n_cols, int canonical, uint64_t* invalid_out, h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (invalid_out) *invalid_out = 0;
+  if (n_cols == 0) return H2MI_OK;
+  if (!cols || n_cols > ASG_MAX_SEGS || (canonical && !invalid_out)) return H2MI_EINVAL;
+  size_t total = 0, listed = 0;
+  for (uint32_t i = 0; i < n_cols; i++) {
+    if (!cols[i].d_column || !cols[i].pairs || cols[i].count == 0 || ((uintptr_t)cols[i].d_column & 15u)) return H2MI_EINVAL;
+    total += cols[i].count;
+    if (cols[i].rows) listed += cols[i].count;
+  }
+  if (total > ((size_t)1 << 32)) return H2MI_ERANGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  hipStream_t s = pick_stream(stream);
+  const uint32_t ntiles = ceil_div_u32(total, ASG_TILE);
+  const size_t rows_fe = (listed + 7) / 8;  // eight row indices per 32 bytes
+  int rc = ensure_tmp(2 * total + rows_fe + 2 * (size_t)ntiles + 1, s);
+  if (rc) return rc;
+  fe* pairs = tmp_base();
+  uint32_t* rows = reinterpret_cast<uint32_t*>(pairs + 2 * total);
+  fe* totals = pairs + 2 * total + rows_fe;
+  unsigned long long* invalid = reinterpret_cast<unsigned long long*>(totals + 2 * (size_t)ntiles);
+  AssignedSegs segs;
+  memset(&segs, 0, sizeof(segs));
+  segs.n_segs = n_cols;
+  size_t at = 0, at_rows = 0;
+  for (uint32_t i = 0; i < n_cols; i++) {
+    H2_HIP(hipMemcpyAsync(pairs + 2 * at, cols[i].pairs, cols[i].count * 64, hipMemcpyHostToDevice, s));
+    segs.dst[i] = (fe*)cols[i].d_column;
+    segs.start[i] = at;
+    if (cols[i].rows) {
+      H2_HIP(hipMemcpyAsync(rows + at_rows, cols[i].rows, cols[i].count * 4, hipMemcpyHostToDevice, s));
+      segs.rows[i] = rows + at_rows;
+      at_rows += cols[i].count;
+    }
+    at += cols[i].count;
+  }
+  segs.start[n_cols] = total;
+  // the caller's buffers are free when this call returns, as after h2mi_memcpy_h2d on the plain route: columns of 64 MB and more are
+  // not images the runtime is sure to have staged by the time hipMemcpyAsync returns.  The chain itself stays asynchronous
+  H2_HIP(hipStreamSynchronize(s));
+  if (canonical) H2_HIP(hipMemsetAsync(invalid, 0, 8, s));
+  rc = assigned_chain(pairs, 2, total, canonical, segs, totals, totals + ntiles, invalid, s);
+  if (rc) return rc;
+  rc = release_tmp(s);
+  if (rc || !canonical) return rc;
+  unsigned long long v = 0;
+  H2_HIP(hipMemcpyAsync(&v, invalid, 8, hipMemcpyDeviceToHost, s));
+  H2_HIP(hipStreamSynchronize(s));
+  *invalid_out = v;
+  return H2MI_OK;
 }
 
 static bool rows_out_of_range(uint32_t k, uint32_t usable_rows) {

@@ -37,10 +37,29 @@ Dev zeros(size_t count) {
 }
 inline void* at(const DeviceVec& d, size_t row) { return (char*)d.p + row * 32; }
 
+// long runs of rational cells (H2MI_CELLS_RATIONAL), collected across the columns of a phase or a keygen: ONE device chain and one
+// field inversion for all of them (h2mi_fr_assigned_columns_dev), each column's cells landing in its own column.  Columns whose
+// halves are canonical integers and columns of Montgomery words are two chains: the conversion is per launch
+struct RationalList {
+  std::vector<h2mi_assigned_cells> cols[2];
+  void add(const DeviceVec& d, const h2mi_column_cells& c) { cols[c.flags & H2MI_CELLS_CANONICAL ? 1 : 0].push_back({d.p, c.rows, c.values, c.count}); }
+  void flush() {
+    for (int canonical = 0; canonical < 2; canonical++) {
+      std::vector<h2mi_assigned_cells> list;
+      list.swap(cols[canonical]);
+      if (list.empty()) continue;
+      uint64_t bad = 0;
+      check(h2mi_fr_assigned_columns_dev(list.data(), (uint32_t)list.size(), canonical, &bad, nullptr), "assigned cells");
+      if (bad) throw Error(H2MI_EINVAL, "a cell value is not reduced modulo r");
+    }
+  }
+};
+
 // cells that travel in kernel arguments (h2mi_fr_patch_cells_dev: one launch per 64), collected across the columns of a phase
 struct PatchList {
   std::vector<void*> cells;
   std::vector<Fr> vals;
+  RationalList rational;  // what the same columns resolve on the device
   void add(const DeviceVec& d, size_t row, const Fr& v) {
     cells.push_back(at(d, row));
     vals.push_back(v);
@@ -50,15 +69,17 @@ struct PatchList {
     for (uint32_t r = 0; r < bf; r++) add(z, u + 1 + r, blind[bf * i + r]);
   }
   void flush() {
+    rational.flush();
     if (!cells.empty()) check(h2mi_fr_patch_cells_dev(cells.data(), (const uint64_t*)vals.data(), cells.size(), nullptr), "patch_cells");
     cells.clear();
     vals.clear();
   }
 };
 
-Fr cell_value(const h2mi_column_cells& c, size_t i) {
+// the 32-byte value at c.values + 4 * word: cell `word` of a plain column, half `word` of a rational one (numerator 2 i, denominator 2 i + 1)
+Fr cell_value(const h2mi_column_cells& c, size_t word) {
   Fr v;
-  std::memcpy(v.l, c.values + 4 * i, 32);
+  std::memcpy(v.l, c.values + 4 * word, 32);
   if (!(c.flags & H2MI_CELLS_CANONICAL)) return v;
   for (int j = 3; j >= 0; j--) {
     if (v.l[j] < fr::MODULUS[j]) return fr::mul(v, fr::R2);
@@ -66,17 +87,34 @@ Fr cell_value(const h2mi_column_cells& c, size_t i) {
   }
   throw Error(H2MI_EINVAL, "a cell value is not reduced modulo r");
 }
+// a short run of rational cells on the host: numerator / denominator, 0 where the denominator is 0 [RECALL Assigned::evaluate,
+// batch_invert_assigned], one zero-skipping batched inversion per column.  (The launch-bound proofs of 2^5 .. 2^8 rows: the device
+// chain is three launches and an upload.)
+std::vector<Fr> resolve_rational(const h2mi_column_cells& c) {
+  std::vector<Fr> v(c.count);
+  for (size_t i = 0; i < c.count; i++) v[i] = cell_value(c, 2 * i + 1);
+  v = fr::batch_invert_skip_zero(v);
+  for (size_t i = 0; i < c.count; i++) v[i] = fr::mul(cell_value(c, 2 * i), v[i]);
+  return v;
+}
 
 // a column of n rows: zero, then the assigned cells.  Short runs ride in the phase's patch launch, long dense runs are one
-// upload (canonical values converted where they land), long scattered runs are staged over their span.
+// upload (canonical values converted where they land), long scattered runs are staged over their span.  Rational cells mirror that:
+// short runs are resolved here and patched, long ones (dense or scattered) join the call's one device chain.
 void fill_column(DeviceVec& d, size_t n, const h2mi_column_cells& c, size_t row_limit, PatchList& pl) {
   check(h2mi_memset_zero(d.p, n * 32), "zero");
   if (c.count == 0) return;
   if (!c.values) throw Error(H2MI_EINVAL, "column cells without values");
+  const bool rational = (c.flags & H2MI_CELLS_RATIONAL) != 0;
   if (!c.rows) {
     if (c.count > row_limit) throw Error(H2MI_ERANGE, "assignment reaches into the blinding rows (NotEnoughRowsAvailable)");
     if (c.count <= 16) {
-      for (size_t i = 0; i < c.count; i++) pl.add(d, i, cell_value(c, i));
+      const std::vector<Fr> resolved = rational ? resolve_rational(c) : std::vector<Fr>();
+      for (size_t i = 0; i < c.count; i++) pl.add(d, i, rational ? resolved[i] : cell_value(c, i));
+      return;
+    }
+    if (rational) {
+      pl.rational.add(d, c);
       return;
     }
     check(h2mi_memcpy_h2d(d.p, c.values, c.count * 32), "column cells");
@@ -94,7 +132,12 @@ void fill_column(DeviceVec& d, size_t n, const h2mi_column_cells& c, size_t row_
   }
   if (hi >= row_limit) throw Error(H2MI_ERANGE, "assignment reaches into the blinding rows (NotEnoughRowsAvailable)");
   if (c.count <= 4096) {
-    for (size_t i = 0; i < c.count; i++) pl.add(d, c.rows[i], cell_value(c, i));
+    const std::vector<Fr> resolved = rational ? resolve_rational(c) : std::vector<Fr>();
+    for (size_t i = 0; i < c.count; i++) pl.add(d, c.rows[i], rational ? resolved[i] : cell_value(c, i));
+    return;
+  }
+  if (rational) {
+    pl.rational.add(d, c);
     return;
   }
   std::vector<Fr> stage((size_t)hi - lo + 1, fr_zero());
@@ -379,10 +422,13 @@ void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells) {
   // values on the usable rows, canonical and Montgomery; unassigned usable rows hold zero
   std::vector<std::pair<Fr, Fr>> vals;  // (canonical, montgomery)
   vals.reserve(cells.count);
+  // this pass reads the caller's cells on the host (the sort below is the host's too): a rational table column is resolved here,
+  // whatever its length, with the values the device column holds
+  const std::vector<Fr> resolved = (cells.flags & H2MI_CELLS_RATIONAL) && cells.count ? resolve_rational(cells) : std::vector<Fr>();
   for (size_t i = 0; i < cells.count; i++) {
     const uint32_t row = cells.rows ? cells.rows[i] : (uint32_t)i;
     if (row >= pk.u) throw Error(H2MI_ERANGE, "lookup table larger than the usable rows (LOOKUP_BITS must be below DEGREE)");
-    const Fr m = cell_value(cells, i);
+    const Fr m = resolved.empty() ? cell_value(cells, i) : resolved[i];
     vals.push_back({to_canonical(m), m});
   }
   const uint64_t zeros_extra = pk.u - cells.count;
@@ -2168,6 +2214,7 @@ int h2mi_prover_instances(h2mi_prover_t prover, const h2mi_column_cells* instanc
     for (uint32_t i = 0; i < cs.n_instance; i++) {
       const h2mi_column_cells& c = instance[i];
       if (c.rows) throw Error(H2MI_EINVAL, "an instance column's values lie on rows 0 .. count - 1");
+      if (c.flags & H2MI_CELLS_RATIONAL) throw Error(H2MI_EINVAL, "public inputs are field elements, not rational cells");
       if (c.count && !c.values) throw Error(H2MI_EINVAL, "column cells without values");
       if (c.count > p.pk->u) throw Error(H2MI_ERANGE, "more public inputs than usable rows (InstanceTooLarge)");
       cols[i].resize(c.count);

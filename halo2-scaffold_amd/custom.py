@@ -34,6 +34,9 @@ rows; required degree 2 + max(1, input degrees, shuffle degrees).  `shuffle_prog
 Merged lookups [RECALL the `mv-lookup` line's merging of lookups over one table — restated from memory and pinned to DESIGN.md 4.5 and
 tests/logup_sets_cases.py]: `merge_lookups(max_degree=None)` is an explicit opt-in that turns the lookups sharing a table into ONE logUp
 argument of several input sets (h2mi_logup_inputs); `Keys(..., logup=True)` then goes through h2mi_prover_keygen_logup.
+Assigned cells [RECALL halo2_proofs v2023_02_02 plonk/assigned.rs]: `assign_advice` / `assign_fixed` take `Rational(numerator,
+denominator)` beside integers — `value.invert()` deferred to the prover, as the reference's is_zero.rs computes value_inv.  Such a
+column crosses to the library unresolved (engine.pack_cells, H2MI_CELLS_RATIONAL) and is inverted there; `mock` evaluates it.
 `mock` is MockProver::run(..).assert_satisfied() on the host, row by row in Python integers; `check` asks the same question of the
 device, at the sizes the prover runs at (h2mi_prover_check: gates, copy constraints and lookups on the columns of a proof in flight).
 """
@@ -85,8 +88,23 @@ class Challenge:
         self.index, self.phase = index, phase
 
 
+Rational = engine.Rational  # Assigned::Rational(numerator, denominator): a cell whose inversion is left to the prover
+
+
+def _assigned(value):
+    """a value as a column keeps it: an integer reduced modulo r, or the Rational as it is (Assigned<F>)"""
+    return value if isinstance(value, Rational) else value % R
+
+
+def _evaluated(value) -> int:
+    """Assigned::evaluate"""
+    return value.evaluate() if isinstance(value, Rational) else value
+
+
 class Cell:
-    def __init__(self, kind: str, column: int, row: int, value: int):
+    """AssignedCell: `value` is what was assigned — an integer, or a Rational (copy_advice copies a rational as a rational)"""
+
+    def __init__(self, kind: str, column: int, row: int, value):
         self.kind, self.column, self.row, self.value = kind, column, row, value
 
 
@@ -481,15 +499,16 @@ class Assignment:
             self.instance = [v % R for v in instance]
         self.copies = []  # ((kind, column, row), (kind, column, row))
 
-    def assign_advice(self, column: Column, row: int, value: int) -> Cell:
+    def assign_advice(self, column: Column, row: int, value) -> Cell:
+        """value: an integer, or a Rational — the column then reaches the prover unresolved and the library inverts"""
         assert column.kind == ADVICE
-        self.advice[column.index][row] = value % R
-        return Cell(ADVICE, column.index, row, value % R)
+        self.advice[column.index][row] = _assigned(value)
+        return Cell(ADVICE, column.index, row, _assigned(value))
 
-    def assign_fixed(self, column: Column, row: int, value: int) -> Cell:
+    def assign_fixed(self, column: Column, row: int, value) -> Cell:
         assert column.kind == FIXED
-        self.fixed[column.index][row] = value % R
-        return Cell(FIXED, column.index, row, value % R)
+        self.fixed[column.index][row] = _assigned(value)
+        return Cell(FIXED, column.index, row, _assigned(value))
 
     def enable_selector(self, selector: Selector, row: int) -> None:
         self.fixed[self.cs.selector_column(selector)][row] = 1
@@ -537,7 +556,7 @@ def mock(asg: Assignment, k: int, challenges=()) -> None:
     for what, row in rows:
         if row >= u:
             raise ValueError(f"NotEnoughRowsAvailable: {what} reaches row {row}, the usable rows end at {u}")
-    value = {ADVICE: lambda c, r: asg.advice[c].get(r, 0), FIXED: lambda c, r: asg.fixed[c].get(r, 0),
+    value = {ADVICE: lambda c, r: _evaluated(asg.advice[c].get(r, 0)), FIXED: lambda c, r: _evaluated(asg.fixed[c].get(r, 0)),
              INSTANCE: lambda c, r: inst[c][r] if r < len(inst[c]) else 0}
     for name, poly in zip(cs.gate_names, cs.polynomials):
         for row in range(u):

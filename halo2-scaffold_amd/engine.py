@@ -20,6 +20,7 @@ from .transcript import Blake2bWrite
 ADVICE, FIXED, INSTANCE = 0, 1, 2  # H2MI_COL_*
 GATES_STANDARD_PLONK, GATES_FLEX_VERTICAL, GATES_EXPRESSIONS = 1, 2, 3
 CELLS_CANONICAL = 1
+CELLS_RATIONAL = 2  # H2MI_CELLS_RATIONAL: (numerator, denominator) pairs, resolved by the library
 KEYGEN_VK_ONLY = 1
 KEYGEN_LOGUP = 2  # H2MI_KEYGEN_LOGUP: the key's program lookups are logUp arguments (include/h2mi_prover.h)
 EUNSAT = -7
@@ -240,10 +241,34 @@ class ColumnCells(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("values", C.c_void_p), ("count", C.c_size_t), ("flags", C.c_uint32)]
 
 
+class Rational:
+    """Assigned::Rational(numerator, denominator) [RECALL halo2_proofs v2023_02_02 plonk/assigned.rs, restated from memory]: a cell whose
+    inversion is deferred to the prover.  evaluate() is Assigned::evaluate: numerator / denominator, and 0 where the denominator is 0.
+    Both halves are kept reduced modulo r; two rationals are equal when their halves are (not when their values are)."""
+    __slots__ = ("numerator", "denominator")
+
+    def __init__(self, numerator: int, denominator: int):
+        self.numerator, self.denominator = numerator % F.FR_MODULUS, denominator % F.FR_MODULUS
+
+    def evaluate(self) -> int:
+        return self.numerator * pow(self.denominator, -1, F.FR_MODULUS) % F.FR_MODULUS if self.denominator else 0
+
+    def __eq__(self, other):
+        return isinstance(other, Rational) and (self.numerator, self.denominator) == (other.numerator, other.denominator)
+
+    def __hash__(self):
+        return hash((self.numerator, self.denominator))
+
+    def __repr__(self):
+        return f"Rational({self.numerator}, {self.denominator})"
+
+
 def pack_cells(columns):
-    """[{row: value} or [value at row 0, 1, ..]] (integers below r) -> (h2mi_column_cells array, objects to keep alive).  The values
-    cross as canonical 32-byte integers (H2MI_CELLS_CANONICAL): one C-level conversion per value and one join here, the Montgomery
-    conversion where they land (long runs: on the device)."""
+    """[{row: value} or [value at row 0, 1, ..]] (integers below r, or Rational) -> (h2mi_column_cells array, objects to keep alive).
+    The values cross as canonical 32-byte integers (H2MI_CELLS_CANONICAL): one C-level conversion per value and one join here, the
+    Montgomery conversion where they land (long runs: on the device).  A column with at least one Rational crosses as (numerator,
+    denominator) pairs (H2MI_CELLS_CANONICAL | H2MI_CELLS_RATIONAL), its integers as (x, 1), and the library resolves it; a column
+    with none crosses exactly as it always has."""
     arr = (ColumnCells * max(len(columns), 1))()
     keep = []
     for i, cells in enumerate(columns):
@@ -256,13 +281,23 @@ def pack_cells(columns):
         count = len(rows)
         if not count:
             continue
+        flags = CELLS_CANONICAL
         try:
-            raw = b"".join(map(int.to_bytes, vals, itertools.repeat(32), itertools.repeat("little")))
+            try:
+                raw = b"".join(map(int.to_bytes, vals, itertools.repeat(32), itertools.repeat("little")))
+            except TypeError:  # a Rational among the values: the plain route above pays nothing for the question
+                vals = cells.values() if isinstance(cells, dict) else cells
+                if not any(isinstance(v, Rational) for v in vals):
+                    raise
+                flags |= CELLS_RATIONAL
+                vals = map(cells.__getitem__, rows) if isinstance(cells, dict) else cells
+                halves = [h for v in vals for h in ((v.numerator, v.denominator) if isinstance(v, Rational) else (v, 1))]
+                raw = b"".join(map(int.to_bytes, halves, itertools.repeat(32), itertools.repeat("little")))
         except OverflowError:
             raise ValueError("a cell value is not reduced modulo r")
         v = np.frombuffer(raw, dtype=np.uint8)
         keep.append(v)
-        arr[i].values, arr[i].count, arr[i].flags = v.ctypes.data, count, CELLS_CANONICAL
+        arr[i].values, arr[i].count, arr[i].flags = v.ctypes.data, count, flags
         if not dense:
             r = np.array(rows, dtype=np.uint32)
             keep.append(r)

@@ -261,6 +261,34 @@ int h2mi_fr_add_head_dev(void* d_poly, const uint64_t* head /* count*4 */, size_
 /* out[i] = a[i] * b[i] over n elements (in place allowed): the row values of a product of columns, e.g. the lookup input
  * q_lookup * a of halo2-base's single-advice-column range check */
 int h2mi_fr_mul_dev(const void* d_a, const void* d_b, size_t n, void* d_out, h2mi_stream_t stream);
+/* ff's BatchInvert: out[i] = in[i]^-1, and out[i] = 0 where in[i] = 0 (a zero is skipped, it does not spoil its neighbours) [RECALL ff
+ * 0.13 BatchInvert / BatchInverter::invert_with_external_scratch, restated from memory].  Inputs are fully reduced Montgomery words;
+ * outputs are the canonical Montgomery words.  ONE field inversion per call whatever n is: Montgomery's trick in tiles of 1024 (three
+ * launches: tile products, the inverses of the tile products, the finish per tile).  In place (d_out == d_in) is allowed.  n = 0: nothing
+ * happens; n > 2^32, a null or misaligned pointer: H2MI_EINVAL. */
+int h2mi_fr_batch_invert_dev(const void* d_in, size_t n, void* d_out, h2mi_stream_t stream);
+/* Assigned::evaluate over a vector [RECALL halo2_proofs v2023_02_02 plonk/assigned.rs, poly.rs batch_invert_assigned]: pairs holds
+ * n x (numerator, denominator), 64 bytes per element; out[i] = numerator[i] * denominator[i]^-1, or 0 where the denominator is 0
+ * (whatever the numerator).  Trivial(x) is (x, 1).  The same chain and the same one inversion as h2mi_fr_batch_invert_dev; d_out must
+ * not be d_pairs. */
+int h2mi_fr_assigned_evaluate_dev(const void* d_pairs, size_t n, void* d_out, h2mi_stream_t stream);
+/* The same for the rational cells of up to 64 COLUMNS in one chain (what h2mi_column_cells with H2MI_CELLS_RATIONAL resolves to,
+ * h2mi_prover.h): every column's pairs (HOST memory, count x 8 limbs) are staged behind one another in the stream's scratch, resolved
+ * with one inversion, and cell i of a column lands at d_column + rows[i] (or + i when rows is NULL; 32-byte elements; the caller has
+ * checked the rows against the column's length).  canonical != 0: both halves are canonical integers; *invalid_out counts the halves
+ * that are not below r (the call then waits for the stream; invalid_out is required).  The call waits for its uploads, so the host
+ * buffers are free when it returns; the chain itself is stream-ordered.  The rows of one column must be distinct: cells that name the
+ * same row are written by different threads in no order.  All columns of a call are staged in ONE slice of 64 bytes per cell (plus 4
+ * per listed row) in the stream's grow-only scratch, which keeps that size afterwards: a call whose cells would fit as resolved
+ * columns can still end in H2MI_ENOMEM — split the columns over several calls then (each pays one inversion).  More than 2^32 cells in
+ * one call: H2MI_ERANGE. */
+typedef struct {
+  void* d_column;
+  const uint32_t* rows;
+  const uint64_t* pairs;
+  size_t count;
+} h2mi_assigned_cells;
+int h2mi_fr_assigned_columns_dev(const h2mi_assigned_cells* cols, uint32_t n_cols, int canonical, uint64_t* invalid_out, h2mi_stream_t stream);
 /* out[i] = value for i < n (Lagrange vectors such as l_active of keygen_pk) */
 int h2mi_fr_fill_dev(void* d_out, size_t n, const uint64_t value[4], h2mi_stream_t stream);
 /* Seeded stand-in for the prover's sweeps of `Scalar::random(rng)` (blinding rows; the vanishing argument's random

@@ -327,6 +327,27 @@ inline std::vector<Fr> batch_invert(const std::vector<Fr>& v) {
   }
   return out;
 }
+// ff's BatchInvert [RECALL, restated from memory]: the same trick over the NONZERO elements — a zero stays zero and does not
+// spoil the others (batch_invert above turns every output to zero when one input is).  One inversion, none when all are zero.
+inline std::vector<Fr> batch_invert_skip_zero(const std::vector<Fr>& v) {
+  auto is_zero = [](const Fr& a) { return (a.l[0] | a.l[1] | a.l[2] | a.l[3]) == 0; };
+  std::vector<Fr> out(v.size());
+  Fr acc = ONE;
+  for (size_t i = 0; i < v.size(); i++) {
+    out[i] = acc;
+    if (!is_zero(v[i])) acc = mul(acc, v[i]);
+  }
+  Fr inv = invert(acc);
+  for (size_t i = v.size(); i-- > 0;) {
+    if (is_zero(v[i])) {
+      out[i] = v[i];
+      continue;
+    }
+    out[i] = mul(out[i], inv);
+    inv = mul(inv, v[i]);
+  }
+  return out;
+}
 // ROOT_OF_UNITY = 7^((r-1)/2^28); ZETA = 7^((r-1)/3)
 inline Fr root_of_unity() {
   // (r - 1) >> 28

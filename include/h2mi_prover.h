@@ -119,6 +119,23 @@ typedef struct {
  * is NULL; every other row of the column is zero.  values: count x 4 limbs.  H2MI_CELLS_CANONICAL in `flags`: the values
  * are canonical little-endian integers below r and the device converts them (for hosts without Montgomery arithmetic). */
 #define H2MI_CELLS_CANONICAL 1u
+/* H2MI_CELLS_RATIONAL: the column is handed over as the circuit ASSIGNED it, before batch_invert_assigned [RECALL halo2_proofs
+ * v2023_02_02 plonk/assigned.rs Assigned::{Zero, Trivial, Rational}, Assigned::evaluate, poly.rs batch_invert_assigned, ff's BatchInvert
+ * (zeros stay in place) — restated from memory like every crate convention here].  values: count x 8 limbs, numerator then denominator
+ * per cell; the cell's value is numerator * denominator^-1, or 0 where the denominator is 0 (whatever the numerator).  Trivial(x)
+ * travels as (x, 1), Zero as (0, 1) or as no cell at all.  With H2MI_CELLS_CANONICAL both halves are canonical integers below r (a half
+ * that is not: H2MI_EINVAL, as for plain cells).  rows means what it means without the flag.  Accepted wherever fixed or advice cells
+ * enter (every h2mi_prover_keygen*, h2mi_prover_advice, h2mi_prover_advice_phase, hence batches); h2mi_prover_instances refuses it
+ * (H2MI_EINVAL): public inputs are field elements.  Short runs (rows NULL: up to 16 cells; a row list: up to 4096 — the runs that ride
+ * in the phase's patch launch) are resolved on the host with one zero-skipping batched inversion per column; longer ones are uploaded
+ * as pairs and all such columns of one call are resolved by ONE device chain with ONE field inversion (h2mi_fr_assigned_columns_dev;
+ * two chains when canonical and Montgomery columns are mixed).  Everything downstream sees the resolved column, byte for byte what
+ * the same values uploaded resolved give; the fixed column behind a cs->lookups[] table, which keygen also reads on the host to sort
+ * it, is resolved there as well.  Each row once, as without the flag — and here it matters more: on the plain route the last of two
+ * cells that name one row wins, on the device chain they are written in no order.  The chain stages 64 bytes per cell of all long
+ * rational columns of the call in one slice of the library's grow-only scratch (three columns at k = 20: 192 MB): where that does not
+ * fit the call is H2MI_ENOMEM although the resolved columns would. */
+#define H2MI_CELLS_RATIONAL 2u
 typedef struct {
   const uint32_t* rows;
   const uint64_t* values;
