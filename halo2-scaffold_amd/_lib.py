@@ -129,6 +129,9 @@ def _load():
                                               C.c_int),
         "h2mi_plonk_evaluate_h_expr_batch_in_dev": ([vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
                                                      vp, vp, vp, vp], C.c_int),
+        # one coset of the extended domain per call (H2MI_KEYGEN_BY_COSET): the batch call's arguments plus the slice
+        "h2mi_plonk_evaluate_h_expr_slice_dev": ([vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
+                                                  vp, vp, C.c_uint32, vp, vp], C.c_int),
         "h2mi_plonk_expr_compress_in_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_expr_check_in_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32), vp],
                                          C.c_int),
@@ -192,6 +195,7 @@ def _load():
         "h2mi_batch_gwc_open": ([vp, vp, vp], C.c_int),
         "h2mi_prover_buffer": ([vp, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(sz)], C.c_int),
         "h2mi_prover_pk_buffer": ([vp, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(sz)], C.c_int),
+        "h2mi_prover_device_bytes": ([vp, C.POINTER(sz), C.POINTER(sz)], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)  # AttributeError here = a symbol the header declares is missing

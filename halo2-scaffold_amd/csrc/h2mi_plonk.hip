@@ -897,6 +897,31 @@ __global__ void __launch_bounds__(256) k_evaluate_h_expr_batch(FlexCosets sh, co
   }
   evaluate_h_finish(acc, ext_k, k, h, idx, out);
 }
+// The same numerator one coset of 2^k points at a time (H2MI_KEYGEN_BY_COSET): extended-coset point c + rot i is X = (zeta w_ext^c) w^i
+// with w = w_ext^rot the domain's generator, so on slice c every vector is the 2^k-point coset transform of its coefficients with shift
+// zeta w_ext^c, a query at rotation r is element (i + r) mod 2^k of the same slice, and the body is the resident one on a domain with
+// ext_k = k: the ops carry r mod n, the power table is w's, h.zeta holds the slice's shift and a logUp lookup's input sets lie 2^k
+// apart.  What knows the extended domain is the finish alone: t_inv[c] and the store at h[c + rot i].
+// (Two waves per SIMD stated: left to itself the allocator takes 255 VGPRs and 2 AGPRs, one register past the two-wave budget the resident
+// kernel keeps; held to it, 199 VGPRs and no scratch.)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_evaluate_h_expr_slice(FlexCosets sh, const CircuitCosets* __restrict__ circuits, uint32_t n_circuits,
+                                                                const fe* __restrict__ consts, const uint2* __restrict__ ops, uint32_t n_ops,
+                                                                uint32_t ext_k, uint32_t k, uint32_t slice, uint32_t last_rot, FlexConsts h,
+                                                                const fe* xlo, const fe* xhi, uint32_t xh, fe* out) {
+  using namespace gen;
+  extern __shared__ uint32_t ex_stack[];  // [level][limb][thread]
+  const uint32_t n = 1u << k;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;  // no barrier below
+  const f29 y = cst(h.y);
+  f29 acc = f29_zero();
+  for (uint32_t m = 0; m < n_circuits; m++) {
+    const CircuitCosets& c = circuits[m];
+    expr_interpret(c.cols, consts, ops, n_ops, i, n, ex_stack, [&](const f29& poly) { horner(acc, y, poly); });
+    evaluate_h_fold(c, sh, k, k, last_rot, h, xlo, xhi, xh, i, acc, y);
+  }
+  evaluate_h_finish(acc, ext_k, k, h, slice + (i << (ext_k - k)), out);
+}
 // The lookup argument's theta compression (plonk/lookup/prover.rs commit_permuted `compress_expressions`, plonk/evaluation.rs for
 // the extended coset [RECALL]): out[i] = sum_j e_j(i) theta^(m-1-j), the fold acc theta + e_j over the program's m polynomials, on
 // the 2^dom_k points of the Lagrange rows (dom_k = k) or of the extended coset.  The same interpreter; the sink at END is Horner's
@@ -1884,16 +1909,18 @@ int h2mi_plonk_evaluate_h_expr_batch_lg_dev(const h2mi_expr_cosets* circuits, co
                                                  blinding_factors, beta, gamma, y, delta, zeta, extended_omega, t_inv, d_h_out, stream);
 }
 
-int h2mi_plonk_evaluate_h_expr_batch_in_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                            const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
-                                            const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
-                                            uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
-                                            const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
-                                            void* d_h_out, h2mi_stream_t stream) {
+// the batch call (slice < 0: every vector on the extended coset) and the by-coset call (every vector the 2^k points of coset `slice`)
+static int evaluate_h_circuits(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                               const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
+                               const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
+                               const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
+                               const uint64_t extended_omega[4], const uint64_t* t_inv, int64_t slice, void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
   if (!circuits || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
   if (n_circuits == 0 || n_circuits > H2MI_MAX_CIRCUITS) return H2MI_EINVAL;
   if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  if (slice >= (int64_t)1 << (extended_k - k)) return H2MI_ERANGE;
+  const uint32_t dom_k = slice < 0 ? extended_k : k;  // the domain the vectors are given on
   const h2mi_expr_cosets& c0 = circuits[0];
   if (c0.n_perm > H2MI_FLEX_MAX_PERM || (c0.n_lookups & ~(uint32_t)H2MI_LOOKUPS_LOGUP) > H2MI_FLEX_MAX_LOOKUPS || (c0.n_perm && c0.chunk_len == 0)) return H2MI_EINVAL;
   // the program, its constants and the challenges once, as the single-circuit call lays them out (the image's own column table is
@@ -1901,7 +1928,7 @@ int h2mi_plonk_evaluate_h_expr_batch_in_dev(const h2mi_expr_cosets* circuits, co
   const InstanceCols inst0(instances, c0.instance);
   if (!inst0.ok) return H2MI_EINVAL;
   ExprImage im;
-  int rc = im.build(gates, challenges, n_challenges, c0.advice, c0.fixed, inst0, k, extended_k);
+  int rc = im.build(gates, challenges, n_challenges, c0.advice, c0.fixed, inst0, k, dom_k);
   if (rc) return rc;
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
   static_assert(sizeof(CircuitCosets) % 8 == 0, "records are arrays of pointers");
@@ -1949,23 +1976,56 @@ int h2mi_plonk_evaluate_h_expr_batch_in_dev(const h2mi_expr_cosets* circuits, co
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
-  PowTab px;
-  rc = get_powtab(extended_omega, extended_k, s, &px);
-  if (rc) return rc;
-  rc = ensure_tmp(im.image.size(), s);
-  if (rc) return rc;
-  fe* d_image = tmp_base();
-  H2_HIP(hipMemcpyAsync(d_image, im.image.data(), im.image.size() * sizeof(fe), hipMemcpyHostToDevice, s));
   const uint32_t rot = 1u << (extended_k - k);
   FlexConsts hc_;
   memset(&hc_, 0, sizeof(hc_));
   hc_.beta = host_fe(beta); hc_.gamma = host_fe(gamma); hc_.y = host_fe(y); hc_.delta = host_fe(delta); hc_.zeta = host_fe(zeta);
   for (uint32_t i = 0; i < rot; i++) hc_.tinv[i] = host_fe(t_inv + 4 * i);
-  const uint32_t size = 1u << extended_k;
-  H2_LAUNCH("k_evaluate_h_expr_batch", k_evaluate_h_expr_batch, ceil_div_u32(size, 256), 256, im.lds, s, sh, (const CircuitCosets*)(d_image + prog_fe),
-            n_circuits, (const fe*)(d_image + im.cols_fe), (const uint2*)(d_image + im.cols_fe + im.const_fe), im.n_ops, extended_k, k,
-            blinding_factors + 1, hc_, (const fe*)px.lo, (const fe*)px.hi, px.h, (fe*)d_h_out);
+  // a slice: X = (zeta extended_omega^slice) omega^i with omega = extended_omega^rot, the generator of the 2^k rows
+  fe x_base = host_fe(extended_omega);
+  if (slice >= 0) {
+    for (int64_t c = 0; c < slice; c++) hc_.zeta = h_mul256(hc_.zeta, x_base);
+    for (uint32_t j = k; j < extended_k; j++) x_base = h_mul256(x_base, x_base);
+  }
+  uint64_t x_words[4];
+  memcpy(x_words, x_base.v, 32);
+  PowTab px;
+  rc = get_powtab(x_words, dom_k, s, &px);
+  if (rc) return rc;
+  rc = ensure_tmp(im.image.size(), s);
+  if (rc) return rc;
+  fe* d_image = tmp_base();
+  H2_HIP(hipMemcpyAsync(d_image, im.image.data(), im.image.size() * sizeof(fe), hipMemcpyHostToDevice, s));
+  const uint32_t size = 1u << dom_k;
+  if (slice < 0)
+    H2_LAUNCH("k_evaluate_h_expr_batch", k_evaluate_h_expr_batch, ceil_div_u32(size, 256), 256, im.lds, s, sh, (const CircuitCosets*)(d_image + prog_fe),
+              n_circuits, (const fe*)(d_image + im.cols_fe), (const uint2*)(d_image + im.cols_fe + im.const_fe), im.n_ops, extended_k, k,
+              blinding_factors + 1, hc_, (const fe*)px.lo, (const fe*)px.hi, px.h, (fe*)d_h_out);
+  else
+    H2_LAUNCH("k_evaluate_h_expr_slice", k_evaluate_h_expr_slice, ceil_div_u32(size, 256), 256, im.lds, s, sh, (const CircuitCosets*)(d_image + prog_fe),
+              n_circuits, (const fe*)(d_image + im.cols_fe), (const uint2*)(d_image + im.cols_fe + im.const_fe), im.n_ops, extended_k, k,
+              (uint32_t)slice, blinding_factors + 1, hc_, (const fe*)px.lo, (const fe*)px.hi, px.h, (fe*)d_h_out);
   return release_tmp(s);
+}
+
+int h2mi_plonk_evaluate_h_expr_batch_in_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                            const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
+                                            const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
+                                            uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
+                                            const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
+                                            void* d_h_out, h2mi_stream_t stream) {
+  return evaluate_h_circuits(circuits, shuffles, logup, instances, n_circuits, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma,
+                             y, delta, zeta, extended_omega, t_inv, -1, d_h_out, stream);
+}
+
+int h2mi_plonk_evaluate_h_expr_slice_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                         const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
+                                         const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
+                                         const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
+                                         const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, uint32_t slice, void* d_h_out,
+                                         h2mi_stream_t stream) {
+  return evaluate_h_circuits(circuits, shuffles, logup, instances, n_circuits, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma,
+                             y, delta, zeta, extended_omega, t_inv, (int64_t)slice, d_h_out, stream);
 }
 
 int h2mi_plonk_expr_compress_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,

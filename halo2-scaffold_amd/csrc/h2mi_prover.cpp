@@ -145,10 +145,13 @@ void fill_column(DeviceVec& d, size_t n, const h2mi_column_cells& c, size_t row_
   check(h2mi_memcpy_h2d(at(d, lo), stage.data(), stage.size() * 32), "column cells");
 }
 
+void to_poly(const poly::EvaluationDomain& dom, const DeviceVec& lagr, DeviceVec& poly, h2mi_stream_t stream = nullptr) {
+  check(h2mi_ntt_bn254_fr_oop_dev(lagr.p, (size_t)1 << dom.k(), poly.p, dom.k(), dom.get_omega_inv().l, nullptr, dom.get_ifft_divisor().l, stream),
+        "lagrange_to_coeff");
+}
 void to_poly_and_coset(const poly::EvaluationDomain& dom, const DeviceVec& lagr, DeviceVec& poly, DeviceVec& coset, h2mi_stream_t stream = nullptr) {
-  const size_t n = (size_t)1 << dom.k();
-  check(h2mi_ntt_bn254_fr_oop_dev(lagr.p, n, poly.p, dom.k(), dom.get_omega_inv().l, nullptr, dom.get_ifft_divisor().l, stream), "lagrange_to_coeff");
-  check(h2mi_ntt_bn254_fr_oop_dev(poly.p, n, coset.p, dom.extended_k(), dom.get_extended_omega().l, dom.get_g_coset().l, nullptr, stream),
+  to_poly(dom, lagr, poly, stream);
+  check(h2mi_ntt_bn254_fr_oop_dev(poly.p, (size_t)1 << dom.k(), coset.p, dom.extended_k(), dom.get_extended_omega().l, dom.get_g_coset().l, nullptr, stream),
         "coeff_to_extended");
 }
 
@@ -371,6 +374,9 @@ struct h2mi_pk_s {
   size_t n, ext;
   uint32_t u, chunk, n_sets;
   bool vk_only = false;
+  // H2MI_KEYGEN_BY_COSET: no extended-coset vector; l_0 / l_last / l_active as coefficients, every slice is a prover's
+  bool by_coset = false;
+  Dev l0_poly, l_last_poly, l_active_poly;
   int users = 0;  // provers created against this key and not yet destroyed
   Fr delta;
   std::vector<Dev> fixed_values, fixed_polys, fixed_cosets, sigma_values, sigma_polys, sigma_cosets;
@@ -494,6 +500,7 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     if (check_shuffle_program(cs, &own, nullptr, &pk.shuffle_slices, pk.phases.n_challenges)) throw Error(H2MI_EINVAL, "shuffle program");
   }
   pk.vk_only = (flags & H2MI_KEYGEN_VK_ONLY) != 0;
+  pk.by_coset = !pk.vk_only && (flags & H2MI_KEYGEN_BY_COSET) != 0;
   pk.logup = lookups && (flags & H2MI_KEYGEN_LOGUP) != 0;
   if (gates) {
     pk.check_gates = pk.gate_program;
@@ -568,30 +575,41 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
   pk.permutation_commitments = commit_points(g_lagrange, pk.sigma_values, n);
   if (pk.vk_only) return pkp;
   for (auto& col : pk.fixed_values) {
-    Dev p = vec(n), e = vec(pk.ext);
-    to_poly_and_coset(dom, *col, *p, *e);
+    Dev p = vec(n), e = pk.by_coset ? nullptr : vec(pk.ext);
+    if (pk.by_coset) to_poly(dom, *col, *p);
+    else to_poly_and_coset(dom, *col, *p, *e);
     pk.fixed_polys.push_back(std::move(p));
-    pk.fixed_cosets.push_back(std::move(e));
+    if (!pk.by_coset) pk.fixed_cosets.push_back(std::move(e));
   }
   for (auto& col : pk.sigma_values) {
-    Dev p = vec(n), e = vec(pk.ext);
-    to_poly_and_coset(dom, *col, *p, *e);
+    Dev p = vec(n), e = pk.by_coset ? nullptr : vec(pk.ext);
+    if (pk.by_coset) to_poly(dom, *col, *p);
+    else to_poly_and_coset(dom, *col, *p, *e);
     pk.sigma_polys.push_back(std::move(p));
-    pk.sigma_cosets.push_back(std::move(e));
+    if (!pk.by_coset) pk.sigma_cosets.push_back(std::move(e));
   }
-  {  // l_0, l_last (row u), l_active = ones on the usable rows: extended-coset forms only
-    Dev l0 = zeros(n), ll = zeros(n), la = vec(n), tmp = vec(n);
+  {  // l_0, l_last (row u), l_active = ones on the usable rows: extended-coset forms only (a by-coset key: coefficients only)
+    Dev l0 = zeros(n), ll = zeros(n), la = vec(n), tmp = pk.by_coset ? nullptr : vec(n);
     pl.add(*l0, 0, fr::ONE);
     pl.add(*ll, u, fr::ONE);
     pl.flush();
     check(h2mi_fr_fill_dev(la->p, n, fr::ONE.l, nullptr), "fill");
     check(h2mi_memset_zero(at(*la, u), (n - u) * 32), "zero");
-    pk.l0 = vec(pk.ext);
-    pk.l_last = vec(pk.ext);
-    pk.l_active = vec(pk.ext);
-    to_poly_and_coset(dom, *l0, *tmp, *pk.l0);
-    to_poly_and_coset(dom, *ll, *tmp, *pk.l_last);
-    to_poly_and_coset(dom, *la, *tmp, *pk.l_active);
+    if (pk.by_coset) {
+      pk.l0_poly = vec(n);
+      pk.l_last_poly = vec(n);
+      pk.l_active_poly = vec(n);
+      to_poly(dom, *l0, *pk.l0_poly);
+      to_poly(dom, *ll, *pk.l_last_poly);
+      to_poly(dom, *la, *pk.l_active_poly);
+    } else {
+      pk.l0 = vec(pk.ext);
+      pk.l_last = vec(pk.ext);
+      pk.l_active = vec(pk.ext);
+      to_poly_and_coset(dom, *l0, *tmp, *pk.l0);
+      to_poly_and_coset(dom, *ll, *tmp, *pk.l_last);
+      to_poly_and_coset(dom, *la, *tmp, *pk.l_active);
+    }
     check(h2mi_sync(), "sync");
   }
   // a lookup given as expressions has no keygen-time table: theta, or an advice column in it, is known only inside a proof
@@ -740,6 +758,11 @@ struct h2mi_prover_s {
   // the instance columns (cs.n_instance of each): rows, extended coset, and — allocated when a column first holds more than 16 values
   // and takes the transform route — coefficients
   std::vector<Dev> instance, instance_poly, instance_coset;
+  // a by-coset key: every `coset` vector of this prover is ONE slice of 2^k elements, filled per slice by the quotient phase, and the
+  // slices of the key's shared columns live here — a batch reads its leader's (`lead`, set by the quotient phase; else this prover)
+  std::vector<Dev> fixed_slices, sigma_slices;
+  Dev l0_slice, l_last_slice, l_active_slice;
+  const h2mi_prover_s* lead = nullptr;
   // h2mi_prover_instances: the public inputs of the NEXT proof, per column, Montgomery; consumed (or dropped) by its phase-0 call
   std::vector<std::vector<Fr>> pending_instances;
   bool have_pending_instances = false;
@@ -795,6 +818,15 @@ struct h2mi_prover_s {
     for (h2mi_stream_t st : {lane[0], lane[1], side})
       if (st) h2mi_stream_destroy(st);
   }
+  // the key's shared columns as the quotient reads them: the key's extended cosets, or the leader's slices
+  const h2mi_prover_s& shared() const { return lead ? *lead : *this; }
+  const void* fixed_coset(uint32_t j) const { return pk->by_coset ? shared().fixed_slices[j]->p : pk->fixed_cosets[j]->p; }
+  const void* sigma_coset(uint32_t j) const { return pk->by_coset ? shared().sigma_slices[j]->p : pk->sigma_cosets[j]->p; }
+  const void* l0_coset() const { return pk->by_coset ? shared().l0_slice->p : pk->l0->p; }
+  const void* l_last_coset() const { return pk->by_coset ? shared().l_last_slice->p : pk->l_last->p; }
+  const void* l_active_coset() const { return pk->by_coset ? shared().l_active_slice->p : pk->l_active->p; }
+  // the length of a `coset` vector: the extended domain, or one slice of it
+  size_t coset_len() const { return pk->by_coset ? pk->n : pk->ext; }
   const DeviceVec& lookup_input(uint32_t l) const {
     if (pk->lookup_exprs) return *lk[l].c.input;
     const h2mi_lookup& d = pk->cs.lookups[l];
@@ -807,10 +839,10 @@ struct h2mi_prover_s {
     const h2mi_constraint_system& cs = pk->cs;
     const void *adv[H2MI_MAX_ADVICE], *fix[H2MI_MAX_FIXED];
     for (uint32_t j = 0; j < cs.n_advice; j++) adv[j] = coset ? advice[j].coset->p : advice[j].value->p;
-    for (uint32_t j = 0; j < cs.n_fixed; j++) fix[j] = coset ? pk->fixed_cosets[j]->p : pk->fixed_values[j]->p;
+    for (uint32_t j = 0; j < cs.n_fixed; j++) fix[j] = coset ? fixed_coset(j) : pk->fixed_values[j]->p;
     const h2mi_instance_cosets inst = instance_columns(coset);
     check(h2mi_plonk_expr_compress_in_dev(adv, cs.n_advice, fix, cs.n_fixed, &inst, &prog, challenge_limbs(), pk->phases.n_challenges, cs.k,
-                                          coset ? pk->domain.extended_k() : cs.k, (th ? *th : theta).l, (char*)out.p + at * 32, nullptr),
+                                          coset && !pk->by_coset ? pk->domain.extended_k() : cs.k, (th ? *th : theta).l, (char*)out.p + at * 32, nullptr),
           "expr_compress");
   }
   // every instance column on the rows (coset = false) or on the extended coset, as the interpreting kernels take them
@@ -824,14 +856,14 @@ struct h2mi_prover_s {
   // both sides of argument i of `sl` (a lookup given as expressions, a shuffle) on the rows or on the extended coset: input set j
   // lands one domain's length behind set j - 1 in `in`, the table (shuffle) side in `tab`
   void compress_sides(const ArgumentSlices& sl, uint32_t i, bool coset, DeviceVec& in, DeviceVec& tab, const Fr* th = nullptr) const {
-    for (uint32_t j = 0; j < sl.sets[i]; j++) compress(sl.input[i][j], coset, in, th, j * (coset ? pk->ext : pk->n));
+    for (uint32_t j = 0; j < sl.sets[i]; j++) compress(sl.input[i][j], coset, in, th, j * (coset ? coset_len() : pk->n));
     compress(sl.table[i], coset, tab, th);
   }
   // a permutation column on the rows (coset = false) or on the extended coset
   const void* perm_column(const h2mi_column& c, bool coset) const {
     if (c.kind == H2MI_COL_ADVICE) return coset ? advice[c.index].coset->p : advice[c.index].value->p;
     if (c.kind == H2MI_COL_INSTANCE) return coset ? instance_coset[c.index]->p : instance[c.index]->p;
-    return coset ? pk->fixed_cosets[c.index]->p : pk->fixed_values[c.index]->p;
+    return coset ? fixed_coset(c.index) : pk->fixed_values[c.index]->p;
   }
   const uint64_t* challenge_limbs() const { return pk->phases.n_challenges ? (const uint64_t*)challenges.data() : nullptr; }
   // a key with challenges: the phases behind the advice need their values
@@ -869,7 +901,10 @@ struct h2mi_prover_s {
     const std::vector<G1Affine> aff = normalize_host_batch(jac);
     std::memcpy(out, aff.data(), k * 64);
   }
-  void forms(Forms& f, h2mi_stream_t stream) { to_poly_and_coset(pk->domain, *f.value, *f.poly, *f.coset, stream); }
+  void forms(Forms& f, h2mi_stream_t stream) {
+    if (pk->by_coset) to_poly(pk->domain, *f.value, *f.poly, stream);  // its slices are the quotient phase's
+    else to_poly_and_coset(pk->domain, *f.value, *f.poly, *f.coset, stream);
+  }
   // `count` blinding scalars for purpose 1 .. 6 (advice rows, permutation products, the random polynomial, permuted lookup columns,
   // lookup products, shuffle products): the streams seed + purpose of the seeded generator, or ChaCha20 stream id (nonce << 3 | purpose) under the key
   std::vector<Fr> blinding(uint32_t purpose, size_t count) const {
@@ -919,7 +954,7 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
   p.lo = lo;
   p.cnt = cnt;
   const h2mi_constraint_system& cs = pk->cs;
-  const size_t n = pk->n, ext = pk->ext;
+  const size_t n = pk->n, ext = pk->by_coset ? pk->n : pk->ext;  // a by-coset key: every `coset` vector is one slice
   p.advice.resize(cs.n_advice);
   for (Forms& f : p.advice) f.alloc(n, ext);
   p.z.resize(pk->n_sets);
@@ -928,6 +963,14 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
   for (uint32_t i = 0; i < cs.n_instance; i++) {
     p.instance.push_back(vec(n));
     p.instance_coset.push_back(vec(ext));
+    if (pk->by_coset) p.instance_poly[i] = vec(n);  // always the coefficient route
+  }
+  if (pk->by_coset) {
+    for (uint32_t j = 0; j < cs.n_fixed; j++) p.fixed_slices.push_back(vec(n));
+    for (uint32_t j = 0; j < cs.n_perm; j++) p.sigma_slices.push_back(vec(n));
+    p.l0_slice = vec(n);
+    p.l_last_slice = vec(n);
+    p.l_active_slice = vec(n);
   }
   for (uint32_t l = 0; l < cs.n_lookups; l++) {
     if (pk->lookup_exprs) {
@@ -946,7 +989,7 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
     p.sf[i].z.alloc(n, ext);
   }
   p.random_poly = vec(n);
-  p.h = vec(ext);
+  p.h = vec(pk->ext);
   p.h_poly = vec(n);
   p.points = vec(3 * std::max<size_t>(max_phase_points(*pk), gwc_num_points(*pk)));  // 96 B per commitment of the largest phase (GWC's tail included)
   for (int i = 0; i < 3; i++) {
@@ -1057,7 +1100,9 @@ void phase_advice(h2mi_prover_s& p, uint32_t ph, const h2mi_column_cells* advice
     void* short_out[H2MI_MAX_INSTANCE];
     uint32_t n_short = 0;
     for (uint32_t i = 0; i < cs.n_instance; i++) {
-      if (inst[i].size() <= 16) {
+      if (pk.by_coset) {  // the shortcut reads an extended l_0: whatever its length the column goes through its coefficients
+        to_poly(pk.domain, *p.instance[i], *p.instance_poly[i], p.side);
+      } else if (inst[i].size() <= 16) {
         short_vals[n_short] = inst[i].data();
         short_counts[n_short] = inst[i].size();
         short_out[n_short++] = p.instance_coset[i]->p;
@@ -1384,14 +1429,14 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_coset
   const uint32_t L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
   std::memset(&ec, 0, sizeof(ec));
   for (uint32_t j = 0; j < cs.n_advice; j++) ec.advice[j] = p.advice[j].coset->p;
-  for (uint32_t j = 0; j < cs.n_fixed; j++) ec.fixed[j] = pk.fixed_cosets[j]->p;
+  for (uint32_t j = 0; j < cs.n_fixed; j++) ec.fixed[j] = p.fixed_coset(j);
   ic = p.instance_columns(true);
   ec.instance = ic.column[0];  // what the calls without an h2mi_instance_cosets read
   ec.n_perm = m;
   ec.chunk_len = pk.chunk;
   for (uint32_t j = 0; j < m; j++) {
     ec.perm_value[j] = p.perm_column(cs.perm_columns[j], true);
-    ec.perm_sigma[j] = pk.sigma_cosets[j]->p;
+    ec.perm_sigma[j] = p.sigma_coset(j);
   }
   for (uint32_t s = 0; s < n_sets; s++) ec.perm_z[s] = p.z[s].coset->p;
   ec.n_lookups = L | (pk.logup ? H2MI_LOOKUPS_LOGUP : 0u);
@@ -1406,16 +1451,16 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_coset
       ec.lookup_table[l] = p.lk[l].c.tab_coset->p;
     } else {
       ec.lookup_input[l] = p.advice[lk.input.index].coset->p;
-      ec.lookup_input_b[l] = lk.selector_fixed >= 0 ? pk.fixed_cosets[lk.selector_fixed]->p : nullptr;
-      ec.lookup_table[l] = pk.fixed_cosets[lk.table_fixed]->p;
+      ec.lookup_input_b[l] = lk.selector_fixed >= 0 ? p.fixed_coset(lk.selector_fixed) : nullptr;
+      ec.lookup_table[l] = p.fixed_coset(lk.table_fixed);
     }
     ec.lookup_permuted_input[l] = p.lk[l].a.coset->p;
     ec.lookup_permuted_table[l] = pk.logup ? nullptr : p.lk[l].s.coset->p;
     ec.lookup_z[l] = p.lk[l].z.coset->p;
   }
-  ec.l0 = pk.l0->p;
-  ec.l_last = pk.l_last->p;
-  ec.l_active = pk.l_active->p;
+  ec.l0 = p.l0_coset();
+  ec.l_last = p.l_last_coset();
+  ec.l_active = p.l_active_coset();
   std::memset(&sc, 0, sizeof(sc));
   sc.n_shuffles = pk.n_shuffles;
   for (uint32_t i = 0; i < pk.n_shuffles; i++) {  // compressed on the extended coset itself, as the lookups given as expressions are
@@ -1443,6 +1488,54 @@ void finish_members(const Circuits& all) {
 // the numerator of one circuit by the kernel of its shape (the single prover's route, unchanged)
 void evaluate_h_single(h2mi_prover_s& p, const Fr& y);
 
+// The numerator of a by-coset key, single prover or batch.  Extended-coset point c + rot i is (zeta w_ext^c) w^i: per slice c every
+// column's coefficients go to the 2^k points of that coset (one transform each, shift zeta w_ext^c), the lookups' and shuffles' sides
+// are compressed on the slices, and ONE launch folds every circuit's terms into h[c + rot i] — whatever the key's shape, through the
+// program keygen built for the witness check, as batches do.  The shared columns' slices are the leader's.
+void evaluate_h_by_coset(const Circuits& all, const Fr& y) {
+  h2mi_prover_s& lead = *all[0];
+  const h2mi_pk_s& pk = *lead.pk;
+  const h2mi_constraint_system& cs = pk.cs;
+  const poly::EvaluationDomain& d = pk.domain;
+  const size_t n = pk.n;
+  const uint32_t rot = 1u << (d.extended_k() - d.k());
+  const std::vector<Fr>& t_inv = d.t_inv();
+  for (h2mi_prover_s* c : all) c->lead = &lead;
+  Fr shift = d.get_g_coset();
+  for (uint32_t c = 0; c < rot; c++, shift = fr::mul(shift, d.get_extended_omega())) {
+    auto slice = [&](const DeviceVec& poly, DeviceVec& out) {
+      check(h2mi_ntt_bn254_fr_oop_dev(poly.p, n, out.p, d.k(), d.get_omega().l, shift.l, nullptr, nullptr), "coeff_to_slice");
+    };
+    for (uint32_t j = 0; j < cs.n_fixed; j++) slice(*pk.fixed_polys[j], *lead.fixed_slices[j]);
+    for (uint32_t j = 0; j < cs.n_perm; j++) slice(*pk.sigma_polys[j], *lead.sigma_slices[j]);
+    slice(*pk.l0_poly, *lead.l0_slice);
+    slice(*pk.l_last_poly, *lead.l_last_slice);
+    slice(*pk.l_active_poly, *lead.l_active_slice);
+    for (h2mi_prover_s* m : all) {
+      for (Forms& f : m->advice) slice(*f.poly, *f.coset);
+      for (Forms& f : m->z) slice(*f.poly, *f.coset);
+      for (uint32_t i = 0; i < cs.n_instance; i++) slice(*m->instance_poly[i], *m->instance_coset[i]);
+      for (uint32_t l = 0; l < cs.n_lookups; l++) {
+        slice(*m->lk[l].a.poly, *m->lk[l].a.coset);
+        if (!pk.logup) slice(*m->lk[l].s.poly, *m->lk[l].s.coset);
+        slice(*m->lk[l].z.poly, *m->lk[l].z.coset);
+      }
+      for (uint32_t i = 0; i < pk.n_shuffles; i++) slice(*m->sf[i].z.poly, *m->sf[i].z.coset);
+    }
+    std::vector<h2mi_expr_cosets> ec(all.size());
+    std::vector<h2mi_shuffle_cosets> sc(all.size());
+    std::vector<h2mi_instance_cosets> ic(all.size());
+    h2mi_logup_cosets lg;
+    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i], sc[i], lg, ic[i]);  // compresses on the slices
+    check(h2mi_plonk_evaluate_h_expr_slice_dev(ec.data(), pk.n_shuffles ? sc.data() : nullptr, &lg, ic.data(), (uint32_t)ec.size(), &pk.check_gates,
+                                               lead.challenge_limbs(), pk.phases.n_challenges, d.k(), d.extended_k(), cs.blinding_factors, lead.beta.l,
+                                               lead.gamma.l, y.l, pk.delta.l, d.get_g_coset().l, d.get_extended_omega().l, (const uint64_t*)t_inv.data(),
+                                               c, lead.h->p, nullptr),
+          "evaluate_h");
+  }
+  for (h2mi_prover_s* c : all) c->lead = nullptr;
+}
+
 void phase_quotient(const Circuits& all, const Fr& y, uint64_t* points_out) {
   h2mi_prover_s& p = *all[0];
   const h2mi_pk_s& pk = *p.pk;
@@ -1453,7 +1546,9 @@ void phase_quotient(const Circuits& all, const Fr& y, uint64_t* points_out) {
   require_members(all);
   p.phase = IDLE;
   DeviceVec& h = *p.h;
-  if (!p.batch) {
+  if (pk.by_coset) {
+    evaluate_h_by_coset(all, y);
+  } else if (!p.batch) {
     evaluate_h_single(p, y);
   } else {
     // several circuits (or a batch of one): ONE launch folds every circuit's terms into h, whatever the key's shape — a hard-wired
@@ -1994,7 +2089,7 @@ extern "C" {
 
 int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies,
                        unsigned flags, h2mi_pk_t* pk_out) {
-  return keygen_entry(cs, {}, H2MI_KEYGEN_VK_ONLY, nullptr, nullptr, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
+  return keygen_entry(cs, {}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_BY_COSET, nullptr, nullptr, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
 }
 
 int h2mi_gate_program_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint32_t* degree_out, uint32_t* max_stack_out) {
@@ -2058,7 +2153,7 @@ int h2mi_shape_gate_program(const h2mi_constraint_system* cs, h2mi_expr_op* ops,
 
 int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed,
                              const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY, gates, nullptr, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
+  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_BY_COSET, gates, nullptr, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
 }
 
 int h2mi_lookup_program_check(const h2mi_constraint_system* cs, const h2mi_lookup_program* lookups, uint32_t* degree_out) {
@@ -2069,7 +2164,7 @@ int h2mi_lookup_program_check(const h2mi_constraint_system* cs, const h2mi_looku
 int h2mi_prover_keygen_exprs(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, uint64_t g_lagrange_handle,
                              const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
   if (!lookups) return h2mi_prover_keygen_gates(cs, gates, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
-  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP, gates, lookups, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies,
+  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP | H2MI_KEYGEN_BY_COSET, gates, lookups, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies,
                       flags, pk_out);
 }
 
@@ -2082,7 +2177,7 @@ int h2mi_advice_phases_check(const h2mi_constraint_system* cs, const h2mi_gate_p
 int h2mi_prover_keygen_phases(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                               const h2mi_advice_phases* phases, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
                               size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  return keygen_entry(cs, {gates, phases}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP, gates, lookups, phases, nullptr, nullptr, g_lagrange_handle, fixed, copies,
+  return keygen_entry(cs, {gates, phases}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP | H2MI_KEYGEN_BY_COSET, gates, lookups, phases, nullptr, nullptr, g_lagrange_handle, fixed, copies,
                       n_copies, flags, pk_out);
 }
 
@@ -2115,7 +2210,7 @@ int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_p
                              const h2mi_logup_inputs* inputs, const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles,
                              uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags,
                              h2mi_pk_t* pk_out) {
-  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP, gates, lookups, phases, shuffles, inputs, g_lagrange_handle, fixed, copies,
+  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP | H2MI_KEYGEN_BY_COSET, gates, lookups, phases, shuffles, inputs, g_lagrange_handle, fixed, copies,
                       n_copies, flags, pk_out);
 }
 
@@ -2423,6 +2518,7 @@ int h2mi_prover_buffer(h2mi_prover_t prover, uint32_t kind, uint32_t index, void
   if (!d_ptr_out) return H2MI_EINVAL;
   h2mi_prover_s& p = *prover;
   auto form = [&](std::vector<Forms>& v, int which) -> int {
+    if (which == 2 && p.pk->by_coset) return H2MI_EINVAL;  // a slice is no extended coset
     if (index >= v.size()) return H2MI_ERANGE;
     const Dev& d = which == 0 ? v[index].value : which == 1 ? v[index].poly : v[index].coset;
     return pick(d, 0, d_ptr_out, count_out);
@@ -2454,9 +2550,46 @@ int h2mi_prover_buffer(h2mi_prover_t prover, uint32_t kind, uint32_t index, void
   }
 }
 
+int h2mi_prover_device_bytes(h2mi_prover_t prover, size_t* key_bytes_out, size_t* prover_bytes_out) {
+  if (!alive(g_live_provers, prover)) return H2MI_EHANDLE;
+  const h2mi_prover_s& p = *prover;
+  const h2mi_pk_s& pk = *p.pk;
+  size_t total = 0;
+  auto one = [&](const Dev& d) { total += d ? d->n * 32 : 0; };
+  auto many = [&](const std::vector<Dev>& v) { for (const Dev& d : v) one(d); };
+  auto forms = [&](const Forms& f) { one(f.value); one(f.poly); one(f.coset); };
+  auto table = [&](const Table& t) { one(t.sorted); one(t.sorted_mont); one(t.mult); };
+  many(pk.fixed_values); many(pk.fixed_polys); many(pk.fixed_cosets); many(pk.sigma_values); many(pk.sigma_polys); many(pk.sigma_cosets);
+  for (const Dev* d : {&pk.l0, &pk.l_last, &pk.l_active, &pk.l0_poly, &pk.l_last_poly, &pk.l_active_poly, &pk.active_rows, &pk.moved_cells_dev}) one(*d);
+  for (const Table& t : pk.tables) table(t);
+  if (key_bytes_out) *key_bytes_out = total;
+  total = 0;
+  for (const Forms& f : p.advice) forms(f);
+  for (const Forms& f : p.z) forms(f);
+  many(p.instance); many(p.instance_poly); many(p.instance_coset); many(p.fixed_slices); many(p.sigma_slices); many(p.q); many(p.s);
+  for (const h2mi_prover_s::Lk& l : p.lk) {
+    for (const Dev* d : {&l.c.input, &l.c.table, &l.c.in_coset, &l.c.tab_coset}) one(*d);
+    forms(l.a); forms(l.s); forms(l.z);
+    table(l.sorted);
+  }
+  for (const h2mi_prover_s::Sf& f : p.sf) {
+    for (const Dev* d : {&f.c.input, &f.c.table, &f.c.in_coset, &f.c.tab_coset}) one(*d);
+    forms(f.z);
+  }
+  for (const Dev* d : {&p.l0_slice, &p.l_last_slice, &p.l_active_slice, &p.check_in, &p.check_tab, &p.random_poly, &p.h, &p.h_poly, &p.points, &p.evals,
+                       &p.nx[0], &p.nx[1], &p.nx[2], &p.tmp[0], &p.tmp[1], &p.tmp[2], &p.h_x, &p.l_x, &p.h2_x})
+    one(*d);
+  table(p.check_sorted); table(p.check_sorted_in);
+  if (prover_bytes_out) *prover_bytes_out = total;
+  return H2MI_OK;
+}
+
 int h2mi_prover_pk_buffer(h2mi_pk_t pk, uint32_t kind, uint32_t index, void** d_ptr_out, size_t* count_out) {
   if (!alive(g_live_pks, pk)) return H2MI_EHANDLE;
   if (!d_ptr_out) return H2MI_EINVAL;
+  if (pk->by_coset && (kind == H2MI_PKBUF_FIXED_COSET || kind == H2MI_PKBUF_SIGMA_COSET || kind == H2MI_PKBUF_L0_COSET || kind == H2MI_PKBUF_L_LAST_COSET ||
+                       kind == H2MI_PKBUF_L_ACTIVE_COSET))
+    return H2MI_EINVAL;  // the key holds no extended-coset vector
   switch (kind) {
     case H2MI_PKBUF_FIXED: return pick(pk->fixed_values, index, d_ptr_out, count_out);
     case H2MI_PKBUF_FIXED_POLY: return pick(pk->fixed_polys, index, d_ptr_out, count_out);

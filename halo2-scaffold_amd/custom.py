@@ -586,11 +586,15 @@ class Keys:
     DESIGN.md 4.5 and tests/logup_cases.py, not to a crate]: every lookup of the key is proven with a multiplicity column and a running
     sum (H2MI_KEYGEN_LOGUP) in place of the permuted columns and the grand product; needs a circuit with lookups.  `create_proof` and
     `prove_many` follow the key; `mock` and `check` test membership and do not depend on it.  A constraint system after
-    merge_lookups() goes through h2mi_prover_keygen_logup and needs logup=True."""
+    merge_lookups() goes through h2mi_prover_keygen_logup and needs logup=True.
+    by_coset=True (H2MI_KEYGEN_BY_COSET): the key and its provers keep no column in extended-coset form and the quotient is evaluated
+    one coset at a time — the same proof bytes from a fraction of the device memory, at the price of transforms redone
+    in every proof; `fixed_cosets` / `sigma_cosets` are then refused by the library."""
 
-    def __init__(self, params: ParamsKZG, cs: ConstraintSystem, asg: Assignment, logup: bool = False):
+    def __init__(self, params: ParamsKZG, cs: ConstraintSystem, asg: Assignment, logup: bool = False, by_coset: bool = False):
         self.cs = cs
         self.logup = bool(logup)
+        self.by_coset = bool(by_coset)
         if not logup and any(len(arg) > 1 for arg in cs.lookup_arguments):
             raise ValueError("merge_lookups() merged lookups over one table: only a logUp key proves them, Keys(..., logup=True)")
         self.params = params  # prove_many's default SRS
@@ -600,7 +604,8 @@ class Keys:
         index = {col: j for j, col in enumerate(cs.perm_columns)}
         copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
         self.keys = engine.Keys(cs.abi(k), params, list(asg.fixed), copies, gates=cs.gate_program(), lookups=cs.lookup_program(),
-                                phases=cs.phases(), shuffles=cs.shuffle_program(), logup=logup, logup_inputs=cs.logup_inputs() if logup else None)
+                                phases=cs.phases(), shuffles=cs.shuffle_program(), logup=logup, logup_inputs=cs.logup_inputs() if logup else None,
+                                by_coset=by_coset)
         self.fixed_commitments, self.permutation_commitments = self.keys.fixed_commitments, self.keys.permutation_commitments
         nf, m = cs.n_fixed, len(cs.perm_columns)
         self.fixed_values, self.fixed_polys, self.fixed_cosets = (self.keys.views(kd, nf) for kd in (engine.PKBUF_FIXED, engine.PKBUF_FIXED_POLY, engine.PKBUF_FIXED_COSET))

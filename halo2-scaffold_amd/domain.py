@@ -86,6 +86,13 @@ class EvaluationDomain:
         check(lib.h2mi_ntt_bn254_fr_oop_dev(d_coeff.ptr, self.n, d_ext.ptr, self.extended_k, self._eomega.ctypes.data,
                                             self._zeta.ctypes.data, None, stream), "coset_fft_oop_dev")
 
+    def coeff_to_slice_oop_dev(self, d_coeff: DevBuf, c: int, d_slice: DevBuf, stream=None):
+        """d_coeff: n coefficients; d_slice receives the n evaluations on coset c of the extended domain: element i is element
+        c + 2^(extended_k - k) i of coeff_to_extended — the point (zeta extended_omega^c) omega^i"""
+        shift = F.fr_to_mont_limbs(self.g_coset * pow(self.extended_omega, c, F.FR_MODULUS) % F.FR_MODULUS)
+        check(lib.h2mi_ntt_bn254_fr_oop_dev(d_coeff.ptr, self.n, d_slice.ptr, self.k, self._omega.ctypes.data, shift.ctypes.data, None, stream),
+              "coset_slice_oop_dev")
+
     def extended_to_coeff_dev(self, d_ext: DevBuf, stream=None):
         check(lib.h2mi_ntt_bn254_fr_dev(d_ext.ptr, self.extended_k, self._eomega_inv.ctypes.data, None, None, stream), "coset_ifft_dev")
         check(

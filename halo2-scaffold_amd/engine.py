@@ -22,6 +22,7 @@ GATES_STANDARD_PLONK, GATES_FLEX_VERTICAL, GATES_EXPRESSIONS = 1, 2, 3
 CELLS_CANONICAL = 1
 CELLS_RATIONAL = 2  # H2MI_CELLS_RATIONAL: (numerator, denominator) pairs, resolved by the library
 KEYGEN_VK_ONLY = 1
+KEYGEN_BY_COSET = 8  # H2MI_KEYGEN_BY_COSET: no extended-coset columns, the quotient one coset at a time (include/h2mi_prover.h)
 KEYGEN_LOGUP = 2  # H2MI_KEYGEN_LOGUP: the key's program lookups are logUp arguments (include/h2mi_prover.h)
 EUNSAT = -7
 MAX_GATES, MAX_PERM, MAX_LOOKUPS, MAX_QUERIES = 32, 64, 8, 192  # H2MI_MAX_* (include/h2mi_prover.h)
@@ -370,14 +371,15 @@ class Keys:
 
     def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False, gates: GateProgram = None,
                  lookups: LookupProgram = None, phases: AdvicePhases = None, shuffles: ShuffleProgram = None, logup: bool = False,
-                 logup_inputs: "LogupInputs" = None):
+                 logup_inputs: "LogupInputs" = None, by_coset: bool = False):
         self.cs = cs
+        self.by_coset = bool(by_coset)  # H2MI_KEYGEN_BY_COSET: same proofs, a device footprint without 2^extended_k columns, slower
         self.logup = bool(logup)  # H2MI_KEYGEN_LOGUP; the library refuses it without a lookup program
         self.n_shuffles = shuffles.n_shuffles if shuffles is not None else 0
         cells, keep = pack_cells(fixed)
         cp = np.ascontiguousarray(np.array(copies, dtype=np.uint32).reshape(-1, 4))
         h = C.c_void_p()
-        flags = (KEYGEN_VK_ONLY if vk_only else 0) | (KEYGEN_LOGUP if logup else 0)
+        flags = (KEYGEN_VK_ONLY if vk_only else 0) | (KEYGEN_LOGUP if logup else 0) | (KEYGEN_BY_COSET if by_coset else 0)
         opt = lambda s: C.byref(s) if s is not None else None
         if logup_inputs is not None:  # several input sets per logUp lookup: h2mi_prover_keygen_shuffles with the counts beside it
             check(lib.h2mi_prover_keygen_logup(C.byref(cs), C.byref(gates), opt(lookups), C.byref(logup_inputs), opt(phases), opt(shuffles),
@@ -481,6 +483,13 @@ class Prover:
         if key is not None and len(key) != 32:
             raise ValueError("the key is 32 bytes")
         check(lib.h2mi_prover_set_rng_key(self.handle, key), "set_rng_key")
+
+    def device_bytes(self) -> tuple:
+        """h2mi_prover_device_bytes: (key bytes, prover bytes) of the device vectors the key and this prover own; the library-wide
+        caches (window tables, twiddles, scratch) are not in it"""
+        kb, pb = C.c_size_t(), C.c_size_t()
+        check(lib.h2mi_prover_device_bytes(self.handle, C.byref(kb), C.byref(pb)), "device_bytes")
+        return kb.value, pb.value
 
     def views(self, kind: int, count: int) -> _Views:
         return _Views(lib.h2mi_prover_buffer, self.handle, kind, count)

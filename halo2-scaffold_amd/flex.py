@@ -360,10 +360,12 @@ class FlexKeys:
     """keygen_vk + keygen_pk (src/scaffold.rs:284,287) through h2mi_prover_keygen: the fixed cells of a run of the closure (the
     lookup table dense), the copy constraints with their columns renumbered into the permutation argument's order; the library
     builds the sigma polynomials (Assembly::copy over advice, constants and instance cells alike), l_0 / l_last / l_active, the
-    lookup table's sorted form and the verifying key's commitments."""
+    lookup table's sorted form and the verifying key's commitments.  by_coset=True (H2MI_KEYGEN_BY_COSET): no extended-coset column
+    on the device, the quotient one coset at a time — the same proof bytes; `fixed_cosets` / `sigma_cosets` are then refused."""
 
-    def __init__(self, params: ParamsKZG, cs: FlexGateCS, asg: Assignment):
+    def __init__(self, params: ParamsKZG, cs: FlexGateCS, asg: Assignment, by_coset: bool = False):
         self.cs = cs
+        self.by_coset = bool(by_coset)
         k = params.k
         self.domain = d = EvaluationDomain(cs.degree, k)
         self.u = u = d.n - (cs.blinding_factors + 1)
@@ -375,7 +377,7 @@ class FlexKeys:
             fixed_cells[cs.col_table] = [v % R for v in tv]  # dense: rows 0 .. len - 1
         index = {col: j for j, col in enumerate(cs.perm_columns)}
         copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
-        self.keys = engine.Keys(cs.abi(k), params, fixed_cells, copies)
+        self.keys = engine.Keys(cs.abi(k), params, fixed_cells, copies, by_coset=by_coset)
         self.fixed_commitments, self.permutation_commitments = self.keys.fixed_commitments, self.keys.permutation_commitments
         # read-only views of the key's library-owned vectors (Lagrange / coefficient / extended-coset forms), for callers that check them
         nf, m = cs.n_fixed, len(cs.perm_columns)

@@ -60,10 +60,10 @@ def constraint_system(circuit, k: int) -> engine.ConstraintSystem:
         [(engine.ADVICE, c) for c in circuit.PERMUTATION_COLUMNS], [], circuit.ADVICE_QUERIES, circuit.FIXED_QUERIES)
 
 
-def _keygen(params: ParamsKZG, circuit, vk_only: bool) -> engine.Keys:
+def _keygen(params: ParamsKZG, circuit, vk_only: bool, by_coset: bool = False) -> engine.Keys:
     syn = circuit.without_witnesses().synthesize()
     copies = [(lc, lr, rc, rr) for (lc, lr), (rc, rr) in syn.copies]  # columns are already indices into the permutation argument
-    return engine.Keys(constraint_system(circuit, params.k), params, syn.fixed, copies, vk_only=vk_only)
+    return engine.Keys(constraint_system(circuit, params.k), params, syn.fixed, copies, vk_only=vk_only, by_coset=by_coset)
 
 
 def keygen_vk(params: ParamsKZG, circuit) -> VerifyingKey:
@@ -100,8 +100,9 @@ class ProvingKey:
         self.keys.release()
 
 
-def keygen_pk(params: ParamsKZG, vk: VerifyingKey, circuit) -> ProvingKey:
-    keys = _keygen(params, circuit, vk_only=False)
+def keygen_pk(params: ParamsKZG, vk: VerifyingKey, circuit, by_coset: bool = False) -> ProvingKey:
+    """by_coset (H2MI_KEYGEN_BY_COSET): no extended-coset column on the device, the quotient one coset at a time; the same proofs"""
+    keys = _keygen(params, circuit, vk_only=False, by_coset=by_coset)
     if not (np.array_equal(keys.fixed_commitments, vk.fixed_commitments) and np.array_equal(keys.permutation_commitments, vk.permutation_commitments)):
         keys.release()
         raise ValueError("keygen_pk: the verifying key belongs to another circuit or SRS")

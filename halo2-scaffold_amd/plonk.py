@@ -372,6 +372,61 @@ def evaluate_h_expr_batch(domain: EvaluationDomain, program, cosets, n_circuits:
                                                     out.ptr, None), "evaluate_h_expr_batch")
 
 
+class _ShuffleCosets(C.Structure):
+    """include/h2mi.h h2mi_shuffle_cosets"""
+    _fields_ = [("n_shuffles", C.c_uint32), ("input", C.c_void_p * 8), ("shuffle", C.c_void_p * 8), ("z", C.c_void_p * 8)]
+
+
+class _InstanceCosets(C.Structure):
+    """include/h2mi.h h2mi_instance_cosets"""
+    _fields_ = [("n_instance", C.c_uint32), ("column", C.c_void_p * 8)]
+
+
+class _LogupCosets(C.Structure):
+    """include/h2mi.h h2mi_logup_cosets"""
+    _fields_ = [("n_inputs", C.c_uint32 * _ExprCosets.L)]
+
+
+def argument_cosets(circuits, logup_sets=None):
+    """-> (h2mi_shuffle_cosets array or None, h2mi_logup_cosets or None, h2mi_instance_cosets array) for the circuits of a proof: per
+    circuit `shuffles` [(input, shuffle side, product)] and `instances` [DevBuf or None] beside what expr_cosets_array reads;
+    logup_sets: the input sets per lookup of a logUp proof (the entries' n_lookups then carry H2MI_LOOKUPS_LOGUP: set by the caller)"""
+    n = max(len(circuits), 1)
+    shs, ins = (_ShuffleCosets * n)(), (_InstanceCosets * n)()
+    for sh, ic, c in zip(shs, ins, circuits):
+        sh.n_shuffles = len(c.get("shuffles", ()))
+        for i, (a_in, s_in, z) in enumerate(c.get("shuffles", ())):
+            sh.input[i], sh.shuffle[i], sh.z[i] = a_in.ptr, s_in.ptr, z.ptr
+        ic.n_instance = len(c.get("instances", ()))
+        for i, col in enumerate(c.get("instances", ())):
+            ic.column[i] = col.ptr if col is not None else None
+    lg = None
+    if logup_sets is not None:
+        lg = _LogupCosets()
+        for l in range(_ExprCosets.L):
+            lg.n_inputs[l] = logup_sets[l] if l < len(logup_sets) else 1
+    return (shs if any(sh.n_shuffles for sh in shs) else None), lg, ins
+
+
+def evaluate_h_expr_slice(domain: EvaluationDomain, program, cosets, n_circuits: int, slice_index, beta: int, gamma: int, y: int, out: DevBuf,
+                          blinding_factors: int = BLINDING_FACTORS, challenges=(), shuffles=None, logup=None, instances=None) -> None:
+    """h2mi_plonk_evaluate_h_expr_slice_dev: the numerator of the circuits on ONE coset of 2^k points — every column of `cosets`
+    (expr_cosets_array), `shuffles`, `logup` and `instances` (argument_cosets) is slice `slice_index` of its extended-coset vector
+    (coeff_to_slice_oop_dev), `out` the whole vector of 2^extended_k elements, of which elements slice_index + rot i are written.
+    slice_index None: the resident call over whole extended-coset vectors (h2mi_plonk_evaluate_h_expr_batch_in_dev), same arguments."""
+    mm = F.fr_to_mont_limbs
+    t_inv = np.ascontiguousarray(vanishing_inverses(domain))
+    args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
+    ch = _challenge_limbs(challenges)
+    head = (cosets, shuffles, C.byref(logup) if logup is not None else None, instances, n_circuits, C.byref(program),
+            ch.ctypes.data if len(challenges) else None, len(challenges), domain.k, domain.extended_k, blinding_factors, *[x.ctypes.data for x in args],
+            t_inv.ctypes.data)
+    if slice_index is None:
+        _check(lib.h2mi_plonk_evaluate_h_expr_batch_in_dev(*head, out.ptr, None), "evaluate_h_expr_batch_in")
+    else:
+        _check(lib.h2mi_plonk_evaluate_h_expr_slice_dev(*head, slice_index, out.ptr, None), "evaluate_h_expr_slice")
+
+
 def _challenge_limbs(challenges) -> np.ndarray:
     return np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in challenges])) if len(challenges) else np.zeros((1, 4), dtype=np.uint64)
 

@@ -74,14 +74,14 @@ class ProvingKey:
         self.params.release()
 
 
-def gen_key(f, dummy_inputs):
+def gen_key(f, dummy_inputs, by_coset: bool = False):
     """src/scaffold.rs:95-156: the circuit's shape from a run on dummy inputs (GateThreadBuilder::keygen + builder.config), the SRS
-    from gen_srs(k), keygen_vk + keygen_pk -> (pk, break_points)"""
+    from gen_srs(k), keygen_vk + keygen_pk -> (pk, break_points).  by_coset: flex.FlexKeys' (no extended-coset columns on the device)"""
     k, lookup_bits, minimum_rows = _env()
     cs = _config(f, dummy_inputs, k, lookup_bits, minimum_rows)
     asg = _synthesize(f, dummy_inputs, cs, lookup_bits)
     params = gen_srs(k)
-    pk = ProvingKey(params, flex.FlexKeys(params, cs, asg))
+    pk = ProvingKey(params, flex.FlexKeys(params, cs, asg, by_coset=by_coset))
     pk.lookup_bits = lookup_bits
     return pk, [list(asg.break_points)]
 

@@ -653,6 +653,24 @@ int h2mi_plonk_evaluate_h_expr_batch_in_dev(const h2mi_expr_cosets* circuits, co
                                             const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
                                             void* d_h_out, h2mi_stream_t stream);
 
+/* The same numerator ONE COSET at a time (the quotient of a key made with H2MI_KEYGEN_BY_COSET, include/h2mi_prover.h).  With
+ * rot = 2^(extended_k - k), extended-coset point slice + rot i is X = (zeta extended_omega^slice) omega^i, omega = extended_omega^rot:
+ * the 2^extended_k evaluations of a polynomial of degree < 2^k are rot coset transforms of 2^k points, one per shift.  The arguments are
+ * the call's above and `slice` < rot; every column pointer — of `circuits`, `shuffles`, `instances` — is the 2^k-element slice `slice` of
+ * the vector the call above takes: element i the value at extended-coset point slice + rot i, which for a column is
+ * h2mi_ntt_bn254_fr_oop_dev(coefficients, 2^k, out, k, omega, pre = zeta extended_omega^slice).  A query at rotation r reads element
+ * (i + r) mod 2^k of the same slice; a compressed side is h2mi_plonk_expr_compress_in_dev over the slices with domain_k = k; input set j of
+ * a logUp lookup lies j 2^k elements behind lookup_input[l] (the call above: j 2^extended_k).  zeta, extended_omega and the rot values
+ * of t_inv are the DOMAIN'S, as for the call above.  d_h_out is the whole vector of 2^extended_k elements: the call writes elements
+ * slice + rot i, i < 2^k, each word for word what the call above stores there, and no other; rot calls, one per slice, fill it.
+ * H2MI_ERANGE: slice >= rot. */
+int h2mi_plonk_evaluate_h_expr_slice_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
+                                         const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
+                                         const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
+                                         const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
+                                         const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, uint32_t slice, void* d_h_out,
+                                         h2mi_stream_t stream);
+
 /* A lookup's expressions compressed with theta (plonk/lookup/prover.rs compress_expressions): `exprs` holds m polynomials e_0 ..
  * e_(m-1) and d_out[i] = sum_j e_j(i) theta^(m-1-j) — the fold acc theta + e_j — for the 2^domain_k points the columns are given on:
  * the Lagrange rows (domain_k = k) or the extended coset (domain_k = extended_k).  A query at rotation r reads point

@@ -559,7 +559,7 @@ struct FlexKeys {
 
 // keygen_vk + keygen_pk (src/scaffold.rs:284,287) from the cells a run of the closure assigns: the fixed columns (the table
 // column dense, the others sparse) and the copy constraints, columns renumbered into the permutation argument's order
-inline std::unique_ptr<FlexKeys> keygen(const poly::kzg::ParamsKZG& params, const FlexGateCS& cs, const Assignment& asg) {
+inline std::unique_ptr<FlexKeys> keygen(const poly::kzg::ParamsKZG& params, const FlexGateCS& cs, const Assignment& asg, unsigned flags = 0) {
   std::unique_ptr<FlexKeys> keys(new FlexKeys(cs));
   plonk::KeygenInput in;
   for (uint32_t c = 0; c < cs.n_fixed; c++) {
@@ -579,7 +579,7 @@ inline std::unique_ptr<FlexKeys> keygen(const poly::kzg::ParamsKZG& params, cons
   };
   for (const auto& c : asg.copies)
     in.copies.insert(in.copies.end(), {perm_index(c.first.kind, c.first.col), c.first.row, perm_index(c.second.kind, c.second.col), c.second.row});
-  plonk::run_keygen(cs.abi(params.k()), params, in, 0, keys->pk, keys->vk);
+  plonk::run_keygen(cs.abi(params.k()), params, in, flags, keys->pk, keys->vk);  // flags: 0 or H2MI_KEYGEN_BY_COSET
   return keys;
 }
 

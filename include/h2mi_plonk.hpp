@@ -180,10 +180,11 @@ inline VerifyingKey keygen_vk(const poly::kzg::ParamsKZG& params, const Standard
   run_keygen(StandardPlonk::constraint_system(params.k()), params, detail::standard_plonk_keygen_input(), H2MI_KEYGEN_VK_ONLY, tmp, vk);
   return vk;
 }
-inline std::unique_ptr<ProvingKey> keygen_pk(const poly::kzg::ParamsKZG& params, const VerifyingKey& vk, const StandardPlonk& circuit) {
+// flags: 0, or H2MI_KEYGEN_BY_COSET for a key without extended-coset columns (the same proofs, include/h2mi_prover.h)
+inline std::unique_ptr<ProvingKey> keygen_pk(const poly::kzg::ParamsKZG& params, const VerifyingKey& vk, const StandardPlonk& circuit, unsigned flags = 0) {
   (void)circuit;
   std::unique_ptr<ProvingKey> pk(new ProvingKey);
-  run_keygen(StandardPlonk::constraint_system(params.k()), params, detail::standard_plonk_keygen_input(), 0, pk->pk, pk->vk);
+  run_keygen(StandardPlonk::constraint_system(params.k()), params, detail::standard_plonk_keygen_input(), flags, pk->pk, pk->vk);
   if (pk->vk.to_bytes() != vk.to_bytes()) throw Error(H2MI_EINVAL, "keygen_pk: the verifying key belongs to another circuit or SRS");
   return pk;
 }

@@ -173,6 +173,19 @@ typedef struct h2mi_prover_s* h2mi_prover_t; /* the buffers, streams and phase s
  * Evaluations per lookup in the place of its five: phi(x), phi(omega x), M(x); lookups.open: phi at x, phi at omega x, M at x.
  * h2mi_prover_check tests membership and does not depend on the argument.  Batches: M and phi per member, one joint quotient. */
 #define H2MI_KEYGEN_LOGUP 2u
+/* H2MI_KEYGEN_BY_COSET: the quotient is evaluated one coset of 2^k points at a time, and no column is kept in extended-coset form
+ * (DESIGN.md 3 and 4.5 hold the memory formulas of both layouts).  Accepted by every keygen entry point, alone or with
+ * H2MI_KEYGEN_LOGUP; with H2MI_KEYGEN_VK_ONLY it changes nothing.  The key holds its fixed and sigma columns in Lagrange and coefficient
+ * form and l_0 / l_last / l_active as coefficients; commitments, tables, moved cells and programs are the resident key's, and so is what
+ * h2mi_prover_vk_commitments returns.  A prover on such a key holds no vector of 2^extended_k elements but h: per vector the numerator
+ * reads, one slice of 2^k elements (a logUp lookup's input sets: sets 2^k, one slice behind the other), the slices of the key's shared
+ * columns among them — in a batch the leader's are read, and the key stays immutable.  h2mi_prover_quotient / h2mi_batch_quotient then
+ * run, for each slice c < 2^(extended_k - k): every column's coefficients to slice c (a 2^k-point transform with shift
+ * zeta extended_omega^c), the lookups' and shuffles' sides compressed on the slices, ONE launch of the interpreting kernel over all
+ * members (h2mi_plonk_evaluate_h_expr_slice_dev; a hard-wired shape through its equivalent program, as batches do).  Every phase and every
+ * byte of the proof is the resident key's; instance columns always take the coefficient route.  The price is time: the fixed and sigma
+ * slices are recomputed in every proof.  h2mi_prover_buffer / _pk_buffer: see the *_COSET kinds below. */
+#define H2MI_KEYGEN_BY_COSET 8u /* bit 4 stays unassigned: every keygen entry refuses it with H2MI_EINVAL, as it always has */
 int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
                        size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
 /* The same with the gates as a program (cs->gates == H2MI_GATES_EXPRESSIONS; any other value: H2MI_EINVAL, as is that value given to
@@ -519,8 +532,17 @@ enum {
   H2MI_PKBUF_FIXED = 64, H2MI_PKBUF_FIXED_POLY, H2MI_PKBUF_FIXED_COSET, H2MI_PKBUF_SIGMA, H2MI_PKBUF_SIGMA_POLY, H2MI_PKBUF_SIGMA_COSET,
   H2MI_PKBUF_L0_COSET, H2MI_PKBUF_L_LAST_COSET, H2MI_PKBUF_L_ACTIVE_COSET
 };
+/* A key made with H2MI_KEYGEN_BY_COSET holds no extended-coset column: the *_COSET kinds (H2MI_BUF_ADVICE_COSET, H2MI_BUF_PERM_Z_COSET,
+ * H2MI_PKBUF_FIXED_COSET, _SIGMA_COSET, _L0_COSET, _L_LAST_COSET, _L_ACTIVE_COSET) are H2MI_EINVAL for it and for its provers.  Every
+ * other kind is what it is for a resident key, H2MI_BUF_H included. */
 int h2mi_prover_buffer(h2mi_prover_t prover, uint32_t kind, uint32_t index, void** d_ptr_out, size_t* count_out);
 int h2mi_prover_pk_buffer(h2mi_pk_t pk, uint32_t kind, uint32_t index, void** d_ptr_out, size_t* count_out);
+
+/* The bytes of the device vectors the prover's key (key_bytes_out) and the prover itself (prover_bytes_out) own: every column, form and
+ * scratch vector allocated for them, 32 bytes per field element, as allocated so far (h2mi_prover_check's scratch and a long instance
+ * column's coefficients appear with their first use).  Not counted: what the library shares among all keys — window tables of the
+ * registered bases, twiddle and power tables, the scratch arena.  Either pointer may be NULL.  Resident and by-coset keys alike. */
+int h2mi_prover_device_bytes(h2mi_prover_t prover, size_t* key_bytes_out, size_t* prover_bytes_out);
 
 #ifdef __cplusplus
 }
