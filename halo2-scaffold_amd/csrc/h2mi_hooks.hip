@@ -1,6 +1,7 @@
 // libh2mi_hooks.so = the product's objects + this file: elementwise device arithmetic exposed for the parity tests
 // (tests/test_gpu_parity.py: every field operation, the XYZZ point formulas and the lane-cooperative quad operations against the
-// oracle; tests/test_gpu_f29.py: the 29-bit-limb primitives f29_mul / sqr / mul2 / mul3 / reduce_loose / inv and the xyzz29 chains on
+// oracle; tests/test_gpu_wire.py: the field operations of fp.cuh (h2mi_dbg_field_op) on Montgomery words at the limb extremes;
+// tests/test_gpu_f29.py: the 29-bit-limb primitives f29_mul / sqr / mul2 / mul3 / reduce_loose / inv and the xyzz29 chains on
 // chosen limbs, at the limits of their contracts; tests/test_gpu_g1_29_edges.py: the point operations on raw-limb operands at the bounds of their coordinate invariants).  NOT part of the product: libh2mi.so neither contains nor exports these (round-4 VERDICT: debug hooks shipped in the
 // product library).  The kernels below instantiate the same device functions the product's kernels inline: fp.cuh for the field
 // hooks, and for every point hook the one group law (g1_29.cuh, g1_29_quad.cuh) through the format bridge of g1.cuh — what the MSM

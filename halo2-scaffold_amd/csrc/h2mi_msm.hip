@@ -2361,8 +2361,11 @@ static int adhoc_handle(const uint64_t* bases, size_t n, uint64_t* handle_out) {
     size_t victim = 0;
     for (size_t i = 1; i < g_adhoc.size(); i++)
       if (g_adhoc[i].last_use < g_adhoc[victim].last_use) victim = i;
-    h2mi_bases_release(g_adhoc[victim].handle);
+    // the entry goes first: h2mi_bases_release drops the cache entry of the handle it frees, and erasing by position after it
+    // dropped a second, live entry (its tables leaked, its next use a rebuild) or, with the victim last, erased end()
+    const uint64_t old = g_adhoc[victim].handle;
     g_adhoc.erase(g_adhoc.begin() + victim);
+    h2mi_bases_release(old);
   }
   uint64_t nh = 0;
   int rc = register_dev(d.p, n, &nh, s, /*allow_small=*/false);

@@ -7,6 +7,8 @@
 //   G1Affine::to_bytes          32 bytes: x.to_bytes() with flags in the two spare top bits of byte 31:
 //                               bit 6 = y is odd (lsb of canonical y), bit 7 = point at infinity (x = 0)
 //   from_bytes                  rejects x >= q, x^3 + 3 a non-residue, and infinity flag with x != 0
+// Checked against oracle/formats.py by tests/test_formats.py and, at the limb extremes, beyond one workgroup and for both moduli, by
+// tests/test_gpu_wire.py (cases: tests/wire_cases.py).
 // The square root is y = (x^3 + 3)^((q+1)/4) (q = 3 mod 4).  Device-side because an SRS file holds 2^(k+1)
 // compressed points: at k = 20 two million 254-bit exponentiations (a minute of one CPU core, milliseconds here).
 #include "g1.cuh"
