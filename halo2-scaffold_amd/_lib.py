@@ -49,6 +49,9 @@ def _load():
         "h2mi_msm_flush": ([], C.c_int),
         "h2mi_bases_register": ([vp, sz, u64p], C.c_int),
         "h2mi_bases_register_dev": ([vp, sz, u64p], C.c_int),
+        "h2mi_bases_register_depth": ([vp, sz, C.c_uint32, u64p], C.c_int),
+        "h2mi_bases_register_depth_dev": ([vp, sz, C.c_uint32, u64p], C.c_int),
+        "h2mi_bases_memory": ([C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64p, u64p], C.c_int),
         "h2mi_bases_release": ([C.c_uint64], C.c_int),
         "h2mi_bases_info": ([C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64p], C.c_int),
         "h2mi_msm_bn254_g1": ([C.c_uint64, vp, vp, sz, vp], C.c_int),

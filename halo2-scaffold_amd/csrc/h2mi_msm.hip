@@ -166,6 +166,11 @@ struct Bases {
   uint8_t* stable = nullptr;    // [2^(sc-1)][sW][n] affine: j 2^(sc w) P_i
   uint32_t since_join = 0;      // MSMs issued on this handle since the last join (msm_join_all): how deep the caller's queue is
   bool last_small = false;      // the path the last MSM took (h2mi_msm_last_stats)
+  // table depth (see "table depth"): the table holds `rows` = ceil(W / depth) rows 2^(c depth j) P_i and an MSM runs `depth` passes
+  uint32_t depth = 1, rows = 0;
+  uint32_t pass = 0;            // the pass msm_general is queueing (msm_compact)
+  uint8_t* pass_out = nullptr;  // depth > 1: [W >= depth] Jacobian pass results, what k_msm_combine reads
+  uint64_t table_bytes = 0, workspace_bytes = 0;  // requested bytes of the table(s) and of the slots' workspaces (h2mi_bases_memory)
 };
 
 static std::map<uint64_t, Bases*> g_bases;
@@ -207,8 +212,8 @@ __global__ void __launch_bounds__(256) k_msm_table_first(const uint8_t* bases, u
   }
   affine_store(table0 + i * 64, p);
 }
-// window w from window w-1: c doublings in XYZZ, one inversion back to affine
-__global__ void __launch_bounds__(256) k_msm_table_next(const uint8_t* prev, uint8_t* next, size_t n, uint32_t c) {
+// row j from row j-1: `step` doublings in XYZZ (c for a full table, c * D' at table depth D': see "table depth"), one inversion back to affine
+__global__ void __launch_bounds__(256) k_msm_table_next(const uint8_t* prev, uint8_t* next, size_t n, uint32_t step) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   affine p = affine_load(prev + i * 64);
@@ -217,7 +222,7 @@ __global__ void __launch_bounds__(256) k_msm_table_next(const uint8_t* prev, uin
     return;
   }
   xyzz29 acc = xyzz29_dbl_affine(f29_unpack(p.x.v), f29_unpack(p.y.v));
-  for (uint32_t k = 1; k < c; k++) acc = xyzz29_dbl(acc);
+  for (uint32_t k = 1; k < step; k++) acc = xyzz29_dbl(acc);
   f29 x, y;
   xyzz29_to_affine(acc, x, y);
   affine q;
@@ -226,11 +231,11 @@ __global__ void __launch_bounds__(256) k_msm_table_next(const uint8_t* prev, uin
   affine_store(next + i * 64, q);
 }
 
-// table slot n of every window: 2^(c*w) * B for B = the sum of the n bases (a Jacobian Montgomery-2^256 point, the
-// result of an all-ones MSM at registration); thread w does its c*w doublings and one inversion
-__global__ void __launch_bounds__(64) k_msm_table_sum_point(const uint8_t* sum_jac, uint8_t* table, size_t stride, size_t n, uint32_t W, uint32_t c) {
+// table slot n of every row: 2^(step*w) * B for B = the sum of the n bases (a Jacobian Montgomery-2^256 point, the
+// result of an all-ones MSM at registration); thread w does its step*w doublings and one inversion (step = c and rows = W for a full table)
+__global__ void __launch_bounds__(64) k_msm_table_sum_point(const uint8_t* sum_jac, uint8_t* table, size_t stride, size_t n, uint32_t rows, uint32_t step) {
   const uint32_t w = threadIdx.x;
-  if (w >= W) return;
+  if (w >= rows) return;
   const xyzz29 b = xyzz29_from_jac(jac_load(sum_jac));
   affine out;
   out.x = fe_zero();
@@ -240,7 +245,7 @@ __global__ void __launch_bounds__(64) k_msm_table_sum_point(const uint8_t* sum_j
     xyzz29_to_affine(b, x, y);
     if (w) {
       xyzz29 acc = xyzz29_dbl_affine(x, y);
-      for (uint32_t k = 1; k < c * w; k++) acc = xyzz29_dbl(acc);
+      for (uint32_t k = 1; k < step * w; k++) acc = xyzz29_dbl(acc);
       xyzz29_to_affine(acc, x, y);
     }
     f29_pack(x, out.x.v);
@@ -369,9 +374,17 @@ __device__ __forceinline__ fe msm_scalar(const fe* scalars, size_t i, size_t n, 
   return o;
 }
 
-template <uint32_t CT>
+// Window filter (FILT, "table depth" below): one pass of a base set that keeps every D'-th table row takes the windows whose bit is set
+// in `wmask` (w = r mod D') and gathers row floor(w / D') = the number of the pass's windows below w.  The whole scalar is recoded in
+// every pass — carries cross pass boundaries — and only the pass's own windows leave an entry.  FILT = false is the code without it.
+template <bool FILT>
+__device__ __forceinline__ bool window_taken(uint32_t wmask, uint32_t w) { return !FILT || ((wmask >> w) & 1u); }
+template <bool FILT>
+__device__ __forceinline__ uint32_t window_row(uint32_t wmask, uint32_t w) { return FILT ? (uint32_t)__popc(wmask & ((1u << w) - 1u)) : w; }
+
+template <uint32_t CT, bool FILT = false>
 __device__ __forceinline__ void msm_bin_count_body(const fe* scalars, size_t n, const fe* shift, uint32_t c, uint32_t W, uint32_t lb, uint32_t nbins,
-                                                   uint32_t ntiles, uint32_t* cnt_out, uint32_t* tile_live) {
+                                                   uint32_t ntiles, uint32_t* cnt_out, uint32_t* tile_live, uint32_t wmask = 0) {
   __shared__ uint32_t cnt[NBINS_MAX];
   __shared__ uint32_t any_live;
   const uint32_t tid = threadIdx.x;
@@ -383,7 +396,9 @@ __device__ __forceinline__ void msm_bin_count_body(const fe* scalars, size_t n, 
     fe s = msm_scalar(scalars, i, n, shift);
     if (!fe_is_zero(s)) {
       any_live = 1;  // benign race: every writer stores the same value
-      for_each_digit<CT>(s, c, W, [&](uint32_t, uint32_t bucket, uint32_t) { atomicAdd(&cnt[bin_of<(CT >= WIDE_MIN_C)>(bucket, lb)], 1u); });
+      for_each_digit<CT>(s, c, W, [&](uint32_t w, uint32_t bucket, uint32_t) {
+        if (window_taken<FILT>(wmask, w)) atomicAdd(&cnt[bin_of<(CT >= WIDE_MIN_C)>(bucket, lb)], 1u);
+      });
     }
   }
   __syncthreads();
@@ -398,13 +413,19 @@ __global__ void __launch_bounds__(P1_TS) k_msm_bin_count(const fe* scalars, size
                                                          uint32_t nbins, uint32_t ntiles, uint32_t* cnt_out, uint32_t* tile_live) {
   msm_bin_count_body<CT>(scalars, n, shift, c, W, lb, nbins, ntiles, cnt_out, tile_live);
 }
+// one pass of a base set with a table depth above 1: the kernel above under the window filter
+template <uint32_t CT>
+__global__ void __launch_bounds__(P1_TS) k_msm_bin_count_f(const fe* scalars, size_t n, const fe* shift, uint32_t c, uint32_t W, uint32_t lb,
+                                                           uint32_t nbins, uint32_t ntiles, uint32_t* cnt_out, uint32_t* tile_live, uint32_t wmask) {
+  msm_bin_count_body<CT, true>(scalars, n, shift, c, W, lb, nbins, ntiles, cnt_out, tile_live, wmask);
+}
 
 extern __shared__ uint4 h2_msm_smem[];
 
-template <uint32_t CT>
+template <uint32_t CT, bool FILT = false>
 __device__ __forceinline__ void msm_bin_scatter_body(const fe* scalars, size_t n, const fe* shift, size_t n_reg, uint32_t c, uint32_t W, uint32_t lb,
                                                      uint32_t nbins, uint32_t ntiles, const uint32_t* base, uint32_t* vals_out, void* keys_out_,
-                                                     const uint32_t* tile_live) {
+                                                     const uint32_t* tile_live, uint32_t wmask = 0) {
   constexpr bool WIDE = CT >= WIDE_MIN_C;  // in-bin keys of up to 10 bits: staged and written as 16-bit values
   if (!tile_live[blockIdx.x]) return;  // no non-zero scalar in this tile (k_msm_bin_count): block-uniform, before any barrier
   __shared__ uint32_t cnt[NBINS_MAX], lstart[NBINS_MAX + 1], wsum[NBINS_MAX / 64];
@@ -433,6 +454,7 @@ __device__ __forceinline__ void msm_bin_scatter_body(const fe* scalars, size_t n
   }
   if (live_nz) {
     for_each_digit<CT>(s, c, W, [&](uint32_t w, uint32_t bucket, uint32_t neg) {
+      if (!window_taken<FILT>(wmask, w)) return;
       uint32_t r = atomicAdd(&cnt[bin_of<WIDE>(bucket, lb)], 1u);
       if (CT) {
         ent[w] = bucket | (neg << 31);
@@ -464,13 +486,14 @@ __device__ __forceinline__ void msm_bin_scatter_body(const fe* scalars, size_t n
       if (ent[w] != 0xFFFFFFFFu) {
         const uint32_t bucket = ent[w] & 0x7FFFFFFFu;
         const uint32_t pos = lstart[bin_of<WIDE>(bucket, lb)] + rk[w];
-        stage_val[pos] = (ent[w] & 0x80000000u) | (uint32_t)((size_t)w * n_reg + i);
+        stage_val[pos] = (ent[w] & 0x80000000u) | (uint32_t)((size_t)window_row<FILT>(wmask, w) * n_reg + i);
         stage_key[pos] = (uint16_t)(WIDE ? key_of<true>(bucket, mask) : bucket);
       }
   } else if (live_nz) {
     for_each_digit<CT>(s, c, W, [&](uint32_t w, uint32_t bucket, uint32_t neg) {
+      if (!window_taken<FILT>(wmask, w)) return;
       uint32_t pos = atomicAdd(&cnt[bucket >> lb], 1u);
-      stage_val[pos] = (neg << 31) | (uint32_t)((size_t)w * n_reg + i);
+      stage_val[pos] = (neg << 31) | (uint32_t)((size_t)window_row<FILT>(wmask, w) * n_reg + i);
       stage_key[pos] = (uint16_t)bucket;
     });
   }
@@ -509,6 +532,12 @@ __global__ void __launch_bounds__(P1_TS) k_msm_bin_scatter(const fe* scalars, si
                                                            uint32_t lb, uint32_t nbins, uint32_t ntiles, const uint32_t* base, uint32_t* vals_out,
                                                            void* keys_out_, const uint32_t* tile_live) {
   msm_bin_scatter_body<CT>(scalars, n, shift, n_reg, c, W, lb, nbins, ntiles, base, vals_out, keys_out_, tile_live);
+}
+template <uint32_t CT>
+__global__ void __launch_bounds__(P1_TS) k_msm_bin_scatter_f(const fe* scalars, size_t n, const fe* shift, size_t n_reg, uint32_t c, uint32_t W,
+                                                             uint32_t lb, uint32_t nbins, uint32_t ntiles, const uint32_t* base, uint32_t* vals_out,
+                                                             void* keys_out_, const uint32_t* tile_live, uint32_t wmask) {
+  msm_bin_scatter_body<CT, true>(scalars, n, shift, n_reg, c, W, lb, nbins, ntiles, base, vals_out, keys_out_, tile_live, wmask);
 }
 
 constexpr uint32_t NQ_MAX = 128;  // buckets per bin (c = 17: 2^16 buckets in 512 bins)
@@ -1138,6 +1167,32 @@ __global__ void __launch_bounds__(128) k_msm_final(const TailBatch tb) {
   }
 }
 
+// ---- table depth: every D-th window row, D passes (h2mi_bases_register_depth) ------------------------------------------
+// The full table lets all W windows share one bucket set at the price of W x the SRS in HBM.  A base set registered with table
+// depth D keeps the rows T'[j][i] = 2^(c D' j) P_i, j < rows = ceil(W / D'), D' = min(D, W), and computes an MSM in D' passes.
+// With the signed digits d_w of a scalar, s = sum_w d_w 2^(c w): pass r takes the windows w = r mod D' and gathers row
+// floor(w / D') (the window filter of the head kernels), so the unchanged partition -> accumulation -> bucket reduction yields
+//     R_r = sum_(w = r mod D') d_w T'[floor(w / D')],     and the result is     sum_r 2^(c r) R_r.
+// Slot n of every row is the same multiple of the sum of the bases, so the dominant-value shift works per pass as it does per
+// MSM: every pass samples the same scalars and picks the same value.
+// k_msm_combine: Horner over the D' pass results, c doublings and one addition per step, on one quad of lanes — a chain of
+// (D' - 1) (c + 1) dependent lane-cooperative operations.  The pass results are converted from their 96-byte Jacobian form by
+// D' lanes at once and handed to the quad through LDS, so that the conversions are not on the chain.
+constexpr uint32_t COMBINE_THREADS = 64, COMBINE_MAX = 32;  // D' <= W <= 24 (c >= 11)
+__global__ void __launch_bounds__(COMBINE_THREADS) k_msm_combine(const uint8_t* pass_out, uint32_t passes, uint32_t c, uint32_t canonical, uint8_t* out) {
+  __shared__ xyzz29 lds[COMBINE_MAX];
+  const uint32_t tid = threadIdx.x;
+  if (tid < passes && tid < COMBINE_MAX) lds[tid] = xyzz29_from_jac(jac_load(pass_out + (size_t)tid * 96));
+  __syncthreads();
+  if (tid >= 4) return;  // one whole quad goes on
+  xyzz29 acc = lds[passes - 1];
+  for (uint32_t r = passes - 1; r-- > 0;) {
+    for (uint32_t k = 0; k < c; k++) acc = xyzz29_dbl_quad(acc);
+    acc = xyzz29_add_quad(acc, lds[r]);
+  }
+  if (tid == 0) jac_store(out, jac_from_xyzz29(acc, canonical != 0));
+}
+
 // ---- small base sets: n <= SMALL_MAX_N (round 4) --------------------------------------------------------------------
 // The pipeline above is built for throughput: nine partition kernels, an accumulation over >= 2^12 buckets and a
 // five-kernel bucket reduction whose chain of ~40 dependent point operations is the same at every size — 217 us for a
@@ -1395,6 +1450,7 @@ static void free_bases(Bases* B) {
   H2_IGNORE(hipFree(B->table));
   H2_IGNORE(hipFree(B->stable));
   H2_IGNORE(hipFree(B->host_stage));
+  H2_IGNORE(hipFree(B->pass_out));
   for (Slot& S : B->slot) {
     H2_IGNORE(hipFree(S.vals[0])); H2_IGNORE(hipFree(S.vals[1]));
     H2_IGNORE(hipFree(S.bkeys)); H2_IGNORE(hipFree(S.bincnt)); H2_IGNORE(hipFree(S.binbase)); H2_IGNORE(hipFree(S.binseg)); H2_IGNORE(hipFree(S.tile_live));
@@ -1481,12 +1537,25 @@ static int launch_level1(const Bases* B, const Slot& S, const fe* scalars, size_
   static bool attr_set_dev[16] = {};
   int rc = allow_scatter_lds(PlainWidths{}, attr_set_dev, [](auto ct) { return reinterpret_cast<const void*>(k_msm_bin_scatter<decltype(ct)::value>); });
   if (rc) return rc;
+  if (B->depth > 1) {
+    static bool attr_set_dev_f[16] = {};
+    rc = allow_scatter_lds(PlainWidths{}, attr_set_dev_f, [](auto ct) { return reinterpret_cast<const void*>(k_msm_bin_scatter_f<decltype(ct)::value>); });
+    if (rc) return rc;
+  }
   const uint32_t W = B->W;
   const fe* shift = shifted ? S.shift : nullptr;
   // the partition's first level reads the scalars twice (count, scatter): both stay on s, so work queued
   // on s after this call may overwrite them
   if (shifted) H2_LAUNCH("k_msm_pick_shift", k_msm_pick_shift, 1, 64, 0, s, scalars, n, S.shift);
+  // table depth above 1: this pass's windows (w = pass mod depth), as the filter of the _f kernels
+  uint32_t wmask = 0;
+  for (uint32_t w = B->pass; B->depth > 1 && w < W; w += B->depth) wmask |= 1u << w;
   rc = with_width(PlainWidths{}, B->c, [&](auto ct) -> int {
+    if (B->depth > 1) {
+      H2_LAUNCH("k_msm_bin_count", k_msm_bin_count_f<decltype(ct)::value>, ntiles, P1_TS, 0, s, scalars, n, shift, B->c, W, B->lb, B->nbins, ntiles, S.bincnt,
+                S.tile_live, wmask);
+      return H2MI_OK;
+    }
     H2_LAUNCH("k_msm_bin_count", k_msm_bin_count<decltype(ct)::value>, ntiles, P1_TS, 0, s, scalars, n, shift, B->c, W, B->lb, B->nbins, ntiles, S.bincnt, S.tile_live);
     return H2MI_OK;
   });
@@ -1497,6 +1566,11 @@ static int launch_level1(const Bases* B, const Slot& S, const fe* scalars, size_
   H2_LAUNCH("k_scan_seg_bins", k_scan_seg<SCAN_SEG_BINS>, dim3(nseg, 1), 1024, 0, s, (const uint32_t*)S.bincnt, S.binbase, (const uint32_t*)nullptr,
             (uint32_t*)nullptr, cells, (const uint32_t*)S.binseg);
   return with_width(PlainWidths{}, B->c, [&](auto ct) -> int {
+    if (B->depth > 1) {
+      H2_LAUNCH("k_msm_bin_scatter", k_msm_bin_scatter_f<decltype(ct)::value>, ntiles, P1_TS, (size_t)P1_TS * W * 6, s, scalars, n, shift, B->stride, B->c, W,
+                B->lb, B->nbins, ntiles, (const uint32_t*)S.binbase, S.vals[0], S.bkeys, (const uint32_t*)S.tile_live, wmask);
+      return H2MI_OK;
+    }
     H2_LAUNCH("k_msm_bin_scatter", k_msm_bin_scatter<decltype(ct)::value>, ntiles, P1_TS, (size_t)P1_TS * W * 6, s, scalars, n, shift, B->stride, B->c, W, B->lb,
               B->nbins, ntiles, (const uint32_t*)S.binbase, S.vals[0], S.bkeys, (const uint32_t*)S.tile_live);
     return H2MI_OK;
@@ -1542,8 +1616,8 @@ static TailDesc tail_desc(const Bases* B, const Slot& S) {
   d.part0 = S.part[0];
   d.toff0 = S.toff[0]; d.np0 = S.np[0]; d.toff1 = S.toff[1]; d.np1 = S.np[1]; d.off = S.off;
   d.part1 = S.part[1]; d.dense = S.dense; d.rc = S.rc; d.g = S.g; d.out = (uint8_t*)S.d_out;
-  d.stats = S.stats;
-  d.nb = B->nb; d.logNh = B->logNh; d.logNl = B->logNl; d.canonical = g_canonical ? 1u : 0u;
+  d.stats = S.stats + (B->depth > 1 ? 1 + B->pass : 0);  // table depth above 1: one cell per pass behind [0] (h2mi_msm_last_stats sums them)
+  d.nb = B->nb; d.logNh = B->logNh; d.logNl = B->logNl; d.canonical = g_canonical && B->depth == 1 ? 1u : 0u;  // (a pass result is normalised by k_msm_combine, if at all)
   d.seg_log = B->seg_log; d.dense2 = S.dense2; d.vsum = S.vsum; d.mat = B->seg_log ? S.dense2 : S.dense;
   d.hot_min = B->seg_log ? HOT_MIN_WIDE : HOT_MIN;
   // wide windows: 2^17 .. 2^19 buckets hold a partial or two each, the fold level would copy them (0.08 - 0.18 ms per MSM, measured);
@@ -1758,7 +1832,7 @@ static int msm_general(Bases* B, const void* const* d_scalars, size_t m, size_t 
   // dominant-value shift: only when the MSM covers every registered base (the extra base is their sum)
   const bool shifted = B->has_sum && n == B->n;
   const size_t n_eff = n + (shifted ? 1 : 0);
-  const uint32_t total = (uint32_t)(n_eff * W), ntiles = ceil_div_u32(n_eff, P1_TS);
+  const uint32_t total = (uint32_t)(n_eff * B->rows), ntiles = ceil_div_u32(n_eff, P1_TS);  // rows = W at table depth 1; a pass leaves at most one entry per row
   // chunk length: chosen by k_msm_bin_sort from the entry count unless H2MI_MSM_S0 fixes it; the partial buffers
   // were sized at registration, so an override must not produce more chunks than they hold
   uint32_t s0_fixed = chunk_override();
@@ -1853,7 +1927,28 @@ static bool take_small(const Bases* B, bool general) {
 constexpr size_t HEAD_BATCH_MAX_N = (size_t)1 << 17;  // largest base set whose MSMs are partitioned and accumulated as a batch
 // m MSMs over one base set, issued together: one path for the group (a long phase crosses the streaming threshold of take_small
 // on its way, group by group).  `batch`: the forms that launch all m heads at once (msm_batch_entry); else m = 1.
+// One MSM over a base set with a table depth above 1 (see "table depth"): its passes through the `inorder` form of the general pipeline,
+// one after the other on s with nothing deferred, pass r writing pass_out + 96 r, then k_msm_combine on s — the result is written in
+// stream order.  The handle's one slot carries the ordering against its next MSM on another stream: the tail event is recorded again
+// behind the combine, the last reader of pass_out.
+static int msm_compact(Bases* B, const void* d_scalars, size_t n, void* d_out, hipStream_t s) {
+  B->last_small = false;
+  B->since_join++;
+  for (uint32_t r = 0; r < B->depth; r++) {
+    B->pass = r;
+    int rc = msm_general(B, &d_scalars, 1, n, B->pass_out + (size_t)r * 96, s, /*inorder=*/true, /*batch=*/false);
+    if (rc) return rc;
+  }
+  H2_LAUNCH("k_msm_combine", k_msm_combine, 1, COMBINE_THREADS, 0, s, (const uint8_t*)B->pass_out, B->depth, B->c, g_canonical ? 1u : 0u, (uint8_t*)d_out);
+  H2_HIP(B->slot[0].tail.record(s));
+  return H2MI_OK;
+}
 static int msm_group(Bases* B, const void* const* d_scalars, size_t m, size_t n, void* d_out, hipStream_t s, bool inorder, bool general, bool batch) {
+  if (B->depth > 1) {  // the flags change nothing here; a group is the loop over its members
+    for (size_t j = 0; j < m; j++)
+      if (int rc = msm_compact(B, d_scalars[j], n, (char*)d_out + 96 * j, s)) return rc;
+    return H2MI_OK;
+  }
   B->last_small = take_small(B, general);
   B->since_join += (uint32_t)m;
   return B->last_small ? msm_small(B, d_scalars, m, n, d_out, s, inorder, batch) : msm_general(B, d_scalars, m, n, d_out, s, inorder, batch);
@@ -1865,6 +1960,7 @@ static int msm_dev(Bases* B, const void* d_scalars, size_t n, void* d_out, hipSt
 #define H2_ALLOC(ptr, bytes)                                   \
   do {                                                         \
     hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));        \
+    B->workspace_bytes += (bytes);                             \
     if (e_ != hipSuccess) {                                    \
       note_hip_error(e_, __FILE__, __LINE__);                  \
       free_bases(B);                                           \
@@ -1872,7 +1968,7 @@ static int msm_dev(Bases* B, const void* d_scalars, size_t n, void* d_out, hipSt
     }                                                          \
   } while (0)
 
-static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hipStream_t s, bool allow_small = true) {
+static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hipStream_t s, bool allow_small = true, uint32_t depth = 1) {
   if (n == 0 || n > ((size_t)1 << 26)) return H2MI_ERANGE;
   Bases* B = new Bases();
   B->n = n;
@@ -1884,12 +1980,16 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
   B->seg_log = B->c - 1 > MAT_LOG ? B->c - 1 - MAT_LOG : 0;
   B->logNl = (B->c - 1 - B->seg_log + 1) / 2;
   B->logNh = (B->c - 1 - B->seg_log) - B->logNl;
-  if ((uint64_t)B->stride * B->W >= (1ull << 31)) { delete B; return H2MI_ERANGE; }
-  const size_t nW = B->stride * B->W;
+  B->depth = std::min(depth, B->W);
+  B->rows = (B->W + B->depth - 1) / B->depth;  // = W at depth 1
+  if ((uint64_t)B->stride * B->rows >= (1ull << 31)) { delete B; return H2MI_ERANGE; }
+  const size_t nW = B->stride * B->rows;  // table entries, and the most entries one pass of an MSM leaves
   // partial sums of one accumulation: one per chunk (at most whole rounds of the resident grid) + one per bucket
   B->max_tasks0 = std::min(accum_rounds((uint32_t)nW) * ACCUM_RESIDENT_CHUNKS, (uint32_t)nW) + B->nb + 1;
   B->max_tasks1 = B->max_tasks0 / S1 + B->nb;
   H2_ALLOC(B->table, nW * 64);
+  B->table_bytes = B->workspace_bytes;
+  B->workspace_bytes = 0;
   B->lb = B->c - 1 > 9 ? B->c - 1 - 9 : 0;
   B->nbins = B->nb >> B->lb;  // <= NBINS_MAX
   const size_t ntiles_max = (B->stride + P1_TS - 1) / P1_TS;
@@ -1898,7 +1998,8 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
   // the own scans (k_scan_seg) take 16-byte vectors: the [bin][tile] matrix has 512 rows and the task arrays
   // 2^(c-1) >= 1024 entries for every window width pick_window() can return
   if ((B->nbins & 3u) || B->nb < 4 || (B->nb > SCAN_SEG_TASKS && !B->seg_log) || B->nbins > NBINS_MAX || (1u << B->lb) > NQW) { free_bases(B); return H2MI_ERANGE; }
-  B->nslot = n > ((size_t)1 << 17) ? 4 : NSLOT;
+  B->nslot = B->depth > 1 ? 1 : n > ((size_t)1 << 17) ? 4 : NSLOT;  // the passes of a compact handle run one after the other
+  if (B->depth > 1) H2_ALLOC(B->pass_out, (size_t)B->W * 96);  // depth <= W results (the size does not grow with the depth: h2mi_bases_memory is monotone)
   for (int si_ = 0; si_ < B->nslot; si_++) {
     Slot& S = B->slot[si_];
     for (int i = 0; i < 2; i++) H2_ALLOC(S.vals[i], nW * 4);
@@ -1923,7 +2024,7 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
     H2_ALLOC(S.part[1], (size_t)B->max_tasks1 * PART_BYTES);
     H2_ALLOC(S.rc, (size_t)((2u << B->logNh) + (1u << B->logNl)) * PART_BYTES);  // row, column (and wide: vsum row) sums
     H2_ALLOC(S.g, (size_t)64 * PART_BYTES);
-    H2_ALLOC(S.stats, 64);
+    H2_ALLOC(S.stats, B->depth > 1 ? 256 : 64);  // depth > 1: [1 + pass] = insertions of the pass (depth <= 24)
     H2_ALLOC(S.shift, 32);
     if (S.create_events() != hipSuccess) {
       free_bases(B);
@@ -1936,16 +2037,16 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
     hipLaunchKernelGGL(k_msm_table_first, dim3(ceil_div_u32(n, 256)), dim3(256), 0, s, (const uint8_t*)d_bases, B->table, n);
     if (prof_) prof_end(s);
   }
-  for (uint32_t w = 1; w < B->W; w++) {
+  for (uint32_t w = 1; w < B->rows; w++) {
     const bool prof_ = prof_on("k_msm_table_next");
     if (prof_) prof_begin("k_msm_table_next", s);
     hipLaunchKernelGGL(k_msm_table_next, dim3(ceil_div_u32(n, 256)), dim3(256), 0, s, (const uint8_t*)(B->table + (size_t)(w - 1) * B->stride * 64),
-                       B->table + (size_t)w * B->stride * 64, n, B->c);
+                       B->table + (size_t)w * B->stride * 64, n, B->c * B->depth);
     if (prof_) prof_end(s);
   }
   // (an ad-hoc base set — handle = 0: used once or a few times — keeps the general pipeline: the multiples table costs ~10 ms of
   // dependent conversions to build, which pays for a registered SRS and not for a one-off slice)
-  if (allow_small && small_geometry(n, &B->sc, &B->slanes, &B->sr)) {  // second table for the latency path: every multiple a signed digit can select
+  if (allow_small && B->depth == 1 && small_geometry(n, &B->sc, &B->slanes, &B->sr)) {  // second table for the latency path: every multiple a signed digit can select
     B->sW = (255 + B->sc - 1) / B->sc;
     B->sG = ceil_div_u32((uint64_t)n * B->sW, (uint64_t)B->slanes * B->sr);
     const uint32_t NBs = 1u << (B->sc - 1);
@@ -1973,6 +2074,8 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
       B->stable = nullptr;
     }
     if (fits) {
+    B->table_bytes += (uint64_t)NBs * plane * 64;
+    B->workspace_bytes += (uint64_t)B->nslot * (plane + (size_t)B->sG * PART_BYTES + (size_t)(B->sG + 1) * 4);
     if (hipMemcpyAsync(B->stable, B->table, n * 64, hipMemcpyDeviceToDevice, s) != hipSuccess) { free_bases(B); return H2MI_EHIP; }
     for (uint32_t w = 1; w < B->sW; w++)
       hipLaunchKernelGGL(k_msm_table_next, dim3(ceil_div_u32(n, 64)), dim3(64), 0, s, (const uint8_t*)(B->stable + (size_t)(w - 1) * n * 64),
@@ -1981,8 +2084,8 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
     B->small = true;
     }
   }
-  // slot n of every window stays the identity until the sum point is known
-  for (uint32_t w = 0; w < B->W; w++)
+  // slot n of every row stays the identity until the sum point is known
+  for (uint32_t w = 0; w < B->rows; w++)
     if (hipMemsetAsync(B->table + ((size_t)w * B->stride + n) * 64, 0, 64, s) != hipSuccess) { free_bases(B); return H2MI_EHIP; }
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { free_bases(B); return H2MI_EHIP; }
   // B = sum of the bases, by an all-ones MSM through the pipeline just built (the shift is off while has_sum is
@@ -2000,7 +2103,7 @@ static int register_dev(const void* d_bases, size_t n, uint64_t* handle_out, hip
     }
     if (!rc) rc = msm_join_all(s);
     if (!rc) {
-      hipLaunchKernelGGL(k_msm_table_sum_point, dim3(1), dim3(64), 0, s, (const uint8_t*)sum, B->table, B->stride, n, B->W, B->c);
+      hipLaunchKernelGGL(k_msm_table_sum_point, dim3(1), dim3(64), 0, s, (const uint8_t*)sum, B->table, B->stride, n, B->rows, B->c * B->depth);
       if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) rc = H2MI_EHIP;
     }
     H2_IGNORE(hipFree(ones));
@@ -2260,6 +2363,59 @@ int h2mi_bases_register(const uint64_t* bases, size_t n, uint64_t* handle_out) {
   return rc;
 }
 
+int h2mi_bases_register_depth_dev(const void* d_bases, size_t n, uint32_t table_depth, uint64_t* handle_out) {
+  if (table_depth == 0) return H2MI_EINVAL;
+  if (table_depth == 1) return h2mi_bases_register_dev(d_bases, n, handle_out);
+  H2_REQUIRE_INIT();
+  if (!d_bases || !handle_out) return H2MI_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  if (ctx().devs.size() > 1) return H2MI_EINVAL;  // sharded compact sets: not built
+  return register_dev(d_bases, n, handle_out, ctx().stream, /*allow_small=*/false, table_depth);
+}
+
+int h2mi_bases_register_depth(const uint64_t* bases, size_t n, uint32_t table_depth, uint64_t* handle_out) {
+  if (table_depth == 0) return H2MI_EINVAL;
+  if (table_depth == 1) return h2mi_bases_register(bases, n, handle_out);
+  H2_REQUIRE_INIT();
+  if (!bases || !handle_out || n == 0) return H2MI_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  if (ctx().devs.size() > 1) return H2MI_EINVAL;
+  DevMem d;
+  hipError_t e = d.alloc(n * 64);
+  if (e == hipErrorOutOfMemory) return H2MI_ENOMEM;
+  H2_HIP(e);
+  int rc = H2MI_OK;
+  if (hipMemcpyAsync(d.p, bases, n * 64, hipMemcpyHostToDevice, ctx().stream) != hipSuccess) rc = H2MI_EHIP;
+  if (!rc) rc = register_dev(d.p, n, handle_out, ctx().stream, /*allow_small=*/false, table_depth);
+  H2_IGNORE(hipStreamSynchronize(ctx().stream));
+  return rc;
+}
+
+int h2mi_bases_memory(uint64_t handle, uint32_t* table_depth, uint32_t* table_rows, uint64_t* table_bytes, uint64_t* workspace_bytes) {
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  auto sh = g_sharded.find(handle);
+  if (sh != g_sharded.end()) {  // depth and rows of the first slice, bytes summed over the slices
+    uint64_t tb = 0, wb = 0;
+    for (size_t i = 0; i < sh->second->shard.size(); i++) {
+      uint64_t t = 0, w = 0;
+      int rc = h2mi_bases_memory(sh->second->shard[i].handle, i ? nullptr : table_depth, i ? nullptr : table_rows, &t, &w);
+      if (rc) return rc;
+      tb += t;
+      wb += w;
+    }
+    if (table_bytes) *table_bytes = tb;
+    if (workspace_bytes) *workspace_bytes = wb;
+    return H2MI_OK;
+  }
+  auto it = g_bases.find(handle);
+  if (it == g_bases.end()) return H2MI_EHANDLE;
+  if (table_depth) *table_depth = it->second->depth;
+  if (table_rows) *table_rows = it->second->rows;
+  if (table_bytes) *table_bytes = it->second->table_bytes;
+  if (workspace_bytes) *workspace_bytes = it->second->workspace_bytes;
+  return H2MI_OK;
+}
+
 int h2mi_bases_release(uint64_t handle) {
   H2_REQUIRE_INIT();
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
@@ -2412,7 +2568,8 @@ static int msm_batch_entry(uint64_t handle, const void* const* d_scalars, size_t
   // `sparse` (the caller's promise that the columns are mostly zeros or one repeated value): the kernels of such an MSM are short at
   // EVERY size — a 2^20-row witness column is 25 us of digit counting and a handful of 6-us kernels — so the batch is taken at any size
   if (count == 1 && inorder) return msm_dev_entry(handle, d_scalars[0], n, d_out_jacobian, stream, true, general);
-  if (n != 0 && count > 1 && pipelined(s, /*inorder=*/false) && it != g_bases.end() && n <= it->second->n && (it->second->n <= HEAD_BATCH_MAX_N || sparse)) {
+  if (n != 0 && count > 1 && pipelined(s, /*inorder=*/false) && it != g_bases.end() && n <= it->second->n && it->second->depth == 1 &&
+      (it->second->n <= HEAD_BATCH_MAX_N || sparse)) {
     Bases* B = it->second;
     if (B->small || B->seg_log == 0) {
       for (size_t j0 = 0; j0 < count;) {
@@ -2530,7 +2687,13 @@ int h2mi_msm_last_stats(uint64_t handle, uint64_t* bucket_adds, uint64_t* reduce
   }
   H2_HIP(hipDeviceSynchronize());
   uint64_t st = 0;
-  H2_HIP(hipMemcpy(&st, B->slot[B->last_slot].stats, 8, hipMemcpyDeviceToHost));
+  if (B->depth > 1) {  // sums over the passes; the combine adds (depth - 1) (c + 1) point operations
+    uint64_t per_pass[32];
+    H2_HIP(hipMemcpy(per_pass, B->slot[0].stats + 1, (size_t)B->depth * 8, hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < B->depth; r++) st += per_pass[r];
+  } else {
+    H2_HIP(hipMemcpy(&st, B->slot[B->last_slot].stats, 8, hipMemcpyDeviceToHost));
+  }
   if (bucket_adds) *bucket_adds = st;
   if (reduce_adds && B->last_small) {  // the quad trees: 255 additions per workgroup of 256 lanes, then over the partial sums
     *reduce_adds = (uint64_t)B->sG * (B->slanes - 1) + B->sG;
@@ -2540,6 +2703,7 @@ int h2mi_msm_last_stats(uint64_t handle, uint64_t* bucket_adds, uint64_t* reduce
     const uint64_t mat = (uint64_t)B->nb >> B->seg_log;  // wide windows: 2 (L - 1) additions per segment of L buckets first
     *reduce_adds = (B->seg_log ? 2ull * (B->nb - mat) + mat : 0ull) + 2ull * mat + (B->logNh * Nh + (B->logNl + 1) * Nl) / 2 +
                    (B->logNh + B->logNl + 1) * (uint64_t)(B->c);
+    if (B->depth > 1) *reduce_adds = *reduce_adds * B->depth + (uint64_t)(B->depth - 1) * (B->c + 1);
   }
   return H2MI_OK;
 }

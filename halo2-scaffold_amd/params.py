@@ -50,17 +50,17 @@ def gen_srs_secret() -> int:
     return wide % F.FR_MODULUS
 
 
-def gen_srs(k: int, params_dir: str = None) -> "ParamsKZG":
+def gen_srs(k: int, params_dir: str = None, table_depth: int = 1) -> "ParamsKZG":
     """halo2-base `gen_srs` / `read_or_create_srs`: read {PARAMS_DIR or ./params}/kzg_bn254_{k}.srs if it exists, else
-    set the SRS up from the fixed-seed rng above and write the file."""
+    set the SRS up from the fixed-seed rng above and write the file.  table_depth: see ParamsKZG."""
     import os
 
     d = params_dir or os.environ.get("PARAMS_DIR", "./params")
     path = os.path.join(d, f"kzg_bn254_{k}.srs")
     if os.path.exists(path):
         with open(path, "rb") as f:
-            return ParamsKZG.read(f)
-    p = ParamsKZG.setup(k, gen_srs_secret())
+            return ParamsKZG.read(f, table_depth=table_depth)
+    p = ParamsKZG.setup(k, gen_srs_secret(), table_depth=table_depth)
     os.makedirs(d, exist_ok=True)
     with open(path, "wb") as f:
         p.write(f)
@@ -68,8 +68,13 @@ def gen_srs(k: int, params_dir: str = None) -> "ParamsKZG":
 
 
 class ParamsKZG:
-    def __init__(self, k: int):
+    """table_depth (setup / from_bases / from_monomial / read / register_slice, default 1): the MSM tables of both base sets keep
+    every table_depth-th window row and an MSM runs that many passes (h2mi_bases_register_depth: less device memory, slower
+    commitments, the same points).  device_bytes() says what the handles hold."""
+
+    def __init__(self, k: int, table_depth: int = 1):
         self.k = k
+        self.table_depth = table_depth
         self.n = 1 << k
         self.g_handle = None
         self.g_lagrange_handle = None
@@ -80,10 +85,10 @@ class ParamsKZG:
         self.s_g2_bytes = None
 
     @classmethod
-    def setup(cls, k: int, s: int, register: bool = True) -> "ParamsKZG":
+    def setup(cls, k: int, s: int, register: bool = True, table_depth: int = 1) -> "ParamsKZG":
         """register=False: generate the SRS on the device but build no MSM tables (a multi-GPU rank registers only
         its slice, see register_slice)."""
-        p = cls(k)
+        p = cls(k, table_depth)
         n = p.n
         p.g2_bytes = G2.to_bytes(G2.G2_GENERATOR)
         p.s_g2_bytes = G2.to_bytes(G2.scalar_mul(s))
@@ -104,25 +109,25 @@ class ParamsKZG:
             p._register()
         return p
 
-    def register_slice(self, lo: int, hi: int) -> "ParamsKZG":
+    def register_slice(self, lo: int, hi: int, table_depth: int = 1) -> "ParamsKZG":
         """ParamsKZG over bases [lo, hi) of both sets: the slice one rank of a sliced multi-GPU MSM owns
         (SURVEY.md 8e).  The window tables are built straight from this SRS's device-resident points."""
         assert 0 <= lo < hi <= self.n and self._gl_dev is not None
-        p = ParamsKZG(self.k)
+        p = ParamsKZG(self.k, table_depth)
         p.n = hi - lo
         p.lo = lo
         p.g2_bytes, p.s_g2_bytes = self.g2_bytes, self.s_g2_bytes
         h = C.c_uint64()
-        check(lib.h2mi_bases_register_dev(self._g_dev.ptr + lo * 64, p.n, C.byref(h)), "register g slice")
+        check(lib.h2mi_bases_register_depth_dev(self._g_dev.ptr + lo * 64, p.n, table_depth, C.byref(h)), "register g slice")
         p.g_handle = h.value
         h2 = C.c_uint64()
-        check(lib.h2mi_bases_register_dev(self._gl_dev.ptr + lo * 64, p.n, C.byref(h2)), "register g_lagrange slice")
+        check(lib.h2mi_bases_register_depth_dev(self._gl_dev.ptr + lo * 64, p.n, table_depth, C.byref(h2)), "register g_lagrange slice")
         p.g_lagrange_handle = h2.value
         return p
 
     @classmethod
-    def from_bases(cls, k: int, g: np.ndarray, g_lagrange: np.ndarray = None) -> "ParamsKZG":
-        p = cls(k)
+    def from_bases(cls, k: int, g: np.ndarray, g_lagrange: np.ndarray = None, table_depth: int = 1) -> "ParamsKZG":
+        p = cls(k, table_depth)
         assert len(g) == p.n
         p._g_dev = DevBuf.from_numpy(np.ascontiguousarray(g, dtype=np.uint64))
         if g_lagrange is not None:
@@ -131,12 +136,12 @@ class ParamsKZG:
         return p
 
     @classmethod
-    def from_monomial(cls, k: int, g: np.ndarray, g2_bytes: bytes = None, s_g2_bytes: bytes = None) -> "ParamsKZG":
+    def from_monomial(cls, k: int, g: np.ndarray, g2_bytes: bytes = None, s_g2_bytes: bytes = None, table_depth: int = 1) -> "ParamsKZG":
         """the whole SRS from its monomial half, WITHOUT the secret — what ParamsKZG::setup does after its powers of s
         (`best_fft(&mut g_lagrange_projective, root.invert(), k)`, then n^-1; poly/kzg/commitment.rs [RECALL]): the group-valued inverse
         transform of g on the device (h2mi_fft_bn254_g1_dev).  For an SRS that arrives as points (a ceremony file, a fork's own
         `setup`); `setup(k, s)` above takes the shortcut through the exponents that knowing s allows."""
-        p = cls(k)
+        p = cls(k, table_depth)
         assert len(g) == p.n
         p.g2_bytes, p.s_g2_bytes = g2_bytes, s_g2_bytes
         p._g_dev = DevBuf.from_numpy(np.ascontiguousarray(g, dtype=np.uint64))
@@ -149,11 +154,11 @@ class ParamsKZG:
 
     def _register(self):
         h = C.c_uint64()
-        check(lib.h2mi_bases_register_dev(self._g_dev.ptr, self.n, C.byref(h)), "register g")
+        check(lib.h2mi_bases_register_depth_dev(self._g_dev.ptr, self.n, self.table_depth, C.byref(h)), "register g")
         self.g_handle = h.value
         if self._gl_dev is not None:
             h2 = C.c_uint64()
-            check(lib.h2mi_bases_register_dev(self._gl_dev.ptr, self.n, C.byref(h2)), "register g_lagrange")
+            check(lib.h2mi_bases_register_depth_dev(self._gl_dev.ptr, self.n, self.table_depth, C.byref(h2)), "register g_lagrange")
             self.g_lagrange_handle = h2.value
 
     # ---- ParamsKZG::write / read: k (u32 LE), g, g_lagrange (32-byte compressed points), g2, s_g2 ----
@@ -171,14 +176,14 @@ class ParamsKZG:
         writer.write(self.s_g2_bytes)
 
     @classmethod
-    def read(cls, reader) -> "ParamsKZG":
+    def read(cls, reader, table_depth: int = 1) -> "ParamsKZG":
         head = reader.read(4)
         if len(head) != 4:
             raise serde.DecodeError("SRS file too short")
         (k,) = struct.unpack("<I", head)
         if not 1 <= k <= 26:
             raise serde.DecodeError(f"implausible k = {k} in SRS file")
-        p = cls(k)
+        p = cls(k, table_depth)
         n = p.n
         tmp = DevBuf(n * 32)
         devs = []
@@ -219,6 +224,17 @@ class ParamsKZG:
     def commit_dev(self, d_poly: DevBuf, d_out: DevBuf, n=None, lagrange=False, stream=None, out_offset=0):
         h = self.g_lagrange_handle if lagrange else self.g_handle
         check(lib.h2mi_msm_bn254_g1_dev(h, d_poly.ptr, self.n if n is None else n, d_out.ptr + out_offset, stream), "commit_dev")
+
+    def device_bytes(self):
+        """(table bytes, workspace bytes) the registered handles hold on the device: the sums of h2mi_bases_memory over them"""
+        tb_sum = wb_sum = 0
+        for h in (self.g_handle, self.g_lagrange_handle):
+            if h:
+                tb, wb = C.c_uint64(), C.c_uint64()
+                check(lib.h2mi_bases_memory(h, None, None, C.byref(tb), C.byref(wb)), "bases memory")
+                tb_sum += tb.value
+                wb_sum += wb.value
+        return tb_sum, wb_sum
 
     def release(self):
         for h in (self.g_handle, self.g_lagrange_handle):

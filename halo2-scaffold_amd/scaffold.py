@@ -74,13 +74,14 @@ class ProvingKey:
         self.params.release()
 
 
-def gen_key(f, dummy_inputs, by_coset: bool = False):
+def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1):
     """src/scaffold.rs:95-156: the circuit's shape from a run on dummy inputs (GateThreadBuilder::keygen + builder.config), the SRS
-    from gen_srs(k), keygen_vk + keygen_pk -> (pk, break_points).  by_coset: flex.FlexKeys' (no extended-coset columns on the device)"""
+    from gen_srs(k), keygen_vk + keygen_pk -> (pk, break_points).  by_coset: flex.FlexKeys' (no extended-coset columns on the device);
+    table_depth: ParamsKZG's (every table_depth-th row of the MSM tables, as many passes per commitment)"""
     k, lookup_bits, minimum_rows = _env()
     cs = _config(f, dummy_inputs, k, lookup_bits, minimum_rows)
     asg = _synthesize(f, dummy_inputs, cs, lookup_bits)
-    params = gen_srs(k)
+    params = gen_srs(k, table_depth=table_depth)
     pk = ProvingKey(params, flex.FlexKeys(params, cs, asg, by_coset=by_coset))
     pk.lookup_bits = lookup_bits
     return pk, [list(asg.break_points)]
@@ -109,9 +110,9 @@ def mock_device(f, private_inputs, pk: ProvingKey):
     return list(asg.instance)
 
 
-def prove(f, private_inputs, dummy_inputs):
+def prove(f, private_inputs, dummy_inputs, by_coset: bool = False, table_depth: int = 1):
     """src/scaffold.rs:246-366: keygen on dummy inputs, then one proof of the private inputs -> (proof bytes, public inputs)"""
-    pk, break_points = gen_key(f, dummy_inputs)
+    pk, break_points = gen_key(f, dummy_inputs, by_coset=by_coset, table_depth=table_depth)
     try:
         public_io = prove_private(f, private_inputs, pk, break_points)
         return pk.last_proof, public_io

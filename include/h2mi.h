@@ -118,6 +118,27 @@ int h2mi_bases_register_dev(const void* d_bases /* n*64 B */, size_t n, uint64_t
 int h2mi_bases_release(uint64_t handle);
 /* window bits c, window count W, bucket count, registered n */
 int h2mi_bases_info(uint64_t handle, uint32_t* c, uint32_t* windows, uint32_t* buckets, uint64_t* n);
+/* Registration with a TABLE DEPTH: the full table is W x (n + 1) x 64 B per base set (0.94 GiB at n = 2^20, 3.25 GiB at 2^22) and lets
+ * all windows share one bucket set.  At table depth D the handle keeps only every D'-th window row, D' = min(D, W): rows =
+ * ceil(W / D') rows 2^(c D' j) P_i, and one workspace slot sized for rows x (n + 1) entries instead of four or eight for W x (n + 1).
+ * An MSM on it runs D' passes, pass r over the windows w = r mod D' (partition, accumulation and bucket reduction as ever, against row
+ * floor(w / D')), and one last kernel combines the pass results as sum_r 2^(c r) R_r.  The mode trades time for memory:
+ * the accumulation work is unchanged, the partition head and the bucket reduction run D' times (profiles/table_depth_cost.txt).
+ *   table_depth == 0    H2MI_EINVAL
+ *   table_depth == 1    exactly h2mi_bases_register{,_dev}
+ *   table_depth >= W    the bases alone (1 / W of the table)
+ * MSMs on such a handle run in order on the stream they are given (NULL = the library's) with nothing deferred to the next join: the
+ * result is written in stream order, and the scalars may be overwritten by work queued on that stream after the call.  The handle never
+ * has the latency path's table; the flags of h2mi_msm_bn254_g1_phase_dev are accepted and change nothing, and a group is the loop
+ * over its members.  Results are the same group elements as at depth 1 (and with h2mi_msm_set_canonical(1) the same bytes).
+ * After h2mi_init_devices with more than one device a depth above 1 is H2MI_EINVAL: sharded compact base sets are not built yet.
+ * The ad-hoc cache of h2mi_msm_bn254_g1 (handle == 0) keeps full tables. */
+int h2mi_bases_register_depth(const uint64_t* bases /* n*8 limbs */, size_t n, uint32_t table_depth, uint64_t* handle_out);
+int h2mi_bases_register_depth_dev(const void* d_bases /* n*64 B */, size_t n, uint32_t table_depth, uint64_t* handle_out);
+/* what the handle holds on the device: effective depth D', table rows, bytes of the table(s) incl. the latency
+ * path's, bytes of the slots' workspaces (the bytes asked of the allocator; a sharded handle: summed over its slices,
+ * depth and rows of the first); any pointer may be NULL */
+int h2mi_bases_memory(uint64_t handle, uint32_t* table_depth, uint32_t* table_rows, uint64_t* table_bytes, uint64_t* workspace_bytes);
 
 /* ---- MSM: halo2_proofs::arithmetic::best_multiexp(coeffs, bases) -> C::Curve ---------------------
  * Replaces best_multiexp for C = bn256::G1Affine; computes sum_i s_i * P_i over

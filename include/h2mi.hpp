@@ -506,7 +506,8 @@ namespace kzg {
 class ParamsKZG {
  public:
   // ParamsKZG::setup(k, rng): the toxic-waste scalar is passed explicitly (the reference draws it from OsRng)
-  static ParamsKZG setup(uint32_t k, const Fr& s) {
+  // table_depth: h2mi_bases_register_depth's (1 = full MSM tables; D keeps every D-th window row and commits in D passes)
+  static ParamsKZG setup(uint32_t k, const Fr& s, uint32_t table_depth = 1) {
     ParamsKZG p(k);
     const size_t n = p.n_;
     arithmetic::DeviceVec pw(n);
@@ -518,8 +519,8 @@ class ParamsKZG {
     check(h2mi_malloc(n * 64, &p.d_gl_), "h2mi_malloc");
     check(h2mi_g1_fixed_base_mul_dev(pw.p, n, p.d_gl_, nullptr), "g_lagrange");
     check(h2mi_sync(), "sync");
-    check(h2mi_bases_register_dev(p.d_g_, n, &p.h_g_), "register g");
-    check(h2mi_bases_register_dev(p.d_gl_, n, &p.h_gl_), "register g_lagrange");
+    check(h2mi_bases_register_depth_dev(p.d_g_, n, table_depth, &p.h_g_), "register g");
+    check(h2mi_bases_register_depth_dev(p.d_gl_, n, table_depth, &p.h_gl_), "register g_lagrange");
     return p;
   }
   ParamsKZG(ParamsKZG&& o) noexcept { *this = std::move(o); }
@@ -569,7 +570,7 @@ class ParamsKZG {
     w.write(reinterpret_cast<const char*>(g2_.data()), 64);
     w.write(reinterpret_cast<const char*>(s_g2_.data()), 64);
   }
-  static ParamsKZG read(std::istream& r) {
+  static ParamsKZG read(std::istream& r, uint32_t table_depth = 1) {
     uint32_t k32 = 0;
     r.read(reinterpret_cast<char*>(&k32), 4);
     if (!r || k32 < 1 || k32 > 26) throw Error(H2MI_EINVAL, "ParamsKZG::read: bad header");
@@ -594,8 +595,8 @@ class ParamsKZG {
     r.read(reinterpret_cast<char*>(p.s_g2_.data()), 64);
     if (!r) throw Error(H2MI_EINVAL, "ParamsKZG::read: truncated file");
     p.have_g2_ = true;
-    check(h2mi_bases_register_dev(p.d_g_, n, &p.h_g_), "register g");
-    check(h2mi_bases_register_dev(p.d_gl_, n, &p.h_gl_), "register g_lagrange");
+    check(h2mi_bases_register_depth_dev(p.d_g_, n, table_depth, &p.h_g_), "register g");
+    check(h2mi_bases_register_depth_dev(p.d_gl_, n, table_depth, &p.h_gl_), "register g_lagrange");
     return p;
   }
 
