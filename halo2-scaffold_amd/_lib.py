@@ -33,6 +33,7 @@ def _load():
         "h2mi_init": ([C.c_int], C.c_int),
         "h2mi_init_devices": ([C.c_int], C.c_int),
         "h2mi_device_count": ([], C.c_int),
+        "h2mi_primary_device": ([], C.c_int),
         "h2mi_shutdown": ([], None),
         "h2mi_strerror": ([C.c_int], C.c_char_p),
         "h2mi_version": ([], C.c_char_p),
@@ -82,6 +83,9 @@ def _load():
         "h2mi_fr_batch_invert_dev": ([vp, sz, vp, vp], C.c_int),
         "h2mi_fr_assigned_evaluate_dev": ([vp, sz, vp, vp], C.c_int),
         "h2mi_fr_assigned_columns_dev": ([vp, C.c_uint32, C.c_int, u64p, vp], C.c_int),
+        # witness cells from device memory / as 64-bit integers: one k_cells_scatter launch for up to 64 columns
+        "h2mi_fr_scatter_cells_dev": ([vp, C.c_uint32, u64p, vp], C.c_int),
+        "h2mi_fr_scatter_cells_staged_dev": ([vp, C.c_uint32, C.c_uint64, u64p, vp], C.c_int),
         "h2mi_fr_random_dev": ([vp, sz, C.c_uint64, C.c_uint64, vp], C.c_int),
         "h2mi_fr_random_chacha_dev": ([vp, sz, vp, C.c_uint64, C.c_uint64, vp], C.c_int),
         "h2mi_ntt_bn254_fr": ([vp, vp, C.c_uint32], C.c_int),
@@ -153,6 +157,7 @@ def _load():
         "h2mi_profile_query": ([C.c_char_p, C.POINTER(C.c_double), u64p], C.c_int),
         # include/h2mi_prover.h: the resident prover behind its phase-level ABI
         "h2mi_prover_keygen": ([vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
+        "h2mi_column_cells_check": ([vp, C.c_uint32, C.c_uint], C.c_int),
         "h2mi_gate_program_check": ([vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_shape_gate_program": ([vp, vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_prover_keygen_gates": ([vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),

@@ -213,6 +213,11 @@ int h2mi_device_count(void) {
   return ctx().inited ? (int)ctx().devs.size() : 0;
 }
 
+int h2mi_primary_device(void) {
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  return ctx().inited && !ctx().devs.empty() ? ctx().devs[0].device : -1;
+}
+
 static hipEvent_t g_wait_ring[32] = {};  // h2mi_stream_wait's events; destroyed by h2mi_shutdown (they belong to its device)
 static unsigned g_wait_next = 0;
 

@@ -55,11 +55,37 @@ struct RationalList {
   }
 };
 
+// columns whose cells are in device memory (H2MI_CELLS_DEVICE) and long host runs of 64-bit integers (H2MI_CELLS_I64), collected across
+// the columns of a phase or a keygen: ONE k_cells_scatter launch for all of them (h2mi_fr_scatter_cells_staged_dev stages the host ones in
+// the stream's scratch).  Rows and canonical values that only the device can see are refused here, from the kernel's status words: the
+// flush precedes the phase's commitments, so a refused call returns none
+struct ScatterList {
+  std::vector<h2mi_cells_source> cols;
+  uint64_t host_mask = 0;
+  void add(const DeviceVec& d, const h2mi_column_cells& c, size_t row_limit) {
+    if (cols.size() == 64) flush();
+    if (!(c.flags & H2MI_CELLS_DEVICE)) host_mask |= (uint64_t)1 << cols.size();
+    cols.push_back({d.p, c.rows, c.values, c.count, (uint32_t)row_limit, c.flags & (H2MI_CELLS_CANONICAL | H2MI_CELLS_I64)});
+  }
+  void flush() {
+    if (cols.empty()) return;
+    std::vector<h2mi_cells_source> list;
+    list.swap(cols);
+    const uint64_t mask = host_mask;
+    host_mask = 0;
+    uint64_t status[2] = {0, 0};
+    check(h2mi_fr_scatter_cells_staged_dev(list.data(), (uint32_t)list.size(), mask, status, nullptr), "scatter cells");
+    if (status[0]) throw Error(H2MI_ERANGE, "assignment reaches into the blinding rows (NotEnoughRowsAvailable)");
+    if (status[1]) throw Error(H2MI_EINVAL, "a cell value is not reduced modulo r");
+  }
+};
+
 // cells that travel in kernel arguments (h2mi_fr_patch_cells_dev: one launch per 64), collected across the columns of a phase
 struct PatchList {
   std::vector<void*> cells;
   std::vector<Fr> vals;
   RationalList rational;  // what the same columns resolve on the device
+  ScatterList scatter;    // what the same columns take from device memory, or as long runs of 64-bit integers
   void add(const DeviceVec& d, size_t row, const Fr& v) {
     cells.push_back(at(d, row));
     vals.push_back(v);
@@ -70,6 +96,7 @@ struct PatchList {
   }
   void flush() {
     rational.flush();
+    scatter.flush();
     if (!cells.empty()) check(h2mi_fr_patch_cells_dev(cells.data(), (const uint64_t*)vals.data(), cells.size(), nullptr), "patch_cells");
     cells.clear();
     vals.clear();
@@ -77,8 +104,15 @@ struct PatchList {
 };
 
 // the 32-byte value at c.values + 4 * word: cell `word` of a plain column, half `word` of a rational one (numerator 2 i, denominator 2 i + 1)
+// (a column of 64-bit integers, H2MI_CELLS_I64: cell `word` is v mod r — |v| in the low limb, the product with R^2, negated for v < 0)
 Fr cell_value(const h2mi_column_cells& c, size_t word) {
   Fr v;
+  if (c.flags & H2MI_CELLS_I64) {
+    int64_t x;
+    std::memcpy(&x, (const char*)c.values + 8 * word, 8);
+    v = fr::mul(Fr{{x < 0 ? 0 - (uint64_t)x : (uint64_t)x, 0, 0, 0}}, fr::R2);
+    return x < 0 ? fr::neg(v) : v;
+  }
   std::memcpy(v.l, c.values + 4 * word, 32);
   if (!(c.flags & H2MI_CELLS_CANONICAL)) return v;
   for (int j = 3; j >= 0; j--) {
@@ -98,14 +132,27 @@ std::vector<Fr> resolve_rational(const h2mi_column_cells& c) {
   return v;
 }
 
+// h2mi_column_cells_check, as the entry points apply it; device memory is read on the primary device's stream only
+void check_cells(const h2mi_column_cells* cells, uint32_t n_columns, unsigned where) {
+  if (const int rc = h2mi_column_cells_check(cells, n_columns, where)) throw Error(rc, "column cells");
+  for (uint32_t i = 0; i < n_columns; i++)
+    if ((cells[i].flags & H2MI_CELLS_DEVICE) && h2mi_device_count() > 1) throw Error(H2MI_EINVAL, "device cells with more than one device");
+}
+
 // a column of n rows: zero, then the assigned cells.  Short runs ride in the phase's patch launch, long dense runs are one
 // upload (canonical values converted where they land), long scattered runs are staged over their span.  Rational cells mirror that:
-// short runs are resolved here and patched, long ones (dense or scattered) join the call's one device chain.
+// short runs are resolved here and patched, long ones (dense or scattered) join the call's one device chain.  So do 64-bit integers:
+// short runs are converted here and patched, long ones join the call's one scatter launch — as every non-empty device column does.
 void fill_column(DeviceVec& d, size_t n, const h2mi_column_cells& c, size_t row_limit, PatchList& pl) {
   check(h2mi_memset_zero(d.p, n * 32), "zero");
   if (c.count == 0) return;
   if (!c.values) throw Error(H2MI_EINVAL, "column cells without values");
-  const bool rational = (c.flags & H2MI_CELLS_RATIONAL) != 0;
+  const bool rational = (c.flags & H2MI_CELLS_RATIONAL) != 0, i64 = (c.flags & H2MI_CELLS_I64) != 0;
+  if (c.flags & H2MI_CELLS_DEVICE) {  // no host shortcut: the values are not here, whatever the count.  The rows are the kernel's to check
+    if (!c.rows && c.count > row_limit) throw Error(H2MI_ERANGE, "assignment reaches into the blinding rows (NotEnoughRowsAvailable)");
+    pl.scatter.add(d, c, row_limit);
+    return;
+  }
   if (!c.rows) {
     if (c.count > row_limit) throw Error(H2MI_ERANGE, "assignment reaches into the blinding rows (NotEnoughRowsAvailable)");
     if (c.count <= 16) {
@@ -115,6 +162,10 @@ void fill_column(DeviceVec& d, size_t n, const h2mi_column_cells& c, size_t row_
     }
     if (rational) {
       pl.rational.add(d, c);
+      return;
+    }
+    if (i64) {  // 8 bytes per cell cross, and the launch that serves the call's device columns converts them
+      pl.scatter.add(d, c, row_limit);
       return;
     }
     check(h2mi_memcpy_h2d(d.p, c.values, c.count * 32), "column cells");
@@ -138,6 +189,10 @@ void fill_column(DeviceVec& d, size_t n, const h2mi_column_cells& c, size_t row_
   }
   if (rational) {
     pl.rational.add(d, c);
+    return;
+  }
+  if (i64) {  // 12 bytes per cell instead of 32 per row of the span
+    pl.scatter.add(d, c, row_limit);
     return;
   }
   std::vector<Fr> stage((size_t)hi - lo + 1, fr_zero());
@@ -1038,6 +1093,7 @@ void phase_advice(h2mi_prover_s& p, uint32_t ph, const h2mi_column_cells* advice
     inst.swap(p.pending_instances);
     p.have_pending_instances = false;
   }
+  check_cells(advice, na, H2MI_CELLS_FOR_ADVICE);
   if (ph >= phases.n_phases) throw Error(H2MI_EINVAL, "advice phase beyond the key's");
   if (ph > 0 && (was != ADVICE_PHASES || p.advice_done != ph)) throw Error(H2MI_EINVAL, "advice phases out of order");
   for (uint32_t j = 0; j < na; j++)
@@ -2074,6 +2130,7 @@ int keygen_entry(const h2mi_constraint_system* cs, std::initializer_list<const v
   if (inputs && !lookups) return H2MI_EINVAL;
   for (uint32_t l = 0; inputs && l < lookups->n_lookups && l < H2MI_MAX_LOOKUPS; l++)  // several sets are a logUp key's
     if (inputs->n_inputs[l] != 1 && !(flags & H2MI_KEYGEN_LOGUP)) return H2MI_EINVAL;
+  if (const int rc = h2mi_column_cells_check(fixed, cs->n_fixed, H2MI_CELLS_FOR_FIXED)) return rc;
   if (h2mi_device_count() == 0) return H2MI_ENODEV;  // no CPU fallback: the prover exists on a GPU or not at all
   return guarded([&] {
     std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, phases, g_lagrange_handle, fixed, copies, n_copies, flags, shuffles, inputs);
@@ -2090,6 +2147,24 @@ extern "C" {
 int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies,
                        unsigned flags, h2mi_pk_t* pk_out) {
   return keygen_entry(cs, {}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_BY_COSET, nullptr, nullptr, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
+}
+
+int h2mi_column_cells_check(const h2mi_column_cells* cells, uint32_t n_columns, unsigned where) {
+  if (where != H2MI_CELLS_FOR_ADVICE && where != H2MI_CELLS_FOR_INSTANCE && where != H2MI_CELLS_FOR_FIXED) return H2MI_EINVAL;
+  if (n_columns && !cells) return H2MI_EINVAL;
+  for (uint32_t i = 0; i < n_columns; i++) {
+    const h2mi_column_cells& c = cells[i];
+    const uint32_t f = c.flags;
+    if (f & ~(H2MI_CELLS_CANONICAL | H2MI_CELLS_RATIONAL | H2MI_CELLS_I64 | H2MI_CELLS_DEVICE)) return H2MI_EINVAL;
+    if ((f & H2MI_CELLS_I64) && (f & (H2MI_CELLS_CANONICAL | H2MI_CELLS_RATIONAL))) return H2MI_EINVAL;
+    if ((f & H2MI_CELLS_DEVICE) && ((f & H2MI_CELLS_RATIONAL) || where != H2MI_CELLS_FOR_ADVICE)) return H2MI_EINVAL;
+    if (where == H2MI_CELLS_FOR_INSTANCE && ((f & H2MI_CELLS_RATIONAL) || c.rows)) return H2MI_EINVAL;
+    if (c.count && !c.values) return H2MI_EINVAL;
+    const uintptr_t value_align = (f & H2MI_CELLS_DEVICE) && !(f & H2MI_CELLS_I64) ? 15u : 7u;
+    if (((uintptr_t)c.values & value_align) || ((uintptr_t)c.rows & 3u)) return H2MI_EINVAL;
+    if (c.count > ((size_t)1 << H2MI_MAX_LOG_N)) return H2MI_ERANGE;
+  }
+  return H2MI_OK;
 }
 
 int h2mi_gate_program_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint32_t* degree_out, uint32_t* max_stack_out) {
@@ -2305,6 +2380,7 @@ int h2mi_prover_instances(h2mi_prover_t prover, const h2mi_column_cells* instanc
   const h2mi_constraint_system& cs = p.pk->cs;
   if (cs.n_instance && !instance) return H2MI_EINVAL;
   return guarded([&] {
+    check_cells(instance, cs.n_instance, H2MI_CELLS_FOR_INSTANCE);
     std::vector<std::vector<Fr>> cols(cs.n_instance);
     for (uint32_t i = 0; i < cs.n_instance; i++) {
       const h2mi_column_cells& c = instance[i];

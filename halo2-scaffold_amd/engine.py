@@ -21,6 +21,8 @@ ADVICE, FIXED, INSTANCE = 0, 1, 2  # H2MI_COL_*
 GATES_STANDARD_PLONK, GATES_FLEX_VERTICAL, GATES_EXPRESSIONS = 1, 2, 3
 CELLS_CANONICAL = 1
 CELLS_RATIONAL = 2  # H2MI_CELLS_RATIONAL: (numerator, denominator) pairs, resolved by the library
+CELLS_I64 = 4  # H2MI_CELLS_I64: signed 64-bit integers, 8 bytes per cell (IntCells)
+CELLS_DEVICE = 8  # H2MI_CELLS_DEVICE: values and rows are device addresses (DeviceCells)
 KEYGEN_VK_ONLY = 1
 KEYGEN_BY_COSET = 8  # H2MI_KEYGEN_BY_COSET: no extended-coset columns, the quotient one coset at a time (include/h2mi_prover.h)
 KEYGEN_LOGUP = 2  # H2MI_KEYGEN_LOGUP: the key's program lookups are logUp arguments (include/h2mi_prover.h)
@@ -242,6 +244,12 @@ class ColumnCells(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("values", C.c_void_p), ("count", C.c_size_t), ("flags", C.c_uint32)]
 
 
+class CellsSource(C.Structure):
+    """h2mi_cells_source (include/h2mi.h): one column of h2mi_fr_scatter_cells_dev — device pointers, format 0 / CELLS_CANONICAL / CELLS_I64"""
+    _fields_ = [("d_column", C.c_void_p), ("rows", C.c_void_p), ("values", C.c_void_p), ("count", C.c_size_t), ("row_limit", C.c_uint32),
+                ("format", C.c_uint32)]
+
+
 class Rational:
     """Assigned::Rational(numerator, denominator) [RECALL halo2_proofs v2023_02_02 plonk/assigned.rs, restated from memory]: a cell whose
     inversion is deferred to the prover.  evaluate() is Assigned::evaluate: numerator / denominator, and 0 where the denominator is 0.
@@ -264,15 +272,158 @@ class Rational:
         return f"Rational({self.numerator}, {self.denominator})"
 
 
+class IntCells:
+    """a column whose cells are 64-bit integers (H2MI_CELLS_I64): range-check limbs, lookup advice, multiplicities, selectors,
+    fixed-point values, lookup tables.  array: a host numpy int64 array, cell i the value array[i] mod r (negative values wrap to
+    r - |v|); rows: the uint32 row of each cell, or None for rows 0 .. len - 1.  The array crosses as it is, 8 bytes per cell: no
+    Python integer is made.  Accepted wherever pack_cells takes a column: advice, fixed columns (lookup tables included), instances."""
+
+    def __init__(self, array, rows=None):
+        a = np.asarray(array)
+        if a.dtype != np.int64 or a.ndim != 1:
+            raise ValueError(f"IntCells takes a one-dimensional int64 array, not {a.dtype} of shape {a.shape}")
+        self.values = np.ascontiguousarray(a)
+        self.rows = None
+        if rows is not None:
+            r = np.asarray(rows)
+            if r.dtype != np.uint32 or r.shape != a.shape:
+                raise ValueError(f"rows: one uint32 per cell, not {r.dtype} of shape {r.shape}")
+            self.rows = np.ascontiguousarray(r)
+
+    def __len__(self):
+        return len(self.values)
+
+    def _pack(self, out: ColumnCells, keep: list) -> None:
+        out.count, out.flags = len(self.values), CELLS_I64
+        if len(self.values):
+            out.values = self.values.ctypes.data
+            if self.rows is not None:
+                out.rows = self.rows.ctypes.data
+        keep.append(self)
+
+
+def _is_tensor(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+class DeviceCells:
+    """a column whose cells are in device memory already (H2MI_CELLS_DEVICE): advice only.  fmt: "montgomery" — 32-byte Montgomery
+    words, carried verbatim; "canonical" — 32-byte integers below r; "i64" — signed 64-bit integers, the cell is v mod r.
+    values / rows: a contiguous torch tensor on the library's device (values: int64 of shape (n,) for "i64", int64 or uint64 of shape
+    (n, 4) for the 32-byte formats, limbs little-endian; rows: int32 or int64 of shape (n,) — int64 is converted once, on the device),
+    an engine.DevView or device.DevBuf, or an integer device address with `count`.  rows None: rows 0 .. count - 1.
+    The library reads the memory on its own stream during the advice call and not afterwards: a tensor's current stream is
+    synchronised when the column is packed (pack_cells — every drive / create_proof does that right in front of the call); whoever
+    hands over a bare address has ordered its producer already.  Bad rows and unreduced canonical values are found on the device and
+    raise from the advice call (H2miError -6 / -1) like their host counterparts.  Rows of one column must be distinct."""
+
+    FORMATS = {"montgomery": 0, "canonical": CELLS_CANONICAL, "i64": CELLS_I64}
+
+    def __init__(self, values, rows=None, fmt: str = "montgomery", count: int = None):
+        if fmt not in self.FORMATS:
+            raise ValueError(f"fmt must be one of {tuple(self.FORMATS)}, not {fmt!r}")
+        self.fmt, self.flags = fmt, CELLS_DEVICE | self.FORMATS[fmt]
+        self._tensors = []  # kept alive, and their streams synchronised at packing
+        width = 8 if fmt == "i64" else 32
+        if _is_tensor(values):
+            import torch
+
+            self._require_device_tensor(values, "values")
+            if fmt == "i64":
+                ok = values.dtype == torch.int64 and values.dim() == 1
+            else:
+                ok = values.dtype in (torch.int64, getattr(torch, "uint64", torch.int64)) and values.dim() == 2 and values.shape[1] == 4
+            if not ok:
+                raise ValueError(f"values for fmt={fmt!r}: int64 of shape (n,) for 'i64', int64 / uint64 of shape (n, 4) otherwise; not "
+                                 f"{values.dtype} of shape {tuple(values.shape)}")
+            if count is not None and count != values.shape[0]:
+                raise ValueError("count does not match the tensor")
+            self.count, self.values_ptr = int(values.shape[0]), int(values.data_ptr())
+            self._tensors.append(values)
+        elif hasattr(values, "ptr") and hasattr(values, "nbytes"):  # DevView / DevBuf
+            self.count = values.nbytes // width if count is None else int(count)
+            if self.count * width > values.nbytes:
+                raise ValueError("count exceeds the buffer")
+            self.values_ptr = int(values.ptr)
+            self._tensors.append(values)
+        elif isinstance(values, (int, np.integer)):
+            if count is None:
+                raise ValueError("a device address needs count")
+            self.count, self.values_ptr = int(count), int(values)
+        else:
+            raise ValueError(f"values: a torch tensor on the device, a DevView or an address with count, not {type(values).__name__}")
+        self.rows_ptr = None
+        if rows is None:
+            return
+        if _is_tensor(rows):
+            import torch
+
+            self._require_device_tensor(rows, "rows")
+            if rows.dtype not in (torch.int32, torch.int64) or rows.dim() != 1 or rows.shape[0] != self.count:
+                raise ValueError(f"rows: int32 or int64 of shape ({self.count},), not {rows.dtype} of shape {tuple(rows.shape)}")
+            if rows.dtype == torch.int64:  # once, on the device; what does not fit stays out of range, where the library refuses it
+                rows = rows.clamp(min=-1, max=0x7FFFFFFF).to(torch.int32)
+            self.rows_ptr = int(rows.data_ptr())
+            self._tensors.append(rows)
+        elif hasattr(rows, "ptr") and hasattr(rows, "nbytes"):
+            if self.count * 4 > rows.nbytes:
+                raise ValueError("fewer rows than cells")
+            self.rows_ptr = int(rows.ptr)
+            self._tensors.append(rows)
+        elif isinstance(rows, (int, np.integer)):
+            self.rows_ptr = int(rows)
+        else:
+            raise ValueError(f"rows: a torch tensor on the device, a DevView or an address, not {type(rows).__name__}")
+
+    @staticmethod
+    def _require_device_tensor(t, what: str) -> None:
+        if not t.is_cuda:
+            raise ValueError(f"{what}: a CPU tensor (DeviceCells takes device memory; a host array goes as IntCells or as a list)")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: the tensor is not contiguous")
+        primary = lib.h2mi_primary_device()
+        if primary >= 0 and t.device.index != primary:
+            raise ValueError(f"{what}: the tensor is on device {t.device.index}, the library on device {primary}")
+
+    def __len__(self):
+        return self.count
+
+    def _pack(self, out: ColumnCells, keep: list) -> None:
+        for t in self._tensors:
+            if _is_tensor(t):
+                import torch
+
+                torch.cuda.current_stream(t.device).synchronize()  # the producer is done before the library's stream reads
+        out.count, out.flags = self.count, self.flags
+        if self.count:
+            out.values = self.values_ptr
+            if self.rows_ptr is not None:
+                out.rows = self.rows_ptr
+        keep.append(self)
+
+
+CELLS_FOR_ADVICE, CELLS_FOR_INSTANCE, CELLS_FOR_FIXED = 0, 1, 2  # h2mi_column_cells_check's `where`
+
+
+def cells_check(cells, n_columns: int, where: int) -> None:
+    """h2mi_column_cells_check (host only, reads no cell memory): H2miError for what the entry point named by `where` would refuse
+    at first sight — flag combinations, null and misaligned pointers, counts"""
+    check(lib.h2mi_column_cells_check(cells, n_columns, where), "column_cells_check")
+
+
 def pack_cells(columns):
     """[{row: value} or [value at row 0, 1, ..]] (integers below r, or Rational) -> (h2mi_column_cells array, objects to keep alive).
     The values cross as canonical 32-byte integers (H2MI_CELLS_CANONICAL): one C-level conversion per value and one join here, the
     Montgomery conversion where they land (long runs: on the device).  A column with at least one Rational crosses as (numerator,
     denominator) pairs (H2MI_CELLS_CANONICAL | H2MI_CELLS_RATIONAL), its integers as (x, 1), and the library resolves it; a column
-    with none crosses exactly as it always has."""
+    with none crosses exactly as it always has.  A column may also be an IntCells (a host int64 array, H2MI_CELLS_I64) or a
+    DeviceCells (device memory, H2MI_CELLS_DEVICE): neither is touched cell by cell here."""
     arr = (ColumnCells * max(len(columns), 1))()
     keep = []
     for i, cells in enumerate(columns):
+        if isinstance(cells, (IntCells, DeviceCells)):
+            cells._pack(arr[i], keep)
+            continue
         if isinstance(cells, dict):
             rows = sorted(cells)
             dense = bool(rows) and rows[0] == 0 and rows[-1] == len(rows) - 1
@@ -366,7 +517,7 @@ class _Views:
 
 class Keys:
     """h2mi_prover_keygen (h2mi_prover_keygen_gates when `gates` is given, h2mi_prover_keygen_exprs when `lookups` is too): keygen_vk + keygen_pk for a constraint system given as data.  fixed: one {row: value} dict (or dense
-    list) per fixed column as synthesize() assigns them; copies: [(left column, left row, right column, right row)] per
+    list, or an IntCells for a column of small integers such as a selector or a lookup table) per fixed column as synthesize() assigns them; copies: [(left column, left row, right column, right row)] per
     constrain_equal in call order, columns as indices into the permutation argument.  `params` is the WHOLE SRS."""
 
     def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False, gates: GateProgram = None,
@@ -546,7 +697,8 @@ class Prover:
 
     def drive(self, advice, instance, seed: int, transcript: Blake2bWrite, trace: dict = None, witness_check: str = None,
               multiopen: str = "shplonk"):
-        """create_proof between the transcript's challenges.  advice: one {row: value} dict or dense list per advice column;
+        """create_proof between the transcript's challenges.  advice: one {row: value} dict or dense list per advice column, or an
+        IntCells (a host int64 array) or a DeviceCells (device memory: a torch tensor, a DevView, an address) in its place;
         instance: the public inputs — a flat list of integers (one instance column), or a list of columns, each a list of integers (any
         number of instance columns; engine.instance_values gives the order in which the caller hashes them).  The caller has hashed
         vk.transcript_repr and the public inputs already.
@@ -775,4 +927,4 @@ class Batch:
                     check(lib.h2mi_prover_get_counts(p.handle, C.byref(p.counts)), "prover counts")
 
 
-__all__ = ["ConstraintSystem", "Keys", "Prover", "Batch", "DevView", "H2miError", "ShuffleProgram"]
+__all__ = ["ConstraintSystem", "Keys", "Prover", "Batch", "DevView", "H2miError", "ShuffleProgram", "IntCells", "DeviceCells"]

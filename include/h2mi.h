@@ -60,6 +60,8 @@ int h2mi_init(int device);
  * the sharding, scalar distribution and fold.  Mutually exclusive with h2mi_init. */
 int h2mi_init_devices(int n_devices);
 int h2mi_device_count(void); /* devices this process drives (0 before init) */
+int h2mi_primary_device(void); /* the ordinal of the device every d_* pointer lives on (-1 before init): what a host compares a foreign
+                                  allocation's device with before it hands the pointer over (H2MI_CELLS_DEVICE, h2mi_prover.h) */
 void h2mi_shutdown(void);
 const char* h2mi_strerror(int code);
 const char* h2mi_version(void);
@@ -310,6 +312,30 @@ typedef struct {
   size_t count;
 } h2mi_assigned_cells;
 int h2mi_fr_assigned_columns_dev(const h2mi_assigned_cells* cols, uint32_t n_cols, int canonical, uint64_t* invalid_out, h2mi_stream_t stream);
+/* Witness cells that are in DEVICE memory already, written into up to 64 columns by ONE launch (k_cells_scatter; what h2mi_column_cells
+ * with H2MI_CELLS_DEVICE, or a long host run with H2MI_CELLS_I64, becomes: h2mi_prover.h).  Cell i of a source lands at d_column + 32 rows[i]
+ * (or + 32 i when rows is NULL), converted where `format` asks: 0 — 32-byte Montgomery words, carried verbatim (not range-checked);
+ * H2MI_CELLS_CANONICAL (1) — 32-byte canonical integers, times R^2 as h2mi_fe_from_repr_dev does; H2MI_CELLS_I64 (4) — signed 64-bit
+ * integers v, the cell is v mod r (|v| in the low limb, the same product, negated when v < 0).  Work is partitioned over the total cell
+ * count, not per column; rows of a destination that no cell names are left untouched.  status_out[0] counts the cells whose row is at or
+ * beyond row_limit: they are skipped, so nothing is written outside a column's first row_limit rows whatever `rows` holds.
+ * status_out[1] counts the canonical values not below r: they are written as zero.  status_out is required and the call waits for the
+ * stream to deliver it.  Rows of one source must be distinct: cells that name the same row are written in no order.  Pointers: d_column
+ * and 32-byte values 16-byte aligned, I64 values 8, rows 4; a source with count == 0 is skipped and none of its pointers is looked at.
+ * H2MI_EINVAL: a null or misaligned pointer, an unknown format, n_cols > 64; H2MI_ERANGE: more than 2^32 cells in one call. */
+typedef struct {
+  void* d_column;        /* 32-byte elements */
+  const uint32_t* rows;  /* device; NULL = rows 0 .. count-1 */
+  const void* values;    /* device */
+  size_t count;
+  uint32_t row_limit;    /* rows at or beyond it are counted, not written */
+  uint32_t format;       /* 0, H2MI_CELLS_CANONICAL or H2MI_CELLS_I64 */
+} h2mi_cells_source;
+int h2mi_fr_scatter_cells_dev(const h2mi_cells_source* cols, uint32_t n_cols, uint64_t status_out[2], h2mi_stream_t stream);
+/* The same with some sources in HOST memory: bit i of host_mask says that cols[i].values and cols[i].rows are host pointers.  They are
+ * staged behind one another in the stream's grow-only scratch (8 or 32 bytes per cell, plus 4 per listed row), which keeps that size
+ * afterwards: H2MI_ENOMEM where it does not fit.  The host buffers are free when the call returns.  Still one launch. */
+int h2mi_fr_scatter_cells_staged_dev(const h2mi_cells_source* cols, uint32_t n_cols, uint64_t host_mask, uint64_t status_out[2], h2mi_stream_t stream);
 /* out[i] = value for i < n (Lagrange vectors such as l_active of keygen_pk) */
 int h2mi_fr_fill_dev(void* d_out, size_t n, const uint64_t value[4], h2mi_stream_t stream);
 /* Seeded stand-in for the prover's sweeps of `Scalar::random(rng)` (blinding rows; the vanishing argument's random

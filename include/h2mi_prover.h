@@ -136,12 +136,47 @@ typedef struct {
  * rational columns of the call in one slice of the library's grow-only scratch (three columns at k = 20: 192 MB): where that does not
  * fit the call is H2MI_ENOMEM although the resolved columns would. */
 #define H2MI_CELLS_RATIONAL 2u
+/* H2MI_CELLS_I64: values holds `count` signed 64-bit two's-complement integers, 8 bytes per cell (read through the pointer as int64_t;
+ * 8-byte aligned), for the columns whose cells are small: range-check limbs, lookup advice, multiplicities, selectors, fixed-point
+ * values, lookup tables.  The cell's value is v mod r: v for v >= 0, r - |v| for v < 0, -2^63 |-> r - 2^63.  rows means what it means
+ * without the flag.  With H2MI_CELLS_CANONICAL or H2MI_CELLS_RATIONAL: H2MI_EINVAL.  Accepted wherever cells enter: every
+ * h2mi_prover_keygen* (the fixed column behind a cs->lookups[] table included), h2mi_prover_instances, h2mi_prover_advice,
+ * h2mi_prover_advice_phase, hence batches.  Short runs (rows NULL: up to 16 cells; a row list: up to 4096) are converted on the host and
+ * ride in the phase's patch launch like plain cells; longer ones are staged as they are — 8 bytes per cell plus 4 per listed row, where
+ * plain scattered cells upload 32 bytes per row of their span — in the library's grow-only scratch (H2MI_ENOMEM where that does not
+ * fit, as for the rational chain) and converted by the ONE launch that also serves the call's device columns (k_cells_scatter,
+ * h2mi_fr_scatter_cells_dev).  Everything downstream sees the column byte for byte as the same values uploaded as field elements give. */
+#define H2MI_CELLS_I64 4u
+/* H2MI_CELLS_DEVICE: values, and rows when not NULL, are DEVICE addresses — any pointer the library's device can read: h2mi_malloc, a
+ * torch tensor's data_ptr().  For callers whose witness is in HBM already.  Alone (32-byte Montgomery words, not range-checked, as on
+ * the host), with H2MI_CELLS_CANONICAL or with H2MI_CELLS_I64; with H2MI_CELLS_RATIONAL: H2MI_EINVAL.  Accepted by h2mi_prover_advice and
+ * h2mi_prover_advice_phase (hence batch members) only: h2mi_prover_instances (the caller hashes public inputs on the host and the library
+ * keeps a host copy) and every h2mi_prover_keygen* (a key is made once, and a lookup table is sorted on the host) return H2MI_EINVAL, and
+ * so does every entry after h2mi_init_devices with more than one device.  Pointers: 32-byte values 16-byte aligned, I64 values 8, rows 4
+ * (H2MI_EINVAL).  The library reads the memory on its own stream: the caller has ordered its producer before the call, by a host
+ * synchronise or by a wait placed on h2mi_library_stream.  The memory is free again when the call returns.  There is no host shortcut,
+ * whatever the count: all non-empty device columns of a call, and its long I64 runs, are written by one k_cells_scatter launch.  What
+ * the host routes find on the host is found on the device here and still returned by the same call, with no commitment and the proof
+ * abandoned, the prover usable: H2MI_ERANGE for a listed row at or beyond 2^k - blinding_factors - 1 (a dense run longer than that is
+ * refused before any launch), H2MI_EINVAL for a canonical value not below r.  Nothing is written outside the column's usable rows
+ * whatever rows holds.  Each row once: cells that name the same row are written in no order, as on the rational chain. */
+#define H2MI_CELLS_DEVICE 8u
 typedef struct {
   const uint32_t* rows;
   const uint64_t* values;
   size_t count;
   uint32_t flags;
 } h2mi_column_cells;
+/* The rules above, on the host alone (it works without a GPU and reads no cell memory): what every entry point that takes cells applies
+ * first.  `where` says which: H2MI_CELLS_FOR_ADVICE (h2mi_prover_advice / _advice_phase), _FOR_INSTANCE (h2mi_prover_instances),
+ * _FOR_FIXED (every h2mi_prover_keygen*).  H2MI_EINVAL: cells NULL with n_columns > 0; an unknown `where`; a flag bit beyond the four
+ * above; H2MI_CELLS_I64 with _CANONICAL or _RATIONAL; H2MI_CELLS_DEVICE with _RATIONAL or anywhere but on advice; for instances
+ * H2MI_CELLS_RATIONAL or a row list; count > 0 with values NULL; a misaligned pointer — rows 4 bytes, values 8, the 32-byte values of a
+ * device column 16.  H2MI_ERANGE: a count above 2^28, more rows than any column has (the usable rows are the entry points' to check). */
+#define H2MI_CELLS_FOR_ADVICE 0u
+#define H2MI_CELLS_FOR_INSTANCE 1u
+#define H2MI_CELLS_FOR_FIXED 2u
+int h2mi_column_cells_check(const h2mi_column_cells* cells, uint32_t n_columns, unsigned where);
 
 typedef struct h2mi_pk_s* h2mi_pk_t;         /* keygen_pk's ProvingKey, resident in HBM */
 typedef struct h2mi_prover_s* h2mi_prover_t; /* the buffers, streams and phase state of one create_proof at a time; reused from proof to proof */
