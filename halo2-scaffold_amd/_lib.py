@@ -86,6 +86,8 @@ def _load():
         # witness cells from device memory / as 64-bit integers: one k_cells_scatter launch for up to 64 columns
         "h2mi_fr_scatter_cells_dev": ([vp, C.c_uint32, u64p, vp], C.c_int),
         "h2mi_fr_scatter_cells_staged_dev": ([vp, C.c_uint32, C.c_uint64, u64p, vp], C.c_int),
+        # the inverse: device columns -> their nonzero cells in row order (count, prefix, ordered scatter; no atomic)
+        "h2mi_fr_compact_cells_dev": ([vp, C.c_uint32, C.c_uint, vp, vp, vp], C.c_int),
         "h2mi_fr_random_dev": ([vp, sz, C.c_uint64, C.c_uint64, vp], C.c_int),
         "h2mi_fr_random_chacha_dev": ([vp, sz, vp, C.c_uint64, C.c_uint64, vp], C.c_int),
         "h2mi_ntt_bn254_fr": ([vp, vp, C.c_uint32], C.c_int),
@@ -171,6 +173,10 @@ def _load():
         "h2mi_logup_inputs_check": ([vp, vp, vp, vp, C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_prover_keygen_logup": ([vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_prover_pk_release": ([vp], C.c_int),
+        # proving-key files: one self-describing blob out of HBM and back
+        "h2mi_prover_pk_export": ([vp, vp, sz, vp, sz, C.POINTER(sz)], C.c_int),
+        "h2mi_prover_pk_import": ([vp, sz, C.c_uint64, C.c_uint, C.POINTER(vp)], C.c_int),
+        "h2mi_prover_pk_blob_check": ([vp, sz, vp, C.POINTER(vp), C.POINTER(sz)], C.c_int),
         "h2mi_prover_vk_commitments": ([vp, vp, vp], C.c_int),
         "h2mi_prover_create": ([vp, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(vp)], C.c_int),
         "h2mi_prover_destroy": ([vp], C.c_int),

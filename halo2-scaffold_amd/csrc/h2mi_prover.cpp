@@ -21,6 +21,7 @@
 #include "../../include/h2mi_prover.h"
 #include "h2mi_expr.hpp"
 #include "h2mi_hostmath.hpp"
+#include "h2mi_keyfile.hpp"
 
 namespace {
 
@@ -455,6 +456,8 @@ struct h2mi_pk_s {
   std::vector<h2mi_expr_op> shuffle_ops;
   std::vector<uint64_t> shuffle_constants;
   ArgumentSlices shuffle_slices;
+  // the pair counts of both programs as the caller stated them: what h2mi_prover_pk_export writes beside the ops
+  uint32_t lookup_pairs[H2MI_MAX_LOOKUPS] = {0}, shuffle_pairs[H2MI_MAX_SHUFFLES] = {0};
   // advice phases and challenges (h2mi_prover_keygen_phases); every other keygen: one phase, no challenges
   h2mi_advice_phases phases;
   uint32_t phase_columns[H2MI_MAX_ADVICE_PHASES] = {0, 0, 0};
@@ -530,9 +533,17 @@ h2mi_gate_program own_program(const h2mi_gate_program& g, std::vector<h2mi_expr_
   return {ops.data(), g.n_ops, constants.data(), g.n_constants};
 }
 
+// One body, two front ends.  keygen proper (h2mi_prover_keygen*): the caller's fixed cells and its copy constraints, from which the
+// permutation is assembled.  Import (h2mi_prover_pk_import): the cells of a key file, handed over in the same h2mi_column_cells, and
+// `stored_moved` — the moved cells a key once assembled, {column, row, image column, image row} ascending — in place of the assembly.
+// From the moved cells on both run the same code: sigma columns, active rows, commitments, transforms, tables.  Import also hands over
+// the blob's `stored_commitments` (n_fixed + n_perm points of 64 bytes): they are compared as soon as the key's own exist, before any
+// transform is issued or any coefficient or coset vector allocated, so a blob that is refused there has cost the columns and two batches
+// of MSMs.
 std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                                   const h2mi_advice_phases* phases, uint64_t g_lagrange, const h2mi_column_cells* fixed, const uint32_t* copies,
-                                  size_t n_copies, unsigned flags, const h2mi_shuffle_program* shuffles = nullptr, const h2mi_logup_inputs* inputs = nullptr) {
+                                  size_t n_copies, unsigned flags, const h2mi_shuffle_program* shuffles = nullptr, const h2mi_logup_inputs* inputs = nullptr,
+                                  const std::vector<std::array<uint32_t, 4>>* stored_moved = nullptr, const uint8_t* stored_commitments = nullptr) {
   validate(cs, gates, lookups, phases, shuffles, inputs);
   std::unique_ptr<h2mi_pk_s> pkp(new h2mi_pk_s(cs));
   h2mi_pk_s& pk = *pkp;
@@ -544,6 +555,7 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
   if (lookups) {
     pk.lookup_exprs = true;
     h2mi_lookup_program own = *lookups;
+    std::memcpy(pk.lookup_pairs, lookups->n_pairs, sizeof(pk.lookup_pairs));
     own.exprs = own_program(lookups->exprs, pk.lookup_ops, pk.lookup_constants);
     // an h2mi_logup_inputs is copied into the slices (their `sets`): the key reads the caller's struct here and never again
     if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices, pk.phases.n_challenges, inputs)) throw Error(H2MI_EINVAL, "lookup program");
@@ -551,6 +563,7 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
   if (shuffles) {
     pk.n_shuffles = shuffles->n_shuffles;
     h2mi_shuffle_program own = *shuffles;
+    std::memcpy(pk.shuffle_pairs, shuffles->n_pairs, sizeof(pk.shuffle_pairs));
     own.exprs = own_program(shuffles->exprs, pk.shuffle_ops, pk.shuffle_constants);
     if (check_shuffle_program(cs, &own, nullptr, &pk.shuffle_slices, pk.phases.n_challenges)) throw Error(H2MI_EINVAL, "shuffle program");
   }
@@ -605,12 +618,18 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     }
     std::vector<uint32_t> pos;
     std::vector<std::array<uint32_t, 4>> moved;
-    asm_.for_each([&](const Cell& from, const Cell& to) {
-      if (from == to) return;
-      pl.add(*pk.sigma_values[from.first], from.second, fr::mul(dpow[to.first], fr::pow_u64(dom.get_omega(), to.second)));
-      if (from.second < u) pos.push_back((from.first / pk.chunk) * u + from.second);
-      if (!pk.vk_only) moved.push_back({from.first, from.second, to.first, to.second});
-    });
+    auto place = [&](uint32_t from_col, uint32_t from_row, uint32_t to_col, uint32_t to_row) {  // one moved cell, whichever front end names it
+      pl.add(*pk.sigma_values[from_col], from_row, fr::mul(dpow[to_col], fr::pow_u64(dom.get_omega(), to_row)));
+      if (from_row < u) pos.push_back((from_col / pk.chunk) * u + from_row);
+      if (!pk.vk_only) moved.push_back({from_col, from_row, to_col, to_row});
+    };
+    if (stored_moved) {
+      for (const std::array<uint32_t, 4>& mv : *stored_moved) place(mv[0], mv[1], mv[2], mv[3]);  // the parser has bounded every column and row
+    } else {
+      asm_.for_each([&](const Cell& from, const Cell& to) {
+        if (!(from == to)) place(from.first, from.second, to.first, to.second);
+      });
+    }
     pl.flush();
     if (!moved.empty()) {  // what h2mi_prover_check compares: 16 bytes per moved cell, uploaded once
       std::sort(moved.begin(), moved.end());
@@ -628,6 +647,14 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
   }
   pk.fixed_commitments = commit_points(g_lagrange, pk.fixed_values, n);
   pk.permutation_commitments = commit_points(g_lagrange, pk.sigma_values, n);
+  if (stored_commitments) {  // a damaged cell section, or an SRS that is not the one the key was made against
+    const bool same = (cs.n_fixed == 0 || !std::memcmp(pk.fixed_commitments.data(), stored_commitments, 64 * (size_t)cs.n_fixed)) &&
+                      (m == 0 || !std::memcmp(pk.permutation_commitments.data(), stored_commitments + 64 * (size_t)cs.n_fixed, 64 * (size_t)m));
+    if (!same) {
+      h2mi_sync();  // nothing queued may still read the vectors released with the key
+      throw Error(H2MI_EINVAL, "key file: the commitments recomputed from its cells are not the stored ones");
+    }
+  }
   if (pk.vk_only) return pkp;
   for (auto& col : pk.fixed_values) {
     Dev p = vec(n), e = pk.by_coset ? nullptr : vec(pk.ext);
@@ -2140,9 +2167,200 @@ int keygen_entry(const h2mi_constraint_system* cs, std::initializer_list<const v
   });
 }
 
+// ---- proving-key files (h2mi_keyfile.hpp holds the format; DESIGN.md 3 describes it) ---------------------------------------------------
+// a parsed blob's programs in the structs the keygen entries take; the pointers are NULL where the key has none
+struct BlobPrograms {
+  h2mi_gate_program gates_;
+  h2mi_lookup_program lookups_;
+  h2mi_shuffle_program shuffles_;
+  h2mi_logup_inputs inputs_;
+  const h2mi_gate_program* gates = nullptr;
+  const h2mi_lookup_program* lookups = nullptr;
+  const h2mi_shuffle_program* shuffles = nullptr;
+  const h2mi_logup_inputs* inputs = nullptr;
+  const h2mi_advice_phases* phases = nullptr;
+  explicit BlobPrograms(const keyfile::Blob& b) {
+    if (b.has_gates) {
+      gates_ = b.gates.view();
+      gates = &gates_;
+    }
+    if (b.has_lookups) {
+      std::memset(&lookups_, 0, sizeof(lookups_));
+      lookups_.n_lookups = b.n_lookups;
+      std::memcpy(lookups_.n_pairs, b.lookup_pairs, sizeof(lookups_.n_pairs));
+      lookups_.exprs = b.lookup_exprs.view();
+      std::memcpy(inputs_.n_inputs, b.lookup_inputs, sizeof(inputs_.n_inputs));
+      lookups = &lookups_;
+      inputs = &inputs_;
+    }
+    if (b.has_shuffles) {
+      std::memset(&shuffles_, 0, sizeof(shuffles_));
+      shuffles_.n_shuffles = b.n_shuffles;
+      std::memcpy(shuffles_.n_pairs, b.shuffle_pairs, sizeof(shuffles_.n_pairs));
+      shuffles_.exprs = b.shuffle_exprs.view();
+      shuffles = &shuffles_;
+    }
+    if (b.has_phases) phases = &b.phases;
+  }
+};
+
+// everything import checks before it touches the device: the format's own rules, then the constraint system's and its programs'
+void check_blob(const uint8_t* blob, size_t len, keyfile::Blob& b) {
+  if (keyfile::parse(blob, len, b)) throw Error(H2MI_EINVAL, "key file: not a well-formed proving-key blob");
+  const BlobPrograms p(b);
+  validate(b.cs, p.gates, p.lookups, p.phases, p.shuffles, p.inputs);
+}
+
+void* arena_alloc(void* ctx, size_t bytes) {
+  std::vector<uint64_t>* v = (std::vector<uint64_t>*)ctx;
+  v->assign((bytes + 7) / 8, 0);
+  return v->data();
+}
+
+// the key as one blob; with_cells == false: the same sections with zeros where the cells would be, for the length alone (the counts
+// take the first two launches of the compaction, not the third)
+void export_key(h2mi_pk_s& pk, const uint8_t* user, size_t user_len, bool with_cells, std::vector<uint8_t>& out) {
+  const h2mi_constraint_system& cs = pk.cs;
+  std::vector<h2mi_cells_compacted> cols(cs.n_fixed);
+  for (uint32_t f = 0; f < cs.n_fixed; f++) {
+    std::memset(&cols[f], 0, sizeof(cols[f]));
+    cols[f].d_column = pk.fixed_values[f]->p;  // the primary device's, in every multi-device mode
+    cols[f].row_limit = pk.u;
+  }
+  std::vector<uint64_t> arena;
+  check(h2mi_fr_compact_cells_dev(cols.data(), cs.n_fixed, 0, with_cells ? arena_alloc : nullptr, &arena, nullptr), "compact cells");
+  keyfile::Writer w;
+  w.header(pk.logup ? keyfile::FLAG_LOGUP : 0);
+  w.constraint_system(cs, pk.lookup_exprs);
+  w.begin();
+  if (cs.gates == H2MI_GATES_EXPRESSIONS) w.program(pk.gate_program);
+  w.end();
+  w.begin();
+  if (pk.lookup_exprs) {
+    w.u32(cs.n_lookups);
+    for (uint32_t l = 0; l < cs.n_lookups; l++) w.u32(pk.lookup_pairs[l]);
+    for (uint32_t l = 0; l < cs.n_lookups; l++) w.u32(pk.lookup_slices.sets[l]);
+    w.program({pk.lookup_ops.data(), (uint32_t)pk.lookup_ops.size(), pk.lookup_constants.data(), (uint32_t)(pk.lookup_constants.size() / 4)});
+  }
+  w.end();
+  w.begin();
+  if (pk.n_shuffles) {
+    w.u32(pk.n_shuffles);
+    for (uint32_t i = 0; i < pk.n_shuffles; i++) w.u32(pk.shuffle_pairs[i]);
+    w.program({pk.shuffle_ops.data(), (uint32_t)pk.shuffle_ops.size(), pk.shuffle_constants.data(), (uint32_t)(pk.shuffle_constants.size() / 4)});
+  }
+  w.end();
+  w.begin();
+  if (pk.phases.n_phases > 1 || pk.phases.n_challenges) {
+    w.u32(pk.phases.n_phases);
+    w.u32(pk.phases.n_challenges);
+    for (uint32_t j = 0; j < cs.n_advice; j++) w.u32(pk.phases.advice_phase[j]);
+    for (uint32_t i = 0; i < pk.phases.n_challenges; i++) w.u32(pk.phases.challenge_phase[i]);
+  }
+  w.end();
+  for (uint32_t f = 0; f < cs.n_fixed; f++) {
+    const h2mi_cells_compacted& c = cols[f];
+    const uint32_t layout = keyfile::layout_of(c.count, c.last, c.width);
+    if (with_cells) {
+      if (layout != c.layout) throw Error(H2MI_EINVAL, "key file: the compaction's layout is not the format's");
+      w.column(layout, c.width, c.count, c.last, c.values, c.rows);
+    } else {
+      w.begin();
+      w.u32(layout); w.u32(layout ? c.width : 0); w.u32((uint32_t)c.count); w.u32(c.last);
+      w.b.resize(w.b.size() + (layout == keyfile::LAYOUT_DENSE ? (size_t)c.last * c.width : (size_t)c.count * (c.width + 4)), 0);
+      w.end();
+    }
+  }
+  w.begin();
+  w.bytes(pk.moved_cells.data(), pk.moved_cells.size() * 4);
+  w.end();
+  w.begin();
+  w.bytes(pk.fixed_commitments.data(), pk.fixed_commitments.size() * 64);
+  w.bytes(pk.permutation_commitments.data(), pk.permutation_commitments.size() * 64);
+  w.end();
+  w.begin();
+  w.bytes(user, user_len);
+  w.end();
+  w.finish();
+  out.swap(w.b);
+}
+
+std::unique_ptr<h2mi_pk_s> import_key(const uint8_t* blob, size_t len, uint64_t g_lagrange, unsigned flags) {
+  keyfile::Blob b;
+  check_blob(blob, len, b);
+  if (h2mi_device_count() == 0) throw Error(H2MI_ENODEV, "no device");
+  const BlobPrograms p(b);
+  const h2mi_constraint_system& cs = b.cs;
+  // the blob's own cells as the caller's would arrive: dense runs without a row list, sparse ones with theirs, as 64-bit integers or
+  // as canonical words — fill_column / k_cells_scatter from here on, and build_table reads them on the host
+  std::vector<h2mi_column_cells> fixed(cs.n_fixed);
+  for (uint32_t f = 0; f < cs.n_fixed; f++) {
+    const keyfile::Column& c = b.fixed[f];
+    h2mi_column_cells& out = fixed[f];
+    out = {nullptr, nullptr, 0, 0};
+    if (c.layout == keyfile::LAYOUT_EMPTY) continue;
+    out.values = (const uint64_t*)(blob + c.values_at);
+    out.flags = c.width == 8 ? H2MI_CELLS_I64 : H2MI_CELLS_CANONICAL;
+    out.count = c.layout == keyfile::LAYOUT_DENSE ? c.last : c.count;
+    if (c.layout == keyfile::LAYOUT_SPARSE) out.rows = (const uint32_t*)(blob + c.rows_at);
+  }
+  check_cells(fixed.data(), cs.n_fixed, H2MI_CELLS_FOR_FIXED);
+  std::vector<std::array<uint32_t, 4>> moved(b.n_moved);
+  if (b.n_moved) std::memcpy(moved.data(), blob + b.moved_at, 16 * b.n_moved);
+  // keygen compares the commitments it recomputes with the stored ones and throws H2MI_EINVAL where they differ
+  return keygen(cs, p.gates, p.lookups, p.phases, g_lagrange, fixed.data(), nullptr, 0, flags | (b.logup ? H2MI_KEYGEN_LOGUP : 0u), p.shuffles, p.inputs, &moved,
+                blob + b.commitments_at);
+}
+
 }  // namespace
 
 extern "C" {
+
+int h2mi_prover_pk_export(h2mi_pk_t pk, const void* user, size_t user_len, void* buf, size_t cap, size_t* len_out) {
+  if (!len_out || (user_len && !user) || user_len > keyfile::MAX_USER_BYTES) return H2MI_EINVAL;
+  *len_out = 0;
+  if (!alive(g_live_pks, pk)) return H2MI_EHANDLE;
+  if (pk->vk_only) return H2MI_EINVAL;  // it holds no moved cells: not a key anything could prove with
+  int range = H2MI_OK;
+  const int rc = guarded([&] {
+    std::vector<uint8_t> blob;
+    export_key(*pk, (const uint8_t*)user, user_len, buf != nullptr, blob);
+    *len_out = blob.size();
+    if (!buf) return;
+    if (blob.size() > cap) range = H2MI_ERANGE;
+    else std::memcpy(buf, blob.data(), blob.size());
+  });
+  return rc ? rc : range;
+}
+
+int h2mi_prover_pk_blob_check(const void* buf, size_t len, h2mi_constraint_system* cs_out, const void** user_out, size_t* user_len_out) {
+  if (!buf) return H2MI_EINVAL;
+  return guarded([&] {
+    keyfile::Blob b;
+    check_blob((const uint8_t*)buf, len, b);
+    if (cs_out) *cs_out = b.cs;
+    if (user_out) *user_out = (const uint8_t*)buf + b.user_at;
+    if (user_len_out) *user_len_out = b.user_len;
+  });
+}
+
+int h2mi_prover_pk_import(const void* buf, size_t len, uint64_t g_lagrange_handle, unsigned flags, h2mi_pk_t* pk_out) {
+  if (!buf || !pk_out || (flags & ~H2MI_KEYGEN_BY_COSET)) return H2MI_EINVAL;
+  *pk_out = nullptr;
+  return guarded([&] {
+    std::vector<uint64_t> aligned;  // the cell sections are read through uint64_t / uint32_t pointers
+    const uint8_t* blob = (const uint8_t*)buf;
+    if ((uintptr_t)buf & 7u) {
+      aligned.resize((len + 7) / 8);
+      std::memcpy(aligned.data(), buf, len);
+      blob = (const uint8_t*)aligned.data();
+    }
+    std::unique_ptr<h2mi_pk_s> pk = import_key(blob, len, g_lagrange_handle, flags);
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    g_live_pks.insert(pk.get());
+    *pk_out = pk.release();
+  });
+}
 
 int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies,
                        unsigned flags, h2mi_pk_t* pk_out) {

@@ -606,6 +606,11 @@ class Keys:
         self.keys = engine.Keys(cs.abi(k), params, list(asg.fixed), copies, gates=cs.gate_program(), lookups=cs.lookup_program(),
                                 phases=cs.phases(), shuffles=cs.shuffle_program(), logup=logup, logup_inputs=cs.logup_inputs() if logup else None,
                                 by_coset=by_coset)
+        self._finish()
+
+    def _finish(self):
+        """what the key shows of its engine.Keys, however that was made"""
+        cs, k = self.cs, self.params.k
         self.fixed_commitments, self.permutation_commitments = self.keys.fixed_commitments, self.keys.permutation_commitments
         nf, m = cs.n_fixed, len(cs.perm_columns)
         self.fixed_values, self.fixed_polys, self.fixed_cosets = (self.keys.views(kd, nf) for kd in (engine.PKBUF_FIXED, engine.PKBUF_FIXED_POLY, engine.PKBUF_FIXED_COSET))
@@ -617,6 +622,32 @@ class Keys:
 
     def release(self):
         self.keys.release()
+
+    def save(self, path_or_file, user: bytes = b"") -> int:
+        """the key as a file (engine.Keys.save: h2mi_prover_pk_export) -> the bytes written"""
+        return self.keys.save(path_or_file, user)
+
+    @classmethod
+    def load(cls, params: ParamsKZG, cs: ConstraintSystem, path_or_file, by_coset: bool = False) -> "Keys":
+        """the key of a file against the constraint system of the caller's own configure() — the crate's `ProvingKey::read::<_, C>`
+        re-runs configure as well — without the circuit's synthesis.  ValueError when the file's constraint system, one of its
+        programs or its advice phases is not what `cs` gives at params.k: such a key would prove another circuit.  logup is the file's."""
+        blob = path_or_file.read() if hasattr(path_or_file, "read") else open(path_or_file, "rb").read()
+        engine.blob_check(blob)
+        logup = bool(blob[12] & 1)
+        want = engine.key_blob_head(cs.abi(params.k), cs.gate_program(), cs.lookup_program(), cs.logup_inputs(), cs.shuffle_program(), cs.phases())
+        for name, got, exp in zip(("constraint system", "gate program", "lookup program", "shuffle program", "advice phases"),
+                                  engine.blob_sections(blob, 5), want):
+            if got != exp:
+                raise ValueError(f"key file: its {name} is not the one this constraint system gives")
+        self = cls.__new__(cls)
+        self.cs, self.logup, self.by_coset, self.params = cs, logup, bool(by_coset), params
+        self.domain = d = EvaluationDomain(cs.degree(), params.k)
+        self.u = d.n - (cs.blinding_factors() + 1)
+        self.keys = engine.Keys.from_blob(params, blob, by_coset)
+        self.user = self.keys.user
+        self._finish()
+        return self
 
 
 Workspace = flex.FlexWorkspace  # one library prover kept from proof to proof: nothing in it depends on the gate shape

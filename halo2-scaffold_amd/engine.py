@@ -571,6 +571,120 @@ class Keys:
             check(lib.h2mi_prover_pk_release(self.handle), "pk_release")
             self.handle = None
 
+    # ---- key files: h2mi_prover_pk_export / _import (include/h2mi_prover.h; the format is DESIGN.md 3) ----
+    def export(self, user: bytes = b"") -> bytes:
+        """the key as one blob: the fixed columns' cells compacted on the device, the moved cells, the programs, the commitments and
+        `user` (an opaque section of up to 1 MiB: break points, builder parameters).  The same key gives the same bytes every time."""
+        user = bytes(user)
+        n = C.c_size_t()
+        check(lib.h2mi_prover_pk_export(self.handle, user, len(user), None, 0, C.byref(n)), "pk_export")
+        buf = np.zeros(n.value // 8, dtype=np.uint64)
+        check(lib.h2mi_prover_pk_export(self.handle, user, len(user), buf.ctypes.data, buf.nbytes, C.byref(n)), "pk_export")
+        return buf.tobytes()
+
+    def save(self, path_or_file, user: bytes = b"") -> int:
+        """write export(user) to a path or to a binary file object -> the bytes written"""
+        blob = self.export(user)
+        if hasattr(path_or_file, "write"):
+            path_or_file.write(blob)
+        else:
+            with open(path_or_file, "wb") as f:
+                f.write(blob)
+        return len(blob)
+
+    @classmethod
+    def from_blob(cls, params, blob: bytes, by_coset: bool = False) -> "Keys":
+        """h2mi_prover_pk_import: the key a blob describes, against `params` (the WHOLE SRS the key was made against: the library
+        recomputes the commitments and refuses, H2miError(-1), a blob whose stored ones differ).  The layout in HBM is the importer's:
+        by_coset does not depend on how the exporting key was made.  cs, commitments, logup, n_shuffles and phases come from the blob;
+        `user` holds its user section."""
+        cs, user = blob_check(blob)
+        buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+        h = C.c_void_p()
+        check(lib.h2mi_prover_pk_import(buf.ctypes.data, buf.nbytes, params.g_lagrange_handle, KEYGEN_BY_COSET if by_coset else 0, C.byref(h)), "pk_import")
+        self = cls.__new__(cls)
+        self.cs, self.user, self.by_coset, self.handle = cs, user, bool(by_coset), h.value
+        self.logup, self.n_shuffles, self.phases = _blob_programs(blob, cs)
+        self._provers = weakref.WeakSet()
+        self.fixed_commitments = np.zeros((cs.n_fixed, 8), dtype=np.uint64)
+        self.permutation_commitments = np.zeros((cs.n_perm, 8), dtype=np.uint64)
+        check(lib.h2mi_prover_vk_commitments(self.handle, self.fixed_commitments.ctypes.data, self.permutation_commitments.ctypes.data), "vk commitments")
+        return self
+
+    @classmethod
+    def load(cls, params, path_or_file, by_coset: bool = False) -> "Keys":
+        """from_blob over the contents of a path or of a binary file object"""
+        if hasattr(path_or_file, "read"):
+            return cls.from_blob(params, path_or_file.read(), by_coset)
+        with open(path_or_file, "rb") as f:
+            return cls.from_blob(params, f.read(), by_coset)
+
+
+def blob_check(blob: bytes):
+    """h2mi_prover_pk_blob_check (host only, works without a GPU): every validation import applies before its first device call ->
+    (the blob's ConstraintSystem, its user section); H2miError(-1) for a blob import would refuse"""
+    buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+    cs = ConstraintSystem()
+    user, user_len = C.c_void_p(), C.c_size_t()
+    check(lib.h2mi_prover_pk_blob_check(buf.ctypes.data, buf.nbytes, C.byref(cs), C.byref(user), C.byref(user_len)), "pk_blob_check")
+    at = (user.value or 0) - buf.ctypes.data
+    return cs, bytes(buf[at:at + user_len.value]) if user_len.value else b""
+
+
+def blob_sections(blob: bytes, count: int) -> list:
+    """the payloads of the first `count` sections of a CHECKED blob behind its 32-byte header (a 64-bit length, the payload, zeros to 8)"""
+    at, out = 32, []
+    for _ in range(count):
+        n = int.from_bytes(blob[at:at + 8], "little")
+        out.append(bytes(blob[at + 8:at + 8 + n]))
+        at += 8 + (n + 7) // 8 * 8
+    return out
+
+
+def key_blob_head(cs: ConstraintSystem, gates: GateProgram = None, lookups: LookupProgram = None, logup_inputs: LogupInputs = None,
+                  shuffles: ShuffleProgram = None, phases: AdvicePhases = None) -> list:
+    """the five sections a key of this constraint system and these programs exports in front of its cells: the constraint
+    system field by field, the gate, lookup and shuffle programs, the advice phases — what a host that re-runs its cheap configure()
+    holds a key file against before it loads it (custom.Keys.load)"""
+    u32s = lambda *v: b"".join(int(x & 0xFFFFFFFF).to_bytes(4, "little") for x in v)
+    program = lambda g: u32s(g.n_ops, g.n_constants) + b"".join(u32s(o.op, o.index, o.rotation) for o in g._ops[:g.n_ops]) + \
+        g._constants[:g.n_constants].tobytes()
+    n_gates = cs.n_gates if cs.gates == GATES_FLEX_VERTICAL else 0
+    head = u32s(cs.k, cs.n_advice, cs.n_fixed, cs.n_instance, cs.degree, cs.blinding_factors, cs.gates, n_gates, cs.n_perm, cs.n_lookups,
+                cs.n_advice_queries, cs.n_fixed_queries)
+    head += u32s(*cs.gate_advice[:n_gates]) + u32s(*cs.gate_selector[:n_gates])
+    head += b"".join(u32s(c.kind, c.index) for c in cs.perm_columns[:cs.n_perm])
+    head += b"".join(u32s(0, 0, 0, 0) if lookups is not None else u32s(l.input.kind, l.input.index, l.selector_fixed, l.table_fixed)
+                     for l in cs.lookups[:cs.n_lookups])
+    head += b"".join(u32s(q.column, q.rotation) for q in list(cs.advice_queries[:cs.n_advice_queries]) + list(cs.fixed_queries[:cs.n_fixed_queries]))
+    out = [head, program(gates) if gates is not None else b"", b"", b"", b""]
+    if lookups is not None:
+        sets = [logup_inputs.n_inputs[l] if logup_inputs is not None else 1 for l in range(lookups.n_lookups)]
+        out[2] = u32s(lookups.n_lookups, *lookups.n_pairs[:lookups.n_lookups], *sets) + program(lookups._exprs)
+    if shuffles is not None:
+        out[3] = u32s(shuffles.n_shuffles, *shuffles.n_pairs[:shuffles.n_shuffles]) + program(shuffles._exprs)
+    if phases is not None and (phases.n_phases > 1 or phases.n_challenges):
+        out[4] = u32s(phases.n_phases, phases.n_challenges, *phases.advice_phase[:cs.n_advice], *phases.challenge_phase[:phases.n_challenges])
+    return out
+
+
+def _blob_programs(blob: bytes, cs: ConstraintSystem):
+    """what a prover's host needs of a CHECKED blob beside cs -> (logup, n_shuffles, AdvicePhases or None): the header's flag word, and
+    the shuffle and phase sections — the fourth and fifth behind the 32-byte header, each a 64-bit length and a payload padded to 8"""
+    u32 = lambda at: int.from_bytes(blob[at:at + 4], "little")
+    at, payloads = 32, []
+    for _ in range(5):
+        n = int.from_bytes(blob[at:at + 8], "little")
+        payloads.append((at + 8, n))
+        at += 8 + (n + 7) // 8 * 8
+    (sh_at, sh_len), (ph_at, ph_len) = payloads[3], payloads[4]
+    phases = None
+    if ph_len:
+        n_phases, n_challenges = u32(ph_at), u32(ph_at + 4)
+        phases = AdvicePhases.build([u32(ph_at + 8 + 4 * j) for j in range(cs.n_advice)],
+                                    [u32(ph_at + 8 + 4 * cs.n_advice + 4 * i) for i in range(n_challenges)], n_phases=n_phases)
+    return bool(u32(12) & 1), (u32(sh_at) if sh_len else 0), phases
+
 
 class _Counts(C.Structure):
     _fields_ = [("advice", C.c_uint32), ("lookups", C.c_uint32), ("products", C.c_uint32), ("quotient", C.c_uint32), ("evaluations", C.c_uint32)]

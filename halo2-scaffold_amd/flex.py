@@ -20,6 +20,8 @@ small k, accepted by its verifier at k = 16 and above (tests/test_gpu_flex.py).
 rng stand-in as in prover.py, plus streams seed+4 (blinding rows of the permuted lookup columns) and seed+5 (of the
 lookup product).
 """
+import json
+
 from . import engine
 from . import field as F
 from .domain import EvaluationDomain
@@ -378,6 +380,11 @@ class FlexKeys:
         index = {col: j for j, col in enumerate(cs.perm_columns)}
         copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
         self.keys = engine.Keys(cs.abi(k), params, fixed_cells, copies, by_coset=by_coset)
+        self._finish(k)
+
+    def _finish(self, k: int):
+        """what the key shows of its engine.Keys, however that was made"""
+        cs = self.cs
         self.fixed_commitments, self.permutation_commitments = self.keys.fixed_commitments, self.keys.permutation_commitments
         # read-only views of the key's library-owned vectors (Lagrange / coefficient / extended-coset forms), for callers that check them
         nf, m = cs.n_fixed, len(cs.perm_columns)
@@ -390,6 +397,39 @@ class FlexKeys:
 
     def release(self):
         self.keys.release()
+
+    def save(self, path_or_file, user: bytes = b"") -> int:
+        """the key as a file (engine.Keys.save: h2mi_prover_pk_export) -> the bytes written.  The builder's parameters — lookup, the
+        column counts, k, minimum_rows, num_fixed — travel in the file's user section, in front of the caller's `user` bytes (the
+        scaffold's break points): a 32-bit length, that many bytes of JSON, then `user`."""
+        cs = self.cs
+        head = json.dumps({"lookup": bool(cs.lookup), "num_advice": cs.num_advice, "num_lookup_advice": cs.num_lookup_advice, "k": self.domain.k,
+                           "minimum_rows": cs.minimum_rows, "num_fixed": cs.num_fixed}, sort_keys=True).encode()
+        return self.keys.save(path_or_file, len(head).to_bytes(4, "little") + head + bytes(user))
+
+    @classmethod
+    def load(cls, params: ParamsKZG, path_or_file, by_coset: bool = False) -> "FlexKeys":
+        """the key of a file written by save(), without the closure: the builder's constraint system is rebuilt from the parameters in
+        the user section and must be the file's own (ValueError otherwise).  `user` holds the caller's bytes."""
+        blob = path_or_file.read() if hasattr(path_or_file, "read") else open(path_or_file, "rb").read()
+        _, user = engine.blob_check(blob)
+        n = int.from_bytes(user[:4], "little")
+        if len(user) < 4 or len(user) < 4 + n:
+            raise ValueError("key file: no builder parameters in its user section (not written by FlexKeys.save)")
+        p = json.loads(user[4:4 + n].decode())
+        if p["k"] != params.k:
+            raise ValueError(f"key file: made for 2^{p['k']} rows, the SRS has 2^{params.k}")
+        cs = FlexGateCS(p["lookup"], p["num_advice"], p["num_lookup_advice"], k=p["k"], minimum_rows=p["minimum_rows"], num_fixed=p["num_fixed"])
+        if engine.blob_sections(blob, 1) != engine.key_blob_head(cs.abi(params.k))[:1]:
+            raise ValueError("key file: its constraint system is not the one its builder parameters give")
+        self = cls.__new__(cls)
+        self.cs, self.by_coset = cs, bool(by_coset)
+        self.domain = d = EvaluationDomain(cs.degree, params.k)
+        self.u = d.n - (cs.blinding_factors + 1)
+        self.keys = engine.Keys.from_blob(params, blob, by_coset)
+        self.user = user[4 + n:]
+        self._finish(params.k)
+        return self
 
 
 # ---- create_proof --------------------------------------------------------------------------------------------------------

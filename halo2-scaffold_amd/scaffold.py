@@ -13,6 +13,7 @@ table raises ValueError from the prover (ConstraintSystemFailure), "LOOKUP_BITS 
 Added: `mock_device(f, private_inputs, pk)` — `mock` against a key `gen_key` made, on the device (flex.check): at DEGREE 20 - 22 the
 prover says nothing about an unsatisfied gate or copy constraint, and its proof would be accepted by no verifier.
 """
+import json
 import os
 
 from . import flex
@@ -74,17 +75,39 @@ class ProvingKey:
         self.params.release()
 
 
-def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1):
+def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1, key_file=None):
     """src/scaffold.rs:95-156: the circuit's shape from a run on dummy inputs (GateThreadBuilder::keygen + builder.config), the SRS
     from gen_srs(k), keygen_vk + keygen_pk -> (pk, break_points).  by_coset: flex.FlexKeys' (no extended-coset columns on the device);
-    table_depth: ParamsKZG's (every table_depth-th row of the MSM tables, as many passes per commitment)"""
+    table_depth: ParamsKZG's (every table_depth-th row of the MSM tables, as many passes per commitment).
+    key_file ("in production the proving key is generated only once"): a path.  Where the file exists the key and the break points
+    are read from it (flex.FlexKeys.load) and the closure is NOT called; where it does not, the key is generated as without the
+    argument and written there, the break points and LOOKUP_BITS as JSON in the file's user section (a file made under another
+    LOOKUP_BITS is refused with ValueError, as one made for another DEGREE is).  None: nothing is read or written."""
     k, lookup_bits, minimum_rows = _env()
+    if key_file is not None and os.path.exists(key_file):
+        params = gen_srs(k, table_depth=table_depth)
+        try:
+            keys = flex.FlexKeys.load(params, key_file, by_coset=by_coset)
+        except Exception:
+            params.release()
+            raise
+        stored = json.loads(keys.user.decode())
+        if stored["lookup_bits"] != lookup_bits:  # the key's range table would disagree with ctx.lookup_bits at prove time
+            keys.release()
+            params.release()
+            raise ValueError(f"key file: made with LOOKUP_BITS {stored['lookup_bits']}, the environment says {lookup_bits}")
+        pk = ProvingKey(params, keys)
+        pk.lookup_bits = lookup_bits
+        return pk, stored["break_points"]
     cs = _config(f, dummy_inputs, k, lookup_bits, minimum_rows)
     asg = _synthesize(f, dummy_inputs, cs, lookup_bits)
     params = gen_srs(k, table_depth=table_depth)
     pk = ProvingKey(params, flex.FlexKeys(params, cs, asg, by_coset=by_coset))
     pk.lookup_bits = lookup_bits
-    return pk, [list(asg.break_points)]
+    break_points = [list(asg.break_points)]
+    if key_file is not None:
+        pk.keys.save(key_file, json.dumps({"break_points": break_points, "lookup_bits": lookup_bits}).encode())
+    return pk, break_points
 
 
 def prove_private(f, private_inputs, pk: ProvingKey, break_points):

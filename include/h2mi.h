@@ -336,6 +336,43 @@ int h2mi_fr_scatter_cells_dev(const h2mi_cells_source* cols, uint32_t n_cols, ui
  * staged behind one another in the stream's grow-only scratch (8 or 32 bytes per cell, plus 4 per listed row), which keeps that size
  * afterwards: H2MI_ENOMEM where it does not fit.  The host buffers are free when the call returns.  Still one launch. */
 int h2mi_fr_scatter_cells_staged_dev(const h2mi_cells_source* cols, uint32_t n_cols, uint64_t host_mask, uint64_t status_out[2], h2mi_stream_t stream);
+/* The inverse: up to 64 device columns of Montgomery Fr words -> each column's nonzero cells below its row_limit, in ascending row order
+ * (what a proving-key file stores of a fixed column: h2mi_prover_pk_export).  Three launches serve all columns of the call:
+ * k_cells_count (one word per tile of 1024 rows), k_cells_prefix (each column's offsets and its count / last / fits64), k_cells_compact
+ * (the cells; it reads only the tiles that hold any).  No atomic decides a position: the output does not depend on scheduling.
+ * Per column the call reports count (nonzero cells), last (last nonzero row + 1) and fits64 (every nonzero canonical value v has v <=
+ * 2^63 - 1 or v >= r - 2^63; 1 for an empty column), and picks
+ *   width   8 when fits64 — the cell is the signed 64-bit integer v, or -(r - v), exactly what H2MI_CELLS_I64 decodes — else 32: the
+ *           canonical little-endian word, below r, as H2MI_CELLS_CANONICAL reads it;
+ *   layout  H2MI_COMPACT_LAYOUT_DENSE when last * width <= count * (4 + width): `values` holds rows 0 .. last - 1, zeros included, and
+ *           there is no row list; H2MI_COMPACT_LAYOUT_SPARSE otherwise: `rows` holds count uint32 rows, `values` their count cells;
+ *           0 for an empty column (count 0: nothing is written for it).
+ * flags: H2MI_COMPACT_SPARSE forces the sparse layout, H2MI_COMPACT_WORDS forces width 32.  With alloc == NULL the call ends after the
+ * counts (two launches).  Otherwise the library calls alloc(alloc_ctx, bytes) ONCE, with the exact size of the output — per non-empty
+ * column its values, then its row list, each part padded to 16 bytes — and sets every column's values / rows to point into the block
+ * it returned (NULL: H2MI_ENOMEM).  The block is host memory: the cells are staged in the stream's grow-only scratch and copied, the
+ * padding is not written.  Nothing is
+ * written beyond the stated parts.  The call waits for the stream.  The columns are read twice and must not change meanwhile; their words
+ * must be reduced below r.  H2MI_EINVAL: n_cols > 64, a null or misaligned column with row_limit > 0, an unknown flag; H2MI_ERANGE:
+ * row_limit > 2^28. */
+#define H2MI_COMPACT_SPARSE 2u
+#define H2MI_COMPACT_WORDS 4u
+#define H2MI_COMPACT_LAYOUT_DENSE 1u
+#define H2MI_COMPACT_LAYOUT_SPARSE 2u
+typedef struct {
+  const void* d_column; /* in: 32-byte Montgomery words, at least row_limit of them */
+  uint32_t row_limit;   /* in: rows at or beyond it are not read */
+  uint32_t last;        /* out */
+  uint64_t count;       /* out */
+  uint32_t fits64;      /* out */
+  uint32_t layout;      /* out: 0, H2MI_COMPACT_LAYOUT_DENSE, H2MI_COMPACT_LAYOUT_SPARSE */
+  uint32_t width;       /* out: 8 or 32 (0 for an empty column) */
+  uint32_t* rows;       /* out: into the allocated block; NULL unless sparse */
+  void* values;         /* out: into the allocated block */
+} h2mi_cells_compacted;
+typedef void* (*h2mi_compact_alloc_fn)(void* ctx, size_t bytes);
+int h2mi_fr_compact_cells_dev(h2mi_cells_compacted* cols, uint32_t n_cols, unsigned flags, h2mi_compact_alloc_fn alloc, void* alloc_ctx,
+                              h2mi_stream_t stream);
 /* out[i] = value for i < n (Lagrange vectors such as l_active of keygen_pk) */
 int h2mi_fr_fill_dev(void* d_out, size_t n, const uint64_t value[4], h2mi_stream_t stream);
 /* Seeded stand-in for the prover's sweeps of `Scalar::random(rng)` (blinding rows; the vanishing argument's random

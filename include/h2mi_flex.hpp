@@ -17,6 +17,8 @@
 // rng stand-in: `seed`, handed to the library (h2mi_prover.h).
 #pragma once
 #include <array>
+#include <cstdio>
+#include <string>
 
 #include "h2mi_plonk.hpp"
 
@@ -555,6 +557,47 @@ struct FlexKeys {
   plonk::VerifyingKey vk;
   plonk::PkHandle pk;
   explicit FlexKeys(const FlexGateCS& c) : cs(c) {}
+  // The key as a file (plonk::export_key) and back without the closure.  The builder's parameters travel in the file's user section in
+  // front of the caller's `user` bytes (break points), in the form halo2-scaffold_amd/flex.py FlexKeys.save writes — a 32-bit length,
+  // that many bytes of JSON with sorted keys, then `user` — so either host reads the other's files.
+  void write(std::ostream& out, const std::vector<uint8_t>& user = {}) const {
+    char json[192];
+    const int n = std::snprintf(json, sizeof(json), "{\"k\": %u, \"lookup\": %s, \"minimum_rows\": %u, \"num_advice\": %u, \"num_fixed\": %u, \"num_lookup_advice\": %u}",
+                                vk.k, cs.lookup ? "true" : "false", cs.minimum_rows, cs.num_advice, cs.num_fixed, cs.num_lookup_advice);
+    std::vector<uint8_t> section = {(uint8_t)n, (uint8_t)(n >> 8), 0, 0};
+    section.insert(section.end(), json, json + n);
+    section.insert(section.end(), user.begin(), user.end());
+    const std::vector<uint8_t> blob = plonk::export_key(pk, section);
+    out.write((const char*)blob.data(), (std::streamsize)blob.size());
+  }
+  static std::unique_ptr<FlexKeys> read(const poly::kzg::ParamsKZG& params, std::istream& in, unsigned flags = 0, std::vector<uint8_t>* user_out = nullptr) {
+    const std::vector<uint8_t> blob = plonk::read_stream(in);
+    h2mi_constraint_system cs;
+    const void* user = nullptr;
+    size_t user_len = 0;
+    h2mi::check(h2mi_prover_pk_blob_check(blob.data(), blob.size(), &cs, &user, &user_len), "pk_blob_check");
+    const uint8_t* u = (const uint8_t*)user;
+    const size_t n = user_len >= 4 ? (size_t)u[0] | ((size_t)u[1] << 8) | ((size_t)u[2] << 16) | ((size_t)u[3] << 24) : 0;
+    unsigned k = 0, minimum_rows = 0, num_advice = 0, num_fixed = 0, num_lookup = 0;
+    char lookup[8] = {0};
+    const std::string json = n && user_len >= 4 + n ? std::string((const char*)u + 4, n) : std::string();
+    if (std::sscanf(json.c_str(), "{\"k\": %u, \"lookup\": %5[a-z], \"minimum_rows\": %u, \"num_advice\": %u, \"num_fixed\": %u, \"num_lookup_advice\": %u}", &k, lookup,
+                    &minimum_rows, &num_advice, &num_fixed, &num_lookup) != 6)
+      throw Error(H2MI_EINVAL, "FlexKeys::read: no builder parameters in the key file's user section");
+    if (k != params.k() || k != cs.k) throw Error(H2MI_EINVAL, "FlexKeys::read: the key file was made for another number of rows");
+    const bool with_lookup = std::string(lookup) == "true";
+    const FlexGateCS rebuilt = num_advice > 1 ? FlexGateCS(with_lookup, num_advice, num_lookup, k, minimum_rows, num_fixed) : FlexGateCS(with_lookup);
+    const h2mi_constraint_system want = rebuilt.abi(k);
+    if (want.gates != cs.gates || want.n_advice != cs.n_advice || want.n_fixed != cs.n_fixed || want.n_perm != cs.n_perm || want.n_lookups != cs.n_lookups ||
+        want.degree != cs.degree || want.n_gates != cs.n_gates)
+      throw Error(H2MI_EINVAL, "FlexKeys::read: the key file's constraint system is not the one its builder parameters give");
+    std::unique_ptr<FlexKeys> keys(new FlexKeys(rebuilt));
+    keys->cs.k = k;
+    keys->cs.minimum_rows = minimum_rows;
+    plonk::import_key(params, blob, flags, keys->pk, keys->vk);
+    if (user_out) user_out->assign(u + 4 + n, u + user_len);
+    return keys;
+  }
 };
 
 // keygen_vk + keygen_pk (src/scaffold.rs:284,287) from the cells a run of the closure assigns: the fixed columns (the table

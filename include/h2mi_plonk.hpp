@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <iterator>
 #include <map>
 #include <memory>
 #include <optional>
@@ -157,10 +158,51 @@ inline void run_keygen(const h2mi_constraint_system& cs, const poly::kzg::Params
   vk.compute_transcript_repr();
 }
 
+// key files (h2mi_prover_pk_export / _import, include/h2mi_prover.h): the key behind a handle as one blob with the caller's `user`
+// section (at most 1 MiB) ...
+inline std::vector<uint8_t> export_key(const PkHandle& pk, const std::vector<uint8_t>& user = {}) {
+  size_t len = 0;
+  check(h2mi_prover_pk_export(pk.h, user.data(), user.size(), nullptr, 0, &len), "pk_export");
+  std::vector<uint8_t> blob(len);
+  check(h2mi_prover_pk_export(pk.h, user.data(), user.size(), blob.data(), blob.size(), &len), "pk_export");
+  return blob;
+}
+// ... and the key of a blob against `params` (the whole SRS the key was made against: the library recomputes the commitments and
+// refuses a blob whose stored ones differ); flags: 0 or H2MI_KEYGEN_BY_COSET, the importer's choice.  cs_out / user_out: the blob's
+inline void import_key(const poly::kzg::ParamsKZG& params, const std::vector<uint8_t>& blob, unsigned flags, PkHandle& pk, VerifyingKey& vk,
+                       h2mi_constraint_system* cs_out = nullptr, std::vector<uint8_t>* user_out = nullptr) {
+  h2mi_constraint_system cs;
+  const void* user = nullptr;
+  size_t user_len = 0;
+  check(h2mi_prover_pk_blob_check(blob.data(), blob.size(), &cs, &user, &user_len), "pk_blob_check");
+  check(h2mi_prover_pk_import(blob.data(), blob.size(), params.g_lagrange_handle(), flags, &pk.h), "pk_import");
+  vk.k = cs.k;
+  vk.cs_degree = cs.degree;
+  vk.fixed_commitments.resize(cs.n_fixed);
+  vk.permutation_commitments.resize(cs.n_perm);
+  check(h2mi_prover_vk_commitments(pk.h, (uint64_t*)vk.fixed_commitments.data(), (uint64_t*)vk.permutation_commitments.data()), "vk commitments");
+  vk.compute_transcript_repr();
+  if (cs_out) *cs_out = cs;
+  if (user_out) user_out->assign((const uint8_t*)user, (const uint8_t*)user + user_len);
+}
+inline std::vector<uint8_t> read_stream(std::istream& in) { return std::vector<uint8_t>(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>()); }
+
 struct ProvingKey {
   VerifyingKey vk;
   PkHandle pk;
   const VerifyingKey& get_vk() const { return vk; }
+  // ProvingKey::write / read of the crate, in this project's own format: the StandardPlonk key without keygen
+  void write(std::ostream& out) const {
+    const std::vector<uint8_t> blob = export_key(pk);
+    out.write((const char*)blob.data(), (std::streamsize)blob.size());
+  }
+  static std::unique_ptr<ProvingKey> read(const poly::kzg::ParamsKZG& params, std::istream& in, unsigned flags = 0) {
+    std::unique_ptr<ProvingKey> key(new ProvingKey);
+    h2mi_constraint_system cs;
+    import_key(params, read_stream(in), flags, key->pk, key->vk, &cs);
+    if (cs.gates != H2MI_GATES_STANDARD_PLONK || cs.k != params.k()) throw Error(H2MI_EINVAL, "ProvingKey::read: not a StandardPlonk key for this SRS");
+    return key;
+  }
 };
 
 namespace detail {

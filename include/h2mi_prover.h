@@ -348,6 +348,34 @@ int h2mi_prover_pk_release(h2mi_pk_t pk); /* H2MI_EINVAL while a prover created 
 /* VerifyingKey::{fixed_commitments, permutation.commitments}: affine points (8 limbs each); either pointer may be NULL */
 int h2mi_prover_vk_commitments(h2mi_pk_t pk, uint64_t* fixed_out /* n_fixed x 8 */, uint64_t* permutation_out /* n_perm x 8 */);
 
+/* ---- proving-key files: "in production the proving key is generated only once" (the reference on gen_key) ------------------------------
+ * A key leaves HBM as ONE self-describing blob and comes back without the circuit's synthesis.  The blob (DESIGN.md 3 is the normative
+ * layout; little-endian, 8-byte-aligned sections with 64-bit lengths): magic and version, the logUp flag, its length, a 64-bit checksum
+ * of everything else, the constraint system field by field, the gate / lookup / shuffle programs with the logUp input-set counts and the
+ * advice phases where the key has them, per fixed column its nonzero cells as the device compacts them (h2mi_fr_compact_cells_dev, h2mi.h:
+ * signed 64-bit integers where every cell fits, canonical 32-byte words otherwise; rows 0 .. last - 1 where that is no longer than a row
+ * list), the cells the permutation moves (16 bytes each, sorted), the fixed and permutation commitments, and `user`.  Nothing else:
+ * coefficients, cosets, l_0 / l_last / l_active, the active rows and the sorted tables are recomputed.
+ * h2mi_prover_pk_export: `user` is an opaque section of up to 1 MiB for the host (break points, builder parameters).  buf == NULL: *len_out
+ * is the blob's length and nothing is written; otherwise the blob goes to buf[0 .. cap) — H2MI_ERANGE, with *len_out set, when it does
+ * not fit.  The same key exports the same bytes every time, and a resident and a by-coset key of one circuit export the same bytes.
+ * H2MI_EINVAL: a H2MI_KEYGEN_VK_ONLY key (it holds no moved cells), user_len above 1 MiB.  With several devices the primary's columns
+ * are read.
+ * h2mi_prover_pk_blob_check: on the host alone (it works without a GPU), every validation import applies before its first device call —
+ * the format's (lengths and counts against the blob's length and the ABI limits, rows strictly ascending and usable, moved cells sorted
+ * and inside n_perm and the usable rows, no unknown version or flag bit, the checksum) and the constraint system's and its programs'
+ * (what every keygen entry applies, the *_check functions among it).  cs_out / user_out / user_len_out (each may be NULL) receive the
+ * blob's constraint system — fields the shape does not read are zero — and its user section, a pointer into buf.
+ * h2mi_prover_pk_import: flags 0 or H2MI_KEYGEN_BY_COSET — the layout in HBM is the importer's choice, whatever the exporter's was;
+ * H2MI_KEYGEN_LOGUP is the blob's and not accepted here.  The cells go through the route keygen has (h2mi_column_cells with H2MI_CELLS_I64
+ * or H2MI_CELLS_CANONICAL), the stored moved cells stand where keygen assembles the permutation, and from there on import IS keygen:
+ * sigma columns, active rows, commitments, transforms, tables.  The recomputed commitments must be the stored ones: H2MI_EINVAL
+ * otherwise — a damaged cell section and an SRS other than the key's are both found there.  H2MI_ERANGE: the Lagrange SRS is shorter
+ * than 2^k, as at keygen.  A refused import leaves no key and no device allocation behind.  Multi-device modes: keygen's rules. */
+int h2mi_prover_pk_export(h2mi_pk_t pk, const void* user, size_t user_len, void* buf, size_t cap, size_t* len_out);
+int h2mi_prover_pk_blob_check(const void* buf, size_t len, h2mi_constraint_system* cs_out, const void** user_out, size_t* user_len_out);
+int h2mi_prover_pk_import(const void* buf, size_t len, uint64_t g_lagrange_handle, unsigned flags, h2mi_pk_t* pk_out);
+
 /* ---- one prover per (pk, SRS) ----------------------------------------------------------------------------------------------
  * g_handle / g_lagrange_handle: the base sets commitments are made against.  base_lo, base_count: they hold bases
  * [base_lo, base_lo + base_count) of the 2^k — the whole SRS (0, 2^k), or one rank's contiguous slice of it in the

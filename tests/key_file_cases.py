@@ -1,0 +1,275 @@
+"""Proving-key files in Python integers: a writer and a reader of the blob format, written from DESIGN.md 3 alone, and the cases the
+host and GPU tests share.  This file is the pin for the blob's bytes (tests/test_gpu_key_file.py compares h2mi_prover_pk_export with
+write_blob byte for byte) and the way a tampered blob gets a valid checksum again (reseal).
+
+The format, little-endian throughout:
+  header, 32 bytes: the magic "H2MI.PK\\n", u32 version (1), u32 flags (bit 0: the key's lookups are logUp arguments), u64 length of the
+      whole blob, u64 checksum;
+  then sections, each a u64 payload length, the payload, zeros up to the next multiple of 8, always in this order:
+      the constraint system; the gate program; the lookup program; the shuffle program; the advice phases (each of the four empty
+      where the key has none); one section per fixed column; the moved cells; the commitments; the user section.
+The checksum is FNV-1a over the blob's 64-bit words (h = (h ^ word) * 0x100000001b3 mod 2^64 from 0xcbf29ce484222325) with the
+checksum's own word taken as zero."""
+import random
+
+R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+MAGIC = b"H2MI.PK\n"
+VERSION = 1
+FLAG_LOGUP = 1
+HEADER = 32
+MAX_USER = 1 << 20
+EMPTY, DENSE, SPARSE = 0, 1, 2
+GATES_STANDARD_PLONK, GATES_FLEX_VERTICAL, GATES_EXPRESSIONS = 1, 2, 3
+I64_MAX = (1 << 63) - 1
+# the values at which the int64 rule turns: the last that fits from below, the first that does not, the first that fits from above, the
+# last that does not, and the largest field element
+EDGES = [1, R - 1, I64_MAX, 1 << 63, R - (1 << 63), R - (1 << 63) - 1]
+
+u32 = lambda *v: b"".join(int(x & 0xFFFFFFFF).to_bytes(4, "little") for x in v)
+u64 = lambda v: int(v).to_bytes(8, "little")
+pad8 = lambda n: (n + 7) // 8 * 8
+
+
+# ---- the rules ------------------------------------------------------------------------------------------------------------------------
+def checksum(blob: bytes) -> int:
+    h = 0xCBF29CE484222325
+    for i in range(0, len(blob) - 7, 8):
+        w = 0 if i == 24 else int.from_bytes(blob[i:i + 8], "little")
+        h = ((h ^ w) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def fits64(v: int) -> bool:
+    """a canonical nonzero value travels as a signed 64-bit integer when it is at most 2^63 - 1 or at least r - 2^63"""
+    return v <= I64_MAX or v >= R - (1 << 63)
+
+
+def to_i64(v: int) -> int:
+    return v if v <= I64_MAX else -(R - v)
+
+
+def layout_of(count: int, last: int, width: int) -> int:
+    """dense — rows 0 .. last - 1, zeros included, no row list — where that is no longer than the cells with their row list"""
+    if count == 0:
+        return EMPTY
+    return DENSE if last * width <= count * (4 + width) else SPARSE
+
+
+def column_stats(cells: dict, limit: int):
+    """{row: value} -> (rows of the nonzero cells below `limit` in ascending order, count, last, fits64)"""
+    rows = sorted(r for r, v in cells.items() if v % R and r < limit)
+    return rows, len(rows), (rows[-1] + 1 if rows else 0), all(fits64(cells[r] % R) for r in rows)
+
+
+def value_bytes(v: int, width: int) -> bytes:
+    return to_i64(v).to_bytes(8, "little", signed=True) if width == 8 else v.to_bytes(32, "little")
+
+
+def column_payload(cells: dict, limit: int) -> bytes:
+    rows, count, last, fits = column_stats(cells, limit)
+    if count == 0:
+        return u32(EMPTY, 0, 0, 0)
+    width = 8 if fits else 32
+    layout = layout_of(count, last, width)
+    if layout == DENSE:
+        return u32(DENSE, width, count, last) + b"".join(value_bytes(cells.get(r, 0) % R, width) for r in range(last))
+    return u32(SPARSE, width, count, last) + b"".join(value_bytes(cells[r] % R, width) for r in rows) + u32(*rows)
+
+
+def moved_cells(copies) -> list:
+    """the crate's permutation Assembly::copy over (column, row, column, row) in call order -> the cells whose image is another cell,
+    (column, row, image column, image row) ascending"""
+    nxt, aux, sizes = {}, {}, {}
+    g = lambda d, c: d.get(c, c)
+    for lc, lr, rc, rr in copies:
+        left, right = (lc, lr), (rc, rr)
+        lcy, rcy = g(aux, left), g(aux, right)
+        if lcy == rcy:
+            continue
+        if sizes.get(lcy, 1) < sizes.get(rcy, 1):
+            lcy, rcy = rcy, lcy
+        sizes[lcy] = sizes.get(lcy, 1) + sizes.get(rcy, 1)
+        i = rcy
+        while True:
+            aux[i] = lcy
+            i = g(nxt, i)
+            if i == rcy:
+                break
+        nxt[left], nxt[right] = g(nxt, right), g(nxt, left)
+    return sorted((c, r, *to) for (c, r), to in nxt.items() if to != (c, r))
+
+
+# ---- the writer -----------------------------------------------------------------------------------------------------------------------
+def cs_fields(abi) -> dict:
+    """an h2mi_constraint_system (engine.ConstraintSystem) as plain numbers"""
+    return dict(k=abi.k, n_advice=abi.n_advice, n_fixed=abi.n_fixed, n_instance=abi.n_instance, degree=abi.degree,
+                blinding_factors=abi.blinding_factors, gates=abi.gates,
+                gate_columns=[(abi.gate_advice[g], abi.gate_selector[g]) for g in range(abi.n_gates)],
+                perm_columns=[(abi.perm_columns[j].kind, abi.perm_columns[j].index) for j in range(abi.n_perm)],
+                n_lookups=abi.n_lookups,
+                lookups=[(abi.lookups[l].input.kind, abi.lookups[l].input.index, abi.lookups[l].selector_fixed, abi.lookups[l].table_fixed)
+                         for l in range(abi.n_lookups)],
+                advice_queries=[(abi.advice_queries[i].column, abi.advice_queries[i].rotation) for i in range(abi.n_advice_queries)],
+                fixed_queries=[(abi.fixed_queries[i].column, abi.fixed_queries[i].rotation) for i in range(abi.n_fixed_queries)])
+
+
+def program_of(gp):
+    """an h2mi_gate_program (engine.GateProgram) -> ([(op, index, rotation)], [constant as the integer of its Montgomery word])"""
+    return ([(o.op, o.index, o.rotation) for o in gp._ops[:gp.n_ops]],
+            [sum(int(l) << (64 * j) for j, l in enumerate(gp._constants[i])) for i in range(gp.n_constants)])
+
+
+def program_payload(program) -> bytes:
+    ops, constants = program
+    return u32(len(ops), len(constants)) + b"".join(u32(*o) for o in ops) + b"".join(c.to_bytes(32, "little") for c in constants)
+
+
+def cs_payload(cs: dict, lookup_program: bool) -> bytes:
+    gate_columns = cs["gate_columns"] if cs["gates"] == GATES_FLEX_VERTICAL else []  # no other shape reads them
+    out = u32(cs["k"], cs["n_advice"], cs["n_fixed"], cs["n_instance"], cs["degree"], cs["blinding_factors"], cs["gates"], len(gate_columns),
+              len(cs["perm_columns"]), cs["n_lookups"], len(cs["advice_queries"]), len(cs["fixed_queries"]))
+    out += u32(*[a for a, _ in gate_columns]) + u32(*[q for _, q in gate_columns])
+    out += b"".join(u32(kind, index) for kind, index in cs["perm_columns"])
+    out += b"".join(u32(0, 0, 0, 0) if lookup_program else u32(*cs["lookups"][l]) for l in range(cs["n_lookups"]))  # a program replaces them
+    out += b"".join(u32(c, r) for c, r in cs["advice_queries"] + cs["fixed_queries"])
+    return out
+
+
+def usable_rows(cs: dict) -> int:
+    return (1 << cs["k"]) - cs["blinding_factors"] - 1
+
+
+def sections(cs: dict, fixed, moved, commitments: bytes, user: bytes = b"", gates=None, lookups=None, shuffles=None, phases=None) -> list:
+    """the payloads in file order.  fixed: {row: value} per fixed column; moved: moved_cells(copies); commitments: n_fixed + n_perm
+    points of 64 bytes; gates: program_of(..); lookups: (n_pairs, n_inputs, program); shuffles: (n_pairs, program); phases:
+    (n_phases, advice_phase, challenge_phase) — given only for more than one phase or a challenge"""
+    out = [cs_payload(cs, lookups is not None), program_payload(gates) if gates is not None else b"", b"", b"", b""]
+    if lookups is not None:
+        n_pairs, n_inputs, program = lookups
+        out[2] = u32(len(n_pairs), *n_pairs, *n_inputs) + program_payload(program)
+    if shuffles is not None:
+        n_pairs, program = shuffles
+        out[3] = u32(len(n_pairs), *n_pairs) + program_payload(program)
+    if phases is not None:
+        n_phases, advice_phase, challenge_phase = phases
+        out[4] = u32(n_phases, len(challenge_phase), *advice_phase, *challenge_phase)
+    out += [column_payload(cells, usable_rows(cs)) for cells in fixed]
+    out += [b"".join(u32(*m) for m in moved), bytes(commitments), bytes(user)]
+    return out
+
+
+def assemble(payloads, flags: int = 0, version: int = VERSION, magic: bytes = MAGIC) -> bytes:
+    body = b"".join(u64(len(p)) + p + bytes(pad8(len(p)) - len(p)) for p in payloads)
+    blob = magic + u32(version, flags) + u64(HEADER + len(body)) + u64(0) + body
+    return reseal(blob, length=False)
+
+
+def write_blob(cs: dict, fixed, moved, commitments: bytes, user: bytes = b"", logup: bool = False, **programs) -> bytes:
+    return assemble(sections(cs, fixed, moved, commitments, user, **programs), FLAG_LOGUP if logup else 0)
+
+
+def blob_length(payloads) -> int:
+    """the size formula: 32 + sum over the sections of 8 + their payload rounded up to 8; a column's payload is 16 + last * w (dense)
+    or 16 + count * (w + 4) (sparse), the moved cells' 16 each, the commitments' 64 each"""
+    return HEADER + sum(8 + pad8(len(p)) for p in payloads)
+
+
+def reseal(blob: bytes, length: bool = True) -> bytes:
+    """the blob with its length word (unless length=False) and its checksum made right again: what a tampered blob needs for the
+    STRUCTURAL check to be the one that refuses it"""
+    b = bytearray(blob)
+    if length:
+        b[16:24] = u64(len(b))
+    b[24:32] = u64(0)
+    b[24:32] = u64(checksum(bytes(b)))
+    return bytes(b)
+
+
+def custom_inputs(custom, cs, asg, k: int):
+    """a circuit of halo2_scaffold_amd.custom -> (cs fields, fixed cells, copies over the permutation's columns, the programs as
+    write_blob's keywords): what custom.Keys hands to keygen, as plain numbers"""
+    abi = cs.abi(k)
+    index = {col: j for j, col in enumerate(cs.perm_columns)}
+    copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
+    fixed = [{row: custom._evaluated(v) % R for row, v in col.items()} for col in asg.fixed]
+    programs = dict(gates=program_of(cs.gate_program()))
+    lp, li, sp, ph = cs.lookup_program(), cs.logup_inputs(), cs.shuffle_program(), cs.phases()
+    if lp is not None:
+        n = lp.n_lookups
+        programs["lookups"] = (list(lp.n_pairs[:n]), [li.n_inputs[l] if li is not None else 1 for l in range(n)], program_of(lp._exprs))
+    if sp is not None:
+        programs["shuffles"] = (list(sp.n_pairs[:sp.n_shuffles]), program_of(sp._exprs))
+    if ph is not None:
+        programs["phases"] = (ph.n_phases, list(ph.advice_phase[:abi.n_advice]), list(ph.challenge_phase[:ph.n_challenges]))
+    return cs_fields(abi), fixed, copies, programs
+
+
+# ---- the reader -----------------------------------------------------------------------------------------------------------------------
+def split(blob: bytes):
+    """-> (flags, [(offset of the payload, payload)]) of a well-formed blob"""
+    assert blob[:8] == MAGIC and int.from_bytes(blob[8:12], "little") == VERSION and int.from_bytes(blob[16:24], "little") == len(blob)
+    assert int.from_bytes(blob[24:32], "little") == checksum(blob)
+    at, out = HEADER, []
+    while at < len(blob):
+        n = int.from_bytes(blob[at:at + 8], "little")
+        out.append((at + 8, blob[at + 8:at + 8 + n]))
+        at += 8 + pad8(n)
+    assert at == len(blob)
+    return int.from_bytes(blob[12:16], "little"), out
+
+
+def read_column(payload: bytes) -> dict:
+    """a fixed column's section -> {row: value}"""
+    layout, width, count, last = (int.from_bytes(payload[i:i + 4], "little") for i in (0, 4, 8, 12))
+    if layout == EMPTY:
+        return {}
+    n = last if layout == DENSE else count
+    raw = [payload[16 + width * i:16 + width * (i + 1)] for i in range(n)]
+    vals = [int.from_bytes(b, "little", signed=True) % R if width == 8 else int.from_bytes(b, "little") for b in raw]
+    rows = range(last) if layout == DENSE else [int.from_bytes(payload[16 + width * n + 4 * i:][:4], "little") for i in range(n)]
+    return {r: v for r, v in zip(rows, vals) if v}
+
+
+def read_blob(blob: bytes) -> dict:
+    flags, secs = split(blob)
+    w = lambda p, i: int.from_bytes(p[4 * i:4 * i + 4], "little")
+    head = secs[0][1]
+    n_fixed, n_perm = w(head, 2), w(head, 8)
+    assert len(secs) == 5 + n_fixed + 3
+    moved = secs[5 + n_fixed][1]
+    return dict(logup=bool(flags & FLAG_LOGUP), k=w(head, 0), n_fixed=n_fixed, n_perm=n_perm,
+                fixed=[read_column(secs[5 + f][1]) for f in range(n_fixed)],
+                moved=[tuple(w(moved, 4 * i + j) for j in range(4)) for i in range(len(moved) // 16)],
+                commitments=secs[6 + n_fixed][1], user=secs[7 + n_fixed][1], offsets=[at for at, _ in secs], payloads=[p for _, p in secs])
+
+
+# ---- columns for the compaction kernel ---------------------------------------------------------------------------------------------------
+def value_stream(seed: int):
+    """the edge values first, then 254-bit randoms, then small integers, in a seeded order"""
+    rng = random.Random(seed)
+    while True:
+        pick = rng.random()
+        yield rng.choice(EDGES) if pick < 0.3 else rng.randrange(1, R) if pick < 0.65 else rng.randrange(1, 1 << 20)
+
+
+def kernel_patterns(n_rows: int, limit: int, seed: int) -> dict:
+    """name -> {row: nonzero value} over a column of n_rows rows whose first `limit` are read"""
+    vs = value_stream(seed)
+    small = lambda: random.Random(seed).randrange(1, 1 << 40)
+    edges = sorted({t - d for step in (64, 256, 1024) for t in range(step, limit + 1, step) for d in (0, 1) if 0 <= t - d < limit})
+    fit = [1, I64_MAX, R - (1 << 63), R - 1]  # every class that travels as int64, at its edge
+    out = {
+        "empty": {},
+        "row0": {0: next(vs)},
+        "last_usable": {limit - 1: next(vs)},
+        "full": {r: next(vs) for r in range(limit)},
+        "tile_edges": {r: next(vs) for r in edges},
+        "alternating": {r: next(vs) for r in range(0, limit, 2)},
+        "beyond_limit": {r: next(vs) for r in range(limit, n_rows)},
+        "just_fits": {r: fit[r % 4] for r in range(0, limit, 3)},
+        "just_not_low": {**{r: fit[r % 4] for r in range(0, limit, 3)}, (limit // 2) // 3 * 3: 1 << 63},
+        "just_not_high": {**{r: fit[r % 4] for r in range(0, limit, 3)}, (limit // 2) // 3 * 3: R - (1 << 63) - 1},
+        "small_sparse": {r: small() + r for r in range(5, limit, 37)},
+        "small_dense": {r: small() + r for r in range(limit - limit // 4)},
+    }
+    return out
