@@ -77,7 +77,22 @@ int main(int argc, char** argv) {
     if (cs.num_advice > 1) std::printf("columns %u gate + %u lookup-advice\n", cs.num_advice, cs.num_lookup_advice);
     auto closure = [&](uint64_t v) { return run(cs, v); };
     // keygen: the reference runs the closure once on dummy inputs to fix the circuit's shape
-    auto pk = [&] { Timer t("Generating verifying and proving key"); return flex::keygen(params, cs, closure(0)); }();
+    // H2MI_LOGUP: the lookups proven by logUp against the key's sorted table (flex::keygen's logup): "1" one argument per lookup column,
+    // "K" runs of at most K columns, "a,b,.." the runs themselves
+    bool logup = false;
+    std::vector<uint32_t> lookup_sets;
+    if (const char* lg = std::getenv("H2MI_LOGUP")) {
+      logup = true;
+      for (const char* p = lg; *p;) {
+        char* end = nullptr;
+        const unsigned long v = std::strtoul(p, &end, 10);
+        if (end == p) break;
+        lookup_sets.push_back((uint32_t)v);
+        p = *end == ',' ? end + 1 : end;
+      }
+      if (lookup_sets.size() == 1 && lookup_sets[0] <= 1) lookup_sets.clear();
+    }
+    auto pk = [&] { Timer t("Generating verifying and proving key"); return flex::keygen(params, cs, closure(0), 0, logup, lookup_sets); }();
     flex::Assignment asg = closure(x);
     flex::mock(asg, k);  // scaffold::mock (the reference's examples run it first: MockProver::run(..).assert_satisfied())
     std::vector<uint8_t> proof;

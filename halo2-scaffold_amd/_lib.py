@@ -116,6 +116,8 @@ def _load():
         "h2mi_plonk_logup_sum_dev": ([vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_logup_multiplicity_sets_dev": ([vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, u64p, vp], C.c_int),
         "h2mi_plonk_logup_sum_sets_dev": ([vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
+        "h2mi_plonk_logup_rank_cols_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp, u64p, vp], C.c_int),
+        "h2mi_plonk_logup_sum_ranked_dev": ([vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_expr_lg_dev": ([vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_evaluate_h_expr_batch_lg_dev": ([vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
                                                      vp, vp], C.c_int),
@@ -172,6 +174,8 @@ def _load():
         "h2mi_prover_keygen_shuffles": ([vp, vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_logup_inputs_check": ([vp, vp, vp, vp, C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_prover_keygen_logup": ([vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
+        "h2mi_table_logup_check": ([vp, vp, C.POINTER(C.c_uint32)], C.c_int),
+        "h2mi_prover_keygen_table_logup": ([vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_prover_pk_release": ([vp], C.c_int),
         # proving-key files: one self-describing blob out of HBM and back
         "h2mi_prover_pk_export": ([vp, vp, sz, vp, sz, C.POINTER(sz)], C.c_int),

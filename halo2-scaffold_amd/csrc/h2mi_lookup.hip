@@ -41,15 +41,16 @@ __device__ __forceinline__ int cmp256(const fe& a, const fe& b) {  // canonical 
 // uniform), then within the workgroup through a 64-slot LDS table keyed by rank (a slot taken by another rank falls
 // back to the global atomic), and only the table is flushed to HBM: 2^22 zero rows -> 4096 global atomics.
 constexpr uint32_t LK_SLOTS = 64, LK_EMPTY = 0xFFFFFFFFu;
-// `src`: this thread's input element, NULL for a thread beyond the rows
-__device__ __forceinline__ void lk_rank_body(const fe* src, const fe* sorted, uint32_t n_unique, uint32_t* cnt, uint32_t* missing) {
+// `src`: this thread's input element, NULL for a thread beyond the rows.  -> the element's rank, LK_EMPTY for an input that is no table
+// value and for a thread beyond the rows (k_lk_rank_cols stores it; the other kernels drop it)
+__device__ __forceinline__ uint32_t lk_rank_body(const fe* src, const fe* sorted, uint32_t n_unique, uint32_t* cnt, uint32_t* missing) {
   __shared__ uint32_t hkey[LK_SLOTS], hcnt[LK_SLOTS];
   if (threadIdx.x < LK_SLOTS) {
     hkey[threadIdx.x] = LK_EMPTY;
     hcnt[threadIdx.x] = 0;
   }
   __syncthreads();
-  uint32_t lo = LK_EMPTY;
+  uint32_t lo = LK_EMPTY, rank = LK_EMPTY;
   bool active = false;
   if (src) {
     const fe v = fe_from_mont<Fr>(fe_load(src));
@@ -69,6 +70,7 @@ __device__ __forceinline__ void lk_rank_body(const fe* src, const fe* sorted, ui
     }
     if (lo < n_unique && cmp256(fe_load(&sorted[lo]), v) == 0) {
       active = true;
+      rank = lo;
     } else {
       atomicAdd(missing, 1u);
     }
@@ -91,6 +93,7 @@ __device__ __forceinline__ void lk_rank_body(const fe* src, const fe* sorted, ui
   }
   __syncthreads();
   if (threadIdx.x < LK_SLOTS && hkey[threadIdx.x] != LK_EMPTY) atomicAdd(&cnt[hkey[threadIdx.x]], hcnt[threadIdx.x]);
+  return rank;
 }
 __global__ void __launch_bounds__(1024) k_lk_rank(const fe* input, uint32_t u, const fe* sorted, uint32_t n_unique, uint32_t* cnt, uint32_t* missing) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -103,6 +106,19 @@ __global__ void __launch_bounds__(1024) k_lk_rank_sets(const fe* inputs, size_t 
                                                        uint32_t* missing) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   lk_rank_body(i < u ? &inputs[(size_t)blockIdx.y * stride + i] : nullptr, sorted, n_unique, cnt, missing);
+}
+
+// logUp against a table sorted at keygen (h2mi_plonk_logup_rank_cols_dev) [restated in DESIGN.md 4.5]: the columns come through a
+// pointer list (advice columns are no consecutive vectors), blockIdx.y is the column as above, and every usable row's rank is KEPT:
+// ranks[j 2^k + i], which the ranked running sum gathers by.  An absent input stores LK_EMPTY there
+struct RankCols {
+  const fe* col[H2MI_MAX_LOGUP_INPUTS];
+};
+__global__ void __launch_bounds__(1024) k_lk_rank_cols(RankCols cols, size_t stride, uint32_t u, const fe* sorted, uint32_t n_unique, uint32_t* cnt,
+                                                       uint32_t* missing, uint32_t* ranks) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t rank = lk_rank_body(i < u ? &cols.col[blockIdx.y][i] : nullptr, sorted, n_unique, cnt, missing);
+  if (i < u) ranks[(size_t)blockIdx.y * stride + i] = rank;
 }
 
 // Membership alone, for the witness check (h2mi_prover_check): is the input of usable row i one of the table's distinct values?  The
@@ -674,6 +690,49 @@ int h2mi_plonk_logup_multiplicity_sets_dev(const void* d_inputs, uint32_t n_inpu
               (const fe*)sorted, n_unique, cnt, missing);
   }
   H2_LAUNCH("k_logup_scatter", k_logup_scatter, ceil_div_u32(n_unique, 256), 256, 0, s, (const uint32_t*)cnt, (const uint32_t*)first, n_unique, u, (fe*)d_m);
+  if (!g_lk_event) H2_HIP(hipEventCreateWithFlags(&g_lk_event, hipEventDisableTiming));
+  H2_HIP(hipEventRecord(g_lk_event, s));
+  g_lk_stream = s;
+  uint32_t m = 0;
+  H2_HIP(hipMemcpyAsync(&m, missing, 4, hipMemcpyDeviceToHost, s));
+  H2_HIP(hipStreamSynchronize(s));
+  *not_in_table_out = m;
+  return H2MI_OK;
+}
+
+int h2mi_plonk_logup_rank_cols_dev(const void* const* d_inputs, uint32_t n_inputs, const void* d_sorted_canonical, uint32_t n_unique, const void* d_first,
+                                   uint32_t k, uint32_t usable_rows, void* d_ranks, void* d_counts, void* d_m, uint64_t* not_in_table_out,
+                                   h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_inputs || !d_sorted_canonical || !d_first || !d_ranks || !d_counts || !d_m || !not_in_table_out || n_unique == 0) return H2MI_EINVAL;
+  if (n_inputs == 0 || n_inputs > H2MI_MAX_LOGUP_INPUTS) return H2MI_EINVAL;
+  RankCols cols;
+  memset(&cols, 0, sizeof(cols));
+  for (uint32_t j = 0; j < n_inputs; j++) {
+    if (!d_inputs[j]) return H2MI_EINVAL;
+    cols.col[j] = (const fe*)d_inputs[j];
+  }
+  if (k == 0 || k > H2MI_MAX_LOG_N || usable_rows == 0 || usable_rows >= ((uint64_t)1 << k) || n_unique > usable_rows) return H2MI_ERANGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  {
+    int rc0 = use_device(0);
+    if (rc0) return rc0;
+  }
+  hipStream_t s = pick_stream(stream);
+  const uint32_t u = usable_rows;
+  {
+    int rcs = lk_scratch_reserve(4);  // the counter of absent inputs; the histogram and the ranks are the caller's
+    if (rcs) return rcs;
+  }
+  uint32_t* missing = g_lk_scratch;
+  if (g_lk_event && g_lk_stream != s) H2_HIP(hipStreamWaitEvent(s, g_lk_event, 0));
+  H2_HIP(hipMemsetAsync(missing, 0, 16, s));
+  H2_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_unique * 4, s));
+  H2_HIP(hipMemsetAsync(d_m, 0, (size_t)u * 32, s));  // rows 0 .. u - 1; the blinding rows behind them are the caller's
+  H2_LAUNCH("k_lk_rank_cols", k_lk_rank_cols, dim3(ceil_div_u32(u, 1024), n_inputs), 1024, 0, s, cols, (size_t)1 << k, u, (const fe*)d_sorted_canonical,
+            n_unique, (uint32_t*)d_counts, missing, (uint32_t*)d_ranks);
+  H2_LAUNCH("k_logup_scatter", k_logup_scatter, ceil_div_u32(n_unique, 256), 256, 0, s, (const uint32_t*)d_counts, (const uint32_t*)d_first, n_unique, u,
+            (fe*)d_m);
   if (!g_lk_event) H2_HIP(hipEventCreateWithFlags(&g_lk_event, hipEventDisableTiming));
   H2_HIP(hipEventRecord(g_lk_event, s));
   g_lk_stream = s;

@@ -1163,7 +1163,9 @@ __global__ void __launch_bounds__(1024) k_addscan_offsets(const fe* totals, uint
   }
 }
 // apply, as the plain exclusive scan the column is: phi[0] = 0, phi[i] = local[i - 1] + offsets[tile of i - 1] for 1 <= i <= u, brought
-// to the columns' Montgomery-2^256 form; rows beyond u untouched.  offsets == NULL: one tile
+// to the columns' Montgomery-2^256 form; rows beyond u untouched.  offsets == NULL: one tile.  FROM261 = false: the terms were summed
+// in the columns' own form (the ranked sum below), and the word is stored as it is
+template <bool FROM261>
 __global__ void __launch_bounds__(256) k_addscan_apply(const fe* local, const fe* offsets, uint32_t u, fe* phi) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i > u) return;
@@ -1171,9 +1173,41 @@ __global__ void __launch_bounds__(256) k_addscan_apply(const fe* local, const fe
   if (i) {
     fe v = fe_load(&local[i - 1]);
     if (offsets && i - 1 >= AS_TILE) v = fe_add<Fr>(v, fe_load(&offsets[(i - 1) / AS_TILE]));
-    f29_to_mont256<F9>(f29_unpack(v.v), o.v);
+    if (FROM261) f29_to_mont256<F9>(f29_unpack(v.v), o.v);
+    else o = v;
   }
   fe_store(&phi[i], o);
+}
+// ---- logUp against a table sorted at keygen: the running sum by rank (h2mi_plonk_logup_sum_ranked_dev) -------------------------------
+// Every input IS a table value, so 1 / (A + beta) takes at most n_unique values: T[r] = 1 / (sorted[r] + beta) is inverted once (the
+// tile chain of the assigned cells, ONE field inversion) and a row's term is a GATHER, sum_j T[rank_j[i]]: additions only, whatever the
+// number of rows.  The table side, counts[r] T[r], is subtracted on row first[r] (n_unique products; the rows are distinct).  All words
+// are reduced Montgomery-2^256 ones, so the additive scan runs on them as they are.
+__global__ void __launch_bounds__(256) k_logup_table_den(const fe* sorted_mont, fe beta, uint32_t n_unique, fe* den) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n_unique) fe_store(&den[r], fe_add<Fr>(fe_load(&sorted_mont[r]), beta));
+}
+// a rank that is no table index (an input h2mi_plonk_logup_rank_cols_dev counted as absent) adds nothing and reads nothing
+__global__ void __launch_bounds__(256) k_logup_gather(const uint32_t* ranks, uint32_t n_inputs, size_t stride, const fe* T, uint32_t n_unique, uint32_t u,
+                                                      fe* term) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= u) return;
+  fe acc = fe_zero();
+  for (uint32_t j = 0; j < n_inputs; j++) {
+    const uint32_t r = ranks[(size_t)j * stride + i];
+    if (r < n_unique) acc = fe_add<Fr>(acc, fe_load(&T[r]));
+  }
+  fe_store(&term[i], acc);
+}
+__global__ void __launch_bounds__(256) k_logup_table_side(const uint32_t* counts, const uint32_t* first, const fe* T, uint32_t n_unique, uint32_t u,
+                                                          fe* term) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_unique || !counts[r]) return;
+  const uint32_t row = first[r];
+  if (row >= u) return;  // always false for the first rows of a table's usable part
+  fe c = fe_zero();
+  c.v[0] = counts[r];
+  fe_store(&term[row], fe_sub<Fr>(fe_load(&term[row]), fe_mul<Fr>(fe_to_mont<Fr>(c), fe_load(&T[r]))));
 }
 
 struct HostY {  // y^0 .. y^(count-1), Montgomery-2^256
@@ -1707,8 +1741,48 @@ int h2mi_plonk_logup_sum_sets_dev(const void* d_inputs, uint32_t n_inputs, const
   if (rc) return rc;
   H2_LAUNCH("k_addscan_local", k_addscan_local, nblocks, 256, 0, s, (const fe*)t.num, usable_rows, t.num, t.totals);
   if (nblocks > 1) H2_LAUNCH("k_addscan_offsets", k_addscan_offsets, 1, 1024, 0, s, (const fe*)t.totals, nblocks, t.offsets);
-  H2_LAUNCH("k_addscan_apply", k_addscan_apply, ceil_div_u32((uint64_t)usable_rows + 1, 256), 256, 0, s, (const fe*)t.num,
+  H2_LAUNCH("k_addscan_apply", k_addscan_apply<true>, ceil_div_u32((uint64_t)usable_rows + 1, 256), 256, 0, s, (const fe*)t.num,
             (const fe*)(nblocks > 1 ? t.offsets : nullptr), usable_rows, (fe*)d_phi);
+  return release_tmp(s);
+}
+
+int h2mi_plonk_logup_sum_ranked_dev(const void* d_ranks, uint32_t n_inputs, const void* d_sorted_mont, const void* d_counts, const void* d_first,
+                                    uint32_t n_unique, uint32_t k, uint32_t usable_rows, const uint64_t beta[4], void* d_phi, h2mi_stream_t stream) {
+  H2_REQUIRE_INIT();
+  if (!d_ranks || !d_sorted_mont || !d_counts || !d_first || !beta || !d_phi || n_unique == 0 || n_inputs == 0 || n_inputs > H2MI_MAX_LOGUP_INPUTS)
+    return H2MI_EINVAL;
+  if (rows_out_of_range(k, usable_rows) || n_unique > usable_rows) return H2MI_ERANGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  CallScope scope_;
+  hipStream_t s = pick_stream(stream);
+  const size_t u = usable_rows;
+  const uint32_t nblocks = ceil_div_u32(u, AS_TILE), ntiles = ceil_div_u32(n_unique, ASG_TILE);
+  // scratch (elements): term[u] den[n_unique] T[n_unique] totals[nblocks] offsets[nblocks] tile products[ntiles] tile inverses[ntiles] invalid[1]
+  int rc = ensure_tmp(u + 2 * (size_t)n_unique + 2 * (size_t)nblocks + 2 * (size_t)ntiles + 1, s);
+  if (rc) return rc;
+  fe* term = tmp_base();
+  fe* den = term + u;
+  fe* T = den + n_unique;
+  fe* totals = T + n_unique;
+  fe* offsets = totals + nblocks;
+  fe* tprod = offsets + nblocks;
+  fe* tileinv = tprod + ntiles;
+  AssignedSegs segs;
+  memset(&segs, 0, sizeof(segs));
+  segs.n_segs = 1;
+  segs.dst[0] = T;
+  segs.start[1] = n_unique;
+  H2_LAUNCH("k_logup_table_den", k_logup_table_den, ceil_div_u32(n_unique, 256), 256, 0, s, (const fe*)d_sorted_mont, host_fe(beta), n_unique, den);
+  rc = assigned_chain(den, 1, n_unique, 0, segs, tprod, tileinv, reinterpret_cast<unsigned long long*>(tileinv + ntiles), s);  // the ONE inversion
+  if (rc) return rc;
+  H2_LAUNCH("k_logup_gather", k_logup_gather, ceil_div_u32(u, 256), 256, 0, s, (const uint32_t*)d_ranks, n_inputs, (size_t)1 << k, (const fe*)T, n_unique,
+            usable_rows, term);
+  H2_LAUNCH("k_logup_table_side", k_logup_table_side, ceil_div_u32(n_unique, 256), 256, 0, s, (const uint32_t*)d_counts, (const uint32_t*)d_first,
+            (const fe*)T, n_unique, usable_rows, term);
+  H2_LAUNCH("k_addscan_local", k_addscan_local, nblocks, 256, 0, s, (const fe*)term, usable_rows, term, totals);
+  if (nblocks > 1) H2_LAUNCH("k_addscan_offsets", k_addscan_offsets, 1, 1024, 0, s, (const fe*)totals, nblocks, offsets);
+  H2_LAUNCH("k_addscan_apply", k_addscan_apply<false>, ceil_div_u32((uint64_t)usable_rows + 1, 256), 256, 0, s, (const fe*)term,
+            (const fe*)(nblocks > 1 ? offsets : nullptr), usable_rows, (fe*)d_phi);
   return release_tmp(s);
 }
 

@@ -12,6 +12,7 @@
 #include <array>
 #include <cstring>
 #include <initializer_list>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -355,7 +356,7 @@ int check_phases(const h2mi_constraint_system& cs, const h2mi_gate_program* gate
 }
 
 void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, const h2mi_advice_phases* phases,
-              const h2mi_shuffle_program* shuffles, const h2mi_logup_inputs* inputs = nullptr) {
+              const h2mi_shuffle_program* shuffles, const h2mi_logup_inputs* inputs = nullptr, bool table_logup = false) {
   auto bad = [](const char* what) { throw Error(H2MI_EINVAL, std::string("constraint system: ") + what); };
   const uint32_t n_ch = phases ? phases->n_challenges : 0;
   if (phases && check_phases(cs, gates, lookups, *phases, inputs)) bad("advice phases / challenges");
@@ -388,7 +389,8 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, 
       if (cs.n_gates == 0 || cs.n_gates > H2MI_MAX_GATES) bad("gate count");
       for (uint32_t g = 0; g < cs.n_gates; g++)
         if (cs.gate_advice[g] >= cs.n_advice || cs.gate_selector[g] >= cs.n_fixed) bad("gate columns");
-      if (cs.n_perm && cs.degree - 2 > 3) bad("permutation chunks longer than three columns");
+      // (a table-logUp key's quotient is the interpreting kernel's, which takes any chunk; merged arguments need the degree)
+      if (cs.n_perm && cs.degree - 2 > 3 && !table_logup) bad("permutation chunks longer than three columns");
     }
     if (lookups) {  // the lookups as a program: cs.lookups[] is not read
       if (cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_exprs takes H2MI_GATES_EXPRESSIONS");
@@ -412,8 +414,50 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, 
   }
 }
 
+// the rules of h2mi_table_logup_check (include/h2mi_prover.h): the single-expression lookups of a hard-wired shape grouped, in order,
+// into logUp arguments over their fixed tables -> per argument its first entry of cs.lookups and its number of entries
+struct TableLogup {
+  uint32_t n_args = 0;
+  uint32_t first[H2MI_MAX_LOOKUPS], sets[H2MI_MAX_LOOKUPS];
+};
+int check_table_logup(const h2mi_constraint_system& cs, const h2mi_logup_inputs* li, uint32_t* degree_out, TableLogup* out) {
+  if (cs.gates != H2MI_GATES_STANDARD_PLONK && cs.gates != H2MI_GATES_FLEX_VERTICAL) return H2MI_EINVAL;  // a program's lookups: h2mi_prover_keygen_logup
+  if (cs.n_lookups == 0 || cs.n_lookups > H2MI_MAX_LOOKUPS || cs.n_advice > H2MI_MAX_ADVICE || cs.n_fixed > H2MI_MAX_FIXED) return H2MI_EINVAL;
+  for (uint32_t l = 0; l < cs.n_lookups; l++) {
+    const h2mi_lookup& lk = cs.lookups[l];
+    if (lk.input.kind != H2MI_COL_ADVICE || lk.input.index >= cs.n_advice || lk.table_fixed >= cs.n_fixed) return H2MI_EINVAL;
+    if (lk.selector_fixed >= (int32_t)cs.n_fixed || lk.selector_fixed < -1) return H2MI_EINVAL;
+  }
+  TableLogup g;
+  uint32_t used = 0, degree = 0;
+  uint64_t merged = 0;  // advice columns that are an input of an argument with several: their extended cosets lie behind one another
+  while (used < cs.n_lookups) {
+    const uint32_t K = li ? li->n_inputs[g.n_args] : 1u;
+    if (K == 0 || K > H2MI_MAX_LOGUP_INPUTS || K > cs.n_lookups - used) return H2MI_EINVAL;
+    uint32_t d = 2 + 1;  // 2 + sum_j deg A_j + deg S [DESIGN.md 4.5]
+    for (uint32_t j = 0; j < K; j++) {
+      const h2mi_lookup& lk = cs.lookups[used + j];
+      if (lk.table_fixed != cs.lookups[used].table_fixed) return H2MI_EINVAL;
+      d += lk.selector_fixed >= 0 ? 2 : 1;
+      if (K > 1) {  // the quotient reads the K input cosets as consecutive vectors: plain columns, each in one place only
+        if (lk.selector_fixed >= 0 || ((merged >> lk.input.index) & 1u)) return H2MI_EINVAL;
+        merged |= (uint64_t)1 << lk.input.index;
+      }
+    }
+    if (d > cs.degree) return H2MI_EINVAL;
+    degree = std::max(degree, d);
+    g.first[g.n_args] = used;
+    g.sets[g.n_args++] = K;
+    used += K;
+  }
+  if (degree_out) *degree_out = degree;
+  if (out) *out = g;
+  return H2MI_OK;
+}
+
 struct Table {  // a lookup table's distinct usable values in ascending canonical order, for the device's counting sort
   Dev sorted, sorted_mont, mult;
+  Dev first;  // a key of h2mi_prover_keygen_table_logup: per distinct value the lowest usable row that holds it (u32)
   uint32_t n_unique = 0;
   void alloc(size_t rows) {  // room for `rows` distinct values (h2mi_fr_sort_unique_dev inside a proof fills it)
     sorted = vec(rows);
@@ -451,6 +495,13 @@ struct h2mi_pk_s {
   std::vector<h2mi_expr_op> lookup_ops;
   std::vector<uint64_t> lookup_constants;
   ArgumentSlices lookup_slices;
+  // h2mi_prover_keygen_table_logup: logUp over the single-expression lookups of a hard-wired shape (logup && !lookup_exprs).  cs.n_lookups
+  // is then the number of ARGUMENTS and cs.lookups[a] the first input of argument a; the caller's entries live here, argument by
+  // argument, and tables[tl_table[a]] is argument a's table — arguments over one fixed column share one
+  bool table_logup = false;
+  uint32_t tl_sets[H2MI_MAX_LOOKUPS] = {0};
+  h2mi_lookup tl_inputs[H2MI_MAX_LOOKUPS][H2MI_MAX_LOGUP_INPUTS];
+  uint32_t tl_table[H2MI_MAX_LOOKUPS] = {0};
   // shuffle arguments (h2mi_prover_keygen_shuffles): the key's own copy, cut into each shuffle's input and shuffle-side polynomials
   uint32_t n_shuffles = 0;
   std::vector<h2mi_expr_op> shuffle_ops;
@@ -482,10 +533,19 @@ bool alive(const std::set<const void*>& s, T p) {
   return p && s.count((const void*)p);
 }
 
-void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells) {
+// with_first: also Table::first, per distinct value the lowest usable row that holds it — the padding zeros count as rows
+void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells, bool with_first = false) {
   // values on the usable rows, canonical and Montgomery; unassigned usable rows hold zero
   std::vector<std::pair<Fr, Fr>> vals;  // (canonical, montgomery)
   vals.reserve(cells.count);
+  std::map<std::array<uint64_t, 4>, uint32_t> lowest;  // canonical value -> its lowest row (with_first)
+  auto seen_at = [&](const Fr& canonical, uint32_t row) {
+    const std::array<uint64_t, 4> key = {canonical.l[0], canonical.l[1], canonical.l[2], canonical.l[3]};
+    auto it = lowest.find(key);
+    if (it == lowest.end()) lowest[key] = row;
+    else it->second = std::min(it->second, row);
+  };
+  std::vector<bool> assigned(with_first ? pk.u : 0, false);
   // this pass reads the caller's cells on the host (the sort below is the host's too): a rational table column is resolved here,
   // whatever its length, with the values the device column holds
   const std::vector<Fr> resolved = (cells.flags & H2MI_CELLS_RATIONAL) && cells.count ? resolve_rational(cells) : std::vector<Fr>();
@@ -494,8 +554,13 @@ void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells) {
     if (row >= pk.u) throw Error(H2MI_ERANGE, "lookup table larger than the usable rows (LOOKUP_BITS must be below DEGREE)");
     const Fr m = resolved.empty() ? cell_value(cells, i) : resolved[i];
     vals.push_back({to_canonical(m), m});
+    if (with_first) {
+      seen_at(vals.back().first, row);
+      assigned[row] = true;
+    }
   }
   const uint64_t zeros_extra = pk.u - cells.count;
+  if (with_first && zeros_extra) seen_at(fr_zero(), (uint32_t)(std::find(assigned.begin(), assigned.end(), false) - assigned.begin()));
   auto less = [](const std::pair<Fr, Fr>& a, const std::pair<Fr, Fr>& b) {
     for (int i = 3; i >= 0; i--)
       if (a.first.l[i] != b.first.l[i]) return a.first.l[i] < b.first.l[i];
@@ -524,6 +589,12 @@ void build_table(h2mi_pk_s& pk, Table& t, const h2mi_column_cells& cells) {
   check(h2mi_memcpy_h2d(t.sorted->p, canon.data(), canon.size() * 32), "table");
   check(h2mi_memcpy_h2d(t.sorted_mont->p, mont.data(), mont.size() * 32), "table");
   check(h2mi_memcpy_h2d(t.mult->p, mult.data(), mult.size() * 4), "table");
+  if (with_first) {
+    std::vector<uint32_t> first;
+    for (const Fr& c : canon) first.push_back(lowest.at({c.l[0], c.l[1], c.l[2], c.l[3]}));
+    t.first = vec(first.size() / 8 + 1);
+    check(h2mi_memcpy_h2d(t.first->p, first.data(), first.size() * 4), "table");
+  }
 }
 
 // a caller's program copied into vectors the key owns -> the view over the copy
@@ -543,10 +614,21 @@ h2mi_gate_program own_program(const h2mi_gate_program& g, std::vector<h2mi_expr_
 std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                                   const h2mi_advice_phases* phases, uint64_t g_lagrange, const h2mi_column_cells* fixed, const uint32_t* copies,
                                   size_t n_copies, unsigned flags, const h2mi_shuffle_program* shuffles = nullptr, const h2mi_logup_inputs* inputs = nullptr,
-                                  const std::vector<std::array<uint32_t, 4>>* stored_moved = nullptr, const uint8_t* stored_commitments = nullptr) {
-  validate(cs, gates, lookups, phases, shuffles, inputs);
+                                  const std::vector<std::array<uint32_t, 4>>* stored_moved = nullptr, const uint8_t* stored_commitments = nullptr,
+                                  const TableLogup* table_logup = nullptr) {
+  validate(cs, gates, lookups, phases, shuffles, inputs, table_logup != nullptr);
   std::unique_ptr<h2mi_pk_s> pkp(new h2mi_pk_s(cs));
   h2mi_pk_s& pk = *pkp;
+  if (table_logup) {  // h2mi_prover_keygen_table_logup: from here on the key's lookups are the ARGUMENTS, each named by its first input
+    const TableLogup& g = *table_logup;
+    pk.table_logup = pk.logup = true;
+    pk.cs.n_lookups = g.n_args;
+    for (uint32_t a = 0; a < g.n_args; a++) {
+      pk.tl_sets[a] = g.sets[a];
+      for (uint32_t j = 0; j < g.sets[a]; j++) pk.tl_inputs[a][j] = cs.lookups[g.first[a] + j];
+      pk.cs.lookups[a] = cs.lookups[g.first[a]];
+    }
+  }
   std::memset(&pk.phases, 0, sizeof(pk.phases));
   pk.phases.n_phases = 1;
   if (phases) pk.phases = *phases;
@@ -569,7 +651,7 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
   }
   pk.vk_only = (flags & H2MI_KEYGEN_VK_ONLY) != 0;
   pk.by_coset = !pk.vk_only && (flags & H2MI_KEYGEN_BY_COSET) != 0;
-  pk.logup = lookups && (flags & H2MI_KEYGEN_LOGUP) != 0;
+  pk.logup = pk.table_logup || (lookups && (flags & H2MI_KEYGEN_LOGUP) != 0);
   if (gates) {
     pk.check_gates = pk.gate_program;
   } else {  // a hard-wired shape: its gates as the program the witness check interprets
@@ -695,7 +777,14 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     check(h2mi_sync(), "sync");
   }
   // a lookup given as expressions has no keygen-time table: theta, or an advice column in it, is known only inside a proof
-  for (uint32_t l = 0; !pk.lookup_exprs && l < cs.n_lookups; l++) build_table(pk, pk.tables[l], fixed[cs.lookups[l].table_fixed]);
+  for (uint32_t l = 0; !pk.lookup_exprs && !pk.table_logup && l < cs.n_lookups; l++) build_table(pk, pk.tables[l], fixed[cs.lookups[l].table_fixed]);
+  // a table-logUp key: one sorted table (with its first rows) per distinct fixed column, whatever the number of arguments over it
+  for (uint32_t a = 0; pk.table_logup && a < pk.cs.n_lookups; a++) {
+    pk.tl_table[a] = a;
+    for (uint32_t b = 0; b < a; b++)
+      if (pk.cs.lookups[b].table_fixed == pk.cs.lookups[a].table_fixed) pk.tl_table[a] = std::min(pk.tl_table[a], pk.tl_table[b]);
+    if (pk.tl_table[a] == a) build_table(pk, pk.tables[a], fixed[pk.cs.lookups[a].table_fixed], /*with_first=*/true);
+  }
   return pkp;
 }
 
@@ -859,7 +948,13 @@ struct h2mi_prover_s {
     Sides c;
     Forms a, s, z;
     Table sorted;
+    // a table-logUp key: every input's rank in the key's sorted table (u32 x inputs x 2^k) and the joint histogram (u32 x n_unique),
+    // written by the lookups phase and gathered by the products phase
+    Dev ranks, counts;
   } lk[H2MI_MAX_LOOKUPS];
+  // a table-logUp key: per argument with several inputs ONE vector that holds their advice columns' extended cosets behind one another
+  // (the `coset` of those columns is a window into it), so that the quotient reads the inputs where the transforms put them
+  std::vector<Dev> coset_blocks;
   // shuffle arguments: both sides compressed, the product in its three forms
   struct Sf {
     Sides c;
@@ -1038,7 +1133,19 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
   const h2mi_constraint_system& cs = pk->cs;
   const size_t n = pk->n, ext = pk->by_coset ? pk->n : pk->ext;  // a by-coset key: every `coset` vector is one slice
   p.advice.resize(cs.n_advice);
-  for (Forms& f : p.advice) f.alloc(n, ext);
+  for (uint32_t a = 0; pk->table_logup && a < cs.n_lookups; a++) {
+    const uint32_t K = pk->tl_sets[a];
+    if (K == 1) continue;
+    p.coset_blocks.push_back(vec(K * ext));
+    for (uint32_t j = 0; j < K; j++) {  // each such column is an input of one merged argument only (h2mi_table_logup_check)
+      Forms& f = p.advice[pk->tl_inputs[a][j].input.index];
+      f.value = vec(n);
+      f.poly = vec(n);
+      f.coset = Dev(new DeviceVec(*p.coset_blocks.back(), j * ext, ext));
+    }
+  }
+  for (Forms& f : p.advice)
+    if (!f.value) f.alloc(n, ext);
   p.z.resize(pk->n_sets);
   for (Forms& f : p.z) f.alloc(n, ext);
   p.instance_poly.resize(cs.n_instance);
@@ -1061,6 +1168,10 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
       p.lk[l].sorted.alloc(pk->u);
     } else if (cs.lookups[l].selector_fixed >= 0) {
       p.lk[l].c.input = vec(n);
+    }
+    if (pk->table_logup) {
+      p.lk[l].ranks = vec(pk->tl_sets[l] * n / 8 + (pk->tl_sets[l] * n % 8 ? 1 : 0));
+      p.lk[l].counts = vec(pk->tables[pk->tl_table[l]].n_unique / 8 + 1);
     }
     p.lk[l].a.alloc(n, ext);
     if (!pk->logup) p.lk[l].s.alloc(n, ext);  // a logUp key: `a` holds M, `z` the running sum, there is no permuted table
@@ -1220,7 +1331,40 @@ void phase_lookups(h2mi_prover_s& p, const uint64_t* theta, uint64_t* points_out
     p.theta = take_theta(theta);
     p.have_theta = true;
   }
-  if (L && pk.logup) {
+  if (L && pk.table_logup) {
+    // logUp against the key's sorted tables [DESIGN.md 4.5]: nothing is compressed and nothing sorted — per argument ONE ranking launch
+    // over its input columns where they lie (ranks and the joint histogram stay for the products phase), M scattered by the table's first
+    // rows.  Blinding rows and commitments: the program route's below, word for word
+    const std::vector<Fr> mb = p.blinding(4, (size_t)(bf + 1) * L);
+    PatchList pl;
+    std::vector<const void*> cols;
+    for (uint32_t a = 0; a < L; a++) {
+      const void* inputs[H2MI_MAX_LOGUP_INPUTS];
+      for (uint32_t j = 0; j < pk.tl_sets[a]; j++) {
+        const h2mi_lookup& d = pk.tl_inputs[a][j];
+        inputs[j] = p.advice[d.input.index].value->p;
+        if (d.selector_fixed >= 0) {  // q_lookup * a: an argument of one input (h2mi_table_logup_check)
+          check(h2mi_fr_mul_dev(pk.fixed_values[d.selector_fixed]->p, inputs[j], n, p.lk[a].c.input->p, nullptr), "lookup input");
+          inputs[j] = p.lk[a].c.input->p;
+        }
+      }
+      const Table& t = pk.tables[pk.tl_table[a]];
+      DeviceVec& mult = *p.lk[a].a.value;
+      uint64_t missing = 0;
+      check(h2mi_plonk_logup_rank_cols_dev(inputs, pk.tl_sets[a], t.sorted->p, t.n_unique, t.first->p, cs.k, u, p.lk[a].ranks->p, p.lk[a].counts->p, mult.p,
+                                           &missing, nullptr),
+            "logup_rank_cols");
+      if (missing) throw Error(H2MI_EUNSAT, "lookup input not in the table (ConstraintSystemFailure)");
+      for (uint32_t r = 0; r <= bf; r++) pl.add(mult, u + r, mb[(size_t)(bf + 1) * a + r]);
+      cols.push_back(p.col(mult));
+    }
+    pl.flush();
+    p.commit_phase(true, cols, 0, /*sparse=*/false, /*inorder=*/true);
+    check(h2mi_msm_flush(), "flush");
+    check(h2mi_stream_wait(p.side, nullptr), "stream_wait");
+    for (uint32_t a = 0; a < L; a++) p.forms(p.lk[a].a, p.side);
+    p.read_points(L, points_out);
+  } else if (L && pk.logup) {
     // logUp [restated in DESIGN.md 4.5]: compress -> multiplicities -> blinding rows -> one in-order commitment group of L columns.
     // M's blinding rows u .. 2^k - 1 come from the permuted columns' stream (purpose 4): bf + 1 scalars per lookup, in lookup order
     p.theta = take_theta(theta);
@@ -1344,14 +1488,17 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
         member(p.check_in->p, ts, absent, first_row);
       }
     } else {
-      const h2mi_lookup& d = cs.lookups[l];
-      const void* input = p.advice[d.input.index].value->p;
-      if (d.selector_fixed >= 0) {
-        if (!p.check_in) p.check_in = vec(n);
-        check(h2mi_fr_mul_dev(pk.fixed_values[d.selector_fixed]->p, input, n, p.check_in->p, nullptr), "lookup input");
-        input = p.check_in->p;
+      // a table-logUp key: every input of the argument against its table, the entry counting the absent (row, input) pairs
+      for (uint32_t j = 0; j < (pk.table_logup ? pk.tl_sets[l] : 1u); j++) {
+        const h2mi_lookup& d = pk.table_logup ? pk.tl_inputs[l][j] : cs.lookups[l];
+        const void* input = p.advice[d.input.index].value->p;
+        if (d.selector_fixed >= 0) {
+          if (!p.check_in) p.check_in = vec(n);
+          check(h2mi_fr_mul_dev(pk.fixed_values[d.selector_fixed]->p, input, n, p.check_in->p, nullptr), "lookup input");
+          input = p.check_in->p;
+        }
+        member(input, pk.tables[pk.table_logup ? pk.tl_table[l] : l], absent, first_row);
       }
-      member(input, pk.tables[l], absent, first_row);
     }
     if (absent) out.push_back({H2MI_CHECK_LOOKUP, l, first_row, absent});
   }
@@ -1409,8 +1556,15 @@ void phase_products(h2mi_prover_s& p, const Fr& beta, const Fr& gamma, uint64_t*
     PatchList pl;
     for (uint32_t l = 0; l < L; l++) {
       DeviceVec& phi = *p.lk[l].z.value;
-      check(h2mi_plonk_logup_sum_sets_dev(p.lk[l].c.input->p, pk.lookup_slices.sets[l], p.lk[l].c.table->p, p.lk[l].a.value->p, cs.k, u, beta.l, phi.p, nullptr),
-            "logup_sum");
+      if (pk.table_logup) {  // by rank: one inversion per distinct table value, a gather per row
+        const Table& t = pk.tables[pk.tl_table[l]];
+        check(h2mi_plonk_logup_sum_ranked_dev(p.lk[l].ranks->p, pk.tl_sets[l], t.sorted_mont->p, p.lk[l].counts->p, t.first->p, t.n_unique, cs.k, u, beta.l,
+                                              phi.p, nullptr),
+              "logup_sum_ranked");
+      } else {
+        check(h2mi_plonk_logup_sum_sets_dev(p.lk[l].c.input->p, pk.lookup_slices.sets[l], p.lk[l].c.table->p, p.lk[l].a.value->p, cs.k, u, beta.l, phi.p, nullptr),
+              "logup_sum");
+      }
       pl.add_tail(phi, u, bf, pb, l);
     }
     pl.flush();
@@ -1523,7 +1677,9 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_coset
   }
   for (uint32_t s = 0; s < n_sets; s++) ec.perm_z[s] = p.z[s].coset->p;
   ec.n_lookups = L | (pk.logup ? H2MI_LOOKUPS_LOGUP : 0u);
-  for (uint32_t l = 0; l < H2MI_FLEX_MAX_LOOKUPS; l++) lg.n_inputs[l] = l < L && pk.lookup_exprs ? pk.lookup_slices.sets[l] : 1u;
+  // a table-logUp key: the K inputs are the advice columns' own cosets, K consecutive vectors from the first one's (create_prover)
+  for (uint32_t l = 0; l < H2MI_FLEX_MAX_LOOKUPS; l++)
+    lg.n_inputs[l] = l < L && pk.lookup_exprs ? pk.lookup_slices.sets[l] : l < L && pk.table_logup ? pk.tl_sets[l] : 1u;
   for (uint32_t l = 0; l < L; l++) {
     const h2mi_lookup& lk = cs.lookups[l];
     if (pk.lookup_exprs) {
@@ -1679,14 +1835,15 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
     check(h2mi_plonk_evaluate_h_standard_dev(&sc, d.k(), d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l,
                                              (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
-  } else if (cs.gates == H2MI_GATES_EXPRESSIONS) {
-    // gates given as a program: the interpreting kernel reads any column of the proof through one pointer table
+  } else if (cs.gates == H2MI_GATES_EXPRESSIONS || pk.table_logup) {
+    // gates given as a program: the interpreting kernel reads any column of the proof through one pointer table.  A table-logUp key of
+    // a hard-wired shape goes the same way through the shape's equivalent program, as batches do: the shapes' own kernels have no logUp term
     h2mi_expr_cosets ec;
     h2mi_shuffle_cosets sc;
     h2mi_logup_cosets lg;
     h2mi_instance_cosets ic;
     fill_expr_cosets(p, ec, sc, lg, ic);
-    check(h2mi_plonk_evaluate_h_expr_in_dev(&ec, pk.n_shuffles ? &sc : nullptr, &lg, &ic, &pk.gate_program, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
+    check(h2mi_plonk_evaluate_h_expr_in_dev(&ec, pk.n_shuffles ? &sc : nullptr, &lg, &ic, &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
                                             d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l,
                                             (const uint64_t*)t_inv.data(), h.p, nullptr),
           "evaluate_h");
@@ -2321,6 +2478,7 @@ int h2mi_prover_pk_export(h2mi_pk_t pk, const void* user, size_t user_len, void*
   *len_out = 0;
   if (!alive(g_live_pks, pk)) return H2MI_EHANDLE;
   if (pk->vk_only) return H2MI_EINVAL;  // it holds no moved cells: not a key anything could prove with
+  if (pk->table_logup) return H2MI_EINVAL;  // the blob format has no section for the grouping of a hard-wired shape's lookups
   int range = H2MI_OK;
   const int rc = guarded([&] {
     std::vector<uint8_t> blob;
@@ -2505,6 +2663,28 @@ int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_p
                              h2mi_pk_t* pk_out) {
   return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP | H2MI_KEYGEN_BY_COSET, gates, lookups, phases, shuffles, inputs, g_lagrange_handle, fixed, copies,
                       n_copies, flags, pk_out);
+}
+
+int h2mi_table_logup_check(const h2mi_constraint_system* cs, const h2mi_logup_inputs* sets, uint32_t* degree_out) {
+  if (!cs) return H2MI_EINVAL;
+  return check_table_logup(*cs, sets, degree_out, nullptr);
+}
+
+int h2mi_prover_keygen_table_logup(const h2mi_constraint_system* cs, const h2mi_logup_inputs* sets, uint64_t g_lagrange_handle,
+                                   const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
+  if (!cs || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP))) return H2MI_EINVAL;
+  *pk_out = nullptr;
+  TableLogup groups;
+  if (const int rc = check_table_logup(*cs, sets, nullptr, &groups)) return rc;  // every rule of the grouping, before any device work
+  if (const int rc = h2mi_column_cells_check(fixed, cs->n_fixed, H2MI_CELLS_FOR_FIXED)) return rc;
+  if (h2mi_device_count() == 0) return H2MI_ENODEV;
+  return guarded([&] {
+    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags & H2MI_KEYGEN_VK_ONLY, nullptr,
+                                           nullptr, nullptr, nullptr, &groups);
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    g_live_pks.insert(pk.get());
+    *pk_out = pk.release();
+  });
 }
 
 int h2mi_prover_pk_release(h2mi_pk_t pk) {
@@ -2852,7 +3032,7 @@ int h2mi_prover_device_bytes(h2mi_prover_t prover, size_t* key_bytes_out, size_t
   auto one = [&](const Dev& d) { total += d ? d->n * 32 : 0; };
   auto many = [&](const std::vector<Dev>& v) { for (const Dev& d : v) one(d); };
   auto forms = [&](const Forms& f) { one(f.value); one(f.poly); one(f.coset); };
-  auto table = [&](const Table& t) { one(t.sorted); one(t.sorted_mont); one(t.mult); };
+  auto table = [&](const Table& t) { one(t.sorted); one(t.sorted_mont); one(t.mult); one(t.first); };
   many(pk.fixed_values); many(pk.fixed_polys); many(pk.fixed_cosets); many(pk.sigma_values); many(pk.sigma_polys); many(pk.sigma_cosets);
   for (const Dev* d : {&pk.l0, &pk.l_last, &pk.l_active, &pk.l0_poly, &pk.l_last_poly, &pk.l_active_poly, &pk.active_rows, &pk.moved_cells_dev}) one(*d);
   for (const Table& t : pk.tables) table(t);
@@ -2865,6 +3045,7 @@ int h2mi_prover_device_bytes(h2mi_prover_t prover, size_t* key_bytes_out, size_t
     for (const Dev* d : {&l.c.input, &l.c.table, &l.c.in_coset, &l.c.tab_coset}) one(*d);
     forms(l.a); forms(l.s); forms(l.z);
     table(l.sorted);
+    one(l.ranks); one(l.counts);  // a table-logUp key: 4 bytes per input and row, 4 per distinct table value (rounded up to 32 bytes)
   }
   for (const h2mi_prover_s::Sf& f : p.sf) {
     for (const Dev* d : {&f.c.input, &f.c.table, &f.c.in_coset, &f.c.tab_coset}) one(*d);

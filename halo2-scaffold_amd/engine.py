@@ -161,6 +161,18 @@ class LogupInputs(C.Structure):
                                           C.byref(degree)), "logup_inputs_check")
         return degree.value
 
+    def check_table(self, cs: "ConstraintSystem") -> int:
+        """h2mi_table_logup_check: these counts as the grouping of a hard-wired shape's cs.lookups[] into logUp arguments over their fixed
+        tables -> the largest required degree; H2miError(-1) for what h2mi_prover_keygen_table_logup would refuse"""
+        return table_logup_check(cs, self)
+
+
+def table_logup_check(cs: "ConstraintSystem", logup_inputs: "LogupInputs" = None) -> int:
+    """h2mi_table_logup_check (host only, works without a GPU); logup_inputs None: one argument per entry of cs.lookups[]"""
+    degree = C.c_uint32()
+    check(lib.h2mi_table_logup_check(C.byref(cs), C.byref(logup_inputs) if logup_inputs is not None else None, C.byref(degree)), "table_logup_check")
+    return degree.value
+
 
 class ShuffleProgram(C.Structure):
     """h2mi_shuffle_program: the shuffle arguments of a constraint system — per shuffle its n_pairs input polynomials, then its n_pairs
@@ -532,7 +544,12 @@ class Keys:
         h = C.c_void_p()
         flags = (KEYGEN_VK_ONLY if vk_only else 0) | (KEYGEN_LOGUP if logup else 0) | (KEYGEN_BY_COSET if by_coset else 0)
         opt = lambda s: C.byref(s) if s is not None else None
-        if logup_inputs is not None:  # several input sets per logUp lookup: h2mi_prover_keygen_shuffles with the counts beside it
+        if gates is None and logup:  # a hard-wired shape's single-expression lookups as logUp arguments over their keygen-sorted tables
+            if by_coset:
+                raise ValueError("a table-logUp key has no by-coset form (h2mi_prover_keygen_table_logup refuses H2MI_KEYGEN_BY_COSET)")
+            check(lib.h2mi_prover_keygen_table_logup(C.byref(cs), opt(logup_inputs), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags,
+                                                     C.byref(h)), "keygen")
+        elif logup_inputs is not None:  # several input sets per logUp lookup: h2mi_prover_keygen_shuffles with the counts beside it
             check(lib.h2mi_prover_keygen_logup(C.byref(cs), C.byref(gates), opt(lookups), C.byref(logup_inputs), opt(phases), opt(shuffles),
                                                params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
         elif shuffles is not None:  # shuffle arguments: h2mi_prover_keygen_phases with the shuffles beside it; every other circuit takes the calls below

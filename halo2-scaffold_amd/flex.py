@@ -98,6 +98,31 @@ class FlexGateCS:
         self.blinding_factors = 6
         self.chunk = self.degree - 2
 
+    def use_logup(self, lookup_sets=None):
+        """Opt in to logUp over the fixed table (h2mi_prover_keygen_table_logup; FlexKeys(..., logup=True) calls this): the lookup-advice
+        columns — or the one q_lookup * a input — become logUp arguments, in column order.  lookup_sets None: one argument per column;
+        an integer K: runs of at most K columns per argument; a list: the runs themselves.  The degree follows 2 + sum of the inputs'
+        degrees + 1 per argument: q_lookup * a keeps 5, K lookup-advice columns give 3 + K — which moves the
+        permutation sets and the number of h pieces with it.  -> the runs"""
+        n = (1 if self.lookup else 0) if self.num_advice == 1 else self.num_lookup_advice
+        if n == 0:
+            raise ValueError("logup=True: the constraint system has no lookup")
+        if lookup_sets is None:
+            runs = [1] * n
+        elif isinstance(lookup_sets, int):
+            if not 1 <= lookup_sets <= engine.MAX_LOGUP_INPUTS:
+                raise ValueError(f"lookup_sets must be 1 .. {engine.MAX_LOGUP_INPUTS}")
+            runs = [lookup_sets] * (n // lookup_sets) + ([n % lookup_sets] if n % lookup_sets else [])
+        else:
+            runs = [int(r) for r in lookup_sets]
+            if sum(runs) != n or any(not 1 <= r <= engine.MAX_LOGUP_INPUTS for r in runs):
+                raise ValueError(f"lookup_sets {runs}: runs of 1 .. {engine.MAX_LOGUP_INPUTS} columns that sum to the {n} lookup columns")
+        self.logup_runs = runs
+        input_degree = 2 if self.num_advice == 1 else 1
+        self.degree = max(3, 2 + max(runs) * input_degree + 1)
+        self.chunk = self.degree - 2
+        return runs
+
     def abi(self, k: int) -> engine.ConstraintSystem:
         """this constraint system as the data h2mi_prover_keygen takes: one vertical gate per gate column with its selector, the
         permutation argument's columns, the lookups (single column: q_lookup * a; several: one per lookup-advice column)"""
@@ -365,9 +390,15 @@ class FlexKeys:
     lookup table's sorted form and the verifying key's commitments.  by_coset=True (H2MI_KEYGEN_BY_COSET): no extended-coset column
     on the device, the quotient one coset at a time — the same proof bytes; `fixed_cosets` / `sigma_cosets` are then refused."""
 
-    def __init__(self, params: ParamsKZG, cs: FlexGateCS, asg: Assignment, by_coset: bool = False):
+    def __init__(self, params: ParamsKZG, cs: FlexGateCS, asg: Assignment, by_coset: bool = False, logup: bool = False, lookup_sets=None):
         self.cs = cs
         self.by_coset = bool(by_coset)
+        # logup=True (h2mi_prover_keygen_table_logup): the lookups are proven with multiplicities and a running sum against the key's sorted
+        # table, lookup_sets columns per argument (FlexGateCS.use_logup, which also moves cs.degree); no by-coset form, no key file
+        self.logup = bool(logup)
+        if lookup_sets is not None and not logup:
+            raise ValueError("lookup_sets groups the columns of a logUp key: FlexKeys(..., logup=True)")
+        self.logup_inputs = engine.LogupInputs.build(cs.use_logup(lookup_sets)) if logup else None
         k = params.k
         self.domain = d = EvaluationDomain(cs.degree, k)
         self.u = u = d.n - (cs.blinding_factors + 1)
@@ -379,7 +410,7 @@ class FlexKeys:
             fixed_cells[cs.col_table] = [v % R for v in tv]  # dense: rows 0 .. len - 1
         index = {col: j for j, col in enumerate(cs.perm_columns)}
         copies = [(index[(left[0], left[1])], left[2], index[(right[0], right[1])], right[2]) for left, right in asg.copies]
-        self.keys = engine.Keys(cs.abi(k), params, fixed_cells, copies, by_coset=by_coset)
+        self.keys = engine.Keys(cs.abi(k), params, fixed_cells, copies, by_coset=by_coset, logup=logup, logup_inputs=self.logup_inputs)
         self._finish(k)
 
     def _finish(self, k: int):

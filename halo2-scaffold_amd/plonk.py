@@ -203,6 +203,26 @@ def logup_sum_sets(k: int, d_inputs: DevBuf, n_inputs: int, d_table: DevBuf, d_m
                                              d_phi.ptr, None), "logup_sum_sets")
 
 
+def logup_rank_cols(k: int, d_columns, d_sorted_canonical: DevBuf, n_unique: int, d_first: DevBuf, usable_rows: int, d_ranks: DevBuf,
+                    d_counts: DevBuf, d_m: DevBuf) -> int:
+    """h2mi_plonk_logup_rank_cols_dev: the usable rows of the listed columns (DevBufs anywhere in memory, 1 .. 6 of them) ranked against
+    a table sorted elsewhere, in one launch: d_ranks[j 2^k + i] (u32), the joint histogram d_counts (u32 x n_unique) and the M column
+    d_m (counts[r] on row first[r]).  Returns the inputs of any column that are no table value."""
+    ptrs = (C.c_void_p * len(d_columns))(*[b.ptr for b in d_columns])
+    missing = C.c_uint64()
+    _check(lib.h2mi_plonk_logup_rank_cols_dev(ptrs, len(d_columns), d_sorted_canonical.ptr, n_unique, d_first.ptr, k, usable_rows, d_ranks.ptr,
+                                              d_counts.ptr, d_m.ptr, C.byref(missing), None), "logup_rank_cols")
+    return missing.value
+
+
+def logup_sum_ranked(k: int, d_ranks: DevBuf, n_inputs: int, d_sorted_mont: DevBuf, d_counts: DevBuf, d_first: DevBuf, n_unique: int, beta: int,
+                     usable_rows: int, d_phi: DevBuf) -> None:
+    """h2mi_plonk_logup_sum_ranked_dev: the running sum of h2mi_plonk_logup_sum_sets_dev from the ranks: T[r] = 1 / (sorted[r] + beta) by one
+    inversion, row i adds sum_j T[rank_j[i]], row first[r] subtracts counts[r] T[r]; rows 0 .. usable_rows of d_phi"""
+    _check(lib.h2mi_plonk_logup_sum_ranked_dev(d_ranks.ptr, n_inputs, d_sorted_mont.ptr, d_counts.ptr, d_first.ptr, n_unique, k, usable_rows,
+                                               F.fr_to_mont_limbs(beta).ctypes.data, d_phi.ptr, None), "logup_sum_ranked")
+
+
 class _RangeCosets(C.Structure):
     _fields_ = [("a", C.c_void_p), ("lookup_advice", C.c_void_p), ("lookup_selector", C.c_void_p), ("q", C.c_void_p), ("table", C.c_void_p),
                 ("perm_value", C.c_void_p * 4), ("perm_sigma", C.c_void_p * 4), ("perm_z", C.c_void_p * 4), ("lookup_permuted_input", C.c_void_p),
@@ -482,3 +502,12 @@ def sort_unique(values: DevBuf, count: int):
     n_unique = C.c_uint32()
     _check(lib.h2mi_fr_sort_unique_dev(values.ptr, count, canon.ptr, mont.ptr, mult.ptr, C.byref(n_unique), None), "sort_unique")
     return canon, mont, mult, n_unique.value
+
+
+def sort_unique_first(values: DevBuf, count: int):
+    """h2mi_fr_sort_unique_first_dev -> (canonical values, Montgomery values, u32 multiplicities, u32 first positions, n_unique): the table
+    arguments of h2mi_plonk_logup_rank_cols_dev / _sum_ranked_dev"""
+    canon, mont, mult, first = DevBuf(count * 32), DevBuf(count * 32), DevBuf(count * 4), DevBuf(count * 4)
+    n_unique = C.c_uint32()
+    _check(lib.h2mi_fr_sort_unique_first_dev(values.ptr, count, canon.ptr, mont.ptr, mult.ptr, first.ptr, C.byref(n_unique), None), "sort_unique_first")
+    return canon, mont, mult, first, n_unique.value

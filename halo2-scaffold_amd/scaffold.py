@@ -75,14 +75,18 @@ class ProvingKey:
         self.params.release()
 
 
-def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1, key_file=None):
+def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1, key_file=None, logup: bool = False, lookup_sets=None):
     """src/scaffold.rs:95-156: the circuit's shape from a run on dummy inputs (GateThreadBuilder::keygen + builder.config), the SRS
     from gen_srs(k), keygen_vk + keygen_pk -> (pk, break_points).  by_coset: flex.FlexKeys' (no extended-coset columns on the device);
     table_depth: ParamsKZG's (every table_depth-th row of the MSM tables, as many passes per commitment).
     key_file ("in production the proving key is generated only once"): a path.  Where the file exists the key and the break points
     are read from it (flex.FlexKeys.load) and the closure is NOT called; where it does not, the key is generated as without the
     argument and written there, the break points and LOOKUP_BITS as JSON in the file's user section (a file made under another
-    LOOKUP_BITS is refused with ValueError, as one made for another DEGREE is).  None: nothing is read or written."""
+    LOOKUP_BITS is refused with ValueError, as one made for another DEGREE is).  None: nothing is read or written.
+    logup / lookup_sets: flex.FlexKeys' (the range checks proven by logUp against the key's sorted table, lookup_sets lookup-advice
+    columns per argument).  Such a key has no file form: together with key_file it is a ValueError."""
+    if logup and key_file is not None:
+        raise ValueError("key_file with logup=True: the key-file format has no section for a logUp key of the builders' lookups")
     k, lookup_bits, minimum_rows = _env()
     if key_file is not None and os.path.exists(key_file):
         params = gen_srs(k, table_depth=table_depth)
@@ -102,7 +106,7 @@ def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1, key_f
     cs = _config(f, dummy_inputs, k, lookup_bits, minimum_rows)
     asg = _synthesize(f, dummy_inputs, cs, lookup_bits)
     params = gen_srs(k, table_depth=table_depth)
-    pk = ProvingKey(params, flex.FlexKeys(params, cs, asg, by_coset=by_coset))
+    pk = ProvingKey(params, flex.FlexKeys(params, cs, asg, by_coset=by_coset, logup=logup, lookup_sets=lookup_sets))
     pk.lookup_bits = lookup_bits
     break_points = [list(asg.break_points)]
     if key_file is not None:
@@ -110,9 +114,17 @@ def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1, key_f
     return pk, break_points
 
 
-def prove_private(f, private_inputs, pk: ProvingKey, break_points):
+def prove_private(f, private_inputs, pk: ProvingKey, break_points, logup: bool = False, lookup_sets=None):
     """src/scaffold.rs:158-244: witness generation with the stored break points (GateThreadBuilder::prover), create_proof -> the public
-    inputs (the proof bytes are kept in pk.last_proof)"""
+    inputs (the proof bytes are kept in pk.last_proof).  logup / lookup_sets: what gen_key was given — the argument is the key's, so a
+    pair that is not the key's is a ValueError"""
+    same = bool(logup) == bool(getattr(pk.keys, "logup", False))
+    if same and logup and lookup_sets is not None:
+        runs = list(pk.cs.logup_runs)
+        same = pk.cs.use_logup(lookup_sets) == runs
+        pk.cs.use_logup(runs)  # the key's own grouping again, whatever was asked
+    if not same:
+        raise ValueError("prove_private: logup / lookup_sets are not the ones the key was generated with")
     _, lookup_bits, _ = _env()
     asg = _synthesize(f, private_inputs, pk.cs, lookup_bits)
     if [list(asg.break_points)] != [list(b) for b in break_points]:
@@ -133,11 +145,11 @@ def mock_device(f, private_inputs, pk: ProvingKey):
     return list(asg.instance)
 
 
-def prove(f, private_inputs, dummy_inputs, by_coset: bool = False, table_depth: int = 1):
+def prove(f, private_inputs, dummy_inputs, by_coset: bool = False, table_depth: int = 1, logup: bool = False, lookup_sets=None):
     """src/scaffold.rs:246-366: keygen on dummy inputs, then one proof of the private inputs -> (proof bytes, public inputs)"""
-    pk, break_points = gen_key(f, dummy_inputs, by_coset=by_coset, table_depth=table_depth)
+    pk, break_points = gen_key(f, dummy_inputs, by_coset=by_coset, table_depth=table_depth, logup=logup, lookup_sets=lookup_sets)
     try:
-        public_io = prove_private(f, private_inputs, pk, break_points)
+        public_io = prove_private(f, private_inputs, pk, break_points, logup=logup)
         return pk.last_proof, public_io
     finally:
         pk.release()

@@ -524,6 +524,34 @@ int h2mi_plonk_logup_multiplicity_sets_dev(const void* d_inputs, uint32_t n_inpu
                                            uint64_t* not_in_table_out, h2mi_stream_t stream);
 int h2mi_plonk_logup_sum_sets_dev(const void* d_inputs, uint32_t n_inputs, const void* d_table, const void* d_m, uint32_t k, uint32_t usable_rows,
                                   const uint64_t beta[4], void* d_phi, h2mi_stream_t stream);
+/* The same argument against a table whose distinct values were sorted ELSEWHERE (a fixed table: once, at keygen), for input columns that
+ * are table values as they stand (one component, no theta) [DESIGN.md 4.5, pinned to tests/table_logup_cases.py].  No sort, no
+ * compressed vector and no per-row fraction inside a proof.
+ * h2mi_plonk_logup_rank_cols_dev: d_inputs lists n_inputs (1 .. H2MI_MAX_LOGUP_INPUTS) device columns of 2^k elements, anywhere in memory
+ * (Montgomery).  d_sorted_canonical: the n_unique distinct values of the table's usable rows, ascending, canonical 256-bit words;
+ * d_first[r]: the lowest usable row that holds distinct value r (both as h2mi_fr_sort_unique_first_dev gives them).  ONE ranking launch
+ * whatever n_inputs:
+ *   d_ranks[j 2^k + i] = the rank of input j at usable row i (u32; rows >= usable_rows are not written; unspecified for an input that
+ *     is no table value);
+ *   d_counts[r] = the joint histogram, sum_j #{i < usable_rows : A_j[i] = sorted[r]} (u32 x n_unique, cleared by the call);
+ *   d_m[first[r]] = counts[r] as a field element (Montgomery), every other usable row 0, rows >= usable_rows untouched: the M column
+ *     h2mi_plonk_logup_multiplicity_sets_dev writes for the same columns and table;
+ *   *not_in_table_out = the inputs of any column that are no table value (mandatory; the call synchronises the stream on it).
+ * H2MI_EINVAL: a NULL pointer (a listed column included), n_unique == 0, n_inputs == 0 or above the maximum.  H2MI_ERANGE: k,
+ * usable_rows out of range or n_unique > usable_rows.
+ * h2mi_plonk_logup_sum_ranked_dev: the running sum from those ranks.  T[r] = 1 / (sorted[r] + beta), r < n_unique, by ONE field inversion
+ * per call; usable row i contributes sum_j T[rank_j[i]], row first[r] also - counts[r] T[r]; phi[0] = 0 and phi[i + 1] = phi[i] + that,
+ * on rows 0 .. usable_rows of d_phi, the rows behind untouched.  d_sorted_mont: the distinct values in the memory format.  The words
+ * are those h2mi_plonk_logup_sum_sets_dev writes for the same columns and multiplicities (both store reduced Montgomery words).  A rank
+ * that is no index below n_unique contributes nothing.  A zero denominator (sorted[r] = -beta) gets no special handling, as there: phi
+ * is then meaningless. */
+int h2mi_plonk_logup_rank_cols_dev(const void* const* d_inputs, uint32_t n_inputs, const void* d_sorted_canonical, uint32_t n_unique,
+                                   const void* d_first /* u32 x n_unique */, uint32_t k, uint32_t usable_rows,
+                                   void* d_ranks /* u32 x n_inputs x 2^k */, void* d_counts /* u32 x n_unique */, void* d_m,
+                                   uint64_t* not_in_table_out, h2mi_stream_t stream);
+int h2mi_plonk_logup_sum_ranked_dev(const void* d_ranks, uint32_t n_inputs, const void* d_sorted_mont, const void* d_counts, const void* d_first,
+                                    uint32_t n_unique, uint32_t k, uint32_t usable_rows, const uint64_t beta[4], void* d_phi,
+                                    h2mi_stream_t stream);
 /* evaluate_h + vanishing division for the halo2-lib constraint systems [halo2-base shapes restated from memory]: gate
  * q (a + a(wX) a(w^2 X) - a(w^3 X)), permutation argument over n_perm <= 4 columns in chunks of chunk_len (= cs.degree()
  * - 2 = 1 .. 3), and — has_lookup (the Range builder, extended domain 4n) — one lookup in `table` of either

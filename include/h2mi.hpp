@@ -400,10 +400,12 @@ inline int msm_batch_sparse_dev(uint64_t handle, const void* const* d_scalars, s
 struct DeviceVec {  // RAII device copy of a coefficient vector
   void* p = nullptr;
   size_t n = 0;
+  bool window = false;  // elements [first, first + count) of another vector, which owns the memory and outlives this one
   explicit DeviceVec(size_t count) : n(count) { check(h2mi_malloc(count * 32, &p), "h2mi_malloc"); }
   explicit DeviceVec(const std::vector<Fr>& v) : DeviceVec(v.size()) { check(h2mi_memcpy_h2d(p, v.data(), n * 32), "h2d"); }
+  DeviceVec(const DeviceVec& whole, size_t first, size_t count) : p((char*)whole.p + first * 32), n(count), window(true) {}
   DeviceVec(const DeviceVec&) = delete;
-  ~DeviceVec() { if (p) h2mi_free(p); }
+  ~DeviceVec() { if (p && !window) h2mi_free(p); }
   std::vector<Fr> download() const {
     std::vector<Fr> v(n);
     check(h2mi_memcpy_d2h(v.data(), p, n * 32), "d2h");

@@ -104,6 +104,33 @@ struct FlexGateCS {
     degree = Lc ? 4 : 3;
     chunk = degree - 2;
   }
+  // Opt in to logUp over the fixed table (h2mi_prover_keygen_table_logup; flex::keygen with logup = true calls this): the lookup-advice
+  // columns — or the one q_lookup * a input — become logUp arguments in column order.  lookup_sets empty: one argument per column; one
+  // element K: runs of at most K columns; several: the runs themselves.  The degree follows 2 + sum of the inputs' degrees + 1 per
+  // argument (q_lookup * a keeps 5, K lookup-advice columns give 3 + K), and the permutation sets and h pieces with it
+  std::vector<uint32_t> logup_runs;
+  void use_logup(const std::vector<uint32_t>& lookup_sets = {}) {
+    const uint32_t n = num_advice == 1 ? (lookup ? 1u : 0u) : num_lookup_advice;
+    if (n == 0) throw Error(H2MI_EINVAL, "use_logup: the constraint system has no lookup");
+    std::vector<uint32_t> runs;
+    if (lookup_sets.empty()) {
+      runs.assign(n, 1u);
+    } else if (lookup_sets.size() == 1 && lookup_sets[0] >= 1 && lookup_sets[0] <= H2MI_MAX_LOGUP_INPUTS) {
+      for (uint32_t left = n; left; left -= runs.back()) runs.push_back(std::min(left, lookup_sets[0]));
+    } else {
+      runs = lookup_sets;
+    }
+    uint32_t sum = 0, longest = 0;
+    for (uint32_t r : runs) {
+      if (r == 0 || r > H2MI_MAX_LOGUP_INPUTS) throw Error(H2MI_EINVAL, "use_logup: runs of 1 .. 6 columns");
+      sum += r;
+      longest = std::max(longest, r);
+    }
+    if (sum != n) throw Error(H2MI_EINVAL, "use_logup: the runs do not sum to the lookup columns");
+    logup_runs = runs;
+    degree = std::max(3u, 2 + longest * (num_advice == 1 ? 2u : 1u) + 1);
+    chunk = degree - 2;
+  }
   // the same constraint system as the numbers create_proof reads off it (h2mi_prover.h)
   h2mi_constraint_system abi(uint32_t k_) const {
     h2mi_constraint_system cs;
@@ -602,8 +629,13 @@ struct FlexKeys {
 
 // keygen_vk + keygen_pk (src/scaffold.rs:284,287) from the cells a run of the closure assigns: the fixed columns (the table
 // column dense, the others sparse) and the copy constraints, columns renumbered into the permutation argument's order
-inline std::unique_ptr<FlexKeys> keygen(const poly::kzg::ParamsKZG& params, const FlexGateCS& cs, const Assignment& asg, unsigned flags = 0) {
+// logup (off by default): the lookups proven by logUp against the key's sorted table, lookup_sets as FlexGateCS::use_logup takes them —
+// the key's constraint system is then keys->cs, whose degree may differ from cs's; such a key has no by-coset form and no file form
+inline std::unique_ptr<FlexKeys> keygen(const poly::kzg::ParamsKZG& params, const FlexGateCS& cs, const Assignment& asg, unsigned flags = 0, bool logup = false,
+                                        const std::vector<uint32_t>& lookup_sets = {}) {
   std::unique_ptr<FlexKeys> keys(new FlexKeys(cs));
+  if (logup) keys->cs.use_logup(lookup_sets);
+  else if (!lookup_sets.empty()) throw Error(H2MI_EINVAL, "keygen: lookup_sets groups the columns of a logUp key");
   plonk::KeygenInput in;
   for (uint32_t c = 0; c < cs.n_fixed; c++) {
     if ((int)c == cs.col_table) {
@@ -622,7 +654,24 @@ inline std::unique_ptr<FlexKeys> keygen(const poly::kzg::ParamsKZG& params, cons
   };
   for (const auto& c : asg.copies)
     in.copies.insert(in.copies.end(), {perm_index(c.first.kind, c.first.col), c.first.row, perm_index(c.second.kind, c.second.col), c.second.row});
-  plonk::run_keygen(cs.abi(params.k()), params, in, flags, keys->pk, keys->vk);  // flags: 0 or H2MI_KEYGEN_BY_COSET
+  if (!logup) {
+    plonk::run_keygen(cs.abi(params.k()), params, in, flags, keys->pk, keys->vk);  // flags: 0 or H2MI_KEYGEN_BY_COSET
+    return keys;
+  }
+  const h2mi_constraint_system abi = keys->cs.abi(params.k());
+  h2mi_logup_inputs sets;
+  for (uint32_t l = 0; l < H2MI_MAX_LOOKUPS; l++) sets.n_inputs[l] = l < keys->cs.logup_runs.size() ? keys->cs.logup_runs[l] : 1u;
+  std::vector<h2mi_column_cells> fixed;
+  for (const plonk::ColumnCells& c : in.fixed) fixed.push_back(c.view());
+  h2mi::check(h2mi_prover_keygen_table_logup(&abi, &sets, params.g_lagrange_handle(), fixed.data(), in.copies.data(), in.copies.size() / 4, flags, &keys->pk.h),
+              "keygen_table_logup");
+  plonk::VerifyingKey& vk = keys->vk;
+  vk.k = abi.k;
+  vk.cs_degree = abi.degree;
+  vk.fixed_commitments.resize(abi.n_fixed);
+  vk.permutation_commitments.resize(abi.n_perm);
+  h2mi::check(h2mi_prover_vk_commitments(keys->pk.h, (uint64_t*)vk.fixed_commitments.data(), (uint64_t*)vk.permutation_commitments.data()), "vk commitments");
+  vk.compute_transcript_repr();
   return keys;
 }
 

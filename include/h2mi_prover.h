@@ -344,6 +344,37 @@ int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_p
                              const h2mi_logup_inputs* inputs, const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles,
                              uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags,
                              h2mi_pk_t* pk_out);
+/* logUp for the single-expression lookups of a HARD-WIRED shape (cs->lookups[], the range checks of H2MI_GATES_FLEX_VERTICAL): the argument
+ * stated for h2mi_logup_inputs above — the same M, phi, quotient terms, evaluations, openings, blinding streams and offsets — with every
+ * tuple of ONE component, so theta does not enter: A_j is entry j's advice column, or fixed[selector_fixed] * advice, and S is the fixed
+ * table column.  The table is fixed, so the key holds its distinct values sorted once, with first[r], the lowest usable row that holds
+ * distinct value r (the padding zeros of the column count as rows); a proof then compresses nothing and sorts nothing: per argument ONE
+ * h2mi_plonk_logup_rank_cols_dev over the input columns where they lie, and the running sum by rank (h2mi_plonk_logup_sum_ranked_dev: one
+ * inversion per distinct table value, a gather per row).  The quotient runs through the shape's equivalent program
+ * (h2mi_shape_gate_program), as batches do, with the advice columns' own extended cosets as the inputs.
+ * Grouping: sets == NULL makes one argument per entry of cs->lookups; otherwise argument a takes the next sets->n_inputs[a] entries, in
+ * order.  h2mi_table_logup_check (host only, works without a GPU) is the validation keygen applies before any device work; H2MI_EINVAL:
+ * cs->gates == H2MI_GATES_EXPRESSIONS (such lookups are a program: h2mi_prover_keygen_logup) or unknown; no lookups; a lookup's columns out
+ * of range; a count of 0 or above H2MI_MAX_LOGUP_INPUTS; counts that do not sum to cs->n_lookups (the struct states no length: the counts are read
+ * until they reach cs->n_lookups, and an argument that would pass the last entry is the violation); entries of one argument with different
+ * table_fixed; cs->degree below an argument's 2 + sum_j deg A_j + 1, deg A_j = 2 with a selector and 1 without; and, for an argument of
+ * SEVERAL entries, an entry with a selector or an advice column that another such argument (or the same one) reads already — the
+ * quotient takes the K inputs as consecutive vectors, which the prover arranges by placing those columns' cosets behind one another.
+ * degree_out (may be NULL): the largest required degree.  A permutation chunk of cs->degree - 2 columns may be longer than the three the
+ * shape's own kernels take.
+ * h2mi_prover_keygen_table_logup: flags H2MI_KEYGEN_VK_ONLY and H2MI_KEYGEN_LOGUP (implied) are accepted; H2MI_KEYGEN_BY_COSET and every
+ * other bit are H2MI_EINVAL.  Two arguments over one fixed column share one sorted table in the key.  A proof of this key is byte for
+ * byte the proof of the key h2mi_prover_keygen_logup makes from the same circuit written as programs (gates = H2MI_GATES_EXPRESSIONS with
+ * h2mi_shape_gate_program's program, one lookup per argument whose input polynomials are the entries' queries and whose table
+ * polynomial is the fixed query, the same counts, H2MI_KEYGEN_LOGUP), for the same seed and challenges.  h2mi_prover_lookups returns one
+ * [M] per argument and H2MI_EUNSAT for an input of any entry that is no table value; h2mi_prover_get_counts, h2mi_prover_buffer
+ * (H2MI_BUF_LOGUP_M / _PHI per argument), h2mi_prover_check (per argument: the absent (row, entry) pairs), both multi-openings and
+ * batches work as for any logUp key.  Beside a logUp key's M and phi a prover holds per argument 4 bytes per entry and row (the ranks)
+ * and 4 per distinct table value, and no compressed vector.  h2mi_prover_pk_export of such a key is H2MI_EINVAL: the blob format has no
+ * section for the grouping. */
+int h2mi_table_logup_check(const h2mi_constraint_system* cs, const h2mi_logup_inputs* sets, uint32_t* degree_out);
+int h2mi_prover_keygen_table_logup(const h2mi_constraint_system* cs, const h2mi_logup_inputs* sets_or_null, uint64_t g_lagrange_handle,
+                                   const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
 int h2mi_prover_pk_release(h2mi_pk_t pk); /* H2MI_EINVAL while a prover created against it is alive */
 /* VerifyingKey::{fixed_commitments, permutation.commitments}: affine points (8 limbs each); either pointer may be NULL */
 int h2mi_prover_vk_commitments(h2mi_pk_t pk, uint64_t* fixed_out /* n_fixed x 8 */, uint64_t* permutation_out /* n_perm x 8 */);
