@@ -46,6 +46,15 @@ int h2mi_dbg_g1_29_raw_op(int op, const uint32_t* a, const uint32_t* b, uint32_t
  * The pair-affine chain (f29t_pair_chain) has no device hook: no product kernel uses affine29_pair_add any more, so it stays a
  * host-only test of the header. */
 int h2mi_dbg_g1_29_chains(const uint32_t* pts, const uint8_t* signs, const uint64_t* offsets, size_t nchains, uint32_t* out_xyzz, int tree);
+/* What the general MSM pipeline left in a workspace slot (tests/test_gpu_msm_occupancy.py): the slot of the last MSM of `handle`
+ * (back = 0) or of the back-th one before it; the handle must have been registered with this library instance.  Flushes the deferred
+ * reductions and synchronises, as h2mi_msm_last_stats.  H2MI_EINVAL when the handle's last MSM took the small path (no bucket
+ * tables).  Two calls, like h2mi_profile_dump: data = NULL returns the size in *need_words, then data receives that many 32-bit words.
+ * geometry: c, W, nb, lb, nbins, logNl, logNh, seg_log, n, payload row stride, rows, has_sum, entries, slot, last MSM took the small
+ *           path, nseg (segments of wide windows, else 0).
+ * data, in this order: s0 [1]; off, np0, np1, toff0, toff1 [nb + 1 each]; the payloads in bucket order [entries]; shift [8, Montgomery];
+ *           dense [nb x 36]; dense2, vsum [nseg x 36 each].  A partial sum is 36 words: X, Y, ZZ, ZZZ as nine 29-bit limbs, Montgomery-2^261. */
+int h2mi_dbg_msm_snapshot(uint64_t handle, int back, uint64_t geometry[16], uint32_t* data, size_t cap_words, size_t* need_words);
 #ifdef __cplusplus
 }
 #endif

@@ -317,4 +317,36 @@ int h2mi_dbg_g1_29_chains(const uint32_t* pts, const uint8_t* signs, const uint6
   return H2MI_OK;
 }
 
+// The workspace of one of a handle's recent general-pipeline MSMs (h2::msm_debug_snapshot) copied to the host; the handle is one
+// registered with THIS library instance.  Layout: h2mi_hooks.h.
+int h2mi_dbg_msm_snapshot(uint64_t handle, int back, uint64_t geometry[16], uint32_t* data, size_t cap_words, size_t* need_words) {
+  H2_REQUIRE_INIT();
+  if (!geometry || (!data && !need_words)) return H2MI_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  MsmSnapshot m;
+  if (int rc = msm_debug_snapshot(handle, back, &m)) return rc;
+  if (m.last_small) return H2MI_EINVAL;  // the handle's last MSM took the small path: its slot holds no bucket tables to read
+  uint32_t entries = 0;
+  H2_HIP(hipMemcpy(&entries, m.off + m.nb, 4, hipMemcpyDeviceToHost));
+  if (entries > m.vals_cap) return H2MI_ERANGE;
+  const uint64_t g[16] = {m.c, m.W, m.nb, m.lb, m.nbins, m.logNl, m.logNh, m.seg_log, m.n, m.stride, m.rows, m.has_sum, entries, m.slot, m.last_small, m.nseg};
+  memcpy(geometry, g, sizeof g);
+  constexpr size_t PART_WORDS = 36;
+  const size_t tab = (size_t)m.nb + 1;
+  const struct { const void* src; size_t words; } parts[] = {
+      {m.s0_dev, 1}, {m.off, tab}, {m.np[0], tab}, {m.np[1], tab}, {m.toff[0], tab}, {m.toff[1], tab}, {m.vals1, entries}, {m.shift, 8},
+      {m.dense, (size_t)m.nb * PART_WORDS}, {m.dense2, (size_t)m.nseg * PART_WORDS}, {m.vsum, (size_t)m.nseg * PART_WORDS}};
+  size_t need = 0;
+  for (const auto& p : parts) need += p.words;
+  if (need_words) *need_words = need;
+  if (!data) return H2MI_OK;
+  if (cap_words < need) return H2MI_ERANGE;
+  size_t at = 0;
+  for (const auto& p : parts) {
+    if (p.words) H2_HIP(hipMemcpy(data + at, p.src, p.words * 4, hipMemcpyDeviceToHost));
+    at += p.words;
+  }
+  return H2MI_OK;
+}
+
 }  // extern "C"

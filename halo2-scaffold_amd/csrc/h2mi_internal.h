@@ -135,6 +135,27 @@ int launch_fold_groups(const uint8_t* pts, size_t world, size_t k, uint8_t* out,
 // h2mi_msm.hip: make `s` wait for all outstanding MSM tails
 int msm_join_all(hipStream_t s);
 int msm_flush_all();
+// h2mi_msm.hip, test hook only (csrc/h2mi_hooks.hip: h2mi_dbg_msm_snapshot): what the general pipeline left in the workspace slot of the
+// handle's last MSM (back = 0) or of the back-th MSM before it (the phase entry's batches take consecutive slots).  Flushes the
+// deferred reductions and synchronises the device, as h2mi_msm_last_stats does; host code only.  Geometry, then device pointers with
+// their lengths: 32-bit words unless stated, partial sums of PART = 144 bytes.
+struct MsmSnapshot {
+  uint32_t c, W, nb, lb, nbins, logNl, logNh, seg_log, rows, has_sum, slot, last_small;
+  uint64_t n, stride;             // registered points; payload row stride (n + 1: slot n of a row is the sum point)
+  const uint32_t* s0_dev;         // [1] chunk length of the accumulation
+  const uint32_t* off;            // [nb + 1] first entry of each bucket, [nb] = entries
+  const uint32_t* np[2];          // [nb + 1] partials the accumulation leaves per bucket, fold tasks
+  const uint32_t* toff[2];        // [nb + 1] their exclusive scans, [nb] = totals
+  const uint32_t* vals1;          // [vals_cap] payloads in bucket order; off[nb] of them are this MSM's
+  uint64_t vals_cap;              // stride * rows
+  const uint8_t* dense;           // [nb] bucket sums
+  const uint8_t *dense2, *vsum;   // wide windows: [nseg] plain and local weighted segment sums; else null
+  uint64_t nseg;                  // 2^16 for wide windows, else 0
+  const uint32_t* shift;          // [8] the dominant value this slot's last shifted MSM subtracted (Montgomery)
+};
+// Hidden: libh2mi.so does not export it, and the hook's call binds to the copy inside libh2mi_hooks.so (whose handles it knows) even
+// when the product library is loaded beside it with global symbols.
+__attribute__((visibility("hidden"))) int msm_debug_snapshot(uint64_t handle, int back, MsmSnapshot* out);
 // per-module teardown hooks of h2mi_shutdown (device memory, events and cached tables of the devices being released)
 void msm_teardown();
 void ntt_teardown();

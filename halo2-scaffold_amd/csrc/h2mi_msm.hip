@@ -2332,6 +2332,32 @@ int msm_join_all(hipStream_t s) {
   return H2MI_OK;
 }
 
+// Test hook (h2mi_internal.h): the workspace of one of the handle's recent MSMs, for tests/test_gpu_msm_occupancy.py.  Host code
+// only: no kernel, no launch and no buffer exists for it.
+int msm_debug_snapshot(uint64_t handle, int back, MsmSnapshot* out) {
+  if (!out) return H2MI_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  auto it = g_bases.find(handle);
+  if (it == g_bases.end()) return H2MI_EHANDLE;
+  const Bases* B = it->second;
+  if (back < 0 || back >= B->nslot) return H2MI_ERANGE;
+  if (int rc = flush_tails()) return rc;
+  H2_HIP(hipDeviceSynchronize());
+  const int si = (B->last_slot + B->nslot - back) % B->nslot;
+  const Slot& S = B->slot[si];
+  MsmSnapshot m = {};
+  m.c = B->c; m.W = B->W; m.nb = B->nb; m.lb = B->lb; m.nbins = B->nbins; m.logNl = B->logNl; m.logNh = B->logNh; m.seg_log = B->seg_log;
+  m.rows = B->rows; m.has_sum = B->has_sum ? 1u : 0u; m.slot = (uint32_t)si; m.last_small = B->last_small ? 1u : 0u;
+  m.n = B->n; m.stride = B->stride;
+  m.s0_dev = S.s0_dev; m.off = S.off;
+  for (int i = 0; i < 2; i++) { m.np[i] = S.np[i]; m.toff[i] = S.toff[i]; }
+  m.vals1 = S.vals[1]; m.vals_cap = (uint64_t)B->stride * B->rows;
+  m.dense = S.dense; m.dense2 = S.dense2; m.vsum = S.vsum; m.nseg = B->seg_log ? (uint64_t)1 << MAT_LOG : 0;
+  m.shift = reinterpret_cast<const uint32_t*>(S.shift);
+  *out = m;
+  return H2MI_OK;
+}
+
 }  // namespace h2
 
 using namespace h2;

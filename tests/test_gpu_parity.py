@@ -591,14 +591,24 @@ def test_msm_vs_c_oracle_large(gpu):
 
 
 def test_msm_hot_buckets_large(gpu):
-    """2^16 points whose scalars fall into a handful of buckets: one partition bin receives everything (many
-    chunks through the per-bin sort), accumulation chunks never or rarely cross a bucket boundary, and the
-    fold level carries thousands of partial sums per bucket (both its lane and quad forms are reached through
-    the two sizes).  Against the C restatement of best_multiexp."""
-    from oracle import cref
+    """Scalars that fall into a handful of buckets, at two sizes, against the C restatement of best_multiexp.  2^16 points take the
+    general pipeline: one partition bin receives everything (many chunks through the per-bin sort), accumulation chunks never or
+    rarely cross a bucket boundary, and the fold level carries thousands of partial sums per bucket.  2^12 points are a small base
+    set: the commitment takes the small path (k_msm_small_*: no buckets at all; the general pipeline when H2MI_MSM_C forces a window
+    width), so the same four columns are run again through the general pipeline with H2MI_MSM_GENERAL, where 15-bit windows over 4096
+    points leave hot buckets of up to 4096 entries.  The route
+    of every call is read from the launch profile.  (The bucket pipeline at chosen occupancies, stage by stage:
+    tests/test_gpu_msm_occupancy.py.)"""
+    import ctypes as C
 
+    from oracle import cref
+    from test_gpu_msm_schedule import MSM_GENERAL, Profile
+    import msm_schedule_cases as S
+
+    lib = gpu.lib
     for k in (16, 12):
         n = 1 << k
+        small = k == 12 and "H2MI_MSM_C" not in os.environ  # a forced window width (test_msm_wide_windows_forced_at_small_sizes) registers without the small path's table
         params = gpu.ParamsKZG.setup(k, 0xFEED + k)
         bases = params.get_g()
         rng = np.random.default_rng(k)
@@ -608,9 +618,25 @@ def test_msm_hot_buckets_large(gpu):
             "small digits": [int(v) for v in rng.integers(0, 8, n)],
             "one window only": [int(v) << 48 for v in rng.integers(1, 1 << 16, n)],
         }
+        d_sc, d_out = gpu.DevBuf(n * 32), gpu.DevBuf(96)
+        assert lib.h2mi_sync() == 0
         for name, vals in cases.items():
             sc = o.pack(vals, o.R)
-            assert np.array_equal(cref.normalize(params.commit(sc)), cref.normalize(cref.msm(sc, bases, 8))), (k, name)
+            want = cref.normalize(cref.msm(sc, bases, 8))
+            with Profile(lib) as prof:
+                got = params.commit(sc)
+            assert np.array_equal(cref.normalize(got), want), (k, name)
+            assert prof.heads == [S.SMALL if small else S.GENERAL], (k, name, "the route of the commitment")
+            if k == 12:
+                d_sc.upload(sc)
+                ptr = (C.c_void_p * 1)(d_sc.ptr)
+                with Profile(lib) as prof:
+                    assert lib.h2mi_msm_bn254_g1_phase_dev(params.g_handle, ptr, 1, n, d_out.ptr, MSM_GENERAL, None) == 0
+                    got = d_out.to_numpy(shape=(12,))
+                assert np.array_equal(cref.normalize(got), want), (k, name, "H2MI_MSM_GENERAL")
+                assert prof.heads == [S.GENERAL] and prof.census[S.ACCUM] == 1 and prof.census[S.FINAL] == 1, (k, name, "the route under H2MI_MSM_GENERAL")
+        d_sc.free()
+        d_out.free()
         params.release()
 
 
