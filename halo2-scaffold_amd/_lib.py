@@ -88,6 +88,13 @@ def _load():
         "h2mi_fr_scatter_cells_staged_dev": ([vp, C.c_uint32, C.c_uint64, u64p, vp], C.c_int),
         # the inverse: device columns -> their nonzero cells in row order (count, prefix, ordered scatter; no atomic)
         "h2mi_fr_compact_cells_dev": ([vp, C.c_uint32, C.c_uint, vp, vp, vp], C.c_int),
+        # witness programs: a recorded builder closure evaluated on the device (csrc/h2mi_witness.hip)
+        "h2mi_witness_check": ([vp], C.c_int),
+        "h2mi_witness_create": ([vp, C.POINTER(vp)], C.c_int),
+        "h2mi_witness_info": ([vp, vp], C.c_int),
+        "h2mi_witness_run": ([vp, vp, vp, C.POINTER(C.c_uint32)], C.c_int),
+        "h2mi_witness_read": ([vp, vp, C.c_uint32, vp], C.c_int),
+        "h2mi_witness_release": ([vp], C.c_int),
         "h2mi_fr_random_dev": ([vp, sz, C.c_uint64, C.c_uint64, vp], C.c_int),
         "h2mi_fr_random_chacha_dev": ([vp, sz, vp, C.c_uint64, C.c_uint64, vp], C.c_int),
         "h2mi_ntt_bn254_fr": ([vp, vp, C.c_uint32], C.c_int),

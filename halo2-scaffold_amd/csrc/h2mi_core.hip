@@ -235,6 +235,7 @@ void h2mi_shutdown(void) {
   use_device(0);
   ntt_teardown();     // plans, power tables, scratch vectors (primary device)
   lookup_teardown();  // counting-sort scratch and its event
+  witness_teardown(); // the witness programs still alive
   if (g_fixed_table) { H2_IGNORE(hipFree(g_fixed_table)); g_fixed_table = nullptr; g_fixed_built.destroy(); }
   for (hipEvent_t& ev : g_wait_ring)
     if (ev) { H2_IGNORE(hipEventDestroy(ev)); ev = nullptr; }

@@ -160,6 +160,7 @@ __attribute__((visibility("hidden"))) int msm_debug_snapshot(uint64_t handle, in
 void msm_teardown();
 void ntt_teardown();
 void lookup_teardown();
+void witness_teardown();
 
 // The environment variables the library reads, each a plain getenv: H2MI_VERBOSE, H2MI_VIRTUAL_DEVICES, H2MI_MSM_C /
 // H2MI_MSM_S0 / H2MI_MSM_NO_PIPELINE (forced-path parity tests) and H2MI_POWTAB_MAX.  No tuning variable is read.

@@ -414,6 +414,88 @@ class DeviceCells:
         keep.append(self)
 
 
+class WitnessDesc(C.Structure):
+    """h2mi_witness_desc (include/h2mi.h): a witness program as data — ops sorted by level, constants, checks, the placement"""
+    _fields_ = [("ops", C.c_void_p), ("level_ends", C.c_void_p), ("constants", C.c_void_p), ("checks", C.c_void_p), ("placement", C.c_void_p),
+                ("counts", C.c_void_p), ("n_ops", C.c_uint32), ("n_levels", C.c_uint32), ("n_constants", C.c_uint32), ("n_inputs", C.c_uint32),
+                ("n_checks", C.c_uint32), ("n_columns", C.c_uint32)]
+
+    @classmethod
+    def build(cls, ops, level_ends, constants, n_inputs, checks, placement) -> "WitnessDesc":
+        """ops: (n, 4) uint32 rows (dst, kind | bits << 8 | shift << 16, a, b); constants: integers (canonical limbs cross as they are:
+        the check refuses one not below r); checks: [(a, b)]; placement: one sequence of cell indices per column.  The arrays stay alive
+        with the object."""
+        d = cls()
+        limbs = lambda v: [(int(v) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+        d._keep = [np.ascontiguousarray(np.asarray(ops, dtype=np.uint32).reshape(-1, 4)), np.ascontiguousarray(level_ends, dtype=np.uint32),
+                   np.array([limbs(c) for c in constants], dtype=np.uint64).reshape(-1, 4), np.array(checks, dtype=np.uint32).reshape(-1, 2),
+                   np.concatenate([np.asarray(p, dtype=np.uint32) for p in placement] + [np.zeros(0, dtype=np.uint32)]),
+                   np.array([len(p) for p in placement], dtype=np.uint32)]
+        d.ops, d.level_ends, d.constants, d.checks, d.placement, d.counts = (a.ctypes.data if a.size else None for a in d._keep)
+        d.n_ops, d.n_levels, d.n_constants, d.n_inputs = len(d._keep[0]), len(d._keep[1]), len(d._keep[2]), n_inputs
+        d.n_checks, d.n_columns = len(d._keep[3]), len(d._keep[5])
+        return d
+
+    def check(self) -> None:
+        """h2mi_witness_check (host only, works without a GPU); H2miError(-1 / -6) for a program h2mi_witness_create would refuse"""
+        check(lib.h2mi_witness_check(C.byref(self)), "witness_check")
+
+
+class WitnessInfo(C.Structure):
+    """h2mi_witness_info_t"""
+    _fields_ = [("n_cells", C.c_uint32), ("n_levels", C.c_uint32), ("n_grid_launches", C.c_uint32), ("n_wg_launches", C.c_uint32),
+                ("device_bytes", C.c_uint64)]
+
+
+class WitnessProgram:
+    """one h2mi_witness_t: a witness program in HBM.  run(inputs) evaluates it and returns its dense Montgomery columns as DeviceCells
+    (they belong to the program: valid until its next run or its release — the advice call that follows has consumed them when it
+    returns); read(cells) the canonical values of cells after a run (the public inputs).  A failed check raises ValueError("witness
+    out of range ...") naming the lowest failing check; the program and every prover stay usable."""
+
+    def __init__(self, desc: WitnessDesc):
+        h = C.c_void_p()
+        check(lib.h2mi_witness_create(C.byref(desc), C.byref(h)), "witness_create")
+        self.handle = h.value
+        self.n_inputs, self.counts = desc.n_inputs, [int(c) for c in desc._keep[5]]
+        self.checks = desc._keep[3].copy()
+        self._columns = (C.c_void_p * max(len(self.counts), 1))()
+
+    @property
+    def info(self) -> WitnessInfo:
+        out = WitnessInfo()
+        check(lib.h2mi_witness_info(self.handle, C.byref(out)), "witness_info")
+        return out
+
+    def run(self, inputs) -> list:
+        """inputs: n_inputs integers below r -> [DeviceCells(address, count=count_j)]"""
+        if len(inputs) != self.n_inputs:
+            raise ValueError(f"the program takes {self.n_inputs} inputs, not {len(inputs)}")
+        try:
+            raw = np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in inputs), dtype=np.uint64)
+        except OverflowError:
+            raise ValueError("an input is not reduced modulo r")
+        failed = C.c_uint32()
+        rc = lib.h2mi_witness_run(self.handle, raw.ctypes.data if len(inputs) else None, self._columns, C.byref(failed))
+        if rc == EUNSAT:
+            a, b = self.checks[failed.value]
+            raise ValueError(f"witness out of range: check {failed.value} fails, cells {a} and {b} differ")
+        check(rc, "witness_run")
+        return [DeviceCells(self._columns[j] or 0, count=n) for j, n in enumerate(self.counts)]
+
+    def read(self, cells) -> list:
+        """the canonical values of the listed cells of the last run"""
+        idx = np.ascontiguousarray(cells, dtype=np.uint32)
+        out = np.zeros((max(len(idx), 1), 4), dtype=np.uint64)
+        check(lib.h2mi_witness_read(self.handle, idx.ctypes.data if len(idx) else None, len(idx), out.ctypes.data), "witness_read")
+        return [int.from_bytes(out[i].tobytes(), "little") for i in range(len(idx))]
+
+    def release(self):
+        if self.handle:
+            check(lib.h2mi_witness_release(self.handle), "witness_release")
+            self.handle = None
+
+
 CELLS_FOR_ADVICE, CELLS_FOR_INSTANCE, CELLS_FOR_FIXED = 0, 1, 2  # h2mi_column_cells_check's `where`
 
 
@@ -1058,4 +1140,4 @@ class Batch:
                     check(lib.h2mi_prover_get_counts(p.handle, C.byref(p.counts)), "prover counts")
 
 
-__all__ = ["ConstraintSystem", "Keys", "Prover", "Batch", "DevView", "H2miError", "ShuffleProgram", "IntCells", "DeviceCells"]
+__all__ = ["ConstraintSystem", "Keys", "Prover", "Batch", "DevView", "H2miError", "ShuffleProgram", "IntCells", "DeviceCells", "WitnessProgram"]

@@ -12,11 +12,13 @@ public inputs; blinding comes from a fresh 256-bit key per prover (`h2mi_prover_
 table raises ValueError from the prover (ConstraintSystemFailure), "LOOKUP_BITS needs to be less than DEGREE" is asserted as there.
 Added: `mock_device(f, private_inputs, pk)` — `mock` against a key `gen_key` made, on the device (flex.check): at DEGREE 20 - 22 the
 prover says nothing about an unsatisfied gate or copy constraint, and its proof would be accepted by no verifier.
+Added: `gen_key(..., witness_program=True)` records the closure's run as a witness program (witness.py); `prove_private` and
+`mock_device` on such a key evaluate it on the device and do not call the closure.
 """
 import json
 import os
 
-from . import flex
+from . import flex, witness
 from .params import gen_srs
 
 
@@ -61,6 +63,7 @@ class ProvingKey:
         self.workspace.prover.set_rng_key(os.urandom(32))  # the reference passes OsRng
         self.proofs = 0
         self.last_proof = None
+        self.program = None  # gen_key(..., witness_program=True): the closure as a witness.Program
 
     @property
     def cs(self):
@@ -70,12 +73,15 @@ class ProvingKey:
         return self.keys
 
     def release(self):
+        if self.program is not None:
+            self.program.release()
         self.workspace.release()
         self.keys.release()
         self.params.release()
 
 
-def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1, key_file=None, logup: bool = False, lookup_sets=None):
+def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1, key_file=None, logup: bool = False, lookup_sets=None,
+            witness_program: bool = False):
     """src/scaffold.rs:95-156: the circuit's shape from a run on dummy inputs (GateThreadBuilder::keygen + builder.config), the SRS
     from gen_srs(k), keygen_vk + keygen_pk -> (pk, break_points).  by_coset: flex.FlexKeys' (no extended-coset columns on the device);
     table_depth: ParamsKZG's (every table_depth-th row of the MSM tables, as many passes per commitment).
@@ -84,9 +90,14 @@ def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1, key_f
     argument and written there, the break points and LOOKUP_BITS as JSON in the file's user section (a file made under another
     LOOKUP_BITS is refused with ValueError, as one made for another DEGREE is).  None: nothing is read or written.
     logup / lookup_sets: flex.FlexKeys' (the range checks proven by logUp against the key's sorted table, lookup_sets lookup-advice
-    columns per argument).  Such a key has no file form: together with key_file it is a ValueError."""
+    columns per argument).  Such a key has no file form: together with key_file it is a ValueError.
+    witness_program: the run on the dummy inputs is recorded (witness.Program.record) and kept as pk.program; prove_private and
+    mock_device on such a key do not call the closure again: they run the program on the device.  A closure a tape cannot express is
+    refused here with ValueError.  The tape is not part of the key file: together with key_file it is a ValueError."""
     if logup and key_file is not None:
         raise ValueError("key_file with logup=True: the key-file format has no section for a logUp key of the builders' lookups")
+    if witness_program and key_file is not None:
+        raise ValueError("key_file with witness_program=True: the witness program is not part of the key file")
     k, lookup_bits, minimum_rows = _env()
     if key_file is not None and os.path.exists(key_file):
         params = gen_srs(k, table_depth=table_depth)
@@ -104,14 +115,30 @@ def gen_key(f, dummy_inputs, by_coset: bool = False, table_depth: int = 1, key_f
         pk.lookup_bits = lookup_bits
         return pk, stored["break_points"]
     cs = _config(f, dummy_inputs, k, lookup_bits, minimum_rows)
-    asg = _synthesize(f, dummy_inputs, cs, lookup_bits)
+    program = None
+    if witness_program:
+        program, asg = witness.Program.record(f, dummy_inputs, cs, lookup_bits)
+    else:
+        asg = _synthesize(f, dummy_inputs, cs, lookup_bits)
     params = gen_srs(k, table_depth=table_depth)
     pk = ProvingKey(params, flex.FlexKeys(params, cs, asg, by_coset=by_coset, logup=logup, lookup_sets=lookup_sets))
     pk.lookup_bits = lookup_bits
+    pk.program = program
     break_points = [list(asg.break_points)]
     if key_file is not None:
         pk.keys.save(key_file, json.dumps({"break_points": break_points, "lookup_bits": lookup_bits}).encode())
     return pk, break_points
+
+
+def _witness(f, private_inputs, pk: ProvingKey, lookup_bits):
+    """the witness of the private inputs: the closure run on the host, or — a key made with witness_program=True — its program run on the
+    device without calling the closure (witness.assignment: columns in HBM, the public cells read back; ValueError("witness out of
+    range ...") for a failed check, before anything is committed)"""
+    if pk.program is None:
+        return _synthesize(f, private_inputs, pk.cs, lookup_bits)
+    asg = witness.assignment(pk.program, private_inputs)
+    asg.break_points = list(pk.program.break_points)
+    return asg
 
 
 def prove_private(f, private_inputs, pk: ProvingKey, break_points, logup: bool = False, lookup_sets=None):
@@ -126,7 +153,7 @@ def prove_private(f, private_inputs, pk: ProvingKey, break_points, logup: bool =
     if not same:
         raise ValueError("prove_private: logup / lookup_sets are not the ones the key was generated with")
     _, lookup_bits, _ = _env()
-    asg = _synthesize(f, private_inputs, pk.cs, lookup_bits)
+    asg = _witness(f, private_inputs, pk, lookup_bits)
     if [list(asg.break_points)] != [list(b) for b in break_points]:
         raise ValueError("the circuit's break points differ from the ones stored at keygen: the closure's shape depends on its inputs")
     pk.proofs += 1
@@ -139,15 +166,18 @@ def mock_device(f, private_inputs, pk: ProvingKey):
     gates, copy constraints, lookups; ValueError naming the first violation) -> the public inputs.  No proof is made and none is
     verified; the advice commitments of the proof the check rides on are paid, and the nonce it takes is not used again."""
     _, lookup_bits, _ = _env()
-    asg = _synthesize(f, private_inputs, pk.cs, lookup_bits)
+    asg = _witness(f, private_inputs, pk, lookup_bits)
     pk.proofs += 1
     flex.check(pk.params, pk.keys, asg, pk.proofs, ws=pk.workspace)
     return list(asg.instance)
 
 
-def prove(f, private_inputs, dummy_inputs, by_coset: bool = False, table_depth: int = 1, logup: bool = False, lookup_sets=None):
-    """src/scaffold.rs:246-366: keygen on dummy inputs, then one proof of the private inputs -> (proof bytes, public inputs)"""
-    pk, break_points = gen_key(f, dummy_inputs, by_coset=by_coset, table_depth=table_depth, logup=logup, lookup_sets=lookup_sets)
+def prove(f, private_inputs, dummy_inputs, by_coset: bool = False, table_depth: int = 1, logup: bool = False, lookup_sets=None,
+          witness_program: bool = False):
+    """src/scaffold.rs:246-366: keygen on dummy inputs, then one proof of the private inputs -> (proof bytes, public inputs).
+    witness_program: gen_key's (the proof's witness comes from the recorded program, on the device)"""
+    pk, break_points = gen_key(f, dummy_inputs, by_coset=by_coset, table_depth=table_depth, logup=logup, lookup_sets=lookup_sets,
+                               witness_program=witness_program)
     try:
         public_io = prove_private(f, private_inputs, pk, break_points, logup=logup)
         return pk.last_proof, public_io

@@ -373,6 +373,73 @@ typedef struct {
 typedef void* (*h2mi_compact_alloc_fn)(void* ctx, size_t bytes);
 int h2mi_fr_compact_cells_dev(h2mi_cells_compacted* cols, uint32_t n_cols, unsigned flags, h2mi_compact_alloc_fn alloc, void* alloc_ctx,
                               h2mi_stream_t stream);
+/* Witness programs: a builder closure whose shape does not depend on its inputs is a fixed straight-line program over field elements.
+ * Recorded once (the Python recorder is halo2-scaffold_amd/witness.py), it is evaluated on the device for every proof and its cells land
+ * in dense Montgomery columns that h2mi_prover_advice takes as H2MI_CELLS_DEVICE (h2mi_prover.h) — no cell crosses the host.
+ * The program describes a flat list of n_ops cells, one op per cell: op = (dst, kind | bits << 8 | shift << 16, a, b), 16 bytes.
+ *   H2MI_WITNESS_INPUT  cells[dst] = inputs[a]          (h2mi_witness_run's inputs: canonical, below r)
+ *   H2MI_WITNESS_CONST  cells[dst] = constants[a]       (canonical, below r)
+ *   H2MI_WITNESS_COPY   cells[dst] = cells[a]
+ *   H2MI_WITNESS_GATE   cells[dst] = cells[dst - 3] + cells[dst - 2] * cells[dst - 1]      (the fourth cell of a vertical gate)
+ *   H2MI_WITNESS_LIMB   cells[dst] = (canonical(cells[a]) >> shift) & (2^bits - 1), 1 <= bits <= 64, shift + bits <= 254
+ * Levels: ops[level_ends[l - 1] .. level_ends[l]) are level l (level_ends[-1] = 0, no level is empty, the last one ends at n_ops); an op
+ * reads only cells written at strictly lower levels.  checks: n_checks pairs (a, b) of cells that must hold equal values (the
+ * equalities no COPY makes true, such as range_check's constrain_equal of the value with its recomposed limbs).  Placement: column j of
+ * the n_columns dense output columns is cells[placement[start_j + row]] for row < counts[j], start_j = counts[0] + .. + counts[j - 1].
+ * Launches (the rule is part of the interface): a level of more than H2MI_WITNESS_WG_OPS ops is one k_witness_level launch; every
+ * maximal run of consecutive levels of at most H2MI_WITNESS_WG_OPS ops is a sequence of k_witness_levels_wg launches — ONE workgroup,
+ * a barrier between levels — of at most H2MI_WITNESS_WG_LEVELS levels each; one k_witness_place launch gathers the columns and
+ * evaluates the checks.
+ * h2mi_witness_check (host only, works without a GPU; h2mi_witness_create applies it first): H2MI_EINVAL for an unknown kind, a dst
+ * named twice or never, an operand whose level is not strictly below its reader's, level_ends that do not ascend to n_ops, a GATE with
+ * dst < 3, shift / bits outside their bounds, an INPUT or CONST index out of range, a constant not below r, a placement source or a
+ * check index >= n_ops, a null array with a nonzero count; H2MI_ERANGE for more than 2^28 cells, more than 2^28 cells in one column or
+ * more than H2MI_WITNESS_MAX_COLUMNS columns.
+ * h2mi_witness_create uploads the program once and allocates the cells and column buffers (H2MI_EINVAL with more than one device
+ * under h2mi_init_devices, as for H2MI_CELLS_DEVICE).  h2mi_witness_run takes n_inputs x 4 canonical limbs (host memory; H2MI_EINVAL
+ * for one not below r), enqueues everything on the library's stream, and returns in d_columns_out the n_columns device addresses of the
+ * columns: they belong to the program and stay valid until its next run or its release; an advice call that follows is ordered behind
+ * the run on the same stream and has consumed them when it returns.  The run ends with one small transfer of the check status: a
+ * failed check is H2MI_EUNSAT with the lowest failing check index in *first_failed_check (0xffffffff otherwise), and the columns of
+ * such a run are not to be used.  h2mi_witness_read: the canonical values (n x 4 limbs) of the listed cells after a run — the public
+ * inputs are read this way. */
+#define H2MI_WITNESS_INPUT 0u
+#define H2MI_WITNESS_CONST 1u
+#define H2MI_WITNESS_COPY 2u
+#define H2MI_WITNESS_GATE 3u
+#define H2MI_WITNESS_LIMB 4u
+#define H2MI_WITNESS_WG_OPS 1024u    /* the workgroup limit */
+#define H2MI_WITNESS_WG_LEVELS 4096u /* keeps any one kernel short whatever the circuit's depth */
+#define H2MI_WITNESS_MAX_COLUMNS 64u /* = H2MI_MAX_ADVICE of h2mi_prover.h */
+typedef struct { uint32_t dst; uint32_t code; uint32_t a; uint32_t b; } h2mi_witness_op;
+typedef struct {
+  const h2mi_witness_op* ops;
+  const uint32_t* level_ends;
+  const uint64_t* constants;  /* n_constants x 4 canonical limbs */
+  const uint32_t* checks;     /* n_checks pairs */
+  const uint32_t* placement;  /* counts[0] + .. + counts[n_columns - 1] cell indices */
+  const uint32_t* counts;
+  uint32_t n_ops;             /* = the number of cells */
+  uint32_t n_levels;
+  uint32_t n_constants;
+  uint32_t n_inputs;
+  uint32_t n_checks;
+  uint32_t n_columns;
+} h2mi_witness_desc;
+typedef struct {
+  uint32_t n_cells;
+  uint32_t n_levels;
+  uint32_t n_grid_launches; /* k_witness_level launches of one run */
+  uint32_t n_wg_launches;   /* k_witness_levels_wg launches of one run */
+  uint64_t device_bytes;    /* held by the program: ops, cells, columns, placement, checks, constants, inputs */
+} h2mi_witness_info_t;
+typedef void* h2mi_witness_t;
+int h2mi_witness_check(const h2mi_witness_desc* d);
+int h2mi_witness_create(const h2mi_witness_desc* d, h2mi_witness_t* out);
+int h2mi_witness_info(h2mi_witness_t w, h2mi_witness_info_t* out);
+int h2mi_witness_run(h2mi_witness_t w, const uint64_t* inputs, void** d_columns_out, uint32_t* first_failed_check);
+int h2mi_witness_read(h2mi_witness_t w, const uint32_t* cells, uint32_t n, uint64_t* out);
+int h2mi_witness_release(h2mi_witness_t w);
 /* out[i] = value for i < n (Lagrange vectors such as l_active of keygen_pk) */
 int h2mi_fr_fill_dev(void* d_out, size_t n, const uint64_t value[4], h2mi_stream_t stream);
 /* Seeded stand-in for the prover's sweeps of `Scalar::random(rng)` (blinding rows; the vanishing argument's random
