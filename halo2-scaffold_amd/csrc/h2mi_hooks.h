@@ -55,6 +55,18 @@ int h2mi_dbg_g1_29_chains(const uint32_t* pts, const uint8_t* signs, const uint6
  * data, in this order: s0 [1]; off, np0, np1, toff0, toff1 [nb + 1 each]; the payloads in bucket order [entries]; shift [8, Montgomery];
  *           dense [nb x 36]; dense2, vsum [nseg x 36 each].  A partial sum is 36 words: X, Y, ZZ, ZZZ as nine 29-bit limbs, Montgomery-2^261. */
 int h2mi_dbg_msm_snapshot(uint64_t handle, int back, uint64_t geometry[16], uint32_t* data, size_t cap_words, size_t* need_words);
+/* The same for a small-path MSM (tests/test_gpu_msm_small.py).  H2MI_EINVAL when the slot's last MSM did not take the small path.
+ * Two calls as above, sizes in bytes.
+ * geometry: c, W, gathering lanes per workgroup, cells per lane, workgroups of a full-length MSM (sG), registered points, points of
+ *           this MSM, its workgroups G, slot; the rest 0.
+ * data, in this order: the entries each workgroup added [sG + 1 words, the last one the arrival counter; beyond G: what earlier MSMs
+ *           left]; the partial sums [G x 144 bytes: 36 words as above]; the digit bytes sign << 7 | magnitude [W][registered points]
+ *           (columns beyond this MSM's points: what earlier MSMs left). */
+int h2mi_dbg_msm_small_snapshot(uint64_t handle, int back, uint64_t geometry[16], uint8_t* data, size_t cap_bytes, size_t* need_bytes);
+/* `count` chosen entries of the digit-multiples table of a handle whose last MSM took the small path: entry ((j - 1) W + w) n + i is
+ * the affine point j 2^(c w) P_i, j = 1 .. 2^(c-1), as 16 canonical Montgomery-2^261 words (x, y), all zeros for the identity.
+ * H2MI_ERANGE for an entry beyond the table. */
+int h2mi_dbg_msm_small_table(uint64_t handle, const uint64_t* entries, size_t count, uint32_t* out);
 #ifdef __cplusplus
 }
 #endif

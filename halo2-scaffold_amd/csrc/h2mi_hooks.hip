@@ -349,4 +349,44 @@ int h2mi_dbg_msm_snapshot(uint64_t handle, int back, uint64_t geometry[16], uint
   return H2MI_OK;
 }
 
+// What a small-path MSM left in its workspace slot (h2::msm_debug_small_snapshot) copied to the host.  Layout: h2mi_hooks.h.
+int h2mi_dbg_msm_small_snapshot(uint64_t handle, int back, uint64_t geometry[16], uint8_t* data, size_t cap_bytes, size_t* need_bytes) {
+  H2_REQUIRE_INIT();
+  if (!geometry || (!data && !need_bytes)) return H2MI_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  MsmSmallSnapshot m;
+  if (int rc = msm_debug_small_snapshot(handle, back, &m)) return rc;
+  if (m.G > m.sG || m.small_n > m.n_reg) return H2MI_ERANGE;
+  const uint64_t g[16] = {m.sc, m.sW, m.slanes, m.sr, m.sG, m.n_reg, m.small_n, m.G, m.slot};
+  memcpy(geometry, g, sizeof g);
+  constexpr size_t PART = 144;
+  const struct { const void* src; size_t bytes; } parts[] = {
+      {m.scnt, ((size_t)m.sG + 1) * 4}, {m.spart, (size_t)m.G * PART}, {m.sdig, (size_t)m.sW * m.n_reg}};
+  size_t need = 0;
+  for (const auto& p : parts) need += p.bytes;
+  if (need_bytes) *need_bytes = need;
+  if (!data) return H2MI_OK;
+  if (cap_bytes < need) return H2MI_ERANGE;
+  size_t at = 0;
+  for (const auto& p : parts) {
+    if (p.bytes) H2_HIP(hipMemcpy(data + at, p.src, p.bytes, hipMemcpyDeviceToHost));
+    at += p.bytes;
+  }
+  return H2MI_OK;
+}
+
+// Chosen entries of the handle's digit-multiples table: entry ((j - 1) W + w) n_reg + i is j 2^(c w) P_i.
+int h2mi_dbg_msm_small_table(uint64_t handle, const uint64_t* entries, size_t count, uint32_t* out) {
+  H2_REQUIRE_INIT();
+  if (!entries || !out) return H2MI_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  MsmSmallSnapshot m;
+  if (int rc = msm_debug_small_snapshot(handle, 0, &m)) return rc;
+  const uint64_t total = ((uint64_t)1 << (m.sc - 1)) * m.sW * m.n_reg;
+  for (size_t k = 0; k < count; k++)
+    if (entries[k] >= total) return H2MI_ERANGE;
+  for (size_t k = 0; k < count; k++) H2_HIP(hipMemcpy(out + 16 * k, m.stable + entries[k] * 64, 64, hipMemcpyDeviceToHost));
+  return H2MI_OK;
+}
+
 }  // extern "C"

@@ -156,6 +156,17 @@ struct MsmSnapshot {
 // Hidden: libh2mi.so does not export it, and the hook's call binds to the copy inside libh2mi_hooks.so (whose handles it knows) even
 // when the product library is loaded beside it with global symbols.
 __attribute__((visibility("hidden"))) int msm_debug_snapshot(uint64_t handle, int back, MsmSnapshot* out);
+// The same for the small path (h2mi_dbg_msm_small_snapshot, h2mi_dbg_msm_small_table): geometry of the base set and of the slot's
+// MSM, then device pointers.  H2MI_EINVAL when the slot's last MSM did not take the small path.  Host code only.
+struct MsmSmallSnapshot {
+  uint32_t sc, sW, slanes, sr, sG, small_n, G, slot;  // G = workgroups (partial sums) of this MSM over small_n <= n_reg points
+  uint64_t n_reg;
+  const uint8_t* sdig;    // [sW][n_reg] digit bytes, sign << 7 | magnitude
+  const uint32_t* scnt;   // [sG + 1] entries per workgroup, [sG] = the arrival counter
+  const uint8_t* spart;   // [sG] partial sums, G of them this MSM's
+  const uint8_t* stable;  // [2^(sc-1)][sW][n_reg] affine multiples, 64 bytes each
+};
+__attribute__((visibility("hidden"))) int msm_debug_small_snapshot(uint64_t handle, int back, MsmSmallSnapshot* out);
 // per-module teardown hooks of h2mi_shutdown (device memory, events and cached tables of the devices being released)
 void msm_teardown();
 void ntt_teardown();

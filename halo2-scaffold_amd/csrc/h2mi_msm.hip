@@ -119,7 +119,7 @@ struct Slot {
   uint8_t* spart = nullptr;
   uint32_t* scnt = nullptr;
   bool small_deferred = false;  // the deferred work of this slot is the small path's accumulate + final pair
-  uint32_t small_n = 0;         // points of that MSM
+  uint32_t small_n = 0;         // points of the slot's last MSM if it took the small path, else 0
 
   hipError_t create_events() {
     for (Stage* st : {&input_ready, &head, &accum, &tail})
@@ -1873,6 +1873,7 @@ static int msm_general(Bases* B, const void* const* d_scalars, size_t m, size_t 
     S.last_stream = s;
     S.d_out = (char*)d_out + 96 * j;
     S.tasks1 = tasks0 / S1 + nb;  // the reduction's fold grid bound
+    S.small_n = 0;                // the slot's last MSM is not a small one (msm_debug_small_snapshot)
     work[j] = {B, &S};
     if (batch) {
       HeadDesc& d = hb.d[j];
@@ -2354,6 +2355,28 @@ int msm_debug_snapshot(uint64_t handle, int back, MsmSnapshot* out) {
   m.vals1 = S.vals[1]; m.vals_cap = (uint64_t)B->stride * B->rows;
   m.dense = S.dense; m.dense2 = S.dense2; m.vsum = S.vsum; m.nseg = B->seg_log ? (uint64_t)1 << MAT_LOG : 0;
   m.shift = reinterpret_cast<const uint32_t*>(S.shift);
+  *out = m;
+  return H2MI_OK;
+}
+
+// The same for the small path, for tests/test_gpu_msm_small.py: host code only.
+int msm_debug_small_snapshot(uint64_t handle, int back, MsmSmallSnapshot* out) {
+  if (!out) return H2MI_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+  auto it = g_bases.find(handle);
+  if (it == g_bases.end()) return H2MI_EHANDLE;
+  const Bases* B = it->second;
+  if (back < 0 || back >= B->nslot) return H2MI_ERANGE;
+  if (int rc = flush_tails()) return rc;
+  H2_HIP(hipDeviceSynchronize());
+  const int si = (B->last_slot + B->nslot - back) % B->nslot;
+  const Slot& S = B->slot[si];
+  if (!B->small || !S.small_n || (back == 0 && !B->last_small)) return H2MI_EINVAL;  // the slot's last MSM was not a small one
+  MsmSmallSnapshot m = {};
+  m.sc = B->sc; m.sW = B->sW; m.slanes = B->slanes; m.sr = B->sr; m.sG = B->sG; m.small_n = S.small_n; m.slot = (uint32_t)si;
+  m.G = ceil_div_u32((uint64_t)S.small_n * B->sW, (uint64_t)B->slanes * B->sr);  // small_desc
+  m.n_reg = B->n;
+  m.sdig = S.sdig; m.scnt = S.scnt; m.spart = S.spart; m.stable = B->stable;
   *out = m;
   return H2MI_OK;
 }

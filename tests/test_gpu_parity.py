@@ -448,9 +448,11 @@ def test_msm_small_path_and_general_pipeline_agree_with_oracle(gpu, n):
 
 
 def test_msm_small_path_edge_points(gpu):
-    """identity bases, duplicated bases (P + P in one lane's chain and in the tree: the doubling cases), P and -P with equal scalars
-    (cancellation to the identity), n * G, and digit-carry chains — through the small path (REGISTERED base sets: an ad-hoc slice,
-    handle = 0, keeps the general pipeline) and through the general pipeline on the same handle, against the oracle."""
+    """identity bases, duplicated bases (P + P in the first tree: the doubling case), P and -P with equal scalars (cancellation to the
+    identity), n * G, and digit-carry chains — through the small path (REGISTERED base sets: an ad-hoc slice, handle = 0, keeps the
+    general pipeline) and through the general pipeline on the same handle, against the oracle.  At 96 points the geometry is 128
+    lanes with one cell each: this reaches the first tree and no lane chain (a lane adds one point to the identity); the chains, the
+    6-bit window and the second tree's classes are tests/test_gpu_msm_small.py's."""
 
     def case(scalars, points):
         bases = o.pack_points(points)
