@@ -10,7 +10,10 @@ The format, little-endian throughout:
       where the key has none); one section per fixed column; the moved cells; the commitments; the user section.
 The checksum is FNV-1a over the blob's 64-bit words (h = (h ^ word) * 0x100000001b3 mod 2^64 from 0xcbf29ce484222325) with the
 checksum's own word taken as zero."""
+import ctypes as C
 import random
+
+import numpy as np
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 MAGIC = b"H2MI.PK\n"
@@ -273,3 +276,81 @@ def kernel_patterns(n_rows: int, limit: int, seed: int) -> dict:
         "small_dense": {r: small() + r for r in range(limit - limit // 4)},
     }
     return out
+
+
+# ---- the compaction call and what it must give (tests/test_gpu_key_file.py, tests/test_gpu_tile_regimes.py) ------------------------------
+class Compacted(C.Structure):
+    """h2mi_cells_compacted (include/h2mi.h)"""
+    _fields_ = [("d_column", C.c_void_p), ("row_limit", C.c_uint32), ("last", C.c_uint32), ("count", C.c_uint64), ("fits64", C.c_uint32),
+                ("layout", C.c_uint32), ("width", C.c_uint32), ("rows", C.c_void_p), ("values", C.c_void_p)]
+
+
+ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
+GUARD = 64
+SENTINEL = 0xA5
+
+
+def column_limbs(cells, n_rows: int) -> np.ndarray:
+    """{row: value} (or an object with limbs(n_rows)) -> the column's n_rows Montgomery words"""
+    if hasattr(cells, "limbs"):
+        return cells.limbs(n_rows)
+    out = np.zeros((n_rows, 4), dtype=np.uint64)
+    for r, v in cells.items():
+        if r < n_rows:
+            m = ((v % R) << 256) % R
+            out[r] = [(m >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+    return out
+
+
+def compact(gpu, columns, n_rows, limit, flags=0):
+    """columns: [{row: value}] -> per column (count, last, fits64, layout, width, rows, value bytes), with the block the library asked
+    for checked to be written nowhere but in the stated parts.  n_rows and limit: one number for all columns, or one per column"""
+    per = lambda x: list(x) if isinstance(x, (list, tuple)) else [x] * len(columns)
+    bufs = [gpu.DevBuf.from_numpy(column_limbs(c, rows)) for c, rows in zip(columns, per(n_rows))]
+    arr = (Compacted * len(columns))()
+    for a, b, lim in zip(arr, bufs, per(limit)):
+        a.d_column, a.row_limit = b.ptr, lim
+    block = {}
+
+    def alloc(_, n):
+        block["a"] = np.full(n + GUARD, SENTINEL, dtype=np.uint8)
+        block["n"] = n
+        return block["a"].ctypes.data
+
+    cb = ALLOC(alloc)
+    rc = gpu.lib.h2mi_fr_compact_cells_dev(arr, len(columns), flags, C.cast(cb, C.c_void_p), None, None)
+    for b in bufs:
+        b.free()
+    assert rc == 0
+    out, written = [], np.zeros(block.get("n", 0) + GUARD, dtype=bool)
+    base = block["a"].ctypes.data if block else 0
+    for a in arr:
+        rows, vals = None, b""
+        if a.count:
+            n_values = a.last if a.layout == DENSE else a.count
+            at = a.values - base
+            vals = block["a"][at:at + n_values * a.width].tobytes()
+            written[at:at + n_values * a.width] = True
+            if a.layout == SPARSE:
+                at = a.rows - base
+                rows = np.frombuffer(block["a"][at:at + 4 * a.count].tobytes(), dtype=np.uint32).tolist()
+                written[at:at + 4 * a.count] = True
+        else:
+            assert not a.values and not a.rows and a.layout == 0 and a.width == 0
+        out.append((a.count, a.last, a.fits64, a.layout, a.width, rows, vals))
+    if block:
+        assert (block["a"][~written] == SENTINEL).all()  # the padding between the parts and the guard behind the block
+    return out
+
+
+def expect(cells, limit, flags=0):
+    if hasattr(cells, "expect"):
+        return cells.expect(limit, flags)
+    rows, count, last, fits = column_stats(cells, limit)
+    if count == 0:
+        return (0, 0, 1, 0, 0, None, b"")
+    width = 8 if fits and not flags & 4 else 32
+    layout = SPARSE if flags & 2 else layout_of(count, last, width)
+    if layout == DENSE:
+        return (count, last, int(fits), layout, width, None, b"".join(value_bytes(cells.get(r, 0) % R, width) for r in range(last)))
+    return (count, last, int(fits), layout, width, rows, b"".join(value_bytes(cells[r] % R, width) for r in rows))

@@ -28,17 +28,9 @@ R = K.R
 SRS_SECRET = 0x5EC2E7 + 0x48324D49
 EINVAL, ERANGE = -1, -6
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SENTINEL = 0xA5
 
 
-class Compacted(C.Structure):
-    """h2mi_cells_compacted (include/h2mi.h)"""
-    _fields_ = [("d_column", C.c_void_p), ("row_limit", C.c_uint32), ("last", C.c_uint32), ("count", C.c_uint64), ("fits64", C.c_uint32),
-                ("layout", C.c_uint32), ("width", C.c_uint32), ("rows", C.c_void_p), ("values", C.c_void_p)]
-
-
-ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
-GUARD = 64
+Compacted = K.Compacted
 
 
 def _profile(gpu, call) -> dict:
@@ -58,55 +50,7 @@ def _profile(gpu, call) -> dict:
     return counts, out
 
 
-def _compact(gpu, columns, n_rows, limit, flags=0):
-    """columns: [{row: value}] -> per column (count, last, fits64, layout, width, rows, value bytes), with the block the library asked
-    for checked to be written nowhere but in the stated parts"""
-    bufs = [gpu.DevBuf.from_numpy(o.pack([c.get(r, 0) % R for r in range(n_rows)], R)) for c in columns]
-    arr = (Compacted * len(columns))()
-    for a, b in zip(arr, bufs):
-        a.d_column, a.row_limit = b.ptr, limit
-    block = {}
-
-    def alloc(_, n):
-        block["a"] = np.full(n + GUARD, SENTINEL, dtype=np.uint8)
-        block["n"] = n
-        return block["a"].ctypes.data
-
-    cb = ALLOC(alloc)
-    rc = gpu.lib.h2mi_fr_compact_cells_dev(arr, len(columns), flags, C.cast(cb, C.c_void_p), None, None)
-    for b in bufs:
-        b.free()
-    assert rc == 0
-    out, written = [], np.zeros(block.get("n", 0) + GUARD, dtype=bool)
-    base = block["a"].ctypes.data if block else 0
-    for a in arr:
-        rows, vals = None, b""
-        if a.count:
-            n_values = a.last if a.layout == K.DENSE else a.count
-            at = a.values - base
-            vals = block["a"][at:at + n_values * a.width].tobytes()
-            written[at:at + n_values * a.width] = True
-            if a.layout == K.SPARSE:
-                at = a.rows - base
-                rows = np.frombuffer(block["a"][at:at + 4 * a.count].tobytes(), dtype=np.uint32).tolist()
-                written[at:at + 4 * a.count] = True
-        else:
-            assert not a.values and not a.rows and a.layout == 0 and a.width == 0
-        out.append((a.count, a.last, a.fits64, a.layout, a.width, rows, vals))
-    if block:
-        assert (block["a"][~written] == SENTINEL).all()  # the padding between the parts and the guard behind the block
-    return out
-
-
-def _expect(cells, limit, flags=0):
-    rows, count, last, fits = K.column_stats(cells, limit)
-    if count == 0:
-        return (0, 0, 1, 0, 0, None, b"")
-    width = 8 if fits and not flags & 4 else 32
-    layout = K.SPARSE if flags & 2 else K.layout_of(count, last, width)
-    if layout == K.DENSE:
-        return (count, last, int(fits), layout, width, None, b"".join(K.value_bytes(cells.get(r, 0) % R, width) for r in range(last)))
-    return (count, last, int(fits), layout, width, rows, b"".join(K.value_bytes(cells[r] % R, width) for r in rows))
+_compact, _expect = K.compact, K.expect  # shared with tests/test_gpu_tile_regimes.py
 
 
 @pytest.mark.parametrize("log_rows", [5, 11, 13])

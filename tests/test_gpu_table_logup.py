@@ -131,6 +131,7 @@ CIRCUITS = {
     "q_lookup": dict(k=7, bits=4, x=0xDEADBEEFCAFE1234, count=1, columns=None),
     "11+4": dict(k=7, bits=4, x=0xF1E2D3C4B5A6978, count=24, columns=(11, 4)),
     "11+8": dict(k=7, bits=4, x=0x123456789ABCDEF, count=10, columns=(11, 8)),
+    "q_lookup, k = 17": dict(k=17, bits=8, x=0xDEADBEEFCAFE1234, count=1, columns=None),  # tests/test_gpu_tile_regimes.py: 128 tiles
 }
 CASES = [("q_lookup", None), ("11+4", None), ("11+8", None), ("11+8", 2), ("11+8", 4), ("11+8", [6, 2])]
 
@@ -177,7 +178,8 @@ class _Proving:
         self.m, self.A = len(cs.perm_columns), len(self.runs)
         self.n_sets = -(-self.m // (cs.degree - 2))
 
-    def verify(self, proof, instances=None):
+    def verify(self, proof, instances=None, ending=None):
+        """ending: the module whose `verify` reads the proof's tail — logup_sets_cases (SHPLONK, the default) or gwc_cases"""
         import logup_sets_cases as sets_cases
         from lookup_expr_cases import one_pair_lookups
 
@@ -185,7 +187,7 @@ class _Proving:
         gates = [wrap(g) for g in self.ocs.gates]
         entries = [([wrap(g) for g in ins], [wrap(g) for g in tab]) for ins, tab in one_pair_lookups(self.ocs)]
         instances = [self.asg.instance] if instances is None else instances
-        return sets_cases.verify(self.vk, proof, [[list(v)] for v in instances], gates, sets_cases.lookup_sets(entries, self.runs), logup=True)
+        return (ending or sets_cases).verify(self.vk, proof, [[list(v)] for v in instances], gates, sets_cases.lookup_sets(entries, self.runs), logup=True)
 
     def offsets(self, N=1):
         """byte offsets of the first [M], the first [phi], the first lookup evaluation"""
