@@ -113,7 +113,15 @@ def _load():
         "h2mi_fr_kate_division_multi_dev": ([vp, sz, vp, vp, vp, sz, vp, vp], C.c_int),
         "h2mi_fr_lincomb_dev": ([vp, vp, sz, sz, vp, vp], C.c_int),
         "h2mi_fr_gwc_witness_dev": ([vp, vp, vp, vp, vp, sz, sz, vp, vp], C.c_int),
-        "h2mi_plonk_evaluate_h_standard_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        # the quotient calls: (cosets or h2mi_quotient_circuits, h2mi_quotient_scalars, [slice,] out, stream); plonk.py mirrors the records
+        "h2mi_plonk_evaluate_h_standard_dev": ([vp, vp, vp, vp], C.c_int),
+        "h2mi_plonk_evaluate_h_range_dev": ([vp, vp, vp, vp], C.c_int),
+        "h2mi_plonk_evaluate_h_flex_dev": ([vp, vp, vp, vp], C.c_int),
+        "h2mi_plonk_evaluate_h_expr_dev": ([vp, vp, vp, vp], C.c_int),
+        "h2mi_plonk_evaluate_h_expr_batch_dev": ([vp, vp, C.c_int32, vp, vp], C.c_int),
+        # (h2mi_expr_columns, domain_k, theta, out, stream) / (h2mi_expr_columns, n_rows, report, n_polys, stream)
+        "h2mi_plonk_expr_compress_dev": ([vp, C.c_uint32, vp, vp, vp], C.c_int),
+        "h2mi_plonk_expr_check_dev": ([vp, C.c_uint32, vp, C.POINTER(C.c_uint32), vp], C.c_int),
         "h2mi_plonk_permutation_product_dev": ([vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "h2mi_plonk_lookup_permute_dev": ([vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64p, vp], C.c_int),
         "h2mi_plonk_instance_coset_dev": ([vp, C.c_uint32, C.c_uint32, vp, sz, vp, vp], C.c_int),
@@ -125,34 +133,8 @@ def _load():
         "h2mi_plonk_logup_sum_sets_dev": ([vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         "h2mi_plonk_logup_rank_cols_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp, u64p, vp], C.c_int),
         "h2mi_plonk_logup_sum_ranked_dev": ([vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
-        "h2mi_plonk_evaluate_h_expr_lg_dev": ([vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
-        "h2mi_plonk_evaluate_h_expr_batch_lg_dev": ([vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
-                                                     vp, vp], C.c_int),
-        "h2mi_plonk_evaluate_h_range_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
-        "h2mi_plonk_evaluate_h_flex_dev": ([vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
-        "h2mi_plonk_evaluate_h_expr_dev": ([vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
-        "h2mi_plonk_expr_compress_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
-        "h2mi_plonk_evaluate_h_expr_ch_dev": ([vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
-        "h2mi_plonk_evaluate_h_expr_batch_dev": ([vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-                                                 C.c_int),
-        "h2mi_plonk_evaluate_h_expr_sh_dev": ([vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
-        "h2mi_plonk_evaluate_h_expr_batch_sh_dev": ([vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                     vp], C.c_int),
-        "h2mi_plonk_expr_compress_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
-        "h2mi_plonk_expr_check_ch_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32), vp],
-                                         C.c_int),
         # several instance columns (h2mi_instance_cosets)
         "h2mi_plonk_instance_coset_multi_dev": ([vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, vp], C.c_int),
-        "h2mi_plonk_evaluate_h_expr_in_dev": ([vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-                                              C.c_int),
-        "h2mi_plonk_evaluate_h_expr_batch_in_dev": ([vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
-                                                     vp, vp, vp, vp], C.c_int),
-        # one coset of the extended domain per call (H2MI_KEYGEN_BY_COSET): the batch call's arguments plus the slice
-        "h2mi_plonk_evaluate_h_expr_slice_dev": ([vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
-                                                  vp, vp, C.c_uint32, vp, vp], C.c_int),
-        "h2mi_plonk_expr_compress_in_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
-        "h2mi_plonk_expr_check_in_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32), vp],
-                                         C.c_int),
         "h2mi_plonk_copy_check_dev": ([vp, C.c_uint32, vp, C.c_uint32, vp, vp], C.c_int),
         "h2mi_plonk_lookup_member_dev": ([vp, vp, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
         "h2mi_plonk_shuffle_member_dev": ([vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp], C.c_int),

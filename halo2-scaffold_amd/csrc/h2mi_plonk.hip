@@ -1217,20 +1217,34 @@ struct HostY {  // y^0 .. y^(count-1), Montgomery-2^256
     for (uint32_t i = 1; i < count && i < 24; i++) p[i] = h_mul256(p[i - 1], y);
   }
 };
-static void fill_common(HConsts& h, const fe& beta, const fe& gamma, const fe& delta, const fe& zeta, uint32_t n_cur, const uint64_t* t_inv,
-                        uint32_t rot) {
+// what every quotient call asks of its scalars: no NULL (H2MI_EINVAL), an extended domain of 1 .. 16 cosets (H2MI_ERANGE)
+static int check_scalars(const h2mi_quotient_scalars* q) {
+  if (!q || !q->beta || !q->gamma || !q->y || !q->delta || !q->zeta || !q->extended_omega || !q->t_inv) return H2MI_EINVAL;
+  if (q->extended_k < q->k || q->extended_k - q->k > 4 || q->extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  return H2MI_OK;
+}
+static void fill_common(HConsts& h, const h2mi_quotient_scalars& q, uint32_t n_cur) {
+  const fe beta = host_fe(q.beta), delta = host_fe(q.delta);
   memset(&h, 0, sizeof(h));
   h.beta0 = beta;
   h.beta_m1 = h_level(beta, -1);
-  h.gamma0 = gamma;
+  h.gamma0 = host_fe(q.gamma);
   h.one0 = h_canon(f29_const<F9>(F9::TO256));
   h.one_m2 = h_level(h.one0, -2);
-  fe cur = h_mul256(beta, zeta);
+  fe cur = h_mul256(beta, host_fe(q.zeta));
   for (uint32_t j = 0; j < n_cur; j++) {
     h.cur[j] = cur;
     cur = h_mul256(cur, delta);
   }
-  for (uint32_t i = 0; i < rot; i++) h.tinv[i] = h_level(host_fe(t_inv + 4 * i), -1);
+  for (uint32_t i = 0; i < 1u << (q.extended_k - q.k); i++) h.tinv[i] = h_level(host_fe(q.t_inv + 4 * i), -1);
+}
+// the same scalars as the general and the interpreting kernels take them
+static FlexConsts flex_consts(const h2mi_quotient_scalars& q) {
+  FlexConsts h;
+  memset(&h, 0, sizeof(h));
+  h.beta = host_fe(q.beta); h.gamma = host_fe(q.gamma); h.y = host_fe(q.y); h.delta = host_fe(q.delta); h.zeta = host_fe(q.zeta);
+  for (uint32_t i = 0; i < 1u << (q.extended_k - q.k); i++) h.tinv[i] = host_fe(q.t_inv + 4 * i);
+  return h;
 }
 
 // the permutation / lookup / Lagrange pointers of h2mi_flex_cosets or h2mi_expr_cosets (the same fields) -> the kernels' argument
@@ -1321,8 +1335,8 @@ static void expr_encode(const h2mi_gate_program* g, uint32_t k, uint32_t extende
 // rotation of 2^k or more is H2MI_EINVAL) and laid out as ONE buffer: the column-pointer table, the constants and behind them the
 // challenges as Montgomery-2^261 words, the ops (each part a whole number of 32-byte words).  dom_k: the domain the columns are given
 // on (k or extended_k).
-// the instance columns of one circuit as the entry points take them: an h2mi_instance_cosets, or the one pointer of the older calls
-// (column 0).  ok = false: more columns than the table holds
+// the instance columns of one circuit as the entry points take them: an h2mi_instance_cosets, or without one the entry's own
+// `instance` pointer (column 0).  ok = false: more columns than the table holds
 struct InstanceCols {
   const void* col[H2MI_MAX_INSTANCE] = {nullptr};
   bool ok = true;
@@ -1363,6 +1377,23 @@ struct ExprImage {
     memcpy(&image[cols_fe + const_fe], ops.data(), ops.size() * 8);
     n_ops = (uint32_t)ops.size();
     lds = (size_t)(shape.max_stack - 1) * 9 * 256 * sizeof(uint32_t);  // at most 7 levels: 63 KB
+    return H2MI_OK;
+  }
+};
+// an h2mi_expr_columns on the 2^dom_k points it is given on, as ExprImage::build takes the columns (expr_compress, expr_check)
+struct ColumnTables {
+  const void* adv[H2MI_EXPR_MAX_ADVICE] = {nullptr};
+  const void* fix[H2MI_EXPR_MAX_FIXED] = {nullptr};
+  InstanceCols inst{nullptr, nullptr};
+  int fill(const h2mi_expr_columns* c, uint32_t dom_k) {
+    if (!c) return H2MI_EINVAL;
+    inst = InstanceCols(c->instances, nullptr);
+    if (!inst.ok || !c->program || (c->n_advice && !c->advice) || (c->n_fixed && !c->fixed) || c->n_advice > H2MI_EXPR_MAX_ADVICE ||
+        c->n_fixed > H2MI_EXPR_MAX_FIXED)
+      return H2MI_EINVAL;
+    if (c->k == 0 || dom_k < c->k || dom_k - c->k > 4 || dom_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+    for (uint32_t i = 0; i < c->n_advice; i++) adv[i] = c->advice[i];
+    for (uint32_t i = 0; i < c->n_fixed; i++) fix[i] = c->fixed[i];
     return H2MI_OK;
   }
 };
@@ -1786,12 +1817,12 @@ int h2mi_plonk_logup_sum_ranked_dev(const void* d_ranks, uint32_t n_inputs, cons
   return release_tmp(s);
 }
 
-int h2mi_plonk_evaluate_h_range_dev(const h2mi_range_cosets* c, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
-                                    const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
-                                    const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
+int h2mi_plonk_evaluate_h_range_dev(const h2mi_range_cosets* c, const h2mi_quotient_scalars* q, void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
-  if (!c || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
-  if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  if (!c || !d_h_out) return H2MI_EINVAL;
+  int rc = check_scalars(q);
+  if (rc) return rc;
+  const uint32_t k = q->k, extended_k = q->extended_k, blinding_factors = q->blinding_factors;
   if (c->n_perm == 0 || c->n_perm > 4 || c->chunk_len == 0 || c->chunk_len > 3) return H2MI_EINVAL;
   RangeCosets rc_;
   memset(&rc_, 0, sizeof(rc_));
@@ -1816,15 +1847,14 @@ int h2mi_plonk_evaluate_h_range_dev(const h2mi_range_cosets* c, uint32_t k, uint
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
   PowTab px;
-  int rc = get_powtab(extended_omega, extended_k, s, &px);
+  rc = get_powtab(q->extended_omega, extended_k, s, &px);
   if (rc) return rc;
-  const uint32_t rot = 1u << (extended_k - k);
   HConsts hcst;
-  fill_common(hcst, host_fe(beta), host_fe(gamma), host_fe(delta), host_fe(zeta), c->n_perm, t_inv, rot);
+  fill_common(hcst, *q, c->n_perm);
   {  // term i carries y^(N-1-i) at the level its expression needs (see the kernel's header)
     const uint32_t sets = (c->n_perm + c->chunk_len - 1) / c->chunk_len;
     const uint32_t N = 2 + 2 * sets + (rc_.has_lookup ? 5 : 0);
-    const HostY yp(host_fe(y), N);
+    const HostY yp(host_fe(q->y), N);
     auto put = [&](uint32_t term, int level) { hcst.y[term] = h_level(yp.p[N - 1 - term], level); };
     put(0, -3);
     put(1, -2);
@@ -1849,12 +1879,12 @@ int h2mi_plonk_evaluate_h_range_dev(const h2mi_range_cosets* c, uint32_t k, uint
   return H2MI_OK;
 }
 
-int h2mi_plonk_evaluate_h_flex_dev(const h2mi_flex_cosets* c, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
-                                   const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
-                                   const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
+int h2mi_plonk_evaluate_h_flex_dev(const h2mi_flex_cosets* c, const h2mi_quotient_scalars* q, void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
-  if (!c || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
-  if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  if (!c || !d_h_out) return H2MI_EINVAL;
+  int rc = check_scalars(q);
+  if (rc) return rc;
+  const uint32_t k = q->k, extended_k = q->extended_k, blinding_factors = q->blinding_factors;
   if (c->n_gates == 0 || c->n_gates > H2MI_FLEX_MAX_GATES || c->n_perm > H2MI_FLEX_MAX_PERM || c->n_lookups > H2MI_FLEX_MAX_LOOKUPS) return H2MI_EINVAL;
   if (c->n_perm && (c->chunk_len == 0 || c->chunk_len > 3)) return H2MI_EINVAL;
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 64 <= 4096, "the quotient kernel's arguments travel by value");
@@ -1870,86 +1900,44 @@ int h2mi_plonk_evaluate_h_flex_dev(const h2mi_flex_cosets* c, uint32_t k, uint32
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
   PowTab px;
-  int rc = get_powtab(extended_omega, extended_k, s, &px);
+  rc = get_powtab(q->extended_omega, extended_k, s, &px);
   if (rc) return rc;
-  const uint32_t rot = 1u << (extended_k - k);
-  FlexConsts hc_;
-  memset(&hc_, 0, sizeof(hc_));
-  hc_.beta = host_fe(beta); hc_.gamma = host_fe(gamma); hc_.y = host_fe(y); hc_.delta = host_fe(delta); hc_.zeta = host_fe(zeta);
-  for (uint32_t i = 0; i < rot; i++) hc_.tinv[i] = host_fe(t_inv + 4 * i);
+  const FlexConsts hc_ = flex_consts(*q);
   const uint32_t size = 1u << extended_k;
   H2_LAUNCH("k_evaluate_h_flex", k_evaluate_h_flex, ceil_div_u32(size, 256), 256, 0, s, fc, extended_k, k, blinding_factors + 1, hc_, (const fe*)px.lo,
             (const fe*)px.hi, px.h, (fe*)d_h_out);
   return H2MI_OK;
 }
 
-int h2mi_plonk_evaluate_h_expr_dev(const h2mi_expr_cosets* c, const h2mi_gate_program* gates, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
-                                   const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
-                                   const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
-  return h2mi_plonk_evaluate_h_expr_ch_dev(c, gates, nullptr, 0, k, extended_k, blinding_factors, beta, gamma, y, delta, zeta, extended_omega, t_inv, d_h_out,
-                                           stream);
-}
-
-int h2mi_plonk_evaluate_h_expr_ch_dev(const h2mi_expr_cosets* c, const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k,
-                                      uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
-                                      const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out,
-                                      h2mi_stream_t stream) {
-  return h2mi_plonk_evaluate_h_expr_sh_dev(c, nullptr, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma, y, delta, zeta,
-                                           extended_omega, t_inv, d_h_out, stream);
-}
-
-int h2mi_plonk_evaluate_h_expr_sh_dev(const h2mi_expr_cosets* c, const h2mi_shuffle_cosets* shuffles, const h2mi_gate_program* gates,
-                                      const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
-                                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
-                                      const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out,
-                                      h2mi_stream_t stream) {
-  return h2mi_plonk_evaluate_h_expr_lg_dev(c, shuffles, nullptr, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma, y, delta, zeta,
-                                           extended_omega, t_inv, d_h_out, stream);
-}
-
-int h2mi_plonk_evaluate_h_expr_lg_dev(const h2mi_expr_cosets* c, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                      const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
-                                      uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
-                                      const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
-                                      void* d_h_out, h2mi_stream_t stream) {
-  return h2mi_plonk_evaluate_h_expr_in_dev(c, shuffles, logup, nullptr, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma, y, delta,
-                                           zeta, extended_omega, t_inv, d_h_out, stream);
-}
-
-int h2mi_plonk_evaluate_h_expr_in_dev(const h2mi_expr_cosets* c, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                      const h2mi_instance_cosets* instances, const h2mi_gate_program* gates, const uint64_t* challenges,
-                                      uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
-                                      const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
-                                      const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
+int h2mi_plonk_evaluate_h_expr_dev(const h2mi_quotient_circuits* qc, const h2mi_quotient_scalars* q, void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
-  if (!c || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
-  if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  if (!qc || !qc->circuits || !qc->gates || !d_h_out || qc->n_circuits != 1) return H2MI_EINVAL;
+  int rc = check_scalars(q);
+  if (rc) return rc;
+  const uint32_t k = q->k, extended_k = q->extended_k, blinding_factors = q->blinding_factors;
+  const h2mi_expr_cosets* c = qc->circuits;
   if (c->n_perm > H2MI_FLEX_MAX_PERM || (c->n_lookups & ~(uint32_t)H2MI_LOOKUPS_LOGUP) > H2MI_FLEX_MAX_LOOKUPS || (c->n_perm && c->chunk_len == 0)) return H2MI_EINVAL;
-  const InstanceCols inst(instances, c->instance);
+  const InstanceCols inst(qc->instances, c->instance);
   if (!inst.ok) return H2MI_EINVAL;
   ExprImage im;
-  int rc = im.build(gates, challenges, n_challenges, c->advice, c->fixed, inst, k, extended_k);
+  rc = im.build(qc->gates, qc->challenges, qc->n_challenges, c->advice, c->fixed, inst, k, extended_k);
   if (rc) return rc;
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
   FlexCosets fc;
   memset(&fc, 0, sizeof(fc));
-  if (!fill_tail(fc, *c) || !fill_shuffles(fc, shuffles) || !fill_sets(fc, logup)) return H2MI_EINVAL;
+  if (!fill_tail(fc, *c) || !fill_shuffles(fc, qc->shuffles) || !fill_sets(fc, qc->logup)) return H2MI_EINVAL;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
   PowTab px;
-  rc = get_powtab(extended_omega, extended_k, s, &px);
+  rc = get_powtab(q->extended_omega, extended_k, s, &px);
   if (rc) return rc;
   rc = ensure_tmp(im.image.size(), s);
   if (rc) return rc;
   fe* d_image = tmp_base();
   // pageable source: the copy has left `image` when the call returns
   H2_HIP(hipMemcpyAsync(d_image, im.image.data(), im.image.size() * sizeof(fe), hipMemcpyHostToDevice, s));
-  const uint32_t rot = 1u << (extended_k - k);
-  FlexConsts hc_;
-  memset(&hc_, 0, sizeof(hc_));
-  hc_.beta = host_fe(beta); hc_.gamma = host_fe(gamma); hc_.y = host_fe(y); hc_.delta = host_fe(delta); hc_.zeta = host_fe(zeta);
-  for (uint32_t i = 0; i < rot; i++) hc_.tinv[i] = host_fe(t_inv + 4 * i);
+  const FlexConsts hc_ = flex_consts(*q);
   const uint32_t size = 1u << extended_k;
   H2_LAUNCH("k_evaluate_h_expr", k_evaluate_h_expr, ceil_div_u32(size, 256), 256, im.lds, s, fc, (const fe* const*)d_image, (const fe*)(d_image + im.cols_fe),
             (const uint2*)(d_image + im.cols_fe + im.const_fe), im.n_ops, extended_k, k, blinding_factors + 1, hc_, (const fe*)px.lo,
@@ -1957,42 +1945,19 @@ int h2mi_plonk_evaluate_h_expr_in_dev(const h2mi_expr_cosets* c, const h2mi_shuf
   return release_tmp(s);
 }
 
-int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_expr_cosets* circuits, uint32_t n_circuits, const h2mi_gate_program* gates, const uint64_t* challenges,
-                                         uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
-                                         const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
-                                         const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
-  return h2mi_plonk_evaluate_h_expr_batch_sh_dev(circuits, nullptr, n_circuits, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma,
-                                                 y, delta, zeta, extended_omega, t_inv, d_h_out, stream);
-}
-
-int h2mi_plonk_evaluate_h_expr_batch_sh_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, uint32_t n_circuits,
-                                            const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k,
-                                            uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
-                                            const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
-                                            const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
-  return h2mi_plonk_evaluate_h_expr_batch_lg_dev(circuits, shuffles, nullptr, n_circuits, gates, challenges, n_challenges, k, extended_k, blinding_factors,
-                                                 beta, gamma, y, delta, zeta, extended_omega, t_inv, d_h_out, stream);
-}
-
-int h2mi_plonk_evaluate_h_expr_batch_lg_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                            uint32_t n_circuits, const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges,
-                                            uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
-                                            const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
-                                            const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream) {
-  return h2mi_plonk_evaluate_h_expr_batch_in_dev(circuits, shuffles, logup, nullptr, n_circuits, gates, challenges, n_challenges, k, extended_k,
-                                                 blinding_factors, beta, gamma, y, delta, zeta, extended_omega, t_inv, d_h_out, stream);
-}
-
 // the batch call (slice < 0: every vector on the extended coset) and the by-coset call (every vector the 2^k points of coset `slice`)
-static int evaluate_h_circuits(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                               const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
-                               const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
-                               const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
-                               const uint64_t extended_omega[4], const uint64_t* t_inv, int64_t slice, void* d_h_out, h2mi_stream_t stream) {
+static int evaluate_h_circuits(const h2mi_quotient_circuits* qc, const h2mi_quotient_scalars* q, int64_t slice, void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
-  if (!circuits || !gates || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
-  if (n_circuits == 0 || n_circuits > H2MI_MAX_CIRCUITS) return H2MI_EINVAL;
-  if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  if (!qc || !qc->circuits || !qc->gates || !d_h_out) return H2MI_EINVAL;
+  const h2mi_expr_cosets* circuits = qc->circuits;
+  const h2mi_shuffle_cosets* shuffles = qc->shuffles;
+  const h2mi_instance_cosets* instances = qc->instances;
+  const h2mi_gate_program* gates = qc->gates;
+  const uint32_t n_circuits = qc->n_circuits, n_challenges = qc->n_challenges;
+  if (n_circuits == 0 || n_circuits > H2MI_MAX_CIRCUITS || slice < H2MI_WHOLE_COSET) return H2MI_EINVAL;
+  int rc = check_scalars(q);
+  if (rc) return rc;
+  const uint32_t k = q->k, extended_k = q->extended_k, blinding_factors = q->blinding_factors;
   if (slice >= (int64_t)1 << (extended_k - k)) return H2MI_ERANGE;
   const uint32_t dom_k = slice < 0 ? extended_k : k;  // the domain the vectors are given on
   const h2mi_expr_cosets& c0 = circuits[0];
@@ -2002,13 +1967,13 @@ static int evaluate_h_circuits(const h2mi_expr_cosets* circuits, const h2mi_shuf
   const InstanceCols inst0(instances, c0.instance);
   if (!inst0.ok) return H2MI_EINVAL;
   ExprImage im;
-  int rc = im.build(gates, challenges, n_challenges, c0.advice, c0.fixed, inst0, k, dom_k);
+  rc = im.build(gates, qc->challenges, n_challenges, c0.advice, c0.fixed, inst0, k, dom_k);
   if (rc) return rc;
   static_assert(sizeof(FlexCosets) + sizeof(FlexConsts) + 96 <= 4096, "the quotient kernel's arguments travel by value");
   static_assert(sizeof(CircuitCosets) % 8 == 0, "records are arrays of pointers");
   FlexCosets sh;
   memset(&sh, 0, sizeof(sh));
-  if (!fill_tail(sh, c0) || !fill_shuffles(sh, shuffles) || !fill_sets(sh, logup)) return H2MI_EINVAL;  // the counts are the key's: one struct for the batch
+  if (!fill_tail(sh, c0) || !fill_shuffles(sh, shuffles) || !fill_sets(sh, qc->logup)) return H2MI_EINVAL;  // the counts are the key's: one struct for the batch
   const size_t rec_fe = (sizeof(CircuitCosets) + sizeof(fe) - 1) / sizeof(fe), prog_fe = im.image.size();
   im.image.resize(prog_fe + rec_fe * n_circuits);
   for (uint32_t i = 0; i < n_circuits; i++) {
@@ -2050,13 +2015,9 @@ static int evaluate_h_circuits(const h2mi_expr_cosets* circuits, const h2mi_shuf
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
-  const uint32_t rot = 1u << (extended_k - k);
-  FlexConsts hc_;
-  memset(&hc_, 0, sizeof(hc_));
-  hc_.beta = host_fe(beta); hc_.gamma = host_fe(gamma); hc_.y = host_fe(y); hc_.delta = host_fe(delta); hc_.zeta = host_fe(zeta);
-  for (uint32_t i = 0; i < rot; i++) hc_.tinv[i] = host_fe(t_inv + 4 * i);
+  FlexConsts hc_ = flex_consts(*q);
   // a slice: X = (zeta extended_omega^slice) omega^i with omega = extended_omega^rot, the generator of the 2^k rows
-  fe x_base = host_fe(extended_omega);
+  fe x_base = host_fe(q->extended_omega);
   if (slice >= 0) {
     for (int64_t c = 0; c < slice; c++) hc_.zeta = h_mul256(hc_.zeta, x_base);
     for (uint32_t j = k; j < extended_k; j++) x_base = h_mul256(x_base, x_base);
@@ -2082,54 +2043,19 @@ static int evaluate_h_circuits(const h2mi_expr_cosets* circuits, const h2mi_shuf
   return release_tmp(s);
 }
 
-int h2mi_plonk_evaluate_h_expr_batch_in_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                            const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
-                                            const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
-                                            uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
-                                            const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
-                                            void* d_h_out, h2mi_stream_t stream) {
-  return evaluate_h_circuits(circuits, shuffles, logup, instances, n_circuits, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma,
-                             y, delta, zeta, extended_omega, t_inv, -1, d_h_out, stream);
-}
-
-int h2mi_plonk_evaluate_h_expr_slice_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                         const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
-                                         const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
-                                         const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
-                                         const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, uint32_t slice, void* d_h_out,
+int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_quotient_circuits* circuits, const h2mi_quotient_scalars* scalars, int32_t slice, void* d_h_out,
                                          h2mi_stream_t stream) {
-  return evaluate_h_circuits(circuits, shuffles, logup, instances, n_circuits, gates, challenges, n_challenges, k, extended_k, blinding_factors, beta, gamma,
-                             y, delta, zeta, extended_omega, t_inv, (int64_t)slice, d_h_out, stream);
+  return evaluate_h_circuits(circuits, scalars, slice, d_h_out, stream);
 }
 
-int h2mi_plonk_expr_compress_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
-                                 const h2mi_gate_program* exprs, uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out,
-                                 h2mi_stream_t stream) {
-  return h2mi_plonk_expr_compress_ch_dev(d_advice, n_advice, d_fixed, n_fixed, d_instance, exprs, nullptr, 0, k, domain_k, theta, d_out, stream);
-}
-
-int h2mi_plonk_expr_compress_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
-                                    const h2mi_gate_program* exprs, const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t domain_k,
-                                    const uint64_t theta[4], void* d_out, h2mi_stream_t stream) {
-  const h2mi_instance_cosets one = {1, {d_instance}};
-  return h2mi_plonk_expr_compress_in_dev(d_advice, n_advice, d_fixed, n_fixed, &one, exprs, challenges, n_challenges, k, domain_k, theta, d_out, stream);
-}
-
-int h2mi_plonk_expr_compress_in_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
-                                    const h2mi_instance_cosets* instances, const h2mi_gate_program* exprs, const uint64_t* challenges,
-                                    uint32_t n_challenges, uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out, h2mi_stream_t stream) {
+int h2mi_plonk_expr_compress_dev(const h2mi_expr_columns* cols, uint32_t domain_k, const uint64_t theta[4], void* d_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
-  const InstanceCols inst(instances, nullptr);
-  if (!inst.ok) return H2MI_EINVAL;
-  if (!exprs || !theta || !d_out || (n_advice && !d_advice) || (n_fixed && !d_fixed) || n_advice > H2MI_EXPR_MAX_ADVICE || n_fixed > H2MI_EXPR_MAX_FIXED)
-    return H2MI_EINVAL;
-  if (k == 0 || domain_k < k || domain_k - k > 4 || domain_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
-  const void* adv[H2MI_EXPR_MAX_ADVICE] = {nullptr};
-  const void* fix[H2MI_EXPR_MAX_FIXED] = {nullptr};
-  for (uint32_t i = 0; i < n_advice; i++) adv[i] = d_advice[i];
-  for (uint32_t i = 0; i < n_fixed; i++) fix[i] = d_fixed[i];
+  if (!theta || !d_out) return H2MI_EINVAL;
+  ColumnTables t;
+  int rc = t.fill(cols, domain_k);
+  if (rc) return rc;
   ExprImage im;
-  int rc = im.build(exprs, challenges, n_challenges, adv, fix, inst, k, domain_k);
+  rc = im.build(cols->program, cols->challenges, cols->n_challenges, t.adv, t.fix, t.inst, cols->k, domain_k);
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
@@ -2144,29 +2070,17 @@ int h2mi_plonk_expr_compress_in_dev(const void* const* d_advice, uint32_t n_advi
   return release_tmp(s);
 }
 
-int h2mi_plonk_expr_check_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
-                                 const h2mi_gate_program* polys, const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t n_rows,
-                                 uint32_t* report_out, uint32_t* n_polys_out, h2mi_stream_t stream) {
-  const h2mi_instance_cosets one = {1, {d_instance}};
-  return h2mi_plonk_expr_check_in_dev(d_advice, n_advice, d_fixed, n_fixed, &one, polys, challenges, n_challenges, k, n_rows, report_out, n_polys_out, stream);
-}
-
-int h2mi_plonk_expr_check_in_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
-                                 const h2mi_instance_cosets* instances, const h2mi_gate_program* polys, const uint64_t* challenges,
-                                 uint32_t n_challenges, uint32_t k, uint32_t n_rows, uint32_t* report_out, uint32_t* n_polys_out,
-                                 h2mi_stream_t stream) {
+int h2mi_plonk_expr_check_dev(const h2mi_expr_columns* cols, uint32_t n_rows, uint32_t* report_out, uint32_t* n_polys_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
-  const InstanceCols inst(instances, nullptr);
-  if (!inst.ok) return H2MI_EINVAL;
-  if (!polys || !report_out || (n_advice && !d_advice) || (n_fixed && !d_fixed) || n_advice > H2MI_EXPR_MAX_ADVICE || n_fixed > H2MI_EXPR_MAX_FIXED)
-    return H2MI_EINVAL;
-  if (k == 0 || k > H2MI_MAX_LOG_N || n_rows == 0 || n_rows > ((uint64_t)1 << k)) return H2MI_ERANGE;
-  const void* adv[H2MI_EXPR_MAX_ADVICE] = {nullptr};
-  const void* fix[H2MI_EXPR_MAX_FIXED] = {nullptr};
-  for (uint32_t i = 0; i < n_advice; i++) adv[i] = d_advice[i];
-  for (uint32_t i = 0; i < n_fixed; i++) fix[i] = d_fixed[i];
+  if (!report_out) return H2MI_EINVAL;
+  ColumnTables t;
+  int rc = t.fill(cols, cols ? cols->k : 0);
+  if (rc) return rc;
+  const h2mi_gate_program* polys = cols->program;
+  const uint32_t k = cols->k;
+  if (n_rows == 0 || n_rows > ((uint64_t)1 << k)) return H2MI_ERANGE;
   ExprImage im;
-  int rc = im.build(polys, challenges, n_challenges, adv, fix, inst, k, k);
+  rc = im.build(polys, cols->challenges, cols->n_challenges, t.adv, t.fix, t.inst, k, k);
   if (rc) return rc;
   uint32_t n_polys = 0;
   for (uint32_t i = 0; i < polys->n_ops; i++) n_polys += polys->ops[i].op == H2MI_EXPR_END;
@@ -2218,13 +2132,12 @@ int h2mi_plonk_copy_check_dev(const void* const* d_values, uint32_t m, const voi
   return release_tmp(s);
 }
 
-int h2mi_plonk_evaluate_h_standard_dev(const h2mi_standard_plonk_cosets* c, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
-                                       const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
-                                       const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out,
-                                       h2mi_stream_t stream) {
+int h2mi_plonk_evaluate_h_standard_dev(const h2mi_standard_plonk_cosets* c, const h2mi_quotient_scalars* q, void* d_h_out, h2mi_stream_t stream) {
   H2_REQUIRE_INIT();
-  if (!c || !beta || !gamma || !y || !delta || !zeta || !extended_omega || !t_inv || !d_h_out) return H2MI_EINVAL;
-  if (extended_k < k || extended_k - k > 4 || extended_k > H2MI_MAX_LOG_N) return H2MI_ERANGE;
+  if (!c || !d_h_out) return H2MI_EINVAL;
+  int rc = check_scalars(q);
+  if (rc) return rc;
+  const uint32_t k = q->k, extended_k = q->extended_k, blinding_factors = q->blinding_factors;
   std::lock_guard<std::recursive_mutex> lk(ctx().mu);
   CallScope scope_;
   hipStream_t s = pick_stream(stream);
@@ -2236,12 +2149,12 @@ int h2mi_plonk_evaluate_h_standard_dev(const h2mi_standard_plonk_cosets* c, uint
   for (int i = 0; i < 5; i++) if (!pc.fixed[i]) return H2MI_EINVAL;
   if (!pc.l0 || !pc.l_last || !pc.l_active) return H2MI_EINVAL;
   PowTab px;
-  int rc = get_powtab(extended_omega, extended_k, s, &px);
+  rc = get_powtab(q->extended_omega, extended_k, s, &px);
   if (rc) return rc;
   HConsts hcst;
-  fill_common(hcst, host_fe(beta), host_fe(gamma), host_fe(delta), host_fe(zeta), 3, t_inv, 1u << (extended_k - k));
+  fill_common(hcst, *q, 3);
   {
-    const HostY yp(host_fe(y), 8);  // eight terms: term i carries y^(7-i)
+    const HostY yp(host_fe(q->y), 8);  // eight terms: term i carries y^(7-i)
     hcst.y[0] = h_level(yp.p[7], -2);
     hcst.y[1] = h_level(yp.p[7], -3);
     hcst.y[2] = h_level(yp.p[7], -1);

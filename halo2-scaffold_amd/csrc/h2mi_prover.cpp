@@ -1018,8 +1018,9 @@ struct h2mi_prover_s {
     for (uint32_t j = 0; j < cs.n_advice; j++) adv[j] = coset ? advice[j].coset->p : advice[j].value->p;
     for (uint32_t j = 0; j < cs.n_fixed; j++) fix[j] = coset ? fixed_coset(j) : pk->fixed_values[j]->p;
     const h2mi_instance_cosets inst = instance_columns(coset);
-    check(h2mi_plonk_expr_compress_in_dev(adv, cs.n_advice, fix, cs.n_fixed, &inst, &prog, challenge_limbs(), pk->phases.n_challenges, cs.k,
-                                          coset && !pk->by_coset ? pk->domain.extended_k() : cs.k, (th ? *th : theta).l, (char*)out.p + at * 32, nullptr),
+    const h2mi_expr_columns cols = {adv, cs.n_advice, fix, cs.n_fixed, &inst, &prog, challenge_limbs(), pk->phases.n_challenges, cs.k};
+    check(h2mi_plonk_expr_compress_dev(&cols, coset && !pk->by_coset ? pk->domain.extended_k() : cs.k, (th ? *th : theta).l, (char*)out.p + at * 32,
+                                       nullptr),
           "expr_compress");
   }
   // every instance column on the rows (coset = false) or on the extended coset, as the interpreting kernels take them
@@ -1448,9 +1449,8 @@ std::vector<h2mi_check_failure> run_check(h2mi_prover_s& p, const uint64_t* thet
     for (uint32_t i = 0; i < pk.check_gates.n_ops; i++) n_polys += pk.check_gates.ops[i].op == H2MI_EXPR_END;
     std::vector<uint32_t> report(2 * (size_t)n_polys);
     const h2mi_instance_cosets inst = p.instance_columns(false);
-    check(h2mi_plonk_expr_check_in_dev(adv, cs.n_advice, fix, cs.n_fixed, &inst, &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, cs.k,
-                                       (uint32_t)n, report.data(), nullptr, nullptr),
-          "expr_check");
+    const h2mi_expr_columns cols = {adv, cs.n_advice, fix, cs.n_fixed, &inst, &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, cs.k};
+    check(h2mi_plonk_expr_check_dev(&cols, (uint32_t)n, report.data(), nullptr, nullptr), "expr_check");
     for (uint32_t j = 0; j < n_polys; j++)
       if (report[2 * j]) out.push_back({H2MI_CHECK_GATE, j, report[2 * j + 1], report[2 * j]});
   }
@@ -1709,6 +1709,26 @@ void fill_expr_cosets(h2mi_prover_s& p, h2mi_expr_cosets& ec, h2mi_shuffle_coset
     sc.z[i] = p.sf[i].z.coset->p;
   }
 }
+// the circuits of a proof for those kernels: the record and what it points into (the lookups' and shuffles' sides are compressed here)
+struct QuotientCircuits {
+  std::vector<h2mi_expr_cosets> ec;
+  std::vector<h2mi_shuffle_cosets> sc;
+  std::vector<h2mi_instance_cosets> ic;
+  h2mi_logup_cosets lg;  // the key's: the same for every member
+  h2mi_quotient_circuits rec;
+  explicit QuotientCircuits(const Circuits& all) : ec(all.size()), sc(all.size()), ic(all.size()) {
+    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i], sc[i], lg, ic[i]);
+    const h2mi_prover_s& p = *all[0];
+    rec = {ec.data(), (uint32_t)ec.size(), p.pk->n_shuffles ? sc.data() : nullptr, &lg, ic.data(), &p.pk->check_gates, p.challenge_limbs(),
+           p.pk->phases.n_challenges};
+  }
+};
+// what every quotient call of a proof knows of the domain and the transcript
+h2mi_quotient_scalars quotient_scalars(const h2mi_pk_s& pk, const h2mi_prover_s& p, const Fr& y) {
+  const poly::EvaluationDomain& d = pk.domain;
+  return {d.k(), d.extended_k(), pk.cs.blinding_factors, p.beta.l, p.gamma.l, y.l, pk.delta.l, d.get_g_coset().l, d.get_extended_omega().l,
+          (const uint64_t*)d.t_inv().data()};  // (X^n - 1)^-1 on the coset: cached in the domain
+}
 
 // a joint phase of a batch: the members behind the leader must still be where their products left them (one that has started another
 // proof since has overwritten its columns)
@@ -1738,7 +1758,7 @@ void evaluate_h_by_coset(const Circuits& all, const Fr& y) {
   const poly::EvaluationDomain& d = pk.domain;
   const size_t n = pk.n;
   const uint32_t rot = 1u << (d.extended_k() - d.k());
-  const std::vector<Fr>& t_inv = d.t_inv();
+  const h2mi_quotient_scalars scalars = quotient_scalars(pk, lead, y);
   for (h2mi_prover_s* c : all) c->lead = &lead;
   Fr shift = d.get_g_coset();
   for (uint32_t c = 0; c < rot; c++, shift = fr::mul(shift, d.get_extended_omega())) {
@@ -1761,16 +1781,8 @@ void evaluate_h_by_coset(const Circuits& all, const Fr& y) {
       }
       for (uint32_t i = 0; i < pk.n_shuffles; i++) slice(*m->sf[i].z.poly, *m->sf[i].z.coset);
     }
-    std::vector<h2mi_expr_cosets> ec(all.size());
-    std::vector<h2mi_shuffle_cosets> sc(all.size());
-    std::vector<h2mi_instance_cosets> ic(all.size());
-    h2mi_logup_cosets lg;
-    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i], sc[i], lg, ic[i]);  // compresses on the slices
-    check(h2mi_plonk_evaluate_h_expr_slice_dev(ec.data(), pk.n_shuffles ? sc.data() : nullptr, &lg, ic.data(), (uint32_t)ec.size(), &pk.check_gates,
-                                               lead.challenge_limbs(), pk.phases.n_challenges, d.k(), d.extended_k(), cs.blinding_factors, lead.beta.l,
-                                               lead.gamma.l, y.l, pk.delta.l, d.get_g_coset().l, d.get_extended_omega().l, (const uint64_t*)t_inv.data(),
-                                               c, lead.h->p, nullptr),
-          "evaluate_h");
+    const QuotientCircuits qc(all);  // compresses on the slices
+    check(h2mi_plonk_evaluate_h_expr_batch_dev(&qc.rec, &scalars, (int32_t)c, lead.h->p, nullptr), "evaluate_h");
   }
   for (h2mi_prover_s* c : all) c->lead = nullptr;
 }
@@ -1792,16 +1804,9 @@ void phase_quotient(const Circuits& all, const Fr& y, uint64_t* points_out) {
   } else {
     // several circuits (or a batch of one): ONE launch folds every circuit's terms into h, whatever the key's shape — a hard-wired
     // shape through the equivalent program keygen built for the witness check, which computes the same field elements
-    std::vector<h2mi_expr_cosets> ec(all.size());
-    std::vector<h2mi_shuffle_cosets> sc(all.size());
-    std::vector<h2mi_instance_cosets> ic(all.size());
-    h2mi_logup_cosets lg;  // the key's: the same for every member
-    for (size_t i = 0; i < all.size(); i++) fill_expr_cosets(*all[i], ec[i], sc[i], lg, ic[i]);
-    const std::vector<Fr>& t_inv = d.t_inv();
-    check(h2mi_plonk_evaluate_h_expr_batch_in_dev(ec.data(), pk.n_shuffles ? sc.data() : nullptr, &lg, ic.data(), (uint32_t)ec.size(), &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
-                                                  d.extended_k(), cs.blinding_factors, p.beta.l, p.gamma.l, y.l, pk.delta.l, d.get_g_coset().l,
-                                                  d.get_extended_omega().l, (const uint64_t*)t_inv.data(), h.p, nullptr),
-          "evaluate_h");
+    const QuotientCircuits qc(all);
+    const h2mi_quotient_scalars scalars = quotient_scalars(pk, p, y);
+    check(h2mi_plonk_evaluate_h_expr_batch_dev(&qc.rec, &scalars, H2MI_WHOLE_COSET, h.p, nullptr), "evaluate_h");
   }
   check(h2mi_ntt_bn254_fr_dev(h.p, d.extended_k(), d.get_extended_omega_inv().l, nullptr, nullptr, nullptr), "extended_to_coeff");
   check(h2mi_fr_scale_powers_dev(h.p, pk.ext, d.get_g_coset_inv().l, d.get_extended_ifft_divisor().l, nullptr), "distribute_powers_zeta");
@@ -1816,11 +1821,9 @@ void phase_quotient(const Circuits& all, const Fr& y, uint64_t* points_out) {
 void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
   const h2mi_pk_s& pk = *p.pk;
   const h2mi_constraint_system& cs = pk.cs;
-  const poly::EvaluationDomain& d = pk.domain;
-  const uint32_t bf = cs.blinding_factors, L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
+  const uint32_t L = cs.n_lookups, m = cs.n_perm, n_sets = pk.n_sets;
   DeviceVec& h = *p.h;
-  const Fr& zeta = d.get_g_coset();
-  const std::vector<Fr>& t_inv = d.t_inv();  // (X^n - 1)^-1 on the coset: cached in the domain
+  const h2mi_quotient_scalars scalars = quotient_scalars(pk, p, y);
   if (cs.gates == H2MI_GATES_STANDARD_PLONK) {
     h2mi_standard_plonk_cosets sc;
     for (int i = 0; i < 3; i++) {
@@ -1832,21 +1835,12 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
     sc.l0 = pk.l0->p;
     sc.l_last = pk.l_last->p;
     sc.l_active = pk.l_active->p;
-    check(h2mi_plonk_evaluate_h_standard_dev(&sc, d.k(), d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l,
-                                             (const uint64_t*)t_inv.data(), h.p, nullptr),
-          "evaluate_h");
+    check(h2mi_plonk_evaluate_h_standard_dev(&sc, &scalars, h.p, nullptr), "evaluate_h");
   } else if (cs.gates == H2MI_GATES_EXPRESSIONS || pk.table_logup) {
     // gates given as a program: the interpreting kernel reads any column of the proof through one pointer table.  A table-logUp key of
     // a hard-wired shape goes the same way through the shape's equivalent program, as batches do: the shapes' own kernels have no logUp term
-    h2mi_expr_cosets ec;
-    h2mi_shuffle_cosets sc;
-    h2mi_logup_cosets lg;
-    h2mi_instance_cosets ic;
-    fill_expr_cosets(p, ec, sc, lg, ic);
-    check(h2mi_plonk_evaluate_h_expr_in_dev(&ec, pk.n_shuffles ? &sc : nullptr, &lg, &ic, &pk.check_gates, p.challenge_limbs(), pk.phases.n_challenges, d.k(),
-                                            d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l,
-                                            (const uint64_t*)t_inv.data(), h.p, nullptr),
-          "evaluate_h");
+    const QuotientCircuits qc({&p});
+    check(h2mi_plonk_evaluate_h_expr_dev(&qc.rec, &scalars, h.p, nullptr), "evaluate_h");
   } else if (cs.n_gates == 1 && m >= 1 && m <= 4 && L <= 1) {
     // one gate column: the specialised kernel (its level bookkeeping is written for this shape; faster per point than the general one)
     h2mi_range_cosets rc;
@@ -1877,9 +1871,7 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
       rc.lookup_permuted_table = p.lk[0].s.coset->p;
       rc.lookup_z = p.lk[0].z.coset->p;
     }
-    check(h2mi_plonk_evaluate_h_range_dev(&rc, d.k(), d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l,
-                                          (const uint64_t*)t_inv.data(), h.p, nullptr),
-          "evaluate_h");
+    check(h2mi_plonk_evaluate_h_range_dev(&rc, &scalars, h.p, nullptr), "evaluate_h");
   } else {
     // several gate columns: the general quotient kernel (one gate per column, one lookup per lookup-advice column)
     h2mi_flex_cosets fc;
@@ -1909,9 +1901,7 @@ void evaluate_h_single(h2mi_prover_s& p, const Fr& y) {
     fc.l0 = pk.l0->p;
     fc.l_last = pk.l_last->p;
     fc.l_active = pk.l_active->p;
-    check(h2mi_plonk_evaluate_h_flex_dev(&fc, d.k(), d.extended_k(), bf, p.beta.l, p.gamma.l, y.l, pk.delta.l, zeta.l, d.get_extended_omega().l,
-                                         (const uint64_t*)t_inv.data(), h.p, nullptr),
-          "evaluate_h");
+    check(h2mi_plonk_evaluate_h_flex_dev(&fc, &scalars, h.p, nullptr), "evaluate_h");
   }
 }
 

@@ -47,11 +47,8 @@ def evaluate_h(domain: EvaluationDomain, advice, fixed, sigma, z, l0: DevBuf, l_
     for i in range(5):
         cs.fixed[i] = fixed[i].ptr
     cs.l0, cs.l_last, cs.l_active = l0.ptr, l_last.ptr, l_active.ptr
-    m = F.fr_to_mont_limbs
-    t_inv = np.ascontiguousarray(vanishing_inverses(domain))
-    args = [m(beta), m(gamma), m(y), m(FR_DELTA), m(domain.g_coset), m(domain.extended_omega)]
-    check(lib.h2mi_plonk_evaluate_h_standard_dev(C.byref(cs), domain.k, domain.extended_k, BLINDING_FACTORS, *[a.ctypes.data for a in args],
-                                                 t_inv.ctypes.data, out.ptr, stream), "evaluate_h")
+    qs = quotient_scalars(domain, beta, gamma, y)
+    check(lib.h2mi_plonk_evaluate_h_standard_dev(C.byref(cs), C.byref(qs), out.ptr, stream), "evaluate_h")
 
 
 def permutation_product(k: int, values, sigmas, column_indices, beta: int, gamma: int, usable_rows: int, d_z: DevBuf,
@@ -256,11 +253,8 @@ def evaluate_h_range(domain: EvaluationDomain, a: DevBuf, lookup_advice: DevBuf,
         cs.perm_z[s] = perm_zs[s].ptr
     cs.l0, cs.l_last, cs.l_active = l0.ptr, l_last.ptr, l_active.ptr
     cs.n_perm = m
-    mm = F.fr_to_mont_limbs
-    t_inv = np.ascontiguousarray(vanishing_inverses(domain))
-    args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
-    _check(lib.h2mi_plonk_evaluate_h_range_dev(C.byref(cs), domain.k, domain.extended_k, blinding_factors, *[x.ctypes.data for x in args],
-                                               t_inv.ctypes.data, out.ptr, None), "evaluate_h_range")
+    qs = quotient_scalars(domain, beta, gamma, y, blinding_factors)
+    _check(lib.h2mi_plonk_evaluate_h_range_dev(C.byref(cs), C.byref(qs), out.ptr, None), "evaluate_h_range")
 
 
 class _FlexCosets(C.Structure):
@@ -273,17 +267,10 @@ class _FlexCosets(C.Structure):
                 ("l0", C.c_void_p), ("l_last", C.c_void_p), ("l_active", C.c_void_p)]
 
 
-def evaluate_h_flex(domain: EvaluationDomain, gates, perm_values, perm_sigmas, perm_zs, chunk_len: int, lookups, l0: DevBuf, l_last: DevBuf,
-                    l_active: DevBuf, beta: int, gamma: int, y: int, out: DevBuf, blinding_factors: int = BLINDING_FACTORS) -> None:
-    """h(X) on the extended coset for the GENERAL halo2-base shapes (h2mi_plonk_evaluate_h_flex_dev): `gates` = [(advice coset, selector
-    coset)] (<= 32 vertical gates), the permutation argument over <= 64 columns, `lookups` = [(input coset, second input factor or None,
-    table coset, permuted input, permuted table, product)] (<= 8) — what builder.config() configures when one column overflows."""
+def _fill_arguments(cs, perm_values, perm_sigmas, perm_zs, chunk_len: int, lookups, l0: DevBuf, l_last: DevBuf, l_active: DevBuf) -> None:
+    """the permutation, lookup and Lagrange fields that h2mi_flex_cosets and h2mi_expr_cosets share"""
     m = len(perm_values)
-    assert 1 <= len(gates) <= _FlexCosets.G and m <= _FlexCosets.P and len(perm_sigmas) == m and len(perm_zs) == (-(-m // chunk_len) if m else 0) and len(lookups) <= _FlexCosets.L
-    cs = _FlexCosets()
-    cs.n_gates = len(gates)
-    for g, (a, q) in enumerate(gates):
-        cs.gate_a[g], cs.gate_q[g] = a.ptr, q.ptr
+    assert m <= _FlexCosets.P and len(perm_sigmas) == m and len(perm_zs) == (-(-m // chunk_len) if m else 0) and len(lookups) <= _FlexCosets.L
     cs.n_perm, cs.chunk_len = m, chunk_len
     for j in range(m):
         cs.perm_value[j], cs.perm_sigma[j] = perm_values[j].ptr, perm_sigmas[j].ptr
@@ -295,11 +282,21 @@ def evaluate_h_flex(domain: EvaluationDomain, gates, perm_values, perm_sigmas, p
         cs.lookup_input_b[l] = b_in.ptr if b_in is not None else None
         cs.lookup_permuted_input[l], cs.lookup_permuted_table[l], cs.lookup_z[l] = pin.ptr, ptab.ptr, z.ptr
     cs.l0, cs.l_last, cs.l_active = l0.ptr, l_last.ptr, l_active.ptr
-    mm = F.fr_to_mont_limbs
-    t_inv = np.ascontiguousarray(vanishing_inverses(domain))
-    args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
-    _check(lib.h2mi_plonk_evaluate_h_flex_dev(C.byref(cs), domain.k, domain.extended_k, blinding_factors, *[x.ctypes.data for x in args],
-                                              t_inv.ctypes.data, out.ptr, None), "evaluate_h_flex")
+
+
+def evaluate_h_flex(domain: EvaluationDomain, gates, perm_values, perm_sigmas, perm_zs, chunk_len: int, lookups, l0: DevBuf, l_last: DevBuf,
+                    l_active: DevBuf, beta: int, gamma: int, y: int, out: DevBuf, blinding_factors: int = BLINDING_FACTORS) -> None:
+    """h(X) on the extended coset for the GENERAL halo2-base shapes (h2mi_plonk_evaluate_h_flex_dev): `gates` = [(advice coset, selector
+    coset)] (<= 32 vertical gates), the permutation argument over <= 64 columns, `lookups` = [(input coset, second input factor or None,
+    table coset, permuted input, permuted table, product)] (<= 8) — what builder.config() configures when one column overflows."""
+    assert 1 <= len(gates) <= _FlexCosets.G
+    cs = _FlexCosets()
+    cs.n_gates = len(gates)
+    for g, (a, q) in enumerate(gates):
+        cs.gate_a[g], cs.gate_q[g] = a.ptr, q.ptr
+    _fill_arguments(cs, perm_values, perm_sigmas, perm_zs, chunk_len, lookups, l0, l_last, l_active)
+    qs = quotient_scalars(domain, beta, gamma, y, blinding_factors)
+    _check(lib.h2mi_plonk_evaluate_h_flex_dev(C.byref(cs), C.byref(qs), out.ptr, None), "evaluate_h_flex")
 
 
 class _ExprCosets(C.Structure):
@@ -310,86 +307,6 @@ class _ExprCosets(C.Structure):
                 ("lookup_input", C.c_void_p * L), ("lookup_input_b", C.c_void_p * L), ("lookup_table", C.c_void_p * L),
                 ("lookup_permuted_input", C.c_void_p * L), ("lookup_permuted_table", C.c_void_p * L), ("lookup_z", C.c_void_p * L),
                 ("l0", C.c_void_p), ("l_last", C.c_void_p), ("l_active", C.c_void_p)]
-
-
-def evaluate_h_expr(domain: EvaluationDomain, program, advice, fixed, instance, perm_values, perm_sigmas, perm_zs, chunk_len: int, lookups,
-                    l0: DevBuf, l_last: DevBuf, l_active: DevBuf, beta: int, gamma: int, y: int, out: DevBuf,
-                    blinding_factors: int = BLINDING_FACTORS, challenges=None) -> None:
-    """h(X) on the extended coset with the gates given as a postfix program (h2mi_plonk_evaluate_h_expr_dev): `program` an
-    engine.GateProgram over the coset forms `advice` / `fixed` (lists, None for a column the program does not read) and `instance`
-    (or None); permutation argument and lookups as evaluate_h_flex takes them, both optional.  challenges: a list of integers, the
-    values CHALLENGE ops push (h2mi_plonk_evaluate_h_expr_ch_dev); None: the entry point that knows of none."""
-    m = len(perm_values)
-    assert len(advice) <= _ExprCosets.A and len(fixed) <= _ExprCosets.Fx and m <= _ExprCosets.P and len(perm_sigmas) == m
-    assert len(perm_zs) == (-(-m // chunk_len) if m else 0) and len(lookups) <= _ExprCosets.L
-    cs = _ExprCosets()
-    for j, a in enumerate(advice):
-        cs.advice[j] = a.ptr if a is not None else None
-    for j, f in enumerate(fixed):
-        cs.fixed[j] = f.ptr if f is not None else None
-    cs.instance = instance.ptr if instance is not None else None
-    cs.n_perm, cs.chunk_len = m, chunk_len
-    for j in range(m):
-        cs.perm_value[j], cs.perm_sigma[j] = perm_values[j].ptr, perm_sigmas[j].ptr
-    for s, z in enumerate(perm_zs):
-        cs.perm_z[s] = z.ptr
-    cs.n_lookups = len(lookups)
-    for l, (a_in, b_in, table, pin, ptab, z) in enumerate(lookups):
-        cs.lookup_input[l], cs.lookup_table[l] = a_in.ptr, table.ptr
-        cs.lookup_input_b[l] = b_in.ptr if b_in is not None else None
-        cs.lookup_permuted_input[l], cs.lookup_permuted_table[l], cs.lookup_z[l] = pin.ptr, ptab.ptr, z.ptr
-    cs.l0, cs.l_last, cs.l_active = l0.ptr, l_last.ptr, l_active.ptr
-    mm = F.fr_to_mont_limbs
-    t_inv = np.ascontiguousarray(vanishing_inverses(domain))
-    args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
-    if challenges is None:
-        _check(lib.h2mi_plonk_evaluate_h_expr_dev(C.byref(cs), C.byref(program), domain.k, domain.extended_k, blinding_factors,
-                                                  *[x.ctypes.data for x in args], t_inv.ctypes.data, out.ptr, None), "evaluate_h_expr")
-    else:
-        ch = _challenge_limbs(challenges)
-        _check(lib.h2mi_plonk_evaluate_h_expr_ch_dev(C.byref(cs), C.byref(program), ch.ctypes.data, len(challenges), domain.k, domain.extended_k,
-                                                     blinding_factors, *[x.ctypes.data for x in args], t_inv.ctypes.data, out.ptr, None), "evaluate_h_expr")
-
-
-def expr_cosets_array(circuits, perm_sigmas, chunk_len: int, l0: DevBuf, l_last: DevBuf, l_active: DevBuf):
-    """-> an array of h2mi_expr_cosets, one entry per circuit of a proof.  circuits: per circuit a dict with `advice`, `fixed` (lists of
-    DevBuf, None for a column the program does not read), `instance` (or None), `perm_values`, `perm_zs`, `lookups` as evaluate_h_expr
-    takes them; what the proof shares — perm_sigmas, chunk_len, the Lagrange cosets — is given once and stated in every entry."""
-    arr = (_ExprCosets * max(len(circuits), 1))()
-    for cs, c in zip(arr, circuits):
-        m = len(c["perm_values"])
-        assert len(perm_sigmas) == m and len(c["perm_zs"]) == (-(-m // chunk_len) if m else 0)
-        for j, a in enumerate(c["advice"]):
-            cs.advice[j] = a.ptr if a is not None else None
-        for j, f in enumerate(c["fixed"]):
-            cs.fixed[j] = f.ptr if f is not None else None
-        cs.instance = c["instance"].ptr if c.get("instance") is not None else None
-        cs.n_perm, cs.chunk_len = m, chunk_len
-        for j in range(m):
-            cs.perm_value[j], cs.perm_sigma[j] = c["perm_values"][j].ptr, perm_sigmas[j].ptr
-        for s, z in enumerate(c["perm_zs"]):
-            cs.perm_z[s] = z.ptr
-        cs.n_lookups = len(c["lookups"])
-        for l, (a_in, b_in, table, pin, ptab, z) in enumerate(c["lookups"]):
-            cs.lookup_input[l], cs.lookup_table[l] = a_in.ptr, table.ptr
-            cs.lookup_input_b[l] = b_in.ptr if b_in is not None else None
-            cs.lookup_permuted_input[l], cs.lookup_permuted_table[l], cs.lookup_z[l] = pin.ptr, ptab.ptr, z.ptr
-        cs.l0, cs.l_last, cs.l_active = l0.ptr, l_last.ptr, l_active.ptr
-    return arr
-
-
-def evaluate_h_expr_batch(domain: EvaluationDomain, program, cosets, n_circuits: int, beta: int, gamma: int, y: int, out: DevBuf,
-                          blinding_factors: int = BLINDING_FACTORS, challenges=()) -> None:
-    """h(X) of SEVERAL circuits in one proof (h2mi_plonk_evaluate_h_expr_batch_dev): one accumulator folded with y over every circuit's
-    gate, permutation and lookup terms in circuit order, one division by X^n - 1.  cosets: expr_cosets_array's result (the first
-    n_circuits entries are read); program and challenges are the proof's."""
-    mm = F.fr_to_mont_limbs
-    t_inv = np.ascontiguousarray(vanishing_inverses(domain))
-    args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
-    ch = _challenge_limbs(challenges)
-    _check(lib.h2mi_plonk_evaluate_h_expr_batch_dev(cosets, n_circuits, C.byref(program), ch.ctypes.data if len(challenges) else None, len(challenges),
-                                                    domain.k, domain.extended_k, blinding_factors, *[x.ctypes.data for x in args], t_inv.ctypes.data,
-                                                    out.ptr, None), "evaluate_h_expr_batch")
 
 
 class _ShuffleCosets(C.Structure):
@@ -405,6 +322,87 @@ class _InstanceCosets(C.Structure):
 class _LogupCosets(C.Structure):
     """include/h2mi.h h2mi_logup_cosets"""
     _fields_ = [("n_inputs", C.c_uint32 * _ExprCosets.L)]
+
+
+# The three argument records of include/h2mi.h, field for field (tests/test_quotient_records_host.py compares the layouts with the C
+# compiler's).  A record built by the helpers below holds what its pointers name in `_keep`.
+class QuotientScalars(C.Structure):
+    """include/h2mi.h h2mi_quotient_scalars"""
+    _fields_ = [("k", C.c_uint32), ("extended_k", C.c_uint32), ("blinding_factors", C.c_uint32), ("beta", C.c_void_p), ("gamma", C.c_void_p),
+                ("y", C.c_void_p), ("delta", C.c_void_p), ("zeta", C.c_void_p), ("extended_omega", C.c_void_p), ("t_inv", C.c_void_p)]
+
+
+class QuotientCircuits(C.Structure):
+    """include/h2mi.h h2mi_quotient_circuits"""
+    _fields_ = [("circuits", C.c_void_p), ("n_circuits", C.c_uint32), ("shuffles", C.c_void_p), ("logup", C.c_void_p), ("instances", C.c_void_p),
+                ("gates", C.c_void_p), ("challenges", C.c_void_p), ("n_challenges", C.c_uint32)]
+
+
+class ExprColumns(C.Structure):
+    """include/h2mi.h h2mi_expr_columns"""
+    _fields_ = [("advice", C.c_void_p), ("n_advice", C.c_uint32), ("fixed", C.c_void_p), ("n_fixed", C.c_uint32), ("instances", C.c_void_p),
+                ("program", C.c_void_p), ("challenges", C.c_void_p), ("n_challenges", C.c_uint32), ("k", C.c_uint32)]
+
+
+def _addr(obj):
+    return C.addressof(obj) if obj is not None else None
+
+
+def _challenge_limbs(challenges):
+    """-> (the values as n x 4 Montgomery limbs or None, n)"""
+    if challenges is None or len(challenges) == 0:
+        return None, 0
+    return np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in challenges])), len(challenges)
+
+
+def quotient_scalars(domain: EvaluationDomain, beta: int, gamma: int, y: int, blinding_factors: int = BLINDING_FACTORS) -> QuotientScalars:
+    """the h2mi_quotient_scalars of a domain and a transcript's beta, gamma, y: DELTA, the coset generator, extended_omega and the
+    inverses of X^n - 1 on the coset are the domain's"""
+    bufs = [F.fr_to_mont_limbs(v) for v in (beta, gamma, y, FR_DELTA, domain.g_coset, domain.extended_omega)]
+    bufs.append(np.ascontiguousarray(vanishing_inverses(domain)))
+    qs = QuotientScalars(domain.k, domain.extended_k, blinding_factors, *[b.ctypes.data for b in bufs])
+    qs._keep = bufs
+    return qs
+
+
+def quotient_circuits(program, cosets, n_circuits: int, challenges=(), shuffles=None, logup=None, instances=None) -> QuotientCircuits:
+    """the h2mi_quotient_circuits of a proof: `cosets` an h2mi_expr_cosets or an array of them (expr_cosets_array), `shuffles`, `logup`,
+    `instances` as argument_cosets gives them (each may be None), `challenges` a list of integers (None or empty: none)"""
+    ch, n_ch = _challenge_limbs(challenges)
+    qc = QuotientCircuits(_addr(cosets), n_circuits, _addr(shuffles), _addr(logup), _addr(instances), _addr(program),
+                          ch.ctypes.data if ch is not None else None, n_ch)
+    qc._keep = (cosets, shuffles, logup, instances, program, ch)
+    return qc
+
+
+def expr_columns(program, advice, fixed, instance, k: int, challenges=None) -> ExprColumns:
+    """the h2mi_expr_columns of a program over `advice` / `fixed` (lists of DevBuf, None for a column the program does not read) on one
+    domain; `instance`: a DevBuf or None (the one instance column), or an h2mi_instance_cosets"""
+    ptrs = lambda cols: (C.c_void_p * max(len(cols), 1))(*[c.ptr if c is not None else None for c in cols])
+    adv, fix = ptrs(advice), ptrs(fixed)
+    if not isinstance(instance, _InstanceCosets):
+        instance = _InstanceCosets(1, (C.c_void_p * 8)(instance.ptr if instance is not None else None))
+    ch, n_ch = _challenge_limbs(challenges)
+    ec = ExprColumns(C.addressof(adv), len(advice), C.addressof(fix), len(fixed), C.addressof(instance), _addr(program),
+                     ch.ctypes.data if ch is not None else None, n_ch, k)
+    ec._keep = (adv, fix, instance, program, ch)
+    return ec
+
+
+def expr_cosets_array(circuits, perm_sigmas, chunk_len: int, l0: DevBuf, l_last: DevBuf, l_active: DevBuf):
+    """-> an array of h2mi_expr_cosets, one entry per circuit of a proof.  circuits: per circuit a dict with `advice`, `fixed` (lists of
+    DevBuf, None for a column the program does not read), `instance` (or None), `perm_values`, `perm_zs`, `lookups` as evaluate_h_flex
+    takes them; what the proof shares — perm_sigmas, chunk_len, the Lagrange cosets — is given once and stated in every entry."""
+    arr = (_ExprCosets * max(len(circuits), 1))()
+    for cs, c in zip(arr, circuits):
+        assert len(c["advice"]) <= _ExprCosets.A and len(c["fixed"]) <= _ExprCosets.Fx
+        for j, a in enumerate(c["advice"]):
+            cs.advice[j] = a.ptr if a is not None else None
+        for j, f in enumerate(c["fixed"]):
+            cs.fixed[j] = f.ptr if f is not None else None
+        cs.instance = c["instance"].ptr if c.get("instance") is not None else None
+        _fill_arguments(cs, c["perm_values"], perm_sigmas, c["perm_zs"], chunk_len, c["lookups"], l0, l_last, l_active)
+    return arr
 
 
 def argument_cosets(circuits, logup_sets=None):
@@ -428,54 +426,55 @@ def argument_cosets(circuits, logup_sets=None):
     return (shs if any(sh.n_shuffles for sh in shs) else None), lg, ins
 
 
+def evaluate_h_expr(domain: EvaluationDomain, program, advice, fixed, instance, perm_values, perm_sigmas, perm_zs, chunk_len: int, lookups,
+                    l0: DevBuf, l_last: DevBuf, l_active: DevBuf, beta: int, gamma: int, y: int, out: DevBuf,
+                    blinding_factors: int = BLINDING_FACTORS, challenges=None, shuffles=None, logup=None, instances=None) -> None:
+    """h(X) on the extended coset of ONE circuit with the gates given as a postfix program (h2mi_plonk_evaluate_h_expr_dev): `program` an
+    engine.GateProgram over the coset forms `advice` / `fixed` (lists, None for a column the program does not read) and `instance`
+    (or None); permutation argument and lookups as evaluate_h_flex takes them, both optional.  challenges: a list of integers, the
+    values CHALLENGE ops push (None: none); shuffles, logup, instances: argument_cosets' results for this one circuit."""
+    cosets = expr_cosets_array([dict(advice=advice, fixed=fixed, instance=instance, perm_values=perm_values, perm_zs=perm_zs, lookups=lookups)],
+                               perm_sigmas, chunk_len, l0, l_last, l_active)
+    qc = quotient_circuits(program, cosets, 1, challenges, shuffles, logup, instances)
+    qs = quotient_scalars(domain, beta, gamma, y, blinding_factors)
+    _check(lib.h2mi_plonk_evaluate_h_expr_dev(C.byref(qc), C.byref(qs), out.ptr, None), "evaluate_h_expr")
+
+
 def evaluate_h_expr_slice(domain: EvaluationDomain, program, cosets, n_circuits: int, slice_index, beta: int, gamma: int, y: int, out: DevBuf,
                           blinding_factors: int = BLINDING_FACTORS, challenges=(), shuffles=None, logup=None, instances=None) -> None:
-    """h2mi_plonk_evaluate_h_expr_slice_dev: the numerator of the circuits on ONE coset of 2^k points — every column of `cosets`
-    (expr_cosets_array), `shuffles`, `logup` and `instances` (argument_cosets) is slice `slice_index` of its extended-coset vector
+    """h2mi_plonk_evaluate_h_expr_batch_dev with a slice: the numerator of the circuits on ONE coset of 2^k points — every column of
+    `cosets` (expr_cosets_array), `shuffles`, `logup` and `instances` (argument_cosets) is slice `slice_index` of its extended-coset vector
     (coeff_to_slice_oop_dev), `out` the whole vector of 2^extended_k elements, of which elements slice_index + rot i are written.
-    slice_index None: the resident call over whole extended-coset vectors (h2mi_plonk_evaluate_h_expr_batch_in_dev), same arguments."""
-    mm = F.fr_to_mont_limbs
-    t_inv = np.ascontiguousarray(vanishing_inverses(domain))
-    args = [mm(beta), mm(gamma), mm(y), mm(FR_DELTA), mm(domain.g_coset), mm(domain.extended_omega)]
-    ch = _challenge_limbs(challenges)
-    head = (cosets, shuffles, C.byref(logup) if logup is not None else None, instances, n_circuits, C.byref(program),
-            ch.ctypes.data if len(challenges) else None, len(challenges), domain.k, domain.extended_k, blinding_factors, *[x.ctypes.data for x in args],
-            t_inv.ctypes.data)
-    if slice_index is None:
-        _check(lib.h2mi_plonk_evaluate_h_expr_batch_in_dev(*head, out.ptr, None), "evaluate_h_expr_batch_in")
-    else:
-        _check(lib.h2mi_plonk_evaluate_h_expr_slice_dev(*head, slice_index, out.ptr, None), "evaluate_h_expr_slice")
+    slice_index None: the resident call over whole extended-coset vectors (H2MI_WHOLE_COSET), same arguments."""
+    qc = quotient_circuits(program, cosets, n_circuits, challenges, shuffles, logup, instances)
+    qs = quotient_scalars(domain, beta, gamma, y, blinding_factors)
+    _check(lib.h2mi_plonk_evaluate_h_expr_batch_dev(C.byref(qc), C.byref(qs), -1 if slice_index is None else slice_index, out.ptr, None),
+           "evaluate_h_expr_batch" if slice_index is None else "evaluate_h_expr_slice")
 
 
-def _challenge_limbs(challenges) -> np.ndarray:
-    return np.ascontiguousarray(np.stack([F.fr_to_mont_limbs(v) for v in challenges])) if len(challenges) else np.zeros((1, 4), dtype=np.uint64)
+def evaluate_h_expr_batch(domain: EvaluationDomain, program, cosets, n_circuits: int, beta: int, gamma: int, y: int, out: DevBuf,
+                          blinding_factors: int = BLINDING_FACTORS, challenges=(), shuffles=None, logup=None, instances=None) -> None:
+    """h(X) of SEVERAL circuits in one proof (h2mi_plonk_evaluate_h_expr_batch_dev): one accumulator folded with y over every circuit's
+    gate, permutation, lookup and shuffle terms in circuit order, one division by X^n - 1.  cosets: expr_cosets_array's result (the first
+    n_circuits entries are read); program and challenges are the proof's; shuffles, logup, instances: argument_cosets' results."""
+    evaluate_h_expr_slice(domain, program, cosets, n_circuits, None, beta, gamma, y, out, blinding_factors, challenges, shuffles, logup, instances)
 
 
 def expr_compress(program, advice, fixed, instance, k: int, domain_k: int, theta: int, out: DevBuf, challenges=None) -> None:
     """h2mi_plonk_expr_compress_dev: out[i] = sum_j e_j(i) theta^(m-1-j) over the m polynomials of `program` (an engine.GateProgram) on
-    the 2^domain_k points the columns are given on (lists of DevBuf, None for a column the program does not read).  challenges: as
-    evaluate_h_expr takes them (h2mi_plonk_expr_compress_ch_dev)."""
-    ptrs = lambda cols: (C.c_void_p * max(len(cols), 1))(*[c.ptr if c is not None else None for c in cols])
-    if challenges is not None:
-        ch = _challenge_limbs(challenges)
-        _check(lib.h2mi_plonk_expr_compress_ch_dev(ptrs(advice), len(advice), ptrs(fixed), len(fixed), instance.ptr if instance is not None else None,
-                                                   C.byref(program), ch.ctypes.data, len(challenges), k, domain_k, F.fr_to_mont_limbs(theta).ctypes.data,
-                                                   out.ptr, None), "expr_compress")
-        return
-    _check(lib.h2mi_plonk_expr_compress_dev(ptrs(advice), len(advice), ptrs(fixed), len(fixed), instance.ptr if instance is not None else None,
-                                            C.byref(program), k, domain_k, F.fr_to_mont_limbs(theta).ctypes.data, out.ptr, None), "expr_compress")
+    the 2^domain_k points the columns are given on (expr_columns' arguments); challenges: as evaluate_h_expr takes them."""
+    cols = expr_columns(program, advice, fixed, instance, k, challenges)
+    _check(lib.h2mi_plonk_expr_compress_dev(C.byref(cols), domain_k, F.fr_to_mont_limbs(theta).ctypes.data, out.ptr, None), "expr_compress")
 
 
 def expr_check(program, advice, fixed, instance, k: int, n_rows: int = None, challenges=None):
-    """h2mi_plonk_expr_check_ch_dev: per polynomial of `program` (an engine.GateProgram) -> (the number of rows below n_rows on which it
+    """h2mi_plonk_expr_check_dev: per polynomial of `program` (an engine.GateProgram) -> (the number of rows below n_rows on which it
     is not zero, the smallest such row or 0xffffffff); columns on the 2^k rows as expr_compress takes them, n_rows = 2^k by default"""
-    ptrs = lambda cols: (C.c_void_p * max(len(cols), 1))(*[c.ptr if c is not None else None for c in cols])
-    ch = _challenge_limbs(challenges) if challenges else None
+    cols = expr_columns(program, advice, fixed, instance, k, challenges)
     report = np.zeros((max(sum(1 for i in range(program.n_ops) if program.ops[i].op == 8), 1), 2), dtype=np.uint32)
     n_polys = C.c_uint32()
-    _check(lib.h2mi_plonk_expr_check_ch_dev(ptrs(advice), len(advice), ptrs(fixed), len(fixed), instance.ptr if instance is not None else None,
-                                            C.byref(program), ch.ctypes.data if ch is not None else None, len(challenges) if challenges else 0, k,
-                                            (1 << k) if n_rows is None else n_rows, report.ctypes.data, C.byref(n_polys), None), "expr_check")
+    _check(lib.h2mi_plonk_expr_check_dev(C.byref(cols), (1 << k) if n_rows is None else n_rows, report.ctypes.data, C.byref(n_polys), None),
+           "expr_check")
     return [(int(c), int(f)) for c, f in report[: n_polys.value]]
 
 

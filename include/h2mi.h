@@ -455,9 +455,18 @@ int h2mi_fr_random_chacha_dev(void* d_out, size_t n, const uint8_t key[32], uint
 /* ---- quotient numerator for the reference's StandardPlonk circuit -------------------------
  * halo2_proofs plonk/evaluation.rs `evaluate_h` + vanishing division, specialised to the circuit of reference
  * src/circuits/standard_plonk.rs (one degree-3 gate over 3 advice + 5 fixed columns, 3 permutation sets of one
- * column).  All vectors are extended-domain evaluations (2^extended_k elements) resident in HBM. t_inv holds the
- * 2^(extended_k - k) values of (X^n - 1)^-1 on the coset.  The result (h on the extended coset, already divided)
- * goes to d_h_out; h2mi_ntt_bn254_fr_dev + h2mi_fr_scale_powers_dev bring it to coefficients. */
+ * column).  All vectors are extended-domain evaluations (2^extended_k elements) resident in HBM.  The result (h on
+ * the extended coset, already divided) goes to d_h_out; h2mi_ntt_bn254_fr_dev + h2mi_fr_scale_powers_dev bring it
+ * to coefficients. */
+/* What every quotient call knows of the domain and the transcript, in the order of evaluate_h's own parameters.  Every
+ * pointer: 4 limbs, Montgomery, host memory; t_inv: the 2^(extended_k - k) values of (X^n - 1)^-1 on the coset, 4 limbs
+ * each.  Every quotient call refuses a NULL record or a NULL field of it with H2MI_EINVAL, and extended_k < k,
+ * extended_k - k > 4 or extended_k > H2MI_MAX_LOG_N with H2MI_ERANGE. */
+typedef struct {
+  uint32_t k, extended_k, blinding_factors;
+  const uint64_t *beta, *gamma, *y, *delta, *zeta, *extended_omega;
+  const uint64_t* t_inv;
+} h2mi_quotient_scalars;
 typedef struct {
   const void* advice[3];  /* a, b, c */
   const void* fixed[5];   /* q_a, q_b, q_c, q_ab, constant */
@@ -467,11 +476,8 @@ typedef struct {
   const void* l_last;
   const void* l_active;
 } h2mi_standard_plonk_cosets;
-int h2mi_plonk_evaluate_h_standard_dev(const h2mi_standard_plonk_cosets* cosets, uint32_t k, uint32_t extended_k,
-                                       uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
-                                       const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
-                                       const uint64_t extended_omega[4], const uint64_t* t_inv /* 2^(extended_k-k) x 4 */,
-                                       void* d_h_out, h2mi_stream_t stream);
+int h2mi_plonk_evaluate_h_standard_dev(const h2mi_standard_plonk_cosets* cosets, const h2mi_quotient_scalars* scalars, void* d_h_out,
+                                       h2mi_stream_t stream);
 
 /* the permutation argument's grand-product column for one chunk of m <= 64 columns (plonk/permutation/prover.rs,
  * the z vectors are produced where they are consumed): z[0] = start (one if NULL),
@@ -645,10 +651,7 @@ typedef struct {
   uint32_t chunk_len;          /* 1, 2 or 3 */
   uint32_t has_lookup;         /* 0: gate + permutation terms only */
 } h2mi_range_cosets;
-int h2mi_plonk_evaluate_h_range_dev(const h2mi_range_cosets* cosets, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
-                                    const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
-                                    const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv /* 2^(extended_k-k) x 4 */,
-                                    void* d_h_out, h2mi_stream_t stream);
+int h2mi_plonk_evaluate_h_range_dev(const h2mi_range_cosets* cosets, const h2mi_quotient_scalars* scalars, void* d_h_out, h2mi_stream_t stream);
 
 /* The general form of the halo2-base constraint systems (round 4; the column limits below from round 5): what
  * `builder.config(k, Some(minimum_rows))` (src/scaffold.rs:268) configures when the cells overflow ONE advice column — n_gates <=
@@ -681,10 +684,7 @@ typedef struct {
   const void* l_last;
   const void* l_active;
 } h2mi_flex_cosets;
-int h2mi_plonk_evaluate_h_flex_dev(const h2mi_flex_cosets* cosets, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
-                                   const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
-                                   const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv /* 2^(extended_k-k) x 4 */,
-                                   void* d_h_out, h2mi_stream_t stream);
+int h2mi_plonk_evaluate_h_flex_dev(const h2mi_flex_cosets* cosets, const h2mi_quotient_scalars* scalars, void* d_h_out, h2mi_stream_t stream);
 
 /* Gates given as DATA: the polynomials of `meta.create_gate(...)` (reference src/circuits/is_zero.rs, or.rs) as a postfix program that
  * one kernel interprets on the extended coset, in front of the permutation and lookup terms of the general form above.
@@ -696,7 +696,7 @@ enum { H2MI_EXPR_ADVICE = 0, H2MI_EXPR_FIXED = 1, H2MI_EXPR_INSTANCE = 2,   /* =
        H2MI_EXPR_ADD, H2MI_EXPR_SUB, H2MI_EXPR_MUL, H2MI_EXPR_NEG,          /* on the top of the stack */
        H2MI_EXPR_END,                                                      /* the one value left is this polynomial */
        H2MI_EXPR_CHALLENGE };                                              /* push challenge `index` (rotation ignored): Expression::Challenge,
-                                                                              degree 0.  Known only to the entry points that take challenges */
+                                                                              degree 0.  index < the n_challenges of the call's record */
 #define H2MI_MAX_EXPR_OPS 4096
 #define H2MI_MAX_EXPR_CONSTANTS 256
 #define H2MI_MAX_EXPR_STACK 8
@@ -735,43 +735,10 @@ typedef struct {
  * and a lookup contributes three terms in the place of its five, Horner in y: l_0 phi, l_last phi, l_active ((phi(wX) - phi(X)) (A +
  * beta)(S + beta) - ((S + beta) - M (A + beta))); gamma is not read.  In a batch every entry states the same mode. */
 #define H2MI_LOOKUPS_LOGUP 0x80000000u
-/* H2MI_EINVAL for a program that is malformed (unknown op, stack underflow or deeper than H2MI_MAX_EXPR_STACK, not exactly one value
- * at an END, no final END, empty), reads a NULL column or a constant beyond n_constants, or rotates by 2^k or more.  The column
- * pointers, the program and its constants (converted to the kernel's domain) travel in one device buffer written on `stream`. */
-int h2mi_plonk_evaluate_h_expr_dev(const h2mi_expr_cosets* cosets, const h2mi_gate_program* gates, uint32_t k, uint32_t extended_k,
-                                   uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
-                                   const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
-                                   const uint64_t* t_inv /* 2^(extended_k-k) x 4 */, void* d_h_out, h2mi_stream_t stream);
-/* The same with the values of the circuit's challenges: n_challenges x 4 limbs, Montgomery, n_challenges <= H2MI_MAX_CHALLENGES (NULL
- * with 0).  An H2MI_EXPR_CHALLENGE op pushes challenges[index]; index >= n_challenges is H2MI_EINVAL.  The values travel behind the
- * program's constants in the launch's one device buffer.  The call above is this one with no challenges: a CHALLENGE op is H2MI_EINVAL
- * there. */
-int h2mi_plonk_evaluate_h_expr_ch_dev(const h2mi_expr_cosets* cosets, const h2mi_gate_program* gates, const uint64_t* challenges,
-                                      uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
-                                      const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
-                                      const uint64_t extended_omega[4], const uint64_t* t_inv /* 2^(extended_k-k) x 4 */, void* d_h_out,
-                                      h2mi_stream_t stream);
-/* Several circuits of one proof [RECALL halo2_proofs v2023_02_02 plonk/evaluation.rs evaluate_h]: ONE accumulator walks circuits[0 ..
- * n_circuits - 1] in order, per circuit acc = acc y + term over its gate polynomials, its permutation terms and its lookup terms, and
- * the division by X^n - 1 comes behind the last circuit — one launch and one pass over d_h_out whatever n_circuits is.  The program,
- * its constants and the challenges are the proof's; an entry holds what belongs to one circuit (advice, instance, perm_value, perm_z,
- * the six vectors of each lookup).  What the circuits share — fixed, perm_sigma, l0, l_last, l_active — is stated in every entry:
- * perm_sigma and the three Lagrange cosets are read from entry 0 and must be the same pointers in the others; two entries may share
- * any other pointer too (the same advice twice is folded twice).  The entries travel as consecutive records behind the program in the
- * launch's one device buffer.  H2MI_EINVAL: n_circuits == 0 or > H2MI_MAX_CIRCUITS; entries that disagree in n_perm, chunk_len or
- * n_lookups; whatever the call above refuses, in any entry.  With n_circuits == 1 the words of d_h_out are that call's. */
-#define H2MI_MAX_CIRCUITS 8
-int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_expr_cosets* circuits, uint32_t n_circuits, const h2mi_gate_program* gates,
-                                         const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
-                                         uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
-                                         const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
-                                         const uint64_t* t_inv /* 2^(extended_k-k) x 4 */, void* d_h_out, h2mi_stream_t stream);
-/* The two calls above with shuffle arguments [RECALL halo2_proofs (PSE line) plonk/shuffle.rs, plonk/evaluation.rs — restated from
- * memory, pinned to DESIGN.md 4.5]: behind a circuit's lookup terms, per shuffle, l_0 (1 - z), l_last (z^2 - z), l_active (z(wX) (S +
- * gamma) - z(X) (A + gamma)), Horner in y; beta is not read.  input / shuffle: both sides compressed with theta on the extended coset
- * (h2mi_plonk_expr_compress_dev at domain_k = extended_k); z: the product's extended-coset form.  `shuffles` is one entry (the batch
- * call: n_circuits entries, all with the same n_shuffles) or NULL, which is the call above word for word.  H2MI_EINVAL: n_shuffles >
- * H2MI_MAX_SHUFFLES, a NULL vector. */
+/* Shuffle arguments of one circuit [RECALL halo2_proofs (PSE line) plonk/shuffle.rs, plonk/evaluation.rs — restated from memory, pinned
+ * to DESIGN.md 4.5]: behind the circuit's lookup terms, per shuffle, l_0 (1 - z), l_last (z^2 - z), l_active (z(wX) (S + gamma) - z(X) (A +
+ * gamma)), Horner in y; beta is not read.  input / shuffle: both sides compressed with theta on the extended coset
+ * (h2mi_plonk_expr_compress_dev at domain_k = extended_k); z: the product's extended-coset form. */
 #define H2MI_MAX_SHUFFLES 8
 typedef struct {
   uint32_t n_shuffles;
@@ -779,113 +746,105 @@ typedef struct {
   const void* shuffle[H2MI_MAX_SHUFFLES];
   const void* z[H2MI_MAX_SHUFFLES];
 } h2mi_shuffle_cosets;
-int h2mi_plonk_evaluate_h_expr_sh_dev(const h2mi_expr_cosets* cosets, const h2mi_shuffle_cosets* shuffles, const h2mi_gate_program* gates,
-                                      const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
-                                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
-                                      const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out,
-                                      h2mi_stream_t stream);
-int h2mi_plonk_evaluate_h_expr_batch_sh_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, uint32_t n_circuits,
-                                            const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k,
-                                            uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
-                                            const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
-                                            const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream);
-/* The two calls above for logUp lookups with SEVERAL INPUT SETS over one table [restated from memory, pinned to DESIGN.md 4.5 and
- * tests/logup_sets_cases.py].  `logup` states per lookup the number K of input tuples, 1 .. H2MI_MAX_LOGUP_INPUTS; lookup_input[l] then
- * points at K CONSECUTIVE extended-coset vectors (set j at element j 2^extended_k), each compressed with theta, and the lookup's third
- * term is l_active ((phi(wX) - phi(X)) D - N) with (N, D) from the recurrence (N, D) = (-M, S + beta), then per input N <- N (A_j + beta)
- * + D, D <- D (A_j + beta).  h2mi_expr_cosets keeps its layout and the meaning of every field.  `logup` is one struct for the call (the
- * batch call: for every circuit) or NULL; NULL or all ones is the call above word for word.  Counts beyond n_lookups are not read.
- * H2MI_EINVAL: a count of 0 or above the maximum; a count other than 1 without H2MI_LOOKUPS_LOGUP. */
+/* logUp lookups with SEVERAL INPUT SETS over one table [restated from memory, pinned to DESIGN.md 4.5 and tests/logup_sets_cases.py]:
+ * per lookup the number K of input tuples, 1 .. H2MI_MAX_LOGUP_INPUTS.  lookup_input[l] then points at K CONSECUTIVE vectors (set j at
+ * element j 2^extended_k), each compressed with theta, and the lookup's third term is l_active ((phi(wX) - phi(X)) D - N) with (N, D)
+ * from the recurrence (N, D) = (-M, S + beta), then per input N <- N (A_j + beta) + D, D <- D (A_j + beta).  h2mi_expr_cosets keeps its
+ * layout and the meaning of every field.  One struct holds for every circuit of a proof; counts beyond n_lookups are not read. */
 typedef struct {
   uint32_t n_inputs[H2MI_FLEX_MAX_LOOKUPS];
 } h2mi_logup_cosets;
-int h2mi_plonk_evaluate_h_expr_lg_dev(const h2mi_expr_cosets* cosets, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                      const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
-                                      uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
-                                      const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
-                                      void* d_h_out, h2mi_stream_t stream);
-int h2mi_plonk_evaluate_h_expr_batch_lg_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                            uint32_t n_circuits, const h2mi_gate_program* gates, const uint64_t* challenges, uint32_t n_challenges,
-                                            uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4],
-                                            const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4],
-                                            const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream);
-/* The two calls above for a circuit with SEVERAL INSTANCE COLUMNS (up to H2MI_MAX_INSTANCE: `meta.instance_column()` called more than
- * once).  An H2MI_EXPR_INSTANCE op carries the column's index as the advice and fixed queries do; the interpreter's pointer table holds
- * instance column i behind the advice and fixed columns, in slot H2MI_EXPR_MAX_ADVICE + H2MI_EXPR_MAX_FIXED + i.  h2mi_expr_cosets keeps its
- * layout: its one `instance` pointer is column 0 of every call that takes no `instances`.  `instances` is one entry (the batch call:
- * n_circuits entries, one per circuit) or NULL; with it, cosets->instance is not read and column i of the circuit is column[i] (a column the
- * program does not read may be NULL).  NULL is the call above word for word, and so is an entry {1, {cosets->instance}}.
- * H2MI_EINVAL: n_instance > H2MI_MAX_INSTANCE; a query of a column at or beyond n_instance, or of a NULL column. */
+/* The instance columns of one circuit (up to H2MI_MAX_INSTANCE: `meta.instance_column()` called more than once).  An H2MI_EXPR_INSTANCE
+ * op carries the column's index as the advice and fixed queries do; the interpreter's pointer table holds instance column i behind the
+ * advice and fixed columns, in slot H2MI_EXPR_MAX_ADVICE + H2MI_EXPR_MAX_FIXED + i.  A column the program does not read may be NULL. */
 typedef struct {
   uint32_t n_instance;
   const void* column[H2MI_MAX_INSTANCE];
 } h2mi_instance_cosets;
-int h2mi_plonk_evaluate_h_expr_in_dev(const h2mi_expr_cosets* cosets, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                      const h2mi_instance_cosets* instances, const h2mi_gate_program* gates, const uint64_t* challenges,
-                                      uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors, const uint64_t beta[4],
-                                      const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4], const uint64_t zeta[4],
-                                      const uint64_t extended_omega[4], const uint64_t* t_inv, void* d_h_out, h2mi_stream_t stream);
-int h2mi_plonk_evaluate_h_expr_batch_in_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                            const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
-                                            const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k,
-                                            uint32_t blinding_factors, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
-                                            const uint64_t delta[4], const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv,
-                                            void* d_h_out, h2mi_stream_t stream);
-
-/* The same numerator ONE COSET at a time (the quotient of a key made with H2MI_KEYGEN_BY_COSET, include/h2mi_prover.h).  With
- * rot = 2^(extended_k - k), extended-coset point slice + rot i is X = (zeta extended_omega^slice) omega^i, omega = extended_omega^rot:
- * the 2^extended_k evaluations of a polynomial of degree < 2^k are rot coset transforms of 2^k points, one per shift.  The arguments are
- * the call's above and `slice` < rot; every column pointer — of `circuits`, `shuffles`, `instances` — is the 2^k-element slice `slice` of
- * the vector the call above takes: element i the value at extended-coset point slice + rot i, which for a column is
- * h2mi_ntt_bn254_fr_oop_dev(coefficients, 2^k, out, k, omega, pre = zeta extended_omega^slice).  A query at rotation r reads element
- * (i + r) mod 2^k of the same slice; a compressed side is h2mi_plonk_expr_compress_in_dev over the slices with domain_k = k; input set j of
- * a logUp lookup lies j 2^k elements behind lookup_input[l] (the call above: j 2^extended_k).  zeta, extended_omega and the rot values
- * of t_inv are the DOMAIN'S, as for the call above.  d_h_out is the whole vector of 2^extended_k elements: the call writes elements
- * slice + rot i, i < 2^k, each word for word what the call above stores there, and no other; rot calls, one per slice, fill it.
- * H2MI_ERANGE: slice >= rot. */
-int h2mi_plonk_evaluate_h_expr_slice_dev(const h2mi_expr_cosets* circuits, const h2mi_shuffle_cosets* shuffles, const h2mi_logup_cosets* logup,
-                                         const h2mi_instance_cosets* instances, uint32_t n_circuits, const h2mi_gate_program* gates,
-                                         const uint64_t* challenges, uint32_t n_challenges, uint32_t k, uint32_t extended_k, uint32_t blinding_factors,
-                                         const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], const uint64_t delta[4],
-                                         const uint64_t zeta[4], const uint64_t extended_omega[4], const uint64_t* t_inv, uint32_t slice, void* d_h_out,
+/* The circuits of one proof for the interpreting kernels.  circuits, gates: required.  The program, its constants and the challenges
+ * are the proof's; an entry of `circuits` holds what belongs to one circuit (advice, instance, perm_value, perm_z, the six vectors of
+ * each lookup).  What the circuits share — fixed, perm_sigma, l0, l_last, l_active — is stated in every entry: perm_sigma and the three
+ * Lagrange cosets are read from entry 0 and must be the same pointers in the others; two entries may share any other pointer too (the
+ * same advice twice is folded twice).
+ *   shuffles    NULL (no shuffle: the same words as n_shuffles == 0 in every entry), or n_circuits entries with one n_shuffles
+ *   logup       NULL (one input set per lookup: the same words as all ones), or one struct for the proof
+ *   instances   NULL (circuits[i].instance is column 0 and the only one: the same words as {1, {circuits[i].instance}}), or n_circuits
+ *               entries; circuits[i].instance is not read then
+ *   challenges  n_challenges x 4 limbs, Montgomery, host, n_challenges <= H2MI_MAX_CHALLENGES; NULL with 0.  An H2MI_EXPR_CHALLENGE op
+ *               pushes challenges[index] */
+#define H2MI_MAX_CIRCUITS 8
+typedef struct {
+  const h2mi_expr_cosets* circuits;      uint32_t n_circuits;
+  const h2mi_shuffle_cosets* shuffles;
+  const h2mi_logup_cosets* logup;
+  const h2mi_instance_cosets* instances;
+  const h2mi_gate_program* gates;
+  const uint64_t* challenges;            uint32_t n_challenges;
+} h2mi_quotient_circuits;
+/* The quotient of ONE circuit (k_evaluate_h_expr): n_circuits must be 1.  Terms in evaluate_h's order, Horner in y: the gate
+ * polynomials, the permutation terms, the lookup terms, the shuffle terms; then the division by X^n - 1.  The column pointers, the
+ * program, its constants and behind them the challenges (converted to the kernel's domain) travel in one device buffer written on
+ * `stream`.
+ * H2MI_EINVAL: a NULL record, a NULL required field or d_h_out; n_circuits != 1; a program that is malformed (unknown op, stack
+ * underflow or deeper than H2MI_MAX_EXPR_STACK, not exactly one value at an END, no final END, empty), reads a NULL column, a constant
+ * beyond n_constants, a challenge at or beyond n_challenges or an instance column at or beyond n_instance, or rotates by 2^k or more;
+ * n_perm, n_lookups, n_shuffles, n_instance or n_challenges above its maximum; a NULL vector of a stated permutation column, lookup or
+ * shuffle; a logUp count of 0 or above H2MI_MAX_LOGUP_INPUTS, or other than 1 without H2MI_LOOKUPS_LOGUP.  H2MI_ERANGE: the scalars'. */
+int h2mi_plonk_evaluate_h_expr_dev(const h2mi_quotient_circuits* circuits, const h2mi_quotient_scalars* scalars, void* d_h_out,
+                                   h2mi_stream_t stream);
+/* The quotient of 1 .. H2MI_MAX_CIRCUITS circuits of one proof [RECALL halo2_proofs v2023_02_02 plonk/evaluation.rs evaluate_h]: ONE
+ * accumulator walks circuits[0 .. n_circuits - 1] in order, per circuit acc = acc y + term over its gate polynomials, its permutation,
+ * lookup and shuffle terms, and the division by X^n - 1 comes behind the last circuit — one launch and one pass over d_h_out whatever
+ * n_circuits is.  The entries travel as consecutive records behind the program in the launch's one device buffer.  With n_circuits == 1
+ * the words of d_h_out are those of h2mi_plonk_evaluate_h_expr_dev.
+ * slice == H2MI_WHOLE_COSET: k_evaluate_h_expr_batch; every vector is an extended-coset evaluation.
+ * 0 <= slice < rot = 2^(extended_k - k): k_evaluate_h_expr_slice, ONE COSET at a time (the quotient of a key made with
+ * H2MI_KEYGEN_BY_COSET, include/h2mi_prover.h).  Extended-coset point slice + rot i is X = (zeta extended_omega^slice) omega^i, omega =
+ * extended_omega^rot: the 2^extended_k evaluations of a polynomial of degree < 2^k are rot coset transforms of 2^k points, one per
+ * shift.  Every column pointer of the record is then the 2^k-element slice `slice` of the extended-coset vector: element i the value at
+ * extended-coset point slice + rot i, which for a column is h2mi_ntt_bn254_fr_oop_dev(coefficients, 2^k, out, k, omega, pre = zeta
+ * extended_omega^slice).  A query at rotation r reads element (i + r) mod 2^k of the same slice; a compressed side is
+ * h2mi_plonk_expr_compress_dev over the slices with domain_k = k; input set j of a logUp lookup lies j 2^k elements behind
+ * lookup_input[l].  zeta, extended_omega and the rot values of t_inv stay the DOMAIN'S.  d_h_out is the whole vector of 2^extended_k
+ * elements: the call writes elements slice + rot i, i < 2^k, each word for word what the whole-coset call stores there, and no other;
+ * rot calls, one per slice, fill it.
+ * H2MI_EINVAL: whatever the single call refuses, in any entry; n_circuits == 0 or > H2MI_MAX_CIRCUITS; entries that disagree in n_perm,
+ * chunk_len, n_lookups or n_shuffles, or that name other sigma or Lagrange cosets than entry 0; slice < H2MI_WHOLE_COSET.
+ * H2MI_ERANGE: the scalars'; slice >= rot. */
+#define H2MI_WHOLE_COSET (-1)
+int h2mi_plonk_evaluate_h_expr_batch_dev(const h2mi_quotient_circuits* circuits, const h2mi_quotient_scalars* scalars, int32_t slice, void* d_h_out,
                                          h2mi_stream_t stream);
 
-/* A lookup's expressions compressed with theta (plonk/lookup/prover.rs compress_expressions): `exprs` holds m polynomials e_0 ..
+/* The columns a program reads on one domain: the 2^k rows or the extended coset.  advice / fixed: n_advice <= H2MI_EXPR_MAX_ADVICE /
+ * n_fixed <= H2MI_EXPR_MAX_FIXED column pointers (the arrays may be NULL with a count of 0; a column the program does not read may be
+ * NULL); instances: the instance columns on the same points, whatever the struct's name says (NULL: none; one column: {1, {ptr}}, and
+ * {1, {NULL}} for a program that reads none); program: required; challenges: as h2mi_quotient_circuits takes them; k: rotations are
+ * modulo 2^k.  The same interpreter, the same uploader and the same refusals of a program as h2mi_plonk_evaluate_h_expr_dev. */
+typedef struct {
+  const void* const* advice; uint32_t n_advice;
+  const void* const* fixed;  uint32_t n_fixed;
+  const h2mi_instance_cosets* instances;
+  const h2mi_gate_program* program;
+  const uint64_t* challenges; uint32_t n_challenges;
+  uint32_t k;
+} h2mi_expr_columns;
+/* A lookup's expressions compressed with theta (plonk/lookup/prover.rs compress_expressions): the program holds m polynomials e_0 ..
  * e_(m-1) and d_out[i] = sum_j e_j(i) theta^(m-1-j) — the fold acc theta + e_j — for the 2^domain_k points the columns are given on:
  * the Lagrange rows (domain_k = k) or the extended coset (domain_k = extended_k).  A query at rotation r reads point
- * (i + (r mod 2^k) 2^(domain_k-k)) mod 2^domain_k.  d_advice / d_fixed: n_advice / n_fixed column pointers (a column the program does
- * not read may be NULL); d_instance: the instance column or NULL.  The same interpreter and the same refusals as
- * h2mi_plonk_evaluate_h_expr_dev.  d_out must not be one of the columns.  Values are stored fully reduced, Montgomery. */
-int h2mi_plonk_expr_compress_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed, const void* d_instance,
-                                 const h2mi_gate_program* exprs, uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out,
-                                 h2mi_stream_t stream);
-/* The same with challenges, as h2mi_plonk_evaluate_h_expr_ch_dev takes them; the call above is this one with none. */
-int h2mi_plonk_expr_compress_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
-                                    const void* d_instance, const h2mi_gate_program* exprs, const uint64_t* challenges, uint32_t n_challenges,
-                                    uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out, h2mi_stream_t stream);
-/* The same with several instance columns (h2mi_instance_cosets, above: here the columns are given on the 2^domain_k points, whatever
- * the struct's name says); `instances` NULL: no instance column.  The call above is this one with {1, {d_instance}}. */
-int h2mi_plonk_expr_compress_in_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
-                                    const h2mi_instance_cosets* instances, const h2mi_gate_program* exprs, const uint64_t* challenges,
-                                    uint32_t n_challenges, uint32_t k, uint32_t domain_k, const uint64_t theta[4], void* d_out, h2mi_stream_t stream);
+ * (i + (r mod 2^k) 2^(domain_k-k)) mod 2^domain_k.  d_out must not be one of the columns.  Values are stored fully reduced, Montgomery.
+ * H2MI_EINVAL: a NULL record, program, theta or d_out; H2MI_ERANGE: k == 0, domain_k < k, domain_k - k > 4, domain_k > H2MI_MAX_LOG_N. */
+int h2mi_plonk_expr_compress_dev(const h2mi_expr_columns* columns, uint32_t domain_k, const uint64_t theta[4], void* d_out, h2mi_stream_t stream);
 
 /* ---- the witness check on the rows (what MockProver::run(..).assert_satisfied() answers on the host): does a witness satisfy the
  * circuit, and where not?  Three calls over Lagrange-row columns; each returns when its report is on the host.  h2mi_prover_check
  * (h2mi_prover.h) runs them on the columns of a proof in flight.
- * Polynomials: `polys` holds n polynomials (any program the calls above take: the same interpreter, the same uploader, the same
- * refusals; columns on the 2^k rows, rotations modulo 2^k).  report_out receives, per polynomial in program order, {the number of
- * rows i < n_rows on which it is not zero modulo r, the smallest such row or 0xffffffff}: 2 uint32 per polynomial, HOST memory, room
- * for every END of the program; n_polys_out (may be NULL) their number.  n_rows in [1, 2^k]: rows at or beyond it are not tested but
- * are read by rotations.  A satisfied witness costs no atomic operation. */
-int h2mi_plonk_expr_check_ch_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
-                                 const void* d_instance, const h2mi_gate_program* polys, const uint64_t* challenges, uint32_t n_challenges,
-                                 uint32_t k, uint32_t n_rows, uint32_t* report_out /* host, n_polys x 2 */, uint32_t* n_polys_out,
-                                 h2mi_stream_t stream);
-/* The same with several instance columns on the rows (h2mi_instance_cosets); NULL: none.  The call above is this one with {1, {d_instance}}. */
-int h2mi_plonk_expr_check_in_dev(const void* const* d_advice, uint32_t n_advice, const void* const* d_fixed, uint32_t n_fixed,
-                                 const h2mi_instance_cosets* instances, const h2mi_gate_program* polys, const uint64_t* challenges,
-                                 uint32_t n_challenges, uint32_t k, uint32_t n_rows, uint32_t* report_out /* host, n_polys x 2 */,
-                                 uint32_t* n_polys_out, h2mi_stream_t stream);
+ * Polynomials: the program holds n polynomials (columns on the 2^k rows, rotations modulo 2^k).  report_out receives, per polynomial in
+ * program order, {the number of rows i < n_rows on which it is not zero modulo r, the smallest such row or 0xffffffff}: 2 uint32 per
+ * polynomial, HOST memory, room for every END of the program; n_polys_out (may be NULL) their number.  n_rows in [1, 2^k]: rows at or
+ * beyond it are not tested but are read by rotations.  A satisfied witness costs no atomic operation.
+ * H2MI_EINVAL: a NULL record, program or report_out; H2MI_ERANGE: k == 0, k > H2MI_MAX_LOG_N, n_rows out of range. */
+int h2mi_plonk_expr_check_dev(const h2mi_expr_columns* columns, uint32_t n_rows, uint32_t* report_out /* host, n_polys x 2 */, uint32_t* n_polys_out,
+                              h2mi_stream_t stream);
 /* Copy constraints: d_cells holds n_cells x 4 uint32 in DEVICE memory, {column, row, image column, image row} per cell that the
  * permutation moves, columns as indices into d_values (m <= H2MI_FLEX_MAX_PERM Lagrange-row columns, the permutation argument's order)
  * — trusted like the active rows of h2mi_plonk_permutation_products_sparse_dev: every column below m, every row inside its column.

@@ -217,7 +217,7 @@ typedef struct h2mi_prover_s* h2mi_prover_t; /* the buffers, streams and phase s
  * columns among them — in a batch the leader's are read, and the key stays immutable.  h2mi_prover_quotient / h2mi_batch_quotient then
  * run, for each slice c < 2^(extended_k - k): every column's coefficients to slice c (a 2^k-point transform with shift
  * zeta extended_omega^c), the lookups' and shuffles' sides compressed on the slices, ONE launch of the interpreting kernel over all
- * members (h2mi_plonk_evaluate_h_expr_slice_dev; a hard-wired shape through its equivalent program, as batches do).  Every phase and every
+ * members (h2mi_plonk_evaluate_h_expr_batch_dev with a slice; a hard-wired shape through its equivalent program, as batches do).  Every phase and every
  * byte of the proof is the resident key's; instance columns always take the coefficient route.  The price is time: the fixed and sigma
  * slices are recomputed in every proof.  h2mi_prover_buffer / _pk_buffer: see the *_COSET kinds below. */
 #define H2MI_KEYGEN_BY_COSET 8u /* bit 4 stays unassigned: every keygen entry refuses it with H2MI_EINVAL, as it always has */

@@ -1,4 +1,4 @@
-"""The witness check (h2mi_plonk_expr_check_ch_dev, h2mi_prover_check), shared by tests/test_check_host.py and tests/test_gpu_check.py:
+"""The witness check (h2mi_plonk_expr_check_dev, h2mi_prover_check), shared by tests/test_check_host.py and tests/test_gpu_check.py:
 every case with the report it must give, computed here with Python integers.
 
 Level A: programs `tree - c` whose fixed column c holds the tree's value on every row but a planted set, so that the count and the

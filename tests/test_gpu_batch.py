@@ -63,7 +63,7 @@ def _device_case(gpu, kc):
 
 @pytest.mark.parametrize("case", range(len(cases.KERNEL_CASES)))
 def test_batch_kernel_against_python_integers(gpu, case):
-    """every element of h, exactly; with one circuit the words of h2mi_plonk_evaluate_h_expr_ch_dev; with three circuits also
+    """every element of h, exactly; with one circuit the words of h2mi_plonk_evaluate_h_expr_dev; with three circuits also
     sum_i y^(T (N - 1 - i)) H_i over the single-circuit call's outputs H_i (T: the Horner terms of one circuit)"""
     from halo2_scaffold_amd import custom, plonk
     from halo2_scaffold_amd.device import DevBuf

@@ -1,6 +1,6 @@
 """The coset-by-coset quotient on the device (H2MI_KEYGEN_BY_COSET, include/h2mi_prover.h).
 
-1. k_evaluate_h_expr_slice through h2mi_plonk_evaluate_h_expr_slice_dev: h assembled from rot launches over slices made by the transform
+1. k_evaluate_h_expr_slice through h2mi_plonk_evaluate_h_expr_batch_dev with a slice: h assembled from rot launches over slices made by the transform
    export, word for word against the Python-integer quotient of tests/instance_cases.py on every extended-coset point and against the
    resident batch kernel on the same polynomials; a launch for slice c writes elements c + rot i and no other.
 2. A by-coset key and a resident key of the same circuit give the same proof bytes — every shape, argument and ending the prover takes

@@ -1,4 +1,4 @@
-"""The witness check on the device.  Level A: h2mi_plonk_expr_check_ch_dev on the planted programs and the redundant zeros of
+"""The witness check on the device.  Level A: h2mi_plonk_expr_check_dev on the planted programs and the redundant zeros of
 tests/check_cases.py (counts and first rows exactly), its refusals, and the copy / membership calls on small vectors.  Level B:
 h2mi_prover_check through custom.check / flex.check / engine.Prover.check on circuits given as data, the hard-wired shapes, copy
 constraints beyond one workgroup, a gate left on over the blinding rows; that a proof's bytes do not depend on the call; when the
@@ -72,20 +72,22 @@ def test_redundant_zeros(gpu):
 
 
 def test_expr_check_refusals(gpu):
-    """the refusals of h2mi_plonk_expr_compress_ch_dev, and n_rows outside [1, 2^k]"""
-    from halo2_scaffold_amd import engine
+    """the refusals of h2mi_plonk_expr_check_dev, and n_rows outside [1, 2^k]"""
+    from halo2_scaffold_amd import engine, plonk
     from halo2_scaffold_amd.device import DevBuf
 
     col = DevBuf(32 * 32)
     cols = (C.c_void_p * 1)(col.ptr)
+    inst = plonk._InstanceCosets(1)  # one instance column, which the programs do not read: {1, {NULL}}
     report = np.zeros((4, 2), dtype=np.uint32)
     ch = np.zeros((17, 4), dtype=np.uint64)
     OP_CHALLENGE = phase_cases.OP_CHALLENGE
 
     def call(ops, k=5, n_rows=32, n_adv=1, challenges=0, out=report.ctypes.data):
         prog = engine.GateProgram.build(ops, [])
-        return gpu.lib.h2mi_plonk_expr_check_ch_dev(cols, n_adv, None, 0, None, C.byref(prog), ch.ctypes.data if challenges else None, challenges, k, n_rows,
-                                                    out, None, None)
+        rec = plonk.ExprColumns(C.addressof(cols), n_adv, None, 0, C.addressof(inst), C.addressof(prog), ch.ctypes.data if challenges else None,
+                                challenges, k)
+        return gpu.lib.h2mi_plonk_expr_check_dev(C.byref(rec), n_rows, out, None, None)
 
     ok = [(OP_ADVICE, 0, 0), (OP_END, 0, 0)]
     assert call(ok) == 0

@@ -20,7 +20,7 @@ The references are Python integers: oracle.bn254, tests/batch_cases.py batched_q
 tests/perm_scale_cases.py formula_products, oracle/lookup.py lookup_product, the recurrences of tests/shuffle_cases.py and
 tests/logup_sets_cases.py.  All comparisons are exact, and the words the kernels store are canonical (below r).
 k_evaluate_h_range takes at most four permutation columns, so the six columns in chunks of two run through k_evaluate_h_flex; that
-kernel's entry carries no shuffles and no logUp lookups, so those terms (the shared evaluate_h_fold) run through the _lg_dev entry."""
+kernel's entry carries no shuffles and no logUp lookups, so those terms (the shared evaluate_h_fold) run through the expression entry's record."""
 import ctypes as C
 import types
 
@@ -305,22 +305,30 @@ def test_flex_quotient_at_the_extremes(gpu):
     out.free()
 
 
-def _scalars_tail(plonk, dom, rnd, k, out, challenges=()):
-    """the arguments every evaluate_h_expr_* entry ends with -> (tuple, objects to keep alive)"""
+def _scalars(plonk, dom, rnd):
+    """the h2mi_quotient_scalars of a round -> (record, objects to keep alive)"""
     from halo2_scaffold_amd import field as F
 
     mm = F.fr_to_mont_limbs
     t_inv = np.ascontiguousarray(plonk.vanishing_inverses(dom))
     scal = [mm(rnd["beta"]), mm(rnd["gamma"]), mm(rnd["y"]), mm(plonk.FR_DELTA), mm(dom.g_coset), mm(dom.extended_omega)]
+    return plonk.QuotientScalars(dom.k, dom.extended_k, X.BF, *[x.ctypes.data for x in scal], t_inv.ctypes.data), (t_inv, scal)
+
+
+def _records(plonk, dom, rnd, program, cosets, n_circuits, challenges=(), shuffles=None, logup=None):
+    """the two records every evaluate_h_expr entry takes -> (h2mi_quotient_circuits, h2mi_quotient_scalars, objects to keep alive)"""
+    qs, keep = _scalars(plonk, dom, rnd)
     ch = _mont(challenges) if len(challenges) else None
-    keep = (t_inv, scal, ch)
-    return (ch.ctypes.data if ch is not None else None, len(challenges), k, dom.extended_k, X.BF, *[x.ctypes.data for x in scal], t_inv.ctypes.data, out.ptr, None), keep
+    addr = lambda x: C.addressof(x) if x is not None else None
+    qc = plonk.QuotientCircuits(addr(cosets), n_circuits, addr(shuffles), addr(logup), None, addr(program), ch.ctypes.data if ch is not None else None,
+                                len(challenges))
+    return qc, qs, (keep, ch)
 
 
 @pytest.mark.parametrize("n_sets", X.LOGUP_SETS)
 def test_shuffle_and_logup_terms_at_the_extremes(gpu, n_sets):
     """evaluate_h_fold's shuffle terms and its logUp term with 1 and 6 input sets (N starts as a negation: 4p for M = 0), behind a
-    one-query program, through h2mi_plonk_evaluate_h_expr_lg_dev"""
+    one-query program, through h2mi_plonk_evaluate_h_expr_dev"""
     from halo2_scaffold_amd import engine, plonk
 
     k = X.FLEX_K
@@ -344,8 +352,8 @@ def test_shuffle_and_logup_terms_at_the_extremes(gpu, n_sets):
         sh.n_shuffles = X.FLEX_SHUFFLES
         for s in range(X.FLEX_SHUFFLES):
             sh.input[s], sh.shuffle[s], sh.z[s] = d[f"sf{s}_in"].ptr, d[f"sf{s}_side"].ptr, d[f"sf{s}_z"].ptr
-        tail, keep = _scalars_tail(plonk, dom, rnd, k, out)
-        assert gpu.lib.h2mi_plonk_evaluate_h_expr_lg_dev(C.byref(cs), C.byref(sh), C.byref(logup), C.byref(program), *tail) == 0
+        qc, qs, keep = _records(plonk, dom, rnd, program, cs, 1, shuffles=sh, logup=logup)
+        assert gpu.lib.h2mi_plonk_evaluate_h_expr_dev(C.byref(qc), C.byref(qs), out.ptr, None) == 0
         circuit = {"advice": [v["advice0"]], "fixed": [], "instance": None, "perm_values": [], "perm_zs": [],
                    "lookups": [([v[f"lg_in{j}"] for j in range(n_sets)], None, v["lg_table"], v["lg_m"], None, v["lg_phi"])],
                    "shuffles": [(v[f"sf{s}_in"], v[f"sf{s}_side"], v[f"sf{s}_z"]) for s in range(X.FLEX_SHUFFLES)]}
@@ -369,7 +377,7 @@ def _expr_program(custom):
 def test_expr_quotient_at_the_extremes(gpu, n_circuits, with_terms):
     """k_evaluate_h_expr (one circuit) and k_evaluate_h_expr_batch (two) on the bound-tight programs over the value patterns: without any
     argument terms through plonk.evaluate_h_expr / evaluate_h_expr_batch, and with a permutation argument, a lookup with a second input
-    factor and a shuffle through the _sh_dev entries"""
+    factor and a shuffle through records filled here"""
     from halo2_scaffold_amd import custom, plonk
 
     k = X.EXPR_K
@@ -397,11 +405,11 @@ def test_expr_quotient_at_the_extremes(gpu, n_circuits, with_terms):
                 sh.n_shuffles = len(c["shuffles"])
                 for s, (a_in, s_in, z) in enumerate(c["shuffles"]):
                     sh.input[s], sh.shuffle[s], sh.z[s] = a_in.ptr, s_in.ptr, z.ptr
-            tail, keep = _scalars_tail(plonk, dom, rnd, k, out, ch)
+            qc, qs, keep = _records(plonk, dom, rnd, program, arr, n_circuits, ch, shuffles=shs)
             if n_circuits == 1:
-                assert gpu.lib.h2mi_plonk_evaluate_h_expr_sh_dev(C.byref(arr[0]), C.byref(shs[0]), C.byref(program), *tail) == 0
+                assert gpu.lib.h2mi_plonk_evaluate_h_expr_dev(C.byref(qc), C.byref(qs), out.ptr, None) == 0
             else:
-                assert gpu.lib.h2mi_plonk_evaluate_h_expr_batch_sh_dev(arr, shs, n_circuits, C.byref(program), *tail) == 0
+                assert gpu.lib.h2mi_plonk_evaluate_h_expr_batch_dev(C.byref(qc), C.byref(qs), -1, out.ptr, None) == 0
             del keep
         want = shuffle_cases.batched_quotient(*_quotient_args(dom, k, ops, constants, ch), circuits, shared, rnd["beta"], rnd["gamma"], rnd["y"])
         _same(_read(out, size), want, f"evaluate_h_expr, {n_circuits} circuit(s), terms: {with_terms}, {rnd['name']}")
@@ -464,6 +472,72 @@ def test_expr_check_at_the_extremes(gpu):
         assert want[0] == (7, X.CHECK_PLANTED_ROW - 6) and want[1:] == [(0, 0xFFFFFFFF)] * 3, name
         assert plonk.expr_check(program, [d[0], d1, d[2], d[3]], [], None, k) == want, name
         _free(d1, *d)
+
+
+def test_quotient_records_are_refused_before_any_launch(gpu):
+    """the three argument records of the quotient calls, one circuit on 512 extended points: a NULL record, each required field NULL in
+    turn, two circuits on the single-circuit call and a slice outside H2MI_WHOLE_COSET .. rot - 1 are refused with the header's codes,
+    and no refused call launches a kernel"""
+    from halo2_scaffold_amd import engine, plonk
+
+    EINVAL, ERANGE = -1, -6
+    k = X.EXPR_K
+    dom = gpu.EvaluationDomain(4, k)
+    size, rot = 1 << dom.extended_k, 1 << (dom.extended_k - k)
+    assert size == 512
+    col, out = gpu.DevBuf(32 * size), gpu.DevBuf(32 * size)
+    program = engine.GateProgram.build([(engine.ADVICE, 0, 0), (engine.EXPR_END, 0, 0)], [])
+    cs = plonk._ExprCosets()
+    cs.advice[0] = cs.l0 = cs.l_last = cs.l_active = col.ptr
+    qs, keep = _scalars(plonk, dom, {"beta": 2, "gamma": 3, "y": 5})
+    qc = plonk.QuotientCircuits(C.addressof(cs), 1, None, None, None, C.addressof(program), None, 0)
+    cols = (C.c_void_p * 1)(col.ptr)
+    ec = plonk.ExprColumns(C.addressof(cols), 1, None, 0, None, C.addressof(program), None, 0, k)
+    theta, report = _mont([7]), np.zeros((1, 2), dtype=np.uint32)
+    lib = gpu.lib
+    ref = lambda rec: C.byref(rec) if rec is not None else None
+    single = lambda c, s: lib.h2mi_plonk_evaluate_h_expr_dev(ref(c), ref(s), out.ptr, None)
+    batch = lambda c, s, sl=-1: lib.h2mi_plonk_evaluate_h_expr_batch_dev(ref(c), ref(s), sl, out.ptr, None)
+    compress = lambda e, th=theta.ctypes.data, dst=out.ptr: lib.h2mi_plonk_expr_compress_dev(ref(e), dom.extended_k, th, dst, None)
+    check = lambda e, rep=report.ctypes.data: lib.h2mi_plonk_expr_check_dev(ref(e), 1 << k, rep, None, None)
+
+    def without(rec, field, **changed):
+        """a copy of the record with one field NULL (or given another value)"""
+        other = type(rec).from_buffer_copy(rec)
+        for name, value in {field: None, **changed}.items():
+            if name:
+                setattr(other, name, value)
+        return other
+
+    def refusals():
+        codes = []
+        hard_wired = [(lib.h2mi_plonk_evaluate_h_standard_dev, plonk._Cosets()), (lib.h2mi_plonk_evaluate_h_range_dev, plonk._RangeCosets()),
+                      (lib.h2mi_plonk_evaluate_h_flex_dev, plonk._FlexCosets())]
+        for call, cosets in hard_wired:  # the scalars are looked at before the cosets' fields
+            codes += [(call(C.byref(cosets), None, out.ptr, None), EINVAL), (call(None, C.byref(qs), out.ptr, None), EINVAL)]
+        codes += [(single(None, qs), EINVAL), (single(qc, None), EINVAL), (batch(None, qs), EINVAL), (batch(qc, None), EINVAL)]
+        for field in ("beta", "gamma", "y", "delta", "zeta", "extended_omega", "t_inv"):
+            codes += [(single(qc, without(qs, field)), EINVAL), (batch(qc, without(qs, field)), EINVAL)]
+            codes += [(call(C.byref(cosets), C.byref(without(qs, field)), out.ptr, None), EINVAL) for call, cosets in hard_wired]
+        for field in ("circuits", "gates"):
+            codes += [(single(without(qc, field), qs), EINVAL), (batch(without(qc, field), qs), EINVAL)]
+        codes += [(lib.h2mi_plonk_evaluate_h_expr_dev(C.byref(qc), C.byref(qs), None, None), EINVAL),
+                  (lib.h2mi_plonk_evaluate_h_expr_batch_dev(C.byref(qc), C.byref(qs), -1, None, None), EINVAL)]
+        codes += [(single(without(qc, "", n_circuits=2), qs), EINVAL), (single(without(qc, "", n_circuits=0), qs), EINVAL)]
+        codes += [(batch(qc, qs, rot), ERANGE), (batch(qc, qs, -2), EINVAL), (batch(qc, without(qs, "", extended_k=k + 5), 0), ERANGE)]
+        codes += [(compress(None), EINVAL), (check(None), EINVAL), (compress(without(ec, "program")), EINVAL), (check(without(ec, "program")), EINVAL),
+                  (compress(without(ec, "advice")), EINVAL), (check(without(ec, "advice")), EINVAL), (compress(ec, th=None), EINVAL),
+                  (compress(ec, dst=None), EINVAL), (check(ec, rep=None), EINVAL)]
+        return codes
+
+    codes = []
+    assert _launches(gpu, b"k_", lambda: codes.extend(refusals())) == 0
+    assert len(codes) > 60 and all(got == want for got, want in codes), [i for i, (got, want) in enumerate(codes) if got != want]
+    # and the records as they stand are taken: the single call, a batch of one whole and by slices, both column calls
+    assert single(qc, qs) == 0 and batch(qc, qs) == 0 and all(batch(qc, qs, sl) == 0 for sl in range(rot))
+    assert compress(ec) == 0 and check(ec) == 0
+    del keep
+    _free(col, out)
 
 
 # ---- 3. grand products and running sums -------------------------------------------------------------------------------------------------

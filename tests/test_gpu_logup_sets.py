@@ -1,7 +1,7 @@
 """LogUp lookups with several input sets over one table on the device, bit for bit against the Python integers of
 tests/logup_sets_cases.py: the multiplicity column of K input columns (h2mi_plonk_logup_multiplicity_sets_dev) and the running sum
 (h2mi_plonk_logup_sum_sets_dev) around the ranking kernel's 1024-thread workgroup and the scan tile, K = 2, 3, 6; the quotient kernels
-with the K-input term, recovered from H2MI_BUF_H on every extended-coset point, and the `_lg_dev` entries against the existing ones word
+with the K-input term, recovered from H2MI_BUF_H on every extended-coset point, and the quotient calls with `logup` NULL against all ones word
 for word; proofs of every merged circuit accepted by the generalised verifier and rejected after one-byte flips; proof lengths and the
 merged M column against the unmerged key's; a key of h2mi_prover_keygen_logup with all counts 1 against tests/golden/logup_proofs.json;
 an absent cell of one set in the check and in the lookups phase; the committed golden."""
@@ -328,10 +328,9 @@ def test_quotient_with_one_three_and_two_sets(gpu):
 
 
 def test_lg_entries_with_null_or_ones_are_the_existing_entries(gpu):
-    """h2mi_plonk_evaluate_h_expr_lg_dev / _batch_lg_dev with logup == NULL or all ones against the _sh_dev entries word for word (random
-    vectors: the quotient is evaluated pointwise), and their refusals"""
+    """h2mi_plonk_evaluate_h_expr_dev / _batch_dev: the record with logup == NULL against the record with all ones word for word (random
+    vectors: the quotient is evaluated pointwise), and the refusals of a logup field"""
     from halo2_scaffold_amd import engine, plonk
-    from halo2_scaffold_amd import field as F
     from halo2_scaffold_amd._lib import lib
     from halo2_scaffold_amd.device import DevBuf
     from halo2_scaffold_amd.domain import EvaluationDomain
@@ -351,32 +350,32 @@ def test_lg_entries_with_null_or_ones_are_the_existing_entries(gpu):
             cs.lookup_input[l], cs.lookup_table[l] = bufs[3 + l].ptr, bufs[5 + l + i].ptr
             cs.lookup_permuted_input[l], cs.lookup_z[l] = bufs[7 + l].ptr, bufs[8 + l + i].ptr
         cs.l0, cs.l_last, cs.l_active = bufs[9].ptr, bufs[10].ptr, bufs[11].ptr
-    mm = F.fr_to_mont_limbs
-    t_inv = np.ascontiguousarray(plonk.vanishing_inverses(dom))
-    scal = [mm(rng.randrange(R)) for _ in range(3)] + [mm(plonk.FR_DELTA), mm(dom.g_coset), mm(dom.extended_omega)]
-    tail = lambda out: (None, 0, k, dom.extended_k, 5, *[x.ctypes.data for x in scal], t_inv.ctypes.data, out.ptr, None)
-    outs = [DevBuf(size * 32) for _ in range(6)]
+    scalars = plonk.quotient_scalars(dom, rng.randrange(R), rng.randrange(R), rng.randrange(R), 5)
+    outs = [DevBuf(size * 32) for _ in range(4)]
     ones, two = engine.LogupInputs.build([1] * 8), engine.LogupInputs.build([2, 1])
-    assert lib.h2mi_plonk_evaluate_h_expr_sh_dev(C.byref(arr[0]), None, C.byref(program), *tail(outs[0])) == 0
-    assert lib.h2mi_plonk_evaluate_h_expr_lg_dev(C.byref(arr[0]), None, None, C.byref(program), *tail(outs[1])) == 0
-    assert lib.h2mi_plonk_evaluate_h_expr_lg_dev(C.byref(arr[0]), None, C.byref(ones), C.byref(program), *tail(outs[2])) == 0
-    assert lib.h2mi_plonk_evaluate_h_expr_batch_sh_dev(arr, None, 2, C.byref(program), *tail(outs[3])) == 0
-    assert lib.h2mi_plonk_evaluate_h_expr_batch_lg_dev(arr, None, None, 2, C.byref(program), *tail(outs[4])) == 0
-    assert lib.h2mi_plonk_evaluate_h_expr_batch_lg_dev(arr, None, C.byref(ones), 2, C.byref(program), *tail(outs[5])) == 0
+
+    def single(logup, out):
+        return lib.h2mi_plonk_evaluate_h_expr_dev(C.byref(plonk.quotient_circuits(program, arr, 1, logup=logup)), C.byref(scalars), out.ptr, None)
+
+    def batch(logup, out):
+        return lib.h2mi_plonk_evaluate_h_expr_batch_dev(C.byref(plonk.quotient_circuits(program, arr, 2, logup=logup)), C.byref(scalars), -1, out.ptr, None)
+
+    assert single(None, outs[0]) == 0 and single(ones, outs[1]) == 0
+    assert batch(None, outs[2]) == 0 and batch(ones, outs[3]) == 0
     words = [b.to_numpy(shape=(size, 4), nbytes=size * 32).tobytes() for b in outs]
-    assert words[0] == words[1] == words[2] and words[3] == words[4] == words[5] and words[0] != words[3]
+    assert words[0] == words[1] and words[2] == words[3] and words[0] != words[2]
     # refusals: a count of 0 or above the maximum; another count than 1 without H2MI_LOOKUPS_LOGUP
     for counts in ([0, 1], [1, 7]):
         bad = engine.LogupInputs.build(counts)
-        assert lib.h2mi_plonk_evaluate_h_expr_lg_dev(C.byref(arr[0]), None, C.byref(bad), C.byref(program), *tail(outs[1])) == -1
-        assert lib.h2mi_plonk_evaluate_h_expr_batch_lg_dev(arr, None, C.byref(bad), 2, C.byref(program), *tail(outs[4])) == -1
+        assert single(bad, outs[1]) == -1
+        assert batch(bad, outs[3]) == -1
     for cs in arr:
         cs.n_lookups = 2
         for l in range(2):
             cs.lookup_permuted_table[l] = bufs[l].ptr
-    assert lib.h2mi_plonk_evaluate_h_expr_lg_dev(C.byref(arr[0]), None, C.byref(two), C.byref(program), *tail(outs[1])) == -1
-    assert lib.h2mi_plonk_evaluate_h_expr_batch_lg_dev(arr, None, C.byref(two), 2, C.byref(program), *tail(outs[4])) == -1
-    assert lib.h2mi_plonk_evaluate_h_expr_lg_dev(C.byref(arr[0]), None, C.byref(ones), C.byref(program), *tail(outs[1])) == 0
+    assert single(two, outs[1]) == -1
+    assert batch(two, outs[3]) == -1
+    assert single(ones, outs[1]) == 0
     for b in bufs + outs:
         b.free()
 

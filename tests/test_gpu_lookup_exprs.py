@@ -225,16 +225,18 @@ def test_compress_cases_cover_what_they_should(h2):
 
 
 def test_expr_compress_refusals(gpu):
-    from halo2_scaffold_amd import engine
+    from halo2_scaffold_amd import engine, plonk
     from halo2_scaffold_amd.device import DevBuf
 
     col, out = DevBuf(32 * 32), DevBuf(32 * 32)
     theta = np.zeros(4, dtype=np.uint64)
     cols = (C.c_void_p * 1)(col.ptr)
+    inst = plonk._InstanceCosets(1)  # one instance column, which the programs do not read: {1, {NULL}}
 
     def call(ops, k=5, domain_k=5, n_adv=1):
         prog = engine.GateProgram.build(ops, [])
-        return gpu.lib.h2mi_plonk_expr_compress_dev(cols, n_adv, None, 0, None, C.byref(prog), k, domain_k, theta.ctypes.data, out.ptr, None)
+        rec = plonk.ExprColumns(C.addressof(cols), n_adv, None, 0, C.addressof(inst), C.addressof(prog), None, 0, k)
+        return gpu.lib.h2mi_plonk_expr_compress_dev(C.byref(rec), domain_k, theta.ctypes.data, out.ptr, None)
 
     assert call([(OP_ADVICE, 0, 0), (OP_END, 0, 0)]) == 0
     assert call([(OP_ADVICE, 1, 0), (OP_END, 0, 0)]) == -1     # a column that is not there

@@ -105,8 +105,8 @@ def _program(engine, trees):
 
 @pytest.mark.parametrize("case", range(N_KERNEL_CASES))
 def test_challenge_operand_against_python_integers(gpu, case):
-    """h2mi_plonk_evaluate_h_expr_ch_dev (no permutation, no lookups: h[i] = Horner in y over the polynomials times t_inv) on the extended
-    coset, and h2mi_plonk_expr_compress_ch_dev (the fold with theta) on the rows and on the extended coset: every element, exactly"""
+    """h2mi_plonk_evaluate_h_expr_dev (no permutation, no lookups: h[i] = Horner in y over the polynomials times t_inv) on the extended
+    coset, and h2mi_plonk_expr_compress_dev (the fold with theta) on the rows and on the extended coset: every element, exactly"""
     from halo2_scaffold_amd import custom, engine, plonk
     from halo2_scaffold_amd.device import DevBuf
 

@@ -3,8 +3,7 @@
 - a(w^3 X)) as a program, 33 permutation sets of one column, 512 extended points, random cosets.  One process: --warmup launches,
 then --launches launches with the library's events around each; prints the microseconds per launch.  Two builds are compared by
 running this from two checkouts in alternation (a parent and a branch; the process pair is the unit, the median over pairs the
-figure).  --challenges N: the gates' selector is multiplied by challenge i mod N (h2mi_plonk_evaluate_h_expr_ch_dev), for a build
-that knows the operand.
+figure).  --challenges N: the gates' selector is multiplied by challenge i mod N.
 
     python tools/expr_kernel_yardstick.py --launches 50 --warmup 10"""
 import argparse
