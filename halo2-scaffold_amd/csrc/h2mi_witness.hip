@@ -15,6 +15,15 @@
 // The columns of a program lie behind one another in one buffer, so the gather needs no search for its column: placed cell e of the
 // concatenated placement lands at word e.  The arithmetic is the fp.cuh layer's: canonical -> Montgomery is the product with R^2,
 // Montgomery -> canonical the product with 1.
+// Hint ops (DIVQ, DIVR, ISZERO, INV: the values halo2-base computes outside the gates — quotients, remainders, is-zero flags, inverses)
+// live in a second instantiation of the two level kernels, k_witness_level_hints / k_witness_levels_wg_hints, launched for the programs
+// that hold one; a program without them runs the kernels it always ran.  Division is restoring long division on the canonical words,
+// one quotient bit per round: dividend and remainder shift left as one 512-bit register (16 shifts), the divisor is subtracted with
+// borrow (8) and the difference taken where it did not borrow (8 selects, the quotient bit enters the dividend's low word) — about 36
+// instructions a round, 256 rounds, ~9 k instructions per op, beside one product out of Montgomery form per cell operand and one back
+// in.  Nothing cleverer is needed for a value computed once per lane: the inversion beside it (fe_inv_ds, ~15 k instructions, out of
+// line as everywhere it is used) costs more.  A signed dividend (above 2^252: the fixed-point chip's negative numbers) is divided as
+// its magnitude r - x and the quotient rounded toward minus infinity afterwards.
 #include <algorithm>
 #include <memory>
 #include <set>
@@ -26,15 +35,84 @@
 namespace h2 {
 
 constexpr uint32_t WP_INPUT = 0, WP_CONST = 1, WP_COPY = 2, WP_GATE = 3, WP_LIMB = 4;  // H2MI_WITNESS_*
+constexpr uint32_t WP_DIVQ = 8, WP_DIVR = 9, WP_ISZERO = 10, WP_INV = 11;  // the hint ops; 5 .. 7 stay unassigned
+constexpr uint32_t WP_DIV_CONST = 1, WP_DIV_SIGNED = 2;                     // H2MI_WITNESS_DIV_*: the flags of DIVQ / DIVR, in the bits byte
 constexpr uint32_t WP_BLOCK = 256;
 constexpr uint32_t WP_WG = 1024;         // H2MI_WITNESS_WG_OPS: the workgroup limit
 constexpr uint32_t WP_WG_LEVELS = 4096;  // H2MI_WITNESS_WG_LEVELS
 constexpr uint32_t WP_NO_FAILURE = 0xffffffffu;
 
+// x / y and x mod y of plain 256-bit integers by restoring long division, y != 0: (rem : x) shifts left one bit a round, the quotient
+// bit enters x's low word.  rem < y <= 2^256 - 1 before every shift; the bit shifted out of rem's top word joins the comparison.
+__device__ __forceinline__ void divmod_256(fe& x, const fe& y, fe& rem) {
+  rem = fe_zero();
+  for (uint32_t round = 0; round < 256; round++) {
+    const uint32_t out = rem.v[7] >> 31;
+#pragma unroll
+    for (int i = 7; i > 0; i--) rem.v[i] = (rem.v[i] << 1) | (rem.v[i - 1] >> 31);
+    rem.v[0] = (rem.v[0] << 1) | (x.v[7] >> 31);
+#pragma unroll
+    for (int i = 7; i > 0; i--) x.v[i] = (x.v[i] << 1) | (x.v[i - 1] >> 31);
+    x.v[0] <<= 1;
+    uint32_t borrow;
+    const fe d = raw_sub(rem, y, borrow);
+    const bool take = out || !borrow;
+    rem = fe_select(take, d, rem);
+    x.v[0] |= take ? 1u : 0u;
+  }
+}
+
+// DIVQ / DIVR of include/h2mi.h on canonical words -> the canonical result
+__device__ __forceinline__ fe witness_div(fe x, const fe& y, bool want_q, bool is_signed) {
+  const fe zero = fe_zero();
+  uint32_t low = 0;
+#pragma unroll
+  for (int i = 0; i < 7; i++) low |= x.v[i];
+  const bool neg = is_signed && (x.v[7] > 0x10000000u || (x.v[7] == 0x10000000u && low != 0));  // x > 2^252: read as x - r
+  const fe mod = fe_const<Fr>(Fr::MOD);
+  uint32_t bo;
+  if (neg) x = raw_sub(mod, x, bo);  // the magnitude, 0 < r - x < r
+  fe rem;
+  divmod_256(x, y, rem);  // x is the quotient now
+  if (neg) {              // floor(-m / y) = -(m / y) - (m mod y != 0); the remainder y - m mod y, or 0
+    const bool exact = fe_is_zero(rem);
+    fe one = zero;
+    one.v[0] = exact ? 0u : 1u;
+    uint32_t carry;
+    x = raw_sub(mod, raw_add(x, one, carry), bo);  // ceil(m / y) is in 1 .. m: r minus it is in [0, r)
+    rem = fe_select(exact, rem, raw_sub(y, rem, bo));
+  }
+  const fe r = want_q ? x : rem;
+  return fe_select(fe_is_zero(y), zero, r);
+}
+
+// the hint ops: the values a builder computes outside the gates (include/h2mi.h)
+__device__ __forceinline__ void witness_hint(const uint4 op, uint32_t kind, fe* cells, const fe* consts) {
+  const fe x = fe_load(cells + op.z);
+  fe r;
+  if (kind == WP_ISZERO) {
+    r = fe_is_zero(x) ? fe_one<Fr>() : fe_zero();  // reduced: zero is the zero word
+  } else if (kind == WP_INV) {
+    r = fe_is_zero(x) ? fe_one<Fr>() : fe_inv_ds<Fr>(x);
+  } else {
+    const uint32_t flags = (op.y >> 8) & 0xffu;
+    const fe y = (flags & WP_DIV_CONST) ? fe_load(consts + op.w) : fe_from_mont<Fr>(fe_load(cells + op.w));  // the constants are canonical
+    r = fe_to_mont<Fr>(witness_div(fe_from_mont<Fr>(x), y, kind == WP_DIVQ, (flags & WP_DIV_SIGNED) != 0));
+  }
+  fe_store(cells + op.x, r);
+}
+
 // op = (dst, kind | bits << 8 | shift << 16, a, b).  Every index was checked on the host (h2mi_witness_check): nothing here can reach
-// outside cells[0 .. n_cells), values[0 .. n_inputs) or consts[0 .. n_constants).
+// outside cells[0 .. n_cells), values[0 .. n_inputs) or consts[0 .. n_constants).  HINTS: the instantiation that also knows the hint ops.
+template <bool HINTS>
 __device__ __forceinline__ void witness_op(const uint4 op, fe* cells, const fe* values, const fe* consts) {
   const uint32_t dst = op.x, kind = op.y & 0xffu;
+  if constexpr (HINTS) {
+    if (kind >= WP_DIVQ) {
+      witness_hint(op, kind, cells, consts);
+      return;
+    }
+  }
   if (kind == WP_COPY) {
     fe_store(cells + dst, fe_load(cells + op.z));
     return;
@@ -79,7 +157,11 @@ __device__ __forceinline__ void witness_op(const uint4 op, fe* cells, const fe* 
 // one wide level: a lane per op
 __global__ void __launch_bounds__(WP_BLOCK) k_witness_level(const uint4* ops, uint32_t count, fe* cells, const fe* values, const fe* consts) {
   const uint32_t e = blockIdx.x * WP_BLOCK + threadIdx.x;
-  if (e < count) witness_op(ops[e], cells, values, consts);
+  if (e < count) witness_op<false>(ops[e], cells, values, consts);
+}
+__global__ void __launch_bounds__(WP_BLOCK) k_witness_level_hints(const uint4* ops, uint32_t count, fe* cells, const fe* values, const fe* consts) {
+  const uint32_t e = blockIdx.x * WP_BLOCK + threadIdx.x;
+  if (e < count) witness_op<true>(ops[e], cells, values, consts);
 }
 
 // levels l0 .. l1 - 1, none of more than WP_WG ops, in ONE workgroup: a level's stores are visible to the next level's loads behind the
@@ -89,7 +171,18 @@ __global__ void __launch_bounds__(WP_WG) k_witness_levels_wg(const uint4* ops, c
   uint32_t begin = l0 ? level_ends[l0 - 1] : 0u;
   for (uint32_t l = l0; l < l1; l++) {  // uniform trip count: every thread reaches every barrier
     const uint32_t end = level_ends[l];
-    if (end - begin <= WP_WG && threadIdx.x < end - begin) witness_op(ops[begin + threadIdx.x], cells, values, consts);
+    if (end - begin <= WP_WG && threadIdx.x < end - begin) witness_op<false>(ops[begin + threadIdx.x], cells, values, consts);
+    begin = end;
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(WP_WG) k_witness_levels_wg_hints(const uint4* ops, const uint32_t* level_ends, uint32_t l0, uint32_t l1, fe* cells,
+                                                             const fe* values, const fe* consts) {
+  uint32_t begin = l0 ? level_ends[l0 - 1] : 0u;
+  for (uint32_t l = l0; l < l1; l++) {  // uniform trip count: every thread reaches every barrier
+    const uint32_t end = level_ends[l];
+    if (end - begin <= WP_WG && threadIdx.x < end - begin) witness_op<true>(ops[begin + threadIdx.x], cells, values, consts);
     begin = end;
     __syncthreads();
   }
@@ -166,6 +259,15 @@ static int witness_check(const h2mi_witness_desc* d) {
       case WP_COPY:
         if (op.a >= n || level_of[op.a] >= level) return H2MI_EINVAL;
         break;
+      case WP_DIVQ:
+      case WP_DIVR:  // bits: the flags; b: a constant or a cell of a lower level, by the flag
+        if (shift || (bits & ~(WP_DIV_CONST | WP_DIV_SIGNED)) || op.a >= n || level_of[op.a] >= level) return H2MI_EINVAL;
+        if (bits & WP_DIV_CONST ? op.b >= d->n_constants : (op.b >= n || level_of[op.b] >= level)) return H2MI_EINVAL;
+        break;
+      case WP_ISZERO:
+      case WP_INV:
+        if (bits || shift || op.b || op.a >= n || level_of[op.a] >= level) return H2MI_EINVAL;
+        break;
       case WP_GATE:
         if (op.dst < 3) return H2MI_EINVAL;
         for (uint32_t back = 1; back <= 3; back++)
@@ -191,6 +293,7 @@ struct WitnessProgram {
   uint32_t n_cells = 0, n_levels = 0, n_inputs = 0, n_constants = 0, n_checks = 0, n_columns = 0, n_grid = 0, n_wg = 0;
   uint64_t placed = 0, device_bytes = 0;
   bool ran = false;
+  bool hints = false;  // holds a hint op: its levels run in the _hints instantiations
   std::vector<uint32_t> level_ends;
   std::vector<uint64_t> column_start;  // in words of the column buffer
   std::vector<Segment> plan;
@@ -249,6 +352,7 @@ static int witness_create(const h2mi_witness_desc* d, h2mi_witness_t* out) {
   w->column_start.assign(d->n_columns + 1, 0);
   for (uint32_t j = 0; j < d->n_columns; j++) w->column_start[j + 1] = w->column_start[j] + d->counts[j];
   w->placed = w->column_start[d->n_columns];
+  for (uint32_t at = 0; at < d->n_ops; at++) w->hints |= (d->ops[at].code & 0xffu) >= WP_DIVQ;
   witness_plan(*w);
   const struct {
     DevMem& m;
@@ -298,7 +402,13 @@ static int witness_run(h2mi_witness_t h, const uint64_t* inputs, void** d_column
   for (const Segment& g : w->plan) {
     if (g.grid) {
       const uint32_t begin = g.l0 ? w->level_ends[g.l0 - 1] : 0u, count = w->level_ends[g.l0] - begin;
-      H2_LAUNCH("k_witness_level", k_witness_level, ceil_div_u32(count, WP_BLOCK), WP_BLOCK, 0, s, ops + begin, count, cells, values, consts);
+      if (w->hints)
+        H2_LAUNCH("k_witness_level_hints", k_witness_level_hints, ceil_div_u32(count, WP_BLOCK), WP_BLOCK, 0, s, ops + begin, count, cells, values, consts);
+      else
+        H2_LAUNCH("k_witness_level", k_witness_level, ceil_div_u32(count, WP_BLOCK), WP_BLOCK, 0, s, ops + begin, count, cells, values, consts);
+    } else if (w->hints) {
+      H2_LAUNCH("k_witness_levels_wg_hints", k_witness_levels_wg_hints, 1, WP_WG, 0, s, ops, (const uint32_t*)w->d_level_ends.as<uint32_t>(), g.l0, g.l1,
+                cells, values, consts);
     } else {
       H2_LAUNCH("k_witness_levels_wg", k_witness_levels_wg, 1, WP_WG, 0, s, ops, (const uint32_t*)w->d_level_ends.as<uint32_t>(), g.l0, g.l1, cells,
                 values, consts);

@@ -33,6 +33,42 @@ R = F.FR_MODULUS
 ADVICE, FIXED, INSTANCE = "advice", "fixed", "instance"
 _KIND = {ADVICE: engine.ADVICE, FIXED: engine.FIXED, INSTANCE: engine.INSTANCE}
 
+# the hints: values halo2-base computes outside the gates and assigns as witnesses (H2MI_WITNESS_DIVQ .. INV of include/h2mi.h)
+DIVQ, DIVR, ISZERO, INV = 8, 9, 10, 11
+HINT_CONST, HINT_SIGNED = 1, 2  # DIVQ / DIVR: the divisor is a constant, not a cell; the dividend is signed (above 2^252: x - r)
+
+
+def hint(kind: int, x: int, y: int = 0, flags: int = 0) -> int:
+    """THE definition of the four hints, on canonical integers below r: what flex.Context assigns, what witness.Program.cells replays
+    and what the device kernels are tested against.  DIVQ / DIVR: quotient and remainder of x by y, 0 for y = 0; signed, a dividend
+    above 2^252 is x - r, the quotient rounds toward minus infinity and is stored mod r, the remainder is in [0, y) (the reference's
+    signed_div_scale: src/gadget/fixed_point.rs:991-1001).  ISZERO: 1 for 0, else 0.  INV: x^-1 mod r, and 1 for 0 (halo2-base's
+    is_zero assigns Assigned::Trivial(1) there [RECALL])."""
+    if kind == ISZERO:
+        return int(x == 0)
+    if kind == INV:
+        return pow(x, -1, R) if x else 1
+    assert kind in (DIVQ, DIVR) and not flags & ~(HINT_CONST | HINT_SIGNED)
+    if y == 0:
+        return 0
+    if flags & HINT_SIGNED and x > 1 << 252:
+        x -= R
+    q, rem = divmod(x, y)  # Python's floor division: toward minus infinity, 0 <= rem < y
+    return q % R if kind == DIVQ else rem
+
+
+class Constant(int):
+    """an operand that is a constant of the circuit instead of a cell (QuantumCell::Constant); a plain integer operand is a cell"""
+
+
+class Aux:
+    """a value derived from cells and constants as x + y * z outside the columns (Context.derive): what halo2-base computes in Rust and
+    assigns as a Witness where it is not the fourth cell of a gate — the a - b of `sub`, the shifted value of `check_less_than`.  `ref`
+    is the recorder's (witness.RecordingContext): the unplaced cell of the tape that holds it."""
+
+    def __init__(self, value: int, ref=None):
+        self.value, self.ref = value, ref
+
 
 class FlexGateCS:
     """the constraint system of the Gate builder (lookup = False) or the Range builder (lookup = True) when the circuit
@@ -176,12 +212,22 @@ class Context:
         return len(self.cells) - 1
 
     def assign_region_last(self, items, gate_offsets) -> int:
+        """items: ("existing", cell) | ("constant", value) | ("witness", value), and for the values halo2-base computes outside the
+        gates: ("hint", (kind, a, b, flags)) — hint() of cell a and of cell b or, HINT_CONST, the constant b —, ("aux", Aux) — a
+        derived value — and ("copy", cell) — a cell's value again, the equality left to assign_region_smart"""
         base = len(self.cells)
         for kind, v in items:
             row = len(self.cells)
             if kind == "existing":
                 self.cells.append(self.cells[v])
                 self.eqs.append((row, v))
+            elif kind == "hint":
+                assert not isinstance(v[1], (Constant, Aux)), "a hint reads a cell: load_constant first"
+                self.cells.append(self.hint_value(*v))
+            elif kind == "aux":
+                self.cells.append(v.value)
+            elif kind == "copy":
+                self.cells.append(self.cells[v])
             else:
                 self.cells.append(v % R)
                 if kind == "constant":
@@ -190,12 +236,107 @@ class Context:
             self.gates.append(base + off)
         return len(self.cells) - 1
 
-    # GateInstructions
+    def assign_region_smart(self, items, gate_offsets, equalities) -> int:
+        """assign_region_last, then constrain_equal of the listed (offset, offset) pairs of the region"""
+        last = self.assign_region_last(items, gate_offsets)
+        base = last + 1 - len(items)
+        self.eqs += [(base + i, base + j) for i, j in equalities]
+        return last
+
+    def hint_value(self, kind, a, b, flags) -> int:
+        return hint(kind, self.cells[a], b % R if flags & HINT_CONST else self.cells[b], flags)
+
+    # operands: a cell (a plain integer: its index), a Constant or an Aux
+    def _v(self, q) -> int:
+        return q.value if isinstance(q, Aux) else int(q) % R if isinstance(q, Constant) else self.cells[q]
+
+    def _i(self, q):
+        return ("aux", q) if isinstance(q, Aux) else ("constant", int(q)) if isinstance(q, Constant) else ("existing", q)
+
+    def derive(self, x, y, z) -> Aux:
+        """x + y * z of operands, outside the columns"""
+        return Aux((self._v(x) + self._v(y) * self._v(z)) % R)
+
+    # GateInstructions [RECALL halo2-base 0.3 gates/flex_gate.rs; the layouts are tabled in DESIGN.md 4.5]
     def mul(self, a, b):
-        return self.assign_region_last([("constant", 0), ("existing", a), ("existing", b), ("witness", self.cells[a] * self.cells[b])], [0])
+        return self.assign_region_last([("constant", 0), self._i(a), self._i(b), ("witness", self._v(a) * self._v(b))], [0])
 
     def add(self, a, b):
-        return self.assign_region_last([("existing", a), ("existing", b), ("constant", 1), ("witness", self.cells[a] + self.cells[b])], [0])
+        return self.assign_region_last([self._i(a), self._i(b), ("constant", 1), ("witness", self._v(a) + self._v(b))], [0])
+
+    def sub(self, a, b):
+        """| a - b | b | 1 | a | -> the first cell"""
+        out = self.derive(a, b, Constant(-1))
+        return self.assign_region_last([("aux", out), self._i(b), ("constant", 1), self._i(a)], [0]) - 3
+
+    def neg(self, a):
+        """| a | -a | 1 | 0 | -> the second cell"""
+        out = self.derive(Constant(0), a, Constant(-1))
+        return self.assign_region_last([self._i(a), ("aux", out), ("constant", 1), ("constant", 0)], [0]) - 2
+
+    def mul_add(self, a, b, c):
+        """| c | a | b | a * b + c |"""
+        return self.assign_region_last([self._i(c), self._i(a), self._i(b), ("witness", self._v(a) * self._v(b) + self._v(c))], [0])
+
+    def select(self, a, b, sel):
+        """sel ? a : b as | a - b | 1 | b | a | b | sel | a - b | out |, gates at 0 and 4, cells 0 = 6 and 2 = 4"""
+        diff = self.derive(a, b, Constant(-1))
+        base = len(self.cells)
+        return self.assign_region_smart([("aux", diff), ("constant", 1), self._i(b), self._i(a), self._i(b), self._i(sel), ("copy", base),
+                                         ("witness", diff.value * self._v(sel) + self._v(b))], [0, 4], [(0, 6), (2, 4)])
+
+    def not_(self, a):
+        return self.sub(Constant(1), a)
+
+    def and_(self, a, b):
+        return self.mul(a, b)
+
+    def or_(self, a, b):
+        """| 1 - b | 1 | b | 1 | b | a | 1 - b | a + b - a * b |, gates at 0 and 4, cells 0 = 6 and 2 = 4"""
+        not_b = self.derive(Constant(1), b, Constant(-1))
+        base = len(self.cells)
+        return self.assign_region_smart([("aux", not_b), ("constant", 1), self._i(b), ("constant", 1), self._i(b), self._i(a), ("copy", base),
+                                         ("witness", self._v(b) + self._v(a) * not_b.value)], [0, 4], [(0, 6), (2, 4)])
+
+    def is_zero(self, a):
+        """| is_zero | a | inv | 1 | 0 | a | is_zero | 0 |: is_zero + a * inv = 1 and a * is_zero = 0, cells 0 = 6 -> cell 6.  inv is
+        a^-1, or 1 for a = 0; a is a cell"""
+        base = len(self.cells)
+        return self.assign_region_smart([("hint", (ISZERO, a, 0, 0)), ("existing", a), ("hint", (INV, a, 0, 0)), ("constant", 1), ("constant", 0),
+                                         ("existing", a), ("copy", base), ("constant", 0)], [0, 4], [(0, 6)]) - 1
+
+    def is_equal(self, a, b):
+        return self.is_zero(self.sub(a, b))
+
+    def assert_bit(self, x):
+        """| 0 | x | x | x |"""
+        self.assign_region_last([("constant", 0), self._i(x), self._i(x), self._i(x)], [0])
+
+    def assert_is_const(self, a, c: int):
+        """no cell: cell a joins the constant's fixed cell"""
+        self.const_cells.append((a, c % R))
+
+    def load_constant(self, c: int) -> int:
+        return self.assign_region_last([("constant", c)], [])
+
+    def load_zero(self) -> int:
+        """one cell, the first time; the same cell afterwards"""
+        if getattr(self, "_zero", None) is None:
+            self._zero = self.load_constant(0)
+        return self._zero
+
+    def sum(self, a):
+        """| a0 | a1 | 1 | a0 + a1 | a2 | 1 | a0 + a1 + a2 | ...: a gate every third cell; one operand: its cell again; none: load_zero"""
+        a = list(a)
+        if not a:
+            return self.load_zero()
+        if len(a) == 1:
+            return self.assign_region_last([self._i(a[0])], [])
+        acc, items = self._v(a[0]), [self._i(a[0])]
+        for q in a[1:]:
+            acc += self._v(q)
+            items += [self._i(q), ("constant", 1), ("witness", acc)]
+        return self.assign_region_last(items, [3 * i for i in range(len(a) - 1)])
 
     def add_constant(self, a, c):
         return self.assign_region_last([("existing", a), ("constant", c), ("constant", 1), ("witness", self.cells[a] + c)], [0])
@@ -229,6 +370,48 @@ class Context:
         elif rem:  # the top limb times 2^(lookup_bits - rem) must be in the table too
             self.lookup_cells.append(self.assign_region_last([("constant", 0), ("existing", rows[-1]), ("constant", 1 << (lookup_bits - rem)),
                                                               ("witness", limbs[-1] << (lookup_bits - rem))], [0]))
+
+    # RangeInstructions [RECALL halo2-base 0.3 gates/range.rs]; the limbs are of self.lookup_bits bits (the scaffold sets it)
+    def _shifted(self, a, b, bits: int) -> int:
+        """| a + 2^bits - b | b | 1 | a + 2^bits | -2^bits | 1 | a |, gates at 0 and 3 -> the first cell"""
+        shift_a = self.derive(a, Constant(1 << bits), Constant(1))
+        shifted = self.derive(shift_a, b, Constant(-1))
+        return self.assign_region_last([("aux", shifted), self._i(b), ("constant", 1), ("witness", shift_a.value), ("constant", -(1 << bits)),
+                                        ("constant", 1), self._i(a)], [0, 3]) - 6
+
+    def check_less_than(self, a, b, num_bits: int):
+        """a < b for a, b below 2^num_bits: a + 2^num_bits - b is range-checked to num_bits bits"""
+        self.range_check(self._shifted(a, b, num_bits), num_bits, self.lookup_bits)
+
+    def check_big_less_than_safe(self, a, b: int):
+        """a < b for a cell a and an integer b: range_check to b's bit length rounded up to whole limbs, then check_less_than"""
+        range_bits = -(-b.bit_length() // self.lookup_bits) * self.lookup_bits
+        self.range_check(a, range_bits, self.lookup_bits)
+        self.check_less_than(a, Constant(b), range_bits)
+
+    def is_less_than(self, a, b, num_bits: int) -> int:
+        """the bit a < b for a, b below 2^num_bits: a + 2^padded - b is range-checked to one limb more than padded bits, and that top limb
+        (the last cell to look up) is zero exactly when a < b"""
+        padded = -(-num_bits // self.lookup_bits) * self.lookup_bits
+        self.range_check(self._shifted(a, b, padded), padded + self.lookup_bits, self.lookup_bits)
+        return self.is_zero(self.lookup_cells[-1])
+
+    def div_mod(self, a, b: int, a_num_bits: int):
+        """(a div b, a mod b) for a cell a below 2^a_num_bits and an integer b: | rem | b | div | a |, then div < 2^a_num_bits / b + 1 and
+        rem < b"""
+        last = self.assign_region_last([("hint", (DIVR, a, b, HINT_CONST)), ("constant", b), ("hint", (DIVQ, a, b, HINT_CONST)), ("existing", a)], [0])
+        rem, div = last - 3, last - 1
+        self.check_big_less_than_safe(div, (1 << a_num_bits) // b + 1)
+        self.check_big_less_than_safe(rem, b)
+        return div, rem
+
+    def div_mod_var(self, a, b, a_num_bits: int, b_num_bits: int):
+        """the same by a cell b below 2^b_num_bits: div is range-checked to a_num_bits bits, rem < b.  b = 0 satisfies nothing"""
+        last = self.assign_region_last([("hint", (DIVR, a, b, 0)), ("existing", b), ("hint", (DIVQ, a, b, 0)), ("existing", a)], [0])
+        rem, div = last - 3, last - 1
+        self.range_check(div, a_num_bits, self.lookup_bits)
+        self.check_less_than(rem, b, b_num_bits)
+        return div, rem
 
     def finish(self, public_rows):
         asg = self.asg

@@ -3,8 +3,10 @@
 `scaffold.prove_private` refuses a closure whose shape depends on its inputs (the break-point check), so under that rule a closure
 `f(ctx, inputs, make_public)` is a fixed straight-line program over field elements in which only the private inputs change from proof
 to proof.  `Program.record` runs the closure once in a `RecordingContext` — `flex.Context` with an op noted per cell — and keeps the
-tape: one op per cell of `Context.cells` (INPUT, CONST, COPY, GATE, LIMB: include/h2mi.h), sorted into levels; the equalities no COPY
-makes true (the checks); per advice column the flat cell index of every row (the placement, exactly what `finish` / `_finish_multi`
+tape: one op per cell of `Context.cells` (INPUT, CONST, COPY, GATE, LIMB and the hints DIVQ, DIVR, ISZERO, INV: include/h2mi.h), sorted
+into levels; behind them the auxiliary cells no column places — a value derived outside the gates (the a - b of `sub`) is the GATE of three
+such cells, and an enabled gate whose fourth cell is not a GATE op is computed once more among them; the equalities no COPY makes true
+(the checks), the auxiliary gates against their fourth cells among them; per advice column the flat cell index of every row (the placement, exactly what `finish` / `_finish_multi`
 do with the cells); the public cells.  `Program.cells` interprets the tape on Python integers (the tests' reference);
 `Program.on_device` hands it to libh2mi.so (engine.WitnessProgram: csrc/h2mi_witness.hip), whose run leaves dense Montgomery columns
 in HBM that the advice call takes as engine.DeviceCells.  What a tape cannot express — a value computed in Python from the inputs
@@ -18,6 +20,7 @@ from . import field as F
 
 R = F.FR_MODULUS
 INPUT, CONST, COPY, GATE, LIMB = range(5)  # H2MI_WITNESS_*
+HINTS = (flex.DIVQ, flex.DIVR, flex.ISZERO, flex.INV)
 WG_OPS, WG_LEVELS = 1024, 4096  # H2MI_WITNESS_WG_OPS, H2MI_WITNESS_WG_LEVELS
 
 
@@ -58,8 +61,28 @@ class RecordingContext(flex.Context):
 
     def __init__(self, asg):
         super().__init__(asg)
-        self.ops = []  # per cell: (kind, a, bits, shift)
+        self.ops = []  # per cell: (kind, a, bits, shift), a hint (kind, a, flags, 0, b)
         self.constants, self._constant_index = [], {}
+        # the cells no column places, numbered -1, -2, ... until the cells are counted (from_context), and their checks
+        self.aux_ops, self.aux_checks = [], []
+
+    def _aux(self, op) -> int:
+        self.aux_ops.append(op)
+        return -len(self.aux_ops)
+
+    def _aux_gate(self, operands) -> int:
+        """x + y * z of three operands ((COPY, cell) or (CONST, index)) as four consecutive auxiliary cells -> the gate's"""
+        for kind, a in operands:
+            self._aux((kind, a, 0, 0))
+        return self._aux((GATE, 0, 0, 0))
+
+    def derive(self, x, y, z) -> flex.Aux:
+        operand = lambda q: (COPY, q.ref) if isinstance(q, flex.Aux) else (CONST, self._constant(int(q) % R)) if isinstance(q, flex.Constant) else (COPY, q)
+        return flex.Aux(super().derive(x, y, z).value, self._aux_gate([operand(q) for q in (x, y, z)]))
+
+    def assert_is_const(self, a, c: int):
+        super().assert_is_const(a, c)
+        self.aux_checks.append((a, self._aux((CONST, self._constant(c % R), 0, 0))))
 
     def _constant(self, v: int) -> int:
         if v not in self._constant_index:
@@ -74,7 +97,9 @@ class RecordingContext(flex.Context):
         self.ops.append((INPUT, v.index, 0, 0))
         return super().load_witness(v)
 
-    def assign_region_last(self, items, gate_offsets) -> int:
+    def assign_region_last(self, items, gate_offsets, gates_hold: bool = False) -> int:
+        """gates_hold: the caller knows the region's gates to hold for every input (range_check's one-bit top limb), so a gate that
+        closes on a cell that is no GATE op needs no check"""
         base = len(self.cells)
         fourth = {off + 3 for off in gate_offsets}
         value = lambda row: vals[row - base] if row >= base else self.cells[row]
@@ -87,6 +112,16 @@ class RecordingContext(flex.Context):
             elif kind == "constant":
                 ops.append((CONST, self._constant(v % R), 0, 0))
                 vals.append(v % R)
+            elif kind == "hint":
+                hint_kind, a, b, flags = v
+                ops.append((hint_kind, a, flags, 0, self._constant(b % R) if flags & flex.HINT_CONST else b))
+                vals.append(self.hint_value(*v))
+            elif kind == "aux":
+                ops.append((COPY, v.ref, 0, 0))
+                vals.append(v.value)
+            elif kind == "copy":
+                ops.append((COPY, v, 0, 0))
+                vals.append(value(v))
             elif isinstance(v, Input):
                 ops.append((INPUT, v.index, 0, 0))
                 vals.append(v % R)
@@ -99,6 +134,9 @@ class RecordingContext(flex.Context):
             else:
                 raise ValueError(f"cell {row}: a witness value that is neither an Input nor the fourth cell of a gate enabled in this call")
         self.ops += ops
+        for off in gate_offsets:  # a gate that closes on an existing cell, a constant or an input: computed once more, and compared
+            if ops[off + 3][0] != GATE and not gates_hold:
+                self.aux_checks.append((base + off + 3, self._aux_gate([(COPY, base + off + i) for i in range(3)])))
         return super().assign_region_last(items, gate_offsets)
 
     def range_check(self, a, range_bits: int, lookup_bits: int):
@@ -132,7 +170,7 @@ class RecordingContext(flex.Context):
         self.lookup_cells += rows
         rem = range_bits % lookup_bits
         if rem == 1:
-            self.assign_region_last([("constant", 0), ("existing", rows[-1]), ("existing", rows[-1]), ("existing", rows[-1])], [0])
+            self.assign_region_last([("constant", 0), ("existing", rows[-1]), ("existing", rows[-1]), ("existing", rows[-1])], [0], gates_hold=True)
         elif rem:
             self.lookup_cells.append(self.assign_region_last([("constant", 0), ("existing", rows[-1]), ("constant", 1 << (lookup_bits - rem)),
                                                               ("witness", limbs[-1] << (lookup_bits - rem))], [0]))
@@ -191,15 +229,17 @@ def segmentation(level_sizes):
 class Program:
     """a recorded closure.  ops: (n_cells, 4) uint32 rows (dst, kind | bits << 8 | shift << 16, a, b) sorted by level; level_ends;
     constants (integers below r); n_inputs; checks [(a, b)]; placement (one uint32 array of cell indices per advice column); public
-    (the cells of make_public); break_points (of the gate columns, as gen_key returns them)."""
+    (the cells of make_public); break_points (of the gate columns, as gen_key returns them); n_aux: the last n_aux cells are auxiliary
+    (no column places them, and `cells` does not return them)."""
 
-    def __init__(self, ops, level_ends, constants, n_inputs, checks, placement, public, break_points=()):
+    def __init__(self, ops, level_ends, constants, n_inputs, checks, placement, public, break_points=(), n_aux: int = 0):
         self.ops = np.ascontiguousarray(np.asarray(ops, dtype=np.uint32).reshape(-1, 4))
         self.level_ends = np.ascontiguousarray(level_ends, dtype=np.uint32)
         self.constants, self.n_inputs = [int(c) for c in constants], int(n_inputs)
         self.checks = [(int(a), int(b)) for a, b in checks]
         self.placement = [np.ascontiguousarray(p, dtype=np.uint32) for p in placement]
         self.public, self.break_points = [int(c) for c in public], list(break_points)
+        self.n_aux = int(n_aux)
         self._device = None
 
     @property
@@ -215,17 +255,39 @@ class Program:
     def from_context(cls, ctx: RecordingContext, n_inputs: int, public) -> "Program":
         n = len(ctx.cells)
         assert len(ctx.ops) == n, "every cell has its op"
-        operands = lambda i, op: (i - 3, i - 2, i - 1) if op[0] == GATE else (op[1],) if op[0] in (COPY, LIMB) else ()
-        level = [0] * n
-        for i, op in enumerate(ctx.ops):  # operands precede their reader in program order
-            level[i] = 1 + max((level[s] for s in operands(i, op)), default=-1)
-        order = sorted(range(n), key=lambda i: (level[i], i))
-        rows = [(i, ctx.ops[i][0] | ctx.ops[i][2] << 8 | ctx.ops[i][3] << 16, ctx.ops[i][1], 0) for i in order]
-        sizes = np.bincount(np.array(level, dtype=np.int64), minlength=1) if n else np.zeros(0, dtype=np.int64)
-        made = {(i, op[1]) for i, op in enumerate(ctx.ops) if op[0] == COPY}  # the equalities a COPY makes true
-        checks = [(a, b) for a, b in ctx.eqs if (a, b) not in made and (b, a) not in made]
+        cell = lambda s: s if s >= 0 else n - 1 - s  # auxiliary cell -1 - j is cell n + j
+        ops = [tuple(op) + (0,) * (5 - len(op)) for op in list(ctx.ops) + ctx.aux_ops]
+        ops = [(kind, cell(a) if kind in (COPY, LIMB) + HINTS else a, bits, shift, cell(b) if kind in (flex.DIVQ, flex.DIVR) and not bits & flex.HINT_CONST else b)
+               for kind, a, bits, shift, b in ops]
+        total = len(ops)
+
+        def operands(i):
+            kind, a, bits, _, b = ops[i]
+            if kind == GATE:
+                return (i - 3, i - 2, i - 1)
+            if kind in (flex.DIVQ, flex.DIVR) and not bits & flex.HINT_CONST:
+                return (a, b)
+            return (a,) if kind in (COPY, LIMB) + HINTS else ()
+
+        level = [None] * total  # one above the highest operand; an auxiliary cell may be read by a cell of a lower index
+        for root in range(total):
+            stack = [root]
+            while stack:
+                i = stack[-1]
+                if level[i] is None:
+                    waiting = [s for s in operands(i) if level[s] is None]
+                    if waiting:
+                        stack += waiting
+                        continue
+                    level[i] = 1 + max((level[s] for s in operands(i)), default=-1)
+                stack.pop()
+        order = sorted(range(total), key=lambda i: (level[i], i))
+        rows = [(i, ops[i][0] | ops[i][2] << 8 | ops[i][3] << 16, ops[i][1], ops[i][4]) for i in order]
+        sizes = np.bincount(np.array(level, dtype=np.int64), minlength=1) if total else np.zeros(0, dtype=np.int64)
+        made = {(i, op[1]) for i, op in enumerate(ops) if op[0] == COPY}  # the equalities a COPY makes true
+        checks = [(a, b) for a, b in ctx.eqs if (a, b) not in made and (b, a) not in made] + [(cell(a), cell(b)) for a, b in ctx.aux_checks]
         placement, breaks = place(n, ctx.gates, ctx.lookup_cells, ctx.asg.cs)
-        return cls(rows, np.cumsum(sizes), ctx.constants, n_inputs, checks, placement, public, breaks)
+        return cls(rows, np.cumsum(sizes), ctx.constants, n_inputs, checks, placement, public, breaks, n_aux=total - n)
 
     @classmethod
     def record(cls, f, dummy_inputs, cs, lookup_bits):
@@ -255,7 +317,7 @@ class Program:
         if len(values) != self.n_inputs:
             raise ValueError(f"the program takes {self.n_inputs} inputs, not {len(values)}")
         cells = [None] * self.n_cells
-        for dst, code, a, _ in self.ops.tolist():
+        for dst, code, a, b in self.ops.tolist():
             kind, bits, shift = code & 0xFF, (code >> 8) & 0xFF, (code >> 16) & 0xFF
             if kind == INPUT:
                 cells[dst] = values[a]
@@ -265,12 +327,14 @@ class Program:
                 cells[dst] = cells[a]
             elif kind == GATE:
                 cells[dst] = (cells[dst - 3] + cells[dst - 2] * cells[dst - 1]) % R
-            else:
+            elif kind == LIMB:
                 cells[dst] = (cells[a] >> shift) & ((1 << bits) - 1)
+            else:  # a hint; bits holds its flags
+                cells[dst] = flex.hint(kind, cells[a], (self.constants[b] if bits & flex.HINT_CONST else cells[b]) if kind in (flex.DIVQ, flex.DIVR) else 0, bits)
         for i, (a, b) in enumerate(self.checks):
             if cells[a] != cells[b]:
                 raise ValueError(f"witness out of range: check {i} fails, cells {a} and {b} differ")
-        return cells
+        return cells[:self.n_cells - self.n_aux]
 
     def columns(self, cells) -> list:
         """the dense advice columns of a cell list, by the placement"""

@@ -376,14 +376,29 @@ int h2mi_fr_compact_cells_dev(h2mi_cells_compacted* cols, uint32_t n_cols, unsig
 /* Witness programs: a builder closure whose shape does not depend on its inputs is a fixed straight-line program over field elements.
  * Recorded once (the Python recorder is halo2-scaffold_amd/witness.py), it is evaluated on the device for every proof and its cells land
  * in dense Montgomery columns that h2mi_prover_advice takes as H2MI_CELLS_DEVICE (h2mi_prover.h) — no cell crosses the host.
- * The program describes a flat list of n_ops cells, one op per cell: op = (dst, kind | bits << 8 | shift << 16, a, b), 16 bytes.
+ * The program describes a flat list of n_ops cells, one op per cell: op = (dst, kind | bits << 8 | shift << 16, a, b), 16 bytes; the top
+ * byte of the code is zero.
  *   H2MI_WITNESS_INPUT  cells[dst] = inputs[a]          (h2mi_witness_run's inputs: canonical, below r)
  *   H2MI_WITNESS_CONST  cells[dst] = constants[a]       (canonical, below r)
  *   H2MI_WITNESS_COPY   cells[dst] = cells[a]
  *   H2MI_WITNESS_GATE   cells[dst] = cells[dst - 3] + cells[dst - 2] * cells[dst - 1]      (the fourth cell of a vertical gate)
  *   H2MI_WITNESS_LIMB   cells[dst] = (canonical(cells[a]) >> shift) & (2^bits - 1), 1 <= bits <= 64, shift + bits <= 254
+ * The hint ops — the values a builder computes outside the gates and assigns as witnesses.  With x = canonical(cells[a]), 0 <= x < r:
+ *   H2MI_WITNESS_DIVQ   cells[dst] = the quotient, H2MI_WITNESS_DIVR the remainder, of x by y.  The bits byte holds the flags:
+ *                       H2MI_WITNESS_DIV_CONST: y = constants[b], otherwise y = canonical(cells[b]) — b is the second operand;
+ *                       H2MI_WITNESS_DIV_SIGNED: a dividend x > 2^252 is read as x~ = x - r (the fixed-point chip's negative numbers).
+ *                       Unsigned: q = floor(x / y), rem = x - y q.  Signed: q = floor(x~ / y), rounded toward minus infinity and stored
+ *                       modulo r, rem = x~ - y q in [0, y).  y = 0 gives 0 for both.  shift = 0; any other flag bit is refused.
+ *   H2MI_WITNESS_ISZERO cells[dst] = 1 if x = 0, else 0.                        No flags, shift = 0, b = 0.
+ *   H2MI_WITNESS_INV    cells[dst] = x^-1 mod r, and 1 for x = 0 (what halo2-base's is_zero assigns there).  No flags, shift = 0, b = 0.
+ * Kinds 5 .. 7 are unassigned and refused, as is every kind above H2MI_WITNESS_INV.  A program that holds a hint op runs its levels in
+ * a second instantiation of the two level kernels, k_witness_level_hints / k_witness_levels_wg_hints, under the same launch rule; a
+ * program without one launches what it always launched.
+ * Cells that no column places are allowed: a recorder uses them for values derived outside the columns and for gates it evaluates once
+ * more to compare them, by a check, with a fourth cell that is not a GATE op.
  * Levels: ops[level_ends[l - 1] .. level_ends[l]) are level l (level_ends[-1] = 0, no level is empty, the last one ends at n_ops); an op
- * reads only cells written at strictly lower levels.  checks: n_checks pairs (a, b) of cells that must hold equal values (the
+ * reads only cells written at strictly lower levels: cell a of COPY, LIMB and the hints, cell b of a DIVQ / DIVR whose divisor is a
+ * cell, the three cells before dst of a GATE.  checks: n_checks pairs (a, b) of cells that must hold equal values (the
  * equalities no COPY makes true, such as range_check's constrain_equal of the value with its recomposed limbs).  Placement: column j of
  * the n_columns dense output columns is cells[placement[start_j + row]] for row < counts[j], start_j = counts[0] + .. + counts[j - 1].
  * Launches (the rule is part of the interface): a level of more than H2MI_WITNESS_WG_OPS ops is one k_witness_level launch; every
@@ -392,7 +407,8 @@ int h2mi_fr_compact_cells_dev(h2mi_cells_compacted* cols, uint32_t n_cols, unsig
  * evaluates the checks.
  * h2mi_witness_check (host only, works without a GPU; h2mi_witness_create applies it first): H2MI_EINVAL for an unknown kind, a dst
  * named twice or never, an operand whose level is not strictly below its reader's, level_ends that do not ascend to n_ops, a GATE with
- * dst < 3, shift / bits outside their bounds, an INPUT or CONST index out of range, a constant not below r, a placement source or a
+ * dst < 3, shift / bits outside their bounds, an unknown flag or a shift on a hint, flags or b on ISZERO / INV, an INPUT or CONST index
+ * (DIVQ / DIVR with H2MI_WITNESS_DIV_CONST: b) out of range, a constant not below r, a placement source or a
  * check index >= n_ops, a null array with a nonzero count; H2MI_ERANGE for more than 2^28 cells, more than 2^28 cells in one column or
  * more than H2MI_WITNESS_MAX_COLUMNS columns.
  * h2mi_witness_create uploads the program once and allocates the cells and column buffers (H2MI_EINVAL with more than one device
@@ -408,6 +424,12 @@ int h2mi_fr_compact_cells_dev(h2mi_cells_compacted* cols, uint32_t n_cols, unsig
 #define H2MI_WITNESS_COPY 2u
 #define H2MI_WITNESS_GATE 3u
 #define H2MI_WITNESS_LIMB 4u
+#define H2MI_WITNESS_DIVQ 8u
+#define H2MI_WITNESS_DIVR 9u
+#define H2MI_WITNESS_ISZERO 10u
+#define H2MI_WITNESS_INV 11u
+#define H2MI_WITNESS_DIV_CONST 1u  /* flags of DIVQ / DIVR, in the bits byte */
+#define H2MI_WITNESS_DIV_SIGNED 2u
 #define H2MI_WITNESS_WG_OPS 1024u    /* the workgroup limit */
 #define H2MI_WITNESS_WG_LEVELS 4096u /* keeps any one kernel short whatever the circuit's depth */
 #define H2MI_WITNESS_MAX_COLUMNS 64u /* = H2MI_MAX_ADVICE of h2mi_prover.h */
@@ -429,8 +451,8 @@ typedef struct {
 typedef struct {
   uint32_t n_cells;
   uint32_t n_levels;
-  uint32_t n_grid_launches; /* k_witness_level launches of one run */
-  uint32_t n_wg_launches;   /* k_witness_levels_wg launches of one run */
+  uint32_t n_grid_launches; /* k_witness_level (or k_witness_level_hints) launches of one run */
+  uint32_t n_wg_launches;   /* k_witness_levels_wg (or k_witness_levels_wg_hints) launches of one run */
   uint64_t device_bytes;    /* held by the program: ops, cells, columns, placement, checks, constants, inputs */
 } h2mi_witness_info_t;
 typedef void* h2mi_witness_t;
