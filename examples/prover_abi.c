@@ -302,7 +302,14 @@ int main(int argc, char** argv) {
   fixed[4].rows = row2;   fixed[4].values = c72.l;    fixed[4].count = 1;
   const uint32_t copies[16] = {0, 1, 0, 0, 1, 1, 0, 0, 0, 2, 0, 0, 1, 2, 0, 0}; /* constrain_equal(new cell, (a, 0)) in call order */
   h2mi_pk_t pk = NULL;
-  check(h2mi_prover_keygen(&cs, hgl, fixed, copies, 4, 0, &pk), "keygen");
+  h2mi_keygen_args keygen_args;
+  memset(&keygen_args, 0, sizeof(keygen_args)); /* every optional field NULL: a hard-wired shape, one phase, no shuffles, flags 0 */
+  keygen_args.cs = &cs;
+  keygen_args.g_lagrange_handle = hgl;
+  keygen_args.fixed = fixed;
+  keygen_args.copies = copies;
+  keygen_args.n_copies = 4;
+  check(h2mi_prover_keygen(&keygen_args, &pk), "keygen");
 
   /* the verifying key: k, degree, the eight compressed commitments; transcript_repr = the hosts' stand-in (see the header comment) */
   uint64_t commitments[8 * 8];

@@ -149,22 +149,16 @@ def _load():
         "h2mi_profile_dump": ([C.c_char_p, sz, C.POINTER(sz)], C.c_int),
         "h2mi_profile_query": ([C.c_char_p, C.POINTER(C.c_double), u64p], C.c_int),
         # include/h2mi_prover.h: the resident prover behind its phase-level ABI
-        "h2mi_prover_keygen": ([vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
+        "h2mi_prover_keygen": ([vp, C.POINTER(vp)], C.c_int),
         "h2mi_column_cells_check": ([vp, C.c_uint32, C.c_uint], C.c_int),
         "h2mi_gate_program_check": ([vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_shape_gate_program": ([vp, vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, C.POINTER(C.c_uint32)], C.c_int),
-        "h2mi_prover_keygen_gates": ([vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_lookup_program_check": ([vp, vp, C.POINTER(C.c_uint32)], C.c_int),
-        "h2mi_prover_keygen_exprs": ([vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_advice_phases_check": ([vp, vp, vp, vp], C.c_int),
-        "h2mi_prover_keygen_phases": ([vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_shuffle_program_check": ([vp, vp, C.POINTER(C.c_uint32)], C.c_int),
         "h2mi_shuffle_phases_check": ([vp, vp, vp, C.POINTER(C.c_uint32)], C.c_int),
-        "h2mi_prover_keygen_shuffles": ([vp, vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_logup_inputs_check": ([vp, vp, vp, vp, C.POINTER(C.c_uint32)], C.c_int),
-        "h2mi_prover_keygen_logup": ([vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_table_logup_check": ([vp, vp, C.POINTER(C.c_uint32)], C.c_int),
-        "h2mi_prover_keygen_table_logup": ([vp, vp, C.c_uint64, vp, vp, sz, C.c_uint, C.POINTER(vp)], C.c_int),
         "h2mi_prover_pk_release": ([vp], C.c_int),
         # proving-key files: one self-describing blob out of HBM and back
         "h2mi_prover_pk_export": ([vp, vp, sz, vp, sz, C.POINTER(sz)], C.c_int),

@@ -355,11 +355,14 @@ int check_phases(const h2mi_constraint_system& cs, const h2mi_gate_program* gate
   return rc;
 }
 
-void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, const h2mi_advice_phases* phases,
-              const h2mi_shuffle_program* shuffles, const h2mi_logup_inputs* inputs = nullptr, bool table_logup = false) {
+// H2MI_KEYGEN_LOGUP on a hard-wired shape: logUp over cs->lookups[], with `inputs` as the grouping (h2mi_table_logup_check)
+bool table_mode(const h2mi_keygen_args& args) { return (args.flags & H2MI_KEYGEN_LOGUP) && args.cs->gates != H2MI_GATES_EXPRESSIONS; }
+
+void validate(const h2mi_keygen_args& args) {
+  const h2mi_constraint_system& cs = *args.cs;
   auto bad = [](const char* what) { throw Error(H2MI_EINVAL, std::string("constraint system: ") + what); };
-  const uint32_t n_ch = phases ? phases->n_challenges : 0;
-  if (phases && check_phases(cs, gates, lookups, *phases, inputs)) bad("advice phases / challenges");
+  const uint32_t n_ch = args.phases ? args.phases->n_challenges : 0;
+  if (args.phases && check_phases(cs, args.gates, args.lookups, *args.phases, args.inputs)) bad("advice phases / challenges");
   if (cs.k == 0 || cs.k > H2MI_MAX_LOG_N) throw Error(H2MI_ERANGE, "constraint system: k");
   if (cs.degree < 3 || cs.degree > 9) bad("degree");
   if (((uint64_t)1 << cs.k) <= (uint64_t)cs.blinding_factors + 2) throw Error(H2MI_ERANGE, "constraint system: no usable rows");
@@ -383,20 +386,20 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, 
   } else if (cs.gates == H2MI_GATES_FLEX_VERTICAL || cs.gates == H2MI_GATES_EXPRESSIONS) {
     if (cs.gates == H2MI_GATES_EXPRESSIONS) {
       // the permutation products take any chunk length, and so does the quotient kernel that interprets the program
-      if (!gates) bad("gates given as expressions go through h2mi_prover_keygen_gates");
-      if (check_program(cs, gates, nullptr, n_ch)) bad("gate program");
+      if (!args.gates) bad("gates given as expressions need a gate program");
+      if (check_program(cs, args.gates, nullptr, n_ch)) bad("gate program");
     } else {
       if (cs.n_gates == 0 || cs.n_gates > H2MI_MAX_GATES) bad("gate count");
       for (uint32_t g = 0; g < cs.n_gates; g++)
         if (cs.gate_advice[g] >= cs.n_advice || cs.gate_selector[g] >= cs.n_fixed) bad("gate columns");
       // (a table-logUp key's quotient is the interpreting kernel's, which takes any chunk; merged arguments need the degree)
-      if (cs.n_perm && cs.degree - 2 > 3 && !table_logup) bad("permutation chunks longer than three columns");
+      if (cs.n_perm && cs.degree - 2 > 3 && !table_mode(args)) bad("permutation chunks longer than three columns");
     }
-    if (lookups) {  // the lookups as a program: cs.lookups[] is not read
-      if (cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_exprs takes H2MI_GATES_EXPRESSIONS");
-      if (check_lookup_program(cs, lookups, nullptr, nullptr, n_ch, inputs)) bad("lookup program");
+    if (args.lookups) {  // the lookups as a program: cs.lookups[] is not read
+      if (cs.gates != H2MI_GATES_EXPRESSIONS) bad("a lookup program takes H2MI_GATES_EXPRESSIONS");
+      if (check_lookup_program(cs, args.lookups, nullptr, nullptr, n_ch, args.inputs)) bad("lookup program");
     }
-    for (uint32_t l = 0; !lookups && l < cs.n_lookups; l++) {
+    for (uint32_t l = 0; !args.lookups && l < cs.n_lookups; l++) {
       const h2mi_lookup& lk = cs.lookups[l];
       if (lk.input.kind != H2MI_COL_ADVICE || lk.input.index >= cs.n_advice || lk.table_fixed >= cs.n_fixed) bad("lookup columns");
       if (lk.selector_fixed >= (int32_t)cs.n_fixed || lk.selector_fixed < -1) bad("lookup selector");
@@ -407,10 +410,10 @@ void validate(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, 
   uint32_t ext_k = cs.k;
   while (((uint64_t)1 << ext_k) < ((uint64_t)1 << cs.k) * (cs.degree - 1)) ext_k++;
   if (ext_k - cs.k > 4 || ext_k > H2MI_MAX_LOG_N) throw Error(H2MI_ERANGE, "constraint system: extended domain");
-  if ((gates || lookups) && cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_gates / _exprs take H2MI_GATES_EXPRESSIONS");
-  if (shuffles) {
-    if (cs.gates != H2MI_GATES_EXPRESSIONS) bad("h2mi_prover_keygen_shuffles takes H2MI_GATES_EXPRESSIONS");
-    if (check_shuffle_program(cs, shuffles, nullptr, nullptr, n_ch)) bad("shuffle program");
+  if ((args.gates || args.lookups) && cs.gates != H2MI_GATES_EXPRESSIONS) bad("a gate or lookup program takes H2MI_GATES_EXPRESSIONS");
+  if (args.shuffles) {
+    if (cs.gates != H2MI_GATES_EXPRESSIONS) bad("a shuffle program takes H2MI_GATES_EXPRESSIONS");
+    if (check_shuffle_program(cs, args.shuffles, nullptr, nullptr, n_ch)) bad("shuffle program");
   }
 }
 
@@ -421,7 +424,7 @@ struct TableLogup {
   uint32_t first[H2MI_MAX_LOOKUPS], sets[H2MI_MAX_LOOKUPS];
 };
 int check_table_logup(const h2mi_constraint_system& cs, const h2mi_logup_inputs* li, uint32_t* degree_out, TableLogup* out) {
-  if (cs.gates != H2MI_GATES_STANDARD_PLONK && cs.gates != H2MI_GATES_FLEX_VERTICAL) return H2MI_EINVAL;  // a program's lookups: h2mi_prover_keygen_logup
+  if (cs.gates != H2MI_GATES_STANDARD_PLONK && cs.gates != H2MI_GATES_FLEX_VERTICAL) return H2MI_EINVAL;  // a program's lookups are a lookup program
   if (cs.n_lookups == 0 || cs.n_lookups > H2MI_MAX_LOOKUPS || cs.n_advice > H2MI_MAX_ADVICE || cs.n_fixed > H2MI_MAX_FIXED) return H2MI_EINVAL;
   for (uint32_t l = 0; l < cs.n_lookups; l++) {
     const h2mi_lookup& lk = cs.lookups[l];
@@ -457,7 +460,7 @@ int check_table_logup(const h2mi_constraint_system& cs, const h2mi_logup_inputs*
 
 struct Table {  // a lookup table's distinct usable values in ascending canonical order, for the device's counting sort
   Dev sorted, sorted_mont, mult;
-  Dev first;  // a key of h2mi_prover_keygen_table_logup: per distinct value the lowest usable row that holds it (u32)
+  Dev first;  // a table-logUp key: per distinct value the lowest usable row that holds it (u32)
   uint32_t n_unique = 0;
   void alloc(size_t rows) {  // room for `rows` distinct values (h2mi_fr_sort_unique_dev inside a proof fills it)
     sorted = vec(rows);
@@ -488,28 +491,28 @@ struct h2mi_pk_s {
   std::vector<h2mi_expr_op> gate_ops;
   std::vector<uint64_t> gate_constants;
   h2mi_gate_program gate_program = {nullptr, 0, nullptr, 0};
-  // lookups given as a program (h2mi_prover_keygen_exprs): the key's own copy, cut into each lookup's input and table polynomials
+  // lookups given as a program (h2mi_keygen_args.lookups): the key's own copy, cut into each lookup's input and table polynomials
   bool lookup_exprs = false;
   // H2MI_KEYGEN_LOGUP: every program lookup of the key is a logUp argument (multiplicities M and a running sum phi)
   bool logup = false;
   std::vector<h2mi_expr_op> lookup_ops;
   std::vector<uint64_t> lookup_constants;
   ArgumentSlices lookup_slices;
-  // h2mi_prover_keygen_table_logup: logUp over the single-expression lookups of a hard-wired shape (logup && !lookup_exprs).  cs.n_lookups
+  // table logUp: logUp over the single-expression lookups of a hard-wired shape (logup && !lookup_exprs).  cs.n_lookups
   // is then the number of ARGUMENTS and cs.lookups[a] the first input of argument a; the caller's entries live here, argument by
   // argument, and tables[tl_table[a]] is argument a's table — arguments over one fixed column share one
   bool table_logup = false;
   uint32_t tl_sets[H2MI_MAX_LOOKUPS] = {0};
   h2mi_lookup tl_inputs[H2MI_MAX_LOOKUPS][H2MI_MAX_LOGUP_INPUTS];
   uint32_t tl_table[H2MI_MAX_LOOKUPS] = {0};
-  // shuffle arguments (h2mi_prover_keygen_shuffles): the key's own copy, cut into each shuffle's input and shuffle-side polynomials
+  // shuffle arguments (h2mi_keygen_args.shuffles): the key's own copy, cut into each shuffle's input and shuffle-side polynomials
   uint32_t n_shuffles = 0;
   std::vector<h2mi_expr_op> shuffle_ops;
   std::vector<uint64_t> shuffle_constants;
   ArgumentSlices shuffle_slices;
   // the pair counts of both programs as the caller stated them: what h2mi_prover_pk_export writes beside the ops
   uint32_t lookup_pairs[H2MI_MAX_LOOKUPS] = {0}, shuffle_pairs[H2MI_MAX_SHUFFLES] = {0};
-  // advice phases and challenges (h2mi_prover_keygen_phases); every other keygen: one phase, no challenges
+  // advice phases and challenges (h2mi_keygen_args.phases); without them: one phase, no challenges
   h2mi_advice_phases phases;
   uint32_t phase_columns[H2MI_MAX_ADVICE_PHASES] = {0, 0, 0};
   // h2mi_prover_check: the cells the permutation moves, {column, row, image column, image row} sorted by (column, row), on the host
@@ -604,23 +607,25 @@ h2mi_gate_program own_program(const h2mi_gate_program& g, std::vector<h2mi_expr_
   return {ops.data(), g.n_ops, constants.data(), g.n_constants};
 }
 
-// One body, two front ends.  keygen proper (h2mi_prover_keygen*): the caller's fixed cells and its copy constraints, from which the
+// One body, two front ends.  keygen proper (h2mi_prover_keygen): the caller's fixed cells and its copy constraints, from which the
 // permutation is assembled.  Import (h2mi_prover_pk_import): the cells of a key file, handed over in the same h2mi_column_cells, and
 // `stored_moved` — the moved cells a key once assembled, {column, row, image column, image row} ascending — in place of the assembly.
 // From the moved cells on both run the same code: sigma columns, active rows, commitments, transforms, tables.  Import also hands over
 // the blob's `stored_commitments` (n_fixed + n_perm points of 64 bytes): they are compared as soon as the key's own exist, before any
 // transform is issued or any coefficient or coset vector allocated, so a blob that is refused there has cost the columns and two batches
-// of MSMs.
-std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
-                                  const h2mi_advice_phases* phases, uint64_t g_lagrange, const h2mi_column_cells* fixed, const uint32_t* copies,
-                                  size_t n_copies, unsigned flags, const h2mi_shuffle_program* shuffles = nullptr, const h2mi_logup_inputs* inputs = nullptr,
-                                  const std::vector<std::array<uint32_t, 4>>* stored_moved = nullptr, const uint8_t* stored_commitments = nullptr,
-                                  const TableLogup* table_logup = nullptr) {
-  validate(cs, gates, lookups, phases, shuffles, inputs, table_logup != nullptr);
+// of MSMs.  The grouping of a table-logUp record (table_mode: args.inputs checked and resolved by check_table_logup) travels the same way.
+struct KeygenExtra {
+  const std::vector<std::array<uint32_t, 4>>* stored_moved = nullptr;
+  const uint8_t* stored_commitments = nullptr;
+  const TableLogup* table_logup = nullptr;
+};
+std::unique_ptr<h2mi_pk_s> keygen(const h2mi_keygen_args& args, const KeygenExtra& extra = {}) {
+  validate(args);
+  const h2mi_constraint_system& cs = *args.cs;
   std::unique_ptr<h2mi_pk_s> pkp(new h2mi_pk_s(cs));
   h2mi_pk_s& pk = *pkp;
-  if (table_logup) {  // h2mi_prover_keygen_table_logup: from here on the key's lookups are the ARGUMENTS, each named by its first input
-    const TableLogup& g = *table_logup;
+  if (extra.table_logup) {  // from here on the key's lookups are the ARGUMENTS, each named by its first input
+    const TableLogup& g = *extra.table_logup;
     pk.table_logup = pk.logup = true;
     pk.cs.n_lookups = g.n_args;
     for (uint32_t a = 0; a < g.n_args; a++) {
@@ -631,28 +636,28 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
   }
   std::memset(&pk.phases, 0, sizeof(pk.phases));
   pk.phases.n_phases = 1;
-  if (phases) pk.phases = *phases;
+  if (args.phases) pk.phases = *args.phases;
   for (uint32_t j = 0; j < cs.n_advice; j++) pk.phase_columns[pk.phases.advice_phase[j]]++;
-  if (gates) pk.gate_program = own_program(*gates, pk.gate_ops, pk.gate_constants);
-  if (lookups) {
+  if (args.gates) pk.gate_program = own_program(*args.gates, pk.gate_ops, pk.gate_constants);
+  if (args.lookups) {
     pk.lookup_exprs = true;
-    h2mi_lookup_program own = *lookups;
-    std::memcpy(pk.lookup_pairs, lookups->n_pairs, sizeof(pk.lookup_pairs));
-    own.exprs = own_program(lookups->exprs, pk.lookup_ops, pk.lookup_constants);
+    h2mi_lookup_program own = *args.lookups;
+    std::memcpy(pk.lookup_pairs, args.lookups->n_pairs, sizeof(pk.lookup_pairs));
+    own.exprs = own_program(args.lookups->exprs, pk.lookup_ops, pk.lookup_constants);
     // an h2mi_logup_inputs is copied into the slices (their `sets`): the key reads the caller's struct here and never again
-    if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices, pk.phases.n_challenges, inputs)) throw Error(H2MI_EINVAL, "lookup program");
+    if (check_lookup_program(cs, &own, nullptr, &pk.lookup_slices, pk.phases.n_challenges, args.inputs)) throw Error(H2MI_EINVAL, "lookup program");
   }
-  if (shuffles) {
-    pk.n_shuffles = shuffles->n_shuffles;
-    h2mi_shuffle_program own = *shuffles;
-    std::memcpy(pk.shuffle_pairs, shuffles->n_pairs, sizeof(pk.shuffle_pairs));
-    own.exprs = own_program(shuffles->exprs, pk.shuffle_ops, pk.shuffle_constants);
+  if (args.shuffles) {
+    pk.n_shuffles = args.shuffles->n_shuffles;
+    h2mi_shuffle_program own = *args.shuffles;
+    std::memcpy(pk.shuffle_pairs, args.shuffles->n_pairs, sizeof(pk.shuffle_pairs));
+    own.exprs = own_program(args.shuffles->exprs, pk.shuffle_ops, pk.shuffle_constants);
     if (check_shuffle_program(cs, &own, nullptr, &pk.shuffle_slices, pk.phases.n_challenges)) throw Error(H2MI_EINVAL, "shuffle program");
   }
-  pk.vk_only = (flags & H2MI_KEYGEN_VK_ONLY) != 0;
-  pk.by_coset = !pk.vk_only && (flags & H2MI_KEYGEN_BY_COSET) != 0;
-  pk.logup = pk.table_logup || (lookups && (flags & H2MI_KEYGEN_LOGUP) != 0);
-  if (gates) {
+  pk.vk_only = (args.flags & H2MI_KEYGEN_VK_ONLY) != 0;
+  pk.by_coset = !pk.vk_only && (args.flags & H2MI_KEYGEN_BY_COSET) != 0;
+  pk.logup = pk.table_logup || (args.lookups && (args.flags & H2MI_KEYGEN_LOGUP) != 0);
+  if (args.gates) {
     pk.check_gates = pk.gate_program;
   } else {  // a hard-wired shape: its gates as the program the witness check interprets
     uint32_t n_ops = 0, n_constants = 0;
@@ -666,7 +671,7 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
   const uint32_t u = pk.u, m = cs.n_perm;
   {
     uint64_t base_n = 0;
-    check(h2mi_bases_info(g_lagrange, nullptr, nullptr, nullptr, &base_n), "g_lagrange handle");
+    check(h2mi_bases_info(args.g_lagrange_handle, nullptr, nullptr, nullptr, &base_n), "g_lagrange handle");
     if (base_n < n) throw Error(H2MI_ERANGE, "keygen: the Lagrange SRS is shorter than 2^k");
   }
   PatchList pl;
@@ -675,14 +680,14 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
   // the blinding rows, so a cycle through one would not be enforced and the proof would not verify
   for (uint32_t c = 0; c < cs.n_fixed; c++) {
     Dev d = vec(n);
-    fill_column(*d, n, fixed[c], u, pl);
+    fill_column(*d, n, args.fixed[c], u, pl);
     pk.fixed_values.push_back(std::move(d));
   }
   pl.flush();
   // sigma_j[i] = DELTA^(j') omega^(i') for (j', i') = mapping[(j, i)]  (permutation/keygen.rs build_vk / build_pk)
   PermutationAssembly asm_;
-  for (size_t i = 0; i < n_copies; i++) {
-    const uint32_t* c = copies + 4 * i;
+  for (size_t i = 0; i < args.n_copies; i++) {
+    const uint32_t* c = args.copies + 4 * i;
     if (c[0] >= m || c[2] >= m) throw Error(H2MI_EINVAL, "copy constraint on a column without equality enabled");
     if (c[1] >= u || c[3] >= u) throw Error(H2MI_ERANGE, "copy constraint beyond the usable rows (NotEnoughRowsAvailable)");
     asm_.copy(Cell(c[0], c[1]), Cell(c[2], c[3]));
@@ -705,8 +710,8 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
       if (from_row < u) pos.push_back((from_col / pk.chunk) * u + from_row);
       if (!pk.vk_only) moved.push_back({from_col, from_row, to_col, to_row});
     };
-    if (stored_moved) {
-      for (const std::array<uint32_t, 4>& mv : *stored_moved) place(mv[0], mv[1], mv[2], mv[3]);  // the parser has bounded every column and row
+    if (extra.stored_moved) {
+      for (const std::array<uint32_t, 4>& mv : *extra.stored_moved) place(mv[0], mv[1], mv[2], mv[3]);  // the parser has bounded every column and row
     } else {
       asm_.for_each([&](const Cell& from, const Cell& to) {
         if (!(from == to)) place(from.first, from.second, to.first, to.second);
@@ -727,11 +732,11 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     pk.active_rows = vec(pos.size() / 8 + 1);
     if (!pos.empty()) check(h2mi_memcpy_h2d(pk.active_rows->p, pos.data(), pos.size() * 4), "active rows");
   }
-  pk.fixed_commitments = commit_points(g_lagrange, pk.fixed_values, n);
-  pk.permutation_commitments = commit_points(g_lagrange, pk.sigma_values, n);
-  if (stored_commitments) {  // a damaged cell section, or an SRS that is not the one the key was made against
-    const bool same = (cs.n_fixed == 0 || !std::memcmp(pk.fixed_commitments.data(), stored_commitments, 64 * (size_t)cs.n_fixed)) &&
-                      (m == 0 || !std::memcmp(pk.permutation_commitments.data(), stored_commitments + 64 * (size_t)cs.n_fixed, 64 * (size_t)m));
+  pk.fixed_commitments = commit_points(args.g_lagrange_handle, pk.fixed_values, n);
+  pk.permutation_commitments = commit_points(args.g_lagrange_handle, pk.sigma_values, n);
+  if (extra.stored_commitments) {  // a damaged cell section, or an SRS that is not the one the key was made against
+    const bool same = (cs.n_fixed == 0 || !std::memcmp(pk.fixed_commitments.data(), extra.stored_commitments, 64 * (size_t)cs.n_fixed)) &&
+                      (m == 0 || !std::memcmp(pk.permutation_commitments.data(), extra.stored_commitments + 64 * (size_t)cs.n_fixed, 64 * (size_t)m));
     if (!same) {
       h2mi_sync();  // nothing queued may still read the vectors released with the key
       throw Error(H2MI_EINVAL, "key file: the commitments recomputed from its cells are not the stored ones");
@@ -777,13 +782,13 @@ std::unique_ptr<h2mi_pk_s> keygen(const h2mi_constraint_system& cs, const h2mi_g
     check(h2mi_sync(), "sync");
   }
   // a lookup given as expressions has no keygen-time table: theta, or an advice column in it, is known only inside a proof
-  for (uint32_t l = 0; !pk.lookup_exprs && !pk.table_logup && l < cs.n_lookups; l++) build_table(pk, pk.tables[l], fixed[cs.lookups[l].table_fixed]);
+  for (uint32_t l = 0; !pk.lookup_exprs && !pk.table_logup && l < cs.n_lookups; l++) build_table(pk, pk.tables[l], args.fixed[cs.lookups[l].table_fixed]);
   // a table-logUp key: one sorted table (with its first rows) per distinct fixed column, whatever the number of arguments over it
   for (uint32_t a = 0; pk.table_logup && a < pk.cs.n_lookups; a++) {
     pk.tl_table[a] = a;
     for (uint32_t b = 0; b < a; b++)
       if (pk.cs.lookups[b].table_fixed == pk.cs.lookups[a].table_fixed) pk.tl_table[a] = std::min(pk.tl_table[a], pk.tl_table[b]);
-    if (pk.tl_table[a] == a) build_table(pk, pk.tables[a], fixed[pk.cs.lookups[a].table_fixed], /*with_first=*/true);
+    if (pk.tl_table[a] == a) build_table(pk, pk.tables[a], args.fixed[pk.cs.lookups[a].table_fixed], /*with_first=*/true);
   }
   return pkp;
 }
@@ -1164,7 +1169,7 @@ std::unique_ptr<h2mi_prover_s> create_prover(h2mi_pk_s* pk, uint64_t g, uint64_t
   }
   for (uint32_t l = 0; l < cs.n_lookups; l++) {
     if (pk->lookup_exprs) {
-      const size_t sets = pk->lookup_slices.sets[l];  // a logUp lookup's input sets, contiguous: one but for a key of h2mi_prover_keygen_logup
+      const size_t sets = pk->lookup_slices.sets[l];  // a logUp lookup's input sets, contiguous: one unless the key was made with an h2mi_logup_inputs
       p.lk[l].c = {vec(sets * n), vec(n), vec(sets * ext), vec(ext)};
       p.lk[l].sorted.alloc(pk->u);
     } else if (cs.lookups[l].selector_fixed >= 0) {
@@ -2292,70 +2297,46 @@ int pick(const Dev& d, uint32_t index, void** d_ptr, size_t* count) {
   return H2MI_OK;
 }
 
-// What the five keygen entries share.  `required`: the pointers the entry refuses to do without (besides cs and pk_out); `allowed`:
-// its flags.  An h2mi_logup_inputs comes through h2mi_prover_keygen_logup alone.
-int keygen_entry(const h2mi_constraint_system* cs, std::initializer_list<const void*> required, unsigned allowed, const h2mi_gate_program* gates,
-                 const h2mi_lookup_program* lookups, const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles, const h2mi_logup_inputs* inputs,
-                 uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  if (!cs || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~allowed) || ((flags & H2MI_KEYGEN_LOGUP) && !lookups)) return H2MI_EINVAL;
-  for (const void* ptr : required)
-    if (!ptr) return H2MI_EINVAL;
-  *pk_out = nullptr;
-  if (inputs && !lookups) return H2MI_EINVAL;
-  for (uint32_t l = 0; inputs && l < lookups->n_lookups && l < H2MI_MAX_LOOKUPS; l++)  // several sets are a logUp key's
-    if (inputs->n_inputs[l] != 1 && !(flags & H2MI_KEYGEN_LOGUP)) return H2MI_EINVAL;
-  if (const int rc = h2mi_column_cells_check(fixed, cs->n_fixed, H2MI_CELLS_FOR_FIXED)) return rc;
-  if (h2mi_device_count() == 0) return H2MI_ENODEV;  // no CPU fallback: the prover exists on a GPU or not at all
-  return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, gates, lookups, phases, g_lagrange_handle, fixed, copies, n_copies, flags, shuffles, inputs);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_live_pks.insert(pk.get());
-    *pk_out = pk.release();
-  });
-}
-
 // ---- proving-key files (h2mi_keyfile.hpp holds the format; DESIGN.md 3 describes it) ---------------------------------------------------
-// a parsed blob's programs in the structs the keygen entries take; the pointers are NULL where the key has none
-struct BlobPrograms {
-  h2mi_gate_program gates_;
-  h2mi_lookup_program lookups_;
-  h2mi_shuffle_program shuffles_;
-  h2mi_logup_inputs inputs_;
-  const h2mi_gate_program* gates = nullptr;
-  const h2mi_lookup_program* lookups = nullptr;
-  const h2mi_shuffle_program* shuffles = nullptr;
-  const h2mi_logup_inputs* inputs = nullptr;
-  const h2mi_advice_phases* phases = nullptr;
-  explicit BlobPrograms(const keyfile::Blob& b) {
+// a parsed blob as the record keygen takes; the program pointers are NULL where the key has none
+struct BlobArgs {
+  h2mi_gate_program gates;
+  h2mi_lookup_program lookups;
+  h2mi_shuffle_program shuffles;
+  h2mi_logup_inputs inputs;
+  h2mi_keygen_args args;
+  explicit BlobArgs(const keyfile::Blob& b) {
+    std::memset(&args, 0, sizeof(args));
+    args.cs = &b.cs;
+    args.flags = b.logup ? H2MI_KEYGEN_LOGUP : 0u;
     if (b.has_gates) {
-      gates_ = b.gates.view();
-      gates = &gates_;
+      gates = b.gates.view();
+      args.gates = &gates;
     }
     if (b.has_lookups) {
-      std::memset(&lookups_, 0, sizeof(lookups_));
-      lookups_.n_lookups = b.n_lookups;
-      std::memcpy(lookups_.n_pairs, b.lookup_pairs, sizeof(lookups_.n_pairs));
-      lookups_.exprs = b.lookup_exprs.view();
-      std::memcpy(inputs_.n_inputs, b.lookup_inputs, sizeof(inputs_.n_inputs));
-      lookups = &lookups_;
-      inputs = &inputs_;
+      std::memset(&lookups, 0, sizeof(lookups));
+      lookups.n_lookups = b.n_lookups;
+      std::memcpy(lookups.n_pairs, b.lookup_pairs, sizeof(lookups.n_pairs));
+      lookups.exprs = b.lookup_exprs.view();
+      std::memcpy(inputs.n_inputs, b.lookup_inputs, sizeof(inputs.n_inputs));
+      args.lookups = &lookups;
+      args.inputs = &inputs;
     }
     if (b.has_shuffles) {
-      std::memset(&shuffles_, 0, sizeof(shuffles_));
-      shuffles_.n_shuffles = b.n_shuffles;
-      std::memcpy(shuffles_.n_pairs, b.shuffle_pairs, sizeof(shuffles_.n_pairs));
-      shuffles_.exprs = b.shuffle_exprs.view();
-      shuffles = &shuffles_;
+      std::memset(&shuffles, 0, sizeof(shuffles));
+      shuffles.n_shuffles = b.n_shuffles;
+      std::memcpy(shuffles.n_pairs, b.shuffle_pairs, sizeof(shuffles.n_pairs));
+      shuffles.exprs = b.shuffle_exprs.view();
+      args.shuffles = &shuffles;
     }
-    if (b.has_phases) phases = &b.phases;
+    if (b.has_phases) args.phases = &b.phases;
   }
 };
 
 // everything import checks before it touches the device: the format's own rules, then the constraint system's and its programs'
 void check_blob(const uint8_t* blob, size_t len, keyfile::Blob& b) {
   if (keyfile::parse(blob, len, b)) throw Error(H2MI_EINVAL, "key file: not a well-formed proving-key blob");
-  const BlobPrograms p(b);
-  validate(b.cs, p.gates, p.lookups, p.phases, p.shuffles, p.inputs);
+  validate(BlobArgs(b).args);
 }
 
 void* arena_alloc(void* ctx, size_t bytes) {
@@ -2436,7 +2417,7 @@ std::unique_ptr<h2mi_pk_s> import_key(const uint8_t* blob, size_t len, uint64_t 
   keyfile::Blob b;
   check_blob(blob, len, b);
   if (h2mi_device_count() == 0) throw Error(H2MI_ENODEV, "no device");
-  const BlobPrograms p(b);
+  BlobArgs p(b);
   const h2mi_constraint_system& cs = b.cs;
   // the blob's own cells as the caller's would arrive: dense runs without a row list, sparse ones with theirs, as 64-bit integers or
   // as canonical words — fill_column / k_cells_scatter from here on, and build_table reads them on the host
@@ -2455,8 +2436,10 @@ std::unique_ptr<h2mi_pk_s> import_key(const uint8_t* blob, size_t len, uint64_t 
   std::vector<std::array<uint32_t, 4>> moved(b.n_moved);
   if (b.n_moved) std::memcpy(moved.data(), blob + b.moved_at, 16 * b.n_moved);
   // keygen compares the commitments it recomputes with the stored ones and throws H2MI_EINVAL where they differ
-  return keygen(cs, p.gates, p.lookups, p.phases, g_lagrange, fixed.data(), nullptr, 0, flags | (b.logup ? H2MI_KEYGEN_LOGUP : 0u), p.shuffles, p.inputs, &moved,
-                blob + b.commitments_at);
+  p.args.g_lagrange_handle = g_lagrange;
+  p.args.fixed = fixed.data();
+  p.args.flags |= flags;
+  return keygen(p.args, {&moved, blob + b.commitments_at, nullptr});
 }
 
 }  // namespace
@@ -2510,9 +2493,30 @@ int h2mi_prover_pk_import(const void* buf, size_t len, uint64_t g_lagrange_handl
   });
 }
 
-int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies,
-                       unsigned flags, h2mi_pk_t* pk_out) {
-  return keygen_entry(cs, {}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_BY_COSET, nullptr, nullptr, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
+int h2mi_prover_keygen(const h2mi_keygen_args* args, h2mi_pk_t* pk_out) {
+  if (!args || !pk_out || !args->cs || (args->cs->n_fixed && !args->fixed) || (args->n_copies && !args->copies)) return H2MI_EINVAL;
+  const h2mi_keygen_args& a = *args;
+  if (a.flags & ~(H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP | H2MI_KEYGEN_BY_COSET)) return H2MI_EINVAL;
+  *pk_out = nullptr;
+  TableLogup groups;
+  KeygenExtra extra;
+  if (table_mode(a)) {
+    if ((a.flags & H2MI_KEYGEN_BY_COSET) || a.gates || a.lookups || a.phases || a.shuffles) return H2MI_EINVAL;
+    if (const int rc = check_table_logup(*a.cs, a.inputs, nullptr, &groups)) return rc;  // every rule of the grouping, before any device work
+    extra.table_logup = &groups;
+  } else {
+    if (((a.flags & H2MI_KEYGEN_LOGUP) || a.inputs) && !a.lookups) return H2MI_EINVAL;
+    for (uint32_t l = 0; a.inputs && l < a.lookups->n_lookups && l < H2MI_MAX_LOOKUPS; l++)  // several sets are a logUp key's
+      if (a.inputs->n_inputs[l] != 1 && !(a.flags & H2MI_KEYGEN_LOGUP)) return H2MI_EINVAL;
+  }
+  if (const int rc = h2mi_column_cells_check(a.fixed, a.cs->n_fixed, H2MI_CELLS_FOR_FIXED)) return rc;
+  if (h2mi_device_count() == 0) return H2MI_ENODEV;  // no CPU fallback: the prover exists on a GPU or not at all
+  return guarded([&] {
+    std::unique_ptr<h2mi_pk_s> pk = keygen(a, extra);
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    g_live_pks.insert(pk.get());
+    *pk_out = pk.release();
+  });
 }
 
 int h2mi_column_cells_check(const h2mi_column_cells* cells, uint32_t n_columns, unsigned where) {
@@ -2592,34 +2596,15 @@ int h2mi_shape_gate_program(const h2mi_constraint_system* cs, h2mi_expr_op* ops,
   return H2MI_OK;
 }
 
-int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed,
-                             const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_BY_COSET, gates, nullptr, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
-}
-
 int h2mi_lookup_program_check(const h2mi_constraint_system* cs, const h2mi_lookup_program* lookups, uint32_t* degree_out) {
   if (!cs || !lookups) return H2MI_EINVAL;
   return check_lookup_program(*cs, lookups, degree_out, nullptr);
-}
-
-int h2mi_prover_keygen_exprs(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups, uint64_t g_lagrange_handle,
-                             const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  if (!lookups) return h2mi_prover_keygen_gates(cs, gates, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
-  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP | H2MI_KEYGEN_BY_COSET, gates, lookups, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies,
-                      flags, pk_out);
 }
 
 int h2mi_advice_phases_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                              const h2mi_advice_phases* phases) {
   if (!cs || !gates || !phases) return H2MI_EINVAL;
   return check_phases(*cs, gates, lookups, *phases);
-}
-
-int h2mi_prover_keygen_phases(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
-                              const h2mi_advice_phases* phases, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
-                              size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  return keygen_entry(cs, {gates, phases}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP | H2MI_KEYGEN_BY_COSET, gates, lookups, phases, nullptr, nullptr, g_lagrange_handle, fixed, copies,
-                      n_copies, flags, pk_out);
 }
 
 int h2mi_shuffle_program_check(const h2mi_constraint_system* cs, const h2mi_shuffle_program* shuffles, uint32_t* degree_out) {
@@ -2634,12 +2619,6 @@ int h2mi_shuffle_phases_check(const h2mi_constraint_system* cs, const h2mi_shuff
   return check_shuffle_program(*cs, shuffles, degree_out, nullptr, phases ? phases->n_challenges : 0);
 }
 
-int h2mi_prover_keygen_shuffles(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
-                                const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles, uint64_t g_lagrange_handle,
-                                const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  return h2mi_prover_keygen_logup(cs, gates, lookups, nullptr, phases, shuffles, g_lagrange_handle, fixed, copies, n_copies, flags, pk_out);
-}
-
 int h2mi_logup_inputs_check(const h2mi_constraint_system* cs, const h2mi_lookup_program* lookups, const h2mi_logup_inputs* inputs,
                             const h2mi_advice_phases* phases, uint32_t* degree_out) {
   if (!cs || !lookups) return H2MI_EINVAL;
@@ -2647,34 +2626,9 @@ int h2mi_logup_inputs_check(const h2mi_constraint_system* cs, const h2mi_lookup_
   return check_lookup_program(*cs, lookups, degree_out, nullptr, phases ? phases->n_challenges : 0, inputs);
 }
 
-int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
-                             const h2mi_logup_inputs* inputs, const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles,
-                             uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags,
-                             h2mi_pk_t* pk_out) {
-  return keygen_entry(cs, {gates}, H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP | H2MI_KEYGEN_BY_COSET, gates, lookups, phases, shuffles, inputs, g_lagrange_handle, fixed, copies,
-                      n_copies, flags, pk_out);
-}
-
 int h2mi_table_logup_check(const h2mi_constraint_system* cs, const h2mi_logup_inputs* sets, uint32_t* degree_out) {
   if (!cs) return H2MI_EINVAL;
   return check_table_logup(*cs, sets, degree_out, nullptr);
-}
-
-int h2mi_prover_keygen_table_logup(const h2mi_constraint_system* cs, const h2mi_logup_inputs* sets, uint64_t g_lagrange_handle,
-                                   const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out) {
-  if (!cs || !pk_out || (cs->n_fixed && !fixed) || (n_copies && !copies) || (flags & ~(H2MI_KEYGEN_VK_ONLY | H2MI_KEYGEN_LOGUP))) return H2MI_EINVAL;
-  *pk_out = nullptr;
-  TableLogup groups;
-  if (const int rc = check_table_logup(*cs, sets, nullptr, &groups)) return rc;  // every rule of the grouping, before any device work
-  if (const int rc = h2mi_column_cells_check(fixed, cs->n_fixed, H2MI_CELLS_FOR_FIXED)) return rc;
-  if (h2mi_device_count() == 0) return H2MI_ENODEV;
-  return guarded([&] {
-    std::unique_ptr<h2mi_pk_s> pk = keygen(*cs, nullptr, nullptr, nullptr, g_lagrange_handle, fixed, copies, n_copies, flags & H2MI_KEYGEN_VK_ONLY, nullptr,
-                                           nullptr, nullptr, nullptr, &groups);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_live_pks.insert(pk.get());
-    *pk_out = pk.release();
-  });
 }
 
 int h2mi_prover_pk_release(h2mi_pk_t pk) {

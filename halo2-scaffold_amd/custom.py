@@ -19,21 +19,21 @@ halo2's bookkeeping, restated from memory [RECALL halo2_proofs plonk/circuit.rs]
     and does not care.
 Lookups: `meta.lookup(name, |meta| vec![(input, table), ..])` and `lookup_any` take any expressions on both sides (the crate's `lookup`
 wants its table side to be TableColumn queries; here both spell the same argument).  `lookup_program()` compiles them to an
-h2mi_lookup_program and `Keys` hands it to h2mi_prover_keygen_exprs: each side is compressed with theta and the table sorted inside
+h2mi_lookup_program and `Keys` hands it to keygen beside the gates: each side is compressed with theta and the table sorted inside
 every proof (csrc/h2mi_lookup.hip h2mi_fr_sort_unique_dev).  The single-expression lookups against a fixed table, sorted once at
 keygen, stay the fast path of range checks and are reached through flex.py.
 Phases and challenges [RECALL halo2_proofs v2023_02_02 plonk/circuit.rs, plonk/prover.rs]: `advice_column_in(phase)` (phases 0 .. 2; a
 later phase needs a column in the one before), `challenge_usable_after(phase)` (needs a column in that phase; numbered in creation
-order), `query_challenge` -> an Expression of degree 0 that any gate and either side of any lookup may hold.  `Keys` then goes through
-h2mi_prover_keygen_phases, and `create_proof` takes synthesize(challenges) -> Assignment in place of an Assignment: it is called once
+order), `query_challenge` -> an Expression of degree 0 that any gate and either side of any lookup may hold.  `Keys` then passes an
+h2mi_advice_phases, and `create_proof` takes synthesize(challenges) -> Assignment in place of an Assignment: it is called once
 per advice phase with the challenges squeezed so far, and only that phase's columns are taken from what it returns.
 Shuffles [RECALL halo2_proofs, PSE line, plonk/shuffle.rs — restated from memory and pinned to DESIGN.md 4.5, not to the crate]:
 `meta.shuffle(name, |meta| vec![(input, shuffle), ..])` states that the two tuples take the same multiset of values over the usable
 rows; required degree 2 + max(1, input degrees, shuffle degrees).  `shuffle_program()` compiles them to an h2mi_shuffle_program and
-`Keys` goes through h2mi_prover_keygen_shuffles — only for a circuit that has shuffles: every other circuit takes the calls it took.
+`Keys` passes it to keygen — only a circuit that has shuffles passes one.
 Merged lookups [RECALL the `mv-lookup` line's merging of lookups over one table — restated from memory and pinned to DESIGN.md 4.5 and
 tests/logup_sets_cases.py]: `merge_lookups(max_degree=None)` is an explicit opt-in that turns the lookups sharing a table into ONE logUp
-argument of several input sets (h2mi_logup_inputs); `Keys(..., logup=True)` then goes through h2mi_prover_keygen_logup.
+argument of several input sets (h2mi_logup_inputs); `Keys(..., logup=True)` then passes the counts to keygen.
 Assigned cells [RECALL halo2_proofs v2023_02_02 plonk/assigned.rs]: `assign_advice` / `assign_fixed` take `Rational(numerator,
 denominator)` beside integers — `value.invert()` deferred to the prover, as the reference's is_zero.rs computes value_inv.  Such a
 column crosses to the library unresolved (engine.pack_cells, H2MI_CELLS_RATIONAL) and is inverted there; `mock` evaluates it.
@@ -578,15 +578,15 @@ def mock(asg: Assignment, k: int, challenges=()) -> None:
 
 
 class Keys:
-    """keygen_vk + keygen_pk through h2mi_prover_keygen_gates (h2mi_prover_keygen_exprs when the circuit has lookups,
-    h2mi_prover_keygen_phases when it has an advice column in a later phase or a challenge): the fixed cells of a run of synthesize() (selector columns included), the
+    """keygen_vk + keygen_pk through h2mi_prover_keygen, with the lookup and shuffle programs, the logUp input sets and the advice phases
+    the circuit has: the fixed cells of a run of synthesize() (selector columns included), the
     copy constraints with their columns renumbered into the permutation argument's order, the gates as a program the key copies.
     Same attributes as flex.FlexKeys.
     logup=True [the `mv-lookup` feature of the Scroll and ezkl lines of halo2_proofs, after Haboeck — restated from memory and pinned to
     DESIGN.md 4.5 and tests/logup_cases.py, not to a crate]: every lookup of the key is proven with a multiplicity column and a running
     sum (H2MI_KEYGEN_LOGUP) in place of the permuted columns and the grand product; needs a circuit with lookups.  `create_proof` and
     `prove_many` follow the key; `mock` and `check` test membership and do not depend on it.  A constraint system after
-    merge_lookups() goes through h2mi_prover_keygen_logup and needs logup=True.
+    merge_lookups() passes its input-set counts and needs logup=True.
     by_coset=True (H2MI_KEYGEN_BY_COSET): the key and its provers keep no column in extended-coset form and the quotient is evaluated
     one coset at a time — the same proof bytes from a fraction of the device memory, at the price of transforms redone
     in every proof; `fixed_cosets` / `sigma_cosets` are then refused by the library."""

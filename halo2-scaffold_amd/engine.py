@@ -163,7 +163,7 @@ class LogupInputs(C.Structure):
 
     def check_table(self, cs: "ConstraintSystem") -> int:
         """h2mi_table_logup_check: these counts as the grouping of a hard-wired shape's cs.lookups[] into logUp arguments over their fixed
-        tables -> the largest required degree; H2miError(-1) for what h2mi_prover_keygen_table_logup would refuse"""
+        tables -> the largest required degree; H2miError(-1) for what keygen with H2MI_KEYGEN_LOGUP would refuse"""
         return table_logup_check(cs, self)
 
 
@@ -609,46 +609,34 @@ class _Views:
         return (self[i] for i in range(self._count))
 
 
+class KeygenArgs(C.Structure):
+    """h2mi_keygen_args: the one record h2mi_prover_keygen takes; a pointer left NULL means what include/h2mi_prover.h says beside the field"""
+    _fields_ = [("cs", C.POINTER(ConstraintSystem)), ("gates", C.POINTER(GateProgram)), ("lookups", C.POINTER(LookupProgram)),
+                ("inputs", C.POINTER(LogupInputs)), ("phases", C.POINTER(AdvicePhases)), ("shuffles", C.POINTER(ShuffleProgram)),
+                ("g_lagrange_handle", C.c_uint64), ("fixed", C.c_void_p), ("copies", C.c_void_p), ("n_copies", C.c_size_t), ("flags", C.c_uint)]
+
+
 class Keys:
-    """h2mi_prover_keygen (h2mi_prover_keygen_gates when `gates` is given, h2mi_prover_keygen_exprs when `lookups` is too): keygen_vk + keygen_pk for a constraint system given as data.  fixed: one {row: value} dict (or dense
-    list, or an IntCells for a column of small integers such as a selector or a lookup table) per fixed column as synthesize() assigns them; copies: [(left column, left row, right column, right row)] per
-    constrain_equal in call order, columns as indices into the permutation argument.  `params` is the WHOLE SRS."""
+    """h2mi_prover_keygen: keygen_vk + keygen_pk for a constraint system given as data, with what the circuit has beside it (gates, lookups,
+    phases, shuffles, logUp input sets) as optional programs.  fixed: one {row: value} dict (or dense list, or an IntCells for a column of
+    small integers such as a selector or a lookup table) per fixed column as synthesize() assigns them; copies: [(left column, left row,
+    right column, right row)] per constrain_equal in call order, columns as indices into the permutation argument.  `params` is the WHOLE SRS."""
 
     def __init__(self, cs: ConstraintSystem, params, fixed, copies, vk_only: bool = False, gates: GateProgram = None,
                  lookups: LookupProgram = None, phases: AdvicePhases = None, shuffles: ShuffleProgram = None, logup: bool = False,
                  logup_inputs: "LogupInputs" = None, by_coset: bool = False):
         self.cs = cs
         self.by_coset = bool(by_coset)  # H2MI_KEYGEN_BY_COSET: same proofs, a device footprint without 2^extended_k columns, slower
-        self.logup = bool(logup)  # H2MI_KEYGEN_LOGUP; the library refuses it without a lookup program
+        self.logup = bool(logup)  # H2MI_KEYGEN_LOGUP: a lookup program's lookups, or a hard-wired shape's over their keygen-sorted tables
         self.n_shuffles = shuffles.n_shuffles if shuffles is not None else 0
         cells, keep = pack_cells(fixed)
         cp = np.ascontiguousarray(np.array(copies, dtype=np.uint32).reshape(-1, 4))
         h = C.c_void_p()
         flags = (KEYGEN_VK_ONLY if vk_only else 0) | (KEYGEN_LOGUP if logup else 0) | (KEYGEN_BY_COSET if by_coset else 0)
-        opt = lambda s: C.byref(s) if s is not None else None
-        if gates is None and logup:  # a hard-wired shape's single-expression lookups as logUp arguments over their keygen-sorted tables
-            if by_coset:
-                raise ValueError("a table-logUp key has no by-coset form (h2mi_prover_keygen_table_logup refuses H2MI_KEYGEN_BY_COSET)")
-            check(lib.h2mi_prover_keygen_table_logup(C.byref(cs), opt(logup_inputs), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags,
-                                                     C.byref(h)), "keygen")
-        elif logup_inputs is not None:  # several input sets per logUp lookup: h2mi_prover_keygen_shuffles with the counts beside it
-            check(lib.h2mi_prover_keygen_logup(C.byref(cs), C.byref(gates), opt(lookups), C.byref(logup_inputs), opt(phases), opt(shuffles),
-                                               params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
-        elif shuffles is not None:  # shuffle arguments: h2mi_prover_keygen_phases with the shuffles beside it; every other circuit takes the calls below
-            check(lib.h2mi_prover_keygen_shuffles(C.byref(cs), C.byref(gates), C.byref(lookups) if lookups is not None else None,
-                                                  C.byref(phases) if phases is not None else None, C.byref(shuffles), params.g_lagrange_handle, cells,
-                                                  cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
-        elif phases is not None:  # advice columns of a later phase, challenges: h2mi_prover_keygen_exprs with the phases beside it
-            check(lib.h2mi_prover_keygen_phases(C.byref(cs), C.byref(gates), C.byref(lookups) if lookups is not None else None, C.byref(phases),
-                                                params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
-        elif gates is None:
-            check(lib.h2mi_prover_keygen(C.byref(cs), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)), "keygen")
-        elif lookups is not None:  # the lookups as expressions too
-            check(lib.h2mi_prover_keygen_exprs(C.byref(cs), C.byref(gates), C.byref(lookups), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp),
-                                               flags, C.byref(h)), "keygen")
-        else:  # GATES_EXPRESSIONS: the gates travel beside the struct; the key copies them
-            check(lib.h2mi_prover_keygen_gates(C.byref(cs), C.byref(gates), params.g_lagrange_handle, cells, cp.ctypes.data, len(cp), flags, C.byref(h)),
-                  "keygen")
+        opt = lambda s: C.pointer(s) if s is not None else None
+        args = KeygenArgs(C.pointer(cs), opt(gates), opt(lookups), opt(logup_inputs), opt(phases), opt(shuffles), params.g_lagrange_handle,
+                          C.cast(cells, C.c_void_p), cp.ctypes.data, len(cp), flags)
+        check(lib.h2mi_prover_keygen(C.byref(args), C.byref(h)), "keygen")
         del keep
         self.handle = h.value
         self.phases = phases

@@ -135,7 +135,7 @@ class FlexGateCS:
         self.chunk = self.degree - 2
 
     def use_logup(self, lookup_sets=None):
-        """Opt in to logUp over the fixed table (h2mi_prover_keygen_table_logup; FlexKeys(..., logup=True) calls this): the lookup-advice
+        """Opt in to logUp over the fixed table (H2MI_KEYGEN_LOGUP on this shape; FlexKeys(..., logup=True) calls this): the lookup-advice
         columns — or the one q_lookup * a input — become logUp arguments, in column order.  lookup_sets None: one argument per column;
         an integer K: runs of at most K columns per argument; a list: the runs themselves.  The degree follows 2 + sum of the inputs'
         degrees + 1 per argument: q_lookup * a keeps 5, K lookup-advice columns give 3 + K — which moves the
@@ -576,7 +576,7 @@ class FlexKeys:
     def __init__(self, params: ParamsKZG, cs: FlexGateCS, asg: Assignment, by_coset: bool = False, logup: bool = False, lookup_sets=None):
         self.cs = cs
         self.by_coset = bool(by_coset)
-        # logup=True (h2mi_prover_keygen_table_logup): the lookups are proven with multiplicities and a running sum against the key's sorted
+        # logup=True (H2MI_KEYGEN_LOGUP on a hard-wired shape): the lookups are proven with multiplicities and a running sum against the key's sorted
         # table, lookup_sets columns per argument (FlexGateCS.use_logup, which also moves cs.degree); no by-coset form, no key file
         self.logup = bool(logup)
         if lookup_sets is not None and not logup:

@@ -104,7 +104,7 @@ struct FlexGateCS {
     degree = Lc ? 4 : 3;
     chunk = degree - 2;
   }
-  // Opt in to logUp over the fixed table (h2mi_prover_keygen_table_logup; flex::keygen with logup = true calls this): the lookup-advice
+  // Opt in to logUp over the fixed table (H2MI_KEYGEN_LOGUP on this shape; flex::keygen with logup = true calls this): the lookup-advice
   // columns — or the one q_lookup * a input — become logUp arguments in column order.  lookup_sets empty: one argument per column; one
   // element K: runs of at most K columns; several: the runs themselves.  The degree follows 2 + sum of the inputs' degrees + 1 per
   // argument (q_lookup * a keeps 5, K lookup-advice columns give 3 + K), and the permutation sets and h pieces with it
@@ -661,17 +661,7 @@ inline std::unique_ptr<FlexKeys> keygen(const poly::kzg::ParamsKZG& params, cons
   const h2mi_constraint_system abi = keys->cs.abi(params.k());
   h2mi_logup_inputs sets;
   for (uint32_t l = 0; l < H2MI_MAX_LOOKUPS; l++) sets.n_inputs[l] = l < keys->cs.logup_runs.size() ? keys->cs.logup_runs[l] : 1u;
-  std::vector<h2mi_column_cells> fixed;
-  for (const plonk::ColumnCells& c : in.fixed) fixed.push_back(c.view());
-  h2mi::check(h2mi_prover_keygen_table_logup(&abi, &sets, params.g_lagrange_handle(), fixed.data(), in.copies.data(), in.copies.size() / 4, flags, &keys->pk.h),
-              "keygen_table_logup");
-  plonk::VerifyingKey& vk = keys->vk;
-  vk.k = abi.k;
-  vk.cs_degree = abi.degree;
-  vk.fixed_commitments.resize(abi.n_fixed);
-  vk.permutation_commitments.resize(abi.n_perm);
-  h2mi::check(h2mi_prover_vk_commitments(keys->pk.h, (uint64_t*)vk.fixed_commitments.data(), (uint64_t*)vk.permutation_commitments.data()), "vk commitments");
-  vk.compute_transcript_repr();
+  plonk::run_keygen(abi, params, in, flags | H2MI_KEYGEN_LOGUP, keys->pk, keys->vk, &sets);
   return keys;
 }
 

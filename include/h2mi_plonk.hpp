@@ -145,11 +145,20 @@ struct PkHandle {  // RAII over h2mi_pk_t
     if (h) h2mi_prover_pk_release(h);
   }
 };
+// a hard-wired shape: no program beside cs; logup_sets goes with H2MI_KEYGEN_LOGUP in flags (the table logUp's grouping)
 inline void run_keygen(const h2mi_constraint_system& cs, const poly::kzg::ParamsKZG& params, const KeygenInput& in, unsigned flags, PkHandle& pk,
-                       VerifyingKey& vk) {
+                       VerifyingKey& vk, const h2mi_logup_inputs* logup_sets = nullptr) {
   std::vector<h2mi_column_cells> fixed;
   for (const ColumnCells& c : in.fixed) fixed.push_back(c.view());
-  check(h2mi_prover_keygen(&cs, params.g_lagrange_handle(), fixed.data(), in.copies.data(), in.copies.size() / 4, flags, &pk.h), "keygen");
+  h2mi_keygen_args args = {};
+  args.cs = &cs;
+  args.inputs = logup_sets;
+  args.g_lagrange_handle = params.g_lagrange_handle();
+  args.fixed = fixed.data();
+  args.copies = in.copies.data();
+  args.n_copies = in.copies.size() / 4;
+  args.flags = flags;
+  check(h2mi_prover_keygen(&args, &pk.h), "keygen");
   vk.k = cs.k;
   vk.cs_degree = cs.degree;
   vk.fixed_commitments.resize(cs.n_fixed);

@@ -38,20 +38,20 @@
  *                              column, up to H2MI_MAX_PERM (64) equality-enabled columns: every column count
  *                              `builder.config(k, Some(minimum_rows))` takes for a circuit that fills a few dozen columns
  *   H2MI_GATES_EXPRESSIONS     any `meta.create_gate(...)` (src/circuits/is_zero.rs, or.rs; the StandardPlonk and vertical gates too):
- *                              the gate polynomials as a postfix program beside the struct (h2mi_gate_program, h2mi.h; keygen through
- *                              h2mi_prover_keygen_gates) which ONE kernel interprets on the extended coset — any query of an advice,
+ *                              the gate polynomials as a postfix program beside the struct (h2mi_gate_program, h2mi.h: the `gates`
+ *                              of h2mi_keygen_args) which ONE kernel interprets on the extended coset — any query of an advice,
  *                              fixed or instance column at any rotation, constants, + - *, degree up to 9 (permutation chunks up to
  *                              7); permutation and column limits as for FLEX_VERTICAL, but up to H2MI_MAX_INSTANCE (h2mi.h: 8)
  *                              instance columns, any of them in the permutation argument, in gates and on either side of a lookup
  *                              or shuffle (public inputs per column: h2mi_prover_instances).  Its lookups are either the
  *                              single-expression ones of FLEX_VERTICAL (cs->lookups[], a fixed table sorted once at keygen: the fast
  *                              path of range checks) or DATA as well — any `meta.lookup` / `meta.lookup_any`: per lookup a list of
- *                              (input expression, table expression) pairs in the same postfix form (h2mi_lookup_program; keygen
- *                              through h2mi_prover_keygen_exprs), compressed with theta and sorted inside each proof.  Advice columns
- *                              of a later phase and challenges (h2mi_advice_phases; keygen through h2mi_prover_keygen_phases): the
+ *                              (input expression, table expression) pairs in the same postfix form (h2mi_lookup_program: the record's
+ *                              `lookups`), compressed with theta and sorted inside each proof.  Advice columns
+ *                              of a later phase and challenges (h2mi_advice_phases: the record's `phases`): the
  *                              advice is then committed phase by phase (h2mi_prover_advice_phase) with the caller squeezing the
  *                              challenges in between, and gates and lookups may read them.  Shuffle arguments (`meta.shuffle` of
- *                              the PSE line of halo2_proofs, h2mi_shuffle_program; keygen through h2mi_prover_keygen_shuffles): per
+ *                              the PSE line of halo2_proofs, h2mi_shuffle_program: the record's `shuffles`): per
  *                              shuffle a list of (input expression, shuffle expression) pairs whose tuples must be the same multiset
  *                              over the usable rows; one grand product each, committed behind the lookups' products
  * Every function returns H2MI_OK or a negative H2MI_E* code (h2mi.h); no exception crosses the boundary.  Field elements
@@ -125,7 +125,7 @@ typedef struct {
  * per cell; the cell's value is numerator * denominator^-1, or 0 where the denominator is 0 (whatever the numerator).  Trivial(x)
  * travels as (x, 1), Zero as (0, 1) or as no cell at all.  With H2MI_CELLS_CANONICAL both halves are canonical integers below r (a half
  * that is not: H2MI_EINVAL, as for plain cells).  rows means what it means without the flag.  Accepted wherever fixed or advice cells
- * enter (every h2mi_prover_keygen*, h2mi_prover_advice, h2mi_prover_advice_phase, hence batches); h2mi_prover_instances refuses it
+ * enter (h2mi_prover_keygen, h2mi_prover_advice, h2mi_prover_advice_phase, hence batches); h2mi_prover_instances refuses it
  * (H2MI_EINVAL): public inputs are field elements.  Short runs (rows NULL: up to 16 cells; a row list: up to 4096 — the runs that ride
  * in the phase's patch launch) are resolved on the host with one zero-skipping batched inversion per column; longer ones are uploaded
  * as pairs and all such columns of one call are resolved by ONE device chain with ONE field inversion (h2mi_fr_assigned_columns_dev;
@@ -139,8 +139,8 @@ typedef struct {
 /* H2MI_CELLS_I64: values holds `count` signed 64-bit two's-complement integers, 8 bytes per cell (read through the pointer as int64_t;
  * 8-byte aligned), for the columns whose cells are small: range-check limbs, lookup advice, multiplicities, selectors, fixed-point
  * values, lookup tables.  The cell's value is v mod r: v for v >= 0, r - |v| for v < 0, -2^63 |-> r - 2^63.  rows means what it means
- * without the flag.  With H2MI_CELLS_CANONICAL or H2MI_CELLS_RATIONAL: H2MI_EINVAL.  Accepted wherever cells enter: every
- * h2mi_prover_keygen* (the fixed column behind a cs->lookups[] table included), h2mi_prover_instances, h2mi_prover_advice,
+ * without the flag.  With H2MI_CELLS_CANONICAL or H2MI_CELLS_RATIONAL: H2MI_EINVAL.  Accepted wherever cells enter: 
+ * h2mi_prover_keygen (the fixed column behind a cs->lookups[] table included), h2mi_prover_instances, h2mi_prover_advice,
  * h2mi_prover_advice_phase, hence batches.  Short runs (rows NULL: up to 16 cells; a row list: up to 4096) are converted on the host and
  * ride in the phase's patch launch like plain cells; longer ones are staged as they are — 8 bytes per cell plus 4 per listed row, where
  * plain scattered cells upload 32 bytes per row of their span — in the library's grow-only scratch (H2MI_ENOMEM where that does not
@@ -151,7 +151,7 @@ typedef struct {
  * torch tensor's data_ptr().  For callers whose witness is in HBM already.  Alone (32-byte Montgomery words, not range-checked, as on
  * the host), with H2MI_CELLS_CANONICAL or with H2MI_CELLS_I64; with H2MI_CELLS_RATIONAL: H2MI_EINVAL.  Accepted by h2mi_prover_advice and
  * h2mi_prover_advice_phase (hence batch members) only: h2mi_prover_instances (the caller hashes public inputs on the host and the library
- * keeps a host copy) and every h2mi_prover_keygen* (a key is made once, and a lookup table is sorted on the host) return H2MI_EINVAL, and
+ * keeps a host copy) and h2mi_prover_keygen (a key is made once, and a lookup table is sorted on the host) return H2MI_EINVAL, and
  * so does every entry after h2mi_init_devices with more than one device.  Pointers: 32-byte values 16-byte aligned, I64 values 8, rows 4
  * (H2MI_EINVAL).  The library reads the memory on its own stream: the caller has ordered its producer before the call, by a host
  * synchronise or by a wait placed on h2mi_library_stream.  The memory is free again when the call returns.  There is no host shortcut,
@@ -169,7 +169,7 @@ typedef struct {
 } h2mi_column_cells;
 /* The rules above, on the host alone (it works without a GPU and reads no cell memory): what every entry point that takes cells applies
  * first.  `where` says which: H2MI_CELLS_FOR_ADVICE (h2mi_prover_advice / _advice_phase), _FOR_INSTANCE (h2mi_prover_instances),
- * _FOR_FIXED (every h2mi_prover_keygen*).  H2MI_EINVAL: cells NULL with n_columns > 0; an unknown `where`; a flag bit beyond the four
+ * _FOR_FIXED (h2mi_prover_keygen).  H2MI_EINVAL: cells NULL with n_columns > 0; an unknown `where`; a flag bit beyond the four
  * above; H2MI_CELLS_I64 with _CANONICAL or _RATIONAL; H2MI_CELLS_DEVICE with _RATIONAL or anywhere but on advice; for instances
  * H2MI_CELLS_RATIONAL or a row list; count > 0 with values NULL; a misaligned pointer — rows 4 bytes, values 8, the 32-byte values of a
  * device column 16.  H2MI_ERANGE: a count above 2^28, more rows than any column has (the usable rows are the entry points' to check). */
@@ -182,6 +182,9 @@ typedef struct h2mi_pk_s* h2mi_pk_t;         /* keygen_pk's ProvingKey, resident
 typedef struct h2mi_prover_s* h2mi_prover_t; /* the buffers, streams and phase state of one create_proof at a time; reused from proof to proof */
 
 /* ---- keygen_vk + keygen_pk (examples/standard_plonk.rs:33-34; src/scaffold.rs:284,287) ----------------------------------------
+ * ONE call, h2mi_prover_keygen, takes ONE record, h2mi_keygen_args (at the end of this section, behind the structs it points to): the
+ * constraint system, what the circuit has beside it — each an optional pointer — and the cells.  The key keeps its own copy of every
+ * program and struct: the caller's memory is free after the call.
  * fixed: cs->n_fixed columns as the circuit's synthesize() (without witnesses) assigns them — selectors included, as the columns keygen
  * appends for them; a lookup's table column is the whole table.  copies: n_copies x 4 uint32 = (left column, left row, right column,
  * right row) per constrain_equal call, in call order, columns as indices into cs->perm_columns (permutation/keygen.rs Assembly::copy;
@@ -195,8 +198,8 @@ typedef struct h2mi_prover_s* h2mi_prover_t; /* the buffers, streams and phase s
  * `mv-lookup` feature of the Scroll and ezkl lines of halo2_proofs) in place of the permuted columns and the grand product.  Like the
  * shuffle it is RESTATED FROM MEMORY: DESIGN.md 4.5 and tests/logup_cases.py are the pin, not a crate.  Selection is per key — all of
  * its lookups or none.  A lookup of the key may hold several input tuples over its one table (h2mi_logup_inputs, below).
- * Accepted by h2mi_prover_keygen_exprs / _phases / _shuffles with lookups != NULL only (H2MI_EINVAL otherwise, and from
- * h2mi_prover_keygen / _keygen_gates always); h2mi_lookup_program, its check, the required degree, blinding_factors and the query lists
+ * With cs->gates == H2MI_GATES_EXPRESSIONS it needs `lookups` (H2MI_EINVAL without); on a hard-wired shape it selects the table logUp
+ * described with h2mi_table_logup_check below.  h2mi_lookup_program, its check, the required degree, blinding_factors and the query lists
  * are what they are without it.  Per lookup, with A and S the two sides compressed with theta and u the usable rows:
  *   M[r] = #{i < u : A[i] = S[r]} on the FIRST usable row r that holds its table value, 0 on every other usable row, blinding scalars
  *          on rows u .. 2^k - 1 (the permuted columns' stream: (blinding_factors + 1) scalars per lookup, in lookup order);
@@ -209,8 +212,9 @@ typedef struct h2mi_prover_s* h2mi_prover_t; /* the buffers, streams and phase s
  * h2mi_prover_check tests membership and does not depend on the argument.  Batches: M and phi per member, one joint quotient. */
 #define H2MI_KEYGEN_LOGUP 2u
 /* H2MI_KEYGEN_BY_COSET: the quotient is evaluated one coset of 2^k points at a time, and no column is kept in extended-coset form
- * (DESIGN.md 3 and 4.5 hold the memory formulas of both layouts).  Accepted by every keygen entry point, alone or with
- * H2MI_KEYGEN_LOGUP; with H2MI_KEYGEN_VK_ONLY it changes nothing.  The key holds its fixed and sigma columns in Lagrange and coefficient
+ * (DESIGN.md 3 and 4.5 hold the memory formulas of both layouts).  Accepted alone or with H2MI_KEYGEN_LOGUP on a lookup
+ * program (with the table logUp of a hard-wired shape: H2MI_EINVAL); with H2MI_KEYGEN_VK_ONLY it changes nothing.  The key holds its
+ * fixed and sigma columns in Lagrange and coefficient
  * form and l_0 / l_last / l_active as coefficients; commitments, tables, moved cells and programs are the resident key's, and so is what
  * h2mi_prover_vk_commitments returns.  A prover on such a key holds no vector of 2^extended_k elements but h: per vector the numerator
  * reads, one slice of 2^k elements (a logUp lookup's input sets: sets 2^k, one slice behind the other), the slices of the key's shared
@@ -220,11 +224,8 @@ typedef struct h2mi_prover_s* h2mi_prover_t; /* the buffers, streams and phase s
  * members (h2mi_plonk_evaluate_h_expr_batch_dev with a slice; a hard-wired shape through its equivalent program, as batches do).  Every phase and every
  * byte of the proof is the resident key's; instance columns always take the coefficient route.  The price is time: the fixed and sigma
  * slices are recomputed in every proof.  h2mi_prover_buffer / _pk_buffer: see the *_COSET kinds below. */
-#define H2MI_KEYGEN_BY_COSET 8u /* bit 4 stays unassigned: every keygen entry refuses it with H2MI_EINVAL, as it always has */
-int h2mi_prover_keygen(const h2mi_constraint_system* cs, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
-                       size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
-/* The same with the gates as a program (cs->gates == H2MI_GATES_EXPRESSIONS; any other value: H2MI_EINVAL, as is that value given to
- * h2mi_prover_keygen).  The key keeps its own copy of the ops and constants: the caller's memory is free after the call.
+#define H2MI_KEYGEN_BY_COSET 8u /* bit 4 stays unassigned: keygen refuses it with H2MI_EINVAL, as it always has */
+/* The gates as a program (`gates`): cs->gates == H2MI_GATES_EXPRESSIONS needs one, every other shape refuses one (H2MI_EINVAL).
  * h2mi_gate_program_check is the validation keygen applies, on the host alone (it works without a GPU): H2MI_EINVAL unless every op is
  * known, every column index is within n_advice / n_fixed / n_instance and every constant index within n_constants, |rotation| < 2^k,
  * the stack never underflows nor exceeds H2MI_MAX_EXPR_STACK and holds exactly one value at each END, the program ends with END and
@@ -243,8 +244,6 @@ int h2mi_gate_program_check(const h2mi_constraint_system* cs, const h2mi_gate_pr
 #define H2MI_SHAPE_PROGRAM_MAX_OPS (10 * H2MI_MAX_GATES)
 int h2mi_shape_gate_program(const h2mi_constraint_system* cs, h2mi_expr_op* ops, uint32_t ops_cap, uint32_t* n_ops_out, uint64_t* constants,
                             uint32_t constants_cap, uint32_t* n_constants_out);
-int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, uint64_t g_lagrange_handle,
-                             const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
 /* Lookups as a program beside the constraint system: `meta.lookup(|meta| vec![(input, table), ..])` with any expressions on both sides,
  * advice in the table (lookup_any) and rotations included.  The argument compresses each side with the challenge theta, A = theta^(m-1)
  * a_0 + .. + a_(m-1) and S likewise (on all 2^k rows, rotations modulo 2^k), permutes and multiplies over the usable rows; transcript
@@ -253,17 +252,13 @@ int h2mi_prover_keygen_gates(const h2mi_constraint_system* cs, const h2mi_gate_p
  * n_pairs >= 1, exprs passes the rules of h2mi_gate_program_check except the degree rule (every advice / fixed query in the query
  * lists), holds exactly 2 * sum n_pairs polynomials, and every lookup's required degree max(4, 2 + max(1, input degrees) + max(1, table
  * degrees)) is at most cs->degree.  degree_out (may be NULL): the largest required degree.
- * h2mi_prover_keygen_exprs: h2mi_prover_keygen_gates with the lookups given this way (lookups == NULL: exactly that call).  Requires
- * cs->gates == H2MI_GATES_EXPRESSIONS; the key copies the program. */
+ * `lookups` requires cs->gates == H2MI_GATES_EXPRESSIONS. */
 typedef struct {
   uint32_t n_lookups;                 /* == cs->n_lookups; cs->lookups[] is then ignored */
   uint32_t n_pairs[H2MI_MAX_LOOKUPS]; /* >= 1 */
   h2mi_gate_program exprs;            /* per lookup: its n_pairs input polynomials, then its n_pairs table polynomials */
 } h2mi_lookup_program;
 int h2mi_lookup_program_check(const h2mi_constraint_system* cs, const h2mi_lookup_program* lookups, uint32_t* degree_out);
-int h2mi_prover_keygen_exprs(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
-                             uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags,
-                             h2mi_pk_t* pk_out);
 /* Advice phases and challenges beside the constraint system: `meta.advice_column_in(SecondPhase)`, `meta.challenge_usable_after(phase)`
  * and Expression::Challenge [RECALL halo2_proofs v2023_02_02 plonk/circuit.rs, plonk/prover.rs — restated from memory like the rest].
  * create_proof commits the advice columns phase by phase and squeezes, after each phase, the challenges usable after it; the next
@@ -274,8 +269,7 @@ int h2mi_prover_keygen_exprs(const h2mi_constraint_system* cs, const h2mi_gate_p
  * (the crate: a column in phase p > 0 needs one in phase p - 1, a challenge after p needs a column in p), n_challenges <=
  * H2MI_MAX_CHALLENGES, and `gates` / `lookups` (may be NULL) pass h2mi_gate_program_check / h2mi_lookup_program_check with CHALLENGE
  * ops of an index below n_challenges allowed — those two functions by themselves know of no challenges and refuse the op.
- * h2mi_prover_keygen_phases: h2mi_prover_keygen_exprs with the phases; the key copies the struct.  With n_phases == 1 and no challenges
- * the key is the one h2mi_prover_keygen_exprs makes. */
+ * With n_phases == 1 and no challenges the key is the one `phases` == NULL makes. */
 typedef struct {
   uint32_t n_phases;                                 /* 1 .. H2MI_MAX_ADVICE_PHASES */
   uint32_t advice_phase[H2MI_MAX_ADVICE];            /* phase of advice column j (cs->n_advice entries) */
@@ -284,9 +278,6 @@ typedef struct {
 } h2mi_advice_phases;
 int h2mi_advice_phases_check(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
                              const h2mi_advice_phases* phases);
-int h2mi_prover_keygen_phases(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
-                              const h2mi_advice_phases* phases, uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies,
-                              size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
 /* Shuffle arguments beside the constraint system: `meta.shuffle(name, |meta| vec![(input, shuffle), ..])` [RECALL halo2_proofs, PSE
  * line, plonk/shuffle.rs, plonk/shuffle/prover.rs, plonk/shuffle/verifier.rs — restated from memory like everything else here, and
  * pinned only to the restatement in DESIGN.md 4.5 and tests/shuffle_cases.py, not to the crate].  Two tuples of expressions take the
@@ -302,8 +293,7 @@ int h2mi_prover_keygen_phases(const h2mi_constraint_system* cs, const h2mi_gate_
  * and every shuffle's required degree is at most cs->degree.  degree_out (may be NULL): the largest required degree.  It knows of no
  * challenges and refuses H2MI_EXPR_CHALLENGE; h2mi_shuffle_phases_check is the same with CHALLENGE ops of an index below
  * phases->n_challenges allowed (phases == NULL: exactly the call above), as h2mi_advice_phases_check is for gates and lookups.
- * h2mi_prover_keygen_shuffles: h2mi_prover_keygen_phases plus the shuffles.  phases == NULL: one phase, no challenges; shuffles == NULL:
- * exactly the key the existing calls make.  Requires cs->gates == H2MI_GATES_EXPRESSIONS; the key copies the program. */
+ * `shuffles` requires cs->gates == H2MI_GATES_EXPRESSIONS. */
 typedef struct {
   uint32_t n_shuffles;                  /* 1 .. H2MI_MAX_SHUFFLES */
   uint32_t n_pairs[H2MI_MAX_SHUFFLES];  /* >= 1 */
@@ -312,9 +302,6 @@ typedef struct {
 int h2mi_shuffle_program_check(const h2mi_constraint_system* cs, const h2mi_shuffle_program* shuffles, uint32_t* degree_out);
 int h2mi_shuffle_phases_check(const h2mi_constraint_system* cs, const h2mi_shuffle_program* shuffles, const h2mi_advice_phases* phases,
                               uint32_t* degree_out);
-int h2mi_prover_keygen_shuffles(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
-                                const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles, uint64_t g_lagrange_handle,
-                                const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
 /* Several input sets over one table in a logUp lookup [the merging of lookups that share a table, restated from memory like the
  * argument itself: DESIGN.md 4.5 and tests/logup_sets_cases.py are the pin, not a crate].  Lookup l has K = n_inputs[l] input tuples A_1
  * .. A_K and one table tuple S, all of n_pairs[l] components; with an h2mi_logup_inputs, lookups->exprs holds per lookup its n_inputs x
@@ -332,18 +319,13 @@ int h2mi_prover_keygen_shuffles(const h2mi_constraint_system* cs, const h2mi_gat
  * h2mi_logup_inputs_check (host only, works without a GPU): the rules of h2mi_lookup_program_check with sum (n_inputs + 1) n_pairs
  * polynomials and the degree rule above; every count in 1 .. H2MI_MAX_LOGUP_INPUTS; CHALLENGE ops of an index below phases->n_challenges
  * allowed (phases == NULL: none).  inputs == NULL: one set per lookup.  degree_out (may be NULL): the largest required degree.
- * h2mi_prover_keygen_logup: h2mi_prover_keygen_shuffles plus `inputs`.  A count above 1 without H2MI_KEYGEN_LOGUP (or without
- * lookups): H2MI_EINVAL.  inputs == NULL or all ones: the key h2mi_prover_keygen_shuffles makes.  The key copies the struct.
+ * Keygen: `inputs` without `lookups`, or a count other than 1 without H2MI_KEYGEN_LOGUP: H2MI_EINVAL.  All ones: the key inputs == NULL makes.
  * h2mi_prover_check tests the membership of every set: a lookup's entry counts the absent (row, set) pairs and names the smallest row. */
 typedef struct {
   uint32_t n_inputs[H2MI_MAX_LOOKUPS]; /* 1 .. H2MI_MAX_LOGUP_INPUTS for the lookups->n_lookups lookups; the rest is not read */
 } h2mi_logup_inputs;
 int h2mi_logup_inputs_check(const h2mi_constraint_system* cs, const h2mi_lookup_program* lookups, const h2mi_logup_inputs* inputs,
                             const h2mi_advice_phases* phases, uint32_t* degree_out);
-int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_program* gates, const h2mi_lookup_program* lookups,
-                             const h2mi_logup_inputs* inputs, const h2mi_advice_phases* phases, const h2mi_shuffle_program* shuffles,
-                             uint64_t g_lagrange_handle, const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags,
-                             h2mi_pk_t* pk_out);
 /* logUp for the single-expression lookups of a HARD-WIRED shape (cs->lookups[], the range checks of H2MI_GATES_FLEX_VERTICAL): the argument
  * stated for h2mi_logup_inputs above — the same M, phi, quotient terms, evaluations, openings, blinding streams and offsets — with every
  * tuple of ONE component, so theta does not enter: A_j is entry j's advice column, or fixed[selector_fixed] * advice, and S is the fixed
@@ -354,7 +336,7 @@ int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_p
  * (h2mi_shape_gate_program), as batches do, with the advice columns' own extended cosets as the inputs.
  * Grouping: sets == NULL makes one argument per entry of cs->lookups; otherwise argument a takes the next sets->n_inputs[a] entries, in
  * order.  h2mi_table_logup_check (host only, works without a GPU) is the validation keygen applies before any device work; H2MI_EINVAL:
- * cs->gates == H2MI_GATES_EXPRESSIONS (such lookups are a program: h2mi_prover_keygen_logup) or unknown; no lookups; a lookup's columns out
+ * cs->gates == H2MI_GATES_EXPRESSIONS (such lookups are a program: `lookups`) or unknown; no lookups; a lookup's columns out
  * of range; a count of 0 or above H2MI_MAX_LOGUP_INPUTS; counts that do not sum to cs->n_lookups (the struct states no length: the counts are read
  * until they reach cs->n_lookups, and an argument that would pass the last entry is the violation); entries of one argument with different
  * table_fixed; cs->degree below an argument's 2 + sum_j deg A_j + 1, deg A_j = 2 with a selector and 1 without; and, for an argument of
@@ -362,9 +344,10 @@ int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_p
  * quotient takes the K inputs as consecutive vectors, which the prover arranges by placing those columns' cosets behind one another.
  * degree_out (may be NULL): the largest required degree.  A permutation chunk of cs->degree - 2 columns may be longer than the three the
  * shape's own kernels take.
- * h2mi_prover_keygen_table_logup: flags H2MI_KEYGEN_VK_ONLY and H2MI_KEYGEN_LOGUP (implied) are accepted; H2MI_KEYGEN_BY_COSET and every
- * other bit are H2MI_EINVAL.  Two arguments over one fixed column share one sorted table in the key.  A proof of this key is byte for
- * byte the proof of the key h2mi_prover_keygen_logup makes from the same circuit written as programs (gates = H2MI_GATES_EXPRESSIONS with
+ * Keygen makes this key for H2MI_KEYGEN_LOGUP on a cs->gates other than H2MI_GATES_EXPRESSIONS, with `inputs` as the grouping (`sets`
+ * here); H2MI_KEYGEN_VK_ONLY is accepted beside it, and H2MI_KEYGEN_BY_COSET or any of `gates`, `lookups`, `phases`, `shuffles` is
+ * H2MI_EINVAL.  Two arguments over one fixed column share one sorted table in the key.  A proof of this key is byte for
+ * byte the proof of the key made from the same circuit written as programs (gates = H2MI_GATES_EXPRESSIONS with
  * h2mi_shape_gate_program's program, one lookup per argument whose input polynomials are the entries' queries and whose table
  * polynomial is the fixed query, the same counts, H2MI_KEYGEN_LOGUP), for the same seed and challenges.  h2mi_prover_lookups returns one
  * [M] per argument and H2MI_EUNSAT for an input of any entry that is no table value; h2mi_prover_get_counts, h2mi_prover_buffer
@@ -373,8 +356,24 @@ int h2mi_prover_keygen_logup(const h2mi_constraint_system* cs, const h2mi_gate_p
  * and 4 per distinct table value, and no compressed vector.  h2mi_prover_pk_export of such a key is H2MI_EINVAL: the blob format has no
  * section for the grouping. */
 int h2mi_table_logup_check(const h2mi_constraint_system* cs, const h2mi_logup_inputs* sets, uint32_t* degree_out);
-int h2mi_prover_keygen_table_logup(const h2mi_constraint_system* cs, const h2mi_logup_inputs* sets_or_null, uint64_t g_lagrange_handle,
-                                   const h2mi_column_cells* fixed, const uint32_t* copies, size_t n_copies, unsigned flags, h2mi_pk_t* pk_out);
+/* The one keygen call.  Refusals, in this order: H2MI_EINVAL for args, pk_out or cs NULL, cs->n_fixed without fixed, n_copies without
+ * copies, a flag bit beyond the three above; then, with *pk_out = NULL, the rules of the table logUp or — on every other record —
+ * H2MI_EINVAL for H2MI_KEYGEN_LOGUP or `inputs` without `lookups` and for a count other than 1 without the flag; h2mi_column_cells_check;
+ * H2MI_ENODEV without a device; the constraint system's and its programs' rules (the *_check functions among them). */
+typedef struct {
+  const h2mi_constraint_system* cs;
+  const h2mi_gate_program* gates;       /* NULL: a hard-wired shape (cs->gates says which) */
+  const h2mi_lookup_program* lookups;   /* NULL: the single-expression lookups cs->lookups[] */
+  const h2mi_logup_inputs* inputs;      /* NULL: one input set per lookup; with the table logUp: one argument per entry of cs->lookups */
+  const h2mi_advice_phases* phases;     /* NULL: one phase, no challenges */
+  const h2mi_shuffle_program* shuffles; /* NULL: no shuffle argument */
+  uint64_t g_lagrange_handle;
+  const h2mi_column_cells* fixed;       /* NULL only with cs->n_fixed == 0 */
+  const uint32_t* copies;               /* NULL only with n_copies == 0 */
+  size_t n_copies;
+  unsigned flags;                       /* H2MI_KEYGEN_* */
+} h2mi_keygen_args;
+int h2mi_prover_keygen(const h2mi_keygen_args* args, h2mi_pk_t* pk_out);
 int h2mi_prover_pk_release(h2mi_pk_t pk); /* H2MI_EINVAL while a prover created against it is alive */
 /* VerifyingKey::{fixed_commitments, permutation.commitments}: affine points (8 limbs each); either pointer may be NULL */
 int h2mi_prover_vk_commitments(h2mi_pk_t pk, uint64_t* fixed_out /* n_fixed x 8 */, uint64_t* permutation_out /* n_perm x 8 */);
@@ -395,7 +394,7 @@ int h2mi_prover_vk_commitments(h2mi_pk_t pk, uint64_t* fixed_out /* n_fixed x 8 
  * h2mi_prover_pk_blob_check: on the host alone (it works without a GPU), every validation import applies before its first device call —
  * the format's (lengths and counts against the blob's length and the ABI limits, rows strictly ascending and usable, moved cells sorted
  * and inside n_perm and the usable rows, no unknown version or flag bit, the checksum) and the constraint system's and its programs'
- * (what every keygen entry applies, the *_check functions among it).  cs_out / user_out / user_len_out (each may be NULL) receive the
+ * (what keygen applies, the *_check functions among it).  cs_out / user_out / user_len_out (each may be NULL) receive the
  * blob's constraint system — fields the shape does not read are zero — and its user section, a pointer into buf.
  * h2mi_prover_pk_import: flags 0 or H2MI_KEYGEN_BY_COSET — the layout in HBM is the importer's choice, whatever the exporter's was;
  * H2MI_KEYGEN_LOGUP is the blob's and not accepted here.  The cells go through the route keygen has (h2mi_column_cells with H2MI_CELLS_I64
@@ -464,7 +463,7 @@ int h2mi_prover_advice(h2mi_prover_t prover, const h2mi_column_cells* advice, co
  * launch for all of them, h2mi_plonk_instance_coset_multi_dev), longer ones are transformed one by one.
  * Batches: every member has its own instance columns; the call goes to the member, like its advice. */
 int h2mi_prover_instances(h2mi_prover_t prover, const h2mi_column_cells* instance /* cs->n_instance entries */);
-/* The same, one advice phase at a time (a key of h2mi_prover_keygen_phases; on a one-phase key phase 0 IS h2mi_prover_advice, and
+/* The same, one advice phase at a time (a key made with `phases`; on a one-phase key phase 0 IS h2mi_prover_advice, and
  * h2mi_prover_advice on a key with more phases is H2MI_EINVAL).  Per phase p = 0 .. n_phases - 1 the caller synthesizes with the
  * challenges known so far, calls this, writes points_out to its transcript and squeezes, in index order, the challenges whose phase
  * is p.  advice: cs->n_advice entries; only the columns of phase p are read, and an entry of another phase's column must have count ==
@@ -511,7 +510,7 @@ int h2mi_prover_set_challenges(h2mi_prover_t prover, const uint64_t* values);
 #define H2MI_CHECK_SHUFFLE 3u
 typedef struct { uint32_t kind /* H2MI_CHECK_* */, index, row, count; } h2mi_check_failure;
 int h2mi_prover_check(h2mi_prover_t prover, const uint64_t theta[4], h2mi_check_failure* out, size_t cap, size_t* n_out);
-/* theta compresses the lookups of a key made by h2mi_prover_keygen_exprs (each side's expressions folded with it on the rows, the
+/* theta compresses the lookups of a key made with a lookup program (each side's expressions folded with it on the rows, the
  * table's usable rows sorted on the device); the single-expression lookups do not use it.
  * points_out: per lookup the permuted input, then the permuted table commitment (2 x n_lookups; nothing without lookups — the call
  * may then be skipped — except on a key with shuffles, whose two sides the products phase compresses with this theta: there the call is

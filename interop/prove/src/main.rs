@@ -81,6 +81,21 @@ struct ColumnCells {
     count: usize,
     flags: u32,
 }
+// h2mi_keygen_args: a pointer left null means what include/h2mi_prover.h says beside the field; this caller's circuit has none of the five
+#[repr(C)]
+struct KeygenArgs {
+    cs: *const ConstraintSystem,
+    gates: *const c_void,
+    lookups: *const c_void,
+    inputs: *const c_void,
+    phases: *const c_void,
+    shuffles: *const c_void,
+    g_lagrange_handle: u64,
+    fixed: *const ColumnCells,
+    copies: *const u32,
+    n_copies: usize,
+    flags: c_uint,
+}
 #[repr(C)]
 #[derive(Default)]
 struct Counts {
@@ -93,8 +108,7 @@ struct Counts {
 extern "C" {
     fn h2mi_init(device: c_int) -> c_int;
     fn h2mi_bases_register(bases: *const u64, n: usize, handle_out: *mut u64) -> c_int;
-    fn h2mi_prover_keygen(cs: *const ConstraintSystem, g_lagrange: u64, fixed: *const ColumnCells, copies: *const u32, n_copies: usize, flags: c_uint,
-                          pk_out: *mut *mut c_void) -> c_int;
+    fn h2mi_prover_keygen(args: *const KeygenArgs, pk_out: *mut *mut c_void) -> c_int;
     fn h2mi_prover_vk_commitments(pk: *mut c_void, fixed_out: *mut u64, permutation_out: *mut u64) -> c_int;
     fn h2mi_prover_create(pk: *mut c_void, g: u64, g_lagrange: u64, lo: usize, count: usize, prover_out: *mut *mut c_void) -> c_int;
     fn h2mi_prover_set_rng_key(prover: *mut c_void, key: *const u8) -> c_int;
@@ -171,7 +185,21 @@ fn main() {
     ];
     let copies: [[u32; 4]; 4] = [[0, 1, 0, 0], [1, 1, 0, 0], [0, 2, 0, 0], [1, 2, 0, 0]];
     let mut pk: *mut c_void = std::ptr::null_mut();
-    check(unsafe { h2mi_prover_keygen(&cs, hgl, fixed.as_ptr(), copies.as_ptr() as *const u32, copies.len(), 0, &mut pk) }, "keygen");
+    let null = std::ptr::null::<c_void>();
+    let keygen_args = KeygenArgs {
+        cs: &cs,
+        gates: null,
+        lookups: null,
+        inputs: null,
+        phases: null,
+        shuffles: null,
+        g_lagrange_handle: hgl,
+        fixed: fixed.as_ptr(),
+        copies: copies.as_ptr() as *const u32,
+        n_copies: copies.len(),
+        flags: 0,
+    };
+    check(unsafe { h2mi_prover_keygen(&keygen_args, &mut pk) }, "keygen");
     // the library's keygen against the crate's: the eight commitments of the verifying key
     let mut fc = [G1Affine::default(); 5];
     let mut pc = [G1Affine::default(); 3];

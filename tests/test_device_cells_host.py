@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import device_cells_cases as D
+import keygen_call
 
 EINVAL, ERANGE = -1, -6
 
@@ -206,7 +207,6 @@ def test_the_entry_points_apply_the_check_before_any_device_work(h2, engine):
     """keygen answers H2MI_EINVAL to cells the check refuses whether or not there is a device: the check comes first"""
     cs = engine.ConstraintSystem.build(5, 3, 5, 0, 3, 5, engine.GATES_STANDARD_PLONK, [], [(engine.ADVICE, 0)], [], [(0, 0)], [(0, 0)])
     fixed = (engine.ColumnCells * 5)()
-    pk = C.c_void_p()
     for flags in (engine.CELLS_DEVICE, engine.CELLS_DEVICE | engine.CELLS_I64, engine.CELLS_I64 | engine.CELLS_CANONICAL, 16):
         fixed[2].flags = flags
-        assert h2.lib.h2mi_prover_keygen(C.byref(cs), 1, fixed, None, 0, 0, C.byref(pk)) == EINVAL and not pk.value
+        assert keygen_call.keygen(cs, g_lagrange=1, fixed=fixed, pk=0) == (EINVAL, None)

@@ -2,7 +2,6 @@
 golden proofs of StandardPlonk, halo2_lib and the multi-column range circuit reproduced with their gates handed over as programs; the
 reference's is_zero and or circuits and a degree-6 circuit through custom.py against the oracle's generic prover and verifier
 (oracle/flex.py takes gates as callables), byte for byte; the ABI's refusals."""
-import ctypes as C
 import json
 import os
 import random
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import custom_gate_cases as cases
+import keygen_call
 from custom_gate_cases import OP_ADD, OP_ADVICE, OP_CONSTANT, OP_END, OP_FIXED, OP_INSTANCE, OP_MUL, OP_NEG, OP_SUB
 from oracle import bn254 as o
 from oracle import flex as FX
@@ -289,7 +289,7 @@ def test_degree_six_circuit_matches_the_oracle(gpu, k):
 
 
 # ---- 5. refusals -------------------------------------------------------------------------------------------------------------------
-def test_keygen_refuses_the_wrong_entry_point_and_bad_programs(gpu):
+def test_keygen_refuses_the_wrong_shape_and_bad_programs(gpu):
     from halo2_scaffold_amd import custom, engine, flex
 
     lib = gpu.lib
@@ -300,13 +300,9 @@ def test_keygen_refuses_the_wrong_entry_point_and_bad_programs(gpu):
     copies = np.array([[1, 0, 0, 1]], dtype=np.uint32)
 
     def keygen_gates(abi_, prog):
-        pk = C.c_void_p(0xDEAD)
-        rc = lib.h2mi_prover_keygen_gates(C.byref(abi_), C.byref(prog) if prog is not None else None, params.g_lagrange_handle, cells, copies.ctypes.data, 1,
-                                          0, C.byref(pk))
-        return rc, pk.value
+        return keygen_call.keygen(abi_, gates=prog, g_lagrange=params.g_lagrange_handle, fixed=cells, copies=copies.ctypes.data, n_copies=1)
 
-    pk = C.c_void_p(0xDEAD)
-    assert lib.h2mi_prover_keygen(C.byref(abi), params.g_lagrange_handle, cells, copies.ctypes.data, 1, 0, C.byref(pk)) == -1 and pk.value is None
+    assert keygen_gates(abi, None) == (-1, None)
     rc, handle = keygen_gates(abi, good)
     assert rc == 0 and handle
     assert lib.h2mi_prover_pk_release(handle) == 0
@@ -316,9 +312,8 @@ def test_keygen_refuses_the_wrong_entry_point_and_bad_programs(gpu):
         assert keygen_gates(abi, prog) == (-1, None)
     fabi = flex.FlexGateCS(lookup=False).abi(5)  # gates == 2
     fcells, fkeep = engine.pack_cells([{}, {}])
-    pk = C.c_void_p(0xDEAD)
     prog = engine.GateProgram.build(cases.vertical_gate_ops([(0, 1)]), [])
-    assert lib.h2mi_prover_keygen_gates(C.byref(fabi), C.byref(prog), params.g_lagrange_handle, fcells, None, 0, 0, C.byref(pk)) == -1 and pk.value is None
+    assert keygen_call.keygen(fabi, gates=prog, g_lagrange=params.g_lagrange_handle, fixed=fcells) == (-1, None)
     # a degree-3 constraint system cannot take a degree-4 polynomial; permutation chunks above three are fine for this shape
     deg4 = engine.GateProgram.build([(OP_ADVICE, 0, 0)] * 4 + [(OP_MUL, 0, 0)] * 3 + [(OP_END, 0, 0)], [])
     assert keygen_gates(abi, deg4) == (-1, None)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import custom_gate_cases as gate_cases
+import keygen_call
 import logup_cases as cases
 import lookup_expr_cases as lookup_cases
 import shuffle_cases
@@ -412,8 +413,8 @@ def test_unsatisfied_lookup_is_refused_and_named(gpu, name):
 
 # ---- 6. the flag -----------------------------------------------------------------------------------------------------------------------
 def test_flag_refusals_and_acceptance(gpu):
-    """the flag with lookups == NULL and on h2mi_prover_keygen / _keygen_gates is H2MI_EINVAL; beside a lookup program every
-    program-taking call accepts it"""
+    """the flag with lookups == NULL is H2MI_EINVAL whatever else the record holds; beside a lookup program it is accepted, with phases
+    and with H2MI_KEYGEN_VK_ONLY too"""
     from halo2_scaffold_amd import custom, engine
     from halo2_scaffold_amd._lib import check, lib
 
@@ -424,22 +425,14 @@ def test_flag_refusals_and_acceptance(gpu):
     cells, keep = engine.pack_cells(list(asg.fixed))
     abi, gates, lks = cs.abi(k), cs.gate_program(), cs.lookup_program()
     ph = engine.AdvicePhases.build([0] * cs.n_advice, [])
-    gl, cp, nc, h = params.g_lagrange_handle, copies.ctypes.data, len(copies), C.c_void_p()
+    common = dict(g_lagrange=params.g_lagrange_handle, fixed=cells, copies=copies.ctypes.data, n_copies=len(copies))
     flag = engine.KEYGEN_LOGUP
-    assert lib.h2mi_prover_keygen(C.byref(abi), gl, cells, cp, nc, flag, C.byref(h)) == -1
-    assert lib.h2mi_prover_keygen_gates(C.byref(abi), C.byref(gates), gl, cells, cp, nc, flag, C.byref(h)) == -1
-    assert lib.h2mi_prover_keygen_exprs(C.byref(abi), C.byref(gates), None, gl, cells, cp, nc, flag, C.byref(h)) == -1
-    assert lib.h2mi_prover_keygen_phases(C.byref(abi), C.byref(gates), None, C.byref(ph), gl, cells, cp, nc, flag, C.byref(h)) == -1
-    assert lib.h2mi_prover_keygen_shuffles(C.byref(abi), C.byref(gates), None, None, None, gl, cells, cp, nc, flag, C.byref(h)) == -1
-    made = []
-    check(lib.h2mi_prover_keygen_exprs(C.byref(abi), C.byref(gates), C.byref(lks), gl, cells, cp, nc, flag, C.byref(h)), "keygen_exprs")
-    made.append(h.value)
-    check(lib.h2mi_prover_keygen_phases(C.byref(abi), C.byref(gates), C.byref(lks), C.byref(ph), gl, cells, cp, nc, flag, C.byref(h)), "keygen_phases")
-    made.append(h.value)
-    check(lib.h2mi_prover_keygen_shuffles(C.byref(abi), C.byref(gates), C.byref(lks), None, None, gl, cells, cp, nc, flag | engine.KEYGEN_VK_ONLY, C.byref(h)),
-          "keygen_shuffles")
-    made.append(h.value)
-    for handle in made:
+    assert keygen_call.keygen(abi, flags=flag, pk=0, **common)[0] == -1
+    assert keygen_call.keygen(abi, gates=gates, flags=flag, pk=0, **common)[0] == -1
+    assert keygen_call.keygen(abi, gates=gates, phases=ph, flags=flag, pk=0, **common)[0] == -1
+    for more in (dict(flags=flag), dict(phases=ph, flags=flag), dict(flags=flag | engine.KEYGEN_VK_ONLY)):
+        rc, handle = keygen_call.keygen(abi, gates=gates, lookups=lks, **more, **common)
+        check(rc, "keygen")
         check(lib.h2mi_prover_pk_release(handle), "pk_release")
     del keep
     params.release()

@@ -3,7 +3,7 @@ tests/logup_sets_cases.py: the multiplicity column of K input columns (h2mi_plon
 (h2mi_plonk_logup_sum_sets_dev) around the ranking kernel's 1024-thread workgroup and the scan tile, K = 2, 3, 6; the quotient kernels
 with the K-input term, recovered from H2MI_BUF_H on every extended-coset point, and the quotient calls with `logup` NULL against all ones word
 for word; proofs of every merged circuit accepted by the generalised verifier and rejected after one-byte flips; proof lengths and the
-merged M column against the unmerged key's; a key of h2mi_prover_keygen_logup with all counts 1 against tests/golden/logup_proofs.json;
+merged M column against the unmerged key's; a key made with an h2mi_logup_inputs of all counts 1 against tests/golden/logup_proofs.json;
 an absent cell of one set in the check and in the lookups phase; the committed golden."""
 import ctypes as C
 import json
@@ -453,8 +453,7 @@ def test_a_batch_of_two(gpu):
 
 
 def test_all_counts_one_reproduces_the_logup_goldens(gpu):
-    """a key made through h2mi_prover_keygen_logup with every count 1 is the key h2mi_prover_keygen_shuffles makes: every byte of
-    tests/golden/logup_proofs.json"""
+    """a key made with `inputs` of every count 1 is the key `inputs` == NULL makes: every byte of tests/golden/logup_proofs.json"""
     g = json.load(open(os.path.join(GOLD, "logup_proofs.json")))
     from halo2_scaffold_amd import custom
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import custom_gate_cases as gate_cases
+import keygen_call
 import lookup_expr_cases as cases
 from custom_gate_cases import OP_ADVICE, OP_END, OP_FIXED
 from oracle import bn254 as o
@@ -423,10 +424,7 @@ def test_keygen_exprs_refusals(gpu):
     copies = np.array([[0, 0, 0, 5]], dtype=np.uint32)
 
     def keygen_exprs(abi_, gates_, lp_):
-        pk = C.c_void_p(0xDEAD)
-        rc = lib.h2mi_prover_keygen_exprs(C.byref(abi_), C.byref(gates_), C.byref(lp_) if lp_ is not None else None, params.g_lagrange_handle, cells,
-                                          copies.ctypes.data, 1, 0, C.byref(pk))
-        return rc, pk.value
+        return keygen_call.keygen(abi_, gates=gates_, lookups=lp_, g_lagrange=params.g_lagrange_handle, fixed=cells, copies=copies.ctypes.data, n_copies=1)
 
     rc, handle = keygen_exprs(abi, gates, lp)
     assert rc == 0 and handle and lib.h2mi_prover_pk_release(handle) == 0
@@ -438,16 +436,13 @@ def test_keygen_exprs_refusals(gpu):
     vertical = flex.FlexGateCS(lookup=True).abi(5)  # gates == H2MI_GATES_FLEX_VERTICAL
     one = engine.LookupProgram.build(*cases.one_pair_ops(vertical), [])
     assert keygen_exprs(vertical, gates, one) == (-1, None)
-    # lookups == NULL is h2mi_prover_keygen_gates, which reads cs->lookups[]: a constraint system without lookups goes through,
-    # and the older entry points behave as before
+    # lookups == NULL reads cs->lookups[]: a constraint system without lookups goes through, and not without its gate program
     plain, pasg = gate_cases.is_zero_circuit(custom, 3)
     pcells, pkeep = engine.pack_cells(pasg.fixed)
     pcopies = np.array([[1, 0, 0, 1]], dtype=np.uint32)
-    for fn, args in ((lib.h2mi_prover_keygen_exprs, (C.byref(plain.gate_program()), None)), (lib.h2mi_prover_keygen_gates, (C.byref(plain.gate_program()),))):
-        pk = C.c_void_p()
-        assert fn(C.byref(plain.abi(5)), *args, params.g_lagrange_handle, pcells, pcopies.ctypes.data, 1, 0, C.byref(pk)) == 0
-        assert lib.h2mi_prover_pk_release(pk.value) == 0
-    pk = C.c_void_p(0xDEAD)
-    assert lib.h2mi_prover_keygen(C.byref(plain.abi(5)), params.g_lagrange_handle, pcells, pcopies.ctypes.data, 1, 0, C.byref(pk)) == -1 and pk.value is None
+    common = dict(g_lagrange=params.g_lagrange_handle, fixed=pcells, copies=pcopies.ctypes.data, n_copies=1)
+    rc, handle = keygen_call.keygen(plain.abi(5), gates=plain.gate_program(), **common)
+    assert rc == 0 and lib.h2mi_prover_pk_release(handle) == 0
+    assert keygen_call.keygen(plain.abi(5), **common) == (-1, None)
     del keep, pkeep
     params.release()

@@ -1,6 +1,6 @@
 """Advice phases and challenges on the device: the interpreter's challenge operand against Python integers through both level-A entry
-points that take challenges; a key of h2mi_prover_keygen_phases with one phase and no challenges giving the bytes of the existing
-route; a two-phase running linear combination and a three-phase circuit with a challenge inside a lookup, proved through custom.py
+points that take challenges; a key made with an h2mi_advice_phases of one phase and no challenges giving the bytes of the key
+without one; a two-phase running linear combination and a three-phase circuit with a challenge inside a lookup, proved through custom.py
 and accepted by the phase-aware verifier of tests/phase_cases.py; the order and argument errors of the new calls."""
 import ctypes as C
 import random
@@ -205,7 +205,7 @@ def test_one_phase_key_gives_the_existing_bytes(gpu, name):
     assert keys.keys.phases is None
     want = custom.create_proof(params, keys, asg, 77)
     keys.release()
-    cs.phases = lambda: engine.AdvicePhases.build([0] * cs.n_advice)  # h2mi_prover_keygen_phases with one phase and no challenges
+    cs.phases = lambda: engine.AdvicePhases.build([0] * cs.n_advice)  # `phases` given, with one phase and no challenges
     phased = custom.Keys(params, cs, asg)
     assert phased.keys.phases is not None and phased.transcript_repr == keys.transcript_repr
     ws = custom.Workspace(params, phased)

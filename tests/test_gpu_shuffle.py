@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import custom_gate_cases as gate_cases
+import keygen_call
 import shuffle_cases as cases
 from lookup_expr_cases import compress
 from oracle import bn254 as o
@@ -366,9 +367,7 @@ def test_products_return_eunsat_and_need_theta(gpu):
 
 
 def test_keygen_without_shuffles_is_the_existing_key(gpu):
-    """h2mi_prover_keygen_shuffles with shuffles == NULL makes the key the existing calls make: the same proof bytes"""
-    import ctypes as C
-
+    """a raw record with shuffles == NULL (and every other optional field NULL) makes the key custom.Keys makes: the same proof bytes"""
     from halo2_scaffold_amd import custom, engine
     from halo2_scaffold_amd._lib import check, lib
 
@@ -379,18 +378,17 @@ def test_keygen_without_shuffles_is_the_existing_key(gpu):
     index = {col: j for j, col in enumerate(cs.perm_columns)}
     copies = np.ascontiguousarray(np.array([(index[(le[0], le[1])], le[2], index[(ri[0], ri[1])], ri[2]) for le, ri in asg.copies], dtype=np.uint32).reshape(-1, 4))
     cells, keep = engine.pack_cells(list(asg.fixed))
-    h = C.c_void_p()
     abi, gates = cs.abi(5), cs.gate_program()
-    check(lib.h2mi_prover_keygen_shuffles(C.byref(abi), C.byref(gates), None, None, None, params.g_lagrange_handle, cells, copies.ctypes.data, len(copies), 0,
-                                          C.byref(h)), "keygen_shuffles")
+    rc, handle = keygen_call.keygen(abi, gates=gates, g_lagrange=params.g_lagrange_handle, fixed=cells, copies=copies.ctypes.data, n_copies=len(copies))
+    check(rc, "keygen")
     old = keys.keys.handle
-    keys.keys.handle = h.value  # the same wrapper over the other key
+    keys.keys.handle = handle  # the same wrapper over the other key
     try:
         assert custom.create_proof(params, keys, asg, 77) == want
     finally:
         for pr in list(keys.keys._provers):
             pr.release()
-        check(lib.h2mi_prover_pk_release(h.value), "pk_release")
+        check(lib.h2mi_prover_pk_release(handle), "pk_release")
         keys.keys.handle = old
     _release(params, keys)
 

@@ -154,7 +154,7 @@ def _circuit(name, x_step=0):
 
 class _Proving:
     """a circuit's table-logUp key (FlexKeys(..., logup=True)), the oracle's verifier keys for the same constraint system at the key's
-    degree, and the pieces of the program-route key h2mi_prover_keygen_logup takes for it"""
+    degree, and the pieces of the program-route key (gates, lookups, inputs) for it"""
 
     def __init__(self, gpu, name, lookup_sets):
         from halo2_scaffold_amd import engine, flex

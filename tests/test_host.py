@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import keygen_call
 from oracle import bn254 as o
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,9 +58,9 @@ def test_prover_abi_refuses_without_gpu(h2):
     cs = keygen.constraint_system(circuits.StandardPlonk, 5)
     cells, keep = engine.pack_cells([{} for _ in range(5)])
     out = C.c_void_p()
-    assert h2.lib.h2mi_prover_keygen(C.byref(cs), 1, cells, None, 0, 0, C.byref(out)) == -2 and not out.value
+    assert keygen_call.keygen(cs, g_lagrange=1, fixed=cells, pk=0) == (-2, None)
     assert h2.lib.h2mi_prover_create(None, 1, 2, 0, 32, C.byref(out)) == -2
-    assert h2.lib.h2mi_prover_keygen(None, 1, cells, None, 0, 0, C.byref(out)) == -1  # argument checks come first
+    assert keygen_call.keygen(None, g_lagrange=1, fixed=cells, pk=0)[0] == -1  # argument checks come first
     bogus = C.c_void_p(0x1234)
     pts = np.zeros((8, 8), dtype=np.uint64)
     one = np.array([1, 0, 0, 0], dtype=np.uint64)
@@ -519,7 +520,7 @@ def test_cpp_host_layout_clean_under_sanitizers(tmp_path, h2):
 def test_rust_mirror_of_the_prover_abi_matches_the_header():
     """interop/prove (Rust, compiled by nobody here) declares h2mi_constraint_system by hand: its array lengths must be the header's
     H2MI_MAX_* (a stale mirror would hand keygen a struct of the wrong size), its field order the header's, and the Python mirror
-    (engine.py) the same numbers."""
+    (engine.py) the same numbers; and h2mi_keygen_args as KeygenArgs, field for field in the header's order."""
     import re
 
     hdr = open(os.path.join(ROOT, "include", "h2mi_prover.h")).read() + open(os.path.join(ROOT, "include", "h2mi.h")).read()
@@ -535,6 +536,11 @@ def test_rust_mirror_of_the_prover_abi_matches_the_header():
     struct_rs = re.search(r"struct ConstraintSystem \{(.*?)\n\}", rs, re.S).group(1)
     fields_rs = re.findall(r"^\s*(\w+):", struct_rs, re.M)
     assert fields_rs == fields_c, (fields_rs, fields_c)
+    # the keygen record: the same fields in the header's order (tests/test_keygen_args_host.py pins the Python mirror to the C layout)
+    args_c = re.search(r"typedef struct \{\s*const h2mi_constraint_system\* cs;.*?\} h2mi_keygen_args;", hdr, re.S).group(0)
+    keygen_c = re.findall(r"^  [\w \*]*?(\w+);", args_c, re.M)
+    keygen_rs = re.findall(r"^\s*(\w+):", re.search(r"struct KeygenArgs \{(.*?)\n\}", rs, re.S).group(1), re.M)
+    assert keygen_rs == keygen_c and len(keygen_c) == 11, (keygen_rs, keygen_c)
     eng = open(os.path.join(ROOT, "halo2-scaffold_amd", "engine.py")).read()
     m = re.search(r"MAX_GATES, MAX_PERM, MAX_LOOKUPS, MAX_QUERIES = (\d+), (\d+), (\d+), (\d+)", eng)
     assert [int(v) for v in m.groups()] == [want["GATES"], want["PERM"], want["LOOKUPS"], want["QUERIES"]]

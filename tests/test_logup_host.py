@@ -2,7 +2,6 @@
 and against tests/shuffle_cases.verify; for every case the restatement's multiplicities sum to the usable rows, its running sum ends
 at zero and the three quotient terms vanish on every row of the domain for random theta, beta; an altered input is reported missing;
 the keygen flag's refusals that need no device; the lookup program check is what it was."""
-import ctypes as C
 import json
 import os
 import random
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 import custom_gate_cases as gate_cases
+import keygen_call
 import logup_cases as cases
 import lookup_expr_cases as lookup_cases
 import phase_cases
@@ -164,10 +164,9 @@ def test_lookup_program_check_is_what_it_was(h2):
 
 
 def test_the_flag_is_refused_without_a_lookup_program(h2):
-    """H2MI_KEYGEN_LOGUP: H2MI_EINVAL from h2mi_prover_keygen and _keygen_gates always, from the program-taking calls with lookups ==
-    NULL; an unknown flag bit everywhere.  All of it is decided on the host, in front of any device work."""
+    """H2MI_KEYGEN_LOGUP: H2MI_EINVAL from h2mi_prover_keygen with lookups == NULL, whatever else the record holds; an unknown flag bit
+    always.  All of it is decided on the host, in front of any device work."""
     from halo2_scaffold_amd import custom, engine
-    from halo2_scaffold_amd._lib import lib
 
     assert engine.KEYGEN_LOGUP == cases.KEYGEN_LOGUP == 2 and engine.KEYGEN_VK_ONLY == 1
     assert isinstance(engine.BUF_LOGUP_M, int) and engine.BUF_LOGUP_PHI == engine.BUF_LOGUP_M + 1 == engine.BUF_SHUFFLE_TABLE + 2
@@ -175,17 +174,15 @@ def test_the_flag_is_refused_without_a_lookup_program(h2):
     abi, gates = cs.abi(5), cs.gate_program()
     cells, keep = engine.pack_cells(list(asg.fixed))
     copies = np.zeros((1, 4), dtype=np.uint32)
-    h = C.c_void_p()
     ph = engine.AdvicePhases.build([0] * cs.n_advice, [])
+    common = dict(fixed=cells, copies=copies.ctypes.data, pk=0)
     for flags in (2, 3, 4):
-        assert lib.h2mi_prover_keygen(C.byref(abi), 0, cells, copies.ctypes.data, 0, flags, C.byref(h)) == EINVAL
-        assert lib.h2mi_prover_keygen_gates(C.byref(abi), C.byref(gates), 0, cells, copies.ctypes.data, 0, flags, C.byref(h)) == EINVAL
-        assert lib.h2mi_prover_keygen_exprs(C.byref(abi), C.byref(gates), None, 0, cells, copies.ctypes.data, 0, flags, C.byref(h)) == EINVAL
-        assert lib.h2mi_prover_keygen_phases(C.byref(abi), C.byref(gates), None, C.byref(ph), 0, cells, copies.ctypes.data, 0, flags, C.byref(h)) == EINVAL
-        assert lib.h2mi_prover_keygen_shuffles(C.byref(abi), C.byref(gates), None, None, None, 0, cells, copies.ctypes.data, 0, flags, C.byref(h)) == EINVAL
+        assert keygen_call.keygen(abi, flags=flags, **common)[0] == EINVAL
+        assert keygen_call.keygen(abi, gates=gates, flags=flags, **common)[0] == EINVAL
+        assert keygen_call.keygen(abi, gates=gates, phases=ph, flags=flags, **common)[0] == EINVAL
     # an unknown bit beside a lookup program
     cs2, asg2, k2 = cases.build(custom, "xor")
     abi2, gates2, lks2 = cs2.abi(k2), cs2.gate_program(), cs2.lookup_program()
     cells2, keep2 = engine.pack_cells(list(asg2.fixed))
-    assert lib.h2mi_prover_keygen_exprs(C.byref(abi2), C.byref(gates2), C.byref(lks2), 0, cells2, copies.ctypes.data, 0, 4 | 2, C.byref(h)) == EINVAL
+    assert keygen_call.keygen(abi2, gates=gates2, lookups=lks2, fixed=cells2, copies=copies.ctypes.data, flags=4 | 2, pk=0)[0] == EINVAL
     del keep, keep2

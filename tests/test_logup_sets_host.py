@@ -3,7 +3,6 @@ of tests/logup_cases.py on one input set; the generalised verifier accepts and r
 tests/golden/logup_proofs.json; for every merged circuit the restatement's sum ends at zero and the three terms vanish on every row;
 h2mi_logup_inputs_check (the polynomial count, the degree rule, the counts, the challenges) and the keygen refusals that need no
 device; ConstraintSystem.merge_lookups (grouping by table, declaration order, chunk sizes at budgets 5 and 9)."""
-import ctypes as C
 import json
 import os
 import random
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import custom_gate_cases as gate_cases
+import keygen_call
 import logup_cases
 import logup_sets_cases as cases
 from lookup_expr_cases import compress
@@ -209,21 +209,18 @@ def test_inputs_check_and_challenges(h2):
 
 
 def test_a_count_without_the_flag_is_refused(h2):
-    """h2mi_prover_keygen_logup: a count above 1 without H2MI_KEYGEN_LOGUP is H2MI_EINVAL, decided in front of any device work; custom.Keys
+    """h2mi_prover_keygen with `inputs`: a count above 1 without H2MI_KEYGEN_LOGUP is H2MI_EINVAL, decided in front of any device work; custom.Keys
     refuses merged lookups with logup=False in words"""
     from halo2_scaffold_amd import custom, engine
-    from halo2_scaffold_amd._lib import lib
 
     cs, asg = cases.range_circuit(custom)
     assert cs.lookup_arguments == [[0, 1, 2]]
     abi, gates, lp, li = cs.abi(5), cs.gate_program(), cs.lookup_program(), cs.logup_inputs()
     cells, keep = engine.pack_cells(list(asg.fixed))
     copies = np.zeros((1, 4), dtype=np.uint32)
-    h = C.c_void_p()
     for flags in (0, engine.KEYGEN_VK_ONLY, 4 | engine.KEYGEN_LOGUP):
-        assert lib.h2mi_prover_keygen_logup(C.byref(abi), C.byref(gates), C.byref(lp), C.byref(li), None, None, 0, cells, copies.ctypes.data, 0, flags,
-                                            C.byref(h)) == EINVAL
-    assert lib.h2mi_prover_keygen_logup(C.byref(abi), C.byref(gates), None, C.byref(li), None, None, 0, cells, copies.ctypes.data, 0, 0, C.byref(h)) == EINVAL
+        assert keygen_call.keygen(abi, gates=gates, lookups=lp, inputs=li, fixed=cells, copies=copies.ctypes.data, flags=flags, pk=0)[0] == EINVAL
+    assert keygen_call.keygen(abi, gates=gates, inputs=li, fixed=cells, copies=copies.ctypes.data, pk=0)[0] == EINVAL
     del keep
 
     class NoParams:

@@ -1,17 +1,17 @@
 """LogUp against a table sorted at keygen, on the host: the Python-integer references of tests/table_logup_cases.py against the argument
 as tests/logup_sets_cases.py states it, every named input of the kernel tests checked to reach what it is named for, and the refusals of
-h2mi_table_logup_check / h2mi_prover_keygen_table_logup, which are decided before any device work (no GPU here)."""
-import ctypes as C
+h2mi_table_logup_check / h2mi_prover_keygen with H2MI_KEYGEN_LOGUP on a hard-wired shape, which are decided before any device work (no GPU here)."""
 import random
 
 import pytest
 
+import keygen_call
 import logup_sets_cases as sets_cases
 import table_logup_cases as cases
 from oracle import bn254 as o
 
 R = o.R
-EINVAL = -1
+EINVAL, ENODEV = -1, -2
 
 
 @pytest.mark.parametrize("kind", cases.KINDS)
@@ -130,13 +130,11 @@ def test_check_refusals(h2):
 def test_keygen_refuses_on_the_host(h2):
     """every violation is H2MI_EINVAL before any device work: there is no device here, and none is asked for"""
     from halo2_scaffold_amd import engine
-    from halo2_scaffold_amd._lib import lib
 
     def keygen(abi, counts, flags):
         cells, keep = engine.pack_cells([{} for _ in range(abi.n_fixed)])
         li = engine.LogupInputs.build(counts) if counts is not None else None
-        pk = C.c_void_p(0xDEAD)
-        rc = lib.h2mi_prover_keygen_table_logup(C.byref(abi), C.byref(li) if li is not None else None, 0, cells, None, 0, flags, C.byref(pk))
+        rc, _ = keygen_call.keygen(abi, inputs=li, fixed=cells, flags=flags | engine.KEYGEN_LOGUP)
         del keep
         return rc
 
@@ -156,11 +154,13 @@ def test_keygen_refuses_on_the_host(h2):
     engine, none = _abi(h2, degree=9)
     none.n_lookups = 0
     assert keygen(none, None, 0) == EINVAL
-    # the existing entry keeps refusing the flag
+    # the flag is what selects the argument: a grouping without it is refused, the same record with it passes every host rule (and finds
+    # no device here)
     cells, keep = engine.pack_cells([{} for _ in range(abi.n_fixed)])
-    pk = C.c_void_p()
-    assert lib.h2mi_prover_keygen(C.byref(abi), 0, cells, None, 0, engine.KEYGEN_LOGUP, C.byref(pk)) == EINVAL
-    assert lib.h2mi_prover_keygen(C.byref(abi), 0, cells, None, 0, 4, C.byref(pk)) == EINVAL
+    li = engine.LogupInputs.build([2, 2])
+    assert keygen_call.keygen(abi, inputs=li, fixed=cells) == (EINVAL, None)
+    assert keygen_call.keygen(abi, inputs=li, fixed=cells, flags=engine.KEYGEN_LOGUP) == (ENODEV, None)
+    assert keygen_call.keygen(abi, fixed=cells, flags=4, pk=0)[0] == EINVAL
     del keep
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the table-logUp mode (flex.FlexKeys(..., logup=True), h2mi_prover_keygen_table_logup) costs against the permuted argument on the
+"""What the table-logUp mode (flex.FlexKeys(..., logup=True): H2MI_KEYGEN_LOGUP on the hard-wired shape) costs against the permuted argument on the
 Range builder's circuits, every ratio inside ONE run (the method of the other tools here: resident workspaces, a warm-up round, then
 --proofs alternating rounds, host-inclusive wall clock of create_proof, median (min .. max) in ms):
 
