@@ -15,7 +15,8 @@
 // The columns of a program lie behind one another in one buffer, so the gather needs no search for its column: placed cell e of the
 // concatenated placement lands at word e.  The arithmetic is the fp.cuh layer's: canonical -> Montgomery is the product with R^2,
 // Montgomery -> canonical the product with 1.
-// Hint ops (DIVQ, DIVR, ISZERO, INV: the values halo2-base computes outside the gates — quotients, remainders, is-zero flags, inverses)
+// Hint ops (DIVQ, DIVR, ISZERO, INV, MSB, POW2: the values halo2-base computes outside the gates — quotients, remainders, is-zero flags,
+// inverses, the index of a value's highest set bit and a power of two chosen by a cell)
 // live in a second instantiation of the two level kernels, k_witness_level_hints / k_witness_levels_wg_hints, launched for the programs
 // that hold one; a program without them runs the kernels it always ran.  Division is restoring long division on the canonical words,
 // one quotient bit per round: dividend and remainder shift left as one 512-bit register (16 shifts), the divisor is subtracted with
@@ -23,7 +24,9 @@
 // instructions a round, 256 rounds, ~9 k instructions per op, beside one product out of Montgomery form per cell operand and one back
 // in.  Nothing cleverer is needed for a value computed once per lane: the inversion beside it (fe_inv_ds, ~15 k instructions, out of
 // line as everywhere it is used) costs more.  A signed dividend (above 2^252: the fixed-point chip's negative numbers) is divided as
-// its magnitude r - x and the quotient rounded toward minus infinity afterwards.
+// its magnitude r - x and the quotient rounded toward minus infinity afterwards.  MSB is a count of leading zeros on the highest nonzero
+// canonical word; POW2 builds its one-bit word with a select per word, as LIMB picks its words (an indexed register array would go to
+// scratch): both are a product out of Montgomery form, a dozen instructions and a product back in.
 #include <algorithm>
 #include <memory>
 #include <set>
@@ -36,7 +39,9 @@ namespace h2 {
 
 constexpr uint32_t WP_INPUT = 0, WP_CONST = 1, WP_COPY = 2, WP_GATE = 3, WP_LIMB = 4;  // H2MI_WITNESS_*
 constexpr uint32_t WP_DIVQ = 8, WP_DIVR = 9, WP_ISZERO = 10, WP_INV = 11;  // the hint ops; 5 .. 7 stay unassigned
+constexpr uint32_t WP_MSB = 13, WP_POW2 = 14;                              // 12 is reserved
 constexpr uint32_t WP_DIV_CONST = 1, WP_DIV_SIGNED = 2;                     // H2MI_WITNESS_DIV_*: the flags of DIVQ / DIVR, in the bits byte
+constexpr uint32_t WP_POW2_OF_MSB = 1;                                      // H2MI_WITNESS_POW2_OF_MSB: the flag of POW2, in the bits byte
 constexpr uint32_t WP_BLOCK = 256;
 constexpr uint32_t WP_WG = 1024;         // H2MI_WITNESS_WG_OPS: the workgroup limit
 constexpr uint32_t WP_WG_LEVELS = 4096;  // H2MI_WITNESS_WG_LEVELS
@@ -86,6 +91,34 @@ __device__ __forceinline__ fe witness_div(fe x, const fe& y, bool want_q, bool i
   return fe_select(fe_is_zero(y), zero, r);
 }
 
+// the index of the highest set bit of a canonical word, 0 .. 253; 1 for zero (MSB of include/h2mi.h)
+__device__ __forceinline__ uint32_t msb_256(const fe& x) {
+  uint32_t idx = 1;
+#pragma unroll
+  for (uint32_t i = 0; i < 8; i++)  // the highest nonzero word is the last to write
+    if (x.v[i]) idx = 32 * i + 31 - (uint32_t)__clz((int)x.v[i]);
+  return idx;
+}
+
+// MSB / POW2 of include/h2mi.h on the canonical word -> the canonical result
+__device__ __forceinline__ fe witness_bit(const fe& x, bool want_pow2, bool of_msb) {
+  uint32_t high = 0;
+#pragma unroll
+  for (int i = 1; i < 8; i++) high |= x.v[i];
+  const uint32_t msb = msb_256(x);
+  const uint32_t e = of_msb ? msb : x.v[0];
+  const bool in_table = of_msb || (high == 0 && e <= 253);  // 2^253 < r < 2^254
+  fe r = fe_zero();
+  if (!want_pow2) {
+    r.v[0] = msb;
+    return r;
+  }
+  const uint32_t w = e >> 5, bit = in_table ? 1u << (e & 31u) : 0u;
+#pragma unroll
+  for (uint32_t i = 0; i < 8; i++) r.v[i] = i == w ? bit : 0u;  // selects, not an indexed register array
+  return r;
+}
+
 // the hint ops: the values a builder computes outside the gates (include/h2mi.h)
 __device__ __forceinline__ void witness_hint(const uint4 op, uint32_t kind, fe* cells, const fe* consts) {
   const fe x = fe_load(cells + op.z);
@@ -94,6 +127,8 @@ __device__ __forceinline__ void witness_hint(const uint4 op, uint32_t kind, fe* 
     r = fe_is_zero(x) ? fe_one<Fr>() : fe_zero();  // reduced: zero is the zero word
   } else if (kind == WP_INV) {
     r = fe_is_zero(x) ? fe_one<Fr>() : fe_inv_ds<Fr>(x);
+  } else if (kind >= WP_MSB) {
+    r = fe_to_mont<Fr>(witness_bit(fe_from_mont<Fr>(x), kind == WP_POW2, ((op.y >> 8) & WP_POW2_OF_MSB) != 0));
   } else {
     const uint32_t flags = (op.y >> 8) & 0xffu;
     const fe y = (flags & WP_DIV_CONST) ? fe_load(consts + op.w) : fe_from_mont<Fr>(fe_load(cells + op.w));  // the constants are canonical
@@ -266,7 +301,11 @@ static int witness_check(const h2mi_witness_desc* d) {
         break;
       case WP_ISZERO:
       case WP_INV:
+      case WP_MSB:
         if (bits || shift || op.b || op.a >= n || level_of[op.a] >= level) return H2MI_EINVAL;
+        break;
+      case WP_POW2:  // bits: the flag
+        if ((bits & ~WP_POW2_OF_MSB) || shift || op.b || op.a >= n || level_of[op.a] >= level) return H2MI_EINVAL;
         break;
       case WP_GATE:
         if (op.dst < 3) return H2MI_EINVAL;

@@ -35,19 +35,31 @@ _KIND = {ADVICE: engine.ADVICE, FIXED: engine.FIXED, INSTANCE: engine.INSTANCE}
 
 # the hints: values halo2-base computes outside the gates and assigns as witnesses (H2MI_WITNESS_DIVQ .. INV of include/h2mi.h)
 DIVQ, DIVR, ISZERO, INV = 8, 9, 10, 11
+MSB, POW2 = 13, 14  # H2MI_WITNESS_MSB, H2MI_WITNESS_POW2; 12 is reserved
 HINT_CONST, HINT_SIGNED = 1, 2  # DIVQ / DIVR: the divisor is a constant, not a cell; the dividend is signed (above 2^252: x - r)
+HINT_OF_MSB = 1  # POW2: of the index of the operand's highest set bit (H2MI_WITNESS_POW2_OF_MSB)
+NUM_BITS = 254  # F::NUM_BITS: the length of pow_of_two
 
 
 def hint(kind: int, x: int, y: int = 0, flags: int = 0) -> int:
-    """THE definition of the four hints, on canonical integers below r: what flex.Context assigns, what witness.Program.cells replays
+    """THE definition of the hints, on canonical integers below r: what flex.Context assigns, what witness.Program.cells replays
     and what the device kernels are tested against.  DIVQ / DIVR: quotient and remainder of x by y, 0 for y = 0; signed, a dividend
     above 2^252 is x - r, the quotient rounds toward minus infinity and is stored mod r, the remainder is in [0, y) (the reference's
     signed_div_scale: src/gadget/fixed_point.rs:991-1001).  ISZERO: 1 for 0, else 0.  INV: x^-1 mod r, and 1 for 0 (halo2-base's
-    is_zero assigns Assigned::Trivial(1) there [RECALL])."""
+    is_zero assigns Assigned::Trivial(1) there [RECALL]).  MSB: the index of the highest set bit, and 1 for 0 (the fold over the bits in the
+    reference's qlog2: src/gadget/fixed_point.rs:725-737).  POW2: 2^x for x <= 253 and 0 beyond (the reference indexes pow_of_two and
+    would panic there: 0 satisfies no check_power_of_two); HINT_OF_MSB: 2^MSB(x)."""
     if kind == ISZERO:
         return int(x == 0)
     if kind == INV:
         return pow(x, -1, R) if x else 1
+    if kind == MSB:
+        assert not flags
+        return x.bit_length() - 1 if x else 1
+    if kind == POW2:
+        assert not flags & ~HINT_OF_MSB
+        e = hint(MSB, x) if flags & HINT_OF_MSB else x
+        return 1 << e if e < NUM_BITS else 0
     assert kind in (DIVQ, DIVR) and not flags & ~(HINT_CONST | HINT_SIGNED)
     if y == 0:
         return 0
@@ -213,8 +225,9 @@ class Context:
 
     def assign_region_last(self, items, gate_offsets) -> int:
         """items: ("existing", cell) | ("constant", value) | ("witness", value), and for the values halo2-base computes outside the
-        gates: ("hint", (kind, a, b, flags)) — hint() of cell a and of cell b or, HINT_CONST, the constant b —, ("aux", Aux) — a
-        derived value — and ("copy", cell) — a cell's value again, the equality left to assign_region_smart"""
+        gates: ("hint", (kind, a, b, flags)) — hint() of cell a (or of a Constant a, with no cell beside it: a value known with the
+        circuit) and of cell b or, HINT_CONST, the constant b —, ("limb", (cell, bits, shift)) — bits of a cell's canonical value —,
+        ("aux", Aux) — a derived value — and ("copy", cell) — a cell's value again, the equality left to assign_region_smart"""
         base = len(self.cells)
         for kind, v in items:
             row = len(self.cells)
@@ -222,8 +235,10 @@ class Context:
                 self.cells.append(self.cells[v])
                 self.eqs.append((row, v))
             elif kind == "hint":
-                assert not isinstance(v[1], (Constant, Aux)), "a hint reads a cell: load_constant first"
+                assert not isinstance(v[1], Aux), "a hint reads a cell or a Constant"
                 self.cells.append(self.hint_value(*v))
+            elif kind == "limb":
+                self.cells.append((self.cells[v[0]] >> v[2]) & ((1 << v[1]) - 1))
             elif kind == "aux":
                 self.cells.append(v.value)
             elif kind == "copy":
@@ -244,7 +259,8 @@ class Context:
         return last
 
     def hint_value(self, kind, a, b, flags) -> int:
-        return hint(kind, self.cells[a], b % R if flags & HINT_CONST else self.cells[b], flags)
+        unary = kind not in (DIVQ, DIVR)
+        return hint(kind, int(a) % R if isinstance(a, Constant) else self.cells[a], 0 if unary else b % R if flags & HINT_CONST else self.cells[b], flags)
 
     # operands: a cell (a plain integer: its index), a Constant or an Aux
     def _v(self, q) -> int:
@@ -344,6 +360,65 @@ class Context:
     def mul_add_constant(self, a, b, c):
         return self.assign_region_last([("constant", c), ("existing", a), ("existing", b), ("witness", self.cells[a] * self.cells[b] + c)], [0])
 
+    @staticmethod
+    def pow_of_two() -> list:
+        """the constants 2^0 .. 2^253"""
+        return [Constant(1 << i) for i in range(NUM_BITS)]
+
+    def inner_product(self, a, b):
+        """| 0 | a0 | b0 | s0 | a1 | b1 | s1 | ...: a gate every third cell -> the last sum.  A b that starts with Constant(1) gives
+        | a0 | a1 | b1 | s1 | ... instead: a0 is the first accumulator"""
+        a, b = list(a), list(b)
+        assert len(a) == len(b) and a
+        if isinstance(b[0], Constant) and int(b[0]) % R == 1:
+            acc, items = self._v(a[0]), [self._i(a[0])]
+            a, b = a[1:], b[1:]
+        else:
+            acc, items = 0, [("constant", 0)]
+        for x, y in zip(a, b):
+            acc += self._v(x) * self._v(y)
+            items += [self._i(x), self._i(y), ("witness", acc)]
+        return self.assign_region_last(items, [3 * i for i in range(len(a))])
+
+    def num_to_bits(self, a, range_bits: int) -> list:
+        """the low range_bits bits of cell a, lowest first, as inner_product of the bits with pow_of_two lays them out:
+        | bit0 | bit1 | 2 | acc1 | bit2 | 4 | acc2 | ..., the last sum constrained equal to a — a value beyond range_bits bits satisfies
+        no such sum —, then assert_bit of every bit in order"""
+        assert 1 <= range_bits <= NUM_BITS
+        x, base = self.cells[a], len(self.cells)
+        items = [("limb", (a, 1, 0))]
+        for i in range(1, range_bits):
+            items += [("limb", (a, 1, i)), ("constant", 1 << i), ("witness", x & ((2 << i) - 1))]
+        acc = self.assign_region_last(items, [3 * i for i in range(range_bits - 1)])
+        self.eqs.append((a, acc))
+        bits = [base] + [base + 1 + 3 * (i - 1) for i in range(1, range_bits)]
+        for bit in bits:
+            self.assert_bit(bit)
+        return bits
+
+    def idx_to_indicator(self, idx, length: int) -> list:
+        """[idx == 0, idx == 1, ..]: the first entry is is_zero unrolled — | is_zero | idx | inv | 1 | 0 | idx | is_zero | 0 |, cells
+        0 = 6 and 1 = 5 —, the others is_equal(the sixth cell of that region, Constant(i)).  An index of `length` or more gives zeros only"""
+        base = len(self.cells)
+        self.assign_region_smart([("hint", (ISZERO, idx, 0, 0)), ("existing", idx), ("hint", (INV, idx, 0, 0)), ("constant", 1), ("constant", 0),
+                                  ("existing", idx), ("copy", base), ("constant", 0)], [0, 4], [(0, 6), (1, 5)])
+        return [base + 6] + [self.is_equal(base + 5, Constant(i)) for i in range(1, length)]
+
+    def select_by_indicator(self, a, indicator):
+        """| 0 | a0 | ind0 | s0 | a1 | ind1 | s1 | ...: a gate every third cell -> the last sum, the a whose indicator is 1"""
+        a, indicator = list(a), list(indicator)
+        assert len(a) == len(indicator) and a
+        acc, items = 0, [("constant", 0)]
+        for x, ind in zip(a, indicator):
+            acc += self._v(x) * self.cells[ind]
+            items += [self._i(x), ("existing", ind), ("witness", acc)]
+        return self.assign_region_last(items, [3 * i for i in range(len(a))])
+
+    def select_from_idx(self, cells, idx):
+        """cells[idx] of operands `cells` by a cell idx; 0 for an index beyond them"""
+        cells = list(cells)
+        return self.select_by_indicator(cells, self.idx_to_indicator(idx, len(cells)))
+
     # RangeInstructions::range_check(a, range_bits)
     def range_check(self, a, range_bits: int, lookup_bits: int):
         x = self.cells[a]
@@ -399,15 +474,17 @@ class Context:
     def div_mod(self, a, b: int, a_num_bits: int):
         """(a div b, a mod b) for a cell a below 2^a_num_bits and an integer b: | rem | b | div | a |, then div < 2^a_num_bits / b + 1 and
         rem < b"""
-        last = self.assign_region_last([("hint", (DIVR, a, b, HINT_CONST)), ("constant", b), ("hint", (DIVQ, a, b, HINT_CONST)), ("existing", a)], [0])
+        last = self.assign_region_last([("hint", (DIVR, a, b, HINT_CONST)), ("constant", b), ("hint", (DIVQ, a, b, HINT_CONST)), self._i(a)], [0])
         rem, div = last - 3, last - 1
         self.check_big_less_than_safe(div, (1 << a_num_bits) // b + 1)
         self.check_big_less_than_safe(rem, b)
         return div, rem
 
     def div_mod_var(self, a, b, a_num_bits: int, b_num_bits: int):
-        """the same by a cell b below 2^b_num_bits: div is range-checked to a_num_bits bits, rem < b.  b = 0 satisfies nothing"""
-        last = self.assign_region_last([("hint", (DIVR, a, b, 0)), ("existing", b), ("hint", (DIVQ, a, b, 0)), ("existing", a)], [0])
+        """the same by a cell b below 2^b_num_bits (or a Constant b: the hints then take it as their constant divisor): div is
+        range-checked to a_num_bits bits, rem < b.  b = 0 satisfies nothing"""
+        by = (int(b) % R, HINT_CONST) if isinstance(b, Constant) else (b, 0)
+        last = self.assign_region_last([("hint", (DIVR, a) + by), self._i(b), ("hint", (DIVQ, a) + by), self._i(a)], [0])
         rem, div = last - 3, last - 1
         self.range_check(div, a_num_bits, self.lookup_bits)
         self.check_less_than(rem, b, b_num_bits)

@@ -3,7 +3,7 @@
 `scaffold.prove_private` refuses a closure whose shape depends on its inputs (the break-point check), so under that rule a closure
 `f(ctx, inputs, make_public)` is a fixed straight-line program over field elements in which only the private inputs change from proof
 to proof.  `Program.record` runs the closure once in a `RecordingContext` — `flex.Context` with an op noted per cell — and keeps the
-tape: one op per cell of `Context.cells` (INPUT, CONST, COPY, GATE, LIMB and the hints DIVQ, DIVR, ISZERO, INV: include/h2mi.h), sorted
+tape: one op per cell of `Context.cells` (INPUT, CONST, COPY, GATE, LIMB and the hints DIVQ, DIVR, ISZERO, INV, MSB, POW2: include/h2mi.h), sorted
 into levels; behind them the auxiliary cells no column places — a value derived outside the gates (the a - b of `sub`) is the GATE of three
 such cells, and an enabled gate whose fourth cell is not a GATE op is computed once more among them; the equalities no COPY makes true
 (the checks), the auxiliary gates against their fourth cells among them; per advice column the flat cell index of every row (the placement, exactly what `finish` / `_finish_multi`
@@ -20,7 +20,7 @@ from . import field as F
 
 R = F.FR_MODULUS
 INPUT, CONST, COPY, GATE, LIMB = range(5)  # H2MI_WITNESS_*
-HINTS = (flex.DIVQ, flex.DIVR, flex.ISZERO, flex.INV)
+HINTS = (flex.DIVQ, flex.DIVR, flex.ISZERO, flex.INV, flex.MSB, flex.POW2)
 WG_OPS, WG_LEVELS = 1024, 4096  # H2MI_WITNESS_WG_OPS, H2MI_WITNESS_WG_LEVELS
 
 
@@ -114,8 +114,17 @@ class RecordingContext(flex.Context):
                 vals.append(v % R)
             elif kind == "hint":
                 hint_kind, a, b, flags = v
-                ops.append((hint_kind, a, flags, 0, self._constant(b % R) if flags & flex.HINT_CONST else b))
+                unary = hint_kind not in (flex.DIVQ, flex.DIVR)
+                if isinstance(a, flex.Constant):  # known with the circuit: a CONST op, and no fixed cell beside it
+                    if not unary and not flags & flex.HINT_CONST:
+                        raise ValueError(f"cell {row}: a hint that divides a constant by a cell is not an op of the tape: load_constant the dividend")
+                    ops.append((CONST, self._constant(self.hint_value(*v)), 0, 0))
+                else:
+                    ops.append((hint_kind, a, flags, 0, 0 if unary else self._constant(b % R) if flags & flex.HINT_CONST else b))
                 vals.append(self.hint_value(*v))
+            elif kind == "limb":
+                ops.append((LIMB, v[0], v[1], v[2]))
+                vals.append((self.cells[v[0]] >> v[2]) & ((1 << v[1]) - 1))
             elif kind == "aux":
                 ops.append((COPY, v.ref, 0, 0))
                 vals.append(v.value)

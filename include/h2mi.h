@@ -391,7 +391,12 @@ int h2mi_fr_compact_cells_dev(h2mi_cells_compacted* cols, uint32_t n_cols, unsig
  *                       modulo r, rem = x~ - y q in [0, y).  y = 0 gives 0 for both.  shift = 0; any other flag bit is refused.
  *   H2MI_WITNESS_ISZERO cells[dst] = 1 if x = 0, else 0.                        No flags, shift = 0, b = 0.
  *   H2MI_WITNESS_INV    cells[dst] = x^-1 mod r, and 1 for x = 0 (what halo2-base's is_zero assigns there).  No flags, shift = 0, b = 0.
- * Kinds 5 .. 7 are unassigned and refused, as is every kind above H2MI_WITNESS_INV.  A program that holds a hint op runs its levels in
+ *   H2MI_WITNESS_MSB    cells[dst] = the index of the highest set bit of x, 0 .. 253; x = 0 gives 1 (what the fold over the bits in the
+ *                       reference's qlog2 yields there).  No flags, shift = 0, b = 0.
+ *   H2MI_WITNESS_POW2   cells[dst] = 2^x for x <= 253, and 0 for every larger x up to r - 1.  One flag in the bits byte,
+ *                       H2MI_WITNESS_POW2_OF_MSB: cells[dst] = 2^MSB(x) — so that a power of two can be assigned before its exponent,
+ *                       from the same cell.  shift = 0, b = 0; any other flag bit is refused.
+ * Kinds 5 .. 7 are unassigned and refused, kind 12 is reserved and refused, as is every kind above H2MI_WITNESS_POW2.  A program that holds a hint op runs its levels in
  * a second instantiation of the two level kernels, k_witness_level_hints / k_witness_levels_wg_hints, under the same launch rule; a
  * program without one launches what it always launched.
  * Cells that no column places are allowed: a recorder uses them for values derived outside the columns and for gates it evaluates once
@@ -407,7 +412,7 @@ int h2mi_fr_compact_cells_dev(h2mi_cells_compacted* cols, uint32_t n_cols, unsig
  * evaluates the checks.
  * h2mi_witness_check (host only, works without a GPU; h2mi_witness_create applies it first): H2MI_EINVAL for an unknown kind, a dst
  * named twice or never, an operand whose level is not strictly below its reader's, level_ends that do not ascend to n_ops, a GATE with
- * dst < 3, shift / bits outside their bounds, an unknown flag or a shift on a hint, flags or b on ISZERO / INV, an INPUT or CONST index
+ * dst < 3, shift / bits outside their bounds, an unknown flag or a shift on a hint, flags or b on ISZERO / INV / MSB, b on POW2, an INPUT or CONST index
  * (DIVQ / DIVR with H2MI_WITNESS_DIV_CONST: b) out of range, a constant not below r, a placement source or a
  * check index >= n_ops, a null array with a nonzero count; H2MI_ERANGE for more than 2^28 cells, more than 2^28 cells in one column or
  * more than H2MI_WITNESS_MAX_COLUMNS columns.
@@ -428,6 +433,9 @@ int h2mi_fr_compact_cells_dev(h2mi_cells_compacted* cols, uint32_t n_cols, unsig
 #define H2MI_WITNESS_DIVR 9u
 #define H2MI_WITNESS_ISZERO 10u
 #define H2MI_WITNESS_INV 11u
+#define H2MI_WITNESS_MSB 13u /* 12 is reserved */
+#define H2MI_WITNESS_POW2 14u
+#define H2MI_WITNESS_POW2_OF_MSB 1u /* flag of POW2, in the bits byte */
 #define H2MI_WITNESS_DIV_CONST 1u  /* flags of DIVQ / DIVR, in the bits byte */
 #define H2MI_WITNESS_DIV_SIGNED 2u
 #define H2MI_WITNESS_WG_OPS 1024u    /* the workgroup limit */
