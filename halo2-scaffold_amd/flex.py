@@ -341,6 +341,17 @@ class Context:
             self._zero = self.load_constant(0)
         return self._zero
 
+    def constrain_equal(self, a, b):
+        """no cell: cells a and b join one another"""
+        self.eqs.append((a, b))
+
+    def load_copy(self, cell) -> int:
+        """| cell's value |, constrained equal to the cell: load_witness(*cell.value()) and constrain_equal(new, cell), for a value read
+        back from a cell — which is no input, so a recorder would not know where a plain load_witness of it came from"""
+        new = self.assign_region_last([("copy", cell)], [])
+        self.constrain_equal(new, cell)
+        return new
+
     def sum(self, a):
         """| a0 | a1 | 1 | a0 + a1 | a2 | 1 | a0 + a1 + a2 | ...: a gate every third cell; one operand: its cell again; none: load_zero"""
         a = list(a)
@@ -470,6 +481,13 @@ class Context:
         padded = -(-num_bits // self.lookup_bits) * self.lookup_bits
         self.range_check(self._shifted(a, b, padded), padded + self.lookup_bits, self.lookup_bits)
         return self.is_zero(self.lookup_cells[-1])
+
+    def is_less_than_safe(self, a, b: int) -> int:
+        """the bit a < b for a cell a and an integer b: range_check to b's bit length rounded up to whole limbs, then is_less_than
+        against the constant"""
+        range_bits = -(-b.bit_length() // self.lookup_bits) * self.lookup_bits
+        self.range_check(a, range_bits, self.lookup_bits)
+        return self.is_less_than(a, Constant(b), range_bits)
 
     def div_mod(self, a, b: int, a_num_bits: int):
         """(a div b, a mod b) for a cell a below 2^a_num_bits and an integer b: | rem | b | div | a |, then div < 2^a_num_bits / b + 1 and
